@@ -13,6 +13,9 @@ for N > 1, the RCCL all-gather that reassembles the masks.  Patches shard across
 Prints ONE JSON line on rank 0 (contract in the task description), including
   roofline     -- live HIP-event measurement of the dominant kernel over the timed region
   cpu_baseline -- the CPU oracle (plain-torch fp32 restatement, oracle/) timed on the host cores (rank 0, N=1 only)
+
+--dump-outputs DIR writes the outputs of the last timed step as DIR/<name>.npy (float32; seeded, fixed inputs: two builds run with the
+same arguments compare output for output).
 """
 from __future__ import annotations
 
@@ -52,7 +55,12 @@ def parse():
     ap.add_argument("--launch-check", action="store_true", help="rendezvous only (gloo, no GPU): every rank joins, all-reduces its rank and rank 0 prints\n                    {launch_check, n_gpus}; covers the self-launch / env contract on a CPU box")
     ap.add_argument("--no-pipeline", action="store_true", help="one batch in flight: every step joins its own decodes before the next one is enqueued")
     ap.add_argument("--tiny", action="store_true", help="reduced-width graph + 64x64 patches (plumbing check only; not a valid bench line)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step returned (masks, and the latents,\n"
+                    "                    features and rgb of rank 0's patches) as DIR/<name>.npy in float32; see dump_outputs()")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def usable_cpus() -> int:
@@ -124,6 +132,31 @@ def cpu_baseline(ucfg, vcfg, usd, vsd, img, n_passes):
             "sample": f"1 patch {img}x{img} through the whole {n_passes}-pass sampler (oracle.pipeline.sample_v6), timed end to end once "
                       f"({per_patch:.1f} s) after a 64x64 warm-up; plain-torch fp32 restatement (oracle/), torch {torch.__version__}, "
                       f"{threads} threads -- not diffusers"}
+
+
+DUMP_MAX_ELEMS = 1 << 22   # per array: 4 Mi float32 = 16 MB, so the four outputs stay under 64 MB
+DUMP_SEED = 1237
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32 (uint8 values are exact).  An array of at most DUMP_MAX_ELEMS elements is
+    written whole in its own shape; a larger one as the 1-D sample of DUMP_MAX_ELEMS elements at sorted flat indices drawn without
+    replacement by numpy's default_rng(DUMP_SEED) -- the same indices in every run, so two builds compare element for element.
+    out_dir/manifest.json records the full shape, source dtype and sampling of each array."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    manifest = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        n = a.size
+        entry = {"shape": list(a.shape), "dtype": str(a.dtype), "sampled": n > DUMP_MAX_ELEMS}
+        if n > DUMP_MAX_ELEMS:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_ELEMS, replace=False))]
+            entry["sample"] = f"flat indices np.sort(np.random.default_rng({DUMP_SEED}).choice({n}, {DUMP_MAX_ELEMS}, replace=False))"
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.astype(np.float32))
+        manifest[name] = entry
+    with open(os.path.join(out_dir, "manifest.json"), "w") as f:
+        json.dump(manifest, f, indent=1)
 
 
 def self_launch(args) -> int:
@@ -289,6 +322,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     assert masks.shape[0] == total and masks.dtype == torch.uint8
+    if args.dump_outputs and rank == 0:   # untimed: the last timed step's masks (all ranks') and sampler outputs (this rank's patches)
+        dump_outputs(args.dump_outputs, {"masks": masks, **{k: last_out["out"][k] for k in ("latents", "features", "rgb")}})
     timed_out = {k: last_out["out"][k].clone() for k in ("features", "latents")}   # of the LAST timed step (this rank's patches); the sampler reuses its buffers
     feat_crc = None
     # result check (untimed): the masks of the LAST timed step (two batches in flight, deferred joins, persistent conv kernels on short

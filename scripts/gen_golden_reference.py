@@ -19,11 +19,15 @@ import sys
 import types
 from unittest.mock import MagicMock
 
-import numpy as np
-import torch
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from oracle.pinned_cpu import PINNED_CPU_ENV  # noqa: E402
+
+os.environ.update(PINNED_CPU_ENV)   # before torch loads: the oracle's bits do not depend on the host (oracle/pinned_cpu.py)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
 REF = "/root/reference"
 OUT = os.path.join(ROOT, "tests", "golden")
 

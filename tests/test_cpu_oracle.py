@@ -4,9 +4,13 @@ third_party fixtures (tests/golden/{laplace_torch,luma_pil,round_numpy}.npz, ref
 they were produced by installed torch / Pillow / numpy and by the reference's own python (scripts/gen_golden*.py).
 restatement fixtures (pndm.npz, tiny_graph.npz) freeze the restated diffusers semantics (diffusers itself is absent:
 parity for those functions is unpinned, see oracle/__init__.py).
+Fixtures compared bit for bit against the oracle's own float arithmetic are taken and checked under oracle/pinned_cpu.py.
 """
+import functools
 import json
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -14,12 +18,27 @@ import torch
 
 from ldiffusion_amd import configs, weights
 from oracle import metrics, noise_post, pipeline as op, schedule, unet as ounet
+from oracle.pinned_cpu import PINNED_CPU_ENV
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
 
 def gold(name):
     return np.load(os.path.join(GOLD, name), allow_pickle=False)
+
+
+def pinned_cpu_numerics(test):
+    """Runs `test` in a fresh pytest process under PINNED_CPU_ENV (the environment its fixture was generated in): torch's CPU
+    kernels round differently per CPU vendor, instruction set and thread count, and the environment must precede torch's load."""
+    @functools.wraps(test)
+    def run():
+        if all(os.environ.get(k) == v for k, v in PINNED_CPU_ENV.items()):
+            return test()
+        cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + [
+            "-m", "pytest", "-q", "-p", "no:cacheprovider", f"{os.path.abspath(__file__)}::{test.__name__}"]
+        r = subprocess.run(cmd, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), env=dict(os.environ, **PINNED_CPU_ENV), capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, f"{test.__name__} under {PINNED_CPU_ENV}:\n{r.stdout[-6000:]}\n{r.stderr[-2000:]}"
+    return run
 
 
 # ---------------------------------------------------------------- pinned against third-party code
@@ -83,6 +102,7 @@ def test_metrics_and_luts_match_reference_python():
     assert metrics.map_mask(np.array(fx["luts"]["map_mask_in"], np.uint8)).tolist() == fx["luts"]["map_mask_out"]
 
 
+@pinned_cpu_numerics
 def test_one_pass_sampler_restatement_equals_reference_loop():
     """Segmentor.ldiffusion_augment (reference code, segmentor.py:86-112) was run on the oracle's objects to make the fixture;
     the oracle's own restatement of that loop must reproduce it: same UNet timesteps, same decoded images."""
@@ -108,6 +128,7 @@ def test_one_pass_sampler_restatement_equals_reference_loop():
     assert np.array_equal(torch.nn.functional.avg_pool2d(out, 64).numpy(), z["pooled"])
 
 
+@pinned_cpu_numerics
 def test_v4_restatement_equals_reference_copy_or_convert_image():
     """utils.copy_or_convert_image (reference code, utils.py:176-208; sampler variant V4) was run on the oracle's objects to make the
     fixture (scripts/gen_golden_v4.py), with the text-alignment wrapper of its call site around the UNet.  Pinned: the wrapper is handed
@@ -134,6 +155,7 @@ def test_v4_restatement_equals_reference_copy_or_convert_image():
 
 
 # ---------------------------------------------------------------- restated diffusers semantics (regression fixtures)
+@pinned_cpu_numerics
 def test_pndm_schedule_and_trajectory():
     z = gold("pndm.npz")
     sch = schedule.PNDMOracle()
