@@ -414,31 +414,41 @@ def adamw_step(params, grads, state, lr, betas=(0.9, 0.999), eps=1e-8, weight_de
     """One AdamW update (torch.optim.AdamW semantics; the reference's DeepSpeed config, ldiffusion.py:168-171) of float32 CUDA
     parameters, in place, ALL tensors in one launch (ldiff_op_adamw_multi).  `state` is a dict the caller keeps: the step count, the two
     moment buffers per parameter and the device tables of the launch (parameter / moment pointers and the chunk list are built once;
-    only the gradient pointers change from step to step)."""
+    only the gradient pointers change from step to step).  As in torch, a tensor whose gradient is None is skipped and its own step count
+    (the bias correction) does not advance; tensors whose counts differ are updated by one launch per count."""
     lib = _lib.load()
     live = [(i, p, g) for i, (p, g) in enumerate(zip(params, grads)) if g is not None]
     if not live:
         return   # nothing to update: the bias-correction step count must not advance either
     state["step"] = state.get("step", 0) + 1
+    steps = state.setdefault("_steps", {})   # per-tensor step counts
     dev = live[0][1].device
     for i, p, g in live:
         if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
             raise ValueError("adamw_step: parameters must be contiguous float32 CUDA tensors")
         if i not in state:
             state[i] = (torch.zeros_like(p), torch.zeros_like(p))
-    key = tuple((i, p.data_ptr(), p.numel()) for i, p, _ in live)
-    tab = state.get("_tables")
-    if tab is None or tab[0] != key:
-        tensors, chunks = [], []
-        for t, (i, p, _) in enumerate(live):
-            m, v = state[i]
-            tensors += [p.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()]
-            for first in range(0, p.numel(), ADAMW_CHUNK):
-                chunks += [t, first]        # {int32 tensor, int32 pad} packed into one int64 (little endian), then int64 first
-        tab = (key, torch.tensor(tensors, dtype=torch.int64).to(dev), torch.tensor(chunks, dtype=torch.int64).to(dev), len(chunks) // 2)
-        state["_tables"] = tab
-    keep = [g.detach().to(torch.float32).contiguous() for _, _, g in live]
-    gptr = torch.tensor([g.data_ptr() for g in keep], dtype=torch.int64).to(dev)
-    _lib.check(lib.ldiff_op_adamw_multi(tab[1].data_ptr(), gptr.data_ptr(), tab[2].data_ptr(), tab[3], float(lr), float(betas[0]), float(betas[1]), float(eps),
-                                        float(weight_decay), int(state["step"]), _sp()))
-    state["_keep"] = (keep, gptr)   # the launch is asynchronous: the pointer table and converted gradients must outlive it
+    groups = {}
+    for e in live:
+        steps[e[0]] = steps.get(e[0], 0) + 1
+        groups.setdefault(steps[e[0]], []).append(e)
+    old, tabs, keep = state.get("_tables") or [], [], []
+    for step, members in sorted(groups.items()):
+        key = tuple((i, p.data_ptr(), p.numel()) for i, p, _ in members)
+        tab = next((t for t in old if t[0] == key), None)
+        if tab is None:
+            tensors, chunks = [], []
+            for t, (i, p, _) in enumerate(members):
+                m, v = state[i]
+                tensors += [p.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()]
+                for first in range(0, p.numel(), ADAMW_CHUNK):
+                    chunks += [t, first]        # {int32 tensor, int32 pad} packed into one int64 (little endian), then int64 first
+            tab = (key, torch.tensor(tensors, dtype=torch.int64).to(dev), torch.tensor(chunks, dtype=torch.int64).to(dev), len(chunks) // 2)
+        tabs.append(tab)
+        gs = [g.detach().to(torch.float32).contiguous() for _, _, g in members]
+        gptr = torch.tensor([g.data_ptr() for g in gs], dtype=torch.int64).to(dev)
+        _lib.check(lib.ldiff_op_adamw_multi(tab[1].data_ptr(), gptr.data_ptr(), tab[2].data_ptr(), tab[3], float(lr), float(betas[0]), float(betas[1]),
+                                            float(eps), float(weight_decay), int(step), _sp()))
+        keep.append((gs, gptr))
+    state["_tables"] = tabs
+    state["_keep"] = keep   # the launches are asynchronous: the pointer tables and converted gradients must outlive them

@@ -345,6 +345,8 @@ void launch_attn_bwd(const AttnParams& p, const f16* dO, f16* dq, f16* dk, f16* 
   const int staged = (smem + stage <= 150 * 1024 && even) ? 1 : 0;
   if (staged) smem += stage;
   ensure_dyn_smem(reinterpret_cast<const void*>(attn_bwd_kernel), (int)smem);
+  const double bh = (double)p.B * p.heads;
+  ProfScope prof(staged ? "attn_bwd<staged>" : "attn_bwd<direct>", 10.0 * bh * p.Lq * p.Lk * p.d, 2.0 * bh * p.d * (3.0 * p.Lq + 4.0 * p.Lk), s);
   hipLaunchKernelGGL(attn_bwd_kernel, dim3(p.heads, p.B), dim3(256), smem, s, p.q, p.ldq, p.k, p.ldk, p.v, p.ldv, dO, p.ldo, dq, dk, dv, p.Lq, p.Lk, p.d,
                      p.q_bstride, p.kv_bstride, p.o_bstride, p.scale, staged);
   HIP_CHECK(hipGetLastError());

@@ -8,8 +8,9 @@ import contextlib
 
 from ldiffusion_amd import _lib
 
-# the matrix-engine kernels this inventory is about (norms, GroupNorm statistics and the elementwise kernels are tested bit-exactly elsewhere)
-ROUTED_PREFIXES = ("conv3x3<", "igemm<", "gemm_dma<", "gemm_df", "lngemm<", "attn<", "xattn<")
+# the matrix-engine kernels this inventory is about, and the two paths of the attention backward (norms, GroupNorm statistics and the
+# elementwise kernels are tested bit-exactly elsewhere)
+ROUTED_PREFIXES = ("conv3x3<", "igemm<", "gemm_dma<", "gemm_df", "lngemm<", "attn<", "xattn<", "attn_bwd<")
 
 
 def matrix_kernels(names):
@@ -83,6 +84,8 @@ KERNEL_VARIANTS = {
     # launch_attention (kernels_attn.hip): xattn_selected, attn_fr40_selected, attn_cfg by head dim, attn_d512_selected, else attn_dsplit
     "launch_attention": ["xattn<short-kv>", "attn<40,fixref>", "attn<32,16>", "attn<32,32>", "attn<64,48>", "attn<64,64>", "attn<96,80>",
                          "attn<96,96>", "attn<128,128>", "attn<160,160>", "attn<512,128q>", "attn<512,512>"],
+    # launch_attn_bwd (kernels_bwd.hip): operands staged through LDS when the staging fits and every pitch, stride and pointer is even
+    "launch_attn_bwd": ["attn_bwd<staged>", "attn_bwd<direct>"],
 }
 ALL_VARIANTS = {n for group in KERNEL_VARIANTS.values() for n in group}
 

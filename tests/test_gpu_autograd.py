@@ -197,6 +197,37 @@ def test_adamw_matches_torch():
         assert (d.cpu() - r.detach()).abs().max() <= 2e-6 * max(1.0, r.abs().max().item())
 
 
+def test_adamw_across_chunk_boundaries_none_gradients_and_table_rebuilds():
+    """ldiff_op_adamw_multi runs one workgroup per ADAMW_CHUNK elements: tensors of exactly one chunk, one chunk + 1 and 3 chunks - 7, beside
+    small ones; a None gradient in the middle of the list (that tensor is skipped, and as in torch its own step count does not advance); and
+    steps at which the set of live tensors changes, so that the device tables are rebuilt.  Against torch.optim.AdamW over several steps, at the bound of
+    test_adamw_matches_torch."""
+    n = ag.ADAMW_CHUNK
+    g = torch.Generator().manual_seed(18)
+    shapes = [(n,), (n + 1,), (7, 3), (3 * n - 7,), (129, 127), (5,)]
+    ps = [torch.randn(s, generator=g) for s in shapes]
+    ref = [p.clone().requires_grad_(True) for p in ps]
+    opt = torch.optim.AdamW(ref, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01)
+    dev = [p.clone().to(DEV) for p in ps]
+    state = {}
+    # which gradients are None at each step: steady, one in the middle missing, back to all, a different set, all again
+    plan = [set(), {2}, {2}, set(), {0, 4}, set()]
+    tables = []
+    for missing in plan:
+        grads = [None if i in missing else torch.randn(p.shape, generator=g) for i, p in enumerate(ps)]
+        for r, gr in zip(ref, grads):
+            r.grad = None if gr is None else gr.clone()
+        opt.step()                          # skips the tensors without a gradient: their step counts do not advance
+        ag.adamw_step(dev, [None if gr is None else gr.to(DEV) for gr in grads], state, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01)
+        tables.append(tuple(t[0] for t in state["_tables"]))
+        for i, (d, r) in enumerate(zip(dev, ref)):
+            err = (d.cpu() - r.detach()).abs().max().item()
+            assert err <= 2e-6 * max(1.0, r.abs().max().item()), f"tensor {i} {tuple(ps[i].shape)} after the step without {sorted(missing)}: {err:.3e}"
+    assert tables[1] != tables[0] and tables[2] == tables[1] and tables[4] != tables[3], "the live-tensor tables were not rebuilt"
+    assert len(tables[-1]) == 3, "tensors that skipped steps carry their own bias-correction step counts"
+    assert sum(t[3] for t in state["_tables"]) == sum(-(-p.numel() // n) for p in ps)   # chunks of the last step: 1 + 2 + 1 + 3 + 2 + 1
+
+
 def test_pack_weight_multi_equals_the_single_launches():
     """ag.PackPlan (ldiff_op_pack_weight_multi: every forward and dgrad layout of a weight list in one launch) against ldiff_op_pack_weight
     tensor by tensor: 3x3 and 1x1 convs, linears, ragged channel counts (padding rows / columns must come out zero)."""

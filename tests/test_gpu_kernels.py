@@ -1881,8 +1881,9 @@ def model_routes(lib):
 
 
 def pinned_kernels():
-    """Every kernel some parity case of this file states it reaches."""
-    pinned = set(CONV_KERNEL.values()) | set(ATTN_KERNEL.values()) | {k for _, _, k in SPLITK_CASES.values()}
+    """Every kernel some parity case of this file, or of the backward-pass cases (test_gpu_backward.py), states it reaches."""
+    import test_gpu_backward
+    pinned = set(CONV_KERNEL.values()) | set(ATTN_KERNEL.values()) | {k for _, _, k in SPLITK_CASES.values()} | test_gpu_backward.pinned_kernels()
     for table in (SPLIT_KERNEL, FUSED_STATS_KERNEL, GEMM_DF_KERNEL):
         pinned |= {n for names in table.values() for n in names}
     probes = [dict(d=40, M=4096, geglu=False), dict(d=80, M=300, geglu=True), dict(d=512, M=8192, geglu=False), dict(d=40, M=512, geglu=False)]
