@@ -530,29 +530,30 @@ int ldiff_op_conv(const ldiff_conv_args* a, void* stream) {
   API_BEGIN
   ConvParams p;
   conv_args_to_params(a, p);
-  if (a->splitk) {   // an explicit split count (tests, timing): validated here, the kernels take it as the executors' plans
+  if (a->splitk)   // an explicit split count (tests, timing), taken as the executors' plans are
     LDIFF_CHECK(a->splitk >= 2 && a->splitk <= 16 && !p.out_f32 && !p.geglu && !p.ups && !p.xs && !p.lo8_slab0 && p.df_force <= 0, LDIFF_ERR_INVALID,
                 "op_conv: splitk = %d needs 2..16 splits, an fp16 output and a plain 3x3 / 1x1 / strided launch", a->splitk);
-    LDIFF_CHECK(a->splitk <= (conv3x3_eligible(p) ? (p.C1 + p.C2) / 64 : (p.K + 63) / 64), LDIFF_ERR_INVALID, "op_conv: more splits than K steps");
-    p.splitk = a->splitk;
-  }
-  p.stats_R = p.stats ? conv_stats_blocks_per_image(p) : 0;
+  const bool df_asked = p.df_force > 0;
+  ConvAsk ask;
+  ask.splitk = a->splitk ? a->splitk : (p.stats || p.xs || df_asked) ? 1 : 0;   // no planned split beside fused statistics, a folded shortcut or a forced gemm_df
+  ask.stats = p.stats != nullptr;
+  const ConvPlan pl = plan_conv(p, ask);
   LDIFF_CHECK(!p.stats || p.stats_R > 0, LDIFF_ERR_INVALID, "op_conv: fused statistics are not supported for this shape");
-  // same split-K plan and 2x-upsample folding the executors use.  This test/bench entry point has no handle to own the scratch, so
-  // it keeps one grow-only buffer per (device, stream): reuse is stream-ordered, and two streams or devices never share one.
+  LDIFF_CHECK(!p.xs || (a->sc_w && pl.kernel == ConvKernel::C3_DATAFLOW), LDIFF_ERR_INVALID, "op_conv: a folded shortcut (sc_x) needs sc_w and a launch the dataflow conv3x3 kernel takes");
+  if (df_asked) LDIFF_CHECK(pl.kernel == ConvKernel::GEMM_DF, LDIFF_ERR_INVALID, "op_conv: gemm_df asked for a launch the dataflow GEMM does not take");
+  // This test/bench entry point has no handle to own the derived weights and the scratch, so it keeps one grow-only buffer per (device, stream):
+  // reuse is stream-ordered, and two streams or devices never share one.
   hipStream_t st = (hipStream_t)stream;
-  if (p.ups && conv3x3_eligible(p)) {
+  if (pl.parity) {
     f16* wpar = (f16*)op_scratch(st, 0, (size_t)4 * p.Nrows * 4 * (p.C1 + p.C2) * sizeof(f16));
     launch_make_parity_weights(p.w, wpar, p.Nrows, p.C1 + p.C2, st);
     p.w_par = wpar;
-    if (p.stats) p.stats_R = conv_stats_blocks_per_image(p);
   }
-  LDIFF_CHECK(!p.xs || (a->sc_w && conv3x3_eligible(p) && conv3x3d_selected(p)), LDIFF_ERR_INVALID, "op_conv: a folded shortcut (sc_x) needs sc_w and a launch the dataflow conv3x3 kernel takes");
-  if (conv3x3d_selected(p)) {   // dataflow kernel: fragment-packed weights (the executors cache them per layer; here per call)
+  if (pl.weights == ConvWeights::FRAG || pl.weights == ConvWeights::FRAG_PAR || pl.weights == ConvWeights::FRAG_SC) {   // the executors cache these per layer; here per call
     f16* wf = (f16*)op_scratch(st, 3, conv3x3d_frag_bytes(p));
-    if (p.ups) launch_pack_frag_weights_par(p.w_par, wf, p.N, p.Nrows, p.C1, st);
+    if (pl.weights == ConvWeights::FRAG_PAR) launch_pack_frag_weights_par(p.w_par, wf, p.N, p.Nrows, p.C1, st);
     else launch_pack_frag_weights(p.w, wf, p.N, p.C1, st);
-    if (p.xs) {   // the folded shortcut's weights behind the nine taps, the two biases summed
+    if (pl.weights == ConvWeights::FRAG_SC) {   // the folded shortcut's weights behind the nine taps, the two biases summed
       launch_pack_frag_weights_sc((const f16*)a->sc_w, wf, p.N, p.C1, p.Cs, p.Cs, st);
       float* bsum = (float*)op_scratch(st, 5, (size_t)p.Nrows * sizeof(float));
       launch_add_vectors(p.bias, (const float*)a->sc_bias, bsum, p.Nrows, st);
@@ -560,13 +561,9 @@ int ldiff_op_conv(const ldiff_conv_args* a, void* stream) {
     }
     p.w_frag = wf;
   }
-  const bool df_asked = p.df_force > 0;
-  if (df_asked) LDIFF_CHECK(!conv3x3_eligible(p) && gemm_df_selected(p), LDIFF_ERR_INVALID, "op_conv: gemm_df asked for a launch the dataflow GEMM does not take");
-  // (a folded shortcut was validated against the dataflow kernel above: a split-K plan would take the launch away from it)
-  if (!p.splitk && !p.stats && !p.out_f32 && !df_asked && !p.xs) p.splitk = conv3x3_eligible(p) ? conv3x3_splitk_plan(p) : gemm_dma_eligible(p) ? gemm_dma_splitk_plan(p) : igemm_splitk_plan(p);
   if (p.splitk > 1) p.splitk_ws = (float*)op_scratch(st, 1, (size_t)p.splitk * p.M * p.N * sizeof(float));
-  if (!conv3x3_eligible(p) && gemm_df_selected(p)) {   // dataflow GEMM: fragment-packed weights, per call as above.  LDIFF_OP_CACHE_FRAG=1 (timing scripts
-    // only): pack once per (matrix address, shape) -- stale as soon as the caller rewrites the matrix in place, which the tests do
+  if (pl.weights == ConvWeights::GEMM_FRAG) {   // LDIFF_OP_CACHE_FRAG=1 (timing scripts only): pack once per (matrix address, shape) -- stale as soon
+    // as the caller rewrites the matrix in place, which the tests do
     static const bool cache = [] { const char* e = getenv("LDIFF_OP_CACHE_FRAG"); return e && atoi(e) != 0; }();
     static std::mutex mu;
     static std::map<std::tuple<const void*, int, int>, f16*> packed;
@@ -581,16 +578,18 @@ int ldiff_op_conv(const ldiff_conv_args* a, void* stream) {
       p.w_frag = wf;
     }
   }
-  launch_igemm(p, (hipStream_t)stream);
+  launch_igemm(p, pl, st);
   API_END
 }
 int ldiff_op_conv_stats_blocks(const ldiff_conv_args* a) {
   try {
     ConvParams p;
     conv_args_to_params(a, p);
-    if (p.ups && conv3x3_eligible(p)) p.w_par = p.w;   // (what ldiff_op_conv will do: the kernels choose by null / non-null only)
-    if (a->splitk > 1) p.splitk = a->splitk;
-    return conv_stats_blocks_per_image(p);
+    ConvAsk ask;   // as ldiff_op_conv plans a launch with statistics
+    ask.splitk = a->splitk > 1 ? a->splitk : 1;
+    ask.stats = true;
+    plan_conv(p, ask);
+    return p.stats_R;
   } catch (const LdiffError& e) { return e.code; }
 }
 int ldiff_op_gn_finalize(const void* part1, int R1, int C1, const void* part2, int R2, int C2, int B, int HW, int groups, float eps,

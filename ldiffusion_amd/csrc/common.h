@@ -104,37 +104,37 @@ constexpr int LO8_SHIFT = 15;   // lo = x - fp16(x) of a GroupNorm + SiLU output
                                 // for |x| in [32, 64) it reaches 512 and saturates at 448 (the correction term is clamped, harmless), as for everything beyond
 // [Nrows][taps][Cin] fp16 -> [Nrows][taps][Cin fp16 | Cin e4m3 of w * 2^sw], sw = floor(log2(448 / max |w|)); scale_out[0] = 127 - sw (one int)
 void launch_lo8_weights(const f16* w, void* wd, int* scale_out, int Nrows, int taps, int Cin, hipStream_t s);
-void launch_igemm(const ConvParams& p, hipStream_t s);   // dispatches to the halo-tile 3x3 kernel when eligible
-bool conv3x3_eligible(const ConvParams& p);
-int conv3x3_splitk_plan(const ConvParams& p);
-int gemm_dma_splitk_plan(const ConvParams& p);           // ... and for the LDS-DMA GEMM (1x1 convs / linears with few tiles and a long K)
-int igemm_splitk_plan(const ConvParams& p);              // same contract for the register-staged implicit GEMM (stride-2 convs with few tiles)
+// Which kernel takes a conv / GEMM launch (conv_route.hip).  plan_conv decides, in this order: the kernel family, parity weights, the split
+// count, the fused statistics' row blocks, the kernel with its tile, and the pre-packed weights it reads.  It writes ConvParams::splitk (0 = no
+// split), ::stats_R (0 = no fused statistics for this launch) and, with ConvPlan::fold_gn, the per-image weight strides; every buffer the plan
+// names (w_par, splitk_ws, stats, w_frag, folded weights) is the caller's to provide before launch_igemm.
+enum class ConvKernel { C3_NARROW, C3_NARROW_FOLD, C3_DATAFLOW, C3_PINGPONG, C3_HALO, GEMM_DF, GEMM_DMA, IGEMM, NONE /* an fp8 lo half the ping-pong kernel does not take */ };
+enum class ConvWeights { PLAIN, FRAG, FRAG_PAR, FRAG_SC, GEMM_FRAG };   // launch_pack_frag_weights{,_par,_sc} / launch_pack_gemm_frag -> ConvParams::w_frag
+struct ConvAsk {          // what the caller states beside the launch itself
+  int splitk = 0;         // 0: plan a split count; 1: never split; >= 2: this count (ldiff_op_conv: tests, timing), checked against the K steps
+  bool stats = false;     // fused GroupNorm statistics of the output wanted
+  bool fold_gn = false;   // a GroupNorm prologue without SiLU in front of a 1x1 conv may become per-image weights (the caller folds them: launch_fold_gn_weights)
+};
+struct ConvPlan {
+  ConvKernel kernel = ConvKernel::NONE;
+  ConvWeights weights = ConvWeights::PLAIN;
+  bool parity = false;    // nearest-2x upsample folded into four 2x2 convs: the caller provides ConvParams::w_par (launch_make_parity_weights)
+  bool fold_gn = false;   // GroupNorm folded: the caller provides the per-image weights and biases as ConvParams::w / ::bias
+  int bm = 0, bn = 0;     // tile of C3_HALO (bm / 8 = pixel tile width), GEMM_DMA and IGEMM: bm output rows x bn output channels
+};
+ConvPlan plan_conv(ConvParams& p, const ConvAsk& ask);
+bool conv_lo8_enabled();   // LDIFF_LO8 (conv_route.hip)
+void launch_igemm(const ConvParams& p, const ConvPlan& pl, hipStream_t s);   // runs the planned kernel (the register-staged igemm itself: kernels_igemm.hip)
+bool conv3x3_eligible(const ConvParams& p);   // the halo-tile 3x3 family: kernels_conv3x3.hip
 void launch_splitk_reduce(const ConvParams& p, hipStream_t s);   // sums p.splitk fp32 partials of splitk_ws and applies the epilogue (+ the fused GroupNorm statistics: R = H W / 32)
-// Split count of a launch whose tiles do not fill the chip (round 6).  What bounds such a launch is not bytes: a workgroup takes its operand slices
-// (16 KiB per K-step) at ~0.95 us per step whatever the ring depth or the slice layout, from HBM and L2 alike (scripts/micro/hbm_ring.hip,
-// profiles/r06_hbm_ring.txt: the same 30 MB take 22 us on 80 workgroups, 13 on 160, 10.6 on 240, 8.9 on 480), so the lever is the NUMBER of workgroups --
-// against the fp32 partials a finer cut writes and the reduce launch reads.  Returns the S in [s_old, s_cap] with the shortest modelled time
-//     T(S) = 4 us + ceil(steps / S) * 0.95 us * max(1, tiles S / 330)  +  [S > 1] * (4 us + 2 * S * partial_bytes / 3 TB/s)
-// and s_old (the rule of rounds 2-5, which the B = 8 shapes were tuned with) unless the model sees at least 15 % less.
-inline int splitk_by_model(long long tiles, int steps, int min_steps, double partial_bytes, int s_old, int s_cap = 16) {
-  auto T = [&](int S) {
-    const double wgs = (double)tiles * S, per = (steps + S - 1) / S;
-    return 4.0 + per * 0.95 * (wgs > 330.0 ? wgs / 330.0 : 1.0) + (S > 1 ? 4.0 + 2.0 * S * partial_bytes / 3.0e6 : 0.0);
-  };
-  if (s_old < 1) s_old = 1;
-  int best = s_old;
-  double tb = T(s_old);
-  for (int S = s_old + 1; S <= s_cap && steps / S >= min_steps; ++S)
-    if (T(S) < tb) { tb = T(S); best = S; }
-  return tb <= 0.85 * T(s_old) ? best : s_old;
-}
 // nearest-2x upsample + conv3x3 == four 2x2 convs on the source grid (one per output parity) with pre-summed taps:
 // w_par[q][n][t][c] from w[n][ky][kx][c]  (2.25x fewer MACs than gathering 9 taps from the upsampled image)
-void launch_make_parity_weights(const f16* w, f16* w_par, int Nrows, int Cin, hipStream_t s);                  // 1 = no split; >1 needs splitk_ws of splitk*M*N floats
-void launch_conv3x3(const ConvParams& p, hipStream_t s);       // kernels_conv3x3.hip
-// 16x16-tile ping-pong variant for the maps that fill the chip (kernels_conv3x3p.hip); launch_conv3x3 dispatches to it
-bool conv3x3n_selected(const ConvParams& p);   // narrow-output kernel (N == 4, plain epilogue, weights resident in LDS): kernels_conv3x3n.hip
-void launch_conv3x3n(const ConvParams& p, hipStream_t s);
+void launch_make_parity_weights(const f16* w, f16* w_par, int Nrows, int Cin, hipStream_t s);
+void launch_conv3x3(const ConvParams& p, int bm, int bn, hipStream_t s);   // the 8 x bm/8 pixel x bn channel halo-tile kernels: kernels_conv3x3.hip
+bool conv3x3n_selected(const ConvParams& p);    // narrow-output kernel (N == 4, plain epilogue, weights resident in LDS): kernels_conv3x3n.hip
+bool conv3x3nt_selected(const ConvParams& p);   // ... in its tap-folded form
+void launch_conv3x3n(const ConvParams& p, bool fold, hipStream_t s);
+// 16x16-tile ping-pong variant for the maps that fill the chip (kernels_conv3x3p.hip)
 bool conv3x3p_selected(const ConvParams& p);
 // producer / consumer ("dataflow") kernel for GroupNorm-prologue convs on the large maps: kernels_conv3x3d.hip
 bool conv3x3d_selected(const ConvParams& p);
@@ -158,7 +158,7 @@ bool gemm_df_selected(const ConvParams& p);
 size_t gemm_df_frag_bytes(const ConvParams& p);
 void launch_pack_gemm_frag(const f16* w, f16* wf, int Nrows, int K, hipStream_t s);   // [Nrows][K] K-major -> MFMA A fragments, one KiB each
 void launch_gemm_df(const ConvParams& p, hipStream_t s);   // needs ConvParams::w_frag
-void launch_gemm_dma(const ConvParams& p, hipStream_t s);      // kernels_gemm.hip
+void launch_gemm_dma(const ConvParams& p, int bm, int bn, hipStream_t s);   // kernels_gemm.hip
 
 // ---- attention (kernels_attn.hip) ------------------------------------------------------------
 // O[b, q, h*d + :] = softmax(Q K^T / sqrt(d)) V   per (b, head).   All fp16, row strides in elements.
@@ -307,9 +307,7 @@ __device__ __forceinline__ float gelu_erf(float g) { return 0.5f * g * (1.0f + e
 // Row blocks never straddle two images (R = ConvParams::stats_R blocks per image):
 //   conv3x3   : r = ty*tiles_x + tx (8x16 tiles, both wave halves combined through LDS) or (ty*tiles_x + tx)*2 + wave_m (8x8 tiles)
 //   gemm/igemm: r = (m % HW) / 32                      (32 consecutive rows; needs HW % 32 == 0)
-// conv_stats_blocks_per_image() returns R for a launch (0 = not supported -> the caller falls back to the separate
-// statistics pass of kernels_norm.hip).
-int conv_stats_blocks_per_image(const ConvParams& p);
+// plan_conv sets R for a launch (0 = not supported -> the caller falls back to the separate statistics pass of kernels_norm.hip).
 void launch_gn_finalize(const float* part1, int R1, int C1, const float* part2, int R2, int C2, int B, int HW, int groups, float eps,
                         const float* gamma, const float* beta, float* scale, float* shift, hipStream_t s, int* nonfinite = nullptr);
 

@@ -951,18 +951,6 @@ void launch_c3_gn(const ConvParams& p, hipStream_t s) {
 
 }  // namespace
 
-static inline int c3_tile_w(const ConvParams& p) { return (p.w_par ? p.Win : p.Wout) >= 16 ? 16 : 8; }
-
-int conv3x3_stats_blocks(const ConvParams& p) {
-  if (p.lo8_slab0) return conv3x3p_stats_blocks(p);
-  if (conv3x3d_selected(p)) return conv3x3d_stats_blocks(p);
-  if (conv3x3p_selected(p)) return conv3x3p_stats_blocks(p);
-  const int TW = c3_tile_w(p);
-  const int Ht = p.w_par ? p.Hin : p.Hout, Wt = p.w_par ? p.Win : p.Wout;
-  // 8x16 tiles (wide kernel): one block per workgroup; 8x8 tiles: one per wave half
-  return ((Ht + 7) / 8) * ((Wt + TW - 1) / TW) * (TW == 16 ? 1 : 2) * (p.w_par ? 4 : 1);
-}
-
 // w_par[q][n][t][c] = sum of the 3x3 taps of w[n][ky][kx][c] that read the same source pixel for output parity q=(py,px):
 //   rows:  py=0: t_y=0 <- {ky=0},   t_y=1 <- {ky=1,2};   py=1: t_y=0 <- {ky=0,1}, t_y=1 <- {ky=2}   (same for columns)
 __global__ void make_parity_weights_kernel(const f16* __restrict__ w, f16* __restrict__ wp, int Nrows, int Cin) {
@@ -995,43 +983,8 @@ bool conv3x3_eligible(const ConvParams& p) {
 
 void launch_splitk_reduce(const ConvParams& p, hipStream_t s) { launch_splitk_reduce_impl(p, s); }
 
-int conv3x3_splitk_plan(const ConvParams& p) {
-  if (p.w_par) return 1;
-  // few workgroups and a long K loop (UNet 8x8 / 16x16 levels, K = 9*1280..9*2560): split the slabs so the grid fills the chip
-  const int TW = p.Wout >= 16 ? 16 : 8;
-  const int bn = (p.N % 128 != 0 && p.N % 160 == 0) ? 160 : (p.N <= 32 ? 32 : (p.N <= 64 ? 64 : 128));
-  const int wgs = p.B * ((p.Hout + 7) / 8) * ((p.Wout + TW - 1) / TW) * ((p.N + bn - 1) / bn);
-  const int nslab = (p.C1 + p.C2) / 64;
-  int S = 512 / (wgs > 0 ? wgs : 1);
-  if (S > nslab / 4) S = nslab / 4;
-  if (S > 8) S = 8;
-  if (S < 1) S = 1;
-  // small grids (batch 1 / 2, and the 8 x 8 level at any batch): a finer cut where the model of common.h sees it (whole slabs: a split starts at a slab)
-  static const bool fine = [] { const char* e = getenv("LDIFF_SPLITK_FINE"); return !e || atoi(e) != 0; }();
-  if (fine && wgs > 0 && wgs * S < 256) {
-    int Sm = splitk_by_model(wgs, nslab * 9, 9, (double)p.M * p.N * 4.0, S);
-    while (Sm > S && nslab / Sm < 1) --Sm;
-    S = Sm;
-  }
-  return S >= 2 ? S : 1;
-}
-
-void launch_conv3x3(const ConvParams& p, hipStream_t s) {
-  LDIFF_CHECK(p.splitk <= 1 || p.splitk_ws, LDIFF_ERR_INVALID, "conv3x3: split-K needs a workspace");   // (fused statistics of a split launch: by the reduce kernel)
-  LDIFF_CHECK(!p.w_par || (p.ups == 1 && p.splitk <= 1), LDIFF_ERR_INVALID, "conv3x3: parity weights need ups=1 and no split-K");
-  if (p.lo8_slab0) {   // split operand with an fp8 lo half: only the 16 x 16 ping-pong kernel reads that layout
-    LDIFF_CHECK(p.splitk <= 1 && conv3x3p_selected(p), LDIFF_ERR_INVALID, "conv3x3: an fp8 lo half needs the 16 x 16 ping-pong kernel (C1=%d N=%d %dx%d)", p.C1, p.N, p.Hout, p.Wout);
-    launch_conv3x3p(p, s);
-    return;
-  }
-  if (conv3x3n_selected(p)) { LDIFF_CHECK(!p.xs, LDIFF_ERR_INVALID, "conv3x3: a folded shortcut (xs) needs the dataflow kernel"); launch_conv3x3n(p, s); return; }
-  if (conv3x3d_selected(p)) { launch_conv3x3d(p, s); return; }
-  // every kernel below ignores ConvParams::xs while the caller has already summed the shortcut's bias into p.bias: refuse instead of a silently wrong sum
-  LDIFF_CHECK(!p.xs, LDIFF_ERR_INVALID, "conv3x3: a folded shortcut (xs) needs the dataflow kernel, which does not take this launch (split-K %d)", p.splitk);
-  if (conv3x3p_selected(p)) { launch_conv3x3p(p, s); return; }
-  const bool wide = c3_tile_w(p) == 16;
-  const int bn = (p.N % 128 != 0 && p.N % 160 == 0) ? 160 : (p.N <= 32 ? 32 : (p.N <= 64 ? 64 : 128));
-  if (wide) {
+void launch_conv3x3(const ConvParams& p, int bm, int bn, hipStream_t s) {
+  if (bm == 128) {
     if (bn == 160) launch_c3w_gn<160>(p, s);
     else if (bn == 64) launch_c3w_gn<64>(p, s);
     else if (bn == 32) launch_c3w_gn<32>(p, s);

@@ -914,22 +914,18 @@ void launch_pack_frag_weights(const f16* w, f16* wf, int N, int Cin, hipStream_t
   HIP_CHECK(hipGetLastError());
 }
 
-// LDIFF_CONV3X3_DATAFLOW: 0 = off, 1 (default) = where the unit list fills the chip, 2 = every eligible launch (tests, A/B timing)
+// the launches the dataflow kernel takes where its unit list fills the chip
 bool conv3x3d_selected(const ConvParams& p) {
-  static const int mode = [] { const char* e = getenv("LDIFF_CONV3X3_DATAFLOW"); return e ? atoi(e) : 1; }();
-  if (mode == 0) return false;
   if (p.ks != 3 || p.stride != 1 || p.pad_t != 1 || p.pad_l != 1 || p.splitk > 1) return false;
   if (p.x2 || p.C2 != 0 || p.C1 % 64 != 0 || p.N % 128 != 0 || p.Nrows < p.N) return false;
   const bool ups = p.ups != 0;
-  if (ups) {   // nearest-2x upsample folded into the conv (ConvParams::w_par): no prologue, no residual, no time embedding; LDIFF_C3D_UPS=0: the 16 x 16 ping-pong kernel
+  if (ups) {   // nearest-2x upsample folded into the conv (ConvParams::w_par): no prologue, no residual, no time embedding
     // Where it is chosen: measured against the 16 x 16 ping-pong kernel on one box (profiles/r05_conv3x3d_upsample.txt) it wins 11 % on the 256^2 -> 512^2 conv with one
     // persistent workgroup per CU and nothing (0 ... +4 % time) on the smaller maps or with one-unit runs beside the UNet stream -- a parity unit streams a whole halo
     // image for four taps instead of nine, so the producers' DMA per MFMA is 2.25 times the plain conv's; the whole step, where the decode runs one-unit workgroups, gets
-    // 0.3-0.9 % SLOWER.  So it is OFF unless asked for: ConvParams::c3d_ups = 1 (tests, timing) or LDIFF_C3D_UPS=1 for the whole process.  (A choice by short_runs would
-    // also give the pipelined and the serial sampler different kernels for one layer, and bench.py checks the two bit for bit.)
-    static const int env = [] { const char* e = getenv("LDIFF_C3D_UPS"); return e ? (atoi(e) != 0 ? 1 : -1) : 0; }();
-    const int want = p.c3d_ups ? p.c3d_ups : env;
-    if (want <= 0) return false;
+    // 0.3-0.9 % SLOWER.  So it is OFF unless asked for: ConvParams::c3d_ups = 1 (tests, timing).  (A choice by short_runs would also give the
+    // pipelined and the serial sampler different kernels for one layer, and bench.py checks the two bit for bit.)
+    if (p.c3d_ups <= 0) return false;
     if (!p.w_par || p.gn_scale || p.res || p.temb || p.xs || p.Hin % 16 != 0 || p.Win % 16 != 0 || p.Hout != 2 * p.Hin || p.Wout != 2 * p.Win) return false;
   } else {
     if (p.w_par || !p.gn_scale || !p.silu_in) return false;
@@ -941,7 +937,6 @@ bool conv3x3d_selected(const ConvParams& p) {
   if (px * (p.ld1 ? p.ld1 : p.C1) * 2 >= (1LL << 31) || (long long)p.M * p.ldy * 2 >= (1LL << 31) || (p.res && (long long)p.M * p.ld_res * 2 >= (1LL << 31))) return false;
   if ((long long)p.Nrows * 9 * p.C1 * 2 >= (1LL << 31)) return false;
   const long long units = (long long)p.B * (p.Hin >> 4) * (p.Win >> 4) * (p.N >> 7) * (ups ? 4 : 1);
-  if (mode == 2) return true;
   const int cus = d_num_cus();
   const long long rounds = (units + cus - 1) / cus;
   return units >= cus && units * 100 >= rounds * cus * 88;   // the runs must split evenly over the CUs

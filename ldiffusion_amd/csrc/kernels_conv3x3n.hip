@@ -382,21 +382,19 @@ __global__ __launch_bounds__(256, 2) void conv3x3nt_kernel(const ConvParams p, c
 
 // plain epilogue only (bias; fp32 or fp16 output of 4 stored columns), one or two sources, <= 512 input channels (weights resident in LDS)
 bool conv3x3n_selected(const ConvParams& p) {
-  static const bool off = [] { const char* e = getenv("LDIFF_CONV3X3_NARROW"); return e && atoi(e) == 0; }();   // =0: A/B timing and tests
   const int Cin = p.C1 + p.C2;
-  return !off && p.N == 4 && p.Nrows >= 4 && p.ups == 0 && !p.w_par && !p.res && !p.temb && !p.stats && p.splitk <= 1 && !p.y_lo && !p.geglu &&
+  return p.N == 4 && p.Nrows >= 4 && p.ups == 0 && !p.w_par && !p.res && !p.temb && !p.stats && p.splitk <= 1 && !p.y_lo && !p.geglu &&
          p.w_bstride == 0 && Cin <= 512 && p.ldy % 4 == 0 && p.Wout >= 16 && p.Hout >= 8;
 }
 
 // the tap-folded form: at most three real output channels (27 of the 32 columns), one source of 128 channels (weights in registers), no zero
-// row needed behind the real ones.  LDIFF_CONV3X3_NARROW_FOLD=0: the LDS-image kernel (A/B timing, tests)
-static bool conv3x3nt_selected(const ConvParams& p) {
-  static const bool off = [] { const char* e = getenv("LDIFF_CONV3X3_NARROW_FOLD"); return e && atoi(e) == 0; }();
-  return !off && p.n_real > 0 && p.n_real <= 3 && p.C2 == 0 && p.C1 == 128 && ((p.ld1 ? p.ld1 : p.C1) & 7) == 0;
+// row needed behind the real ones
+bool conv3x3nt_selected(const ConvParams& p) {
+  return p.n_real > 0 && p.n_real <= 3 && p.C2 == 0 && p.C1 == 128 && ((p.ld1 ? p.ld1 : p.C1) & 7) == 0;
 }
 
-void launch_conv3x3n(const ConvParams& p, hipStream_t s) {
-  if (conv3x3nt_selected(p)) {
+void launch_conv3x3n(const ConvParams& p, bool fold, hipStream_t s) {
+  if (fold) {
     const int tiles = p.B * ((p.Hout + 7) / 8) * ((p.Wout + 15) / 16);
     static const int run = [] { const char* e = getenv("LDIFF_C3N_RUN"); const int v = e ? atoi(e) : 16; return v > 0 ? v : 16; }();   // tiles per workgroup (same box: 242 / 226 / 222 / 215 us at 2 / 4 / 8 / 16)
     const int grid = tiles <= 512 ? tiles : std::max(512, (tiles + run - 1) / run);

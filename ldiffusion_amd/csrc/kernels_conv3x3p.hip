@@ -690,11 +690,10 @@ int c3p_bn(const ConvParams& p) { return p.N <= 64 ? 64 : 128; }
 
 // The 16x16 ping-pong kernel serves the maps that fill the chip with one 512-thread workgroup per CU and whose outputs take the
 // 16-byte store path; everything else (small maps, split-K levels, narrow or fp32 outputs, GroupNorm in front of an upsampling conv)
-// stays on the 8x16 / 8x8 kernels.  LDIFF_CONV3X3_PINGPONG=0 switches it off, =2 also takes grids smaller than the chip (A/B timing and tests only).
+// stays on the 8x16 / 8x8 kernels.
 static bool c3p_instantiated(const ConvParams& p);
 bool conv3x3p_selected(const ConvParams& p) {
-  static const int mode = [] { const char* e = getenv("LDIFF_CONV3X3_PINGPONG"); return e ? atoi(e) : 1; }();   // 0: off, 2: also for grids smaller than the chip
-  if (mode == 0 || p.splitk > 1 || p.out_f32) return false;
+  if (p.splitk > 1 || p.out_f32) return false;
   const bool par = p.w_par != nullptr;
   if (p.gn_scale || !c3p_instantiated(p)) return false;   // GroupNorm prologue: the 8x16 kernel (see the header)
   if (p.lo8_slab0 && (par || p.x2 || p.ups || p.ld1 || p.C1 != 96 * p.lo8_slab0 || (p.lo8_slab0 & 1) || !p.lo8_sa)) return false;   // fp8 lo half: one source of 3C/2 "elements", C % 128 == 0
@@ -710,7 +709,7 @@ bool conv3x3p_selected(const ConvParams& p) {
   // second round)
   const int cus = c3p_num_cus();
   const long long rounds = (wgs + cus - 1) / cus;
-  return mode == 2 || wgs * 100 >= rounds * cus * 88;
+  return wgs * 100 >= rounds * cus * 88;
 }
 int conv3x3p_stats_blocks(const ConvParams& p) {
   const bool par = p.w_par != nullptr;

@@ -378,40 +378,8 @@ bool gemm_dma_eligible(const ConvParams& p) {
          p.Hout == p.Hin && p.Wout == p.Win && p.M < (1 << 24) && pmax * 2 < (1 << 24) && (long long)p.M * pmax * 2 < (1LL << 31) && (long long)p.Nrows * p.K * 2 < (1LL << 31);
 }
 
-// Split-K for the LDS-DMA GEMM, same rule as igemm_splitk_plan: only where the tiles leave most workgroup slots empty and K is long
-// (1x1 shortcut convs over the concat input at the 8x8 level: M = 512, K = 2560 or 5120 on split operands)
-int gemm_dma_splitk_plan(const ConvParams& p) {
-  if (p.out_f32 || p.geglu || p.w_bstride != 0 || p.M <= 0 || !gemm_dma_eligible(p)) return 1;
-  if (p.stats && (p.Hout * p.Wout) % 32 != 0) return 1;   // the reduce kernel emits them in 32-row blocks
-  auto tiles = [&](int bm, int bn) { return (long long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
-  if (tiles(128, 64) >= 384) return 1;
-  const int nk = p.K / 64;
-  auto splits = [&](long long t) { int S = (int)(512 / t); S = S > nk / 16 ? nk / 16 : S; return S > 8 ? 8 : S; };
-  // the largest tile whose splits fill the chip (128x128: 0.0156 operand bytes per flop, 128x64: 0.023, 64x64: 0.031); launch_gemm_dma picks
-  // the tile by tiles x S with the same thresholds
-  const bool n_small = p.N <= 64 || (p.N % 128 != 0 && p.N % 128 <= 64 && p.N < 512);
-  const int S256 = n_small ? 1 : splits(tiles(128, 128));
-  if (S256 >= 2 && tiles(128, 128) * S256 >= 384) return S256;
-  const int S128 = splits(tiles(128, 64));
-  if (S128 >= 2 && tiles(128, 64) * S128 >= 384) return S128;
-  int S64 = splits(tiles(64, 64));
-  if (S64 < 1) S64 = 1;
-  // small grids (batch 1 / 2; the 8 x 8 level): a finer cut where the model of common.h sees it
-  static const bool fine = [] { const char* e = getenv("LDIFF_SPLITK_FINE"); return !e || atoi(e) != 0; }();
-  if (fine && tiles(64, 64) * S64 < 256) S64 = splitk_by_model(tiles(64, 64), nk, 4, (double)p.M * p.N * 4.0, S64);
-  return S64 >= 2 ? S64 : 1;
-}
-
-void launch_gemm_dma(const ConvParams& p, hipStream_t s) {
-  static const int force = [] { const char* e = getenv("LDIFF_GEMM_TILE"); return e ? atoi(e) : 0; }();   // diagnostic: 1 = 128x128, 2 = 128x64, 3 = 64x64
-  if (force == 1 && (p.w_bstride == 0 || (p.Hout * p.Wout) % 128 == 0)) return launch_g<128, 128>(p, s);
-  if (force == 2 && (p.w_bstride == 0 || (p.Hout * p.Wout) % 128 == 0)) return launch_g<128, 64>(p, s);
-  if (force == 3) return launch_g<64, 64>(p, s);
-  const int S = p.splitk > 1 ? p.splitk : 1;   // split-K multiplies the workgroups of a tile shape
-  auto tiles = [&](int bm, int bn) { return (long long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
-  const bool n_small = p.N <= 64 || (p.N % 128 != 0 && p.N % 128 <= 64 && p.N < 512);
-  const bool bm128_ok = p.w_bstride == 0 || (p.Hout * p.Wout) % 128 == 0;   // per-image weights: 128-row tiles only if they divide an image
-  if (!n_small && bm128_ok && tiles(128, 128) * S >= 384) launch_g<128, 128>(p, s);
-  else if (bm128_ok && tiles(128, 64) * S >= 384) launch_g<128, 64>(p, s);
+void launch_gemm_dma(const ConvParams& p, int bm, int bn, hipStream_t s) {
+  if (bm == 128 && bn == 128) launch_g<128, 128>(p, s);
+  else if (bm == 128) launch_g<128, 64>(p, s);
   else launch_g<64, 64>(p, s);
 }

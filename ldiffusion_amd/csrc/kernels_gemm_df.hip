@@ -602,8 +602,6 @@ struct DfPlan { int mt, ntw; };
 // sums).  A step costs its matrix cycles or the cycles its operand bytes take to arrive at ~28 B per cycle and CU, whichever is longer -- at these
 // tile sizes it is nearly always the bytes (profiles/r05_gemm_df.md: the unit shapes rank as this model says on all 22 UNet shapes measured).
 DfPlan df_plan(const ConvParams& p) {
-  static const int force_mt = [] { const char* e = getenv("LDIFF_GEMM_DF_MT"); return e ? atoi(e) : 0; }();
-  static const int force_ntw = [] { const char* e = getenv("LDIFF_GEMM_DF_NTW"); return e ? atoi(e) : 0; }();
   const int cus = f_num_cus();
   DfPlan best{8, 5};
   double best_t = 1e30;
@@ -612,8 +610,7 @@ DfPlan df_plan(const ConvParams& p) {
               "gemm (dataflow): unit shape %d x %d is not built", arg_mt * 16, arg_ntw * 64);
   for (int mt : {8, 4})
     for (int ntw : {5, 4, 2}) {
-      if (arg_mt ? mt != arg_mt : (force_mt && mt != force_mt)) continue;
-      if (arg_ntw ? ntw != arg_ntw : (force_ntw && ntw != force_ntw)) continue;
+      if ((arg_mt && mt != arg_mt) || (arg_ntw && ntw != arg_ntw)) continue;
       const int bm = mt * 16, bn = ntw * 64;
       const long long units = (long long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn);
       const double rounds = (double)((units + cus - 1) / cus);
@@ -679,17 +676,16 @@ void launch_pack_gemm_frag(const f16* w, f16* wf, int Nrows, int K, hipStream_t 
 }
 size_t gemm_df_frag_bytes(const ConvParams& p) { return (size_t)p.Nrows * p.K * sizeof(f16); }
 
-// LDIFF_GEMM_DF: 0 = off, 1 (default) = where the unit list fills the chip, 2 = every eligible launch (tests, A/B timing)
+// of the launches gemm_dma_eligible takes (plan_conv asks for no others): where the unit list fills the chip, or as ConvParams::df_force says
 bool gemm_df_selected(const ConvParams& p) {
-  static const int mode = [] { const char* e = getenv("LDIFF_GEMM_DF"); return e ? atoi(e) : 1; }();
-  if (p.df_force < 0 || (mode == 0 && p.df_force == 0) || !gemm_dma_eligible(p)) return false;
+  if (p.df_force < 0) return false;
   if (p.w_bstride != 0 || p.splitk > 1 || p.out_f32 || p.M <= 0) return false;
   if (p.stats && (p.geglu || (p.Hout * p.Wout) % 32 != 0 || p.stats_R != (p.Hout * p.Wout) / 32)) return false;
   if (p.C1 % 64 != 0 || p.C2 % 64 != 0 || p.Nrows % 16 != 0 || p.Nrows < p.N) return false;
   if ((p.N & 7) || (p.ldy & 7) || (p.y_lo & 7) || (p.res && ((p.ld_res & 7) || (p.res_lo & 7)))) return false;
   if (p.geglu && (p.N % 64 != 0 || p.res || p.y_lo)) return false;
   if ((long long)p.M * p.ldy * 2 >= (1LL << 31) || (p.res && (long long)p.M * p.ld_res * 2 >= (1LL << 31)) || (long long)p.Nrows * p.K * 2 >= (1LL << 31)) return false;
-  if (mode == 2 || p.df_force > 0) return true;
+  if (p.df_force > 0) return true;
   // fused statistics: built and bit-identical to gemm_dma's, but with two epilogue waves summing beside their stores the launch takes twice
   // gemm_dma's time (proj_out at level 0: 36 -> 68 us): only on request
   if (p.stats) return false;

@@ -292,34 +292,7 @@ static void launch_bmn(const ConvParams& p, bool fast, hipStream_t s) {
   else      { if (gn) launch_cfg<BM, BN, false, true>(p, s); else launch_cfg<BM, BN, false, false>(p, s); }
 }
 
-int conv3x3_stats_blocks(const ConvParams& p);
-
-int conv_stats_blocks_per_image(const ConvParams& p) {
-  if (p.out_f32) return 0;
-  const int hw = p.Hout * p.Wout;
-  if (p.splitk > 1) return hw % 32 == 0 ? hw / 32 : 0;   // a split launch: the reduce kernel's 32-row blocks, whichever kernel wrote the partials
-  if (conv3x3_eligible(p)) return conv3x3_stats_blocks(p);
-  return hw % 32 == 0 ? hw / 32 : 0;
-}
-
-// Split-K for the register-staged kernel: only where its launcher picks 64x64 tiles, the tiles leave most workgroup slots empty and the
-// K loop is long (stride-2 3x3 convs of the UNet's 16x16 -> 8x8 level: 160 tiles x 180-360 K-steps)
-int igemm_splitk_plan(const ConvParams& p) {
-  if (p.out_f32 || p.geglu || p.M <= 0) return 1;
-  if (p.stats && (p.Hout * p.Wout) % 32 != 0) return 1;   // the reduce kernel emits them in 32-row blocks
-  if (conv3x3_eligible(p) || gemm_dma_eligible(p)) return 1;
-  auto tiles = [&](int bm, int bn) { return (long long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
-  if (tiles(128, 64) >= 384) return 1;
-  const int nk = (p.K + BK - 1) / BK;
-  auto splits = [&](long long t) { int S = (int)(512 / t); S = S > nk / 16 ? nk / 16 : S; return S > 8 ? 8 : S; };
-  // 128x64 tiles (half the operand bytes per flop of 64x64) when their splits fill the chip; launch_igemm picks the tile by tiles x S
-  const int S128 = splits(tiles(128, 64));
-  if (S128 >= 2 && tiles(128, 64) * S128 >= 384) return S128;
-  const int S64 = splits(tiles(64, 64));
-  return S64 >= 2 ? S64 : 1;
-}
-
-void launch_igemm(const ConvParams& p, hipStream_t s) {
+void launch_igemm(const ConvParams& p, const ConvPlan& pl, hipStream_t s) {
   const int Cin = p.C1 + p.C2;
   LDIFF_CHECK(p.C1 % 8 == 0 && p.C2 % 8 == 0 && Cin > 0, LDIFF_ERR_INVALID, "igemm: channel counts must be multiples of 8 (C1=%d C2=%d)", p.C1, p.C2);
   LDIFF_CHECK(p.K == p.ks * p.ks * Cin, LDIFF_ERR_INVALID, "igemm: K=%d != ks*ks*Cin=%d", p.K, p.ks * p.ks * Cin);
@@ -331,22 +304,26 @@ void launch_igemm(const ConvParams& p, hipStream_t s) {
   LDIFF_CHECK((p.ld1 == 0 || (p.ld1 >= p.C1 && p.ld1 % 8 == 0)) && (p.ld2 == 0 || (p.ld2 >= p.C2 && p.ld2 % 8 == 0)), LDIFF_ERR_INVALID,
               "igemm: row pitches must be multiples of 8 and >= the channel counts");
   // per-image weights (GroupNorm folded into the layer) exist only in the LDS-DMA GEMM: any other kernel would silently use image 0's
-  LDIFF_CHECK(p.w_bstride == 0 || (!conv3x3_eligible(p) && gemm_dma_eligible(p)), LDIFF_ERR_INVALID, "igemm: per-image weights need the DMA GEMM path");
+  LDIFF_CHECK(p.w_bstride == 0 || pl.kernel == ConvKernel::GEMM_DMA, LDIFF_ERR_INVALID, "igemm: per-image weights need the DMA GEMM path");
   LDIFF_CHECK(!p.temb || p.ld_temb % 4 == 0, LDIFF_ERR_INVALID, "igemm: ld_temb must be a multiple of 4");
   if (p.M <= 0) return;
-  if (conv3x3_eligible(p)) { launch_conv3x3(p, s); return; }
-  if (gemm_dma_eligible(p)) {
-    if (p.w_frag && gemm_df_selected(p)) launch_gemm_df(p, s);   // the caller packed the weights for the dataflow kernel
-    else launch_gemm_dma(p, s);
-    return;
+  LDIFF_CHECK(p.splitk <= 1 || p.splitk_ws, LDIFF_ERR_INVALID, "conv: split-K needs a workspace");   // (fused statistics of a split launch: by the reduce kernel)
+  LDIFF_CHECK(!p.w_par || (p.ups == 1 && p.splitk <= 1), LDIFF_ERR_INVALID, "conv3x3: parity weights need ups=1 and no split-K");
+  LDIFF_CHECK(pl.kernel != ConvKernel::NONE, LDIFF_ERR_INVALID, "conv3x3: an fp8 lo half needs the 16 x 16 ping-pong kernel (C1=%d N=%d %dx%d)", p.C1, p.N, p.Hout, p.Wout);
+  // every kernel but the dataflow conv ignores ConvParams::xs while the caller has already summed the shortcut's bias into p.bias: refuse instead of a silently wrong sum
+  LDIFF_CHECK(!p.xs || pl.kernel == ConvKernel::C3_DATAFLOW, LDIFF_ERR_INVALID, "conv3x3: a folded shortcut (xs) needs the dataflow kernel, which does not take this launch (split-K %d)", p.splitk);
+  switch (pl.kernel) {
+    case ConvKernel::C3_NARROW: case ConvKernel::C3_NARROW_FOLD: launch_conv3x3n(p, pl.kernel == ConvKernel::C3_NARROW_FOLD, s); return;
+    case ConvKernel::C3_DATAFLOW: launch_conv3x3d(p, s); return;
+    case ConvKernel::C3_PINGPONG: launch_conv3x3p(p, s); return;
+    case ConvKernel::C3_HALO: launch_conv3x3(p, pl.bm, pl.bn, s); return;
+    case ConvKernel::GEMM_DF: launch_gemm_df(p, s); return;
+    case ConvKernel::GEMM_DMA: launch_gemm_dma(p, pl.bm, pl.bn, s); return;
+    default: break;
   }
   LDIFF_CHECK(!p.geglu, LDIFF_ERR_INVALID, "GEGLU epilogue: only on 1x1 / linear layers with K %% 64 == 0, N %% 32 == 0, fp16 output, no residual");
   const bool fast = (Cin % BK == 0) && (p.C1 % BK == 0);
-  // Tile choice: largest tile that still yields >= ~2 workgroups per CU worth of tiles; narrow N gets BN=64.
-  const int S = p.splitk > 1 ? p.splitk : 1;   // split-K multiplies the workgroups of a tile shape (igemm_splitk_plan)
-  auto tiles = [&](int bm, int bn) { return (long long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
-  const bool n_small = p.N <= 64 || (p.N % 128 != 0 && p.N % 128 <= 64 && p.N < 512);
-  if (!n_small && S == 1 && tiles(128, 128) >= 384) launch_bmn<128, 128>(p, fast, s);
-  else if (tiles(128, 64) * S >= 384) launch_bmn<128, 64>(p, fast, s);
+  if (pl.bm == 128 && pl.bn == 128) launch_bmn<128, 128>(p, fast, s);
+  else if (pl.bm == 128) launch_bmn<128, 64>(p, fast, s);
   else launch_bmn<64, 64>(p, fast, s);
 }

@@ -329,10 +329,8 @@ const f16* Exec::derived_lo8(const MatW& w, const int** scale) {
   *scale = sc;
   return w.lo8.p;
 }
-// LDIFF_LO8: 1 (default) = the lo half of a split conv operand travels as fp8 where the 16 x 16 ping-pong kernel takes it, 0 = fp16 lo halves everywhere
 bool Exec::lo8_conv_ok(const MatW& w, const Act& x, bool res, bool split_out) const {
-  static const int mode = [] { const char* e = getenv("LDIFF_LO8"); return e ? atoi(e) : 1; }();
-  if (!mode || w.ks != 3 || x.C != w.Cin || x.C % 128 != 0 || w.Cin_logical > 0 || !split_out) return false;
+  if (!conv_lo8_enabled() || w.ks != 3 || x.C != w.Cin || x.C % 128 != 0 || w.Cin_logical > 0 || !split_out) return false;
   ConvParams p;
   memset(&p, 0, sizeof(p));
   static const int one = 127;
@@ -340,9 +338,11 @@ bool Exec::lo8_conv_ok(const MatW& w, const Act& x, bool res, bool split_out) co
   p.B = x.B; p.Hin = p.Hout = x.H; p.Win = p.Wout = x.W; p.ks = 3; p.stride = 1; p.pad_t = p.pad_l = 1;
   p.w = w.w; p.N = roundup(w.N, 4); p.n_real = w.N; p.Nrows = w.Nrows; p.K = 9 * p.C1; p.M = x.B * x.H * x.W;
   if (p.N != w.N || p.N % 8 != 0) return false;
-  p.y = x.p; p.ldy = 2 * p.N; p.y_lo = p.N; p.stats = reinterpret_cast<float*>(x.p);   // (placeholders: only null / non-null and the layout matter)
+  p.y = x.p; p.ldy = 2 * p.N; p.y_lo = p.N;   // (placeholders: only null / non-null and the layout matter)
   if (res) { p.res = x.p; p.ld_res = 2 * p.N; p.res_lo = p.N; }
-  return conv3x3_eligible(p) && conv3x3_splitk_plan(p) <= 1 && conv3x3p_selected(p);
+  ConvAsk ask;   // as Exec::conv plans the resnet convs
+  ask.stats = true;
+  return plan_conv(p, ask).kernel == ConvKernel::C3_PINGPONG;
 }
 const f16* Exec::derived_frag(const MatW& w, const ConvParams& p) {
   const int gen = weights_gen ? *weights_gen : 0;
@@ -474,8 +474,6 @@ Act Exec::conv(const MatW& w, const Act& x, const Act* x2, const ConvOpts& o) {
   p.N = o.N_override ? o.N_override : roundup(w.N, 4);
   p.n_real = o.N_override ? 0 : w.N;
   p.bias = w.b;
-  f16* wfold = nullptr;
-  float* bfold = nullptr;
   if (o.gn) { p.gn_scale = o.gn->scale; p.gn_shift = o.gn->shift; p.silu_in = o.silu; }
   p.temb = o.temb; p.ld_temb = o.ld_temb;
   p.M = x.B * p.Hout * p.Wout;
@@ -483,81 +481,65 @@ Act Exec::conv(const MatW& w, const Act& x, const Act* x2, const ConvOpts& o) {
     LDIFF_CHECK(o.res->rows() == p.M && o.res->C >= p.N, LDIFF_ERR_INVALID, "conv: residual shape mismatch");
     p.res = o.res->p; p.ld_res = o.res->ld(); p.res_lo = o.res->lo();
   }
-  // GroupNorm -> 1x1 conv / Linear with no activation in between (VAE attention q/k/v; transformer proj_in under PREC_FAST): fold the
-  // normalisation into per-image weights and bias and run the plain LDS-DMA GEMM instead of the register-staged GN prologue
-  if (o.gn && !o.silu && w.ks == 1 && !x2 && !o.out_f32 && !o.geglu && !o.want_stats && !o.split_in) {
-    ConvParams q = p;
-    q.gn_scale = nullptr; q.gn_shift = nullptr; q.silu_in = 0;
-    q.w_bstride = (long long)w.Nrows * w.K; q.bias_bstride = w.Nrows;
-    q.ldy = roundup(p.N, 8) * (o.split_out ? 2 : 1);
-    if (gemm_dma_eligible(q)) {          // same predicate the dispatcher uses: no silent fall-through to a kernel without per-image weights
-      wfold = tmp<f16>((size_t)x.B * w.Nrows * w.K);
-      bfold = tmp<float>((size_t)x.B * w.Nrows);
-      launch_fold_gn_weights(w.w, w.b, o.gn->scale, o.gn->shift, wfold, bfold, x.B, w.Nrows, w.K, s);
-      p = q;
-      p.w = wfold; p.bias = bfold;
-    }
-  }
-  Act y;
+  int C = 0;   // the output's layout (the tensor itself is allocated once the launch is planned)
   if (o.geglu) {
     LDIFF_CHECK(w.geglu && !o.out_f32 && !o.res && !o.want_stats && !o.split_out && p.N % 32 == 0, LDIFF_ERR_INVALID, "conv: GEGLU epilogue on a layer that was not built for it");
-    p.geglu = 1;
-    y = new_act(x.B, p.Hout, p.Wout, p.N / 2);
-    p.y = y.p; p.ldy = p.N / 2;
-    LDIFF_CHECK(gemm_dma_eligible(p), LDIFF_ERR_INVALID, "conv: GEGLU epilogue needs the DMA GEMM (K %% 64 == 0)");
+    p.geglu = 1; p.ldy = p.N / 2;
   } else if (o.out_f32) {
     LDIFF_CHECK(!o.split_out, LDIFF_ERR_INVALID, "conv: fp32 output cannot be split");
     p.y = o.out_f32; p.ldy = o.ldy_f32; p.out_f32 = 1;
+  } else {
+    C = o.ldy ? o.ldy : (o.split_out ? roundup(p.N, 4) : roundup(p.N, 8));
+    p.ldy = o.split_out ? 2 * C : C; p.y_lo = o.split_out ? C : 0;
+  }
+  if (o.sc_done) *o.sc_done = false;
+  if (o.sc_x && o.sc_w && o.sc_done && !o.split_in && !o.res && !o.sc_x->split && o.sc_w->ks == 1 && o.sc_w->Nrows == w.Nrows && o.sc_w->K == o.sc_x->C) {
+    p.xs = o.sc_x->p; p.Cs = o.sc_x->C; p.lds = o.sc_x->ld();   // the block's 1x1 shortcut, folded in where the dataflow kernel takes the launch
+  }
+  ConvAsk ask;
+  ask.stats = o.want_stats && C == p.N && p.N == w.N;   // (split-K launches too: their reduce kernel emits the statistics in 32-row blocks)
+  ask.fold_gn = !o.want_stats && !o.split_in;
+  const ConvPlan pl = plan_conv(p, ask);
+  if (o.sc_x && pl.weights != ConvWeights::FRAG_SC) return Act{};   // asked for the folded form only: nothing is launched, the caller takes the two-launch form
+  f16* wfold = nullptr;
+  float* bfold = nullptr;
+  if (pl.fold_gn) {
+    wfold = tmp<f16>((size_t)x.B * w.Nrows * w.K);
+    bfold = tmp<float>((size_t)x.B * w.Nrows);
+    launch_fold_gn_weights(w.w, w.b, o.gn->scale, o.gn->shift, wfold, bfold, x.B, w.Nrows, w.K, s);
+    p.w = wfold; p.bias = bfold;
+  }
+  Act y;
+  if (o.geglu) {
+    y = new_act(x.B, p.Hout, p.Wout, p.N / 2);
+    p.y = y.p;
+    LDIFF_CHECK(pl.kernel == ConvKernel::GEMM_DMA || pl.kernel == ConvKernel::GEMM_DF, LDIFF_ERR_INVALID, "conv: GEGLU epilogue needs the DMA GEMM (K %% 64 == 0)");
+  } else if (o.out_f32) {
     if (o.post_done) {   // fused only where the narrow-output kernel runs (it is the one epilogue that knows the tail)
-      ConvParams t = p;
-      t.splitk = 1;
-      const bool fused = conv3x3_eligible(t) && conv3x3n_selected(t);
+      const bool fused = pl.kernel == ConvKernel::C3_NARROW || pl.kernel == ConvKernel::C3_NARROW_FOLD;
       *o.post_done = fused;
       if (fused) { p.post_img = o.post_img; p.post_rgb = o.post_rgb; p.post_luma = o.post_luma; p.post_slots = o.post_slots; p.post_slot = o.post_slot; p.post_only = o.post_only ? 1 : 0; }
     }
   } else {
-    const int C = o.ldy ? o.ldy : (o.split_out ? roundup(p.N, 4) : roundup(p.N, 8));
     y = new_act(x.B, p.Hout, p.Wout, C, o.split_out);
     if (C > p.N) launch_zero_bytes(y.p, y.bytes(), s);  // zero the pad columns (a kernel: the forward may be inside a captured graph)
-    p.y = y.p; p.ldy = y.ld(); p.y_lo = y.lo();
-    if (o.ups && conv3x3_eligible(p))   // nearest-2x upsample folded algebraically (4 parity convs with pre-summed taps)
-      p.w_par = derived_par(w, wsrc, Cin_eff, o.split_in ? w.dup_par : w.par);
-    // split-K launches write raw partials: their reduce kernel applies the epilogue and (round 6) emits the GroupNorm statistics too, in 32-row blocks
-    p.splitk = conv3x3_eligible(p) ? conv3x3_splitk_plan(p) : gemm_dma_eligible(p) ? gemm_dma_splitk_plan(p) : igemm_splitk_plan(p);
-    if (o.want_stats && C == p.N && p.N == w.N) {
-      const int R = conv_stats_blocks_per_image(p);
-      if (R > 0) {
-        y.st = tmp<float>((size_t)x.B * R * p.N * 2);
-        y.st_R = R;
-        p.stats = y.st;
-        p.stats_R = R;
-      }
-    }
+    p.y = y.p;
   }
-  if (!o.out_f32 && p.splitk > 1) p.splitk_ws = tmp<float>((size_t)p.splitk * p.M * p.N);
-  else p.splitk = 0;
-  if (o.sc_done) *o.sc_done = false;
-  if (o.sc_x && o.sc_w && o.sc_done && !o.split_in && !o.res && !o.sc_x->split && o.sc_w->ks == 1 && o.sc_w->Nrows == w.Nrows) {
-    // fold the block's 1x1 shortcut into this conv where the dataflow kernel takes the launch (LDIFF_C3D_FOLD_SC=0: never)
-    static const bool fold = [] { const char* e = getenv("LDIFF_C3D_FOLD_SC"); return !e || atoi(e) != 0; }();
-    ConvParams q = p;
-    q.xs = o.sc_x->p; q.Cs = o.sc_x->C; q.lds = o.sc_x->ld();
-    if (fold && o.sc_w->K == q.Cs && conv3x3_eligible(q) && conv3x3d_selected(q)) {   // (selected() is false under a split-K plan: q.splitk was decided above)
-      p = q;
-      p.w_frag = derived_frag_sc(w, *o.sc_w, p, &p.bias);
-      *o.sc_done = true;
-    }
+  if (pl.parity) p.w_par = derived_par(w, wsrc, Cin_eff, o.split_in ? w.dup_par : w.par);
+  if (p.stats_R) {
+    y.st = tmp<float>((size_t)x.B * p.stats_R * p.N * 2);
+    y.st_R = p.stats_R;
+    p.stats = y.st;
   }
-  if (o.sc_x && !p.xs) {   // asked for the folded form only: nothing is launched, the caller takes the two-launch form
-    if (p.splitk_ws) arena.free(p.splitk_ws);
-    release(y);
-    return Act{};
+  if (p.splitk) p.splitk_ws = tmp<float>((size_t)p.splitk * p.M * p.N);
+  switch (pl.weights) {   // MFMA-fragment-packed weights of the dataflow kernels
+    case ConvWeights::FRAG: p.w_frag = derived_frag(w, p); break;
+    case ConvWeights::FRAG_PAR: p.w_frag = derived_frag_par(w, p); break;
+    case ConvWeights::FRAG_SC: p.w_frag = derived_frag_sc(w, *o.sc_w, p, &p.bias); *o.sc_done = true; break;
+    case ConvWeights::GEMM_FRAG: p.w_frag = derived_gfrag(w, wsrc, p.K, o.split_in ? w.gfrag_dup : w.gfrag, o.split_in ? x.C : 0); break;
+    case ConvWeights::PLAIN: break;
   }
-  if (p.xs) {}
-  else if (!o.split_in && conv3x3_eligible(p) && conv3x3d_selected(p)) p.w_frag = p.ups ? derived_frag_par(w, p) : derived_frag(w, p);   // dataflow kernel: MFMA-fragment-packed weights
-  else if (!wfold && w.ks == 1 && !(o.split_in && x.lo8) && !conv3x3_eligible(p) && gemm_df_selected(p))   // dataflow GEMM: the same, of the matrix this launch reads
-    p.w_frag = derived_gfrag(w, wsrc, p.K, o.split_in ? w.gfrag_dup : w.gfrag, o.split_in ? x.C : 0);
-  launch_igemm(p, s);
+  launch_igemm(p, pl, s);
   if (p.splitk_ws) arena.free(p.splitk_ws);   // stream-ordered reuse: safe once the launches are enqueued
   if (wfold) { arena.free(bfold); arena.free(wfold); }
   return y;
@@ -821,7 +803,10 @@ void ldiff_unet::set_context(const float* ctx, int Bc, int L, hipStream_t s) {
     p.x = c16.p; p.C1 = D; p.B = 1; p.Hin = 1; p.Win = rows; p.Hout = 1; p.Wout = rows; p.ks = 1; p.stride = 1;
     p.w = t->kv2.w; p.N = 2 * t->C; p.Nrows = t->kv2.Nrows; p.K = D;
     p.y = t->kv_ctx; p.ldy = 2 * t->C; p.M = rows;
-    launch_igemm(p, s);
+    p.df_force = -1;   // (no fragment-packed copy of these weights for the dataflow GEMM)
+    ConvAsk ask;
+    ask.splitk = 1;
+    launch_igemm(p, plan_conv(p, ask), s);
     off += (size_t)rows * 2 * t->C;
   }
   ex.release(c16);

@@ -1,6 +1,6 @@
 """Race check of the dataflow conv3x3 kernel (diagnostic, GPU): the same launch repeated many times must reproduce its output and its fused
 statistics bit for bit (producers and consumers meet only through progress words: a missing wait shows up as a now-and-then wrong tile).
-usage: python scripts/stress_c3d.py [repeats]   (LDIFF_C3D_RUN / LDIFF_CONV3X3_DATAFLOW as for the library)"""
+usage: python scripts/stress_c3d.py [repeats]   (LDIFF_C3D_RUN as for the library)"""
 import ctypes as C, math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

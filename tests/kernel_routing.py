@@ -1,7 +1,7 @@
 """Which conv / GEMM / attention kernel a launch reaches, through the library's per-launch profiler (ProfScope names, include/ldiff.h
 ldiff_prof_*), and the hand-kept inventory of every such kernel the dispatchers can launch.
 
-The library picks a kernel from shape heuristics (launch_igemm, launch_conv3x3, launch_gemm_dma, launch_attention); a retune of those
+The library picks a kernel from shape heuristics (plan_conv in csrc/conv_route.hip, launch_attention); a retune of those
 heuristics can move a parity case to another kernel without the case failing.  Each kernel case therefore states the kernel it is meant to
 test, and `reached()` checks it before the numbers are compared."""
 import contextlib
@@ -63,21 +63,21 @@ def _both(*stems):
     return [s + t for s in stems for t in (">", ",gn>")]
 
 
-# Every profiled conv / GEMM / attention instantiation, grouped by the dispatch function that chooses it.
+# Every profiled conv / GEMM / attention instantiation, grouped by the launcher that runs it (the conv / GEMM ones as plan_conv chooses them).
 KERNEL_VARIANTS = {
-    # launch_conv3x3 -> conv3x3n_selected / conv3x3nt_selected (kernels_conv3x3n.hip): N == 4 stored columns, weights resident in LDS
+    # plan_conv -> conv3x3n_selected / conv3x3nt_selected (kernels_conv3x3n.hip): N == 4 stored columns, weights resident in LDS
     "launch_conv3x3n": _both("conv3x3<8x16,n4", "conv3x3<8x16,n3fold"),
-    # launch_conv3x3 -> conv3x3d_selected (kernels_conv3x3d.hip): GroupNorm + SiLU prologue, or the parity-folded upsample on request
+    # plan_conv -> conv3x3d_selected (kernels_conv3x3d.hip): GroupNorm + SiLU prologue, or the parity-folded upsample on request
     "launch_conv3x3d": ["conv3x3<16x16d,128,gn>", "conv3x3<16x16d,128,ups>"],
-    # launch_conv3x3 -> conv3x3p_selected / c3p_bn (kernels_conv3x3p.hip)
+    # plan_conv -> conv3x3p_selected / c3p_bn (kernels_conv3x3p.hip)
     "launch_conv3x3p": ["conv3x3<16x16,64>", "conv3x3<16x16,128>"],
-    # launch_conv3x3, otherwise: c3_tile_w == 16 -> launch_c3w<BN, GN>, else launch_c3<8, 8, BN, GN>; BN from the same function
+    # plan_conv, otherwise: c3_tile (conv_route.hip) picks 8x16 -> launch_c3w<BN, GN> or 8x8 -> launch_c3<8, 8, BN, GN> and BN
     "launch_conv3x3": _both(*[f"conv3x3<{t},{bn}" for t in ("8x16", "8x8") for bn in (32, 64, 128, 160)]),
-    # launch_igemm -> gemm_dma_eligible -> launch_gemm_dma (kernels_gemm.hip)
+    # plan_conv -> gemm_dma_eligible, gemm_dma_tile -> launch_gemm_dma (kernels_gemm.hip)
     "launch_gemm_dma": [f"gemm_dma<{bm},{bn}>" for bm, bn in ((128, 128), (128, 64), (64, 64))],
-    # launch_igemm -> gemm_dma_eligible and w_frag and gemm_df_selected -> launch_gemm_df (kernels_gemm_df.hip)
+    # plan_conv -> gemm_dma_eligible and gemm_df_selected -> launch_gemm_df (kernels_gemm_df.hip)
     "launch_gemm_df": ["gemm_df", "gemm_df<geglu>"],
-    # launch_igemm, otherwise: launch_bmn<BM, BN>(fast) -> launch_cfg<BM, BN, FAST, GN> (kernels_igemm.hip)
+    # plan_conv, otherwise: igemm_tile -> launch_bmn<BM, BN>(fast) -> launch_cfg<BM, BN, FAST, GN> (kernels_igemm.hip)
     "launch_igemm": _both(*[f"igemm<{bm},{bn},{f}" for bm, bn in ((128, 128), (128, 64), (64, 64)) for f in ("fast", "gen")]),
     # ldiff_op_ln_linear -> launch_lngemm (kernels_gemm_ast.hip)
     "launch_lngemm": ["lngemm<320>", "lngemm<320,geglu>"],

@@ -411,8 +411,8 @@ def test_conv_explicit_split_counts(lib, name, splitk):
 @pytest.mark.parametrize("silu", [0, 1])
 def test_narrow_conv_tap_folded_against_the_lds_image_kernel(lib, silu):
     """conv_out of the VAE decoder (128 -> 3, GroupNorm prologue): the tap-folded kernel (taps as output columns of one narrow GEMM over the halo
-    pixels, then a gather) against torch AND against the LDS-image kernel it replaces (LDIFF_CONV3X3_NARROW_FOLD=0 in a child process is not
-    needed: n_real = 0 keeps the launch on the old kernel) -- same operands, a different fp32 summation order: equal to 1e-5 of the output range."""
+    pixels, then a gather) against torch AND against the LDS-image kernel it replaces (n_real = 0 keeps the launch on that kernel) -- same
+    operands, a different fp32 summation order: equal to 1e-5 of the output range."""
     g = torch.Generator().manual_seed(11 + silu)
     B, Cc, H, W, Cout = 3, 128, 40, 56, 3
     x = torch.randn((B, Cc, H, W), generator=g)
