@@ -29,6 +29,9 @@
  *       (b) at the latest by the NEXT ldiff_unet_forward / ldiff_vae_encode / ldiff_vae_decode / ldiff_sample on the handle, at entry, for work that has
  *           completed by then (no synchronisation; the flag is cleared when reported).
  *     The results of a flagged call are garbage.  LDIFF_TRACE_ABSMAX=1 prints max |activation| per graph stage to stderr (diagnostic; synchronises).
+ *     The cure for the VAE decoder is ldiff_vae_set_range_shift(vae, k): the decoder then stores its residual stream, and every conv output that feeds
+ *     a GroupNorm, times 2^-k, and every decoder GroupNorm uses eps * 4^-k.  GroupNorm is scale-invariant and a power of two is exact, so the shifted
+ *     graph computes the unshifted one's numbers (up to values that fall into fp16's subnormals), in a range 2^k times wider.
  */
 #ifndef LDIFF_H
 #define LDIFF_H
@@ -37,7 +40,7 @@
 extern "C" {
 #endif
 
-#define LDIFF_VERSION 160 /* 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
+#define LDIFF_VERSION 170 /* 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
 #define LDIFF_MAX_BLOCKS 8
 
 typedef enum { LDIFF_OK = 0, LDIFF_ERR_INVALID = -1, LDIFF_ERR_RUNTIME = -2, LDIFF_ERR_STATE = -3, LDIFF_ERR_NONFINITE = -4 } ldiff_status;
@@ -122,6 +125,11 @@ int ldiff_vae_load(ldiff_vae*, const char* name, const void* host_ptr, int dtype
  * grey level of the fp32 oracle in all three modes -- 6.6 % / 3.5 % / 2.9 % of the pixels differ by one -- and the probe-head
  * masks are identical in all three; modes 1 / 2 cost +20 % / +96 % decode time) */
 int ldiff_vae_set_precision(ldiff_vae*, int encoder_mode, int decoder_mode);
+/* decoder range shift k = 0..16 (default 0; outside: LDIFF_ERR_INVALID), see "Non-finite detection" above: for checkpoints whose decoder activations
+ * pass +-65504.  Decoder only (also the decodes ldiff_sample runs on the side stream); the encoder always runs unshifted.  k costs nothing where
+ * it is not needed beyond the width-changing blocks' shortcut, which then runs as its own launch; large k pushes small activations of a healthy
+ * checkpoint into fp16's subnormals, so use the smallest k that decodes (python: AutoencoderKL.fit_range_shift). */
+int ldiff_vae_set_range_shift(ldiff_vae*, int k);
 int ldiff_vae_missing(ldiff_vae*);
 const char* ldiff_vae_missing_name(ldiff_vae*, int i);
 /* x [B,3,H,W] f32 NCHW -> moments [B, 2*latent, H/8, W/8] f32 NCHW (mean | logvar), i.e. quant_conv(encoder(x)) */
@@ -250,6 +258,9 @@ typedef struct {
   int splitk;                                       /* 0 = the executors' plan (none when `stats` is given: this entry point's historical behaviour); 2..16 = that many K splits
                                                        (tests, timing): fp32 partials + the reduce kernel, which then also emits `stats` in blocks of 32 rows
                                                        (ldiff_op_conv_stats_blocks accounts for it; needs 32 | Hout * Wout).  fp16 output, no GEGLU, no parity-folded upsampling */
+  int out_shift;                                    /* range shift k = 0..16 (0 = none; else LDIFF_ERR_INVALID): y = (sum + bias + temb) * 2^-k + res, res supplied already shifted;
+                                                       hi | lo and `stats` are of that value (ldiff_vae_set_range_shift).  Exact: the k = 0 result times 2^-k wherever it stays
+                                                       out of the fp16 subnormals.  Not with GEGLU; a folded shortcut (sc_x) is refused (LDIFF_ERR_INVALID) */
 } ldiff_conv_args;
 int ldiff_op_conv(const ldiff_conv_args*, void* stream);
 /* row blocks per image the launch would emit statistics for (0 = unsupported for this shape) */

@@ -11,11 +11,13 @@
 const char* ldiff_error_message();
 
 // non-finite detector, reporting rule (b) of include/ldiff.h: an entry point that finds the flag of EARLIER, completed work set reports it once
-static void report_nonfinite(NonFiniteFlag& nf, const char* what) {
+// the VAE's handles add the cure for the decoder (include/ldiff.h "Non-finite detection")
+#define VAE_RANGE_HINT " For the VAE decoder: ldiff_vae_set_range_shift (python: AutoencoderKL.set_range_shift / fit_range_shift) stores its activations times 2^-k."
+static void report_nonfinite(NonFiniteFlag& nf, const char* what, const char* hint = "") {
   LDIFF_CHECK(!nf.test_and_clear(), LDIFF_ERR_NONFINITE,
               "%s: a non-finite activation (fp16 overflow: |x| > 65504, or NaN) was detected in work enqueued earlier on this handle; its results are invalid. "
               "Activations are stored as fp16 in every precision mode (set_precision 1 / 2 add mantissa bits, not range): rescale the input / checkpoint, "
-              "and use LDIFF_TRACE_ABSMAX=1 to see which stage overflows", what);
+              "and use LDIFF_TRACE_ABSMAX=1 to see which stage overflows.%s", what, hint);
 }
 
 #define API_BEGIN try {
@@ -144,12 +146,18 @@ int ldiff_vae_set_precision(ldiff_vae* v, int encoder_mode, int decoder_mode) {
   v->prec_enc = encoder_mode; v->prec_dec = decoder_mode;
   API_END
 }
+int ldiff_vae_set_range_shift(ldiff_vae* v, int k) {
+  API_BEGIN
+  LDIFF_CHECK(v && k >= 0 && k <= 16, LDIFF_ERR_INVALID, "vae_set_range_shift: k = %d outside 0..16", k);
+  v->set_range_shift(k);
+  API_END
+}
 int ldiff_vae_missing(ldiff_vae* v) { return v ? v->ws.missing() : -1; }
 const char* ldiff_vae_missing_name(ldiff_vae* v, int i) { return v ? v->ws.missing_name(i) : ""; }
 int ldiff_vae_encode(ldiff_vae* v, const void* x_dev, int B, int H, int W, void* moments_dev, void* stream) {
   API_BEGIN
   LDIFF_CHECK(v, LDIFF_ERR_INVALID, "vae_encode: null handle");
-  report_nonfinite(v->nf, "vae_encode");
+  report_nonfinite(v->nf, "vae_encode", VAE_RANGE_HINT);
   v->encode((const float*)x_dev, B, H, W, (float*)moments_dev, (hipStream_t)stream);
   API_END
 }
@@ -157,7 +165,7 @@ int ldiff_vae_decode(ldiff_vae* v, const void* z_dev, int B, int h, int w, float
                      void* luma_u8, int n_slots, int slot, void* stream) {
   API_BEGIN
   LDIFF_CHECK(v, LDIFF_ERR_INVALID, "vae_decode: null handle");
-  report_nonfinite(v->nf, "vae_decode");
+  report_nonfinite(v->nf, "vae_decode", VAE_RANGE_HINT);
   v->wait_side((hipStream_t)stream);   // a sampler with a deferred join may still be decoding on the side stream (same workspace)
   v->decode((const float*)z_dev, B, h, w, z_scale, (float*)sample_nchw, (float*)image_nhwc, (uint8_t*)rgb_u8, (uint8_t*)luma_u8, n_slots, slot,
             (hipStream_t)stream);
@@ -169,7 +177,7 @@ int ldiff_vae_check_finite(ldiff_vae* v, void* stream) {
   HIP_CHECK(hipSetDevice(v->device));
   HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
   if (v->side_stream) HIP_CHECK(hipStreamSynchronize(v->side_stream));
-  report_nonfinite(v->nf, "vae_check_finite");
+  report_nonfinite(v->nf, "vae_check_finite", VAE_RANGE_HINT);
   API_END
 }
 void ldiff_vae_destroy(ldiff_vae* v) {
@@ -474,7 +482,7 @@ int ldiff_pipeline_check_finite(ldiff_pipeline* p, void* stream) {
   LDIFF_CHECK(!bad_u && !bad_v, LDIFF_ERR_NONFINITE,
               "pipeline_check_finite: a non-finite activation (fp16 overflow: |x| > 65504, or NaN) was detected in the %s graph; the results of that call are invalid. "
               "Activations are stored as fp16 in every precision mode (set_precision 1 / 2 add mantissa bits, not range): rescale the input / checkpoint, "
-              "and use LDIFF_TRACE_ABSMAX=1 to see which stage overflows", bad_u && bad_v ? "UNet and VAE" : bad_u ? "UNet" : "VAE");
+              "and use LDIFF_TRACE_ABSMAX=1 to see which stage overflows.%s", bad_u && bad_v ? "UNet and VAE" : bad_u ? "UNet" : "VAE", bad_v ? VAE_RANGE_HINT : "");
   API_END
 }
 void ldiff_pipeline_destroy(ldiff_pipeline* p) {
@@ -525,6 +533,7 @@ static void conv_args_to_params(const ldiff_conv_args* a, ConvParams& p) {
   p.lo8_slab0 = a->lo8_slab0; p.lo8_sa = (const int*)a->lo8_scale; p.lo8_sb = a->lo8_slab0 ? 127 - LO8_SHIFT : 0;
   p.df_force = a->gemm_df;
   p.xs = (const f16*)a->sc_x; p.Cs = a->sc_x ? a->sc_C : 0; p.lds = a->sc_x ? a->sc_ld : 0;
+  p.out_shift = a->out_shift;   // (plan_conv checks 0..16)
 }
 int ldiff_op_conv(const ldiff_conv_args* a, void* stream) {
   API_BEGIN

@@ -99,6 +99,10 @@ struct ConvParams {
   // weights behind the nine taps in w_frag (launch_pack_frag_weights_sc), the two biases summed by the caller.  No residual then.
   const f16* xs = nullptr; int Cs = 0, lds = 0;
   int df_force = 0;   // dataflow GEMM (gemm_df_selected): 0 = by the unit list, -1 = never, 1 = wherever eligible, 16 mt + ntw = with that unit shape (ldiff_conv_args.gemm_df)
+  // Range shift of the output (0..16; 0 = none): the epilogue computes v = (sum + bias [+ temb]) * 2^-out_shift, THEN adds the residual, which the caller
+  // supplies already shifted; the stored halves and the fused statistics are of that v.  A power of two is exact, so the result is the unshifted one
+  // times 2^-out_shift bit for bit wherever it stays out of the fp16 subnormals (the VAE decoder's range shift, DESIGN.md section 3 "Range")
+  int out_shift = 0;
 };
 constexpr int LO8_SHIFT = 15;   // lo = x - fp16(x) of a GroupNorm + SiLU output: |lo| <= half an fp16 ulp = 2^-7 for |x| < 32, so lo * 2^15 <= 256 stays inside e4m3's 448;
                                 // for |x| in [32, 64) it reaches 512 and saturates at 448 (the correction term is clamped, harmless), as for everything beyond
@@ -400,6 +404,13 @@ __device__ __forceinline__ unsigned dword4(const uint4& v) {
 // ---- epilogue helpers for split tensors (ConvParams::res_lo / y_lo) ----
 __device__ __forceinline__ f16x4 cvt4(const f32x4& v) { return (f16x4){(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]}; }
 __device__ __forceinline__ f32x4 up4(const f16x4& h) { return (f32x4){(float)h[0], (float)h[1], (float)h[2], (float)h[3]}; }
+// 2^-k (ConvParams::out_shift, 0 <= k <= 16) as an fp32, built from the exponent bits: integer work on a uniform value (SALU), exactly 1.0f for k = 0
+__device__ __forceinline__ float shift_scale(int k) { return __builtin_bit_cast(float, (127 - k) << 23); }
+// The statistics operand of a SPLIT output (whose statistics are taken of the fp32 value v, not of the stored hi half): v itself, unless hi rounds
+// to +-inf -- |v| >= 65520, the midpoint between fp16's largest finite value and the next power of two (round to nearest even) -- then NaN, so that
+// the finalize kernel flags the overflow the stored tensor carries.  Finite results are bit-identical; a compare and a select, no extra register.
+__device__ __forceinline__ float split_stat(float v) { return __builtin_fabsf(v) < 65520.0f ? v : __builtin_bit_cast(float, 0x7fc00000); }
+__device__ __forceinline__ f32x4 split_stat4(const f32x4& v) { return (f32x4){split_stat(v[0]), split_stat(v[1]), split_stat(v[2]), split_stat(v[3])}; }
 // sum over the 16 lanes that share lane>>4 (one MFMA accumulator row group), by DPP (no LDS crossbar traffic)
 __device__ __forceinline__ float row16_sum(float v) {
   v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]

@@ -109,6 +109,7 @@ bool conv_lo8_enabled() {
 
 ConvPlan plan_conv(ConvParams& p, const ConvAsk& ask) {
   ConvPlan pl;
+  LDIFF_CHECK(p.out_shift >= 0 && p.out_shift <= 16, LDIFF_ERR_INVALID, "conv: range shift %d outside 0..16", p.out_shift);
   ConvParams q = p;   // the launch as the predicates see it
   // LDIFF_GEMM_DF: 0 = no dataflow GEMM, 1 (default) = where its unit list fills the chip, 2 = every launch it takes (tests, A/B timing);
   // a launch's own ConvParams::df_force comes first

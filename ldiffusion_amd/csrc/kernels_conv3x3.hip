@@ -221,6 +221,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(const ConvParams p) {  
   // All global loads of the epilogue (bias, time embedding, residual) are issued back to back BEFORE any use; a
   // load -> wait -> store chain per 16x16 tile costs a full memory round trip per tile (16-48 us per workgroup).
   const int ncol = n0 + wave_n * (BN / 2) + g * 4;
+  const float osc = shift_scale(p.out_shift);   // ConvParams::out_shift
   f32x4 bt[NT];
 #pragma unroll
   for (int a = 0; a < NT; ++a) {
@@ -261,7 +262,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(const ConvParams p) {  
     for (int a = 0; a < NT; ++a) {
       const int n = ncol + a * 16;
       if (n >= p.N) continue;
-      f32x4 v = acc[a][m] + bt[a];
+      f32x4 v = (acc[a][m] + bt[a]) * osc;   // range shift before the (pre-shifted) residual
       if (p.res) { v += up4(rr[m][a]); if (p.res_lo) v += up4(rl[m][a]); }
       if (p.out_f32) {
         *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.y) + mrow[m] * p.ldy + n) = v;
@@ -269,7 +270,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(const ConvParams p) {  
         const f16x4 o = cvt4(v);
         *reinterpret_cast<f16x4*>(reinterpret_cast<f16*>(p.y) + mrow[m] * p.ldy + n) = o;
         if (p.y_lo) *reinterpret_cast<f16x4*>(reinterpret_cast<f16*>(p.y) + mrow[m] * p.ldy + p.y_lo + n) = cvt4(v - up4(o));
-        if (p.stats) acc[a][m] = p.y_lo ? v : up4(o);   // what the consumer will read (hi + lo ~ v for a split tensor)
+        if (p.stats) acc[a][m] = p.y_lo ? split_stat4(v) : up4(o);   // what the consumer will read (hi + lo ~ v for a split tensor)
       }
     }
   }
@@ -619,6 +620,7 @@ __global__ __launch_bounds__(256, BN > 128 ? 1 : 2) void conv3x3w_kernel(const C
   // All global loads of the epilogue (bias, time embedding, residual) are issued back to back BEFORE any use; a
   // load -> wait -> store chain per 16x16 tile costs a full memory round trip per tile (16-48 us per workgroup).
   const int ncol = n0 + wave_n * (BN / 2) + g * 4;
+  const float osc = shift_scale(p.out_shift);   // ConvParams::out_shift
   f32x4 bt[NT];
 #pragma unroll
   for (int a = 0; a < NT; ++a) {
@@ -669,10 +671,10 @@ __global__ __launch_bounds__(256, BN > 128 ? 1 : 2) void conv3x3w_kernel(const C
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const int m = mp + h;
-          f32x4 v = acc[a][m] + bt[a];
+          f32x4 v = (acc[a][m] + bt[a]) * osc;   // range shift before the (pre-shifted) residual
           if (p.res) { v += up4(rr[m][a]); if (p.res_lo) v += up4(rl[m][a]); }
           const f16x4 o = cvt4(v);
-          if (p.stats) acc[a][m] = p.y_lo ? v : up4(o);   // what the consumer will read (hi + lo ~ v for a split tensor)
+          if (p.stats) acc[a][m] = p.y_lo ? split_stat4(v) : up4(o);   // what the consumer will read (hi + lo ~ v for a split tensor)
           pq[h] = __builtin_bit_cast(uint2, o);
           pl[h] = __builtin_bit_cast(uint2, cvt4(v - up4(o)));
         }
@@ -695,7 +697,7 @@ __global__ __launch_bounds__(256, BN > 128 ? 1 : 2) void conv3x3w_kernel(const C
     for (int a = 0; a < NT; ++a) {
       const int n = ncol + a * 16;
       if (n >= p.N) continue;
-      f32x4 v = acc[a][m] + bt[a];
+      f32x4 v = (acc[a][m] + bt[a]) * osc;   // range shift before the (pre-shifted) residual
       if (p.res) { v += up4(rr[m][a]); if (p.res_lo) v += up4(rl[m][a]); }
       if (p.out_f32) {
         *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.y) + mrow[m] * p.ldy + n) = v;
@@ -703,7 +705,7 @@ __global__ __launch_bounds__(256, BN > 128 ? 1 : 2) void conv3x3w_kernel(const C
         const f16x4 o = cvt4(v);
         *reinterpret_cast<f16x4*>(reinterpret_cast<f16*>(p.y) + mrow[m] * p.ldy + n) = o;
         if (p.y_lo) *reinterpret_cast<f16x4*>(reinterpret_cast<f16*>(p.y) + mrow[m] * p.ldy + p.y_lo + n) = cvt4(v - up4(o));
-        if (p.stats) acc[a][m] = p.y_lo ? v : up4(o);   // what the consumer will read
+        if (p.stats) acc[a][m] = p.y_lo ? split_stat4(v) : up4(o);   // what the consumer will read
       }
     }
   }
@@ -777,7 +779,7 @@ __global__ __launch_bounds__(256, BN > 128 ? 1 : 2) void conv3x3w_kernel(const C
 }
 
 
-// split-K reduction + epilogue: y[m, n..n+3] = sum_s ws[s][m][n..] + bias + temb + res
+// split-K reduction + epilogue: y[m, n..n+3] = (sum_s ws[s][m][n..] + bias + temb) * 2^-out_shift + res
 // One row's four columns: every partial (and the epilogue's operands) is loaded BEFORE the first add -- as a plain `for s: v += load` the compiler waits
 // for each load in turn, S dependent memory round trips per thread (14.6 us per launch on 40 launches of a UNet pass, round 5); the sum order is s = 0, 1, ...
 constexpr int SPLITK_MAX = 16;
@@ -799,18 +801,20 @@ __device__ __forceinline__ f32x4 splitk_row(const ConvParams& p, long long m, in
   for (int s = 0; s < SM; ++s) if (s < S) v += part[s];
   if (p.bias) { v[0] += tb.x; v[1] += tb.y; v[2] += tb.z; v[3] += tb.w; }
   if (p.temb) { v[0] += tt.x; v[1] += tt.y; v[2] += tt.z; v[3] += tt.w; }
+  v *= shift_scale(p.out_shift);   // range shift: after the partials are summed, before the (pre-shifted) residual
   if (p.res) {
     v += up4(rh);
     if (p.res_lo) v += up4(rl);
   }
   return v;
 }
-// stores the row's four columns; returns what the consumer will read (the statistics are of THAT: hi + lo ~ v for a split tensor, else the fp16 value)
+// stores the row's four columns; returns what the consumer will read (the statistics are of THAT: hi + lo ~ v for a split tensor -- NaN where hi overflowed,
+// split_stat4 -- else the fp16 value)
 __device__ __forceinline__ f32x4 splitk_store(const ConvParams& p, long long m, int n, const f32x4& v) {
   if (p.out_f32) { *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.y) + m * p.ldy + n) = v; return v; }
   const f16x4 o = cvt4(v);
   *reinterpret_cast<f16x4*>(reinterpret_cast<f16*>(p.y) + m * p.ldy + n) = o;
-  if (p.y_lo) { *reinterpret_cast<f16x4*>(reinterpret_cast<f16*>(p.y) + m * p.ldy + p.y_lo + n) = cvt4(v - up4(o)); return v; }
+  if (p.y_lo) { *reinterpret_cast<f16x4*>(reinterpret_cast<f16*>(p.y) + m * p.ldy + p.y_lo + n) = cvt4(v - up4(o)); return split_stat4(v); }
   return up4(o);
 }
 template <int SM>

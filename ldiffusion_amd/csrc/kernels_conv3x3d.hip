@@ -589,6 +589,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_kernel(const ConvParams p, co
     while (flags_min_now(cflags_all) < slabs_done) { DACC(8, 1); }
   };
   auto stage_tile = [&](int i, unsigned hb_last) __attribute__((always_inline)) {   // straight-line: the next unit's weights are in flight across it
+    if (!UPS && p.out_shift) {   // range shift (ConvParams::out_shift; never on an upsampling unit): the sums start at bias + temb, so this is (sum + bias + temb) * 2^-k; a uniform branch, nothing at k = 0
+      const float osc = shift_scale(p.out_shift);
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int m = 0; m < 8; ++m) acc[a][m] *= osc;
+    }
     static_for<0, 4>([&](auto ac) {
       constexpr int a = decltype(ac)::value;
       const int idx = a * 4 + wave;
@@ -932,6 +939,9 @@ bool conv3x3d_selected(const ConvParams& p) {
     if (p.Hout % 16 != 0 || p.Wout % 16 != 0 || p.Hin != p.Hout || p.Win != p.Wout) return false;
   }
   if (p.out_f32 || p.y_lo || p.res_lo || (p.ldy & 7) || (p.res && (p.ld_res & 7))) return false;
+  // a folded shortcut sums W2 a (normalised operand) and Wsc xs (the range-shifted stream) in one accumulator: under a range shift the two would need
+  // different scales, so the executor's two-launch form runs instead
+  if (p.xs && p.out_shift) return false;
   if (p.xs && (p.res || p.Cs % 64 != 0 || p.Cs <= 0 || ((p.lds ? p.lds : p.Cs) & 7) || (long long)p.B * p.Hin * p.Win * (p.lds ? p.lds : p.Cs) * 2 >= (1LL << 31))) return false;
   const long long px = (long long)p.B * p.Hin * p.Win;
   if (px * (p.ld1 ? p.ld1 : p.C1) * 2 >= (1LL << 31) || (long long)p.M * p.ldy * 2 >= (1LL << 31) || (p.res && (long long)p.M * p.ld_res * 2 >= (1LL << 31))) return false;

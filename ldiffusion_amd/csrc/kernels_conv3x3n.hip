@@ -384,7 +384,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3nt_kernel(const ConvParams p, c
 bool conv3x3n_selected(const ConvParams& p) {
   const int Cin = p.C1 + p.C2;
   return p.N == 4 && p.Nrows >= 4 && p.ups == 0 && !p.w_par && !p.res && !p.temb && !p.stats && p.splitk <= 1 && !p.y_lo && !p.geglu &&
-         p.w_bstride == 0 && Cin <= 512 && p.ldy % 4 == 0 && p.Wout >= 16 && p.Hout >= 8;
+         p.w_bstride == 0 && Cin <= 512 && p.ldy % 4 == 0 && p.Wout >= 16 && p.Hout >= 8 &&
+         p.out_shift == 0;   // (never asked to shift: the VAE's conv_out reads a normalised operand)
 }
 
 // the tap-folded form: at most three real output channels (27 of the 32 columns), one source of 128 channels (weights in registers), no zero

@@ -307,6 +307,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3p_kernel(const ConvParams p, co
       for (int m = 0; m < MT; ++m) { acc[a0][m] = b0 + t0; acc[a0 + 1][m] = b1 + t1; }
     });
   };
+  // Range shift (ConvParams::out_shift = k): the residual is added into the sums before the tile's last MFMA steps, so it cannot follow the scale; it
+  // goes in times 2^k instead (exact: it was supplied shifted by 2^-k), and the epilogue scales the finished sums by 2^-k -- the same fp32 operations
+  // as at k = 0, then one exact power of two.  rsc = 1 at k = 0 (the add becomes an fma with 1.0: the same rounding); it is rebuilt from the
+  // kernel argument where it is used (scalar work), so that nothing stays live across the main loop.
   f16x4 rr[MT / 2][NT];     // residual operand in flight: two of the wave's four pixel rows, hi or lo half
   auto load_res = [&](const TileC& t, int mh, int lo_off) __attribute__((always_inline)) {
     const int ncol = t.n0 + wave_n * (BN / 2) + opaque(g) * 4;
@@ -322,10 +326,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3p_kernel(const ConvParams p, co
   };
   auto add_res = [&](auto mhc) __attribute__((always_inline)) {
     constexpr int mh = decltype(mhc)::value;
+    const float rsc = __builtin_bit_cast(float, (127 + p.out_shift) << 23);
 #pragma unroll
     for (int m = 0; m < MT / 2; ++m)
 #pragma unroll
-      for (int a = 0; a < NT; ++a) acc[a][mh * 2 + m] += up4(rr[m][a]);
+      for (int a = 0; a < NT; ++a) acc[a][mh * 2 + m] = up4(rr[m][a]) * rsc + acc[a][mh * 2 + m];
   };
   // lane holds y[pixel = column][n = 4g + r], complete in acc.  16-byte stores after one v_permlane16_swap per dword (conv3x3w_kernel);
   // the launcher guarantees their alignment (N, ldy, y_lo multiples of 8, fp16 output).
@@ -347,6 +352,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3p_kernel(const ConvParams p, co
     const unsigned off0 = (pix0 * (unsigned)p.ldy + (unsigned)nb0) * 2u;
     const unsigned rstride = (unsigned)((PAR ? 2 : 1) * p.Wout * p.ldy) * 2u;
     const bool okx = txs < Wt;
+    if (p.out_shift) {   // (a uniform branch: nothing at k = 0)
+      const float osc = shift_scale(p.out_shift);
+#pragma unroll
+      for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int a = 0; a < NT; ++a) acc[a][m] *= osc;
+    }
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
       const bool ok = okx && ty0 + m < Ht;
@@ -371,6 +383,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3p_kernel(const ConvParams p, co
           auto l1 = __builtin_amdgcn_permlane16_swap(e0.y, e1.y, false, false);
           __builtin_amdgcn_raw_buffer_store_b128((u32x4){l0[0], l1[0], l0[1], l1[1]}, yrsrc, voff + (a * 32 + p.y_lo * 2), 0, 0);
           asm volatile("s_nop 1" ::: "memory");
+          if constexpr (has_st) { acc[a][m] = split_stat4(acc[a][m]); acc[a + 1][m] = split_stat4(acc[a + 1][m]); }   // NaN where hi overflowed
         } else if constexpr (has_st) {   // statistics: of what the consumer will read (hi + lo ~ the fp32 sums for a split tensor)
           acc[a][m] = up4(o[0]); acc[a + 1][m] = up4(o[1]);
         }

@@ -277,6 +277,7 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const ConvParams p) {
     }
     return;
   }
+  const float osc = shift_scale(p.out_shift);   // ConvParams::out_shift
   // 16-byte stores (see kernels_conv3x3.hip): one v_permlane16_swap per dword between the packed values of two m-tiles
   // leaves even-g lanes with channels 4g..4g+7 of the first tile's row and odd-g lanes with 4(g-1)..4(g-1)+7 of the second's
   if (!p.out_f32 && (p.N & 7) == 0 && (p.ldy & 7) == 0 && (p.y_lo & 7) == 0) {
@@ -289,10 +290,10 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const ConvParams p) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const int m = mp + h;
-          f32x4 v = acc[a][m] + bb[a];
+          f32x4 v = (acc[a][m] + bb[a]) * osc;   // range shift before the (pre-shifted) residual
           if (p.res) { v += up4(rr[m][a]); if (p.res_lo) v += up4(rl[m][a]); }
           const f16x4 o = cvt4(v);
-          if (p.stats) acc[a][m] = p.y_lo ? v : up4(o);
+          if (p.stats) acc[a][m] = p.y_lo ? split_stat4(v) : up4(o);
           pq[h] = __builtin_bit_cast(uint2, o);
           pl[h] = __builtin_bit_cast(uint2, cvt4(v - up4(o)));
         }
@@ -315,7 +316,7 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const ConvParams p) {
     for (int a = 0; a < NT; ++a) {
       const int n = ncol + a * 16;
       if (n >= p.N) continue;
-      f32x4 v = acc[a][m] + bb[a];
+      f32x4 v = (acc[a][m] + bb[a]) * osc;   // range shift before the (pre-shifted) residual
       if (p.res) { v += up4(rr[m][a]); if (p.res_lo) v += up4(rl[m][a]); }
       if (p.out_f32) {
         *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.y) + (long long)mrow[m] * p.ldy + n) = v;
@@ -323,7 +324,7 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const ConvParams p) {
         const f16x4 o = cvt4(v);
         *reinterpret_cast<f16x4*>(reinterpret_cast<f16*>(p.y) + (long long)mrow[m] * p.ldy + n) = o;
         if (p.y_lo) *reinterpret_cast<f16x4*>(reinterpret_cast<f16*>(p.y) + (long long)mrow[m] * p.ldy + p.y_lo + n) = cvt4(v - up4(o));
-        if (p.stats) acc[a][m] = p.y_lo ? v : up4(o);
+        if (p.stats) acc[a][m] = p.y_lo ? split_stat4(v) : up4(o);
       }
     }
   }
@@ -371,7 +372,7 @@ void launch_g(const ConvParams& p, hipStream_t s) {
 
 bool gemm_dma_eligible(const ConvParams& p) {
   if (p.w_bstride > 0 && ((p.Hout * p.Wout) % 64 != 0 || p.stats)) return false;   // a tile must lie inside one image
-  if (p.geglu && (p.N % 32 != 0 || (p.ldy & 7) != 0 || p.res || p.out_f32 || p.stats || p.y_lo)) return false;
+  if (p.geglu && (p.N % 32 != 0 || (p.ldy & 7) != 0 || p.res || p.out_f32 || p.stats || p.y_lo || p.out_shift)) return false;   // (the GEGLU epilogue takes no range shift)
   const int pitch1 = p.ld1 ? p.ld1 : p.C1, pitch2 = p.ld2 ? p.ld2 : p.C2, pmax = pitch1 > pitch2 ? pitch1 : pitch2;
   return p.ks == 1 && p.stride == 1 && p.ups == 0 && p.pad_t == 0 && p.pad_l == 0 && !p.gn_scale && !p.temb && p.K % 64 == 0 && p.C1 % 64 == 0 &&
          pitch1 % 8 == 0 && pitch2 % 8 == 0 &&

@@ -320,6 +320,11 @@ __global__ __launch_bounds__(512, 2) void gemm_df_kernel(const ConvParams p, con
           } else {
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = U[it][e >> 2][e & 3] + Bv[e >> 2][e & 3];
+            if (p.out_shift) {   // range shift before the (pre-shifted) residual (ConvParams::out_shift; a uniform branch, nothing at k = 0)
+              const float osc = shift_scale(p.out_shift);
+#pragma unroll
+              for (int e = 0; e < 8; ++e) v[e] *= osc;
+            }
           }
           if constexpr (RES) {
 #pragma unroll
@@ -347,13 +352,13 @@ __global__ __launch_bounds__(512, 2) void gemm_df_kernel(const ConvParams p, con
           __builtin_amdgcn_raw_buffer_store_b128(oh, yrs, yoff[it], 0, 0);
           if constexpr (OUT_SPLIT) __builtin_amdgcn_raw_buffer_store_b128(ol, yrs, yoff[it] == (int)F_OOR ? (int)F_OOR : yoff[it] + p.y_lo * 2, 0, 0);
           if constexpr (STATS) {
-            // what gemm_dma_kernel sums: the fp32 value of a split output, the rounded value of a plain one; rows beyond M count nothing
+            // what gemm_dma_kernel sums: the fp32 value of a split output (NaN where its hi half overflowed), the rounded value of a plain one; rows beyond M count nothing
             const bool rok = yoff[it] != (int)F_OOR;
 #pragma unroll
             for (int d = 0; d < 4; ++d) {
               const unsigned hd = oh[d];
               const f16x2 h = __builtin_bit_cast(f16x2, hd);
-              const float f0 = rok ? (OUT_SPLIT ? v[2 * d] : (float)h[0]) : 0.f, f1 = rok ? (OUT_SPLIT ? v[2 * d + 1] : (float)h[1]) : 0.f;
+              const float f0 = rok ? (OUT_SPLIT ? split_stat(v[2 * d]) : (float)h[0]) : 0.f, f1 = rok ? (OUT_SPLIT ? split_stat(v[2 * d + 1]) : (float)h[1]) : 0.f;
               float (&xs)[16] = x16[it & 1];
               xs[2 * d] += f0; xs[2 * d + 1] += f1;
               xs[8 + 2 * d] = __builtin_fmaf(f0, f0, xs[8 + 2 * d]); xs[8 + 2 * d + 1] = __builtin_fmaf(f1, f1, xs[8 + 2 * d + 1]);
@@ -683,7 +688,7 @@ bool gemm_df_selected(const ConvParams& p) {
   if (p.stats && (p.geglu || (p.Hout * p.Wout) % 32 != 0 || p.stats_R != (p.Hout * p.Wout) / 32)) return false;
   if (p.C1 % 64 != 0 || p.C2 % 64 != 0 || p.Nrows % 16 != 0 || p.Nrows < p.N) return false;
   if ((p.N & 7) || (p.ldy & 7) || (p.y_lo & 7) || (p.res && ((p.ld_res & 7) || (p.res_lo & 7)))) return false;
-  if (p.geglu && (p.N % 64 != 0 || p.res || p.y_lo)) return false;
+  if (p.geglu && (p.N % 64 != 0 || p.res || p.y_lo || p.out_shift)) return false;   // (the GEGLU epilogue takes no range shift)
   if ((long long)p.M * p.ldy * 2 >= (1LL << 31) || (p.res && (long long)p.M * p.ld_res * 2 >= (1LL << 31)) || (long long)p.Nrows * p.K * 2 >= (1LL << 31)) return false;
   if (p.df_force > 0) return true;
   // fused statistics: built and bit-identical to gemm_dma's, but with two epilogue waves summing beside their stores the launch takes twice

@@ -195,6 +195,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const ConvParams p) {   /
     }
     return;
   }
+  const float osc = shift_scale(p.out_shift);   // ConvParams::out_shift
   f32x4 bb[NT];
 #pragma unroll
   for (int a = 0; a < NT; ++a) {
@@ -242,6 +243,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const ConvParams p) {   /
       if (n >= p.N) continue;
       f32x4 v = acc[a][b] + bb[a];
       if (p.temb) v += tt[a];
+      v *= osc;   // range shift before the (pre-shifted) residual
       if (p.res) { v += up4(rr[b][a]); if (p.res_lo) v += up4(rl[b][a]); }
       if (p.out_f32) {
         *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.y) + m * p.ldy + n) = v;
@@ -249,7 +251,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const ConvParams p) {   /
         const f16x4 o = cvt4(v);
         *reinterpret_cast<f16x4*>(reinterpret_cast<f16*>(p.y) + m * p.ldy + n) = o;
         if (p.y_lo) *reinterpret_cast<f16x4*>(reinterpret_cast<f16*>(p.y) + m * p.ldy + p.y_lo + n) = cvt4(v - up4(o));
-        if (p.stats) acc[a][b] = p.y_lo ? v : up4(o);
+        if (p.stats) acc[a][b] = p.y_lo ? split_stat4(v) : up4(o);
       }
     }
   }

@@ -1,6 +1,7 @@
 // Host-side executors: weight store, op helpers over the device arena, UNet / VAE graphs.
 // Internal to libldiff_hip.so.
 #pragma once
+#include <cmath>
 #include <functional>
 #include <map>
 #include <memory>
@@ -50,6 +51,8 @@ struct MatW {   // [Nrows][K] fp16 K-major + fp32 bias
   mutable Derived gfrag_dup;      //   the same of the duplicated (split-operand) matrix; key = C1 of a concat
   mutable Derived tiled;          //   panel-tiled copy for the LayerNorm-fused GEMM (kernels_gemm_ast.hip)
   mutable Derived lo8;            //   split operand with an fp8 lo half: [Nrows][taps][Cin fp16 | Cin e4m3] + one int (the E8M0 scale operand) behind it
+  mutable float* b_shift = nullptr;           //   the bias times 2^-k for a launch whose input is the range-shifted stream (Exec::derived_bias_shift)
+  mutable int b_shift_gen = -1, b_shift_k = -1;
 };
 struct NormW { float* g = nullptr; float* b = nullptr; int C = 0; };
 struct GNss { float* scale = nullptr; float* shift = nullptr; };
@@ -118,6 +121,10 @@ struct ConvOpts {
   // the block's 1x1 conv_shortcut folded into this (its second) conv where the dataflow conv3x3 kernel takes the launch (ConvParams::xs): sc_x = the block's
   // input, sc_w = the shortcut's weights; *sc_done says whether the fold happened (else the caller runs the shortcut conv and passes its output as res)
   const Act* sc_x = nullptr; const struct MatW* sc_w = nullptr; bool* sc_done = nullptr;
+  // range shift (ldiff_vae_set_range_shift, DESIGN.md section 3 "Range"): out_shift = k: y = (sum + bias) * 2^-k + res (ConvParams::out_shift), for a
+  // launch whose output joins the shifted stream from a normalised / true-scale input; bias_shift = k: the bias times 2^-k, for a launch whose input IS
+  // the shifted stream (its sum is shifted already)
+  int out_shift = 0, bias_shift = 0;
 };
 
 class Exec {
@@ -131,6 +138,7 @@ class Exec {
   bool short_runs = false;            // this graph runs beside another stream's (ConvParams::short_runs)
   int* nonfinite = nullptr;           // -> the owning handle's sticky non-finite flag (host-mapped; set by the GroupNorm finalize kernels, NonFiniteFlag below)
   const char* trace_tag = nullptr;    // LDIFF_TRACE_ABSMAX=1: name of the graph whose stages trace() reports (diagnostic, synchronises)
+  int range_shift = 0;                // k: this graph's stream is stored times 2^-k (the VAE decoder's Exec only: ldiff_vae_set_range_shift; trace() reports true magnitudes)
   void trace(const char* stage, const Act& a);   // max |value| of a stage's output to stderr when LDIFF_TRACE_ABSMAX is set; otherwise nothing
   ~Exec();
   void ensure_gn_partial(size_t bytes);
@@ -142,6 +150,7 @@ class Exec {
   const f16* derived_frag_sc(const MatW& w, const MatW& sc, const ConvParams& p, const float** bias_sum);   // ... + the folded shortcut
   const f16* derived_tiled(const MatW& w, int N);
   const f16* derived_gfrag(const MatW& w, const f16* src, int K, Derived& d, int key);   // fragment-packed copy of `src` [Nrows][K] for the dataflow GEMM
+  const float* derived_bias_shift(const MatW& w, int k);   // w.b times 2^-k (nullptr without a bias), rebuilt when k or the checkpoint changes
   const f16* derived_lo8(const MatW& w, const int** scale);   // fp8-lo weights of a split operand + the device int holding their E8M0 scale operand
   bool lo8_conv_ok(const MatW& w, const Act& x, bool res, bool split_out) const;   // would conv(w, norm_apply(x) with an fp8 lo half) run on the ping-pong kernel?
   Act norm_apply(const Act& x, const Act* x2, const GNss& g, bool silu, bool split_out, bool lo8 = false);
@@ -257,6 +266,11 @@ struct ldiff_vae {
   void decode(const float* z, int B, int h, int w, float z_scale, float* sample_nchw, float* image_nhwc, uint8_t* rgb, uint8_t* luma,
               int n_slots, int slot, hipStream_t s);
   Act mid_attention(const VaeAttnW& a, const Act& x);
+  // decoder range shift k (0..16): the decoder's residual stream and every conv output that feeds a GroupNorm are stored times 2^-k, its GroupNorms
+  // use eps * 4^-k (DESIGN.md section 3 "Range").  No captured graph holds decoder launches, so nothing is invalidated; the pre-scaled biases are
+  // rebuilt on their next use (Exec::derived_bias_shift)
+  void set_range_shift(int k) { ex_dec.range_shift = k; }
+  float dec_eps() const { return ldexpf(1e-6f, -2 * ex_dec.range_shift); }
 };
 
 struct ldiff_pipeline {

@@ -248,7 +248,11 @@ void Exec::trace(const char* stage, const Act& a) {
   HIP_CHECK(hipMemcpyAsync(&h, d, sizeof(float), hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
   arena.free(d);
-  fprintf(stderr, "[absmax] %-8s %-28s [%d,%d,%d,%d]%s max|x| = %.6g (fp16 limit 65504)\n", trace_tag ? trace_tag : "", stage, a.B, a.H, a.W, a.C, a.split ? " split" : "", (double)h);
+  if (range_shift)   // the stored tensor is x * 2^-k: report the true magnitude, and what is stored against the limit
+    fprintf(stderr, "[absmax] %-8s %-28s [%d,%d,%d,%d]%s max|x| = %.6g (range shift %d: stored x 2^-%d = %.6g, fp16 limit 65504)\n", trace_tag ? trace_tag : "", stage,
+            a.B, a.H, a.W, a.C, a.split ? " split" : "", ldexp((double)h, range_shift), range_shift, range_shift, (double)h);
+  else
+    fprintf(stderr, "[absmax] %-8s %-28s [%d,%d,%d,%d]%s max|x| = %.6g (fp16 limit 65504)\n", trace_tag ? trace_tag : "", stage, a.B, a.H, a.W, a.C, a.split ? " split" : "", (double)h);
 }
 Exec::~Exec() {
   if (gn_partial) (void)hipFree(gn_partial);
@@ -310,6 +314,22 @@ const f16* Exec::derived_dup(const MatW& w, int C1, int C2) {
     w.dup.gen = gen; w.dup.key = C1;
   }
   return w.dup.p;
+}
+// the bias of a launch whose input is the range-shifted stream: b * 2^-k (exact), so that the epilogue's sum + bias is (true sum + b) * 2^-k
+const float* Exec::derived_bias_shift(const MatW& w, int k) {
+  if (!w.b || k == 0) return w.b;
+  const int gen = weights_gen ? *weights_gen : 0;
+  if (!w.b_shift) {
+    void* q = nullptr;
+    HIP_CHECK(hipMalloc(&q, (size_t)w.Nrows * sizeof(float)));
+    owned.push_back(q);
+    w.b_shift = (float*)q;
+  }
+  if (w.b_shift_gen != gen || w.b_shift_k != k) {   // first use, another k, or the checkpoint was reloaded since
+    launch_scale_f32(w.b, w.b_shift, ldexpf(1.0f, -k), w.Nrows, s);
+    w.b_shift_gen = gen; w.b_shift_k = k;
+  }
+  return w.b_shift;
 }
 // split operand with an fp8 lo half (ConvParams::lo8_slab0): per (row, tap) [Cin fp16 | Cin e4m3 of w * 2^sw]; the int behind the matrix is 127 - sw
 const f16* Exec::derived_lo8(const MatW& w, const int** scale) {
@@ -473,7 +493,8 @@ Act Exec::conv(const MatW& w, const Act& x, const Act* x2, const ConvOpts& o) {
   p.w = wsrc; p.Nrows = w.Nrows; p.K = w.ks * w.ks * Cin_eff;
   p.N = o.N_override ? o.N_override : roundup(w.N, 4);
   p.n_real = o.N_override ? 0 : w.N;
-  p.bias = w.b;
+  p.bias = o.bias_shift ? derived_bias_shift(w, o.bias_shift) : w.b;
+  p.out_shift = o.out_shift;
   if (o.gn) { p.gn_scale = o.gn->scale; p.gn_shift = o.gn->shift; p.silu_in = o.silu; }
   p.temb = o.temb; p.ld_temb = o.ld_temb;
   p.M = x.B * p.Hout * p.Wout;
@@ -590,12 +611,15 @@ Act Exec::geglu(const Act& x) {
 //   PREC_STREAM : x / skip / output split; conv1 reads the hi halves (pitch 2C) through the GN prologue, the shortcut conv and the
 //                 residual add see hi + lo.
 //   PREC_FULL   : additionally the normalised operands are materialised split (norm_apply) and both convs run on split operands.
+//   Range shift (range_shift = k > 0, the VAE decoder only): x is stored times 2^-k and so is the output; conv1 and conv2 shift their epilogues
+//   (conv2's residual is shifted already), the shortcut conv reads the shifted x and takes its bias times 2^-k; the caller passes eps * 4^-k.
 Act Exec::resnet(const ResnetW& r, const Act& x, const Act* skip, const float* temb, int ld_temb, int groups, float eps, int prec) {
   const bool st = prec >= PREC_STREAM, full = prec >= PREC_FULL;
+  const int k = range_shift;
   LDIFF_CHECK(r.has_sc || skip == nullptr, LDIFF_ERR_RUNTIME, "resnet: concat input without shortcut conv");
   GNss g1 = gn(x, skip, r.n1, groups, eps);
   ConvOpts o1;
-  o1.temb = temb; o1.ld_temb = ld_temb; o1.want_stats = true;
+  o1.temb = temb; o1.ld_temb = ld_temb; o1.want_stats = true; o1.out_shift = k;
   Act h;
   if (full) {
     Act a = norm_apply(x, skip, g1, true, true, !skip && lo8_conv_ok(r.c1, x, false, true));
@@ -612,9 +636,9 @@ Act Exec::resnet(const ResnetW& r, const Act& x, const Act* skip, const float* t
   Act sc;
   const Act* resp = &x;
   ConvOpts o2;
-  o2.want_stats = true; o2.split_out = st;
+  o2.want_stats = true; o2.split_out = st; o2.out_shift = k;
   Act out;
-  if (r.has_sc && !st && !skip) {
+  if (r.has_sc && !st && !skip && k == 0) {   // (under a range shift the dataflow kernel declines the fold: the two launches below)
     // plain graph (the VAE decoder's two width-changing blocks): try the shortcut as extra centre-tap slabs of conv2 on the dataflow kernel -- no
     // 1x1 launch, no round trip of its output through memory, the sum in fp32.  Where the kernel does not take the launch: the two-launch form below.
     bool folded = false;
@@ -629,7 +653,7 @@ Act Exec::resnet(const ResnetW& r, const Act& x, const Act* skip, const float* t
   }
   if (r.has_sc) {
     ConvOpts os;
-    os.split_in = st; os.split_out = st;
+    os.split_in = st; os.split_out = st; os.bias_shift = k;
     sc = conv(r.sc, x, skip, os);
     resp = &sc;
   }
@@ -1166,7 +1190,7 @@ void ldiff_vae::build() {
 Act ldiff_vae::mid_attention(const VaeAttnW& a, const Act& x) {
   const int C = a.C, L = x.H * x.W;
   const bool st = prec() >= PREC_STREAM, full = prec() >= PREC_FULL;
-  GNss g = ex().gn(x, nullptr, a.gn, cfg.norm_num_groups, 1e-6f);
+  GNss g = ex().gn(x, nullptr, a.gn, cfg.norm_num_groups, ldexpf(1e-6f, -2 * ex().range_shift));   // (x stored times 2^-k: eps times 4^-k)
   Act qkv;
   if (full) {   // normalised operand materialised split, q/k/v on the split operand
     Act xn = ex().norm_apply(x, nullptr, g, false, true);
@@ -1189,7 +1213,7 @@ Act ldiff_vae::mid_attention(const VaeAttnW& a, const Act& x) {
   launch_attention(ap, ex().s);
   ex().release(qkv);
   ConvOpts oo;
-  oo.res = &x; oo.want_stats = true; oo.split_out = st;
+  oo.res = &x; oo.want_stats = true; oo.split_out = st; oo.out_shift = ex().range_shift;   // to_out joins the (shifted) stream
   Act out = ex().conv(a.out, o, nullptr, oo);
   ex().release(o);
   return out;
@@ -1280,7 +1304,11 @@ void ldiff_vae::decode(const float* z, int B, int h, int w, float z_scale, float
   ex().arena.reserve(mult * ((size_t)B * H * W * boc[0] * 2 * 10 + (size_t)B * h * w * Cmax * 2 * 24) + (64u << 20));
   for (int i = 0; i < nb; ++i) ex().ensure_gn_partial(gn_partial_bytes(B, (H >> i) * (W >> i), boc[std::min(i + 1, nb - 1)]));
   ex().ensure_gn_partial(gn_partial_bytes(B, h * w, Cmax));
-  auto rb = [&](const ResnetW& r, const Act& xin) { return ex().resnet(r, xin, nullptr, nullptr, 0, cfg.norm_num_groups, 1e-6f, pr); };
+  // range shift k (set_range_shift): conv_in's output and everything downstream of it up to conv_norm_out is stored times 2^-k, the GroupNorms use
+  // eps * 4^-k (DESIGN.md section 3 "Range"); post_quant_conv and conv_out are unchanged
+  const int k = ex().range_shift;
+  const float eps = dec_eps();
+  auto rb = [&](const ResnetW& r, const Act& xin) { return ex().resnet(r, xin, nullptr, nullptr, 0, cfg.norm_num_groups, eps, pr); };
 
   const long long nz = (long long)B * cfg.latent_channels * h * w;
   float* zs = ex().tmp<float>((size_t)nz);
@@ -1301,7 +1329,7 @@ void ldiff_vae::decode(const float* z, int B, int h, int w, float z_scale, float
   }
   ex().release(z16);
   ConvOpts odi;
-  odi.want_stats = true; odi.split_in = split_first; odi.split_out = st;
+  odi.want_stats = true; odi.split_in = split_first; odi.split_out = st; odi.out_shift = k;
   Act cur = ex().conv(d_conv_in, pq, nullptr, odi);
   ex().release(pq);
   ex().trace("conv_in", cur);
@@ -1315,12 +1343,12 @@ void ldiff_vae::decode(const float* z, int B, int h, int w, float z_scale, float
     for (auto& r : d_res[i]) { snprintf(nm, sizeof(nm), "up_blocks.%d.resnets.%d", i, j++); advance(rb(r, cur), nm); }
     if (i != nb - 1) {
       ConvOpts o;
-      o.ups = 1; o.want_stats = true; o.split_in = st; o.split_out = st;
+      o.ups = 1; o.want_stats = true; o.split_in = st; o.split_out = st; o.bias_shift = k;   // (reads the shifted stream)
       snprintf(nm, sizeof(nm), "up_blocks.%d.upsamplers.0", i);
       advance(ex().conv(d_up[i], cur, nullptr, o), nm);
     }
   }
-  GNss g = ex().gn(cur, nullptr, d_norm_out, cfg.norm_num_groups, 1e-6f);
+  GNss g = ex().gn(cur, nullptr, d_norm_out, cfg.norm_num_groups, eps);
   const int Nst = 4;
   float* o32 = ex().tmp<float>((size_t)B * H * W * Nst);
   const bool want_post = image_nhwc || rgb || luma;

@@ -217,7 +217,7 @@ class _LatentDist:
 
 
 class AutoencoderKL:
-    def __init__(self, cfg: dict, state_dict, device=None):
+    def __init__(self, cfg: dict, state_dict, device=None, range_shift: int = 0):
         _lib.require_gpu()
         cfg = configs.with_defaults(cfg, configs.VAE_DEFAULTS)    # e.g. `scaling_factor` (decode_latents reads vae.config.scaling_factor)
         configs.validate_vae_config(cfg)
@@ -244,13 +244,16 @@ class AutoencoderKL:
             names = [self._lib.ldiff_vae_missing_name(self._h, i).decode() for i in range(min(n, 5))]
             raise RuntimeError(f"{n} VAE tensors missing from the checkpoint, e.g. {names}")
         self._host_sd = {k: v.detach().to("cpu") for k, v in sd.items()}
+        self.range_shift = 0
+        if range_shift:
+            self.set_range_shift(range_shift)
 
     @classmethod
-    def from_pretrained(cls, path, subfolder=None, device=None, **_ignored):
+    def from_pretrained(cls, path, subfolder=None, device=None, range_shift: int = 0, **_ignored):
         if subfolder:
             path = os.path.join(path, subfolder)
         cfg, sd = weights.load_model_dir(path)
-        return cls(cfg, sd, device=device)
+        return cls(cfg, sd, device=device, range_shift=range_shift)
 
     def save_pretrained(self, path):
         weights.save_model_dir(path, self._cfg, self._host_sd)
@@ -261,6 +264,35 @@ class AutoencoderKL:
         _lib.check(self._lib.ldiff_vae_set_precision(self._h, int(encoder), int(decoder)))
         self.precision = (int(encoder), int(decoder))
         return self
+
+    def set_range_shift(self, k: int):
+        """Decoder range shift (include/ldiff.h ldiff_vae_set_range_shift): the decoder stores its activations times 2^-k, for checkpoints whose decoder
+        activations pass fp16's +-65504.  0 <= k <= 16 (else ValueError); the encoder is unaffected.  Kept in `range_shift`; returns self."""
+        _lib.check(self._lib.ldiff_vae_set_range_shift(self._h, int(k)))
+        self.range_shift = int(k)
+        return self
+
+    def fit_range_shift(self, z, z_scale=None, step: int = 2, k_max: int = 16):
+        """Decodes `z` (times z_scale, default 1 / scaling_factor as decode_latents) at k = 0, step, 2 step, ... until check_finite passes, leaves that k
+        set and returns it.  If k_max (0..16) still overflows, the range shift is put back as it was and NonFiniteError is raised."""
+        if step < 1 or not 0 <= k_max <= 16:
+            raise ValueError(f"fit_range_shift: step must be >= 1 and k_max in 0..16 (got step={step}, k_max={k_max})")
+        z_scale = 1.0 / self.config.scaling_factor if z_scale is None else z_scale
+        self.check_finite()   # (earlier work must not be blamed on the first candidate)
+        prev = self.range_shift
+        ks = list(range(0, k_max + 1, step))
+        if ks[-1] != k_max:
+            ks.append(k_max)
+        for i, k in enumerate(ks):
+            self.set_range_shift(k)
+            self._decode(z, z_scale, want_image=True)
+            try:
+                self.check_finite()
+                return k
+            except _lib.NonFiniteError:
+                if i == len(ks) - 1:
+                    self.set_range_shift(prev)
+                    raise
 
     def check_finite(self):
         """Synchronises the current stream (and the decode side stream) and raises NonFiniteError if an encode / decode enqueued so far produced
