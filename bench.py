@@ -10,9 +10,16 @@ here), followed by the mask tail (stand-in linear probe over the per-pixel laten
 for N > 1, the RCCL all-gather that reassembles the masks.  Patches shard across ranks with no data-path collective
 (weak scaling: 8 patches per GPU).  Inputs are resident in HBM when the timed region starts.
 
-Prints ONE JSON line on rank 0 (contract in the task description), including
-  roofline     -- live HIP-event measurement of the dominant kernel over the timed region
-  cpu_baseline -- the CPU oracle (plain-torch fp32 restatement, oracle/) timed on the host cores (rank 0, N=1 only)
+Prints ONE JSON line on rank 0 (contract in the task description).  A plain run sets up, warms up, times the K steps, writes
+--dump-outputs and prints that line, including
+  roofline     -- live HIP-event measurement of the dominant kernel over the timed region (the per-kernel table comes from the
+                  last warm-up step; --no-prof drops both)
+--full adds, after the timed steps (none of it changes them):
+  checked, check -- the last timed step against one more step on one stream with one batch in flight, bit for bit, and the
+                  non-finite detector
+  unet_step*   -- the UNet pass alone at B = 8, 2 and 1, hipGraph replay and eager launches (--no-unet-step drops them)
+  sample_b1    -- one patch per call through the whole sampler (rank 0; --no-unet-step drops it)
+  cpu_baseline -- the CPU oracle (plain-torch fp32 restatement, oracle/) timed on the host cores (rank 0, N=1 only; --no-cpu-baseline)
 
 --dump-outputs DIR writes the outputs of the last timed step as DIR/<name>.npy (float32; seeded, fixed inputs: two builds run with the
 same arguments compare output for output).
@@ -49,9 +56,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU oracle timing (rank 0, N=1)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the result check, the UNet-step and one-patch timings\n"
+                    "                    and the CPU baseline (off by default)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle timing (rank 0, N=1)")
     ap.add_argument("--no-prof", action="store_true", help="skip the per-launch HIP-event profile")
-    ap.add_argument("--no-unet-step", action="store_true", help="skip the separate UNet-step timing (used under rocprofv3 so that the\n                    kernel mix of the whole process equals the mix of the timed region)")
+    ap.add_argument("--no-unet-step", action="store_true", help="with --full: skip the separate UNet-step and one-patch timings")
     ap.add_argument("--launch-check", action="store_true", help="rendezvous only (gloo, no GPU): every rank joins, all-reduces its rank and rank 0 prints\n                    {launch_check, n_gpus}; covers the self-launch / env contract on a CPU box")
     ap.add_argument("--no-pipeline", action="store_true", help="one batch in flight: every step joins its own decodes before the next one is enqueued")
     ap.add_argument("--tiny", action="store_true", help="reduced-width graph + 64x64 patches (plumbing check only; not a valid bench line)")
@@ -324,32 +333,33 @@ def main():
     assert masks.shape[0] == total and masks.dtype == torch.uint8
     if args.dump_outputs and rank == 0:   # untimed: the last timed step's masks (all ranks') and sampler outputs (this rank's patches)
         dump_outputs(args.dump_outputs, {"masks": masks, **{k: last_out["out"][k] for k in ("latents", "features", "rgb")}})
-    timed_out = {k: last_out["out"][k].clone() for k in ("features", "latents")}   # of the LAST timed step (this rank's patches); the sampler reuses its buffers
-    feat_crc = None
-    # result check (untimed): the masks of the LAST timed step (two batches in flight, deferred joins, persistent conv kernels on short
-    # runs) against one more step with everything on one stream and one batch in flight -- same inputs, so bit for bit
-    import zlib
-    sampler.set_overlap(0)
-    ref_masks = step()
-    sampler.set_overlap(1)
-    torch.cuda.synchronize()
-    ref_out = last_out["out"]
-    checked = bool(torch.equal(masks, ref_masks)) and all(torch.equal(timed_out[k], ref_out[k]) for k in ("features", "latents"))
-    masks_crc = zlib.crc32(masks.cpu().numpy().tobytes()) & 0xFFFFFFFF
-    # arithmetic regression signals (the stand-in head's masks hardly move with the kernels' rounding; these do): CRC of the uint8 per-pixel
-    # latent vectors and the extreme / mean magnitude of the final latents, rank 0's patches
-    feat_crc = zlib.crc32(timed_out["features"].cpu().numpy().tobytes()) & 0xFFFFFFFF
-    lat_absmax = float(timed_out["latents"].abs().max().item())
-    lat_absmean = float(timed_out["latents"].abs().double().mean().item())
-    sampler.check_finite()    # non-finite detector of both graphs (include/ldiff.h): raises if any step of this run overflowed fp16 anywhere
-    if not checked:
-        raise SystemExit(f"bench: the pipelined step's masks differ from the serial step's ({int((masks != ref_masks).sum())} pixels)")
+    # ---- --full only from here to the result line: checks and extra measurements after the timed steps, none of which the headline needs ----
+    if args.full:
+        timed_out = {k: last_out["out"][k].clone() for k in ("features", "latents")}   # of the LAST timed step (this rank's patches); the sampler reuses its buffers
+        # result check (untimed): the masks of the LAST timed step (two batches in flight, deferred joins, persistent conv kernels on short
+        # runs) against one more step with everything on one stream and one batch in flight -- same inputs, so bit for bit
+        import zlib
+        sampler.set_overlap(0)
+        ref_masks = step()
+        sampler.set_overlap(1)
+        torch.cuda.synchronize()
+        ref_out = last_out["out"]
+        checked = bool(torch.equal(masks, ref_masks)) and all(torch.equal(timed_out[k], ref_out[k]) for k in ("features", "latents"))
+        masks_crc = zlib.crc32(masks.cpu().numpy().tobytes()) & 0xFFFFFFFF
+        # arithmetic regression signals (the stand-in head's masks hardly move with the kernels' rounding; these do): CRC of the uint8 per-pixel
+        # latent vectors and the extreme / mean magnitude of the final latents, rank 0's patches
+        feat_crc = zlib.crc32(timed_out["features"].cpu().numpy().tobytes()) & 0xFFFFFFFF
+        lat_absmax = float(timed_out["latents"].abs().max().item())
+        lat_absmean = float(timed_out["latents"].abs().double().mean().item())
+        sampler.check_finite()    # non-finite detector of both graphs (include/ldiff.h): raises if any step of this run overflowed fp16 anywhere
+        if not checked:
+            raise SystemExit(f"bench: the pipelined step's masks differ from the serial step's ({int((masks != ref_masks).sum())} pixels)")
 
     # ---- UNet step alone (the metric's second half: UNet-step HBM GB/s vs peak), HIP events on the launch stream ----
     unet_ms = unet_eager_ms = None
     unet_small = {}
     unet_nodes = {}
-    if not args.no_unet_step:
+    if args.full and not args.no_unet_step:
         def time_unet(lat, reps=5):
             for _ in range(3):
                 pipe.unet(lat, 501, ctx)       # eager, capture, first replay
@@ -378,7 +388,7 @@ def main():
 
     # ---- the reference's own batch (one patch per call: pixel_latent_vector.py:63, segmentor.py:96), whole sampler, untimed extra: latency per patch ----
     sample_b1_ms = None
-    if not args.no_unet_step and rank == 0:
+    if args.full and not args.no_unet_step and rank == 0:
         one = images[:1].contiguous()
         for _ in range(2):
             sampler.sample(one, ctx, N_PASSES, want_features=True, want_rgb=True)
@@ -413,16 +423,17 @@ def main():
                                      "mode 2 (the lo halves of its 3x3 conv operands travel as e4m3 through the block-scaled fp8 MFMA unless LDIFF_LO8=0: "
                                      "a 2^-11 correction term, DESIGN.md section 3), decoder mode 0 (include/ldiff.h ldiff_unet_set_precision): latents within 1e-3 of the fp32 oracle, "
                                      "uint8 features within one grey level")
-    result["checked"] = checked
     result["inputs"] = ("resident in HBM when the timed region starts; uint8 features and masks stay on the device (the reference copies the decoded image "
                         "to the host once per pass, pixel_latent_vector.py:81: 25 MB in + 10.5 MB out per step = 0.4 % at PCIe rates, DESIGN.md section 7)")
     result["setup_s"] = setup_s
-    result["check"] = {"masks_crc32": f"{masks_crc:08x}", "classes_present": int(masks.max().item()) + 1,
-                       "features_crc32": f"{feat_crc:08x}", "latents_absmax": lat_absmax, "latents_absmean": lat_absmean, "finite": True,
-                       "note": "masks_crc32 is of the STAND-IN head's masks (2 of 6 classes occur; it hardly moves with the kernels' rounding): the arithmetic signal is features_crc32 / latents_*; "
-                               "finite = ldiff_pipeline_check_finite passed (no fp16 overflow in either graph during the run)",
-                       "how": "masks, uint8 features and final latents of the last timed step == those of an extra untimed step on ONE stream with one batch in flight (bit for bit); "
-                              "the same configuration against the fp32 CPU oracle: tests/test_gpu_models.py::test_config1_b8_bench_mode_against_oracle"}
+    if args.full:
+        result["checked"] = checked
+        result["check"] = {"masks_crc32": f"{masks_crc:08x}", "classes_present": int(masks.max().item()) + 1,
+                           "features_crc32": f"{feat_crc:08x}", "latents_absmax": lat_absmax, "latents_absmean": lat_absmean, "finite": True,
+                           "note": "masks_crc32 is of the STAND-IN head's masks (2 of 6 classes occur; it hardly moves with the kernels' rounding): the arithmetic signal is features_crc32 / latents_*; "
+                                   "finite = ldiff_pipeline_check_finite passed (no fp16 overflow in either graph during the run)",
+                           "how": "masks, uint8 features and final latents of the last timed step == those of an extra untimed step on ONE stream with one batch in flight (bit for bit); "
+                                  "the same configuration against the fp32 CPU oracle: tests/test_gpu_models.py::test_config1_b8_bench_mode_against_oracle"}
     if dist is not None:
         result["comm"] = {"backend": dist.get_backend(), "world_size": dist.get_world_size(),
                           "collective": "all_gather_into_tensor of uint8 masks, once per step (ldiffusion_amd/parallel.py gather_masks)"}
@@ -473,7 +484,7 @@ def main():
         result["sample_b1"] = {"ms_per_patch": sample_b1_ms, "patches_per_sec": 1e3 / sample_b1_ms,
                                "what": f"one {img}x{img} patch per call through the whole {N_PASSES}-pass sampler (the reference's own batch: pixel_latent_vector.py:63), "
                                        "decodes beside the next UNet pass, joined per call; wall time per call, untimed extra (not the headline)"}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(ucfg, vcfg, usd, vsd, img, N_PASSES)
     print(json.dumps(result), flush=True)
     if dist is not None:

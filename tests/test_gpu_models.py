@@ -1437,13 +1437,14 @@ def test_pixel_latent_vector_entry_point_mirror(tiny, tmp_path):
 def test_bench_two_ranks_control_flow_on_one_gpu():
     """bench.py's N > 1 path end to end on a one-GPU box: `python bench.py --gpus 2` starts its two ranks itself (torch.distributed.run, 127.0.0.1), both on
     cuda:0 over gloo (LDIFF_BENCH_SHARED_GPU=1: test only -- the real run is one rank per GPU over RCCL), reduced-width graph.  Checks the contract of the
-    line: patch sharding, barrier + max over ranks, the mask all-gather, the serial-vs-pipelined result check, the non-finite check, rank 0 alone printing."""
+    line: patch sharding, barrier + max over ranks, the mask all-gather, the serial-vs-pipelined result check and the non-finite check (--full), rank 0
+    alone printing."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, LDIFF_BENCH_SHARED_GPU="1")
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--tiny", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--tiny", "--full", "--no-cpu-baseline"],
                          env=env, capture_output=True, text=True, timeout=800)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -1451,3 +1452,34 @@ def test_bench_two_ranks_control_flow_on_one_gpu():
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["scaling"] == "weak" and d["checked"] is True and d["check"]["finite"] is True
     assert d["comm"]["world_size"] == 2 and d["config"]["parallelism"].startswith("dp2") and d["value"] > 0
+
+
+@pytest.mark.timeout(900)
+def test_bench_full_only_adds_work_after_the_timed_steps(tmp_path):
+    """A plain `python bench.py` prints the headline line without the --full extras (result check, UNet-step and one-patch timings, CPU baseline);
+    --full adds them, and the outputs of the last timed step (--dump-outputs) are the same in both runs: the extras run after the timed steps."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = {}
+    for mode in ("plain", "full"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--tiny", "--dump-outputs", str(tmp_path / mode)]
+        out = subprocess.run(cmd + (["--full"] if mode == "full" else []), capture_output=True, text=True, timeout=400)
+        assert out.returncode == 0, out.stderr[-2000:]
+        got = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(got) == 1, out.stdout[-2000:]
+        lines[mode] = json.loads(got[0])
+    extras = {"checked", "check", "sample_b1", "cpu_baseline"}   # and unet_step*, which --tiny never prints
+    for mode, d in lines.items():
+        assert d["metric"] == "patches/sec (512x512, 5 denoise steps)" and d["unit"] == "patches/sec" and d["higher_is_better"] is True
+        assert d["dtype"] == "f16 (fp32 accumulate)" and d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert "roofline" in d and "kernels" in d
+    assert not extras & lines["plain"].keys()
+    full = lines["full"]
+    assert full["checked"] is True and full["check"]["finite"] is True and full["sample_b1"]["ms_per_patch"] > 0
+    assert full["cpu_baseline"]["value"] > 0
+    manifest = json.loads((tmp_path / "plain" / "manifest.json").read_text())
+    assert set(manifest) == {"masks", "latents", "features", "rgb"}
+    for name in manifest:
+        assert np.array_equal(np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy")), name
