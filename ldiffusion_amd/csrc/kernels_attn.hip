@@ -867,12 +867,14 @@ static void launch_attn_d512(const AttnParams& p, hipStream_t s) {
 // cycles and is bound by them.  This one keeps the same tiling (128 queries per workgroup, 64-key tiles, S^T = K Q^T, P in registers) and
 //   * fixes every query's softmax reference after the first key tile (its maximum + 4 binades, as attn_d512_kernel): no max chain, no lane
 //     swaps, no alpha, no rescale in the loop.  The row sums come out of the P V MFMAs (V^T row 40 = 1: the lanes that hold channel 40 of a
-//     V^T fragment substitute 1.0).  v_cvt_pkrtz CLAMPS an overflowing probability to the largest finite fp16 (round toward zero never
-//     produces inf), so one clamped probability puts >= 65504 into its fp32 row sum: the end of the pass takes "row sum >= 65504" (or not
-//     finite: exp2 itself overflowed) as the overflow signal -- conservative (a row whose in-window probabilities add up to that much also
-//     repeats; both cases need > 2^20 times the weight of the first tile's best key in later tiles) -- and the (rare) workgroup that saw it
-//     takes the true row maxima in a scores-only pass and repeats with those;
-//   * packs P with v_cvt_pkrtz_f16_f32 (one instruction per two scores; numerator and row sum see the same rounded P);
+//     V^T fragment substitute 1.0).  An overflowing probability rounds to inf (or to 65504 just below the overflow threshold), so its fp32
+//     row sum is not below 65504: the end of the pass takes "row sum >= 65504 or not finite" as the overflow signal -- conservative (a row
+//     whose in-window probabilities add up to that much also repeats; both cases need > 2^20 times the weight of the first tile's best key in
+//     later tiles) -- and the (rare) workgroup that saw it takes the true row maxima in a scores-only pass and repeats with those;
+//   * packs P rounded to NEAREST (v_cvt_pk_f16_f32, one instruction per two scores; numerator and row sum see the same rounded P).  Against
+//     the lead of 4 binades, keys more than ~10 binades below the reference land in fp16 subnormals; round toward zero (v_cvt_pkrtz) biased
+//     every one of them down by up to an ulp there, which over thousands of small probabilities moved peaky rows to 1.52x (4,096 keys) and
+//     1.63x (16,384) the error bound of tests/attention_bound.py (to nearest: 0.42x and 0.29x, same time per launch);
 //   * brings K / V in by LDS-DMA, double-buffered, ONE raw barrier per tile (zero padding of the 128-byte K rows and the channel-40..47 chunk of
 //     V by the out-of-range sentinel), operand reads issued in batches with counted waits.
 // ~3.5 issue slots per score.  Two workgroups per CU: one's softmax runs beside the other's MFMAs.
@@ -1016,10 +1018,8 @@ __global__ __launch_bounds__(256, 2) void attn_fr40_kernel(const AttnParams p) {
             e[r] = __builtin_amdgcn_exp2f(fmaf(sacc[qt][t][r], sl2, moff));
             if (TAIL && kv0 + t * 16 + g * 4 + r >= p.Lk) e[r] = 0.f;
           }
-          typedef __fp16 h2_t __attribute__((ext_vector_type(2)));
-          const h2_t a = __builtin_amdgcn_cvt_pkrtz(e[0], e[1]), c = __builtin_amdgcn_cvt_pkrtz(e[2], e[3]);
-          pf[qt][t >> 1][(t & 1) * 4 + 0] = (f16)a[0]; pf[qt][t >> 1][(t & 1) * 4 + 1] = (f16)a[1];
-          pf[qt][t >> 1][(t & 1) * 4 + 2] = (f16)c[0]; pf[qt][t >> 1][(t & 1) * 4 + 3] = (f16)c[1];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) pf[qt][t >> 1][(t & 1) * 4 + r] = (f16)e[r];   // round to nearest: a v_cvt_pk_f16_f32 per pair
         }
       }
       // ---- O^T += V^T P^T; V^T row 40 (d tile 2, lane l15 = 8) is all ones: row 40 of O^T accumulates the row sums ----
@@ -1050,7 +1050,7 @@ __global__ __launch_bounds__(256, 2) void attn_fr40_kernel(const AttnParams p) {
     for (int kv0 = 0; kv0 < full; kv0 += FR_BKV, buf ^= 1) tile(kv0, buf, std::false_type());
     if (full < p.Lk) tile(full, buf, std::true_type());
 
-    // ---- no probability left fp16's range?  (row 40 of O^T: lane g = 2, register 0 of d tile 2; a clamped P alone contributes 65504) ----
+    // ---- no probability left fp16's range?  (row 40 of O^T: lane g = 2, register 0 of d tile 2; an overflowing P alone makes it >= 65504 or inf) ----
     bool bad = false;
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) bad |= g == 2 && !(oacc[qt][2][0] < 65504.0f);

@@ -603,7 +603,7 @@ def test_attention_long_shared_keys_on_the_fixed_reference_kernels(lib, d, heads
 ])
 def test_attention_d40_fixed_reference(lib, name, B, heads, Lq, Lk, fused, late_spike):
     """attn_fr40_kernel (d = 40, at least two key tiles): fixed softmax reference per query (first key tile's maximum + 4 binades), row sums out of
-    the P V MFMAs through a ones row, P packed round-toward-zero, K / V by LDS-DMA.  Cases: fused q/k/v rows (the UNet's layout), ragged query /
+    the P V MFMAs through a ones row, P packed to nearest fp16, K / V by LDS-DMA.  Cases: fused q/k/v rows (the UNet's layout), ragged query /
     key tails, a head count that is not 8, and late keys that overflow fp16 P against the first tile's reference (row sum inf -> the workgroup
     takes the true maxima in a scores-only pass and repeats)."""
     d = 40
@@ -625,8 +625,8 @@ def test_attention_d40_fixed_reference(lib, name, B, heads, Lq, Lk, fused, late_
         k[1, Lk // 2 + 1, :d] = 8.0 * q[1, 290, :d]                    # another workgroup, a middle tile
     elif late_spike == "pair":
         # TWO late keys of one row, 30 and 27 binades above the first tile (both beyond fp16 P's window of 16 - 4 lead binades, both far inside
-        # fp32 exp2's range): true weights 8 : 1.  Packed round-toward-zero both clamp to 65504 -- equal weights, a wrong softmax -- unless the
-        # kernel notices the clamp and repeats the pass with the true maximum (the row-sum test must see a clamped P)
+        # fp32 exp2's range): true weights 8 : 1.  Packed, both overflow (65504 toward zero, inf to nearest) -- equal weights, a wrong softmax -- unless the
+        # kernel notices the overflow and repeats the pass with the true maximum (the row-sum test must see a clamped P)
         k[0, Lk - 7, 3 * d:4 * d] = key_at(0, 9, 3, 30.0)
         k[0, Lk - 70, 3 * d:4 * d] = key_at(0, 9, 3, 27.0)
         k[1, 200, 6 * d:7 * d] = key_at(1, 300, 6, 17.5)              # just outside the window: one clamped key beside in-window mass
@@ -1881,9 +1881,12 @@ def model_routes(lib):
 
 
 def pinned_kernels():
-    """Every kernel some parity case of this file, or of the backward-pass cases (test_gpu_backward.py), states it reaches."""
+    """Every kernel some parity case of this file, of the backward-pass cases (test_gpu_backward.py) or of the forward-attention cases
+    (test_gpu_attention.py) states it reaches."""
+    import test_gpu_attention
     import test_gpu_backward
     pinned = set(CONV_KERNEL.values()) | set(ATTN_KERNEL.values()) | {k for _, _, k in SPLITK_CASES.values()} | test_gpu_backward.pinned_kernels()
+    pinned |= test_gpu_attention.pinned_kernels()
     for table in (SPLIT_KERNEL, FUSED_STATS_KERNEL, GEMM_DF_KERNEL):
         pinned |= {n for names in table.values() for n in names}
     probes = [dict(d=40, M=4096, geglu=False), dict(d=80, M=300, geglu=True), dict(d=512, M=8192, geglu=False), dict(d=40, M=512, geglu=False)]
