@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define LDIFF_VERSION 170 /* 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
+#define LDIFF_VERSION 180 /* 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
 #define LDIFF_MAX_BLOCKS 8
 
 typedef enum { LDIFF_OK = 0, LDIFF_ERR_INVALID = -1, LDIFF_ERR_RUNTIME = -2, LDIFF_ERR_STATE = -3, LDIFF_ERR_NONFINITE = -4 } ldiff_status;
@@ -102,6 +102,41 @@ int ldiff_unet_set_additional_residuals(ldiff_unet*, const void* const* down_dev
 /* non-finite detector (see the conventions above): LDIFF_OK or LDIFF_ERR_NONFINITE for all forwards enqueued on `stream` so far; clears the flag */
 int ldiff_unet_check_finite(ldiff_unet*, void* stream);
 void ldiff_unet_destroy(ldiff_unet*);
+
+/* ------------------------------------------------------------------------------------------------
+ * ControlNetModel  --  replaces `controlnet(latents, t, encoder_hidden_states=..., controlnet_cond=..., return_dict=False)`
+ *   segmentor.py:357-363 (Segmentor.ldiffusion_augment_for_multimodal: RGB + depth map).  The reference takes the module from diffusers;
+ * this is diffusers 0.34's ControlNetModel for SD-v1.5-style configs: a conditioning embedding (3x3 convs conditioning_channels -> e[0], then per
+ * pair e[i] -> e[i] and e[i] -> e[i+1] stride 2, SiLU behind each, then e[last] -> block_out_channels[0] without activation) whose output is added
+ * to conv_in(sample); the UNet's down blocks and mid block on that sum (same time embedding, same context); one 1x1 conv behind every skip
+ * tensor and one behind the mid block, times conditioning_scale.  trunk_cfg is the UNet's config (up_has_attn / out_channels are not read).
+ * Entry points mirror the UNet's; checkpoint names are diffusers' (conv_in, time_embedding.*, down_blocks.*, mid_block.*,
+ * controlnet_cond_embedding.{conv_in, blocks.i, conv_out}, controlnet_down_blocks.i, controlnet_mid_block).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct ldiff_controlnet ldiff_controlnet;
+int ldiff_controlnet_create(ldiff_controlnet** out, const ldiff_unet_cfg* trunk_cfg, int conditioning_channels, const int* embedding_channels, int n_embedding,
+                            int device);
+int ldiff_controlnet_load(ldiff_controlnet*, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim);
+int ldiff_controlnet_missing(ldiff_controlnet*);
+const char* ldiff_controlnet_missing_name(ldiff_controlnet*, int i);
+int ldiff_controlnet_set_precision(ldiff_controlnet*, int mode);   /* as ldiff_unet_set_precision; default 1 */
+int ldiff_controlnet_set_context(ldiff_controlnet*, const void* ctx_dev, int B_ctx, int L, void* stream);
+/* cond [B or 1, conditioning_channels, H, W] f32 NCHW, H x W = 8 x the latent size for the four-entry embedding: runs the conditioning embedding once and
+ * keeps its result for every later forward (it depends on neither timestep nor latents, so a multi-pass loop pays for it once, as set_context does for K / V). */
+int ldiff_controlnet_set_cond(ldiff_controlnet*, const void* cond_dev, int B, int H, int W, void* stream);
+/* The diffusers surface: n_down f32 NCHW device tensors in skip-stack order (shapes of the UNet's skip tensors; n_down = 0: none) and mid_out (may be
+ * NULL) receive conditioning_scale * zero_conv_i(skip_i).  Launched eagerly. */
+int ldiff_controlnet_forward(ldiff_controlnet*, const void* sample_dev, int B, int h, int w, float timestep, float conditioning_scale, void* const* down_out,
+                             int n_down, void* mid_out, void* stream);
+int ldiff_controlnet_check_finite(ldiff_controlnet*, void* stream);
+void ldiff_controlnet_destroy(ldiff_controlnet*);
+/* The fast path.  While a ControlNet is attached, ldiff_unet_forward(sample, t) also runs the ControlNet's blocks on (sample, t, its own context and
+ * conditioning embedding) -- same stream, inside the same captured graph -- and every zero conv is one 1x1 launch that takes the UNet's skip tensor as
+ * its residual operand and writes skip + conditioning_scale * (W cnskip + b) in the UNet's own layout (split where the stream is split, fused GroupNorm
+ * statistics where the launch emits them): no fp32 NCHW tensors, no separate adds.  conditioning_scale is folded into the zero convs' weights and
+ * biases when it changes, not applied per launch.  NULL detaches.  Widths, layers per block, input channels and device must agree (LDIFF_ERR_INVALID
+ * names both).  The ControlNet is borrowed: keep it alive while attached.  ldiff_unet_check_finite then covers its blocks too. */
+int ldiff_unet_attach_controlnet(ldiff_unet*, ldiff_controlnet* cn_or_null, float conditioning_scale);
 
 /* ------------------------------------------------------------------------------------------------
  * AutoencoderKL  --  replaces vae.encode(x).latent_dist / vae.decode(z).sample / pipeline.decode_latents
@@ -261,6 +296,12 @@ typedef struct {
   int out_shift;                                    /* range shift k = 0..16 (0 = none; else LDIFF_ERR_INVALID): y = (sum + bias + temb) * 2^-k + res, res supplied already shifted;
                                                        hi | lo and `stats` are of that value (ldiff_vae_set_range_shift).  Exact: the k = 0 result times 2^-k wherever it stays
                                                        out of the fp16 subnormals.  Not with GEGLU; a folded shortcut (sc_x) is refused (LDIFF_ERR_INVALID) */
+  int silu_out;                                     /* 1: y = silu(sum + bias), the activation BEHIND the sum, rounded once.  Only the conditioning-embedding kernel has it (3x3, pad 1,
+                                                       stride 1 | 2, (C1, N) one of (8, 16) (16, 16) (16, 32) (32, 32) (32, 96) (96, 96) (96, 256), plain fp16 in and out, bias only);
+                                                       any other launch: LDIFF_ERR_INVALID */
+  int cond_conv;                                    /* the conditioning-embedding kernel: 0 = the executors' choice (the eligible launches that ask for silu_out: the embedding's own layers; a plain
+                                                       launch of such a shape goes where it always went), 1 = every eligible launch (tests, timing), -1 = never (timing: the route such a
+                                                       layer had before the kernel existed; silu_out is then refused) */
 } ldiff_conv_args;
 int ldiff_op_conv(const ldiff_conv_args*, void* stream);
 /* row blocks per image the launch would emit statistics for (0 = unsupported for this shape) */

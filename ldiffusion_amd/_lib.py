@@ -38,7 +38,7 @@ class ConvArgs(C.Structure):
                 ("geglu", C.c_int), ("ld1", C.c_int), ("ld2", C.c_int), ("res_lo", C.c_int), ("y_lo", C.c_int), ("short_runs", C.c_int),
                 ("lo8_slab0", C.c_int), ("lo8_scale", C.c_void_p), ("gemm_df", C.c_int),
                 ("sc_x", C.c_void_p), ("sc_C", C.c_int), ("sc_ld", C.c_int), ("sc_w", C.c_void_p), ("sc_bias", C.c_void_p), ("c3d_ups", C.c_int), ("n_real", C.c_int), ("splitk", C.c_int),
-                ("out_shift", C.c_int)]
+                ("out_shift", C.c_int), ("silu_out", C.c_int), ("cond_conv", C.c_int)]
 
 
 # name -> (restype, argtypes); every symbol include/ldiff.h declares
@@ -59,6 +59,17 @@ SIGNATURES = {
     "ldiff_unet_set_additional_residuals": (I, [P, C.POINTER(P), I, P]),
     "ldiff_unet_check_finite": (I, [P, P]),
     "ldiff_unet_destroy": (None, [P]),
+    "ldiff_controlnet_create": (I, [C.POINTER(P), C.POINTER(UNetCfg), I, C.POINTER(I), I, I]),
+    "ldiff_controlnet_load": (I, [P, C.c_char_p, P, I, C.POINTER(I64), I]),
+    "ldiff_controlnet_missing": (I, [P]),
+    "ldiff_controlnet_missing_name": (C.c_char_p, [P, I]),
+    "ldiff_controlnet_set_precision": (I, [P, I]),
+    "ldiff_controlnet_set_context": (I, [P, P, I, I, P]),
+    "ldiff_controlnet_set_cond": (I, [P, P, I, I, I, P]),
+    "ldiff_controlnet_forward": (I, [P, P, I, I, I, F, F, C.POINTER(P), I, P, P]),
+    "ldiff_controlnet_check_finite": (I, [P, P]),
+    "ldiff_controlnet_destroy": (None, [P]),
+    "ldiff_unet_attach_controlnet": (I, [P, P, F]),
     "ldiff_vae_create": (I, [C.POINTER(P), C.POINTER(VaeCfg), I]),
     "ldiff_vae_load": (I, [P, C.c_char_p, P, I, C.POINTER(I64), I]),
     "ldiff_vae_set_precision": (I, [P, I, I]),

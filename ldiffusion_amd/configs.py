@@ -52,6 +52,21 @@ TINY_UNET = dict(copy.deepcopy(SD15_UNET), block_out_channels=[64, 128, 256, 256
 # Same topology, 1/4 width.
 TINY_VAE = dict(copy.deepcopy(SD15_VAE), block_out_channels=[32, 64, 128, 128])
 
+# ControlNetModel (the network `Segmentor.ldiffusion_augment_for_multimodal` takes its thirteen residual tensors from,
+# /root/reference/segmentor.py:301-386): the UNet's conv_in, time embedding, down blocks and mid block, a conditioning embedding in
+# front and one 1x1 "zero conv" behind every skip tensor.  The fields are those of the public SD-v1.5 ControlNet config.json files.
+_CONTROLNET_FIELDS = {
+    "_class_name": "ControlNetModel",
+    "conditioning_channels": 3,
+    "conditioning_embedding_out_channels": [16, 32, 96, 256],
+    "controlnet_conditioning_channel_order": "rgb",
+    "global_pool_conditions": False,
+}
+_UNET_ONLY_FIELDS = ("up_block_types", "out_channels", "sample_size", "center_input_sample")
+SD15_CONTROLNET = dict({k: v for k, v in copy.deepcopy(SD15_UNET).items() if k not in _UNET_ONLY_FIELDS}, **copy.deepcopy(_CONTROLNET_FIELDS))
+# TINY_UNET's widths behind the embedding's REAL channel list: the conditioning-embedding kernel is tested at the channel counts it will see
+TINY_CONTROLNET = dict(copy.deepcopy(SD15_CONTROLNET), block_out_channels=[64, 128, 256, 256], cross_attention_dim=64)
+
 
 # diffusers' constructor defaults for the fields the sampling path reads: a config.json written by an older diffusers (or a
 # hand-trimmed one) may omit any of them, and `from_pretrained` then fills these in (UNet2DConditionModel.__init__ /
@@ -62,6 +77,15 @@ UNET_DEFAULTS = {
     "up_block_types": ["UpBlock2D", "CrossAttnUpBlock2D", "CrossAttnUpBlock2D", "CrossAttnUpBlock2D"],
     "block_out_channels": [320, 640, 1280, 1280], "layers_per_block": 2, "downsample_padding": 1, "act_fn": "silu",
     "norm_num_groups": 32, "norm_eps": 1e-5, "cross_attention_dim": 1280, "attention_head_dim": 8, "use_linear_projection": False,
+}
+CONTROLNET_DEFAULTS = {
+    "in_channels": 4, "conditioning_channels": 3, "flip_sin_to_cos": True, "freq_shift": 0,
+    "down_block_types": ["CrossAttnDownBlock2D", "CrossAttnDownBlock2D", "CrossAttnDownBlock2D", "DownBlock2D"],
+    "block_out_channels": [320, 640, 1280, 1280], "layers_per_block": 2, "downsample_padding": 1, "act_fn": "silu",
+    "norm_num_groups": 32, "norm_eps": 1e-5, "cross_attention_dim": 1280, "attention_head_dim": 8, "use_linear_projection": False,
+    "conditioning_embedding_out_channels": [16, 32, 96, 256], "controlnet_conditioning_channel_order": "rgb",
+    "global_pool_conditions": False, "class_embed_type": None, "addition_embed_type": None, "num_class_embeds": None,
+    "mid_block_type": "UNetMidBlock2DCrossAttn",
 }
 VAE_DEFAULTS = {
     "in_channels": 3, "out_channels": 3, "down_block_types": ["DownEncoderBlock2D"], "up_block_types": ["UpDecoderBlock2D"],
@@ -102,6 +126,35 @@ def validate_unet_config(cfg: dict) -> None:
         raise ValueError("use_linear_projection=True is not supported")
     if cfg.get("act_fn", "silu") != "silu":
         raise ValueError("only SiLU is supported")
+
+
+def controlnet_trunk_config(cfg: dict) -> dict:
+    """The UNet-shaped view of a ControlNet config: what `validate_unet_config` and the UNet-side helpers read.  The up path does not
+    exist in a ControlNet; the mirrored block list stands in so that the shared code sees a well-formed UNet config."""
+    up = ["CrossAttnUpBlock2D" if t == "CrossAttnDownBlock2D" else "UpBlock2D" for t in reversed(cfg["down_block_types"])]
+    return dict(cfg, up_block_types=up, out_channels=cfg["in_channels"])
+
+
+def validate_controlnet_config(cfg: dict) -> None:
+    """Reject ControlNet configs outside what the HIP executor implements (fail loudly, no fallback): everything
+    `validate_unet_config` refuses, plus the ControlNet-only switches."""
+    if cfg.get("global_pool_conditions", False):
+        raise ValueError("global_pool_conditions=True is not supported")
+    for k in ("class_embed_type", "addition_embed_type", "num_class_embeds"):
+        if cfg.get(k) is not None:
+            raise ValueError(f"{k}={cfg[k]!r} is not supported (class / addition embeddings are not built)")
+    if cfg.get("controlnet_conditioning_channel_order", "rgb") != "rgb":
+        raise ValueError(f"controlnet_conditioning_channel_order={cfg['controlnet_conditioning_channel_order']!r} is not supported (only 'rgb')")
+    if cfg.get("mid_block_type", "UNetMidBlock2DCrossAttn") != "UNetMidBlock2DCrossAttn":
+        raise ValueError(f"mid_block_type={cfg['mid_block_type']!r} is not supported")
+    if cfg.get("conditioning_channels", 3) > 8 or cfg.get("conditioning_channels", 3) < 1:
+        raise ValueError("conditioning_channels must be between 1 and 8")
+    emb = list(cfg.get("conditioning_embedding_out_channels", ()))
+    if not 1 <= len(emb) <= 8 or any(c % 8 for c in emb):
+        raise ValueError("conditioning_embedding_out_channels must hold 1..8 channel counts, each a multiple of 8")
+    if len(cfg["down_block_types"]) != len(cfg["block_out_channels"]):
+        raise ValueError("down block list must match block_out_channels")
+    validate_unet_config(controlnet_trunk_config(cfg))
 
 
 def validate_vae_config(cfg: dict) -> None:

@@ -106,6 +106,10 @@ int ldiff_unet_check_finite(ldiff_unet* u, void* stream) {
   LDIFF_CHECK(u, LDIFF_ERR_INVALID, "unet_check_finite: null handle");
   HIP_CHECK(hipSetDevice(u->device));
   HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+  const bool cn_bad = u->cn && u->cn->trunk.nf.test_and_clear();   // an attached ControlNet's blocks ran inside this handle's forwards
+  if (cn_bad) (void)u->nf.test_and_clear();                        // (the UNet's own blocks inherit the overflow through the skips: one report for both)
+  LDIFF_CHECK(!cn_bad, LDIFF_ERR_NONFINITE, "unet_check_finite: a non-finite activation (fp16 overflow: |x| > 65504, or NaN) was detected in the attached ControlNet; "
+              "the results of that forward are invalid.  LDIFF_TRACE_ABSMAX=1 shows which stage overflows.");
   report_nonfinite(u->nf, "unet_check_finite");
   API_END
 }
@@ -115,6 +119,91 @@ void ldiff_unet_destroy(ldiff_unet* u) {
   (void)hipDeviceSynchronize();
   if (u->ctx_buf) (void)hipFree(u->ctx_buf);
   delete u;
+}
+
+// ---- ControlNet ----
+int ldiff_controlnet_create(ldiff_controlnet** out, const ldiff_unet_cfg* trunk_cfg, int conditioning_channels, const int* embedding_channels, int n_embedding, int device) {
+  API_BEGIN
+  LDIFF_CHECK(out && trunk_cfg && embedding_channels && n_embedding >= 1 && n_embedding <= LDIFF_MAX_BLOCKS, LDIFF_ERR_INVALID, "controlnet_create: bad arguments");
+  int ndev = 0;
+  HIP_CHECK(hipGetDeviceCount(&ndev));
+  LDIFF_CHECK(device >= 0 && device < ndev, LDIFF_ERR_INVALID, "controlnet_create: device %d not available (%d devices)", device, ndev);
+  HIP_CHECK(hipSetDevice(device));
+  ldiff_controlnet* c = new ldiff_controlnet();
+  c->trunk.cfg = *trunk_cfg;
+  c->trunk.device = device;
+  c->cond_channels = conditioning_channels;
+  c->emb_ch.assign(embedding_channels, embedding_channels + n_embedding);
+  try { c->build(); } catch (...) { delete c; throw; }
+  *out = c;
+  API_END
+}
+int ldiff_controlnet_load(ldiff_controlnet* c, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
+  API_BEGIN
+  LDIFF_CHECK(c, LDIFF_ERR_INVALID, "controlnet_load: null handle");
+  HIP_CHECK(hipSetDevice(c->trunk.device));
+  c->trunk.ws.load(name, host_ptr, dtype, shape, ndim);
+  API_END
+}
+int ldiff_controlnet_missing(ldiff_controlnet* c) { return c ? c->trunk.ws.missing() : -1; }
+const char* ldiff_controlnet_missing_name(ldiff_controlnet* c, int i) { return c ? c->trunk.ws.missing_name(i) : ""; }
+int ldiff_controlnet_set_precision(ldiff_controlnet* c, int mode) {
+  API_BEGIN
+  LDIFF_CHECK(c && mode >= PREC_FAST && mode <= PREC_FULL, LDIFF_ERR_INVALID, "controlnet_set_precision: mode must be 0, 1 or 2");
+  c->trunk.precision = mode;
+  API_END
+}
+int ldiff_controlnet_set_context(ldiff_controlnet* c, const void* ctx_dev, int B_ctx, int L, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(c, LDIFF_ERR_INVALID, "controlnet_set_context: null handle");
+  c->trunk.set_context((const float*)ctx_dev, B_ctx, L, (hipStream_t)stream);
+  API_END
+}
+int ldiff_controlnet_set_cond(ldiff_controlnet* c, const void* cond_dev, int B, int H, int W, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(c, LDIFF_ERR_INVALID, "controlnet_set_cond: null handle");
+  c->set_cond((const float*)cond_dev, B, H, W, (hipStream_t)stream);
+  API_END
+}
+int ldiff_controlnet_forward(ldiff_controlnet* c, const void* sample_dev, int B, int h, int w, float timestep, float conditioning_scale, void* const* down_out, int n_down,
+                             void* mid_out, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(c, LDIFF_ERR_INVALID, "controlnet_forward: null handle");
+  report_nonfinite(c->trunk.nf, "controlnet_forward");
+  c->forward((const float*)sample_dev, B, h, w, timestep, conditioning_scale, reinterpret_cast<float* const*>(down_out), n_down, (float*)mid_out, (hipStream_t)stream);
+  API_END
+}
+int ldiff_controlnet_check_finite(ldiff_controlnet* c, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(c, LDIFF_ERR_INVALID, "controlnet_check_finite: null handle");
+  HIP_CHECK(hipSetDevice(c->trunk.device));
+  HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+  report_nonfinite(c->trunk.nf, "controlnet_check_finite");
+  API_END
+}
+void ldiff_controlnet_destroy(ldiff_controlnet* c) {
+  if (!c) return;
+  (void)hipSetDevice(c->trunk.device);
+  (void)hipDeviceSynchronize();
+  delete c;
+}
+int ldiff_unet_attach_controlnet(ldiff_unet* u, ldiff_controlnet* c, float conditioning_scale) {
+  API_BEGIN
+  LDIFF_CHECK(u, LDIFF_ERR_INVALID, "unet_attach_controlnet: null handle");
+  if (c) {
+    const ldiff_unet_cfg &a = u->cfg, &b = c->trunk.cfg;
+    bool same = a.n_blocks == b.n_blocks && a.layers_per_block == b.layers_per_block && a.in_channels == b.in_channels && u->device == c->trunk.device;
+    std::string sa, sb;
+    for (int i = 0; i < a.n_blocks; ++i) sa += (i ? "," : "") + std::to_string(a.block_out_channels[i]);
+    for (int i = 0; i < b.n_blocks; ++i) sb += (i ? "," : "") + std::to_string(b.block_out_channels[i]);
+    LDIFF_CHECK(same && sa == sb, LDIFF_ERR_INVALID,
+                "unet_attach_controlnet: the UNet has widths [%s], %d layers per block, %d input channels (device %d); the ControlNet [%s], %d, %d (device %d)", sa.c_str(),
+                a.layers_per_block, a.in_channels, u->device, sb.c_str(), b.layers_per_block, b.in_channels, c->trunk.device);
+  }
+  u->cn = c;
+  u->cn_scale = conditioning_scale;
+  ++u->cn_epoch;
+  API_END
 }
 
 // ---- VAE ----
@@ -534,6 +623,8 @@ static void conv_args_to_params(const ldiff_conv_args* a, ConvParams& p) {
   p.df_force = a->gemm_df;
   p.xs = (const f16*)a->sc_x; p.Cs = a->sc_x ? a->sc_C : 0; p.lds = a->sc_x ? a->sc_ld : 0;
   p.out_shift = a->out_shift;   // (plan_conv checks 0..16)
+  p.silu_out = a->silu_out != 0;
+  p.cond_force = a->cond_conv;
 }
 int ldiff_op_conv(const ldiff_conv_args* a, void* stream) {
   API_BEGIN

@@ -103,6 +103,10 @@ struct ConvParams {
   // supplies already shifted; the stored halves and the fused statistics are of that v.  A power of two is exact, so the result is the unshifted one
   // times 2^-out_shift bit for bit wherever it stays out of the fp16 subnormals (the VAE decoder's range shift, DESIGN.md section 3 "Range")
   int out_shift = 0;
+  // SiLU BEHIND the sum (y = silu(sum + bias), one fp16 rounding): the conditioning-embedding kernel only (kernels_cond.hip); plan_conv refuses it for any
+  // launch that kernel does not take.  cond_force (ldiff_conv_args.cond_conv): 0 = that kernel takes the eligible launches that ask for silu_out (every layer
+  // of the embedding it is made for; a plain launch of the same shape goes where it always went), 1 = every eligible launch (tests, timing), -1 = none
+  int silu_out = 0, cond_force = 0;
 };
 constexpr int LO8_SHIFT = 15;   // lo = x - fp16(x) of a GroupNorm + SiLU output: |lo| <= half an fp16 ulp = 2^-7 for |x| < 32, so lo * 2^15 <= 256 stays inside e4m3's 448;
                                 // for |x| in [32, 64) it reaches 512 and saturates at 448 (the correction term is clamped, harmless), as for everything beyond
@@ -112,7 +116,7 @@ void launch_lo8_weights(const f16* w, void* wd, int* scale_out, int Nrows, int t
 // count, the fused statistics' row blocks, the kernel with its tile, and the pre-packed weights it reads.  It writes ConvParams::splitk (0 = no
 // split), ::stats_R (0 = no fused statistics for this launch) and, with ConvPlan::fold_gn, the per-image weight strides; every buffer the plan
 // names (w_par, splitk_ws, stats, w_frag, folded weights) is the caller's to provide before launch_igemm.
-enum class ConvKernel { C3_NARROW, C3_NARROW_FOLD, C3_DATAFLOW, C3_PINGPONG, C3_HALO, GEMM_DF, GEMM_DMA, IGEMM, NONE /* an fp8 lo half the ping-pong kernel does not take */ };
+enum class ConvKernel { COND /* conditioning-embedding 3x3: kernels_cond.hip */, C3_NARROW, C3_NARROW_FOLD, C3_DATAFLOW, C3_PINGPONG, C3_HALO, GEMM_DF, GEMM_DMA, IGEMM, NONE /* an fp8 lo half the ping-pong kernel does not take */ };
 enum class ConvWeights { PLAIN, FRAG, FRAG_PAR, FRAG_SC, GEMM_FRAG };   // launch_pack_frag_weights{,_par,_sc} / launch_pack_gemm_frag -> ConvParams::w_frag
 struct ConvAsk {          // what the caller states beside the launch itself
   int splitk = 0;         // 0: plan a split count; 1: never split; >= 2: this count (ldiff_op_conv: tests, timing), checked against the K steps
@@ -129,6 +133,10 @@ struct ConvPlan {
 ConvPlan plan_conv(ConvParams& p, const ConvAsk& ask);
 bool conv_lo8_enabled();   // LDIFF_LO8 (conv_route.hip)
 void launch_igemm(const ConvParams& p, const ConvPlan& pl, hipStream_t s);   // runs the planned kernel (the register-staged igemm itself: kernels_igemm.hip)
+// 3x3 conv + bias (+ SiLU epilogue) at the channel counts of the ControlNet's conditioning embedding (3 / 16 / 32 / 96 in, 16 / 32 / 96 / 256 out): kernels_cond.hip
+bool cond_conv_selected(const ConvParams& p);
+void launch_cond_conv(const ConvParams& p, hipStream_t s);
+void launch_scale_f16(const f16* x, f16* y, float a, long long n, hipStream_t s);   // y = f16(x * a)
 bool conv3x3_eligible(const ConvParams& p);   // the halo-tile 3x3 family: kernels_conv3x3.hip
 void launch_splitk_reduce(const ConvParams& p, hipStream_t s);   // sums p.splitk fp32 partials of splitk_ws and applies the epilogue (+ the fused GroupNorm statistics: R = H W / 32)
 // nearest-2x upsample + conv3x3 == four 2x2 convs on the source grid (one per output parity) with pre-summed taps:

@@ -1,5 +1,6 @@
 // Which kernel takes a conv / GEMM launch, with which split, statistics row blocks, tile and weight layout (common.h plan_conv).
 // Each kernel file states its own limits (conv3x3_eligible, conv3x3{n,nt,d,p}_selected, gemm_dma_eligible, gemm_df_selected); this file
+// cond_conv_selected comes first: its launches are ones no other family is made for.  This file
 // is the one place that asks them, in one fixed order, and the only one that reads the routing switches LDIFF_GEMM_DF and LDIFF_LO8.
 #include "common.h"
 
@@ -116,6 +117,16 @@ ConvPlan plan_conv(ConvParams& p, const ConvAsk& ask) {
   static const int df_mode = [] { const char* e = getenv("LDIFF_GEMM_DF"); return e ? atoi(e) : 1; }();
   if (q.df_force == 0 && (df_mode == 0 || df_mode == 2)) q.df_force = df_mode == 0 ? -1 : 1;
 
+  // 0. the conditioning-embedding 3x3 (kernels_cond.hip): channel counts no other family is made for; no split, no fused statistics (the caller's
+  //    separate statistics pass), plain weights.  It is the one kernel with an activation behind its sum
+  if (ask.splitk < 2 && cond_conv_selected(q)) {
+    pl.kernel = ConvKernel::COND;
+    p.splitk = 0;
+    p.stats_R = 0;
+    return pl;
+  }
+  LDIFF_CHECK(!q.silu_out, LDIFF_ERR_INVALID, "conv: a SiLU epilogue (silu_out) exists only in the conditioning-embedding kernel, which does not take this launch (Cin=%d N=%d ks=%d stride=%d)",
+              q.C1 + q.C2, q.N, q.ks, q.stride);
   // 1. the kernel family.  GroupNorm -> 1x1 conv / Linear with no activation in between (VAE attention q/k/v; transformer proj_in under PREC_FAST):
   //    the normalisation folded into per-image weights and bias where the plain LDS-DMA GEMM takes that form, instead of the register-staged GN prologue
   if (ask.fold_gn && q.gn_scale && !q.silu_in && q.ks == 1 && !q.x2 && !q.out_f32 && !q.geglu) {

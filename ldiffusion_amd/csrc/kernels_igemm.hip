@@ -315,6 +315,7 @@ void launch_igemm(const ConvParams& p, const ConvPlan& pl, hipStream_t s) {
   // every kernel but the dataflow conv ignores ConvParams::xs while the caller has already summed the shortcut's bias into p.bias: refuse instead of a silently wrong sum
   LDIFF_CHECK(!p.xs || pl.kernel == ConvKernel::C3_DATAFLOW, LDIFF_ERR_INVALID, "conv3x3: a folded shortcut (xs) needs the dataflow kernel, which does not take this launch (split-K %d)", p.splitk);
   switch (pl.kernel) {
+    case ConvKernel::COND: launch_cond_conv(p, s); return;
     case ConvKernel::C3_NARROW: case ConvKernel::C3_NARROW_FOLD: launch_conv3x3n(p, pl.kernel == ConvKernel::C3_NARROW_FOLD, s); return;
     case ConvKernel::C3_DATAFLOW: launch_conv3x3d(p, s); return;
     case ConvKernel::C3_PINGPONG: launch_conv3x3p(p, s); return;

@@ -24,6 +24,8 @@ struct Act {
   bool lo8 = false;      // split with an fp8 lo half: a row is [C fp16 | C e4m3 of lo * 2^LO8_SHIFT] = 3C bytes (ConvParams::lo8_slab0); conv operands only
   float* st = nullptr;   // producer-fused GroupNorm partial statistics [B][st_R][C][2] (nullptr: none)
   int st_R = 0;
+  bool borrowed = false; // lives in ANOTHER executor's arena (a skip tensor written by an attached ControlNet's zero conv): Exec::release leaves it alone,
+                         // that arena's next reset reclaims it
   long long rows() const { return (long long)B * H * W; }
   int ld() const { return lo8 ? C + C / 2 : (split ? 2 * C : C); }       // row pitch in elements
   int lo() const { return split ? C : 0; }           // offset of the lo half inside a row
@@ -114,6 +116,7 @@ struct ConvOpts {
   int N_override = 0;           // columns to store (multiple of 4), default = roundup4(w.N)
   int ldy = 0;                  // fp16 output channel stride (default N stored rounded up to 8)
   bool want_stats = false;      // also emit GroupNorm partial statistics of the output (consumed by Exec::gn)
+  bool silu_out = false;        // SiLU behind the sum: ConvParams::silu_out where the conditioning-embedding kernel takes the launch (cond_conv_selected), else a SiLU launch of its own
   bool geglu = false;           // apply x * gelu(gate) in the epilogue (weights must be MatW::geglu); output has N/2 channels
   // decode_latents tail in the epilogue (VAE conv_out): applied iff the narrow-output kernel takes the launch; *post_done says whether it did
   float* post_img = nullptr; uint8_t* post_rgb = nullptr; uint8_t* post_luma = nullptr; int post_slots = 0, post_slot = 0; bool post_only = false;
@@ -183,8 +186,10 @@ struct TransformerW {
 //   2  every conv / linear operand split (K doubled everywhere): ~1e-4; used for the VAE encoder, whose error every later pass inherits
 enum { PREC_FAST = 0, PREC_STREAM = 1, PREC_FULL = 2 };
 
+struct ldiff_controlnet;
 struct ldiff_unet {
   ldiff_unet_cfg cfg;
+  bool encoder_only = false;   // the trunk of a ControlNet: conv_in, time embedding, down blocks and mid block only (no up path, no output head)
   int device = 0;
   int precision = PREC_STREAM;
   WeightStore ws;
@@ -209,6 +214,27 @@ struct ldiff_unet {
   // handle-owned staging buffers, so the replay is valid for any caller pointers and any timestep.
   void forward(const float* x, int B, int h, int w, float t, float* out, hipStream_t s);
   void forward_impl(const float* x, int B, int h, int w, float t, const float* t_dev, float* out, hipStream_t s);
+  // The stages of a pass that a UNet and a ControlNet's trunk share, and the state they hand on: begin_pass (argument checks, workspace), run_down
+  // (time embedding, conv_in -- plus `emb`, a plain [B, h, w, C0] tensor added in conv_in's epilogue: the ControlNet's conditioning embedding -- and
+  // the down blocks: fills pass.skips, pass.cur = the last of them) and run_mid (the mid block: pass.cur = its output, the skips stay alive).
+  struct Pass {
+    int B = 0, h = 0, w = 0;
+    float* temb_all = nullptr;
+    std::vector<Act> skips;
+    Act cur;
+    bool cur_is_skip = false;
+    int stage_no = 0;
+  } pass;
+  void begin_pass(int B, int h, int w, hipStream_t s);
+  void run_down(const float* x, float t, const float* t_dev, const Act* emb);
+  void run_mid();
+  void advance(Act nxt);
+  Act resnet(const ResnetW& r, const Act& x, const Act* skip);
+  // An attached ControlNet (ldiff_unet_attach_controlnet): its blocks run inside this UNet's forward and its zero convs write skip + scale * (W cnskip + b)
+  // straight into the skip stack; borrowed, the caller keeps it alive while attached
+  ldiff_controlnet* cn = nullptr;
+  float cn_scale = 1.0f;
+  long long cn_epoch = 0;   // bumped by every attach / detach (a new scale included): part of the graph key
   // ControlNet inputs of the next forward (down_block_additional_residuals, mid_block_additional_residual: segmentor.py:366-372);
   // float32 NCHW device pointers in skip-stack order, consumed (cleared) by that forward, which then runs eagerly
   std::vector<const float*> extra_down;
@@ -217,7 +243,7 @@ struct ldiff_unet {
   struct GraphCache {
     bool enabled = true;
     int uses = 0;                       // forwards seen with the current key (0: none, 1: ran eagerly once, >= 2: graph ready)
-    long long key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    long long key[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     hipStream_t cap_stream = nullptr;
@@ -271,6 +297,33 @@ struct ldiff_vae {
   // rebuilt on their next use (Exec::derived_bias_shift)
   void set_range_shift(int k) { ex_dec.range_shift = k; }
   float dec_eps() const { return ldexpf(1e-6f, -2 * ex_dec.range_shift); }
+};
+
+// ---- ControlNet ---------------------------------------------------------------------------------
+// diffusers ControlNetModel: a conditioning embedding (eight 3x3 convs, SiLU between them) whose output joins conv_in's, the UNet's down blocks and
+// mid block on that (the trunk: an encoder-only ldiff_unet, same builders and executors), and a 1x1 "zero conv" behind every skip tensor and the mid block.
+struct ldiff_controlnet {
+  ldiff_unet trunk;
+  int cond_channels = 3;
+  std::vector<int> emb_ch;
+  MatW e_conv_in, e_conv_out;
+  std::vector<MatW> e_blocks;
+  std::vector<MatW> zc;        // controlnet_down_blocks.i, then controlnet_mid_block: as loaded
+  std::vector<MatW> zs;        // the same times conditioning_scale (weights and bias), what the launches read; rebuilt when the scale or the checkpoint changes
+  float zs_scale = 0.f;
+  int zs_gen = -1;
+  long long state_gen = 0;     // bumped by whatever a captured graph that holds this network's launches must not outlive
+  Exec ex_emb;                 // the embedding's executor (its own workspace: the map is eight times the latent size per side)
+  f16* emb = nullptr;          // conditioning embedding [emb_B, emb_h, emb_w, C0] fp16, kept between set_cond calls
+  size_t emb_cap = 0;
+  int emb_B = 0, emb_h = 0, emb_w = 0;
+  void build();
+  void set_cond(const float* cond, int B, int H, int W, hipStream_t s);
+  void ensure_scaled(float scale, hipStream_t s);
+  // the trunk's pass: fills trunk.pass (skips, cur = the mid block's output); the tensors stay valid until the trunk's next pass
+  void run_trunk(const float* x, int B, int h, int w, float t, const float* t_dev, hipStream_t s);
+  void forward(const float* x, int B, int h, int w, float t, float scale, float* const* down_out, int n_down, float* mid_out, hipStream_t s);
+  ~ldiff_controlnet();
 };
 
 struct ldiff_pipeline {

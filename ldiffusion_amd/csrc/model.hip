@@ -271,6 +271,7 @@ Act Exec::new_act(int B, int H, int W, int C, bool split, bool lo8) {
   return a;
 }
 void Exec::release(Act& a) {
+  if (a.borrowed) { a.p = nullptr; a.st = nullptr; return; }
   if (a.p) arena.free(a.p);
   if (a.st) arena.free(a.st);
   a.p = nullptr;
@@ -513,6 +514,13 @@ Act Exec::conv(const MatW& w, const Act& x, const Act* x2, const ConvOpts& o) {
     C = o.ldy ? o.ldy : (o.split_out ? roundup(p.N, 4) : roundup(p.N, 8));
     p.ldy = o.split_out ? 2 * C : C; p.y_lo = o.split_out ? C : 0;
   }
+  // SiLU behind the sum: in the epilogue where the conditioning-embedding kernel takes the launch (the one kernel that has it), else its own launch below
+  bool silu_after = false;
+  if (o.silu_out) {
+    LDIFF_CHECK(C > 0 && !o.split_out && !o.res && !o.want_stats, LDIFF_ERR_INVALID, "conv: a SiLU behind the sum needs a plain fp16 output without residual or statistics");
+    p.silu_out = 1;
+    if (!cond_conv_selected(p)) { p.silu_out = 0; silu_after = true; }
+  }
   if (o.sc_done) *o.sc_done = false;
   if (o.sc_x && o.sc_w && o.sc_done && !o.split_in && !o.res && !o.sc_x->split && o.sc_w->ks == 1 && o.sc_w->Nrows == w.Nrows && o.sc_w->K == o.sc_x->C) {
     p.xs = o.sc_x->p; p.Cs = o.sc_x->C; p.lds = o.sc_x->ld();   // the block's 1x1 shortcut, folded in where the dataflow kernel takes the launch
@@ -561,6 +569,7 @@ Act Exec::conv(const MatW& w, const Act& x, const Act* x2, const ConvOpts& o) {
     case ConvWeights::PLAIN: break;
   }
   launch_igemm(p, pl, s);
+  if (silu_after) launch_silu_f16(y.p, y.p, (long long)y.rows() * y.C, s);
   if (p.splitk_ws) arena.free(p.splitk_ws);   // stream-ordered reuse: safe once the launches are enqueued
   if (wfold) { arena.free(bfold); arena.free(wfold); }
   return y;
@@ -743,7 +752,8 @@ void ldiff_unet::build() {
     int ch = boc[0];
     for (int i = 0; i < nb; ++i) { for (int j = 0; j < lpb; ++j) { temb_couts.push_back(boc[i]); ch = boc[i]; } }
     temb_couts.push_back(ch); temb_couts.push_back(ch);  // mid
-    for (int i = 0; i < nb; ++i) for (int j = 0; j < lpb + 1; ++j) temb_couts.push_back(boc[nb - 1 - i]);
+    if (!encoder_only)
+      for (int i = 0; i < nb; ++i) for (int j = 0; j < lpb + 1; ++j) temb_couts.push_back(boc[nb - 1 - i]);
   }
   temb_total = 0;
   for (int c : temb_couts) temb_total += c;
@@ -782,7 +792,7 @@ void ldiff_unet::build() {
   mid_attn = make_transformer(ws, "mid_block.attentions.0", ch, ctx);
   mid_res[1] = add_res("mid_block.resnets.1", ch, ch);
   up_res.resize(nb); up_attn.resize(nb); up_sample.resize(nb); has_up.assign(nb, false);
-  for (int i = 0; i < nb; ++i) {
+  for (int i = 0; i < nb && !encoder_only; ++i) {
     const int oc = boc[nb - 1 - i];
     const std::string p = "up_blocks." + std::to_string(i);
     for (int j = 0; j < lpb + 1; ++j) {
@@ -794,8 +804,10 @@ void ldiff_unet::build() {
     }
     if (i != nb - 1) { up_sample[i] = ws.add_conv(p + ".upsamplers.0.conv", ch, ch, 3); has_up[i] = true; }
   }
-  norm_out = ws.add_norm("conv_norm_out", ch);
-  conv_out = ws.add_conv("conv_out", ch, cfg.out_channels, 3);
+  if (!encoder_only) {
+    norm_out = ws.add_norm("conv_norm_out", ch);
+    conv_out = ws.add_conv("conv_out", ch, cfg.out_channels, 3);
+  }
   LDIFF_CHECK(temb_off == temb_total, LDIFF_ERR_RUNTIME, "unet: internal temb bookkeeping error");
 
   for (auto& v : down_attn) for (auto& t : v) all_tf.push_back(&t);
@@ -931,13 +943,16 @@ void ldiff_unet::forward(const float* x, int B, int h, int w, float tval, float*
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (s) (void)hipStreamIsCapturing(s, &cs);   // the legacy default stream cannot be captured
   if (!gc.enabled || env_off || prof_enabled() || cs != hipStreamCaptureStatusNone || !x || !out || B < 1 || h < 1 || w < 1 || !extra_down.empty() ||
-      extra_mid) {
+      extra_mid || encoder_only) {
     forward_impl(x, B, h, w, tval, nullptr, out, s);   // (argument errors are reported by forward_impl)
     return;
   }
   HIP_CHECK(hipSetDevice(device));
   const size_t n_in = (size_t)B * cfg.in_channels * h * w, n_out = (size_t)B * cfg.out_channels * h * w;
-  const long long key[8] = {B, h, w, precision, (long long)ctx_B * 65536 + ctx_L, ws.generation, ctx_gen, (long long)ex.arena.capacity()};
+  // an attached ControlNet's launches are part of the captured sequence: whatever they read through a fixed address or were planned with is part of the key
+  const long long key[13] = {B, h, w, precision, (long long)ctx_B * 65536 + ctx_L, ws.generation, ctx_gen, (long long)ex.arena.capacity(),
+                             (long long)reinterpret_cast<uintptr_t>(cn), cn ? cn->state_gen : 0, cn ? (long long)cn->trunk.ex.arena.capacity() : 0,
+                             cn ? ((long long)cn->trunk.ws.generation << 24) + cn->trunk.ctx_gen * 4 + cn->trunk.precision : 0, cn_epoch};
   if (memcmp(key, gc.key, sizeof(key)) != 0) { gc.drop(); memcpy(gc.key, key, sizeof(key)); }
   if (gc.uses == 0) {               // first use of this configuration: eager (builds lazily derived weights, sizes the workspaces)
     forward_impl(x, B, h, w, tval, nullptr, out, s);
@@ -986,8 +1001,7 @@ void ldiff_unet::forward(const float* x, int B, int h, int w, float tval, float*
   ++gc.replays;
 }
 
-void ldiff_unet::forward_impl(const float* x, int B, int h, int w, float tval, const float* t_dev, float* out, hipStream_t s) {
-  LDIFF_CHECK(x && out && B >= 1 && h >= 1 && w >= 1, LDIFF_ERR_INVALID, "unet_forward: bad arguments (B=%d h=%d w=%d)", B, h, w);
+void ldiff_unet::begin_pass(int B, int h, int w, hipStream_t s) {
   const int nb = cfg.n_blocks;
   LDIFF_CHECK(h % (1 << (nb - 1)) == 0 && w % (1 << (nb - 1)) == 0, LDIFF_ERR_INVALID, "unet_forward: latent size %dx%d must be divisible by %d", h, w, 1 << (nb - 1));
   LDIFF_CHECK(ws.missing() == 0, LDIFF_ERR_STATE, "unet: %d weight tensors not loaded (first: %s)", ws.missing(), ws.missing_name(0));
@@ -1001,7 +1015,27 @@ void ldiff_unet::forward_impl(const float* x, int B, int h, int w, float tval, c
   for (int i = 0; i < nb; ++i) Cmax = std::max(Cmax, cfg.block_out_channels[i]);
   ex.arena.reserve((size_t)B * h * w * C0 * 2 * (precision >= PREC_STREAM ? 160 : 96) + (size_t)B * temb_total * 16 + (64u << 20));
   ex.ensure_gn_partial(gn_partial_bytes(B, h * w, 2 * Cmax));
+  pass = Pass{};
+  pass.B = B; pass.h = h; pass.w = w;
+}
 
+Act ldiff_unet::resnet(const ResnetW& r, const Act& xin, const Act* skip) {
+  return ex.resnet(r, xin, skip, pass.temb_all + r.temb_off, temb_total, cfg.norm_num_groups, cfg.norm_eps, precision);
+}
+
+void ldiff_unet::advance(Act nxt) {
+  if (!pass.cur_is_skip) ex.release(pass.cur);
+  pass.cur = nxt;
+  pass.cur_is_skip = false;
+  char nm[32];
+  snprintf(nm, sizeof(nm), "stage %d", pass.stage_no++);
+  ex.trace(nm, pass.cur);
+}
+
+void ldiff_unet::run_down(const float* x, float tval, const float* t_dev, const Act* emb) {
+  const int nb = cfg.n_blocks, B = pass.B, h = pass.h, w = pass.w;
+  const int C0 = cfg.block_out_channels[0];
+  hipStream_t s = ex.s;
   // time embedding: sinusoid -> linear_1 -> SiLU -> linear_2, then SiLU once and all 22 per-resnet projections in one GEMM
   const int td = C0 * 4;
   Act e16 = ex.new_act(1, 1, B, C0);
@@ -1017,45 +1051,55 @@ void ldiff_unet::forward_impl(const float* x, int B, int h, int w, float tval, c
   float* temb_all = ex.tmp<float>((size_t)B * temb_total);
   { ConvOpts o; o.out_f32 = temb_all; o.ldy_f32 = temb_total; ex.conv(temb_proj_all, l2h, nullptr, o); }
   ex.release(e16); ex.arena.free(l1); ex.release(l1h); ex.arena.free(l2); ex.release(l2h);
+  pass.temb_all = temb_all;
 
   const bool st = precision >= PREC_STREAM;
-  auto rb = [&](const ResnetW& r, const Act& xin, const Act* skip) {
-    return ex.resnet(r, xin, skip, temb_all + r.temb_off, temb_total, cfg.norm_num_groups, cfg.norm_eps, precision);
-  };
   Act x16 = ex.new_act(B, h, w, 8);
   const bool split_first = st && conv_in.Cin_logical > 0;   // the fp32 latents enter as hi | lo inside the 8 padded channels
   launch_nchw_f32_to_nhwc_f16(x, x16.p, B, cfg.in_channels, h, w, 8, s, split_first ? cfg.in_channels : 0);
   ConvOpts oci;
   oci.want_stats = true; oci.split_in = split_first; oci.split_out = st;
-  Act cur = ex.conv(conv_in, x16, nullptr, oci);
+  oci.res = emb;   // (a ControlNet's trunk: conv_in(sample) + embedding, summed in fp32)
+  pass.cur = ex.conv(conv_in, x16, nullptr, oci);
   ex.release(x16);
 
-  std::vector<Act> skips{cur};
-  bool cur_is_skip = true;
-  int stage_no = 0;
-  auto advance = [&](Act nxt) {
-    if (!cur_is_skip) ex.release(cur);
-    cur = nxt;
-    cur_is_skip = false;
-    char nm[32];
-    snprintf(nm, sizeof(nm), "stage %d", stage_no++);
-    ex.trace(nm, cur);
-  };
+  pass.skips.assign(1, pass.cur);
+  pass.cur_is_skip = true;
   for (int i = 0; i < nb; ++i) {
     for (size_t j = 0; j < down_res[i].size(); ++j) {
-      advance(rb(down_res[i][j], cur, nullptr));
-      if (cfg.down_has_attn[i]) advance(transformer(down_attn[i][j], cur));
-      skips.push_back(cur);
-      cur_is_skip = true;
+      advance(resnet(down_res[i][j], pass.cur, nullptr));
+      if (cfg.down_has_attn[i]) advance(transformer(down_attn[i][j], pass.cur));
+      pass.skips.push_back(pass.cur);
+      pass.cur_is_skip = true;
     }
     if (has_down[i]) {
       ConvOpts o;
       o.stride = 2; o.want_stats = true; o.split_in = st; o.split_out = st;
-      advance(ex.conv(down_sample[i], cur, nullptr, o));
-      skips.push_back(cur);
-      cur_is_skip = true;
+      advance(ex.conv(down_sample[i], pass.cur, nullptr, o));
+      pass.skips.push_back(pass.cur);
+      pass.cur_is_skip = true;
     }
   }
+}
+
+void ldiff_unet::run_mid() {
+  advance(resnet(mid_res[0], pass.cur, nullptr));
+  advance(transformer(mid_attn, pass.cur));
+  advance(resnet(mid_res[1], pass.cur, nullptr));
+}
+
+void ldiff_unet::forward_impl(const float* x, int B, int h, int w, float tval, const float* t_dev, float* out, hipStream_t s) {
+  LDIFF_CHECK(x && out && B >= 1 && h >= 1 && w >= 1, LDIFF_ERR_INVALID, "unet_forward: bad arguments (B=%d h=%d w=%d)", B, h, w);
+  LDIFF_CHECK(!encoder_only, LDIFF_ERR_STATE, "unet_forward: this handle is a ControlNet's trunk");
+  const int nb = cfg.n_blocks;
+  begin_pass(B, h, w, s);
+  if (cn) cn->ensure_scaled(cn_scale, s);
+  if (cn) cn->run_trunk(x, B, h, w, tval, t_dev, s);   // the attached ControlNet's blocks first, on the same stream: its skips and mid output wait in ITS workspace
+  run_down(x, tval, t_dev, nullptr);
+  const bool st = precision >= PREC_STREAM;
+  std::vector<Act>& skips = pass.skips;
+  Act& cur = pass.cur;
+  bool& cur_is_skip = pass.cur_is_skip;
   auto add_extra = [&](Act& a, const float* r) {   // a += r (fp32 NCHW); the producer's fused GroupNorm statistics no longer describe a
     launch_add_nchw_residual(a.p, a.ld(), a.lo(), r, a.B, a.C, a.H * a.W, s);
     if (a.st) { ex.arena.free(a.st); a.st = nullptr; a.st_R = 0; }
@@ -1071,12 +1115,32 @@ void ldiff_unet::forward_impl(const float* x, int B, int h, int w, float tval, c
     cur_is_skip = false;     // cur's buffer now belongs to the chain only
     for (size_t i = 0; i < skips.size(); ++i) add_extra(skips[i], extra_down[i]);
   }
-  advance(rb(mid_res[0], cur, nullptr));
-  advance(transformer(mid_attn, cur));
-  advance(rb(mid_res[1], cur, nullptr));
+  // Attached ControlNet: skip_i <- skip_i + scale * (W_i cnskip_i + b_i), one 1x1 launch each with the skip as the residual operand, written in this
+  // graph's own layout (split where the stream is split, fused statistics where the launch emits them).  The sums are new tensors (in the
+  // ControlNet's workspace: Act::borrowed), so the last skip's buffer -- the mid block's input -- stays as it is.
+  auto zero_conv = [&](size_t i, const Act& cnx, const Act& base) {
+    ConvOpts o;
+    o.res = &base; o.want_stats = true; o.split_in = cn->trunk.precision >= PREC_STREAM; o.split_out = st;
+    Act y = cn->trunk.ex.conv(cn->zs[i], cnx, nullptr, o);
+    y.borrowed = true;
+    return y;
+  };
+  if (cn) {
+    LDIFF_CHECK(cn->trunk.pass.skips.size() == skips.size(), LDIFF_ERR_RUNTIME, "unet: the attached ControlNet has %zu skip tensors, this UNet %zu", cn->trunk.pass.skips.size(), skips.size());
+    for (size_t i = 0; i < skips.size(); ++i) {
+      Act y = zero_conv(i, cn->trunk.pass.skips[i], skips[i]);
+      if (i + 1 < skips.size() || !cur_is_skip) ex.release(skips[i]);
+      skips[i] = y;
+    }
+    cur_is_skip = false;   // the stack's last entry is a tensor of its own now
+  }
+  run_mid();
   if (extra_mid) add_extra(cur, extra_mid);
+  if (cn) advance(zero_conv(skips.size(), cn->trunk.pass.cur, cur));
   extra_down.clear();
   extra_mid = nullptr;
+  auto rb = [&](const ResnetW& r, const Act& xin, const Act* skip) { return resnet(r, xin, skip); };
+  auto advance = [&](Act nxt) { this->advance(nxt); };
   for (int i = 0; i < nb; ++i) {
     for (size_t j = 0; j < up_res[i].size(); ++j) {
       Act sk = skips.back();
@@ -1107,8 +1171,146 @@ void ldiff_unet::forward_impl(const float* x, int B, int h, int w, float tval, c
   ex.release(g);
   ex.arena.free(o32);
   ex.release(cur);
-  ex.arena.free(temb_all);
+  ex.arena.free(pass.temb_all);
   LDIFF_CHECK(skips.empty(), LDIFF_ERR_RUNTIME, "unet: skip stack not empty at exit");
+}
+
+// ================================================================================================
+// ControlNet
+// ================================================================================================
+void ldiff_controlnet::build() {
+  trunk.encoder_only = true;
+  trunk.build();
+  trunk.ex.trace_tag = "cnet";
+  WeightStore& ws = trunk.ws;
+  LDIFF_CHECK(cond_channels >= 1 && cond_channels <= 8 && !emb_ch.empty(), LDIFF_ERR_INVALID, "controlnet: conditioning_channels must be 1..8 and the embedding needs channels");
+  for (int c : emb_ch) LDIFF_CHECK(c > 0 && c % 8 == 0, LDIFF_ERR_INVALID, "controlnet: embedding channel count %d must be a multiple of 8", c);
+  const std::string e = "controlnet_cond_embedding";
+  e_conv_in = ws.add_conv(e + ".conv_in", cond_channels, emb_ch[0], 3, true, 8);
+  for (size_t i = 0; i + 1 < emb_ch.size(); ++i) {
+    e_blocks.push_back(ws.add_conv(e + ".blocks." + std::to_string(2 * i), emb_ch[i], emb_ch[i], 3));
+    e_blocks.push_back(ws.add_conv(e + ".blocks." + std::to_string(2 * i + 1), emb_ch[i], emb_ch[i + 1], 3));
+  }
+  const ldiff_unet_cfg& cfg = trunk.cfg;
+  e_conv_out = ws.add_conv(e + ".conv_out", emb_ch.back(), cfg.block_out_channels[0], 3);
+  std::vector<int> skip_ch{cfg.block_out_channels[0]};
+  for (int i = 0; i < cfg.n_blocks; ++i) {
+    for (int j = 0; j < cfg.layers_per_block; ++j) skip_ch.push_back(cfg.block_out_channels[i]);
+    if (i != cfg.n_blocks - 1) skip_ch.push_back(cfg.block_out_channels[i]);
+  }
+  for (size_t i = 0; i < skip_ch.size(); ++i) zc.push_back(ws.add_conv("controlnet_down_blocks." + std::to_string(i), skip_ch[i], skip_ch[i], 1));
+  zc.push_back(ws.add_conv("controlnet_mid_block", skip_ch.back(), skip_ch.back(), 1));
+  for (const MatW& z : zc) {   // the copies the launches read: conditioning_scale folded into weights and bias (ensure_scaled)
+    MatW c = z;
+    c.w = ws.alloc_mat(z.Nrows, z.K);
+    c.b = ws.alloc_vec(z.Nrows);
+    zs.push_back(c);
+  }
+  ex_emb.weights_gen = &ws.generation;
+  ex_emb.nonfinite = trunk.nf.words;
+  ex_emb.trace_tag = "cnet-emb";
+}
+
+ldiff_controlnet::~ldiff_controlnet() {
+  if (emb) (void)hipFree(emb);
+  if (trunk.ctx_buf) (void)hipFree(trunk.ctx_buf);
+}
+
+// emb = conv_out(SiLU(conv(... SiLU(conv_in(cond)) ...))): every layer but the last on the conditioning-embedding kernel with its SiLU epilogue where
+// that kernel was measured faster (cond_conv_selected, kernels_cond.hip), elsewhere on the route plan_conv gives it plus a SiLU launch; the first one
+// on the fp32 image as hi | lo inside its 8 padded channels.  Depends on neither timestep nor latents: computed once per image, kept until the next call.
+void ldiff_controlnet::set_cond(const float* cond, int B, int H, int W, hipStream_t s) {
+  LDIFF_CHECK(cond && B >= 1 && H >= 1 && W >= 1, LDIFF_ERR_INVALID, "controlnet_set_cond: bad arguments (B=%d H=%d W=%d)", B, H, W);
+  int down = 1;
+  for (size_t i = 0; i + 1 < emb_ch.size(); ++i) down *= 2;
+  LDIFF_CHECK(H % down == 0 && W % down == 0, LDIFF_ERR_INVALID, "controlnet_set_cond: conditioning image %dx%d must be divisible by %d", H, W, down);
+  LDIFF_CHECK(trunk.ws.missing() == 0, LDIFF_ERR_STATE, "controlnet: %d weight tensors not loaded (first: %s)", trunk.ws.missing(), trunk.ws.missing_name(0));
+  HIP_CHECK(hipSetDevice(trunk.device));
+  const int C0 = trunk.cfg.block_out_channels[0], h = H / down, w = W / down;
+  const size_t need = (size_t)B * h * w * C0 * sizeof(f16);
+  if (need > emb_cap) {
+    if (emb) { HIP_CHECK(hipDeviceSynchronize()); HIP_CHECK(hipFree(emb)); emb = nullptr; }
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&emb), need));
+    emb_cap = need;
+    ++state_gen;   // a captured graph holds the old address
+  }
+  if (B != emb_B || h != emb_h || w != emb_w) ++state_gen;
+  Exec& ex = ex_emb;
+  ex.s = s;
+  ex.arena.reset();
+  int cmax = 8;
+  for (int c : emb_ch) cmax = std::max(cmax, c);
+  ex.arena.reserve((size_t)B * H * W * (8 + 2 * emb_ch[0]) * sizeof(f16) + (size_t)B * H * W / 4 * 3 * cmax * sizeof(f16) + need + (16u << 20));
+  const bool split_first = trunk.precision >= PREC_STREAM && e_conv_in.Cin_logical > 0;
+  Act x = ex.new_act(B, H, W, 8);
+  launch_nchw_f32_to_nhwc_f16(cond, x.p, B, cond_channels, H, W, 8, s, split_first ? cond_channels : 0);
+  auto layer = [&](const MatW& m, int stride, bool silu, bool split_in) {
+    ConvOpts o;
+    o.stride = stride; o.silu_out = silu; o.split_in = split_in;
+    Act y = ex.conv(m, x, nullptr, o);
+    ex.release(x);
+    x = y;
+    ex.trace("cond embedding", x);
+  };
+  layer(e_conv_in, 1, true, split_first);
+  for (size_t i = 0; i < e_blocks.size(); ++i) layer(e_blocks[i], i % 2 ? 2 : 1, true, false);
+  layer(e_conv_out, 1, false, false);
+  LDIFF_CHECK(x.H == h && x.W == w && x.C == C0 && !x.split, LDIFF_ERR_RUNTIME, "controlnet: embedding came out as [%d,%d,%d,%d]", x.B, x.H, x.W, x.C);
+  HIP_CHECK(hipMemcpyAsync(emb, x.p, need, hipMemcpyDeviceToDevice, s));
+  ex.release(x);
+  emb_B = B; emb_h = h; emb_w = w;
+}
+
+void ldiff_controlnet::ensure_scaled(float scale, hipStream_t s) {
+  if (zs_gen == trunk.ws.generation && zs_scale == scale) return;
+  for (size_t i = 0; i < zc.size(); ++i) {
+    launch_scale_f16(zc[i].w, zs[i].w, scale, (long long)zc[i].Nrows * zc[i].K, s);
+    launch_scale_f32(zc[i].b, zs[i].b, scale, zc[i].Nrows, s);
+    zs[i].dup.gen = zs[i].gfrag.gen = zs[i].gfrag_dup.gen = -1;   // weights derived from the old copy
+  }
+  zs_gen = trunk.ws.generation;
+  zs_scale = scale;
+  ++state_gen;
+}
+
+void ldiff_controlnet::run_trunk(const float* x, int B, int h, int w, float t, const float* t_dev, hipStream_t s) {
+  LDIFF_CHECK(emb && emb_h > 0, LDIFF_ERR_STATE, "controlnet: set_cond has not been called");
+  LDIFF_CHECK(emb_h == h && emb_w == w && (emb_B == B || emb_B == 1), LDIFF_ERR_INVALID,
+              "controlnet: the conditioning embedding is [%d, %d, %d] (image / 8), the sample [%d, %d, %d]", emb_B, emb_h, emb_w, B, h, w);
+  trunk.begin_pass(B, h, w, s);
+  const int C0 = trunk.cfg.block_out_channels[0];
+  Act e;
+  e.p = emb; e.B = B; e.H = h; e.W = w; e.C = C0;
+  Act rep;
+  if (emb_B != B) {   // one image for the whole batch
+    rep = trunk.ex.new_act(B, h, w, C0);
+    const size_t one = (size_t)h * w * C0 * sizeof(f16);
+    for (int b = 0; b < B; ++b) HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(rep.p) + b * one, emb, one, hipMemcpyDeviceToDevice, s));
+    e.p = rep.p;
+  }
+  trunk.run_down(x, t, t_dev, &e);
+  if (rep.p) trunk.ex.release(rep);
+  trunk.run_mid();
+}
+
+void ldiff_controlnet::forward(const float* x, int B, int h, int w, float t, float scale, float* const* down_out, int n_down, float* mid_out, hipStream_t s) {
+  LDIFF_CHECK(x && B >= 1 && h >= 1 && w >= 1, LDIFF_ERR_INVALID, "controlnet_forward: bad arguments (B=%d h=%d w=%d)", B, h, w);
+  LDIFF_CHECK(n_down == 0 || (down_out && n_down == trunk.n_skips()), LDIFF_ERR_INVALID, "controlnet_forward: %d output tensors given, this network has %d skip tensors", n_down, trunk.n_skips());
+  HIP_CHECK(hipSetDevice(trunk.device));
+  ensure_scaled(scale, s);
+  run_trunk(x, B, h, w, t, nullptr, s);
+  Exec& ex = trunk.ex;
+  auto emit = [&](const MatW& m, const Act& a, float* out) {
+    if (!out) return;
+    float* o32 = ex.tmp<float>((size_t)a.rows() * m.N);
+    ConvOpts o;
+    o.split_in = trunk.precision >= PREC_STREAM; o.out_f32 = o32; o.ldy_f32 = m.N;
+    ex.conv(m, a, nullptr, o);
+    launch_nhwc_f32_to_nchw_f32(o32, out, a.B, m.N, a.H, a.W, m.N, s);
+    ex.arena.free(o32);
+  };
+  for (int i = 0; i < n_down; ++i) emit(zs[i], trunk.pass.skips[i], down_out[i]);
+  emit(zs.back(), trunk.pass.cur, mid_out);
 }
 
 // ================================================================================================

@@ -6,6 +6,8 @@ They expose exactly the duck-typed surface the reference touches:
   unet.config.cross_attention_dim                     segmentor.py:33,188    ldiffusion.py:142
   UNet2DConditionModel.from_pretrained(dir) / .eval() / .to(device, dtype=) / .save_pretrained(dir)
                                                       segmentor.py:79        ldiffusion.py:139,273
+  controlnet(sample=, timestep=, encoder_hidden_states=, controlnet_cond=, return_dict=False) -> (list of 12 tensors, tensor)
+                                                      segmentor.py:357-363   (ControlNetModel below; the reference imports diffusers' class)
   vae.encode(x).latent_dist.mean / .sample();  vae.decode(z).sample;  .to() / .eval()
                                                       segmentor.py:99,339,379,437,519   ldiffusion.py:228,240
 All arithmetic runs in libldiff_hip.so; there is no torch/CPU fallback path.
@@ -46,6 +48,31 @@ class _Output:
         return (self.sample,)[i]
 
 
+def _fill_unet_cfg(cfg: dict) -> "_lib.UNetCfg":
+    """ldiff_unet_cfg from a validated UNet-shaped config dict (the UNet's own, or a ControlNet's trunk view)."""
+    c = _lib.UNetCfg()
+    c.in_channels, c.out_channels = cfg["in_channels"], cfg["out_channels"]
+    boc = cfg["block_out_channels"]
+    c.n_blocks = len(boc)
+    for i, v in enumerate(boc):
+        c.block_out_channels[i] = v
+        c.down_has_attn[i] = int(cfg["down_block_types"][i] == "CrossAttnDownBlock2D")
+        c.up_has_attn[i] = int(cfg["up_block_types"][i] == "CrossAttnUpBlock2D")
+    c.layers_per_block = cfg["layers_per_block"]
+    c.heads = cfg["attention_head_dim"]
+    c.cross_attention_dim = cfg["cross_attention_dim"]
+    c.norm_num_groups = cfg["norm_num_groups"]
+    c.norm_eps = cfg["norm_eps"]
+    c.flip_sin_to_cos = int(cfg["flip_sin_to_cos"])
+    c.freq_shift = float(cfg["freq_shift"])
+    return c
+
+
+def _tensor_key(t):
+    """Identity of a tensor's current contents: what set_context / set_cond cache by."""
+    return (t.data_ptr(), tuple(t.shape), t._version, t.dtype, t.device)
+
+
 class UNet2DConditionModel:
     def __init__(self, cfg: dict, state_dict, device=None):
         _lib.require_gpu()
@@ -56,21 +83,8 @@ class UNet2DConditionModel:
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         self.dtype = torch.float32
         self._lib = _lib.load()
-        c = _lib.UNetCfg()
-        c.in_channels, c.out_channels = cfg["in_channels"], cfg["out_channels"]
-        boc = cfg["block_out_channels"]
-        c.n_blocks = len(boc)
-        for i, v in enumerate(boc):
-            c.block_out_channels[i] = v
-            c.down_has_attn[i] = int(cfg["down_block_types"][i] == "CrossAttnDownBlock2D")
-            c.up_has_attn[i] = int(cfg["up_block_types"][i] == "CrossAttnUpBlock2D")
-        c.layers_per_block = cfg["layers_per_block"]
-        c.heads = cfg["attention_head_dim"]
-        c.cross_attention_dim = cfg["cross_attention_dim"]
-        c.norm_num_groups = cfg["norm_num_groups"]
-        c.norm_eps = cfg["norm_eps"]
-        c.flip_sin_to_cos = int(cfg["flip_sin_to_cos"])
-        c.freq_shift = float(cfg["freq_shift"])
+        c = _fill_unet_cfg(cfg)
+        self._controlnet = None
         self._h = C.c_void_p()
         _lib.check(self._lib.ldiff_unet_create(C.byref(self._h), C.byref(c), self.device.index or 0))
         self._host_sd = None
@@ -146,7 +160,7 @@ class UNet2DConditionModel:
         ehs = encoder_hidden_states
         if ehs.dim() != 3 or ehs.shape[-1] != self._cfg["cross_attention_dim"]:
             raise ValueError(f"encoder_hidden_states must be [B, L, {self._cfg['cross_attention_dim']}], got {tuple(ehs.shape)}")
-        key = (ehs.data_ptr(), tuple(ehs.shape), ehs._version, ehs.dtype, ehs.device)
+        key = _tensor_key(ehs)
         if key == self._ctx_key:
             return
         e = ehs.detach().to(self.device, dtype=torch.float32).contiguous()
@@ -154,8 +168,33 @@ class UNet2DConditionModel:
         self._ctx_key = key
         self._ctx_keepalive = (e, ehs)  # holding the source keeps its storage (and thus the cache key) from being recycled
 
+    # ---- ControlNet ----
+    def attach_controlnet(self, controlnet: "ControlNetModel", conditioning_scale: float = 1.0):
+        """Run `controlnet` inside this UNet's forward (include/ldiff.h ldiff_unet_attach_controlnet): `unet(x, t, ctx, controlnet_cond=c)` then
+        equals `unet(x, t, ctx, *controlnet(x, t, ctx, c, conditioning_scale))` in one call, without the thirteen fp32 tensors in between."""
+        if not isinstance(controlnet, ControlNetModel):
+            raise TypeError("attach_controlnet takes a ldiffusion_amd.models.ControlNetModel")
+        _lib.check(self._lib.ldiff_unet_attach_controlnet(self._h, controlnet._h, float(conditioning_scale)))
+        self._controlnet = controlnet   # (also keeps the borrowed handle alive)
+        return self
+
+    def detach_controlnet(self):
+        _lib.check(self._lib.ldiff_unet_attach_controlnet(self._h, None, 1.0))
+        self._controlnet = None
+        return self
+
     def __call__(self, sample, timestep, encoder_hidden_states, *args, **kwargs):
         down_res, mid_res = kwargs.get("down_block_additional_residuals"), kwargs.get("mid_block_additional_residual")
+        cond = kwargs.get("controlnet_cond")
+        if cond is not None and self._controlnet is None:
+            raise ValueError("controlnet_cond= needs an attached ControlNet (attach_controlnet)")
+        if self._controlnet is not None:
+            if cond is None:
+                raise ValueError("a ControlNet is attached: pass controlnet_cond= (or detach_controlnet())")
+            if down_res is not None or mid_res is not None:
+                raise ValueError("additional residuals cannot be combined with an attached ControlNet")
+            self._controlnet.set_context(encoder_hidden_states)
+            self._controlnet.set_cond(cond)
         if sample.dim() != 4 or sample.shape[1] != self._cfg["in_channels"]:
             raise ValueError(f"sample must be [B, {self._cfg['in_channels']}, h, w], got {tuple(sample.shape)}")
         B = sample.shape[0]
@@ -195,6 +234,151 @@ class UNet2DConditionModel:
         try:
             if getattr(self, "_h", None):
                 self._lib.ldiff_unet_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+class ControlNetOutput:
+    """`.down_block_res_samples` / `.mid_block_res_sample`, like diffusers' ControlNetOutput."""
+
+    def __init__(self, down, mid):
+        self.down_block_res_samples = down
+        self.mid_block_res_sample = mid
+
+    def __getitem__(self, i):
+        return (self.down_block_res_samples, self.mid_block_res_sample)[i]
+
+
+class ControlNetModel:
+    """diffusers' ControlNetModel for SD-v1.5-style configs on the HIP library (include/ldiff.h ldiff_controlnet_*): what
+    `Segmentor.ldiffusion_augment_for_multimodal` calls at /root/reference/segmentor.py:357-363."""
+
+    def __init__(self, cfg: dict, state_dict, device=None):
+        _lib.require_gpu()
+        cfg = configs.with_defaults(cfg, configs.CONTROLNET_DEFAULTS)
+        configs.validate_controlnet_config(cfg)
+        self._cfg = dict(cfg)
+        self._trunk_cfg = configs.controlnet_trunk_config(cfg)
+        self.config = SimpleNamespace(**cfg)
+        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.dtype = torch.float32
+        self._lib = _lib.load()
+        c = _fill_unet_cfg(self._trunk_cfg)
+        emb = list(cfg["conditioning_embedding_out_channels"])
+        self._h = C.c_void_p()
+        _lib.check(self._lib.ldiff_controlnet_create(C.byref(self._h), C.byref(c), cfg["conditioning_channels"], (C.c_int * len(emb))(*emb), len(emb),
+                                                     self.device.index or 0))
+        self._host_sd = None
+        self._ctx_key = None
+        self._cond_key = None
+        self.load_state_dict(state_dict)
+
+    def set_precision(self, mode: int):
+        _lib.check(self._lib.ldiff_controlnet_set_precision(self._h, int(mode)))
+        self._cond_key = None   # (the embedding's first layer follows the storage policy)
+        return self
+
+    def check_finite(self):
+        _lib.check(self._lib.ldiff_controlnet_check_finite(self._h, _lib.stream_ptr()))
+        return self
+
+    def load_state_dict(self, sd, strict=True):
+        _load_state_dict(self._lib, self._lib.ldiff_controlnet_load, self._h, sd, weights.controlnet_param_shapes(self._cfg))
+        n = self._lib.ldiff_controlnet_missing(self._h)
+        if n and strict:
+            names = [self._lib.ldiff_controlnet_missing_name(self._h, i).decode() for i in range(min(n, 5))]
+            raise RuntimeError(f"{n} ControlNet tensors missing from the checkpoint, e.g. {names}")
+        self._host_sd = {k: v.detach().to("cpu") for k, v in sd.items()}
+        self._ctx_key = None
+        self._cond_key = None
+
+    @classmethod
+    def from_pretrained(cls, path, subfolder=None, device=None, **_ignored):
+        if subfolder:
+            path = os.path.join(path, subfolder)
+        cfg, sd = weights.load_model_dir(path)
+        return cls(cfg, sd, device=device)
+
+    def save_pretrained(self, path):
+        weights.save_model_dir(path, self._cfg, self._host_sd)
+
+    def state_dict(self):
+        return dict(self._host_sd)
+
+    def parameters(self):
+        return iter(self._host_sd.values())
+
+    def eval(self):
+        return self
+
+    def to(self, *args, **kwargs):
+        dt = kwargs.get("dtype", None)
+        for a in args:
+            if isinstance(a, torch.dtype):
+                dt = a
+        if dt not in (None, torch.float32):
+            raise ValueError("the HIP ControlNet keeps the reference's float32 boundary (fp16 storage is internal)")
+        return self
+
+    def set_context(self, encoder_hidden_states: torch.Tensor):
+        ehs = encoder_hidden_states
+        if ehs.dim() != 3 or ehs.shape[-1] != self._cfg["cross_attention_dim"]:
+            raise ValueError(f"encoder_hidden_states must be [B, L, {self._cfg['cross_attention_dim']}], got {tuple(ehs.shape)}")
+        key = _tensor_key(ehs)
+        if key == self._ctx_key:
+            return
+        e = ehs.detach().to(self.device, dtype=torch.float32).contiguous()
+        _lib.check(self._lib.ldiff_controlnet_set_context(self._h, _lib.ptr(e), e.shape[0], e.shape[1], _lib.stream_ptr()))
+        self._ctx_key = key
+        self._ctx_keepalive = (e, ehs)
+
+    def set_cond(self, controlnet_cond: torch.Tensor):
+        """Runs the conditioning embedding (once per image: cached by the identity key `set_context` uses)."""
+        c = controlnet_cond
+        if c.dim() != 4 or c.shape[1] != self._cfg["conditioning_channels"]:
+            raise ValueError(f"controlnet_cond must be [B, {self._cfg['conditioning_channels']}, H, W], got {tuple(c.shape)}")
+        key = _tensor_key(c)
+        if key == self._cond_key:
+            return
+        x = c.detach().to(self.device, dtype=torch.float32).contiguous()
+        _lib.check(self._lib.ldiff_controlnet_set_cond(self._h, _lib.ptr(x), x.shape[0], x.shape[2], x.shape[3], _lib.stream_ptr()))
+        self._cond_key = key
+        self._cond_keepalive = (x, c)
+
+    def _skip_shapes(self, B, h, w):
+        return UNet2DConditionModel._skip_shapes(self, B, h, w)
+
+    def __call__(self, sample, timestep, encoder_hidden_states, controlnet_cond, conditioning_scale=1.0, guess_mode=False, return_dict=True, **unsupported):
+        if guess_mode:
+            raise ValueError("guess_mode=True is not supported")
+        extra = [k for k, v in unsupported.items() if v is not None]
+        if extra:
+            raise ValueError(f"unsupported ControlNet arguments: {extra}")
+        if sample.dim() != 4 or sample.shape[1] != self._cfg["in_channels"]:
+            raise ValueError(f"sample must be [B, {self._cfg['in_channels']}, h, w], got {tuple(sample.shape)}")
+        B = sample.shape[0]
+        if encoder_hidden_states.shape[0] not in (1, B):
+            raise ValueError(f"encoder_hidden_states batch {encoder_hidden_states.shape[0]} does not match sample batch {B}")
+        if controlnet_cond.shape[0] not in (1, B):
+            raise ValueError(f"controlnet_cond batch {controlnet_cond.shape[0]} does not match sample batch {B}")
+        self.set_context(encoder_hidden_states)
+        self.set_cond(controlnet_cond)
+        x = sample.detach().to(self.device, dtype=torch.float32).contiguous()
+        shapes = self._skip_shapes(B, x.shape[2], x.shape[3])
+        down = [torch.empty(s, device=self.device, dtype=torch.float32) for s in shapes]
+        mid = torch.empty(shapes[-1], device=self.device, dtype=torch.float32)
+        arr = (C.c_void_p * len(down))(*[t.data_ptr() for t in down])
+        _lib.check(self._lib.ldiff_controlnet_forward(self._h, _lib.ptr(x), B, x.shape[2], x.shape[3], float(timestep), float(conditioning_scale), arr, len(down),
+                                                      _lib.ptr(mid), _lib.stream_ptr()))
+        return ControlNetOutput(down, mid) if return_dict else (down, mid)
+
+    forward = __call__
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._lib.ldiff_controlnet_destroy(self._h)
                 self._h = None
         except Exception:
             pass

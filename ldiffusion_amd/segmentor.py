@@ -146,8 +146,10 @@ class Segmentor:
             residuals = controlnet(z_noisy, t, ctx, controlnet_cond = depth x 3)  at set_timesteps(1)     (:355-363)
             eps = unet(z_noisy, t, ctx, down_block_additional_residuals, mid_block_additional_residual)   (:366-372)
             recon = vae.decode((z_noisy - eps * depth) / 0.18215).sample                                  (:375-379)
-        Returns the list of [256, 256, 3] float arrays the reference returns (:381-386).  The ControlNet is the caller's module (the reference
-        trains none and ships no weights for one: SURVEY 8f); the UNet, the VAE and the Laplace transform run on the HIP kernels.
+        Returns the list of [256, 256, 3] float arrays the reference returns (:381-386).  `controlnet` is the caller's module (the reference
+        trains none and ships no weights for one: SURVEY 8f): handed a `models.ControlNetModel` it is attached to the UNet for the call and each sample
+        is ONE UNet call (the ControlNet's blocks inside it); any other object is called as the reference calls it.  The UNet, the VAE and the Laplace
+        transform run on the HIP kernels.
         `u` (optional, [B, 4, 32, 32] uniform draws in (-1, 1)) fixes the Laplace noise (parity is defined given u)."""
         from .pipeline import laplace_noise
         dev = self.device
@@ -158,6 +160,12 @@ class Segmentor:
         ids = torch.as_tensor(ids["input_ids"] if isinstance(ids, dict) else ids.input_ids, dtype=torch.long, device=dev)
         ctx = proj(pipeline.text_encoder(ids)["last_hidden_state"].to(device=dev, dtype=torch.float32)).to(dtype=torch.float32)
         recon = []
+        from .models import ControlNetModel, UNet2DConditionModel
+        fused = isinstance(controlnet, ControlNetModel) and isinstance(unet, UNet2DConditionModel)
+        if fused:
+            was_attached = unet._controlnet
+            if was_attached is not controlnet:
+                unet.attach_controlnet(controlnet)
         for i in range(dtm.shape[0]):
             dtm_i, rgb_i = dtm[i], rgb[i].unsqueeze(0)
             depth_condition = dtm_i.unsqueeze(0).repeat(1, 3, 1, 1)
@@ -168,11 +176,16 @@ class Segmentor:
             noisy = latents + noise * depth
             pipeline.scheduler.set_timesteps(1, device=dev)
             for t in pipeline.scheduler.timesteps:
+                if fused:   # the HIP ControlNet runs inside the UNet's forward: one call, no residual tensors in between
+                    eps = unet(noisy, t, encoder_hidden_states=ctx, controlnet_cond=depth_condition).sample
+                    continue
                 down, mid = controlnet(sample=noisy, timestep=t, encoder_hidden_states=ctx, controlnet_cond=depth_condition, return_dict=False)
                 eps = unet(noisy, t, encoder_hidden_states=ctx, down_block_additional_residuals=down, mid_block_additional_residual=mid).sample
             den = noisy - eps * depth
             img = vae.decode(den / 0.18215).sample
             recon.append(img.squeeze(0).permute(1, 2, 0).cpu().numpy())
+        if fused and was_attached is not controlnet:
+            unet.detach_controlnet()
         return recon
 
     @torch.no_grad()

@@ -106,6 +106,52 @@ def unet_param_shapes(cfg: dict) -> "OrderedDict[str, tuple]":
     return s
 
 
+def _skip_channels(cfg: dict):
+    """Channels of the UNet's skip tensors in stack order (conv_in's output first)."""
+    boc = cfg["block_out_channels"]
+    ch = [boc[0]]
+    for i in range(len(boc)):
+        ch += [boc[i]] * cfg["layers_per_block"]
+        if i != len(boc) - 1:
+            ch.append(boc[i])
+    return ch
+
+
+def controlnet_param_shapes(cfg: dict) -> "OrderedDict[str, tuple]":
+    """diffusers' ControlNetModel key layout: the UNet's conv_in / time_embedding / down_blocks / mid_block names unchanged, the
+    conditioning embedding, and one 1x1 conv per skip tensor plus one behind the mid block (stored [C, C, 1, 1])."""
+    s = OrderedDict()
+    boc = cfg["block_out_channels"]
+    temb = boc[0] * 4
+    ctx = cfg["cross_attention_dim"]
+    lpb = cfg["layers_per_block"]
+    _conv(s, "conv_in", cfg["in_channels"], boc[0], 3)
+    _lin(s, "time_embedding.linear_1", boc[0], temb)
+    _lin(s, "time_embedding.linear_2", temb, temb)
+    emb = list(cfg["conditioning_embedding_out_channels"])
+    _conv(s, "controlnet_cond_embedding.conv_in", cfg["conditioning_channels"], emb[0], 3)
+    for i in range(len(emb) - 1):
+        _conv(s, f"controlnet_cond_embedding.blocks.{2 * i}", emb[i], emb[i], 3)
+        _conv(s, f"controlnet_cond_embedding.blocks.{2 * i + 1}", emb[i], emb[i + 1], 3)
+    _conv(s, "controlnet_cond_embedding.conv_out", emb[-1], boc[0], 3)
+    ch = boc[0]
+    for i, t in enumerate(cfg["down_block_types"]):
+        for j in range(lpb):
+            _resnet(s, f"down_blocks.{i}.resnets.{j}", ch, boc[i], temb)
+            ch = boc[i]
+            if t == "CrossAttnDownBlock2D":
+                _transformer(s, f"down_blocks.{i}.attentions.{j}", ch, ctx)
+        if i != len(boc) - 1:
+            _conv(s, f"down_blocks.{i}.downsamplers.0.conv", ch, ch, 3)
+    for i, c in enumerate(_skip_channels(cfg)):
+        _conv(s, f"controlnet_down_blocks.{i}", c, c, 1)
+    _resnet(s, "mid_block.resnets.0", ch, ch, temb)
+    _transformer(s, "mid_block.attentions.0", ch, ctx)
+    _resnet(s, "mid_block.resnets.1", ch, ch, temb)
+    _conv(s, "controlnet_mid_block", ch, ch, 1)
+    return s
+
+
 def _vae_mid(s, p, c):
     _resnet(s, p + ".resnets.0", c, c, 0)
     a = p + ".attentions.0"
