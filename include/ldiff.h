@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define LDIFF_VERSION 180 /* 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
+#define LDIFF_VERSION 190 /* 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
 #define LDIFF_MAX_BLOCKS 8
 
 typedef enum { LDIFF_OK = 0, LDIFF_ERR_INVALID = -1, LDIFF_ERR_RUNTIME = -2, LDIFF_ERR_STATE = -3, LDIFF_ERR_NONFINITE = -4 } ldiff_status;
@@ -137,6 +137,37 @@ void ldiff_controlnet_destroy(ldiff_controlnet*);
  * biases when it changes, not applied per launch.  NULL detaches.  Widths, layers per block, input channels and device must agree (LDIFF_ERR_INVALID
  * names both).  The ControlNet is borrowed: keep it alive while attached.  ldiff_unet_check_finite then covers its blocks too. */
 int ldiff_unet_attach_controlnet(ldiff_unet*, ldiff_controlnet* cn_or_null, float conditioning_scale);
+
+/* ------------------------------------------------------------------------------------------------
+ * nnU-Net v2 PlainConvUNet, 2-D  --  replaces `self.network(x)` inside nnUNetPredictor's sliding window
+ *   segmentor.py:463-488 (Segmentor.inference_tissue_model_nnUNetv2), model/nnunetv2/inference/predict_from_raw_data.py:538-606
+ * as model/nnunetv2/utilities/get_network_from_plans.py builds it: per encoder stage n_conv_encoder[s] 3x3 convs (bias), the first with stride
+ * strides[s] (1 or 2, both axes), each followed by InstanceNorm2d(eps 1e-5, affine) and LeakyReLU(0.01); per decoder stage j (deepest first) a
+ * transposed conv with kernel = stride = strides[n_stages - 1 - j], cat((upsampled, skip), 1) and n_conv_decoder[j] convs; one 1x1 segmentation
+ * head behind the last decoder stage (deep supervision off).  features[s] are the stage widths (multiples of 16).
+ * Dataflow: a conv stores its raw fp16 output plus per-channel partial sums; a finalize launch makes per-(image, channel) scale / shift; the
+ * consumer applies affine + LeakyReLU in its prologue (ldiff_conv_args.lrelu_in).  No normalised tensor and no concat copy is written.
+ * Checkpoint names are those of dynamic_network_architectures' PlainConvUNet state dict, restated from knowledge of that package (UNPINNED: the
+ * package is not available to the test-suite; scripts/gen_golden_nnunet.py pins them where it is):
+ *   encoder.stages.{s}.0.convs.{i}.conv.{weight,bias}, encoder.stages.{s}.0.convs.{i}.norm.{weight,bias},
+ *   decoder.stages.{j}.convs.{i}.{conv,norm}.{weight,bias}, decoder.transpconvs.{j}.{weight [Cin, Cout, 2, 2], bias},
+ *   decoder.seg_layers.{n_stages - 2}.{weight,bias}.
+ * The aliases a checkpoint also holds (....all_modules.*, decoder.encoder.*, the unused seg_layers, an `_orig_mod.` prefix) are dropped by the
+ * python loader (ldiffusion_amd/nnunet.py clean_state_dict); ldiff_segnet_load refuses names it does not expect.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct ldiff_segnet ldiff_segnet;
+int ldiff_segnet_create(ldiff_segnet** out, int in_channels, int n_stages, const int* features, const int* strides, const int* n_conv_encoder,
+                        const int* n_conv_decoder /* n_stages - 1 entries */, int n_heads, int device);
+int ldiff_segnet_load(ldiff_segnet*, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim);
+int ldiff_segnet_missing(ldiff_segnet*);
+const char* ldiff_segnet_missing_name(ldiff_segnet*, int i);
+/* as ldiff_unet_set_graph: the launch sequence of a (B, H, W, out dtype) configuration is captured on its second use and replayed afterwards */
+int ldiff_segnet_set_graph(ldiff_segnet*, int on);
+int64_t ldiff_segnet_graph_replays(ldiff_segnet*);
+/* x [B, in_channels, H, W] f32 NCHW -> logits [B, n_heads, H, W] NCHW, out_dtype LDIFF_F32 or LDIFF_F16; H and W divisible by the product of the strides */
+int ldiff_segnet_forward(ldiff_segnet*, const void* x_dev, int B, int H, int W, void* logits_dev, int out_dtype, void* stream);
+int ldiff_segnet_check_finite(ldiff_segnet*, void* stream);
+void ldiff_segnet_destroy(ldiff_segnet*);
 
 /* ------------------------------------------------------------------------------------------------
  * AutoencoderKL  --  replaces vae.encode(x).latent_dist / vae.decode(z).sample / pipeline.decode_latents
@@ -302,6 +333,17 @@ typedef struct {
   int cond_conv;                                    /* the conditioning-embedding kernel: 0 = the executors' choice (the eligible launches that ask for silu_out: the embedding's own layers; a plain
                                                        launch of such a shape goes where it always went), 1 = every eligible launch (tests, timing), -1 = never (timing: the route such a
                                                        layer had before the kernel existed; silu_out is then refused) */
+  int lrelu_in;                                     /* with gn_scale / gn_shift: the activation behind the affine is LeakyReLU(0.01) instead of SiLU / none.  Bit 0: on the channels of x, bit 1: on
+                                                       those of x2 (a decoder conv of the nnU-Net head reads cat(upsampled, skip): identity scale / shift and no activation on the first source).
+                                                       silu_in must be 0.  Such launches run on the narrow kernel (seg_conv), on the halo-tile 3x3 kernels where the shape is theirs (64-channel multiples, stride 1:
+                                                       conv3x3_lrelu<...>), else on the register-staged implicit GEMM (igemm_lrelu<...>); with tconv, on the transposed-conv kernel */
+  int tconv;                                        /* 1: transposed conv with kernel = stride = 2 (tconv2x2<...>): ks = 2, stride = 2, Hout = 2 Hin, Wout = 2 Win, one source (C1 % 8 == 0), w =
+                                                       [4][Nrows][C1] f16 (tap dy * 2 + dx, then output channel; from torch's [Cin, Cout, 2, 2]), N == Nrows, N % 16 == 0, bias [N] added once per
+                                                       output pixel, plain fp16 output; optional gn_scale / gn_shift (+ lrelu_in bit 0) prologue.  No residual, statistics, split or fp32 output */
+  int seg_conv;                                     /* the narrow 3x3 kernel of the nnU-Net head (segconv<...>: pad 1, stride 1 | 2, C1 + C2 one of 8, 32, 64, N 32 | 64, optional gn_scale / gn_shift
+                                                       + lrelu_in prologue, bias, plain fp16 output, statistics of the fp32 sums in one row block per wave): 0 = the executors' choice (the eligible
+                                                       launches that carry lrelu_in; a plain launch of such a shape goes where it always went), 1 = every eligible launch (the head's first
+                                                       conv; tests, timing), -1 = never (timing: the implicit-GEMM route) */
 } ldiff_conv_args;
 int ldiff_op_conv(const ldiff_conv_args*, void* stream);
 /* row blocks per image the launch would emit statistics for (0 = unsupported for this shape) */
@@ -309,6 +351,11 @@ int ldiff_op_conv_stats_blocks(const ldiff_conv_args*);
 /* finalize producer-fused partial sums into per-(b,channel) scale/shift; part2 (second concat source) may be NULL */
 int ldiff_op_gn_finalize(const void* part1, int R1, int C1, const void* part2, int R2, int C2, int B, int HW, int groups, float eps,
                          const void* gamma, const void* beta, void* scale, void* shift, void* stream);
+/* InstanceNorm finalize of the nnU-Net head (ldiff_segnet): scale[b, ss_off + c] = gamma[c] * rstd, shift[b, ss_off + c] = beta[c] - mean * scale for c < C, rows of
+ * ld_ss fp32 entries, plus scale 1 / shift 0 in the `ident` leading entries of every row (the upsampled half of a decoder concat).  Statistics from `part`
+ * (f32 [B][C][R][2] partial {sum, sum of squares}, the layout of ldiff_conv_args.stats) or, with part NULL, from the tensor itself (x f16 [B, HW, ldx]). */
+int ldiff_op_in_finalize(const void* part, int R, const void* x_f16, int ldx, int B, int HW, int C, float eps, const void* gamma, const void* beta, void* scale,
+                         void* shift, int ld_ss, int ss_off, int ident, void* stream);
 int ldiff_op_attention(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, int B, int heads,
                        int Lq, int Lk, int d, int64_t q_bstride, int64_t kv_bstride, int64_t o_bstride, float scale, void* stream);
 /* The same with q ALREADY multiplied by scale * log2(e) (the executors do that in the fp32 epilogue of the q/k/v projection, so q is still rounded

@@ -187,6 +187,64 @@ void ldiff_controlnet_destroy(ldiff_controlnet* c) {
   (void)hipDeviceSynchronize();
   delete c;
 }
+// ---- nnU-Net tissue head ----
+int ldiff_segnet_create(ldiff_segnet** out, int in_channels, int n_stages, const int* features, const int* strides, const int* n_conv_encoder, const int* n_conv_decoder,
+                        int n_heads, int device) {
+  API_BEGIN
+  LDIFF_CHECK(out && features && strides && n_conv_encoder && n_conv_decoder && n_stages >= 2 && n_stages <= 16, LDIFF_ERR_INVALID, "segnet_create: null argument or n_stages outside 2..16");
+  int ndev = 0;
+  HIP_CHECK(hipGetDeviceCount(&ndev));
+  LDIFF_CHECK(device >= 0 && device < ndev, LDIFF_ERR_INVALID, "segnet_create: device %d not available (%d devices)", device, ndev);
+  HIP_CHECK(hipSetDevice(device));
+  ldiff_segnet* n = new ldiff_segnet();
+  n->device = device;
+  n->in_ch = in_channels; n->n_stages = n_stages; n->n_heads = n_heads;
+  n->features.assign(features, features + n_stages);
+  n->strides.assign(strides, strides + n_stages);
+  n->nce.assign(n_conv_encoder, n_conv_encoder + n_stages);
+  n->ncd.assign(n_conv_decoder, n_conv_decoder + n_stages - 1);
+  try { n->build(); } catch (...) { delete n; throw; }
+  *out = n;
+  API_END
+}
+int ldiff_segnet_load(ldiff_segnet* n, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
+  API_BEGIN
+  LDIFF_CHECK(n, LDIFF_ERR_INVALID, "segnet_load: null handle");
+  HIP_CHECK(hipSetDevice(n->device));
+  n->ws.load(name, host_ptr, dtype, shape, ndim);
+  API_END
+}
+int ldiff_segnet_missing(ldiff_segnet* n) { return n ? n->ws.missing() : -1; }
+const char* ldiff_segnet_missing_name(ldiff_segnet* n, int i) { return n ? n->ws.missing_name(i) : ""; }
+int ldiff_segnet_set_graph(ldiff_segnet* n, int on) {
+  API_BEGIN
+  LDIFF_CHECK(n, LDIFF_ERR_INVALID, "segnet_set_graph: null handle");
+  n->gc.enabled = on != 0;
+  if (!on) n->gc.drop();
+  API_END
+}
+int64_t ldiff_segnet_graph_replays(ldiff_segnet* n) { return n ? n->gc.replays : -1; }
+int ldiff_segnet_forward(ldiff_segnet* n, const void* x_dev, int B, int H, int W, void* logits_dev, int out_dtype, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(n, LDIFF_ERR_INVALID, "segnet_forward: null handle");
+  report_nonfinite(n->nf, "segnet_forward");
+  n->forward((const float*)x_dev, B, H, W, logits_dev, out_dtype, (hipStream_t)stream);
+  API_END
+}
+int ldiff_segnet_check_finite(ldiff_segnet* n, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(n, LDIFF_ERR_INVALID, "segnet_check_finite: null handle");
+  HIP_CHECK(hipSetDevice(n->device));
+  HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+  report_nonfinite(n->nf, "segnet_check_finite");
+  API_END
+}
+void ldiff_segnet_destroy(ldiff_segnet* n) {
+  if (!n) return;
+  (void)hipSetDevice(n->device);
+  (void)hipDeviceSynchronize();
+  delete n;
+}
 int ldiff_unet_attach_controlnet(ldiff_unet* u, ldiff_controlnet* c, float conditioning_scale) {
   API_BEGIN
   LDIFF_CHECK(u, LDIFF_ERR_INVALID, "unet_attach_controlnet: null handle");
@@ -605,7 +663,7 @@ static void conv_args_to_params(const ldiff_conv_args* a, ConvParams& p) {
   p.x = (const f16*)a->x; p.x2 = (const f16*)a->x2; p.C1 = a->C1; p.C2 = a->C2;
   p.B = a->B; p.Hin = a->Hin; p.Win = a->Win; p.Hout = a->Hout; p.Wout = a->Wout;
   p.ks = a->ks; p.stride = a->stride; p.pad_t = a->pad_t; p.pad_l = a->pad_l; p.ups = a->ups;
-  LDIFF_CHECK((p.ks == 1 || p.ks == 3) && (p.stride == 1 || p.stride == 2) && (p.ups == 0 || p.ups == 1), LDIFF_ERR_INVALID,
+  LDIFF_CHECK((p.ks == 1 || p.ks == 3 || (a->tconv && p.ks == 2)) && (p.stride == 1 || p.stride == 2) && (p.ups == 0 || p.ups == 1), LDIFF_ERR_INVALID,
               "op_conv: unsupported ks=%d stride=%d ups=%d", p.ks, p.stride, p.ups);
   p.w = (const f16*)a->w; p.N = a->N; p.Nrows = a->Nrows; p.K = a->ks * a->ks * (a->C1 + a->C2);
   p.n_real = a->n_real > 0 && a->n_real <= a->N ? a->n_real : 0;
@@ -625,6 +683,8 @@ static void conv_args_to_params(const ldiff_conv_args* a, ConvParams& p) {
   p.out_shift = a->out_shift;   // (plan_conv checks 0..16)
   p.silu_out = a->silu_out != 0;
   p.cond_force = a->cond_conv;
+  p.lrelu_in = a->lrelu_in; p.tconv = a->tconv; p.seg_conv = a->seg_conv;
+  if (p.tconv) p.K = a->C1;   // one GEMM over the coarse map: the four taps are column blocks, not K
 }
 int ldiff_op_conv(const ldiff_conv_args* a, void* stream) {
   API_BEGIN
@@ -679,6 +739,16 @@ int ldiff_op_conv(const ldiff_conv_args* a, void* stream) {
     }
   }
   launch_igemm(p, pl, st);
+  API_END
+}
+int ldiff_op_in_finalize(const void* part, int R, const void* x_f16, int ldx, int B, int HW, int C, float eps, const void* gamma, const void* beta, void* scale, void* shift,
+                         int ld_ss, int ss_off, int ident, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK((part || x_f16) && gamma && beta && scale && shift && B >= 1 && HW >= 1 && C >= 1 && ident >= 0 && ss_off >= ident && ss_off + C <= ld_ss && (part == nullptr || R >= 1) &&
+                  (x_f16 == nullptr || ldx >= C),
+              LDIFF_ERR_INVALID, "op_in_finalize: null argument, empty shape, or a row of %d entries that does not hold %d identity + %d channels at offset %d", ld_ss, ident, C, ss_off);
+  launch_in_finalize((const float*)part, R, (const f16*)x_f16, ldx, B, HW, C, eps, (const float*)gamma, (const float*)beta, (float*)scale, (float*)shift, ld_ss, ss_off, ident,
+                     (hipStream_t)stream, nullptr);
   API_END
 }
 int ldiff_op_conv_stats_blocks(const ldiff_conv_args* a) {

@@ -107,6 +107,10 @@ struct ConvParams {
   // launch that kernel does not take.  cond_force (ldiff_conv_args.cond_conv): 0 = that kernel takes the eligible launches that ask for silu_out (every layer
   // of the embedding it is made for; a plain launch of the same shape goes where it always went), 1 = every eligible launch (tests, timing), -1 = none
   int silu_out = 0, cond_force = 0;
+  // nnU-Net head (ldiff_segnet): LeakyReLU(0.01) behind the prologue's affine, bit 0 = on the channels of x, bit 1 = on those of x2 (ldiff_conv_args.lrelu_in); plan_conv
+  // sends such launches to igemm_lrelu<...> or, with tconv = 1 (transposed conv, kernel = stride = 2: ldiff_conv_args.tconv), to tconv2x2<...> (kernels_seg.hip)
+  int lrelu_in = 0, tconv = 0;
+  int seg_conv = 0;   // the narrow 3x3 kernel segconv<...> (kernels_seg.hip segconv_selected; ldiff_conv_args.seg_conv): 0 = launches with lrelu_in, 1 = every eligible launch, -1 = none
 };
 constexpr int LO8_SHIFT = 15;   // lo = x - fp16(x) of a GroupNorm + SiLU output: |lo| <= half an fp16 ulp = 2^-7 for |x| < 32, so lo * 2^15 <= 256 stays inside e4m3's 448;
                                 // for |x| in [32, 64) it reaches 512 and saturates at 448 (the correction term is clamped, harmless), as for everything beyond
@@ -116,7 +120,7 @@ void launch_lo8_weights(const f16* w, void* wd, int* scale_out, int Nrows, int t
 // count, the fused statistics' row blocks, the kernel with its tile, and the pre-packed weights it reads.  It writes ConvParams::splitk (0 = no
 // split), ::stats_R (0 = no fused statistics for this launch) and, with ConvPlan::fold_gn, the per-image weight strides; every buffer the plan
 // names (w_par, splitk_ws, stats, w_frag, folded weights) is the caller's to provide before launch_igemm.
-enum class ConvKernel { COND /* conditioning-embedding 3x3: kernels_cond.hip */, C3_NARROW, C3_NARROW_FOLD, C3_DATAFLOW, C3_PINGPONG, C3_HALO, GEMM_DF, GEMM_DMA, IGEMM, NONE /* an fp8 lo half the ping-pong kernel does not take */ };
+enum class ConvKernel { COND /* conditioning-embedding 3x3: kernels_cond.hip */, TCONV /* 2x2 transposed conv: kernels_seg.hip */, SEGCONV /* narrow 3x3 of the nnU-Net head: kernels_seg.hip */, C3_NARROW, C3_NARROW_FOLD, C3_DATAFLOW, C3_PINGPONG, C3_HALO, GEMM_DF, GEMM_DMA, IGEMM, NONE /* an fp8 lo half the ping-pong kernel does not take */ };
 enum class ConvWeights { PLAIN, FRAG, FRAG_PAR, FRAG_SC, GEMM_FRAG };   // launch_pack_frag_weights{,_par,_sc} / launch_pack_gemm_frag -> ConvParams::w_frag
 struct ConvAsk {          // what the caller states beside the launch itself
   int splitk = 0;         // 0: plan a split count; 1: never split; >= 2: this count (ldiff_op_conv: tests, timing), checked against the K steps
@@ -136,6 +140,15 @@ void launch_igemm(const ConvParams& p, const ConvPlan& pl, hipStream_t s);   // 
 // 3x3 conv + bias (+ SiLU epilogue) at the channel counts of the ControlNet's conditioning embedding (3 / 16 / 32 / 96 in, 16 / 32 / 96 / 256 out): kernels_cond.hip
 bool cond_conv_selected(const ConvParams& p);
 void launch_cond_conv(const ConvParams& p, hipStream_t s);
+// nnU-Net head (kernels_seg.hip): the 2x2 transposed conv, InstanceNorm finalize (per-(image, channel) scale / shift from fused partial sums, or from the tensor itself where
+// the producer emitted none), and the logits' layout cast
+void launch_tconv2x2(const ConvParams& p, hipStream_t s);
+bool segconv_selected(const ConvParams& p);
+int segconv_stats_blocks(const ConvParams& p);
+void launch_segconv(const ConvParams& p, hipStream_t s);
+void launch_in_finalize(const float* part, int R, const f16* x_or_null, int ldx, int B, int HW, int C, float eps, const float* gamma, const float* beta, float* scale, float* shift,
+                        int ld_ss, int ss_off, int ident /* leading channels set to scale 1, shift 0 */, hipStream_t s, int* nonfinite);
+void launch_nhwc_f32_to_nchw(const float* x, void* y, int B, int C, int H, int W, int ldx, int out_f16, hipStream_t s);
 void launch_scale_f16(const f16* x, f16* y, float a, long long n, hipStream_t s);   // y = f16(x * a)
 bool conv3x3_eligible(const ConvParams& p);   // the halo-tile 3x3 family: kernels_conv3x3.hip
 void launch_splitk_reduce(const ConvParams& p, hipStream_t s);   // sums p.splitk fp32 partials of splitk_ws and applies the epilogue (+ the fused GroupNorm statistics: R = H W / 32)
@@ -398,6 +411,25 @@ __device__ __forceinline__ void gn_quad(unsigned xa, unsigned xb, float s0, floa
     oa = gn_pair<false>(xa, s0, t0, s1, t1);
     ob = gn_pair<false>(xb, s2, t2, s3, t3);
   }
+}
+// InstanceNorm-apply + LeakyReLU of the nnU-Net head's prologues (ConvParams::lrelu_in), ONE definition for every kernel that has it (segconv, tconv2x2,
+// igemm_lrelu, conv3x3_lrelu): y = fma(x, scale, shift) in fp32, y < 0 ? y * slope : y (slope 0.01, or 1 for a source that passes through), ONE rounding to fp16
+__device__ __forceinline__ float in_lrelu(float x, float s, float t, float slope) {
+  const float v = __builtin_fmaf(x, s, t);
+  return v < 0.f ? v * slope : v;
+}
+__device__ __forceinline__ unsigned in_lrelu_pair(unsigned xw, float s0, float t0, float s1, float t1, float slope) {
+  const f16x2 h = __builtin_bit_cast(f16x2, xw);
+  f16x2 o;
+  o[0] = (f16)in_lrelu((float)h[0], s0, t0, slope);
+  o[1] = (f16)in_lrelu((float)h[1], s1, t1, slope);
+  return __builtin_bit_cast(unsigned, o);
+}
+__device__ __forceinline__ uint4 in_lrelu_apply8(uint4 raw, const float* __restrict__ sc, const float* __restrict__ sh, float slope) {
+  const float4 s0 = *reinterpret_cast<const float4*>(sc), s1 = *reinterpret_cast<const float4*>(sc + 4);
+  const float4 t0 = *reinterpret_cast<const float4*>(sh), t1 = *reinterpret_cast<const float4*>(sh + 4);
+  return make_uint4(in_lrelu_pair(raw.x, s0.x, t0.x, s0.y, t0.y, slope), in_lrelu_pair(raw.y, s0.z, t0.z, s0.w, t0.w, slope),
+                    in_lrelu_pair(raw.z, s1.x, t1.x, s1.y, t1.y, slope), in_lrelu_pair(raw.w, s1.z, t1.z, s1.w, t1.w, slope));
 }
 template <int K>
 __device__ __forceinline__ float comp8(const float4& a, const float4& b) {

@@ -125,17 +125,38 @@ ConvPlan plan_conv(ConvParams& p, const ConvAsk& ask) {
     p.stats_R = 0;
     return pl;
   }
+  // 0b. the nnU-Net head's launches (ConvParams::lrelu_in / tconv): the 2x2 transposed conv has a kernel of its own (kernels_seg.hip); a conv with the
+  //     LeakyReLU prologue runs on the halo-tile 3x3 kernels where the launch is theirs (64-channel multiples, stride 1: conv3x3_lrelu<...>), else on the
+  //     register-staged implicit GEMM (igemm_lrelu<...>)
+  LDIFF_CHECK(!q.lrelu_in || (q.gn_scale && q.gn_shift && !q.silu_in && (q.lrelu_in & ~3) == 0), LDIFF_ERR_INVALID, "conv: lrelu_in = %d needs gn_scale / gn_shift, silu_in = 0 and bits 0..1 only", q.lrelu_in);
+  if (q.tconv) {
+    LDIFF_CHECK(q.tconv == 1 && q.ks == 2 && q.stride == 2 && !q.ups && !q.x2 && q.C2 == 0 && q.C1 % 8 == 0 && q.Hout == 2 * q.Hin && q.Wout == 2 * q.Win && q.N == q.Nrows && q.N % 16 == 0 &&
+                    q.K == q.C1 && !q.res && !q.temb && !q.out_f32 && !q.y_lo && !q.geglu && !q.silu_in && !q.silu_out && !q.out_shift && !q.xs && !q.lo8_slab0 && ask.splitk < 2 && !ask.stats &&
+                    q.ldy >= q.N && q.ldy % 4 == 0 && (q.ld1 == 0 || (q.ld1 >= q.C1 && q.ld1 % 8 == 0)) && (long long)q.B * q.Hin * q.Win == q.M / 4 && q.M % 4 == 0,
+                LDIFF_ERR_INVALID, "conv: tconv takes kernel = stride = 2, one source with C1 %% 8 == 0, N == Nrows, N %% 16 == 0, Hout = 2 Hin, a plain fp16 output and bias only (C1=%d N=%d Nrows=%d ks=%d stride=%d)",
+                q.C1, q.N, q.Nrows, q.ks, q.stride);
+    pl.kernel = ConvKernel::TCONV;
+    p.splitk = 0;
+    p.stats_R = 0;
+    return pl;
+  }
+  if (ask.splitk < 2 && segconv_selected(q)) {   // the narrow 3x3 convs of the head's full- and half-resolution stages; statistics per wave (one row block each)
+    pl.kernel = ConvKernel::SEGCONV;
+    p.splitk = 0;
+    p.stats_R = ask.stats ? segconv_stats_blocks(q) : 0;
+    return pl;
+  }
   LDIFF_CHECK(!q.silu_out, LDIFF_ERR_INVALID, "conv: a SiLU epilogue (silu_out) exists only in the conditioning-embedding kernel, which does not take this launch (Cin=%d N=%d ks=%d stride=%d)",
               q.C1 + q.C2, q.N, q.ks, q.stride);
   // 1. the kernel family.  GroupNorm -> 1x1 conv / Linear with no activation in between (VAE attention q/k/v; transformer proj_in under PREC_FAST):
   //    the normalisation folded into per-image weights and bias where the plain LDS-DMA GEMM takes that form, instead of the register-staged GN prologue
-  if (ask.fold_gn && q.gn_scale && !q.silu_in && q.ks == 1 && !q.x2 && !q.out_f32 && !q.geglu) {
+  if (ask.fold_gn && q.gn_scale && !q.silu_in && !q.lrelu_in && q.ks == 1 && !q.x2 && !q.out_f32 && !q.geglu) {
     ConvParams f = q;
     f.gn_scale = nullptr; f.gn_shift = nullptr;
     f.w_bstride = (long long)q.Nrows * q.K; f.bias_bstride = q.Nrows;
     if (gemm_dma_eligible(f)) { q = f; pl.fold_gn = true; }
   }
-  const bool c3 = conv3x3_eligible(q), gemm = !c3 && gemm_dma_eligible(q);
+  const bool c3 = conv3x3_eligible(q) && !(q.lrelu_in && q.ups), gemm = !c3 && !q.lrelu_in && gemm_dma_eligible(q);   // (LeakyReLU prologue: the halo-tile 3x3 kernels and the implicit GEMM have it)
   // 2. nearest-2x upsample + conv3x3 folded algebraically: four 2x2 convs with pre-summed taps (ConvParams::w_par)
   pl.parity = q.ups && c3;
   if (pl.parity) q.w_par = reinterpret_cast<const f16*>(placeholder);
@@ -160,7 +181,10 @@ ConvPlan plan_conv(ConvParams& p, const ConvAsk& ask) {
   if (c3) {
     const bool par = pl.parity;
     const int Ht = par ? q.Hin : q.Hout, Wt = par ? q.Win : q.Wout;
-    if (q.lo8_slab0) pl.kernel = q.splitk <= 1 && conv3x3p_selected(q) ? ConvKernel::C3_PINGPONG : ConvKernel::NONE;   // the one kernel that reads an fp8 lo half
+    if (q.lrelu_in) {   // the halo-tile kernels are the 3x3 family with the LeakyReLU prologue (conv3x3_lrelu<...>)
+      pl.kernel = ConvKernel::C3_HALO;
+      c3_tile(q, pl);
+    } else if (q.lo8_slab0) pl.kernel = q.splitk <= 1 && conv3x3p_selected(q) ? ConvKernel::C3_PINGPONG : ConvKernel::NONE;   // the one kernel that reads an fp8 lo half
     else if (conv3x3n_selected(q)) pl.kernel = conv3x3nt_selected(q) ? ConvKernel::C3_NARROW_FOLD : ConvKernel::C3_NARROW;
     else if (conv3x3d_selected(q)) pl.kernel = ConvKernel::C3_DATAFLOW;
     else if (conv3x3p_selected(q)) pl.kernel = ConvKernel::C3_PINGPONG;

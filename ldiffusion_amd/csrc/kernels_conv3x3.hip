@@ -23,7 +23,9 @@ __device__ __forceinline__ int swz8(int row, int chunk) { return chunk ^ ((row >
 typedef __attribute__((address_space(1))) const void gptr_t;
 typedef __attribute__((address_space(3))) void lptr_t;
 
-template <int TH, int TW, int BN, bool GN>
+// LR (with GN): the prologue's activation is LeakyReLU(0.01) on the sources ConvParams::lrelu_in names (the nnU-Net head: InstanceNorm scale / shift; a slab of
+// 64 channels lies in ONE source, so the slope is uniform per slab: 0.01, or 1 for a source that passes through); the SiLU / plain forms do not see it
+template <int TH, int TW, int BN, bool GN, bool LR = false>
 __global__ __launch_bounds__(256, 2) void conv3x3_kernel(const ConvParams p) {   // 2 waves/SIMD = 2 workgroups per CU
   constexpr int BM = TH * TW, HWD = TW + 2, HP = (TH + 2) * (TW + 2);
   constexpr int MT = BM / 32, NT = BN / 32;
@@ -81,10 +83,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(const ConvParams p) {  
   }
   uint4 ra[A_IT];
   float4 gs0, gs1, gt0, gt1;
+  float lslope = 1.0f;
   auto load_halo = [&](int c) {
     const int cb = c * 64;
     const f16* src; int cs, Cs;
     if (cb < p.C1) { src = p.x; cs = cb; Cs = p.ld1 ? p.ld1 : p.C1; } else { src = p.x2; cs = cb - p.C1; Cs = p.ld2 ? p.ld2 : p.C2; }
+    if (LR) lslope = ((cb < p.C1 ? p.lrelu_in : p.lrelu_in >> 1) & 1) ? 0.01f : 1.0f;
 #pragma unroll
     for (int i = 0; i < A_IT; ++i) {
       uint4 v = make_uint4(0, 0, 0, 0);
@@ -109,7 +113,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(const ConvParams p) {  
       uint4 v = ra[i];
       if (GN && a_off[i] >= 0) {   // zero padding applies to the normalised tensor: padding chunks stay exactly 0
         const uint4 r = v;
-        if (silu) {
+        if constexpr (LR) {
+          v.x = in_lrelu_pair(r.x, sv[0], tv[0], sv[1], tv[1], lslope); v.y = in_lrelu_pair(r.y, sv[2], tv[2], sv[3], tv[3], lslope);
+          v.z = in_lrelu_pair(r.z, sv[4], tv[4], sv[5], tv[5], lslope); v.w = in_lrelu_pair(r.w, sv[6], tv[6], sv[7], tv[7], lslope);
+        } else if (silu) {
           v.x = gn_pair<true>(r.x, sv[0], tv[0], sv[1], tv[1]); v.y = gn_pair<true>(r.y, sv[2], tv[2], sv[3], tv[3]);
           v.z = gn_pair<true>(r.z, sv[4], tv[4], sv[5], tv[5]); v.w = gn_pair<true>(r.w, sv[6], tv[6], sv[7], tv[7]);
         } else {
@@ -338,7 +345,7 @@ __device__ __forceinline__ unsigned long long w_stamp() {
 #define WACC(i, expr)
 #endif
 
-template <int BN, bool GN>
+template <int BN, bool GN, bool LR = false>   // LR: see conv3x3_kernel
 __global__ __launch_bounds__(256, BN > 128 ? 1 : 2) void conv3x3w_kernel(const ConvParams p) {
   constexpr int TH = 8, TW = 16, BM = 128, HWD = 18, HP = 180, MT = 4, NT = BN / 32, A_IT = 6, NP = BN / 32;
   constexpr int ROWB = HWD * 128;                                  // bytes per halo row
@@ -407,10 +414,12 @@ __global__ __launch_bounds__(256, BN > 128 ? 1 : 2) void conv3x3w_kernel(const C
   }
   uint4 ra[A_IT];
   float4 gs0, gs1, gt0, gt1;
+  float lslope = 1.0f;
   auto load_halo = [&](int c) {
     const int cb = c * 64;
     const f16* src; int cs, Cs;
     if (cb < p.C1) { src = p.x; cs = cb; Cs = p.ld1 ? p.ld1 : p.C1; } else { src = p.x2; cs = cb - p.C1; Cs = p.ld2 ? p.ld2 : p.C2; }
+    if (LR) lslope = ((cb < p.C1 ? p.lrelu_in : p.lrelu_in >> 1) & 1) ? 0.01f : 1.0f;
     src += cs + kc * 8;
 #pragma unroll
     for (int i = 0; i < A_IT; ++i) ra[i] = *reinterpret_cast<const uint4*>(src + (size_t)a_pix[i] * (unsigned)Cs);
@@ -432,7 +441,10 @@ __global__ __launch_bounds__(256, BN > 128 ? 1 : 2) void conv3x3w_kernel(const C
   auto xform_store = [&](auto ic, unsigned bufoff) {   // chunk i of the staged slab -> LDS (normalised, activated, masked)
     constexpr int i = decltype(ic)::value;
     uint4 v = ra[i];
-    if (GN) {
+    if constexpr (LR) {
+      v.x = in_lrelu_pair(ra[i].x, gs0.x, gt0.x, gs0.y, gt0.y, lslope); v.y = in_lrelu_pair(ra[i].y, gs0.z, gt0.z, gs0.w, gt0.w, lslope);
+      v.z = in_lrelu_pair(ra[i].z, gs1.x, gt1.x, gs1.y, gt1.y, lslope); v.w = in_lrelu_pair(ra[i].w, gs1.z, gt1.z, gs1.w, gt1.w, lslope);
+    } else if (GN) {
       if (silu) {
         v.x = gn_pair<true>(ra[i].x, gs0.x, gt0.x, gs0.y, gt0.y); v.y = gn_pair<true>(ra[i].y, gs0.z, gt0.z, gs0.w, gt0.w);
         v.z = gn_pair<true>(ra[i].z, gs1.x, gt1.x, gs1.y, gt1.y); v.w = gn_pair<true>(ra[i].w, gs1.z, gt1.z, gs1.w, gt1.w);
@@ -500,7 +512,8 @@ __global__ __launch_bounds__(256, BN > 128 ? 1 : 2) void conv3x3w_kernel(const C
   // its 16 cycles) and the k-half-0 fragments' registers are free for its temporaries
   auto xform_pair = [&](auto ic, auto dc, auto siluc) -> unsigned {   // dword d (elements 2d, 2d+1) of staged chunk i
     constexpr int i = decltype(ic)::value, d = decltype(dc)::value;
-    return gn_pair<decltype(siluc)::value>(dword4<d>(ra[i]), comp8<2 * d>(gs0, gs1), comp8<2 * d>(gt0, gt1), comp8<2 * d + 1>(gs0, gs1), comp8<2 * d + 1>(gt0, gt1));
+    if constexpr (LR) return in_lrelu_pair(dword4<d>(ra[i]), comp8<2 * d>(gs0, gs1), comp8<2 * d>(gt0, gt1), comp8<2 * d + 1>(gs0, gs1), comp8<2 * d + 1>(gt0, gt1), lslope);
+    else return gn_pair<decltype(siluc)::value>(dword4<d>(ra[i]), comp8<2 * d>(gs0, gs1), comp8<2 * d>(gt0, gt1), comp8<2 * d + 1>(gs0, gs1), comp8<2 * d + 1>(gt0, gt1));
   };
   auto mask_store = [&](auto ic, uint4 v, unsigned bufoff) {
     constexpr int i = decltype(ic)::value;
@@ -892,17 +905,17 @@ static bool conv3x3_img_fast(const ConvParams& p, int tiles_per_image, int ntn, 
                                  // layers 77.4 -> 58.1 us; 16 x 16: -2 ... -8 %; 32 x 32 and larger: no change)
 }
 
-template <int TH, int TW, int BN, bool GN>
+template <int TH, int TW, int BN, bool GN, bool LR = false>
 void launch_c3(const ConvParams& p, hipStream_t s) {
   constexpr int HP = (TH + 2) * (TW + 2);
   const size_t smem = (size_t)(2 * HP * 8 + 2 * BN * 8) * 16;
-  auto kern = conv3x3_kernel<TH, TW, BN, GN>;
+  auto kern = conv3x3_kernel<TH, TW, BN, GN, LR>;
   ensure_dyn_smem(reinterpret_cast<const void*>(kern), (int)smem);
   const bool par = p.w_par != nullptr;
   const int Ht = par ? p.Hin : p.Hout, Wt = par ? p.Win : p.Wout;
   const int tiles = p.B * ((Ht + TH - 1) / TH) * ((Wt + TW - 1) / TW);
   const int ntn = (p.N + BN - 1) / BN;
-  static const std::string pname = std::string("conv3x3<") + std::to_string(TH) + "x" + std::to_string(TW) + "," + std::to_string(BN) + (GN ? ",gn>" : ">");
+  static const std::string pname = std::string(LR ? "conv3x3_lrelu<" : "conv3x3<") + std::to_string(TH) + "x" + std::to_string(TW) + "," + std::to_string(BN) + (GN && !LR ? ",gn>" : ">");
   const double bytes = (double)p.B * p.Hin * p.Win * (p.C1 + p.C2) * 2.0 + (double)p.N * p.K * 2.0 + (double)p.M * p.N * (p.out_f32 ? 4.0 : (p.y_lo ? 4.0 : 2.0)) +
                        (p.res ? (double)p.M * p.N * (p.res_lo ? 4.0 : 2.0) : 0.0);
   // flops = MFMA work actually executed: parity mode (nearest-2x folded into 4 taps) runs 16/36 of the 9-tap MACs
@@ -916,17 +929,17 @@ void launch_c3(const ConvParams& p, hipStream_t s) {
   if (S > 1) launch_splitk_reduce_impl(p, s);
 }
 
-template <int BN, bool GN>
+template <int BN, bool GN, bool LR = false>
 void launch_c3w(const ConvParams& p, hipStream_t s) {
   constexpr int TH = 8, TW = 16, HP = 180;
   const size_t smem = (size_t)2 * HP * 128 + (BN == 160 ? 3 : 2) * BN * 128 + 1536;   // (the 160-column kernel's weight ring has three slots)
-  auto kern = conv3x3w_kernel<BN, GN>;
+  auto kern = conv3x3w_kernel<BN, GN, LR>;
   ensure_dyn_smem(reinterpret_cast<const void*>(kern), (int)smem);
   const bool par = p.w_par != nullptr;
   const int Ht = par ? p.Hin : p.Hout, Wt = par ? p.Win : p.Wout;
   const int tiles = p.B * ((Ht + TH - 1) / TH) * ((Wt + TW - 1) / TW);
   const int ntn = (p.N + BN - 1) / BN;
-  static const std::string pname = std::string("conv3x3<8x16,") + std::to_string(BN) + (GN ? ",gn>" : ">");
+  static const std::string pname = std::string(LR ? "conv3x3_lrelu<8x16," : "conv3x3<8x16,") + std::to_string(BN) + (GN && !LR ? ",gn>" : ">");
   const double bytes = (double)p.B * p.Hin * p.Win * (p.C1 + p.C2) * 2.0 + (double)p.N * p.K * 2.0 + (double)p.M * p.N * (p.out_f32 ? 4.0 : (p.y_lo ? 4.0 : 2.0)) +
                        (p.res ? (double)p.M * p.N * (p.res_lo ? 4.0 : 2.0) : 0.0);
   // flops = MFMA work actually executed: parity mode (nearest-2x folded into 4 taps) runs 16/36 of the 9-tap MACs
@@ -945,12 +958,14 @@ void launch_c3w(const ConvParams& p, hipStream_t s) {
 }
 template <int BN>
 void launch_c3w_gn(const ConvParams& p, hipStream_t s) {
-  if (p.gn_scale) launch_c3w<BN, true>(p, s); else launch_c3w<BN, false>(p, s);
+  if (p.lrelu_in) launch_c3w<BN, true, true>(p, s);
+  else if (p.gn_scale) launch_c3w<BN, true>(p, s); else launch_c3w<BN, false>(p, s);
 }
 
 template <int TH, int TW, int BN>
 void launch_c3_gn(const ConvParams& p, hipStream_t s) {
-  if (p.gn_scale) launch_c3<TH, TW, BN, true>(p, s); else launch_c3<TH, TW, BN, false>(p, s);
+  if (p.lrelu_in) launch_c3<TH, TW, BN, true, true>(p, s);
+  else if (p.gn_scale) launch_c3<TH, TW, BN, true>(p, s); else launch_c3<TH, TW, BN, false>(p, s);
 }
 
 }  // namespace

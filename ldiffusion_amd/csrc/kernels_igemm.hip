@@ -43,8 +43,9 @@ __device__ __forceinline__ uint4 gn_apply8(uint4 raw, const float* __restrict__ 
   return __builtin_bit_cast(uint4, o);
 }
 
-template <int BM, int BN, bool FAST, bool GN>
-__global__ __launch_bounds__(256, 2) void igemm_kernel(const ConvParams p) {   // 2 waves/SIMD: accumulators stay in VGPRs
+// LR: the prologue's activation is LeakyReLU (igemm_lrelu_kernel below); the SiLU / plain instantiations do not see it
+template <int BM, int BN, bool FAST, bool GN, bool LR>
+__device__ __forceinline__ void igemm_body(const ConvParams& p) {
   constexpr int MT = BM / 32, NT = BN / 32;       // 16x16 tiles per wave along m / n (wave tile = BM/2 x BN/2)
   constexpr int A_IT = BM * CPR / 256, B_IT = BN * CPR / 256;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -80,6 +81,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const ConvParams p) {   /
 
   uint4 ra[A_IT], rw[B_IT];
   int gidx[A_IT];  // b*Cin + c of the chunk (GN path), -1 when the chunk is padding
+  bool gact[A_IT]; // LR: the chunk's source takes the activation
 
   auto load_tiles = [&](int kt) {
     const int kbase = kt * BK;
@@ -106,6 +108,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const ConvParams p) {   /
         long long pix = ((long long)rb[i] * p.Hin + (iy >> p.ups)) * p.Win + (ix >> p.ups);
         v = *reinterpret_cast<const uint4*>(src + pix * Cs + cs);
         gidx[i] = rb[i] * Cin + c;
+        if (LR) gact[i] = ((c < p.C1 ? p.lrelu_in : p.lrelu_in >> 1) & 1) != 0;
       }
       ra[i] = v;
     }
@@ -124,7 +127,8 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const ConvParams p) {   /
     for (int i = 0; i < A_IT; ++i) {
       int row = (tid >> 3) + i * 32;
       uint4 v = ra[i];
-      if (GN) { if (gidx[i] >= 0) v = gn_apply8(v, p.gn_scale + gidx[i], p.gn_shift + gidx[i], p.silu_in); }
+      if (LR) { if (gidx[i] >= 0) v = in_lrelu_apply8(v, p.gn_scale + gidx[i], p.gn_shift + gidx[i], gact[i] ? 0.01f : 1.0f); }
+      else if (GN) { if (gidx[i] >= 0) v = gn_apply8(v, p.gn_scale + gidx[i], p.gn_shift + gidx[i], p.silu_in); }
       sA[buf * BM * CPR + row * CPR + swz(row, kc)] = v;
     }
 #pragma unroll
@@ -268,13 +272,21 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const ConvParams p) {   /
 }
 
 template <int BM, int BN, bool FAST, bool GN>
+__global__ __launch_bounds__(256, 2) void igemm_kernel(const ConvParams p) {   // 2 waves/SIMD: accumulators stay in VGPRs
+  igemm_body<BM, BN, FAST, GN, false>(p);
+}
+template <int BM, int BN, bool FAST>
+__global__ __launch_bounds__(256, 2) void igemm_lrelu_kernel(const ConvParams p) { igemm_body<BM, BN, FAST, true, true>(p); }
+
+template <int BM, int BN, bool FAST, bool GN, bool LR = false>
 static void launch_cfg(const ConvParams& p, hipStream_t s) {
   const size_t smem = 2 * (BM + BN) * BK * sizeof(f16);
-  auto kern = igemm_kernel<BM, BN, FAST, GN>;
+  void (*kern)(const ConvParams);
+  if constexpr (LR) kern = igemm_lrelu_kernel<BM, BN, FAST>; else kern = igemm_kernel<BM, BN, FAST, GN>;
   ensure_dyn_smem(reinterpret_cast<const void*>(kern), (int)smem);
   const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
-  static const std::string pname = std::string("igemm<") + std::to_string(BM) + "," + std::to_string(BN) + (FAST ? ",fast" : ",gen") +
-                                   (GN ? ",gn>" : ">");
+  static const std::string pname = std::string(LR ? "igemm_lrelu<" : "igemm<") + std::to_string(BM) + "," + std::to_string(BN) + (FAST ? ",fast" : ",gen") +
+                                   (GN && !LR ? ",gn>" : ">");
   // algorithmic work: 2*M*N*K flops; each source tensor, the weights and the residual read once, the output written once
   const double esz = 2.0;
   const double in_bytes = (double)p.B * p.Hin * p.Win * (p.C1 + p.C2) * esz;
@@ -290,6 +302,7 @@ static void launch_cfg(const ConvParams& p, hipStream_t s) {
 template <int BM, int BN>
 static void launch_bmn(const ConvParams& p, bool fast, hipStream_t s) {
   const bool gn = p.gn_scale != nullptr;
+  if (p.lrelu_in) { if (fast) launch_cfg<BM, BN, true, true, true>(p, s); else launch_cfg<BM, BN, false, true, true>(p, s); return; }
   if (fast) { if (gn) launch_cfg<BM, BN, true, true>(p, s); else launch_cfg<BM, BN, true, false>(p, s); }
   else      { if (gn) launch_cfg<BM, BN, false, true>(p, s); else launch_cfg<BM, BN, false, false>(p, s); }
 }
@@ -297,7 +310,7 @@ static void launch_bmn(const ConvParams& p, bool fast, hipStream_t s) {
 void launch_igemm(const ConvParams& p, const ConvPlan& pl, hipStream_t s) {
   const int Cin = p.C1 + p.C2;
   LDIFF_CHECK(p.C1 % 8 == 0 && p.C2 % 8 == 0 && Cin > 0, LDIFF_ERR_INVALID, "igemm: channel counts must be multiples of 8 (C1=%d C2=%d)", p.C1, p.C2);
-  LDIFF_CHECK(p.K == p.ks * p.ks * Cin, LDIFF_ERR_INVALID, "igemm: K=%d != ks*ks*Cin=%d", p.K, p.ks * p.ks * Cin);
+  LDIFF_CHECK(p.K == (p.tconv ? Cin : p.ks * p.ks * Cin), LDIFF_ERR_INVALID, "igemm: K=%d != ks*ks*Cin=%d", p.K, p.ks * p.ks * Cin);
   LDIFF_CHECK(p.N % 4 == 0 && p.N <= p.Nrows && p.ldy % 4 == 0 && (p.geglu ? p.N / 2 : p.N) <= p.ldy, LDIFF_ERR_INVALID, "igemm: bad N=%d Nrows=%d ldy=%d", p.N, p.Nrows, p.ldy);
   LDIFF_CHECK((p.C2 == 0) == (p.x2 == nullptr), LDIFF_ERR_INVALID, "igemm: x2/C2 mismatch");
   LDIFF_CHECK(!p.res || (p.ld_res % 4 == 0 && p.res_lo % 4 == 0), LDIFF_ERR_INVALID, "igemm: ld_res / res_lo must be multiples of 4");
@@ -316,6 +329,8 @@ void launch_igemm(const ConvParams& p, const ConvPlan& pl, hipStream_t s) {
   LDIFF_CHECK(!p.xs || pl.kernel == ConvKernel::C3_DATAFLOW, LDIFF_ERR_INVALID, "conv3x3: a folded shortcut (xs) needs the dataflow kernel, which does not take this launch (split-K %d)", p.splitk);
   switch (pl.kernel) {
     case ConvKernel::COND: launch_cond_conv(p, s); return;
+    case ConvKernel::TCONV: launch_tconv2x2(p, s); return;
+    case ConvKernel::SEGCONV: launch_segconv(p, s); return;
     case ConvKernel::C3_NARROW: case ConvKernel::C3_NARROW_FOLD: launch_conv3x3n(p, pl.kernel == ConvKernel::C3_NARROW_FOLD, s); return;
     case ConvKernel::C3_DATAFLOW: launch_conv3x3d(p, s); return;
     case ConvKernel::C3_PINGPONG: launch_conv3x3p(p, s); return;

@@ -65,6 +65,8 @@ struct LoadSpec {
   std::vector<int64_t> shape;   // expected torch shape
   f16* mat = nullptr; int row_off = 0, K = 0, ks = 1, Cin_pad = 0;   // MATRIX
   float* vec = nullptr; int vec_off = 0;                             // VECTOR
+  bool tconv = false;   // MATRIX of a transposed conv (torch [Cin, Cout, k, k]): element (c, n, tap) lands at row tap * Nrows_t + n, column c
+  int tconv_rows = 0;
   int geglu_half = 0;   // > 0: GEGLU projection of width 2*geglu_half: row r lands at geglu_row(r) (x / gate interleaved by 16 rows)
   bool loaded = false;
 };
@@ -80,6 +82,7 @@ class WeightStore {
   void add_rows(const std::string& wname, const std::string& bname, f16* mat, int K, int ks, int Cin, int Cin_pad, int row_off, int rows,
                 float* bias_vec, bool has_bias);
   NormW add_norm(const std::string& prefix, int C);
+  MatW add_tconv(const std::string& prefix, int Cin, int Cout, int k);   // ConvTranspose2d with kernel = stride = k: [k*k][Cout][Cin] fp16 + bias (kernels_seg.hip)
   void alias(const std::string& alias_name, const std::string& name);
   // loading
   void load(const char* name, const void* host, int dtype, const int64_t* shape, int ndim);
@@ -108,6 +111,9 @@ struct ConvOpts {
   int stride = 1, pad_t = -1 /* -1 => (ks-1)/2 */, pad_l = -1, ups = 0;
   int Hout = -1, Wout = -1;     // override output size (asymmetric-pad downsample)
   const GNss* gn = nullptr; int silu = 0;
+  bool splitk_per_image = false; // plan the K split from ONE image of the batch (the nnU-Net head: a batch then computes bit for bit what its images compute alone)
+  int seg_conv = 0;              // ConvParams::seg_conv (the nnU-Net head's first conv asks for the narrow kernel without a prologue)
+  int lrelu = 0;                 // with gn: LeakyReLU(0.01) behind the affine instead of SiLU, bit 0 = on x, bit 1 = on x2 (ConvParams::lrelu_in: the nnU-Net head)
   const float* temb = nullptr; int ld_temb = 0;
   const Act* res = nullptr;      // residual operand (plain or split)
   bool split_in = false;         // consume the (split) sources as a split operand: K doubled, duplicated weights
@@ -324,6 +330,40 @@ struct ldiff_controlnet {
   void run_trunk(const float* x, int B, int h, int w, float t, const float* t_dev, hipStream_t s);
   void forward(const float* x, int B, int h, int w, float t, float scale, float* const* down_out, int n_down, float* mid_out, hipStream_t s);
   ~ldiff_controlnet();
+};
+
+// ---- nnU-Net tissue head ---------------------------------------------------------------------------
+// PlainConvUNet (2-D) as get_network_from_plans builds it (include/ldiff.h).  Every conv's output is stored raw (before its InstanceNorm) with fused
+// per-channel partial sums; in_finalize turns them into scale / shift; the consumer applies affine + LeakyReLU in its prologue.
+struct SegConvW { MatW conv; NormW norm; };
+struct ldiff_segnet {
+  int device = 0;
+  int in_ch = 0, n_stages = 0, n_heads = 0;
+  std::vector<int> features, strides, nce, ncd;
+  WeightStore ws;
+  Exec ex;
+  NonFiniteFlag nf;
+  std::vector<std::vector<SegConvW>> enc, dec;
+  std::vector<MatW> up;
+  MatW head;
+  void build();
+  void forward(const float* x, int B, int H, int W, void* out, int out_dtype, hipStream_t s);
+  void forward_impl(const float* x, int B, int H, int W, void* out, int out_dtype, hipStream_t s);
+  // scale / shift [B, ident + a.C] of InstanceNorm over `a` (the leading `ident` channels: identity, for the upsampled half of a decoder concat)
+  GNss in_ss(const Act& a, const NormW& w, int ident);
+  struct GraphCache {
+    bool enabled = true;
+    int uses = 0;
+    long long key[6] = {0, 0, 0, 0, 0, 0};
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    hipStream_t cap_stream = nullptr;
+    float* in = nullptr; void* out = nullptr;
+    size_t in_cap = 0, out_cap = 0;
+    long long replays = 0;
+    void drop();
+  } gc;
+  ~ldiff_segnet();
 };
 
 struct ldiff_pipeline {

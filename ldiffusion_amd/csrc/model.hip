@@ -152,6 +152,25 @@ NormW WeightStore::add_norm(const std::string& prefix, int C) {
   specs_[prefix + ".bias"] = b; order_.push_back(prefix + ".bias");
   return n;
 }
+MatW WeightStore::add_tconv(const std::string& prefix, int Cin, int Cout, int k) {
+  MatW m;
+  m.N = Cout; m.Nrows = Cout; m.ks = k; m.Cin = roundup(Cin, 8); m.K = m.Cin;
+  m.w = alloc_mat(k * k * m.Nrows, m.K);
+  m.b = alloc_vec(m.Nrows);
+  LoadSpec w;
+  w.kind = LoadSpec::MATRIX;
+  w.shape = {Cin, Cout, k, k};
+  w.mat = m.w; w.K = m.K; w.ks = k; w.Cin_pad = m.Cin; w.tconv = true; w.tconv_rows = m.Nrows;
+  specs_[prefix + ".weight"] = w;
+  order_.push_back(prefix + ".weight");
+  LoadSpec b;
+  b.kind = LoadSpec::VECTOR;
+  b.shape = {Cout};
+  b.vec = m.b;
+  specs_[prefix + ".bias"] = b;
+  order_.push_back(prefix + ".bias");
+  return m;
+}
 void WeightStore::alias(const std::string& alias_name, const std::string& name) { alias_[alias_name] = name; }
 
 static inline float host_to_float(const void* p, int dtype, size_t i) {
@@ -190,6 +209,13 @@ void WeightStore::load(const char* name_c, const void* host, int dtype, const in
     std::vector<float> tmp(numel);
     for (size_t i = 0; i < numel; ++i) tmp[sp.geglu_half ? (size_t)geglu_row((int)i, sp.geglu_half) : i] = host_to_float(host, dtype, i);
     HIP_CHECK(hipMemcpy(sp.vec + sp.vec_off, tmp.data(), numel * sizeof(float), hipMemcpyHostToDevice));
+  } else if (sp.tconv) {   // torch ConvTranspose2d [Cin, Cout, k, k] -> [tap][Cout][Cin]
+    const int Cin = (int)sp.shape[0], Cout = (int)sp.shape[1], taps = sp.ks * sp.ks;
+    std::vector<f16> tmp((size_t)taps * sp.tconv_rows * sp.K, (f16)0.f);
+    for (int c = 0; c < Cin; ++c)
+      for (int n = 0; n < Cout; ++n)
+        for (int t = 0; t < taps; ++t) tmp[((size_t)t * sp.tconv_rows + n) * sp.K + c] = (f16)host_to_float(host, dtype, ((size_t)c * Cout + n) * taps + t);
+    HIP_CHECK(hipMemcpy(sp.mat, tmp.data(), tmp.size() * sizeof(f16), hipMemcpyHostToDevice));
   } else {
     const int rows = (int)sp.shape[0], Cin = (int)sp.shape[1], ks = sp.ks, taps = ks * ks;
     std::vector<f16> tmp((size_t)rows * sp.K, (f16)0.f);
@@ -496,7 +522,8 @@ Act Exec::conv(const MatW& w, const Act& x, const Act* x2, const ConvOpts& o) {
   p.n_real = o.N_override ? 0 : w.N;
   p.bias = o.bias_shift ? derived_bias_shift(w, o.bias_shift) : w.b;
   p.out_shift = o.out_shift;
-  if (o.gn) { p.gn_scale = o.gn->scale; p.gn_shift = o.gn->shift; p.silu_in = o.silu; }
+  p.seg_conv = o.seg_conv;
+  if (o.gn) { p.gn_scale = o.gn->scale; p.gn_shift = o.gn->shift; p.silu_in = o.silu; p.lrelu_in = o.lrelu; }
   p.temb = o.temb; p.ld_temb = o.ld_temb;
   p.M = x.B * p.Hout * p.Wout;
   if (o.res) {
@@ -528,6 +555,12 @@ Act Exec::conv(const MatW& w, const Act& x, const Act* x2, const ConvOpts& o) {
   ConvAsk ask;
   ask.stats = o.want_stats && C == p.N && p.N == w.N;   // (split-K launches too: their reduce kernel emits the statistics in 32-row blocks)
   ask.fold_gn = !o.want_stats && !o.split_in;
+  if (o.splitk_per_image && x.B > 1) {   // the split count of the same launch at B = 1: the sums of an image do not depend on the batch it travels in
+    ConvParams one = p;
+    one.B = 1; one.M = p.Hout * p.Wout;
+    plan_conv(one, ask);
+    ask.splitk = one.splitk > 1 ? one.splitk : 1;
+  }
   const ConvPlan pl = plan_conv(p, ask);
   if (o.sc_x && pl.weights != ConvWeights::FRAG_SC) return Act{};   // asked for the folded form only: nothing is launched, the caller takes the two-launch form
   f16* wfold = nullptr;

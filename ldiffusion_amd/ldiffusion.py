@@ -174,7 +174,8 @@ class LDiffusionModel:
 
     def inference(self, image_path, ldiffusion_weight, segmentor_weight, num_classes, head=None, predictor=None, output_path=None,
                   text_embeddings=None, **_readme_kwargs):
-        """ldiffusion.py:317-324.  `head` (cell) / `predictor` (tissue) = the segmentation head callable (out of scope, see
+        """ldiffusion.py:317-324.  Tissue: `segmentor_weight` = nnU-Net's trained-model folder, as in the reference (the head then runs on the HIP
+        library, nnunet.py), or `predictor` = any head callable; cell: `head` = the segmentation head callable (out of scope, see
         segmentor.py); `output_path` is the folder-mode argument of the tissue path; other README-era keyword arguments (dtm_path)
         are accepted and ignored like the code ignores them."""
         segmentor = Segmentor(train_loader=None, val_loader=None, level=self.level, num_classes=num_classes)

@@ -530,3 +530,77 @@ class AutoencoderKL:
                 self._h = None
         except Exception:
             pass
+
+
+class PlainConvUNet:
+    """nnU-Net v2's 2-D PlainConvUNet on the HIP library (include/ldiff.h ldiff_segnet_*): the network nnUNetPredictor runs inside its sliding
+    window at /root/reference/segmentor.py:463-488.  `spec` comes from `nnunet.network_spec`; `state_dict` carries the canonical names
+    (`nnunet.clean_state_dict` drops a checkpoint's aliases).  `net(x [B, C, h, w] float32 on the device) -> logits [B, heads, h, w]` in
+    `out_dtype` (float32 default; float16 is what the reference's autocast hands the sliding window)."""
+
+    def __init__(self, spec: dict, state_dict, device=None, out_dtype=torch.float32):
+        from . import nnunet
+        _lib.require_gpu()
+        self.spec = dict(spec)
+        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.out_dtype = out_dtype
+        self._lib = _lib.load()
+        n = spec["n_stages"]
+        arr = lambda v: (C.c_int * len(v))(*[int(i) for i in v])
+        self._h = C.c_void_p()
+        _lib.check(self._lib.ldiff_segnet_create(C.byref(self._h), spec["in_channels"], n, arr(spec["features"]), arr(spec["strides"]),
+                                                 arr(spec["n_conv_encoder"]), arr(spec["n_conv_decoder"]), spec["n_heads"], self.device.index or 0))
+        self._shapes = nnunet.param_shapes(spec)
+        self.load_state_dict(state_dict)
+
+    def load_state_dict(self, sd, strict=True):
+        _load_state_dict(self._lib, self._lib.ldiff_segnet_load, self._h, sd, self._shapes)
+        n = self._lib.ldiff_segnet_missing(self._h)
+        if n and strict:
+            names = [self._lib.ldiff_segnet_missing_name(self._h, i).decode() for i in range(min(n, 5))]
+            raise RuntimeError(f"{n} nnU-Net tensors missing from the checkpoint, e.g. {names}")
+        self._host_sd = {k: v.detach().to("cpu") for k, v in sd.items()}
+
+    def state_dict(self):
+        return dict(self._host_sd)
+
+    def set_graph(self, on: bool):
+        _lib.check(self._lib.ldiff_segnet_set_graph(self._h, int(bool(on))))
+        return self
+
+    @property
+    def graph_replays(self) -> int:
+        return int(self._lib.ldiff_segnet_graph_replays(self._h))
+
+    def check_finite(self):
+        _lib.check(self._lib.ldiff_segnet_check_finite(self._h, _lib.stream_ptr()))
+        return self
+
+    def eval(self):
+        return self
+
+    def to(self, *args, **kwargs):
+        return self
+
+    @torch.no_grad()
+    def __call__(self, x):
+        if x.dim() != 4 or x.shape[1] != self.spec["in_channels"]:
+            raise ValueError(f"PlainConvUNet: input must be [B, {self.spec['in_channels']}, h, w], got {list(x.shape)}")
+        if self.out_dtype not in (torch.float32, torch.float16):
+            raise ValueError("PlainConvUNet: out_dtype must be float32 or float16")
+        x = x.to(self.device, torch.float32).contiguous()
+        B, _, h, w = x.shape
+        out = torch.empty((B, self.spec["n_heads"], h, w), dtype=self.out_dtype, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.ldiff_segnet_forward(self._h, _lib.ptr(x), B, h, w, _lib.ptr(out), _DTYPES[self.out_dtype], _lib.stream_ptr()))
+        return out
+
+    forward = __call__
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._lib.ldiff_segnet_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass

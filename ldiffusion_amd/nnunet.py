@@ -1,0 +1,275 @@
+"""The nnU-Net v2 tissue head: what `nnUNetPredictor.initialize_from_trained_model_folder(segmentor_weight, use_folds=(0,),
+checkpoint_name='checkpoint_best.pth')` (/root/reference/segmentor.py:463-468) reads, resolved for the one architecture the HIP library runs.
+
+Covered: `PlainConvUNet`, 2-D, one fold, as model/nnunetv2/utilities/get_network_from_plans.py builds it (conv bias, InstanceNorm2d(eps=1e-5, affine),
+LeakyReLU(0.01), stride-in-conv downsampling, transposed-conv upsampling with kernel = stride, deep supervision off), 3x3 kernels, strides 1 (first
+stage) and 2 (every later stage) in both axes.  Everything else a plans file can ask for is refused with a ValueError that names the field.
+
+The state-dict key layout belongs to the package `dynamic_network_architectures`, which the test-suite cannot import: it is restated here from
+knowledge of that package and is UNPINNED; scripts/gen_golden_nnunet.py pins names and one forward pass where it is installed.
+
+Nothing in this module touches the GPU except `load_trained_model_folder` (which builds `models.PlainConvUNet`) and the tensors callers hand in.
+"""
+from __future__ import annotations
+
+import json
+import os
+import re
+from copy import deepcopy
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import torch
+
+NORMALIZATIONS = ("ZScoreNormalization", "RGBTo01Normalization", "RescaleTo01Normalization", "NoNormalization")
+# map_channel_name_to_normalization.py: channel names that are not in the mapping (the reference's own datasets name theirs R / G / B,
+# /root/reference/utils.py:277-281) fall back to z-score
+CHANNEL_NAME_TO_NORMALIZATION = {"noNorm": "NoNormalization", "zscore": "ZScoreNormalization", "rescale_to_0_1": "RescaleTo01Normalization",
+                                 "rgb_to_0_1": "RGBTo01Normalization", "CT": "CTNormalization"}
+
+
+def _refuse(field: str, why: str):
+    raise ValueError(f"nnU-Net plans: `{field}` {why}; the HIP tissue head covers PlainConvUNet, 2-D, 3x3 kernels, strides 1 / 2, one fold")
+
+
+def resolve_configuration(plans: dict, name: str) -> dict:
+    """PlansManager._internal_resolve_configuration_inheritance (plans_handler.py:197-219): `inherits_from` chains, child keys win."""
+    visited: Tuple[str, ...] = ()
+    chain = []
+    cur = name
+    while True:
+        if cur not in plans.get("configurations", {}):
+            raise ValueError(f"The configuration {cur} does not exist in the plans. Valid configuration names are {list(plans.get('configurations', {}))}.")
+        if cur in visited:
+            raise RuntimeError(f"Circular dependency detected while solving `inherits_from`: {visited + (cur,)}")
+        visited += (cur,)
+        cfg = plans["configurations"][cur]
+        chain.append(cfg)
+        if "inherits_from" not in cfg:
+            break
+        cur = cfg["inherits_from"]
+    out: dict = {}
+    for cfg in reversed(chain):
+        out.update(deepcopy(cfg))
+    return out
+
+
+def network_spec(plans: dict, configuration_name: str, dataset_json: dict) -> dict:
+    """The layer list of the network `get_network_from_plans` would build, plus what the sliding window and the preprocessing need.
+    Refuses, naming the field, whatever the HIP head does not cover."""
+    cfg = resolve_configuration(plans, configuration_name)
+    if cfg.get("UNet_class_name") != "PlainConvUNet":
+        _refuse("UNet_class_name", f"is {cfg.get('UNet_class_name')!r}")
+    if cfg.get("previous_stage") is not None:
+        _refuse("previous_stage", "names a cascade")
+    ks = cfg["conv_kernel_sizes"]
+    pool = cfg["pool_op_kernel_sizes"]
+    n_stages = len(ks)
+    if any(len(k) != 2 for k in ks):
+        _refuse("conv_kernel_sizes", f"is {len(ks[0])}-dimensional")
+    if any(list(k) != [3, 3] for k in ks):
+        _refuse("conv_kernel_sizes", f"holds a kernel other than [3, 3]: {ks}")
+    if len(pool) != n_stages or any(len(p) != 2 or p[0] != p[1] for p in pool):
+        _refuse("pool_op_kernel_sizes", f"is anisotropic or does not match the stages: {pool}")
+    strides = [int(p[0]) for p in pool]
+    if n_stages < 2 or strides[0] != 1 or any(s != 2 for s in strides[1:]):
+        _refuse("pool_op_kernel_sizes", f"must be [1, 1] for the first stage and [2, 2] for every later one: {pool}")
+    if any(bool(m) for m in cfg.get("use_mask_for_norm", [])):
+        _refuse("use_mask_for_norm", "is true for a channel")
+    tf = list(plans.get("transpose_forward", [0, 1, 2]))
+    if tf != sorted(tf):
+        _refuse("transpose_forward", f"is not the identity: {tf}")
+    schemes = list(cfg["normalization_schemes"])
+    for s in schemes:
+        if s not in NORMALIZATIONS:
+            _refuse("normalization_schemes", f"names {s!r}")
+    labels = dataset_json["labels"]
+    if any(isinstance(v, (list, tuple)) for v in labels.values()):
+        _refuse("labels", "defines regions")
+    if "ignore" in labels:
+        _refuse("labels", "defines an ignore label")
+    channels = dataset_json["channel_names"] if "channel_names" in dataset_json else dataset_json["modality"]
+    in_channels = len(channels)
+    if len(schemes) != in_channels:
+        _refuse("normalization_schemes", f"has {len(schemes)} entries for {in_channels} channels")
+    base, cap = int(cfg["UNet_base_num_features"]), int(cfg["unet_max_num_features"])
+    features = [min(base * 2 ** i, cap) for i in range(n_stages)]
+    if any(f % 16 for f in features):
+        _refuse("UNet_base_num_features", f"gives stage widths that are not multiples of 16: {features}")
+    nce, ncd = [int(v) for v in cfg["n_conv_per_stage_encoder"]], [int(v) for v in cfg["n_conv_per_stage_decoder"]]
+    if len(nce) != n_stages or len(ncd) != n_stages - 1:
+        _refuse("n_conv_per_stage_encoder", f"/ n_conv_per_stage_decoder do not match {n_stages} stages: {nce} / {ncd}")
+    patch = [int(v) for v in cfg["patch_size"]]
+    div = 1
+    for s in strides:
+        div *= s
+    if len(patch) != 2 or any(p % div for p in patch):
+        _refuse("patch_size", f"{patch} is not divisible by the product of the strides, {div}")
+    return dict(in_channels=in_channels, n_stages=n_stages, features=features, strides=strides, n_conv_encoder=nce, n_conv_decoder=ncd,
+                n_heads=len(labels), patch_size=tuple(patch), normalization_schemes=schemes)
+
+
+def param_shapes(spec: dict) -> Dict[str, Tuple[int, ...]]:
+    """name -> shape of every tensor the handle expects (the canonical names of a PlainConvUNet state dict; see the module docstring: unpinned)."""
+    out: Dict[str, Tuple[int, ...]] = {}
+    f, n = spec["features"], spec["n_stages"]
+
+    def block(prefix, cin, cout):
+        out[prefix + ".conv.weight"] = (cout, cin, 3, 3)
+        out[prefix + ".conv.bias"] = (cout,)
+        out[prefix + ".norm.weight"] = (cout,)
+        out[prefix + ".norm.bias"] = (cout,)
+
+    for s in range(n):
+        cin = spec["in_channels"] if s == 0 else f[s - 1]
+        for i in range(spec["n_conv_encoder"][s]):
+            block(f"encoder.stages.{s}.0.convs.{i}", cin, f[s])
+            cin = f[s]
+    for j in range(n - 1):
+        below, skip = f[n - 1 - j], f[n - 2 - j]
+        out[f"decoder.transpconvs.{j}.weight"] = (below, skip, 2, 2)
+        out[f"decoder.transpconvs.{j}.bias"] = (skip,)
+        cin = 2 * skip
+        for i in range(spec["n_conv_decoder"][j]):
+            block(f"decoder.stages.{j}.convs.{i}", cin, skip)
+            cin = skip
+    out[f"decoder.seg_layers.{n - 2}.weight"] = (spec["n_heads"], f[0], 1, 1)
+    out[f"decoder.seg_layers.{n - 2}.bias"] = (spec["n_heads"],)
+    return out
+
+
+_SEG = re.compile(r"^decoder\.seg_layers\.(\d+)\.")
+
+
+def clean_state_dict(sd: dict, spec: dict) -> dict:
+    """Drop what a checkpoint holds beside the canonical names: the `_orig_mod.` prefix of a compiled network, the `....all_modules.{k}.*`
+    views of conv / norm, the decoder's reference to the encoder (`decoder.encoder.*`) and the deep-supervision heads that do not run."""
+    used = spec["n_stages"] - 2
+    out = {}
+    for k, v in sd.items():
+        if k.startswith("_orig_mod."):
+            k = k[len("_orig_mod."):]
+        if ".all_modules." in k or k.startswith("decoder.encoder."):
+            continue
+        m = _SEG.match(k)
+        if m and int(m.group(1)) != used:
+            continue
+        out[k] = v
+    return out
+
+
+def check_state_dict(sd: dict, spec: dict) -> None:
+    """Names and shapes against `param_shapes`: an unexpected name, a missing tensor (by name) or a wrong shape raises."""
+    want = param_shapes(spec)
+    unexpected = [k for k in sd if k not in want]
+    if unexpected:
+        raise ValueError(f"unexpected tensors in checkpoint: {unexpected[:5]}{' ...' if len(unexpected) > 5 else ''}")
+    missing = [k for k in want if k not in sd]
+    if missing:
+        raise RuntimeError(f"{len(missing)} nnU-Net tensors missing from the checkpoint, e.g. {missing[:5]}")
+    for k, shape in want.items():
+        if tuple(sd[k].shape) != tuple(shape):
+            raise ValueError(f"load({k}): shape {list(sd[k].shape)} does not match expected {list(shape)}")
+
+
+# ---- preprocessing: DefaultPreprocessor.run_case_npy for a PNG (default_preprocessor.py:40-113), on the tensor's device ----
+def nonzero_bbox(data: torch.Tensor) -> Tuple[int, int, int, int]:
+    """crop_to_nonzero's box for [C, H, W]: rows / columns where any channel is non-zero, as (y0, y1, x0, x1), end exclusive (filling holes of the
+    mask, as create_nonzero_mask does, never moves its bounding box).  An all-zero image keeps its full extent."""
+    nz = (data != 0).any(0)
+    rows, cols = nz.any(1).nonzero().flatten(), nz.any(0).nonzero().flatten()
+    if rows.numel() == 0:
+        return 0, int(data.shape[1]), 0, int(data.shape[2])
+    return int(rows[0]), int(rows[-1]) + 1, int(cols[0]), int(cols[-1]) + 1
+
+
+def normalize(data: torch.Tensor, schemes: Sequence[str]) -> torch.Tensor:
+    """default_normalization_schemes.py, per channel of a float32 [C, H, W] (use_mask_for_norm false): ZScoreNormalization (x - mean) / max(std, 1e-8)
+    with the population std; RGBTo01Normalization x / 255; RescaleTo01Normalization (x - min) / max(max - min, 1e-8); NoNormalization."""
+    out = torch.empty_like(data, dtype=torch.float32)
+    for c, scheme in enumerate(schemes):
+        x = data[c].to(torch.float32)
+        if scheme == "ZScoreNormalization":
+            out[c] = (x - x.mean()) / max(float(x.std(unbiased=False)), 1e-8)
+        elif scheme == "RGBTo01Normalization":
+            if float(x.min()) < 0 or float(x.max()) > 255:
+                raise ValueError("RGBTo01Normalization: pixel values outside 0..255")
+            out[c] = x / 255.0
+        elif scheme == "RescaleTo01Normalization":
+            x = x - x.min()
+            out[c] = x / max(float(x.max()), 1e-8)
+        elif scheme == "NoNormalization":
+            out[c] = x
+        else:
+            _refuse("normalization_schemes", f"names {scheme!r}")
+    return out
+
+
+def preprocess(data: torch.Tensor, schemes: Sequence[str]):
+    """[C, H, W] in the PNG's 0..255 scale -> (cropped + normalised float32 [C, h, w], (y0, y1, x0, x1)); no resampling (a PNG has spacing 1)."""
+    box = nonzero_bbox(data)
+    return normalize(data[:, box[0]:box[1], box[2]:box[3]].to(torch.float32), schemes), box
+
+
+def uncrop_mask(mask: torch.Tensor, box, full_hw) -> torch.Tensor:
+    """Pixels outside the crop box are label 0 (export_prediction.py: insert_crop_into_image on a zero array)."""
+    out = torch.zeros(tuple(full_hw), dtype=mask.dtype, device=mask.device)
+    out[box[0]:box[1], box[2]:box[3]] = mask
+    return out
+
+
+class TrainedModel:
+    """What the predictor keeps after initialize_from_trained_model_folder: `.network` (callable [B, C, h, w] -> [B, heads, h, w]), `.patch_size`,
+    `.mirror_axes` (the checkpoint's inference_allowed_mirroring_axes), `.normalization_schemes`, `.num_heads`, `.spec`."""
+
+    def __init__(self, network, spec: dict, mirror_axes):
+        self.network = network
+        self.spec = spec
+        self.patch_size = tuple(spec["patch_size"])
+        self.mirror_axes = None if mirror_axes is None else tuple(int(a) for a in mirror_axes)
+        self.normalization_schemes = list(spec["normalization_schemes"])
+        self.num_heads = int(spec["n_heads"])
+
+    def __call__(self, x):
+        return self.network(x)
+
+    @torch.no_grad()
+    def predict_mask(self, data: torch.Tensor, tile_size=None, tile_step_size: float = 0.5, mirror_axes="checkpoint", network=None) -> torch.Tensor:
+        """[C, H, W] in 0..255 scale on the device -> uint8 mask [H, W]: crop to non-zero, normalise, nnU-Net's sliding window, arg-max, un-crop.
+        The tile is the plans' patch size (or `tile_size`), NOT clamped to the image: an image smaller than the patch is zero padded to it
+        (predict_from_raw_data.py:614, tiling.pad_to_tile), as the reference does -- InstanceNorm statistics and Gaussian weights are then those of a full patch.
+        `network` replaces the head (tests: a float64 restatement under the same preprocessing)."""
+        from . import tiling
+        from .segmentor import argmax_mask
+        x, box = preprocess(data, self.normalization_schemes)
+        tile = tuple(int(t) for t in tile_size) if tile_size is not None else self.patch_size
+        div = 1
+        for st in self.spec["strides"]:
+            div *= st
+        if len(tile) != 2 or any(t < div or t % div for t in tile):
+            raise ValueError(f"tile_size {tile} must be a multiple of the product of the network's strides, {div}, in both axes")
+        axes = self.mirror_axes if mirror_axes == "checkpoint" else mirror_axes
+        logits = tiling.predict_sliding_window_return_logits(x, network if network is not None else self.network, self.num_heads, tile, tile_step_size, True, axes)
+        return uncrop_mask(argmax_mask(logits[None].float())[0], box, data.shape[1:])
+
+
+def read_trained_model_folder(model_dir: str, fold=0, checkpoint_name: str = "checkpoint_best.pth"):
+    """predict_from_raw_data.py:78-121 without the network: (spec, cleaned state dict, inference_allowed_mirroring_axes)."""
+    if isinstance(fold, (list, tuple)):
+        if len(fold) != 1:
+            _refuse("use_folds", f"names {len(fold)} folds")
+        fold = fold[0]
+    with open(os.path.join(model_dir, "dataset.json")) as f:
+        dataset_json = json.load(f)
+    with open(os.path.join(model_dir, "plans.json")) as f:
+        plans = json.load(f)
+    ckpt = torch.load(os.path.join(model_dir, f"fold_{fold}", checkpoint_name), map_location="cpu", weights_only=False)
+    spec = network_spec(plans, ckpt["init_args"]["configuration"], dataset_json)
+    sd = clean_state_dict(ckpt["network_weights"], spec)
+    check_state_dict(sd, spec)
+    return spec, sd, ckpt.get("inference_allowed_mirroring_axes")
+
+
+def load_trained_model_folder(model_dir: str, fold=0, checkpoint_name: str = "checkpoint_best.pth", device=None) -> TrainedModel:
+    from .models import PlainConvUNet
+    spec, sd, axes = read_trained_model_folder(model_dir, fold, checkpoint_name)
+    return TrainedModel(PlainConvUNet(spec, sd, device=device), spec, axes)

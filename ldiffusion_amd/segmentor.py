@@ -212,11 +212,30 @@ class Segmentor:
         mask = np.array(Image.fromarray(mask.astype(np.uint8)).resize((width, height), resample=Image.NEAREST))
         return decoded.resize((width, height), Image.BILINEAR), mask
 
+    def _tissue_head(self, model_dir):
+        """The nnU-Net head of a trained-model folder, built once per (folder, checkpoint mtime)."""
+        from . import nnunet
+        ckpt = os.path.join(model_dir, "fold_0", "checkpoint_best.pth")
+        key = (os.path.abspath(model_dir), os.path.getmtime(ckpt) if os.path.exists(ckpt) else None)
+        cache = getattr(self, "_tissue_heads", None)
+        if cache is None:
+            cache = self._tissue_heads = {}
+        if key not in cache:
+            cache.clear()
+            cache[key] = nnunet.load_trained_model_folder(model_dir, 0, "checkpoint_best.pth", device=self.device)
+        return cache[key]
+
     @torch.no_grad()
     def inference_tissue_model_nnUNetv2(self, image_path, diffusion_path, ldiffusion_weight, segmentor_weight, output_path=None,
-                                        predictor=None, text_embeddings=None, tile_size=(512, 512), tile_step_size=0.5,
-                                        mirror_axes=(0, 1), num_heads=None):
-        """segmentor.py:388-488 with the tissue head injected.
+                                        predictor=None, text_embeddings=None, tile_size=None, tile_step_size=0.5,
+                                        mirror_axes=None, num_heads=None):
+        """segmentor.py:388-488.  The tissue head is either
+        * built from `segmentor_weight`, a trained-model folder as the reference's nnUNetPredictor reads it (dataset.json, plans.json,
+          fold_0/checkpoint_best.pth; :463-468), when `predictor` is None: nnU-Net v2's 2-D PlainConvUNet on the HIP library (`nnunet.py`; cached on this
+          Segmentor), with nnU-Net's preprocessing (crop to non-zero, the plans' normalisation) in front of the sliding window, the plans' patch size and
+          the checkpoint's mirror axes unless `tile_size` / `mirror_axes` name others, pixels outside the crop box label 0; or
+        * injected as `predictor` (then `tile_size` / `mirror_axes` default to (512, 512) / (0, 1), the input is the raw 0..255 image, no crop).
+        Neither: RuntimeError.
         * `image_path` a directory: the reference hands the folder to nnU-Net's file predictor and returns `(None, None)`
           (:399-421).  Here `predictor(image_path, output_path)` is called if it accepts two arguments (a file-level predictor),
           else every image of the folder goes through the single-image path and its mask is written as PNG to `output_path`.
@@ -227,8 +246,25 @@ class Segmentor:
           is returned like :486-488."""
         from PIL import Image
         from . import tiling
+        head = None
         if predictor is None:
-            raise RuntimeError("inference_tissue_model_nnUNetv2: the nnU-Net tissue head is outside the hot-path scope; pass `predictor=`")
+            if not (isinstance(segmentor_weight, (str, os.PathLike)) and os.path.isfile(os.path.join(segmentor_weight, "plans.json"))):
+                raise RuntimeError("inference_tissue_model_nnUNetv2: the nnU-Net tissue head needs `segmentor_weight` to be a trained-model folder "
+                                   "(dataset.json, plans.json, fold_0/checkpoint_best.pth), or pass `predictor=`")
+            head = self._tissue_head(segmentor_weight)
+        if head is not None and os.path.isdir(image_path):   # every image of the folder through the same head
+            if not output_path:
+                raise ValueError("When image_path is a folder, output_path must be specified!")
+            os.makedirs(output_path, exist_ok=True)
+            for name in sorted(os.listdir(image_path)):
+                if name.lower().endswith((".png", ".jpg", ".jpeg", ".tif", ".tiff", ".bmp")):
+                    _, m = self.inference_tissue_model_nnUNetv2(os.path.join(image_path, name), diffusion_path, ldiffusion_weight, segmentor_weight,
+                                                                None, None, text_embeddings, tile_size, tile_step_size, mirror_axes, num_heads)
+                    Image.fromarray(m).save(os.path.join(output_path, os.path.splitext(name)[0] + ".png"))
+            return None, None   # batch mode returns no single mask (segmentor.py:421)
+        if head is None:
+            tile_size = (512, 512) if tile_size is None else tile_size
+            mirror_axes = (0, 1) if mirror_axes is None else mirror_axes
         if os.path.isdir(image_path):
             if not output_path:
                 raise ValueError("When image_path is a folder, output_path must be specified!")
@@ -263,6 +299,10 @@ class Segmentor:
             rgb = torch.from_numpy(np.array(image, np.uint8))[None].to(self.device)
             decoded = image
         data = rgb[0].permute(2, 0, 1).float()                                                # what the PNG the reference writes would hold
+        if head is not None:
+            mask = head.predict_mask(data, tile_size, tile_step_size, "checkpoint" if mirror_axes is None else mirror_axes)
+            head.network.check_finite()   # an fp16 overflow inside the head raises instead of yielding a plausible-looking mask
+            return decoded, mask.cpu().numpy()
         heads = int(num_heads if num_heads is not None else self.num_classes)
         th, tw = min(tile_size[0], data.shape[1]), min(tile_size[1], data.shape[2])
         logits = tiling.predict_sliding_window_return_logits(data, predictor, heads, (th, tw), tile_step_size, True, mirror_axes)
