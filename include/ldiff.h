@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define LDIFF_VERSION 190 /* 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
+#define LDIFF_VERSION 200 /* 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
 #define LDIFF_MAX_BLOCKS 8
 
 typedef enum { LDIFF_OK = 0, LDIFF_ERR_INVALID = -1, LDIFF_ERR_RUNTIME = -2, LDIFF_ERR_STATE = -3, LDIFF_ERR_NONFINITE = -4 } ldiff_status;
@@ -168,6 +168,34 @@ int64_t ldiff_segnet_graph_replays(ldiff_segnet*);
 int ldiff_segnet_forward(ldiff_segnet*, const void* x_dev, int B, int H, int W, void* logits_dev, int out_dtype, void* stream);
 int ldiff_segnet_check_finite(ldiff_segnet*, void* stream);
 void ldiff_segnet_destroy(ldiff_segnet*);
+
+/* ------------------------------------------------------------------------------------------------
+ * Instance classifier of the cell head  --  replaces `self.encoder` / `self.adapter` / pooling / `self.classifier` of CellSegClassifier.forward
+ *   model/conductor.py:138-233, segmentor.py:490-545
+ * torchvision's ResNet (v1.5 bottleneck: expansion 4, the stride on the 3x3 conv, a 1x1 strided conv + BatchNorm as `downsample` in the first block of every layer)
+ * without avgpool / fc: conv 7x7 stride 2 (3 -> width) + BatchNorm + ReLU, max pooling 3x3 stride 2, layers[i] bottlenecks of width * 2^i planes (layers 2..4 halve
+ * the map); then adapter = Conv2d(8 * 4 * width, adapter_channels, 3, padding = 1), the mean over its map, Linear(adapter_channels, num_classes).  ResNet152 is
+ * layers (3, 8, 36, 3), width 64.  Restated from the public architecture (UNPINNED: torchvision is not available to the test-suite).
+ * Every BatchNorm (eval mode, eps 1e-5) is folded into its conv on the host in double at load time -- w' = w * gamma / sqrt(var + eps), b' = beta - mean * gamma /
+ * sqrt(var + eps), rounded once to fp16 / fp32 -- so no normalisation ever runs; every conv is one clsconv launch (ldiff_conv_args.relu_out) with bias, the block's
+ * identity and the ReLU in its fp32 epilogue.  No split-K: a crop's logits are bit for bit those of a B = 1 call, whatever else is in the batch.
+ * Checkpoint names (the module's state_dict): encoder.0.weight, encoder.1.{weight,bias,running_mean,running_var}, encoder.{4..7}.{b}.{conv1,bn1,conv2,bn2,conv3,bn3}.*,
+ * encoder.{4..7}.0.downsample.{0,1}.*, adapter.{weight,bias}, classifier.{weight,bias}; *.num_batches_tracked is accepted and dropped.  A conv and its BatchNorm
+ * are folded once all five tensors are present; a later reload of such a group needs all five again.
+ * The epilogues set the handle's sticky non-finite flag where a value is NaN or beyond 65504 before the ReLU (ldiff_resnet_check_finite).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct ldiff_resnet ldiff_resnet;
+int ldiff_resnet_create(ldiff_resnet** out, const int* layers /* 4 entries */, int width /* % 16 == 0 */, int adapter_channels /* % 16 == 0 */, int num_classes /* >= 2 */, int device);
+int ldiff_resnet_load(ldiff_resnet*, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim);
+int ldiff_resnet_missing(ldiff_resnet*);
+const char* ldiff_resnet_missing_name(ldiff_resnet*, int i);
+/* as ldiff_segnet_set_graph: the launch sequence of a (B, S) configuration is captured on its second use and replayed afterwards */
+int ldiff_resnet_set_graph(ldiff_resnet*, int on);
+int64_t ldiff_resnet_graph_replays(ldiff_resnet*);
+/* crops [B, S, S, 8] f16 NHWC (channels 3..7 zero: ldiff_op_crop_resize_norm), S % 32 == 0 -> logits [B, num_classes] f32, labels [B] i32 (may be NULL) = 1 + argmax(logits[:, 1:]) */
+int ldiff_resnet_forward(ldiff_resnet*, const void* crops_nhwc_f16, int B, int S, void* logits_f32, void* labels_i32_or_null, void* stream);
+int ldiff_resnet_check_finite(ldiff_resnet*, void* stream);
+void ldiff_resnet_destroy(ldiff_resnet*);
 
 /* ------------------------------------------------------------------------------------------------
  * AutoencoderKL  --  replaces vae.encode(x).latent_dist / vae.decode(z).sample / pipeline.decode_latents
@@ -344,6 +372,15 @@ typedef struct {
                                                        + lrelu_in prologue, bias, plain fp16 output, statistics of the fp32 sums in one row block per wave): 0 = the executors' choice (the eligible
                                                        launches that carry lrelu_in; a plain launch of such a shape goes where it always went), 1 = every eligible launch (the head's first
                                                        conv; tests, timing), -1 = never (timing: the implicit-GEMM route) */
+  int relu_out;                                     /* 1: y = relu(sum + bias + res), the activation BEHIND the sum, rounded once.  Only the instance classifier's conv family has it
+                                                       (clsconv<...>: ks 1 | 3 | 7 with pad_t = pad_l = ks / 2, stride 1 | 2, one plain fp16 source with C1 % 8 == 0 (row pitch ld1 % 8 == 0),
+                                                       N % 16 == 0, N <= Nrows, bias and a plain fp16 res (ld_res % 4 == 0) only, plain fp16 output with ldy % 4 == 0, Hout = (Hin - 1) / stride + 1,
+                                                       no split, no statistics, pointers aligned for 16-byte operand loads); any other launch, and relu_out beside silu_out / cond_conv = 1 / tconv / lrelu_in /
+                                                       seg_conv = 1 / sc_x: LDIFF_ERR_INVALID, never another route.  The K order of a sum is k = tap * C1 + c in
+                                                       steps of 32 whatever B and the tile: an image's outputs do not depend on the batch it travels in */
+  int cls_conv;                                     /* that family: 0 = the executors' choice (the eligible launches that ask for relu_out; a plain launch of such a shape goes where it
+                                                       always went), 1 = every eligible launch (the classifier's convs without a ReLU; the only route of ks = 7; tests, timing),
+                                                       -1 = never (relu_out is then refused) */
 } ldiff_conv_args;
 int ldiff_op_conv(const ldiff_conv_args*, void* stream);
 /* row blocks per image the launch would emit statistics for (0 = unsupported for this shape) */
@@ -356,6 +393,17 @@ int ldiff_op_gn_finalize(const void* part1, int R1, int C1, const void* part2, i
  * (f32 [B][C][R][2] partial {sum, sum of squares}, the layout of ldiff_conv_args.stats) or, with part NULL, from the tensor itself (x f16 [B, HW, ldx]). */
 int ldiff_op_in_finalize(const void* part, int R, const void* x_f16, int ldx, int B, int HW, int C, float eps, const void* gamma, const void* beta, void* scale,
                          void* shift, int ld_ss, int ss_off, int ident, void* stream);
+/* Kernels of the cell head beside its convs (ldiff_resnet; kernels_cls.hip).
+ * maxpool3x3s2: x [B, H, W, C] f16 NHWC (C % 8 == 0) -> y [B, (H - 1) / 2 + 1, (W - 1) / 2 + 1, C]: 3x3 window, stride 2, padding 1, taps outside the map ignored.
+ * crop_resize_norm: rgb_u8 [H, W, 3] (device), boxes_i32 [n, 4] = (x1, y1, x2, y2) inclusive (device), lut_u8 [3][256] (device) -> out [n, S, S, 8] f16 NHWC, channels 3..7 zero:
+ *   per pixel lut[c][rgb] / 255, resampled to S x S with the anti-aliased bilinear filter of torch's F.interpolate(antialias=True, align_corners=False)
+ *   (plain bilinear for a side <= S), then (v - mean[c]) / std[c], all of it in double (the normalisation cancels near the mean) and rounded once; mean3 / std3 are HOST double[3].  A box that leaves the image yields a zero crop.
+ * cls_head: x [B, HW, ldx] f16 (the first A columns) -> feat = mean over HW (fp32), logits [B, C] f32 = w [C, A] f32 . feat + bias [C] f32, and
+ *   labels [B] i32 (may be NULL) = 1 + argmax(logits[:, 1:]), the first maximum; C >= 2. */
+int ldiff_op_maxpool3x3s2(const void* x, void* y, int B, int H, int W, int C, void* stream);
+int ldiff_op_crop_resize_norm(const void* rgb_u8, int H, int W, const void* boxes_i32, int n, const void* lut_u8, int S, const double* mean3, const double* std3, void* out_f16,
+                              void* stream);
+int ldiff_op_cls_head(const void* x, int B, int HW, int A, int ldx, const void* w_f32, const void* bias_f32, int C, void* logits_f32, void* labels_i32_or_null, void* stream);
 int ldiff_op_attention(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, int B, int heads,
                        int Lq, int Lk, int d, int64_t q_bstride, int64_t kv_bstride, int64_t o_bstride, float scale, void* stream);
 /* The same with q ALREADY multiplied by scale * log2(e) (the executors do that in the fp32 epilogue of the q/k/v projection, so q is still rounded

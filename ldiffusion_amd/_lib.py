@@ -38,7 +38,8 @@ class ConvArgs(C.Structure):
                 ("geglu", C.c_int), ("ld1", C.c_int), ("ld2", C.c_int), ("res_lo", C.c_int), ("y_lo", C.c_int), ("short_runs", C.c_int),
                 ("lo8_slab0", C.c_int), ("lo8_scale", C.c_void_p), ("gemm_df", C.c_int),
                 ("sc_x", C.c_void_p), ("sc_C", C.c_int), ("sc_ld", C.c_int), ("sc_w", C.c_void_p), ("sc_bias", C.c_void_p), ("c3d_ups", C.c_int), ("n_real", C.c_int), ("splitk", C.c_int),
-                ("out_shift", C.c_int), ("silu_out", C.c_int), ("cond_conv", C.c_int), ("lrelu_in", C.c_int), ("tconv", C.c_int), ("seg_conv", C.c_int)]
+                ("out_shift", C.c_int), ("silu_out", C.c_int), ("cond_conv", C.c_int), ("lrelu_in", C.c_int), ("tconv", C.c_int), ("seg_conv", C.c_int),
+                ("relu_out", C.c_int), ("cls_conv", C.c_int)]
 
 
 # name -> (restype, argtypes); every symbol include/ldiff.h declares
@@ -79,6 +80,15 @@ SIGNATURES = {
     "ldiff_segnet_forward": (I, [P, P, I, I, I, P, I, P]),
     "ldiff_segnet_check_finite": (I, [P, P]),
     "ldiff_segnet_destroy": (None, [P]),
+    "ldiff_resnet_create": (I, [C.POINTER(P), C.POINTER(I), I, I, I, I]),
+    "ldiff_resnet_load": (I, [P, C.c_char_p, P, I, C.POINTER(I64), I]),
+    "ldiff_resnet_missing": (I, [P]),
+    "ldiff_resnet_missing_name": (C.c_char_p, [P, I]),
+    "ldiff_resnet_set_graph": (I, [P, I]),
+    "ldiff_resnet_graph_replays": (I64, [P]),
+    "ldiff_resnet_forward": (I, [P, P, I, I, P, P, P]),
+    "ldiff_resnet_check_finite": (I, [P, P]),
+    "ldiff_resnet_destroy": (None, [P]),
     "ldiff_vae_create": (I, [C.POINTER(P), C.POINTER(VaeCfg), I]),
     "ldiff_vae_load": (I, [P, C.c_char_p, P, I, C.POINTER(I64), I]),
     "ldiff_vae_set_precision": (I, [P, I, I]),
@@ -110,6 +120,9 @@ SIGNATURES = {
     "ldiff_op_conv_stats_blocks": (I, [C.POINTER(ConvArgs)]),
     "ldiff_op_gn_finalize": (I, [P, I, I, P, I, I, I, I, I, F, P, P, P, P, P]),
     "ldiff_op_in_finalize": (I, [P, I, P, I, I, I, I, F, P, P, P, P, I, I, I, P]),
+    "ldiff_op_maxpool3x3s2": (I, [P, P, I, I, I, I, P]),
+    "ldiff_op_crop_resize_norm": (I, [P, I, I, P, I, P, I, C.POINTER(C.c_double), C.POINTER(C.c_double), P, P]),
+    "ldiff_op_cls_head": (I, [P, I, I, I, I, P, P, I, P, P, P]),
     "ldiff_op_attention": (I, [P, I, P, I, P, I, P, I, I, I, I, I, I, I64, I64, I64, F, P]),
     "ldiff_op_attention_prescaled": (I, [P, I, P, I, P, I, P, I, I, I, I, I, I, I64, I64, I64, P]),
     "ldiff_op_gn_stats": (I, [P, I, I, I, P, I, I, I, I, I, I, F, P, P, P, P, P]),

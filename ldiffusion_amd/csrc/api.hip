@@ -245,6 +245,77 @@ void ldiff_segnet_destroy(ldiff_segnet* n) {
   (void)hipDeviceSynchronize();
   delete n;
 }
+// ---- instance classifier of the cell head ----
+int ldiff_resnet_create(ldiff_resnet** out, const int* layers, int width, int adapter_channels, int num_classes, int device) {
+  API_BEGIN
+  LDIFF_CHECK(out && layers, LDIFF_ERR_INVALID, "resnet_create: null argument");
+  int ndev = 0;
+  HIP_CHECK(hipGetDeviceCount(&ndev));
+  LDIFF_CHECK(device >= 0 && device < ndev, LDIFF_ERR_INVALID, "resnet_create: device %d not available (%d devices)", device, ndev);
+  HIP_CHECK(hipSetDevice(device));
+  ldiff_resnet* r = new ldiff_resnet();
+  r->device = device;
+  for (int i = 0; i < 4; ++i) r->layers[i] = layers[i];
+  r->width = width; r->adapter_ch = adapter_channels; r->n_classes = num_classes;
+  try { r->build(); } catch (...) { delete r; throw; }
+  *out = r;
+  API_END
+}
+int ldiff_resnet_load(ldiff_resnet* r, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
+  API_BEGIN
+  LDIFF_CHECK(r, LDIFF_ERR_INVALID, "resnet_load: null handle");
+  HIP_CHECK(hipSetDevice(r->device));
+  r->load(name, host_ptr, dtype, shape, ndim);
+  API_END
+}
+int ldiff_resnet_missing(ldiff_resnet* r) { return r ? r->missing() : -1; }
+const char* ldiff_resnet_missing_name(ldiff_resnet* r, int i) { return r ? r->missing_name(i) : ""; }
+int ldiff_resnet_set_graph(ldiff_resnet* r, int on) {
+  API_BEGIN
+  LDIFF_CHECK(r, LDIFF_ERR_INVALID, "resnet_set_graph: null handle");
+  HIP_CHECK(hipSetDevice(r->device));
+  r->gc.enabled = on != 0;
+  if (!on) { HIP_CHECK(hipDeviceSynchronize()); r->gc.drop(); }
+  API_END
+}
+int64_t ldiff_resnet_graph_replays(ldiff_resnet* r) { return r ? r->gc.replays : -1; }
+int ldiff_resnet_forward(ldiff_resnet* r, const void* crops, int B, int S, void* logits, void* labels, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(r, LDIFF_ERR_INVALID, "resnet_forward: null handle");
+  report_nonfinite(r->nf, "resnet_forward");
+  r->forward((const f16*)crops, B, S, (float*)logits, (int*)labels, (hipStream_t)stream);
+  API_END
+}
+int ldiff_resnet_check_finite(ldiff_resnet* r, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(r, LDIFF_ERR_INVALID, "resnet_check_finite: null handle");
+  HIP_CHECK(hipSetDevice(r->device));
+  HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+  report_nonfinite(r->nf, "resnet_check_finite");
+  API_END
+}
+void ldiff_resnet_destroy(ldiff_resnet* r) {
+  if (!r) return;
+  (void)hipSetDevice(r->device);
+  (void)hipDeviceSynchronize();
+  delete r;
+}
+int ldiff_op_maxpool3x3s2(const void* x, void* y, int B, int H, int W, int C, void* stream) {
+  API_BEGIN
+  launch_maxpool3x3s2((const f16*)x, (f16*)y, B, H, W, C, (hipStream_t)stream);
+  API_END
+}
+int ldiff_op_crop_resize_norm(const void* rgb_u8, int H, int W, const void* boxes_i32, int n, const void* lut_u8, int S, const double* mean3, const double* std3, void* out_f16,
+                              void* stream) {
+  API_BEGIN
+  launch_crop_resize_norm((const uint8_t*)rgb_u8, H, W, (const int*)boxes_i32, n, (const uint8_t*)lut_u8, S, mean3, std3, (f16*)out_f16, (hipStream_t)stream);
+  API_END
+}
+int ldiff_op_cls_head(const void* x, int B, int HW, int A, int ldx, const void* w_f32, const void* bias_f32, int C, void* logits_f32, void* labels_i32_or_null, void* stream) {
+  API_BEGIN
+  launch_cls_head((const f16*)x, B, HW, A, ldx, (const float*)w_f32, (const float*)bias_f32, C, (float*)logits_f32, (int*)labels_i32_or_null, (hipStream_t)stream);
+  API_END
+}
 int ldiff_unet_attach_controlnet(ldiff_unet* u, ldiff_controlnet* c, float conditioning_scale) {
   API_BEGIN
   LDIFF_CHECK(u, LDIFF_ERR_INVALID, "unet_attach_controlnet: null handle");
@@ -663,7 +734,7 @@ static void conv_args_to_params(const ldiff_conv_args* a, ConvParams& p) {
   p.x = (const f16*)a->x; p.x2 = (const f16*)a->x2; p.C1 = a->C1; p.C2 = a->C2;
   p.B = a->B; p.Hin = a->Hin; p.Win = a->Win; p.Hout = a->Hout; p.Wout = a->Wout;
   p.ks = a->ks; p.stride = a->stride; p.pad_t = a->pad_t; p.pad_l = a->pad_l; p.ups = a->ups;
-  LDIFF_CHECK((p.ks == 1 || p.ks == 3 || (a->tconv && p.ks == 2)) && (p.stride == 1 || p.stride == 2) && (p.ups == 0 || p.ups == 1), LDIFF_ERR_INVALID,
+  LDIFF_CHECK((p.ks == 1 || p.ks == 3 || (a->tconv && p.ks == 2) || ((a->relu_out || a->cls_conv > 0) && p.ks == 7)) && (p.stride == 1 || p.stride == 2) && (p.ups == 0 || p.ups == 1), LDIFF_ERR_INVALID,
               "op_conv: unsupported ks=%d stride=%d ups=%d", p.ks, p.stride, p.ups);
   p.w = (const f16*)a->w; p.N = a->N; p.Nrows = a->Nrows; p.K = a->ks * a->ks * (a->C1 + a->C2);
   p.n_real = a->n_real > 0 && a->n_real <= a->N ? a->n_real : 0;
@@ -684,6 +755,7 @@ static void conv_args_to_params(const ldiff_conv_args* a, ConvParams& p) {
   p.silu_out = a->silu_out != 0;
   p.cond_force = a->cond_conv;
   p.lrelu_in = a->lrelu_in; p.tconv = a->tconv; p.seg_conv = a->seg_conv;
+  p.relu_out = a->relu_out != 0; p.cls_force = a->cls_conv;
   if (p.tconv) p.K = a->C1;   // one GEMM over the coarse map: the four taps are column blocks, not K
 }
 int ldiff_op_conv(const ldiff_conv_args* a, void* stream) {

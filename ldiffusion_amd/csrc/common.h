@@ -111,6 +111,11 @@ struct ConvParams {
   // sends such launches to igemm_lrelu<...> or, with tconv = 1 (transposed conv, kernel = stride = 2: ldiff_conv_args.tconv), to tconv2x2<...> (kernels_seg.hip)
   int lrelu_in = 0, tconv = 0;
   int seg_conv = 0;   // the narrow 3x3 kernel segconv<...> (kernels_seg.hip segconv_selected; ldiff_conv_args.seg_conv): 0 = launches with lrelu_in, 1 = every eligible launch, -1 = none
+  // ReLU BEHIND the sum (y = relu(sum + bias + res), one fp16 rounding): the classifier's conv family only (clsconv<...>, kernels_cls.hip); plan_conv refuses it for any
+  // launch that family does not take.  cls_force (ldiff_conv_args.cls_conv): 0 = the eligible launches that ask for relu_out, 1 = every eligible launch, -1 = none.
+  // nonfinite: the owning handle's sticky flag, set by that family's epilogue where sum + bias + res is NaN or beyond fp16's range (nullptr: not reported)
+  int relu_out = 0, cls_force = 0;
+  int* nonfinite = nullptr;
 };
 constexpr int LO8_SHIFT = 15;   // lo = x - fp16(x) of a GroupNorm + SiLU output: |lo| <= half an fp16 ulp = 2^-7 for |x| < 32, so lo * 2^15 <= 256 stays inside e4m3's 448;
                                 // for |x| in [32, 64) it reaches 512 and saturates at 448 (the correction term is clamped, harmless), as for everything beyond
@@ -120,7 +125,7 @@ void launch_lo8_weights(const f16* w, void* wd, int* scale_out, int Nrows, int t
 // count, the fused statistics' row blocks, the kernel with its tile, and the pre-packed weights it reads.  It writes ConvParams::splitk (0 = no
 // split), ::stats_R (0 = no fused statistics for this launch) and, with ConvPlan::fold_gn, the per-image weight strides; every buffer the plan
 // names (w_par, splitk_ws, stats, w_frag, folded weights) is the caller's to provide before launch_igemm.
-enum class ConvKernel { COND /* conditioning-embedding 3x3: kernels_cond.hip */, TCONV /* 2x2 transposed conv: kernels_seg.hip */, SEGCONV /* narrow 3x3 of the nnU-Net head: kernels_seg.hip */, C3_NARROW, C3_NARROW_FOLD, C3_DATAFLOW, C3_PINGPONG, C3_HALO, GEMM_DF, GEMM_DMA, IGEMM, NONE /* an fp8 lo half the ping-pong kernel does not take */ };
+enum class ConvKernel { COND /* conditioning-embedding 3x3: kernels_cond.hip */, TCONV /* 2x2 transposed conv: kernels_seg.hip */, SEGCONV /* narrow 3x3 of the nnU-Net head: kernels_seg.hip */, CLSCONV /* the instance classifier's 1x1 / 3x3 / 7x7 convs: kernels_cls.hip */, C3_NARROW, C3_NARROW_FOLD, C3_DATAFLOW, C3_PINGPONG, C3_HALO, GEMM_DF, GEMM_DMA, IGEMM, NONE /* an fp8 lo half the ping-pong kernel does not take */ };
 enum class ConvWeights { PLAIN, FRAG, FRAG_PAR, FRAG_SC, GEMM_FRAG };   // launch_pack_frag_weights{,_par,_sc} / launch_pack_gemm_frag -> ConvParams::w_frag
 struct ConvAsk {          // what the caller states beside the launch itself
   int splitk = 0;         // 0: plan a split count; 1: never split; >= 2: this count (ldiff_op_conv: tests, timing), checked against the K steps
@@ -149,6 +154,12 @@ void launch_segconv(const ConvParams& p, hipStream_t s);
 void launch_in_finalize(const float* part, int R, const f16* x_or_null, int ldx, int B, int HW, int C, float eps, const float* gamma, const float* beta, float* scale, float* shift,
                         int ld_ss, int ss_off, int ident /* leading channels set to scale 1, shift 0 */, hipStream_t s, int* nonfinite);
 void launch_nhwc_f32_to_nchw(const float* x, void* y, int B, int C, int H, int W, int ldx, int out_f16, hipStream_t s);
+// instance classifier of the cell head (kernels_cls.hip): its conv family (bias + residual + ReLU epilogue), the stem's max pooling, the crops, the head
+bool cls_conv_selected(const ConvParams& p);
+void launch_cls_conv(const ConvParams& p, hipStream_t s);
+void launch_maxpool3x3s2(const f16* x, f16* y, int B, int H, int W, int C, hipStream_t s);   // [B, H, W, C] -> [B, (H - 1) / 2 + 1, (W - 1) / 2 + 1, C], C % 8 == 0
+void launch_crop_resize_norm(const uint8_t* rgb, int H, int W, const int* boxes, int n, const uint8_t* lut, int S, const double* mean3, const double* std3, f16* out, hipStream_t s);
+void launch_cls_head(const f16* x, int B, int HW, int A, int ldx, const float* w, const float* bias, int C, float* logits, int* labels_or_null, hipStream_t s);
 void launch_scale_f16(const f16* x, f16* y, float a, long long n, hipStream_t s);   // y = f16(x * a)
 bool conv3x3_eligible(const ConvParams& p);   // the halo-tile 3x3 family: kernels_conv3x3.hip
 void launch_splitk_reduce(const ConvParams& p, hipStream_t s);   // sums p.splitk fp32 partials of splitk_ws and applies the epilogue (+ the fused GroupNorm statistics: R = H W / 32)

@@ -117,6 +117,10 @@ ConvPlan plan_conv(ConvParams& p, const ConvAsk& ask) {
   static const int df_mode = [] { const char* e = getenv("LDIFF_GEMM_DF"); return e ? atoi(e) : 1; }();
   if (q.df_force == 0 && (df_mode == 0 || df_mode == 2)) q.df_force = df_mode == 0 ? -1 : 1;
 
+  // A ReLU behind the sum exists in ONE family (0c below): asked for together with what selects another family it is refused here, before any of them can take the
+  // launch and drop it
+  LDIFF_CHECK(!q.relu_out || !(q.silu_out || q.cond_force > 0 || q.tconv || q.lrelu_in || q.seg_conv > 0), LDIFF_ERR_INVALID,
+              "conv: relu_out cannot be combined with silu_out / cond_conv = 1 / tconv / lrelu_in / seg_conv = 1 (only the classifier's conv family has a ReLU epilogue)");
   // 0. the conditioning-embedding 3x3 (kernels_cond.hip): channel counts no other family is made for; no split, no fused statistics (the caller's
   //    separate statistics pass), plain weights.  It is the one kernel with an activation behind its sum
   if (ask.splitk < 2 && cond_conv_selected(q)) {
@@ -146,6 +150,16 @@ ConvPlan plan_conv(ConvParams& p, const ConvAsk& ask) {
     p.stats_R = ask.stats ? segconv_stats_blocks(q) : 0;
     return pl;
   }
+  // 0c. the instance classifier's convs (kernels_cls.hip): the one family with a ReLU behind its sum, and the only one with 7x7 taps; no split (the K order of a sum
+  //     never depends on the batch), no fused statistics, plain weights
+  if (ask.splitk < 2 && !ask.stats && cls_conv_selected(q)) {
+    pl.kernel = ConvKernel::CLSCONV;
+    p.splitk = 0;
+    p.stats_R = 0;
+    return pl;
+  }
+  LDIFF_CHECK(!q.relu_out && q.ks != 7, LDIFF_ERR_INVALID, "conv: a ReLU epilogue (relu_out) and 7x7 taps exist only in the classifier's conv family, which does not take this launch (Cin=%d N=%d ks=%d stride=%d pad=%d cls_conv=%d)",
+              q.C1 + q.C2, q.N, q.ks, q.stride, q.pad_t, q.cls_force);
   LDIFF_CHECK(!q.silu_out, LDIFF_ERR_INVALID, "conv: a SiLU epilogue (silu_out) exists only in the conditioning-embedding kernel, which does not take this launch (Cin=%d N=%d ks=%d stride=%d)",
               q.C1 + q.C2, q.N, q.ks, q.stride);
   // 1. the kernel family.  GroupNorm -> 1x1 conv / Linear with no activation in between (VAE attention q/k/v; transformer proj_in under PREC_FAST):

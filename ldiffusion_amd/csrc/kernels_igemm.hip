@@ -331,6 +331,7 @@ void launch_igemm(const ConvParams& p, const ConvPlan& pl, hipStream_t s) {
     case ConvKernel::COND: launch_cond_conv(p, s); return;
     case ConvKernel::TCONV: launch_tconv2x2(p, s); return;
     case ConvKernel::SEGCONV: launch_segconv(p, s); return;
+    case ConvKernel::CLSCONV: launch_cls_conv(p, s); return;
     case ConvKernel::C3_NARROW: case ConvKernel::C3_NARROW_FOLD: launch_conv3x3n(p, pl.kernel == ConvKernel::C3_NARROW_FOLD, s); return;
     case ConvKernel::C3_DATAFLOW: launch_conv3x3d(p, s); return;
     case ConvKernel::C3_PINGPONG: launch_conv3x3p(p, s); return;

@@ -366,6 +366,59 @@ struct ldiff_segnet {
   ~ldiff_segnet();
 };
 
+// ---- instance classifier of the cell head -------------------------------------------------------------
+// torchvision's ResNet (v1.5 bottlenecks) + adapter conv + linear head (include/ldiff.h).  The checkpoint's tensors are staged on the host; a conv and its
+// BatchNorm are folded there in double (fold()) into one fp16 K-major matrix + fp32 bias, so every conv is one clsconv launch (kernels_cls.hip).
+struct ClsConvW {
+  std::string conv, bn;          // checkpoint prefixes; bn empty: the conv has its own bias (the adapter)
+  int Cin = 0, Cout = 0, ks = 1, stride = 1;
+  int Cin_pad = 0;               // stored input channels (the stem's 3 padded to 8 with zero weights)
+  f16* w = nullptr;              // [Cout][ks ks Cin_pad]
+  float* b = nullptr;            // [Cout]
+  bool folded = false;
+};
+struct ClsBlockW { int c1 = -1, c2 = -1, c3 = -1, down = -1; };   // indices into ldiff_resnet::convs
+struct ldiff_resnet {
+  int device = 0;
+  int layers[4] = {0, 0, 0, 0}, width = 0, adapter_ch = 0, n_classes = 0;
+  std::vector<ClsConvW> convs;
+  int stem = -1, adapter = -1;
+  std::vector<ClsBlockW> blocks;
+  float* fc_w = nullptr; float* fc_b = nullptr;   // [n_classes][adapter_ch], [n_classes] fp32
+  bool fc_w_loaded = false, fc_b_loaded = false;
+  // expected checkpoint tensors (name -> torch shape) and the host staging of those not yet folded
+  std::vector<std::pair<std::string, std::vector<int64_t>>> expected;
+  std::unordered_map<std::string, std::vector<float>> staged;
+  std::unordered_map<std::string, int> index;   // name -> entry of `expected`
+  std::vector<char> have;                       // loaded at least once
+  mutable std::vector<std::string> missing_cache;
+  std::vector<void*> allocs;
+  int generation = 0;
+  Exec ex;
+  NonFiniteFlag nf;
+  void build();
+  void load(const char* name, const void* host, int dtype, const int64_t* shape, int ndim);
+  void fold();                     // every group whose tensors are all staged -> device (synchronous copies: never inside a capture)
+  int missing() const;
+  const char* missing_name(int i) const;
+  Act conv(const ClsConvW& c, const Act& x, const Act* res, bool relu);
+  void forward(const f16* crops, int B, int S, float* logits, int* labels, hipStream_t s);
+  void forward_impl(const f16* crops, int B, int S, float* logits, int* labels, hipStream_t s);
+  struct GraphCache {
+    bool enabled = true;
+    int uses = 0;
+    long long key[4] = {0, 0, 0, 0};
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    hipStream_t cap_stream = nullptr;
+    f16* in = nullptr; float* logits = nullptr; int* labels = nullptr;
+    size_t in_cap = 0, out_cap = 0;
+    long long replays = 0;
+    void drop();
+  } gc;
+  ~ldiff_resnet();
+};
+
 struct ldiff_pipeline {
   ldiff_unet* unet;
   ldiff_vae* vae;

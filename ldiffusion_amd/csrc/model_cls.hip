@@ -1,0 +1,299 @@
+// ldiff_resnet: the instance classifier of the cell head (include/ldiff.h) -- torchvision's ResNet trunk (v1.5 bottlenecks), adapter conv, mean, linear head.
+// Executor over the same Exec / plan_conv as the other graphs; the weights are its own: a conv and its BatchNorm are folded on the host in double.
+#include <string.h>
+
+#include <algorithm>
+
+#include "model.h"
+
+static const double BN_EPS = 1e-5;   // torchvision's BatchNorm2d default, eval mode (running statistics)
+
+static int add_conv(ldiff_resnet& r, const std::string& conv, const std::string& bn, int Cin, int Cout, int ks, int stride) {
+  ClsConvW c;
+  c.conv = conv; c.bn = bn; c.Cin = Cin; c.Cout = Cout; c.ks = ks; c.stride = stride;
+  c.Cin_pad = (Cin + 7) / 8 * 8;
+  const size_t wbytes = (size_t)Cout * ks * ks * c.Cin_pad * sizeof(f16);
+  HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c.w), wbytes));
+  r.allocs.push_back(c.w);
+  HIP_CHECK(hipMemset(c.w, 0, wbytes));
+  HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c.b), (size_t)Cout * sizeof(float)));
+  r.allocs.push_back(c.b);
+  HIP_CHECK(hipMemset(c.b, 0, (size_t)Cout * sizeof(float)));
+  r.expected.push_back({conv + ".weight", {Cout, Cin, ks, ks}});
+  if (bn.empty()) r.expected.push_back({conv + ".bias", {Cout}});
+  else
+    for (const char* v : {".weight", ".bias", ".running_mean", ".running_var"}) r.expected.push_back({bn + v, {Cout}});
+  r.convs.push_back(c);
+  return (int)r.convs.size() - 1;
+}
+
+void ldiff_resnet::build() {
+  for (int i = 0; i < 4; ++i) LDIFF_CHECK(layers[i] >= 1 && layers[i] <= 64, LDIFF_ERR_INVALID, "resnet_create: layers[%d] = %d outside 1..64", i, layers[i]);
+  LDIFF_CHECK(width >= 16 && width <= 256 && width % 16 == 0, LDIFF_ERR_INVALID, "resnet_create: width = %d must be a multiple of 16 in 16..256", width);
+  LDIFF_CHECK(adapter_ch >= 16 && adapter_ch <= 8192 && adapter_ch % 16 == 0, LDIFF_ERR_INVALID, "resnet_create: adapter_channels = %d must be a multiple of 16 in 16..8192", adapter_ch);
+  LDIFF_CHECK(n_classes >= 2 && n_classes <= 4096, LDIFF_ERR_INVALID, "resnet_create: num_classes = %d outside 2..4096", n_classes);
+  nf.create();
+  ex.weights_gen = &generation;
+  ex.nonfinite = nf.words;
+  ex.trace_tag = "resnet";
+  stem = add_conv(*this, "encoder.0", "encoder.1", 3, width, 7, 2);
+  int inpl = width;
+  for (int L = 0; L < 4; ++L) {
+    const int planes = width << L;
+    for (int b = 0; b < layers[L]; ++b) {
+      const std::string pre = "encoder." + std::to_string(4 + L) + "." + std::to_string(b);
+      const int stride = (b == 0 && L > 0) ? 2 : 1;
+      ClsBlockW k;
+      k.c1 = add_conv(*this, pre + ".conv1", pre + ".bn1", inpl, planes, 1, 1);
+      k.c2 = add_conv(*this, pre + ".conv2", pre + ".bn2", planes, planes, 3, stride);   // v1.5: the stride sits on the 3x3 conv
+      k.c3 = add_conv(*this, pre + ".conv3", pre + ".bn3", planes, 4 * planes, 1, 1);
+      if (b == 0) k.down = add_conv(*this, pre + ".downsample.0", pre + ".downsample.1", inpl, 4 * planes, 1, stride);
+      blocks.push_back(k);
+      inpl = 4 * planes;
+    }
+  }
+  adapter = add_conv(*this, "adapter", "", inpl, adapter_ch, 3, 1);
+  expected.push_back({"classifier.weight", {n_classes, adapter_ch}});
+  expected.push_back({"classifier.bias", {n_classes}});
+  HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&fc_w), (size_t)n_classes * adapter_ch * sizeof(float)));
+  allocs.push_back(fc_w);
+  HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&fc_b), (size_t)n_classes * sizeof(float)));
+  allocs.push_back(fc_b);
+  for (size_t i = 0; i < expected.size(); ++i) index[expected[i].first] = (int)i;
+  have.assign(expected.size(), 0);
+}
+
+void ldiff_resnet::GraphCache::drop() {
+  if (exec) (void)hipGraphExecDestroy(exec);
+  if (graph) (void)hipGraphDestroy(graph);
+  exec = nullptr; graph = nullptr; uses = 0;
+}
+ldiff_resnet::~ldiff_resnet() {
+  nf.destroy();
+  gc.drop();
+  if (gc.in) (void)hipFree(gc.in);
+  if (gc.logits) (void)hipFree(gc.logits);
+  if (gc.labels) (void)hipFree(gc.labels);
+  if (gc.cap_stream) (void)hipStreamDestroy(gc.cap_stream);
+  for (void* p : allocs) (void)hipFree(p);
+}
+
+static inline double host_value(const void* p, int dtype, size_t i) {
+  if (dtype == LDIFF_F32) return ((const float*)p)[i];
+  if (dtype == LDIFF_F16) return (double)((const f16*)p)[i];
+  uint32_t u = (uint32_t)((const uint16_t*)p)[i] << 16;   // bf16
+  float f;
+  memcpy(&f, &u, 4);
+  return f;
+}
+
+void ldiff_resnet::load(const char* name_c, const void* host, int dtype, const int64_t* shape, int ndim) {
+  LDIFF_CHECK(name_c && host && (shape || ndim == 0), LDIFF_ERR_INVALID, "resnet_load: null argument");
+  LDIFF_CHECK(dtype == LDIFF_F32 || dtype == LDIFF_F16 || dtype == LDIFF_BF16, LDIFF_ERR_INVALID, "resnet_load(%s): unsupported dtype %d", name_c, dtype);
+  const std::string name(name_c);
+  static const std::string nbt = "num_batches_tracked";
+  if (name.size() >= nbt.size() && name.compare(name.size() - nbt.size(), nbt.size(), nbt) == 0) return;   // BatchNorm's step counter: not a parameter of the eval-mode forward
+  auto it = index.find(name);
+  LDIFF_CHECK(it != index.end(), LDIFF_ERR_INVALID, "resnet_load: unexpected tensor name '%s'", name_c);
+  const std::vector<int64_t>& want = expected[it->second].second;
+  bool ok = ndim == (int)want.size();
+  for (int i = 0; ok && i < ndim; ++i) ok = shape[i] == want[i];
+  if (!ok) {
+    std::string got, ws;
+    for (int i = 0; i < ndim; ++i) got += (i ? "," : "") + std::to_string((long long)shape[i]);
+    for (size_t i = 0; i < want.size(); ++i) ws += (i ? "," : "") + std::to_string((long long)want[i]);
+    ldiff_set_error("resnet_load(%s): shape [%s] does not match expected [%s]", name_c, got.c_str(), ws.c_str());
+    throw LdiffError{LDIFF_ERR_INVALID};
+  }
+  size_t numel = 1;
+  for (auto d : want) numel *= (size_t)d;
+  std::vector<float> v(numel);
+  for (size_t i = 0; i < numel; ++i) v[i] = (float)host_value(host, dtype, i);
+  if (name == "classifier.weight" || name == "classifier.bias") {
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(name == "classifier.weight" ? fc_w : fc_b, v.data(), numel * sizeof(float), hipMemcpyHostToDevice));
+  } else {
+    staged[name] = std::move(v);
+  }
+  have[it->second] = 1;
+  ++generation;
+}
+
+// w'[n][tap][c] = fp16(w[n][c][tap] * gamma[n] / sqrt(var[n] + eps)), b'[n] = fp32(beta[n] - mean[n] * gamma[n] / sqrt(var[n] + eps)), in double, one rounding each
+void ldiff_resnet::fold() {
+  if (staged.empty()) return;
+  HIP_CHECK(hipDeviceSynchronize());   // (earlier forwards may still read the matrices)
+  for (ClsConvW& c : convs) {
+    std::vector<std::string> names = {c.conv + ".weight"};
+    if (c.bn.empty()) names.push_back(c.conv + ".bias");
+    else
+      for (const char* v : {".weight", ".bias", ".running_mean", ".running_var"}) names.push_back(c.bn + v);
+    size_t n_staged = 0, n_have = 0;
+    for (auto& n : names) { n_staged += staged.count(n); n_have += have[index.at(n)] ? 1 : 0; }
+    if (n_staged == 0 || n_have < names.size()) continue;   // nothing new, or still incomplete (missing() names it)
+    LDIFF_CHECK(n_staged == names.size(), LDIFF_ERR_STATE, "resnet: '%s' was folded with its BatchNorm already; reloading part of the group needs all of %s.* and %s.* again",
+                c.conv.c_str(), c.conv.c_str(), c.bn.empty() ? c.conv.c_str() : c.bn.c_str());
+    const std::vector<float>& w = staged.at(names[0]);
+    const int taps = c.ks * c.ks, K = taps * c.Cin_pad;
+    std::vector<f16> wf((size_t)c.Cout * K, (f16)0.f);
+    std::vector<float> bf(c.Cout);
+    for (int n = 0; n < c.Cout; ++n) {
+      double scale = 1.0, shift;
+      if (c.bn.empty()) shift = staged.at(names[1])[n];
+      else {
+        const double g = staged.at(names[1])[n], be = staged.at(names[2])[n], mu = staged.at(names[3])[n], var = staged.at(names[4])[n];
+        scale = g / std::sqrt(var + BN_EPS);
+        shift = be - mu * scale;
+      }
+      bf[n] = (float)shift;
+      for (int ci = 0; ci < c.Cin; ++ci)
+        for (int t = 0; t < taps; ++t) wf[(size_t)n * K + (size_t)t * c.Cin_pad + ci] = (f16)((double)w[((size_t)n * c.Cin + ci) * taps + t] * scale);
+    }
+    HIP_CHECK(hipMemcpy(c.w, wf.data(), wf.size() * sizeof(f16), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(c.b, bf.data(), bf.size() * sizeof(float), hipMemcpyHostToDevice));
+    c.folded = true;
+    for (auto& n : names) staged.erase(n);
+  }
+}
+
+int ldiff_resnet::missing() const {
+  missing_cache.clear();
+  for (size_t i = 0; i < expected.size(); ++i)
+    if (!have[i]) missing_cache.push_back(expected[i].first);
+  return (int)missing_cache.size();
+}
+const char* ldiff_resnet::missing_name(int i) const {
+  if (i < 0 || i >= (int)missing_cache.size()) return "";
+  return missing_cache[i].c_str();
+}
+
+Act ldiff_resnet::conv(const ClsConvW& c, const Act& x, const Act* res, bool relu) {
+  ConvParams p;
+  memset(&p, 0, sizeof(p));
+  LDIFF_CHECK(x.C == c.Cin_pad && !x.split, LDIFF_ERR_INVALID, "resnet conv %s: input has %d channels, weight expects %d", c.conv.c_str(), x.C, c.Cin_pad);
+  p.x = x.p; p.C1 = x.C;
+  p.B = x.B; p.Hin = x.H; p.Win = x.W;
+  p.ks = c.ks; p.stride = c.stride; p.pad_t = c.ks / 2; p.pad_l = c.ks / 2;
+  p.Hout = (x.H - 1) / c.stride + 1; p.Wout = (x.W - 1) / c.stride + 1;
+  p.w = c.w; p.N = c.Cout; p.Nrows = c.Cout; p.K = c.ks * c.ks * c.Cin_pad;
+  p.bias = c.b;
+  p.M = x.B * p.Hout * p.Wout;
+  p.ldy = c.Cout;
+  p.relu_out = relu ? 1 : 0;
+  p.cls_force = 1;   // (the downsample and adapter convs carry no ReLU: the family on request)
+  p.nonfinite = ex.nonfinite;
+  if (res) {
+    LDIFF_CHECK(res->rows() == p.M && res->C == p.N && !res->split, LDIFF_ERR_INVALID, "resnet conv %s: identity shape mismatch", c.conv.c_str());
+    p.res = res->p; p.ld_res = res->ld();
+  }
+  Act y = ex.new_act(x.B, p.Hout, p.Wout, c.Cout);
+  p.y = y.p;   // (before the plan: the family's eligibility test looks at every pointer's alignment)
+  ConvAsk ask;
+  ask.splitk = 1;   // never split: the K order of a sum must not depend on the batch
+  const ConvPlan pl = plan_conv(p, ask);
+  LDIFF_CHECK(pl.kernel == ConvKernel::CLSCONV, LDIFF_ERR_INVALID, "resnet conv %s: not taken by the classifier's conv family", c.conv.c_str());
+  launch_igemm(p, pl, ex.s);
+  return y;
+}
+
+void ldiff_resnet::forward_impl(const f16* crops, int B, int S, float* logits, int* labels, hipStream_t s) {
+  HIP_CHECK(hipSetDevice(device));
+  ex.s = s;
+  ex.arena.reset();
+  // live at once, at most (first block of layer 1): the pooled map, two quarter-size tensors, the downsampled identity and the block's output: < 3 x the stem's output
+  const size_t unit = (size_t)B * (S / 2) * (S / 2) * width * sizeof(f16);
+  ex.arena.reserve(4 * unit + (8u << 20));
+
+  Act in;
+  in.p = const_cast<f16*>(crops); in.B = B; in.H = S; in.W = S; in.C = 8; in.borrowed = true;
+  Act a = conv(convs[stem], in, nullptr, true);
+  ex.trace("stem", a);
+  Act cur = ex.new_act(B, (a.H - 1) / 2 + 1, (a.W - 1) / 2 + 1, width);
+  launch_maxpool3x3s2(a.p, cur.p, B, a.H, a.W, width, s);
+  ex.release(a);
+  int bi = 0;
+  for (int L = 0; L < 4; ++L) {
+    for (int b = 0; b < layers[L]; ++b, ++bi) {
+      const ClsBlockW& k = blocks[bi];
+      Act t1 = conv(convs[k.c1], cur, nullptr, true);
+      Act t2 = conv(convs[k.c2], t1, nullptr, true);
+      ex.release(t1);
+      Act idn = cur;
+      if (k.down >= 0) idn = conv(convs[k.down], cur, nullptr, false);
+      Act out = conv(convs[k.c3], t2, &idn, true);   // relu(bn3(conv3) + identity)
+      ex.release(t2);
+      if (k.down >= 0) ex.release(idn);
+      ex.release(cur);
+      cur = out;
+    }
+    ex.trace(("layer" + std::to_string(L + 1)).c_str(), cur);
+  }
+  Act ad = conv(convs[adapter], cur, nullptr, false);
+  ex.release(cur);
+  ex.trace("adapter", ad);
+  launch_cls_head(ad.p, B, ad.H * ad.W, adapter_ch, ad.ld(), fc_w, fc_b, n_classes, logits, labels, s);
+  ex.release(ad);
+}
+
+void ldiff_resnet::forward(const f16* crops, int B, int S, float* logits, int* labels, hipStream_t s) {
+  LDIFF_CHECK(crops && logits, LDIFF_ERR_INVALID, "resnet_forward: null pointer");
+  LDIFF_CHECK(B >= 1, LDIFF_ERR_INVALID, "resnet_forward: B = %d must be at least 1", B);
+  LDIFF_CHECK(S >= 32 && S <= 1024 && S % 32 == 0, LDIFF_ERR_INVALID, "resnet_forward: S = %d must be a multiple of 32 in 32..1024", S);
+  LDIFF_CHECK((long long)B * (S / 2) * (S / 2) * width < (1ll << 31), LDIFF_ERR_INVALID, "resnet_forward: B * (S / 2)^2 * width exceeds 2^31 (B = %d, S = %d)", B, S);
+  LDIFF_CHECK(missing() == 0, LDIFF_ERR_STATE, "resnet: %d weight tensors not loaded (first: %s)", missing(), missing_name(0));
+  HIP_CHECK(hipSetDevice(device));
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (s) (void)hipStreamIsCapturing(s, &cs);
+  if (cs == hipStreamCaptureStatusNone) fold();
+  LDIFF_CHECK(staged.empty(), LDIFF_ERR_STATE, "resnet_forward: weights were loaded but not folded yet; the first forward after a load cannot run inside a stream capture");
+  static const bool env_off = getenv("LDIFF_NO_GRAPH") != nullptr;
+  if (!gc.enabled || env_off || prof_enabled() || cs != hipStreamCaptureStatusNone) {
+    forward_impl(crops, B, S, logits, labels, s);
+    return;
+  }
+  const size_t n_in = (size_t)B * S * S * 8 * sizeof(f16), n_log = (size_t)B * n_classes * sizeof(float), n_lab = (size_t)B * sizeof(int);
+  const long long key[4] = {B, S, generation, (long long)ex.arena.capacity()};
+  if (memcmp(key, gc.key, sizeof(key)) != 0) { gc.drop(); memcpy(gc.key, key, sizeof(key)); }
+  if (gc.uses == 0) {   // first use of this configuration: eager (sizes the workspace)
+    forward_impl(crops, B, S, logits, labels, s);
+    gc.uses = 1;
+    gc.key[3] = (long long)ex.arena.capacity();
+    return;
+  }
+  if (gc.uses == 1) {   // second use: capture the same launch sequence on staging buffers
+    if (n_in > gc.in_cap) {
+      if (gc.in) { HIP_CHECK(hipDeviceSynchronize()); HIP_CHECK(hipFree(gc.in)); gc.in = nullptr; }
+      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&gc.in), n_in));
+      gc.in_cap = n_in;
+    }
+    if (n_log + n_lab > gc.out_cap) {
+      HIP_CHECK(hipDeviceSynchronize());
+      if (gc.logits) { HIP_CHECK(hipFree(gc.logits)); gc.logits = nullptr; }
+      if (gc.labels) { HIP_CHECK(hipFree(gc.labels)); gc.labels = nullptr; }
+      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&gc.logits), n_log));
+      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&gc.labels), n_lab));
+      gc.out_cap = n_log + n_lab;
+    }
+    if (!gc.cap_stream) HIP_CHECK(hipStreamCreateWithFlags(&gc.cap_stream, hipStreamNonBlocking));
+    HIP_CHECK(hipStreamBeginCapture(gc.cap_stream, hipStreamCaptureModeThreadLocal));
+    hipGraph_t g = nullptr;
+    try {
+      forward_impl(gc.in, B, S, gc.logits, gc.labels, gc.cap_stream);
+    } catch (...) {
+      (void)hipStreamEndCapture(gc.cap_stream, &g);
+      if (g) (void)hipGraphDestroy(g);
+      gc.enabled = false;   // this configuration cannot be captured: stay eager (same kernels, same results)
+      forward_impl(crops, B, S, logits, labels, s);
+      return;
+    }
+    HIP_CHECK(hipStreamEndCapture(gc.cap_stream, &g));
+    gc.graph = g;
+    HIP_CHECK(hipGraphInstantiate(&gc.exec, g, nullptr, nullptr, 0));
+    gc.uses = 2;
+  }
+  HIP_CHECK(hipMemcpyAsync(gc.in, crops, n_in, hipMemcpyDeviceToDevice, s));
+  HIP_CHECK(hipGraphLaunch(gc.exec, s));
+  HIP_CHECK(hipMemcpyAsync(logits, gc.logits, n_log, hipMemcpyDeviceToDevice, s));
+  if (labels) HIP_CHECK(hipMemcpyAsync(labels, gc.labels, n_lab, hipMemcpyDeviceToDevice, s));
+  ++gc.replays;
+}

@@ -604,3 +604,72 @@ class PlainConvUNet:
                 self._h = None
         except Exception:
             pass
+
+
+class ResNetClassifier:
+    """The cell head's instance classifier on the HIP library (include/ldiff.h ldiff_resnet_*): torchvision's ResNet trunk (ResNet152: layers
+    (3, 8, 36, 3), width 64) without avgpool / fc, `adapter` conv, mean over the map, linear head -- `encoder` / `adapter` / `classifier` of
+    the reference's CellSegClassifier.  `state_dict` carries the module's own names (`cellhead.param_shapes`); every BatchNorm is folded into
+    its conv at load.  `net(crops [B, S, S, 8] float16 NHWC on the device, channels 3..7 zero) -> (logits [B, C] float32, labels [B] int32)`,
+    labels = 1 + argmax(logits[:, 1:])."""
+
+    def __init__(self, num_classes: int, state_dict, device=None, layers=(3, 8, 36, 3), width=64, adapter_channels=256):
+        from . import cellhead
+        _lib.require_gpu()
+        self.num_classes, self.layers, self.width, self.adapter_channels = int(num_classes), tuple(int(v) for v in layers), int(width), int(adapter_channels)
+        if len(self.layers) != 4:
+            raise ValueError(f"ResNetClassifier: layers must have 4 entries, got {layers}")
+        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        _lib.check(self._lib.ldiff_resnet_create(C.byref(self._h), (C.c_int * 4)(*self.layers), self.width, self.adapter_channels, self.num_classes,
+                                                 self.device.index or 0))
+        self._shapes = cellhead.param_shapes(self.num_classes, self.layers, self.width, self.adapter_channels, counters=True)
+        self.load_state_dict(state_dict)
+
+    def load_state_dict(self, sd, strict=True):
+        _load_state_dict(self._lib, self._lib.ldiff_resnet_load, self._h, sd, self._shapes)
+        n = self._lib.ldiff_resnet_missing(self._h)
+        if n and strict:
+            names = [self._lib.ldiff_resnet_missing_name(self._h, i).decode() for i in range(min(n, 5))]
+            raise RuntimeError(f"{n} classifier tensors missing from the checkpoint, e.g. {names}")
+
+    def set_graph(self, on: bool):
+        _lib.check(self._lib.ldiff_resnet_set_graph(self._h, int(bool(on))))
+        return self
+
+    @property
+    def graph_replays(self) -> int:
+        return int(self._lib.ldiff_resnet_graph_replays(self._h))
+
+    def check_finite(self):
+        _lib.check(self._lib.ldiff_resnet_check_finite(self._h, _lib.stream_ptr()))
+        return self
+
+    def eval(self):
+        return self
+
+    def to(self, *args, **kwargs):
+        return self
+
+    @torch.no_grad()
+    def __call__(self, crops):
+        if crops.dim() != 4 or crops.shape[1] != crops.shape[2] or crops.shape[3] != 8 or crops.dtype != torch.float16:
+            raise ValueError(f"ResNetClassifier: crops must be float16 [B, S, S, 8] (NHWC, channels 3..7 zero), got {crops.dtype} {list(crops.shape)}")
+        crops = crops.to(self.device).contiguous()
+        B, S = crops.shape[0], crops.shape[1]
+        logits = torch.empty((B, self.num_classes), dtype=torch.float32, device=self.device)
+        labels = torch.empty((B,), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.ldiff_resnet_forward(self._h, _lib.ptr(crops), B, S, _lib.ptr(logits), _lib.ptr(labels), _lib.stream_ptr()))
+        return logits, labels
+
+    forward = __call__
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._lib.ldiff_resnet_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass

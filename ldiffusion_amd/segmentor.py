@@ -188,12 +188,34 @@ class Segmentor:
             unet.detach_controlnet()
         return recon
 
+    def _cell_head(self, weight_dir):
+        """The cell head of a `segmentor_weight` folder (cellclassifier.pth), built once per (file, mtime)."""
+        from . import cellhead
+        ckpt = os.path.join(weight_dir, "cellclassifier.pth")
+        key = (os.path.abspath(ckpt), os.path.getmtime(ckpt))
+        cache = getattr(self, "_cell_heads", None)
+        if cache is None:
+            cache = self._cell_heads = {}
+        if key not in cache:
+            cache.clear()
+            cache[key] = cellhead.CellSegClassifier(self.num_classes, cellhead.read_cellclassifier(ckpt), self.device)
+        return cache[key]
+
     @torch.no_grad()
-    def inference_cell_model(self, image_path, diffusion_path, ldiffusion_weight, segmentor_weight, head=None, text_embeddings=None):
-        """segmentor.py:490-545 with the head injected: `head(decoded_rgb_float[1,3,1024,1024] normalised) -> logits [1,C,H,W]`."""
+    def inference_cell_model(self, image_path, diffusion_path, ldiffusion_weight, segmentor_weight, head=None, text_embeddings=None, instances=None):
+        """segmentor.py:490-545.  The cell head is either
+        * built from `segmentor_weight`, the folder that holds `cellclassifier.pth` (the reference's CellSegClassifier state_dict, :497), when `head` is
+          None: the ResNet152 instance classifier on the HIP library (`cellhead.py`; cached on this Segmentor).  `instances` = the callable that maps
+          the normalised HWC float32 image to an int label map (Cellpose `cyto2` in the reference: third-party, built lazily if it imports); or
+        * injected: `head(decoded_rgb_float[1,3,1024,1024] normalised) -> logits [1,C,H,W]`.
+        Neither: RuntimeError."""
         from PIL import Image
+        built = None
         if head is None:
-            raise RuntimeError("inference_cell_model: CellSegClassifier (Cellpose + ResNet152) is outside the hot-path scope; pass `head=`")
+            if not (isinstance(segmentor_weight, (str, os.PathLike)) and os.path.isfile(os.path.join(segmentor_weight, "cellclassifier.pth"))):
+                raise RuntimeError("inference_cell_model: the cell head needs `segmentor_weight` to be the folder that holds cellclassifier.pth "
+                                   "(CellSegClassifier's state_dict; Cellpose stays third-party: `instances=`), or pass `head=`")
+            built = self._cell_head(segmentor_weight)
         pipeline, unet, _ = self.load_ldiffusion(ldiffusion_weight, diffusion_path)
         image = Image.open(image_path).convert("RGB")
         width, height = image.size
@@ -206,9 +228,14 @@ class Segmentor:
         out = self._one_pass(x, text_embeddings, pipeline, unet)
         decoded = Image.fromarray(out["rgb"][0].cpu().numpy())
         self._sampler.check_finite()   # fp16 overflow in either graph raises here instead of yielding a plausible-looking mask
-        model_input = (out["rgb"].permute(0, 3, 1, 2).float() / 255.0 - mean) / std
-        logits = head(model_input)
-        mask = argmax_mask(logits)[0].cpu().numpy()
+        if built is not None:
+            mask = built.predict_mask(out["rgb"][0], instances=instances)   # the decoded uint8 image itself (the head's table restates the reference's float round trip); `instances` holds for this call only
+            built.net.check_finite()
+            mask = mask.cpu().numpy()
+        else:
+            model_input = (out["rgb"].permute(0, 3, 1, 2).float() / 255.0 - mean) / std
+            logits = head(model_input)
+            mask = argmax_mask(logits)[0].cpu().numpy()
         mask = np.array(Image.fromarray(mask.astype(np.uint8)).resize((width, height), resample=Image.NEAREST))
         return decoded.resize((width, height), Image.BILINEAR), mask
 
