@@ -39,7 +39,7 @@ class ConvArgs(C.Structure):
                 ("lo8_slab0", C.c_int), ("lo8_scale", C.c_void_p), ("gemm_df", C.c_int),
                 ("sc_x", C.c_void_p), ("sc_C", C.c_int), ("sc_ld", C.c_int), ("sc_w", C.c_void_p), ("sc_bias", C.c_void_p), ("c3d_ups", C.c_int), ("n_real", C.c_int), ("splitk", C.c_int),
                 ("out_shift", C.c_int), ("silu_out", C.c_int), ("cond_conv", C.c_int), ("lrelu_in", C.c_int), ("tconv", C.c_int), ("seg_conv", C.c_int),
-                ("relu_out", C.c_int), ("cls_conv", C.c_int)]
+                ("relu_out", C.c_int), ("cls_conv", C.c_int), ("fold_gn", C.c_int)]
 
 
 # name -> (restype, argtypes); every symbol include/ldiff.h declares

@@ -769,6 +769,7 @@ int ldiff_op_conv(const ldiff_conv_args* a, void* stream) {
   ConvAsk ask;
   ask.splitk = a->splitk ? a->splitk : (p.stats || p.xs || df_asked) ? 1 : 0;   // no planned split beside fused statistics, a folded shortcut or a forced gemm_df
   ask.stats = p.stats != nullptr;
+  ask.fold_gn = a->fold_gn != 0;
   const ConvPlan pl = plan_conv(p, ask);
   LDIFF_CHECK(!p.stats || p.stats_R > 0, LDIFF_ERR_INVALID, "op_conv: fused statistics are not supported for this shape");
   LDIFF_CHECK(!p.xs || (a->sc_w && pl.kernel == ConvKernel::C3_DATAFLOW), LDIFF_ERR_INVALID, "op_conv: a folded shortcut (sc_x) needs sc_w and a launch the dataflow conv3x3 kernel takes");
@@ -792,6 +793,12 @@ int ldiff_op_conv(const ldiff_conv_args* a, void* stream) {
       p.bias = bsum;
     }
     p.w_frag = wf;
+  }
+  if (pl.fold_gn) {   // the executor's two launches (model.hip): per-image weights and biases, then the plain GEMM on them
+    f16* wfold = (f16*)op_scratch(st, 6, (size_t)p.B * p.Nrows * p.K * sizeof(f16));
+    float* bfold = (float*)op_scratch(st, 7, (size_t)p.B * p.Nrows * sizeof(float));
+    launch_fold_gn_weights(p.w, p.bias, (const float*)a->gn_scale, (const float*)a->gn_shift, wfold, bfold, p.B, p.Nrows, p.K, st);
+    p.w = wfold; p.bias = bfold;
   }
   if (p.splitk > 1) p.splitk_ws = (float*)op_scratch(st, 1, (size_t)p.splitk * p.M * p.N * sizeof(float));
   if (pl.weights == ConvWeights::GEMM_FRAG) {   // LDIFF_OP_CACHE_FRAG=1 (timing scripts only): pack once per (matrix address, shape) -- stale as soon

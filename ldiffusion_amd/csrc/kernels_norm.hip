@@ -243,9 +243,10 @@ void launch_gn_stats(SrcView x1, SrcView x2, int B, int HW, int groups, float ep
   // small map with enough (image, group) workgroups, or a batch so small that either form is a latency chain (B = 1, the reference's own batch:
   // the two-launch form costs 22 us per tensor there, 43 tensors per UNet pass -- profiles/r05_unet_launches_b1.txt): one launch.
   // LDIFF_GN_SMALL_BATCH=0 restores the two-launch form for small batches (A/B).
+  // Profiler names: gn_stats<1> = the one-launch form, gn_stats<2> = partial + finalize (the tests pin each case to its form by them).
   static const bool small_batch = [] { const char* e = getenv("LDIFF_GN_SMALL_BATCH"); return !e || atoi(e) != 0; }();
   if ((HW <= 1024 && B * groups >= 64) || (small_batch && B * groups < 256 && HW <= 4096)) {
-    ProfScope prof("gn_stats", 3.0 * B * HW * (double)C, 2.0 * B * HW * ((double)C1 * (x1.lo ? 2 : 1) + (double)C2 * (x2.lo ? 2 : 1)), s);
+    ProfScope prof("gn_stats<1>", 3.0 * B * HW * (double)C, 2.0 * B * HW * ((double)C1 * (x1.lo ? 2 : 1) + (double)C2 * (x2.lo ? 2 : 1)), s);
     hipLaunchKernelGGL(gn_small_kernel, dim3(groups, B), dim3(256), 0, s, x1, x2, HW, groups, eps, gamma, beta, scale, shift, nonfinite);
     HIP_CHECK(hipGetLastError());
     return;
@@ -253,7 +254,7 @@ void launch_gn_stats(SrcView x1, SrcView x2, int B, int HW, int groups, float ep
   const int nchunk = gn_chunks(HW);
   const int pix = (HW + nchunk - 1) / nchunk;
   const size_t smem = 2 * 2048 * sizeof(float);  // [2][R][C] with R*C <= 256*8
-  ProfScope prof("gn_stats", 3.0 * B * HW * (double)C, 2.0 * B * HW * ((double)C1 * (x1.lo ? 2 : 1) + (double)C2 * (x2.lo ? 2 : 1)), s);
+  ProfScope prof("gn_stats<2>", 3.0 * B * HW * (double)C, 2.0 * B * HW * ((double)C1 * (x1.lo ? 2 : 1) + (double)C2 * (x2.lo ? 2 : 1)), s);
   hipLaunchKernelGGL(gn_partial_kernel, dim3(nchunk, B, C2 ? 2 : 1), dim3(256), smem, s, x1, x2, HW, pix, nchunk, partial);
   HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(gn_finalize_kernel, dim3(groups, B), dim3(64), 0, s, partial, nchunk, C, groups, HW, eps, gamma, beta, scale, shift, nonfinite);
@@ -404,6 +405,7 @@ __global__ __launch_bounds__(256) void fold_gn_weights_kernel(const f16* __restr
 void launch_fold_gn_weights(const f16* w, const float* bias, const float* scale, const float* shift, f16* wb, float* biasb, int B, int Nrows, int C,
                             hipStream_t s) {
   LDIFF_CHECK(C % 8 == 0, LDIFF_ERR_INVALID, "fold_gn_weights: C=%d must be a multiple of 8", C);
+  ProfScope prof("fold_gn_weights", 2.0 * B * (double)Nrows * C, (double)Nrows * C * 2.0 * (1 + B) + 8.0 * B * C, s);
   hipLaunchKernelGGL(fold_gn_weights_kernel, dim3((Nrows + 3) / 4, B), dim3(256), 0, s, w, bias, scale, shift, wb, biasb, Nrows, C);
   HIP_CHECK(hipGetLastError());
 }
