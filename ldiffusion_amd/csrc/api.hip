@@ -30,6 +30,46 @@ static void report_nonfinite(NonFiniteFlag& nf, const char* what, const char* hi
   }                                                              \
   return LDIFF_OK;
 
+// ---- what the handle families (unet, controlnet, vae, segnet, resnet) share ----
+template <class H> static int device_of(const H* h) { return h->device; }
+static int device_of(const ldiff_controlnet* c) { return c->trunk.device; }
+template <class H> static NonFiniteFlag& flag_of(H* h) { return h->nf; }
+static NonFiniteFlag& flag_of(ldiff_controlnet* c) { return c->trunk.nf; }
+
+static void select_device(const char* who, int device) {   // of a *_create
+  int ndev = 0;
+  HIP_CHECK(hipGetDeviceCount(&ndev));
+  LDIFF_CHECK(device >= 0 && device < ndev, LDIFF_ERR_INVALID, "%s: device %d not available (%d devices)", who, device, ndev);
+  HIP_CHECK(hipSetDevice(device));
+}
+// *_check_finite: `synced` runs between the synchronisation and the report (the VAE's side stream, the UNet's attached ControlNet)
+template <class H, class F> static int check_finite(H* h, void* stream, const char* who, const char* hint, F synced) {
+  API_BEGIN
+  LDIFF_CHECK(h, LDIFF_ERR_INVALID, "%s: null handle", who);
+  HIP_CHECK(hipSetDevice(device_of(h)));
+  HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+  synced();
+  report_nonfinite(flag_of(h), who, hint);
+  API_END
+}
+template <class H> static int check_finite(H* h, void* stream, const char* who) { return check_finite(h, stream, who, "", [] {}); }
+// *_destroy: `release` frees what the handle's destructor does not
+template <class H, class F> static void destroy(H* h, F release) {
+  if (!h) return;
+  (void)hipSetDevice(device_of(h));
+  (void)hipDeviceSynchronize();
+  release();
+  delete h;
+}
+template <class H> static void destroy(H* h) { destroy(h, [] {}); }
+template <class H> static int set_graph(H* h, int on, const char* who) {
+  API_BEGIN
+  LDIFF_CHECK(h, LDIFF_ERR_INVALID, "%s: null handle", who);
+  HIP_CHECK(hipSetDevice(h->device));
+  h->gc.set_enabled(on != 0);   // (off: waits for the device before the graph goes)
+  API_END
+}
+
 extern "C" {
 
 int ldiff_version(void) { return LDIFF_VERSION; }
@@ -39,10 +79,7 @@ const char* ldiff_last_error(void) { return ldiff_error_message(); }
 int ldiff_unet_create(ldiff_unet** out, const ldiff_unet_cfg* cfg, int device) {
   API_BEGIN
   LDIFF_CHECK(out && cfg, LDIFF_ERR_INVALID, "unet_create: null argument");
-  int ndev = 0;
-  HIP_CHECK(hipGetDeviceCount(&ndev));
-  LDIFF_CHECK(device >= 0 && device < ndev, LDIFF_ERR_INVALID, "unet_create: device %d not available (%d devices)", device, ndev);
-  HIP_CHECK(hipSetDevice(device));
+  select_device("unet_create", device);
   ldiff_unet* u = new ldiff_unet();
   u->cfg = *cfg;
   u->device = device;
@@ -63,14 +100,7 @@ int ldiff_unet_set_precision(ldiff_unet* u, int mode) {
   u->precision = mode;
   API_END
 }
-int ldiff_unet_set_graph(ldiff_unet* u, int on) {
-  API_BEGIN
-  LDIFF_CHECK(u, LDIFF_ERR_INVALID, "unet_set_graph: null handle");
-  HIP_CHECK(hipSetDevice(u->device));
-  if (!on) { HIP_CHECK(hipDeviceSynchronize()); u->gc.drop(); }
-  u->gc.enabled = on != 0;
-  API_END
-}
+int ldiff_unet_set_graph(ldiff_unet* u, int on) { return set_graph(u, on, "unet_set_graph"); }
 int64_t ldiff_unet_graph_replays(ldiff_unet* u) { return u ? (int64_t)u->gc.replays : -1; }
 int64_t ldiff_unet_graph_nodes(ldiff_unet* u) { return u ? (int64_t)u->gc.nodes : -1; }
 int ldiff_unet_missing(ldiff_unet* u) { return u ? u->ws.missing() : -1; }
@@ -102,33 +132,22 @@ int ldiff_unet_set_additional_residuals(ldiff_unet* u, const void* const* down_d
   API_END
 }
 int ldiff_unet_check_finite(ldiff_unet* u, void* stream) {
-  API_BEGIN
-  LDIFF_CHECK(u, LDIFF_ERR_INVALID, "unet_check_finite: null handle");
-  HIP_CHECK(hipSetDevice(u->device));
-  HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-  const bool cn_bad = u->cn && u->cn->trunk.nf.test_and_clear();   // an attached ControlNet's blocks ran inside this handle's forwards
-  if (cn_bad) (void)u->nf.test_and_clear();                        // (the UNet's own blocks inherit the overflow through the skips: one report for both)
-  LDIFF_CHECK(!cn_bad, LDIFF_ERR_NONFINITE, "unet_check_finite: a non-finite activation (fp16 overflow: |x| > 65504, or NaN) was detected in the attached ControlNet; "
-              "the results of that forward are invalid.  LDIFF_TRACE_ABSMAX=1 shows which stage overflows.");
-  report_nonfinite(u->nf, "unet_check_finite");
-  API_END
+  return check_finite(u, stream, "unet_check_finite", "", [u] {
+    const bool cn_bad = u->cn && u->cn->trunk.nf.test_and_clear();   // an attached ControlNet's blocks ran inside this handle's forwards
+    if (cn_bad) (void)u->nf.test_and_clear();                        // (the UNet's own blocks inherit the overflow through the skips: one report for both)
+    LDIFF_CHECK(!cn_bad, LDIFF_ERR_NONFINITE, "unet_check_finite: a non-finite activation (fp16 overflow: |x| > 65504, or NaN) was detected in the attached ControlNet; "
+                "the results of that forward are invalid.  LDIFF_TRACE_ABSMAX=1 shows which stage overflows.");
+  });
 }
 void ldiff_unet_destroy(ldiff_unet* u) {
-  if (!u) return;
-  (void)hipSetDevice(u->device);
-  (void)hipDeviceSynchronize();
-  if (u->ctx_buf) (void)hipFree(u->ctx_buf);
-  delete u;
+  destroy(u, [u] { if (u->ctx_buf) (void)hipFree(u->ctx_buf); });
 }
 
 // ---- ControlNet ----
 int ldiff_controlnet_create(ldiff_controlnet** out, const ldiff_unet_cfg* trunk_cfg, int conditioning_channels, const int* embedding_channels, int n_embedding, int device) {
   API_BEGIN
   LDIFF_CHECK(out && trunk_cfg && embedding_channels && n_embedding >= 1 && n_embedding <= LDIFF_MAX_BLOCKS, LDIFF_ERR_INVALID, "controlnet_create: bad arguments");
-  int ndev = 0;
-  HIP_CHECK(hipGetDeviceCount(&ndev));
-  LDIFF_CHECK(device >= 0 && device < ndev, LDIFF_ERR_INVALID, "controlnet_create: device %d not available (%d devices)", device, ndev);
-  HIP_CHECK(hipSetDevice(device));
+  select_device("controlnet_create", device);
   ldiff_controlnet* c = new ldiff_controlnet();
   c->trunk.cfg = *trunk_cfg;
   c->trunk.device = device;
@@ -173,29 +192,14 @@ int ldiff_controlnet_forward(ldiff_controlnet* c, const void* sample_dev, int B,
   c->forward((const float*)sample_dev, B, h, w, timestep, conditioning_scale, reinterpret_cast<float* const*>(down_out), n_down, (float*)mid_out, (hipStream_t)stream);
   API_END
 }
-int ldiff_controlnet_check_finite(ldiff_controlnet* c, void* stream) {
-  API_BEGIN
-  LDIFF_CHECK(c, LDIFF_ERR_INVALID, "controlnet_check_finite: null handle");
-  HIP_CHECK(hipSetDevice(c->trunk.device));
-  HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-  report_nonfinite(c->trunk.nf, "controlnet_check_finite");
-  API_END
-}
-void ldiff_controlnet_destroy(ldiff_controlnet* c) {
-  if (!c) return;
-  (void)hipSetDevice(c->trunk.device);
-  (void)hipDeviceSynchronize();
-  delete c;
-}
+int ldiff_controlnet_check_finite(ldiff_controlnet* c, void* stream) { return check_finite(c, stream, "controlnet_check_finite"); }
+void ldiff_controlnet_destroy(ldiff_controlnet* c) { destroy(c); }
 // ---- nnU-Net tissue head ----
 int ldiff_segnet_create(ldiff_segnet** out, int in_channels, int n_stages, const int* features, const int* strides, const int* n_conv_encoder, const int* n_conv_decoder,
                         int n_heads, int device) {
   API_BEGIN
   LDIFF_CHECK(out && features && strides && n_conv_encoder && n_conv_decoder && n_stages >= 2 && n_stages <= 16, LDIFF_ERR_INVALID, "segnet_create: null argument or n_stages outside 2..16");
-  int ndev = 0;
-  HIP_CHECK(hipGetDeviceCount(&ndev));
-  LDIFF_CHECK(device >= 0 && device < ndev, LDIFF_ERR_INVALID, "segnet_create: device %d not available (%d devices)", device, ndev);
-  HIP_CHECK(hipSetDevice(device));
+  select_device("segnet_create", device);
   ldiff_segnet* n = new ldiff_segnet();
   n->device = device;
   n->in_ch = in_channels; n->n_stages = n_stages; n->n_heads = n_heads;
@@ -216,13 +220,7 @@ int ldiff_segnet_load(ldiff_segnet* n, const char* name, const void* host_ptr, i
 }
 int ldiff_segnet_missing(ldiff_segnet* n) { return n ? n->ws.missing() : -1; }
 const char* ldiff_segnet_missing_name(ldiff_segnet* n, int i) { return n ? n->ws.missing_name(i) : ""; }
-int ldiff_segnet_set_graph(ldiff_segnet* n, int on) {
-  API_BEGIN
-  LDIFF_CHECK(n, LDIFF_ERR_INVALID, "segnet_set_graph: null handle");
-  n->gc.enabled = on != 0;
-  if (!on) n->gc.drop();
-  API_END
-}
+int ldiff_segnet_set_graph(ldiff_segnet* n, int on) { return set_graph(n, on, "segnet_set_graph"); }
 int64_t ldiff_segnet_graph_replays(ldiff_segnet* n) { return n ? n->gc.replays : -1; }
 int ldiff_segnet_forward(ldiff_segnet* n, const void* x_dev, int B, int H, int W, void* logits_dev, int out_dtype, void* stream) {
   API_BEGIN
@@ -231,28 +229,13 @@ int ldiff_segnet_forward(ldiff_segnet* n, const void* x_dev, int B, int H, int W
   n->forward((const float*)x_dev, B, H, W, logits_dev, out_dtype, (hipStream_t)stream);
   API_END
 }
-int ldiff_segnet_check_finite(ldiff_segnet* n, void* stream) {
-  API_BEGIN
-  LDIFF_CHECK(n, LDIFF_ERR_INVALID, "segnet_check_finite: null handle");
-  HIP_CHECK(hipSetDevice(n->device));
-  HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-  report_nonfinite(n->nf, "segnet_check_finite");
-  API_END
-}
-void ldiff_segnet_destroy(ldiff_segnet* n) {
-  if (!n) return;
-  (void)hipSetDevice(n->device);
-  (void)hipDeviceSynchronize();
-  delete n;
-}
+int ldiff_segnet_check_finite(ldiff_segnet* n, void* stream) { return check_finite(n, stream, "segnet_check_finite"); }
+void ldiff_segnet_destroy(ldiff_segnet* n) { destroy(n); }
 // ---- instance classifier of the cell head ----
 int ldiff_resnet_create(ldiff_resnet** out, const int* layers, int width, int adapter_channels, int num_classes, int device) {
   API_BEGIN
   LDIFF_CHECK(out && layers, LDIFF_ERR_INVALID, "resnet_create: null argument");
-  int ndev = 0;
-  HIP_CHECK(hipGetDeviceCount(&ndev));
-  LDIFF_CHECK(device >= 0 && device < ndev, LDIFF_ERR_INVALID, "resnet_create: device %d not available (%d devices)", device, ndev);
-  HIP_CHECK(hipSetDevice(device));
+  select_device("resnet_create", device);
   ldiff_resnet* r = new ldiff_resnet();
   r->device = device;
   for (int i = 0; i < 4; ++i) r->layers[i] = layers[i];
@@ -270,14 +253,7 @@ int ldiff_resnet_load(ldiff_resnet* r, const char* name, const void* host_ptr, i
 }
 int ldiff_resnet_missing(ldiff_resnet* r) { return r ? r->missing() : -1; }
 const char* ldiff_resnet_missing_name(ldiff_resnet* r, int i) { return r ? r->missing_name(i) : ""; }
-int ldiff_resnet_set_graph(ldiff_resnet* r, int on) {
-  API_BEGIN
-  LDIFF_CHECK(r, LDIFF_ERR_INVALID, "resnet_set_graph: null handle");
-  HIP_CHECK(hipSetDevice(r->device));
-  r->gc.enabled = on != 0;
-  if (!on) { HIP_CHECK(hipDeviceSynchronize()); r->gc.drop(); }
-  API_END
-}
+int ldiff_resnet_set_graph(ldiff_resnet* r, int on) { return set_graph(r, on, "resnet_set_graph"); }
 int64_t ldiff_resnet_graph_replays(ldiff_resnet* r) { return r ? r->gc.replays : -1; }
 int ldiff_resnet_forward(ldiff_resnet* r, const void* crops, int B, int S, void* logits, void* labels, void* stream) {
   API_BEGIN
@@ -286,20 +262,8 @@ int ldiff_resnet_forward(ldiff_resnet* r, const void* crops, int B, int S, void*
   r->forward((const f16*)crops, B, S, (float*)logits, (int*)labels, (hipStream_t)stream);
   API_END
 }
-int ldiff_resnet_check_finite(ldiff_resnet* r, void* stream) {
-  API_BEGIN
-  LDIFF_CHECK(r, LDIFF_ERR_INVALID, "resnet_check_finite: null handle");
-  HIP_CHECK(hipSetDevice(r->device));
-  HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-  report_nonfinite(r->nf, "resnet_check_finite");
-  API_END
-}
-void ldiff_resnet_destroy(ldiff_resnet* r) {
-  if (!r) return;
-  (void)hipSetDevice(r->device);
-  (void)hipDeviceSynchronize();
-  delete r;
-}
+int ldiff_resnet_check_finite(ldiff_resnet* r, void* stream) { return check_finite(r, stream, "resnet_check_finite"); }
+void ldiff_resnet_destroy(ldiff_resnet* r) { destroy(r); }
 int ldiff_op_maxpool3x3s2(const void* x, void* y, int B, int H, int W, int C, void* stream) {
   API_BEGIN
   launch_maxpool3x3s2((const f16*)x, (f16*)y, B, H, W, C, (hipStream_t)stream);
@@ -339,10 +303,7 @@ int ldiff_unet_attach_controlnet(ldiff_unet* u, ldiff_controlnet* c, float condi
 int ldiff_vae_create(ldiff_vae** out, const ldiff_vae_cfg* cfg, int device) {
   API_BEGIN
   LDIFF_CHECK(out && cfg, LDIFF_ERR_INVALID, "vae_create: null argument");
-  int ndev = 0;
-  HIP_CHECK(hipGetDeviceCount(&ndev));
-  LDIFF_CHECK(device >= 0 && device < ndev, LDIFF_ERR_INVALID, "vae_create: device %d not available (%d devices)", device, ndev);
-  HIP_CHECK(hipSetDevice(device));
+  select_device("vae_create", device);
   ldiff_vae* v = new ldiff_vae();
   v->cfg = *cfg;
   v->device = device;
@@ -390,21 +351,15 @@ int ldiff_vae_decode(ldiff_vae* v, const void* z_dev, int B, int h, int w, float
   API_END
 }
 int ldiff_vae_check_finite(ldiff_vae* v, void* stream) {
-  API_BEGIN
-  LDIFF_CHECK(v, LDIFF_ERR_INVALID, "vae_check_finite: null handle");
-  HIP_CHECK(hipSetDevice(v->device));
-  HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-  if (v->side_stream) HIP_CHECK(hipStreamSynchronize(v->side_stream));
-  report_nonfinite(v->nf, "vae_check_finite", VAE_RANGE_HINT);
-  API_END
+  return check_finite(v, stream, "vae_check_finite", VAE_RANGE_HINT, [v] {
+    if (v->side_stream) HIP_CHECK(hipStreamSynchronize(v->side_stream));
+  });
 }
 void ldiff_vae_destroy(ldiff_vae* v) {
-  if (!v) return;
-  (void)hipSetDevice(v->device);
-  (void)hipDeviceSynchronize();
-  if (v->ev_side) (void)hipEventDestroy(v->ev_side);
-  if (v->side_stream) (void)hipStreamDestroy(v->side_stream);
-  delete v;
+  destroy(v, [v] {
+    if (v->ev_side) (void)hipEventDestroy(v->ev_side);
+    if (v->side_stream) (void)hipStreamDestroy(v->side_stream);
+  });
 }
 
 // ---- sampler arithmetic ----

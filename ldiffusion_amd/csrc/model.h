@@ -1,8 +1,10 @@
 // Host-side executors: weight store, op helpers over the device arena, UNet / VAE graphs.
 // Internal to libldiff_hip.so.
 #pragma once
+#include <array>
 #include <cmath>
 #include <functional>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <string>
@@ -70,6 +72,10 @@ struct LoadSpec {
   int geglu_half = 0;   // > 0: GEGLU projection of width 2*geglu_half: row r lands at geglu_row(r) (x / gate interleaved by 16 rows)
   bool loaded = false;
 };
+
+// checkpoint loading, shared by WeightStore::load and ldiff_resnet::load
+float host_to_float(const void* p, int dtype, size_t i);   // element i of a host tensor of dtype LDIFF_F32 / F16 / BF16
+[[noreturn]] void throw_shape_mismatch(const char* who, const char* name, const int64_t* shape, int ndim, const std::vector<int64_t>& want);
 
 class WeightStore {
  public:
@@ -177,6 +183,47 @@ class Exec {
   Act resnet(const struct ResnetW& r, const Act& x, const Act* skip, const float* temb, int ld_temb, int groups, float eps, int prec);
 };
 
+// ---- hipGraph replay of an executor's forward -----------------------------------------------------
+// Growable device buffer: the staging of a captured forward's inputs and outputs.
+struct DeviceBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  ~DeviceBuf();
+  void ensure(size_t bytes);   // synchronises, frees and reallocates only when it grows
+  template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+// The replay cache of one executor (the UNet, the nnU-Net head, the instance classifier).  Lifecycle of a configuration, named by the key the
+// executor supplies (shape, precision, checkpoint generation, workspace capacities: whatever the launch sequence reads through a fixed address or was planned with):
+//   first use    the forward runs eagerly on the caller's pointers (builds lazily derived weights, sizes the workspaces); the key is then taken again
+//                from the executor, so a workspace that this pass grew does not make the next use look like a new configuration;
+//   second use   the same launch sequence is captured on handle-owned staging buffers into a hipGraph and instantiated; if the capture throws, the
+//                cache turns itself off and the forward stays eager (same kernels, same results);
+//   from then on copy-in, hipGraphLaunch on the caller's stream, copy-out: valid for any caller pointers.
+// A different key drops the graph and starts over.  Bypassed (plain eager forward) while disabled, under LDIFF_NO_GRAPH, while per-launch profiling is on and
+// on a stream that is itself being captured.  Whoever destroys a graph that may still be replaying synchronises first (set_enabled(false), the *_destroy entry points).
+struct GraphCache {
+  using Key = std::array<long long, 16>;   // unused entries stay 0
+  struct Staging { DeviceBuf* buf; size_t bytes; };
+  long long replays = 0, captures = 0, nodes = 0;   // nodes: kernel launches of the captured forward
+  ~GraphCache();
+  void set_enabled(bool on);            // off: waits for the device and drops the graph
+  bool bypass(hipStream_t s) const;     // run this forward eagerly, without touching the cache?
+  // one forward through the cache.  current_key: the executor's key now; staging: the buffers `staged` and the copies use, sized before the capture;
+  // eager: the forward on the caller's pointers and stream; staged(cs): the forward on the staging buffers and stream cs; copy_in / copy_out: caller <-> staging on s
+  void run(hipStream_t s, const std::function<Key()>& current_key, std::initializer_list<Staging> staging, const std::function<void()>& eager,
+           const std::function<void(hipStream_t)>& staged, const std::function<void()>& copy_in, const std::function<void()>& copy_out);
+
+ private:
+  bool enabled = true;
+  int uses = 0;   // forwards seen with the current key (0: none, 1: ran eagerly once, 2: graph ready)
+  Key key{};
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
+  hipStream_t cap_stream = nullptr;
+  void drop();
+};
+
 // ---- UNet -------------------------------------------------------------------------------------
 struct ResnetW { NormW n1, n2; MatW c1, c2, sc; bool has_sc = false; int temb_off = 0; int Cin = 0, Cout = 0; };
 struct TransformerW {
@@ -215,9 +262,8 @@ struct ldiff_unet {
   f16* ctx_buf = nullptr; size_t ctx_cap = 0;     // all kv_ctx live in one allocation
   void build();
   void set_context(const float* ctx, int Bc, int L, hipStream_t s);
-  // forward = the ~390-450 launches of one pass (384 at B = 8, 443 at B = 1 at SD-v1.5 size).  With graphs on (default) the launch sequence of a (B, h, w, precision, context)
-  // configuration is captured into a hipGraph on its second use and replayed afterwards: input, timestep and output go through
-  // handle-owned staging buffers, so the replay is valid for any caller pointers and any timestep.
+  // forward = the ~390-450 launches of one pass (384 at B = 8, 443 at B = 1 at SD-v1.5 size), through the replay cache (GraphCache above): the timestep
+  // is staged like the input and the output, so a replay is valid for any timestep.
   void forward(const float* x, int B, int h, int w, float t, float* out, hipStream_t s);
   void forward_impl(const float* x, int B, int h, int w, float t, const float* t_dev, float* out, hipStream_t s);
   // The stages of a pass that a UNet and a ControlNet's trunk share, and the state they hand on: begin_pass (argument checks, workspace), run_down
@@ -246,19 +292,9 @@ struct ldiff_unet {
   std::vector<const float*> extra_down;
   const float* extra_mid = nullptr;
   int n_skips() const;
-  struct GraphCache {
-    bool enabled = true;
-    int uses = 0;                       // forwards seen with the current key (0: none, 1: ran eagerly once, >= 2: graph ready)
-    long long key[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    hipStream_t cap_stream = nullptr;
-    float *in = nullptr, *out = nullptr, *t = nullptr;
-    size_t in_cap = 0;
-    long long replays = 0, captures = 0, nodes = 0;   // nodes: kernel launches of the captured forward
-    void drop();
-  } gc;
-  ~ldiff_unet();
+  GraphCache gc;
+  DeviceBuf st_in, st_out, st_t;   // staging of a captured forward: sample, output, timestep
+  ~ldiff_unet() { nf.destroy(); }
   Act transformer(const TransformerW& t, const Act& x);
 };
 
@@ -351,19 +387,9 @@ struct ldiff_segnet {
   void forward_impl(const float* x, int B, int H, int W, void* out, int out_dtype, hipStream_t s);
   // scale / shift [B, ident + a.C] of InstanceNorm over `a` (the leading `ident` channels: identity, for the upsampled half of a decoder concat)
   GNss in_ss(const Act& a, const NormW& w, int ident);
-  struct GraphCache {
-    bool enabled = true;
-    int uses = 0;
-    long long key[6] = {0, 0, 0, 0, 0, 0};
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    hipStream_t cap_stream = nullptr;
-    float* in = nullptr; void* out = nullptr;
-    size_t in_cap = 0, out_cap = 0;
-    long long replays = 0;
-    void drop();
-  } gc;
-  ~ldiff_segnet();
+  GraphCache gc;
+  DeviceBuf st_in, st_out;
+  ~ldiff_segnet() { nf.destroy(); }
 };
 
 // ---- instance classifier of the cell head -------------------------------------------------------------
@@ -404,18 +430,8 @@ struct ldiff_resnet {
   Act conv(const ClsConvW& c, const Act& x, const Act* res, bool relu);
   void forward(const f16* crops, int B, int S, float* logits, int* labels, hipStream_t s);
   void forward_impl(const f16* crops, int B, int S, float* logits, int* labels, hipStream_t s);
-  struct GraphCache {
-    bool enabled = true;
-    int uses = 0;
-    long long key[4] = {0, 0, 0, 0};
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    hipStream_t cap_stream = nullptr;
-    f16* in = nullptr; float* logits = nullptr; int* labels = nullptr;
-    size_t in_cap = 0, out_cap = 0;
-    long long replays = 0;
-    void drop();
-  } gc;
+  GraphCache gc;
+  DeviceBuf st_in, st_logits, st_labels;
   ~ldiff_resnet();
 };
 

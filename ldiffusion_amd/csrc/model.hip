@@ -173,13 +173,20 @@ MatW WeightStore::add_tconv(const std::string& prefix, int Cin, int Cout, int k)
 }
 void WeightStore::alias(const std::string& alias_name, const std::string& name) { alias_[alias_name] = name; }
 
-static inline float host_to_float(const void* p, int dtype, size_t i) {
+float host_to_float(const void* p, int dtype, size_t i) {
   if (dtype == LDIFF_F32) return ((const float*)p)[i];
   if (dtype == LDIFF_F16) return (float)((const f16*)p)[i];
   uint32_t u = (uint32_t)((const uint16_t*)p)[i] << 16;  // bf16
   float f;
   memcpy(&f, &u, 4);
   return f;
+}
+void throw_shape_mismatch(const char* who, const char* name, const int64_t* shape, int ndim, const std::vector<int64_t>& want) {
+  std::string got, exp;
+  for (int i = 0; i < ndim; ++i) got += (i ? "," : "") + std::to_string((long long)shape[i]);
+  for (size_t i = 0; i < want.size(); ++i) exp += (i ? "," : "") + std::to_string((long long)want[i]);
+  ldiff_set_error("%s(%s): shape [%s] does not match expected [%s]", who, name, got.c_str(), exp.c_str());
+  throw LdiffError{LDIFF_ERR_INVALID};
 }
 
 void WeightStore::load(const char* name_c, const void* host, int dtype, const int64_t* shape, int ndim) {
@@ -197,14 +204,7 @@ void WeightStore::load(const char* name_c, const void* host, int dtype, const in
   bool ok = numel == expect && ndim >= 1 && shape[0] == sp.shape[0];
   if (sp.kind == LoadSpec::MATRIX) ok = ok && ndim >= 2 && shape[1] == sp.shape[1] && (ndim == 4 || (ndim == 2 && sp.ks == 1));
   else ok = ok && ndim == 1;
-  if (!ok) {
-    std::string got;
-    for (int i = 0; i < ndim; ++i) got += (i ? "," : "") + std::to_string((long long)shape[i]);
-    std::string want;
-    for (size_t i = 0; i < sp.shape.size(); ++i) want += (i ? "," : "") + std::to_string((long long)sp.shape[i]);
-    ldiff_set_error("load(%s): shape [%s] does not match expected [%s]", name_c, got.c_str(), want.c_str());
-    throw LdiffError{LDIFF_ERR_INVALID};
-  }
+  if (!ok) throw_shape_mismatch("load", name_c, shape, ndim, sp.shape);
   if (sp.kind == LoadSpec::VECTOR) {
     std::vector<float> tmp(numel);
     for (size_t i = 0; i < numel; ++i) tmp[sp.geglu_half ? (size_t)geglu_row((int)i, sp.geglu_half) : i] = host_to_float(host, dtype, i);
@@ -957,81 +957,31 @@ int ldiff_unet::n_skips() const {
   for (int i = 0; i < cfg.n_blocks; ++i) n += cfg.layers_per_block + (i != cfg.n_blocks - 1 ? 1 : 0);
   return n;
 }
-void ldiff_unet::GraphCache::drop() {
-  if (exec) (void)hipGraphExecDestroy(exec);
-  if (graph) (void)hipGraphDestroy(graph);
-  exec = nullptr; graph = nullptr; uses = 0;
-}
-ldiff_unet::~ldiff_unet() {
-  nf.destroy();
-  gc.drop();
-  if (gc.in) (void)hipFree(gc.in);
-  if (gc.out) (void)hipFree(gc.out);
-  if (gc.t) (void)hipFree(gc.t);
-  if (gc.cap_stream) (void)hipStreamDestroy(gc.cap_stream);
-}
-
 void ldiff_unet::forward(const float* x, int B, int h, int w, float tval, float* out, hipStream_t s) {
-  static const bool env_off = getenv("LDIFF_NO_GRAPH") != nullptr;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (s) (void)hipStreamIsCapturing(s, &cs);   // the legacy default stream cannot be captured
-  if (!gc.enabled || env_off || prof_enabled() || cs != hipStreamCaptureStatusNone || !x || !out || B < 1 || h < 1 || w < 1 || !extra_down.empty() ||
-      extra_mid || encoder_only) {
+  if (!x || !out || B < 1 || h < 1 || w < 1 || !extra_down.empty() || extra_mid || encoder_only || gc.bypass(s)) {
     forward_impl(x, B, h, w, tval, nullptr, out, s);   // (argument errors are reported by forward_impl)
     return;
   }
   HIP_CHECK(hipSetDevice(device));
-  const size_t n_in = (size_t)B * cfg.in_channels * h * w, n_out = (size_t)B * cfg.out_channels * h * w;
+  const size_t n_in = (size_t)B * cfg.in_channels * h * w * sizeof(float), n_out = (size_t)B * cfg.out_channels * h * w * sizeof(float);
   // an attached ControlNet's launches are part of the captured sequence: whatever they read through a fixed address or were planned with is part of the key
-  const long long key[13] = {B, h, w, precision, (long long)ctx_B * 65536 + ctx_L, ws.generation, ctx_gen, (long long)ex.arena.capacity(),
-                             (long long)reinterpret_cast<uintptr_t>(cn), cn ? cn->state_gen : 0, cn ? (long long)cn->trunk.ex.arena.capacity() : 0,
-                             cn ? ((long long)cn->trunk.ws.generation << 24) + cn->trunk.ctx_gen * 4 + cn->trunk.precision : 0, cn_epoch};
-  if (memcmp(key, gc.key, sizeof(key)) != 0) { gc.drop(); memcpy(gc.key, key, sizeof(key)); }
-  if (gc.uses == 0) {               // first use of this configuration: eager (builds lazily derived weights, sizes the workspaces)
-    forward_impl(x, B, h, w, tval, nullptr, out, s);
-    gc.uses = 1;
-    return;
-  }
-  if (gc.uses == 1) {               // second use: capture the same launch sequence on staging buffers
-    const size_t need = std::max(n_in, n_out) * sizeof(float);
-    if (need > gc.in_cap) {
-      if (gc.in) { HIP_CHECK(hipDeviceSynchronize()); HIP_CHECK(hipFree(gc.in)); HIP_CHECK(hipFree(gc.out)); gc.in = gc.out = nullptr; }
-      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&gc.in), need));
-      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&gc.out), need));
-      gc.in_cap = need;
-    }
-    if (!gc.t) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&gc.t), sizeof(float)));
-    // capture on a handle-owned stream (the caller's may be the legacy default stream, which cannot be captured); nothing
-    // executes during capture, and the instantiated graph is launched on the caller's stream
-    if (!gc.cap_stream) HIP_CHECK(hipStreamCreateWithFlags(&gc.cap_stream, hipStreamNonBlocking));
-    HIP_CHECK(hipStreamBeginCapture(gc.cap_stream, hipStreamCaptureModeThreadLocal));
-    hipGraph_t g = nullptr;
-    try {
-      forward_impl(gc.in, B, h, w, 0.f, gc.t, gc.out, gc.cap_stream);
-    } catch (...) {
-      (void)hipStreamEndCapture(gc.cap_stream, &g);
-      if (g) (void)hipGraphDestroy(g);
-      gc.enabled = false;           // this configuration cannot be captured: stay eager (same kernels, same results)
-      forward_impl(x, B, h, w, tval, nullptr, out, s);
-      return;
-    }
-    HIP_CHECK(hipStreamEndCapture(gc.cap_stream, &g));
-    gc.graph = g;
-    {
-      size_t n_nodes = 0;
-      if (hipGraphGetNodes(g, nullptr, &n_nodes) == hipSuccess) gc.nodes = (long long)n_nodes;
-      static const bool debug = getenv("LDIFF_DEBUG") != nullptr;
-      if (debug) fprintf(stderr, "[ldiff_unet] captured forward B=%d %dx%d precision %d: %lld graph nodes (= kernel launches per pass)\n", B, h, w, precision, gc.nodes);
-    }
-    HIP_CHECK(hipGraphInstantiate(&gc.exec, g, nullptr, nullptr, 0));
-    gc.uses = 2;
-    ++gc.captures;
-  }
-  HIP_CHECK(hipMemcpyAsync(gc.in, x, n_in * sizeof(float), hipMemcpyDeviceToDevice, s));
-  launch_set_scalar(gc.t, tval, s);
-  HIP_CHECK(hipGraphLaunch(gc.exec, s));
-  HIP_CHECK(hipMemcpyAsync(out, gc.out, n_out * sizeof(float), hipMemcpyDeviceToDevice, s));
-  ++gc.replays;
+  auto key = [&] {
+    return GraphCache::Key{B, h, w, precision, (long long)ctx_B * 65536 + ctx_L, ws.generation, ctx_gen, (long long)ex.arena.capacity(),
+                           (long long)reinterpret_cast<uintptr_t>(cn), cn ? cn->state_gen : 0, cn ? (long long)cn->trunk.ex.arena.capacity() : 0,
+                           cn ? ((long long)cn->trunk.ws.generation << 24) + cn->trunk.ctx_gen * 4 + cn->trunk.precision : 0, cn_epoch};
+  };
+  const long long captures = gc.captures;
+  gc.run(s, key, {{&st_in, n_in}, {&st_out, n_out}, {&st_t, sizeof(float)}},
+         [&] { forward_impl(x, B, h, w, tval, nullptr, out, s); },
+         [&](hipStream_t cs) { forward_impl(st_in.as<float>(), B, h, w, 0.f, st_t.as<float>(), st_out.as<float>(), cs); },
+         [&] {
+           HIP_CHECK(hipMemcpyAsync(st_in.p, x, n_in, hipMemcpyDeviceToDevice, s));
+           launch_set_scalar(st_t.as<float>(), tval, s);
+         },
+         [&] { HIP_CHECK(hipMemcpyAsync(out, st_out.p, n_out, hipMemcpyDeviceToDevice, s)); });
+  static const bool debug = getenv("LDIFF_DEBUG") != nullptr;
+  if (debug && gc.captures != captures)
+    fprintf(stderr, "[ldiff_unet] captured forward B=%d %dx%d precision %d: %lld graph nodes (= kernel launches per pass)\n", B, h, w, precision, gc.nodes);
 }
 
 void ldiff_unet::begin_pass(int B, int h, int w, hipStream_t s) {

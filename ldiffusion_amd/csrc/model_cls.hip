@@ -63,28 +63,9 @@ void ldiff_resnet::build() {
   have.assign(expected.size(), 0);
 }
 
-void ldiff_resnet::GraphCache::drop() {
-  if (exec) (void)hipGraphExecDestroy(exec);
-  if (graph) (void)hipGraphDestroy(graph);
-  exec = nullptr; graph = nullptr; uses = 0;
-}
 ldiff_resnet::~ldiff_resnet() {
   nf.destroy();
-  gc.drop();
-  if (gc.in) (void)hipFree(gc.in);
-  if (gc.logits) (void)hipFree(gc.logits);
-  if (gc.labels) (void)hipFree(gc.labels);
-  if (gc.cap_stream) (void)hipStreamDestroy(gc.cap_stream);
   for (void* p : allocs) (void)hipFree(p);
-}
-
-static inline double host_value(const void* p, int dtype, size_t i) {
-  if (dtype == LDIFF_F32) return ((const float*)p)[i];
-  if (dtype == LDIFF_F16) return (double)((const f16*)p)[i];
-  uint32_t u = (uint32_t)((const uint16_t*)p)[i] << 16;   // bf16
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
 }
 
 void ldiff_resnet::load(const char* name_c, const void* host, int dtype, const int64_t* shape, int ndim) {
@@ -98,17 +79,11 @@ void ldiff_resnet::load(const char* name_c, const void* host, int dtype, const i
   const std::vector<int64_t>& want = expected[it->second].second;
   bool ok = ndim == (int)want.size();
   for (int i = 0; ok && i < ndim; ++i) ok = shape[i] == want[i];
-  if (!ok) {
-    std::string got, ws;
-    for (int i = 0; i < ndim; ++i) got += (i ? "," : "") + std::to_string((long long)shape[i]);
-    for (size_t i = 0; i < want.size(); ++i) ws += (i ? "," : "") + std::to_string((long long)want[i]);
-    ldiff_set_error("resnet_load(%s): shape [%s] does not match expected [%s]", name_c, got.c_str(), ws.c_str());
-    throw LdiffError{LDIFF_ERR_INVALID};
-  }
+  if (!ok) throw_shape_mismatch("resnet_load", name_c, shape, ndim, want);
   size_t numel = 1;
   for (auto d : want) numel *= (size_t)d;
   std::vector<float> v(numel);
-  for (size_t i = 0; i < numel; ++i) v[i] = (float)host_value(host, dtype, i);
+  for (size_t i = 0; i < numel; ++i) v[i] = host_to_float(host, dtype, i);
   if (name == "classifier.weight" || name == "classifier.bias") {
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(name == "classifier.weight" ? fc_w : fc_b, v.data(), numel * sizeof(float), hipMemcpyHostToDevice));
@@ -246,54 +221,17 @@ void ldiff_resnet::forward(const f16* crops, int B, int S, float* logits, int* l
   if (s) (void)hipStreamIsCapturing(s, &cs);
   if (cs == hipStreamCaptureStatusNone) fold();
   LDIFF_CHECK(staged.empty(), LDIFF_ERR_STATE, "resnet_forward: weights were loaded but not folded yet; the first forward after a load cannot run inside a stream capture");
-  static const bool env_off = getenv("LDIFF_NO_GRAPH") != nullptr;
-  if (!gc.enabled || env_off || prof_enabled() || cs != hipStreamCaptureStatusNone) {
+  if (gc.bypass(s)) {
     forward_impl(crops, B, S, logits, labels, s);
     return;
   }
   const size_t n_in = (size_t)B * S * S * 8 * sizeof(f16), n_log = (size_t)B * n_classes * sizeof(float), n_lab = (size_t)B * sizeof(int);
-  const long long key[4] = {B, S, generation, (long long)ex.arena.capacity()};
-  if (memcmp(key, gc.key, sizeof(key)) != 0) { gc.drop(); memcpy(gc.key, key, sizeof(key)); }
-  if (gc.uses == 0) {   // first use of this configuration: eager (sizes the workspace)
-    forward_impl(crops, B, S, logits, labels, s);
-    gc.uses = 1;
-    gc.key[3] = (long long)ex.arena.capacity();
-    return;
-  }
-  if (gc.uses == 1) {   // second use: capture the same launch sequence on staging buffers
-    if (n_in > gc.in_cap) {
-      if (gc.in) { HIP_CHECK(hipDeviceSynchronize()); HIP_CHECK(hipFree(gc.in)); gc.in = nullptr; }
-      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&gc.in), n_in));
-      gc.in_cap = n_in;
-    }
-    if (n_log + n_lab > gc.out_cap) {
-      HIP_CHECK(hipDeviceSynchronize());
-      if (gc.logits) { HIP_CHECK(hipFree(gc.logits)); gc.logits = nullptr; }
-      if (gc.labels) { HIP_CHECK(hipFree(gc.labels)); gc.labels = nullptr; }
-      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&gc.logits), n_log));
-      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&gc.labels), n_lab));
-      gc.out_cap = n_log + n_lab;
-    }
-    if (!gc.cap_stream) HIP_CHECK(hipStreamCreateWithFlags(&gc.cap_stream, hipStreamNonBlocking));
-    HIP_CHECK(hipStreamBeginCapture(gc.cap_stream, hipStreamCaptureModeThreadLocal));
-    hipGraph_t g = nullptr;
-    try {
-      forward_impl(gc.in, B, S, gc.logits, gc.labels, gc.cap_stream);
-    } catch (...) {
-      (void)hipStreamEndCapture(gc.cap_stream, &g);
-      if (g) (void)hipGraphDestroy(g);
-      gc.enabled = false;   // this configuration cannot be captured: stay eager (same kernels, same results)
-      forward_impl(crops, B, S, logits, labels, s);
-      return;
-    }
-    HIP_CHECK(hipStreamEndCapture(gc.cap_stream, &g));
-    gc.graph = g;
-    HIP_CHECK(hipGraphInstantiate(&gc.exec, g, nullptr, nullptr, 0));
-    gc.uses = 2;
-  }
-  HIP_CHECK(hipMemcpyAsync(gc.in, crops, n_in, hipMemcpyDeviceToDevice, s));
-  HIP_CHECK(hipGraphLaunch(gc.exec, s));
-  HIP_CHECK(hipMemcpyAsync(logits, gc.logits, n_log, hipMemcpyDeviceToDevice, s));
-  if (labels) HIP_CHECK(hipMemcpyAsync(labels, gc.labels, n_lab, hipMemcpyDeviceToDevice, s));
-  ++gc.replays;
+  gc.run(s, [&] { return GraphCache::Key{B, S, generation, (long long)ex.arena.capacity()}; }, {{&st_in, n_in}, {&st_logits, n_log}, {&st_labels, n_lab}},
+         [&] { forward_impl(crops, B, S, logits, labels, s); },
+         [&](hipStream_t cap) { forward_impl(st_in.as<f16>(), B, S, st_logits.as<float>(), st_labels.as<int>(), cap); },
+         [&] { HIP_CHECK(hipMemcpyAsync(st_in.p, crops, n_in, hipMemcpyDeviceToDevice, s)); },
+         [&] {
+           HIP_CHECK(hipMemcpyAsync(logits, st_logits.p, n_log, hipMemcpyDeviceToDevice, s));
+           if (labels) HIP_CHECK(hipMemcpyAsync(labels, st_labels.p, n_lab, hipMemcpyDeviceToDevice, s));
+         });
 }

@@ -54,19 +54,6 @@ void ldiff_segnet::build() {
   head = ws.add_conv("decoder.seg_layers." + std::to_string(n_stages - 2), features[0], n_heads, 1);
 }
 
-void ldiff_segnet::GraphCache::drop() {
-  if (exec) (void)hipGraphExecDestroy(exec);
-  if (graph) (void)hipGraphDestroy(graph);
-  exec = nullptr; graph = nullptr; uses = 0;
-}
-ldiff_segnet::~ldiff_segnet() {
-  nf.destroy();
-  gc.drop();
-  if (gc.in) (void)hipFree(gc.in);
-  if (gc.out) (void)hipFree(gc.out);
-  if (gc.cap_stream) (void)hipStreamDestroy(gc.cap_stream);
-}
-
 GNss ldiff_segnet::in_ss(const Act& a, const NormW& w, int ident) {
   LDIFF_CHECK(a.C == w.C && !a.split, LDIFF_ERR_INVALID, "instance norm: %d channels, weight has %d", a.C, w.C);
   GNss g;
@@ -179,55 +166,15 @@ void ldiff_segnet::forward_impl(const float* x, int B, int H, int W, void* out, 
 }
 
 void ldiff_segnet::forward(const float* x, int B, int H, int W, void* out, int out_dtype, hipStream_t s) {
-  static const bool env_off = getenv("LDIFF_NO_GRAPH") != nullptr;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (s) (void)hipStreamIsCapturing(s, &cs);
-  if (!gc.enabled || env_off || prof_enabled() || cs != hipStreamCaptureStatusNone || !x || !out || B < 1 || H < 1 || W < 1 ||
-      (out_dtype != LDIFF_F32 && out_dtype != LDIFF_F16)) {
+  if (!x || !out || B < 1 || H < 1 || W < 1 || (out_dtype != LDIFF_F32 && out_dtype != LDIFF_F16) || gc.bypass(s)) {
     forward_impl(x, B, H, W, out, out_dtype, s);   // (argument errors are reported by forward_impl)
     return;
   }
   HIP_CHECK(hipSetDevice(device));
   const size_t n_in = (size_t)B * in_ch * H * W * sizeof(float), n_out = (size_t)B * n_heads * H * W * (out_dtype == LDIFF_F16 ? 2 : 4);
-  const long long key[6] = {B, H, W, out_dtype, ws.generation, (long long)ex.arena.capacity()};
-  if (memcmp(key, gc.key, sizeof(key)) != 0) { gc.drop(); memcpy(gc.key, key, sizeof(key)); }
-  if (gc.uses == 0) {   // first use of this configuration: eager (sizes the workspace)
-    forward_impl(x, B, H, W, out, out_dtype, s);
-    gc.uses = 1;
-    const long long cap = (long long)ex.arena.capacity();
-    if (cap != gc.key[5]) gc.key[5] = cap;   // the eager pass grew the workspace: the key of what the next use captures
-    return;
-  }
-  if (gc.uses == 1) {   // second use: capture the same launch sequence on staging buffers
-    if (n_in > gc.in_cap) {
-      if (gc.in) { HIP_CHECK(hipDeviceSynchronize()); HIP_CHECK(hipFree(gc.in)); gc.in = nullptr; }
-      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&gc.in), n_in));
-      gc.in_cap = n_in;
-    }
-    if (n_out > gc.out_cap) {
-      if (gc.out) { HIP_CHECK(hipDeviceSynchronize()); HIP_CHECK(hipFree(gc.out)); gc.out = nullptr; }
-      HIP_CHECK(hipMalloc(&gc.out, n_out));
-      gc.out_cap = n_out;
-    }
-    if (!gc.cap_stream) HIP_CHECK(hipStreamCreateWithFlags(&gc.cap_stream, hipStreamNonBlocking));
-    HIP_CHECK(hipStreamBeginCapture(gc.cap_stream, hipStreamCaptureModeThreadLocal));
-    hipGraph_t g = nullptr;
-    try {
-      forward_impl(gc.in, B, H, W, gc.out, out_dtype, gc.cap_stream);
-    } catch (...) {
-      (void)hipStreamEndCapture(gc.cap_stream, &g);
-      if (g) (void)hipGraphDestroy(g);
-      gc.enabled = false;   // this configuration cannot be captured: stay eager (same kernels, same results)
-      forward_impl(x, B, H, W, out, out_dtype, s);
-      return;
-    }
-    HIP_CHECK(hipStreamEndCapture(gc.cap_stream, &g));
-    gc.graph = g;
-    HIP_CHECK(hipGraphInstantiate(&gc.exec, g, nullptr, nullptr, 0));
-    gc.uses = 2;
-  }
-  HIP_CHECK(hipMemcpyAsync(gc.in, x, n_in, hipMemcpyDeviceToDevice, s));
-  HIP_CHECK(hipGraphLaunch(gc.exec, s));
-  HIP_CHECK(hipMemcpyAsync(out, gc.out, n_out, hipMemcpyDeviceToDevice, s));
-  ++gc.replays;
+  gc.run(s, [&] { return GraphCache::Key{B, H, W, out_dtype, ws.generation, (long long)ex.arena.capacity()}; }, {{&st_in, n_in}, {&st_out, n_out}},
+         [&] { forward_impl(x, B, H, W, out, out_dtype, s); },
+         [&](hipStream_t cs) { forward_impl(st_in.as<float>(), B, H, W, st_out.p, out_dtype, cs); },
+         [&] { HIP_CHECK(hipMemcpyAsync(st_in.p, x, n_in, hipMemcpyDeviceToDevice, s)); },
+         [&] { HIP_CHECK(hipMemcpyAsync(out, st_out.p, n_out, hipMemcpyDeviceToDevice, s)); });
 }

@@ -73,7 +73,64 @@ def _tensor_key(t):
     return (t.data_ptr(), tuple(t.shape), t._version, t.dtype, t.device)
 
 
-class UNet2DConditionModel:
+class _Handle:
+    """What the handle classes share.  A subclass names its entry points (`ldiff_<_prefix>_*`) and the noun its messages use, creates `self._h` and
+    overrides `_param_shapes` / `_after_load`."""
+    _prefix = None
+    _noun = None
+
+    def _fn(self, name):
+        return getattr(self._lib, f"ldiff_{self._prefix}_{name}")
+
+    def _param_shapes(self):
+        """Names (and shapes) of the tensors a checkpoint may carry."""
+        return self._shapes
+
+    def _after_load(self, sd):
+        """What the class keeps or forgets once `sd` is on the device."""
+
+    def load_state_dict(self, sd, strict=True):
+        _load_state_dict(self._lib, self._fn("load"), self._h, sd, self._param_shapes())
+        n = self._fn("missing")(self._h)
+        if n and strict:
+            names = [self._fn("missing_name")(self._h, i).decode() for i in range(min(n, 5))]
+            raise RuntimeError(f"{n} {self._noun} tensors missing from the checkpoint, e.g. {names}")
+        self._after_load(sd)
+
+    def check_finite(self):
+        """Synchronises the current stream (the VAE: and its decode side stream) and raises NonFiniteError if work enqueued so far on this handle
+        produced a non-finite activation (fp16 overflow -- e.g. a decoder fed z / 0.18215 of un-scaled latents; include/ldiff.h "Non-finite detection")."""
+        _lib.check(self._fn("check_finite")(self._h, _lib.stream_ptr()))
+        return self
+
+    def eval(self):
+        return self
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._fn("destroy")(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+class _GraphHandle(_Handle):
+    """A handle whose forward goes through the hipGraph replay cache (include/ldiff.h ldiff_*_set_graph)."""
+
+    def set_graph(self, on: bool):
+        """hipGraph replay of the forward's launch sequence (default on)."""
+        _lib.check(self._fn("set_graph")(self._h, int(bool(on))))
+        return self
+
+    @property
+    def graph_replays(self) -> int:
+        return int(self._fn("graph_replays")(self._h))
+
+
+class UNet2DConditionModel(_GraphHandle):
+    _prefix, _noun = "unet", "UNet"
+
     def __init__(self, cfg: dict, state_dict, device=None):
         _lib.require_gpu()
         cfg = configs.with_defaults(cfg, configs.UNET_DEFAULTS)   # fields a config.json may omit get diffusers' defaults
@@ -97,33 +154,16 @@ class UNet2DConditionModel:
         _lib.check(self._lib.ldiff_unet_set_precision(self._h, int(mode)))
         return self
 
-    def set_graph(self, on: bool):
-        """hipGraph replay of the forward's launch sequence (default on; include/ldiff.h ldiff_unet_set_graph)."""
-        _lib.check(self._lib.ldiff_unet_set_graph(self._h, int(bool(on))))
-        return self
-
-    def check_finite(self):
-        """Synchronises the current stream and raises NonFiniteError if a forward enqueued so far produced a non-finite activation
-        (fp16 overflow; include/ldiff.h "Non-finite detection")."""
-        _lib.check(self._lib.ldiff_unet_check_finite(self._h, _lib.stream_ptr()))
-        return self
-
-    @property
-    def graph_replays(self) -> int:
-        return int(self._lib.ldiff_unet_graph_replays(self._h))
-
     @property
     def graph_nodes(self) -> int:
         """Kernel launches of the currently captured forward (0 before the first capture)."""
         return int(self._lib.ldiff_unet_graph_nodes(self._h))
 
     # ---- checkpoint surface ----
-    def load_state_dict(self, sd, strict=True):
-        _load_state_dict(self._lib, self._lib.ldiff_unet_load, self._h, sd, weights.unet_param_shapes(self._cfg))
-        n = self._lib.ldiff_unet_missing(self._h)
-        if n and strict:
-            names = [self._lib.ldiff_unet_missing_name(self._h, i).decode() for i in range(min(n, 5))]
-            raise RuntimeError(f"{n} UNet tensors missing from the checkpoint, e.g. {names}")
+    def _param_shapes(self):
+        return weights.unet_param_shapes(self._cfg)
+
+    def _after_load(self, sd):
         self._host_sd = {k: v.detach().to("cpu") for k, v in sd.items()}
         self._ctx_key = None
 
@@ -142,9 +182,6 @@ class UNet2DConditionModel:
 
     def parameters(self):
         return iter(self._host_sd.values())
-
-    def eval(self):
-        return self
 
     def to(self, *args, **kwargs):
         dt = kwargs.get("dtype", None)
@@ -230,14 +267,6 @@ class UNet2DConditionModel:
                 shapes.append((B, c, h, w))
         return shapes
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.ldiff_unet_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
 
 class ControlNetOutput:
     """`.down_block_res_samples` / `.mid_block_res_sample`, like diffusers' ControlNetOutput."""
@@ -250,9 +279,10 @@ class ControlNetOutput:
         return (self.down_block_res_samples, self.mid_block_res_sample)[i]
 
 
-class ControlNetModel:
+class ControlNetModel(_Handle):
     """diffusers' ControlNetModel for SD-v1.5-style configs on the HIP library (include/ldiff.h ldiff_controlnet_*): what
     `Segmentor.ldiffusion_augment_for_multimodal` calls at /root/reference/segmentor.py:357-363."""
+    _prefix, _noun = "controlnet", "ControlNet"
 
     def __init__(self, cfg: dict, state_dict, device=None):
         _lib.require_gpu()
@@ -279,16 +309,10 @@ class ControlNetModel:
         self._cond_key = None   # (the embedding's first layer follows the storage policy)
         return self
 
-    def check_finite(self):
-        _lib.check(self._lib.ldiff_controlnet_check_finite(self._h, _lib.stream_ptr()))
-        return self
+    def _param_shapes(self):
+        return weights.controlnet_param_shapes(self._cfg)
 
-    def load_state_dict(self, sd, strict=True):
-        _load_state_dict(self._lib, self._lib.ldiff_controlnet_load, self._h, sd, weights.controlnet_param_shapes(self._cfg))
-        n = self._lib.ldiff_controlnet_missing(self._h)
-        if n and strict:
-            names = [self._lib.ldiff_controlnet_missing_name(self._h, i).decode() for i in range(min(n, 5))]
-            raise RuntimeError(f"{n} ControlNet tensors missing from the checkpoint, e.g. {names}")
+    def _after_load(self, sd):
         self._host_sd = {k: v.detach().to("cpu") for k, v in sd.items()}
         self._ctx_key = None
         self._cond_key = None
@@ -308,9 +332,6 @@ class ControlNetModel:
 
     def parameters(self):
         return iter(self._host_sd.values())
-
-    def eval(self):
-        return self
 
     def to(self, *args, **kwargs):
         dt = kwargs.get("dtype", None)
@@ -375,14 +396,6 @@ class ControlNetModel:
 
     forward = __call__
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.ldiff_controlnet_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
 
 class _LatentDist:
     """DiagonalGaussianDistribution surface: `.mean`, `.sample()` (segmentor.py:99,339)."""
@@ -400,7 +413,9 @@ class _LatentDist:
         return self.mean
 
 
-class AutoencoderKL:
+class AutoencoderKL(_Handle):
+    _prefix, _noun = "vae", "VAE"
+
     def __init__(self, cfg: dict, state_dict, device=None, range_shift: int = 0):
         _lib.require_gpu()
         cfg = configs.with_defaults(cfg, configs.VAE_DEFAULTS)    # e.g. `scaling_factor` (decode_latents reads vae.config.scaling_factor)
@@ -421,13 +436,7 @@ class AutoencoderKL:
         c.scaling_factor = cfg["scaling_factor"]
         self._h = C.c_void_p()
         _lib.check(self._lib.ldiff_vae_create(C.byref(self._h), C.byref(c), self.device.index or 0))
-        sd = weights.normalize_vae_keys(state_dict)
-        _load_state_dict(self._lib, self._lib.ldiff_vae_load, self._h, sd, weights.vae_param_shapes(self._cfg))
-        n = self._lib.ldiff_vae_missing(self._h)
-        if n:
-            names = [self._lib.ldiff_vae_missing_name(self._h, i).decode() for i in range(min(n, 5))]
-            raise RuntimeError(f"{n} VAE tensors missing from the checkpoint, e.g. {names}")
-        self._host_sd = {k: v.detach().to("cpu") for k, v in sd.items()}
+        self.load_state_dict(state_dict)
         self.range_shift = 0
         if range_shift:
             self.set_range_shift(range_shift)
@@ -438,6 +447,15 @@ class AutoencoderKL:
             path = os.path.join(path, subfolder)
         cfg, sd = weights.load_model_dir(path)
         return cls(cfg, sd, device=device, range_shift=range_shift)
+
+    def load_state_dict(self, sd, strict=True):
+        super().load_state_dict(weights.normalize_vae_keys(sd), strict)
+
+    def _param_shapes(self):
+        return weights.vae_param_shapes(self._cfg)
+
+    def _after_load(self, sd):
+        self._host_sd = {k: v.detach().to("cpu") for k, v in sd.items()}
 
     def save_pretrained(self, path):
         weights.save_model_dir(path, self._cfg, self._host_sd)
@@ -478,15 +496,6 @@ class AutoencoderKL:
                     self.set_range_shift(prev)
                     raise
 
-    def check_finite(self):
-        """Synchronises the current stream (and the decode side stream) and raises NonFiniteError if an encode / decode enqueued so far produced
-        a non-finite activation (fp16 overflow -- e.g. a decoder fed z / 0.18215 of un-scaled latents; include/ldiff.h "Non-finite detection")."""
-        _lib.check(self._lib.ldiff_vae_check_finite(self._h, _lib.stream_ptr()))
-        return self
-
-    def eval(self):
-        return self
-
     def to(self, *args, **kwargs):
         return self
 
@@ -523,20 +532,13 @@ class AutoencoderKL:
         sample, _, _ = self._decode(z, 1.0, want_sample=True)
         return SimpleNamespace(sample=sample)
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.ldiff_vae_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
-
-class PlainConvUNet:
+class PlainConvUNet(_GraphHandle):
     """nnU-Net v2's 2-D PlainConvUNet on the HIP library (include/ldiff.h ldiff_segnet_*): the network nnUNetPredictor runs inside its sliding
     window at /root/reference/segmentor.py:463-488.  `spec` comes from `nnunet.network_spec`; `state_dict` carries the canonical names
     (`nnunet.clean_state_dict` drops a checkpoint's aliases).  `net(x [B, C, h, w] float32 on the device) -> logits [B, heads, h, w]` in
     `out_dtype` (float32 default; float16 is what the reference's autocast hands the sliding window)."""
+    _prefix, _noun = "segnet", "nnU-Net"
 
     def __init__(self, spec: dict, state_dict, device=None, out_dtype=torch.float32):
         from . import nnunet
@@ -553,31 +555,11 @@ class PlainConvUNet:
         self._shapes = nnunet.param_shapes(spec)
         self.load_state_dict(state_dict)
 
-    def load_state_dict(self, sd, strict=True):
-        _load_state_dict(self._lib, self._lib.ldiff_segnet_load, self._h, sd, self._shapes)
-        n = self._lib.ldiff_segnet_missing(self._h)
-        if n and strict:
-            names = [self._lib.ldiff_segnet_missing_name(self._h, i).decode() for i in range(min(n, 5))]
-            raise RuntimeError(f"{n} nnU-Net tensors missing from the checkpoint, e.g. {names}")
+    def _after_load(self, sd):
         self._host_sd = {k: v.detach().to("cpu") for k, v in sd.items()}
 
     def state_dict(self):
         return dict(self._host_sd)
-
-    def set_graph(self, on: bool):
-        _lib.check(self._lib.ldiff_segnet_set_graph(self._h, int(bool(on))))
-        return self
-
-    @property
-    def graph_replays(self) -> int:
-        return int(self._lib.ldiff_segnet_graph_replays(self._h))
-
-    def check_finite(self):
-        _lib.check(self._lib.ldiff_segnet_check_finite(self._h, _lib.stream_ptr()))
-        return self
-
-    def eval(self):
-        return self
 
     def to(self, *args, **kwargs):
         return self
@@ -597,21 +579,14 @@ class PlainConvUNet:
 
     forward = __call__
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.ldiff_segnet_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
-
-class ResNetClassifier:
+class ResNetClassifier(_GraphHandle):
     """The cell head's instance classifier on the HIP library (include/ldiff.h ldiff_resnet_*): torchvision's ResNet trunk (ResNet152: layers
     (3, 8, 36, 3), width 64) without avgpool / fc, `adapter` conv, mean over the map, linear head -- `encoder` / `adapter` / `classifier` of
     the reference's CellSegClassifier.  `state_dict` carries the module's own names (`cellhead.param_shapes`); every BatchNorm is folded into
     its conv at load.  `net(crops [B, S, S, 8] float16 NHWC on the device, channels 3..7 zero) -> (logits [B, C] float32, labels [B] int32)`,
     labels = 1 + argmax(logits[:, 1:])."""
+    _prefix, _noun = "resnet", "classifier"
 
     def __init__(self, num_classes: int, state_dict, device=None, layers=(3, 8, 36, 3), width=64, adapter_channels=256):
         from . import cellhead
@@ -626,28 +601,6 @@ class ResNetClassifier:
                                                  self.device.index or 0))
         self._shapes = cellhead.param_shapes(self.num_classes, self.layers, self.width, self.adapter_channels, counters=True)
         self.load_state_dict(state_dict)
-
-    def load_state_dict(self, sd, strict=True):
-        _load_state_dict(self._lib, self._lib.ldiff_resnet_load, self._h, sd, self._shapes)
-        n = self._lib.ldiff_resnet_missing(self._h)
-        if n and strict:
-            names = [self._lib.ldiff_resnet_missing_name(self._h, i).decode() for i in range(min(n, 5))]
-            raise RuntimeError(f"{n} classifier tensors missing from the checkpoint, e.g. {names}")
-
-    def set_graph(self, on: bool):
-        _lib.check(self._lib.ldiff_resnet_set_graph(self._h, int(bool(on))))
-        return self
-
-    @property
-    def graph_replays(self) -> int:
-        return int(self._lib.ldiff_resnet_graph_replays(self._h))
-
-    def check_finite(self):
-        _lib.check(self._lib.ldiff_resnet_check_finite(self._h, _lib.stream_ptr()))
-        return self
-
-    def eval(self):
-        return self
 
     def to(self, *args, **kwargs):
         return self
@@ -665,11 +618,3 @@ class ResNetClassifier:
         return logits, labels
 
     forward = __call__
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.ldiff_resnet_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass

@@ -409,6 +409,37 @@ def test_batch_invariance_and_graph_replay():
         net(torch.zeros((1, 48, 48, 8), dtype=torch.float16, device=DEV))
 
 
+def test_graph_cache_lifecycle():
+    """The replay cache through its states on one handle: eager, capture, replays; off and on again; another batch in between; a reloaded checkpoint
+    (whole: a folded group is reloaded whole).  Every output equals an eager twin's bit for bit, and the replay counter moves exactly when a graph was launched."""
+    spec = REDUCED
+    make = lambda sd: ResNetClassifier(NC, sd, DEV, spec["layers"], spec["width"], spec["adapter"])
+    sd = network_case("reduced", 5, 22)["sd"]
+    sd2 = resnet_ref.synthetic_state_dict(spec["layers"], spec["width"], NC, 23, 0.25, spec["adapter"])
+    x = resnet_ref.to_nhwc8(torch.randn((2, 3, spec["S"], spec["S"]), generator=torch.Generator().manual_seed(24))).to(DEV)
+    same = lambda got, ref: torch.equal(got[0], ref[0]) and torch.equal(got[1], ref[1])
+    ref = make(sd).set_graph(False)(x)
+    net = make(sd)
+    outs = [net(x) for _ in range(4)]        # eager, capture + replay, replay, replay
+    assert net.graph_replays == 3
+    assert all(same(o, ref) for o in outs)
+    net.set_graph(False)
+    assert same(net(x), ref) and net.graph_replays == 3
+    net.set_graph(True)
+    outs = [net(x) for _ in range(3)]        # the graph went with set_graph(False): eager, capture + replay, replay
+    assert net.graph_replays == 5
+    assert all(same(o, ref) for o in outs)
+    assert same(net(x[:1]), (ref[0][:1], ref[1][:1]))   # another batch in between drops the cached graph
+    for _ in range(2):
+        assert same(net(x), ref)
+    net.load_state_dict(sd2)
+    ref2 = make(sd2).set_graph(False)(x)
+    assert not torch.equal(ref2[0], ref[0])
+    for _ in range(3):
+        assert same(net(x), ref2), "a replay of the graph captured with the first checkpoint"
+    net.check_finite()
+
+
 def test_batch_invariance_at_full_size():
     c = network_case("full", 12, 13)
     x = resnet_ref.to_nhwc8(c["x"]).to(DEV)

@@ -509,6 +509,21 @@ def test_unet_graph_replay_equals_eager(tiny):
     assert torch.equal(o, ref[(1, 1, "a")])
 
 
+def test_unet_captures_on_its_second_use(tiny):
+    """include/ldiff.h: a configuration is captured "on its second use".  On a fresh handle the first forward grows the workspace from nothing; the second
+    must still capture and replay (one replay, a positive node count), and both outputs equal the eager launches bit for bit."""
+    g = torch.Generator().manual_seed(51)
+    x = torch.randn((1, 4, 8, 40), generator=g).to(DEV)      # a latent shape no other test of this module uses
+    ctx = (torch.randn((1, 6, 64), generator=g) * 0.5).to(DEV)
+    ref = tiny["unet"].set_graph(False)(x, 301, ctx).sample.clone()
+    tiny["unet"].set_graph(True)
+    for unet in (UNet2DConditionModel(tiny["ucfg"], tiny["usd"], DEV), tiny["unet"]):   # a handle without a workspace yet, and one whose workspace is large enough
+        r0 = unet.graph_replays
+        outs = [unet(x, 301, ctx).sample for _ in range(2)]
+        assert unet.graph_replays - r0 == 1 and unet.graph_nodes > 0
+        assert torch.equal(outs[0], ref) and torch.equal(outs[1], ref)
+
+
 def test_unet_controlnet_additional_residuals(tiny):
     """V7's ControlNet inputs (segmentor.py:357-375): down_block_additional_residuals are added to the skip tensors (not to the mid
     block's input), mid_block_additional_residual to the mid block's output; against the oracle's restatement of that forward."""

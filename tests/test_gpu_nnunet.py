@@ -508,6 +508,35 @@ def test_graph_replay_and_batch_invariance():
         net(x[:, :, :60])
 
 
+def test_graph_cache_lifecycle():
+    """The replay cache through its states on one handle: eager, capture, replays; off and on again; another shape in between; a reloaded checkpoint.
+    Every output equals an eager twin's bit for bit, and the replay counter moves exactly when a graph was launched."""
+    plans, ds = fixtures()
+    spec = nnunet.network_spec(plans, "2d_reduced", ds)
+    sd, sd2 = nnunet_ref.synthetic_state_dict(spec, 41), nnunet_ref.synthetic_state_dict(spec, 42)
+    x = torch.randn((2, 3, 64, 96), generator=torch.Generator().manual_seed(43)).to(DEV)
+    ref = PlainConvUNet(spec, sd, DEV).set_graph(False)(x)
+    net = PlainConvUNet(spec, sd, DEV)
+    outs = [net(x) for _ in range(4)]      # eager, capture + replay, replay, replay
+    assert net.graph_replays == 3
+    assert all(torch.equal(o, ref) for o in outs)
+    net.set_graph(False)
+    assert torch.equal(net(x), ref) and net.graph_replays == 3
+    net.set_graph(True)
+    outs = [net(x) for _ in range(3)]      # the graph went with set_graph(False): eager, capture + replay, replay
+    assert net.graph_replays == 5
+    assert all(torch.equal(o, ref) for o in outs)
+    assert torch.equal(net(x[:1]), ref[:1])   # another shape in between drops the cached graph
+    for _ in range(2):
+        assert torch.equal(net(x), ref)
+    net.load_state_dict(sd2)
+    ref2 = PlainConvUNet(spec, sd2, DEV).set_graph(False)(x)
+    assert not torch.equal(ref2, ref)
+    for _ in range(3):
+        assert torch.equal(net(x), ref2), "a replay of the graph captured with the first checkpoint"
+    net.check_finite()
+
+
 def test_batch_invariance_at_the_default_width():
     """B = 4 equals four B = 1 passes bit for bit at the planner's default width too: the K split of every launch is planned from one image
     (ConvOpts::splitk_per_image), so the sliding window may batch its mirrored evaluations."""
