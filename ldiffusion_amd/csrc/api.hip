@@ -733,21 +733,35 @@ int ldiff_op_conv(const ldiff_conv_args* a, void* stream) {
   // reuse is stream-ordered, and two streams or devices never share one.
   hipStream_t st = (hipStream_t)stream;
   if (pl.parity) {
-    f16* wpar = (f16*)op_scratch(st, 0, (size_t)4 * p.Nrows * 4 * (p.C1 + p.C2) * sizeof(f16));
-    launch_make_parity_weights(p.w, wpar, p.Nrows, p.C1 + p.C2, st);
+    f16* wpar = (f16*)op_scratch(st, 0, parity_weights_bytes(p));
+    pack_parity_weights(p, wpar, st);
     p.w_par = wpar;
   }
-  if (pl.weights == ConvWeights::FRAG || pl.weights == ConvWeights::FRAG_PAR || pl.weights == ConvWeights::FRAG_SC) {   // the executors cache these per layer; here per call
-    f16* wf = (f16*)op_scratch(st, 3, conv3x3d_frag_bytes(p));
-    if (pl.weights == ConvWeights::FRAG_PAR) launch_pack_frag_weights_par(p.w_par, wf, p.N, p.Nrows, p.C1, st);
-    else launch_pack_frag_weights(p.w, wf, p.N, p.C1, st);
-    if (pl.weights == ConvWeights::FRAG_SC) {   // the folded shortcut's weights behind the nine taps, the two biases summed
-      launch_pack_frag_weights_sc((const f16*)a->sc_w, wf, p.N, p.C1, p.Cs, p.Cs, st);
+  if (pl.weights != ConvWeights::PLAIN) {   // the executors cache these per layer (Exec::derived); here per call, by the same recipes (conv_route.hip)
+    // LDIFF_OP_CACHE_FRAG=1 (timing scripts only): the dataflow GEMM's copy is packed once per (matrix address, shape) -- stale as soon as the caller
+    // rewrites the matrix in place, which the tests do
+    static const bool cache = [] { const char* e = getenv("LDIFF_OP_CACHE_FRAG"); return e && atoi(e) != 0; }();
+    static std::mutex mu;
+    static std::map<std::tuple<const void*, int, int>, f16*> packed;
+    const size_t bytes = packed_weights_bytes(pl.weights, p);
+    f16* wf = nullptr;
+    bool pack = true;
+    if (cache && pl.weights == ConvWeights::GEMM_FRAG) {
+      std::lock_guard<std::mutex> lock(mu);
+      f16*& kept = packed[std::make_tuple((const void*)p.w, p.Nrows, p.K)];
+      pack = !kept;
+      if (!kept) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&kept), bytes));
+      wf = kept;
+    } else {
+      wf = (f16*)op_scratch(st, 3, bytes);
+    }
+    if (pack) pack_weights(pl.weights, p, (const f16*)a->sc_w, wf, st);
+    p.w_frag = wf;
+    if (pl.weights == ConvWeights::FRAG_SC) {   // the two biases summed
       float* bsum = (float*)op_scratch(st, 5, (size_t)p.Nrows * sizeof(float));
-      launch_add_vectors(p.bias, (const float*)a->sc_bias, bsum, p.Nrows, st);
+      pack_shortcut_bias(p, (const float*)a->sc_bias, bsum, st);
       p.bias = bsum;
     }
-    p.w_frag = wf;
   }
   if (pl.fold_gn) {   // the executor's two launches (model.hip): per-image weights and biases, then the plain GEMM on them
     f16* wfold = (f16*)op_scratch(st, 6, (size_t)p.B * p.Nrows * p.K * sizeof(f16));
@@ -756,22 +770,6 @@ int ldiff_op_conv(const ldiff_conv_args* a, void* stream) {
     p.w = wfold; p.bias = bfold;
   }
   if (p.splitk > 1) p.splitk_ws = (float*)op_scratch(st, 1, (size_t)p.splitk * p.M * p.N * sizeof(float));
-  if (pl.weights == ConvWeights::GEMM_FRAG) {   // LDIFF_OP_CACHE_FRAG=1 (timing scripts only): pack once per (matrix address, shape) -- stale as soon
-    // as the caller rewrites the matrix in place, which the tests do
-    static const bool cache = [] { const char* e = getenv("LDIFF_OP_CACHE_FRAG"); return e && atoi(e) != 0; }();
-    static std::mutex mu;
-    static std::map<std::tuple<const void*, int, int>, f16*> packed;
-    if (cache) {
-      std::lock_guard<std::mutex> lock(mu);
-      f16*& wf = packed[std::make_tuple((const void*)p.w, p.Nrows, p.K)];
-      if (!wf) { HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&wf), gemm_df_frag_bytes(p))); launch_pack_gemm_frag(p.w, wf, p.Nrows, p.K, st); }
-      p.w_frag = wf;
-    } else {
-      f16* wf = (f16*)op_scratch(st, 4, gemm_df_frag_bytes(p));
-      launch_pack_gemm_frag(p.w, wf, p.Nrows, p.K, st);
-      p.w_frag = wf;
-    }
-  }
   launch_igemm(p, pl, st);
   API_END
 }

@@ -140,6 +140,14 @@ struct ConvPlan {
   int bm = 0, bn = 0;     // tile of C3_HALO (bm / 8 = pixel tile width), GEMM_DMA and IGEMM: bm output rows x bn output channels
 };
 ConvPlan plan_conv(ConvParams& p, const ConvAsk& ask);
+// The recipe of each derived weight layout a plan can name (conv_route.hip): its byte count and the pack launches into a destination the caller provides.
+// No caching here: the executors keep the result per layer (Exec::derived), ldiff_op_conv packs into its scratch on every call.  Each packs from what the
+// launch itself reads: p.w (parity weights, FRAG, FRAG_SC, GEMM_FRAG), p.w_par (FRAG_PAR), p.bias (the summed bias of FRAG_SC).
+size_t parity_weights_bytes(const ConvParams& p);
+void pack_parity_weights(const ConvParams& p, f16* dst, hipStream_t s);                              // ConvPlan::parity -> ConvParams::w_par
+size_t packed_weights_bytes(ConvWeights layout, const ConvParams& p);
+void pack_weights(ConvWeights layout, const ConvParams& p, const f16* sc_w, f16* dst, hipStream_t s);   // ConvPlan::weights -> ConvParams::w_frag; sc_w: FRAG_SC's shortcut matrix [N][Cs]
+void pack_shortcut_bias(const ConvParams& p, const float* sc_bias, float* dst, hipStream_t s);      // FRAG_SC: p.bias + sc_bias, [Nrows] floats -> ConvParams::bias
 bool conv_lo8_enabled();   // LDIFF_LO8 (conv_route.hip)
 void launch_igemm(const ConvParams& p, const ConvPlan& pl, hipStream_t s);   // runs the planned kernel (the register-staged igemm itself: kernels_igemm.hip)
 // 3x3 conv + bias (+ SiLU epilogue) at the channel counts of the ControlNet's conditioning embedding (3 / 16 / 32 / 96 in, 16 / 32 / 96 / 256 out): kernels_cond.hip

@@ -2,6 +2,7 @@
 // Each kernel file states its own limits (conv3x3_eligible, conv3x3{n,nt,d,p}_selected, gemm_dma_eligible, gemm_df_selected); this file
 // cond_conv_selected comes first: its launches are ones no other family is made for.  This file
 // is the one place that asks them, in one fixed order, and the only one that reads the routing switches LDIFF_GEMM_DF and LDIFF_LO8.
+// Behind plan_conv: the recipe (byte count, pack launches) of each derived weight layout a plan names, for the executors and ldiff_op_conv alike.
 #include "common.h"
 
 namespace {
@@ -236,3 +237,23 @@ ConvPlan plan_conv(ConvParams& p, const ConvAsk& ask) {
   }
   return pl;
 }
+
+// ---- the derived weight layouts a plan names: one recipe each (common.h) ----
+size_t parity_weights_bytes(const ConvParams& p) { return (size_t)4 * p.Nrows * 4 * (p.C1 + p.C2) * sizeof(f16); }
+void pack_parity_weights(const ConvParams& p, f16* dst, hipStream_t s) { launch_make_parity_weights(p.w, dst, p.Nrows, p.C1 + p.C2, s); }
+size_t packed_weights_bytes(ConvWeights layout, const ConvParams& p) {
+  return layout == ConvWeights::PLAIN ? 0 : layout == ConvWeights::GEMM_FRAG ? gemm_df_frag_bytes(p) : conv3x3d_frag_bytes(p);
+}
+void pack_weights(ConvWeights layout, const ConvParams& p, const f16* sc_w, f16* dst, hipStream_t s) {
+  switch (layout) {
+    case ConvWeights::PLAIN: break;
+    case ConvWeights::FRAG_PAR: launch_pack_frag_weights_par(p.w_par, dst, p.N, p.Nrows, p.C1, s); break;
+    case ConvWeights::FRAG:
+    case ConvWeights::FRAG_SC:   // the nine taps as in FRAG, the folded shortcut's weights behind them
+      launch_pack_frag_weights(p.w, dst, p.N, p.C1, s);
+      if (layout == ConvWeights::FRAG_SC) launch_pack_frag_weights_sc(sc_w, dst, p.N, p.C1, p.Cs, p.Cs, s);
+      break;
+    case ConvWeights::GEMM_FRAG: launch_pack_gemm_frag(p.w, dst, p.Nrows, p.K, s); break;
+  }
+}
+void pack_shortcut_bias(const ConvParams& p, const float* sc_bias, float* dst, hipStream_t s) { launch_add_vectors(p.bias, sc_bias, dst, p.Nrows, s); }

@@ -35,7 +35,8 @@ struct Act {
   SrcView view() const { return SrcView{p, C, ld(), lo()}; }
 };
 
-struct Derived { f16* p = nullptr; int gen = -1; int key = 0; };   // lazily built weights derived from a checkpoint matrix
+// One lazily built buffer derived from a checkpoint matrix: the pointer, the checkpoint generation and the key it was last built with (Exec::derived).
+struct Derived { void* p = nullptr; int gen = -1; int key = 0; };
 
 struct MatW {   // [Nrows][K] fp16 K-major + fp32 bias
   f16* w = nullptr;
@@ -43,20 +44,21 @@ struct MatW {   // [Nrows][K] fp16 K-major + fp32 bias
   int N = 0, Nrows = 0, K = 0, ks = 1, Cin = 0;  // Cin = padded input channels (K = ks*ks*Cin)
   bool geglu = false;   // rows stored x/gate-interleaved by 16 so that the GEMM epilogue can apply x * gelu(gate) (ConvParams::geglu)
   int Cin_logical = 0;            // unpadded input channels of a first-layer conv (Cin padded to 8): the split form keeps hi | lo inside the pad
-  // derived weights, built on first use by the Exec that needs them and rebuilt when the checkpoint is reloaded:
-  mutable Derived par;            //   upsampler convs: parity weights [4][Nrows][4*Cin]
-  mutable Derived dup;            //   split operand: [Nrows][taps][2*Cin] (same weights against the hi and the lo half); key = C1 of a concat
-  mutable Derived dup_par;        //   parity weights of the duplicated matrix
-  mutable Derived frag;           //   MFMA-fragment-packed copy for the dataflow conv3x3 kernel (kernels_conv3x3d.hip)
-  mutable Derived frag_par;       //   ... of the parity weights (upsampling convs on the dataflow kernel)
-  mutable Derived frag_sc;        //   ... with a folded shortcut's weights behind the nine taps (key = the shortcut matrix's address bits) and the summed bias
-  mutable float* bias_sc = nullptr;
-  mutable Derived gfrag;          //   MFMA-fragment-packed copy for the dataflow GEMM (kernels_gemm_df.hip)
-  mutable Derived gfrag_dup;      //   the same of the duplicated (split-operand) matrix; key = C1 of a concat
-  mutable Derived tiled;          //   panel-tiled copy for the LayerNorm-fused GEMM (kernels_gemm_ast.hip)
-  mutable Derived lo8;            //   split operand with an fp8 lo half: [Nrows][taps][Cin fp16 | Cin e4m3] + one int (the E8M0 scale operand) behind it
-  mutable float* b_shift = nullptr;           //   the bias times 2^-k for a launch whose input is the range-shifted stream (Exec::derived_bias_shift)
-  mutable int b_shift_gen = -1, b_shift_k = -1;
+  // Derived weights: every one a slot of Exec::derived, built on first use by the Exec that needs it, rebuilt when the checkpoint is reloaded or its key
+  // changes.  A copy built from another derived copy takes its source's key, so it is rebuilt whenever the source is.  Per slot: what it holds <- what it is
+  // built from; key.  (The recipes of par, dup_par, frag, frag_par, frag_sc, bias_sc, gfrag and gfrag_dup are conv_route.hip's, shared with ldiff_op_conv.)
+  mutable Derived dup;        // split operand [Nrows][taps][2*Cin], the same weights against the hi and the lo half <- w; key = C1 of a concat
+  mutable Derived lo8;        // split operand with an fp8 lo half [Nrows][taps][Cin fp16 | Cin e4m3] + one int behind it (the E8M0 scale operand) <- w; no key
+  mutable Derived tiled;      // panel-tiled copy for the LayerNorm-fused GEMM (kernels_gemm_ast.hip) <- w; no key
+  mutable Derived b_shift;    // the bias times 2^-k for a launch whose input is the range-shifted stream <- b; key = k
+  mutable Derived par;        // upsampler convs: parity weights [4][Nrows][4*Cin] <- w; no key
+  mutable Derived dup_par;    // ... of the duplicated matrix <- dup; key = dup's
+  mutable Derived frag;       // MFMA-fragment-packed copy for the dataflow conv3x3 kernel (kernels_conv3x3d.hip) <- the matrix the launch reads (w / dup); key = dup's or 0
+  mutable Derived frag_par;   // ... of the parity weights (upsampling convs on the dataflow kernel) <- par / dup_par; key = theirs
+  mutable Derived frag_sc;    // ... with a folded shortcut's weights behind the nine taps <- w and the shortcut's matrix; key = that matrix's address bits and width
+  mutable Derived bias_sc;    // the bias plus that shortcut's <- b and the shortcut's bias; key = frag_sc's
+  mutable Derived gfrag;      // MFMA-fragment-packed copy for the dataflow GEMM (kernels_gemm_df.hip) <- w; no key
+  mutable Derived gfrag_dup;  // ... of the duplicated matrix <- dup; key = dup's
 };
 struct NormW { float* g = nullptr; float* b = nullptr; int C = 0; };
 struct GNss { float* scale = nullptr; float* shift = nullptr; };
@@ -148,7 +150,7 @@ class Exec {
   hipStream_t s = nullptr;
   float* gn_partial = nullptr;
   size_t gn_partial_cap = 0;
-  std::vector<void*> owned;   // lazily built derived weights (parity weights of the upsampler convs)
+  std::vector<void*> owned;   // the buffers of the derived-weight slots this Exec has built (Exec::derived), freed with it
   const int* weights_gen = nullptr;   // -> WeightStore::generation of the owning model
   bool short_runs = false;            // this graph runs beside another stream's (ConvParams::short_runs)
   int* nonfinite = nullptr;           // -> the owning handle's sticky non-finite flag (host-mapped; set by the GroupNorm finalize kernels, NonFiniteFlag below)
@@ -158,13 +160,11 @@ class Exec {
   ~Exec();
   void ensure_gn_partial(size_t bytes);
   Act new_act(int B, int H, int W, int C, bool split = false, bool lo8 = false);
+  // The rule of every derived-weight slot (MatW): `bytes` of device memory on first use (owned by this Exec; zeroed where `zero`),
+  // build(d.p) when the checkpoint generation or `key` differs from what the slot was last built with.  Returns d.p.
+  template <typename Build> void* derived(Derived& d, size_t bytes, int key, Build&& build, bool zero = false);
   const f16* derived_dup(const MatW& w, int C1_logical, int C2_logical);
-  const f16* derived_par(const MatW& w, const f16* src, int Cin, Derived& d);
-  const f16* derived_frag(const MatW& w, const ConvParams& p);
-  const f16* derived_frag_par(const MatW& w, const ConvParams& p);   // ... of the parity-folded weights p.w_par (ups = 1)
-  const f16* derived_frag_sc(const MatW& w, const MatW& sc, const ConvParams& p, const float** bias_sum);   // ... + the folded shortcut
   const f16* derived_tiled(const MatW& w, int N);
-  const f16* derived_gfrag(const MatW& w, const f16* src, int K, Derived& d, int key);   // fragment-packed copy of `src` [Nrows][K] for the dataflow GEMM
   const float* derived_bias_shift(const MatW& w, int k);   // w.b times 2^-k (nullptr without a bias), rebuilt when k or the checkpoint changes
   const f16* derived_lo8(const MatW& w, const int** scale);   // fp8-lo weights of a split operand + the device int holding their E8M0 scale operand
   bool lo8_conv_ok(const MatW& w, const Act& x, bool res, bool split_out) const;   // would conv(w, norm_apply(x) with an fp8 lo half) run on the ping-pong kernel?

@@ -324,57 +324,45 @@ void Exec::release(GNss& g) {
   arena.free(g.shift);
   g.scale = g.shift = nullptr;
 }
+// The one rule of derived weights (model.h MatW): allocate on first use, rebuild when the checkpoint was reloaded or the key changed.
+template <typename Build>
+void* Exec::derived(Derived& d, size_t bytes, int key, Build&& build, bool zero) {
+  const int gen = weights_gen ? *weights_gen : 0;
+  if (!d.p) {
+    HIP_CHECK(hipMalloc(&d.p, bytes));
+    owned.push_back(d.p);
+    if (zero) HIP_CHECK(hipMemset(d.p, 0, bytes));
+  }
+  if (d.gen != gen || d.key != key) {
+    build(d.p);
+    d.gen = gen; d.key = key;
+  }
+  return d.p;
+}
 // duplicated weights of a split-operand contraction: per tap [a(C1) a(C1) b(C2) b(C2)] from [a(C1) b(C2)]; first-layer convs whose
 // input channels are padded to 8 keep hi | lo inside the pad ([a(c) a(c) 0..] with c = Cin_logical)
 const f16* Exec::derived_dup(const MatW& w, int C1, int C2) {
-  const int gen = weights_gen ? *weights_gen : 0;
   const bool small = w.Cin_logical > 0;
   const int dst_stride = small ? w.Cin : 2 * w.Cin;
-  if (!w.dup.p) {
-    void* q = nullptr;
-    HIP_CHECK(hipMalloc(&q, (size_t)w.Nrows * w.ks * w.ks * dst_stride * sizeof(f16)));
-    owned.push_back(q);
-    w.dup.p = (f16*)q;
-  }
-  if (w.dup.gen != gen || w.dup.key != C1) {
-    launch_dup_weights(w.w, w.dup.p, w.Nrows, w.ks * w.ks, w.Cin, small ? w.Cin_logical : C1, small ? 0 : C2, dst_stride, s);
-    w.dup.gen = gen; w.dup.key = C1;
-  }
-  return w.dup.p;
+  return (const f16*)derived(w.dup, (size_t)w.Nrows * w.ks * w.ks * dst_stride * sizeof(f16), C1, [&](void* d) {
+    launch_dup_weights(w.w, (f16*)d, w.Nrows, w.ks * w.ks, w.Cin, small ? w.Cin_logical : C1, small ? 0 : C2, dst_stride, s);
+  });
 }
 // the bias of a launch whose input is the range-shifted stream: b * 2^-k (exact), so that the epilogue's sum + bias is (true sum + b) * 2^-k
 const float* Exec::derived_bias_shift(const MatW& w, int k) {
   if (!w.b || k == 0) return w.b;
-  const int gen = weights_gen ? *weights_gen : 0;
-  if (!w.b_shift) {
-    void* q = nullptr;
-    HIP_CHECK(hipMalloc(&q, (size_t)w.Nrows * sizeof(float)));
-    owned.push_back(q);
-    w.b_shift = (float*)q;
-  }
-  if (w.b_shift_gen != gen || w.b_shift_k != k) {   // first use, another k, or the checkpoint was reloaded since
-    launch_scale_f32(w.b, w.b_shift, ldexpf(1.0f, -k), w.Nrows, s);
-    w.b_shift_gen = gen; w.b_shift_k = k;
-  }
-  return w.b_shift;
+  return (const float*)derived(w.b_shift, (size_t)w.Nrows * sizeof(float), k, [&](void* d) { launch_scale_f32(w.b, (float*)d, ldexpf(1.0f, -k), w.Nrows, s); });
 }
 // split operand with an fp8 lo half (ConvParams::lo8_slab0): per (row, tap) [Cin fp16 | Cin e4m3 of w * 2^sw]; the int behind the matrix is 127 - sw
 const f16* Exec::derived_lo8(const MatW& w, const int** scale) {
-  const int gen = weights_gen ? *weights_gen : 0;
   const size_t bytes = (size_t)w.Nrows * w.ks * w.ks * w.Cin * 3;
-  if (!w.lo8.p) {
-    void* q = nullptr;
-    HIP_CHECK(hipMalloc(&q, bytes + 16));
-    owned.push_back(q);
-    w.lo8.p = (f16*)q;
-  }
-  int* sc = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(w.lo8.p) + bytes);
-  if (w.lo8.gen != gen) {
-    launch_lo8_weights(w.w, w.lo8.p, sc, w.Nrows, w.ks * w.ks, w.Cin, s);
-    w.lo8.gen = gen;
-  }
-  *scale = sc;
-  return w.lo8.p;
+  auto scale_of = [bytes](void* d) { return reinterpret_cast<int*>(static_cast<unsigned char*>(d) + bytes); };
+  void* q = derived(w.lo8, bytes + 16, 0, [&](void* d) { launch_lo8_weights(w.w, d, scale_of(d), w.Nrows, w.ks * w.ks, w.Cin, s); });
+  *scale = scale_of(q);
+  return (const f16*)q;
+}
+const f16* Exec::derived_tiled(const MatW& w, int N) {
+  return (const f16*)derived(w.tiled, (size_t)N * w.K * sizeof(f16), 0, [&](void* d) { launch_lngemm_tile_weights(w.w, (f16*)d, N, w.K, s); });
 }
 bool Exec::lo8_conv_ok(const MatW& w, const Act& x, bool res, bool split_out) const {
   if (!conv_lo8_enabled() || w.ks != 3 || x.C != w.Cin || x.C % 128 != 0 || w.Cin_logical > 0 || !split_out) return false;
@@ -390,102 +378,6 @@ bool Exec::lo8_conv_ok(const MatW& w, const Act& x, bool res, bool split_out) co
   ConvAsk ask;   // as Exec::conv plans the resnet convs
   ask.stats = true;
   return plan_conv(p, ask).kernel == ConvKernel::C3_PINGPONG;
-}
-const f16* Exec::derived_frag(const MatW& w, const ConvParams& p) {
-  const int gen = weights_gen ? *weights_gen : 0;
-  if (!w.frag.p) {
-    void* q = nullptr;
-    HIP_CHECK(hipMalloc(&q, conv3x3d_frag_bytes(p)));
-    owned.push_back(q);
-    w.frag.p = (f16*)q;
-  }
-  if (w.frag.gen != gen) {   // first use, or the checkpoint was reloaded since
-    launch_pack_frag_weights(w.w, w.frag.p, p.N, p.C1, s);
-    w.frag.gen = gen;
-  }
-  return w.frag.p;
-}
-const f16* Exec::derived_frag_par(const MatW& w, const ConvParams& p) {
-  const int gen = weights_gen ? *weights_gen : 0;
-  if (!w.frag_par.p) {
-    void* q = nullptr;
-    HIP_CHECK(hipMalloc(&q, conv3x3d_frag_bytes(p)));
-    HIP_CHECK(hipMemset(q, 0, conv3x3d_frag_bytes(p)));   // (the padding step behind the last block is loaded, never used)
-    owned.push_back(q);
-    w.frag_par.p = (f16*)q;
-  }
-  if (w.frag_par.gen != gen) {   // first use, or the checkpoint was reloaded since (p.w_par has been rebuilt by derived_par just before)
-    launch_pack_frag_weights_par(p.w_par, w.frag_par.p, p.N, p.Nrows, p.C1, s);
-    w.frag_par.gen = gen;
-  }
-  return w.frag_par.p;
-}
-const f16* Exec::derived_frag_sc(const MatW& w, const MatW& sc, const ConvParams& p, const float** bias_sum) {
-  const int gen = weights_gen ? *weights_gen : 0;
-  if (!w.frag_sc.p) {
-    void* q = nullptr;
-    HIP_CHECK(hipMalloc(&q, conv3x3d_frag_bytes(p)));
-    HIP_CHECK(hipMemset(q, 0, conv3x3d_frag_bytes(p)));   // (the padding step behind the shortcut's blocks is loaded, never used)
-    owned.push_back(q);
-    w.frag_sc.p = (f16*)q;
-    HIP_CHECK(hipMalloc(&q, (size_t)w.Nrows * sizeof(float)));
-    owned.push_back(q);
-    w.bias_sc = (float*)q;
-  }
-  // key: the shortcut matrix this copy was packed with and its width (a conv2 reused with another shortcut would otherwise read stale / too few weights)
-  const int key = (int)((reinterpret_cast<uintptr_t>(sc.w) >> 4) & 0x3fffffff) ^ (p.Cs << 20);
-  LDIFF_CHECK(w.frag_sc.gen < 0 || w.frag_sc.key == key, LDIFF_ERR_RUNTIME, "conv: the folded-shortcut weights of this layer were packed for another shortcut matrix");
-  if (w.frag_sc.gen != gen) {   // first use, or the checkpoint was reloaded since
-    w.frag_sc.key = key;
-    launch_pack_frag_weights(w.w, w.frag_sc.p, p.N, p.C1, s);
-    launch_pack_frag_weights_sc(sc.w, w.frag_sc.p, p.N, p.C1, p.Cs, sc.K, s);
-    launch_add_vectors(w.b, sc.b, w.bias_sc, w.Nrows, s);
-    w.frag_sc.gen = gen;
-  }
-  *bias_sum = w.bias_sc;
-  return w.frag_sc.p;
-}
-const f16* Exec::derived_tiled(const MatW& w, int N) {
-  const int gen = weights_gen ? *weights_gen : 0;
-  if (!w.tiled.p) {
-    void* q = nullptr;
-    HIP_CHECK(hipMalloc(&q, (size_t)N * w.K * sizeof(f16)));
-    owned.push_back(q);
-    w.tiled.p = (f16*)q;
-  }
-  if (w.tiled.gen != gen) {   // first use, or the checkpoint was reloaded since
-    launch_lngemm_tile_weights(w.w, w.tiled.p, N, w.K, s);
-    w.tiled.gen = gen;
-  }
-  return w.tiled.p;
-}
-const f16* Exec::derived_gfrag(const MatW& w, const f16* src, int K, Derived& d, int key) {
-  const int gen = weights_gen ? *weights_gen : 0;
-  if (!d.p) {
-    void* q = nullptr;
-    HIP_CHECK(hipMalloc(&q, (size_t)w.Nrows * K * sizeof(f16)));
-    owned.push_back(q);
-    d.p = (f16*)q;
-  }
-  if (d.gen != gen || d.key != key) {   // first use, the checkpoint was reloaded since, or the duplicated source was rebuilt for another concat split
-    launch_pack_gemm_frag(src, d.p, w.Nrows, K, s);
-    d.gen = gen; d.key = key;
-  }
-  return d.p;
-}
-const f16* Exec::derived_par(const MatW& w, const f16* src, int Cin, Derived& d) {
-  const int gen = weights_gen ? *weights_gen : 0;
-  if (!d.p) {
-    void* q = nullptr;
-    HIP_CHECK(hipMalloc(&q, (size_t)4 * w.Nrows * 4 * Cin * sizeof(f16)));
-    owned.push_back(q);
-    d.p = (f16*)q;
-  }
-  if (d.gen != gen) {   // first use, or the checkpoint was reloaded since
-    launch_make_parity_weights(src, d.p, w.Nrows, Cin, s);
-    d.gen = gen;
-  }
-  return d.p;
 }
 Act Exec::conv(const MatW& w, const Act& x, const Act* x2, const ConvOpts& o) {
   ConvParams p;
@@ -587,19 +479,28 @@ Act Exec::conv(const MatW& w, const Act& x, const Act* x2, const ConvOpts& o) {
     if (C > p.N) launch_zero_bytes(y.p, y.bytes(), s);  // zero the pad columns (a kernel: the forward may be inside a captured graph)
     p.y = y.p;
   }
-  if (pl.parity) p.w_par = derived_par(w, wsrc, Cin_eff, o.split_in ? w.dup_par : w.par);
+  // the derived weights the plan names: the recipes are conv_route.hip's, from what the launch reads (p.w = wsrc); a copy of a derived copy takes its key
+  const int wkey = o.split_in && !x.lo8 ? x.C : 0;   // the key wsrc was built with (derived_dup)
+  if (pl.parity) p.w_par = (const f16*)derived(o.split_in ? w.dup_par : w.par, parity_weights_bytes(p), wkey, [&](void* d) { pack_parity_weights(p, (f16*)d, s); });
   if (p.stats_R) {
     y.st = tmp<float>((size_t)x.B * p.stats_R * p.N * 2);
     y.st_R = p.stats_R;
     p.stats = y.st;
   }
   if (p.splitk) p.splitk_ws = tmp<float>((size_t)p.splitk * p.M * p.N);
-  switch (pl.weights) {   // MFMA-fragment-packed weights of the dataflow kernels
-    case ConvWeights::FRAG: p.w_frag = derived_frag(w, p); break;
-    case ConvWeights::FRAG_PAR: p.w_frag = derived_frag_par(w, p); break;
-    case ConvWeights::FRAG_SC: p.w_frag = derived_frag_sc(w, *o.sc_w, p, &p.bias); *o.sc_done = true; break;
-    case ConvWeights::GEMM_FRAG: p.w_frag = derived_gfrag(w, wsrc, p.K, o.split_in ? w.gfrag_dup : w.gfrag, o.split_in ? x.C : 0); break;
-    case ConvWeights::PLAIN: break;
+  if (pl.weights != ConvWeights::PLAIN) {   // MFMA-fragment-packed weights of the dataflow kernels
+    const bool sc = pl.weights == ConvWeights::FRAG_SC;
+    Derived& d = sc ? w.frag_sc : pl.weights == ConvWeights::FRAG_PAR ? w.frag_par : pl.weights == ConvWeights::FRAG ? w.frag : o.split_in ? w.gfrag_dup : w.gfrag;
+    // a folded shortcut's key: the shortcut matrix this copy was packed with and its width (a conv2 reused with another shortcut would otherwise read stale / too few weights)
+    const int key = sc ? (int)((reinterpret_cast<uintptr_t>(o.sc_w->w) >> 4) & 0x3fffffff) ^ (p.Cs << 20) : wkey;
+    LDIFF_CHECK(!sc || d.gen < 0 || d.key == key, LDIFF_ERR_RUNTIME, "conv: the folded-shortcut weights of this layer were packed for another shortcut matrix");
+    // (zeroed: the padding step behind the last block of FRAG_PAR / FRAG_SC is loaded, never used)
+    p.w_frag = (const f16*)derived(d, packed_weights_bytes(pl.weights, p), key, [&](void* q) { pack_weights(pl.weights, p, sc ? o.sc_w->w : nullptr, (f16*)q, s); },
+                                   pl.weights == ConvWeights::FRAG_PAR || sc);
+    if (sc) {
+      p.bias = (const float*)derived(w.bias_sc, (size_t)p.Nrows * sizeof(float), key, [&](void* q) { pack_shortcut_bias(p, o.sc_w->b, (float*)q, s); });
+      *o.sc_done = true;
+    }
   }
   launch_igemm(p, pl, s);
   if (silu_after) launch_silu_f16(y.p, y.p, (long long)y.rows() * y.C, s);

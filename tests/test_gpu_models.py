@@ -1498,3 +1498,77 @@ def test_bench_full_only_adds_work_after_the_timed_steps(tmp_path):
     assert set(manifest) == {"masks", "latents", "features", "rgb"}
     for name in manifest:
         assert np.array_equal(np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy")), name
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# Derived weight layouts are rebuilt on reload (csrc/model.hip Exec::derived).  Device output against device output, bit for
+# bit: a handle that loaded checkpoint A, ran, and then loaded B must compute what a fresh handle built with B computes.  Two handles with the
+# same weights and inputs give identical bits (the suite relies on that elsewhere: graph replay equals eager, the same sub-batch sampled twice).
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+def test_vae_reload_rebuilds_derived_weights():
+    """SD-v1.5 VAE topology cut to two levels [128, 256], one layer per block, B = 1, default precisions (encoder 2, decoder 0).  The decoder's
+    256 x 256 level at 128 output channels is 16 * 16 * 1 = 256 units, the smallest map the dataflow conv3x3 kernel takes on 256 CUs: the decode
+    reaches it (fragment-packed weights, and through the 256 -> 128 block the folded-shortcut copy with its summed bias), its upsampler the parity
+    weights; the encoder at precision 2 runs every conv on duplicated weights (and on the fp8-lo copy where the ping-pong kernel takes the launch)."""
+    from kernel_routing import matrix_kernels, reached
+    vcfg = dict(configs.SD15_VAE, block_out_channels=[128, 256], down_block_types=["DownEncoderBlock2D"] * 2, up_block_types=["UpDecoderBlock2D"] * 2,
+                layers_per_block=1)
+    sd_a = weights.synthetic_state_dict(weights.vae_param_shapes(vcfg), 43, fp16_values=True)
+    sd_b = weights.synthetic_state_dict(weights.vae_param_shapes(vcfg), 44, fp16_values=True)
+    g = torch.Generator().manual_seed(60)
+    z = (torch.randn((1, 4, 128, 128), generator=g) * 0.3).to(DEV)
+    img = torch.rand((1, 3, 256, 256), generator=g).to(DEV)
+
+    def run(vae):
+        dec = vae.decode(z).sample.clone()
+        enc = vae.encode(img).latent_dist.mean.clone()
+        vae.check_finite()
+        return dec, enc
+
+    vae = AutoencoderKL(vcfg, sd_a, DEV)
+    with reached(vae._lib) as names_dec:
+        dec_a = vae.decode(z).sample.clone()
+    with reached(vae._lib) as names_enc:
+        enc_a = vae.encode(img).latent_dist.mean.clone()
+    vae.check_finite()
+    print(f"decode reached {sorted(matrix_kernels(names_dec))}; encode reached {sorted(matrix_kernels(names_enc))}")
+    assert "conv3x3<16x16d,128,gn>" in names_dec, f"the decode did not reach the dataflow conv3x3 kernel: {sorted(names_dec)}"
+    vae.load_state_dict(sd_b)
+    dec_b, enc_b = run(vae)
+    dec_f, enc_f = run(AutoencoderKL(vcfg, sd_b, DEV))
+    assert not torch.equal(dec_a, dec_f) and not torch.equal(enc_a, enc_f), "checkpoints A and B must give different outputs"
+    assert torch.equal(dec_b, dec_f), "decode after a reload differs from a fresh handle's: a derived weight layout of checkpoint A survived"
+    assert torch.equal(enc_b, enc_f), "encode after a reload differs from a fresh handle's: a derived weight layout of checkpoint A survived"
+
+
+def test_unet_reload_under_graph_replay_rebuilds_derived_weights():
+    """SD-v1.5 UNet topology cut to two levels [320, 640] (CrossAttnDownBlock2D, DownBlock2D / UpBlock2D, CrossAttnUpBlock2D), one layer per block,
+    B = 1, 64 x 64 latent (4,096 rows at level 0), context [1, 6, 768], precision 1, graph on.  Reaches the dataflow GEMM (fragment-packed copies of
+    the plain and of the duplicated matrices) and the LayerNorm-fused GEMM (panel-tiled copies); the stream-carrying convs read duplicated weights."""
+    from kernel_routing import matrix_kernels, reached
+    ucfg = dict(configs.SD15_UNET, block_out_channels=[320, 640], down_block_types=["CrossAttnDownBlock2D", "DownBlock2D"],
+                up_block_types=["UpBlock2D", "CrossAttnUpBlock2D"], layers_per_block=1)
+    sd_a = weights.synthetic_state_dict(weights.unet_param_shapes(ucfg), 42, fp16_values=True)
+    sd_b = weights.synthetic_state_dict(weights.unet_param_shapes(ucfg), 45, fp16_values=True)
+    g = torch.Generator().manual_seed(61)
+    x = torch.randn((1, 4, 64, 64), generator=g).to(DEV)
+    ctx = (torch.randn((1, 6, 768), generator=g) * 0.5).to(DEV)
+    unet = UNet2DConditionModel(ucfg, sd_a, DEV).set_precision(1).set_graph(True)
+    out_a = [unet(x, 501, ctx).sample.clone() for _ in range(3)]            # eager, capture, replay
+    assert torch.equal(out_a[0], out_a[1]) and torch.equal(out_a[0], out_a[2])
+    r_a = unet.graph_replays
+    assert r_a == 2 and unet.graph_nodes > 0
+    unet.load_state_dict(sd_b)
+    out_b = [unet(x, 501, ctx).sample.clone() for _ in range(2)]            # eager again (another checkpoint generation), then capture
+    assert unet.graph_replays - r_a == 1, "after the reload only B's own capture may count a replay: A's graph was replayed"
+    fresh = UNet2DConditionModel(ucfg, sd_b, DEV).set_precision(1).set_graph(True)
+    out_f = [fresh(x, 501, ctx).sample.clone() for _ in range(2)]
+    assert fresh.graph_replays == 1
+    assert torch.isfinite(out_f[1]).all()
+    assert not torch.equal(out_a[2], out_f[1]), "checkpoints A and B must give different outputs"
+    assert torch.equal(out_b[0], out_f[0]) and torch.equal(out_b[1], out_f[1]), "a forward after a reload differs from a fresh handle's: a derived weight layout (or the graph) of checkpoint A survived"
+    with reached(unet._lib) as names:                                       # (profiled forwards run eagerly: after the replays, so that those stay replays)
+        out_p = unet(x, 501, ctx).sample.clone()
+    print(f"reached {sorted(matrix_kernels(names))}")
+    assert torch.equal(out_p, out_f[1])
+    assert any(n.startswith("gemm_df") for n in names) and "lngemm<320>" in names, f"meant to reach gemm_df and lngemm<320>: {sorted(names)}"

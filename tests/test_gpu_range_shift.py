@@ -458,3 +458,19 @@ def test_range_shift_api(tiny):
         badvae.fit_range_shift(z.to(DEV), 1 / 0.18215, k_max=0)
     assert badvae.range_shift == 0
     badvae.check_finite()
+
+
+def test_shifted_bias_follows_k(tiny):
+    """The pre-scaled bias copies (shortcut and upsampler convs of a shifted decoder) are kept per layer and keyed on k: decodes at k = 0, 4, 2 on one
+    handle, and the last equals, bit for bit, the first decode of a fresh handle set to k = 2."""
+    vcfg, vsd = tiny["vcfg"], tiny["vsd"]
+    z = (torch.randn((2, 4, 8, 8), generator=torch.Generator().manual_seed(12)) * 0.3).to(DEV)
+    vae = AutoencoderKL(vcfg, vsd, DEV)
+    got = {}
+    for k in (0, 4, 2):
+        got[k] = vae.set_range_shift(k)._decode(z, 1 / 0.18215, want_sample=True)[0].clone()
+    vae.check_finite()
+    fresh = AutoencoderKL(vcfg, vsd, DEV, range_shift=2)
+    ref = fresh._decode(z, 1 / 0.18215, want_sample=True)[0].clone()
+    fresh.check_finite()
+    assert torch.equal(got[2], ref), "k = 2 after k = 4 differs from a fresh handle at k = 2: a bias copy scaled for another k was reused"
