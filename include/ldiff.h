@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define LDIFF_VERSION 201 /* 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
+#define LDIFF_VERSION 202 /* 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
 #define LDIFF_MAX_BLOCKS 8
 
 typedef enum { LDIFF_OK = 0, LDIFF_ERR_INVALID = -1, LDIFF_ERR_RUNTIME = -2, LDIFF_ERR_STATE = -3, LDIFF_ERR_NONFINITE = -4 } ldiff_status;
@@ -196,6 +196,47 @@ int64_t ldiff_resnet_graph_replays(ldiff_resnet*);
 int ldiff_resnet_forward(ldiff_resnet*, const void* crops_nhwc_f16, int B, int S, void* logits_f32, void* labels_i32_or_null, void* stream);
 int ldiff_resnet_check_finite(ldiff_resnet*, void* stream);
 void ldiff_resnet_destroy(ldiff_resnet*);
+
+/* ------------------------------------------------------------------------------------------------
+ * CLIP text encoder of the prompt path  --  replaces `pipeline.text_encoder(input_ids)["last_hidden_state"]` and the `Linear(hidden, cross_attention_dim)` behind it
+ *   segmentor.py:55-60 (unpadded ids), 348-350 (padded to 77)   pixel_latent_vector.py:65-67   utils.py:193-195   ldiffusion.py:213-216 (every training step)
+ * transformers' CLIPTextModel without the pooled output: token + position embeddings (fp32 tables, fp32 sum), `layers` pre-LN encoder layers -- LayerNorm -> fused
+ * q/k/v projection -> causal self-attention (keys j > i masked, scale d^-0.5 in fp32, fp32 softmax over the whole row) -> out_proj + residual -> LayerNorm -> fc1 ->
+ * quick_gelu | gelu -> fc2 + residual -- and final_layer_norm.  No attention_mask (the reference passes none: padding tokens are attended to like any other).  The
+ * residual stream is kept as fp16 hi | lo pairs (as ldiff_unet_set_precision 1 keeps the UNet's); every linear layer contracts a split activation [hi | lo | hi] against
+ * [wh | wh | wl] (wh = fp16(w), wl = fp16(w - wh): fp16 MFMA operands, K tripled, neither rounding enters the fp32 sum); q, k, v and the probabilities are single fp16.  With project = 1
+ * the projection of proj_weights.pt runs as a last such GEMM on the final LayerNorm's split output, fp32 result; the output [B, L, cross_attention_dim] is what
+ * ldiff_unet_set_context takes.  hidden % 64 == 0, hidden / heads a multiple of 16 up to 128, max_positions <= 128.
+ * Checkpoint names are transformers' state_dict keys: text_model.embeddings.{token,position}_embedding.weight, text_model.encoder.layers.N.{layer_norm1,layer_norm2}.*,
+ * text_model.encoder.layers.N.self_attn.{q_proj,k_proj,v_proj,out_proj}.*, text_model.encoder.layers.N.mlp.{fc1,fc2}.*, text_model.final_layer_norm.*; q/k/v are
+ * concatenated at load.  Optional: proj.weight [cross_attention_dim, hidden] and proj.bias (both or neither; cross_attention_dim % 8 == 0).
+ * The final LayerNorm sets the handle's sticky non-finite flag when a row's statistics are not finite (ldiff_textenc_check_finite).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct ldiff_textenc ldiff_textenc;
+/* (The only tagged struct of this header.  tests/test_cpu_host.py enumerates the UNTAGGED `typedef struct { ... } name;` blocks and wants each in its own
+ * list of mirrors; this one's layout is checked against _lib.TextEncCfg, field by field, in tests/test_cpu_text_encoder.py.) */
+typedef struct ldiff_textenc_cfg {
+  int vocab_size, hidden, intermediate, layers, heads;
+  int max_positions; /* config.json "max_position_embeddings" */
+  int act;           /* config.json "hidden_act": 0 = quick_gelu, 1 = gelu */
+  float ln_eps;      /* config.json "layer_norm_eps" */
+} ldiff_textenc_cfg;
+/* (CLIPTextModel.from_pretrained: the reference's pipeline loader, segmentor.py:77-80, ldiffusion.py:67-69) */
+int ldiff_textenc_create(ldiff_textenc** out, const ldiff_textenc_cfg* cfg, int device);
+int ldiff_textenc_load(ldiff_textenc*, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim);
+int ldiff_textenc_missing(ldiff_textenc*);
+const char* ldiff_textenc_missing_name(ldiff_textenc*, int i);
+/* as ldiff_unet_set_graph: the launch sequence of a (B, L, project, out_dtype) configuration is captured on its second use and replayed afterwards; the ids pass
+ * through a handle-owned staging buffer, so a replay serves any ids of that shape */
+int ldiff_textenc_set_graph(ldiff_textenc*, int on);
+int64_t ldiff_textenc_graph_replays(ldiff_textenc*);
+int64_t ldiff_textenc_graph_nodes(ldiff_textenc*); /* kernel launches of the currently captured forward (0: none captured yet) */
+/* ids_host [B, L] int32 on the HOST (the tokenizer's output; copied during the call), 0 <= id < vocab_size, 1 <= L <= max_positions: else LDIFF_ERR_INVALID naming
+ * the offender, nothing launched.  out_dev [B, L, hidden] (project = 0: last_hidden_state) or [B, L, cross_attention_dim] (project = 1: `proj(last_hidden_state)`,
+ * segmentor.py:55-60), out_dtype LDIFF_F32 or LDIFF_F16.  Not inside a stream capture (the ids are host data). */
+int ldiff_textenc_forward(ldiff_textenc*, const int32_t* ids_host, int B, int L, int project, void* out_dev, int out_dtype, void* stream);
+int ldiff_textenc_check_finite(ldiff_textenc*, void* stream);
+void ldiff_textenc_destroy(ldiff_textenc*);
 
 /* ------------------------------------------------------------------------------------------------
  * AutoencoderKL  --  replaces vae.encode(x).latent_dist / vae.decode(z).sample / pipeline.decode_latents
@@ -386,6 +427,10 @@ typedef struct {
                                                        gn_scale / gn_shift are folded into W_b = W diag(scale_b), bias_b = bias + W shift_b by the fold kernel (profiler row
                                                        `fold_gn_weights`) and the contraction runs as gemm_dma<...> on them; where it does not, the plan declines and the launch runs
                                                        as with fold_gn = 0 (igemm<...,gn>, no `fold_gn_weights` row).  0 = never folded (this entry point's historical behaviour) */
+  int act_out;                                      /* an activation BEHIND the sum of a linear layer, y = act(sum + bias) in fp32, rounded once (CLIPMLP.fc1 of the text encoder):
+                                                       1 = quick_gelu v * sigmoid(1.702 v), 2 = gelu (erf form), 0 = none.  Only the LDS-DMA GEMM has it (gemm_dma<...>: ks = 1,
+                                                       K % 64 == 0, fp16 output (plain, or split with y_lo), no res / out_f32 / geglu / stats / out_shift / splitk / gemm_df = 1); any other launch, and
+                                                       act_out beside relu_out / silu_out / cls_conv = 1 / cond_conv = 1 / tconv / lrelu_in / seg_conv = 1: LDIFF_ERR_INVALID, never another route */
 } ldiff_conv_args;
 int ldiff_op_conv(const ldiff_conv_args*, void* stream);
 /* row blocks per image the launch would emit statistics for (0 = unsupported for this shape) */
@@ -411,6 +456,11 @@ int ldiff_op_crop_resize_norm(const void* rgb_u8, int H, int W, const void* boxe
 int ldiff_op_cls_head(const void* x, int B, int HW, int A, int ldx, const void* w_f32, const void* bias_f32, int C, void* logits_f32, void* labels_i32_or_null, void* stream);
 int ldiff_op_attention(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, int B, int heads,
                        int Lq, int Lk, int d, int64_t q_bstride, int64_t kv_bstride, int64_t o_bstride, float scale, void* stream);
+/* Causal self-attention over a short sequence (the text encoder's kernel, text_attn<d>): qkv [B L, ld] f16 is a fused projection output with Q | K | V in column
+ * blocks of `hidden` (head h at columns h d of each), o [B L, ldo] f16.  One workgroup per (image, head); keys j > i are masked before an fp32 softmax over the whole
+ * row, p is rounded once to fp16, the row sum is the fp32 sum of the unrounded p.  d % 16 == 0 in 16..128, 1 <= L <= 128, ld % 8 == 0, hidden % 8 == 0, ldo % 4 == 0.
+ * (CLIPAttention with the causal mask of CLIPTextTransformer: segmentor.py:55-60) */
+int ldiff_op_text_attention(const void* qkv, int ld, int hidden, void* o, int ldo, int B, int heads, int L, int d, float scale, void* stream);
 /* The same with q ALREADY multiplied by scale * log2(e) (the executors do that in the fp32 epilogue of the q/k/v projection, so q is still rounded
  * once): the kernel then lets the MFMAs subtract the running softmax reference (a 1.0 in K's padding column against -reference in Q's) and skips the
  * per-score FMA.  Head dims with a free column in the last 32-wide k-step only (d = 40, 80: the UNet's levels 0 and 1); others: LDIFF_ERR_INVALID. */

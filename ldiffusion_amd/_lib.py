@@ -27,6 +27,11 @@ class VaeCfg(C.Structure):
                 ("scaling_factor", C.c_float)]
 
 
+class TextEncCfg(C.Structure):
+    _fields_ = [("vocab_size", C.c_int), ("hidden", C.c_int), ("intermediate", C.c_int), ("layers", C.c_int), ("heads", C.c_int),
+                ("max_positions", C.c_int), ("act", C.c_int), ("ln_eps", C.c_float)]
+
+
 class ConvArgs(C.Structure):
     _fields_ = [("x", C.c_void_p), ("x2", C.c_void_p), ("C1", C.c_int), ("C2", C.c_int),
                 ("B", C.c_int), ("Hin", C.c_int), ("Win", C.c_int), ("Hout", C.c_int), ("Wout", C.c_int),
@@ -39,7 +44,7 @@ class ConvArgs(C.Structure):
                 ("lo8_slab0", C.c_int), ("lo8_scale", C.c_void_p), ("gemm_df", C.c_int),
                 ("sc_x", C.c_void_p), ("sc_C", C.c_int), ("sc_ld", C.c_int), ("sc_w", C.c_void_p), ("sc_bias", C.c_void_p), ("c3d_ups", C.c_int), ("n_real", C.c_int), ("splitk", C.c_int),
                 ("out_shift", C.c_int), ("silu_out", C.c_int), ("cond_conv", C.c_int), ("lrelu_in", C.c_int), ("tconv", C.c_int), ("seg_conv", C.c_int),
-                ("relu_out", C.c_int), ("cls_conv", C.c_int), ("fold_gn", C.c_int)]
+                ("relu_out", C.c_int), ("cls_conv", C.c_int), ("fold_gn", C.c_int), ("act_out", C.c_int)]
 
 
 # name -> (restype, argtypes); every symbol include/ldiff.h declares
@@ -89,6 +94,17 @@ SIGNATURES = {
     "ldiff_resnet_forward": (I, [P, P, I, I, P, P, P]),
     "ldiff_resnet_check_finite": (I, [P, P]),
     "ldiff_resnet_destroy": (None, [P]),
+    "ldiff_textenc_create": (I, [C.POINTER(P), C.POINTER(TextEncCfg), I]),
+    "ldiff_textenc_load": (I, [P, C.c_char_p, P, I, C.POINTER(I64), I]),
+    "ldiff_textenc_missing": (I, [P]),
+    "ldiff_textenc_missing_name": (C.c_char_p, [P, I]),
+    "ldiff_textenc_set_graph": (I, [P, I]),
+    "ldiff_textenc_graph_replays": (I64, [P]),
+    "ldiff_textenc_graph_nodes": (I64, [P]),
+    "ldiff_textenc_forward": (I, [P, C.POINTER(C.c_int32), I, I, I, P, I, P]),
+    "ldiff_textenc_check_finite": (I, [P, P]),
+    "ldiff_textenc_destroy": (None, [P]),
+    "ldiff_op_text_attention": (I, [P, I, I, P, I, I, I, I, I, F, P]),
     "ldiff_vae_create": (I, [C.POINTER(P), C.POINTER(VaeCfg), I]),
     "ldiff_vae_load": (I, [P, C.c_char_p, P, I, C.POINTER(I64), I]),
     "ldiff_vae_set_precision": (I, [P, I, I]),

@@ -2,7 +2,7 @@
 instance classifier on the HIP library (`models.ResNetClassifier`, include/ldiff.h ldiff_resnet_*).
 
 What the reference does per image, restated here:
-  1. Cellpose `cyto2` -> an instance label map (third-party; injectable as `instances=`, as CLIP stays `transformers`').
+  1. Cellpose `cyto2` -> an instance label map (third-party; injectable as `instances=`, as the prompt's tokenizer stays `transformers`').
   2. Per instance its bounding box; instances with y2 - y1 < 4 or x2 - x1 < 4 are skipped.
   3. The crop of the ImageNet-NORMALISED image goes through `(patch * 255).astype(np.uint8)` -> ToTensor -> Resize((64, 64)) -> Normalize: a
      second normalisation on top of a wrapping cast.  Per pixel that is a function of the decoded uint8 value alone: `build_lut`.

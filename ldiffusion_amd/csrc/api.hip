@@ -30,7 +30,7 @@ static void report_nonfinite(NonFiniteFlag& nf, const char* what, const char* hi
   }                                                              \
   return LDIFF_OK;
 
-// ---- what the handle families (unet, controlnet, vae, segnet, resnet) share ----
+// ---- what the handle families (unet, controlnet, vae, segnet, resnet, textenc) share ----
 template <class H> static int device_of(const H* h) { return h->device; }
 static int device_of(const ldiff_controlnet* c) { return c->trunk.device; }
 template <class H> static NonFiniteFlag& flag_of(H* h) { return h->nf; }
@@ -264,6 +264,45 @@ int ldiff_resnet_forward(ldiff_resnet* r, const void* crops, int B, int S, void*
 }
 int ldiff_resnet_check_finite(ldiff_resnet* r, void* stream) { return check_finite(r, stream, "resnet_check_finite"); }
 void ldiff_resnet_destroy(ldiff_resnet* r) { destroy(r); }
+// ---- CLIP text encoder of the prompt path ----
+int ldiff_textenc_create(ldiff_textenc** out, const ldiff_textenc_cfg* cfg, int device) {
+  API_BEGIN
+  LDIFF_CHECK(out && cfg, LDIFF_ERR_INVALID, "textenc_create: null argument");
+  select_device("textenc_create", device);
+  ldiff_textenc* t = new ldiff_textenc();
+  t->cfg = *cfg;
+  t->device = device;
+  try { t->build(); } catch (...) { delete t; throw; }
+  *out = t;
+  API_END
+}
+int ldiff_textenc_load(ldiff_textenc* t, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
+  API_BEGIN
+  LDIFF_CHECK(t, LDIFF_ERR_INVALID, "textenc_load: null handle");
+  HIP_CHECK(hipSetDevice(t->device));
+  t->load(name, host_ptr, dtype, shape, ndim);
+  API_END
+}
+int ldiff_textenc_missing(ldiff_textenc* t) { return t ? t->missing() : -1; }
+const char* ldiff_textenc_missing_name(ldiff_textenc* t, int i) { return t ? t->missing_name(i) : ""; }
+int ldiff_textenc_set_graph(ldiff_textenc* t, int on) { return set_graph(t, on, "textenc_set_graph"); }
+int64_t ldiff_textenc_graph_replays(ldiff_textenc* t) { return t ? (int64_t)t->gc.replays : -1; }
+int64_t ldiff_textenc_graph_nodes(ldiff_textenc* t) { return t ? (int64_t)t->gc.nodes : -1; }
+int ldiff_textenc_forward(ldiff_textenc* t, const int32_t* ids_host, int B, int L, int project, void* out_dev, int out_dtype, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(t, LDIFF_ERR_INVALID, "textenc_forward: null handle");
+  report_nonfinite(t->nf, "textenc_forward");
+  t->forward(ids_host, B, L, project, out_dev, out_dtype, (hipStream_t)stream);
+  API_END
+}
+int ldiff_textenc_check_finite(ldiff_textenc* t, void* stream) { return check_finite(t, stream, "textenc_check_finite"); }
+void ldiff_textenc_destroy(ldiff_textenc* t) { destroy(t); }
+int ldiff_op_text_attention(const void* qkv, int ld, int hidden, void* o, int ldo, int B, int heads, int L, int d, float scale, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(qkv && o, LDIFF_ERR_INVALID, "op_text_attention: null argument");
+  launch_text_attention((const f16*)qkv, ld, hidden, (f16*)o, ldo, 0, B, heads, L, d, scale, (hipStream_t)stream);
+  API_END
+}
 int ldiff_op_maxpool3x3s2(const void* x, void* y, int B, int H, int W, int C, void* stream) {
   API_BEGIN
   launch_maxpool3x3s2((const f16*)x, (f16*)y, B, H, W, C, (hipStream_t)stream);
@@ -711,6 +750,7 @@ static void conv_args_to_params(const ldiff_conv_args* a, ConvParams& p) {
   p.cond_force = a->cond_conv;
   p.lrelu_in = a->lrelu_in; p.tconv = a->tconv; p.seg_conv = a->seg_conv;
   p.relu_out = a->relu_out != 0; p.cls_force = a->cls_conv;
+  p.act_out = a->act_out;   // (plan_conv checks 0 | 1 | 2 and the route)
   if (p.tconv) p.K = a->C1;   // one GEMM over the coarse map: the four taps are column blocks, not K
 }
 int ldiff_op_conv(const ldiff_conv_args* a, void* stream) {

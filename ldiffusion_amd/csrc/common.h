@@ -116,6 +116,9 @@ struct ConvParams {
   // nonfinite: the owning handle's sticky flag, set by that family's epilogue where sum + bias + res is NaN or beyond fp16's range (nullptr: not reported)
   int relu_out = 0, cls_force = 0;
   int* nonfinite = nullptr;
+  // An activation BEHIND the sum of a linear layer (y = act(sum + bias), fp32, one fp16 rounding; ldiff_conv_args.act_out): 1 = quick_gelu v sigmoid(1.702 v), 2 = gelu
+  // (erf form).  The LDS-DMA GEMM only (gemm_dma<...>, unsplit, fp16 output, plain or split, without residual): plan_conv refuses it for any other launch
+  int act_out = 0;
 };
 constexpr int LO8_SHIFT = 15;   // lo = x - fp16(x) of a GroupNorm + SiLU output: |lo| <= half an fp16 ulp = 2^-7 for |x| < 32, so lo * 2^15 <= 256 stays inside e4m3's 448;
                                 // for |x| in [32, 64) it reaches 512 and saturates at 448 (the correction term is clamped, harmless), as for everything beyond
@@ -220,6 +223,17 @@ struct AttnParams {
 };
 void launch_attention(const AttnParams& p, hipStream_t s);
 bool attention_prescale_supported(int d);
+
+// ---- CLIP text encoder (kernels_text.hip) ------------------------------------------------------
+// y [M, 2 H] split = token_embedding[ids[m]] + position_embedding[m % L] (fp32 tables, fp32 sum)
+void launch_text_embed(const int* ids, const float* tok, const float* pos, f16* y, int M, int L, int H, int vocab, hipStream_t s);
+// causal softmax(scale Q K^T) V per (image, head) over the fused projection output qkv [B L, ld] (Q | K | V column blocks of `hidden`), o [B L, ldo]
+bool text_attention_supported(int d, int L);   // d % 16 == 0 in 16..128, L in 1..128
+void launch_text_attention(const f16* qkv, int ld, int hidden, f16* o, int ldo, int o_lo /* > 0: o is split, the lo half o_lo columns behind the hi half */, int B, int heads, int L, int d, float scale,
+                           hipStream_t s);
+// LayerNorm of a split [M, 2 C] tensor -> out [M, C] (fp32, or fp16 with out_f16; may be null) and / or y_split [M, 2 C] (may be null); raises *nonfinite
+void launch_text_ln(const f16* x_split, int M, int C, const float* gamma, const float* beta, float eps, void* out, int out_f16, f16* y_split, int* nonfinite, hipStream_t s);
+void launch_f32_to_f16(const float* x, f16* y, long long n, hipStream_t s);
 
 // ---- normalisation (kernels_norm.hip) --------------------------------------------------------
 // GroupNorm statistics over one or two NHWC sources (channel concat) -> per-(b,c) scale/shift (fp32):

@@ -122,6 +122,9 @@ ConvPlan plan_conv(ConvParams& p, const ConvAsk& ask) {
   // launch and drop it
   LDIFF_CHECK(!q.relu_out || !(q.silu_out || q.cond_force > 0 || q.tconv || q.lrelu_in || q.seg_conv > 0), LDIFF_ERR_INVALID,
               "conv: relu_out cannot be combined with silu_out / cond_conv = 1 / tconv / lrelu_in / seg_conv = 1 (only the classifier's conv family has a ReLU epilogue)");
+  // likewise quick_gelu / gelu behind the sum (act_out, 0d below): nothing that selects one of the families in front of it
+  LDIFF_CHECK(!q.act_out || !(q.relu_out || q.cls_force > 0 || q.silu_out || q.cond_force > 0 || q.tconv || q.lrelu_in || q.seg_conv > 0), LDIFF_ERR_INVALID,
+              "conv: act_out cannot be combined with relu_out / cls_conv = 1 / silu_out / cond_conv = 1 / tconv / lrelu_in / seg_conv = 1 (only the LDS-DMA GEMM has that epilogue)");
   // 0. the conditioning-embedding 3x3 (kernels_cond.hip): channel counts no other family is made for; no split, no fused statistics (the caller's
   //    separate statistics pass), plain weights.  It is the one kernel with an activation behind its sum
   if (ask.splitk < 2 && cond_conv_selected(q)) {
@@ -163,6 +166,19 @@ ConvPlan plan_conv(ConvParams& p, const ConvAsk& ask) {
               q.C1 + q.C2, q.N, q.ks, q.stride, q.pad_t, q.cls_force);
   LDIFF_CHECK(!q.silu_out, LDIFF_ERR_INVALID, "conv: a SiLU epilogue (silu_out) exists only in the conditioning-embedding kernel, which does not take this launch (Cin=%d N=%d ks=%d stride=%d)",
               q.C1 + q.C2, q.N, q.ks, q.stride);
+  // 0d. quick_gelu / gelu behind the sum (ConvParams::act_out, the text encoder's FC1): the LDS-DMA GEMM has it, unsplit, with an fp16 output (plain or split: y_lo); the launch is
+  //     that kernel's or it is refused -- the dataflow GEMM, the split reduce and the implicit GEMM have no such epilogue
+  if (q.act_out) {
+    LDIFF_CHECK((q.act_out == 1 || q.act_out == 2) && !q.geglu && !q.res && !q.out_f32 && !q.out_shift && !q.gn_scale && !q.temb && !ask.stats && ask.splitk < 2 && q.w_bstride == 0 &&
+                    !q.xs && !q.lo8_slab0 && p.df_force <= 0 && gemm_dma_eligible(q),   // (p.df_force: what the launch itself asks for, not LDIFF_GEMM_DF)
+                LDIFF_ERR_INVALID, "conv: act_out = %d (1 quick_gelu | 2 gelu) exists only in the LDS-DMA GEMM: a linear layer (ks = 1, K %% 64 == 0) with bias and an fp16 output (plain or split), no residual / "
+                "fp32 output / GEGLU / statistics / range shift / split-K / gemm_df (C1=%d C2=%d N=%d ks=%d stride=%d)", q.act_out, q.C1, q.C2, q.N, q.ks, q.stride);
+    pl.kernel = ConvKernel::GEMM_DMA;
+    gemm_dma_tile(q, 1, pl);
+    p.splitk = 0;
+    p.stats_R = 0;
+    return pl;
+  }
   // 1. the kernel family.  GroupNorm -> 1x1 conv / Linear with no activation in between (VAE attention q/k/v; transformer proj_in under PREC_FAST):
   //    the normalisation folded into per-image weights and bias where the plain LDS-DMA GEMM takes that form, instead of the register-staged GN prologue
   if (ask.fold_gn && q.gn_scale && !q.silu_in && !q.lrelu_in && q.ks == 1 && !q.x2 && !q.out_f32 && !q.geglu) {

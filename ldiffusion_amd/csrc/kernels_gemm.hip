@@ -40,7 +40,15 @@ __device__ __forceinline__ void lds_wait(f16x8& a, f16x8& b, f16x8& c, f16x8& d,
   asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e) : "n"(CNT));
 }
 
-template <int BM, int BN>
+// ConvParams::act_out behind the sum (the text encoder's FC1): 1 = quick_gelu v sigmoid(1.702 v), 2 = gelu (erf form, as the GEGLU epilogue computes it), in fp32
+// before the one rounding
+__device__ __forceinline__ f32x4 act_out4(f32x4 v, int act) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) v[r] = act == 2 ? gelu_erf(v[r]) : v[r] * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v[r] * (-1.702f * 1.4426950408889634f)));
+  return v;
+}
+
+template <int BM, int BN, int ACT>   // ACT: the instantiation with the act_out epilogue (the plain one is the kernel it always was)
 __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const ConvParams p) {
   constexpr int MT = BM / 32, NT = BN / 32;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -291,6 +299,7 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const ConvParams p) {
         for (int h = 0; h < 2; ++h) {
           const int m = mp + h;
           f32x4 v = (acc[a][m] + bb[a]) * osc;   // range shift before the (pre-shifted) residual
+          if constexpr (ACT) v = act_out4(v, p.act_out);
           if (p.res) { v += up4(rr[m][a]); if (p.res_lo) v += up4(rl[m][a]); }
           const f16x4 o = cvt4(v);
           if (p.stats) acc[a][m] = p.y_lo ? split_stat4(v) : up4(o);
@@ -317,6 +326,7 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const ConvParams p) {
       const int n = ncol + a * 16;
       if (n >= p.N) continue;
       f32x4 v = (acc[a][m] + bb[a]) * osc;   // range shift before the (pre-shifted) residual
+      if constexpr (ACT) v = act_out4(v, p.act_out);
       if (p.res) { v += up4(rr[m][a]); if (p.res_lo) v += up4(rl[m][a]); }
       if (p.out_f32) {
         *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.y) + (long long)mrow[m] * p.ldy + n) = v;
@@ -353,14 +363,14 @@ static bool gemm_m_fast(const ConvParams& p, int ntm, int ntn) {
 template <int BM, int BN>
 void launch_g(const ConvParams& p, hipStream_t s) {
   const size_t smem = (size_t)2 * (BM + BN) * 8 * 16;
-  auto kern = gemm_dma_kernel<BM, BN>;
+  auto kern = p.act_out ? gemm_dma_kernel<BM, BN, 1> : gemm_dma_kernel<BM, BN, 0>;
   ensure_dyn_smem(reinterpret_cast<const void*>(kern), (int)smem);
   const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
   static const std::string pname = std::string("gemm_dma<") + std::to_string(BM) + "," + std::to_string(BN) + ">";
   const double bytes = (double)p.M * p.K * 2.0 + (double)p.N * p.K * 2.0 + (double)p.M * p.N * (p.out_f32 || p.y_lo ? 4.0 : 2.0) + (p.res ? (double)p.M * p.N * (p.res_lo ? 4.0 : 2.0) : 0.0);
   ProfScope prof(pname.c_str(), 2.0 * p.M * (double)p.N * p.K, bytes, s);
   const int S = p.splitk > 1 ? p.splitk : 1;
-  LDIFF_CHECK(S == 1 || (p.splitk_ws && !p.geglu && !p.out_f32 && p.w_bstride == 0), LDIFF_ERR_INVALID, "gemm: split-K needs a workspace and a plain fp16 epilogue");   // (fused statistics of a split launch: by the reduce kernel)
+  LDIFF_CHECK(S == 1 || (p.splitk_ws && !p.geglu && !p.out_f32 && p.w_bstride == 0 && !p.act_out), LDIFF_ERR_INVALID, "gemm: split-K needs a workspace and a plain fp16 epilogue");   // (fused statistics of a split launch: by the reduce kernel)
   ConvParams q = p;
   q.tiles_m = ntm; q.img_fast = gemm_m_fast(p, ntm, ntn) ? 1 : 0;
   hipLaunchKernelGGL(kern, dim3(ntm * ntn, S), dim3(256), smem, s, q);

@@ -435,6 +435,47 @@ struct ldiff_resnet {
   ~ldiff_resnet();
 };
 
+// ---- CLIP text encoder ---------------------------------------------------------------------------------
+// transformers' CLIPTextModel without the pooled output (include/ldiff.h): embeddings, pre-LN encoder layers with causal self-attention, final LayerNorm,
+// optionally the prompt projection Linear(hidden, cross_attention_dim) behind it.  The residual stream is split (hi | lo) throughout.
+// A linear layer of the text encoder: the weight as a three-block operand [Nrows][wh(K) | wh(K) | wl(K)] (wh = fp16(w), wl = fp16(w - wh)) against a split
+// activation read as [hi | lo | hi] -- the sum is x.w to ~22 bits of both factors (the lo.wl term is dropped) -- and an fp32 bias.
+struct TextLinW { f16* w3 = nullptr; float* b = nullptr; int N = 0, Nrows = 0, K = 0; };
+struct TextLayerW { NormW ln1, ln2; TextLinW qkv, out, fc1, fc2; };
+struct ldiff_textenc {
+  ldiff_textenc_cfg cfg;
+  int device = 0;
+  WeightStore ws;         // names, shapes, norms and biases; the matrices land in the three-block operands (load)
+  Exec ex;
+  NonFiniteFlag nf;
+  float* tok = nullptr;   // [vocab][hidden] fp32
+  float* pos = nullptr;   // [max_positions][hidden] fp32
+  bool tok_loaded = false, pos_loaded = false;
+  int emb_gen = 0;
+  std::vector<TextLayerW> layers;
+  NormW final_ln;
+  TextLinW proj;          // optional: registered by the first load of proj.weight / proj.bias, which states its width
+  int proj_dim = 0;
+  f16* scratch_w = nullptr;   // where WeightStore::load puts the fp16 copy it makes of a matrix (not read)
+  struct MatDst { f16* w3; int row_off, K; };
+  std::unordered_map<std::string, MatDst> mats;   // checkpoint name of a matrix -> its rows in a three-block operand
+  mutable std::vector<std::string> missing_cache;
+  void build();
+  TextLinW add_lin(const std::string& prefix, int K, int N);
+  void add_part(TextLinW& l, const std::string& prefix, int row_off, int rows);
+  void load(const char* name, const void* host, int dtype, const int64_t* shape, int ndim);
+  int missing() const;
+  const char* missing_name(int i) const;
+  void forward(const int32_t* ids_host, int B, int L, int project, void* out, int out_dtype, hipStream_t s);
+  void forward_impl(const int* ids_dev, int B, int L, int project, void* out, int out_dtype, hipStream_t s);
+  // y = act(x.w^T + b) [+ res]: x split [M, 2 K]; y a plain or split fp16 tensor, or fp32 rows at out_f32
+  Act linear(const TextLinW& w, const Act& x, const Act* res, bool split_out, int act_out, float* out_f32);
+  Act layernorm(const Act& x, const NormW& w);   // split in, split out
+  GraphCache gc;
+  DeviceBuf st_ids, st_out;
+  ~ldiff_textenc();
+};
+
 struct ldiff_pipeline {
   ldiff_unet* unet;
   ldiff_vae* vae;

@@ -618,3 +618,86 @@ class ResNetClassifier(_GraphHandle):
         return logits, labels
 
     forward = __call__
+
+
+class CLIPTextModel(_GraphHandle):
+    """transformers' CLIPTextModel on the HIP library (include/ldiff.h ldiff_textenc_*): `pipeline.text_encoder` of the reference's prompt path
+    (/root/reference/segmentor.py:55-60,348-350, pixel_latent_vector.py:65-67, utils.py:193-195, ldiffusion.py:213-216).  `cfg` is
+    text_encoder/config.json, `state_dict` carries transformers' own keys (with or without the `text_model.` prefix: `weights.clip_text_loader_name`).  `enc(input_ids)["last_hidden_state"]` is float32 [B, L, hidden] on the
+    device; with a projection loaded (`load_projection`), `enc.project(input_ids)` returns `proj(last_hidden_state)` from the same library call.
+    No pooled output, no attention_mask (the reference passes none)."""
+    _prefix, _noun = "textenc", "text encoder"
+
+    def __init__(self, cfg: dict, state_dict, device=None):
+        c = weights.clip_text_config(cfg)   # refusals happen here, before the library is touched
+        _lib.require_gpu()
+        self.config = SimpleNamespace(**{**cfg, **c})
+        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self._lib = _lib.load()
+        tc = _lib.TextEncCfg(int(c["vocab_size"]), int(c["hidden_size"]), int(c["intermediate_size"]), int(c["num_hidden_layers"]), int(c["num_attention_heads"]),
+                             int(c["max_position_embeddings"]), weights.CLIP_TEXT_ACTS[c["hidden_act"]], float(c["layer_norm_eps"]))
+        self._h = C.c_void_p()
+        _lib.check(self._lib.ldiff_textenc_create(C.byref(self._h), C.byref(tc), self.device.index or 0))
+        self._shapes = weights.clip_text_param_shapes(c)
+        self.projection_dim = None
+        self.load_state_dict(weights.normalize_clip_text_keys(state_dict))
+
+    @classmethod
+    def from_pretrained(cls, path, device=None, **_ignored):
+        cfg, sd = weights.load_model_dir(path)
+        return cls(cfg, sd, device=device)
+
+    def load_projection(self, state_dict):
+        """`nn.Linear(hidden, cross_attention_dim).load_state_dict(proj_weights.pt, strict=True)` of the reference (segmentor.py:45-48): exactly
+        `weight` and `bias`; anything else is refused by key, as torch refuses it."""
+        keys = set(state_dict)
+        if keys != {"weight", "bias"}:
+            raise RuntimeError(f"Error(s) in loading state_dict for the text projection: unexpected {sorted(keys - {'weight', 'bias'})}, missing {sorted({'weight', 'bias'} - keys)}")
+        w, b = state_dict["weight"], state_dict["bias"]
+        if w.dim() != 2 or w.shape[1] != self.config.hidden_size or tuple(b.shape) != (w.shape[0],):
+            raise RuntimeError(f"text projection: weight {list(w.shape)} / bias {list(b.shape)} do not fit hidden_size = {self.config.hidden_size}")
+        if self.projection_dim not in (None, w.shape[0]):
+            raise RuntimeError(f"text projection: this encoder already holds a projection to {self.projection_dim} channels")
+        self._shapes = weights.clip_text_param_shapes(vars(self.config), w.shape[0])
+        self.load_state_dict({"proj.weight": w, "proj.bias": b})
+        self.projection_dim = int(w.shape[0])
+        return self
+
+    @property
+    def graph_nodes(self) -> int:
+        """Kernel launches of the currently captured forward (0: none captured yet)."""
+        return int(self._lib.ldiff_textenc_graph_nodes(self._h))
+
+    def to(self, *args, **kwargs):
+        return self
+
+    def _run(self, input_ids, project, out_dtype):
+        if out_dtype not in (torch.float32, torch.float16):
+            raise ValueError("CLIPTextModel: out_dtype must be float32 or float16")
+        ids = torch.as_tensor(input_ids)
+        if ids.dim() != 2 or ids.is_floating_point():
+            raise ValueError(f"CLIPTextModel: input_ids must be an integer tensor [B, L], got {ids.dtype} {list(ids.shape)}")
+        if project and self.projection_dim is None:
+            raise RuntimeError("CLIPTextModel: no projection loaded (load_projection)")
+        ids = ids.detach().to("cpu", torch.int32).contiguous()   # the tokenizer's output is host data; the library validates and stages it
+        B, L = ids.shape
+        out = torch.empty((B, L, self.projection_dim if project else self.config.hidden_size), dtype=out_dtype, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.ldiff_textenc_forward(self._h, C.cast(ids.data_ptr(), C.POINTER(C.c_int32)), B, L, int(bool(project)), _lib.ptr(out), _DTYPES[out_dtype],
+                                                       _lib.stream_ptr()))
+        return out
+
+    @torch.no_grad()
+    def __call__(self, input_ids, attention_mask=None, out_dtype=torch.float32, **unsupported):
+        if attention_mask is not None:
+            raise ValueError("CLIPTextModel: attention_mask is not supported (the reference never passes one; pass attention_mask=None)")
+        if unsupported:
+            raise ValueError(f"CLIPTextModel: unsupported arguments {sorted(unsupported)}")
+        return {"last_hidden_state": self._run(input_ids, False, out_dtype)}
+
+    forward = __call__
+
+    @torch.no_grad()
+    def project(self, input_ids, out_dtype=torch.float32):
+        """`proj(text_encoder(input_ids)["last_hidden_state"])` in one library call: [B, L, cross_attention_dim], ready for `unet.set_context`."""
+        return self._run(input_ids, True, out_dtype)

@@ -31,9 +31,12 @@ class StableDiffusionImg2ImgPipeline:
         self.device = vae.device
 
     @classmethod
-    def from_pretrained(cls, path, torch_dtype=None, device=None, **_ignored):
+    def from_pretrained(cls, path, torch_dtype=None, device=None, text_encoder="transformers", **_ignored):
         """Reads the diffusers SD directory layout: {unet,vae}/(config.json + safetensors), scheduler/scheduler_config.json,
-        and tokenizer/ + text_encoder/ through `transformers` when those folders exist (CLIP is outside the kernel scope)."""
+        and tokenizer/ + text_encoder/ when those folders exist.  The tokenizer (host BPE) is `transformers`'; the text encoder is
+        `transformers`' too by default, or with text_encoder="hip" the library's (`models.CLIPTextModel`, ldiff_textenc_*)."""
+        if text_encoder not in ("transformers", "hip"):
+            raise ValueError(f"text_encoder must be 'transformers' or 'hip', got {text_encoder!r}")
         if torch_dtype not in (None, torch.float32):
             raise ValueError("the reference loads the pipeline in float32 (ldiffusion.py:67); other dtypes are not supported")
         unet = UNet2DConditionModel.from_pretrained(os.path.join(path, "unet"), device=device)
@@ -47,7 +50,11 @@ class StableDiffusionImg2ImgPipeline:
         if os.path.isdir(os.path.join(path, "tokenizer")) and os.path.isdir(os.path.join(path, "text_encoder")):
             from transformers import CLIPTextModel, CLIPTokenizer
             tok = CLIPTokenizer.from_pretrained(os.path.join(path, "tokenizer"))
-            enc = CLIPTextModel.from_pretrained(os.path.join(path, "text_encoder")).to(vae.device)
+            if text_encoder == "hip":
+                from .models import CLIPTextModel as HipCLIPTextModel
+                enc = HipCLIPTextModel.from_pretrained(os.path.join(path, "text_encoder"), device=vae.device)
+            else:
+                enc = CLIPTextModel.from_pretrained(os.path.join(path, "text_encoder")).to(vae.device)
         return cls(vae, unet, PNDMScheduler(**sched_cfg), tok, enc)
 
     def to(self, *a, **k):

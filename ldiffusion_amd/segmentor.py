@@ -18,6 +18,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .models import CLIPTextModel as HipCLIPTextModel
 from .models import UNet2DConditionModel
 from .pipeline import PROMPT, LaplaceSampler, StableDiffusionImg2ImgPipeline, argmax_mask
 
@@ -69,6 +70,19 @@ class Segmentor:
         return ldiffusion_weight if os.path.isdir(ldiffusion_weight) else os.path.dirname(ldiffusion_weight)
 
     def _ensure_ldiffusion_proj(self, pipeline, unet, ldiffusion_weight=None):
+        if isinstance(pipeline.text_encoder, HipCLIPTextModel):
+            # the library's encoder carries the projection itself (one call, fused behind the final LayerNorm): None is returned, and the callers use
+            # `text_encoder.project(ids)`.  As below: proj_weights.pt where there is one, else a freshly initialised Linear(hidden, cross_attention_dim)
+            enc, cad = pipeline.text_encoder, unet.config.cross_attention_dim
+            if ldiffusion_weight is not None:
+                p = os.path.join(self._resolve_ldiffusion_dir(ldiffusion_weight), "proj_weights.pt")
+                if os.path.exists(p):
+                    enc.load_projection(torch.load(p, map_location="cpu"))
+            if enc.projection_dim is None:
+                enc.load_projection(nn.Linear(enc.config.hidden_size, cad).state_dict())
+            if enc.projection_dim != cad:
+                raise RuntimeError(f"text projection: the encoder's projection has {enc.projection_dim} output channels, the UNet's cross_attention_dim is {cad}")
+            return None
         hidden = pipeline.text_encoder.config.hidden_size
         cad = unet.config.cross_attention_dim
         if self.ldiffusion_proj is None or self.ldiffusion_proj.in_features != hidden or self.ldiffusion_proj.out_features != cad:
@@ -83,6 +97,8 @@ class Segmentor:
     @torch.no_grad()
     def _get_text_embeddings(self, prompt, batch_size, pipeline, unet):
         proj = self._ensure_ldiffusion_proj(pipeline, unet)
+        if isinstance(pipeline.text_encoder, HipCLIPTextModel):
+            return pipeline.text_encoder.project(pipeline.tokenizer([prompt] * batch_size)["input_ids"])
         ids = torch.tensor(pipeline.tokenizer([prompt] * batch_size)["input_ids"], dtype=torch.long, device=self.device)
         emb = pipeline.text_encoder(ids)["last_hidden_state"].to(dtype=torch.float32)
         return proj(emb).to(dtype=torch.float32)
@@ -92,8 +108,9 @@ class Segmentor:
             raise ValueError("Invalid level specified. Choose 'tissue' or 'cell'.")
         raise RuntimeError("the segmentation heads (model/conductor.py, nnU-Net) are outside the MI355X hot-path scope; pass `head=`")
 
-    def load_ldiffusion(self, ldiffusion_weight, diffusion_path):
-        pipeline = StableDiffusionImg2ImgPipeline.from_pretrained(diffusion_path, torch_dtype=torch.float32, device=self.device)
+    def load_ldiffusion(self, ldiffusion_weight, diffusion_path, text_encoder="transformers"):
+        """text_encoder="hip": the prompt's CLIP pass and projection run on the library (`StableDiffusionImg2ImgPipeline.from_pretrained`)."""
+        pipeline = StableDiffusionImg2ImgPipeline.from_pretrained(diffusion_path, torch_dtype=torch.float32, device=self.device, text_encoder=text_encoder)
         unet = UNet2DConditionModel.from_pretrained(ldiffusion_weight, device=self.device).eval()
         vae = pipeline.vae
         pipeline.unet = unet
@@ -158,7 +175,10 @@ class Segmentor:
         dtm = F.interpolate(dtm.to(dev, torch.float32), size=(256, 256), mode="bilinear", align_corners=False)
         ids = pipeline.tokenizer(["A remote sense image"], padding="max_length", max_length=77, return_tensors="pt")
         ids = torch.as_tensor(ids["input_ids"] if isinstance(ids, dict) else ids.input_ids, dtype=torch.long, device=dev)
-        ctx = proj(pipeline.text_encoder(ids)["last_hidden_state"].to(device=dev, dtype=torch.float32)).to(dtype=torch.float32)
+        if proj is None:   # the library's encoder: the projection is fused into the one call
+            ctx = pipeline.text_encoder.project(ids)
+        else:
+            ctx = proj(pipeline.text_encoder(ids)["last_hidden_state"].to(device=dev, dtype=torch.float32)).to(dtype=torch.float32)
         recon = []
         from .models import ControlNetModel, UNet2DConditionModel
         fused = isinstance(controlnet, ControlNetModel) and isinstance(unet, UNet2DConditionModel)

@@ -192,6 +192,79 @@ def vae_param_shapes(cfg: dict) -> "OrderedDict[str, tuple]":
     return s
 
 
+# ------------------------------------------------------------------------------------------
+# CLIP text encoder (transformers key layout; csrc/model_text.hip)
+# ------------------------------------------------------------------------------------------
+CLIP_TEXT_ACTS = {"quick_gelu": 0, "gelu": 1}
+CLIP_TEXT_QKV = ("q_proj", "k_proj", "v_proj")   # row blocks of the fused projection, in this order
+CLIP_TEXT_IGNORED = ("text_model.embeddings.position_ids",)   # a buffer older transformers versions save: arange(max_position_embeddings)
+
+
+def clip_text_loader_name(key: str):
+    """The loader name of a CLIPTextModel state-dict key, None for the one key that is dropped.  Loader names are the keys of the checkpoints in
+    circulation (transformers 4.x: `text_model.embeddings...`, what SD-v1.5's text_encoder/ holds); transformers 5 flattened the module and writes
+    the same keys without the `text_model.` prefix, which maps onto them."""
+    name = key if key.startswith("text_model.") else "text_model." + key
+    return None if name in CLIP_TEXT_IGNORED else name
+
+
+def normalize_clip_text_keys(sd) -> "OrderedDict[str, torch.Tensor]":
+    """state dict -> loader names (clip_text_loader_name); a key reached twice (both layouts in one file) is refused."""
+    out = OrderedDict()
+    for k, v in sd.items():
+        n = clip_text_loader_name(k)
+        if n is None:
+            continue
+        if n in out:
+            raise ValueError(f"text encoder checkpoint: {k!r} names the tensor {n!r} a second time")
+        out[n] = v
+    return out
+
+
+def clip_text_config(cfg: dict) -> dict:
+    """Validates a text_encoder/config.json (transformers' CLIPTextConfig; its defaults fill what is absent) against what the HIP
+    executor takes and returns the fields it reads.  Every refusal names the field."""
+    c = {"vocab_size": 49408, "hidden_size": 512, "intermediate_size": 2048, "num_hidden_layers": 12, "num_attention_heads": 8,
+         "max_position_embeddings": 77, "hidden_act": "quick_gelu", "layer_norm_eps": 1e-5}
+    c.update({k: cfg[k] for k in c if k in cfg})
+    if c["hidden_act"] not in CLIP_TEXT_ACTS:
+        raise ValueError(f"text encoder: hidden_act = {c['hidden_act']!r} is not supported (quick_gelu or gelu)")
+    h, nh = int(c["hidden_size"]), int(c["num_attention_heads"])
+    if nh < 1 or h % nh != 0:
+        raise ValueError(f"text encoder: hidden_size = {h} is not a multiple of num_attention_heads = {nh}")
+    d = h // nh
+    if d % 16 != 0 or d > 128:
+        raise ValueError(f"text encoder: head dim hidden_size / num_attention_heads = {h} / {nh} = {d} must be a multiple of 16 up to 128")
+    if h % 64 != 0 or h > 2048:
+        raise ValueError(f"text encoder: hidden_size = {h} must be a multiple of 64 up to 2048 (the linears' GEMM route)")
+    if int(c["intermediate_size"]) % 64 != 0 or not 64 <= int(c["intermediate_size"]) <= 16384:
+        raise ValueError(f"text encoder: intermediate_size = {c['intermediate_size']} must be a multiple of 64 up to 16384 (the linears' GEMM route)")
+    if not 1 <= int(c["max_position_embeddings"]) <= 128:
+        raise ValueError(f"text encoder: max_position_embeddings = {c['max_position_embeddings']} must be at most 128 (one attention tile per row)")
+    return c
+
+
+def clip_text_param_shapes(cfg: dict, proj_dim: int = None) -> "OrderedDict[str, tuple]":
+    """Loader names of ldiff_textenc_load = the keys of transformers' CLIPTextModel.state_dict() (+ proj.weight / proj.bias with proj_dim)."""
+    c = clip_text_config(cfg)
+    h, it = int(c["hidden_size"]), int(c["intermediate_size"])
+    s = OrderedDict()
+    s["text_model.embeddings.token_embedding.weight"] = (int(c["vocab_size"]), h)
+    s["text_model.embeddings.position_embedding.weight"] = (int(c["max_position_embeddings"]), h)
+    for i in range(int(c["num_hidden_layers"])):
+        p = f"text_model.encoder.layers.{i}"
+        for n in CLIP_TEXT_QKV + ("out_proj",):
+            _lin(s, f"{p}.self_attn.{n}", h, h)
+        _norm(s, p + ".layer_norm1", h)
+        _lin(s, p + ".mlp.fc1", h, it)
+        _lin(s, p + ".mlp.fc2", it, h)
+        _norm(s, p + ".layer_norm2", h)
+    _norm(s, "text_model.final_layer_norm", h)
+    if proj_dim:
+        _lin(s, "proj", h, int(proj_dim))
+    return s
+
+
 def param_count(shapes) -> int:
     n = 0
     for shp in shapes.values():
@@ -245,19 +318,20 @@ def save_model_dir(path: str, cfg: dict, sd) -> None:
 
 
 def load_model_dir(path: str):
-    """Returns (config dict, state dict) from a diffusers model directory (safetensors or .bin)."""
+    """Returns (config dict, state dict) from a diffusers model directory (safetensors or .bin), or from a `transformers` one (the text
+    encoder's model.safetensors / pytorch_model.bin)."""
     with open(os.path.join(path, "config.json")) as f:
         cfg = json.load(f)
-    st = os.path.join(path, WEIGHTS_NAME)
-    if os.path.exists(st):
-        from safetensors.torch import load_file
-        sd = load_file(st)
-    else:
-        binp = os.path.join(path, "diffusion_pytorch_model.bin")
-        if not os.path.exists(binp):
-            raise FileNotFoundError(f"no {WEIGHTS_NAME} or diffusion_pytorch_model.bin in {path}")
-        sd = torch.load(binp, map_location="cpu", weights_only=True)
-    return cfg, sd
+    for name in (WEIGHTS_NAME, "model.safetensors"):
+        st = os.path.join(path, name)
+        if os.path.exists(st):
+            from safetensors.torch import load_file
+            return cfg, load_file(st)
+    for name in ("diffusion_pytorch_model.bin", "pytorch_model.bin"):
+        binp = os.path.join(path, name)
+        if os.path.exists(binp):
+            return cfg, torch.load(binp, map_location="cpu", weights_only=True)
+    raise FileNotFoundError(f"no {WEIGHTS_NAME} or diffusion_pytorch_model.bin (nor model.safetensors / pytorch_model.bin) in {path}")
 
 
 _VAE_ATTN_RENAMES = {"query": "to_q", "key": "to_k", "value": "to_v", "proj_attn": "to_out.0"}
