@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define LDIFF_VERSION 202 /* 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
+#define LDIFF_VERSION 203 /* 0.2.0.3: + ldiff_confusion (per-image confusion matrices of masks or logits against labels, accumulated on the device), ldiff_seg_metrics (host: Dice / IoU / pixel accuracy / frequency-weighted IoU from one matrix); 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
 #define LDIFF_MAX_BLOCKS 8
 
 typedef enum { LDIFF_OK = 0, LDIFF_ERR_INVALID = -1, LDIFF_ERR_RUNTIME = -2, LDIFF_ERR_STATE = -3, LDIFF_ERR_NONFINITE = -4 } ldiff_status;
@@ -318,6 +318,52 @@ int ldiff_luma_float(const void* rgb_nchw, void* gray, int B, int H, int W, void
 /* F.interpolate(x, size=(out_h,out_w), mode="bilinear", align_corners=False) on fp32 NCHW (ldiffusion.py:240,250: the decoded
  * image is resized to 64x64 before the float luma of the training-time features). */
 int ldiff_bilinear_resize(const void* x_nchw_f32, void* y_nchw_f32, int B, int C, int H, int W, int out_h, int out_w, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Metrics  --  scoring the masks where they are (utils.py:55-104, evaluate.py:11-126, segmentor.py:114-142,284-289)
+ *
+ * The reference's four metrics are functions of one integer matrix, conf[t, p] = #{pixels with target t and prediction p} (`hist` of
+ * evaluate.py:32-35).  ldiff_confusion forms it on the device in ONE launch (the reference: C^2 masked sums with an .item() each for the
+ * frequency-weighted IoU, 2C - 3C more for the other three); ldiff_seg_metrics turns C^2 integers into the figures on the host.  The matrix is
+ * exact and bitwise reproducible (integer atomics), so matrices of batches, images or ranks simply add (parallel.reduce_confusion).
+ * ---------------------------------------------------------------------------------------------- */
+/* confusion matrices, accumulated: evaluate.py:32-35 (hist), utils.py:55-104, segmentor.py:114-142
+ *   conf [B, C, C] int64, rows = targets, columns = predictions: conf[b, t, p] += count.  The call ADDS: stream batches into one matrix, zero it yourself.
+ *   dropped [B] int64 or NULL: += the pixels whose target or prediction is outside [0, C) (the reference's `==` matches no class for them: they are in no cell).
+ *         With such pixels the reference's Dice and IoU are no function of the matrix (a prediction on a pixel whose label is no class still counts there as a
+ *         false positive; here the pixel is left out of every figure): a caller who keeps an "ignore" label checks `dropped`.
+ *   pred: kind 0 = mask u8 [B, H, W]; 1 / 2 = logits [B, C, H, W] float32 / float16, arg-max taken in the kernel by ldiff_argmax_u8's rule bit for bit
+ *         (first maximal class; a pixel with any NaN or +inf logit is class 0); no mask is written.
+ *   target: kind 0 = u8 [B, H, W], 1 = int64 [B, H, W] (the reference's torch.long labels; negative or >= C: dropped).
+ *   LUTs (device, 256 x u8, or NULL): applied to the prediction (mask form only) / the u8 target before counting -- the grey levels of label PNGs to class
+ *         ids, dataset.py:10-32,48-61; an output >= C is dropped.  Any LUT beside an int64 target, or a prediction LUT beside logits: LDIFF_ERR_INVALID.
+ *   1 <= C <= 32, else LDIFF_ERR_INVALID and nothing is enqueued.  H * W and the pointers need no alignment beyond the element's own (int64: 8 bytes).
+ * Everything is enqueued on `stream`: no synchronisation, no allocation, no workspace. */
+int ldiff_confusion(const void* pred, int pred_kind /* 0 u8 mask, 1 f32 logits, 2 f16 logits */, const void* target, int target_kind /* 0 u8, 1 i64 */,
+                    const uint8_t* pred_lut_or_null, const uint8_t* target_lut_or_null, int B, int C, int H, int W, int64_t* conf, int64_t* dropped_or_null,
+                    void* stream);
+/* (Tagged like ldiff_textenc_cfg: tests/test_cpu_host.py enumerates the untagged structs; this one's mirror is _lib.SegMetricsOut, checked in tests/test_cpu_metrics.py.) */
+typedef struct ldiff_seg_metrics_out {
+  int num_classes;
+  float dice[32];        /* per class, float32 as the reference's tensor */
+  float dice_mean;       /* over all C classes */
+  double iou[32];        /* NaN where iou_skipped */
+  int iou_skipped[32];   /* 1: empty union, the reference's None */
+  double iou_mean;       /* over the classes not skipped; 1.0 if none is left */
+  double pa[32];         /* 1.0 for a class absent from the target */
+  double pa_mean;
+  float fw_iou;          /* all classes */
+  float fw_iou_fg;       /* ignore_background=True: class 0 left out, freq NOT renormalised (as the reference) */
+} ldiff_seg_metrics_out;
+/* (host) the reference's four metrics from ONE C x C matrix (rows = targets), with its rules and its arithmetic.  Python and C callers share this routine.
+ *   Dice (utils.py:55-82 = segmentor.py:114-142): a class absent from target and prediction scores 1, else 2 TP / (2 TP + FP + FN) in float32; mean over C.
+ *   IoU (utils.py:84-104): a class with an empty union is skipped; mean over the rest in double, 1.0 if none.
+ *   pixel accuracy (evaluate.py:11-27): TP / |target == c| in double, 1.0 for an absent class; mean over C.
+ *   frequency-weighted IoU (evaluate.py:29-45): float32 matrix and arithmetic, + 1e-10 in the denominator; an all-zero matrix gives what that arithmetic
+ *   gives (NaN).
+ * The reference sums float32 ones, exact only below 2^24 pixels per class; the matrix here is always exact, so beyond that the figures are those of the exact
+ * counts rounded once.  C outside [1, 32], a null pointer or a negative count: LDIFF_ERR_INVALID. */
+int ldiff_seg_metrics(const int64_t* conf_host, int C, ldiff_seg_metrics_out* out);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused sampler  --  replaces the whole per-image loop body of

@@ -47,6 +47,11 @@ class ConvArgs(C.Structure):
                 ("relu_out", C.c_int), ("cls_conv", C.c_int), ("fold_gn", C.c_int), ("act_out", C.c_int)]
 
 
+class SegMetricsOut(C.Structure):
+    _fields_ = [("num_classes", C.c_int), ("dice", C.c_float * 32), ("dice_mean", C.c_float), ("iou", C.c_double * 32), ("iou_skipped", C.c_int * 32),
+                ("iou_mean", C.c_double), ("pa", C.c_double * 32), ("pa_mean", C.c_double), ("fw_iou", C.c_float), ("fw_iou_fg", C.c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/ldiff.h declares
 P, I, F, I64, U64 = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_uint64
 SIGNATURES = {
@@ -120,6 +125,8 @@ SIGNATURES = {
     "ldiff_pndm_coeffs": (I, [F, F, C.POINTER(F), C.POINTER(F)]),
     "ldiff_laplace_add": (I, [P, F, P, U64, U64, P, I64, P]),
     "ldiff_argmax_u8": (I, [P, I, I, I, I, P, P]),
+    "ldiff_confusion": (I, [P, I, P, I, P, P, I, I, I, I, P, P, P]),
+    "ldiff_seg_metrics": (I, [C.POINTER(I64), I, C.POINTER(SegMetricsOut)]),
     "ldiff_probe_argmax_u8": (I, [P, I, I, I, I, P, P, F, I, P, P]),
     "ldiff_window_accumulate": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P]),
     "ldiff_luma_float": (I, [P, P, I, I, I, P]),

@@ -442,6 +442,13 @@ int ldiff_argmax_u8(const void* logits, int B, int C, int H, int W, void* mask_u
   launch_argmax_u8((const float*)logits, B, C, H, W, (uint8_t*)mask_u8, (hipStream_t)stream);
   API_END
 }
+int ldiff_confusion(const void* pred, int pred_kind, const void* target, int target_kind, const uint8_t* pred_lut_or_null, const uint8_t* target_lut_or_null, int B, int C, int H,
+                    int W, int64_t* conf, int64_t* dropped_or_null, void* stream) {
+  API_BEGIN
+  launch_confusion(pred, pred_kind, target, target_kind, pred_lut_or_null, target_lut_or_null, B, C, H, W, conf, dropped_or_null, (hipStream_t)stream);
+  API_END
+}
+int ldiff_seg_metrics(const int64_t* conf_host, int C, ldiff_seg_metrics_out* out) { return seg_metrics_host(conf_host, C, out); }
 int ldiff_probe_argmax_u8(const void* features_u8, int B, int N, int H, int W, const void* weight, const void* bias_or_null, float scale, int C, void* mask_u8,
                           void* stream) {
   API_BEGIN

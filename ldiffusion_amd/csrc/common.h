@@ -276,6 +276,10 @@ void launch_decode_post(const float* x, int ldx, int B, int H, int W, float* img
                         hipStream_t s);
 void launch_argmax_u8(const float* logits, int B, int C, int H, int W, uint8_t* mask, hipStream_t s);
 void launch_probe_argmax_u8(const uint8_t* feat, int B, int N, int H, int W, const float* w, const float* bias, float scale, int C, uint8_t* mask, hipStream_t s);
+// mask scoring (kernels_metrics.hip): per-image confusion matrices, accumulated; the reference's metrics from one matrix (host)
+void launch_confusion(const void* pred, int pred_kind, const void* target, int target_kind, const uint8_t* pred_lut, const uint8_t* target_lut, int B, int C, int H, int W,
+                      int64_t* conf, int64_t* dropped, hipStream_t s);
+int seg_metrics_host(const int64_t* conf, int C, ldiff_seg_metrics_out* out);
 void launch_fold_gn_weights(const f16* w, const float* bias, const float* scale, const float* shift, f16* wb, float* biasb, int B, int Nrows, int C,
                             hipStream_t s);
 void launch_bilinear_resize(const float* x, float* y, int B, int C, int H, int W, int oh, int ow, hipStream_t s);

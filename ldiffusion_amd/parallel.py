@@ -57,3 +57,18 @@ def gather_masks(local: torch.Tensor, total: int, group=None) -> torch.Tensor:
     parts = [torch.empty_like(pad) for _ in range(world)]
     dist.all_gather(parts, pad, group=group)
     return torch.cat([parts[r][: shard_range(total, r, world)[1] - shard_range(total, r, world)[0]] for r in range(world)], 0)
+
+
+def reduce_confusion(conf: torch.Tensor, group=None) -> torch.Tensor:
+    """Sum int64 confusion matrices (metrics.confusion_matrix) over the ranks with ONE all_reduce, in place: a slide sharded over ranks is scored
+    without gathering its masks (C^2 integers per image instead of H W bytes).  Integer sums: every rank ends with the same exact matrix.  The
+    identity without a process group, as `gather_masks` is."""
+    import torch.distributed as dist
+    if not dist.is_available() or not dist.is_initialized():
+        return conf
+    if conf.dtype != torch.int64:
+        raise ValueError(f"reduce_confusion sums int64 matrices, got {conf.dtype}")
+    if not conf.is_contiguous():
+        raise ValueError("reduce_confusion reduces in place and needs a contiguous tensor")
+    dist.all_reduce(conf, op=dist.ReduceOp.SUM, group=group)
+    return conf

@@ -108,6 +108,12 @@ class Segmentor:
             raise ValueError("Invalid level specified. Choose 'tissue' or 'cell'.")
         raise RuntimeError("the segmentation heads (model/conductor.py, nnU-Net) are outside the MI355X hot-path scope; pass `head=`")
 
+    def micro_dice(self, predicted_labels, true_labels, num_classes=7):
+        """segmentor.py:114-142, the figure of the validation loop (:284-289): per-class Dice over the arg-max labels and its mean, from one
+        confusion matrix counted on the device (utils.micro_dice is the same function, as in the reference)."""
+        from .utils import micro_dice
+        return micro_dice(predicted_labels, true_labels, num_classes)
+
     def load_ldiffusion(self, ldiffusion_weight, diffusion_path, text_encoder="transformers"):
         """text_encoder="hip": the prompt's CLIP pass and projection run on the library (`StableDiffusionImg2ImgPipeline.from_pretrained`)."""
         pipeline = StableDiffusionImg2ImgPipeline.from_pretrained(diffusion_path, torch_dtype=torch.float32, device=self.device, text_encoder=text_encoder)

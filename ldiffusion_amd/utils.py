@@ -1,4 +1,6 @@
-"""Mirror of the sampler call site in the reference's utils.py (nnU-Net dataset creation): `copy_or_convert_image`, sampler variant V4
+"""Mirrors of the reference's utils.py.  The mask metrics `micro_dice` (:55-82) and `mean_iou_and_per_class` (:84-104): same names, arguments and
+return shapes, computed from one confusion matrix counted on the device (ldiffusion_amd/metrics.py) instead of 2-3 masked sums and `.item()`s per class.
+The sampler call site (nnU-Net dataset creation): `copy_or_convert_image`, sampler variant V4
 (/root/reference/utils.py:176-208).  Same name, arguments and effect -- a PNG of the one-pass diffusion of the image at `dst_path`, or a plain
 copy -- with the arithmetic on the HIP kernels (no CPU fallback: the pipeline shims raise without the library or a GPU)."""
 from __future__ import annotations
@@ -9,6 +11,7 @@ import numpy as np
 import torch
 from torch import nn
 
+from . import metrics
 from .pipeline import LaplaceSampler
 
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
@@ -55,3 +58,18 @@ def copy_or_convert_image(img, src_path, dst_path, pipeline=None, unet=None, use
     rgb = out["rgb"][0].cpu().numpy()
     sampler.check_finite()   # fp16 overflow in either graph raises instead of writing a garbage PNG
     Image.fromarray(rgb).save(dst_path)
+
+
+def micro_dice(predicted_labels, true_labels, num_classes=7):
+    """utils.py:55-82 (= Segmentor.micro_dice, segmentor.py:114-142): logits [B, C, H, W] and labels [B, H, W] -> (per-class float32 tensor, its mean);
+    the whole batch is flattened together and a class absent from both prediction and labels scores 1.  One launch and one copy of C^2 integers per
+    image; the figures come back as host tensors (they are for reporting: `.item()`, `.cpu().numpy()` and arithmetic on them work as on the reference's)."""
+    m = metrics.score(predicted_labels, true_labels, num_classes)
+    return torch.from_numpy(m.dice_per_class.copy()), torch.tensor(m.dice, dtype=torch.float32)
+
+
+def mean_iou_and_per_class(pred, target, num_classes):
+    """utils.py:84-104: (mean IoU as a float, {class: IoU or None}); a class with an empty union is None and left out of the mean, which is 1.0
+    when no class is left."""
+    m = metrics.score(pred, target, num_classes)
+    return m.miou, m.iou_per_class
