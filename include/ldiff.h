@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define LDIFF_VERSION 203 /* 0.2.0.3: + ldiff_confusion (per-image confusion matrices of masks or logits against labels, accumulated on the device), ldiff_seg_metrics (host: Dice / IoU / pixel accuracy / frequency-weighted IoU from one matrix); 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
+#define LDIFF_VERSION 204 /* 0.2.0.4: + ldiff_op_in_train_fwd / _bwd (InstanceNorm + LeakyReLU with saved statistics), ldiff_op_dice_ce (nnU-Net deep-supervision loss of one scale, value and gradient), ldiff_op_sgd_nesterov_multi; 0.2.0.3: + ldiff_confusion (per-image confusion matrices of masks or logits against labels, accumulated on the device), ldiff_seg_metrics (host: Dice / IoU / pixel accuracy / frequency-weighted IoU from one matrix); 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
 #define LDIFF_MAX_BLOCKS 8
 
 typedef enum { LDIFF_OK = 0, LDIFF_ERR_INVALID = -1, LDIFF_ERR_RUNTIME = -2, LDIFF_ERR_STATE = -3, LDIFF_ERR_NONFINITE = -4 } ldiff_status;
@@ -599,6 +599,34 @@ int ldiff_op_pack_weight_multi(const void* entries, const void* tile_prefix, int
  * chunks[c] = {int32 tensor, int32 pad, int64 first element} (16 bytes): workgroup c updates elements [first, first + 16384) of its tensor. */
 int ldiff_op_adamw_multi(const void* tensors, const void* grads, const void* chunks, int64_t nchunks, float lr, float beta1, float beta2, float eps,
                          float weight_decay, int step, void* stream);
+
+/* Training form of the nnU-Net tissue head (nnUNetTrainer.train_step: PlainConvUNet forward + backward, deep-supervision loss, SGD).  The three
+ * primitives reduce through per-workgroup partial sums in a caller-supplied workspace and a finalize that adds them in a fixed order: no
+ * floating-point atomics, a replay on the same inputs is bit-identical.
+ *
+ * y = leaky_relu(instance_norm(x; gamma, beta, eps), slope) on NHWC f16 [B, HW, C], C % 8 == 0; mean / rstd f32 [B, C] are written for the backward,
+ * which takes them back, recomputes the normalised value and the activation mask from x (no mask tensor), and OVERWRITES dx (f16), dgamma, dbeta
+ * (f32 [C], summed over the batch in image order).  ws: ldiff_op_in_train_ws_bytes(B, HW, C) bytes of device memory, 16-byte aligned. */
+int64_t ldiff_op_in_train_ws_bytes(int B, int HW, int C);
+int ldiff_op_in_train_fwd(const void* x, void* y, const void* gamma, const void* beta, void* mean, void* rstd, int B, int HW, int C, float eps, float slope,
+                          void* ws, int64_t ws_bytes, void* stream);
+int ldiff_op_in_train_bwd(const void* x, const void* dy, const void* gamma, const void* beta, const void* mean, const void* rstd, void* dx, void* dgamma,
+                          void* dbeta, int B, int HW, int C, float slope, void* ws, int64_t ws_bytes, void* stream);
+/* DC_and_CE_loss with MemoryEfficientSoftDiceLoss (do_bg = False, ddp = False) of ONE deep-supervision scale, value and gradient:
+ *   logits f16 [B, HW, ld], ld = roundup(n_heads, 8) (the seg layer's output; the pad columns take no part), 2 <= n_heads <= 32;
+ *   target uint8 (target_i64 = 0) or int64 (1) [B, HW], labels in [0, n_heads) (another label makes the loss and that pixel's dlogits NaN);
+ *   p = softmax over the n_heads real columns (fp32); per foreground class c: intersect = sum p_c [t == c], sum_pred = sum p_c, sum_gt = sum [t == c]
+ *   over the pixels of a sample, and over the batch as well when batch_dice != 0;  dc = (2 intersect + smooth) / max(sum_gt + sum_pred + smooth, 1e-8);
+ *   loss[0] (f32) = mean cross-entropy - mean dc;   dlogits f16 [B, HW, ld] = grad_scale * weight * d loss / d logits, pad columns zero.
+ * grad_scale is the loss scale of the step: most of these gradients lie below float16's range unscaled.  ws: ldiff_op_dice_ce_ws_bytes(...) bytes. */
+int64_t ldiff_op_dice_ce_ws_bytes(int B, int64_t HW, int n_heads);
+int ldiff_op_dice_ce(const void* logits, int ld, int n_heads, const void* target, int target_i64, int B, int64_t HW, int batch_dice, float smooth, float weight,
+                     float grad_scale, void* loss, void* dlogits, void* ws, int64_t ws_bytes, void* stream);
+/* torch.optim.SGD(lr, momentum, nesterov=True, weight_decay) over many f32 tensors in one launch.  Device tables as ldiff_op_adamw_multi's, with
+ * tensors[t] = {float* p, float* momentum_buffer, int64 n} (24 bytes).  inv_scale / clip_coef: device f32 scalars read at execution time.
+ *   g = inv_scale * clip_coef * grad + weight_decay * p;   buf = first ? g : momentum * buf + g;   p -= lr * (g + momentum * buf) */
+int ldiff_op_sgd_nesterov_multi(const void* tensors, const void* grads, const void* chunks, int64_t nchunks, float lr, float momentum, float weight_decay,
+                                int first, const void* inv_scale, const void* clip_coef, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Live measurement for bench.py's roofline line: when enabled, every conv/linear, attention and

@@ -173,6 +173,12 @@ SIGNATURES = {
     "ldiff_op_pack_weight_multi": (I, [P, P, I, I, P]),
     "ldiff_op_adamw_multi": (I, [P, P, P, I64, F, F, F, F, F, I, P]),
     "ldiff_op_infonce": (I, [P, I, I, I64, P, P, P, P, I, P, I, F, P, P, P]),
+    "ldiff_op_in_train_ws_bytes": (I64, [I, I, I]),
+    "ldiff_op_in_train_fwd": (I, [P, P, P, P, P, P, I, I, I, F, F, P, I64, P]),
+    "ldiff_op_in_train_bwd": (I, [P, P, P, P, P, P, P, P, P, I, I, I, F, P, I64, P]),
+    "ldiff_op_dice_ce_ws_bytes": (I64, [I, I64, I]),
+    "ldiff_op_dice_ce": (I, [P, I, I, P, I, I, I64, I, F, F, F, P, P, P, I64, P]),
+    "ldiff_op_sgd_nesterov_multi": (I, [P, P, P, I64, F, F, F, I, P, P, P]),
     "ldiff_stream_create_cu_share": (I, [I, I, P]),
     "ldiff_stream_destroy": (I, [P]),
     "ldiff_vae_set_side_cu_share": (I, [P, I, I]),

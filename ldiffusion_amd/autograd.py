@@ -452,3 +452,142 @@ def adamw_step(params, grads, state, lr, betas=(0.9, 0.999), eps=1e-8, weight_de
         keep.append((gs, gptr))
     state["_tables"] = tabs
     state["_keep"] = keep   # the launches are asynchronous: the pointer tables and converted gradients must outlive them
+
+
+# ---- training form of the nnU-Net tissue head (csrc/kernels_segtrain.hip; ldiffusion_amd/nnunet_train.py) ----
+def _workspace(nbytes, device):
+    return torch.empty(max(int(nbytes), 16) // 8 + 1, dtype=torch.float64, device=device)   # 8-byte elements: the loss kernels keep double sums in it
+
+
+class InstanceNormLReLUFn(torch.autograd.Function):
+    """y = leaky_relu(instance_norm(x, gamma, beta, eps), slope) on NHWC float16 [B, H, W, C], C % 8 == 0 (ldiff_op_in_train_fwd / _bwd): the norm +
+    nonlinearity of every conv block of nnU-Net's PlainConvUNet.  mean / rstd [B, C] float32 are kept; the backward recomputes the mask from x."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps=1e-5, slope=0.01):
+        _check_act(x, "x")
+        lib = _lib.load()
+        B, H, W, Cc = x.shape
+        y = torch.empty_like(x)
+        mean = torch.empty((B, Cc), dtype=torch.float32, device=x.device)
+        rstd = torch.empty_like(mean)
+        g32, b32 = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
+        nb = lib.ldiff_op_in_train_ws_bytes(B, H * W, Cc)
+        ws = _workspace(nb, x.device)
+        _lib.check(lib.ldiff_op_in_train_fwd(x.data_ptr(), y.data_ptr(), g32.data_ptr(), b32.data_ptr(), mean.data_ptr(), rstd.data_ptr(), B, H * W, Cc,
+                                             float(eps), float(slope), ws.data_ptr(), nb, _sp()))
+        ctx.save_for_backward(x, g32, b32, mean, rstd)
+        ctx.slope = float(slope)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, g32, b32, mean, rstd = ctx.saved_tensors
+        B, H, W, Cc = x.shape
+        dy = dy.contiguous()
+        dx = torch.empty_like(x)
+        dg, db = torch.empty(Cc, dtype=torch.float32, device=x.device), torch.empty(Cc, dtype=torch.float32, device=x.device)
+        nb = lib.ldiff_op_in_train_ws_bytes(B, H * W, Cc)
+        ws = _workspace(nb, x.device)
+        _lib.check(lib.ldiff_op_in_train_bwd(x.data_ptr(), dy.data_ptr(), g32.data_ptr(), b32.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
+                                             dg.data_ptr(), db.data_ptr(), B, H * W, Cc, ctx.slope, ws.data_ptr(), nb, _sp()))
+        return dx, dg, db, None, None
+
+
+def dice_ce(logits, target, n_heads, batch_dice, weight=1.0, grad_scale=1.0, smooth=1e-5):
+    """ldiff_op_dice_ce on float16 logits [B, H, W, roundup(n_heads, 8)] and uint8 / int64 labels [B, H, W] (or [B, 1, H, W]):
+    (loss float32 0-dim, dlogits float16 = grad_scale * weight * d loss / d logits in the logits' layout).  Region labels and an ignore label are not
+    covered (nnunet.network_spec refuses them)."""
+    _check_act(logits, "logits")
+    lib = _lib.load()
+    if target.dim() == 4 and target.shape[1] == 1:
+        target = target[:, 0]
+    B, H, W, ld = logits.shape
+    if tuple(target.shape) != (B, H, W):
+        raise ValueError(f"dice_ce: target {tuple(target.shape)} does not match logits {tuple(logits.shape)}")
+    if target.dtype not in (torch.uint8, torch.int64):
+        if target.is_floating_point():   # the nnU-Net loader hands float label maps (RobustCrossEntropyLoss casts them with .long())
+            target = target.long()
+        else:
+            target = target.to(torch.int64)
+    target = target.to(logits.device).contiguous()
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    dlogits = torch.empty_like(logits)
+    nb = lib.ldiff_op_dice_ce_ws_bytes(B, H * W, int(n_heads))
+    ws = _workspace(nb, logits.device)
+    _lib.check(lib.ldiff_op_dice_ce(logits.data_ptr(), ld, int(n_heads), target.data_ptr(), int(target.dtype == torch.int64), B, H * W, int(bool(batch_dice)),
+                                    float(smooth), float(weight), float(grad_scale), loss.data_ptr(), dlogits.data_ptr(), ws.data_ptr(), nb, _sp()))
+    return loss[0], dlogits
+
+
+class DiceCeFn(torch.autograd.Function):
+    """nnU-Net's DC_and_CE_loss of one deep-supervision scale as a term of the step's loss.  forward returns `weight` * loss of the scale in float32
+    (`weight` = the scale's deep-supervision weight; the value is NOT multiplied by the loss scale).  The gradient was formed by the same call in float32
+    and stored as float16 = `grad_scale` * d(weight * loss) / d logits, because most of it lies below float16's range unscaled; backward hands out that
+    tensor times the incoming gradient (1 when the caller backpropagates the sum of the terms: the product is then the stored tensor bit for bit), so
+    `grad_scale` acts as the loss scale of this term and the caller unscales the parameter gradients by 1 / grad_scale (nnunet_train.Trainer.train_step)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, n_heads, batch_dice, weight, grad_scale, smooth=1e-5):
+        loss, dlogits = dice_ce(logits, target, n_heads, batch_dice, weight, grad_scale, smooth)
+        ctx.save_for_backward(dlogits)
+        return loss * float(weight)
+
+    @staticmethod
+    def backward(ctx, g):
+        (dlogits,) = ctx.saved_tensors
+        return (dlogits.float() * g).to(dlogits.dtype), None, None, None, None, None, None
+
+
+def sgd_nesterov_step(params, grads, state, lr, weight_decay=0.0, momentum=0.99, inv_scale=1.0, clip_coef=1.0):
+    """One torch.optim.SGD(momentum, nesterov=True, weight_decay) update of float32 CUDA parameters, in place, all tensors in one launch
+    (ldiff_op_sgd_nesterov_multi; a second launch for tensors that meet their first gradient later than the others: their buffer starts as g).
+    The gradient enters as inv_scale * clip_coef * grad: floats, or float32 device scalars (0-dim / 1-element tensors, read by the kernel).
+    As in torch, a tensor whose gradient is None is left untouched: no weight decay, no buffer.  `state` is the caller's dict: momentum buffers
+    by parameter index, the device tables."""
+    lib = _lib.load()
+    live = [(i, p, g) for i, (p, g) in enumerate(zip(params, grads)) if g is not None]
+    if not live:
+        return
+    dev = live[0][1].device
+
+    def scalar(name, v):
+        if torch.is_tensor(v):
+            if not (v.is_cuda and v.dtype == torch.float32 and v.numel() == 1):
+                raise ValueError(f"sgd_nesterov_step: {name} must be a float or a float32 CUDA scalar")
+            return v
+        return torch.tensor([float(v)], dtype=torch.float32, device=dev)
+
+    s_inv, s_clip = scalar("inv_scale", inv_scale), scalar("clip_coef", clip_coef)
+    bufs = state.setdefault("momentum_buffer", {})
+    groups = {0: [], 1: []}
+    for i, p, g in live:
+        if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
+            raise ValueError("sgd_nesterov_step: parameters must be contiguous float32 CUDA tensors")
+        first = i not in bufs
+        if first:
+            bufs[i] = torch.empty_like(p)
+        groups[int(first)].append((i, p, g))
+    old, tabs, keep = state.get("_tables") or [], [], [s_inv, s_clip]
+    for first, members in groups.items():
+        if not members:
+            continue
+        key = tuple((i, p.data_ptr(), p.numel()) for i, p, _ in members)
+        tab = next((t for t in old if t[0] == key), None)
+        if tab is None:
+            tensors, chunks = [], []
+            for t, (i, p, _) in enumerate(members):
+                tensors += [p.data_ptr(), bufs[i].data_ptr(), p.numel()]
+                for at in range(0, p.numel(), ADAMW_CHUNK):
+                    chunks += [t, at]
+            tab = (key, torch.tensor(tensors, dtype=torch.int64).to(dev), torch.tensor(chunks, dtype=torch.int64).to(dev), len(chunks) // 2)
+        tabs.append(tab)
+        gs = [g.detach().to(torch.float32).contiguous() for _, _, g in members]
+        gptr = torch.tensor([g.data_ptr() for g in gs], dtype=torch.int64).to(dev)
+        _lib.check(lib.ldiff_op_sgd_nesterov_multi(tab[1].data_ptr(), gptr.data_ptr(), tab[2].data_ptr(), tab[3], float(lr), float(momentum), float(weight_decay),
+                                                   first, s_inv.data_ptr(), s_clip.data_ptr(), _sp()))
+        keep.append((gs, gptr))
+    state["_tables"] = tabs
+    state["_keep"] = keep   # the launches are asynchronous: tables, scalars and converted gradients must outlive them
+    state["step"] = state.get("step", 0) + 1

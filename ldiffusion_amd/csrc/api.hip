@@ -1037,6 +1037,47 @@ int ldiff_op_adamw_multi(const void* tensors, const void* grads, const void* chu
                      (hipStream_t)stream);
   API_END
 }
+// ---- training form of the nnU-Net tissue head (kernels_segtrain.hip) ----
+int64_t ldiff_op_in_train_ws_bytes(int B, int HW, int Cc) {
+  if (B < 1 || HW < 1 || Cc < 8 || Cc % 8 != 0) return 0;
+  return in_train_ws_floats(B, HW, Cc) * 4;
+}
+int ldiff_op_in_train_fwd(const void* x, void* y, const void* gamma, const void* beta, void* mean, void* rstd, int B, int HW, int Cc, float eps, float slope,
+                          void* ws, int64_t ws_bytes, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(x && y && gamma && beta && mean && rstd && ws, LDIFF_ERR_INVALID, "op_in_train_fwd: null argument");
+  launch_in_train_fwd((const f16*)x, (f16*)y, (const float*)gamma, (const float*)beta, (float*)mean, (float*)rstd, B, HW, Cc, eps, slope, (float*)ws, ws_bytes,
+                      (hipStream_t)stream);
+  API_END
+}
+int ldiff_op_in_train_bwd(const void* x, const void* dy, const void* gamma, const void* beta, const void* mean, const void* rstd, void* dx, void* dgamma,
+                          void* dbeta, int B, int HW, int Cc, float slope, void* ws, int64_t ws_bytes, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(x && dy && gamma && beta && mean && rstd && dx && dgamma && dbeta && ws, LDIFF_ERR_INVALID, "op_in_train_bwd: null argument");
+  launch_in_train_bwd((const f16*)x, (const f16*)dy, (const float*)gamma, (const float*)beta, (const float*)mean, (const float*)rstd, (f16*)dx, (float*)dgamma,
+                      (float*)dbeta, B, HW, Cc, slope, (float*)ws, ws_bytes, (hipStream_t)stream);
+  API_END
+}
+int64_t ldiff_op_dice_ce_ws_bytes(int B, int64_t HW, int n_heads) {
+  if (B < 1 || HW < 1 || n_heads < 2 || n_heads > 32) return 0;
+  return dice_ce_ws_bytes(B, HW, n_heads);
+}
+int ldiff_op_dice_ce(const void* logits, int ld, int n_heads, const void* target, int target_i64, int B, int64_t HW, int batch_dice, float smooth, float weight,
+                     float grad_scale, void* loss, void* dlogits, void* ws, int64_t ws_bytes, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(logits && target && loss && dlogits && ws, LDIFF_ERR_INVALID, "op_dice_ce: null argument");
+  launch_dice_ce((const f16*)logits, ld, n_heads, target, target_i64, B, HW, batch_dice, smooth, weight, grad_scale, (float*)loss, (f16*)dlogits, ws, ws_bytes,
+                 (hipStream_t)stream);
+  API_END
+}
+int ldiff_op_sgd_nesterov_multi(const void* tensors, const void* grads, const void* chunks, int64_t nchunks, float lr, float momentum, float weight_decay,
+                                int first, const void* inv_scale, const void* clip_coef, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(nchunks >= 0 && inv_scale && clip_coef && (nchunks == 0 || (tensors && grads && chunks)), LDIFF_ERR_INVALID, "op_sgd_nesterov_multi: bad arguments");
+  launch_sgd_nesterov_multi((const SgdTensor*)tensors, (const float* const*)grads, (const AdamChunk*)chunks, nchunks, lr, momentum, weight_decay, first,
+                            (const float*)inv_scale, (const float*)clip_coef, (hipStream_t)stream);
+  API_END
+}
 int ldiff_op_geglu(const void* x, void* y, int64_t M, int C4, void* stream) {
   API_BEGIN
   LDIFF_CHECK(x && y, LDIFF_ERR_INVALID, "op_geglu: null argument");

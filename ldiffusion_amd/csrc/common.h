@@ -314,6 +314,18 @@ void launch_adamw_multi(const AdamTensor* tensors, const float* const* grads, co
 void launch_infonce(const float* feat, int B, int n, long long HW, const int* bi, const int* ai, const int* pi, const int* ni, int T, const int* t_dev, int K,
                     float temperature, float* loss, float* dfeat, hipStream_t s);   // contrastive loss over given sample triples + its gradient (kernels_bwd.hip)
 void launch_adamw(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, float wd, int step, hipStream_t s);
+// training form of the nnU-Net tissue head (kernels_segtrain.hip): InstanceNorm + LeakyReLU with saved statistics, Dice + cross-entropy, Nesterov SGD
+long long in_train_ws_floats(int B, int HW, int C);
+void launch_in_train_fwd(const f16* x, f16* y, const float* gamma, const float* beta, float* mean, float* rstd, int B, int HW, int C, float eps, float slope,
+                         float* ws, long long ws_bytes, hipStream_t s);
+void launch_in_train_bwd(const f16* x, const f16* dy, const float* gamma, const float* beta, const float* mean, const float* rstd, f16* dx, float* dgamma,
+                         float* dbeta, int B, int HW, int C, float slope, float* ws, long long ws_bytes, hipStream_t s);
+long long dice_ce_ws_bytes(int B, long long HW, int n_heads);
+void launch_dice_ce(const f16* logits, int ld, int n_heads, const void* target, int target_i64, int B, long long HW, int batch_dice, float smooth, float weight,
+                    float grad_scale, float* loss, f16* dlogits, void* ws, long long ws_bytes, hipStream_t s);
+struct SgdTensor { float* p; float* buf; long long n; };
+void launch_sgd_nesterov_multi(const SgdTensor* tensors, const float* const* grads, const AdamChunk* chunks, long long nchunks, float lr, float momentum, float wd,
+                               int first, const float* inv_scale, const float* clip_coef, hipStream_t s);
 
 // ---- device arena: bump/free-list allocator over one hipMalloc'd slab ------------------------
 // No hipMalloc/hipFree in a forward pass (graph-capturable, no implicit syncs).  Stream-ordered reuse:

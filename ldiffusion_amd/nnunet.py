@@ -108,8 +108,10 @@ def network_spec(plans: dict, configuration_name: str, dataset_json: dict) -> di
                 n_heads=len(labels), patch_size=tuple(patch), normalization_schemes=schemes)
 
 
-def param_shapes(spec: dict) -> Dict[str, Tuple[int, ...]]:
-    """name -> shape of every tensor the handle expects (the canonical names of a PlainConvUNet state dict; see the module docstring: unpinned)."""
+def param_shapes(spec: dict, deep_supervision: bool = False) -> Dict[str, Tuple[int, ...]]:
+    """name -> shape of every tensor the handle expects (the canonical names of a PlainConvUNet state dict; see the module docstring: unpinned).
+    deep_supervision: also the heads of the lower decoder stages, `decoder.seg_layers.0 .. n_stages - 3` (stage j ends at width features[n - 2 - j]):
+    what the network holds while it trains (nnunet_train) and what a checkpoint's `network_weights` lists."""
     out: Dict[str, Tuple[int, ...]] = {}
     f, n = spec["features"], spec["n_stages"]
 
@@ -132,8 +134,9 @@ def param_shapes(spec: dict) -> Dict[str, Tuple[int, ...]]:
         for i in range(spec["n_conv_decoder"][j]):
             block(f"decoder.stages.{j}.convs.{i}", cin, skip)
             cin = skip
-    out[f"decoder.seg_layers.{n - 2}.weight"] = (spec["n_heads"], f[0], 1, 1)
-    out[f"decoder.seg_layers.{n - 2}.bias"] = (spec["n_heads"],)
+    for j in (range(n - 1) if deep_supervision else (n - 2,)):
+        out[f"decoder.seg_layers.{j}.weight"] = (spec["n_heads"], f[n - 2 - j], 1, 1)
+        out[f"decoder.seg_layers.{j}.bias"] = (spec["n_heads"],)
     return out
 
 
@@ -267,6 +270,17 @@ def read_trained_model_folder(model_dir: str, fold=0, checkpoint_name: str = "ch
     sd = clean_state_dict(ckpt["network_weights"], spec)
     check_state_dict(sd, spec)
     return spec, sd, ckpt.get("inference_allowed_mirroring_axes")
+
+
+def write_trained_model_folder(path: str, plans: dict, dataset_json: dict) -> str:
+    """The two JSON files nnU-Net keeps beside `fold_0/` in a trained-model folder (nnUNetTrainer.__init__ / run_training: plans.json, dataset.json);
+    the checkpoints themselves are written by nnunet_train.Trainer.save_checkpoint.  Returns `path`."""
+    os.makedirs(os.path.join(path, "fold_0"), exist_ok=True)
+    with open(os.path.join(path, "dataset.json"), "w") as f:
+        json.dump(dataset_json, f, indent=4)
+    with open(os.path.join(path, "plans.json"), "w") as f:
+        json.dump(plans, f, indent=4)
+    return path
 
 
 def load_trained_model_folder(model_dir: str, fold=0, checkpoint_name: str = "checkpoint_best.pth", device=None) -> TrainedModel:

@@ -1,0 +1,309 @@
+"""Training the nnU-Net v2 tissue head on the HIP library: what `Segmentor.train_tissue_model_nnUNetv2` (/root/reference/segmentor.py:163-241) has
+nnUNetTrainer do, from a batch to `fold_0/checkpoint_best.pth` -- the file `nnunet.load_trained_model_folder` reads.
+
+Per step (nnUNetTrainer.train_step, nnUNetTrainer.py:883-913):
+    outputs = network(data)                       PlainConvUNet with deep supervision: one head per decoder stage          TrainableSegNet
+    l = sum_i w_i * DC_and_CE(outputs[i], target[i])   w = 1 / 2^i, the last 0, normalised (:364-372)                      ag.DiceCeFn (ldiff_op_dice_ce)
+    scaler.scale(l).backward()                    conv dgrad / wgrad on the forward kernels, InstanceNorm + LeakyReLU backward      ag.Conv2dFn, ag.InstanceNormLReLUFn
+    unscale, clip_grad_norm_(12), SGD(0.99, nesterov), scaler.update()                                                      train.finish_step + ag.sgd_nesterov_step
+Every contraction, normalisation, activation, loss term and parameter update runs in libldiff_hip.so; torch provides the tape, the channel concat, the
+depth-to-space permute behind the transposed conv's GEMM and the global gradient norm.
+
+Not here: nnU-Net's planner, preprocessing and augmentation (the trainer takes batches: `data` [B, C, H, W] float32 and `target`, the
+list the nnU-Net loader supplies, one label map per deep-supervision scale, highest resolution first), DDP, a captured-graph step, ResidualEncoderUNet,
+region labels and an ignore label.
+"""
+from __future__ import annotations
+
+import math
+import os
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import autograd as ag
+from . import metrics, nnunet, train
+
+EPS = 1e-5              # InstanceNorm2d eps (get_network_from_plans: norm_op_kwargs)
+SLOPE = 0.01            # LeakyReLU negative_slope, ditto
+MOMENTUM = 0.99         # nnUNetTrainer.configure_optimizers (:469-473)
+CLIP_NORM = 12.0        # nnUNetTrainer.train_step (:905)
+SMOOTH = 1e-5           # nnUNetTrainer._build_loss (:357-359)
+
+
+def deep_supervision_weights(n: int) -> List[float]:
+    """nnUNetTrainer._build_loss (:364-372): 1 / 2^i for the n outputs, the lowest resolution 0, normalised to sum 1."""
+    if n < 1:
+        raise ValueError("deep_supervision_weights: at least one output")
+    w = np.array([1 / (2 ** i) for i in range(n)])
+    if n > 1:
+        w[-1] = 0
+    w = w / w.sum()
+    return [float(v) for v in w]
+
+
+def poly_lr(epoch: int, initial_lr: float, num_epochs: int, exponent: float = 0.9) -> float:
+    """PolyLRScheduler.step (polylr.py:18)."""
+    return initial_lr * (1 - epoch / num_epochs) ** exponent
+
+
+def initial_state_dict(spec: dict, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """A fresh network as nnU-Net initialises it (InitWeights_He(1e-2): kaiming_normal_(a = 0.01) on every conv / transposed conv, zero biases; norm
+    weights 1, biases 0), from a seeded CPU generator."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for name, shape in nnunet.param_shapes(spec, deep_supervision=True).items():
+        if name.endswith(".norm.weight"):
+            sd[name] = torch.ones(shape)
+        elif name.endswith(".bias"):
+            sd[name] = torch.zeros(shape)
+        else:
+            fan_in = shape[1] * shape[2] * shape[3]
+            sd[name] = torch.randn(shape, generator=g) * math.sqrt(2.0 / ((1 + 0.01 ** 2) * fan_in))
+    return sd
+
+
+class TrainableSegNet(train._Graph):
+    """nnU-Net's 2-D PlainConvUNet with deep supervision on the tape: float32 master parameters under the canonical names
+    (`nnunet.param_shapes(spec, deep_supervision=True)`), NHWC float16 activations.  `net(x [B, C, H, W] float32)` returns the heads' logits as
+    UNetDecoder does with deep supervision on, highest resolution first: n_stages - 1 tensors [B, h, w, roundup(n_heads, 8)] float16 in the layout
+    ag.DiceCeFn reads (pad columns zero).  Lower heads missing from `state_dict` (an inference checkpoint cleaned by nnunet.clean_state_dict) start
+    from `initial_state_dict`'s values."""
+
+    def __init__(self, spec: dict, state_dict, device="cuda:0", slope: float = SLOPE):
+        self.spec = dict(spec)
+        self.slope = float(slope)
+        want = nnunet.param_shapes(spec, deep_supervision=True)
+        sd = dict(state_dict)
+        unexpected = [k for k in sd if k not in want]
+        if unexpected:
+            raise ValueError(f"unexpected tensors in the state dict: {unexpected[:5]}")
+        fresh = None
+        for k, shape in want.items():
+            if k not in sd:
+                if not k.startswith("decoder.seg_layers."):
+                    raise RuntimeError(f"nnU-Net tensor {k} missing from the state dict")
+                fresh = fresh if fresh is not None else initial_state_dict(spec)
+                sd[k] = fresh[k]
+            if tuple(sd[k].shape) != tuple(shape):
+                raise ValueError(f"load({k}): shape {list(sd[k].shape)} does not match expected {list(shape)}")
+        super().__init__({k: sd[k] for k in want}, device, True)
+
+    def block(self, name, x, stride):
+        y = self.conv(name + ".conv", x, stride)
+        return ag.InstanceNormLReLUFn.apply(y, self.p[name + ".norm.weight"], self.p[name + ".norm.bias"], EPS, self.slope)
+
+    def tconv(self, name, x):
+        """ConvTranspose2d(kernel = stride = 2) as the GEMM tconv2x2_kernel states: y[b, 2i + di, 2j + dj, co] = sum_ci x[b, i, j, ci] W[ci, co, di, dj] + bias[co],
+        i.e. a linear layer with the weight viewed as [(di, dj, co), ci], then the 2 x 2 depth-to-space permute; the bias enters once per output pixel."""
+        w, b = self.p[name + ".weight"], self.p[name + ".bias"]
+        cin, cout = w.shape[0], w.shape[1]
+        B, H, W, _ = x.shape
+        y = ag.linear(x, w.permute(2, 3, 1, 0).reshape(4 * cout, cin), b.repeat(4))
+        return y.view(B, H, W, 2, 2, cout).permute(0, 1, 3, 2, 4, 5).reshape(B, 2 * H, 2 * W, cout)
+
+    def __call__(self, x, heads: str = "all"):
+        sp = self.spec
+        if x.dim() != 4 or x.shape[1] != sp["in_channels"]:
+            raise ValueError(f"TrainableSegNet: input must be [B, {sp['in_channels']}, h, w], got {list(x.shape)}")
+        div = 1
+        for st in sp["strides"]:
+            div *= st
+        if x.shape[2] % div or x.shape[3] % div:
+            raise ValueError(f"TrainableSegNet: input {list(x.shape[2:])} is not divisible by the product of the strides, {div}")
+        n = sp["n_stages"]
+        with torch.cuda.device(self.device):
+            h = train._nhwc16(x.to(self.device, torch.float32))
+            skips = []
+            for s in range(n):
+                for i in range(sp["n_conv_encoder"][s]):
+                    h = self.block(f"encoder.stages.{s}.0.convs.{i}", h, sp["strides"][s] if i == 0 else 1)
+                skips.append(h)
+            outs = []
+            for j in range(n - 1):
+                up = self.tconv(f"decoder.transpconvs.{j}", h)
+                h = torch.cat((up, skips[n - 2 - j]), -1)
+                for i in range(sp["n_conv_decoder"][j]):
+                    h = self.block(f"decoder.stages.{j}.convs.{i}", h, 1)
+                if heads == "all" or j == n - 2:
+                    outs.append(self.conv(f"decoder.seg_layers.{j}", h))
+        return outs[::-1]
+
+    @torch.no_grad()
+    def eval_logits(self, x):
+        """The full-resolution head only: [B, n_heads, H, W] float32 (what the network returns with deep supervision off)."""
+        out = self(x, heads="top")[0]
+        return out[..., :self.spec["n_heads"]].permute(0, 3, 1, 2).float().contiguous()
+
+    def state_dict(self):
+        return {k: v.detach().to("cpu").clone() for k, v in self.p.items()}
+
+
+def _batch(b):
+    if isinstance(b, dict):
+        return b["data"], b["target"]
+    return b[0], b[1]
+
+
+class _Stream:
+    """next() over an iterator, or over an iterable that is started again when it runs out (a list of batches)."""
+
+    def __init__(self, src):
+        self.src, self.it = src, iter(src)
+
+    def __next__(self):
+        try:
+            return next(self.it)
+        except StopIteration:
+            self.it = iter(self.src)
+            return next(self.it)
+
+
+class Trainer:
+    """nnUNetTrainer for the covered architecture.  `spec` = nnunet.network_spec(...); `state_dict` the starting weights (`initial_state_dict`);
+    `batch_dice` = the plans' `batch_dice` of the configuration (ConfigurationManager.batch_dice: the 2-D configuration sets it)."""
+
+    def __init__(self, spec: dict, state_dict, batch_dice: bool, num_epochs: int, initial_lr: float = 1e-2, weight_decay: float = 3e-5, device="cuda:0", *,
+                 configuration: str = "2d", init_args: Optional[dict] = None, mirror_axes: Optional[Sequence[int]] = (0, 1), loss_scale: Optional[float] = None,
+                 slope: float = SLOPE):
+        self.spec = dict(spec)
+        self.network = TrainableSegNet(spec, state_dict, device, slope)
+        self.device = self.network.device
+        self.batch_dice = bool(batch_dice)
+        self.num_epochs, self.initial_lr, self.weight_decay = int(num_epochs), float(initial_lr), float(weight_decay)
+        self.n_heads = int(spec["n_heads"])
+        self.weights = deep_supervision_weights(spec["n_stages"] - 1)
+        self.names = [k for k, _ in self.network.named_parameters()]
+        self.params = self.network.parameters()
+        self.state = {"loss_scale": float(loss_scale if loss_scale is not None else train.LOSS_SCALE), "sgd": {}}
+        self.current_epoch = 0
+        self._best_ema = None
+        self.log: Dict[str, list] = {"train_losses": [], "val_losses": [], "mean_fg_dice": [], "ema_fg_dice": [], "dice_per_class_or_region": [], "lrs": []}
+        self.init_args = dict(init_args) if init_args is not None else {"configuration": configuration, "fold": 0}
+        self.init_args.setdefault("configuration", configuration)
+        self.inference_allowed_mirroring_axes = None if mirror_axes is None else tuple(int(a) for a in mirror_axes)
+        self._scale_t = torch.ones(1, dtype=torch.float32, device=self.device)
+        self._clip_t = torch.ones(1, dtype=torch.float32, device=self.device)
+        self.last_grad_norm = None
+        self._inv_scale = 1.0
+
+    def lr(self, epoch: Optional[int] = None) -> float:
+        return poly_lr(self.current_epoch if epoch is None else epoch, self.initial_lr, self.num_epochs)
+
+    def eval_logits(self, x):
+        return self.network.eval_logits(x)
+
+    def _targets(self, targets, n):
+        if torch.is_tensor(targets):
+            targets = [targets]
+        if len(targets) < n:
+            raise ValueError(f"the loss takes one label map per deep-supervision scale: {n} expected, {len(targets)} given (the loader's job)")
+        return list(targets)
+
+    def loss(self, outputs, targets, grad_scale: float = 1.0):
+        """DeepSupervisionWrapper(DC_and_CE_loss): sum_i w_i loss_i over the scales whose weight is not 0 (a zero-weight scale is skipped, not multiplied:
+        its head receives no gradient at all)."""
+        targets = self._targets(targets, len(outputs))
+        total = None
+        for o, t, w in zip(outputs, targets, self.weights):
+            if w == 0.0:
+                continue
+            term = ag.DiceCeFn.apply(o, t, self.n_heads, self.batch_dice, w, grad_scale, SMOOTH)   # the weighted term
+            total = term if total is None else total + term
+        return total
+
+    def _update(self, params, grads, opt_state, lr, weight_decay):
+        """What follows a finite backward pass: clip_grad_norm_'s coefficient (torch: max_norm / (norm + 1e-6), at most 1) from the global norm of the
+        UNSCALED gradients -- train.finish_step has just taken the norm of the scaled ones for its overflow test and left it in the state, so no second
+        pass over the gradients -- and the update: the kernel reads 1 / scale and the coefficient as device scalars, the gradients are not rewritten."""
+        norm = float(opt_state["grad_norm"]) * self._inv_scale
+        self.last_grad_norm = norm
+        self._clip_t.fill_(min(1.0, CLIP_NORM / (norm + 1e-6)))
+        ag.sgd_nesterov_step(params, grads, opt_state["sgd"], lr, weight_decay, MOMENTUM, self._scale_t, self._clip_t)
+
+    def train_step(self, data, targets) -> float:
+        """One step; returns the loss.  A non-finite gradient norm (a float16 activation gradient overflowed under the loss scale) skips the update and
+        halves the scale, a run of finite steps doubles a lowered scale again: train.finish_step's rule, which this calls."""
+        for p in self.params:
+            p.grad = None
+        scale = float(self.state["loss_scale"])
+        with torch.cuda.device(self.device):
+            outputs = self.network(data)
+            total = self.loss(outputs, targets, scale)
+            total.backward()
+            self._inv_scale = 1.0 / scale
+            self._scale_t.fill_(self._inv_scale)
+            train.finish_step(self.params, self.state, self.lr(), self.weight_decay, None, update=self._update)
+        value = float(total.detach())
+        if math.isnan(value):   # the update was skipped: a NaN loss comes with NaN gradients (ldiff_op_dice_ce poisons them)
+            raise ValueError("train_step: the loss is NaN -- a label outside [0, n_heads) (torch's cross_entropy raises there too) or non-finite logits")
+        return value
+
+    @torch.no_grad()
+    def validation_step(self, data, targets) -> dict:
+        """nnUNetTrainer.validation_step (:915-989) for plain labels: the loss, and per foreground class tp / fp / fn of the full-resolution arg-max, from
+        metrics' confusion kernel (rows = targets, columns = predictions)."""
+        with torch.cuda.device(self.device):
+            outputs = self.network(data)
+            tl = self._targets(targets, 1)
+            loss = float(self.loss(outputs, tl)) if len(tl) >= len(outputs) else float("nan")
+            top = tl[0]
+            if top.dim() == 4:
+                top = top[:, 0]
+            if top.is_floating_point():
+                top = top.long()
+            logits = outputs[0][..., :self.n_heads].permute(0, 3, 1, 2).contiguous()
+            conf = metrics.confusion_matrix(logits, top.to(self.device), self.n_heads).sum(0).cpu().numpy()
+        tp = np.diag(conf)
+        fp, fn = conf.sum(0) - tp, conf.sum(1) - tp
+        return {"loss": loss, "tp_hard": tp[1:], "fp_hard": fp[1:], "fn_hard": fn[1:]}
+
+    def on_validation_epoch_end(self, val_outputs: List[dict]) -> float:
+        """:991-1025 and nnunet_logger.py:50-51: global Dice per class from the summed counts, its nan-mean, and the 0.9 / 0.1 EMA."""
+        tp = np.sum([o["tp_hard"] for o in val_outputs], 0)
+        fp = np.sum([o["fp_hard"] for o in val_outputs], 0)
+        fn = np.sum([o["fn_hard"] for o in val_outputs], 0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            per_class = [float(v) for v in 2 * tp / (2 * tp + fp + fn)]
+        mean_fg_dice = float(np.nanmean(per_class))
+        ema = self.log["ema_fg_dice"][-1] * 0.9 + 0.1 * mean_fg_dice if self.log["ema_fg_dice"] else mean_fg_dice
+        self.log["mean_fg_dice"].append(mean_fg_dice)
+        self.log["ema_fg_dice"].append(ema)
+        self.log["dice_per_class_or_region"].append(per_class)
+        self.log["val_losses"].append(float(np.mean([o["loss"] for o in val_outputs])))
+        return mean_fg_dice
+
+    def save_checkpoint(self, filename: str) -> None:
+        """The dictionary nnUNetTrainer.save_checkpoint writes (:1056-1077)."""
+        bufs = self.state["sgd"].get("momentum_buffer", {})
+        opt = {"state": {i: {"momentum_buffer": b.detach().cpu().clone()} for i, b in bufs.items()},
+               "param_groups": [{"lr": self.lr(), "momentum": MOMENTUM, "dampening": 0, "weight_decay": self.weight_decay, "nesterov": True,
+                                 "maximize": False, "foreach": None, "differentiable": False, "initial_lr": self.initial_lr,
+                                 "params": list(range(len(self.params)))}]}
+        scaler = {"scale": float(self.state["loss_scale"]), "growth_factor": 2.0, "backoff_factor": 0.5, "growth_interval": train.LOSS_SCALE_GROWTH_INTERVAL,
+                  "_growth_tracker": int(self.state.get("finite_steps", 0))}
+        os.makedirs(os.path.dirname(os.path.abspath(filename)), exist_ok=True)
+        torch.save({"network_weights": self.network.state_dict(), "optimizer_state": opt, "grad_scaler_state": scaler, "logging": dict(self.log),
+                    "_best_ema": self._best_ema, "current_epoch": self.current_epoch + 1, "init_args": self.init_args, "trainer_name": "nnUNetTrainer",
+                    "inference_allowed_mirroring_axes": self.inference_allowed_mirroring_axes}, filename)
+
+    def run_training(self, train_batches, val_batches, output_folder: str, iterations_per_epoch: int = 250, val_iterations: int = 50) -> dict:
+        """nnUNetTrainer.run_training (:1272-1297): per epoch `iterations_per_epoch` train steps, `val_iterations` validation steps, `checkpoint_best.pth`
+        whenever the EMA of the mean foreground Dice reaches a new best (:1046-1049), `checkpoint_final.pth` at the end (:853).  Batches: dicts with
+        `data` / `target` (the nnU-Net loader's) or pairs.  `output_folder` is the fold's folder (`<model folder>/fold_0`).  Returns the log."""
+        tr, va = _Stream(train_batches), _Stream(val_batches)
+        while self.current_epoch < self.num_epochs:
+            self.log["lrs"].append(self.lr())
+            losses = [self.train_step(*_batch(next(tr))) for _ in range(iterations_per_epoch)]
+            self.log["train_losses"].append(float(np.mean(losses)))
+            self.on_validation_epoch_end([self.validation_step(*_batch(next(va))) for _ in range(val_iterations)])
+            ema = self.log["ema_fg_dice"][-1]
+            if self._best_ema is None or ema > self._best_ema:
+                self._best_ema = ema
+                self.save_checkpoint(os.path.join(output_folder, "checkpoint_best.pth"))
+            self.current_epoch += 1
+        self.current_epoch -= 1   # save_checkpoint stores current_epoch + 1; on_train_end runs after the last on_epoch_end's increment (:853)
+        self.save_checkpoint(os.path.join(output_folder, "checkpoint_final.pth"))
+        self.current_epoch += 1
+        return self.log

@@ -424,6 +424,7 @@ def finish_step(params, opt_state, lr, weight_decay, max_grad_norm, optimizer=No
     else:
         allreduce_gradients(params)
         total = clip_grad_norm(params, max_grad_norm)
+    opt_state["grad_norm"] = total   # of the gradients as the backward pass left them (before clipping, at the loss scale): an `update` callback reuses it
     if not math.isfinite(total):
         opt_state["skipped_steps"] = opt_state.get("skipped_steps", 0) + 1
         opt_state["loss_scale"] = max(1.0, opt_state.get("loss_scale", LOSS_SCALE) * 0.5)
