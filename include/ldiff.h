@@ -32,6 +32,16 @@
  *     The cure for the VAE decoder is ldiff_vae_set_range_shift(vae, k): the decoder then stores its residual stream, and every conv output that feeds
  *     a GroupNorm, times 2^-k, and every decoder GroupNorm uses eps * 4^-k.  GroupNorm is scale-invariant and a power of two is exact, so the shifted
  *     graph computes the unshifted one's numbers (up to values that fall into fp16's subnormals), in a range 2^k times wider.
+ *   - The load contract.  Every ldiff_<family>_load(handle, name, host_ptr, dtype, shape, ndim) takes ONE checkpoint tensor as the checkpoint states it:
+ *     the family's checkpoint key, host memory in the torch layout, dtype LDIFF_F32 / LDIFF_F16 / LDIFF_BF16, its torch shape.  The library converts it
+ *     to the layout its kernels read and copies it; `host_ptr` is not retained.  Refused with LDIFF_ERR_INVALID and a message: a null argument, another
+ *     dtype code ("unsupported dtype"), a name the handle does not expect ("unexpected tensor name"), a shape other than the expected one ("shape [..]
+ *     does not match expected [..]").  The shape must match extent by extent, except for conv / linear weights of the UNet, ControlNet, VAE, nnU-Net head
+ *     and text encoder, where the element count and the first two extents must match and the rank is 4, or 2 for a 1x1 (checkpoints in circulation hold
+ *     the same attention projection as [C, C] and as [C, C, 1, 1]).  Tensors may be loaded in any order and again at any time: a reload of a tensor waits
+ *     for the device first (earlier forwards may still read it), and the next forward uses the new values (derived weight layouts and captured graphs are
+ *     rebuilt).  ldiff_<family>_missing(handle) counts the expected tensors not loaded yet, in the handle's registration order, and
+ *     ldiff_<family>_missing_name(handle, i) names entry i of the list the last _missing call made; a forward with tensors missing is LDIFF_ERR_STATE.
  */
 #ifndef LDIFF_H
 #define LDIFF_H
@@ -71,7 +81,7 @@ typedef struct {
 } ldiff_unet_cfg;
 
 int ldiff_unet_create(ldiff_unet** out, const ldiff_unet_cfg* cfg, int device);
-/* Copy one tensor of diffusion_pytorch_model.safetensors (diffusers key names, torch layouts) to the device.
+/* One tensor of diffusion_pytorch_model.safetensors (diffusers key names): "The load contract" above.
  * (from_pretrained: segmentor.py:79, ldiffusion.py:67) */
 int ldiff_unet_load(ldiff_unet*, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim);
 /* Storage policy of the graph (the reference computes in fp32: ldiffusion.py:67; every MFMA operand here is fp16):
@@ -116,7 +126,7 @@ void ldiff_unet_destroy(ldiff_unet*);
 typedef struct ldiff_controlnet ldiff_controlnet;
 int ldiff_controlnet_create(ldiff_controlnet** out, const ldiff_unet_cfg* trunk_cfg, int conditioning_channels, const int* embedding_channels, int n_embedding,
                             int device);
-int ldiff_controlnet_load(ldiff_controlnet*, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim);
+int ldiff_controlnet_load(ldiff_controlnet*, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim); /* "The load contract" above */
 int ldiff_controlnet_missing(ldiff_controlnet*);
 const char* ldiff_controlnet_missing_name(ldiff_controlnet*, int i);
 int ldiff_controlnet_set_precision(ldiff_controlnet*, int mode);   /* as ldiff_unet_set_precision; default 1 */
@@ -158,7 +168,7 @@ int ldiff_unet_attach_controlnet(ldiff_unet*, ldiff_controlnet* cn_or_null, floa
 typedef struct ldiff_segnet ldiff_segnet;
 int ldiff_segnet_create(ldiff_segnet** out, int in_channels, int n_stages, const int* features, const int* strides, const int* n_conv_encoder,
                         const int* n_conv_decoder /* n_stages - 1 entries */, int n_heads, int device);
-int ldiff_segnet_load(ldiff_segnet*, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim);
+int ldiff_segnet_load(ldiff_segnet*, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim); /* "The load contract" above */
 int ldiff_segnet_missing(ldiff_segnet*);
 const char* ldiff_segnet_missing_name(ldiff_segnet*, int i);
 /* as ldiff_unet_set_graph: the launch sequence of a (B, H, W, out dtype) configuration is captured on its second use and replayed afterwards */
@@ -186,7 +196,7 @@ void ldiff_segnet_destroy(ldiff_segnet*);
  * ---------------------------------------------------------------------------------------------- */
 typedef struct ldiff_resnet ldiff_resnet;
 int ldiff_resnet_create(ldiff_resnet** out, const int* layers /* 4 entries */, int width /* % 16 == 0 */, int adapter_channels /* % 16 == 0 */, int num_classes /* >= 2 */, int device);
-int ldiff_resnet_load(ldiff_resnet*, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim);
+int ldiff_resnet_load(ldiff_resnet*, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim); /* "The load contract" above */
 int ldiff_resnet_missing(ldiff_resnet*);
 const char* ldiff_resnet_missing_name(ldiff_resnet*, int i);
 /* as ldiff_segnet_set_graph: the launch sequence of a (B, S) configuration is captured on its second use and replayed afterwards */
@@ -223,7 +233,7 @@ typedef struct ldiff_textenc_cfg {
 } ldiff_textenc_cfg;
 /* (CLIPTextModel.from_pretrained: the reference's pipeline loader, segmentor.py:77-80, ldiffusion.py:67-69) */
 int ldiff_textenc_create(ldiff_textenc** out, const ldiff_textenc_cfg* cfg, int device);
-int ldiff_textenc_load(ldiff_textenc*, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim);
+int ldiff_textenc_load(ldiff_textenc*, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim); /* "The load contract" above */
 int ldiff_textenc_missing(ldiff_textenc*);
 const char* ldiff_textenc_missing_name(ldiff_textenc*, int i);
 /* as ldiff_unet_set_graph: the launch sequence of a (B, L, project, out_dtype) configuration is captured on its second use and replayed afterwards; the ids pass
@@ -253,7 +263,7 @@ typedef struct {
 } ldiff_vae_cfg;
 
 int ldiff_vae_create(ldiff_vae** out, const ldiff_vae_cfg* cfg, int device);
-int ldiff_vae_load(ldiff_vae*, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim);
+int ldiff_vae_load(ldiff_vae*, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim); /* "The load contract" above */
 /* storage policy of the encoder and of the decoder graph (see ldiff_unet_set_precision); defaults: encoder 2 (its error is
  * inherited by every later pass of the sampler and it runs once per patch), decoder 0 (its output is only consumed as uint8
  * images / luma, never fed back into the latents: measured at SD-v1.5 width, 512x512, 5 passes, the luma features are within one

@@ -35,6 +35,21 @@ template <class H> static int device_of(const H* h) { return h->device; }
 static int device_of(const ldiff_controlnet* c) { return c->trunk.device; }
 template <class H> static NonFiniteFlag& flag_of(H* h) { return h->nf; }
 static NonFiniteFlag& flag_of(ldiff_controlnet* c) { return c->trunk.nf; }
+template <class H> static WeightStore& store_of(H* h) { return h->ws; }
+static WeightStore& store_of(ldiff_controlnet* c) { return c->trunk.ws; }
+// *_load (the contract: model.h, WeightStore): the classifier and the text encoder have a step of their own in front of the store's
+template <class H> static void load_into(H* h, const char* name, const void* host, int dtype, const int64_t* shape, int ndim) { store_of(h).load(name, host, dtype, shape, ndim); }
+static void load_into(ldiff_resnet* r, const char* name, const void* host, int dtype, const int64_t* shape, int ndim) { r->load(name, host, dtype, shape, ndim); }
+static void load_into(ldiff_textenc* t, const char* name, const void* host, int dtype, const int64_t* shape, int ndim) { t->load(name, host, dtype, shape, ndim); }
+template <class H> static int load(H* h, const char* who, const char* name, const void* host, int dtype, const int64_t* shape, int ndim) {
+  API_BEGIN
+  LDIFF_CHECK(h, LDIFF_ERR_INVALID, "%s: null handle", who);
+  HIP_CHECK(hipSetDevice(device_of(h)));
+  load_into(h, name, host, dtype, shape, ndim);
+  API_END
+}
+template <class H> static int missing(H* h) { return h ? store_of(h).missing() : -1; }
+template <class H> static const char* missing_name(H* h, int i) { return h ? store_of(h).missing_name(i) : ""; }
 
 static void select_device(const char* who, int device) {   // of a *_create
   int ndev = 0;
@@ -87,13 +102,7 @@ int ldiff_unet_create(ldiff_unet** out, const ldiff_unet_cfg* cfg, int device) {
   *out = u;
   API_END
 }
-int ldiff_unet_load(ldiff_unet* u, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
-  API_BEGIN
-  LDIFF_CHECK(u, LDIFF_ERR_INVALID, "unet_load: null handle");
-  HIP_CHECK(hipSetDevice(u->device));
-  u->ws.load(name, host_ptr, dtype, shape, ndim);
-  API_END
-}
+int ldiff_unet_load(ldiff_unet* u, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) { return load(u, "unet_load", name, host_ptr, dtype, shape, ndim); }
 int ldiff_unet_set_precision(ldiff_unet* u, int mode) {
   API_BEGIN
   LDIFF_CHECK(u && mode >= PREC_FAST && mode <= PREC_FULL, LDIFF_ERR_INVALID, "unet_set_precision: mode must be 0, 1 or 2");
@@ -103,8 +112,8 @@ int ldiff_unet_set_precision(ldiff_unet* u, int mode) {
 int ldiff_unet_set_graph(ldiff_unet* u, int on) { return set_graph(u, on, "unet_set_graph"); }
 int64_t ldiff_unet_graph_replays(ldiff_unet* u) { return u ? (int64_t)u->gc.replays : -1; }
 int64_t ldiff_unet_graph_nodes(ldiff_unet* u) { return u ? (int64_t)u->gc.nodes : -1; }
-int ldiff_unet_missing(ldiff_unet* u) { return u ? u->ws.missing() : -1; }
-const char* ldiff_unet_missing_name(ldiff_unet* u, int i) { return u ? u->ws.missing_name(i) : ""; }
+int ldiff_unet_missing(ldiff_unet* u) { return missing(u); }
+const char* ldiff_unet_missing_name(ldiff_unet* u, int i) { return missing_name(u, i); }
 int ldiff_unet_set_context(ldiff_unet* u, const void* ctx_dev, int B_ctx, int L, void* stream) {
   API_BEGIN
   LDIFF_CHECK(u, LDIFF_ERR_INVALID, "unet_set_context: null handle");
@@ -157,15 +166,9 @@ int ldiff_controlnet_create(ldiff_controlnet** out, const ldiff_unet_cfg* trunk_
   *out = c;
   API_END
 }
-int ldiff_controlnet_load(ldiff_controlnet* c, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
-  API_BEGIN
-  LDIFF_CHECK(c, LDIFF_ERR_INVALID, "controlnet_load: null handle");
-  HIP_CHECK(hipSetDevice(c->trunk.device));
-  c->trunk.ws.load(name, host_ptr, dtype, shape, ndim);
-  API_END
-}
-int ldiff_controlnet_missing(ldiff_controlnet* c) { return c ? c->trunk.ws.missing() : -1; }
-const char* ldiff_controlnet_missing_name(ldiff_controlnet* c, int i) { return c ? c->trunk.ws.missing_name(i) : ""; }
+int ldiff_controlnet_load(ldiff_controlnet* c, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) { return load(c, "controlnet_load", name, host_ptr, dtype, shape, ndim); }
+int ldiff_controlnet_missing(ldiff_controlnet* c) { return missing(c); }
+const char* ldiff_controlnet_missing_name(ldiff_controlnet* c, int i) { return missing_name(c, i); }
 int ldiff_controlnet_set_precision(ldiff_controlnet* c, int mode) {
   API_BEGIN
   LDIFF_CHECK(c && mode >= PREC_FAST && mode <= PREC_FULL, LDIFF_ERR_INVALID, "controlnet_set_precision: mode must be 0, 1 or 2");
@@ -211,15 +214,9 @@ int ldiff_segnet_create(ldiff_segnet** out, int in_channels, int n_stages, const
   *out = n;
   API_END
 }
-int ldiff_segnet_load(ldiff_segnet* n, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
-  API_BEGIN
-  LDIFF_CHECK(n, LDIFF_ERR_INVALID, "segnet_load: null handle");
-  HIP_CHECK(hipSetDevice(n->device));
-  n->ws.load(name, host_ptr, dtype, shape, ndim);
-  API_END
-}
-int ldiff_segnet_missing(ldiff_segnet* n) { return n ? n->ws.missing() : -1; }
-const char* ldiff_segnet_missing_name(ldiff_segnet* n, int i) { return n ? n->ws.missing_name(i) : ""; }
+int ldiff_segnet_load(ldiff_segnet* n, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) { return load(n, "segnet_load", name, host_ptr, dtype, shape, ndim); }
+int ldiff_segnet_missing(ldiff_segnet* n) { return missing(n); }
+const char* ldiff_segnet_missing_name(ldiff_segnet* n, int i) { return missing_name(n, i); }
 int ldiff_segnet_set_graph(ldiff_segnet* n, int on) { return set_graph(n, on, "segnet_set_graph"); }
 int64_t ldiff_segnet_graph_replays(ldiff_segnet* n) { return n ? n->gc.replays : -1; }
 int ldiff_segnet_forward(ldiff_segnet* n, const void* x_dev, int B, int H, int W, void* logits_dev, int out_dtype, void* stream) {
@@ -244,15 +241,9 @@ int ldiff_resnet_create(ldiff_resnet** out, const int* layers, int width, int ad
   *out = r;
   API_END
 }
-int ldiff_resnet_load(ldiff_resnet* r, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
-  API_BEGIN
-  LDIFF_CHECK(r, LDIFF_ERR_INVALID, "resnet_load: null handle");
-  HIP_CHECK(hipSetDevice(r->device));
-  r->load(name, host_ptr, dtype, shape, ndim);
-  API_END
-}
-int ldiff_resnet_missing(ldiff_resnet* r) { return r ? r->missing() : -1; }
-const char* ldiff_resnet_missing_name(ldiff_resnet* r, int i) { return r ? r->missing_name(i) : ""; }
+int ldiff_resnet_load(ldiff_resnet* r, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) { return load(r, "resnet_load", name, host_ptr, dtype, shape, ndim); }
+int ldiff_resnet_missing(ldiff_resnet* r) { return missing(r); }
+const char* ldiff_resnet_missing_name(ldiff_resnet* r, int i) { return missing_name(r, i); }
 int ldiff_resnet_set_graph(ldiff_resnet* r, int on) { return set_graph(r, on, "resnet_set_graph"); }
 int64_t ldiff_resnet_graph_replays(ldiff_resnet* r) { return r ? r->gc.replays : -1; }
 int ldiff_resnet_forward(ldiff_resnet* r, const void* crops, int B, int S, void* logits, void* labels, void* stream) {
@@ -276,15 +267,9 @@ int ldiff_textenc_create(ldiff_textenc** out, const ldiff_textenc_cfg* cfg, int 
   *out = t;
   API_END
 }
-int ldiff_textenc_load(ldiff_textenc* t, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
-  API_BEGIN
-  LDIFF_CHECK(t, LDIFF_ERR_INVALID, "textenc_load: null handle");
-  HIP_CHECK(hipSetDevice(t->device));
-  t->load(name, host_ptr, dtype, shape, ndim);
-  API_END
-}
-int ldiff_textenc_missing(ldiff_textenc* t) { return t ? t->missing() : -1; }
-const char* ldiff_textenc_missing_name(ldiff_textenc* t, int i) { return t ? t->missing_name(i) : ""; }
+int ldiff_textenc_load(ldiff_textenc* t, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) { return load(t, "textenc_load", name, host_ptr, dtype, shape, ndim); }
+int ldiff_textenc_missing(ldiff_textenc* t) { return missing(t); }
+const char* ldiff_textenc_missing_name(ldiff_textenc* t, int i) { return missing_name(t, i); }
 int ldiff_textenc_set_graph(ldiff_textenc* t, int on) { return set_graph(t, on, "textenc_set_graph"); }
 int64_t ldiff_textenc_graph_replays(ldiff_textenc* t) { return t ? (int64_t)t->gc.replays : -1; }
 int64_t ldiff_textenc_graph_nodes(ldiff_textenc* t) { return t ? (int64_t)t->gc.nodes : -1; }
@@ -350,13 +335,7 @@ int ldiff_vae_create(ldiff_vae** out, const ldiff_vae_cfg* cfg, int device) {
   *out = v;
   API_END
 }
-int ldiff_vae_load(ldiff_vae* v, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
-  API_BEGIN
-  LDIFF_CHECK(v, LDIFF_ERR_INVALID, "vae_load: null handle");
-  HIP_CHECK(hipSetDevice(v->device));
-  v->ws.load(name, host_ptr, dtype, shape, ndim);
-  API_END
-}
+int ldiff_vae_load(ldiff_vae* v, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) { return load(v, "vae_load", name, host_ptr, dtype, shape, ndim); }
 int ldiff_vae_set_precision(ldiff_vae* v, int encoder_mode, int decoder_mode) {
   API_BEGIN
   LDIFF_CHECK(v && encoder_mode >= PREC_FAST && encoder_mode <= PREC_FULL && decoder_mode >= PREC_FAST && decoder_mode <= PREC_FULL, LDIFF_ERR_INVALID,
@@ -370,8 +349,8 @@ int ldiff_vae_set_range_shift(ldiff_vae* v, int k) {
   v->set_range_shift(k);
   API_END
 }
-int ldiff_vae_missing(ldiff_vae* v) { return v ? v->ws.missing() : -1; }
-const char* ldiff_vae_missing_name(ldiff_vae* v, int i) { return v ? v->ws.missing_name(i) : ""; }
+int ldiff_vae_missing(ldiff_vae* v) { return missing(v); }
+const char* ldiff_vae_missing_name(ldiff_vae* v, int i) { return missing_name(v, i); }
 int ldiff_vae_encode(ldiff_vae* v, const void* x_dev, int B, int H, int W, void* moments_dev, void* stream) {
   API_BEGIN
   LDIFF_CHECK(v, LDIFF_ERR_INVALID, "vae_encode: null handle");

@@ -63,47 +63,81 @@ struct MatW {   // [Nrows][K] fp16 K-major + fp32 bias
 struct NormW { float* g = nullptr; float* b = nullptr; int C = 0; };
 struct GNss { float* scale = nullptr; float* shift = nullptr; };
 
-// One expected checkpoint tensor and where/how it lands on the device.
+// ---- checkpoint loading (weight_store.hip) ---------------------------------------------------------------
+// Every handle family owns one WeightStore.  At build() the owner registers each checkpoint tensor it expects as a LoadSpec: the torch shape, where the
+// values land and in which layout.  *_load then is WeightStore::load: one name / alias lookup, the dtype check (LDIFF_F32 / F16 / BF16), the shape check,
+// the repack on the host, the copy, `loaded` and ++generation (what derived weights and captured graphs are keyed by).
+//
+// Kinds:
+//   MATRIX  fp16 rows [row][tap][Cin_pad] at a row offset of a K-major device matrix (a conv or linear weight; several checkpoint tensors may fill one
+//           matrix: fused q / k / v).  Flags: geglu_half (GEGLU row interleave), tconv (transposed conv, [tap][Cout][Cin]), rows3 (the text encoder's
+//           three-block rows [wh(K) | wh(K) | wl(K)], wh = f16(w), wl = f16(w - wh)).
+//   TENSOR  fp32 tensor of any rank copied as is to the device (norms, biases, embedding tables, the classifier's linear head); geglu_half interleaves a bias.
+//   HOST    fp32 tensor kept in a host vector of the spec until the owner takes it (fresh() / consume(): the classifier folds a conv with its BatchNorm).
+// Two shape rules.  TENSOR and HOST: exact, extent by extent.  MATRIX: equal element count, equal first two extents, rank 4 or -- for a 1x1 -- rank 2:
+// diffusers checkpoints store the same attention projection as [C, C] or as [C, C, 1, 1] depending on their age, and both must load.
+// The wait rule: a load that overwrites a tensor that was loaded before waits for the device (hipDeviceSynchronize) before its device write, since a
+// forward enqueued earlier may still read it; a first load does not wait, nothing can have read that memory.  (HOST tensors reach the device in the
+// owner's own step, which waits itself.)
+// missing() lists the tensors not loaded yet in registration order; missing_name(i) indexes the list of the last missing() call.
+// Errors are reported under `who` ("unet_load"-style prefix of the messages), set by the owner at build().
 struct LoadSpec {
-  enum Kind { MATRIX, VECTOR } kind;
+  enum Kind { MATRIX, TENSOR, HOST } kind = TENSOR;
   std::vector<int64_t> shape;   // expected torch shape
   f16* mat = nullptr; int row_off = 0, K = 0, ks = 1, Cin_pad = 0;   // MATRIX
-  float* vec = nullptr; int vec_off = 0;                             // VECTOR
+  float* vec = nullptr; int vec_off = 0;                             // TENSOR
+  std::vector<float> host; bool fresh = false;                       // HOST: the values, and whether they were loaded since the owner last consumed them
   bool tconv = false;   // MATRIX of a transposed conv (torch [Cin, Cout, k, k]): element (c, n, tap) lands at row tap * Nrows_t + n, column c
   int tconv_rows = 0;
+  bool rows3 = false;   // MATRIX of the text encoder: row r of [rows, K] lands as [wh | wh | wl] at row row_off + r of a matrix of pitch 3 K
   int geglu_half = 0;   // > 0: GEGLU projection of width 2*geglu_half: row r lands at geglu_row(r) (x / gate interleaved by 16 rows)
   bool loaded = false;
 };
 
-// checkpoint loading, shared by WeightStore::load and ldiff_resnet::load
-float host_to_float(const void* p, int dtype, size_t i);   // element i of a host tensor of dtype LDIFF_F32 / F16 / BF16
-[[noreturn]] void throw_shape_mismatch(const char* who, const char* name, const int64_t* shape, int ndim, const std::vector<int64_t>& want);
+// The repacks: torch layout, dtype LDIFF_F32 / F16 / BF16 -> device layout, on the host, every element of dst written (pads zero).  No HIP call.
+void repack_rows(const void* src, int dtype, int rows, int Cin, int taps, int Cin_pad, int K, int geglu_half, f16* dst);   // [rows, Cin, taps] -> [rows][K], K >= taps * Cin_pad
+void repack_tconv(const void* src, int dtype, int Cin, int Cout, int taps, int rows_t, int K, f16* dst);                   // [Cin, Cout, taps] -> [taps][rows_t][K]
+void repack_f32(const void* src, int dtype, size_t n, int geglu_half, float* dst);                                         // n values as they are
+void repack_rows3(const void* src, int dtype, int rows, int K, f16* dst);                                                  // [rows, K] -> [rows][3 K]
 
 class WeightStore {
  public:
   ~WeightStore();
+  const char* who = "load";
   // allocation helpers (device memory owned by the store, zero-initialised)
   f16* alloc_mat(int Nrows, int K);
-  float* alloc_vec(int n);
+  float* alloc_vec(size_t n);
   // registration
   MatW add_conv(const std::string& prefix, int Cin, int Cout, int ks, bool bias = true, int Cin_pad = -1, int min_rows = 0, bool geglu = false);
   void add_rows(const std::string& wname, const std::string& bname, f16* mat, int K, int ks, int Cin, int Cin_pad, int row_off, int rows,
                 float* bias_vec, bool has_bias);
+  void add_rows3(const std::string& wname, const std::string& bname, f16* mat, int K, int row_off, int rows, float* bias_vec);   // three-block rows + their bias
   NormW add_norm(const std::string& prefix, int C);
   MatW add_tconv(const std::string& prefix, int Cin, int Cout, int k);   // ConvTranspose2d with kernel = stride = k: [k*k][Cout][Cin] fp16 + bias (kernels_seg.hip)
+  void add_tensor(const std::string& name, std::vector<int64_t> shape, float* dst, int off = 0);
+  void add_host(const std::string& name, std::vector<int64_t> shape);
   void alias(const std::string& alias_name, const std::string& name);
   // loading
+  void check_tensor(const char* name, const void* host, int dtype, const int64_t* shape, int ndim) const;   // null arguments, dtype: load()'s first step
   void load(const char* name, const void* host, int dtype, const int64_t* shape, int ndim);
   int missing() const;
   const char* missing_name(int i) const;
   int generation = 0;   // bumped by every load(): derived weights are rebuilt when it changes
+  // HOST tensors
+  bool loaded(const std::string& name) const;
+  const std::vector<float>* fresh(const std::string& name) const;   // the values if loaded since the last consume(), else nullptr
+  void consume(const std::string& name);                            // the owner has taken them: the host copy goes
+  int n_fresh() const { return n_fresh_; }
 
  private:
+  void* alloc_zeroed(size_t bytes);
+  LoadSpec& add(const std::string& name, LoadSpec::Kind kind, std::vector<int64_t> shape);
   std::unordered_map<std::string, LoadSpec> specs_;
   std::unordered_map<std::string, std::string> alias_;
   std::vector<std::string> order_;
   std::vector<void*> allocs_;
   mutable std::vector<std::string> missing_cache_;
+  int n_fresh_ = 0;
 };
 
 // Sticky non-finite detector of a handle (include/ldiff.h "Non-finite detection").  One int per graph in host-mapped pinned memory: the device sets it
@@ -393,7 +427,7 @@ struct ldiff_segnet {
 };
 
 // ---- instance classifier of the cell head -------------------------------------------------------------
-// torchvision's ResNet (v1.5 bottlenecks) + adapter conv + linear head (include/ldiff.h).  The checkpoint's tensors are staged on the host; a conv and its
+// torchvision's ResNet (v1.5 bottlenecks) + adapter conv + linear head (include/ldiff.h).  The checkpoint's conv and BatchNorm tensors stay on the host (LoadSpec::HOST); a conv and its
 // BatchNorm are folded there in double (fold()) into one fp16 K-major matrix + fp32 bias, so every conv is one clsconv launch (kernels_cls.hip).
 struct ClsConvW {
   std::string conv, bn;          // checkpoint prefixes; bn empty: the conv has its own bias (the adapter)
@@ -411,28 +445,18 @@ struct ldiff_resnet {
   int stem = -1, adapter = -1;
   std::vector<ClsBlockW> blocks;
   float* fc_w = nullptr; float* fc_b = nullptr;   // [n_classes][adapter_ch], [n_classes] fp32
-  bool fc_w_loaded = false, fc_b_loaded = false;
-  // expected checkpoint tensors (name -> torch shape) and the host staging of those not yet folded
-  std::vector<std::pair<std::string, std::vector<int64_t>>> expected;
-  std::unordered_map<std::string, std::vector<float>> staged;
-  std::unordered_map<std::string, int> index;   // name -> entry of `expected`
-  std::vector<char> have;                       // loaded at least once
-  mutable std::vector<std::string> missing_cache;
-  std::vector<void*> allocs;
-  int generation = 0;
+  WeightStore ws;   // the conv / BatchNorm tensors as HOST specs (fold() takes them), the linear head as TENSORs
   Exec ex;
   NonFiniteFlag nf;
   void build();
   void load(const char* name, const void* host, int dtype, const int64_t* shape, int ndim);
-  void fold();                     // every group whose tensors are all staged -> device (synchronous copies: never inside a capture)
-  int missing() const;
-  const char* missing_name(int i) const;
+  void fold();                     // every group whose tensors are all freshly loaded -> device (synchronous copies: never inside a capture)
   Act conv(const ClsConvW& c, const Act& x, const Act* res, bool relu);
   void forward(const f16* crops, int B, int S, float* logits, int* labels, hipStream_t s);
   void forward_impl(const f16* crops, int B, int S, float* logits, int* labels, hipStream_t s);
   GraphCache gc;
   DeviceBuf st_in, st_logits, st_labels;
-  ~ldiff_resnet();
+  ~ldiff_resnet() { nf.destroy(); }
 };
 
 // ---- CLIP text encoder ---------------------------------------------------------------------------------
@@ -445,27 +469,19 @@ struct TextLayerW { NormW ln1, ln2; TextLinW qkv, out, fc1, fc2; };
 struct ldiff_textenc {
   ldiff_textenc_cfg cfg;
   int device = 0;
-  WeightStore ws;         // names, shapes, norms and biases; the matrices land in the three-block operands (load)
+  WeightStore ws;
   Exec ex;
   NonFiniteFlag nf;
   float* tok = nullptr;   // [vocab][hidden] fp32
   float* pos = nullptr;   // [max_positions][hidden] fp32
-  bool tok_loaded = false, pos_loaded = false;
-  int emb_gen = 0;
   std::vector<TextLayerW> layers;
   NormW final_ln;
   TextLinW proj;          // optional: registered by the first load of proj.weight / proj.bias, which states its width
   int proj_dim = 0;
-  f16* scratch_w = nullptr;   // where WeightStore::load puts the fp16 copy it makes of a matrix (not read)
-  struct MatDst { f16* w3; int row_off, K; };
-  std::unordered_map<std::string, MatDst> mats;   // checkpoint name of a matrix -> its rows in a three-block operand
-  mutable std::vector<std::string> missing_cache;
   void build();
   TextLinW add_lin(const std::string& prefix, int K, int N);
   void add_part(TextLinW& l, const std::string& prefix, int row_off, int rows);
   void load(const char* name, const void* host, int dtype, const int64_t* shape, int ndim);
-  int missing() const;
-  const char* missing_name(int i) const;
   void forward(const int32_t* ids_host, int B, int L, int project, void* out, int out_dtype, hipStream_t s);
   void forward_impl(const int* ids_dev, int B, int L, int project, void* out, int out_dtype, hipStream_t s);
   // y = act(x.w^T + b) [+ res]: x split [M, 2 K]; y a plain or split fp16 tensor, or fp32 rows at out_f32
@@ -473,7 +489,7 @@ struct ldiff_textenc {
   Act layernorm(const Act& x, const NormW& w);   // split in, split out
   GraphCache gc;
   DeviceBuf st_ids, st_out;
-  ~ldiff_textenc();
+  ~ldiff_textenc() { nf.destroy(); }
 };
 
 struct ldiff_pipeline {

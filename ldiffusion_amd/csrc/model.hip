@@ -90,156 +90,6 @@ void Arena::free(void* p) {
   throw LdiffError{LDIFF_ERR_RUNTIME};
 }
 
-// ---- WeightStore -------------------------------------------------------------------------------
-WeightStore::~WeightStore() {
-  for (void* p : allocs_) (void)hipFree(p);
-}
-f16* WeightStore::alloc_mat(int Nrows, int K) {
-  void* p = nullptr;
-  size_t bytes = (size_t)Nrows * K * sizeof(f16);
-  HIP_CHECK(hipMalloc(&p, bytes));
-  HIP_CHECK(hipMemset(p, 0, bytes));
-  allocs_.push_back(p);
-  return (f16*)p;
-}
-float* WeightStore::alloc_vec(int n) {
-  void* p = nullptr;
-  HIP_CHECK(hipMalloc(&p, (size_t)n * sizeof(float)));
-  HIP_CHECK(hipMemset(p, 0, (size_t)n * sizeof(float)));
-  allocs_.push_back(p);
-  return (float*)p;
-}
-void WeightStore::add_rows(const std::string& wname, const std::string& bname, f16* mat, int K, int ks, int Cin, int Cin_pad, int row_off,
-                           int rows, float* bias_vec, bool has_bias) {
-  LoadSpec w;
-  w.kind = LoadSpec::MATRIX;
-  w.shape = {rows, Cin, ks, ks};
-  w.mat = mat; w.row_off = row_off; w.K = K; w.ks = ks; w.Cin_pad = Cin_pad;
-  specs_[wname] = w;
-  order_.push_back(wname);
-  if (has_bias) {
-    LoadSpec b;
-    b.kind = LoadSpec::VECTOR;
-    b.shape = {rows};
-    b.vec = bias_vec; b.vec_off = row_off;
-    specs_[bname] = b;
-    order_.push_back(bname);
-  }
-}
-MatW WeightStore::add_conv(const std::string& prefix, int Cin, int Cout, int ks, bool bias, int Cin_pad, int min_rows, bool geglu) {
-  if (Cin_pad < 0) Cin_pad = roundup(Cin, 8);
-  MatW m;
-  m.N = Cout; m.Nrows = roundup(std::max(Cout, min_rows), 16); m.ks = ks; m.Cin = Cin_pad; m.K = ks * ks * Cin_pad;
-  m.Cin_logical = 2 * Cin <= Cin_pad ? Cin : 0;   // hi | lo of a <= 4-channel input fit into the 8 padded channels
-  m.w = alloc_mat(m.Nrows, m.K);
-  m.b = bias ? alloc_vec(m.Nrows) : nullptr;
-  add_rows(prefix + ".weight", prefix + ".bias", m.w, m.K, ks, Cin, Cin_pad, 0, Cout, m.b, bias);
-  if (geglu) {   // Linear(C, 2*half) whose output is [x | gate]: store x rows 16j..16j+15 at 32j.., gate rows 16j.. at 32j+16..
-    LDIFF_CHECK(Cout % 32 == 0, LDIFF_ERR_INVALID, "geglu projection width %d must be a multiple of 32", Cout);
-    m.geglu = true;
-    specs_[prefix + ".weight"].geglu_half = Cout / 2;
-    if (bias) specs_[prefix + ".bias"].geglu_half = Cout / 2;
-  }
-  return m;
-}
-static inline int geglu_row(int r, int half) { const int q = r < half ? r : r - half; return (q / 16) * 32 + (r < half ? 0 : 16) + q % 16; }
-NormW WeightStore::add_norm(const std::string& prefix, int C) {
-  NormW n;
-  n.C = C; n.g = alloc_vec(C); n.b = alloc_vec(C);
-  LoadSpec g; g.kind = LoadSpec::VECTOR; g.shape = {C}; g.vec = n.g; g.vec_off = 0;
-  LoadSpec b = g; b.vec = n.b;
-  specs_[prefix + ".weight"] = g; order_.push_back(prefix + ".weight");
-  specs_[prefix + ".bias"] = b; order_.push_back(prefix + ".bias");
-  return n;
-}
-MatW WeightStore::add_tconv(const std::string& prefix, int Cin, int Cout, int k) {
-  MatW m;
-  m.N = Cout; m.Nrows = Cout; m.ks = k; m.Cin = roundup(Cin, 8); m.K = m.Cin;
-  m.w = alloc_mat(k * k * m.Nrows, m.K);
-  m.b = alloc_vec(m.Nrows);
-  LoadSpec w;
-  w.kind = LoadSpec::MATRIX;
-  w.shape = {Cin, Cout, k, k};
-  w.mat = m.w; w.K = m.K; w.ks = k; w.Cin_pad = m.Cin; w.tconv = true; w.tconv_rows = m.Nrows;
-  specs_[prefix + ".weight"] = w;
-  order_.push_back(prefix + ".weight");
-  LoadSpec b;
-  b.kind = LoadSpec::VECTOR;
-  b.shape = {Cout};
-  b.vec = m.b;
-  specs_[prefix + ".bias"] = b;
-  order_.push_back(prefix + ".bias");
-  return m;
-}
-void WeightStore::alias(const std::string& alias_name, const std::string& name) { alias_[alias_name] = name; }
-
-float host_to_float(const void* p, int dtype, size_t i) {
-  if (dtype == LDIFF_F32) return ((const float*)p)[i];
-  if (dtype == LDIFF_F16) return (float)((const f16*)p)[i];
-  uint32_t u = (uint32_t)((const uint16_t*)p)[i] << 16;  // bf16
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-void throw_shape_mismatch(const char* who, const char* name, const int64_t* shape, int ndim, const std::vector<int64_t>& want) {
-  std::string got, exp;
-  for (int i = 0; i < ndim; ++i) got += (i ? "," : "") + std::to_string((long long)shape[i]);
-  for (size_t i = 0; i < want.size(); ++i) exp += (i ? "," : "") + std::to_string((long long)want[i]);
-  ldiff_set_error("%s(%s): shape [%s] does not match expected [%s]", who, name, got.c_str(), exp.c_str());
-  throw LdiffError{LDIFF_ERR_INVALID};
-}
-
-void WeightStore::load(const char* name_c, const void* host, int dtype, const int64_t* shape, int ndim) {
-  LDIFF_CHECK(name_c && host && shape, LDIFF_ERR_INVALID, "load: null argument");
-  LDIFF_CHECK(dtype == LDIFF_F32 || dtype == LDIFF_F16 || dtype == LDIFF_BF16, LDIFF_ERR_INVALID, "load(%s): unsupported dtype %d", name_c, dtype);
-  std::string name(name_c);
-  auto al = alias_.find(name);
-  if (al != alias_.end()) name = al->second;
-  auto it = specs_.find(name);
-  LDIFF_CHECK(it != specs_.end(), LDIFF_ERR_INVALID, "load: unexpected tensor name '%s'", name_c);
-  LoadSpec& sp = it->second;
-  size_t numel = 1, expect = 1;
-  for (int i = 0; i < ndim; ++i) numel *= (size_t)shape[i];
-  for (auto d : sp.shape) expect *= (size_t)d;
-  bool ok = numel == expect && ndim >= 1 && shape[0] == sp.shape[0];
-  if (sp.kind == LoadSpec::MATRIX) ok = ok && ndim >= 2 && shape[1] == sp.shape[1] && (ndim == 4 || (ndim == 2 && sp.ks == 1));
-  else ok = ok && ndim == 1;
-  if (!ok) throw_shape_mismatch("load", name_c, shape, ndim, sp.shape);
-  if (sp.kind == LoadSpec::VECTOR) {
-    std::vector<float> tmp(numel);
-    for (size_t i = 0; i < numel; ++i) tmp[sp.geglu_half ? (size_t)geglu_row((int)i, sp.geglu_half) : i] = host_to_float(host, dtype, i);
-    HIP_CHECK(hipMemcpy(sp.vec + sp.vec_off, tmp.data(), numel * sizeof(float), hipMemcpyHostToDevice));
-  } else if (sp.tconv) {   // torch ConvTranspose2d [Cin, Cout, k, k] -> [tap][Cout][Cin]
-    const int Cin = (int)sp.shape[0], Cout = (int)sp.shape[1], taps = sp.ks * sp.ks;
-    std::vector<f16> tmp((size_t)taps * sp.tconv_rows * sp.K, (f16)0.f);
-    for (int c = 0; c < Cin; ++c)
-      for (int n = 0; n < Cout; ++n)
-        for (int t = 0; t < taps; ++t) tmp[((size_t)t * sp.tconv_rows + n) * sp.K + c] = (f16)host_to_float(host, dtype, ((size_t)c * Cout + n) * taps + t);
-    HIP_CHECK(hipMemcpy(sp.mat, tmp.data(), tmp.size() * sizeof(f16), hipMemcpyHostToDevice));
-  } else {
-    const int rows = (int)sp.shape[0], Cin = (int)sp.shape[1], ks = sp.ks, taps = ks * ks;
-    std::vector<f16> tmp((size_t)rows * sp.K, (f16)0.f);
-    for (int r = 0; r < rows; ++r)
-      for (int c = 0; c < Cin; ++c)
-        for (int t = 0; t < taps; ++t)
-          tmp[(size_t)(sp.geglu_half ? geglu_row(r, sp.geglu_half) : r) * sp.K + (size_t)t * sp.Cin_pad + c] =
-              (f16)host_to_float(host, dtype, ((size_t)r * Cin + c) * taps + t);
-    HIP_CHECK(hipMemcpy(sp.mat + (size_t)sp.row_off * sp.K, tmp.data(), tmp.size() * sizeof(f16), hipMemcpyHostToDevice));
-  }
-  sp.loaded = true;
-  ++generation;
-}
-int WeightStore::missing() const {
-  missing_cache_.clear();
-  for (auto& n : order_)
-    if (!specs_.at(n).loaded) missing_cache_.push_back(n);
-  return (int)missing_cache_.size();
-}
-const char* WeightStore::missing_name(int i) const {
-  if (i < 0 || i >= (int)missing_cache_.size()) return "";
-  return missing_cache_[i].c_str();
-}
-
 // ---- non-finite flag ------------------------------------------------------------------------------
 void NonFiniteFlag::create() {
   if (words) return;

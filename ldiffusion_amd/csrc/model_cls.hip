@@ -8,21 +8,23 @@
 
 static const double BN_EPS = 1e-5;   // torchvision's BatchNorm2d default, eval mode (running statistics)
 
+static std::vector<std::string> group_names(const ClsConvW& c) {   // the checkpoint tensors folded into one conv: the weight first
+  std::vector<std::string> names = {c.conv + ".weight"};
+  if (c.bn.empty()) names.push_back(c.conv + ".bias");
+  else
+    for (const char* v : {".weight", ".bias", ".running_mean", ".running_var"}) names.push_back(c.bn + v);
+  return names;
+}
+
 static int add_conv(ldiff_resnet& r, const std::string& conv, const std::string& bn, int Cin, int Cout, int ks, int stride) {
   ClsConvW c;
   c.conv = conv; c.bn = bn; c.Cin = Cin; c.Cout = Cout; c.ks = ks; c.stride = stride;
   c.Cin_pad = (Cin + 7) / 8 * 8;
-  const size_t wbytes = (size_t)Cout * ks * ks * c.Cin_pad * sizeof(f16);
-  HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c.w), wbytes));
-  r.allocs.push_back(c.w);
-  HIP_CHECK(hipMemset(c.w, 0, wbytes));
-  HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c.b), (size_t)Cout * sizeof(float)));
-  r.allocs.push_back(c.b);
-  HIP_CHECK(hipMemset(c.b, 0, (size_t)Cout * sizeof(float)));
-  r.expected.push_back({conv + ".weight", {Cout, Cin, ks, ks}});
-  if (bn.empty()) r.expected.push_back({conv + ".bias", {Cout}});
-  else
-    for (const char* v : {".weight", ".bias", ".running_mean", ".running_var"}) r.expected.push_back({bn + v, {Cout}});
+  c.w = r.ws.alloc_mat(Cout, ks * ks * c.Cin_pad);
+  c.b = r.ws.alloc_vec(Cout);
+  const std::vector<std::string> names = group_names(c);
+  r.ws.add_host(names[0], {Cout, Cin, ks, ks});
+  for (size_t i = 1; i < names.size(); ++i) r.ws.add_host(names[i], {Cout});
   r.convs.push_back(c);
   return (int)r.convs.size() - 1;
 }
@@ -33,7 +35,8 @@ void ldiff_resnet::build() {
   LDIFF_CHECK(adapter_ch >= 16 && adapter_ch <= 8192 && adapter_ch % 16 == 0, LDIFF_ERR_INVALID, "resnet_create: adapter_channels = %d must be a multiple of 16 in 16..8192", adapter_ch);
   LDIFF_CHECK(n_classes >= 2 && n_classes <= 4096, LDIFF_ERR_INVALID, "resnet_create: num_classes = %d outside 2..4096", n_classes);
   nf.create();
-  ex.weights_gen = &generation;
+  ws.who = "resnet_load";
+  ex.weights_gen = &ws.generation;
   ex.nonfinite = nf.words;
   ex.trace_tag = "resnet";
   stem = add_conv(*this, "encoder.0", "encoder.1", 3, width, 7, 2);
@@ -53,70 +56,40 @@ void ldiff_resnet::build() {
     }
   }
   adapter = add_conv(*this, "adapter", "", inpl, adapter_ch, 3, 1);
-  expected.push_back({"classifier.weight", {n_classes, adapter_ch}});
-  expected.push_back({"classifier.bias", {n_classes}});
-  HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&fc_w), (size_t)n_classes * adapter_ch * sizeof(float)));
-  allocs.push_back(fc_w);
-  HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&fc_b), (size_t)n_classes * sizeof(float)));
-  allocs.push_back(fc_b);
-  for (size_t i = 0; i < expected.size(); ++i) index[expected[i].first] = (int)i;
-  have.assign(expected.size(), 0);
+  fc_w = ws.alloc_vec((size_t)n_classes * adapter_ch);
+  fc_b = ws.alloc_vec(n_classes);
+  ws.add_tensor("classifier.weight", {n_classes, adapter_ch}, fc_w);
+  ws.add_tensor("classifier.bias", {n_classes}, fc_b);
 }
 
-ldiff_resnet::~ldiff_resnet() {
-  nf.destroy();
-  for (void* p : allocs) (void)hipFree(p);
-}
-
-void ldiff_resnet::load(const char* name_c, const void* host, int dtype, const int64_t* shape, int ndim) {
-  LDIFF_CHECK(name_c && host && (shape || ndim == 0), LDIFF_ERR_INVALID, "resnet_load: null argument");
-  LDIFF_CHECK(dtype == LDIFF_F32 || dtype == LDIFF_F16 || dtype == LDIFF_BF16, LDIFF_ERR_INVALID, "resnet_load(%s): unsupported dtype %d", name_c, dtype);
-  const std::string name(name_c);
+void ldiff_resnet::load(const char* name, const void* host, int dtype, const int64_t* shape, int ndim) {
   static const std::string nbt = "num_batches_tracked";
-  if (name.size() >= nbt.size() && name.compare(name.size() - nbt.size(), nbt.size(), nbt) == 0) return;   // BatchNorm's step counter: not a parameter of the eval-mode forward
-  auto it = index.find(name);
-  LDIFF_CHECK(it != index.end(), LDIFF_ERR_INVALID, "resnet_load: unexpected tensor name '%s'", name_c);
-  const std::vector<int64_t>& want = expected[it->second].second;
-  bool ok = ndim == (int)want.size();
-  for (int i = 0; ok && i < ndim; ++i) ok = shape[i] == want[i];
-  if (!ok) throw_shape_mismatch("resnet_load", name_c, shape, ndim, want);
-  size_t numel = 1;
-  for (auto d : want) numel *= (size_t)d;
-  std::vector<float> v(numel);
-  for (size_t i = 0; i < numel; ++i) v[i] = host_to_float(host, dtype, i);
-  if (name == "classifier.weight" || name == "classifier.bias") {
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(name == "classifier.weight" ? fc_w : fc_b, v.data(), numel * sizeof(float), hipMemcpyHostToDevice));
-  } else {
-    staged[name] = std::move(v);
-  }
-  have[it->second] = 1;
-  ++generation;
+  const size_t n = name ? strlen(name) : 0;
+  if (n >= nbt.size() && nbt.compare(name + n - nbt.size()) == 0) return;   // BatchNorm's step counter: not a parameter of the eval-mode forward
+  ws.load(name, host, dtype, shape, ndim);
 }
 
 // w'[n][tap][c] = fp16(w[n][c][tap] * gamma[n] / sqrt(var[n] + eps)), b'[n] = fp32(beta[n] - mean[n] * gamma[n] / sqrt(var[n] + eps)), in double, one rounding each
 void ldiff_resnet::fold() {
-  if (staged.empty()) return;
+  if (ws.n_fresh() == 0) return;
   HIP_CHECK(hipDeviceSynchronize());   // (earlier forwards may still read the matrices)
   for (ClsConvW& c : convs) {
-    std::vector<std::string> names = {c.conv + ".weight"};
-    if (c.bn.empty()) names.push_back(c.conv + ".bias");
-    else
-      for (const char* v : {".weight", ".bias", ".running_mean", ".running_var"}) names.push_back(c.bn + v);
-    size_t n_staged = 0, n_have = 0;
-    for (auto& n : names) { n_staged += staged.count(n); n_have += have[index.at(n)] ? 1 : 0; }
-    if (n_staged == 0 || n_have < names.size()) continue;   // nothing new, or still incomplete (missing() names it)
-    LDIFF_CHECK(n_staged == names.size(), LDIFF_ERR_STATE, "resnet: '%s' was folded with its BatchNorm already; reloading part of the group needs all of %s.* and %s.* again",
+    const std::vector<std::string> names = group_names(c);
+    size_t n_fresh = 0, n_have = 0;
+    std::vector<const std::vector<float>*> v;
+    for (auto& n : names) { v.push_back(ws.fresh(n)); n_fresh += v.back() ? 1 : 0; n_have += ws.loaded(n) ? 1 : 0; }
+    if (n_fresh == 0 || n_have < names.size()) continue;   // nothing new, or still incomplete (missing() names it)
+    LDIFF_CHECK(n_fresh == names.size(), LDIFF_ERR_STATE, "resnet: '%s' was folded with its BatchNorm already; reloading part of the group needs all of %s.* and %s.* again",
                 c.conv.c_str(), c.conv.c_str(), c.bn.empty() ? c.conv.c_str() : c.bn.c_str());
-    const std::vector<float>& w = staged.at(names[0]);
+    const std::vector<float>& w = *v[0];
     const int taps = c.ks * c.ks, K = taps * c.Cin_pad;
     std::vector<f16> wf((size_t)c.Cout * K, (f16)0.f);
     std::vector<float> bf(c.Cout);
     for (int n = 0; n < c.Cout; ++n) {
       double scale = 1.0, shift;
-      if (c.bn.empty()) shift = staged.at(names[1])[n];
+      if (c.bn.empty()) shift = (*v[1])[n];
       else {
-        const double g = staged.at(names[1])[n], be = staged.at(names[2])[n], mu = staged.at(names[3])[n], var = staged.at(names[4])[n];
+        const double g = (*v[1])[n], be = (*v[2])[n], mu = (*v[3])[n], var = (*v[4])[n];
         scale = g / std::sqrt(var + BN_EPS);
         shift = be - mu * scale;
       }
@@ -127,19 +100,8 @@ void ldiff_resnet::fold() {
     HIP_CHECK(hipMemcpy(c.w, wf.data(), wf.size() * sizeof(f16), hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(c.b, bf.data(), bf.size() * sizeof(float), hipMemcpyHostToDevice));
     c.folded = true;
-    for (auto& n : names) staged.erase(n);
+    for (auto& n : names) ws.consume(n);
   }
-}
-
-int ldiff_resnet::missing() const {
-  missing_cache.clear();
-  for (size_t i = 0; i < expected.size(); ++i)
-    if (!have[i]) missing_cache.push_back(expected[i].first);
-  return (int)missing_cache.size();
-}
-const char* ldiff_resnet::missing_name(int i) const {
-  if (i < 0 || i >= (int)missing_cache.size()) return "";
-  return missing_cache[i].c_str();
 }
 
 Act ldiff_resnet::conv(const ClsConvW& c, const Act& x, const Act* res, bool relu) {
@@ -215,18 +177,18 @@ void ldiff_resnet::forward(const f16* crops, int B, int S, float* logits, int* l
   LDIFF_CHECK(B >= 1, LDIFF_ERR_INVALID, "resnet_forward: B = %d must be at least 1", B);
   LDIFF_CHECK(S >= 32 && S <= 1024 && S % 32 == 0, LDIFF_ERR_INVALID, "resnet_forward: S = %d must be a multiple of 32 in 32..1024", S);
   LDIFF_CHECK((long long)B * (S / 2) * (S / 2) * width < (1ll << 31), LDIFF_ERR_INVALID, "resnet_forward: B * (S / 2)^2 * width exceeds 2^31 (B = %d, S = %d)", B, S);
-  LDIFF_CHECK(missing() == 0, LDIFF_ERR_STATE, "resnet: %d weight tensors not loaded (first: %s)", missing(), missing_name(0));
+  LDIFF_CHECK(ws.missing() == 0, LDIFF_ERR_STATE, "resnet: %d weight tensors not loaded (first: %s)", ws.missing(), ws.missing_name(0));
   HIP_CHECK(hipSetDevice(device));
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (s) (void)hipStreamIsCapturing(s, &cs);
   if (cs == hipStreamCaptureStatusNone) fold();
-  LDIFF_CHECK(staged.empty(), LDIFF_ERR_STATE, "resnet_forward: weights were loaded but not folded yet; the first forward after a load cannot run inside a stream capture");
+  LDIFF_CHECK(ws.n_fresh() == 0, LDIFF_ERR_STATE, "resnet_forward: weights were loaded but not folded yet; the first forward after a load cannot run inside a stream capture");
   if (gc.bypass(s)) {
     forward_impl(crops, B, S, logits, labels, s);
     return;
   }
   const size_t n_in = (size_t)B * S * S * 8 * sizeof(f16), n_log = (size_t)B * n_classes * sizeof(float), n_lab = (size_t)B * sizeof(int);
-  gc.run(s, [&] { return GraphCache::Key{B, S, generation, (long long)ex.arena.capacity()}; }, {{&st_in, n_in}, {&st_logits, n_log}, {&st_labels, n_lab}},
+  gc.run(s, [&] { return GraphCache::Key{B, S, ws.generation, (long long)ex.arena.capacity()}; }, {{&st_in, n_in}, {&st_logits, n_log}, {&st_labels, n_lab}},
          [&] { forward_impl(crops, B, S, logits, labels, s); },
          [&](hipStream_t cap) { forward_impl(st_in.as<f16>(), B, S, st_logits.as<float>(), st_labels.as<int>(), cap); },
          [&] { HIP_CHECK(hipMemcpyAsync(st_in.p, crops, n_in, hipMemcpyDeviceToDevice, s)); },

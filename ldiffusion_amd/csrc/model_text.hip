@@ -23,9 +23,6 @@
 
 #include "model.h"
 
-static const char* TOK_NAME = "text_model.embeddings.token_embedding.weight";
-static const char* POS_NAME = "text_model.embeddings.position_embedding.weight";
-
 void ldiff_textenc::build() {
   const ldiff_textenc_cfg& c = cfg;
   LDIFF_CHECK(c.vocab_size >= 1 && c.vocab_size <= (1 << 20), LDIFF_ERR_INVALID, "textenc_create: vocab_size = %d outside 1..2^20", c.vocab_size);
@@ -39,14 +36,16 @@ void ldiff_textenc::build() {
   LDIFF_CHECK(c.act == 0 || c.act == 1, LDIFF_ERR_INVALID, "textenc_create: act = %d must be 0 (quick_gelu) or 1 (gelu)", c.act);
   LDIFF_CHECK(c.ln_eps > 0.f && c.ln_eps < 1.f, LDIFF_ERR_INVALID, "textenc_create: ln_eps = %g outside (0, 1)", (double)c.ln_eps);
   nf.create();
+  ws.who = "textenc_load";
   ex.weights_gen = &ws.generation;
   ex.nonfinite = nf.words;
   ex.trace_tag = "textenc";
   const int H = c.hidden;
-  HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&tok), (size_t)c.vocab_size * H * sizeof(float)));
-  HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&pos), (size_t)c.max_positions * H * sizeof(float)));
-  // the largest matrix a checkpoint can name: fc1 / fc2 [intermediate x hidden], or a projection of up to 8192 rows
-  HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&scratch_w), (size_t)H * std::max(std::max(H, c.intermediate), 8192) * sizeof(f16)));
+  // the two tables stay fp32: the embedding sum is the reference's, to fp32 round-off
+  tok = ws.alloc_vec((size_t)c.vocab_size * H);
+  pos = ws.alloc_vec((size_t)c.max_positions * H);
+  ws.add_tensor("text_model.embeddings.token_embedding.weight", {c.vocab_size, H}, tok);
+  ws.add_tensor("text_model.embeddings.position_embedding.weight", {c.max_positions, H}, pos);
   layers.resize(c.layers);
   for (int i = 0; i < c.layers; ++i) {
     const std::string p = "text_model.encoder.layers." + std::to_string(i);
@@ -74,60 +73,22 @@ TextLinW ldiff_textenc::add_lin(const std::string& prefix, int K, int N) {
   return l;
 }
 void ldiff_textenc::add_part(TextLinW& l, const std::string& prefix, int row_off, int rows) {
-  // WeightStore checks the name and the shape, loads the bias and keeps the missing list; its fp16 copy of the matrix goes to scratch (load() writes the operand)
-  ws.add_rows(prefix + ".weight", prefix + ".bias", scratch_w, l.K, 1, l.K, l.K, 0, rows, l.b + row_off, true);
-  mats[prefix + ".weight"] = MatDst{l.w3, row_off, l.K};
+  ws.add_rows3(prefix + ".weight", prefix + ".bias", l.w3, l.K, row_off, rows, l.b);
 }
 
-ldiff_textenc::~ldiff_textenc() {
-  nf.destroy();
-  if (tok) (void)hipFree(tok);
-  if (pos) (void)hipFree(pos);
-  if (scratch_w) (void)hipFree(scratch_w);
-}
-
+// the one step of a load that is the text encoder's own: the optional prompt projection is registered by its first tensor, which states the width
 void ldiff_textenc::load(const char* name_c, const void* host, int dtype, const int64_t* shape, int ndim) {
-  LDIFF_CHECK(name_c && host && shape, LDIFF_ERR_INVALID, "textenc_load: null argument");
-  LDIFF_CHECK(dtype == LDIFF_F32 || dtype == LDIFF_F16 || dtype == LDIFF_BF16, LDIFF_ERR_INVALID, "textenc_load(%s): unsupported dtype %d", name_c, dtype);
-  const std::string name(name_c);
-  const int H = cfg.hidden;
-  if (name == TOK_NAME || name == POS_NAME) {   // the two tables stay fp32: the embedding sum is the reference's, to fp32 round-off
-    const bool is_tok = name == TOK_NAME;
-    const std::vector<int64_t> want = {is_tok ? cfg.vocab_size : cfg.max_positions, H};
-    if (ndim != 2 || shape[0] != want[0] || shape[1] != want[1]) throw_shape_mismatch("textenc_load", name_c, shape, ndim, want);
-    const size_t numel = (size_t)want[0] * H;
-    std::vector<float> v(numel);
-    for (size_t i = 0; i < numel; ++i) v[i] = host_to_float(host, dtype, i);
-    HIP_CHECK(hipDeviceSynchronize());   // (an earlier forward may still read the table)
-    HIP_CHECK(hipMemcpy(is_tok ? tok : pos, v.data(), numel * sizeof(float), hipMemcpyHostToDevice));
-    (is_tok ? tok_loaded : pos_loaded) = true;
-    ++emb_gen;
-    return;
-  }
-  if ((name == "proj.weight" || name == "proj.bias") && proj_dim == 0) {   // the optional prompt projection: its first tensor states the width
+  const std::string name(name_c ? name_c : "");
+  if ((name == "proj.weight" || name == "proj.bias") && proj_dim == 0) {
     const bool is_w = name == "proj.weight";
-    LDIFF_CHECK(is_w ? (ndim == 2 && shape[1] == H) : ndim == 1, LDIFF_ERR_INVALID, "textenc_load(%s): expected %s", name_c, is_w ? "[cross_attention_dim, hidden]" : "[cross_attention_dim]");
+    ws.check_tensor(name_c, host, dtype, shape, ndim);
+    LDIFF_CHECK(is_w ? (ndim == 2 && shape[1] == cfg.hidden) : ndim == 1, LDIFF_ERR_INVALID, "textenc_load(%s): expected %s", name_c, is_w ? "[cross_attention_dim, hidden]" : "[cross_attention_dim]");
     LDIFF_CHECK(shape[0] >= 8 && shape[0] <= 8192 && shape[0] % 8 == 0, LDIFF_ERR_INVALID, "textenc_load(%s): cross_attention_dim = %lld must be a multiple of 8 in 8..8192", name_c, (long long)shape[0]);
     // dtype, rank and both extents are checked above, so the load below cannot refuse the tensor that registered the projection
-    HIP_CHECK(hipDeviceSynchronize());
-    proj = add_lin("proj", H, (int)shape[0]);
+    proj = add_lin("proj", cfg.hidden, (int)shape[0]);
     proj_dim = (int)shape[0];
   }
-  ws.load(name_c, host, dtype, shape, ndim);   // (refuses an unknown name or a wrong shape)
-  auto it = mats.find(name);
-  if (it == mats.end()) return;
-  const MatDst& m = it->second;   // [rows][K] -> rows of [wh | wh | wl]
-  const int rows = (int)shape[0], K = m.K;
-  std::vector<f16> tmp((size_t)rows * 3 * K);
-  for (int r = 0; r < rows; ++r)
-    for (int k = 0; k < K; ++k) {
-      const float w = host_to_float(host, dtype, (size_t)r * K + k);
-      const f16 wh = (f16)w;
-      f16* d = tmp.data() + (size_t)r * 3 * K + k;
-      d[0] = wh; d[K] = wh; d[2 * K] = (f16)(w - (float)wh);
-    }
-  HIP_CHECK(hipDeviceSynchronize());   // (an earlier forward may still read the operand)
-  HIP_CHECK(hipMemcpy(m.w3 + (size_t)m.row_off * 3 * K, tmp.data(), tmp.size() * sizeof(f16), hipMemcpyHostToDevice));
+  ws.load(name_c, host, dtype, shape, ndim);
 }
 
 Act ldiff_textenc::layernorm(const Act& x, const NormW& w) {
@@ -163,19 +124,6 @@ Act ldiff_textenc::linear(const TextLinW& w, const Act& x, const Act* res, bool 
   launch_igemm(p, pl, ex.s);
   if (p.splitk_ws) ex.arena.free(p.splitk_ws);   // stream-ordered reuse
   return y;
-}
-
-int ldiff_textenc::missing() const {
-  missing_cache.clear();
-  if (!tok_loaded) missing_cache.push_back(TOK_NAME);
-  if (!pos_loaded) missing_cache.push_back(POS_NAME);
-  const int n = ws.missing();
-  for (int i = 0; i < n; ++i) missing_cache.push_back(ws.missing_name(i));
-  return (int)missing_cache.size();
-}
-const char* ldiff_textenc::missing_name(int i) const {
-  if (i < 0 || i >= (int)missing_cache.size()) return "";
-  return missing_cache[i].c_str();
 }
 
 void ldiff_textenc::forward_impl(const int* ids, int B, int L, int project, void* out, int out_dtype, hipStream_t s) {
@@ -235,7 +183,7 @@ void ldiff_textenc::forward(const int32_t* ids_host, int B, int L, int project, 
   for (int i = 0; i < M; ++i)
     LDIFF_CHECK(ids_host[i] >= 0 && ids_host[i] < cfg.vocab_size, LDIFF_ERR_INVALID, "textenc_forward: ids[%d][%d] = %d outside 0..vocab_size - 1 = %d", i / L, i % L, (int)ids_host[i],
                 cfg.vocab_size - 1);
-  LDIFF_CHECK(missing() == 0, LDIFF_ERR_STATE, "textenc: %d weight tensors not loaded (first: %s)", missing(), missing_name(0));
+  LDIFF_CHECK(ws.missing() == 0, LDIFF_ERR_STATE, "textenc: %d weight tensors not loaded (first: %s)", ws.missing(), ws.missing_name(0));
   LDIFF_CHECK(!project || proj_dim > 0, LDIFF_ERR_STATE, "textenc_forward: project = 1 needs proj.weight / proj.bias loaded");
   HIP_CHECK(hipSetDevice(device));
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -249,7 +197,7 @@ void ldiff_textenc::forward(const int32_t* ids_host, int B, int L, int project, 
     forward_impl(st_ids.as<int>(), B, L, project, out, out_dtype, s);
     return;
   }
-  gc.run(s, [&] { return GraphCache::Key{B, L, project, out_dtype, ws.generation, emb_gen, (long long)ex.arena.capacity(), (long long)reinterpret_cast<uintptr_t>(st_ids.p)}; },
+  gc.run(s, [&] { return GraphCache::Key{B, L, project, out_dtype, ws.generation, (long long)ex.arena.capacity(), (long long)reinterpret_cast<uintptr_t>(st_ids.p)}; },
          {{&st_ids, n_ids}, {&st_out, n_out}},
          [&] { forward_impl(st_ids.as<int>(), B, L, project, out, out_dtype, s); },
          [&](hipStream_t cap) { forward_impl(st_ids.as<int>(), B, L, project, st_out.p, out_dtype, cap); },

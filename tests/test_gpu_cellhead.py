@@ -471,6 +471,28 @@ def test_load_errors():
     ResNetClassifier(NC, dict(sd, **{"encoder.1.num_batches_tracked": torch.tensor(7)}), DEV, spec["layers"], spec["width"], spec["adapter"])   # accepted and dropped
 
 
+def test_partial_reload_of_a_folded_group():
+    """A conv is folded with its BatchNorm at the first forward, so one tensor of the group alone cannot be reloaded: the next forward refuses it and names
+    the rule.  The group's five tensors loaded together are taken, and the output is a fresh handle's built from the same values, bit for bit."""
+    spec = REDUCED
+    make = lambda sd: ResNetClassifier(NC, sd, DEV, spec["layers"], spec["width"], spec["adapter"])
+    sd = network_case("reduced", 5, 22)["sd"]
+    x = resnet_ref.to_nhwc8(torch.randn((2, 3, spec["S"], spec["S"]), generator=torch.Generator().manual_seed(25))).to(DEV)
+    group = ["encoder.4.0.conv1.weight"] + ["encoder.4.0.bn1." + v for v in ("weight", "bias", "running_mean", "running_var")]
+    gamma = sd["encoder.4.0.bn1.weight"] * 1.5 + 0.25
+    net = make(sd)
+    before = net(x)
+    net.load_state_dict({"encoder.4.0.bn1.weight": gamma})
+    with pytest.raises(RuntimeError, match="was folded"):
+        net(x)
+    sd2 = dict(sd, **{"encoder.4.0.bn1.weight": gamma})
+    net.load_state_dict({k: sd2[k] for k in group})
+    got, ref = net(x), make(sd2).set_graph(False)(x)
+    assert not torch.equal(ref[0], before[0]), "the reloaded gamma must change the logits"
+    assert torch.equal(got[0], ref[0]) and torch.equal(got[1], ref[1])
+    net.check_finite()
+
+
 # ---- 7. end to end --------------------------------------------------------------------------------------------------------------------------------
 # Measured on the MI355X for the end-to-end case below: max |lib - f64| over the logits of its 31 instances.  The tie margin is twice this figure, and the run's own
 # error is asserted against twice it.

@@ -231,6 +231,34 @@ def test_replay_serves_new_ids_bit_for_bit():
     enc.check_finite()
 
 
+def test_reload_equals_a_fresh_handle():
+    """One handle under graph replay: checkpoint A, then checkpoint B whole (tables, layers, projection), then A's token table alone.  After each load the
+    outputs equal, bit for bit, the eager output of a fresh handle built from the same tensors, and only B's own graph counts replays: the tables take
+    part in the checkpoint generation like every other tensor."""
+    name, tok = "h64_q", "text_model.embeddings.token_embedding.weight"
+    (hf_a, proj_a), (hf_b, proj_b) = _hf_model(name, seed=0), _hf_model(name, seed=3)
+    sd_a, sd_b = (weights.normalize_clip_text_keys(hf.state_dict()) for hf in (hf_a, hf_b))
+    ids = _ids(name, 2, 5, 21)
+    fresh = lambda sd, proj: models.CLIPTextModel(hf_a.config.to_dict(), sd, DEV).load_projection(proj).set_graph(False).project(ids).clone()
+    ref_a, ref_b = fresh(sd_a, proj_a), fresh(sd_b, proj_b)
+    ref_ba = fresh({**sd_b, tok: sd_a[tok]}, proj_b)
+    assert not torch.equal(ref_a, ref_b) and not torch.equal(ref_b, ref_ba), "the three checkpoints must give different outputs"
+    enc = models.CLIPTextModel(hf_a.config.to_dict(), sd_a, DEV).load_projection(proj_a)
+    for _ in range(3):                                              # eager, capture + replay, replay
+        assert torch.equal(enc.project(ids), ref_a)
+    assert enc.graph_replays == 2
+    enc.load_state_dict(sd_b)
+    enc.load_projection(proj_b)
+    for i in range(3):                                              # eager again (another checkpoint generation), capture + replay, replay
+        assert torch.equal(enc.project(ids), ref_b), f"forward {i} after the reload differs from a fresh handle's"
+    assert enc.graph_replays == 4, "after the reload only B's own graph may count replays"
+    enc.load_state_dict({tok: sd_a[tok]})
+    for i in range(3):
+        assert torch.equal(enc.project(ids), ref_ba), f"forward {i} after the token table's reload differs from a fresh handle's"
+    assert enc.graph_replays == 6
+    enc.check_finite()
+
+
 # ---- 5. the shim end to end ------------------------------------------------------------------------------------------------------------------
 def _tiny_sd_dirs(tmp_path, hidden=64):
     """An SD directory (tiny UNet / VAE, a character-level CLIP tokenizer, a CLIPTextModel of width `hidden` written by `transformers`) and a fine-tuned
