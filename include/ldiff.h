@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define LDIFF_VERSION 204 /* 0.2.0.4: + ldiff_op_in_train_fwd / _bwd (InstanceNorm + LeakyReLU with saved statistics), ldiff_op_dice_ce (nnU-Net deep-supervision loss of one scale, value and gradient), ldiff_op_sgd_nesterov_multi; 0.2.0.3: + ldiff_confusion (per-image confusion matrices of masks or logits against labels, accumulated on the device), ldiff_seg_metrics (host: Dice / IoU / pixel accuracy / frequency-weighted IoU from one matrix); 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
+#define LDIFF_VERSION 205 /* 0.2.0.5: + ldiff_unet_set_plan_batch / ldiff_vae_set_plan_batch / ldiff_controlnet_set_plan_batch (batch-invariant mode: every launch planned for a nominal batch), ldiff_op_conv_pb, ldiff_op_attention_pb, ldiff_op_gn_stats_pb; 0.2.0.4: + ldiff_op_in_train_fwd / _bwd (InstanceNorm + LeakyReLU with saved statistics), ldiff_op_dice_ce (nnU-Net deep-supervision loss of one scale, value and gradient), ldiff_op_sgd_nesterov_multi; 0.2.0.3: + ldiff_confusion (per-image confusion matrices of masks or logits against labels, accumulated on the device), ldiff_seg_metrics (host: Dice / IoU / pixel accuracy / frequency-weighted IoU from one matrix); 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
 #define LDIFF_MAX_BLOCKS 8
 
 typedef enum { LDIFF_OK = 0, LDIFF_ERR_INVALID = -1, LDIFF_ERR_RUNTIME = -2, LDIFF_ERR_STATE = -3, LDIFF_ERR_NONFINITE = -4 } ldiff_status;
@@ -89,6 +89,19 @@ int ldiff_unet_load(ldiff_unet*, const char* name, const void* host_ptr, int dty
  *   1 = residual stream kept as fp16 hi|lo pairs (adds to fp32 round-off), stream-carrying contractions on split operands (default)
  *   2 = every conv / linear operand split (K doubled): ~1e-4 */
 int ldiff_unet_set_precision(ldiff_unet*, int mode);
+/* Plan batch n (default 0 = off: nothing changes).  By default the kernel, tile, split-K count, unit shape and GroupNorm form of a launch are chosen
+ * from its workgroup count, which depends on B: an image alone and the same image inside a batch then differ in the last bits (DESIGN.md "Batch
+ * invariance").  With n >= 1 every such choice is made AS IF the batch were n, while the launch runs at its real size.  The contract: an image
+ * submitted in ANY batch B <= n -- alone, first or last of a short shard -- gets bit-identical results (UNet output; through ldiff_sample: latents,
+ * features, rgb), on one device model and one precision mode.  Not promised: equality across different n, across devices with different CU counts,
+ * or with n = 0.  n = B reproduces the default mode's plans at that B bit for bit (so n = the largest batch any rank submits keeps the tuned plans).
+ *   - n < 0: LDIFF_ERR_INVALID.  A forward with B > n > 0 (and a set_context with B_ctx > n): LDIFF_ERR_INVALID, naming both numbers.
+ *   - a different n makes the next forward capture its graph anew (as a set_precision does) and rebuilds derived weight layouts where the plan names others.
+ *   - the cross-attention K / V of set_context are planned too (at n L rows, whether B_ctx is 1 or B): after a change of n call ldiff_unet_set_context
+ *     again; a forward before that is LDIFF_ERR_STATE.
+ *   - an attached ControlNet must carry the same n at forward time, else LDIFF_ERR_INVALID.
+ * ldiff_sample takes the setting from the UNet and the VAE it borrows. */
+int ldiff_unet_set_plan_batch(ldiff_unet*, int n);
 /* One forward is ~390-450 kernel launches (384 at B = 8, 443 at B = 1 at SD-v1.5 size: ldiff_unet_graph_nodes).  With graphs on (default) the launch sequence of a (B, h, w, precision, context)
  * configuration is captured into a hipGraph on its second use and replayed from then on (input, timestep and output pass through
  * handle-owned staging buffers: any caller pointers, any timestep; bit-identical results).  Off: every forward is launched
@@ -130,6 +143,10 @@ int ldiff_controlnet_load(ldiff_controlnet*, const char* name, const void* host_
 int ldiff_controlnet_missing(ldiff_controlnet*);
 const char* ldiff_controlnet_missing_name(ldiff_controlnet*, int i);
 int ldiff_controlnet_set_precision(ldiff_controlnet*, int mode);   /* as ldiff_unet_set_precision; default 1 */
+/* As ldiff_unet_set_plan_batch, for the trunk, the zero convs and the conditioning embedding: an image's tensors are bit-identical in any batch B <= n.
+ * A different n drops the kept embedding and context projections (call ldiff_controlnet_set_cond and _set_context again; a forward before that is
+ * LDIFF_ERR_STATE) and whatever captured graph of a UNet holds this network's launches.  Attached to a UNet, both must carry the same n. */
+int ldiff_controlnet_set_plan_batch(ldiff_controlnet*, int n);
 int ldiff_controlnet_set_context(ldiff_controlnet*, const void* ctx_dev, int B_ctx, int L, void* stream);
 /* cond [B or 1, conditioning_channels, H, W] f32 NCHW, H x W = 8 x the latent size for the four-entry embedding: runs the conditioning embedding once and
  * keeps its result for every later forward (it depends on neither timestep nor latents, so a multi-pass loop pays for it once, as set_context does for K / V). */
@@ -275,6 +292,9 @@ int ldiff_vae_set_precision(ldiff_vae*, int encoder_mode, int decoder_mode);
  * it is not needed beyond the width-changing blocks' shortcut, which then runs as its own launch; large k pushes small activations of a healthy
  * checkpoint into fp16's subnormals, so use the smallest k that decodes (python: AutoencoderKL.fit_range_shift). */
 int ldiff_vae_set_range_shift(ldiff_vae*, int k);
+/* As ldiff_unet_set_plan_batch, for the encoder and the decoder graph (also the decodes ldiff_sample runs): moments, sample, image, rgb and luma of an image
+ * are bit-identical in any batch B <= n, under any one precision pair and range shift.  n < 0, and an encode / decode with B > n > 0: LDIFF_ERR_INVALID. */
+int ldiff_vae_set_plan_batch(ldiff_vae*, int n);
 int ldiff_vae_missing(ldiff_vae*);
 const char* ldiff_vae_missing_name(ldiff_vae*, int i);
 /* x [B,3,H,W] f32 NCHW -> moments [B, 2*latent, H/8, W/8] f32 NCHW (mean | logvar), i.e. quant_conv(encoder(x)) */
@@ -489,6 +509,10 @@ typedef struct {
                                                        act_out beside relu_out / silu_out / cls_conv = 1 / cond_conv = 1 / tconv / lrelu_in / seg_conv = 1: LDIFF_ERR_INVALID, never another route */
 } ldiff_conv_args;
 int ldiff_op_conv(const ldiff_conv_args*, void* stream);
+/* ldiff_op_conv with a plan batch n (ldiff_unet_set_plan_batch): 0 is ldiff_op_conv; n >= B: kernel, tile, split and unit shape are chosen as if the launch had n
+ * images (n Hout Wout rows), so the rows of an image come out bit-identical at every B <= n.  B > n, n < 0: LDIFF_ERR_INVALID.  (An entry point of its own and
+ * not a field appended to ldiff_conv_args: callers compiled against the struct as it is keep working.) */
+int ldiff_op_conv_pb(const ldiff_conv_args*, int plan_batch, void* stream);
 /* row blocks per image the launch would emit statistics for (0 = unsupported for this shape) */
 int ldiff_op_conv_stats_blocks(const ldiff_conv_args*);
 /* finalize producer-fused partial sums into per-(b,channel) scale/shift; part2 (second concat source) may be NULL */
@@ -512,6 +536,9 @@ int ldiff_op_crop_resize_norm(const void* rgb_u8, int H, int W, const void* boxe
 int ldiff_op_cls_head(const void* x, int B, int HW, int A, int ldx, const void* w_f32, const void* bias_f32, int C, void* logits_f32, void* labels_i32_or_null, void* stream);
 int ldiff_op_attention(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, int B, int heads,
                        int Lq, int Lk, int d, int64_t q_bstride, int64_t kv_bstride, int64_t o_bstride, float scale, void* stream);
+/* ldiff_op_attention with a plan batch (ldiff_unet_set_plan_batch): plan_batch = 0 is ldiff_op_attention; n >= B chooses the kernel as if the batch were n */
+int ldiff_op_attention_pb(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, int B, int heads,
+                          int Lq, int Lk, int d, int64_t q_bstride, int64_t kv_bstride, int64_t o_bstride, float scale, int plan_batch, void* stream);
 /* Causal self-attention over a short sequence (the text encoder's kernel, text_attn<d>): qkv [B L, ld] f16 is a fused projection output with Q | K | V in column
  * blocks of `hidden` (head h at columns h d of each), o [B L, ldo] f16.  One workgroup per (image, head); keys j > i are masked before an fp32 softmax over the whole
  * row, p is rounded once to fp16, the row sum is the fp32 sum of the unrounded p.  d % 16 == 0 in 16..128, 1 <= L <= 128, ld % 8 == 0, hidden % 8 == 0, ldo % 4 == 0.
@@ -525,6 +552,9 @@ int ldiff_op_attention_prescaled(const void* q, int ldq, const void* k, int ldk,
 /* sources are (pointer, channels C, row pitch ld (0 = C), lo offset (0 = plain, > 0 = split tensor hi|lo)) */
 int ldiff_op_gn_stats(const void* x, int C1, int ld1, int lo1, const void* x2, int C2, int ld2, int lo2, int B, int HW, int groups, float eps,
                       const void* gamma, const void* beta, void* scale, void* shift, void* stream);
+/* ldiff_op_gn_stats with a plan batch: 0 is ldiff_op_gn_stats; n >= B chooses the one-launch / two-launch form (gn_stats<1> / gn_stats<2>) as if the batch were n */
+int ldiff_op_gn_stats_pb(const void* x, int C1, int ld1, int lo1, const void* x2, int C2, int ld2, int lo2, int B, int HW, int groups, float eps,
+                         const void* gamma, const void* beta, void* scale, void* shift, int plan_batch, void* stream);
 int ldiff_op_layernorm(const void* x, int ldx, int x_lo, void* y, int rows, int C, const void* gamma, const void* beta, float eps, void* stream);
 /* LayerNorm folded into the linear layer that consumes it (BasicTransformerBlock norm1 -> to_q/k/v, norm2 -> attn2.to_q, norm3 -> ff.net.0.proj):
  *   y[rows, N] = LayerNorm(x; gamma, beta, eps)[rows, C] . w[N, C]^T + bias,  x as in ldiff_op_layernorm (x_lo > 0: split rows hi | lo),

@@ -60,6 +60,7 @@ SIGNATURES = {
     "ldiff_unet_create": (I, [C.POINTER(P), C.POINTER(UNetCfg), I]),
     "ldiff_unet_load": (I, [P, C.c_char_p, P, I, C.POINTER(I64), I]),
     "ldiff_unet_set_precision": (I, [P, I]),
+    "ldiff_unet_set_plan_batch": (I, [P, I]),
     "ldiff_unet_set_graph": (I, [P, I]),
     "ldiff_unet_graph_replays": (I64, [P]),
     "ldiff_unet_graph_nodes": (I64, [P]),
@@ -75,6 +76,7 @@ SIGNATURES = {
     "ldiff_controlnet_missing": (I, [P]),
     "ldiff_controlnet_missing_name": (C.c_char_p, [P, I]),
     "ldiff_controlnet_set_precision": (I, [P, I]),
+    "ldiff_controlnet_set_plan_batch": (I, [P, I]),
     "ldiff_controlnet_set_context": (I, [P, P, I, I, P]),
     "ldiff_controlnet_set_cond": (I, [P, P, I, I, I, P]),
     "ldiff_controlnet_forward": (I, [P, P, I, I, I, F, F, C.POINTER(P), I, P, P]),
@@ -114,6 +116,7 @@ SIGNATURES = {
     "ldiff_vae_load": (I, [P, C.c_char_p, P, I, C.POINTER(I64), I]),
     "ldiff_vae_set_precision": (I, [P, I, I]),
     "ldiff_vae_set_range_shift": (I, [P, I]),
+    "ldiff_vae_set_plan_batch": (I, [P, I]),
     "ldiff_vae_missing": (I, [P]),
     "ldiff_vae_missing_name": (C.c_char_p, [P, I]),
     "ldiff_vae_encode": (I, [P, P, I, I, I, P, P]),
@@ -140,6 +143,7 @@ SIGNATURES = {
     "ldiff_plms_timesteps": (I, [I, C.POINTER(I64), I]),
     "ldiff_pipeline_destroy": (None, [P]),
     "ldiff_op_conv": (I, [C.POINTER(ConvArgs), P]),
+    "ldiff_op_conv_pb": (I, [C.POINTER(ConvArgs), I, P]),
     "ldiff_op_conv_stats_blocks": (I, [C.POINTER(ConvArgs)]),
     "ldiff_op_gn_finalize": (I, [P, I, I, P, I, I, I, I, I, F, P, P, P, P, P]),
     "ldiff_op_in_finalize": (I, [P, I, P, I, I, I, I, F, P, P, P, P, I, I, I, P]),
@@ -147,8 +151,10 @@ SIGNATURES = {
     "ldiff_op_crop_resize_norm": (I, [P, I, I, P, I, P, I, C.POINTER(C.c_double), C.POINTER(C.c_double), P, P]),
     "ldiff_op_cls_head": (I, [P, I, I, I, I, P, P, I, P, P, P]),
     "ldiff_op_attention": (I, [P, I, P, I, P, I, P, I, I, I, I, I, I, I64, I64, I64, F, P]),
+    "ldiff_op_attention_pb": (I, [P, I, P, I, P, I, P, I, I, I, I, I, I, I64, I64, I64, F, I, P]),
     "ldiff_op_attention_prescaled": (I, [P, I, P, I, P, I, P, I, I, I, I, I, I, I64, I64, I64, P]),
     "ldiff_op_gn_stats": (I, [P, I, I, I, P, I, I, I, I, I, I, F, P, P, P, P, P]),
+    "ldiff_op_gn_stats_pb": (I, [P, I, I, I, P, I, I, I, I, I, I, F, P, P, P, P, I, P]),
     "ldiff_op_layernorm": (I, [P, I, I, P, I, I, P, P, F, P]),
     "ldiff_op_ln_linear": (I, [P, I, I, I, I, P, P, F, P, I, I, P, I, P, I, I, F, P]),
     "ldiff_op_norm_apply": (I, [P, I, I, I, P, I, I, I, I, I, P, P, I, P, I, I, P]),

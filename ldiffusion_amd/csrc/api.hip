@@ -109,6 +109,13 @@ int ldiff_unet_set_precision(ldiff_unet* u, int mode) {
   u->precision = mode;
   API_END
 }
+int ldiff_unet_set_plan_batch(ldiff_unet* u, int n) {
+  API_BEGIN
+  LDIFF_CHECK(u, LDIFF_ERR_INVALID, "unet_set_plan_batch: null handle");
+  LDIFF_CHECK(n >= 0, LDIFF_ERR_INVALID, "unet_set_plan_batch: n = %d must be >= 0 (0 = off)", n);
+  u->set_plan_batch(n);
+  API_END
+}
 int ldiff_unet_set_graph(ldiff_unet* u, int on) { return set_graph(u, on, "unet_set_graph"); }
 int64_t ldiff_unet_graph_replays(ldiff_unet* u) { return u ? (int64_t)u->gc.replays : -1; }
 int64_t ldiff_unet_graph_nodes(ldiff_unet* u) { return u ? (int64_t)u->gc.nodes : -1; }
@@ -173,6 +180,13 @@ int ldiff_controlnet_set_precision(ldiff_controlnet* c, int mode) {
   API_BEGIN
   LDIFF_CHECK(c && mode >= PREC_FAST && mode <= PREC_FULL, LDIFF_ERR_INVALID, "controlnet_set_precision: mode must be 0, 1 or 2");
   c->trunk.precision = mode;
+  API_END
+}
+int ldiff_controlnet_set_plan_batch(ldiff_controlnet* c, int n) {
+  API_BEGIN
+  LDIFF_CHECK(c, LDIFF_ERR_INVALID, "controlnet_set_plan_batch: null handle");
+  LDIFF_CHECK(n >= 0, LDIFF_ERR_INVALID, "controlnet_set_plan_batch: n = %d must be >= 0 (0 = off)", n);
+  c->set_plan_batch(n);
   API_END
 }
 int ldiff_controlnet_set_context(ldiff_controlnet* c, const void* ctx_dev, int B_ctx, int L, void* stream) {
@@ -347,6 +361,13 @@ int ldiff_vae_set_range_shift(ldiff_vae* v, int k) {
   API_BEGIN
   LDIFF_CHECK(v && k >= 0 && k <= 16, LDIFF_ERR_INVALID, "vae_set_range_shift: k = %d outside 0..16", k);
   v->set_range_shift(k);
+  API_END
+}
+int ldiff_vae_set_plan_batch(ldiff_vae* v, int n) {
+  API_BEGIN
+  LDIFF_CHECK(v, LDIFF_ERR_INVALID, "vae_set_plan_batch: null handle");
+  LDIFF_CHECK(n >= 0, LDIFF_ERR_INVALID, "vae_set_plan_batch: n = %d must be >= 0 (0 = off)", n);
+  v->set_plan_batch(n);
   API_END
 }
 int ldiff_vae_missing(ldiff_vae* v) { return missing(v); }
@@ -739,10 +760,12 @@ static void conv_args_to_params(const ldiff_conv_args* a, ConvParams& p) {
   p.act_out = a->act_out;   // (plan_conv checks 0 | 1 | 2 and the route)
   if (p.tconv) p.K = a->C1;   // one GEMM over the coarse map: the four taps are column blocks, not K
 }
-int ldiff_op_conv(const ldiff_conv_args* a, void* stream) {
+int ldiff_op_conv_pb(const ldiff_conv_args* a, int plan_batch, void* stream) {
   API_BEGIN
   ConvParams p;
   conv_args_to_params(a, p);
+  LDIFF_CHECK(plan_batch >= 0, LDIFF_ERR_INVALID, "op_conv: plan_batch = %d must be >= 0 (0 = off)", plan_batch);
+  if (plan_batch > 0) { p.plan_B = plan_batch; p.plan_M = plan_batch * a->Hout * a->Wout; }   // (plan_conv refuses B > plan_batch)
   if (a->splitk)   // an explicit split count (tests, timing), taken as the executors' plans are
     LDIFF_CHECK(a->splitk >= 2 && a->splitk <= 16 && !p.out_f32 && !p.geglu && !p.ups && !p.xs && !p.lo8_slab0 && p.df_force <= 0, LDIFF_ERR_INVALID,
                 "op_conv: splitk = %d needs 2..16 splits, an fp16 output and a plain 3x3 / 1x1 / strided launch", a->splitk);
@@ -799,6 +822,7 @@ int ldiff_op_conv(const ldiff_conv_args* a, void* stream) {
   launch_igemm(p, pl, st);
   API_END
 }
+int ldiff_op_conv(const ldiff_conv_args* a, void* stream) { return ldiff_op_conv_pb(a, 0, stream); }
 int ldiff_op_in_finalize(const void* part, int R, const void* x_f16, int ldx, int B, int HW, int C, float eps, const void* gamma, const void* beta, void* scale, void* shift,
                          int ld_ss, int ss_off, int ident, void* stream) {
   API_BEGIN
@@ -828,16 +852,21 @@ int ldiff_op_gn_finalize(const void* part1, int R1, int C1, const void* part2, i
                      (float*)scale, (float*)shift, (hipStream_t)stream);
   API_END
 }
-int ldiff_op_attention(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, int B, int heads, int Lq,
-                       int Lk, int d, int64_t q_bstride, int64_t kv_bstride, int64_t o_bstride, float scale, void* stream) {
+int ldiff_op_attention_pb(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, int B, int heads, int Lq,
+                          int Lk, int d, int64_t q_bstride, int64_t kv_bstride, int64_t o_bstride, float scale, int plan_batch, void* stream) {
   API_BEGIN
-  LDIFF_CHECK(q && k && v && o && B >= 1 && heads >= 1, LDIFF_ERR_INVALID, "op_attention: bad arguments");
+  LDIFF_CHECK(q && k && v && o && B >= 1 && heads >= 1 && plan_batch >= 0, LDIFF_ERR_INVALID, "op_attention: bad arguments");
   AttnParams p;
   p.q = (const f16*)q; p.ldq = ldq; p.k = (const f16*)k; p.ldk = ldk; p.v = (const f16*)v; p.ldv = ldv; p.o = (f16*)o; p.ldo = ldo;
   p.B = B; p.heads = heads; p.Lq = Lq; p.Lk = Lk; p.d = d;
   p.q_bstride = q_bstride; p.kv_bstride = kv_bstride; p.o_bstride = o_bstride; p.scale = scale;
+  p.plan_B = plan_batch;   // (launch_attention refuses B > plan_batch > 0)
   launch_attention(p, (hipStream_t)stream);
   API_END
+}
+int ldiff_op_attention(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, int B, int heads, int Lq,
+                       int Lk, int d, int64_t q_bstride, int64_t kv_bstride, int64_t o_bstride, float scale, void* stream) {
+  return ldiff_op_attention_pb(q, ldq, k, ldk, v, ldv, o, ldo, B, heads, Lq, Lk, d, q_bstride, kv_bstride, o_bstride, scale, 0, stream);
 }
 int ldiff_op_attention_prescaled(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, int B, int heads, int Lq,
                                  int Lk, int d, int64_t q_bstride, int64_t kv_bstride, int64_t o_bstride, void* stream) {
@@ -851,15 +880,19 @@ int ldiff_op_attention_prescaled(const void* q, int ldq, const void* k, int ldk,
   launch_attention(p, (hipStream_t)stream);
   API_END
 }
-int ldiff_op_gn_stats(const void* x, int C1, int ld1, int lo1, const void* x2, int C2, int ld2, int lo2, int B, int HW, int groups, float eps,
-                      const void* gamma, const void* beta, void* scale, void* shift, void* stream) {
+int ldiff_op_gn_stats_pb(const void* x, int C1, int ld1, int lo1, const void* x2, int C2, int ld2, int lo2, int B, int HW, int groups, float eps,
+                         const void* gamma, const void* beta, void* scale, void* shift, int plan_batch, void* stream) {
   API_BEGIN
-  LDIFF_CHECK(x && gamma && beta && scale && shift && B >= 1 && HW >= 1 && groups >= 1, LDIFF_ERR_INVALID, "op_gn_stats: bad arguments");
+  LDIFF_CHECK(x && gamma && beta && scale && shift && B >= 1 && HW >= 1 && groups >= 1 && plan_batch >= 0, LDIFF_ERR_INVALID, "op_gn_stats: bad arguments");
   const size_t bytes = gn_partial_bytes(B, HW, C1 + C2);
   float* partial = (float*)op_scratch((hipStream_t)stream, 2, bytes);
   launch_gn_stats(SrcView{(const f16*)x, C1, ld1, lo1}, SrcView{(const f16*)x2, C2, ld2, lo2}, B, HW, groups, eps, (const float*)gamma,
-                  (const float*)beta, partial, bytes, (float*)scale, (float*)shift, (hipStream_t)stream);
+                  (const float*)beta, partial, bytes, (float*)scale, (float*)shift, (hipStream_t)stream, nullptr, plan_batch);
   API_END
+}
+int ldiff_op_gn_stats(const void* x, int C1, int ld1, int lo1, const void* x2, int C2, int ld2, int lo2, int B, int HW, int groups, float eps,
+                      const void* gamma, const void* beta, void* scale, void* shift, void* stream) {
+  return ldiff_op_gn_stats_pb(x, C1, ld1, lo1, x2, C2, ld2, lo2, B, HW, groups, eps, gamma, beta, scale, shift, 0, stream);
 }
 int ldiff_op_layernorm(const void* x, int ldx, int x_lo, void* y, int rows, int C, const void* gamma, const void* beta, float eps, void* stream) {
   API_BEGIN

@@ -119,7 +119,18 @@ struct ConvParams {
   // An activation BEHIND the sum of a linear layer (y = act(sum + bias), fp32, one fp16 rounding; ldiff_conv_args.act_out): 1 = quick_gelu v sigmoid(1.702 v), 2 = gelu
   // (erf form).  The LDS-DMA GEMM only (gemm_dma<...>, unsplit, fp16 output, plain or split, without residual): plan_conv refuses it for any other launch
   int act_out = 0;
+  // Plan batch (ldiff_*_set_plan_batch, DESIGN.md "Batch invariance"): 0 = every choice is made from this launch's own B and M; > 0 = every choice that depends
+  // on the batch -- kernel family, tile, split-K count, unit shape, tile order -- is made for the NOMINAL launch, B := plan_B and M := plan_M (nominal_launch
+  // below), while grids, buffer extents and loop bounds keep the real B and M.  plan_conv refuses B > plan_B or M > plan_M: every size cap a predicate
+  // applies then holds for the real launch too.  (plan_M is stated, not derived: the rows of a time-embedding or context launch are the batch itself.)
+  int plan_B = 0, plan_M = 0;
 };
+// The launch every batch-dependent choice reads: p itself without a plan batch
+inline ConvParams nominal_launch(const ConvParams& p) {
+  ConvParams q = p;
+  if (p.plan_B > 0) { q.B = p.plan_B; q.M = p.plan_M; }
+  return q;
+}
 constexpr int LO8_SHIFT = 15;   // lo = x - fp16(x) of a GroupNorm + SiLU output: |lo| <= half an fp16 ulp = 2^-7 for |x| < 32, so lo * 2^15 <= 256 stays inside e4m3's 448;
                                 // for |x| in [32, 64) it reaches 512 and saturates at 448 (the correction term is clamped, harmless), as for everything beyond
 // [Nrows][taps][Cin] fp16 -> [Nrows][taps][Cin fp16 | Cin e4m3 of w * 2^sw], sw = floor(log2(448 / max |w|)); scale_out[0] = 127 - sw (one int)
@@ -198,7 +209,8 @@ void launch_conv3x3p(const ConvParams& p, hipStream_t s);
 bool lngemm_eligible(int C, int N, int ldx, int x_lo, int ldy, bool geglu);
 void launch_lngemm_tile_weights(const f16* w, f16* wt, int N, int C, hipStream_t s);   // [N][C] -> the panel images the kernel streams (N*C fp16)
 void launch_lngemm(const f16* x, int ldx, int x_lo, int M, int C, const float* gamma, const float* beta, float eps, const f16* w_tiled, int N,
-                   const float* bias, bool geglu, f16* y, int ldy, hipStream_t s, int qcols = 0, float qscale = 1.0f);   // columns [0, qcols) *= qscale before rounding
+                   const float* bias, bool geglu, f16* y, int ldy, hipStream_t s, int qcols = 0, float qscale = 1.0f,   // columns [0, qcols) *= qscale before rounding
+                   int plan_M = 0);   // plan batch (ConvParams::plan_M): > 0 = the column split is chosen as if the launch had plan_M (>= M) rows
 bool gemm_dma_eligible(const ConvParams& p);
 // producer / consumer ("dataflow") GEMM for 1x1 convs / linears whose unit list fills the chip: kernels_gemm_df.hip
 bool gemm_df_selected(const ConvParams& p);
@@ -220,6 +232,7 @@ struct AttnParams {
   int prescaled = 0;          // q already holds Q * scale * log2(e) (rounded once, by its producer): kernels_attn.hip PRE; `scale` is then unused
   float rescale_log2 = 0.0f;  // set by the launcher: online-softmax rescale threshold in log2 units (kernels_attn.hip; 0 = the maximum moves on every growth)
   int xcd_order = 0;          // set by the launcher: workgroup -> (query tile, head, image) through the XCD-aware remap (kernels_attn.hip)
+  int plan_B = 0;             // plan batch (ConvParams::plan_B): > 0 = the kernel is chosen as if B were plan_B (>= B); the launch runs at B
 };
 void launch_attention(const AttnParams& p, hipStream_t s);
 bool attention_prescale_supported(int d);
@@ -242,7 +255,8 @@ void launch_f32_to_f16(const float* x, f16* y, long long n, hipStream_t s);
 struct SrcView { const f16* p; int C, ld, lo; };
 void launch_gn_stats(SrcView x1, SrcView x2 /* p == nullptr: none */, int B, int HW, int groups, float eps,
                      const float* gamma, const float* beta, float* partial /*workspace*/, size_t partial_bytes,
-                     float* scale, float* shift, hipStream_t s, int* nonfinite = nullptr /* sticky flag of the owning handle: set when a total is not finite */);
+                     float* scale, float* shift, hipStream_t s, int* nonfinite = nullptr /* sticky flag of the owning handle: set when a total is not finite */,
+                     int plan_B = 0 /* plan batch (ConvParams::plan_B): > 0 = the one-launch / two-launch form is chosen as if B were plan_B (>= B) */);
 size_t gn_partial_bytes(int B, int HW, int C);
 void launch_layernorm(SrcView x, f16* y, int rows, const float* gamma, const float* beta, float eps, hipStream_t s);
 // y[m, c] = act(x[m, c] * scale[b, c] + shift[b, c]) over the channel concat of one or two sources, written plain (y_lo = 0,

@@ -112,7 +112,11 @@ bool conv_lo8_enabled() {
 ConvPlan plan_conv(ConvParams& p, const ConvAsk& ask) {
   ConvPlan pl;
   LDIFF_CHECK(p.out_shift >= 0 && p.out_shift <= 16, LDIFF_ERR_INVALID, "conv: range shift %d outside 0..16", p.out_shift);
-  ConvParams q = p;   // the launch as the predicates see it
+  LDIFF_CHECK(p.plan_B >= 0 && (p.plan_B == 0 || (p.B <= p.plan_B && p.M <= p.plan_M)), LDIFF_ERR_INVALID,
+              "conv: a launch of batch %d (%d rows) under a plan batch of %d (%d rows): the plan batch is the largest batch a handle takes", p.B, p.M, p.plan_B, p.plan_M);
+  // the launch as the predicates see it: under a plan batch the nominal one, so that kernel, split, tile and layout do not depend on the batch the images travel in
+  // (what comes back -- splitk, stats_R, the fold strides -- is per image or per K, never per batch)
+  ConvParams q = nominal_launch(p);
   // LDIFF_GEMM_DF: 0 = no dataflow GEMM, 1 (default) = where its unit list fills the chip, 2 = every launch it takes (tests, A/B timing);
   // a launch's own ConvParams::df_force comes first
   static const int df_mode = [] { const char* e = getenv("LDIFF_GEMM_DF"); return e ? atoi(e) : 1; }();

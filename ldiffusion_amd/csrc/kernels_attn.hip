@@ -1254,7 +1254,7 @@ static bool xattn_selected(const AttnParams& p) {
   if ((size_t)2 * 16 * (C + 64) * sizeof(f16) > 150 * 1024) return false;
   // enough workgroups to fill the chip twice: measured same box at B = 8 -- 4096 x 6, d = 40 (512 workgroups): 15.9 -> 13.1 us; 1024 x 6, d = 80 (128):
   // 8.1 -> 11.8 us and 256 x 6, d = 160 (32): 8.1 -> 18.0 us (too few workgroups for the K / V staging): the generic kernel keeps those (mode 2: always)
-  return mode == 2 || (long long)p.B * ((p.Lq + 64 * XRB - 1) / (64 * XRB)) >= 384;
+  return mode == 2 || (long long)(p.plan_B > 0 ? p.plan_B : p.B) * ((p.Lq + 64 * XRB - 1) / (64 * XRB)) >= 384;   // (from the plan batch where one is set)
 }
 
 // head dims whose self-attention can take Q pre-multiplied by scale * log2(e) (AttnParams::prescaled)
@@ -1264,6 +1264,7 @@ void launch_attention(const AttnParams& p, hipStream_t s) {
   LDIFF_CHECK(p.d % 8 == 0 && p.d > 0 && p.d <= 512, LDIFF_ERR_INVALID, "attention: head dim %d must be a multiple of 8 and <= 512", p.d);
   LDIFF_CHECK(p.ldq % 8 == 0 && p.ldk % 8 == 0 && p.ldv % 8 == 0 && p.ldo % 4 == 0, LDIFF_ERR_INVALID, "attention: row strides must be multiples of 8");
   LDIFF_CHECK(p.Lk > 0 && p.Lq > 0, LDIFF_ERR_INVALID, "attention: empty sequence (Lq=%d Lk=%d)", p.Lq, p.Lk);
+  LDIFF_CHECK(p.plan_B == 0 || p.plan_B >= p.B, LDIFF_ERR_INVALID, "attention: batch %d under a plan batch of %d", p.B, p.plan_B);
   const int d = p.d;
   if (xattn_selected(p)) {
     if (d == 40) launch_xattn<40>(p, s); else if (d == 80) launch_xattn<80>(p, s); else launch_xattn<160>(p, s);

@@ -898,7 +898,7 @@ void launch_splitk_reduce_impl(const ConvParams& p, hipStream_t s) {
 // at most n pixel tiles per image.
 static bool conv3x3_img_fast(const ConvParams& p, int tiles_per_image, int ntn, int bn) {
   static const int mode = [] { const char* e = getenv("LDIFF_CONV3X3_IMGFAST"); return e ? atoi(e) : -1; }();
-  if (mode == 0 || ntn <= 1 || p.B <= 1) return false;
+  if (mode == 0 || ntn <= 1 || (p.plan_B > 0 ? p.plan_B : p.B) <= 1) return false;
   if (mode > 0) return tiles_per_image <= mode;
   (void)bn;
   return tiles_per_image <= 2;   // 8 x 8 and 16 x 16 maps (measured, same box: 1280 -> 1280 at 8 x 8 45.6 -> 39.5 us, the 2560-channel concat

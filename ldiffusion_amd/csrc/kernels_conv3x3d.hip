@@ -897,7 +897,8 @@ void launch_c3d(const ConvParams& p, hipStream_t s) {
   // 64^2 maps (the four channel tiles of a pixel tile re-read its halo from L2) it costs 0 ... 4 % (profiles/r05_conv3x3d_cache_hints.txt).  LDIFF_C3D_NT=0 / 1: never / always.
   static const int nt_env = [] { const char* e = getenv("LDIFF_C3D_NT"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
   ConvParams q = p;
-  const double in_b = (double)p.B * p.Hin * p.Win * p.C1 * 2.0, out_b = (double)p.M * p.N * 2.0;
+  const ConvParams nom = nominal_launch(p);
+  const double in_b = (double)nom.B * p.Hin * p.Win * p.C1 * 2.0, out_b = (double)nom.M * p.N * 2.0;
   q.nt_hint = nt_env >= 0 ? nt_env : ((p.short_runs || (in_b >= 192e6 && out_b >= 192e6)) ? 1 : 0);   // beside the UNet stream: always (whole step, same box: 155.5 / 155.0 ms without, 154.4 / 153.1 with the size rule, 152.8 / 153.6 always)
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), D_LDS, s, q, units);
   HIP_CHECK(hipGetLastError());

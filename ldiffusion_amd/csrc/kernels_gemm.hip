@@ -372,7 +372,7 @@ void launch_g(const ConvParams& p, hipStream_t s) {
   const int S = p.splitk > 1 ? p.splitk : 1;
   LDIFF_CHECK(S == 1 || (p.splitk_ws && !p.geglu && !p.out_f32 && p.w_bstride == 0 && !p.act_out), LDIFF_ERR_INVALID, "gemm: split-K needs a workspace and a plain fp16 epilogue");   // (fused statistics of a split launch: by the reduce kernel)
   ConvParams q = p;
-  q.tiles_m = ntm; q.img_fast = gemm_m_fast(p, ntm, ntn) ? 1 : 0;
+  q.tiles_m = ntm; q.img_fast = gemm_m_fast(nominal_launch(p), ntm, ntn) ? 1 : 0;
   hipLaunchKernelGGL(kern, dim3(ntm * ntn, S), dim3(256), smem, s, q);
   if (S > 1) { HIP_CHECK(hipGetLastError()); launch_splitk_reduce(p, s); }
   HIP_CHECK(hipGetLastError());

@@ -388,9 +388,10 @@ void launch_lngemm_tile_weights(const f16* w, f16* wt, int N, int C, hipStream_t
 }
 
 void launch_lngemm(const f16* x, int ldx, int x_lo, int M, int C, const float* gamma, const float* beta, float eps, const f16* w_tiled, int N,
-                   const float* bias, bool geglu, f16* y, int ldy, hipStream_t s, int qcols, float qscale) {
+                   const float* bias, bool geglu, f16* y, int ldy, hipStream_t s, int qcols, float qscale, int plan_M) {
   LDIFF_CHECK(qcols >= 0 && qcols % BN == 0 && qcols <= N && !(geglu && qcols), LDIFF_ERR_INVALID, "ln_linear: scaled column count %d must be a multiple of 64 within N", qcols);
   LDIFF_CHECK(lngemm_eligible(C, N, ldx, x_lo, ldy, geglu) && M > 0, LDIFF_ERR_INVALID, "ln_linear: unsupported shape (C=%d N=%d M=%d)", C, N, M);
+  LDIFF_CHECK(plan_M == 0 || plan_M >= M, LDIFF_ERR_INVALID, "ln_linear: %d rows under a plan of %d rows", M, plan_M);
   LDIFF_CHECK((long long)M * ldx * 2 < (1LL << 40) && (long long)N * C * 2 < (1LL << 31), LDIFF_ERR_INVALID, "ln_linear: operand too large");
   LnGemmParams p;
   p.x = x; p.ld = ldx; p.lo = x_lo; p.M = M; p.gamma = gamma; p.beta = beta; p.eps = eps;
@@ -401,7 +402,7 @@ void launch_lngemm(const f16* x, int ldx, int x_lo, int M, int C, const float* g
   static const int ns_env = [] { const char* e = getenv("LDIFF_LNGEMM_NSPLIT"); return e ? atoi(e) : 0; }();
   const int nchunks = N / BN, cus = num_cus();
   p.npanels = (M + ROWS - 1) / ROWS;
-  int ns = ns_env ? ns_env : cus / p.npanels;
+  int ns = ns_env ? ns_env : cus / (plan_M > 0 ? (plan_M + ROWS - 1) / ROWS : p.npanels);   // (from the plan batch's panels where one is set)
   ns = ns < 1 ? 1 : ns;
   if (ns > nchunks / 2) ns = nchunks / 2 > 0 ? nchunks / 2 : 1;
   p.nsplit = ns;

@@ -659,7 +659,7 @@ void launch_df_l(const ConvParams& p, hipStream_t s) {
 }
 template <int FL>
 void launch_df_f(const ConvParams& p, hipStream_t s) {
-  const DfPlan pl = df_plan(p);
+  const DfPlan pl = df_plan(nominal_launch(p));   // (the unit shape decides which rows share an accumulator's K order: from the plan batch where one is set)
   if (pl.mt == 8) {
     if (pl.ntw == 5) launch_df_l<8, 5, FL>(p, s);
     else if (pl.ntw == 4) launch_df_l<8, 4, FL>(p, s);

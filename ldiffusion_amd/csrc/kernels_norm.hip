@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void gn_small_kernel(SrcView s1, SrcView s2, i
 }
 
 void launch_gn_stats(SrcView x1, SrcView x2, int B, int HW, int groups, float eps, const float* gamma,
-                     const float* beta, float* partial, size_t partial_bytes, float* scale, float* shift, hipStream_t s, int* nonfinite) {
+                     const float* beta, float* partial, size_t partial_bytes, float* scale, float* shift, hipStream_t s, int* nonfinite, int plan_B) {
   x1 = norm_view(x1); x2 = norm_view(x2);
   if (!x2.p) x2.C = 0;
   const int C1 = x1.C, C2 = x2.C, C = C1 + C2;
@@ -240,12 +240,14 @@ void launch_gn_stats(SrcView x1, SrcView x2, int B, int HW, int groups, float ep
   LDIFF_CHECK(x1.ld % 8 == 0 && x1.lo % 8 == 0 && (!x2.p || (x2.ld % 8 == 0 && x2.lo % 8 == 0)), LDIFF_ERR_INVALID, "gn_stats: pitches must be multiples of 8");
   LDIFF_CHECK(C % groups == 0, LDIFF_ERR_INVALID, "gn_stats: C=%d not divisible by groups=%d", C, groups);
   LDIFF_CHECK(gn_partial_bytes(B, HW, C) <= partial_bytes, LDIFF_ERR_INVALID, "gn_stats: workspace too small");
+  LDIFF_CHECK(plan_B == 0 || plan_B >= B, LDIFF_ERR_INVALID, "gn_stats: batch %d under a plan batch of %d", B, plan_B);
+  const int Bn = plan_B > 0 ? plan_B : B;   // the batch the form is chosen for (the two forms sum in different orders)
   // small map with enough (image, group) workgroups, or a batch so small that either form is a latency chain (B = 1, the reference's own batch:
   // the two-launch form costs 22 us per tensor there, 43 tensors per UNet pass -- profiles/r05_unet_launches_b1.txt): one launch.
   // LDIFF_GN_SMALL_BATCH=0 restores the two-launch form for small batches (A/B).
   // Profiler names: gn_stats<1> = the one-launch form, gn_stats<2> = partial + finalize (the tests pin each case to its form by them).
   static const bool small_batch = [] { const char* e = getenv("LDIFF_GN_SMALL_BATCH"); return !e || atoi(e) != 0; }();
-  if ((HW <= 1024 && B * groups >= 64) || (small_batch && B * groups < 256 && HW <= 4096)) {
+  if ((HW <= 1024 && Bn * groups >= 64) || (small_batch && Bn * groups < 256 && HW <= 4096)) {
     ProfScope prof("gn_stats<1>", 3.0 * B * HW * (double)C, 2.0 * B * HW * ((double)C1 * (x1.lo ? 2 : 1) + (double)C2 * (x2.lo ? 2 : 1)), s);
     hipLaunchKernelGGL(gn_small_kernel, dim3(groups, B), dim3(256), 0, s, x1, x2, HW, groups, eps, gamma, beta, scale, shift, nonfinite);
     HIP_CHECK(hipGetLastError());

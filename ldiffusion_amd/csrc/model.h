@@ -176,6 +176,9 @@ struct ConvOpts {
   // launch whose output joins the shifted stream from a normalised / true-scale input; bias_shift = k: the bias times 2^-k, for a launch whose input IS
   // the shifted stream (its sum is shifted already)
   int out_shift = 0, bias_shift = 0;
+  // under a plan batch (Exec::plan_batch): the rows of this launch ARE the batch (a [1, 1, rows, C] tensor: the time-embedding MLP has one row per image),
+  // and plan_rows is their number at the plan batch.  0: an image-shaped tensor, whose nominal launch has plan_batch images of Hout x Wout rows
+  int plan_rows = 0;
 };
 
 class Exec {
@@ -190,6 +193,8 @@ class Exec {
   int* nonfinite = nullptr;           // -> the owning handle's sticky non-finite flag (host-mapped; set by the GroupNorm finalize kernels, NonFiniteFlag below)
   const char* trace_tag = nullptr;    // LDIFF_TRACE_ABSMAX=1: name of the graph whose stages trace() reports (diagnostic, synchronises)
   int range_shift = 0;                // k: this graph's stream is stored times 2^-k (the VAE decoder's Exec only: ldiff_vae_set_range_shift; trace() reports true magnitudes)
+  int plan_batch = 0;                 // n > 0: every launch of this graph is planned as if the batch were n (ldiff_*_set_plan_batch, ConvParams::plan_B); 0: from its own batch
+  void check_plan_batch(const char* who, int B) const;   // refuses B > plan_batch > 0
   void trace(const char* stage, const Act& a);   // max |value| of a stage's output to stderr when LDIFF_TRACE_ABSMAX is set; otherwise nothing
   ~Exec();
   void ensure_gn_partial(size_t bytes);
@@ -293,6 +298,8 @@ struct ldiff_unet {
   std::vector<TransformerW*> all_tf;
   NonFiniteFlag nf;
   int ctx_B = 0, ctx_L = 0, ctx_gen = 0;
+  int ctx_plan = 0;            // the plan batch the cross-attention K / V were projected under (set_context): a forward under another one is refused
+  void set_plan_batch(int n) { ex.plan_batch = n; }   // (captured graphs: the plan batch is part of the replay key)
   f16* ctx_buf = nullptr; size_t ctx_cap = 0;     // all kv_ctx live in one allocation
   void build();
   void set_context(const float* ctx, int Bc, int L, hipStream_t s);
@@ -372,6 +379,7 @@ struct ldiff_vae {
   // use eps * 4^-k (DESIGN.md section 3 "Range").  No captured graph holds decoder launches, so nothing is invalidated; the pre-scaled biases are
   // rebuilt on their next use (Exec::derived_bias_shift)
   void set_range_shift(int k) { ex_dec.range_shift = k; }
+  void set_plan_batch(int n) { ex_dec.plan_batch = ex_enc.plan_batch = n; }   // (no captured graph holds VAE launches)
   float dec_eps() const { return ldexpf(1e-6f, -2 * ex_dec.range_shift); }
 };
 
@@ -396,6 +404,7 @@ struct ldiff_controlnet {
   void build();
   void set_cond(const float* cond, int B, int H, int W, hipStream_t s);
   void ensure_scaled(float scale, hipStream_t s);
+  void set_plan_batch(int n);   // trunk and embedding; a change drops the kept embedding (set_cond again) and whatever graph holds this network's launches
   // the trunk's pass: fills trunk.pass (skips, cur = the mid block's output); the tensors stay valid until the trunk's next pass
   void run_trunk(const float* x, int B, int h, int w, float t, const float* t_dev, hipStream_t s);
   void forward(const float* x, int B, int h, int w, float t, float scale, float* const* down_out, int n_down, float* mid_out, hipStream_t s);

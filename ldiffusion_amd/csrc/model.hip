@@ -146,6 +146,9 @@ Act Exec::new_act(int B, int H, int W, int C, bool split, bool lo8) {
   a.p = (f16*)arena.alloc(a.bytes());
   return a;
 }
+void Exec::check_plan_batch(const char* who, int B) const {
+  LDIFF_CHECK(plan_batch == 0 || B <= plan_batch, LDIFF_ERR_INVALID, "%s: batch %d exceeds the plan batch %d (set_plan_batch: the largest batch the handle takes; 0 = off)", who, B, plan_batch);
+}
 void Exec::release(Act& a) {
   if (a.borrowed) { a.p = nullptr; a.st = nullptr; return; }
   if (a.p) arena.free(a.p);
@@ -166,7 +169,7 @@ GNss Exec::gn(const Act& x, const Act* x2, const NormW& w, int groups, float eps
   }
   LDIFF_CHECK(gn_partial_bytes(x.B, x.H * x.W, C) <= gn_partial_cap, LDIFF_ERR_RUNTIME, "group norm workspace too small");
   launch_gn_stats(x.view(), x2 ? x2->view() : SrcView{nullptr, 0, 0, 0}, x.B, x.H * x.W, groups, eps, w.g, w.b, gn_partial, gn_partial_cap, g.scale,
-                  g.shift, s, nonfinite);
+                  g.shift, s, nonfinite, plan_batch);
   return g;
 }
 void Exec::release(GNss& g) {
@@ -222,6 +225,7 @@ bool Exec::lo8_conv_ok(const MatW& w, const Act& x, bool res, bool split_out) co
   p.x = x.p; p.C1 = x.C + x.C / 2; p.lo8_slab0 = x.C / 64; p.lo8_sb = 127 - LO8_SHIFT; p.lo8_sa = &one;
   p.B = x.B; p.Hin = p.Hout = x.H; p.Win = p.Wout = x.W; p.ks = 3; p.stride = 1; p.pad_t = p.pad_l = 1;
   p.w = w.w; p.N = roundup(w.N, 4); p.n_real = w.N; p.Nrows = w.Nrows; p.K = 9 * p.C1; p.M = x.B * x.H * x.W;
+  if (plan_batch > 0) { p.plan_B = plan_batch; p.plan_M = plan_batch * x.H * x.W; }
   if (p.N != w.N || p.N % 8 != 0) return false;
   p.y = x.p; p.ldy = 2 * p.N; p.y_lo = p.N;   // (placeholders: only null / non-null and the layout matter)
   if (res) { p.res = x.p; p.ld_res = 2 * p.N; p.res_lo = p.N; }
@@ -268,6 +272,10 @@ Act Exec::conv(const MatW& w, const Act& x, const Act* x2, const ConvOpts& o) {
   if (o.gn) { p.gn_scale = o.gn->scale; p.gn_shift = o.gn->shift; p.silu_in = o.silu; p.lrelu_in = o.lrelu; }
   p.temb = o.temb; p.ld_temb = o.ld_temb;
   p.M = x.B * p.Hout * p.Wout;
+  if (plan_batch > 0) {   // the nominal launch (ConvParams::plan_B): plan_batch images, or -- rows that are the batch itself -- ConvOpts::plan_rows rows
+    p.plan_B = o.plan_rows ? x.B : plan_batch;
+    p.plan_M = o.plan_rows ? o.plan_rows : plan_batch * p.Hout * p.Wout;
+  }
   if (o.res) {
     LDIFF_CHECK(o.res->rows() == p.M && o.res->C >= p.N, LDIFF_ERR_INVALID, "conv: residual shape mismatch");
     p.res = o.res->p; p.ld_res = o.res->ld(); p.res_lo = o.res->lo();
@@ -288,7 +296,7 @@ Act Exec::conv(const MatW& w, const Act& x, const Act* x2, const ConvOpts& o) {
   if (o.silu_out) {
     LDIFF_CHECK(C > 0 && !o.split_out && !o.res && !o.want_stats, LDIFF_ERR_INVALID, "conv: a SiLU behind the sum needs a plain fp16 output without residual or statistics");
     p.silu_out = 1;
-    if (!cond_conv_selected(p)) { p.silu_out = 0; silu_after = true; }
+    if (!cond_conv_selected(nominal_launch(p))) { p.silu_out = 0; silu_after = true; }
   }
   if (o.sc_done) *o.sc_done = false;
   if (o.sc_x && o.sc_w && o.sc_done && !o.split_in && !o.res && !o.sc_x->split && o.sc_w->ks == 1 && o.sc_w->Nrows == w.Nrows && o.sc_w->K == o.sc_x->C) {
@@ -299,7 +307,7 @@ Act Exec::conv(const MatW& w, const Act& x, const Act* x2, const ConvOpts& o) {
   ask.fold_gn = !o.want_stats && !o.split_in;
   if (o.splitk_per_image && x.B > 1) {   // the split count of the same launch at B = 1: the sums of an image do not depend on the batch it travels in
     ConvParams one = p;
-    one.B = 1; one.M = p.Hout * p.Wout;
+    one.B = 1; one.M = p.Hout * p.Wout; one.plan_B = one.plan_M = 0;
     plan_conv(one, ask);
     ask.splitk = one.splitk > 1 ? one.splitk : 1;
   }
@@ -377,7 +385,8 @@ Act Exec::ln_linear(const MatW& w, const Act& x, const NormW& ln, bool geglu, in
   if (w.ks == 1 && w.K == x.C && w.Nrows >= N && lngemm_eligible(x.C, N, x.ld(), x.lo(), ldy, fused_geglu) && ldy == Cout && (!geglu || fused_geglu)) {
     Act y = new_act(x.B, x.H, x.W, Cout);
     const bool sc = qcols > 0 && qcols % 64 == 0 && !fused_geglu;
-    launch_lngemm(x.p, x.ld(), x.lo(), (int)x.rows(), x.C, ln.g, ln.b, 1e-5f, derived_tiled(w, N), N, w.b, fused_geglu, y.p, y.ld(), s, sc ? qcols : 0, qscale);
+    launch_lngemm(x.p, x.ld(), x.lo(), (int)x.rows(), x.C, ln.g, ln.b, 1e-5f, derived_tiled(w, N), N, w.b, fused_geglu, y.p, y.ld(), s, sc ? qcols : 0, qscale,
+                  plan_batch * x.H * x.W);
     if (scaled) *scaled = sc;
     return y;
   }
@@ -602,6 +611,7 @@ void ldiff_unet::build() {
 void ldiff_unet::set_context(const float* ctx, int Bc, int L, hipStream_t s) {
   LDIFF_CHECK(ctx && Bc >= 1 && L >= 1, LDIFF_ERR_INVALID, "set_context: need B_ctx >= 1 and L >= 1 (got %d, %d)", Bc, L);
   LDIFF_CHECK(ws.missing() == 0, LDIFF_ERR_STATE, "unet: %d weight tensors not loaded (first: %s)", ws.missing(), ws.missing_name(0));
+  ex.check_plan_batch("set_context", Bc);
   HIP_CHECK(hipSetDevice(device));
   const int D = cfg.cross_attention_dim, rows = Bc * L;
   size_t need = 0;
@@ -624,13 +634,14 @@ void ldiff_unet::set_context(const float* ctx, int Bc, int L, hipStream_t s) {
     p.w = t->kv2.w; p.N = 2 * t->C; p.Nrows = t->kv2.Nrows; p.K = D;
     p.y = t->kv_ctx; p.ldy = 2 * t->C; p.M = rows;
     p.df_force = -1;   // (no fragment-packed copy of these weights for the dataflow GEMM)
+    if (ex.plan_batch > 0) { p.plan_B = 1; p.plan_M = ex.plan_batch * L; }   // planned at n prompts' rows, whether the context came as one prompt or one per image
     ConvAsk ask;
     ask.splitk = 1;
     launch_igemm(p, plan_conv(p, ask), s);
     off += (size_t)rows * 2 * t->C;
   }
   ex.release(c16);
-  ctx_B = Bc; ctx_L = L;
+  ctx_B = Bc; ctx_L = L; ctx_plan = ex.plan_batch;
   ++ctx_gen;   // the K/V buffer may have moved: a captured forward graph holds its old address
 }
 
@@ -667,6 +678,7 @@ Act ldiff_unet::transformer(const TransformerW& t, const Act& x) {
   ap.o = a1.p; ap.ldo = C; ap.B = x.B; ap.heads = heads; ap.Lq = L; ap.Lk = L; ap.d = d;
   ap.q_bstride = (long long)L * 3 * C; ap.kv_bstride = (long long)L * 3 * C; ap.o_bstride = (long long)L * C;
   ap.scale = att_scale;
+  ap.plan_B = ex.plan_batch;
   ap.prescaled = pre ? 1 : 0;
   launch_attention(ap, ex.s);
   ap.prescaled = 0;
@@ -719,7 +731,7 @@ void ldiff_unet::forward(const float* x, int B, int h, int w, float tval, float*
   auto key = [&] {
     return GraphCache::Key{B, h, w, precision, (long long)ctx_B * 65536 + ctx_L, ws.generation, ctx_gen, (long long)ex.arena.capacity(),
                            (long long)reinterpret_cast<uintptr_t>(cn), cn ? cn->state_gen : 0, cn ? (long long)cn->trunk.ex.arena.capacity() : 0,
-                           cn ? ((long long)cn->trunk.ws.generation << 24) + cn->trunk.ctx_gen * 4 + cn->trunk.precision : 0, cn_epoch};
+                           cn ? ((long long)cn->trunk.ws.generation << 24) + cn->trunk.ctx_gen * 4 + cn->trunk.precision : 0, cn_epoch, ex.plan_batch};
   };
   const long long captures = gc.captures;
   gc.run(s, key, {{&st_in, n_in}, {&st_out, n_out}, {&st_t, sizeof(float)}},
@@ -741,6 +753,8 @@ void ldiff_unet::begin_pass(int B, int h, int w, hipStream_t s) {
   LDIFF_CHECK(ws.missing() == 0, LDIFF_ERR_STATE, "unet: %d weight tensors not loaded (first: %s)", ws.missing(), ws.missing_name(0));
   LDIFF_CHECK(ctx_L > 0, LDIFF_ERR_STATE, "unet: set_context has not been called");
   LDIFF_CHECK(ctx_B == 1 || ctx_B == B, LDIFF_ERR_INVALID, "unet: context batch %d does not match sample batch %d", ctx_B, B);
+  ex.check_plan_batch(encoder_only ? "controlnet_forward" : "unet_forward", B);
+  LDIFF_CHECK(ctx_plan == ex.plan_batch, LDIFF_ERR_STATE, "unet: the context's K / V were projected under plan batch %d, the handle is now at %d: call set_context again", ctx_plan, ex.plan_batch);
   HIP_CHECK(hipSetDevice(device));
   ex.s = s;
   ex.arena.reset();
@@ -775,15 +789,16 @@ void ldiff_unet::run_down(const float* x, float tval, const float* t_dev, const 
   Act e16 = ex.new_act(1, 1, B, C0);
   launch_timestep_embed(tval, t_dev, e16.p, B, C0, cfg.flip_sin_to_cos, cfg.freq_shift, s);
   float* l1 = ex.tmp<float>((size_t)B * td);
-  { ConvOpts o; o.out_f32 = l1; o.ldy_f32 = td; ex.conv(t_lin1, e16, nullptr, o); }
+  const int prow = ex.plan_batch;   // one row per image: planned at the plan batch's rows
+  { ConvOpts o; o.out_f32 = l1; o.ldy_f32 = td; o.plan_rows = prow; ex.conv(t_lin1, e16, nullptr, o); }
   Act l1h = ex.new_act(1, 1, B, td);
   launch_silu_f32_to_f16(l1, l1h.p, (long long)B * td, s);
   float* l2 = ex.tmp<float>((size_t)B * td);
-  { ConvOpts o; o.out_f32 = l2; o.ldy_f32 = td; ex.conv(t_lin2, l1h, nullptr, o); }
+  { ConvOpts o; o.out_f32 = l2; o.ldy_f32 = td; o.plan_rows = prow; ex.conv(t_lin2, l1h, nullptr, o); }
   Act l2h = ex.new_act(1, 1, B, td);
   launch_silu_f32_to_f16(l2, l2h.p, (long long)B * td, s);
   float* temb_all = ex.tmp<float>((size_t)B * temb_total);
-  { ConvOpts o; o.out_f32 = temb_all; o.ldy_f32 = temb_total; ex.conv(temb_proj_all, l2h, nullptr, o); }
+  { ConvOpts o; o.out_f32 = temb_all; o.ldy_f32 = temb_total; o.plan_rows = prow; ex.conv(temb_proj_all, l2h, nullptr, o); }
   ex.release(e16); ex.arena.free(l1); ex.release(l1h); ex.arena.free(l2); ex.release(l2h);
   pass.temb_all = temb_all;
 
@@ -826,6 +841,8 @@ void ldiff_unet::forward_impl(const float* x, int B, int h, int w, float tval, c
   LDIFF_CHECK(x && out && B >= 1 && h >= 1 && w >= 1, LDIFF_ERR_INVALID, "unet_forward: bad arguments (B=%d h=%d w=%d)", B, h, w);
   LDIFF_CHECK(!encoder_only, LDIFF_ERR_STATE, "unet_forward: this handle is a ControlNet's trunk");
   const int nb = cfg.n_blocks;
+  LDIFF_CHECK(!cn || cn->trunk.ex.plan_batch == ex.plan_batch, LDIFF_ERR_INVALID, "unet_forward: the attached ControlNet's plan batch is %d, the UNet's %d (set_plan_batch on both)",
+              cn ? cn->trunk.ex.plan_batch : 0, ex.plan_batch);
   begin_pass(B, h, w, s);
   if (cn) cn->ensure_scaled(cn_scale, s);
   if (cn) cn->run_trunk(x, B, h, w, tval, t_dev, s);   // the attached ControlNet's blocks first, on the same stream: its skips and mid output wait in ITS workspace
@@ -959,6 +976,7 @@ void ldiff_controlnet::set_cond(const float* cond, int B, int H, int W, hipStrea
   for (size_t i = 0; i + 1 < emb_ch.size(); ++i) down *= 2;
   LDIFF_CHECK(H % down == 0 && W % down == 0, LDIFF_ERR_INVALID, "controlnet_set_cond: conditioning image %dx%d must be divisible by %d", H, W, down);
   LDIFF_CHECK(trunk.ws.missing() == 0, LDIFF_ERR_STATE, "controlnet: %d weight tensors not loaded (first: %s)", trunk.ws.missing(), trunk.ws.missing_name(0));
+  ex_emb.check_plan_batch("controlnet_set_cond", B);
   HIP_CHECK(hipSetDevice(trunk.device));
   const int C0 = trunk.cfg.block_out_channels[0], h = H / down, w = W / down;
   const size_t need = (size_t)B * h * w * C0 * sizeof(f16);
@@ -993,6 +1011,13 @@ void ldiff_controlnet::set_cond(const float* cond, int B, int H, int W, hipStrea
   HIP_CHECK(hipMemcpyAsync(emb, x.p, need, hipMemcpyDeviceToDevice, s));
   ex.release(x);
   emb_B = B; emb_h = h; emb_w = w;
+}
+
+void ldiff_controlnet::set_plan_batch(int n) {
+  if (n == trunk.ex.plan_batch) return;
+  trunk.ex.plan_batch = ex_emb.plan_batch = n;
+  emb_B = emb_h = emb_w = 0;   // the kept embedding was computed under the old plans
+  ++state_gen;
 }
 
 void ldiff_controlnet::ensure_scaled(float scale, hipStream_t s) {
@@ -1146,6 +1171,7 @@ Act ldiff_vae::mid_attention(const VaeAttnW& a, const Act& x) {
   ap.o = o.p; ap.ldo = C; ap.B = x.B; ap.heads = 1; ap.Lq = L; ap.Lk = L; ap.d = C;
   ap.q_bstride = (long long)L * 3 * C; ap.kv_bstride = ap.q_bstride; ap.o_bstride = (long long)L * C;
   ap.scale = 1.0f / sqrtf((float)C);
+  ap.plan_B = ex().plan_batch;
   launch_attention(ap, ex().s);
   ex().release(qkv);
   ConvOpts oo;
@@ -1160,6 +1186,7 @@ void ldiff_vae::encode(const float* x, int B, int H, int W, float* moments, hipS
   LDIFF_CHECK(x && moments && B >= 1, LDIFF_ERR_INVALID, "vae_encode: bad arguments");
   LDIFF_CHECK(H >= f && W >= f && H % f == 0 && W % f == 0, LDIFF_ERR_INVALID, "vae_encode: image size %dx%d must be a positive multiple of %d", H, W, f);
   LDIFF_CHECK(ws.missing() == 0, LDIFF_ERR_STATE, "vae: %d weight tensors not loaded (first: %s)", ws.missing(), ws.missing_name(0));
+  ex_enc.check_plan_batch("vae_encode", B);
   HIP_CHECK(hipSetDevice(device));
   struct UseEnc { ldiff_vae* v; UseEnc(ldiff_vae* v_) : v(v_) { v->cur = &v->ex_enc; } ~UseEnc() { v->cur = &v->ex_dec; } } use_enc(this);
   const int pr = prec_enc;
@@ -1227,6 +1254,7 @@ void ldiff_vae::decode(const float* z, int B, int h, int w, float z_scale, float
   LDIFF_CHECK(z && B >= 1 && h >= 1 && w >= 1, LDIFF_ERR_INVALID, "vae_decode: bad arguments");
   LDIFF_CHECK(ws.missing() == 0, LDIFF_ERR_STATE, "vae: %d weight tensors not loaded (first: %s)", ws.missing(), ws.missing_name(0));
   LDIFF_CHECK(!luma || (slot >= 0 && slot < n_slots), LDIFF_ERR_INVALID, "vae_decode: luma slot %d out of range [0,%d)", slot, n_slots);
+  ex_dec.check_plan_batch("vae_decode", B);
   HIP_CHECK(hipSetDevice(device));
   const int pr = prec_dec;
   const bool st = pr >= PREC_STREAM, full = pr >= PREC_FULL;

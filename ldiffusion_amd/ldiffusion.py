@@ -15,7 +15,7 @@ from .segmentor import Segmentor
 
 
 class LDiffusionModel:
-    def __init__(self, diffusion_path, level, local_rank=-1):
+    def __init__(self, diffusion_path, level, local_rank=-1, plan_batch=None):
         rank, world, env_local = world_info()                     # ldiffusion.py:34-35,42
         self.world_size, self.rank = world, rank
         self.is_distributed = world > 1
@@ -27,6 +27,7 @@ class LDiffusionModel:
         self.diffusion_path = diffusion_path
         self.level = level
         self.linear_layer = None
+        self.plan_batch = plan_batch   # batch-invariant mode of the pipelines load_model returns (None: the default, plans from each launch's own batch)
 
     def _is_main_process(self):
         return self.rank == 0
@@ -35,6 +36,8 @@ class LDiffusionModel:
         """ldiffusion.py:66-70 -> (pipeline, vae)"""
         from .pipeline import StableDiffusionImg2ImgPipeline
         pipeline = StableDiffusionImg2ImgPipeline.from_pretrained(model_path, torch_dtype=torch.float32, device=self.device)
+        if self.plan_batch is not None:
+            pipeline.set_plan_batch(self.plan_batch)
         return pipeline, pipeline.vae
 
     def _reduce_mean(self, value):

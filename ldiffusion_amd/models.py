@@ -146,12 +146,22 @@ class UNet2DConditionModel(_GraphHandle):
         _lib.check(self._lib.ldiff_unet_create(C.byref(self._h), C.byref(c), self.device.index or 0))
         self._host_sd = None
         self._ctx_key = None
+        self.plan_batch = 0
         self.load_state_dict(state_dict)
 
     def set_precision(self, mode: int):
         """Storage policy of the graph (include/ldiff.h ldiff_unet_set_precision): 0 all-fp16, 1 split residual stream (default),
         2 every contraction operand split."""
         _lib.check(self._lib.ldiff_unet_set_precision(self._h, int(mode)))
+        return self
+
+    def set_plan_batch(self, n: int):
+        """Batch-invariant mode (include/ldiff.h ldiff_unet_set_plan_batch): with n >= 1 every launch is planned as if the batch were n, so an image gets
+        bit-identical outputs in any batch B <= n (B > n raises ValueError); 0 (default) plans every launch from its own batch.  An attached ControlNet
+        needs the same n.  Kept in `plan_batch`; returns self."""
+        _lib.check(self._lib.ldiff_unet_set_plan_batch(self._h, int(n)))
+        self.plan_batch = int(n)
+        self._ctx_key = None   # the context's K / V are planned too: projected again by the next call
         return self
 
     @property
@@ -302,11 +312,20 @@ class ControlNetModel(_Handle):
         self._host_sd = None
         self._ctx_key = None
         self._cond_key = None
+        self.plan_batch = 0
         self.load_state_dict(state_dict)
 
     def set_precision(self, mode: int):
         _lib.check(self._lib.ldiff_controlnet_set_precision(self._h, int(mode)))
         self._cond_key = None   # (the embedding's first layer follows the storage policy)
+        return self
+
+    def set_plan_batch(self, n: int):
+        """As UNet2DConditionModel.set_plan_batch (include/ldiff.h ldiff_controlnet_set_plan_batch): trunk, zero convs and conditioning embedding."""
+        _lib.check(self._lib.ldiff_controlnet_set_plan_batch(self._h, int(n)))
+        self.plan_batch = int(n)
+        self._ctx_key = None    # both are planned too: computed again by the next call
+        self._cond_key = None
         return self
 
     def _param_shapes(self):
@@ -438,6 +457,7 @@ class AutoencoderKL(_Handle):
         _lib.check(self._lib.ldiff_vae_create(C.byref(self._h), C.byref(c), self.device.index or 0))
         self.load_state_dict(state_dict)
         self.range_shift = 0
+        self.plan_batch = 0
         if range_shift:
             self.set_range_shift(range_shift)
 
@@ -472,6 +492,13 @@ class AutoencoderKL(_Handle):
         activations pass fp16's +-65504.  0 <= k <= 16 (else ValueError); the encoder is unaffected.  Kept in `range_shift`; returns self."""
         _lib.check(self._lib.ldiff_vae_set_range_shift(self._h, int(k)))
         self.range_shift = int(k)
+        return self
+
+    def set_plan_batch(self, n: int):
+        """Batch-invariant mode of the encoder and the decoder (include/ldiff.h ldiff_vae_set_plan_batch): with n >= 1 an image's moments, sample and
+        uint8 image are bit-identical in any batch B <= n (B > n raises ValueError); 0 (default) = off.  Kept in `plan_batch`; returns self."""
+        _lib.check(self._lib.ldiff_vae_set_plan_batch(self._h, int(n)))
+        self.plan_batch = int(n)
         return self
 
     def fit_range_shift(self, z, z_scale=None, step: int = 2, k_max: int = 16):

@@ -29,6 +29,15 @@ def shard_range(total: int, rank: int, world: int) -> Tuple[int, int]:
     return lo, lo + base + (1 if rank < rem else 0)
 
 
+def plan_batch(total: int, world: int, batch: int) -> int:
+    """The largest batch any rank submits when `total` patches are sharded by `shard_range` over `world` ranks and every rank cuts its shard into
+    batches of `batch` (the last one short): what every rank passes to `set_plan_batch` so that a patch's mask does not depend on the rank count or on
+    its place in the patch list.  Rank 0 owns the largest shard, so this is min(batch, ceil(total / world))."""
+    if world < 1 or total < 0 or batch < 1:
+        raise ValueError(f"bad plan_batch request total={total} world={world} batch={batch}")
+    return min(batch, -(-total // world))
+
+
 def gather_masks(local: torch.Tensor, total: int, group=None) -> torch.Tensor:
     """All-gather per-rank blocks [n_r, ...] (any dtype, e.g. uint8 masks [n_r, H, W] or features [n_r, N, H, W]) into
     the full [total, ...] tensor on every rank, in patch order.  Even shards use one all_gather_into_tensor; ragged

@@ -60,6 +60,16 @@ class StableDiffusionImg2ImgPipeline:
     def to(self, *a, **k):
         return self
 
+    def set_plan_batch(self, n: int):
+        """Batch-invariant mode of the whole pipeline (DESIGN.md "Batch invariance"): the UNet, the VAE and an attached ControlNet plan every launch as
+        if the batch were n, so a patch gets bit-identical latents, features, rgb and masks in any batch B <= n -- alone, in a short last batch, or on
+        another rank's shard.  n = `parallel.plan_batch(total, world, batch)` on every rank; 0 = off (default)."""
+        self.unet.set_plan_batch(n)
+        self.vae.set_plan_batch(n)
+        if getattr(self.unet, "_controlnet", None) is not None:
+            self.unet._controlnet.set_plan_batch(n)
+        return self
+
     def decode_latents(self, latents):
         """(1/scaling_factor * z) -> vae.decode -> (x/2+0.5).clamp(0,1) -> NHWC float32 numpy on the host."""
         _, image, _ = self.vae._decode(latents, 1.0 / self.vae.config.scaling_factor, want_image=True)

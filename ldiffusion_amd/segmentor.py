@@ -114,12 +114,15 @@ class Segmentor:
         from .utils import micro_dice
         return micro_dice(predicted_labels, true_labels, num_classes)
 
-    def load_ldiffusion(self, ldiffusion_weight, diffusion_path, text_encoder="transformers"):
-        """text_encoder="hip": the prompt's CLIP pass and projection run on the library (`StableDiffusionImg2ImgPipeline.from_pretrained`)."""
+    def load_ldiffusion(self, ldiffusion_weight, diffusion_path, text_encoder="transformers", plan_batch=None):
+        """text_encoder="hip": the prompt's CLIP pass and projection run on the library (`StableDiffusionImg2ImgPipeline.from_pretrained`).
+        plan_batch=n: batch-invariant mode of the UNet and the VAE (`StableDiffusionImg2ImgPipeline.set_plan_batch`; None leaves the default)."""
         pipeline = StableDiffusionImg2ImgPipeline.from_pretrained(diffusion_path, torch_dtype=torch.float32, device=self.device, text_encoder=text_encoder)
         unet = UNet2DConditionModel.from_pretrained(ldiffusion_weight, device=self.device).eval()
         vae = pipeline.vae
         pipeline.unet = unet
+        if plan_batch is not None:
+            pipeline.set_plan_batch(plan_batch)
         if pipeline.text_encoder is not None:
             self._ensure_ldiffusion_proj(pipeline, unet, ldiffusion_weight=ldiffusion_weight)
         return pipeline, unet, vae
