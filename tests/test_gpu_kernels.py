@@ -1757,7 +1757,6 @@ def test_ln_linear_fused(lib, M, N, split, geglu):
         torch.cuda.synchronize()
         if bias is None:
             pr = a16 @ r16(w).t()
-            want = pr[:, :N // 2] * F.gelu(pr[:, N // 2:]) if False else None
             if geglu:
                 p0 = a16 @ r16(w[torch.argsort(_geglu_perm(N // 2))]).t()
                 want = p0[:, :N // 2] * F.gelu(p0[:, N // 2:])
