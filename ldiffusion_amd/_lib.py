@@ -52,6 +52,21 @@ class SegMetricsOut(C.Structure):
                 ("iou_mean", C.c_double), ("pa", C.c_double * 32), ("pa_mean", C.c_double), ("fw_iou", C.c_float), ("fw_iou_fg", C.c_float)]
 
 
+class SegCase(C.Structure):     # ldiff_seg_case
+    _fields_ = [("coef_off", C.c_int64), ("raw_off", C.c_int64), ("label_off", C.c_int64), ("H", C.c_int32), ("W", C.c_int32), ("stride", C.c_int32),
+                ("label_stride", C.c_int32)]
+
+
+class SegSample(C.Structure):   # ldiff_seg_sample
+    _fields_ = [("m", C.c_float * 6), ("case_index", C.c_int32), ("copy", C.c_int32), ("noise_sigma", C.c_float), ("reserved", C.c_uint32),
+                ("philox_offset", C.c_uint64)]
+
+
+class SegChan(C.Structure):     # ldiff_seg_chan
+    _fields_ = [("blur_sigma", C.c_float), ("brightness", C.c_float), ("contrast", C.c_float), ("lowres_zoom", C.c_float), ("gamma_inverted", C.c_float),
+                ("gamma", C.c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/ldiff.h declares
 P, I, F, I64, U64 = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_uint64
 SIGNATURES = {
@@ -185,6 +200,9 @@ SIGNATURES = {
     "ldiff_op_dice_ce_ws_bytes": (I64, [I, I64, I]),
     "ldiff_op_dice_ce": (I, [P, I, I, P, I, I, I64, I, F, F, F, P, P, P, I64, P]),
     "ldiff_op_sgd_nesterov_multi": (I, [P, P, P, I64, F, F, F, I, P, P, P]),
+    "ldiff_op_seg_sample": (I, [P, I64, P, I, P, I, I, I, I, I, P, P, P]),
+    "ldiff_op_seg_intensity_ws_bytes": (I64, [I, I, I, I]),
+    "ldiff_op_seg_intensity": (I, [P, P, P, I, I, I, I, P, U64, P, I64, P]),
     "ldiff_stream_create_cu_share": (I, [I, I, P]),
     "ldiff_stream_destroy": (I, [P]),
     "ldiff_vae_set_side_cu_share": (I, [P, I, I]),

@@ -1090,6 +1090,23 @@ int ldiff_op_sgd_nesterov_multi(const void* tensors, const void* grads, const vo
                             (const float*)inv_scale, (const float*)clip_coef, (hipStream_t)stream);
   API_END
 }
+// ---- training data of the tissue head (kernels_segaug.hip) ----
+int ldiff_op_seg_sample(const void* arena, int64_t arena_bytes, const ldiff_seg_case* cases, int n_cases, const ldiff_seg_sample* samples, int B, int Cc, int h,
+                        int w, int n_scales, void* data, void* target, void* stream) {
+  API_BEGIN
+  launch_seg_sample(arena, arena_bytes, cases, n_cases, samples, B, Cc, h, w, n_scales, (float*)data, (uint8_t*)target, (hipStream_t)stream);
+  API_END
+}
+int64_t ldiff_op_seg_intensity_ws_bytes(int B, int Cc, int h, int w) {
+  if (B < 1 || Cc < 1 || h < 1 || w < 1) return 0;
+  return seg_intensity_ws_bytes(B, Cc, h, w);
+}
+int ldiff_op_seg_intensity(void* data, const ldiff_seg_sample* samples, const ldiff_seg_chan* chans, int B, int Cc, int h, int w, const void* normal_or_null,
+                           uint64_t seed, void* ws, int64_t ws_bytes, void* stream) {
+  API_BEGIN
+  launch_seg_intensity((float*)data, samples, chans, B, Cc, h, w, (const float*)normal_or_null, seed, ws, ws_bytes, (hipStream_t)stream);
+  API_END
+}
 int ldiff_op_geglu(const void* x, void* y, int64_t M, int C4, void* stream) {
   API_BEGIN
   LDIFF_CHECK(x && y, LDIFF_ERR_INVALID, "op_geglu: null argument");

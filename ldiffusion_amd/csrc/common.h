@@ -341,6 +341,28 @@ struct SgdTensor { float* p; float* buf; long long n; };
 void launch_sgd_nesterov_multi(const SgdTensor* tensors, const float* const* grads, const AdamChunk* chunks, long long nchunks, float lr, float momentum, float wd,
                                int first, const float* inv_scale, const float* clip_coef, hipStream_t s);
 
+// training data of the tissue head (kernels_segaug.hip): patch sampling with deep-supervision targets, and the intensity chain, per batch
+void launch_seg_sample(const void* arena, long long arena_bytes, const ldiff_seg_case* cases, int n_cases, const ldiff_seg_sample* samples, int B, int C, int h, int w, int n_scales,
+                       float* data, uint8_t* target, hipStream_t s);
+long long seg_intensity_ws_bytes(int B, int C, int h, int w);
+void launch_seg_intensity(float* data, const ldiff_seg_sample* samples, const ldiff_seg_chan* chans, int B, int C, int h, int w, const float* normal,
+                          unsigned long long seed, void* ws, long long ws_bytes, hipStream_t s);
+
+// Counter-based Philox4x32-10: four 32-bit words per (counter, key).  Used by the Laplace forward noise (kernels_elem.hip) and the augmentation noise
+// (kernels_segaug.hip).
+__device__ __forceinline__ void philox4x32_10(unsigned long long ctr, unsigned long long key, unsigned out[4]) {
+  unsigned c0 = (unsigned)ctr, c1 = (unsigned)(ctr >> 32), c2 = 0, c3 = 0;
+  unsigned k0 = (unsigned)key, k1 = (unsigned)(key >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
+    unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
 // ---- device arena: bump/free-list allocator over one hipMalloc'd slab ------------------------
 // No hipMalloc/hipFree in a forward pass (graph-capturable, no implicit syncs).  Stream-ordered reuse:
 // all kernels of one handle run on one stream, so a block may be reused as soon as it is released on the host.

@@ -231,19 +231,8 @@ void launch_lincomb(const float* coef, const void* const* ops, int nops, float* 
 
 // ---- Laplace forward noise (ldiffusion.py:234-237; torch.distributions.Laplace.rsample) ----
 // x = z0 - scale * sign(u) * log1p(-|u|),  u ~ U(eps_f32 - 1, 1).  `u` may be supplied (parity is defined
-// given u) or drawn from a counter-based Philox4x32-10 stream keyed by (seed, offset + element index / 4).
-__device__ __forceinline__ void philox4x32_10(unsigned long long ctr, unsigned long long key, unsigned out[4]) {
-  unsigned c0 = (unsigned)ctr, c1 = (unsigned)(ctr >> 32), c2 = 0, c3 = 0;
-  unsigned k0 = (unsigned)key, k1 = (unsigned)(key >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-    unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
+// given u) or drawn from a counter-based Philox4x32-10 stream keyed by (seed, offset + element index / 4)
+// (philox4x32_10: common.h).
 __global__ void laplace_add_kernel(const float* __restrict__ z0, float scale, const float* __restrict__ u, unsigned long long seed,
                                    unsigned long long offset, float* __restrict__ out, long long n) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -1,0 +1,421 @@
+"""Training batches for the nnU-Net tissue head, made on the device: what `nnUNetDataLoader2D` and the transforms of
+`nnUNetTrainer.get_training_transforms` (nnUNetTrainer.py:674-765) do on a pool of CPU workers, for cases that stay in device memory.
+
+    CaseStore      preprocessed cases in ONE device arena: normalised image, its cubic B-spline coefficients, labels, foreground locations
+    draw_batch     every random decision of a batch, on the host, as two parameter tables (numpy structured arrays = the C structs of include/ldiff.h)
+    PatchLoader    iterator of {"data": [B, C, h, w] float32, "target": [n_scales x [B, 1, h_k, w_k] uint8]} -- what nnunet_train.Trainer takes.
+                   Per batch: one pinned upload of the tables and two launches (ldiff_op_seg_sample, ldiff_op_seg_intensity); nothing synchronises.
+
+The chain is nnU-Net's minus SimulateLowResolutionTransform; `lowres_zoom` is its reserved table slot.  The bodies of the
+transforms live in `batchgenerators`, restated here from the public package; each rule sits in one function whose docstring names the class it mirrors.
+
+One deliberate difference: nnU-Net crops `initial_patch_size` on the CPU, pads it and transforms that crop; here the kernel samples the case itself, so it
+sees the case's pixels where nnU-Net sees the intermediate crop's pad, and the spline coefficients are those of the whole case.  The crop centre, the
+admissible crop positions and "outside the case is 0 / background" are nnU-Net's.
+
+Order of draws (ours; `numpy.random`'s legacy stream is not reproduced).  Per sample (`draw_sample`), from the caller's Generator, with or without
+`train`:
+    1. integers: the case index
+    2. integers: the class among those present, then the voxel among its recorded locations (a forced sample of a case with foreground), or the crop's
+       first row, then its first column (every other sample)
+    3. random(8): rotation gate, angle; scale gate, coin, scale below 1, scale above 1; mirror of axis 0, of axis 1
+    4. random(2): noise gate, noise sigma;  integers: the Philox offset
+    5. random(5): the per-sample gates of blur, brightness, contrast, gamma on -x, gamma
+    6. random((C, 12)): per channel  blur coin, blur sigma | brightness | contrast coin, below 1, above 1 | gamma on -x coin, below 1, above 1 |
+       gamma coin, below 1, above 1
+A value behind a closed gate, or the unused side of a coin, is drawn and dropped, so a sample always consumes the same count after step 2.
+"""
+from __future__ import annotations
+
+import math
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib, nnunet
+
+# the C structs of include/ldiff.h (ldiff_seg_case / ldiff_seg_sample / ldiff_seg_chan), field for field
+CASE_DTYPE = np.dtype([("coef_off", "<i8"), ("raw_off", "<i8"), ("label_off", "<i8"), ("H", "<i4"), ("W", "<i4"), ("stride", "<i4"), ("label_stride", "<i4")])
+SAMPLE_DTYPE = np.dtype([("m", "<f4", (6,)), ("case_index", "<i4"), ("copy", "<i4"), ("noise_sigma", "<f4"), ("reserved", "<u4"), ("philox_offset", "<u8")])
+CHAN_DTYPE = np.dtype([("blur_sigma", "<f4"), ("brightness", "<f4"), ("contrast", "<f4"), ("lowres_zoom", "<f4"), ("gamma_inverted", "<f4"), ("gamma", "<f4")])
+MAX_SCALES = 8
+
+# nnUNetTrainer.get_training_transforms (:698-727)
+P_ROTATION, P_SCALE, SCALE_RANGE = 0.2, 0.2, (0.7, 1.4)
+P_NOISE, NOISE_SIGMA = 0.1, (0.0, 0.1)
+P_BLUR, P_BLUR_PER_CHANNEL, BLUR_SIGMA = 0.2, 0.5, (0.5, 1.0)
+P_BRIGHTNESS, BRIGHTNESS = 0.15, (0.75, 1.25)
+P_CONTRAST, CONTRAST = 0.15, (0.75, 1.25)
+P_GAMMA_INVERTED, P_GAMMA, GAMMA = 0.1, 0.3, (0.7, 1.5)
+P_MIRROR = 0.5
+OVERSAMPLE_FOREGROUND = 0.33   # nnUNetTrainer.oversample_foreground_percent
+
+
+def rotate_coords_2d(coords: np.ndarray, angle: float) -> np.ndarray:
+    """batchgenerators.augmentations.utils.rotate_coords_2d: coords [2, ...] times the plain rotation [[cos, -sin], [sin, cos]] from the right,
+    (r, c) -> (r cos + c sin, -r sin + c cos)."""
+    coords = np.asarray(coords, dtype=np.float64)
+    rot = np.array([[math.cos(angle), -math.sin(angle)], [math.sin(angle), math.cos(angle)]])
+    return np.dot(coords.reshape(2, -1).transpose(), rot).transpose().reshape(coords.shape)
+
+
+def rotation_range(patch_size: Sequence[int]) -> float:
+    """nnUNetTrainer.configure_rotation_dummyDA_mirroring_and_inital_patch_size (:382-397), 2-D: the half-width r of U(-r, r), pi or 15 degrees."""
+    if len(patch_size) != 2:
+        raise ValueError(f"rotation_range: 2-D patches only, got {tuple(patch_size)}")
+    return 15.0 / 360 * 2.0 * np.pi if max(patch_size) / min(patch_size) > 1.5 else 180.0 / 360 * 2.0 * np.pi
+
+
+def initial_patch_size(patch_size: Sequence[int]) -> Tuple[int, int]:
+    """compute_initial_patch_size.get_patch_size(patch, rot, 0, 0, (0.85, 1.25)) for two dimensions: the extent the patch reaches when turned by
+    min(r, 90 degrees), over 0.85, truncated."""
+    rot = min(90 / 360 * 2.0 * np.pi, abs(rotation_range(patch_size)))
+    coords = np.array(patch_size, dtype=np.float64)
+    shape = np.max(np.vstack((np.abs(rotate_coords_2d(coords, rot)), coords)), 0)
+    shape /= 0.85
+    return tuple(int(v) for v in shape.astype(int))
+
+
+def spline_coefficients(img: np.ndarray) -> np.ndarray:
+    """scipy.ndimage.spline_filter(img, order=3, mode='mirror') over the last two axes, in float64: per axis the recursive filter with pole sqrt(3) - 2 and
+    gain 6, the causal pass started from the whole-sample-mirrored sum, the anti-causal pass from its closed form; vectorised over the other axes."""
+    out = np.array(img, dtype=np.float64)
+    pole = math.sqrt(3.0) - 2.0
+    for axis in (-2, -1):
+        c = np.moveaxis(out, axis, 0)   # a view: the passes below write through it
+        n = c.shape[0]
+        if n == 1:
+            continue
+        c *= (1.0 - pole) * (1.0 - 1.0 / pole)
+        horizon = n if n < 64 else 64   # |pole|^64 = 2e-37
+        if horizon < n:
+            acc = sum((pole ** k) * c[k] for k in range(horizon))
+        else:   # the exact sum over one period 2 n - 2 of the mirrored signal
+            acc = c[0] + (pole ** (n - 1)) * c[n - 1]
+            for k in range(1, n - 1):
+                acc = acc + (pole ** k + pole ** (2 * n - 2 - k)) * c[k]
+            acc = acc / (1.0 - pole ** (2 * n - 2))
+        c[0] = acc
+        for k in range(1, n):
+            c[k] += pole * c[k - 1]
+        c[n - 1] = (pole / (pole * pole - 1.0)) * (c[n - 1] + pole * c[n - 2])
+        for k in range(n - 2, -1, -1):
+            c[k] = pole * (c[k + 1] - c[k])
+    return out
+
+
+def _target_num_samples(count: int) -> int:
+    """default_preprocessor.py:171-172: at most 10,000 locations, at least 1 % of the class."""
+    return max(min(10000, count), int(np.ceil(count * 0.01)))
+
+
+def sample_foreground_locations(seg: np.ndarray, classes: Sequence[int], seed: int = 1234) -> dict:
+    """DefaultPreprocessor._sample_foreground_locations (default_preprocessor.py:152-178) for plain labels of one [H, W] map: per class a subset of
+    np.argwhere(seg == c) chosen without replacement by ONE RandomState(seed) walked through the classes in order; an absent class gets []."""
+    rndst = np.random.RandomState(seed)
+    out = {}
+    for c in classes:
+        locs = np.argwhere(seg == c)
+        if len(locs) == 0:
+            out[int(c)] = []
+            continue
+        out[int(c)] = locs[rndst.choice(len(locs), _target_num_samples(len(locs)), replace=False)]
+    return out
+
+
+class CaseStore:
+    """Preprocessed training cases resident on the device.  `cases`: pairs (image [C, H, W] uint8 or float32, label map [H, W] of integers); sizes may
+    differ.  Each image is normalised by `nnunet.normalize(schemes)`; the arena holds, per case and 16-byte aligned, the cubic B-spline coefficients
+    (float32 [C, H, W]), the normalised image itself (float32 [C, H, W], what an unmodified sample copies) and the labels (uint8 [H, W]); `table` is the
+    per-case ldiff_seg_case row (offsets, H, W, row strides).  `class_locations[i]`: {class: [n, 2] (row, column)} for the foreground classes
+    1 .. n_heads - 1.  `labels`: a dataset.json `labels` mapping, only looked at to refuse what the tissue head does not cover.
+    `device="cpu"` keeps the arena on the host: enough for `draw_batch`, not for a PatchLoader."""
+
+    def __init__(self, cases, schemes: Sequence[str], n_heads: int, device="cuda:0", labels: Optional[dict] = None):
+        if labels is not None:
+            if any(isinstance(v, (list, tuple)) for v in labels.values()):
+                nnunet._refuse("labels", "defines regions")
+            if "ignore" in labels:
+                nnunet._refuse("labels", "defines an ignore label")
+        if not 2 <= int(n_heads) <= 32:
+            raise ValueError(f"CaseStore: n_heads {n_heads} out of range [2, 32]")
+        cases = list(cases)
+        if not cases:
+            raise ValueError("CaseStore: no cases")
+        self.n_heads, self.schemes = int(n_heads), list(schemes)
+        self.device = torch.device(device)
+        self.table = np.zeros(len(cases), CASE_DTYPE)
+        self.class_locations: List[dict] = []
+        parts, size = [], 0
+        self.channels = None
+        for i, (img, seg) in enumerate(cases):
+            img, seg = torch.as_tensor(img), np.asarray(torch.as_tensor(seg).cpu())
+            if img.dim() != 3 or img.dtype not in (torch.uint8, torch.float32):
+                raise ValueError(f"CaseStore: case {i}: the image must be [C, H, W] uint8 or float32, got {tuple(img.shape)} of {img.dtype}")
+            Cc, H, W = (int(v) for v in img.shape)
+            if self.channels is None:
+                self.channels = Cc
+            if Cc != self.channels or Cc != len(self.schemes):
+                raise ValueError(f"CaseStore: case {i} has {Cc} channels; the store has {self.channels} and {len(self.schemes)} normalisation schemes")
+            if seg.shape != (H, W) or seg.dtype.kind not in "iu":
+                raise ValueError(f"CaseStore: case {i}: the label map must be [{H}, {W}] of integers, got {seg.shape} of {seg.dtype}")
+            if seg.min() < 0 or seg.max() >= self.n_heads:
+                bad = sorted(int(v) for v in np.unique(seg) if v < 0 or v >= self.n_heads)
+                raise ValueError(f"CaseStore: case {i}: labels {bad[:5]} outside [0, {self.n_heads})")
+            raw = nnunet.normalize(img.cpu().to(torch.float32), self.schemes).numpy()
+            coef = spline_coefficients(raw).astype(np.float32)
+            row = self.table[i]
+            row["H"], row["W"], row["stride"], row["label_stride"] = H, W, W, W
+            for key, arr in (("coef_off", coef), ("raw_off", raw), ("label_off", seg.astype(np.uint8))):
+                size = (size + 15) // 16 * 16
+                row[key] = size
+                parts.append((size, np.ascontiguousarray(arr).view(np.uint8).reshape(-1)))
+                size += parts[-1][1].size
+            self.class_locations.append(sample_foreground_locations(seg, range(1, self.n_heads)))
+        host = np.zeros((size + 15) // 16 * 16, np.uint8)
+        for off, arr in parts:
+            host[off:off + arr.size] = arr
+        self.arena = torch.from_numpy(host).to(self.device)
+        self.cases_dev = torch.from_numpy(self.table.view(np.uint8).reshape(-1).copy()).to(self.device)
+
+    def __len__(self):
+        return len(self.table)
+
+    def shape(self, i: int) -> Tuple[int, int]:
+        return int(self.table[i]["H"]), int(self.table[i]["W"])
+
+    def _plane(self, key: str, i: int) -> torch.Tensor:
+        H, W = self.shape(i)
+        off = int(self.table[i][key])
+        return self.arena[off:off + self.channels * H * W * 4].view(torch.float32).view(self.channels, H, W)
+
+    def raw(self, i: int) -> torch.Tensor:
+        """The normalised image of case i, float32 [C, H, W] (a view of the arena)."""
+        return self._plane("raw_off", i)
+
+    def coefficients(self, i: int) -> torch.Tensor:
+        return self._plane("coef_off", i)
+
+    def labels(self, i: int) -> torch.Tensor:
+        H, W = self.shape(i)
+        off = int(self.table[i]["label_off"])
+        return self.arena[off:off + H * W].view(H, W)
+
+
+def crop_bounds(shape: Sequence[int], loader_patch: Sequence[int], final_patch: Sequence[int]) -> Tuple[List[int], List[int]]:
+    """nnUNetDataLoaderBase.get_bbox (base_data_loader.py:68-80): the lowest and highest admissible first index of the loader's crop per axis;
+    need_to_pad = loader patch - final patch, widened where the case is smaller than the loader's patch."""
+    lbs, ubs = [], []
+    for d in range(2):
+        pad = int(loader_patch[d]) - int(final_patch[d])
+        if pad + shape[d] < loader_patch[d]:
+            pad = loader_patch[d] - shape[d]
+        lbs.append(-pad // 2)
+        ubs.append(shape[d] + pad // 2 + pad % 2 - loader_patch[d])
+    return lbs, ubs
+
+
+def do_oversample(sample_idx: int, batch_size: int, oversample: float) -> bool:
+    """nnUNetDataLoaderBase._oversample_last_XX_percent (base_data_loader.py:45-49)."""
+    return not sample_idx < round(batch_size * (1 - oversample))
+
+
+def _two_sided(coin: float, low: float, high: float, lo: float, mid: float, hi: float) -> float:
+    """batchgenerators' `if random() < 0.5: U(lo, mid) else: U(mid, hi)` with the two uniforms already drawn in [0, 1)."""
+    return lo + low * (mid - lo) if coin < 0.5 else mid + high * (hi - mid)
+
+
+def draw_crop(rng: np.random.Generator, store: CaseStore, sample_idx: int, batch_size: int, patch_size: Sequence[int], loader_patch: Sequence[int],
+              oversample: float = OVERSAMPLE_FOREGROUND) -> dict:
+    """The case and the loader's crop of one sample (nnUNetDataLoader2D.generate_train_batch + get_bbox): the case index, whether the sample is forced
+    onto foreground, the bounds, the chosen voxel (None for a free crop) and the crop's first index `bbox_lbs`.
+    Draws: case index; then class and voxel (forced, and the case has foreground) or row and column of the crop."""
+    ci = int(rng.integers(len(store)))
+    lbs, ubs = crop_bounds(store.shape(ci), loader_patch, patch_size)
+    forced = do_oversample(sample_idx, batch_size, oversample)
+    eligible = [c for c, locs in store.class_locations[ci].items() if len(locs) > 0]
+    voxel = None
+    if forced and eligible:   # get_bbox (:95-132): a class among those present, one of its recorded voxels as the centre
+        locs = store.class_locations[ci][eligible[int(rng.integers(len(eligible)))]]
+        voxel = [int(v) for v in locs[int(rng.integers(len(locs)))]]
+        bbox = [max(lbs[d], voxel[d] - loader_patch[d] // 2) for d in range(2)]
+    else:                     # :85 / :135: anywhere between the bounds (a forced sample of a case without foreground falls back to this)
+        bbox = [int(rng.integers(lbs[d], ubs[d] + 1)) for d in range(2)]
+    return dict(case=ci, forced=forced, voxel=voxel, lbs=lbs, ubs=ubs, bbox_lbs=bbox, loader_patch=tuple(int(v) for v in loader_patch))
+
+
+def draw_sample(rng: np.random.Generator, store: CaseStore, sample_idx: int, batch_size: int, patch_size: Sequence[int], train: bool = True,
+                oversample: float = OVERSAMPLE_FOREGROUND):
+    """Every random decision of one sample, in the module docstring's order: (a SAMPLE_DTYPE record, [C] CHAN_DTYPE records, `draw_crop`'s dict).
+    The same numbers are drawn with `train=False`; they are then not used."""
+    h, w = int(patch_size[0]), int(patch_size[1])
+    Cc = store.channels
+    loader_patch = initial_patch_size((h, w)) if train else (h, w)
+    s = np.zeros((), SAMPLE_DTYPE)
+    chans = np.zeros(Cc, CHAN_DTYPE)
+    chans["brightness"] = 1.0
+    crop = draw_crop(rng, store, sample_idx, batch_size, (h, w), loader_patch, oversample)
+
+    u = rng.random(8)   # rotation gate, angle; scale gate, coin, scale below 1, scale above 1; mirror axis 0, axis 1
+    rotate, scale = train and u[0] < P_ROTATION, train and u[2] < P_SCALE
+    angle = (2.0 * u[1] - 1.0) * rotation_range((h, w)) if rotate else 0.0
+    zoom = _two_sided(u[3], u[4], u[5], SCALE_RANGE[0], 1.0, SCALE_RANGE[1]) if scale else 1.0
+    flip = [train and u[6] < P_MIRROR, train and u[7] < P_MIRROR]
+    s["case_index"] = crop["case"]
+    s["m"], s["copy"] = spatial_matrix((h, w), loader_patch, crop["bbox_lbs"], angle, zoom, flip, modified=bool(rotate or scale))
+    noise_gate, noise_u = rng.random(2)
+    s["philox_offset"] = int(rng.integers(0, 1 << 62))
+    gates = rng.random(5)                # blur, brightness, contrast, inverted gamma, gamma: one gate per sample
+    per_channel = rng.random((Cc, 12))   # per channel: blur (coin, sigma), brightness, contrast (coin, low, high), gamma on -x (3), gamma (3)
+    if not train:
+        return s, chans, crop
+    s["noise_sigma"] = NOISE_SIGMA[0] + noise_u * (NOISE_SIGMA[1] - NOISE_SIGMA[0]) if noise_gate < P_NOISE else 0.0
+    for c in range(Cc):
+        v, ch = per_channel[c], chans[c]
+        if gates[0] < P_BLUR and v[0] < P_BLUR_PER_CHANNEL:
+            ch["blur_sigma"] = BLUR_SIGMA[0] + v[1] * (BLUR_SIGMA[1] - BLUR_SIGMA[0])
+        if gates[1] < P_BRIGHTNESS:
+            ch["brightness"] = BRIGHTNESS[0] + v[2] * (BRIGHTNESS[1] - BRIGHTNESS[0])
+        if gates[2] < P_CONTRAST:
+            ch["contrast"] = _two_sided(v[3], v[4], v[5], CONTRAST[0], 1.0, CONTRAST[1])
+        if gates[3] < P_GAMMA_INVERTED:
+            ch["gamma_inverted"] = _two_sided(v[6], v[7], v[8], GAMMA[0], 1.0, GAMMA[1])
+        if gates[4] < P_GAMMA:
+            ch["gamma"] = _two_sided(v[9], v[10], v[11], GAMMA[0], 1.0, GAMMA[1])
+    return s, chans, crop
+
+
+def draw_batch(rng: np.random.Generator, store: CaseStore, batch_size: int, patch_size: Sequence[int], train: bool = True,
+               oversample: float = OVERSAMPLE_FOREGROUND):
+    """The random decisions of one batch, sample after sample (`draw_sample`): (samples [B] of SAMPLE_DTYPE, channels [B, C] of CHAN_DTYPE).
+    `train=False`: no augmentation, the loader's patch is the final patch (need_to_pad = 0), every sample an exact crop."""
+    samples = np.zeros(batch_size, SAMPLE_DTYPE)
+    chans = np.zeros((batch_size, store.channels), CHAN_DTYPE)
+    for b in range(batch_size):
+        samples[b], chans[b], _ = draw_sample(rng, store, b, batch_size, patch_size, train, oversample)
+    return samples, chans
+
+
+def spatial_matrix(patch, loader_patch, bbox_lbs, angle: float, zoom: float, flip, modified: bool):
+    """SpatialTransform(random_crop=False, no elastic deformation) + MirrorTransform as one map from the patch index to the case coordinate, float32
+    [m00 m01 m02 m10 m11 m12], and the copy flag.  The centred grid g = (i - (h-1)/2, j - (w-1)/2) is rotated (`rotate_coords_2d`) and scaled, and the
+    centre of the loader's crop, bbox_lbs + (loader_patch - 1) / 2, is added.  Without rotation and scale batchgenerators takes the integer centre crop
+    of the loader's crop instead: translation bbox_lbs + (loader_patch - patch) // 2, flagged as a copy.  A mirrored axis walks its grid backwards
+    (every step between the two transforms is pointwise or symmetric, so the flip commutes with them)."""
+    h, w = patch
+    f = [-1.0 if flip[0] else 1.0, -1.0 if flip[1] else 1.0]
+    if not modified:
+        ty, tx = (int(bbox_lbs[d]) + (int(loader_patch[d]) - int(patch[d])) // 2 for d in range(2))
+        m = [f[0], 0.0, ty + (h - 1 if flip[0] else 0), 0.0, f[1], tx + (w - 1 if flip[1] else 0)]
+        return np.array(m, np.float32), 1
+    cos, sin = math.cos(angle), math.sin(angle)
+    a = np.array([[cos, sin], [-sin, cos]]) * zoom    # (r, c) -> (r cos + c sin, -r sin + c cos), scaled
+    a = a * np.array(f)[None, :]
+    centre = [bbox_lbs[d] + (loader_patch[d] - 1) / 2.0 for d in range(2)]
+    g0 = np.array([(h - 1) / 2.0, (w - 1) / 2.0])
+    t = np.array(centre) - a @ g0
+    return np.array([a[0, 0], a[0, 1], t[0], a[1, 0], a[1, 1], t[1]], np.float32), 0
+
+
+# ---- the two launches ------------------------------------------------------------------------------------------------------------------------
+def _table_bytes(arr: np.ndarray) -> np.ndarray:
+    return np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
+
+
+def upload_tables(samples: np.ndarray, chans: np.ndarray, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Both tables through ONE pinned staging buffer and one asynchronous copy; returns device views (samples, channels).  The staging buffer comes
+    from torch's pinned-memory cache, which hands it out again only after the copy has run."""
+    if samples.dtype != SAMPLE_DTYPE or chans.dtype != CHAN_DTYPE:
+        raise ValueError("upload_tables: tables must be of SAMPLE_DTYPE and CHAN_DTYPE")
+    sb, cb = _table_bytes(samples), _table_bytes(chans)
+    stage = torch.empty(sb.size + cb.size, dtype=torch.uint8, pin_memory=True)
+    view = stage.numpy()
+    view[:sb.size] = sb
+    view[sb.size:] = cb
+    dev = torch.empty(stage.numel(), dtype=torch.uint8, device=device)
+    dev.copy_(stage, non_blocking=True)
+    return dev[:sb.size], dev[sb.size:]
+
+
+def _scale_shapes(patch, n_scales):
+    h, w = int(patch[0]), int(patch[1])
+    if not 1 <= n_scales <= MAX_SCALES:
+        raise ValueError(f"n_scales {n_scales} out of range [1, {MAX_SCALES}]")
+    div = 2 ** (n_scales - 1)
+    if h % div or w % div:
+        raise ValueError(f"patch {h} x {w} is not divisible by 2^(n_scales - 1) = {div} ({n_scales} deep-supervision scales)")
+    return [(h >> k, w >> k) for k in range(n_scales)]
+
+
+def sample_patches(store: CaseStore, samples_dev: torch.Tensor, batch_size: int, patch_size: Sequence[int], n_scales: int):
+    """ldiff_op_seg_sample on the current stream: (data [B, C, h, w] float32, [n_scales label maps [B, 1, h_k, w_k] uint8])."""
+    _lib.require_gpu()
+    shapes = _scale_shapes(patch_size, n_scales)
+    h, w = shapes[0]
+    B = int(batch_size)
+    if samples_dev.numel() != B * SAMPLE_DTYPE.itemsize:
+        raise ValueError(f"sample_patches: the sample table holds {samples_dev.numel()} bytes, {B} samples need {B * SAMPLE_DTYPE.itemsize}")
+    dev = store.arena.device
+    data = torch.empty((B, store.channels, h, w), dtype=torch.float32, device=dev)
+    flat = torch.empty(B * sum(a * b for a, b in shapes), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().ldiff_op_seg_sample(_lib.ptr(store.arena), store.arena.numel(), _lib.ptr(store.cases_dev), len(store), _lib.ptr(samples_dev), B,
+                                                   store.channels, h, w, n_scales, _lib.ptr(data), _lib.ptr(flat), _lib.stream_ptr()))
+    targets, off = [], 0
+    for hk, wk in shapes:
+        targets.append(flat[off:off + B * hk * wk].view(B, 1, hk, wk))
+        off += B * hk * wk
+    return data, targets
+
+
+def augment_intensity_(data: torch.Tensor, samples_dev: torch.Tensor, chans_dev: torch.Tensor, seed: int = 0, normal: Optional[torch.Tensor] = None,
+                       workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ldiff_op_seg_intensity in place on `data` [B, C, h, w] float32 (contiguous), on the current stream.  `normal`: the N(0, 1) draws to use, same shape,
+    instead of the Philox stream keyed by (seed, each sample's offset)."""
+    _lib.require_gpu()
+    if data.dim() != 4 or data.dtype != torch.float32 or not data.is_contiguous() or not data.is_cuda:
+        raise ValueError("augment_intensity_: data must be a contiguous float32 [B, C, h, w] device tensor")
+    B, Cc, h, w = (int(v) for v in data.shape)
+    if samples_dev.numel() != B * SAMPLE_DTYPE.itemsize or chans_dev.numel() != B * Cc * CHAN_DTYPE.itemsize:
+        raise ValueError("augment_intensity_: table sizes do not match the batch")
+    if normal is not None and (normal.shape != data.shape or normal.dtype != torch.float32 or not normal.is_contiguous() or normal.device != data.device):
+        raise ValueError("augment_intensity_: normal must match data")
+    lib = _lib.load()
+    need = int(lib.ldiff_op_seg_intensity_ws_bytes(B, Cc, h, w))
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=data.device)
+    with torch.cuda.device(data.device):
+        _lib.check(lib.ldiff_op_seg_intensity(_lib.ptr(data), _lib.ptr(samples_dev), _lib.ptr(chans_dev), B, Cc, h, w, _lib.ptr(normal), int(seed) & (2 ** 64 - 1),
+                                              _lib.ptr(workspace), workspace.numel() * workspace.element_size(), _lib.stream_ptr()))
+    return data
+
+
+class PatchLoader:
+    """nnUNetDataLoader2D + the training transforms as an endless iterator of batches on the store's device:
+    {"data": [B, C, h, w] float32, "target": [n_scales tensors [B, 1, h >> k, w >> k] uint8]}, highest resolution first -- what
+    `Trainer.train_step`, `validation_step` and `run_training` take.  `train=False` is the validation loader: exact crops, no augmentation.
+    The same seed yields the same batches."""
+
+    def __init__(self, store: CaseStore, patch_size: Sequence[int], batch_size: int, n_scales: int, seed: int, train: bool = True,
+                 oversample: float = OVERSAMPLE_FOREGROUND):
+        if store.arena.device.type != "cuda":
+            raise ValueError("PatchLoader: the store must live on a GPU")
+        self.shapes = _scale_shapes(patch_size, n_scales)
+        self.store, self.patch_size, self.batch_size, self.n_scales = store, (int(patch_size[0]), int(patch_size[1])), int(batch_size), int(n_scales)
+        self.train, self.oversample, self.seed = bool(train), float(oversample), int(seed)
+        self.rng = np.random.default_rng(self.seed)
+        need = int(_lib.load().ldiff_op_seg_intensity_ws_bytes(self.batch_size, store.channels, *self.patch_size))
+        self._ws = torch.empty(max(need, 16), dtype=torch.uint8, device=store.arena.device) if self.train else None
+
+    def __iter__(self):
+        return self
+
+    def __next__(self) -> dict:
+        samples, chans = draw_batch(self.rng, self.store, self.batch_size, self.patch_size, self.train, self.oversample)
+        with torch.cuda.device(self.store.arena.device):
+            s_dev, c_dev = upload_tables(samples, chans, self.store.arena.device)
+            data, targets = sample_patches(self.store, s_dev, self.batch_size, self.patch_size, self.n_scales)
+            if self.train:
+                augment_intensity_(data, s_dev, c_dev, self.seed, workspace=self._ws)
+        return {"data": data, "target": targets}

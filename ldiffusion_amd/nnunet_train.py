@@ -9,8 +9,8 @@ Per step (nnUNetTrainer.train_step, nnUNetTrainer.py:883-913):
 Every contraction, normalisation, activation, loss term and parameter update runs in libldiff_hip.so; torch provides the tape, the channel concat, the
 depth-to-space permute behind the transposed conv's GEMM and the global gradient norm.
 
-Not here: nnU-Net's planner, preprocessing and augmentation (the trainer takes batches: `data` [B, C, H, W] float32 and `target`, the
-list the nnU-Net loader supplies, one label map per deep-supervision scale, highest resolution first), DDP, a captured-graph step, ResidualEncoderUNet,
+The trainer takes batches: `data` [B, C, H, W] float32 and `target`, the list the nnU-Net loader supplies, one label map per deep-supervision scale, highest
+resolution first; `nnunet_data.PatchLoader` makes them on the device.  Not here: nnU-Net's planner and dataset creation, DDP, a captured-graph step, ResidualEncoderUNet,
 region labels and an ignore label.
 """
 from __future__ import annotations
