@@ -14,14 +14,10 @@
 //     traffic), double-buffered one tap ahead.
 // LDS rows are 128 B; 16-byte chunk c of row r lives at position c ^ ((r>>1)&7) (conflict-free ds_read_b128 for
 // the 16x16x32 operand fetch).  The DMA writes LDS linearly, so the swizzle is applied on the weight SOURCE address.
-#include "common.h"
+#include "epilogue.h"
+#include "lds_prims.h"
 
 namespace {
-
-__device__ __forceinline__ int swz8(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
-
-typedef __attribute__((address_space(1))) const void gptr_t;
-typedef __attribute__((address_space(3))) void lptr_t;
 
 // LR (with GN): the prologue's activation is LeakyReLU(0.01) on the sources ConvParams::lrelu_in names (the nnU-Net head: InstanceNorm scale / shift; a slab of
 // 64 channels lies in ONE source, so the slope is uniform per slab: 0.01, or 1 for a source that passes through); the SiLU / plain forms do not see it
@@ -305,22 +301,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(const ConvParams p) {  
 //   * operand reads as inline asm with counted lgkmcnt waits (hipcc only ever emits lgkmcnt(0) there);
 //   * halo staging without exec masking (clamped source address, AND mask, dump slot for the lanes beyond the halo),
 //     GroupNorm+SiLU of chunk i spread over taps 1.., SiLU chosen by one uniform branch per chunk.
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<I + 1, N>(f); }
-}
-template <int OFF>
-__device__ __forceinline__ void lds_read128(f16x8& d, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory");
-}
-// s_waitcnt lgkmcnt(CNT); the fragments it covers are in/out operands so no MFMA consuming them can move above it
-template <int CNT>
-__device__ __forceinline__ void lds_wait(f16x8& a) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a) : "n"(CNT)); }
-template <int CNT>
-__device__ __forceinline__ void lds_wait(f16x8& a, f16x8& b, f16x8& c, f16x8& d, f16x8& e) {
-  asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e) : "n"(CNT));
-}
-
 // Column swizzle of the halo image: 16-byte chunk c of halo pixel (hy, hx) sits at position c ^ swzx(hx) of its 128-B row.
 // A 16x16x32 operand fetch reads 16 consecutive pixels of one halo row starting at column kx = 0, 1 or 2; its four
 // ds_read_b128 lane groups mix chunks c (8 lanes) and c^1 (8 lanes).  The table (one 3-bit entry per column PAIR, found by
@@ -814,21 +794,7 @@ __device__ __forceinline__ f32x4 splitk_row(const ConvParams& p, long long m, in
   for (int s = 0; s < SM; ++s) if (s < S) v += part[s];
   if (p.bias) { v[0] += tb.x; v[1] += tb.y; v[2] += tb.z; v[3] += tb.w; }
   if (p.temb) { v[0] += tt.x; v[1] += tt.y; v[2] += tt.z; v[3] += tt.w; }
-  v *= shift_scale(p.out_shift);   // range shift: after the partials are summed, before the (pre-shifted) residual
-  if (p.res) {
-    v += up4(rh);
-    if (p.res_lo) v += up4(rl);
-  }
-  return v;
-}
-// stores the row's four columns; returns what the consumer will read (the statistics are of THAT: hi + lo ~ v for a split tensor -- NaN where hi overflowed,
-// split_stat4 -- else the fp16 value)
-__device__ __forceinline__ f32x4 splitk_store(const ConvParams& p, long long m, int n, const f32x4& v) {
-  if (p.out_f32) { *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.y) + m * p.ldy + n) = v; return v; }
-  const f16x4 o = cvt4(v);
-  *reinterpret_cast<f16x4*>(reinterpret_cast<f16*>(p.y) + m * p.ldy + n) = o;
-  if (p.y_lo) { *reinterpret_cast<f16x4*>(reinterpret_cast<f16*>(p.y) + m * p.ldy + p.y_lo + n) = cvt4(v - up4(o)); return split_stat4(v); }
-  return up4(o);
+  return epi_value(p, v, shift_scale(p.out_shift), rh, rl);   // range shift: after the partials are summed, before the (pre-shifted) residual
 }
 template <int SM>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ConvParams p) {
@@ -837,7 +803,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ConvParams p) 
   if (i >= (long long)p.M * n4) return;
   const long long m = i / n4;
   const int n = (int)(i - m * n4) * 4;
-  splitk_store(p, m, n, splitk_row<SM>(p, m, n));
+  f32x4 unused;
+  epi_store8(p, m, n, splitk_row<SM>(p, m, n), false, unused);
 }
 // The same with the fused GroupNorm partial statistics of the output (common.h: stats[((b N + n) R + r) 2 + {0, 1}], r = (m % HW) / 32, R = HW / 32 --
 // the layout of the GEMM kernels' epilogues): a split-K launch's own epilogue never sees final values, so before round 6 every such tensor paid a
@@ -854,7 +821,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const ConvPara
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const long long m = m0 + rr + h * 16;
-      const f32x4 o = splitk_store(p, m, n, splitk_row<SM>(p, m, n));
+      const f32x4 v = splitk_row<SM>(p, m, n);
+      f32x4 o = v;   // what the consumer will read, which the statistics are of (epilogue.h)
+      epi_store8(p, m, n, v, true, o);
 #pragma unroll
       for (int r = 0; r < 4; ++r) { sm[r] += o[r]; sq[r] = __builtin_fmaf(o[r], o[r], sq[r]); }
     }

@@ -34,19 +34,12 @@
 //
 // Scope (conv3x3d_selected): one source, Cin % 64 == 0, N % 128 == 0, H, W % 16 == 0, GroupNorm + SiLU prologue, plain fp16 output and
 // residual (no split hi|lo tensors: the staged tile is fp16).  Everything else stays on the kernels of kernels_conv3x3.hip / kernels_conv3x3p.hip.
-#include "common.h"
+#include "lds_prims.h"
 #include <map>
 #include <mutex>
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lptr_t;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<I + 1, N>(f); }
-}
 template <int V> using ic_t = std::integral_constant<int, V>;
 
 constexpr int D_HWD = 18, D_HPX = 18 * 18, D_ROWB = D_HWD * 128;       // halo image of a 16x16 tile: 18 x 18 pixels of 128 B (64 channels)
@@ -70,10 +63,6 @@ enum { D_RES = 1, D_STATS = 2, D_SC = 4, D_UPS = 8 };   // D_UPS: nearest-2x ups
 __device__ __forceinline__ int d_swzx(int hx) { return (0xcb5888 >> (3 * (hx >> 1))) & 7; }   // column swizzle of the halo image (kernels_conv3x3.hip)
 
 // ---- LDS / memory primitives the compiler must not fence or wait for (counted by hand) ----
-template <int OFF>
-__device__ __forceinline__ void lds_read128(f16x8& d, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory");
-}
 template <int CNT>
 __device__ __forceinline__ void lds_wait4(f16x8& a, f16x8& b, f16x8& c, f16x8& d) {
   asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(CNT));

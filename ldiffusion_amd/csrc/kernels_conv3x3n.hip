@@ -9,12 +9,11 @@
 // loaded once per workgroup and stay in LDS: Cin/64 x 9 x 512 B = 9 KB at 128 channels.  No DMA, no per-tap barrier; the tap loop is LDS
 // reads + 4 MFMAs per wave.  What is left is a streaming kernel (one HBM pass over the input, GroupNorm+SiLU of the halo image on the way),
 // and a streaming kernel lives on occupancy: ONE halo buffer (23 KB + weights) and <= 168 VGPRs put three workgroups on a CU.
-#include "common.h"
+#include "lds_prims.h"
 #include <algorithm>
 
 namespace {
 
-__device__ __forceinline__ int swz8(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
 __device__ __forceinline__ float silu_f(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.4426950408889634f)); }
 
 // grid: workgroups that each walk tiles blockIdx.x, blockIdx.x + gridDim.x, ... (8 x 16 output pixels of one image; neighbours in the grid work

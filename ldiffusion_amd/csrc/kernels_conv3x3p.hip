@@ -40,29 +40,12 @@
 #include <map>
 #include <mutex>
 
-#include "common.h"
+#include "lds_prims.h"
 
 namespace {
 
-__device__ __forceinline__ int swz8(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
 __device__ __forceinline__ float silu_f(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.4426950408889634f)); }
-typedef __attribute__((address_space(3))) void lptr_t;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<I + 1, N>(f); }
-}
-template <int OFF>
-__device__ __forceinline__ void lds_read128(f16x8& d, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory");
-}
-template <int CNT>
-__device__ __forceinline__ void lds_wait(f16x8& a) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a) : "n"(CNT)); }
-template <int CNT>
-__device__ __forceinline__ void lds_wait(f16x8& a, f16x8& b, f16x8& c, f16x8& d, f16x8& e) {
-  asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e) : "n"(CNT));
-}
 // LDS accesses the compiler must not see as such: it orders every LDS access it knows of behind ALL pending vector-memory operations
 // when an LDS-DMA may be among them (s_waitcnt vmcnt(0)), which after the epilogue's stores means a full write round trip
 template <int OFF>

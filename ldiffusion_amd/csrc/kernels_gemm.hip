@@ -10,35 +10,9 @@
 // Tile BM x BN x 64, 256 threads (4 waves as 2x2), two LDS stages, one barrier per K-step.  LDS rows are 128 B with
 // 16-byte chunk c of row r at position c ^ ((r>>1)&7); the DMA writes LDS linearly, so the XOR is applied to the SOURCE
 // chunk each lane fetches.  Per-lane source offsets are fixed 32-bit values; per step only a uniform base moves.
-#include "common.h"
+#include "lds_prims.h"
 
 namespace {
-
-__device__ __forceinline__ int swz8(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
-typedef __attribute__((address_space(1))) const void gptr_t;
-typedef __attribute__((address_space(3))) void lptr_t;
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<I + 1, N>(f); }
-}
-// operand reads as inline asm + counted lgkmcnt waits (hipcc only emits lgkmcnt(0)); see kernels_conv3x3.hip
-template <int OFF>
-__device__ __forceinline__ void lds_read128(f16x8& d, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory");
-}
-template <int CNT>
-__device__ __forceinline__ void lds_wait(f16x8& a) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a) : "n"(CNT)); }
-template <int CNT>
-__device__ __forceinline__ void lds_wait(f16x8& a, f16x8& b, f16x8& c) { asm volatile("s_waitcnt lgkmcnt(%3)" : "+v"(a), "+v"(b), "+v"(c) : "n"(CNT)); }
-template <int CNT>
-__device__ __forceinline__ void lds_wait(f16x8& a, f16x8& b, f16x8& c, f16x8& d) {
-  asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(CNT));
-}
-template <int CNT>
-__device__ __forceinline__ void lds_wait(f16x8& a, f16x8& b, f16x8& c, f16x8& d, f16x8& e) {
-  asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e) : "n"(CNT));
-}
 
 // ConvParams::act_out behind the sum (the text encoder's FC1): 1 = quick_gelu v sigmoid(1.702 v), 2 = gelu (erf form, as the GEGLU epilogue computes it), in fp32
 // before the one rounding

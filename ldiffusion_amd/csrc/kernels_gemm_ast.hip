@@ -24,11 +24,9 @@
 // With one wave per SIMD nothing else covers a panel's epilogue, so the epilogue of panel c - 1 is cut into ten pieces that sit between the MFMA
 // groups of panel c (the matrix pipe runs while the VALU converts and the GEGLU erf evaluates); stores in full lines: the wave transposes its
 // 32 x 64 tile through a private LDS patch and writes 128 contiguous bytes per row.
-#include "common.h"
+#include "lds_prims.h"
 
 namespace {
-
-typedef __attribute__((address_space(3))) void lptr_t;
 
 template <int I, int N, class F>
 __device__ __forceinline__ void sfor(F&& f) {
@@ -36,10 +34,6 @@ __device__ __forceinline__ void sfor(F&& f) {
 }
 // LDS traffic as inline asm with counted waits: hipcc would put s_waitcnt vmcnt(0) in front of plain LDS reads while an LDS-DMA is in flight
 // (it cannot prove they do not alias the DMA's destination) and lgkmcnt(0) in front of every MFMA group.
-template <int OFF>
-__device__ __forceinline__ void lds_read128(f16x8& d, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory");
-}
 template <int OFF>
 __device__ __forceinline__ void lds_read128u(uint4& d, unsigned addr) {
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory");

@@ -25,19 +25,12 @@
 // Scope (gemm_df_selected): ks == 1, K % 64 == 0, one or two row-major sources (channel concat at a multiple of 64), fp16 output plain or split,
 // optional plain / split residual, optional GEGLU epilogue or fused GroupNorm partial statistics; no per-image weights, no split-K (those stay on
 // gemm_dma_kernel).
-#include "common.h"
+#include "lds_prims.h"
 #include <map>
 #include <mutex>
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lptr_t;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<I + 1, N>(f); }
-}
 template <int V> using ic_t = std::integral_constant<int, V>;
 
 // (tuning builds override these: scripts/gemm_df_stamps.py --def=...; measured in profiles/r05_gemm_df.md: three slots + three slice buffers and
@@ -65,12 +58,6 @@ static_assert(F_LDS <= 160 * 1024, "LDS budget of one workgroup per CU");
 constexpr unsigned F_OOR = 0x80000000u;                  // beyond num_records of every descriptor used here
 enum { FG_RES = 1, FG_RES_SPLIT = 2, FG_OUT_SPLIT = 4, FG_GEGLU = 8, FG_STATS = 16 };
 
-__device__ __forceinline__ int swz8(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
-
-template <int OFF>
-__device__ __forceinline__ void lds_read128(f16x8& d, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory");
-}
 template <int CNT>
 __device__ __forceinline__ void lds_wait2(f16x8& a, f16x8& b) { asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(CNT)); }
 // (every register exactly once: a register named twice is COPIED in front of the statement, i.e. read while its load is still in flight)

@@ -15,12 +15,11 @@
 // holding 4 consecutive output channels of one pixel -> 8-byte epilogue loads/stores.
 // LDS rows are 128 B; 16-byte chunks are XOR-swizzled with (row>>1)&7, which makes every ds_read_b128
 // lane group of the 16x16x32 operand fetch conflict-free (bank math in DESIGN.md).
-#include "common.h"
+#include "epilogue.h"
+#include "lds_prims.h"
 
 #define BK 64
 #define CPR (BK / 8)  // 16-byte chunks per tile row
-
-__device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
 
 // x * sigmoid(x) with the two hardware transcendentals only (v_exp_f32, v_rcp_f32: 1 ulp); __frcp_rn would expand to a
 // 11-instruction IEEE division per element
@@ -129,12 +128,12 @@ __device__ __forceinline__ void igemm_body(const ConvParams& p) {
       uint4 v = ra[i];
       if (LR) { if (gidx[i] >= 0) v = in_lrelu_apply8(v, p.gn_scale + gidx[i], p.gn_shift + gidx[i], gact[i] ? 0.01f : 1.0f); }
       else if (GN) { if (gidx[i] >= 0) v = gn_apply8(v, p.gn_scale + gidx[i], p.gn_shift + gidx[i], p.silu_in); }
-      sA[buf * BM * CPR + row * CPR + swz(row, kc)] = v;
+      sA[buf * BM * CPR + row * CPR + swz8(row, kc)] = v;
     }
 #pragma unroll
     for (int i = 0; i < B_IT; ++i) {
       int row = (tid >> 3) + i * 32;
-      sB[buf * BN * CPR + row * CPR + swz(row, kc)] = rw[i];
+      sB[buf * BN * CPR + row * CPR + swz8(row, kc)] = rw[i];
     }
   };
 
@@ -165,12 +164,12 @@ __device__ __forceinline__ void igemm_body(const ConvParams& p) {
 #pragma unroll
       for (int a = 0; a < NT; ++a) {
         int row = wave_n * (BN / 2) + a * 16 + l15;
-        wf[a] = __builtin_bit_cast(f16x8, cB[row * CPR + swz(row, kk * 4 + g)]);
+        wf[a] = __builtin_bit_cast(f16x8, cB[row * CPR + swz8(row, kk * 4 + g)]);
       }
 #pragma unroll
       for (int b = 0; b < MT; ++b) {
         int row = wave_m * (BM / 2) + b * 16 + l15;
-        xf[b] = __builtin_bit_cast(f16x8, cA[row * CPR + swz(row, kk * 4 + g)]);
+        xf[b] = __builtin_bit_cast(f16x8, cA[row * CPR + swz8(row, kk * 4 + g)]);
       }
 #pragma unroll
       for (int a = 0; a < NT; ++a)
@@ -182,93 +181,26 @@ __device__ __forceinline__ void igemm_body(const ConvParams& p) {
     __syncthreads();
   }
 
-  // ---- epilogue: lane holds y[m = col][n = 4g + r], r = 0..3 ----
+  // ---- epilogue (epilogue.h): lane holds y[m = col][n = 4g + r], r = 0..3 ----
   // Loads (bias, time embedding, residual) are issued back to back before any use: a load -> wait -> store chain per
   // 16x16 tile costs one memory round trip per tile.
   const int ncol = n0 + wave_n * (BN / 2) + g * 4;
-  if (S > 1) {
-#pragma unroll
-    for (int b = 0; b < MT; ++b) {
-      const int m = m0 + wave_m * (BM / 2) + b * 16 + l15;
-      if (m >= p.M) continue;
-#pragma unroll
-      for (int a = 0; a < NT; ++a) {
-        const int n = ncol + a * 16;
-        if (n < p.N) *reinterpret_cast<f32x4*>(p.splitk_ws + ((long long)ksplit * p.M + m) * p.N + n) = acc[a][b];
-      }
-    }
-    return;
-  }
+  auto row_of = [&](int mt) { const int m = m0 + wave_m * (BM / 2) + mt * 16 + l15; return m < p.M ? m : -1; };
+  if (S > 1) { epi_store_partial<MT, NT>(p, acc, row_of, ksplit, ncol); return; }
   const float osc = shift_scale(p.out_shift);   // ConvParams::out_shift
   f32x4 bb[NT];
-#pragma unroll
-  for (int a = 0; a < NT; ++a) {
-    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (p.bias && ncol + a * 16 < p.N) t = *reinterpret_cast<const float4*>(p.bias + ncol + a * 16);
-    bb[a] = (f32x4){t.x, t.y, t.z, t.w};
-  }
-  int mrow[MT];
-#pragma unroll
-  for (int b = 0; b < MT; ++b) {
-    const int m = m0 + wave_m * (BM / 2) + b * 16 + l15;
-    mrow[b] = m < p.M ? m : -1;
-  }
+  epi_load_cols<NT>(p.bias, ncol, p.N, bb);
   f16x4 rr[MT][NT], rl[MT][NT];
-  if (p.res) {
-#pragma unroll
-    for (int b = 0; b < MT; ++b)
-#pragma unroll
-      for (int a = 0; a < NT; ++a) {
-        rr[b][a] = (f16x4){(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f};
-        rl[b][a] = rr[b][a];
-        if (mrow[b] >= 0 && ncol + a * 16 < p.N) {
-          rr[b][a] = *reinterpret_cast<const f16x4*>(p.res + (long long)mrow[b] * p.ld_res + ncol + a * 16);
-          if (p.res_lo) rl[b][a] = *reinterpret_cast<const f16x4*>(p.res + (long long)mrow[b] * p.ld_res + p.res_lo + ncol + a * 16);
-        }
-      }
-  }
+  epi_load_residual<MT, NT>(p, row_of, ncol, rr, rl);
 #pragma unroll
   for (int b = 0; b < MT; ++b) {
-    if (mrow[b] < 0) continue;
-    const long long m = mrow[b];
-    f32x4 tt[NT];
-    if (p.temb) {
-      const int bi = mrow[b] / HWo;
-#pragma unroll
-      for (int a = 0; a < NT; ++a) {
-        float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (ncol + a * 16 < p.N) t = *reinterpret_cast<const float4*>(p.temb + (long long)bi * p.ld_temb + ncol + a * 16);
-        tt[a] = (f32x4){t.x, t.y, t.z, t.w};
-      }
-    }
-#pragma unroll
-    for (int a = 0; a < NT; ++a) {
-      const int n = ncol + a * 16;
-      if (n >= p.N) continue;
-      f32x4 v = acc[a][b] + bb[a];
-      if (p.temb) v += tt[a];
-      v *= osc;   // range shift before the (pre-shifted) residual
-      if (p.res) { v += up4(rr[b][a]); if (p.res_lo) v += up4(rl[b][a]); }
-      if (p.out_f32) {
-        *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.y) + m * p.ldy + n) = v;
-      } else {
-        const f16x4 o = cvt4(v);
-        *reinterpret_cast<f16x4*>(reinterpret_cast<f16*>(p.y) + m * p.ldy + n) = o;
-        if (p.y_lo) *reinterpret_cast<f16x4*>(reinterpret_cast<f16*>(p.y) + m * p.ldy + p.y_lo + n) = cvt4(v - up4(o));
-        if (p.stats) acc[a][b] = p.y_lo ? split_stat4(v) : up4(o);
-      }
-    }
+    const int m = row_of(b);
+    if (m < 0) continue;
+    f32x4 tt[NT];   // the time embedding of this row's image
+    if (p.temb) epi_load_cols<NT>(p.temb + (long long)(m / HWo) * p.ld_temb, ncol, p.N, tt);
+    epi_store8_row<MT, NT>(p, acc, b, m, [&](int a, int mt) { f32x4 v = acc[a][mt] + bb[a]; if (p.temb) v += tt[a]; return v; }, osc, rr, rl, ncol);
   }
-  if (p.stats) {   // fused GroupNorm statistics per 32-row block (common.h)
-    bool ok[MT];
-#pragma unroll
-    for (int b = 0; b < MT; ++b) ok[b] = mrow[b] >= 0;
-#pragma unroll
-    for (int sb = 0; sb < MT / 2; ++sb) {
-      const long long blk = (m0 + wave_m * (BM / 2)) / 32 + sb, R = p.stats_R;   // global 32-row block -> (image, block in image)
-      if (blk * 32 < p.M) wave_stats_store<MT, NT>(acc, ok, 2 * sb, 2 * sb + 2, p.stats + ((blk / R) * p.N * R + blk % R) * 2, R, p.N, ncol, l15);
-    }
-  }
+  if (p.stats) epi_stats_blocks32<MT, NT>(p, acc, row_of, (m0 + wave_m * (BM / 2)) / 32, ncol, l15);   // fused GroupNorm statistics per 32-row block
 }
 
 template <int BM, int BN, bool FAST, bool GN>

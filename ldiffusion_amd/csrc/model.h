@@ -14,6 +14,8 @@
 #include "../../include/ldiff.h"
 #include "common.h"
 
+static inline int roundup(int x, int m) { return (x + m - 1) / m * m; }
+
 // NHWC fp16 activation (tokens [M, C] are B=1,H=1,W=M or keep the image shape).  A SPLIT activation stores every row as
 // [hi(C) | lo(C)] with value = hi + lo (~22 significant bits): the residual stream is kept this way so that
 // the reference's fp32 residual adds survive ~40 chained blocks; plain consumers read the hi half with row pitch 2C, split

@@ -21,8 +21,6 @@ void ldiff_set_error(const char* fmt, ...) {
 }
 const char* ldiff_error_message() { return g_err; }
 
-static inline int roundup(int x, int m) { return (x + m - 1) / m * m; }
-
 // ---- per-(device, kernel) launch attribute ---------------------------------------------------------
 #include <mutex>
 #include <set>

@@ -6,7 +6,6 @@
 
 #include "model.h"
 
-static inline int roundup(int x, int m) { return (x + m - 1) / m * m; }
 static const float IN_EPS = 1e-5f;   // InstanceNorm2d's eps in every nnU-Net plans file (norm_op_kwargs)
 
 void ldiff_segnet::build() {

@@ -7,8 +7,6 @@
 
 #include "model.h"
 
-static inline int roundup(int x, int m) { return (x + m - 1) / m * m; }
-
 // ---- host repack ---------------------------------------------------------------------------------
 static float host_to_float(const void* p, int dtype, size_t i) {   // element i of a host tensor of dtype LDIFF_F32 / F16 / BF16
   if (dtype == LDIFF_F32) return ((const float*)p)[i];

@@ -408,6 +408,21 @@ def test_conv_explicit_split_counts(lib, name, splitk):
     assert_conv_close(got, ref, f"{name} splitk={splitk}", gn=use_gn)
 
 
+@pytest.mark.parametrize("name", ["3x3_8x8_bn32", "3x3_wide_bn32", "1x1_gemm_dma_64x64", "3x3_stride2_sym"])
+def test_conv_fp32_output_on_row_group_kernels(lib, name):
+    """The fp32-output branch of the shared row-group epilogue (csrc/epilogue.h) on each kernel that has it, with bias and residual: test_conv
+    reaches an fp32 output only on the narrow-output kernels, which have an epilogue of their own."""
+    B, C1, C2, H, W, Cout, ks, stride, ups, asym, use_gn, _ = CONV_CASES[name]
+    g = torch.Generator().manual_seed(zlib.crc32(name.encode()) % 1000 + 32)
+    x = torch.randn((B, C1, H, W), generator=g)
+    w = torch.randn((Cout, C1, ks, ks), generator=g) / math.sqrt(C1 * ks * ks)
+    bias = torch.randn(Cout, generator=g) * 0.1
+    Ho, Wo = (H + 2 * (ks // 2) - ks) // stride + 1, (W + 2 * (ks // 2) - ks) // stride + 1
+    res = torch.randn((B, Cout, Ho, Wo), generator=g)
+    got, ref = run_conv(lib, x, w, bias, None, stride, (ks // 2, ks // 2), 0, None, 0, None, res, True, False, expect=CONV_KERNEL[name])
+    assert_conv_close(got, ref, f"{name} fp32 output")
+
+
 @pytest.mark.parametrize("silu", [0, 1])
 def test_narrow_conv_tap_folded_against_the_lds_image_kernel(lib, silu):
     """conv_out of the VAE decoder (128 -> 3, GroupNorm prologue): the tap-folded kernel (taps as output columns of one narrow GEMM over the halo
