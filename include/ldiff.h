@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define LDIFF_VERSION 206 /* 0.2.0.6: + ldiff_op_seg_sample (patches, labels and deep-supervision targets of a training batch from cases resident on the device), ldiff_op_seg_intensity (nnU-Net's intensity augmentations, one workgroup per plane); 0.2.0.5: + ldiff_unet_set_plan_batch / ldiff_vae_set_plan_batch / ldiff_controlnet_set_plan_batch (batch-invariant mode: every launch planned for a nominal batch), ldiff_op_conv_pb, ldiff_op_attention_pb, ldiff_op_gn_stats_pb; 0.2.0.4: + ldiff_op_in_train_fwd / _bwd (InstanceNorm + LeakyReLU with saved statistics), ldiff_op_dice_ce (nnU-Net deep-supervision loss of one scale, value and gradient), ldiff_op_sgd_nesterov_multi; 0.2.0.3: + ldiff_confusion (per-image confusion matrices of masks or logits against labels, accumulated on the device), ldiff_seg_metrics (host: Dice / IoU / pixel accuracy / frequency-weighted IoU from one matrix); 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
+#define LDIFF_VERSION 207 /* 0.2.0.7: + ldiff_op_conv_wgrad (direct MFMA weight gradient of the narrow convs over the pixel index, no im2col), ldiff_op_colsum_slabs (slab-reduced bias gradient), both with fixed-order partials; 0.2.0.6: + ldiff_op_seg_sample (patches, labels and deep-supervision targets of a training batch from cases resident on the device), ldiff_op_seg_intensity (nnU-Net's intensity augmentations, one workgroup per plane); 0.2.0.5: + ldiff_unet_set_plan_batch / ldiff_vae_set_plan_batch / ldiff_controlnet_set_plan_batch (batch-invariant mode: every launch planned for a nominal batch), ldiff_op_conv_pb, ldiff_op_attention_pb, ldiff_op_gn_stats_pb; 0.2.0.4: + ldiff_op_in_train_fwd / _bwd (InstanceNorm + LeakyReLU with saved statistics), ldiff_op_dice_ce (nnU-Net deep-supervision loss of one scale, value and gradient), ldiff_op_sgd_nesterov_multi; 0.2.0.3: + ldiff_confusion (per-image confusion matrices of masks or logits against labels, accumulated on the device), ldiff_seg_metrics (host: Dice / IoU / pixel accuracy / frequency-weighted IoU from one matrix); 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
 #define LDIFF_MAX_BLOCKS 8
 
 typedef enum { LDIFF_OK = 0, LDIFF_ERR_INVALID = -1, LDIFF_ERR_RUNTIME = -2, LDIFF_ERR_STATE = -3, LDIFF_ERR_NONFINITE = -4 } ldiff_status;
@@ -667,6 +667,24 @@ int ldiff_op_dice_ce(const void* logits, int ld, int n_heads, const void* target
  *   g = inv_scale * clip_coef * grad + weight_decay * p;   buf = first ? g : momentum * buf + g;   p -= lr * (g + momentum * buf) */
 int ldiff_op_sgd_nesterov_multi(const void* tensors, const void* grads, const void* chunks, int64_t nchunks, float lr, float momentum, float weight_decay,
                                 int first, const void* inv_scale, const void* clip_coef, void* stream);
+
+/* Weight and bias gradients of the narrow convs of nnUNetTrainer.train_step's backward (`self.grad_scaler.scale(l).backward()`), where M = B Ho Wo runs to
+ * millions of rows under 32 .. 128 channels: both reduce through per-workgroup fp32 partials in a caller-supplied workspace (16-byte aligned) and a finalize
+ * that adds them in workgroup order -- no floating-point atomics, a replay on the same inputs is bit-identical.
+ *
+ * ldiff_op_conv_wgrad: dw[n][c][ky][kx] (f32, torch's [Cout][Cin][k][k], OVERWRITTEN) = sum_(b,oy,ox) dy[b,oy,ox,n] x[b, oy stride - pad + ky, ox stride - pad + kx, c],
+ *   zero outside the image, straight from x f16 [B,H,W,Cx] and dy f16 [B,Ho,Wo,Cy] (NHWC; channels c >= Cin of x and n >= Cout of dy take no part): no
+ *   im2col, no transposed copy, no unpack launch.  Accepted, anything else LDIFF_ERR_INVALID naming the argument: k = 3 with stride 1 or 2 (pad 1) or k = 1
+ *   with stride 1 (pad 0); Ho, Wo = the conv's output size (no upsampling); Cx % 8 == 0, Cx <= 128; Cy % 8 == 0, Cy <= 64 (k = 3) or 128 (k = 1);
+ *   1 <= Cout <= Cy, 1 <= Cin <= Cx; ws_bytes >= ldiff_op_conv_wgrad_ws_bytes(...) (0 for a shape that is not accepted) for the same wgs.
+ *   wgs = 0: the library plans the persistent grid; wgs > 0: that many tile-walking workgroups per 32-channel slab of Cx (tests: few workgroups walking many
+ *   tiles, or more workgroups than tiles -- an idle workgroup contributes exact zeros).
+ * ldiff_op_colsum_slabs: db[n] (f32 [N], OVERWRITTEN) = sum_m dy[m, n] over row slabs; dy f16 [M, ld], N % 8 == 0, N <= 2048, ld % 8 == 0, ld >= N, M >= 1. */
+int64_t ldiff_op_conv_wgrad_ws_bytes(int B, int Ho, int Wo, int Cx, int Cy, int k, int wgs);
+int ldiff_op_conv_wgrad(const void* x, const void* dy, void* dw_f32, int B, int H, int W, int Cx, int Ho, int Wo, int Cy, int Cout, int Cin, int k, int stride, int wgs,
+                        void* ws, int64_t ws_bytes, void* stream);
+int64_t ldiff_op_colsum_slabs_ws_bytes(int64_t M, int N);
+int ldiff_op_colsum_slabs(const void* dy, void* db_f32, int64_t M, int N, int ld, void* ws, int64_t ws_bytes, void* stream);
 
 /* Tissue head, training data: nnUNetDataLoader2D + the transforms of nnUNetTrainer.get_training_transforms (minus SimulateLowResolutionTransform),
  * on cases that stay on the device.  The host draws every random number and hands the kernels three tables (device memory, plain C structs):

@@ -200,6 +200,10 @@ SIGNATURES = {
     "ldiff_op_dice_ce_ws_bytes": (I64, [I, I64, I]),
     "ldiff_op_dice_ce": (I, [P, I, I, P, I, I, I64, I, F, F, F, P, P, P, I64, P]),
     "ldiff_op_sgd_nesterov_multi": (I, [P, P, P, I64, F, F, F, I, P, P, P]),
+    "ldiff_op_conv_wgrad_ws_bytes": (I64, [I, I, I, I, I, I, I]),
+    "ldiff_op_conv_wgrad": (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, I64, P]),
+    "ldiff_op_colsum_slabs_ws_bytes": (I64, [I64, I]),
+    "ldiff_op_colsum_slabs": (I, [P, P, I64, I, I, P, I64, P]),
     "ldiff_op_seg_sample": (I, [P, I64, P, I, P, I, I, I, I, I, P, P, P]),
     "ldiff_op_seg_intensity_ws_bytes": (I64, [I, I, I, I]),
     "ldiff_op_seg_intensity": (I, [P, P, P, I, I, I, I, P, U64, P, I64, P]),

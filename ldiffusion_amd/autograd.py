@@ -6,7 +6,9 @@ This is the arithmetic layer of the reference's fine-tuning step (/root/referenc
 by the weights it reads and writes.  Conventions: activations and their gradients are NHWC float16 CUDA tensors, parameters are float32
 masters in the torch / diffusers layouts ([Cout, Cin, k, k], [out, in]) and receive float32 gradients.
   * dgrad = the forward conv kernel on the weights rearranged to [Cin][k][k][Cout] with the taps flipped (a layout cast in torch),
-  * wgrad = the forward GEMM kernel over K = M on dy^T (ldiff_op_transpose) and im2col(x)^T (ldiff_op_im2col_t),
+  * wgrad = the forward GEMM kernel over K = M on dy^T (ldiff_op_transpose) and im2col(x)^T (ldiff_op_im2col_t): the "staged" route, the default;
+    under `wgrad_route("direct")` / `("auto")` the narrow convs over many pixels take ldiff_op_conv_wgrad (an MFMA contraction over the pixel index straight
+    from the NHWC tensors) and the bias gradients ldiff_op_colsum_slabs instead (csrc/kernels_wgrad.hip; the tissue-head trainer runs under "auto"),
   * GroupNorm(+SiLU), LayerNorm, GEGLU, attention: dedicated backward kernels (csrc/kernels_bwd.hip).
 There is no CPU or torch-op fallback for those; reshapes / layout casts / the residual `+` are torch tensor plumbing.
 """
@@ -161,6 +163,116 @@ def _conv_call(x, w16, Cout, k, stride, ups, bias=None, Ho=None, Wo=None, out_f3
     return y
 
 
+# ---- which kernels form a conv's weight and bias gradient ----
+# "staged": transpose + im2col_t + GEMM over K = M, and ldiff_op_colsum: what the fine-tuning step was built on (M a few hundred rows, N hundreds of columns).
+# "direct": ldiff_op_conv_wgrad wherever the shape is eligible (else staged) and ldiff_op_colsum_slabs for every bias gradient.
+# "auto":   "direct" for the launches with M = B Ho Wo >= WGRAD_DIRECT_MIN_ROWS, "staged" below.
+# The route is read when the FORWARD runs and kept with the node, so a backward() called outside the `with` follows the forward's route.
+WGRAD_ROUTES = ("staged", "direct", "auto")
+# Crossover of the two routes at 32 -> 32 channels, 3 x 3, B = 1 (scripts/bench_wgrad_routes.py on an MI355X, weight + bias gradient, device time per backward,
+# median of 20, the routes alternating; DESIGN.md section 7 "Direct weight and bias gradients"):
+#     M        1024    4096    9216    16384    36864    65536    262144
+#     staged    178     231     346     1044     2480     4389     17397  us
+#     direct    161     163      70       71      104      109       176  us
+# The direct route is the faster one from the smallest M measured on: the crossover lies BELOW 16384, and the constant never goes below 16384 -- the trainer's
+# tests reach M = 2 * 64^2 = 8192 and keep the staged route bit for bit -- so the floor is the value.
+WGRAD_DIRECT_MIN_ROWS = 16384
+_WGRAD_ROUTE = "staged"
+_WGRAD_ROUTE_STATED = False   # a caller has set the route (nnunet_train.TrainableSegNet runs under "auto" unless one has)
+
+
+def _check_route(mode):
+    if mode not in WGRAD_ROUTES:
+        raise ValueError(f"wgrad route {mode!r}: one of {WGRAD_ROUTES}")
+
+
+def set_wgrad_route(mode: str) -> str:
+    """Set the module-wide route of weight / bias gradients ("staged", "direct" or "auto"); returns the previous one."""
+    global _WGRAD_ROUTE, _WGRAD_ROUTE_STATED
+    _check_route(mode)
+    prev, _WGRAD_ROUTE, _WGRAD_ROUTE_STATED = _WGRAD_ROUTE, mode, True
+    return prev
+
+
+def stated_wgrad_route(default: str) -> str:
+    """The route a caller has set (set_wgrad_route, or an enclosing wgrad_route), else `default`."""
+    return _WGRAD_ROUTE if _WGRAD_ROUTE_STATED else default
+
+
+class wgrad_route:
+    """`with wgrad_route("direct"):` -- the Conv2dFn nodes whose forward runs inside take that route in their backward."""
+
+    def __init__(self, mode: str):
+        _check_route(mode)
+        self.mode = mode
+
+    def __enter__(self):
+        global _WGRAD_ROUTE, _WGRAD_ROUTE_STATED
+        self.prev = (_WGRAD_ROUTE, _WGRAD_ROUTE_STATED)
+        _WGRAD_ROUTE, _WGRAD_ROUTE_STATED = self.mode, True
+        return self
+
+    def __exit__(self, *exc):
+        global _WGRAD_ROUTE, _WGRAD_ROUTE_STATED
+        _WGRAD_ROUTE, _WGRAD_ROUTE_STATED = self.prev
+        return False
+
+
+def wgrad_direct_eligible(k, stride, ups, Cx, Cy, Cout, Cin) -> bool:
+    """The shapes ldiff_op_conv_wgrad takes (include/ldiff.h)."""
+    return (ups == 0 and ((k == 3 and stride in (1, 2)) or (k == 1 and stride == 1)) and Cx % 8 == 0 and 8 <= Cx <= 128 and Cy % 8 == 0
+            and 8 <= Cy <= (64 if k == 3 else 128) and 1 <= Cout <= Cy and 1 <= Cin <= Cx)
+
+
+def wgrad_plan(B, Ho, Wo, Cx, Cy, k, wgs=0) -> dict:
+    """The plan ldiff_op_conv_wgrad makes for a launch (csrc/kernels_wgrad.hip wgrad_plan), for the error bounds of the tests: tiles of TH x 32 output pixels
+    (k = 1: TH * 32 consecutive pixels), `wgs` tile-walking workgroups per 32-channel slab of Cx, `chain` = the most terms one accumulator adds (an MFMA's inner
+    sum counted as 32) and `partials` = the partial sums the finalize adds per element."""
+    TH = 8 if k == 1 else 4
+    ntw = 1 if Cy <= 32 else 2 if Cy <= 64 else 4
+    slabs = -(-Cx // 32)
+    tiles = -(-(B * Ho * Wo) // (TH * 32)) if k == 1 else B * (-(-Ho // TH)) * (-(-Wo // 32))
+    n = wgs if wgs > 0 else min(tiles, 1024 // slabs)
+    return dict(TH=TH, tiles=tiles, wgs=n, slabs=slabs, chain=-(-tiles // n) * TH * 32, partials=n, ws_bytes=n * 32 * ntw * k * k * slabs * 32 * 4)
+
+
+def colsum_slabs_plan(M, N) -> dict:
+    """The plan of ldiff_op_colsum_slabs (csrc/kernels_wgrad.hip colsum_plan): `chain` = rows one thread adds plus the row lanes one LDS pass adds."""
+    rp = 256 // (N // 8)
+    slabs = min(max(-(-M // 256), 1), 1024)
+    rows = -(-M // slabs)
+    slabs = -(-M // rows)
+    return dict(slabs=slabs, rows=rows, row_lanes=rp, chain=-(-rows // rp) + rp, partials=slabs, ws_bytes=slabs * N * 4)
+
+
+def conv_wgrad_direct(x, dy, Cout, Cin, k, stride, wgs=0):
+    """ldiff_op_conv_wgrad: x [B,H,W,Cx], dy [B,Ho,Wo,Cy] NHWC float16 -> dw float32 [Cout, Cin, k, k]."""
+    _check_act(x, "x")
+    _check_act(dy, "dy")
+    lib = _lib.load()
+    B, H, W, Cx = x.shape
+    _, Ho, Wo, Cy = dy.shape
+    dw = torch.empty((Cout, Cin, k, k), dtype=torch.float32, device=x.device)
+    nb = lib.ldiff_op_conv_wgrad_ws_bytes(B, Ho, Wo, Cx, Cy, k, int(wgs))
+    ws = _workspace(nb, x.device)
+    _lib.check(lib.ldiff_op_conv_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, Cx, Ho, Wo, Cy, Cout, Cin, k, stride, int(wgs), ws.data_ptr(), nb, _sp()))
+    return dw
+
+
+def colsum_slabs(dy, N=None):
+    """ldiff_op_colsum_slabs over the rows of float16 dy [..., ld]: float32 [N] (N = ld unless given)."""
+    _check_act(dy, "dy")
+    lib = _lib.load()
+    ld = dy.shape[-1]
+    N = ld if N is None else N
+    M = dy.numel() // ld
+    db = torch.empty(N, dtype=torch.float32, device=dy.device)
+    nb = lib.ldiff_op_colsum_slabs_ws_bytes(M, N)
+    ws = _workspace(nb, dy.device)
+    _lib.check(lib.ldiff_op_colsum_slabs(dy.data_ptr(), db.data_ptr(), M, N, ld, ws.data_ptr(), nb, _sp()))
+    return db
+
+
 class Conv2dFn(torch.autograd.Function):
     """y = conv2d(nearest_up(x, 2**ups), weight, bias, stride, padding=k//2) on NHWC float16 activations (k in {1, 3}).
     Channel counts of x must be multiples of 8 (pad the 4-channel latents); y has roundup(Cout, 8) channels, the pad columns zero."""
@@ -174,6 +286,7 @@ class Conv2dFn(torch.autograd.Function):
         y = _conv_call(x, pack_weight(weight), Cout, k, stride, ups, bias)
         ctx.save_for_backward(x, weight)
         ctx.meta = (stride, ups, bias is not None, k, Cout, Cin)
+        ctx.wgrad_route = _WGRAD_ROUTE
         return y
 
     @staticmethod
@@ -186,6 +299,7 @@ class Conv2dFn(torch.autograd.Function):
         _, Ho, Wo, Cy = dy.shape
         w4 = weight if weight.dim() == 4 else weight[:, :, None, None]
         dx = dw = db = None
+        direct = ctx.wgrad_route == "direct" or (ctx.wgrad_route == "auto" and B * Ho * Wo >= WGRAD_DIRECT_MIN_ROWS)
         if ctx.needs_input_grad[0]:
             # dgrad: conv (stride 1) of dy -- zero-inserted for a stride-2 forward -- with the weights [Cin][k][k][Cout], taps flipped
             wd = pack_weight(w4, dgrad=True, cols=Cy)
@@ -196,7 +310,9 @@ class Conv2dFn(torch.autograd.Function):
                 g[:, ::2, ::2] = dy
             dxu = _conv_call(g, wd, Cx, k, 1, 0)
             dx = dxu if ups == 0 else dxu.view(B, H, 2, W, 2, Cx).float().sum((2, 4)).to(torch.float16)
-        if ctx.needs_input_grad[1]:
+        if ctx.needs_input_grad[1] and direct and wgrad_direct_eligible(k, stride, ups, Cx, Cy, Cout, Cin):
+            dw = conv_wgrad_direct(x, dy, Cout, Cin, k, stride).view(weight.shape)
+        elif ctx.needs_input_grad[1]:
             # wgrad: dW[n][tap*Cx + c] = sum_m dy[m, n] * xcol[m, tap*Cx + c]  as a GEMM over K = M
             M = B * Ho * Wo
             Mpad = _r(M, 8)
@@ -214,8 +330,11 @@ class Conv2dFn(torch.autograd.Function):
                 dw = torch.empty(weight.shape, dtype=torch.float32, device=x.device)
                 _lib.check(lib.ldiff_op_unpack_wgrad(g.data_ptr(), dw.data_ptr(), Cout, Cin, k, Cx, g.shape[-1], _sp()))
         if has_bias and ctx.needs_input_grad[2]:
-            db = torch.empty(Cy, dtype=torch.float32, device=x.device)
-            _lib.check(lib.ldiff_op_colsum(dy.data_ptr(), db.data_ptr(), B * Ho * Wo, Cy, Cy, _sp()))
+            if direct and Cy % 8 == 0 and Cy <= 2048:
+                db = colsum_slabs(dy)
+            else:
+                db = torch.empty(Cy, dtype=torch.float32, device=x.device)
+                _lib.check(lib.ldiff_op_colsum(dy.data_ptr(), db.data_ptr(), B * Ho * Wo, Cy, Cy, _sp()))
             db = db[:Cout]
         return dx, dw, db, None, None
 

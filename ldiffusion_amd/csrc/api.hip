@@ -1090,6 +1090,27 @@ int ldiff_op_sgd_nesterov_multi(const void* tensors, const void* grads, const vo
                             (const float*)inv_scale, (const float*)clip_coef, (hipStream_t)stream);
   API_END
 }
+// ---- direct weight / bias gradients of the tissue head's narrow convs (kernels_wgrad.hip) ----
+int64_t ldiff_op_conv_wgrad_ws_bytes(int B, int Ho, int Wo, int Cx, int Cy, int k, int wgs) { return conv_wgrad_ws_bytes(B, Ho, Wo, Cx, Cy, k, wgs); }
+int ldiff_op_conv_wgrad(const void* x, const void* dy, void* dw_f32, int B, int H, int W, int Cx, int Ho, int Wo, int Cy, int Cout, int Cin, int k, int stride, int wgs,
+                        void* ws, int64_t ws_bytes, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(x, LDIFF_ERR_INVALID, "op_conv_wgrad: null argument x");
+  LDIFF_CHECK(dy, LDIFF_ERR_INVALID, "op_conv_wgrad: null argument dy");
+  LDIFF_CHECK(dw_f32, LDIFF_ERR_INVALID, "op_conv_wgrad: null argument dw_f32");
+  LDIFF_CHECK(ws, LDIFF_ERR_INVALID, "op_conv_wgrad: null argument ws");
+  launch_conv_wgrad((const f16*)x, (const f16*)dy, (float*)dw_f32, B, H, W, Cx, Ho, Wo, Cy, Cout, Cin, k, stride, wgs, (float*)ws, ws_bytes, (hipStream_t)stream);
+  API_END
+}
+int64_t ldiff_op_colsum_slabs_ws_bytes(int64_t M, int N) { return colsum_slabs_ws_bytes(M, N); }
+int ldiff_op_colsum_slabs(const void* dy, void* db_f32, int64_t M, int N, int ld, void* ws, int64_t ws_bytes, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(dy, LDIFF_ERR_INVALID, "op_colsum_slabs: null argument dy");
+  LDIFF_CHECK(db_f32, LDIFF_ERR_INVALID, "op_colsum_slabs: null argument db_f32");
+  LDIFF_CHECK(ws, LDIFF_ERR_INVALID, "op_colsum_slabs: null argument ws");
+  launch_colsum_slabs((const f16*)dy, (float*)db_f32, M, N, ld, (float*)ws, ws_bytes, (hipStream_t)stream);
+  API_END
+}
 // ---- training data of the tissue head (kernels_segaug.hip) ----
 int ldiff_op_seg_sample(const void* arena, int64_t arena_bytes, const ldiff_seg_case* cases, int n_cases, const ldiff_seg_sample* samples, int B, int Cc, int h,
                         int w, int n_scales, void* data, void* target, void* stream) {

@@ -340,6 +340,12 @@ void launch_dice_ce(const f16* logits, int ld, int n_heads, const void* target, 
 struct SgdTensor { float* p; float* buf; long long n; };
 void launch_sgd_nesterov_multi(const SgdTensor* tensors, const float* const* grads, const AdamChunk* chunks, long long nchunks, float lr, float momentum, float wd,
                                int first, const float* inv_scale, const float* clip_coef, hipStream_t s);
+// direct weight gradient of the narrow convs and slab-reduced bias gradient (kernels_wgrad.hip): per-workgroup partials in the caller's workspace, fixed-order finalize
+long long conv_wgrad_ws_bytes(int B, int Ho, int Wo, int Cx, int Cy, int k, int wgs);   // 0: a shape the kernel does not take
+void launch_conv_wgrad(const f16* x, const f16* dy, float* dw, int B, int H, int W, int Cx, int Ho, int Wo, int Cy, int Cout, int Cin, int k, int stride, int wgs,
+                       float* ws, long long ws_bytes, hipStream_t s);
+long long colsum_slabs_ws_bytes(long long M, int N);
+void launch_colsum_slabs(const f16* dy, float* db, long long M, int N, int ld, float* ws, long long ws_bytes, hipStream_t s);
 
 // training data of the tissue head (kernels_segaug.hip): patch sampling with deep-supervision targets, and the intensity chain, per batch
 void launch_seg_sample(const void* arena, long long arena_bytes, const ldiff_seg_case* cases, int n_cases, const ldiff_seg_sample* samples, int B, int C, int h, int w, int n_scales,

@@ -113,7 +113,10 @@ class TrainableSegNet(train._Graph):
         if x.shape[2] % div or x.shape[3] % div:
             raise ValueError(f"TrainableSegNet: input {list(x.shape[2:])} is not divisible by the product of the strides, {div}")
         n = sp["n_stages"]
-        with torch.cuda.device(self.device):
+        # "auto": the convs with M = B Ho Wo >= ag.WGRAD_DIRECT_MIN_ROWS take the direct weight gradient and the slab column sum in their backward (the route is kept
+        # with each node); a route the caller has stated (ag.wgrad_route, ag.set_wgrad_route) holds instead
+        route = ag.wgrad_route(ag.stated_wgrad_route("auto"))
+        with torch.cuda.device(self.device), route:
             h = train._nhwc16(x.to(self.device, torch.float32))
             skips = []
             for s in range(n):
