@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define LDIFF_VERSION 207 /* 0.2.0.7: + ldiff_op_conv_wgrad (direct MFMA weight gradient of the narrow convs over the pixel index, no im2col), ldiff_op_colsum_slabs (slab-reduced bias gradient), both with fixed-order partials; 0.2.0.6: + ldiff_op_seg_sample (patches, labels and deep-supervision targets of a training batch from cases resident on the device), ldiff_op_seg_intensity (nnU-Net's intensity augmentations, one workgroup per plane); 0.2.0.5: + ldiff_unet_set_plan_batch / ldiff_vae_set_plan_batch / ldiff_controlnet_set_plan_batch (batch-invariant mode: every launch planned for a nominal batch), ldiff_op_conv_pb, ldiff_op_attention_pb, ldiff_op_gn_stats_pb; 0.2.0.4: + ldiff_op_in_train_fwd / _bwd (InstanceNorm + LeakyReLU with saved statistics), ldiff_op_dice_ce (nnU-Net deep-supervision loss of one scale, value and gradient), ldiff_op_sgd_nesterov_multi; 0.2.0.3: + ldiff_confusion (per-image confusion matrices of masks or logits against labels, accumulated on the device), ldiff_seg_metrics (host: Dice / IoU / pixel accuracy / frequency-weighted IoU from one matrix); 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
+#define LDIFF_VERSION 208 /* 0.2.0.8: + ldiff_op_seg_intensity_lr (the intensity chain with nnU-Net's low-resolution simulation between contrast and the gammas), ldiff_op_spline_prefilter (cubic B-spline prefilter on the device, one workgroup per plane); 0.2.0.7: + ldiff_op_conv_wgrad (direct MFMA weight gradient of the narrow convs over the pixel index, no im2col), ldiff_op_colsum_slabs (slab-reduced bias gradient), both with fixed-order partials; 0.2.0.6: + ldiff_op_seg_sample (patches, labels and deep-supervision targets of a training batch from cases resident on the device), ldiff_op_seg_intensity (nnU-Net's intensity augmentations, one workgroup per plane); 0.2.0.5: + ldiff_unet_set_plan_batch / ldiff_vae_set_plan_batch / ldiff_controlnet_set_plan_batch (batch-invariant mode: every launch planned for a nominal batch), ldiff_op_conv_pb, ldiff_op_attention_pb, ldiff_op_gn_stats_pb; 0.2.0.4: + ldiff_op_in_train_fwd / _bwd (InstanceNorm + LeakyReLU with saved statistics), ldiff_op_dice_ce (nnU-Net deep-supervision loss of one scale, value and gradient), ldiff_op_sgd_nesterov_multi; 0.2.0.3: + ldiff_confusion (per-image confusion matrices of masks or logits against labels, accumulated on the device), ldiff_seg_metrics (host: Dice / IoU / pixel accuracy / frequency-weighted IoU from one matrix); 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
 #define LDIFF_MAX_BLOCKS 8
 
 typedef enum { LDIFF_OK = 0, LDIFF_ERR_INVALID = -1, LDIFF_ERR_RUNTIME = -2, LDIFF_ERR_STATE = -3, LDIFF_ERR_NONFINITE = -4 } ldiff_status;
@@ -686,15 +686,15 @@ int ldiff_op_conv_wgrad(const void* x, const void* dy, void* dw_f32, int B, int 
 int64_t ldiff_op_colsum_slabs_ws_bytes(int64_t M, int N);
 int ldiff_op_colsum_slabs(const void* dy, void* db_f32, int64_t M, int N, int ld, void* ws, int64_t ws_bytes, void* stream);
 
-/* Tissue head, training data: nnUNetDataLoader2D + the transforms of nnUNetTrainer.get_training_transforms (minus SimulateLowResolutionTransform),
- * on cases that stay on the device.  The host draws every random number and hands the kernels three tables (device memory, plain C structs):
+/* Tissue head, training data: nnUNetDataLoader2D + the transforms of nnUNetTrainer.get_training_transforms (SimulateLowResolutionTransform only through
+ * ldiff_op_seg_intensity_lr), on cases that stay on the device.  The host draws every random number and hands the kernels three tables (device memory, plain C structs):
  *   ldiff_seg_case    one per case: byte offsets into ONE arena (16-byte aligned) of the cubic B-spline coefficients f32 [C, H, stride], the raw
  *                     normalised image f32 [C, H, stride] and the labels u8 [H, label_stride]
  *   ldiff_seg_sample  one per sample: the case; m, the patch index (i, j) -> case coordinate map  y = m[0] i + m[1] j + m[2],  x = m[3] i + m[4] j + m[5]
  *                     (rotation, scale, mirror and crop centre folded in); copy != 0: m[0], m[4] are +-1 and m[2], m[5] integers, and the sample is an
  *                     exact crop of the raw image; the Gaussian noise's sigma (0 = off) and the sample's first Philox counter
- *   ldiff_seg_chan    one per (sample, channel): 0 = off, except brightness (1 = off).  lowres_zoom is reserved (the low-resolution simulation is
- *                     not built) and is not read.
+ *   ldiff_seg_chan    one per (sample, channel): 0 = off, except brightness (1 = off).  lowres_zoom is read by ldiff_op_seg_intensity_lr alone; for
+ *                     ldiff_op_seg_intensity it stays a reserved slot that is not read.
  * ldiff_op_seg_sample: data f32 [B, C, h, w]: order-3 spline of the coefficients (scipy.ndimage.map_coordinates(order=3, mode='constant', cval=0): taps
  *   mirrored at whole samples, 0 where a coordinate leaves [0, n - 1]).  target u8: the n_scales label maps [B, 1, h >> k, w >> k], one after the other,
  *   scale k holding the label of full-resolution pixel (2^k i + 2^(k-1), 2^k j + 2^(k-1)); a label is the highest one whose bilinear indicator reaches
@@ -705,7 +705,18 @@ int ldiff_op_colsum_slabs(const void* dy, void* db_f32, int64_t M, int N, int ld
  *   counts as off and the plane is not blurred); x * brightness; clip((x - mean) contrast + mean, min, max); gamma with retained statistics on -x (gamma_inverted) and on x (gamma):
  *   ((x - min) / (max - min + 1e-7))^g (max - min) + min, then (x - mean') / (std' + 1e-8) * std + mean.  normal: f32 [B, C, h, w] draws, or NULL:
  *   Box-Muller over Philox4x32-10 keyed by (seed, philox_offset + (c h w + i) / 4).  ws: ldiff_op_seg_intensity_ws_bytes(...) bytes.  No atomics:
- *   a replay on the same inputs is bit-identical. */
+ *   a replay on the same inputs is bit-identical.
+ * ldiff_op_seg_intensity_lr: the same chain with SimulateLowResolutionTransform between contrast and the gammas, per plane with zoom = lowres_zoom:
+ *   target shape m = rint(h zoom), rint(w zoom) (float32 product, half to even); the step is off and the plane untouched when zoom is NaN or outside
+ *   (0, 1], when an m is below 1, or when m = (h, w).  d[i, j] = x[((2 i + 1) h) / (2 m0), ((2 j + 1) w) / (2 m1)] (order 0, integer division); d padded by 12
+ *   edge samples a side and prefiltered as by ldiff_op_spline_prefilter; output (i, j) = the cubic B-spline at (((2 i + 1) m0 - h) / (2 h),
+ *   ((2 j + 1) m1 - w) / (2 w)), floor and fraction formed in integers, 4 x 4 taps clamped to the padded plane; clipped to [min d, max d].  That is
+ *   scipy.ndimage.zoom(order 0, then order 3, mode='nearest', grid_mode=True) and the clip of skimage.transform.resize; where scipy's floating-point
+ *   order-0 index rounds an exact tie one lower, the integer rule stands.  h, w <= 16384.  ws: ldiff_op_seg_intensity_lr_ws_bytes(...) =
+ *   B C (h + 24) (w + 24) 4 bytes (the blur's plane lives in it too).  Same reduction order and determinism as ldiff_op_seg_intensity.
+ * ldiff_op_spline_prefilter: scipy.ndimage.spline_filter(order=3, mode='mirror') in place on n_planes f32 planes [H, W] of row stride `stride`, plane
+ *   p at planes + p H stride; axis 0 then axis 1, one workgroup per plane, the causal start summed over 64 samples (or exactly, over the mirrored
+ *   period, below 64).  Refused: H < 1, W < 1, stride < W, a pointer not aligned to 4 bytes, H stride >= 2^30. */
 typedef struct ldiff_seg_case { int64_t coef_off, raw_off, label_off; int32_t H, W, stride, label_stride; } ldiff_seg_case;
 typedef struct ldiff_seg_sample { float m[6]; int32_t case_index, copy; float noise_sigma; uint32_t reserved; uint64_t philox_offset; } ldiff_seg_sample;
 typedef struct ldiff_seg_chan { float blur_sigma, brightness, contrast, lowres_zoom, gamma_inverted, gamma; } ldiff_seg_chan;
@@ -714,6 +725,10 @@ int ldiff_op_seg_sample(const void* arena, int64_t arena_bytes, const ldiff_seg_
 int64_t ldiff_op_seg_intensity_ws_bytes(int B, int C, int h, int w);
 int ldiff_op_seg_intensity(void* data, const ldiff_seg_sample* samples, const ldiff_seg_chan* chans, int B, int C, int h, int w, const void* normal_or_null,
                            uint64_t seed, void* ws, int64_t ws_bytes, void* stream);
+int64_t ldiff_op_seg_intensity_lr_ws_bytes(int B, int C, int h, int w);
+int ldiff_op_seg_intensity_lr(void* data, const ldiff_seg_sample* samples, const ldiff_seg_chan* chans, int B, int C, int h, int w, const void* normal_or_null,
+                              uint64_t seed, void* ws, int64_t ws_bytes, void* stream);
+int ldiff_op_spline_prefilter(void* planes_f32, int n_planes, int H, int W, int stride, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Live measurement for bench.py's roofline line: when enabled, every conv/linear, attention and

@@ -207,6 +207,9 @@ SIGNATURES = {
     "ldiff_op_seg_sample": (I, [P, I64, P, I, P, I, I, I, I, I, P, P, P]),
     "ldiff_op_seg_intensity_ws_bytes": (I64, [I, I, I, I]),
     "ldiff_op_seg_intensity": (I, [P, P, P, I, I, I, I, P, U64, P, I64, P]),
+    "ldiff_op_seg_intensity_lr_ws_bytes": (I64, [I, I, I, I]),
+    "ldiff_op_seg_intensity_lr": (I, [P, P, P, I, I, I, I, P, U64, P, I64, P]),
+    "ldiff_op_spline_prefilter": (I, [P, I, I, I, I, P]),
     "ldiff_stream_create_cu_share": (I, [I, I, P]),
     "ldiff_stream_destroy": (I, [P]),
     "ldiff_vae_set_side_cu_share": (I, [P, I, I]),

@@ -1128,6 +1128,21 @@ int ldiff_op_seg_intensity(void* data, const ldiff_seg_sample* samples, const ld
   launch_seg_intensity((float*)data, samples, chans, B, Cc, h, w, (const float*)normal_or_null, seed, ws, ws_bytes, (hipStream_t)stream);
   API_END
 }
+int64_t ldiff_op_seg_intensity_lr_ws_bytes(int B, int Cc, int h, int w) {
+  if (B < 1 || Cc < 1 || h < 1 || w < 1) return 0;
+  return seg_intensity_lr_ws_bytes(B, Cc, h, w);
+}
+int ldiff_op_seg_intensity_lr(void* data, const ldiff_seg_sample* samples, const ldiff_seg_chan* chans, int B, int Cc, int h, int w, const void* normal_or_null,
+                              uint64_t seed, void* ws, int64_t ws_bytes, void* stream) {
+  API_BEGIN
+  launch_seg_intensity((float*)data, samples, chans, B, Cc, h, w, (const float*)normal_or_null, seed, ws, ws_bytes, (hipStream_t)stream, true);
+  API_END
+}
+int ldiff_op_spline_prefilter(void* planes_f32, int n_planes, int H, int W, int stride, void* stream) {
+  API_BEGIN
+  launch_spline_prefilter((float*)planes_f32, n_planes, H, W, stride, (hipStream_t)stream);
+  API_END
+}
 int ldiff_op_geglu(const void* x, void* y, int64_t M, int C4, void* stream) {
   API_BEGIN
   LDIFF_CHECK(x && y, LDIFF_ERR_INVALID, "op_geglu: null argument");

@@ -352,7 +352,10 @@ void launch_seg_sample(const void* arena, long long arena_bytes, const ldiff_seg
                        float* data, uint8_t* target, hipStream_t s);
 long long seg_intensity_ws_bytes(int B, int C, int h, int w);
 void launch_seg_intensity(float* data, const ldiff_seg_sample* samples, const ldiff_seg_chan* chans, int B, int C, int h, int w, const float* normal,
-                          unsigned long long seed, void* ws, long long ws_bytes, hipStream_t s);
+                          unsigned long long seed, void* ws, long long ws_bytes, hipStream_t s, bool lowres = false);
+// ... with the low-resolution simulation between contrast and the gammas (lowres = true; its own workspace size), and its cubic B-spline prefilter alone
+long long seg_intensity_lr_ws_bytes(int B, int C, int h, int w);
+void launch_spline_prefilter(float* planes, int n_planes, int H, int W, int stride, hipStream_t s);
 
 // Counter-based Philox4x32-10: four 32-bit words per (counter, key).  Used by the Laplace forward noise (kernels_elem.hip) and the augmentation noise
 // (kernels_segaug.hip).

@@ -6,8 +6,10 @@
     PatchLoader    iterator of {"data": [B, C, h, w] float32, "target": [n_scales x [B, 1, h_k, w_k] uint8]} -- what nnunet_train.Trainer takes.
                    Per batch: one pinned upload of the tables and two launches (ldiff_op_seg_sample, ldiff_op_seg_intensity); nothing synchronises.
 
-The chain is nnU-Net's minus SimulateLowResolutionTransform; `lowres_zoom` is its reserved table slot.  The bodies of the
-transforms live in `batchgenerators`, restated here from the public package; each rule sits in one function whose docstring names the class it mirrors.
+With `lowres=True` (draw_sample, draw_batch, augment_intensity_, PatchLoader) the chain is nnU-Net's whole chain: SimulateLowResolutionTransform is
+drawn into the table slot `lowres_zoom` and applied between contrast and the gammas by ldiff_op_seg_intensity_lr.  The default, `lowres=False`, is the
+chain minus that transform, byte for byte what it was.  The bodies of the transforms live in `batchgenerators`, restated here
+from the public package; each rule sits in one function whose docstring names the class it mirrors.
 
 One deliberate difference: nnU-Net crops `initial_patch_size` on the CPU, pads it and transforms that crop; here the kernel samples the case itself, so it
 sees the case's pixels where nnU-Net sees the intermediate crop's pad, and the spline coefficients are those of the whole case.  The crop centre, the
@@ -23,6 +25,7 @@ Order of draws (ours; `numpy.random`'s legacy stream is not reproduced).  Per sa
     5. random(5): the per-sample gates of blur, brightness, contrast, gamma on -x, gamma
     6. random((C, 12)): per channel  blur coin, blur sigma | brightness | contrast coin, below 1, above 1 | gamma on -x coin, below 1, above 1 |
        gamma coin, below 1, above 1
+    7. only with `lowres=True`: random(1): the per-sample gate of the low-resolution simulation; random((C, 2)): per channel its coin and zoom
 A value behind a closed gate, or the unused side of a coin, is drawn and dropped, so a sample always consumes the same count after step 2.
 """
 from __future__ import annotations
@@ -49,7 +52,16 @@ P_BRIGHTNESS, BRIGHTNESS = 0.15, (0.75, 1.25)
 P_CONTRAST, CONTRAST = 0.15, (0.75, 1.25)
 P_GAMMA_INVERTED, P_GAMMA, GAMMA = 0.1, 0.3, (0.7, 1.5)
 P_MIRROR = 0.5
+P_LOWRES, P_LOWRES_PER_CHANNEL, LOWRES_ZOOM = 0.25, 0.5, (0.5, 1.0)   # SimulateLowResolutionTransform (:719-722)
 OVERSAMPLE_FOREGROUND = 0.33   # nnUNetTrainer.oversample_foreground_percent
+SPLINE_PAD = 12                # edge samples a side around the down-sampled plane before its prefilter (scipy's 'nearest' spline extension)
+
+
+def lowres_shape(patch: Sequence[int], zoom) -> Tuple[int, int]:
+    """SimulateLowResolutionTransform's target shape of an [h, w] plane, np.round(shape * zoom), formed as the kernel forms it: the float32 product
+    rounded half to even."""
+    z = np.float32(zoom)
+    return int(np.rint(np.float32(int(patch[0])) * z)), int(np.rint(np.float32(int(patch[1])) * z))
 
 
 def rotate_coords_2d(coords: np.ndarray, angle: float) -> np.ndarray:
@@ -130,9 +142,16 @@ class CaseStore:
     (float32 [C, H, W]), the normalised image itself (float32 [C, H, W], what an unmodified sample copies) and the labels (uint8 [H, W]); `table` is the
     per-case ldiff_seg_case row (offsets, H, W, row strides).  `class_locations[i]`: {class: [n, 2] (row, column)} for the foreground classes
     1 .. n_heads - 1.  `labels`: a dataset.json `labels` mapping, only looked at to refuse what the tissue head does not cover.
-    `device="cpu"` keeps the arena on the host: enough for `draw_batch`, not for a PatchLoader."""
+    `device="cpu"` keeps the arena on the host: enough for `draw_batch`, not for a PatchLoader.
+    `prefilter`: "host" (the default) forms the coefficients by `spline_coefficients` in float64 and rounds them once; "device" uploads the normalised
+    image in their place and filters it there (`spline_prefilter_`), so the coefficients carry the float32 filter's own error, a few 1e-6 of the
+    image's magnitude (tests/nnunet_lowres_ref.py bounds it), and building the store needs the GPU."""
 
-    def __init__(self, cases, schemes: Sequence[str], n_heads: int, device="cuda:0", labels: Optional[dict] = None):
+    def __init__(self, cases, schemes: Sequence[str], n_heads: int, device="cuda:0", labels: Optional[dict] = None, prefilter: str = "host"):
+        if prefilter not in ("host", "device"):
+            raise ValueError(f"CaseStore: prefilter must be 'host' or 'device', got {prefilter!r}")
+        if prefilter == "device" and torch.device(device).type != "cuda":
+            raise ValueError("CaseStore: prefilter='device' needs the store on a GPU")
         if labels is not None:
             if any(isinstance(v, (list, tuple)) for v in labels.values()):
                 nnunet._refuse("labels", "defines regions")
@@ -164,7 +183,7 @@ class CaseStore:
                 bad = sorted(int(v) for v in np.unique(seg) if v < 0 or v >= self.n_heads)
                 raise ValueError(f"CaseStore: case {i}: labels {bad[:5]} outside [0, {self.n_heads})")
             raw = nnunet.normalize(img.cpu().to(torch.float32), self.schemes).numpy()
-            coef = spline_coefficients(raw).astype(np.float32)
+            coef = spline_coefficients(raw).astype(np.float32) if prefilter == "host" else raw
             row = self.table[i]
             row["H"], row["W"], row["stride"], row["label_stride"] = H, W, W, W
             for key, arr in (("coef_off", coef), ("raw_off", raw), ("label_off", seg.astype(np.uint8))):
@@ -177,6 +196,9 @@ class CaseStore:
         for off, arr in parts:
             host[off:off + arr.size] = arr
         self.arena = torch.from_numpy(host).to(self.device)
+        if prefilter == "device":
+            for i in range(len(cases)):
+                spline_prefilter_(self.coefficients(i))
         self.cases_dev = torch.from_numpy(self.table.view(np.uint8).reshape(-1).copy()).to(self.device)
 
     def __len__(self):
@@ -246,9 +268,10 @@ def draw_crop(rng: np.random.Generator, store: CaseStore, sample_idx: int, batch
 
 
 def draw_sample(rng: np.random.Generator, store: CaseStore, sample_idx: int, batch_size: int, patch_size: Sequence[int], train: bool = True,
-                oversample: float = OVERSAMPLE_FOREGROUND):
+                oversample: float = OVERSAMPLE_FOREGROUND, lowres: bool = False):
     """Every random decision of one sample, in the module docstring's order: (a SAMPLE_DTYPE record, [C] CHAN_DTYPE records, `draw_crop`'s dict).
-    The same numbers are drawn with `train=False`; they are then not used."""
+    The same numbers are drawn with `train=False`; they are then not used.  `lowres`: step 7, the low-resolution simulation's 1 + 2 C numbers, after
+    the others; without it nothing more is drawn and `lowres_zoom` stays 0."""
     h, w = int(patch_size[0]), int(patch_size[1])
     Cc = store.channels
     loader_patch = initial_patch_size((h, w)) if train else (h, w)
@@ -268,6 +291,8 @@ def draw_sample(rng: np.random.Generator, store: CaseStore, sample_idx: int, bat
     s["philox_offset"] = int(rng.integers(0, 1 << 62))
     gates = rng.random(5)                # blur, brightness, contrast, inverted gamma, gamma: one gate per sample
     per_channel = rng.random((Cc, 12))   # per channel: blur (coin, sigma), brightness, contrast (coin, low, high), gamma on -x (3), gamma (3)
+    if lowres:
+        lowres_gate, lowres_u = rng.random(1)[0], rng.random((Cc, 2))   # the sample's gate; per channel: coin, zoom
     if not train:
         return s, chans, crop
     s["noise_sigma"] = NOISE_SIGMA[0] + noise_u * (NOISE_SIGMA[1] - NOISE_SIGMA[0]) if noise_gate < P_NOISE else 0.0
@@ -283,17 +308,20 @@ def draw_sample(rng: np.random.Generator, store: CaseStore, sample_idx: int, bat
             ch["gamma_inverted"] = _two_sided(v[6], v[7], v[8], GAMMA[0], 1.0, GAMMA[1])
         if gates[4] < P_GAMMA:
             ch["gamma"] = _two_sided(v[9], v[10], v[11], GAMMA[0], 1.0, GAMMA[1])
+        if lowres and lowres_gate < P_LOWRES and lowres_u[c, 0] < P_LOWRES_PER_CHANNEL:
+            ch["lowres_zoom"] = LOWRES_ZOOM[0] + lowres_u[c, 1] * (LOWRES_ZOOM[1] - LOWRES_ZOOM[0])
     return s, chans, crop
 
 
 def draw_batch(rng: np.random.Generator, store: CaseStore, batch_size: int, patch_size: Sequence[int], train: bool = True,
-               oversample: float = OVERSAMPLE_FOREGROUND):
+               oversample: float = OVERSAMPLE_FOREGROUND, lowres: bool = False):
     """The random decisions of one batch, sample after sample (`draw_sample`): (samples [B] of SAMPLE_DTYPE, channels [B, C] of CHAN_DTYPE).
-    `train=False`: no augmentation, the loader's patch is the final patch (need_to_pad = 0), every sample an exact crop."""
+    `train=False`: no augmentation, the loader's patch is the final patch (need_to_pad = 0), every sample an exact crop.  `lowres`: also draw the
+    low-resolution simulation (`draw_sample`'s step 7)."""
     samples = np.zeros(batch_size, SAMPLE_DTYPE)
     chans = np.zeros((batch_size, store.channels), CHAN_DTYPE)
     for b in range(batch_size):
-        samples[b], chans[b], _ = draw_sample(rng, store, b, batch_size, patch_size, train, oversample)
+        samples[b], chans[b], _ = draw_sample(rng, store, b, batch_size, patch_size, train, oversample, lowres)
     return samples, chans
 
 
@@ -370,9 +398,10 @@ def sample_patches(store: CaseStore, samples_dev: torch.Tensor, batch_size: int,
 
 
 def augment_intensity_(data: torch.Tensor, samples_dev: torch.Tensor, chans_dev: torch.Tensor, seed: int = 0, normal: Optional[torch.Tensor] = None,
-                       workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       workspace: Optional[torch.Tensor] = None, lowres: bool = False) -> torch.Tensor:
     """ldiff_op_seg_intensity in place on `data` [B, C, h, w] float32 (contiguous), on the current stream.  `normal`: the N(0, 1) draws to use, same shape,
-    instead of the Philox stream keyed by (seed, each sample's offset)."""
+    instead of the Philox stream keyed by (seed, each sample's offset).  `lowres`: ldiff_op_seg_intensity_lr instead, which reads `lowres_zoom` and
+    takes the larger workspace of ldiff_op_seg_intensity_lr_ws_bytes."""
     _lib.require_gpu()
     if data.dim() != 4 or data.dtype != torch.float32 or not data.is_contiguous() or not data.is_cuda:
         raise ValueError("augment_intensity_: data must be a contiguous float32 [B, C, h, w] device tensor")
@@ -382,40 +411,65 @@ def augment_intensity_(data: torch.Tensor, samples_dev: torch.Tensor, chans_dev:
     if normal is not None and (normal.shape != data.shape or normal.dtype != torch.float32 or not normal.is_contiguous() or normal.device != data.device):
         raise ValueError("augment_intensity_: normal must match data")
     lib = _lib.load()
-    need = int(lib.ldiff_op_seg_intensity_ws_bytes(B, Cc, h, w))
+    ws_bytes, op = (lib.ldiff_op_seg_intensity_lr_ws_bytes, lib.ldiff_op_seg_intensity_lr) if lowres else (lib.ldiff_op_seg_intensity_ws_bytes, lib.ldiff_op_seg_intensity)
+    need = int(ws_bytes(B, Cc, h, w))
     if workspace is None or workspace.numel() * workspace.element_size() < need:
         workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=data.device)
     with torch.cuda.device(data.device):
-        _lib.check(lib.ldiff_op_seg_intensity(_lib.ptr(data), _lib.ptr(samples_dev), _lib.ptr(chans_dev), B, Cc, h, w, _lib.ptr(normal), int(seed) & (2 ** 64 - 1),
-                                              _lib.ptr(workspace), workspace.numel() * workspace.element_size(), _lib.stream_ptr()))
+        _lib.check(op(_lib.ptr(data), _lib.ptr(samples_dev), _lib.ptr(chans_dev), B, Cc, h, w, _lib.ptr(normal), int(seed) & (2 ** 64 - 1),
+                      _lib.ptr(workspace), workspace.numel() * workspace.element_size(), _lib.stream_ptr()))
     return data
+
+
+def spline_prefilter_(planes: torch.Tensor) -> torch.Tensor:
+    """ldiff_op_spline_prefilter in place on `planes` [..., H, W] float32 on the device, on the current stream: scipy.ndimage.spline_filter(order=3,
+    mode='mirror') of every [H, W] plane, what `spline_coefficients` is in float64.  The last axis must be dense and the planes evenly spaced, a row
+    stride apart per row (a contiguous tensor, or one sliced along W)."""
+    _lib.require_gpu()
+    if planes.dim() < 2 or planes.dtype != torch.float32 or not planes.is_cuda:
+        raise ValueError("spline_prefilter_: planes must be a float32 [..., H, W] device tensor")
+    H, W = int(planes.shape[-2]), int(planes.shape[-1])
+    stride = int(planes.stride(-2)) if H > 1 else W
+    n_planes = int(planes.numel() // max(H * W, 1))
+    dense = planes.stride(-1) == 1 or W == 1
+    step, size = H * stride, 1
+    for d in range(planes.dim() - 3, -1, -1):   # the leading axes must walk the planes in steps of H * stride
+        dense = dense and (planes.shape[d] == 1 or planes.stride(d) == step * size)
+        size *= int(planes.shape[d])
+    if not dense or planes.numel() == 0:
+        raise ValueError(f"spline_prefilter_: planes of shape {tuple(planes.shape)} and strides {tuple(planes.stride())} are not evenly spaced rows and planes")
+    with torch.cuda.device(planes.device):
+        _lib.check(_lib.load().ldiff_op_spline_prefilter(_lib.ptr(planes), n_planes, H, W, stride, _lib.stream_ptr()))
+    return planes
 
 
 class PatchLoader:
     """nnUNetDataLoader2D + the training transforms as an endless iterator of batches on the store's device:
     {"data": [B, C, h, w] float32, "target": [n_scales tensors [B, 1, h >> k, w >> k] uint8]}, highest resolution first -- what
     `Trainer.train_step`, `validation_step` and `run_training` take.  `train=False` is the validation loader: exact crops, no augmentation.
-    The same seed yields the same batches."""
+    The same seed yields the same batches.  `lowres=True` draws and applies the low-resolution simulation too: nnU-Net's whole chain."""
 
     def __init__(self, store: CaseStore, patch_size: Sequence[int], batch_size: int, n_scales: int, seed: int, train: bool = True,
-                 oversample: float = OVERSAMPLE_FOREGROUND):
+                 oversample: float = OVERSAMPLE_FOREGROUND, lowres: bool = False):
         if store.arena.device.type != "cuda":
             raise ValueError("PatchLoader: the store must live on a GPU")
         self.shapes = _scale_shapes(patch_size, n_scales)
         self.store, self.patch_size, self.batch_size, self.n_scales = store, (int(patch_size[0]), int(patch_size[1])), int(batch_size), int(n_scales)
-        self.train, self.oversample, self.seed = bool(train), float(oversample), int(seed)
+        self.train, self.oversample, self.seed, self.lowres = bool(train), float(oversample), int(seed), bool(lowres)
         self.rng = np.random.default_rng(self.seed)
-        need = int(_lib.load().ldiff_op_seg_intensity_ws_bytes(self.batch_size, store.channels, *self.patch_size))
+        lib = _lib.load()
+        ws_bytes = lib.ldiff_op_seg_intensity_lr_ws_bytes if self.lowres else lib.ldiff_op_seg_intensity_ws_bytes
+        need = int(ws_bytes(self.batch_size, store.channels, *self.patch_size))
         self._ws = torch.empty(max(need, 16), dtype=torch.uint8, device=store.arena.device) if self.train else None
 
     def __iter__(self):
         return self
 
     def __next__(self) -> dict:
-        samples, chans = draw_batch(self.rng, self.store, self.batch_size, self.patch_size, self.train, self.oversample)
+        samples, chans = draw_batch(self.rng, self.store, self.batch_size, self.patch_size, self.train, self.oversample, self.lowres)
         with torch.cuda.device(self.store.arena.device):
             s_dev, c_dev = upload_tables(samples, chans, self.store.arena.device)
             data, targets = sample_patches(self.store, s_dev, self.batch_size, self.patch_size, self.n_scales)
             if self.train:
-                augment_intensity_(data, s_dev, c_dev, self.seed, workspace=self._ws)
+                augment_intensity_(data, s_dev, c_dev, self.seed, workspace=self._ws, lowres=self.lowres)
         return {"data": data, "target": targets}

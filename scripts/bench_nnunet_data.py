@@ -4,8 +4,12 @@ cases of 1024^2.  Device time by events around the two launches (ldiff_op_seg_sa
     expected  the tables draw_batch produces (nnU-Net's probabilities)
     host      wall time of a whole PatchLoader batch (draws, table upload, launches) without waiting for the device
 and, for scale, the same pipeline in numpy / scipy on 16 threads, one sample per task (what nnU-Net's worker pool does).
+--lowres adds, from the same process, the two device rows with the low-resolution simulation (ldiff_op_seg_intensity_lr):
+    worst_lowres     the worst case above with every plane's step on, zooms spread over 0.5 ... 1
+    expected_lowres  the tables draw_batch(lowres=True) produces (25 % of the samples, half of their channels)
+and the loader rows with PatchLoader(lowres=True).  The numpy pipeline does not run the step.
 
-    python scripts/bench_nnunet_data.py [--batches 20] [--warmup 3] [--no-numpy]
+    python scripts/bench_nnunet_data.py [--batches 20] [--warmup 3] [--no-numpy] [--lowres]
 """
 import argparse
 import json
@@ -19,6 +23,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from ldiffusion_amd import _lib  # noqa: E402
 from ldiffusion_amd import nnunet_data as nd  # noqa: E402
 
 B, C, PATCH, SCALES, CASE, N_HEADS, N_CASES = 12, 3, (512, 512), 7, 1024, 7, 8
@@ -35,8 +40,10 @@ def make_store(device):
     return nd.CaseStore(cases, ["ZScoreNormalization"] * C, N_HEADS, device)
 
 
-def worst_tables(rng, store):
+def worst_tables(rng, store, lowres=False):
     s, ch = nd.draw_batch(rng, store, B, PATCH)
+    if lowres:
+        ch["lowres_zoom"] = np.linspace(0.5, 0.99, B * C, dtype=np.float32).reshape(B, C)
     loader_patch = nd.initial_patch_size(PATCH)
     for b in range(B):
         s[b]["m"], s[b]["copy"] = nd.spatial_matrix(PATCH, loader_patch, (200, 180), 0.3 + 0.2 * b, 0.7 + 0.05 * b, (b % 2 == 0, b % 3 == 0), True)
@@ -45,7 +52,7 @@ def worst_tables(rng, store):
     return s, ch
 
 
-def device_ms(store, tables, warmup):
+def device_ms(store, tables, warmup, lowres=False):
     ws = None
     times = []
     for i, (s, ch) in enumerate(tables):
@@ -56,8 +63,9 @@ def device_ms(store, tables, warmup):
         data, _ = nd.sample_patches(store, s_dev, B, PATCH, SCALES)
         e[1].record()
         if ws is None:
-            ws = torch.empty(data.numel() * 4, dtype=torch.uint8, device=data.device)
-        nd.augment_intensity_(data, s_dev, c_dev, 0, workspace=ws)
+            need = int(_lib.load().ldiff_op_seg_intensity_lr_ws_bytes(B, C, *PATCH)) if lowres else data.numel() * 4
+            ws = torch.empty(need, dtype=torch.uint8, device=data.device)
+        nd.augment_intensity_(data, s_dev, c_dev, 0, workspace=ws, lowres=lowres)
         e[2].record()
         torch.cuda.synchronize()
         if i >= warmup:
@@ -127,6 +135,7 @@ def main():
     ap.add_argument("--batches", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-numpy", action="store_true")
+    ap.add_argument("--lowres", action="store_true", help="also time the chain with the low-resolution simulation")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     t0 = time.perf_counter()
@@ -139,7 +148,10 @@ def main():
     expected = [nd.draw_batch(rng, store, B, PATCH) for _ in range(n)]
     out["worst"] = device_ms(store, worst, args.warmup)
     out["expected"] = device_ms(store, expected, args.warmup)
-    loader = nd.PatchLoader(store, PATCH, B, SCALES, seed=2)
+    if args.lowres:
+        out["worst_lowres"] = device_ms(store, [worst_tables(rng, store, True) for _ in range(n)], args.warmup, True)
+        out["expected_lowres"] = device_ms(store, [nd.draw_batch(rng, store, B, PATCH, lowres=True) for _ in range(n)], args.warmup, True)
+    loader = nd.PatchLoader(store, PATCH, B, SCALES, seed=2, lowres=args.lowres)
     for _ in range(args.warmup):
         next(loader)
     torch.cuda.synchronize()
