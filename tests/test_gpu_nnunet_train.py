@@ -51,7 +51,7 @@ def run_in_train(lib, x, dy, gm, bt, eps, slope):
     return tuple(t.double().cpu() for t in (y, mean, rstd, dx, dg, db))
 
 
-IN_SHAPES = [(2, 32, 4, 4), (1, 16, 24, 40), (2, 64, 64, 64), (3, 256, 8, 8)]
+IN_SHAPES = [(2, 32, 4, 4), (1, 16, 24, 40), (2, 64, 64, 64), (3, 256, 8, 8), (2, 512, 2, 2), (2, 512, 8, 8)]   # the last two: the bottleneck norms of the `2d` plan
 
 
 @pytest.mark.parametrize("slope", [0.01, 1.0])
