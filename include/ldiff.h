@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define LDIFF_VERSION 208 /* 0.2.0.8: + ldiff_op_seg_intensity_lr (the intensity chain with nnU-Net's low-resolution simulation between contrast and the gammas), ldiff_op_spline_prefilter (cubic B-spline prefilter on the device, one workgroup per plane); 0.2.0.7: + ldiff_op_conv_wgrad (direct MFMA weight gradient of the narrow convs over the pixel index, no im2col), ldiff_op_colsum_slabs (slab-reduced bias gradient), both with fixed-order partials; 0.2.0.6: + ldiff_op_seg_sample (patches, labels and deep-supervision targets of a training batch from cases resident on the device), ldiff_op_seg_intensity (nnU-Net's intensity augmentations, one workgroup per plane); 0.2.0.5: + ldiff_unet_set_plan_batch / ldiff_vae_set_plan_batch / ldiff_controlnet_set_plan_batch (batch-invariant mode: every launch planned for a nominal batch), ldiff_op_conv_pb, ldiff_op_attention_pb, ldiff_op_gn_stats_pb; 0.2.0.4: + ldiff_op_in_train_fwd / _bwd (InstanceNorm + LeakyReLU with saved statistics), ldiff_op_dice_ce (nnU-Net deep-supervision loss of one scale, value and gradient), ldiff_op_sgd_nesterov_multi; 0.2.0.3: + ldiff_confusion (per-image confusion matrices of masks or logits against labels, accumulated on the device), ldiff_seg_metrics (host: Dice / IoU / pixel accuracy / frequency-weighted IoU from one matrix); 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
+#define LDIFF_VERSION 209 /* 0.2.0.9: + ldiff_op_case_bbox / _stats / _counts / _apply / _rank_to_coord (plan and preprocess of the tissue head's training cases on the device: non-zero box, crop statistics, label counts per row, normalise into the arena, rank -> pixel); 0.2.0.8: + ldiff_op_seg_intensity_lr (the intensity chain with nnU-Net's low-resolution simulation between contrast and the gammas), ldiff_op_spline_prefilter (cubic B-spline prefilter on the device, one workgroup per plane); 0.2.0.7: + ldiff_op_conv_wgrad (direct MFMA weight gradient of the narrow convs over the pixel index, no im2col), ldiff_op_colsum_slabs (slab-reduced bias gradient), both with fixed-order partials; 0.2.0.6: + ldiff_op_seg_sample (patches, labels and deep-supervision targets of a training batch from cases resident on the device), ldiff_op_seg_intensity (nnU-Net's intensity augmentations, one workgroup per plane); 0.2.0.5: + ldiff_unet_set_plan_batch / ldiff_vae_set_plan_batch / ldiff_controlnet_set_plan_batch (batch-invariant mode: every launch planned for a nominal batch), ldiff_op_conv_pb, ldiff_op_attention_pb, ldiff_op_gn_stats_pb; 0.2.0.4: + ldiff_op_in_train_fwd / _bwd (InstanceNorm + LeakyReLU with saved statistics), ldiff_op_dice_ce (nnU-Net deep-supervision loss of one scale, value and gradient), ldiff_op_sgd_nesterov_multi; 0.2.0.3: + ldiff_confusion (per-image confusion matrices of masks or logits against labels, accumulated on the device), ldiff_seg_metrics (host: Dice / IoU / pixel accuracy / frequency-weighted IoU from one matrix); 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
 #define LDIFF_MAX_BLOCKS 8
 
 typedef enum { LDIFF_OK = 0, LDIFF_ERR_INVALID = -1, LDIFF_ERR_RUNTIME = -2, LDIFF_ERR_STATE = -3, LDIFF_ERR_NONFINITE = -4 } ldiff_status;
@@ -729,6 +729,38 @@ int64_t ldiff_op_seg_intensity_lr_ws_bytes(int B, int C, int h, int w);
 int ldiff_op_seg_intensity_lr(void* data, const ldiff_seg_sample* samples, const ldiff_seg_chan* chans, int B, int C, int h, int w, const void* normal_or_null,
                               uint64_t seed, void* ws, int64_t ws_bytes, void* stream);
 int ldiff_op_spline_prefilter(void* planes_f32, int n_planes, int H, int W, int stride, void* stream);
+
+/* Tissue head, plan and preprocess: what DefaultPreprocessor.run_case_npy and DatasetFingerprintExtractor.analyze_case do per training case, for a case that
+ * is on the device: img, C planes [H, W] of uint8 (dtype 0) or float32 (dtype 1), rows row_stride and planes plane_stride ELEMENTS apart; label_u8 [H, W]
+ * uint8, rows label_stride bytes apart.  C <= 16, H, W <= 32768.  A box is (y0, y1, x0, x1), ends exclusive, non-empty and inside the case; the host
+ * reads it back from ldiff_op_case_bbox and hands it to the other four.  No kernel reads or writes outside the case, the box or the stated outputs.
+ * ldiff_op_case_bbox: box (device, int32 [4]) of the pixels where any channel is non-zero (NaN counts as non-zero); the full extent for an all-zero image:
+ *   crop_to_nonzero's box (cropping.py:24-49; filling the mask's holes never moves it).
+ * ldiff_op_case_stats: stats (device, C records of 32 bytes): the sum and the sum of squares of the channel over the box -- uint64 for uint8 input (exact),
+ *   float64 for float32 input (per-workgroup partial sums over fixed slices of rows, added in index order: no float atomics, bit-identical from run to
+ *   run) -- then min and max as float64.  ws: ldiff_op_case_stats_ws_bytes(C) bytes, 8-byte aligned.
+ * ldiff_op_case_counts: row_counts uint32 [rows, n_heads + 1]: per row of the box the pixels of class 0 .. n_heads - 1, then those with a label >= n_heads;
+ *   row_prefix uint32 [n_heads + 1, rows + 1]: per selector -- class c, or (index n_heads) `label > 0` -- the selected pixels above each row, the last
+ *   entry the total; totals uint32 [n_heads + 2]: per class, `label > 0`, labels >= n_heads.  n_heads <= 32.  Exact.
+ * ldiff_op_case_apply: the cropped planes as float32 (x - sub[c]) / div[c] (sub, div: HOST arrays of C floats; one subtraction and one correctly rounded
+ *   division) to arena + row->raw_off [C, h, row->stride], also to row->coef_off when write_coef != 0 (ldiff_op_spline_prefilter then runs in place),
+ *   and the cropped labels to row->label_off [h, row->label_stride].  row: a HOST ldiff_seg_case with H, W the box's extent; refused when a span leaves
+ *   the arena or a float offset is no multiple of 4.
+ * ldiff_op_case_rank_to_coord: coords int32 [n, 2] = (row, column) inside the box of the rank-th selected pixel in row-major order, numpy's
+ *   argwhere(selection)[rank]; selector = a class, or -1 for `label > 0`; row_prefix: that selector's uint32 [rows + 1] of ldiff_op_case_counts; ranks int64
+ *   [n], any order, repeats allowed.  values_or_null [n, C] of the image's dtype: the pixel's C channels.  A rank outside [0, total) yields (-1, -1) and
+ *   zeros. */
+int ldiff_op_case_bbox(const void* img, int dtype, int C, int H, int W, int64_t row_stride, int64_t plane_stride, int32_t* box, void* stream);
+int64_t ldiff_op_case_stats_ws_bytes(int C);
+int ldiff_op_case_stats(const void* img, int dtype, int C, int H, int W, int64_t row_stride, int64_t plane_stride, int y0, int y1, int x0, int x1, void* stats, void* ws,
+                        int64_t ws_bytes, void* stream);
+int ldiff_op_case_counts(const void* label_u8, int H, int W, int64_t label_stride, int y0, int y1, int x0, int x1, int n_heads, uint32_t* row_counts, uint32_t* row_prefix,
+                         uint32_t* totals, void* stream);
+int ldiff_op_case_apply(const void* img, int dtype, int C, int H, int W, int64_t row_stride, int64_t plane_stride, const void* label_u8, int64_t label_stride, int y0, int y1,
+                        int x0, int x1, const float* sub, const float* div, void* arena, int64_t arena_bytes, const ldiff_seg_case* row, int write_coef, void* stream);
+int ldiff_op_case_rank_to_coord(const void* label_u8, int H, int W, int64_t label_stride, int y0, int y1, int x0, int x1, int selector, const uint32_t* row_prefix,
+                                const int64_t* ranks, int64_t n, int32_t* coords, const void* img_or_null, int dtype, int C, int64_t row_stride, int64_t plane_stride,
+                                void* values_or_null, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Live measurement for bench.py's roofline line: when enabled, every conv/linear, attention and

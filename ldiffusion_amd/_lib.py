@@ -210,6 +210,12 @@ SIGNATURES = {
     "ldiff_op_seg_intensity_lr_ws_bytes": (I64, [I, I, I, I]),
     "ldiff_op_seg_intensity_lr": (I, [P, P, P, I, I, I, I, P, U64, P, I64, P]),
     "ldiff_op_spline_prefilter": (I, [P, I, I, I, I, P]),
+    "ldiff_op_case_bbox": (I, [P, I, I, I, I, I64, I64, P, P]),
+    "ldiff_op_case_stats_ws_bytes": (I64, [I]),
+    "ldiff_op_case_stats": (I, [P, I, I, I, I, I64, I64, I, I, I, I, P, P, I64, P]),
+    "ldiff_op_case_counts": (I, [P, I, I, I64, I, I, I, I, I, P, P, P, P]),
+    "ldiff_op_case_apply": (I, [P, I, I, I, I, I64, I64, P, I64, I, I, I, I, C.POINTER(F), C.POINTER(F), P, I64, C.POINTER(SegCase), I, P]),
+    "ldiff_op_case_rank_to_coord": (I, [P, I, I, I64, I, I, I, I, I, P, P, I64, P, P, I, I, I64, I64, P, P]),
     "ldiff_stream_create_cu_share": (I, [I, I, P]),
     "ldiff_stream_destroy": (I, [P]),
     "ldiff_vae_set_side_cu_share": (I, [P, I, I]),

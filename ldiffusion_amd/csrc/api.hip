@@ -1143,6 +1143,39 @@ int ldiff_op_spline_prefilter(void* planes_f32, int n_planes, int H, int W, int 
   launch_spline_prefilter((float*)planes_f32, n_planes, H, W, stride, (hipStream_t)stream);
   API_END
 }
+// ---- plan and preprocess of the tissue head's cases (kernels_segprep.hip) ----
+int ldiff_op_case_bbox(const void* img, int dtype, int Cc, int H, int W, int64_t row_stride, int64_t plane_stride, int32_t* box, void* stream) {
+  API_BEGIN
+  launch_case_bbox(img, dtype, Cc, H, W, row_stride, plane_stride, box, (hipStream_t)stream);
+  API_END
+}
+int64_t ldiff_op_case_stats_ws_bytes(int Cc) { return case_stats_ws_bytes(Cc); }
+int ldiff_op_case_stats(const void* img, int dtype, int Cc, int H, int W, int64_t row_stride, int64_t plane_stride, int y0, int y1, int x0, int x1, void* stats, void* ws,
+                        int64_t ws_bytes, void* stream) {
+  API_BEGIN
+  launch_case_stats(img, dtype, Cc, H, W, row_stride, plane_stride, y0, y1, x0, x1, stats, ws, ws_bytes, (hipStream_t)stream);
+  API_END
+}
+int ldiff_op_case_counts(const void* label_u8, int H, int W, int64_t label_stride, int y0, int y1, int x0, int x1, int n_heads, uint32_t* row_counts, uint32_t* row_prefix,
+                         uint32_t* totals, void* stream) {
+  API_BEGIN
+  launch_case_counts(label_u8, H, W, label_stride, y0, y1, x0, x1, n_heads, row_counts, row_prefix, totals, (hipStream_t)stream);
+  API_END
+}
+int ldiff_op_case_apply(const void* img, int dtype, int Cc, int H, int W, int64_t row_stride, int64_t plane_stride, const void* label_u8, int64_t label_stride, int y0, int y1,
+                        int x0, int x1, const float* sub, const float* div, void* arena, int64_t arena_bytes, const ldiff_seg_case* row, int write_coef, void* stream) {
+  API_BEGIN
+  launch_case_apply(img, dtype, Cc, H, W, row_stride, plane_stride, label_u8, label_stride, y0, y1, x0, x1, sub, div, arena, arena_bytes, row, write_coef, (hipStream_t)stream);
+  API_END
+}
+int ldiff_op_case_rank_to_coord(const void* label_u8, int H, int W, int64_t label_stride, int y0, int y1, int x0, int x1, int selector, const uint32_t* row_prefix,
+                                const int64_t* ranks, int64_t n, int32_t* coords, const void* img_or_null, int dtype, int Cc, int64_t row_stride, int64_t plane_stride,
+                                void* values_or_null, void* stream) {
+  API_BEGIN
+  launch_case_rank_to_coord(label_u8, H, W, label_stride, y0, y1, x0, x1, selector, row_prefix, (const long long*)ranks, n, coords, img_or_null, dtype, Cc, row_stride,
+                            plane_stride, values_or_null, (hipStream_t)stream);
+  API_END
+}
 int ldiff_op_geglu(const void* x, void* y, int64_t M, int C4, void* stream) {
   API_BEGIN
   LDIFF_CHECK(x && y, LDIFF_ERR_INVALID, "op_geglu: null argument");

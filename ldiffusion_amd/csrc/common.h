@@ -356,6 +356,18 @@ void launch_seg_intensity(float* data, const ldiff_seg_sample* samples, const ld
 // ... with the low-resolution simulation between contrast and the gammas (lowres = true; its own workspace size), and its cubic B-spline prefilter alone
 long long seg_intensity_lr_ws_bytes(int B, int C, int h, int w);
 void launch_spline_prefilter(float* planes, int n_planes, int H, int W, int stride, hipStream_t s);
+// plan and preprocess of one case of the tissue head (kernels_segprep.hip): non-zero box, crop statistics, label counts, normalise into the arena, rank -> pixel
+void launch_case_bbox(const void* img, int dtype, int C, int H, int W, long long row_stride, long long plane_stride, int* box, hipStream_t s);
+long long case_stats_ws_bytes(int C);
+void launch_case_stats(const void* img, int dtype, int C, int H, int W, long long row_stride, long long plane_stride, int y0, int y1, int x0, int x1, void* stats,
+                       void* ws, long long ws_bytes, hipStream_t s);
+void launch_case_counts(const void* label, int H, int W, long long label_stride, int y0, int y1, int x0, int x1, int n_heads, unsigned* row_counts, unsigned* row_prefix,
+                        unsigned* totals, hipStream_t s);
+void launch_case_apply(const void* img, int dtype, int C, int H, int W, long long row_stride, long long plane_stride, const void* label, long long label_stride, int y0, int y1,
+                       int x0, int x1, const float* sub, const float* div, void* arena, long long arena_bytes, const ldiff_seg_case* row, int write_coef, hipStream_t s);
+void launch_case_rank_to_coord(const void* label, int H, int W, long long label_stride, int y0, int y1, int x0, int x1, int selector, const unsigned* row_prefix,
+                               const long long* ranks, long long n, int* coords, const void* img, int dtype, int C, long long row_stride, long long plane_stride, void* values,
+                               hipStream_t s);
 
 // Counter-based Philox4x32-10: four 32-bit words per (counter, key).  Used by the Laplace forward noise (kernels_elem.hip) and the augmentation noise
 // (kernels_segaug.hip).

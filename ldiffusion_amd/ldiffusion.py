@@ -2,7 +2,8 @@
 sampling path: same constructor and `inference(...)` signature (cell and tissue levels), same error for an invalid level.
 Training: `train_ldiffusion` (ldiffusion.py:121-295) runs on the HIP kernels, forward and backward (`ldiffusion_amd.train`,
 parity-tested against torch.autograd over the oracle), with the data loader injected; what differs from the reference (no ZeRO-3, optional
-VGG19 content term, fp16 operands) is listed in its docstring.  The segmentor stage of `train` trains the out-of-scope heads and raises.
+VGG19 content term, fp16 operands) is listed in its docstring.  The segmentor stage of `train` runs at the tissue level
+(`Segmentor.train_tissue_model_nnUNetv2`); at the cell level it raises.
 """
 from __future__ import annotations
 
@@ -159,11 +160,17 @@ class LDiffusionModel:
         return save_path
 
     def train(self, args, component="all", ldiffusion_weight=None, train_loader=None, val_loader=None, **_ignored):
-        """ldiffusion.py:297-315.  The PUMA dataset / dataloader (dataset.py, cv2) and the segmentation heads are outside this build: the
-        loaders are injected, `component="ldiffusion"` runs the L-Diffusion warm-up on the HIP kernels and returns the saved weight
-        directory; the segmentor stage raises."""
+        """ldiffusion.py:297-315.  The PUMA dataset / dataloader (dataset.py, cv2) is outside this build: the loaders are injected.
+        `component="ldiffusion"` runs the L-Diffusion warm-up on the HIP kernels and returns the saved weight directory.  The segmentor stage
+        ("segmentor", or after the warm-up with "all") at level "tissue" is `Segmentor.train_tissue_model_nnUNetv2(args.num_epochs - 10,
+        ldiffusion_weight, args.diffusion_path)` with the loaders' `dataset.image_dir` / `label_dir` lists (:306-311) and returns the trained-model
+        folder; loaders without such a dataset (plain lists of batches) need the four lists as keyword arguments `train_images`, `train_labels`,
+        `test_images`, `test_labels`.  `iterations_per_epoch`, `val_iterations` and `num_foreground_voxels` are handed on too.  At level "cell" it
+        raises NotImplementedError: the cell trainer is not built."""
         if component not in ("all", "ldiffusion", "segmentor"):
             raise ValueError(f"unknown component {component!r}")
+        segmentor_kwargs = {k: _ignored[k] for k in ("train_images", "train_labels", "test_images", "test_labels", "iterations_per_epoch", "val_iterations",
+                                                          "num_foreground_voxels") if k in _ignored}
         if component in ("all", "ldiffusion"):
             if train_loader is None:
                 raise RuntimeError("LDiffusionModel.train: the reference's dataset pipeline (load_data, dataset.py) is outside this build; pass train_loader=")
@@ -171,8 +178,19 @@ class LDiffusionModel:
                 print("Starting LDiffusion warming up...")
             ldiffusion_weight = self.train_ldiffusion(args, train_loader, val_loader)
         if component in ("all", "segmentor"):
-            raise NotImplementedError("segmentor training (train_cell_model / train_tissue_model_nnUNetv2, segmentor.py:163-299) trains the "
-                                      f"out-of-scope heads; the L-Diffusion weights are at {ldiffusion_weight!r}")
+            if self.level == "cell":
+                raise NotImplementedError("segmentor training at the cell level (train_cell_model, segmentor.py:243-299) trains the out-of-scope "
+                                          f"cell head; the L-Diffusion weights are at {ldiffusion_weight!r}")
+            if self.level != "tissue":
+                raise ValueError("Invalid level specified. Choose 'tissue' or 'cell'.")
+            if self._is_main_process():
+                print("Starting Segmentor training...")
+            segmentor = Segmentor(train_loader, val_loader, self.level, args.num_classes)
+            if "train_images" not in segmentor_kwargs and hasattr(train_loader, "dataset") and hasattr(val_loader, "dataset"):
+                # ldiffusion.py:306-311 hands the loaders on; their datasets hold the file lists
+                segmentor_kwargs.update(train_images=train_loader.dataset.image_dir, train_labels=train_loader.dataset.label_dir,
+                                        test_images=val_loader.dataset.image_dir, test_labels=val_loader.dataset.label_dir)
+            return segmentor.train_tissue_model_nnUNetv2(args.num_epochs - 10, ldiffusion_weight, args.diffusion_path, **segmentor_kwargs)
         return ldiffusion_weight
 
     def inference(self, image_path, ldiffusion_weight, segmentor_weight, num_classes, head=None, predictor=None, output_path=None,

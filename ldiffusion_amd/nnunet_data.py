@@ -1,7 +1,9 @@
 """Training batches for the nnU-Net tissue head, made on the device: what `nnUNetDataLoader2D` and the transforms of
 `nnUNetTrainer.get_training_transforms` (nnUNetTrainer.py:674-765) do on a pool of CPU workers, for cases that stay in device memory.
 
-    CaseStore      preprocessed cases in ONE device arena: normalised image, its cubic B-spline coefficients, labels, foreground locations
+    CaseStore      preprocessed cases in ONE device arena: normalised image, its cubic B-spline coefficients, labels, foreground locations; built on the
+                   host, or with `build="device"` by the case kernels below (crop to non-zero, statistics, normalisation, foreground locations)
+    case_bbox, case_stats, case_counts, case_rank_to_coord   DefaultPreprocessor.run_case_npy's per-case scans on the device (ldiff_op_case_*)
     draw_batch     every random decision of a batch, on the host, as two parameter tables (numpy structured arrays = the C structs of include/ldiff.h)
     PatchLoader    iterator of {"data": [B, C, h, w] float32, "target": [n_scales x [B, 1, h_k, w_k] uint8]} -- what nnunet_train.Trainer takes.
                    Per batch: one pinned upload of the tables and two launches (ldiff_op_seg_sample, ldiff_op_seg_intensity); nothing synchronises.
@@ -145,13 +147,25 @@ class CaseStore:
     `device="cpu"` keeps the arena on the host: enough for `draw_batch`, not for a PatchLoader.
     `prefilter`: "host" (the default) forms the coefficients by `spline_coefficients` in float64 and rounds them once; "device" uploads the normalised
     image in their place and filters it there (`spline_prefilter_`), so the coefficients carry the float32 filter's own error, a few 1e-6 of the
-    image's magnitude (tests/nnunet_lowres_ref.py bounds it), and building the store needs the GPU."""
+    image's magnitude (tests/nnunet_lowres_ref.py bounds it), and building the store needs the GPU.
+    `build`: "host" (the default) normalises each case on the CPU and finds the foreground with np.argwhere; it does NOT crop to non-zero unless
+    `crop=True` (default False: the case is stored whole, as it always was).  "device" takes the same pairs on the device or the host and runs the case
+    kernels (ldiff_op_case_*): it CROPS TO NON-ZERO as DefaultPreprocessor.run_case_npy does, forms mean / std / min / max on the host in float64 from the
+    kernels' exact sums, normalises into the arena, and fills `class_locations` with what `sample_foreground_locations` returns -- the RandomState is
+    walked on the host over the per-class counts, the chosen ranks become pixels on the device.  Pixels that crop_to_nonzero would relabel -1 (background
+    outside the non-zero mask) stay 0 in both builds: nnU-Net's RemoveLabelTransform(-1, 0) makes them 0 before the loss.  `boxes[i]`: the crop box
+    (y0, y1, x0, x1) of case i in its source image (the full extent without a crop)."""
 
-    def __init__(self, cases, schemes: Sequence[str], n_heads: int, device="cuda:0", labels: Optional[dict] = None, prefilter: str = "host"):
+    def __init__(self, cases, schemes: Sequence[str], n_heads: int, device="cuda:0", labels: Optional[dict] = None, prefilter: str = "host",
+                 build: str = "host", crop: bool = False):
         if prefilter not in ("host", "device"):
             raise ValueError(f"CaseStore: prefilter must be 'host' or 'device', got {prefilter!r}")
         if prefilter == "device" and torch.device(device).type != "cuda":
             raise ValueError("CaseStore: prefilter='device' needs the store on a GPU")
+        if build not in ("host", "device"):
+            raise ValueError(f"CaseStore: build must be 'host' or 'device', got {build!r}")
+        if build == "device" and torch.device(device).type != "cuda":
+            raise ValueError("CaseStore: build='device' needs the store on a GPU")
         if labels is not None:
             if any(isinstance(v, (list, tuple)) for v in labels.values()):
                 nnunet._refuse("labels", "defines regions")
@@ -166,8 +180,12 @@ class CaseStore:
         self.device = torch.device(device)
         self.table = np.zeros(len(cases), CASE_DTYPE)
         self.class_locations: List[dict] = []
+        self.boxes: List[Tuple[int, int, int, int]] = []
         parts, size = [], 0
         self.channels = None
+        if build == "device":
+            self._build_on_device(cases, prefilter)
+            return
         for i, (img, seg) in enumerate(cases):
             img, seg = torch.as_tensor(img), np.asarray(torch.as_tensor(seg).cpu())
             if img.dim() != 3 or img.dtype not in (torch.uint8, torch.float32):
@@ -179,6 +197,11 @@ class CaseStore:
                 raise ValueError(f"CaseStore: case {i} has {Cc} channels; the store has {self.channels} and {len(self.schemes)} normalisation schemes")
             if seg.shape != (H, W) or seg.dtype.kind not in "iu":
                 raise ValueError(f"CaseStore: case {i}: the label map must be [{H}, {W}] of integers, got {seg.shape} of {seg.dtype}")
+            box = nnunet.nonzero_bbox(img) if crop else (0, H, 0, W)
+            self.boxes.append(box)
+            if crop:
+                img, seg = img[:, box[0]:box[1], box[2]:box[3]], seg[box[0]:box[1], box[2]:box[3]]
+                H, W = box[1] - box[0], box[3] - box[2]
             if seg.min() < 0 or seg.max() >= self.n_heads:
                 bad = sorted(int(v) for v in np.unique(seg) if v < 0 or v >= self.n_heads)
                 raise ValueError(f"CaseStore: case {i}: labels {bad[:5]} outside [0, {self.n_heads})")
@@ -200,6 +223,76 @@ class CaseStore:
             for i in range(len(cases)):
                 spline_prefilter_(self.coefficients(i))
         self.cases_dev = torch.from_numpy(self.table.view(np.uint8).reshape(-1).copy()).to(self.device)
+
+    def _build_on_device(self, cases, prefilter: str):
+        """build="device": the case kernels in three rounds with one synchronisation each -- boxes; statistics and label counts over the boxes; then the
+        arena is laid out, every case normalised into it and the sampled foreground ranks turned into pixels."""
+        dev, nh = self.device, self.n_heads
+        imgs, segs, given = [], [], []
+        for i, (img, seg) in enumerate(cases):
+            img, seg = torch.as_tensor(img), torch.as_tensor(seg)
+            if img.dim() != 3 or img.dtype not in (torch.uint8, torch.float32):
+                raise ValueError(f"CaseStore: case {i}: the image must be [C, H, W] uint8 or float32, got {tuple(img.shape)} of {img.dtype}")
+            Cc, H, W = (int(v) for v in img.shape)
+            if self.channels is None:
+                self.channels = Cc
+            if Cc != self.channels or Cc != len(self.schemes):
+                raise ValueError(f"CaseStore: case {i} has {Cc} channels; the store has {self.channels} and {len(self.schemes)} normalisation schemes")
+            if tuple(seg.shape) != (H, W) or seg.dtype.is_floating_point or seg.dtype in (torch.bool, torch.complex64, torch.complex128):
+                raise ValueError(f"CaseStore: case {i}: the label map must be [{H}, {W}] of integers, got {tuple(seg.shape)} of {seg.dtype}")
+            img, seg = img.to(dev), seg.to(dev)
+            given.append(seg)
+            if seg.dtype != torch.uint8:   # any other integer type: what does not fit a byte becomes 255, which no head count reaches
+                seg = torch.where((seg < 0) | (seg > 255), torch.full_like(seg, 255), seg).to(torch.uint8)
+            imgs.append(img if img.stride(-1) == 1 else img.contiguous())
+            segs.append(seg if seg.stride(-1) == 1 else seg.contiguous())
+        n = len(imgs)
+        with torch.cuda.device(dev):
+            boxes_dev = torch.empty((n, 4), dtype=torch.int32, device=dev)
+            for i in range(n):
+                _launch_case_bbox(imgs[i], boxes_dev[i])
+            self.boxes = [tuple(int(v) for v in b) for b in boxes_dev.cpu().numpy()]
+            stats_dev = torch.empty((n, self.channels, 4), dtype=torch.int64, device=dev)
+            totals_dev = torch.empty((n, nh + 2), dtype=torch.int32, device=dev)
+            ws = torch.empty(max(int(_lib.load().ldiff_op_case_stats_ws_bytes(self.channels)), 16), dtype=torch.uint8, device=dev)
+            prefixes = []
+            for i in range(n):
+                _launch_case_stats(imgs[i], self.boxes[i], stats_dev[i], ws)
+                prefixes.append(_launch_case_counts(segs[i], self.boxes[i], nh, totals_dev[i])[1])
+            stats, totals = stats_dev.cpu().numpy(), totals_dev.cpu().numpy().astype(np.int64)
+            size = 0
+            norm = []
+            for i in range(n):
+                if totals[i, nh + 1]:
+                    b = self.boxes[i]
+                    bad = sorted(int(v) for v in torch.unique(given[i][b[0]:b[1], b[2]:b[3]]).cpu() if v < 0 or v >= nh)   # the error path alone looks at values
+                    raise ValueError(f"CaseStore: case {i}: labels {bad[:5]} outside [0, {nh})")
+                h, w = self.boxes[i][1] - self.boxes[i][0], self.boxes[i][3] - self.boxes[i][2]
+                norm.append(normalization_scalars(stats[i], imgs[i].dtype, h * w, self.schemes))
+                row = self.table[i]
+                row["H"], row["W"], row["stride"], row["label_stride"] = h, w, w, w
+                for key, nbytes in (("coef_off", self.channels * h * w * 4), ("raw_off", self.channels * h * w * 4), ("label_off", h * w)):
+                    size = (size + 15) // 16 * 16
+                    row[key] = size
+                    size += nbytes
+            self.arena = torch.zeros((size + 15) // 16 * 16, dtype=torch.uint8, device=dev)
+            for i in range(n):
+                _launch_case_apply(imgs[i], segs[i], self.boxes[i], norm[i][0], norm[i][1], self.arena, self.table[i], prefilter == "device")
+                if prefilter == "device":
+                    spline_prefilter_(self.coefficients(i))
+                else:
+                    self.coefficients(i).copy_(torch.from_numpy(spline_coefficients(self.raw(i).cpu().numpy()).astype(np.float32)))
+            for i in range(n):   # sample_foreground_locations: ONE RandomState per case walked through the classes; only the counts are needed here
+                rndst, picked = np.random.RandomState(1234), {}
+                for c in range(1, nh):
+                    count = int(totals[i, c])
+                    if count == 0:
+                        picked[c] = []
+                        continue
+                    ranks = torch.from_numpy(rndst.choice(count, _target_num_samples(count), replace=False).astype(np.int64)).to(dev)
+                    picked[c] = _launch_case_rank(segs[i], self.boxes[i], c, prefixes[i][c], ranks, None)[0]
+                self.class_locations.append({c: (v if isinstance(v, list) else v.cpu().numpy().astype(np.int64)) for c, v in picked.items()})
+        self.cases_dev = torch.from_numpy(self.table.view(np.uint8).reshape(-1).copy()).to(dev)
 
     def __len__(self):
         return len(self.table)
@@ -441,6 +534,169 @@ def spline_prefilter_(planes: torch.Tensor) -> torch.Tensor:
     with torch.cuda.device(planes.device):
         _lib.check(_lib.load().ldiff_op_spline_prefilter(_lib.ptr(planes), n_planes, H, W, stride, _lib.stream_ptr()))
     return planes
+
+
+# ---- plan and preprocess of one case (kernels_segprep.hip) ---------------------------------------------------------------------------------------
+def _case_image(img: torch.Tensor, who: str):
+    """(dtype code, C, H, W, row stride, plane stride) of a [C, H, W] uint8 / float32 device tensor whose last axis is dense (a view sliced along H or W
+    of a wider tensor is fine)."""
+    if img.dim() != 3 or img.dtype not in (torch.uint8, torch.float32) or not img.is_cuda:
+        raise ValueError(f"{who}: the image must be a [C, H, W] uint8 or float32 device tensor, got {tuple(img.shape)} of {img.dtype} on {img.device}")
+    Cc, H, W = (int(v) for v in img.shape)
+    if Cc < 1 or H < 1 or W < 1 or (W > 1 and img.stride(2) != 1):
+        raise ValueError(f"{who}: image of shape {tuple(img.shape)} and strides {tuple(img.stride())}: empty, or the last axis is not dense")
+    return 0 if img.dtype == torch.uint8 else 1, Cc, H, W, max(int(img.stride(1)), W) if H > 1 else W, int(img.stride(0)) if Cc > 1 else H * max(int(img.stride(1)), W)
+
+
+def _case_labels(seg: torch.Tensor, who: str, like: Optional[torch.Tensor] = None):
+    if seg.dim() != 2 or seg.dtype != torch.uint8 or not seg.is_cuda or (seg.shape[1] > 1 and seg.stride(1) != 1) or seg.numel() == 0:
+        raise ValueError(f"{who}: the label map must be a [H, W] uint8 device tensor with a dense last axis, got {tuple(seg.shape)} of {seg.dtype} on {seg.device}")
+    if like is not None and (tuple(seg.shape) != tuple(like.shape[1:]) or seg.device != like.device):
+        raise ValueError(f"{who}: labels {tuple(seg.shape)} on {seg.device} do not fit the image {tuple(like.shape)} on {like.device}")
+    H, W = int(seg.shape[0]), int(seg.shape[1])
+    return H, W, max(int(seg.stride(0)), W) if H > 1 else W
+
+
+def _check_box(box, H: int, W: int, who: str):
+    y0, y1, x0, x1 = (int(v) for v in box)
+    if not (0 <= y0 < y1 <= H and 0 <= x0 < x1 <= W):
+        raise ValueError(f"{who}: box {(y0, y1, x0, x1)} is empty or leaves the {H} x {W} case")
+    return y0, y1, x0, x1
+
+
+def _launch_case_bbox(img: torch.Tensor, out: torch.Tensor) -> None:
+    dt, Cc, H, W, rs, ps = _case_image(img, "case_bbox")
+    with torch.cuda.device(img.device):
+        _lib.check(_lib.load().ldiff_op_case_bbox(_lib.ptr(img), dt, Cc, H, W, rs, ps, _lib.ptr(out), _lib.stream_ptr()))
+
+
+def case_bbox(img: torch.Tensor) -> Tuple[int, int, int, int]:
+    """ldiff_op_case_bbox: `nnunet.nonzero_bbox(img)` -- (y0, y1, x0, x1), ends exclusive, of the pixels where any channel is non-zero; the full extent
+    for an all-zero image -- for a [C, H, W] uint8 / float32 image on the device.  Synchronises (the box comes back to the host)."""
+    _lib.require_gpu()
+    out = torch.empty(4, dtype=torch.int32, device=img.device)
+    _launch_case_bbox(img, out)
+    return tuple(int(v) for v in out.cpu())
+
+
+def _launch_case_stats(img: torch.Tensor, box, out: torch.Tensor, ws: torch.Tensor) -> None:
+    dt, Cc, H, W, rs, ps = _case_image(img, "case_stats")
+    y0, y1, x0, x1 = _check_box(box, H, W, "case_stats")
+    with torch.cuda.device(img.device):
+        _lib.check(_lib.load().ldiff_op_case_stats(_lib.ptr(img), dt, Cc, H, W, rs, ps, y0, y1, x0, x1, _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+
+
+def case_stats(img: torch.Tensor, box) -> np.ndarray:
+    """ldiff_op_case_stats: per channel over the box, a numpy record array with `sum`, `sumsq` (python-exact uint64 for a uint8 image, float64 sums in a
+    fixed order for a float32 image), `min`, `max` (float64).  Synchronises."""
+    _lib.require_gpu()
+    out = torch.empty((int(img.shape[0]), 4), dtype=torch.int64, device=img.device)
+    ws = torch.empty(max(int(_lib.load().ldiff_op_case_stats_ws_bytes(int(img.shape[0]))), 16), dtype=torch.uint8, device=img.device)
+    _launch_case_stats(img, box, out, ws)
+    return stats_records(out.cpu().numpy(), img.dtype)
+
+
+def stats_records(raw: np.ndarray, dtype) -> np.ndarray:
+    """The [C, 4] int64 words ldiff_op_case_stats writes, viewed as records: the sums are uint64 for a uint8 image and float64 for a float32 one."""
+    kind = "<u8" if dtype == torch.uint8 else "<f8"
+    return np.ascontiguousarray(raw).view(np.dtype([("sum", kind), ("sumsq", kind), ("min", "<f8"), ("max", "<f8")])).reshape(-1)
+
+
+def normalization_scalars(raw_stats: np.ndarray, dtype, n_pixels: int, schemes: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
+    """(sub [C], div [C]) float32 with which ldiff_op_case_apply states `nnunet.normalize`: out = (x - sub) / div.  Mean and population standard deviation
+    are formed here in float64 (exactly, in integers, for a uint8 image) from the kernel's sums and rounded once to float32."""
+    rec = stats_records(raw_stats, dtype)
+    sub, div = np.zeros(len(schemes), np.float32), np.ones(len(schemes), np.float32)
+    for c, scheme in enumerate(schemes):
+        mn, mx = float(rec["min"][c]), float(rec["max"][c])
+        if scheme == "ZScoreNormalization":
+            if dtype == torch.uint8:
+                s1, s2, n = int(rec["sum"][c]), int(rec["sumsq"][c]), int(n_pixels)
+                mean, var = s1 / n, (n * s2 - s1 * s1) / (n * n)
+            else:
+                mean = float(rec["sum"][c]) / n_pixels
+                var = max(float(rec["sumsq"][c]) / n_pixels - mean * mean, 0.0)
+            sub[c], div[c] = mean, max(float(np.float32(math.sqrt(var))), 1e-8)
+        elif scheme == "RGBTo01Normalization":
+            if mn < 0 or mx > 255:
+                raise ValueError("RGBTo01Normalization: pixel values outside 0..255")
+            div[c] = 255.0
+        elif scheme == "RescaleTo01Normalization":
+            sub[c] = mn
+            div[c] = max(float(np.float32(mx) - np.float32(mn)), 1e-8)   # the float32 difference, as nnunet.normalize forms it
+        elif scheme != "NoNormalization":
+            nnunet._refuse("normalization_schemes", f"names {scheme!r}")
+    return sub, div
+
+
+def _launch_case_counts(seg: torch.Tensor, box, n_heads: int, totals: torch.Tensor):
+    H, W, ls = _case_labels(seg, "case_counts")
+    y0, y1, x0, x1 = _check_box(box, H, W, "case_counts")
+    if not 1 <= int(n_heads) <= 32:
+        raise ValueError(f"case_counts: n_heads {n_heads} out of range [1, 32]")
+    rows = y1 - y0
+    row_counts = torch.empty((rows, n_heads + 1), dtype=torch.int32, device=seg.device)
+    prefix = torch.empty((n_heads + 1, rows + 1), dtype=torch.int32, device=seg.device)
+    with torch.cuda.device(seg.device):
+        _lib.check(_lib.load().ldiff_op_case_counts(_lib.ptr(seg), H, W, ls, y0, y1, x0, x1, int(n_heads), _lib.ptr(row_counts), _lib.ptr(prefix), _lib.ptr(totals),
+                                                    _lib.stream_ptr()))
+    return row_counts, prefix
+
+
+def case_counts(seg: torch.Tensor, box, n_heads: int):
+    """ldiff_op_case_counts on a [H, W] uint8 label map on the device: (row_counts [rows, n_heads + 1] -- per row of the box the pixels of each class,
+    then those with a label >= n_heads; row_prefix [n_heads + 1, rows + 1] -- per class, and for `label > 0` at index n_heads, the exclusive prefix of
+    the selected pixels over the rows, the last entry the total; totals, a host array [n_heads + 2]: per class, `label > 0`, labels >= n_heads).  The first
+    two stay on the device (int32 holding the kernel's uint32 counts: a case has fewer than 2^31 pixels).  Synchronises."""
+    _lib.require_gpu()
+    totals = torch.empty(int(n_heads) + 2, dtype=torch.int32, device=seg.device)
+    row_counts, prefix = _launch_case_counts(seg, box, n_heads, totals)
+    return row_counts, prefix, totals.cpu().numpy().astype(np.int64)
+
+
+def _launch_case_apply(img: torch.Tensor, seg: torch.Tensor, box, sub: np.ndarray, div: np.ndarray, arena: torch.Tensor, row: np.ndarray, write_coef: bool) -> None:
+    dt, Cc, H, W, rs, ps = _case_image(img, "case_apply")
+    _, _, ls = _case_labels(seg, "case_apply", img)
+    y0, y1, x0, x1 = _check_box(box, H, W, "case_apply")
+    sub, div = np.ascontiguousarray(sub, np.float32), np.ascontiguousarray(div, np.float32)
+    if sub.shape != (Cc,) or div.shape != (Cc,) or arena.dtype != torch.uint8 or not arena.is_contiguous() or arena.device != img.device:
+        raise ValueError("case_apply: sub / div must hold one float per channel and the arena be a contiguous uint8 tensor on the image's device")
+    FP = _lib.C.POINTER(_lib.C.c_float)
+    c_row = _lib.SegCase(*(int(row[k]) for k in ("coef_off", "raw_off", "label_off", "H", "W", "stride", "label_stride")))
+    with torch.cuda.device(img.device):
+        _lib.check(_lib.load().ldiff_op_case_apply(_lib.ptr(img), dt, Cc, H, W, rs, ps, _lib.ptr(seg), ls, y0, y1, x0, x1, sub.ctypes.data_as(FP), div.ctypes.data_as(FP),
+                                                   _lib.ptr(arena), arena.numel(), _lib.C.byref(c_row), int(bool(write_coef)), _lib.stream_ptr()))
+
+
+def _launch_case_rank(seg: torch.Tensor, box, selector: int, prefix_row: torch.Tensor, ranks: torch.Tensor, image: Optional[torch.Tensor]):
+    H, W, ls = _case_labels(seg, "case_rank_to_coord", image)
+    y0, y1, x0, x1 = _check_box(box, H, W, "case_rank_to_coord")
+    if ranks.dim() != 1 or ranks.dtype != torch.int64 or not ranks.is_contiguous() or ranks.device != seg.device:
+        raise ValueError("case_rank_to_coord: ranks must be a contiguous int64 vector on the labels' device")
+    if prefix_row.dtype != torch.int32 or tuple(prefix_row.shape) != (y1 - y0 + 1,) or not prefix_row.is_contiguous() or prefix_row.device != seg.device:
+        raise ValueError(f"case_rank_to_coord: row_prefix must be the selector's contiguous int32 [{y1 - y0 + 1}] of case_counts")
+    n = int(ranks.numel())
+    coords = torch.empty((n, 2), dtype=torch.int32, device=seg.device)
+    values, dt, Cc, rs, ps = None, 0, 0, 0, 0
+    if image is not None:
+        dt, Cc, _, _, rs, ps = _case_image(image, "case_rank_to_coord")
+        values = torch.empty((n, Cc), dtype=image.dtype, device=seg.device)
+    with torch.cuda.device(seg.device):
+        _lib.check(_lib.load().ldiff_op_case_rank_to_coord(_lib.ptr(seg), H, W, ls, y0, y1, x0, x1, int(selector), _lib.ptr(prefix_row), _lib.ptr(ranks), n,
+                                                           _lib.ptr(coords), _lib.ptr(image), dt, Cc, rs, ps, _lib.ptr(values), _lib.stream_ptr()))
+    return coords, values
+
+
+def case_rank_to_coord(seg: torch.Tensor, box, selector: int, prefix_row: torch.Tensor, ranks: torch.Tensor, image: Optional[torch.Tensor] = None):
+    """ldiff_op_case_rank_to_coord: (coords int32 [n, 2], values [n, C] or None), on the device.  coords[k] = np.argwhere(selection)[ranks[k]] inside the
+    box, where the selection is `label == selector`, or `label > 0` for selector -1; `prefix_row` = `case_counts(...)[1][selector]` (index n_heads for
+    -1); values[k] = image[:, pixel].  Every rank must lie in [0, count): checked here against the prefix' last entry, which synchronises."""
+    _lib.require_gpu()
+    if ranks.numel():
+        lo, hi, count = int(ranks.min()), int(ranks.max()), int(prefix_row[-1])
+        if lo < 0 or hi >= count:
+            raise ValueError(f"case_rank_to_coord: ranks span [{lo}, {hi}], the selection has {count} pixels")
+    return _launch_case_rank(seg, box, selector, prefix_row, ranks, image)
 
 
 class PatchLoader:

@@ -10,7 +10,7 @@ Every contraction, normalisation, activation, loss term and parameter update run
 depth-to-space permute behind the transposed conv's GEMM and the global gradient norm.
 
 The trainer takes batches: `data` [B, C, H, W] float32 and `target`, the list the nnU-Net loader supplies, one label map per deep-supervision scale, highest
-resolution first; `nnunet_data.PatchLoader` makes them on the device.  Not here: nnU-Net's planner and dataset creation, DDP, a captured-graph step, ResidualEncoderUNet,
+resolution first; `nnunet_data.PatchLoader` makes them on the device; `Segmentor.train_tissue_model_nnUNetv2` wires planner, stores, loaders and this trainer together.  Not here: DDP, a captured-graph step, ResidualEncoderUNet,
 region labels and an ignore label.
 """
 from __future__ import annotations

@@ -217,6 +217,86 @@ class Segmentor:
             unet.detach_controlnet()
         return recon
 
+    def train_tissue_model_nnUNetv2(self, epochs, ldiffusion_weight, diffusion_path, train_images=None, train_labels=None, test_images=None, test_labels=None,
+                                    num_classes=None, *, iterations_per_epoch=250, val_iterations=50, num_foreground_voxels=None):
+        """segmentor.py:163-241: the tissue head's training stage, from image lists to a trained-model folder.
+        Dataset (:167-205): `load_ldiffusion`, the cached text embeddings of "A pathological slide", the text-alignment wrapper, and
+        `utils.create_nnunet_dataset` under nnUNet_raw (the one-pass diffusion of every image when all share one size, else copies).
+        Planning (`plan_and_preprocess_entry()`, :207-215): the written PNGs are read back onto the device; `nnunet_plan.extract_fingerprint`,
+        `plan_experiment` and `crossval_splits` give dataset_fingerprint.json, nnUNetPlans.json, dataset.json and splits_final.json under
+        nnUNet_preprocessed/<dataset>.  The cases themselves are not written there: they stay on the device.
+        Training (`get_trainer_from_args(...).run_training()`, :221-241): fold 0's train and validation keys as two `CaseStore(build="device")`, two
+        `PatchLoader`s with the plans' patch and batch size, `nnunet_train.Trainer.run_training`; checkpoints under
+        nnUNet_results/<dataset>/nnUNetTrainer__nnUNetPlans__2d/fold_0, plans.json and dataset.json beside it.
+        `iterations_per_epoch`, `val_iterations`: nnUNetTrainer's 250 / 50.  `num_foreground_voxels`: the fingerprint's sample budget (None: the
+        reference's 10e7).  The three folders come from the environment variables nnUNet_raw, nnUNet_preprocessed, nnUNet_results.
+        Returns the model folder -- what `inference_tissue_model_nnUNetv2(segmentor_weight=...)` takes."""
+        import json
+        from PIL import Image
+        from . import nnunet, nnunet_data, nnunet_plan, nnunet_train, utils
+        roots = {}
+        for name in ("nnUNet_raw", "nnUNet_preprocessed", "nnUNet_results"):
+            if not os.environ.get(name):
+                raise RuntimeError(f"train_tissue_model_nnUNetv2: the environment variable {name} is not set")
+            roots[name] = os.environ[name]
+        print("\033[32m[LDiffusion] Preparing data by L-Diffusion...\033[0m")
+        pipeline, unet, _ = self.load_ldiffusion(ldiffusion_weight, diffusion_path)
+        if num_classes is None:
+            num_classes = self.num_classes
+        if train_images is None or train_labels is None or test_images is None or test_labels is None:
+            if self.train_loader is None or self.val_loader is None:
+                raise ValueError("train_loader/val_loader are required when explicit nnUNet data lists are not provided")
+            train_images, train_labels = self.train_loader.dataset.image_dir, self.train_loader.dataset.label_dir
+            test_images, test_labels = self.val_loader.dataset.image_dir, self.val_loader.dataset.label_dir
+        aligned_unet = unet
+        if utils.check_images_same_size(train_images) and utils.check_images_same_size(test_images):   # only then does a sampler run (utils.py:213)
+            self._ensure_ldiffusion_proj(pipeline, unet, ldiffusion_weight=ldiffusion_weight)
+            aligned_unet = TextAlignedUNet(unet, self._get_text_embeddings(PROMPT, 1, pipeline, unet))
+        new_num, dataset_name = utils.create_nnunet_dataset(train_images, train_labels, test_images, test_labels, num_classes, pipeline, aligned_unet,
+                                                            raw_dir=roots["nnUNet_raw"])
+
+        print("\033[32m[Segmentor-nnUNet] Data preprocessing and plan generation in progress...\033[0m")
+        raw_dir = os.path.join(roots["nnUNet_raw"], dataset_name)
+        with open(os.path.join(raw_dir, "dataset.json")) as f:
+            dataset_json = json.load(f)
+        keys = sorted(n[:-len("_0000.png")] for n in os.listdir(os.path.join(raw_dir, "imagesTr")) if n.endswith("_0000.png"))
+        cases = {}
+        for k in keys:   # NaturalImage2DIO: the PNG's channels first; the label PNG as it is
+            img = np.array(Image.open(os.path.join(raw_dir, "imagesTr", k + "_0000.png")).convert("RGB"), np.uint8)
+            seg = np.array(Image.open(os.path.join(raw_dir, "labelsTr", k + ".png")).convert("L"), np.uint8)
+            cases[k] = (torch.from_numpy(img).permute(2, 0, 1).contiguous().to(self.device), torch.from_numpy(seg).to(self.device))
+        budget = {} if num_foreground_voxels is None else {"num_foreground_voxels": num_foreground_voxels}
+        pre_dir = os.path.join(roots["nnUNet_preprocessed"], dataset_name)
+        os.makedirs(pre_dir, exist_ok=True)
+
+        def save_json(name, obj, sort_keys=True):   # batchgenerators' save_json: indent 4, keys sorted unless the caller says otherwise
+            with open(os.path.join(pre_dir, name), "w") as f:
+                json.dump(obj, f, indent=4, sort_keys=sort_keys)
+
+        save_json("dataset_fingerprint.json", nnunet_plan.extract_fingerprint([cases[k] for k in keys], dataset_json, **budget))
+        with open(os.path.join(pre_dir, "dataset_fingerprint.json")) as f:   # the planner plans from the file (ExperimentPlanner.__init__ :46): its key order
+            fingerprint = json.load(f)
+        plans = nnunet_plan.plan_experiment(fingerprint, dataset_json, dataset_name)
+        splits = nnunet_plan.crossval_splits(keys)
+        save_json("nnUNetPlans.json", plans, sort_keys=False)
+        save_json("dataset.json", dataset_json, sort_keys=False)
+        save_json("splits_final.json", splits)
+
+        print("\033[32m[Segmentor-nnUNet] Training is starting...\033[0m")
+        spec = nnunet.network_spec(plans, "2d", dataset_json)
+        cfg = plans["configurations"]["2d"]
+        stores = [nnunet_data.CaseStore([cases[k] for k in splits[0][part]], spec["normalization_schemes"], spec["n_heads"], device=self.device,
+                                        labels=dataset_json["labels"], prefilter="device", build="device") for part in ("train", "val")]
+        n_scales = spec["n_stages"] - 1
+        loaders = [nnunet_data.PatchLoader(store, spec["patch_size"], cfg["batch_size"], n_scales, seed=seed, train=train)
+                   for store, seed, train in ((stores[0], 0, True), (stores[1], 1, False))]
+        trainer = nnunet_train.Trainer(spec, nnunet_train.initial_state_dict(spec), cfg["batch_dice"], num_epochs=epochs, device=self.device)
+        model_dir = os.path.join(roots["nnUNet_results"], dataset_name, "nnUNetTrainer__nnUNetPlans__2d")
+        nnunet.write_trained_model_folder(model_dir, plans, dataset_json)
+        self.training_log = trainer.run_training(loaders[0], loaders[1], os.path.join(model_dir, "fold_0"), iterations_per_epoch=iterations_per_epoch,
+                                                 val_iterations=val_iterations)
+        return model_dir
+
     def _cell_head(self, weight_dir):
         """The cell head of a `segmentor_weight` folder (cellclassifier.pth), built once per (file, mtime)."""
         from . import cellhead

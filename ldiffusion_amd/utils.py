@@ -60,6 +60,93 @@ def copy_or_convert_image(img, src_path, dst_path, pipeline=None, unet=None, use
     Image.fromarray(rgb).save(dst_path)
 
 
+_warned = False   # utils.py:15: the size warning is printed once
+
+
+def check_images_same_size(image_paths):
+    """utils.py:155-163: True when every image has the same (width, height)."""
+    from PIL import Image
+    sizes = set()
+    for path in image_paths:
+        with Image.open(path) as img:
+            sizes.add(img.size)
+        if len(sizes) > 1:
+            return False
+    return True
+
+
+def fix_label_size(img, lbl, img_name, lbl_name):
+    """utils.py:17-24: a label image whose size differs from its image's is resized to it with NEAREST (warned about once)."""
+    global _warned
+    from PIL import Image
+    if img.size != lbl.size:
+        if not _warned:
+            print("\033[91m[WARNING] Some image/label sizes are inconsistent. Labels will be resized to match images.\033[0m")
+            _warned = True
+        lbl = lbl.resize(img.size, Image.NEAREST)
+    return lbl
+
+
+def convert_and_save_label(lbl, dst_path, mapping):
+    """utils.py:165-174: grey levels -> class indices by `mapping` (levels it does not name become 0), saved as an 8-bit PNG."""
+    from PIL import Image
+    lut = np.zeros(256, np.uint8)
+    for level, index in mapping.items():
+        lut[int(level)] = index
+    Image.fromarray(lut[np.asarray(lbl.convert("L"), np.uint8)]).save(dst_path)
+
+
+def create_nnunet_dataset(train_images, train_labels, test_images, test_labels, num_classes, pipeline, unet, raw_dir=None):
+    """utils.py:210-294: the next `DatasetNNN_Custom` under nnUNet_raw (`raw_dir`, else the environment variable nnUNet_raw) with imagesTr / labelsTr /
+    imagesTs / labelsTs, `case_%03d_0000.png` + `case_%03d.png` and `caseTs_%03d...`; every image goes through `copy_or_convert_image` -- the
+    one-pass diffusion when ALL train and ALL test images share one size, else a plain copy --, every label is resized to its image (NEAREST) and
+    mapped through metrics.PIXEL_TO_LABEL; `dataset.json` as the reference writes it.  Returns (new_num, new_dataset_name)."""
+    import json
+    import os
+    from pathlib import Path
+    from PIL import Image
+    raw = raw_dir if raw_dir is not None else os.environ.get("nnUNet_raw")
+    if raw is None:
+        raise RuntimeError("create_nnunet_dataset: no nnUNet_raw folder: pass raw_dir= or set the environment variable nnUNet_raw")
+    raw_path = Path(raw)
+    if not raw_path.exists():
+        raise FileNotFoundError(f"create_nnunet_dataset: nnUNet_raw = {raw} does not exist")
+    use_diffusion = check_images_same_size(train_images) and check_images_same_size(test_images)
+    max_num = 0
+    for d in raw_path.iterdir():
+        if d.is_dir() and d.name.startswith("Dataset"):
+            try:
+                max_num = max(max_num, int(d.name[7:10]))
+            except ValueError:
+                continue
+    new_num = max_num + 1
+    new_dataset_name = f"Dataset{new_num:03d}_Custom"
+    new_path = raw_path / new_dataset_name
+    new_path.mkdir(parents=True, exist_ok=False)
+    for sub in ("imagesTr", "labelsTr", "imagesTs", "labelsTs"):
+        (new_path / sub).mkdir()
+    n_train = 0
+    for images, labels, stem, img_dir, lbl_dir in ((train_images, train_labels, "case", "imagesTr", "labelsTr"), (test_images, test_labels, "caseTs", "imagesTs", "labelsTs")):
+        for idx, (img_path, lbl_path) in enumerate(zip(images, labels)):
+            case_id = f"{stem}_{idx:03d}"
+            img_path = Path(img_path)
+            img = Image.open(img_path).convert("RGB")
+            lbl = fix_label_size(img, Image.open(lbl_path).convert("L"), img_path.name, lbl_path)
+            copy_or_convert_image(img, img_path, new_path / img_dir / f"{case_id}_0000.png", pipeline, unet, use_diffusion)
+            convert_and_save_label(lbl, new_path / lbl_dir / f"{case_id}.png", metrics.PIXEL_TO_LABEL)
+            n_train += stem == "case"
+    dataset_json = {
+        "channel_names": {"0": "R", "1": "G", "2": "B"},
+        "labels": {"background": 0, **{f"class{i}": i for i in range(1, num_classes)}},
+        "numTraining": n_train,
+        "file_ending": ".png",
+    }
+    with open(new_path / "dataset.json", "w") as f:
+        json.dump(dataset_json, f, indent=4)
+    print(f"create new nnUNet Dataset：{new_dataset_name}")
+    return new_num, new_dataset_name
+
+
 def micro_dice(predicted_labels, true_labels, num_classes=7):
     """utils.py:55-82 (= Segmentor.micro_dice, segmentor.py:114-142): logits [B, C, H, W] and labels [B, H, W] -> (per-class float32 tensor, its mean);
     the whole batch is flattened together and a class absent from both prediction and labels scores 1.  One launch and one copy of C^2 integers per
