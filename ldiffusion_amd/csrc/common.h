@@ -83,7 +83,7 @@ struct ConvParams {
   const f16* w_par;       // conv3x3 with ups=1 only: parity weights [4][Nrows][4*Cin] (see kernels_conv3x3.hip); nullptr => 9-tap gather
   unsigned div_ntn, div_tx, div_ty;   // conv3x3 8x16 kernel only, set by its launcher: reciprocals of its tile decode (0 = divisor 1)
   // decode_latents tail fused into the epilogue (narrow-output kernel only, conv3x3n_selected): from the fp32 sums (x/2+0.5).clamp(0,1) -> post_img
-  // [M,3] f32, (.*255).round() half-even -> post_rgb [M,3] u8, ITU-601 integer luma -> post_luma[b, post_slot, pixel] (kernels_elem.hip decode_post)
+  // [M,3] f32, (.*255).round() half-even -> post_rgb [M,3] u8, ITU-601 integer luma -> post_luma[b, post_slot, pixel] (decode_tail below)
   float* post_img = nullptr; uint8_t* post_rgb = nullptr; uint8_t* post_luma = nullptr; int post_slots = 0, post_slot = 0, post_only = 0;   // post_only: y is not written
   int short_runs = 0;   // set by the executor of a graph that shares the chip with another stream (the VAE decoder beside the UNet): persistent kernels cap their run length
   unsigned div_tm; int tiles_m, img_fast;   // conv3x3 halo-tile kernels, set by their launchers: pixel tiles of the launch; tile order (see conv3x3_img_fast)
@@ -125,6 +125,29 @@ struct ConvParams {
   // applies then holds for the real launch too.  (plan_M is stated, not derived: the rows of a time-embedding or context launch are the batch itself.)
   int plan_B = 0, plan_M = 0;
 };
+// The decode_latents tail on a pixel's three fp32 sums (ConvParams::post_*; the epilogues of kernels_conv3x3n.hip and decode_post_kernel of kernels_elem.hip),
+// pinned bit for bit to torch, numpy and Pillow:
+//   (x/2+0.5).clamp(0,1)                                -> img[row, 3] f32   (two roundings; clamp propagates NaN in torch)
+//   (img*255).round().astype(uint8), half-even          -> rgb[row, 3] u8
+//   convert("L"): (19595R + 38470G + 7471B + 0x8000) >> 16 -> luma() of the return value (the caller knows the pixel's place in its luma slot and stores it last)
+// A null pointer skips its output.
+struct DecodedPx {
+  unsigned q[3];   // the pixel's uint8 levels
+  __device__ __forceinline__ uint8_t luma() const { return (uint8_t)((19595u * q[0] + 38470u * q[1] + 7471u * q[2] + 0x8000u) >> 16); }
+};
+__device__ __forceinline__ DecodedPx decode_tail(const float* x, long long row, float* img, uint8_t* rgb) {
+  DecodedPx d;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    float v = __fadd_rn(__fmul_rn(x[c], 0.5f), 0.5f);
+    v = fminf(fmaxf(v, 0.f), 1.f);
+    if (x[c] != x[c]) v = x[c];
+    if (img) img[row * 3 + c] = v;
+    d.q[c] = (unsigned)(int)rintf(__fmul_rn(v, 255.0f));
+  }
+  if (rgb) { rgb[row * 3 + 0] = (uint8_t)d.q[0]; rgb[row * 3 + 1] = (uint8_t)d.q[1]; rgb[row * 3 + 2] = (uint8_t)d.q[2]; }
+  return d;
+}
 // The launch every batch-dependent choice reads: p itself without a plan batch
 inline ConvParams nominal_launch(const ConvParams& p) {
   ConvParams q = p;

@@ -14,7 +14,7 @@
 // tile 2s+1); the V^T read uses the same order, so no permutation is ever materialised.
 #include <type_traits>
 
-#include "common.h"
+#include "lds_prims.h"
 
 template <int DQK>
 struct KLayout {
@@ -360,25 +360,7 @@ static void launch_attn_cfg2(const AttnParams& p, hipStream_t s) {
 
 // Hand-scheduled LDS fetches for the d-split kernel (one wave per SIMD: nothing else hides an LDS round trip).  hipcc emits
 // "ds_read; s_waitcnt lgkmcnt(0); v_mfma" per fragment, i.e. 32 exposed round trips per tile in S^T = K Q^T alone; the reads
-// are therefore issued in batches as inline asm and waited for with counted lgkmcnt (the wait names its fragment as an
-// in/out operand so the consuming MFMA cannot move above it).
-template <int I, int N, class F>
-__device__ __forceinline__ void attn_static_for(F&& f) {
-  if constexpr (I < N) { f(std::integral_constant<int, I>{}); attn_static_for<I + 1, N>(f); }
-}
-template <int OFF>
-__device__ __forceinline__ void attn_lds_read128(f16x8& d, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory");
-}
-template <int OFF>
-__device__ __forceinline__ void attn_lds_read_tr(f16x4& d, unsigned addr) {
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory");
-}
-template <int CNT>
-__device__ __forceinline__ void attn_lds_wait(f16x8& a) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a) : "n"(CNT)); }
-template <int CNT>
-__device__ __forceinline__ void attn_lds_wait(f16x4& a, f16x4& b) { asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(CNT)); }
-
+// are therefore issued in batches and waited for with counted lgkmcnt (lds_read128 / lds_read_tr / lds_wait of lds_prims.h).
 template <int BKV>
 __global__ __launch_bounds__(256, 1) void attn_dsplit_kernel(const AttnParams p) {
   constexpr int D = 512, KS = D / 32, NT = BKV / 16, DTW = 8, PSTR = BKV * 2 + 16;   // P row stride in bytes (16-B aligned, odd multiple of 16)
@@ -467,13 +449,13 @@ __global__ __launch_bounds__(256, 1) void attn_dsplit_kernel(const AttnParams p)
     f32x4 sacc[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) sacc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    attn_static_for<0, NT * KS / 8>([&](auto bc) {
+    static_for<0, NT * KS / 8>([&](auto bc) {
       constexpr int t = decltype(bc)::value / (KS / 8), k0 = (decltype(bc)::value % (KS / 8)) * 8;
       f16x8 kf[8];
-      attn_static_for<0, 8>([&](auto ic) { constexpr int i = decltype(ic)::value; attn_lds_read128<t * 16 * 1024>(kf[i], kbase ^ (unsigned)((k0 + i) * 64)); });
-      attn_static_for<0, 8>([&](auto ic) {
+      static_for<0, 8>([&](auto ic) { constexpr int i = decltype(ic)::value; lds_read128<t * 16 * 1024>(kf[i], kbase ^ (unsigned)((k0 + i) * 64)); });
+      static_for<0, 8>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
-        attn_lds_wait<7 - i>(kf[i]);
+        lds_wait<7 - i>(kf[i]);
         sacc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[i], qf[k0 + i], sacc[t], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
       });
@@ -536,14 +518,14 @@ __global__ __launch_bounds__(256, 1) void attn_dsplit_kernel(const AttnParams p)
     // V^T fragments: all 16 transposed reads of the step are issued first (lane 4q+p of its 16-lane group addresses key row
     // 8g+q (+4), d columns 4p..4p+3 of d tile dt), then 8 x 4 MFMAs with counted waits
     f16x4 vlo[DTW], vhi[DTW];
-    attn_static_for<0, DTW>([&](auto dc) {
+    static_for<0, DTW>([&](auto dc) {
       constexpr int dt = decltype(dc)::value;
-      attn_lds_read_tr<dt * 32>(vlo[dt], vbase);                    // keys 8g .. 8g+3
-      attn_lds_read_tr<dt * 32 + 4 * VSTR * 4>(vhi[dt], vbase);     // keys 8g+4 .. 8g+7
+      lds_read_tr<dt * 32>(vlo[dt], vbase);                    // keys 8g .. 8g+3
+      lds_read_tr<dt * 32 + 4 * VSTR * 4>(vhi[dt], vbase);     // keys 8g+4 .. 8g+7
     });
-    attn_static_for<0, DTW>([&](auto dc) {
+    static_for<0, DTW>([&](auto dc) {
       constexpr int dt = decltype(dc)::value;
-      attn_lds_wait<2 * (DTW - 1 - dt)>(vlo[dt], vhi[dt]);
+      lds_wait<2 * (DTW - 1 - dt)>(vlo[dt], vhi[dt]);
       const f16x8 vf = {vlo[dt][0], vlo[dt][1], vlo[dt][2], vlo[dt][3], vhi[dt][0], vhi[dt][1], vhi[dt][2], vhi[dt][3]};
 #pragma unroll
       for (int j = 0; j < 4; ++j) oacc[j][dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pf[j], oacc[j][dt], 0, 0, 0);
@@ -607,10 +589,6 @@ constexpr unsigned D5_K0 = 0, D5_V0 = 2 * D5_KB, D5_P0 = D5_V0 + 2 * D5_VB, D5_A
 static_assert(D5_LDS <= 160 * 1024, "LDS budget");
 constexpr float D5_LEAD = 4.0f, D5_WINDOW = 15.0f;   // binades: reference above the first tile's maximum; headroom of fp16 P above the reference
 
-__device__ __forceinline__ void d5_lds_write64(unsigned addr, uint2 v) { asm volatile("ds_write_b64 %0, %1" :: "v"(addr), "v"(v) : "memory"); }
-__device__ __forceinline__ void d5_lds_write32(unsigned addr, float v) { asm volatile("ds_write_b32 %0, %1" :: "v"(addr), "v"(v) : "memory"); }
-__device__ __forceinline__ void d5_lds_read32(float& d, unsigned addr) { asm volatile("ds_read_b32 %0, %1" : "=v"(d) : "v"(addr) : "memory"); }
-
 __global__ __launch_bounds__(256, 1) void attn_d512_kernel(const AttnParams p) {
   typedef __attribute__((address_space(3))) void lds_void;
   constexpr int D = 512, KS = D / 32, NT = D5_BKV / 16, DTW = 8, NJ = D5_QB / 16;
@@ -645,7 +623,7 @@ __global__ __launch_bounds__(256, 1) void attn_d512_kernel(const AttnParams p) {
 #endif
   };
   auto issue_tile = [&](int kv0, int buf) __attribute__((always_inline)) {
-    attn_static_for<0, 8>([&](auto pc) { issue_row(kv0, buf, pc); });
+    static_for<0, 8>([&](auto pc) { issue_row(kv0, buf, pc); });
   };
   issue_tile(0, 0);
 
@@ -682,15 +660,15 @@ __global__ __launch_bounds__(256, 1) void attn_d512_kernel(const AttnParams p) {
     f16x8 kf[2][4];
     auto issue_k = [&](auto bc) __attribute__((always_inline)) {
       constexpr int bb = decltype(bc)::value, t = bb / (KS / 4), k0 = (bb % (KS / 4)) * 4;
-      attn_static_for<0, 4>([&](auto ic) { constexpr int i = decltype(ic)::value; attn_lds_read128<t * 16 * 1024>(kf[bb & 1][i], kb ^ (unsigned)((k0 + i) * 64)); });
+      static_for<0, 4>([&](auto ic) { constexpr int i = decltype(ic)::value; lds_read128<t * 16 * 1024>(kf[bb & 1][i], kb ^ (unsigned)((k0 + i) * 64)); });
     };
     issue_k(std::integral_constant<int, 0>{});
-    attn_static_for<0, NB>([&](auto bc) {
+    static_for<0, NB>([&](auto bc) {
       constexpr int bb = decltype(bc)::value, t = bb / (KS / 4), k0 = (bb % (KS / 4)) * 4;
       if constexpr (bb + 1 < NB) issue_k(std::integral_constant<int, bb + 1>{});
-      attn_static_for<0, 4>([&](auto ic) {
+      static_for<0, 4>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
-        attn_lds_wait<(bb + 1 < NB ? 4 : 0) + 3 - i>(kf[bb & 1][i]);
+        lds_wait<(bb + 1 < NB ? 4 : 0) + 3 - i>(kf[bb & 1][i]);
         sacc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[bb & 1][i], qf[0][k0 + i], sacc[0][t], 0, 0, 0);
         sacc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[bb & 1][i], qf[1][k0 + i], sacc[1][t], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
@@ -756,7 +734,7 @@ __global__ __launch_bounds__(256, 1) void attn_d512_kernel(const AttnParams p) {
             lsum[j] += pv;
             ph[r] = (f16)pv;
           }
-          d5_lds_write64(pw_base + (unsigned)(j * 16 * D5_PSTR + t * 32), __builtin_bit_cast(uint2, ph));
+          lds_write64(pw_base + (unsigned)(j * 16 * D5_PSTR + t * 32), __builtin_bit_cast(uint2, ph));
         }
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -764,28 +742,28 @@ __global__ __launch_bounds__(256, 1) void attn_d512_kernel(const AttnParams p) {
 
       // ---- O^T[d slice of this wave][128 queries] += V^T P^T ----
       f16x8 pf[NJ];
-      attn_static_for<0, NJ>([&](auto jc) {
+      static_for<0, NJ>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
-        attn_lds_read128<j * 16 * (int)D5_PSTR>(pf[j], pr_base);
+        lds_read128<j * 16 * (int)D5_PSTR>(pf[j], pr_base);
       });
       const unsigned vb = vbase + (unsigned)buf * D5_VB;
       f16x4 vlo[2][2], vhi[2][2];   // [parity of the batch][d tile of the batch]: the next batch's reads are issued before this batch's MFMAs
       auto issue_v = [&](auto hc) __attribute__((always_inline)) {
         constexpr int hb = decltype(hc)::value;
-        attn_static_for<0, 2>([&](auto dc) {
+        static_for<0, 2>([&](auto dc) {
           constexpr int i = decltype(dc)::value, dt = hb * 2 + i;
-          attn_lds_read_tr<dt * 32>(vlo[hb & 1][i], vb);                                          // keys 8g .. 8g+3
-          attn_lds_read_tr<dt * 32 + 4 * (int)D5_VROW>(vhi[hb & 1][i], vb);                       // keys 8g+4 .. 8g+7
+          lds_read_tr<dt * 32>(vlo[hb & 1][i], vb);                                          // keys 8g .. 8g+3
+          lds_read_tr<dt * 32 + 4 * (int)D5_VROW>(vhi[hb & 1][i], vb);                       // keys 8g+4 .. 8g+7
         });
       };
       issue_v(std::integral_constant<int, 0>{});
       asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(pf[0]), "+v"(pf[1]), "+v"(pf[2]), "+v"(pf[3]), "+v"(pf[4]), "+v"(pf[5]), "+v"(pf[6]), "+v"(pf[7]));
-      attn_static_for<0, 4>([&](auto hc) {
+      static_for<0, 4>([&](auto hc) {
         constexpr int hb = decltype(hc)::value;
         if constexpr (hb < 3) issue_v(std::integral_constant<int, hb + 1>{});
-        attn_static_for<0, 2>([&](auto dc) {
+        static_for<0, 2>([&](auto dc) {
           constexpr int i = decltype(dc)::value, dt = hb * 2 + i;
-          attn_lds_wait<(hb < 3 ? 4 : 0) + 2 * (1 - i)>(vlo[hb & 1][i], vhi[hb & 1][i]);
+          lds_wait<(hb < 3 ? 4 : 0) + 2 * (1 - i)>(vlo[hb & 1][i], vhi[hb & 1][i]);
           const f16x8 vf = {vlo[hb & 1][i][0], vlo[hb & 1][i][1], vlo[hb & 1][i][2], vlo[hb & 1][i][3], vhi[hb & 1][i][0], vhi[hb & 1][i][1], vhi[hb & 1][i][2], vhi[hb & 1][i][3]};
 #pragma unroll
           for (int j = 0; j < NJ; ++j) oacc[j][dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pf[j], oacc[j][dt], 0, 0, 0);
@@ -803,7 +781,7 @@ __global__ __launch_bounds__(256, 1) void attn_d512_kernel(const AttnParams p) {
     const bool left = mobs[0] - mref[0] > D5_WINDOW || mobs[1] - mref[1] > D5_WINDOW;
     __builtin_amdgcn_s_barrier();   // the last tile's P has been read
     const float flag = __builtin_amdgcn_ballot_w64(left) != 0 ? 1.0f : 0.0f;   // (all lanes vote: outside the branch below)
-    if (lane == 0) d5_lds_write32(lds0 + D5_FL + (unsigned)(wave * 4), flag);
+    if (lane == 0) lds_write32(lds0 + D5_FL + (unsigned)(wave * 4), flag);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     f32x4 fl;
@@ -821,7 +799,7 @@ __global__ __launch_bounds__(256, 1) void attn_d512_kernel(const AttnParams p) {
     float l = lsum[j];
     l += __shfl_xor(l, 16);
     l += __shfl_xor(l, 32);
-    d5_lds_write32(al_w + (unsigned)(j * 64), l);   // (the four g lanes of a query write the same value)
+    lds_write32(al_w + (unsigned)(j * 64), l);   // (the four g lanes of a query write the same value)
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -830,7 +808,7 @@ __global__ __launch_bounds__(256, 1) void attn_d512_kernel(const AttnParams p) {
   for (int j = 0; j < NJ; ++j) {
     const int qi = q0 + j * 16 + l15;
     float sum;
-    d5_lds_read32(sum, al_r + (unsigned)(j * 64));
+    lds_read32(sum, al_r + (unsigned)(j * 64));
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(sum));
     const float inv = 1.0f / sum;
     if (qi < p.Lq) {
@@ -954,17 +932,17 @@ __global__ __launch_bounds__(256, 2) void attn_fr40_kernel(const AttnParams p) {
       for (int t = 0; t < NT; ++t) sacc[qt][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const unsigned kb = kb0 + (unsigned)buf * FR_KB;
     f16x8 kf[NT][KS];
-    attn_static_for<0, NT>([&](auto tc) {
+    static_for<0, NT>([&](auto tc) {
       constexpr int t = decltype(tc)::value;
-      attn_lds_read128<t * 16 * 128>(kf[t][0], kb);
-      attn_lds_read128<t * 16 * 128>(kf[t][1], kb ^ 64u);
+      lds_read128<t * 16 * 128>(kf[t][0], kb);
+      lds_read128<t * 16 * 128>(kf[t][1], kb ^ 64u);
     });
-    attn_static_for<0, NT>([&](auto tc) {
+    static_for<0, NT>([&](auto tc) {
       constexpr int t = decltype(tc)::value;
-      attn_lds_wait<2 * (NT - 1 - t) + 1>(kf[t][0]);
+      lds_wait<2 * (NT - 1 - t) + 1>(kf[t][0]);
       sacc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[t][0], qf[0][0], sacc[0][t], 0, 0, 0);
       sacc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[t][0], qf[1][0], sacc[1][t], 0, 0, 0);
-      attn_lds_wait<2 * (NT - 1 - t)>(kf[t][1]);
+      lds_wait<2 * (NT - 1 - t)>(kf[t][1]);
       sacc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[t][1], qf[0][1], sacc[0][t], 0, 0, 0);
       sacc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[t][1], qf[1][1], sacc[1][t], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
@@ -1025,19 +1003,19 @@ __global__ __launch_bounds__(256, 2) void attn_fr40_kernel(const AttnParams p) {
       // ---- O^T += V^T P^T; V^T row 40 (d tile 2, lane l15 = 8) is all ones: row 40 of O^T accumulates the row sums ----
       const unsigned vb = vb0 + (unsigned)buf * FR_VB;
       f16x4 vlo[NT / 2][DT], vhi[NT / 2][DT];
-      attn_static_for<0, NT / 2>([&](auto sc) {
+      static_for<0, NT / 2>([&](auto sc) {
         constexpr int s2 = decltype(sc)::value;
-        attn_static_for<0, DT>([&](auto dc) {
+        static_for<0, DT>([&](auto dc) {
           constexpr int dt = decltype(dc)::value;
-          attn_lds_read_tr<(2 * s2) * 16 * (int)FR_VROW + dt * 32>(vlo[s2][dt], vb);
-          attn_lds_read_tr<(2 * s2 + 1) * 16 * (int)FR_VROW + dt * 32>(vhi[s2][dt], vb);
+          lds_read_tr<(2 * s2) * 16 * (int)FR_VROW + dt * 32>(vlo[s2][dt], vb);
+          lds_read_tr<(2 * s2 + 1) * 16 * (int)FR_VROW + dt * 32>(vhi[s2][dt], vb);
         });
       });
-      attn_static_for<0, NT / 2>([&](auto sc) {
+      static_for<0, NT / 2>([&](auto sc) {
         constexpr int s2 = decltype(sc)::value;
-        attn_static_for<0, DT>([&](auto dc) {
+        static_for<0, DT>([&](auto dc) {
           constexpr int dt = decltype(dc)::value;
-          attn_lds_wait<2 * ((NT / 2 - 1 - s2) * DT + (DT - 1 - dt))>(vlo[s2][dt], vhi[s2][dt]);
+          lds_wait<2 * ((NT / 2 - 1 - s2) * DT + (DT - 1 - dt))>(vlo[s2][dt], vhi[s2][dt]);
           f16x8 vf = {vlo[s2][dt][0], vlo[s2][dt][1], vlo[s2][dt][2], vlo[s2][dt][3], vhi[s2][dt][0], vhi[s2][dt][1], vhi[s2][dt][2], vhi[s2][dt][3]};
           if constexpr (dt == 2) vf = l15 == 8 ? ones8 : vf;
 #pragma unroll
@@ -1056,7 +1034,7 @@ __global__ __launch_bounds__(256, 2) void attn_fr40_kernel(const AttnParams p) {
     for (int qt = 0; qt < QT; ++qt) bad |= g == 2 && !(oacc[qt][2][0] < 65504.0f);
     const float flag = __builtin_amdgcn_ballot_w64(bad) != 0 ? 1.0f : 0.0f;
     __builtin_amdgcn_s_barrier();   // (all K / V reads of the pass are done)
-    if (lane == 0) d5_lds_write32(lds0 + FR_FL + (unsigned)(wave * 4), flag);
+    if (lane == 0) lds_write32(lds0 + FR_FL + (unsigned)(wave * 4), flag);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     f32x4 fl;

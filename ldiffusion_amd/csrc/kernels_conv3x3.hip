@@ -16,6 +16,7 @@
 // the 16x16x32 operand fetch).  The DMA writes LDS linearly, so the swizzle is applied on the weight SOURCE address.
 #include "epilogue.h"
 #include "lds_prims.h"
+#include "stamps.h"
 
 namespace {
 
@@ -301,28 +302,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(const ConvParams p) {  
 //   * operand reads as inline asm with counted lgkmcnt waits (hipcc only ever emits lgkmcnt(0) there);
 //   * halo staging without exec masking (clamped source address, AND mask, dump slot for the lanes beyond the halo),
 //     GroupNorm+SiLU of chunk i spread over taps 1.., SiLU chosen by one uniform branch per chunk.
-// Column swizzle of the halo image: 16-byte chunk c of halo pixel (hy, hx) sits at position c ^ swzx(hx) of its 128-B row.
-// A 16x16x32 operand fetch reads 16 consecutive pixels of one halo row starting at column kx = 0, 1 or 2; its four
-// ds_read_b128 lane groups mix chunks c (8 lanes) and c^1 (8 lanes).  The table (one 3-bit entry per column PAIR, found by
-// exhaustive search against the bank model of MI355X_MICROARCH.md, LDS) makes all three starts conflict-free; the plain
-// (hx>>1)&7 is conflict-free only for kx = 0 and costs 2x on the other two thirds of the taps (SQ_LDS_BANK_CONFLICT = 26 %
-// of the LDS-active cycles).  The position is an XOR of the chunk index, so k-half 1 is still byte address ^ 64.
-__device__ __forceinline__ int swzx(int hx) { return (0xcb5888 >> (3 * (hx >> 1))) & 7; }
+// (the halo image's column swizzle: swzx of lds_prims.h)
 
-#ifdef C3W_STAMPS   // diagnostic build only (scripts/build_c3w_stamps.sh, scripts/conv_stamps_w.py): where a (slab, tap) step of wave 0 of workgroup 0 goes
+#ifdef LDIFF_STAMPS   // diagnostic build only (stamps.h, scripts/conv_stamps_w.py): where a (slab, tap) step of wave 0 of workgroup 0 goes
 __device__ unsigned long long c3w_dbg[32];   // [0..4] totals, [8 + T] MFMA segment of tap T, [20 + T] issue segment of tap T
-__device__ __forceinline__ unsigned long long w_stamp() {
-  __builtin_amdgcn_sched_barrier(0);
-  unsigned long long t = __builtin_amdgcn_s_memtime();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#define WSTAMP(v) const unsigned long long v = w_stamp()
-#define WACC(i, expr) wdbg[i] += (expr)
-#else
-#define WSTAMP(v)
-#define WACC(i, expr)
 #endif
 
 template <int BN, bool GN, bool LR = false>   // LR: see conv3x3_kernel
@@ -374,9 +357,9 @@ __global__ __launch_bounds__(256, BN > 128 ? 1 : 2) void conv3x3w_kernel(const C
   const int sh = par ? 0 : p.ups;
   const int He = p.Hin << sh, We = p.Win << sh;
   const unsigned lds0 = (unsigned)(size_t)(lptr_t*)smem_raw;
-#ifdef C3W_STAMPS
-  unsigned long long wdbg[32] = {0};
-  WSTAMP(w_t0);
+#ifdef LDIFF_STAMPS
+  unsigned long long dbg[32] = {0};
+  STAMP(w_t0);
 #endif
 
   // ---- halo staging: thread owns chunk column kc of halo pixels hp = tid/8 + 32*i ----
@@ -525,7 +508,7 @@ __global__ __launch_bounds__(256, BN > 128 ? 1 : 2) void conv3x3w_kernel(const C
         constexpr int NE = GN && STAGE && C0 < C1 ? (C1 - C0) * 4 : 0, EPG = (NE + NT - 1) / NT;   // NE element PAIRS (dwords), EPG per MFMA group
         unsigned pk[NE > 0 ? NE : 1];         // normalised elements, packed f16 pairs
         f16x8 wf[2][NT], xf[2][MT];
-        WSTAMP(s0);
+        STAMP(s0);
         // k-half 0 up front; the k-half-1 reads go out between the first MFMA groups (an LDS instruction issues while the matrix pipe
         // works: all sixteen in front of the first MFMA cost ~100 cycles of every step)
         // RING3: slot T % 3 (static); the slice of step + 2 goes out piece by piece between the first MFMA groups below
@@ -543,7 +526,7 @@ __global__ __launch_bounds__(256, BN > 128 ? 1 : 2) void conv3x3w_kernel(const C
         }
         if (T == 0 && stage) load_halo(c + 1);
         __builtin_amdgcn_sched_barrier(0);
-        WSTAMP(s1);   // (the stamp drains the LDS queue: the first MFMA group no longer waits for its operands inside the next segment)
+        STAMP(s1);   // (the stamp drains the LDS queue: the first MFMA group no longer waits for its operands inside the next segment)
         static_for<0, 2 * NT>([&](auto ic) {
           constexpr int kk = decltype(ic)::value / NT, a = decltype(ic)::value % NT;
           constexpr int WI = NT > 1 ? 1 : 0;   // the k-half-1 X reads follow group 0 of k-half 0, the W reads group WI
@@ -569,7 +552,7 @@ __global__ __launch_bounds__(256, BN > 128 ? 1 : 2) void conv3x3w_kernel(const C
           if constexpr (GN) v = make_uint4(pk[(i - C0) * 4], pk[(i - C0) * 4 + 1], pk[(i - C0) * 4 + 2], pk[(i - C0) * 4 + 3]);
           mask_store(ic, v, (unsigned)(HP * 128) - hbuf);
         });
-        WSTAMP(s2);
+        STAMP(s2);
         if constexpr (RING3) {
           // the slice the NEXT step reads was issued a step ago: everything older than this step's NP pieces must have landed (the halo loads of tap 0,
           // issued in front of them, included); the staged halo chunk's LDS stores must be out before the barrier publishes them
@@ -577,8 +560,8 @@ __global__ __launch_bounds__(256, BN > 128 ? 1 : 2) void conv3x3w_kernel(const C
           else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
           __builtin_amdgcn_s_barrier();
         } else __syncthreads();   // drains this step's weight DMA (vmcnt(0)) and publishes it
-        WSTAMP(s3);
-        WACC(1, s1 - s0); WACC(2, s2 - s1); WACC(3, s3 - s2); WACC(4, 1); WACC(8 + T, s2 - s1); WACC(20 + T, s1 - s0);
+        STAMP(s3);
+        STAMP_ACC(1, s1 - s0); STAMP_ACC(2, s2 - s1); STAMP_ACC(3, s3 - s2); STAMP_ACC(4, 1); STAMP_ACC(8 + T, s2 - s1); STAMP_ACC(20 + T, s1 - s0);
       });
       sp ^= (unsigned)(NTAPS & 1);
     };
@@ -587,9 +570,9 @@ __global__ __launch_bounds__(256, BN > 128 ? 1 : 2) void conv3x3w_kernel(const C
   };
   if (GN && silu) { if (par) run(std::true_type{}, std::true_type{}); else run(std::false_type{}, std::true_type{}); }
   else { if (par) run(std::true_type{}, std::false_type{}); else run(std::false_type{}, std::false_type{}); }
-#ifdef C3W_STAMPS
-  { WSTAMP(w_t1); wdbg[0] = w_t1 - w_t0; }   // kernel start -> end of the main loop (set-up and the first halo / weight round trip included; the epilogue is not)
-  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) for (int i = 0; i < 32; ++i) c3w_dbg[i] = wdbg[i];
+#ifdef LDIFF_STAMPS
+  { STAMP(w_t1); dbg[0] = w_t1 - w_t0; }   // kernel start -> end of the main loop (set-up and the first halo / weight round trip included; the epilogue is not)
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) for (int i = 0; i < 32; ++i) c3w_dbg[i] = dbg[i];
 #endif
 
   if (S > 1) {   // raw fp32 partial sums; bias / time embedding / residual are applied by splitk_reduce_kernel
@@ -985,7 +968,7 @@ void launch_conv3x3(const ConvParams& p, int bm, int bn, hipStream_t s) {
   }
 }
 
-#ifdef C3W_STAMPS
+#ifdef LDIFF_STAMPS
 extern "C" int ldiff_debug_c3w_stamps(unsigned long long* out) {   // diagnostic build only
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(c3w_dbg), sizeof(unsigned long long) * 32);
 }

@@ -35,6 +35,7 @@
 // Scope (conv3x3d_selected): one source, Cin % 64 == 0, N % 128 == 0, H, W % 16 == 0, GroupNorm + SiLU prologue, plain fp16 output and
 // residual (no split hi|lo tensors: the staged tile is fp16).  Everything else stays on the kernels of kernels_conv3x3.hip / kernels_conv3x3p.hip.
 #include "lds_prims.h"
+#include "stamps.h"
 #include <map>
 #include <mutex>
 
@@ -60,13 +61,7 @@ constexpr unsigned D_OOR = 0x80000000u;                                // beyond
 constexpr int D_NROUND = 11;                                           // pieces per producer wave and slab: 41 = 4 x 10 + 1
 enum { D_RES = 1, D_STATS = 2, D_SC = 4, D_UPS = 8 };   // D_UPS: nearest-2x upsample folded into the conv (ConvParams::w_par): units per output parity, four taps, raw operand   // D_SC: the folded 1x1 shortcut (ConvParams::xs) -- a flag of its own so that the other instantiations carry none of its code
 
-__device__ __forceinline__ int d_swzx(int hx) { return (0xcb5888 >> (3 * (hx >> 1))) & 7; }   // column swizzle of the halo image (kernels_conv3x3.hip)
-
 // ---- LDS / memory primitives the compiler must not fence or wait for (counted by hand) ----
-template <int CNT>
-__device__ __forceinline__ void lds_wait4(f16x8& a, f16x8& b, f16x8& c, f16x8& d) {
-  asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(CNT));
-}
 template <int CNT>
 __device__ __forceinline__ void vm_wait4(f16x8& a, f16x8& b, f16x8& c, f16x8& d) {
   asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(CNT));
@@ -75,33 +70,11 @@ template <int OFF>
 __device__ __forceinline__ void glb_read128(f16x8& d, const char* addr) {
   asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory");
 }
-__device__ __forceinline__ unsigned flags_min_now(unsigned addr) {   // read four progress words and wait for them
-  u32x4 v;
-  asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
-  const unsigned m = min(min(v[0], v[1]), min(v[2], v[3]));
-  return (unsigned)__builtin_amdgcn_readfirstlane((int)m);
-}
-__device__ __forceinline__ void lds_write32(unsigned addr, unsigned v) { asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory"); }
-__device__ __forceinline__ void lds_write128(unsigned addr, const u32x4& v) { asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory"); }
-// (a __builtin_bit_cast applied directly to a vector ELEMENT expression reads element 0 whatever the index: hipcc 7.2; by value it is fine)
-__device__ __forceinline__ float u2f(unsigned v) { return __builtin_bit_cast(float, v); }
 
 struct UnitC { int b, oy0, ox0, n0, q; };   // q: output parity 2 py + px of a D_UPS unit (else 0)
 
-#ifdef C3D_STAMPS   // diagnostic build only (scripts/conv_stamps_d.py): cycle sums / poll counts of waves 0 and 4 of workgroup 0
+#ifdef LDIFF_STAMPS   // diagnostic build only (stamps.h, scripts/conv_stamps_d.py): cycle sums / poll counts of waves 0 and 4 of workgroup 0
 __device__ unsigned long long c3d_dbg[48];
-__device__ __forceinline__ unsigned long long d_stamp() {
-  __builtin_amdgcn_sched_barrier(0);
-  unsigned long long t = __builtin_amdgcn_s_memtime();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#define DSTAMP(v) const unsigned long long v = d_stamp()
-#define DACC(i, expr) dbg[i] += (expr)
-#else
-#define DSTAMP(v)
-#define DACC(i, expr)
 #endif
 
 template <int FLAGS>
@@ -179,7 +152,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_kernel(const ConvParams p, co
 #pragma unroll
     for (int r = 0; r < D_NROUND; ++r) {
       const int px = (pw + 4 * r) * 8 + (lane >> 3);
-      const int hy = px / D_HWD, hx = px - hy * D_HWD, sz = d_swzx(hx);
+      const int hy = px / D_HWD, hx = px - hy * D_HWD, sz = swzx(hx);
       rc_yx[r] = px < D_HPX ? (unsigned)(hy << 8 | hx) : 0xffffu;
       rc_rel[r] = (unsigned)(((hy * W + hx) * ld1 + ((lane & 7) ^ sz) * 8) * 2);
       rc_lds[r] = lds0 + (unsigned)(px * 128 + (((lane & 7) ^ sz) << 4));
@@ -248,7 +221,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_kernel(const ConvParams p, co
 #if defined(__HIP_DEVICE_COMPILE__)
           if (extra) {
             const int hy = (int)(rc_yx[r] >> 8), hx = (int)(rc_yx[r] & 0xff);
-            if ((sc.vbits >> r) & 1u) voff = ((hy * W + hx) * lds2 + (((lane & 7) ^ d_swzx(hx)) << 3)) * 2;
+            if ((sc.vbits >> r) & 1u) voff = ((hy * W + hx) * lds2 + (((lane & 7) ^ swzx(hx)) << 3)) * 2;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(sc.xrsrc2, (lptr_t*)dst, 16, voff, (sc.c - nslab) * 128, 0, 0);
           } else
             { if (nt) __builtin_amdgcn_raw_ptr_buffer_load_lds(sc.xrsrc, (lptr_t*)dst, 16, voff, sc.c * 128, 0, 2); else __builtin_amdgcn_raw_ptr_buffer_load_lds(sc.xrsrc, (lptr_t*)dst, 16, voff, sc.c * 128, 0, 0); }
@@ -295,7 +268,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_kernel(const ConvParams p, co
       }
     };
 
-#ifdef C3D_STAMPS
+#ifdef LDIFF_STAMPS
     unsigned long long dbg[32] = {0};
 #endif
     // Epilogue of local unit i, from the tile the consumers staged (D_STG + the halo image `hb_last` of the unit's last slab): producer wave
@@ -327,7 +300,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_kernel(const ConvParams p, co
           R[j] = nt ? __builtin_amdgcn_raw_buffer_load_b128(rrsrc, ro, 0, 2) : __builtin_amdgcn_raw_buffer_load_b128(rrsrc, ro, 0, 0);
         }
       }
-      while ((int)flags_min_now(eflags) < i + 1) { __builtin_amdgcn_s_sleep(2); DACC(8, 1); }
+      while ((int)flags_min_now(eflags) < i + 1) { __builtin_amdgcn_s_sleep(2); STAMP_ACC(8, 1); }
       u32x4 U[16];
       {
         const int idx = (e_o >> 1) * 4 + pw;   // chunk of this lane's channel tile
@@ -401,7 +374,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_kernel(const ConvParams p, co
       }
     };
 
-    DSTAMP(p_t0);
+    STAMP(p_t0);
     // Software pipeline over the run's slabs: the pieces of slab k + 1 are in flight while slab k is normalised.  Iteration k is also where
     // the tile of the unit whose LAST slab was k - 2 is stored (nslab >= 2: at most every other iteration): its staged rows occupy image
     // (k + 1) % 3, the one slab k + 1 goes to, so that slab's pieces are issued behind the stores instead of in front of the transform --
@@ -415,27 +388,27 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_kernel(const ConvParams p, co
       advance(nxt);
       const bool store_here = k >= 2 && (k - 1) % nsl == 0;
       int n_next = 0;
-      DSTAMP(q0);
+      STAMP(q0);
       if (!store_here && nxt.k < total_slabs) {
         // image (k + 1) % 3 held slab k - 2: free once every consumer has all of that slab's pixels in registers
-        while ((int)flags_min_now(cflags) < k - 1) { __builtin_amdgcn_s_sleep(2); DACC(5, 1); }
+        while ((int)flags_min_now(cflags) < k - 1) { __builtin_amdgcn_s_sleep(2); STAMP_ACC(5, 1); }
         n_next = issue_slab(nxt);
       }
-      DSTAMP(q1);
+      STAMP(q1);
       // slab k's pieces are older than everything just issued: leave exactly those in flight
       if (n_next >= 15) asm volatile("s_waitcnt vmcnt(15)" ::: "memory");
       else if (n_next >= 14) asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
       else if (n_next >= 13) asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
       else if (n_next >= 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      DSTAMP(q2);
+      STAMP(q2);
 #ifndef C3D_ABL_NOXF
       if constexpr (!UPS)   // (D_UPS: the conv behind an Upsample2D has no GroupNorm in front of it -- raw operand; zero padding = the DMA's zeros)
         if ((FLAGS & D_SC) == 0 || cur.c < nslab) xform_slab(cur);   // (a slab of the folded shortcut is a raw operand)
 #endif
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       lds_write32(pflag_addr, (unsigned)k + 1u);
-      DSTAMP(q3);
+      STAMP(q3);
       if (store_here) {
         const int i = (k - 1) / nsl - 1;
 #ifndef C3D_ABL_NOSTORE
@@ -445,20 +418,20 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_kernel(const ConvParams p, co
 #endif
         stored = i + 1;
         if (nxt.k < total_slabs) {
-          while ((int)flags_min_now(dflags) < i + 1) { __builtin_amdgcn_s_sleep(1); DACC(9, 1); }   // every producer has its part of the staged tile in registers
+          while ((int)flags_min_now(dflags) < i + 1) { __builtin_amdgcn_s_sleep(1); STAMP_ACC(9, 1); }   // every producer has its part of the staged tile in registers
           issue_slab(nxt);
         }
       }
-      DSTAMP(q4);
-      DACC(1, q1 - q0); DACC(2, q2 - q1); DACC(3, q3 - q2); DACC(4, q4 - q3); DACC(6, 1);
+      STAMP(q4);
+      STAMP_ACC(1, q1 - q0); STAMP_ACC(2, q2 - q1); STAMP_ACC(3, q3 - q2); STAMP_ACC(4, q4 - q3); STAMP_ACC(6, 1);
       cur = nxt;
     }
 #ifndef C3D_ABL_NOSTORE
     for (int i = stored; i < n_u; ++i) store_unit(i, (unsigned)(((i + 1) * nsl - 1) % D_NBUF) * D_HB);   // the last unit (one-slab units: the last two)
 #endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef C3D_STAMPS
-    { DSTAMP(p_t2); dbg[7] = p_t2 - p_t0; if (blockIdx.x == 0 && pw == 0 && lane == 0) for (int i = 0; i < 32; ++i) c3d_dbg[16 + i] = dbg[i]; }
+#ifdef LDIFF_STAMPS
+    { STAMP(p_t2); dbg[7] = p_t2 - p_t0; if (blockIdx.x == 0 && pw == 0 && lane == 0) for (int i = 0; i < 32; ++i) c3d_dbg[16 + i] = dbg[i]; }
 #endif
     return;
   }
@@ -470,7 +443,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_kernel(const ConvParams p, co
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
     const int hx = l15 + j;
-    xb[j] = lds0 + (unsigned)(((wave_m * 8) * D_HWD + hx) * 128 + ((g ^ d_swzx(hx)) << 4));
+    xb[j] = lds0 + (unsigned)(((wave_m * 8) * D_HWD + hx) * 128 + ((g ^ swzx(hx)) << 4));
   }
   const unsigned pflags = lds0 + D_FLAGS;
   const unsigned cflag_addr = lane == 0 ? lds0 + D_FLAGS + 16u + (unsigned)wave * 4u : lds0 + D_DUMP + (unsigned)wave * 256u + (unsigned)lane * 4u;
@@ -484,7 +457,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_kernel(const ConvParams p, co
 #endif
   const long long w_step_bytes = (long long)ntn * 16384;   // from slab c to slab c + 1 of a tap; a tap is nslab of these
 
-#ifdef C3D_STAMPS
+#ifdef LDIFF_STAMPS
   unsigned long long dbg[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
   f32x4 acc[4][8];
@@ -561,7 +534,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_kernel(const ConvParams p, co
       }
   };
   auto wait_producers = [&](unsigned need) __attribute__((always_inline)) {
-    while (flags_min_now(pflags) < need) { DACC(1, 1); }
+    while (flags_min_now(pflags) < need) { STAMP_ACC(1, 1); }
   };
 
   // End of a unit: the consumer only ROUNDS its sums to fp16 and hands them to the producers through LDS (store_unit above) -- 16 ds_write_b128
@@ -574,8 +547,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_kernel(const ConvParams p, co
   const unsigned cflags_all = lds0 + D_FLAGS + 16u, dflags = lds0 + D_FLAGS + 48u;
   const unsigned eflag_addr = lane == 0 ? lds0 + D_FLAGS + 32u + (unsigned)wave * 4u : lds0 + D_DUMP + (unsigned)wave * 256u + (unsigned)lane * 4u;
   auto stage_ready = [&](int i, unsigned slabs_done) __attribute__((always_inline)) {
-    while ((int)flags_min_now(dflags) < i) { DACC(7, 1); }
-    while (flags_min_now(cflags_all) < slabs_done) { DACC(8, 1); }
+    while ((int)flags_min_now(dflags) < i) { STAMP_ACC(7, 1); }
+    while (flags_min_now(cflags_all) < slabs_done) { STAMP_ACC(8, 1); }
   };
   auto stage_tile = [&](int i, unsigned hb_last) __attribute__((always_inline)) {   // straight-line: the next unit's weights are in flight across it
     if (!UPS && p.out_shift) {   // range shift (ConvParams::out_shift; never on an upsampling unit): the sums start at bias + temb, so this is (sum + bias + temb) * 2^-k; a uniform branch, nothing at k = 0
@@ -618,7 +591,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_kernel(const ConvParams p, co
     }
   };
 
-  DSTAMP(c_t0);
+  STAMP(c_t0);
   // ---- prologue ----
   UnitC cur = decode(u0);
   {   // the first unit's bias + time embedding straight from memory
@@ -637,8 +610,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_kernel(const ConvParams p, co
   if constexpr (UPS) set_parity(cur);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (nothing of the compiler's may be younger than the hand-counted loads below)
   wait_producers(1u);
-  DSTAMP(c_t1);
-  DACC(0, c_t1 - c_t0);
+  STAMP(c_t1);
+  STAMP_ACC(0, c_t1 - c_t0);
   if constexpr (UPS) issue_xb(ic_t<0>{}, ic_t<0>{}, ic_t<0>{}, ub[0], X[0]);
   else issue_x(ic_t<0>{}, ic_t<0>{}, ic_t<0>{}, ic_t<0>{}, 0u, X[0]);
   issue_w(ic_t<0>{}, wq);
@@ -661,28 +634,28 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_kernel(const ConvParams p, co
           const unsigned xc = ub[tx] + hb;
           issue_w(ic_t<1>{}, wq);
           issue_xb(ic_t<1>{}, ic_t<ty>{}, ic_t<0>{}, xc, X[1]);
-          lds_wait4<4>(X[0][0], X[0][1], X[0][2], X[0][3]);
+          lds_wait<4>(X[0][0], X[0][1], X[0][2], X[0][3]);
           vm_wait4<4>(Wf[0][0], Wf[0][1], Wf[0][2], Wf[0][3]);
           mfma16(ic_t<0>{}, ic_t<0>{}, X[0]);
           __builtin_amdgcn_sched_barrier(0);
           issue_xb(ic_t<0>{}, ic_t<ty>{}, ic_t<1>{}, xc, X[0]);
-          lds_wait4<4>(X[1][0], X[1][1], X[1][2], X[1][3]);
+          lds_wait<4>(X[1][0], X[1][1], X[1][2], X[1][3]);
           mfma16(ic_t<0>{}, ic_t<1>{}, X[1]);
           __builtin_amdgcn_sched_barrier(0);
           issue_w(ic_t<0>{}, wn);
           issue_xb(ic_t<1>{}, ic_t<ty>{}, ic_t<1>{}, xc, X[1]);
-          lds_wait4<4>(X[0][0], X[0][1], X[0][2], X[0][3]);
+          lds_wait<4>(X[0][0], X[0][1], X[0][2], X[0][3]);
           vm_wait4<4>(Wf[1][0], Wf[1][1], Wf[1][2], Wf[1][3]);
           mfma16(ic_t<1>{}, ic_t<0>{}, X[0]);
           __builtin_amdgcn_sched_barrier(0);
           if constexpr (T == 3) {
-            lds_wait4<0>(X[1][0], X[1][1], X[1][2], X[1][3]);
+            lds_wait<0>(X[1][0], X[1][1], X[1][2], X[1][3]);
             lds_write32(cflag_addr, (unsigned)k + 1u);
-            if (!last_slab) { DACC(2, 1); wait_producers((unsigned)k + 2u); }
+            if (!last_slab) { STAMP_ACC(2, 1); wait_producers((unsigned)k + 2u); }
             issue_xb(ic_t<0>{}, ic_t<0>{}, ic_t<0>{}, ub[0] + hbn, X[0]);
           } else {
             issue_xb(ic_t<0>{}, ic_t<nty>{}, ic_t<0>{}, ub[ntx] + hb, X[0]);
-            lds_wait4<4>(X[1][0], X[1][1], X[1][2], X[1][3]);
+            lds_wait<4>(X[1][0], X[1][1], X[1][2], X[1][3]);
           }
           mfma16(ic_t<1>{}, ic_t<1>{}, X[1]);
           __builtin_amdgcn_sched_barrier(0);
@@ -698,18 +671,18 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_kernel(const ConvParams p, co
         // ---- k-half 0 ----
         issue_w(ic_t<1>{}, wq);
         issue_x(ic_t<1>{}, ic_t<ky>{}, ic_t<kx>{}, ic_t<0>{}, hb, X[1]);
-        lds_wait4<4>(X[0][0], X[0][1], X[0][2], X[0][3]);
+        lds_wait<4>(X[0][0], X[0][1], X[0][2], X[0][3]);
         vm_wait4<4>(Wf[0][0], Wf[0][1], Wf[0][2], Wf[0][3]);
         mfma16(ic_t<0>{}, ic_t<0>{}, X[0]);
         __builtin_amdgcn_sched_barrier(0);
         issue_x(ic_t<0>{}, ic_t<ky>{}, ic_t<kx>{}, ic_t<1>{}, hb, X[0]);
-        lds_wait4<4>(X[1][0], X[1][1], X[1][2], X[1][3]);
+        lds_wait<4>(X[1][0], X[1][1], X[1][2], X[1][3]);
         mfma16(ic_t<0>{}, ic_t<1>{}, X[1]);
         __builtin_amdgcn_sched_barrier(0);
         // ---- k-half 1 ----
         issue_w(ic_t<0>{}, wn);
         issue_x(ic_t<1>{}, ic_t<ky>{}, ic_t<kx>{}, ic_t<1>{}, hb, X[1]);
-        lds_wait4<4>(X[0][0], X[0][1], X[0][2], X[0][3]);
+        lds_wait<4>(X[0][0], X[0][1], X[0][2], X[0][3]);
         vm_wait4<4>(Wf[1][0], Wf[1][1], Wf[1][2], Wf[1][3]);
         mfma16(ic_t<1>{}, ic_t<0>{}, X[0]);
         __builtin_amdgcn_sched_barrier(0);
@@ -717,14 +690,14 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_kernel(const ConvParams p, co
           // every pixel of slab k is in registers once the last group has landed: its image is free.  The next slab (if it is this unit's)
           // must be complete before its first rows are read; at a unit's last step the same reads go out unchecked and unused (one code
           // path, no join for the register allocator), and the next unit's first operands are issued again behind the epilogue.
-          lds_wait4<0>(X[1][0], X[1][1], X[1][2], X[1][3]);
+          lds_wait<0>(X[1][0], X[1][1], X[1][2], X[1][3]);
           lds_write32(cflag_addr, (unsigned)k + 1u);
-          if (!last_slab) { DACC(2, 1); wait_producers((unsigned)k + 2u); }
+          if (!last_slab) { STAMP_ACC(2, 1); wait_producers((unsigned)k + 2u); }
           if (to_extra) issue_x(ic_t<0>{}, ic_t<1>{}, ic_t<1>{}, ic_t<0>{}, hbn, X[0]);
           else issue_x(ic_t<0>{}, ic_t<0>{}, ic_t<0>{}, ic_t<0>{}, hbn, X[0]);
         } else {
           issue_x(ic_t<0>{}, ic_t<nky>{}, ic_t<nkx>{}, ic_t<0>{}, hb, X[0]);
-          lds_wait4<4>(X[1][0], X[1][1], X[1][2], X[1][3]);
+          lds_wait<4>(X[1][0], X[1][1], X[1][2], X[1][3]);
         }
         mfma16(ic_t<1>{}, ic_t<1>{}, X[1]);
         __builtin_amdgcn_sched_barrier(0);
@@ -739,30 +712,30 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_kernel(const ConvParams p, co
       const char* wn = wq + w_step_bytes;   // the next slab's block (behind the last one: padding, loaded and unused)
       issue_w(ic_t<1>{}, wq);
       issue_x(ic_t<1>{}, ic_t<1>{}, ic_t<1>{}, ic_t<0>{}, hb, X[1]);
-      lds_wait4<4>(X[0][0], X[0][1], X[0][2], X[0][3]);
+      lds_wait<4>(X[0][0], X[0][1], X[0][2], X[0][3]);
       vm_wait4<4>(Wf[0][0], Wf[0][1], Wf[0][2], Wf[0][3]);
       mfma16(ic_t<0>{}, ic_t<0>{}, X[0]);
       __builtin_amdgcn_sched_barrier(0);
       issue_x(ic_t<0>{}, ic_t<1>{}, ic_t<1>{}, ic_t<1>{}, hb, X[0]);
-      lds_wait4<4>(X[1][0], X[1][1], X[1][2], X[1][3]);
+      lds_wait<4>(X[1][0], X[1][1], X[1][2], X[1][3]);
       mfma16(ic_t<0>{}, ic_t<1>{}, X[1]);
       __builtin_amdgcn_sched_barrier(0);
       issue_w(ic_t<0>{}, wn);
       issue_x(ic_t<1>{}, ic_t<1>{}, ic_t<1>{}, ic_t<1>{}, hb, X[1]);
-      lds_wait4<4>(X[0][0], X[0][1], X[0][2], X[0][3]);
+      lds_wait<4>(X[0][0], X[0][1], X[0][2], X[0][3]);
       vm_wait4<4>(Wf[1][0], Wf[1][1], Wf[1][2], Wf[1][3]);
       mfma16(ic_t<1>{}, ic_t<0>{}, X[0]);
       __builtin_amdgcn_sched_barrier(0);
-      lds_wait4<0>(X[1][0], X[1][1], X[1][2], X[1][3]);
+      lds_wait<0>(X[1][0], X[1][1], X[1][2], X[1][3]);
       lds_write32(cflag_addr, (unsigned)k + 1u);
-      if (!last_slab) { DACC(2, 1); wait_producers((unsigned)k + 2u); }
+      if (!last_slab) { STAMP_ACC(2, 1); wait_producers((unsigned)k + 2u); }
       issue_x(ic_t<0>{}, ic_t<1>{}, ic_t<1>{}, ic_t<0>{}, hbn, X[0]);
       mfma16(ic_t<1>{}, ic_t<1>{}, X[1]);
       __builtin_amdgcn_sched_barrier(0);
       wq = wn;
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // the unused operands of the unit's last step
-    DSTAMP(e0);
+    STAMP(e0);
     UnitC nxt = cur;
     if (has_next) nxt = decode(u + 1);
     wq = wbase(nxt);
@@ -774,20 +747,20 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_kernel(const ConvParams p, co
     lds_write32(eflag_addr, (unsigned)(u - u0) + 1u);
 #endif
     vm_wait4<0>(Wf[0][0], Wf[0][1], Wf[0][2], Wf[0][3]);   // landed long ago; nothing asynchronous is live across the polls below
-    DSTAMP(e1);
-    DACC(3, e1 - e0); DACC(4, 1);
+    STAMP(e1);
+    STAMP_ACC(3, e1 - e0); STAMP_ACC(4, 1);
     if (has_next) {
       wait_producers((unsigned)k + 1u);                 // the next unit's first slab (and with it the bias table producer wave 0 issued in front of it)
       init_from_table((u + 1 - u0) & 1);
-      DSTAMP(e2);
-      DACC(5, e2 - e1);
+      STAMP(e2);
+      STAMP_ACC(5, e2 - e1);
       if constexpr (UPS) { set_parity(nxt); issue_xb(ic_t<0>{}, ic_t<0>{}, ic_t<0>{}, ub[0] + (unsigned)(k % D_NBUF) * D_HB, X[0]); }
       else issue_x(ic_t<0>{}, ic_t<0>{}, ic_t<0>{}, ic_t<0>{}, (unsigned)(k % D_NBUF) * D_HB, X[0]);
       cur = nxt;
     }
   }
-#ifdef C3D_STAMPS
-  { DSTAMP(c_t2); dbg[6] = c_t2 - c_t0; if (blockIdx.x == 0 && wave == 0 && lane == 0) for (int i = 0; i < 16; ++i) c3d_dbg[i] = dbg[i]; }
+#ifdef LDIFF_STAMPS
+  { STAMP(c_t2); dbg[6] = c_t2 - c_t0; if (blockIdx.x == 0 && wave == 0 && lane == 0) for (int i = 0; i < 16; ++i) c3d_dbg[i] = dbg[i]; }
 #endif
 }
 
@@ -947,7 +920,7 @@ size_t conv3x3d_frag_bytes(const ConvParams& p) {
   return (size_t)p.N * (9 * p.C1 + p.Cs) * sizeof(f16) + (p.Cs ? (size_t)(p.N >> 7) * 16384 + 16384 : 0);
 }
 int conv3x3d_stats_blocks(const ConvParams& p) { return p.ups ? (p.Hin >> 4) * (p.Win >> 4) * 8 : (p.Hout >> 4) * (p.Wout >> 4) * 2; }   // one row block per consumer wave pair (8 x 16 pixels)
-#ifdef C3D_STAMPS
+#ifdef LDIFF_STAMPS
 extern "C" int ldiff_debug_c3d_stamps(unsigned long long* out) {   // diagnostic build only
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(c3d_dbg), sizeof(unsigned long long) * 48);
 }

@@ -14,7 +14,6 @@
 
 namespace {
 
-__device__ __forceinline__ float silu_f(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.4426950408889634f)); }
 
 // grid: workgroups that each walk tiles blockIdx.x, blockIdx.x + gridDim.x, ... (8 x 16 output pixels of one image; neighbours in the grid work
 // on neighbouring tiles at the same time: their halos meet in L2); block 256 = 4 waves, wave w owns pixels [32w, 32w + 32) of the tile (two
@@ -169,21 +168,12 @@ __global__ __launch_bounds__(256, 3) void conv3x3n_kernel(const ConvParams p, co
             if (p.out_f32) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.y) + row * p.ldy) = v;
             else *reinterpret_cast<f16x4*>(reinterpret_cast<f16*>(p.y) + row * p.ldy) = cvt4(v);
           }
-          if (p.post_img || p.post_rgb || p.post_luma) {   // the decode_latents tail on the fp32 sums, operation for operation as decode_post_kernel
-            unsigned q[3];
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-              float u = __fadd_rn(__fmul_rn(v[ch], 0.5f), 0.5f);
-              u = fminf(fmaxf(u, 0.f), 1.f);
-              if (v[ch] != v[ch]) u = v[ch];   // clamp propagates NaN in torch
-              if (p.post_img) p.post_img[row * 3 + ch] = u;
-              q[ch] = (unsigned)(int)rintf(__fmul_rn(u, 255.0f));
-            }
-            if (p.post_rgb) { p.post_rgb[row * 3 + 0] = (uint8_t)q[0]; p.post_rgb[row * 3 + 1] = (uint8_t)q[1]; p.post_rgb[row * 3 + 2] = (uint8_t)q[2]; }
+          if (p.post_img || p.post_rgb || p.post_luma) {   // the decode_latents tail on the fp32 sums
+            const float sums[3] = {v[0], v[1], v[2]};
+            const DecodedPx px = decode_tail(sums, row, p.post_img, p.post_rgb);
             if (p.post_luma) {
               const long long hw = (long long)p.Hout * p.Wout;
-              p.post_luma[((long long)cur.b * p.post_slots + p.post_slot) * hw + (long long)oy * p.Wout + ox] =
-                  (uint8_t)((19595u * q[0] + 38470u * q[1] + 7471u * q[2] + 0x8000u) >> 16);
+              p.post_luma[((long long)cur.b * p.post_slots + p.post_slot) * hw + (long long)oy * p.Wout + ox] = px.luma();
             }
           }
         }
@@ -351,21 +341,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3nt_kernel(const ConvParams p, c
           if (p.out_f32) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.y) + row * p.ldy) = v;
           else *reinterpret_cast<f16x4*>(reinterpret_cast<f16*>(p.y) + row * p.ldy) = cvt4(v);
         }
-        if (p.post_img || p.post_rgb || p.post_luma) {   // the decode_latents tail on the fp32 sums, operation for operation as decode_post_kernel
-          unsigned q[3];
-#pragma unroll
-          for (int ch = 0; ch < 3; ++ch) {
-            float u = __fadd_rn(__fmul_rn(v[ch], 0.5f), 0.5f);
-            u = fminf(fmaxf(u, 0.f), 1.f);
-            if (v[ch] != v[ch]) u = v[ch];   // clamp propagates NaN in torch
-            if (p.post_img) p.post_img[row * 3 + ch] = u;
-            q[ch] = (unsigned)(int)rintf(__fmul_rn(u, 255.0f));
-          }
-          if (p.post_rgb) { p.post_rgb[row * 3 + 0] = (uint8_t)q[0]; p.post_rgb[row * 3 + 1] = (uint8_t)q[1]; p.post_rgb[row * 3 + 2] = (uint8_t)q[2]; }
+        if (p.post_img || p.post_rgb || p.post_luma) {   // the decode_latents tail on the fp32 sums
+          const float sums[3] = {v[0], v[1], v[2]};
+          const DecodedPx px = decode_tail(sums, row, p.post_img, p.post_rgb);
           if (p.post_luma) {
             const long long hw = (long long)p.Hout * p.Wout;
-            p.post_luma[((long long)cur.b * p.post_slots + p.post_slot) * hw + (long long)oy * p.Wout + ox] =
-                (uint8_t)((19595u * q[0] + 38470u * q[1] + 7471u * q[2] + 0x8000u) >> 16);
+            p.post_luma[((long long)cur.b * p.post_slots + p.post_slot) * hw + (long long)oy * p.Wout + ox] = px.luma();
           }
         }
       }

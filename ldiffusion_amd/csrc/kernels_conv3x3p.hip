@@ -41,48 +41,21 @@
 #include <mutex>
 
 #include "lds_prims.h"
+#include "stamps.h"
 
 namespace {
 
-__device__ __forceinline__ float silu_f(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.4426950408889634f)); }
-
-// LDS accesses the compiler must not see as such: it orders every LDS access it knows of behind ALL pending vector-memory operations
-// when an LDS-DMA may be among them (s_waitcnt vmcnt(0)), which after the epilogue's stores means a full write round trip
-template <int OFF>
-__device__ __forceinline__ void lds_read128f(f32x4& d, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory");
-}
-__device__ __forceinline__ void lds_wait0(f32x4& a, f32x4& b, f32x4& c, f32x4& d) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
-}
-__device__ __forceinline__ void lds_write64(unsigned addr, float2 v) {
-  asm volatile("ds_write_b64 %0, %1" :: "v"(addr), "v"(v) : "memory");
-}
 // end of a load segment: the LDS accesses of this wave are done, its LDS-DMAs and global loads stay in flight
 __device__ __forceinline__ void lgkm_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 // end of a matrix segment: everything this wave issued one segment ago (LDS-DMA weight rows and halo pieces) has landed.  Explicit:
 // __syncthreads() alone does not drain LDS-DMA (a workgroup-scope fence needs no vmcnt wait on this target).
 __device__ __forceinline__ void full_barrier() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// column swizzle of the halo image (kernels_conv3x3.hip): conflict-free 16x16x32 operand fetch at all three column shifts
-__device__ __forceinline__ int swzx(int hx) { return (0xcb5888 >> (3 * (hx >> 1))) & 7; }
 // lane-invariant values recomputed per tile: keep the optimiser from hoisting them out of the persistent loop (each one would
 // occupy a register for the whole kernel)
 __device__ __forceinline__ int opaque(int v) { asm volatile("" : "+v"(v)); return v; }
 
-#ifdef C3P_STAMPS   // diagnostic build only (scripts/conv_stamps.py): per-segment cycle sums of waves 0 and 4 of workgroup 0
+#ifdef LDIFF_STAMPS   // diagnostic build only (stamps.h, scripts/conv_stamps.py): per-segment cycle sums of waves 0 and 4 of workgroup 0
 __device__ unsigned long long c3p_dbg[2][16];
-__device__ __forceinline__ unsigned long long stamp() {
-  __builtin_amdgcn_sched_barrier(0);
-  unsigned long long t = __builtin_amdgcn_s_memtime();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#define STAMP(v) const unsigned long long v = stamp()
-#define ACCUM(i, a, b) dbg[i] += (b) - (a)
-#else
-#define STAMP(v)
-#define ACCUM(i, a, b)
 #endif
 struct TileC { int b, oy0, ox0, n0, q; };   // image, pixel origin (tile space), first output channel, output parity (parity mode)
 
@@ -283,9 +256,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3p_kernel(const ConvParams p, co
     static_for<0, NT / 2>([&](auto hc) {
       constexpr int a0 = decltype(hc)::value * 2;
       f32x4 b0, b1, t0, t1;
-      lds_read128f<a0 * 64>(b0, tb); lds_read128f<a0 * 64 + 64>(b1, tb);
-      lds_read128f<BN * 4 + a0 * 64>(t0, tb); lds_read128f<BN * 4 + a0 * 64 + 64>(t1, tb);
-      lds_wait0(b0, b1, t0, t1);
+      lds_read128<a0 * 64>(b0, tb); lds_read128<a0 * 64 + 64>(b1, tb);
+      lds_read128<BN * 4 + a0 * 64>(t0, tb); lds_read128<BN * 4 + a0 * 64 + 64>(t1, tb);
+      lds_wait<0>(b0, b1, t0, t1);
 #pragma unroll
       for (int m = 0; m < MT; ++m) { acc[a0][m] = b0 + t0; acc[a0 + 1][m] = b1 + t1; }
     });
@@ -445,7 +418,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3p_kernel(const ConvParams p, co
   if (grp) lgkm_barrier();   // group B runs one phase behind
 
   unsigned sp = 0, hb = 0;   // ring slot of the slab's tap 0; halo image of the slab
-#ifdef C3P_STAMPS
+#ifdef LDIFF_STAMPS
   unsigned long long dbg[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
   // The step loop.  ONE code block for every slab (tile-first / tile-last / last of the workgroup are uniform run-time flags): three
@@ -523,7 +496,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3p_kernel(const ConvParams p, co
       // end of the matrix segment: this wave's DMAs issued one segment ago have landed (vmcnt(0)) and are published.
       // Group B's very last matrix segment needs neither (nothing follows it but its epilogue).
       STAMP(t1);
-#ifdef C3P_STAMPS
+#ifdef LDIFF_STAMPS
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       STAMP(t1b);
       dbg[14] += t1b - t1;
@@ -557,8 +530,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3p_kernel(const ConvParams p, co
           STAMP(e1);
           if (stage) { cur = nxt; if (PAR) set_xb(cur); init_acc(); }
           STAMP(e2);
-          ACCUM(8, e0, e1); ACCUM(9, e1, e2); ACCUM(11, t2, e0);
-#ifdef C3P_STAMPS
+          STAMP_ACC(8, e1 - e0); STAMP_ACC(9, e2 - e1); STAMP_ACC(11, e0 - t2);
+#ifdef LDIFF_STAMPS
           dbg[12] = e2;
 #endif
         }
@@ -602,8 +575,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3p_kernel(const ConvParams p, co
       if (!final) lgkm_barrier();
       __builtin_amdgcn_sched_barrier(0);
       STAMP(t4);
-      ACCUM(0, t0, t1); ACCUM(1, t1, t2); ACCUM(2, t2, t3); ACCUM(3, t3, t4);
-#ifdef C3P_STAMPS
+      STAMP_ACC(0, t1 - t0); STAMP_ACC(1, t2 - t1); STAMP_ACC(2, t3 - t2); STAMP_ACC(3, t4 - t3);
+#ifdef LDIFF_STAMPS
       dbg[4] += 1; if (T == 0) { dbg[5] += t3 - t2; } if (LAST && tlast) { dbg[6] += t3 - t2; dbg[7] += 1; dbg[10] += t3 - dbg[12]; }
       if (T == 3) dbg[13] += t3 - t2;
 #endif
@@ -632,7 +605,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3p_kernel(const ConvParams p, co
     }
   }
 
-#ifdef C3P_STAMPS
+#ifdef LDIFF_STAMPS
   if (blockIdx.x == 0 && (wave & 3) == 0 && lane == 0)
     for (int i = 0; i < 16; ++i) c3p_dbg[grp][i] = dbg[i];
 #endif
@@ -736,7 +709,7 @@ void launch_conv3x3p(const ConvParams& p, hipStream_t s) {
   else c3p_dispatch<128, false>(p, s, std::integer_sequence<int, 0, 1, 2, 3, 4, 5, 6, 7, 15>{});
 }
 
-#ifdef C3P_STAMPS
+#ifdef LDIFF_STAMPS
 extern "C" int ldiff_debug_c3p_stamps(unsigned long long* out) {   // diagnostic build only
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(c3p_dbg), sizeof(unsigned long long) * 32);
 }

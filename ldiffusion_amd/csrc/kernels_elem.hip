@@ -266,28 +266,16 @@ void launch_scale_f32(const float* x, float* y, float a, long long n, hipStream_
   HIP_CHECK(hipGetLastError());
 }
 
-// ---- decode post-process + uint8 + luma feature slot --------------------------------------------
-// decode_latents tail  (x/2+0.5).clamp(0,1)                       -> img_f32 [B,H,W,3]   (segmentor.py:106)
-// numpy_to_pil         (img*255).round().astype(uint8), half-even -> rgb_u8  [B,H,W,3]   (segmentor.py:107)
-// PIL convert("L")     (19595R + 38470G + 7471B + 0x8000) >> 16   -> luma[b, slot, h, w] (pixel_latent_vector.py:85)
+// ---- decode post-process + uint8 + luma feature slot: decode_tail (common.h) per pixel -> img_f32 [B,H,W,3], rgb_u8 [B,H,W,3], luma[b, slot, h, w] ----
 __global__ void decode_post_kernel(const float* __restrict__ x, int ldx, long long npix, int HW, float* __restrict__ img,
                                    uint8_t* __restrict__ rgb, uint8_t* __restrict__ luma, int n_slots, int slot) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= npix) return;
   const float* px = x + i * ldx;
-  unsigned q[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    float v = __fadd_rn(__fmul_rn(px[c], 0.5f), 0.5f);
-    v = fminf(fmaxf(v, 0.f), 1.f);
-    if (px[c] != px[c]) v = px[c];  // clamp propagates NaN in torch
-    if (img) img[i * 3 + c] = v;
-    q[c] = (unsigned)(int)rintf(__fmul_rn(v, 255.0f));
-  }
-  if (rgb) { rgb[i * 3 + 0] = (uint8_t)q[0]; rgb[i * 3 + 1] = (uint8_t)q[1]; rgb[i * 3 + 2] = (uint8_t)q[2]; }
+  const DecodedPx d = decode_tail(px, i, img, rgb);
   if (luma) {
     long long b = i / HW, pix = i - b * HW;
-    luma[(b * n_slots + slot) * HW + pix] = (uint8_t)((19595u * q[0] + 38470u * q[1] + 7471u * q[2] + 0x8000u) >> 16);
+    luma[(b * n_slots + slot) * HW + pix] = d.luma();
   }
 }
 void launch_decode_post(const float* x, int ldx, int B, int H, int W, float* img_f32, uint8_t* rgb_u8, uint8_t* luma, int n_slots, int slot,

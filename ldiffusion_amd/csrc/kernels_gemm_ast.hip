@@ -28,28 +28,6 @@
 
 namespace {
 
-template <int I, int N, class F>
-__device__ __forceinline__ void sfor(F&& f) {
-  if constexpr (I < N) { f(std::integral_constant<int, I>{}); sfor<I + 1, N>(f); }
-}
-// LDS traffic as inline asm with counted waits: hipcc would put s_waitcnt vmcnt(0) in front of plain LDS reads while an LDS-DMA is in flight
-// (it cannot prove they do not alias the DMA's destination) and lgkmcnt(0) in front of every MFMA group.
-template <int OFF>
-__device__ __forceinline__ void lds_read128u(uint4& d, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory");
-}
-template <int OFF>
-__device__ __forceinline__ void lds_read128f(float4& d, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory");
-}
-template <int OFF>
-__device__ __forceinline__ void lds_write64(unsigned addr, const uint2& v) {
-  asm volatile("ds_write_b64 %0, %1 offset:%2" : : "v"(addr), "v"(v), "n"(OFF) : "memory");
-}
-template <int CNT>
-__device__ __forceinline__ void lds_wait4(f16x8& a, f16x8& b, f16x8& c, f16x8& d) {
-  asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(CNT));
-}
 __device__ __forceinline__ void lds_wait_all() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 struct LnGemmParams {
@@ -124,7 +102,7 @@ __global__ __launch_bounds__(NW * 64, 1) void lngemm_kernel(const LnGemmParams p
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lptr_t*)(smem + buf * PANEL + wave * (PPW * 1024) + j * 1024), 16, w_voff + j * 1024, chunk * (BN * C * 2), 0, 0);
 #endif
   };
-  auto issue_w = [&](int chunk, int buf) { sfor<0, PPW>([&](auto jc) { issue_piece(chunk, buf, jc); }); };
+  auto issue_w = [&](int chunk, int buf) { static_for<0, PPW>([&](auto jc) { issue_piece(chunk, buf, jc); }); };
   // ---- gamma / beta / this split's bias -> LDS (plain stores, then a barrier with no LDS-DMA in flight yet) ----
   float* vec = reinterpret_cast<float*>(smem + VEC);
   for (int i = tid; i < C; i += NW * 64) { vec[i] = p.gamma[i]; vec[C + i] = p.beta[i]; }
@@ -206,7 +184,7 @@ __global__ __launch_bounds__(NW * 64, 1) void lngemm_kernel(const LnGemmParams p
     constexpr int s = decltype(sc)::value;
     if constexpr (s == 0) {
       const unsigned bva = lds0 + VEC + (unsigned)(2 * C + (chunk - c0) * BN + g * 4) * 4;   // this lane's bias columns
-      sfor<0, NT>([&](auto ac) { constexpr int a = decltype(ac)::value; lds_read128f<a * 64>(bq[a], bva); });
+      static_for<0, NT>([&](auto ac) { constexpr int a = decltype(ac)::value; lds_read128<a * 64>(bq[a], bva); });
     } else if constexpr (!GEGLU) {
       if constexpr (s >= 1 && s <= 4) {                   // two 16 x 16 tiles per piece
 #pragma unroll
@@ -222,7 +200,7 @@ __global__ __launch_bounds__(NW * 64, 1) void lngemm_kernel(const LnGemmParams p
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int r = i * 8 + (lane >> 3);
-          lds_read128u<0>(tq[i], stg + r * 128 + (((lane & 7) ^ ((r >> 1) & 7)) << 4));
+          lds_read128<0>(tq[i], stg + r * 128 + (((lane & 7) ^ ((r >> 1) & 7)) << 4));
         }
       } else if constexpr (s == 9) {                      // (the k-loop's wait of step 6 has retired the reads of piece 5; last: behind this iteration's DMA pieces)
 #pragma unroll
@@ -246,7 +224,7 @@ __global__ __launch_bounds__(NW * 64, 1) void lngemm_kernel(const LnGemmParams p
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
           const int r = i * 16 + (lane >> 2);
-          lds_read128u<0>(tq[i], stg + r * 64 + (((lane & 3) ^ ((r >> 1) & 3)) << 4));
+          lds_read128<0>(tq[i], stg + r * 64 + (((lane & 3) ^ ((r >> 1) & 3)) << 4));
         }
       }
     }
@@ -274,16 +252,16 @@ __global__ __launch_bounds__(NW * 64, 1) void lngemm_kernel(const LnGemmParams p
       for (int m = 0; m < MT; ++m) acc[a][m] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const unsigned wa = wa0 + buf * PANEL, wb = wa ^ 64u;
     f16x8 wf[2][NT];
-    sfor<0, NT>([&](auto ac) { constexpr int a = decltype(ac)::value; lds_read128<a * 2048>(wf[0][a], wa); });
-    sfor<0, KS>([&](auto sc) {
+    static_for<0, NT>([&](auto ac) { constexpr int a = decltype(ac)::value; lds_read128<a * 2048>(wf[0][a], wa); });
+    static_for<0, KS>([&](auto sc) {
       constexpr int s = decltype(sc)::value, cur = s & 1, nxt = cur ^ 1;
       if constexpr (s + 1 < KS) {
         constexpr int kt = (s + 1) >> 1;
-        if constexpr (((s + 1) & 1) == 0) sfor<0, NT>([&](auto ac) { constexpr int a = decltype(ac)::value; lds_read128<kt * 8192 + a * 2048>(wf[nxt][a], wa); });
-        else sfor<0, NT>([&](auto ac) { constexpr int a = decltype(ac)::value; lds_read128<kt * 8192 + a * 2048>(wf[nxt][a], wb); });
-        lds_wait4<NT>(wf[cur][0], wf[cur][1], wf[cur][2], wf[cur][3]);   // everything but the NT reads just issued (the previous piece's LDS traffic included)
+        if constexpr (((s + 1) & 1) == 0) static_for<0, NT>([&](auto ac) { constexpr int a = decltype(ac)::value; lds_read128<kt * 8192 + a * 2048>(wf[nxt][a], wa); });
+        else static_for<0, NT>([&](auto ac) { constexpr int a = decltype(ac)::value; lds_read128<kt * 8192 + a * 2048>(wf[nxt][a], wb); });
+        lds_wait<NT>(wf[cur][0], wf[cur][1], wf[cur][2], wf[cur][3]);   // everything but the NT reads just issued (the previous piece's LDS traffic included)
       } else {
-        lds_wait4<0>(wf[cur][0], wf[cur][1], wf[cur][2], wf[cur][3]);
+        lds_wait<0>(wf[cur][0], wf[cur][1], wf[cur][2], wf[cur][3]);
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -325,7 +303,7 @@ __global__ __launch_bounds__(NW * 64, 1) void lngemm_kernel(const LnGemmParams p
     stamp();
   }
   if (c1 > c0) {   // the last panel's epilogue has no matrix work to hide behind
-    sfor<0, KS>([&](auto sc) {
+    static_for<0, KS>([&](auto sc) {
       epi_piece(sc, c1 - 1);
       lds_wait_all();
       __builtin_amdgcn_sched_barrier(0);

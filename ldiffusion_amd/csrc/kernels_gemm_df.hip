@@ -26,6 +26,7 @@
 // optional plain / split residual, optional GEGLU epilogue or fused GroupNorm partial statistics; no per-image weights, no split-K (those stay on
 // gemm_dma_kernel).
 #include "lds_prims.h"
+#include "stamps.h"
 #include <map>
 #include <mutex>
 
@@ -58,8 +59,6 @@ static_assert(F_LDS <= 160 * 1024, "LDS budget of one workgroup per CU");
 constexpr unsigned F_OOR = 0x80000000u;                  // beyond num_records of every descriptor used here
 enum { FG_RES = 1, FG_RES_SPLIT = 2, FG_OUT_SPLIT = 4, FG_GEGLU = 8, FG_STATS = 16 };
 
-template <int CNT>
-__device__ __forceinline__ void lds_wait2(f16x8& a, f16x8& b) { asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(CNT)); }
 // (every register exactly once: a register named twice is COPIED in front of the statement, i.e. read while its load is still in flight)
 __device__ __forceinline__ void vm_wait_frags(f16x8& a) { asm volatile("s_waitcnt vmcnt(1)" : "+v"(a)); }
 __device__ __forceinline__ void vm_wait_frags(f16x8& a, f16x8& b) { asm volatile("s_waitcnt vmcnt(2)" : "+v"(a), "+v"(b)); }
@@ -72,14 +71,6 @@ template <int OFF>
 __device__ __forceinline__ void glb_read128(f16x8& d, unsigned voff, const char* sbase) {
   asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(d) : "v"(voff), "s"(sbase), "n"(OFF) : "memory");
 }
-__device__ __forceinline__ unsigned flags_min_now(unsigned addr) {   // read four progress words and wait for them
-  u32x4 v;
-  asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
-  const unsigned m = min(min(v[0], v[1]), min(v[2], v[3]));
-  return (unsigned)__builtin_amdgcn_readfirstlane((int)m);
-}
-__device__ __forceinline__ void lds_write32(unsigned addr, unsigned v) { asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory"); }
-__device__ __forceinline__ void lds_write128f(unsigned addr, const f32x4& v) { asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory"); }
 __device__ __forceinline__ void vm_wait_n(int n) {   // s_waitcnt vmcnt(n), n uniform at run time (the immediate is an instruction field)
   switch (n) {
 #define VMW(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
@@ -90,22 +81,9 @@ __device__ __forceinline__ void vm_wait_n(int n) {   // s_waitcnt vmcnt(n), n un
     default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
   }
 }
-__device__ __forceinline__ float u2f(unsigned v) { return __builtin_bit_cast(float, v); }
 
-#ifdef GDF_STAMPS   // diagnostic build only (scripts/gemm_df_stamps.py): cycle sums / poll counts of one wave per role of workgroup 0
+#ifdef LDIFF_STAMPS   // diagnostic build only (stamps.h, scripts/gemm_df_stamps.py): cycle sums / poll counts of one wave per role of workgroup 0
 __device__ unsigned long long gdf_dbg[64];
-__device__ __forceinline__ unsigned long long g_stamp() {
-  __builtin_amdgcn_sched_barrier(0);
-  unsigned long long t = __builtin_amdgcn_s_memtime();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#define GSTAMP(v) const unsigned long long v = g_stamp()
-#define GACC(i, expr) dbg[i] += (expr)
-#else
-#define GSTAMP(v)
-#define GACC(i, expr)
 #endif
 
 // MT: 16-row tiles per unit (8 = 128 rows, 4 = 64 rows); NTW: 16-column tiles per consumer wave (a unit has 64 NTW columns);
@@ -193,30 +171,30 @@ __global__ __launch_bounds__(512, 2) void gemm_df_kernel(const ConvParams p, con
       ++issued;
       if (++ikt == nk) { ikt = 0; ++iu; }
     };
-#ifdef GDF_STAMPS
+#ifdef LDIFF_STAMPS
     unsigned long long dbg[16] = {0};
-    GSTAMP(l_t0);
+    STAMP(l_t0);
 #endif
     const int ahead = total < F_S - 1 ? total : F_S - 1;
     for (int k = 0; k < ahead; ++k) issue();
     for (int j = 0; j < total; ++j) {
-      GSTAMP(q0);
+      STAMP(q0);
       vm_wait_n((issued - j - 1) * np);   // step j's pieces are older than the steps issued after it (a bias DMA among those only makes the wait longer)
       lds_write32(pflag_addr, (unsigned)j + 1u);
-      GSTAMP(q1);
+      STAMP(q1);
       if (issued < total) {
         // slot issued % F_S held step issued - F_S: free once every consumer has that step's fragments in registers
-        while ((int)flags_min_now(cflags) < issued - F_S + 1) { __builtin_amdgcn_s_sleep(2); GACC(4, 1); }
-        GSTAMP(q2);
+        while ((int)flags_min_now(cflags) < issued - F_S + 1) { __builtin_amdgcn_s_sleep(2); STAMP_ACC(4, 1); }
+        STAMP(q2);
         issue();
-        GSTAMP(q3);
-        GACC(2, q2 - q1); GACC(3, q3 - q2);
+        STAMP(q3);
+        STAMP_ACC(2, q2 - q1); STAMP_ACC(3, q3 - q2);
       }
-      GACC(1, q1 - q0); GACC(5, 1);
+      STAMP_ACC(1, q1 - q0); STAMP_ACC(5, 1);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef GDF_STAMPS
-    { GSTAMP(l_t1); dbg[0] = l_t1 - l_t0; if (blockIdx.x == 0 && lw == 0 && lane == 0) for (int i = 0; i < 16; ++i) gdf_dbg[16 + i] = dbg[i]; }
+#ifdef LDIFF_STAMPS
+    { STAMP(l_t1); dbg[0] = l_t1 - l_t0; if (blockIdx.x == 0 && lw == 0 && lane == 0) for (int i = 0; i < 16; ++i) gdf_dbg[16 + i] = dbg[i]; }
 #endif
     return;
   }
@@ -234,9 +212,9 @@ __global__ __launch_bounds__(512, 2) void gemm_df_kernel(const ConvParams p, con
     // row group of iteration `it`: dealt round-robin -- or, with statistics, in runs of four (one 32-row block) round-robin
     auto row_group = [&](int it) __attribute__((always_inline)) -> int { return STATS ? ((it >> 2) * NEPI + ew) * 4 + (it & 3) : ew + it * NEPI; };
     const int px = GEGLU ? lane >> 2 : lane >> 3, o = GEGLU ? lane & 3 : lane & 7;
-#ifdef GDF_STAMPS
+#ifdef LDIFF_STAMPS
     unsigned long long dbg[16] = {0};
-    GSTAMP(e_t0);
+    STAMP(e_t0);
 #endif
     int sidx = 0;
     for (int i = 0; i < n_u; ++i) {
@@ -270,10 +248,10 @@ __global__ __launch_bounds__(512, 2) void gemm_df_kernel(const ConvParams p, con
             if constexpr (RES_SPLIT) Rl[it] = __builtin_amdgcn_raw_buffer_load_b128(rrs, ok ? roff + p.res_lo * 2 : (int)F_OOR, 0, 0);
           }
         }
-        GSTAMP(w0);
-        while ((int)flags_min_now(eflags) < sidx + 1) { __builtin_amdgcn_s_sleep(2); GACC(3, 1); }
-        GSTAMP(w1);
-        GACC(1, w1 - w0);
+        STAMP(w0);
+        while ((int)flags_min_now(eflags) < sidx + 1) { __builtin_amdgcn_s_sleep(2); STAMP_ACC(3, 1); }
+        STAMP(w1);
+        STAMP_ACC(1, w1 - w0);
         f32x4 U[NIT][GEGLU ? 4 : 2];
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
@@ -383,12 +361,12 @@ __global__ __launch_bounds__(512, 2) void gemm_df_kernel(const ConvParams p, con
             }
           }
         }
-        GSTAMP(w2);
-        GACC(2, w2 - w1); GACC(4, 1);
+        STAMP(w2);
+        STAMP_ACC(2, w2 - w1); STAMP_ACC(4, 1);
       }
     }
-#ifdef GDF_STAMPS
-    { GSTAMP(e_t1); dbg[0] = e_t1 - e_t0; if (blockIdx.x == 0 && ew == 0 && lane == 0) for (int i = 0; i < 16; ++i) gdf_dbg[32 + i] = dbg[i]; }
+#ifdef LDIFF_STAMPS
+    { STAMP(e_t1); dbg[0] = e_t1 - e_t0; if (blockIdx.x == 0 && ew == 0 && lane == 0) for (int i = 0; i < 16; ++i) gdf_dbg[32 + i] = dbg[i]; }
 #endif
     return;
   }
@@ -404,7 +382,7 @@ __global__ __launch_bounds__(512, 2) void gemm_df_kernel(const ConvParams p, con
   const int ntiles = p.Nrows >> 4;                     // 16-column tiles the packed matrix holds
   const char* wbase = reinterpret_cast<const char*>(p.w_frag);
 
-#ifdef GDF_STAMPS
+#ifdef LDIFF_STAMPS
   unsigned long long dbg[16] = {0};
 #endif
   // activation fragments travel in groups of GR = 2 row tiles, XD - 1 groups ahead (XD register sets).  ONE group ahead is the kept form: three
@@ -461,7 +439,7 @@ __global__ __launch_bounds__(512, 2) void gemm_df_kernel(const ConvParams p, con
 #ifdef GDF_ABL_NOX
     return;
 #endif
-    lds_wait2<CNT>(x[0], x[1]);
+    lds_wait<CNT>(x[0], x[1]);
   };
   auto mfma_g = [&](auto khc, auto gc, f16x8 (&x)[GR]) __attribute__((always_inline)) {
     constexpr int kh = decltype(khc)::value, gr = decltype(gc)::value;
@@ -475,7 +453,7 @@ __global__ __launch_bounds__(512, 2) void gemm_df_kernel(const ConvParams p, con
 #ifdef GDF_ABL_NOP   // ablation (timing only): the consumers never wait for a slot to land
     return;
 #endif
-    while (have < n) { have = flags_min_now(pflags); GACC(1, 1); }
+    while (have < n) { have = flags_min_now(pflags); STAMP_ACC(1, 1); }
   };
   unsigned taken = 0;  // slices known to be out of their buffers
   auto zero_sums = [&]() __attribute__((always_inline)) {
@@ -485,7 +463,7 @@ __global__ __launch_bounds__(512, 2) void gemm_df_kernel(const ConvParams p, con
       for (int m = 0; m < MT; ++m) acc[a][m] = (f32x4){0.f, 0.f, 0.f, 0.f};
   };
 
-  GSTAMP(c_t0);
+  STAMP(c_t0);
   int n0 = 0;
   {
     const int mb = u0 / nunits;
@@ -498,8 +476,8 @@ __global__ __launch_bounds__(512, 2) void gemm_df_kernel(const ConvParams p, con
   need_steps(1u);
   zero_sums();
   static_for<0, XA>([&](auto tc) { constexpr int t = decltype(tc)::value; issue_x(ic_t<t % NGH>{}, ic_t<t / NGH>{}, 0u, X[t]); });
-  GSTAMP(c_t1);
-  GACC(0, c_t1 - c_t0);
+  STAMP(c_t1);
+  STAMP_ACC(0, c_t1 - c_t0);
 
   int j = 0, sidx = 0;   // global K step / slice of this workgroup
   for (int i = 0; i < n_u; ++i) {
@@ -534,32 +512,32 @@ __global__ __launch_bounds__(512, 2) void gemm_df_kernel(const ConvParams p, con
       });
     }
     // ---- end of the unit: hand the sums to the epilogue waves, slice by slice (two buffers) ----
-    GSTAMP(e0);
+    STAMP(e0);
     static_for<0, NTW>([&](auto ac) {
       constexpr int a = decltype(ac)::value;
 #ifdef GDF_ABL_NOSTAGE   // ablation (timing only): no hand-over of the sums (the epilogue waves see the flags only)
       ++sidx; lds_write32(eflag_addr, (unsigned)sidx); return;
 #endif
-      while ((int)taken < sidx - (F_NH - 1)) { taken = flags_min_now(dflags); GACC(2, 1); }
+      while ((int)taken < sidx - (F_NH - 1)) { taken = flags_min_now(dflags); STAMP_ACC(2, 1); }
       const unsigned hb = lds0 + F_HAND + (unsigned)(sidx % F_NH) * F_HS + (unsigned)l15 * F_HP + (unsigned)(cw * 16 + g * 4) * 4u;
 #pragma unroll
-      for (int m = 0; m < MT; ++m) lds_write128f(hb + (unsigned)m * 16u * F_HP, acc[a][m]);
+      for (int m = 0; m < MT; ++m) lds_write128(hb + (unsigned)m * 16u * F_HP, acc[a][m]);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       ++sidx;
       lds_write32(eflag_addr, (unsigned)sidx);
     });
-    GSTAMP(e1);
-    GACC(3, e1 - e0); GACC(4, 1);
+    STAMP(e1);
+    STAMP_ACC(3, e1 - e0); STAMP_ACC(4, 1);
     if (has_next) {
       zero_sums();   // (the next unit's first fragments are already on their way: the read stream does not stop at a unit's end)
       n0 = n0_next;
     }
-    GSTAMP(e2);
-    GACC(5, e2 - e1);
+    STAMP(e2);
+    STAMP_ACC(5, e2 - e1);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the unused weights of the step after the last
-#ifdef GDF_STAMPS
-  { GSTAMP(c_t2); dbg[6] = c_t2 - c_t0; if (blockIdx.x == 0 && cw == 0 && lane == 0) for (int i = 0; i < 16; ++i) gdf_dbg[i] = dbg[i]; }
+#ifdef LDIFF_STAMPS
+  { STAMP(c_t2); dbg[6] = c_t2 - c_t0; if (blockIdx.x == 0 && cw == 0 && lane == 0) for (int i = 0; i < 16; ++i) gdf_dbg[i] = dbg[i]; }
 #endif
 }
 
@@ -689,7 +667,7 @@ bool gemm_df_selected(const ConvParams& p) {
   return true;
 }
 
-#ifdef GDF_STAMPS
+#ifdef LDIFF_STAMPS
 extern "C" int ldiff_debug_gdf_stamps(unsigned long long* out) {   // diagnostic build only
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(gdf_dbg), sizeof(unsigned long long) * 64);
 }

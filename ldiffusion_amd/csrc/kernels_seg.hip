@@ -13,13 +13,11 @@
 //   nhwc_f32_to_nchw  the logits' layout cast, fp32 or fp16 output.
 // Tiling of tconv2x2 as the register-staged implicit GEMM's (kernels_igemm.hip): 64 coarse pixels x 64 columns x 64 K per 256-thread workgroup, C^T accumulators so
 // that a lane holds 4 consecutive output channels of one pixel (8-byte stores), XOR-swizzled 128-byte LDS rows, double buffered, one barrier per K step.
-#include "common.h"
+#include "lds_prims.h"
 
 namespace {
 
 constexpr int TBK = 64, TCPR = TBK / 8, TBM = 64, TBN = 64;
-
-__device__ __forceinline__ int tswz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
 
 // IN: the operand carries an InstanceNorm (+ LeakyReLU where lrelu_in bit 0 is set) prologue
 template <bool IN>
@@ -69,12 +67,12 @@ __global__ __launch_bounds__(256, 2) void tconv2x2_kernel(const ConvParams p) {
       const int row = (tid >> 3) + i * 32;
       uint4 v = ra[i];
       if (IN) { if (gidx[i] >= 0) v = in_lrelu_apply8(v, p.gn_scale + gidx[i], p.gn_shift + gidx[i], slope); }
-      sA[buf][row * TCPR + tswz(row, kc)] = v;
+      sA[buf][row * TCPR + swz8(row, kc)] = v;
     }
 #pragma unroll
     for (int i = 0; i < B_IT; ++i) {
       const int row = (tid >> 3) + i * 32;
-      sB[buf][row * TCPR + tswz(row, kc)] = rw[i];
+      sB[buf][row * TCPR + swz8(row, kc)] = rw[i];
     }
   };
 
@@ -98,12 +96,12 @@ __global__ __launch_bounds__(256, 2) void tconv2x2_kernel(const ConvParams p) {
 #pragma unroll
       for (int a = 0; a < 2; ++a) {
         const int row = wave_n * 32 + a * 16 + l15;
-        wf[a] = __builtin_bit_cast(f16x8, sB[cur][row * TCPR + tswz(row, kk * 4 + g)]);
+        wf[a] = __builtin_bit_cast(f16x8, sB[cur][row * TCPR + swz8(row, kk * 4 + g)]);
       }
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
         const int row = wave_m * 32 + b * 16 + l15;
-        xf[b] = __builtin_bit_cast(f16x8, sA[cur][row * TCPR + tswz(row, kk * 4 + g)]);
+        xf[b] = __builtin_bit_cast(f16x8, sA[cur][row * TCPR + swz8(row, kk * 4 + g)]);
       }
 #pragma unroll
       for (int a = 0; a < 2; ++a)

@@ -1,4 +1,5 @@
 # same-box A/B of dataflow conv3x3 variants (diagnostic): scripts/ab_c3d.sh <outdir> <variant dirs under build/ ...>
+# (variants: scripts/build_variant.sh <name> --only kernels_conv3x3d.hip <flags>)
 O=gpurun_out/$1; shift; mkdir -p $O
 for v in product "$@"; do
   if [ $v = product ]; then unset LDIFF_LIB; else export LDIFF_LIB=build/$v/libldiff_hip.so; fi

@@ -1,4 +1,5 @@
 # same-box timing of ablation builds of the dataflow conv (diagnostic; results of the ablated builds are wrong by construction):
+# (scripts/build_variant.sh <name> --only kernels_conv3x3d.hip -DC3D_ABL_...)
 # scripts/ab_c3d_abl.sh <outdir> <variant dirs under build/ ...>; LDIFF_C3D_RUN=0 (one persistent workgroup per CU), plain layers
 O=gpurun_out/$1; shift; mkdir -p $O
 export LDIFF_C3D_RUN=0

@@ -1,5 +1,5 @@
-"""In-kernel cycle stamps of the 16x16 ping-pong conv3x3 kernel (diagnostic build: -DC3P_STAMPS, never the product library).
-build:  hipcc ... -DC3P_STAMPS into build/stamps/libldiff_hip.so (scripts/build_stamps.sh);  usage: python scripts/conv_stamps.py [shape...]
+"""In-kernel cycle stamps of the 16x16 ping-pong conv3x3 kernel (diagnostic build, never the product library).
+build:  scripts/build_variant.sh stamps --only kernels_conv3x3p.hip -DLDIFF_STAMPS  (-> build/stamps/libldiff_hip.so);  usage: python scripts/conv_stamps.py [shape...]
 Prints, for wave 0 (group A) and wave 4 (group B) of workgroup 0, the mean cycles per step spent in the matrix segment, the
 barrier after it, the load segment and the barrier after that."""
 import ctypes as C

@@ -1,4 +1,5 @@
-"""In-kernel stamps of the dataflow conv3x3 kernel (diagnostic build: scripts/build_variant.sh stampsd -DC3D_STAMPS; never the product library).
+"""In-kernel stamps of the dataflow conv3x3 kernel (diagnostic build: scripts/build_variant.sh stampsd --only kernels_conv3x3d.hip -DLDIFF_STAMPS;
+never the product library).
 usage: LDIFF_LIB=build/stampsd/libldiff_hip.so python scripts/conv_stamps_d.py [B Cin H Cout [res stats]] ..."""
 import ctypes as C, math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

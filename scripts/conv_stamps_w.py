@@ -1,5 +1,5 @@
-"""In-kernel cycle stamps of the 8x16-tile conv3x3 kernel `conv3x3w_kernel` (diagnostic build: -DC3W_STAMPS, scripts/build_c3w_stamps.sh; never the product
-library).  For wave 0 of workgroup 0: mean time per (slab, tap) step spent (1) issuing the step's LDS reads, the next step's weight DMA and, once per slab, the
+"""In-kernel cycle stamps of the 8x16-tile conv3x3 kernel `conv3x3w_kernel` (diagnostic build: scripts/build_variant.sh stamps_c3w --only
+kernels_conv3x3.hip -DLDIFF_STAMPS; never the product library).  For wave 0 of workgroup 0: mean time per (slab, tap) step spent (1) issuing the step's LDS reads, the next step's weight DMA and, once per slab, the
 next halo's loads; (2) in the MFMA groups with their operand waits and the GroupNorm transform of the next slab's chunk; (3) at the step's barrier, which also waits
 for the weight DMA issued in (1).  s_memtime ticks are converted with the launch's own wall time.  usage: python scripts/conv_stamps_w.py"""
 import ctypes as C

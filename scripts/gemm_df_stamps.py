@@ -1,23 +1,17 @@
-"""In-kernel stamps of the dataflow GEMM (diagnostic build -DGDF_STAMPS; never the product library): where one consumer, one loader and one
+"""In-kernel stamps of the dataflow GEMM (diagnostic build: scripts/build_variant.sh <name> --only kernels_gemm_df.hip -DLDIFF_STAMPS; never the product library): where one consumer, one loader and one
 epilogue wave of workgroup 0 spend their cycles.  Build + run:
   python scripts/gemm_df_stamps.py --build          (here or on the GPU box: hipcc cross-compiles)
   python scripts/gemm_df_stamps.py [shape-filter]   (on the GPU box)
 """
 import ctypes as C, math, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "build", "stamps")
 DEFS = [a[6:] for a in sys.argv[1:] if a.startswith("--def=")]       # e.g. --def=GDF_TUNE --def=GDF_RING=3 --def=GDF_SLICES=3
 ABL = [a[6:] for a in sys.argv[1:] if a.startswith("--abl=")]       # e.g. --abl=NOW --abl=NOX: ablation builds (timing only, results wrong)
 TAG = "".join("_" + a.lower() for a in ABL) + "".join("_" + d.lower().replace("gdf_", "").replace("=", "") for d in DEFS)
-LIB = os.path.join(OUT, f"libldiff_hip_gdf_stamps{TAG}.so")
+LIB = os.path.join(ROOT, "build", f"stamps_gdf{TAG}", "libldiff_hip.so")
 if "--build" in sys.argv:
-    os.makedirs(OUT, exist_ok=True)
-    obj = os.path.join(OUT, f"kernels_gemm_df{TAG}.o")
-    subprocess.run(["hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wno-comment", "-DGDF_STAMPS"] + [f"-DGDF_ABL_{a}" for a in ABL] + [f"-D{d}" for d in DEFS] + ["-c",
-                    os.path.join(ROOT, "ldiffusion_amd", "csrc", "kernels_gemm_df.hip"), "-o", obj], check=True)
-    others = [os.path.join(ROOT, "build", "obj", f) for f in os.listdir(os.path.join(ROOT, "build", "obj")) if f.endswith(".o") and f != "kernels_gemm_df.o"]
-    subprocess.run(["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, obj] + others, check=True)
-    print("built", LIB)
+    subprocess.run([os.path.join(ROOT, "scripts", "build_variant.sh"), f"stamps_gdf{TAG}", "--only", "kernels_gemm_df.hip", "-DLDIFF_STAMPS"] + [f"-DGDF_ABL_{a}" for a in ABL] +
+                   [f"-D{d}" for d in DEFS], check=True)
     sys.exit(0)
 sys.path.insert(0, ROOT)
 os.environ["LDIFF_OP_CACHE_FRAG"] = "1"

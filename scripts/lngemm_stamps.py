@@ -1,5 +1,7 @@
+"""Phase stamps of the fused LayerNorm GEMM (kernels_gemm_ast.hip).  No diagnostic build: the product library takes them at run time under LDIFF_LNGEMM_STAMPS=1
+(a pointer-gated path that is always compiled; the -DLDIFF_STAMPS builds of csrc/stamps.h are a different mechanism).  usage: python scripts/lngemm_stamps.py"""
 import ctypes as C, math, sys, os
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from ldiffusion_amd import _lib
 lib = _lib.load()
