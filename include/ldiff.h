@@ -662,6 +662,27 @@ int ldiff_op_in_train_bwd(const void* x, const void* dy, const void* gamma, cons
 int64_t ldiff_op_dice_ce_ws_bytes(int B, int64_t HW, int n_heads);
 int ldiff_op_dice_ce(const void* logits, int ld, int n_heads, const void* target, int target_i64, int B, int64_t HW, int batch_dice, float smooth, float weight,
                      float grad_scale, void* loss, void* dlogits, void* ws, int64_t ws_bytes, void* stream);
+/* The same loss split at its sums, for data-parallel training (the reference's DC_and_CE_loss with ddp = True gathers the Dice statistics of all ranks
+ * when batch_dice is set).  NACC = 3 ld + 2 doubles per row: sum_pred[ld], intersect[ld], sum_gt[ld], the cross-entropy sum, the count of labels outside
+ * [0, n_heads); one row with batch_dice, B rows without.
+ *   ldiff_op_dice_ce_stats      sums (device f64 [rows, NACC]) of this process's pixels, added in the order ldiff_op_dice_ce adds them.
+ *   ldiff_op_dice_ce_from_sums  loss[0] = local cross-entropy sum / (B HW) - mean dc(dice_sums);  dlogits = grad_scale * weight * ((p - 1_t) / (B HW) +
+ *                               world * d(-mean dc)/d logits at dice_sums).  dice_sums: the local sums, or with batch_dice the sum of `world` processes'
+ *                               (their backward all-reduces identical rows: the factor world).  local_sums supplies the cross-entropy sum and B is local.
+ * stats then from_sums on the same sums with world = 1 give ldiff_op_dice_ce's loss and dlogits bit for bit.  ws: ldiff_op_dice_ce_ws_bytes(...) bytes each. */
+int ldiff_op_dice_ce_stats(const void* logits, int ld, int n_heads, const void* target, int target_i64, int B, int64_t HW, int batch_dice, void* sums, void* ws,
+                           int64_t ws_bytes, void* stream);
+int ldiff_op_dice_ce_from_sums(const void* logits, int ld, int n_heads, const void* target, int target_i64, int B, int64_t HW, int batch_dice, float smooth,
+                               float weight, float grad_scale, const void* dice_sums, const void* local_sums, int world, void* loss, void* dlogits, void* ws,
+                               int64_t ws_bytes, void* stream);
+/* The gradient bucket of a data-parallel step.  ldiff_op_bucket_pack: bucket[offsets[t] + i] = grads[t][i] for every tensor in one launch; grads = device
+ * table of const float*, offsets = device int64 [T + 1] (prefix sums of the element counts), chunks as ldiff_op_adamw_multi's.
+ * ldiff_op_sumsq: out_f32[0] = sqrt(sum x^2) of n f32 elements (4-byte aligned) through one fp32 partial per 16384 elements (at most 27 dependent roundings
+ * each) and a fixed-order double finalize: no atomics, a replay gives the same bits; a non-finite element gives a non-finite result.
+ * ws: ldiff_op_sumsq_ws_bytes(n) bytes = 4 bytes per partial. */
+int ldiff_op_bucket_pack(const void* grads, const void* offsets, const void* chunks, int64_t nchunks, void* bucket, void* stream);
+int64_t ldiff_op_sumsq_ws_bytes(int64_t n);
+int ldiff_op_sumsq(const void* x, int64_t n, void* out_f32, void* ws, int64_t ws_bytes, void* stream);
 /* torch.optim.SGD(lr, momentum, nesterov=True, weight_decay) over many f32 tensors in one launch.  Device tables as ldiff_op_adamw_multi's, with
  * tensors[t] = {float* p, float* momentum_buffer, int64 n} (24 bytes).  inv_scale / clip_coef: device f32 scalars read at execution time.
  *   g = inv_scale * clip_coef * grad + weight_decay * p;   buf = first ? g : momentum * buf + g;   p -= lr * (g + momentum * buf) */

@@ -199,6 +199,11 @@ SIGNATURES = {
     "ldiff_op_in_train_bwd": (I, [P, P, P, P, P, P, P, P, P, I, I, I, F, P, I64, P]),
     "ldiff_op_dice_ce_ws_bytes": (I64, [I, I64, I]),
     "ldiff_op_dice_ce": (I, [P, I, I, P, I, I, I64, I, F, F, F, P, P, P, I64, P]),
+    "ldiff_op_dice_ce_stats": (I, [P, I, I, P, I, I, I64, I, P, P, I64, P]),
+    "ldiff_op_dice_ce_from_sums": (I, [P, I, I, P, I, I, I64, I, F, F, F, P, P, I, P, P, P, I64, P]),
+    "ldiff_op_bucket_pack": (I, [P, P, P, I64, P, P]),
+    "ldiff_op_sumsq_ws_bytes": (I64, [I64]),
+    "ldiff_op_sumsq": (I, [P, I64, P, P, I64, P]),
     "ldiff_op_sgd_nesterov_multi": (I, [P, P, P, I64, F, F, F, I, P, P, P]),
     "ldiff_op_conv_wgrad_ws_bytes": (I64, [I, I, I, I, I, I, I]),
     "ldiff_op_conv_wgrad": (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, I64, P]),

@@ -659,6 +659,133 @@ class DiceCeFn(torch.autograd.Function):
         return (dlogits.float() * g).to(dlogits.dtype), None, None, None, None, None, None
 
 
+def _dice_ce_args(logits, target, what):
+    _check_act(logits, "logits")
+    if target.dim() == 4 and target.shape[1] == 1:
+        target = target[:, 0]
+    B, H, W, ld = logits.shape
+    if tuple(target.shape) != (B, H, W):
+        raise ValueError(f"{what}: target {tuple(target.shape)} does not match logits {tuple(logits.shape)}")
+    if target.dtype not in (torch.uint8, torch.int64):
+        target = target.long() if target.is_floating_point() else target.to(torch.int64)
+    return target.to(logits.device).contiguous(), B, H, W, ld
+
+
+def dice_ce_nacc(n_heads):
+    """Doubles per row of the loss statistics: sum_pred, intersect, sum_gt per padded class, the cross-entropy sum, the count of labels outside [0, n_heads)."""
+    return 3 * 8 * ((int(n_heads) + 7) // 8) + 2
+
+
+def dice_ce_stats(logits, target, n_heads, batch_dice, out=None):
+    """ldiff_op_dice_ce_stats: the sums `dice_ce` forms before its coefficients, float64 [1 or B, dice_ce_nacc(n_heads)] on the device (one row with
+    `batch_dice`), added in dice_ce's order.  `out`: a contiguous float64 device tensor of that many elements to write into (a row of a caller's table)."""
+    lib = _lib.load()
+    target, B, H, W, ld = _dice_ce_args(logits, target, "dice_ce_stats")
+    rows, nacc = (1 if batch_dice else B), dice_ce_nacc(n_heads)
+    if out is None:
+        out = torch.empty((rows, nacc), dtype=torch.float64, device=logits.device)
+    elif not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == rows * nacc):
+        raise ValueError(f"dice_ce_stats: out must be a contiguous float64 CUDA tensor of {rows * nacc} elements")
+    nb = lib.ldiff_op_dice_ce_ws_bytes(B, H * W, int(n_heads))
+    ws = _workspace(nb, logits.device)
+    _lib.check(lib.ldiff_op_dice_ce_stats(logits.data_ptr(), ld, int(n_heads), target.data_ptr(), int(target.dtype == torch.int64), B, H * W,
+                                          int(bool(batch_dice)), out.data_ptr(), ws.data_ptr(), nb, _sp()))
+    return out
+
+
+def dice_ce_from_sums(logits, target, n_heads, batch_dice, dice_sums, local_sums, world=1, weight=1.0, grad_scale=1.0, smooth=1e-5):
+    """ldiff_op_dice_ce_from_sums: (loss, dlogits) as `dice_ce` returns them, the Dice term from `dice_sums` (with `batch_dice` possibly the sum of `world`
+    processes' statistics; its gradient then carries the factor `world`), the cross-entropy from `local_sums` over this process's B H W pixels."""
+    lib = _lib.load()
+    target, B, H, W, ld = _dice_ce_args(logits, target, "dice_ce_from_sums")
+    rows, nacc = (1 if batch_dice else B), dice_ce_nacc(n_heads)
+    for name, t in (("dice_sums", dice_sums), ("local_sums", local_sums)):
+        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == rows * nacc):
+            raise ValueError(f"dice_ce_from_sums: {name} must be a contiguous float64 CUDA tensor of {rows * nacc} elements")
+    if not batch_dice and (int(world) != 1 or dice_sums.data_ptr() != local_sums.data_ptr()):
+        raise ValueError("dice_ce_from_sums: without batch_dice the Dice term is per sample and stays local (world = 1, dice_sums is local_sums)")
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    dlogits = torch.empty_like(logits)
+    nb = lib.ldiff_op_dice_ce_ws_bytes(B, H * W, int(n_heads))
+    ws = _workspace(nb, logits.device)
+    _lib.check(lib.ldiff_op_dice_ce_from_sums(logits.data_ptr(), ld, int(n_heads), target.data_ptr(), int(target.dtype == torch.int64), B, H * W,
+                                              int(bool(batch_dice)), float(smooth), float(weight), float(grad_scale), dice_sums.data_ptr(), local_sums.data_ptr(),
+                                              int(world), loss.data_ptr(), dlogits.data_ptr(), ws.data_ptr(), nb, _sp()))
+    return loss[0], dlogits
+
+
+class DiceCeSumsFn(torch.autograd.Function):
+    """DiceCeFn with the statistics supplied: the term of a data-parallel rank.  `dice_sums` / `local_sums` / `world` as dice_ce_from_sums takes them;
+    value, stored gradient and backward as DiceCeFn's.  At world = 1 on `dice_ce_stats`' own sums it is DiceCeFn bit for bit."""
+
+    @staticmethod
+    def forward(ctx, logits, target, n_heads, batch_dice, dice_sums, local_sums, world, weight, grad_scale, smooth=1e-5):
+        loss, dlogits = dice_ce_from_sums(logits, target, n_heads, batch_dice, dice_sums, local_sums, world, weight, grad_scale, smooth)
+        ctx.save_for_backward(dlogits)
+        return loss * float(weight)
+
+    @staticmethod
+    def backward(ctx, g):
+        (dlogits,) = ctx.saved_tensors
+        return (dlogits.float() * g).to(dlogits.dtype), None, None, None, None, None, None, None, None, None
+
+
+SUMSQ_CHAIN = 27   # dependent fp32 roundings on the longest path into one partial of ldiff_op_sumsq (csrc/kernels_segtrain.hip: 16 + 1 + 2 + 6 + 2)
+
+
+def sumsq_plan(n):
+    """(chain, partials) of ldiff_op_sumsq on n elements: fp32 roundings per partial, and the most partials the double finalize adds."""
+    return SUMSQ_CHAIN, max(1, (((int(n) + 3) // 4) + ADAMW_CHUNK // 4 - 1) // (ADAMW_CHUNK // 4))
+
+
+def sumsq(x, out=None):
+    """ldiff_op_sumsq: sqrt(sum x^2) of a contiguous float32 CUDA tensor as a float32 device scalar [1] (no read-back here)."""
+    lib = _lib.load()
+    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() >= 1):
+        raise ValueError("sumsq: a non-empty contiguous float32 CUDA tensor is expected")
+    out = out if out is not None else torch.empty(1, dtype=torch.float32, device=x.device)
+    nb = lib.ldiff_op_sumsq_ws_bytes(x.numel())
+    ws = torch.empty(nb // 4, dtype=torch.float32, device=x.device)
+    _lib.check(lib.ldiff_op_sumsq(x.data_ptr(), x.numel(), out.data_ptr(), ws.data_ptr(), nb, _sp()))
+    return out
+
+
+def bucket_pack(grads, state=None, out=None):
+    """ldiff_op_bucket_pack: the float32 CUDA gradients that are not None, flattened in order into one buffer in ONE launch (torch.cat's result).
+    `state`: a dict the caller keeps; the offset and chunk tables are built once per set of sizes.  Returns (bucket, offsets): offsets[j] is the start of
+    the j-th live gradient, offsets[-1] the length."""
+    lib = _lib.load()
+    live = [g for g in grads if g is not None]
+    if not live:
+        raise ValueError("bucket_pack: no gradient")
+    dev = live[0].device
+    gs = []
+    for g in live:
+        if not (g.is_cuda and g.dtype == torch.float32):
+            raise ValueError("bucket_pack: gradients must be float32 CUDA tensors")
+        gs.append(g.detach().contiguous())
+    state = state if state is not None else {}
+    key = tuple(g.numel() for g in gs)
+    tab = state.get("_pack")
+    if tab is None or tab[0] != key:
+        offsets, chunks = [0], []
+        for t, n in enumerate(key):
+            offsets.append(offsets[-1] + n)
+            for at in range(0, n, ADAMW_CHUNK):
+                chunks += [t, at]
+        tab = (key, offsets, torch.tensor(offsets, dtype=torch.int64).to(dev), torch.tensor(chunks, dtype=torch.int64).to(dev), len(chunks) // 2)
+        state["_pack"] = tab
+    _, offsets, off_d, chunks_d, nchunks = tab
+    if out is None:
+        out = torch.empty(offsets[-1], dtype=torch.float32, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == offsets[-1]):
+        raise ValueError(f"bucket_pack: out must be a contiguous float32 CUDA tensor of {offsets[-1]} elements")
+    gptr = torch.tensor([g.data_ptr() for g in gs], dtype=torch.int64).to(dev)
+    _lib.check(lib.ldiff_op_bucket_pack(gptr.data_ptr(), off_d.data_ptr(), chunks_d.data_ptr(), nchunks, out.data_ptr(), _sp()))
+    state["_pack_keep"] = (gs, gptr)   # the launch is asynchronous
+    return out, offsets
+
+
 def sgd_nesterov_step(params, grads, state, lr, weight_decay=0.0, momentum=0.99, inv_scale=1.0, clip_coef=1.0):
     """One torch.optim.SGD(momentum, nesterov=True, weight_decay) update of float32 CUDA parameters, in place, all tensors in one launch
     (ldiff_op_sgd_nesterov_multi; a second launch for tensors that meet their first gradient later than the others: their buffer starts as g).

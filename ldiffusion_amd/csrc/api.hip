@@ -1082,6 +1082,35 @@ int ldiff_op_dice_ce(const void* logits, int ld, int n_heads, const void* target
                  (hipStream_t)stream);
   API_END
 }
+int ldiff_op_dice_ce_stats(const void* logits, int ld, int n_heads, const void* target, int target_i64, int B, int64_t HW, int batch_dice, void* sums, void* ws,
+                           int64_t ws_bytes, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(logits && target && sums && ws, LDIFF_ERR_INVALID, "op_dice_ce_stats: null argument");
+  launch_dice_ce_stats((const f16*)logits, ld, n_heads, target, target_i64, B, HW, batch_dice, (double*)sums, ws, ws_bytes, (hipStream_t)stream);
+  API_END
+}
+int ldiff_op_dice_ce_from_sums(const void* logits, int ld, int n_heads, const void* target, int target_i64, int B, int64_t HW, int batch_dice, float smooth,
+                               float weight, float grad_scale, const void* dice_sums, const void* local_sums, int world, void* loss, void* dlogits, void* ws,
+                               int64_t ws_bytes, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(logits && target && dice_sums && local_sums && loss && dlogits && ws, LDIFF_ERR_INVALID, "op_dice_ce_from_sums: null argument");
+  launch_dice_ce_from_sums((const f16*)logits, ld, n_heads, target, target_i64, B, HW, batch_dice, smooth, weight, grad_scale, (const double*)dice_sums,
+                           (const double*)local_sums, world, (float*)loss, (f16*)dlogits, ws, ws_bytes, (hipStream_t)stream);
+  API_END
+}
+int ldiff_op_bucket_pack(const void* grads, const void* offsets, const void* chunks, int64_t nchunks, void* bucket, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(nchunks >= 0 && (nchunks == 0 || (grads && offsets && chunks && bucket)), LDIFF_ERR_INVALID, "op_bucket_pack: bad arguments");
+  launch_bucket_pack((const float* const*)grads, (const long long*)offsets, (const AdamChunk*)chunks, nchunks, (float*)bucket, (hipStream_t)stream);
+  API_END
+}
+int64_t ldiff_op_sumsq_ws_bytes(int64_t n) { return sumsq_ws_bytes(n); }
+int ldiff_op_sumsq(const void* x, int64_t n, void* out_f32, void* ws, int64_t ws_bytes, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(x && out_f32 && ws, LDIFF_ERR_INVALID, "op_sumsq: null argument");
+  launch_sumsq((const float*)x, n, (float*)out_f32, (float*)ws, ws_bytes, (hipStream_t)stream);
+  API_END
+}
 int ldiff_op_sgd_nesterov_multi(const void* tensors, const void* grads, const void* chunks, int64_t nchunks, float lr, float momentum, float weight_decay,
                                 int first, const void* inv_scale, const void* clip_coef, void* stream) {
   API_BEGIN

@@ -360,6 +360,16 @@ void launch_in_train_bwd(const f16* x, const f16* dy, const float* gamma, const 
 long long dice_ce_ws_bytes(int B, long long HW, int n_heads);
 void launch_dice_ce(const f16* logits, int ld, int n_heads, const void* target, int target_i64, int B, long long HW, int batch_dice, float smooth, float weight,
                     float grad_scale, float* loss, f16* dlogits, void* ws, long long ws_bytes, hipStream_t s);
+// the same loss split at its sums (data-parallel step): dice_sums may be the sum over ranks, the cross-entropy stays local; ws as launch_dice_ce's
+void launch_dice_ce_stats(const f16* logits, int ld, int n_heads, const void* target, int target_i64, int B, long long HW, int batch_dice, double* sums, void* ws,
+                          long long ws_bytes, hipStream_t s);
+void launch_dice_ce_from_sums(const f16* logits, int ld, int n_heads, const void* target, int target_i64, int B, long long HW, int batch_dice, float smooth,
+                              float weight, float grad_scale, const double* dice_sums, const double* local_sums, int world, float* loss, f16* dlogits, void* ws,
+                              long long ws_bytes, hipStream_t s);
+// every gradient into one flat buffer in one launch, and the buffer's L2 norm (fixed-order reduction)
+void launch_bucket_pack(const float* const* grads, const long long* offsets, const AdamChunk* chunks, long long nchunks, float* bucket, hipStream_t s);
+long long sumsq_ws_bytes(long long n);
+void launch_sumsq(const float* x, long long n, float* out, float* ws, long long ws_bytes, hipStream_t s);
 struct SgdTensor { float* p; float* buf; long long n; };
 void launch_sgd_nesterov_multi(const SgdTensor* tensors, const float* const* grads, const AdamChunk* chunks, long long nchunks, float lr, float momentum, float wd,
                                int first, const float* inv_scale, const float* clip_coef, hipStream_t s);

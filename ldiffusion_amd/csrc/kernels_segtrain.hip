@@ -2,8 +2,10 @@
 // fine-tuning step already has (kernels_bwd.hip):
 //   in_train_fwd / in_train_bwd   InstanceNorm2d(eps, affine) + LeakyReLU(slope) with saved statistics, and its backward
 //   dice_ce                       DC_and_CE_loss with MemoryEfficientSoftDiceLoss of ONE deep-supervision scale: value and d loss / d logits
+//   dice_ce_stats / _from_sums    the same loss split at its sums, so that data-parallel ranks can add their statistics between the two halves
 //   sgd_nesterov_multi            torch.optim.SGD(momentum, nesterov=True, weight_decay) over many tensors in one launch
-// All three are bandwidth-bound reductions over NHWC fp16 tensors.  Every cross-workgroup sum goes through per-workgroup partials in a caller-supplied
+//   bucket_pack / sumsq           every gradient into one flat buffer in one launch (the all-reduce's operand), and that buffer's L2 norm
+// All are bandwidth-bound passes over NHWC fp16 tensors or fp32 gradients.  Every cross-workgroup sum goes through per-workgroup partials in a caller-supplied
 // workspace and a small finalize that adds them in a fixed order (double): no floating-point atomics, so a replay on the same inputs is bit-identical.
 #include "common.h"
 
@@ -263,13 +265,10 @@ __global__ __launch_bounds__(256) void dce_partial_kernel(const f16* __restrict_
   if (tid < NACC) part[((long long)b * gridDim.x + blockIdx.x) * NACC + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
 }
 
-// One workgroup.  sums[Bd][NACC] (double, workspace) in a fixed order, then per (sample or batch, foreground class) the Dice coefficient and the two factors
-// of its derivative, then the scalar.  With D = sum_gt + sum_pred + smooth, N = 2 intersect + smooth, M = Bd (n - 1) averaged terms:
-//   dc = N / max(D, 1e-8);   coef[..][c] = {2 / (max(D, 1e-8) M),  D < 1e-8 ? 0 : N / (D^2 M)}     d(-mean dc) / d p_c(pixel) = -(coef0 [t == c] - coef1)
-__global__ __launch_bounds__(256) void dce_finalize_kernel(const float* __restrict__ part, int chunks, int B, long long HW, int n, int NC, int batch_dice,
-                                                           float smooth, double* sums, double* dcs, float* __restrict__ coef,
-                                                           float* __restrict__ loss) {
-  const int NACC = 3 * NC + 2, Bd = batch_dice ? 1 : B, tid = threadIdx.x;
+// The two halves of the finalize, shared by the one-call loss and the split one (the same statements in both, so world = 1 gives the same bits).
+// dce_reduce_sums: sums[Bd][NACC] (double) from the workgroups' partials in ONE fixed order: per slot the images in order, each image's chunks in order.
+__device__ __forceinline__ void dce_reduce_sums(const float* __restrict__ part, int chunks, int B, int NACC, int batch_dice, double* sums) {
+  const int Bd = batch_dice ? 1 : B, tid = threadIdx.x;
   for (int slot = tid; slot < Bd * NACC; slot += 256) {
     const int bo = slot / NACC, k = slot - bo * NACC;
     const int b0 = batch_dice ? 0 : bo, b1 = batch_dice ? B : bo + 1;
@@ -278,13 +277,22 @@ __global__ __launch_bounds__(256) void dce_finalize_kernel(const float* __restri
       for (int ch = 0; ch < chunks; ++ch) a += (double)part[((long long)b * chunks + ch) * NACC + k];
     sums[slot] = a;
   }
-  __syncthreads();
+}
+
+// dce_coef_loss: per (sample or batch, foreground class) the Dice coefficient from `dsums` and the two factors of its derivative, then the scalar, whose
+// cross-entropy part comes from `lsums` (this process's pixels) over B HW.  With D = sum_gt + sum_pred + smooth, N = 2 intersect + smooth, M = Bd (n - 1) averaged terms:
+//   dc = N / max(D, 1e-8);   coef[..][c] = world {2 / (max(D, 1e-8) M),  D < 1e-8 ? 0 : N / (D^2 M)}     d(-mean dc) / d p_c(pixel) = -(coef0 [t == c] - coef1)
+// world = 1 and dsums == lsums is the single-process loss.  Under data parallelism dsums is the sum of the ranks' statistics and world their number: the
+// gathered statistics' backward all-reduces identical rows, so every rank's Dice gradient carries the factor world (x 1.0 is exact).
+__device__ __forceinline__ void dce_coef_loss(const double* dsums, const double* lsums, int B, long long HW, int n, int NC, int batch_dice, float smooth, double world,
+                                              double* dcs, float* __restrict__ coef, float* __restrict__ loss) {
+  const int NACC = 3 * NC + 2, Bd = batch_dice ? 1 : B, tid = threadIdx.x;
   const double M = (double)Bd * (double)(n - 1);
   for (int e = tid; e < Bd * NC; e += 256) {
     const int bo = e / NC, c = e - bo * NC;
     double dc = 0.0, c0 = 0.0, c1 = 0.0;
     if (c >= 1 && c < n) {
-      const double* s = sums + (long long)bo * NACC;
+      const double* s = dsums + (long long)bo * NACC;
       const double D = s[2 * NC + c] + s[c] + (double)smooth, N = 2.0 * s[NC + c] + (double)smooth;
       const double Dc = D < 1e-8 ? 1e-8 : D;
       dc = N / Dc;
@@ -292,17 +300,40 @@ __global__ __launch_bounds__(256) void dce_finalize_kernel(const float* __restri
       c1 = D < 1e-8 ? 0.0 : N / (D * D * M);
     }
     dcs[e] = dc;
-    coef[(long long)e * 2] = (float)c0;
-    coef[(long long)e * 2 + 1] = (float)c1;
+    coef[(long long)e * 2] = (float)(c0 * world);
+    coef[(long long)e * 2 + 1] = (float)(c1 * world);
   }
   __syncthreads();
   if (tid == 0) {
     double dsum = 0.0, ce = 0.0, bad = 0.0;
     for (int e = 0; e < Bd * NC; ++e) dsum += dcs[e];
-    for (int bo = 0; bo < Bd; ++bo) { ce += sums[(long long)bo * NACC + 3 * NC]; bad += sums[(long long)bo * NACC + 3 * NC + 1]; }
+    for (int bo = 0; bo < Bd; ++bo) {
+      ce += lsums[(long long)bo * NACC + 3 * NC];
+      bad += lsums[(long long)bo * NACC + 3 * NC + 1];
+      if (dsums != lsums) bad += dsums[(long long)bo * NACC + 3 * NC + 1];   // another process's bad label: the exchanged count
+    }
     const double v = ce / ((double)B * (double)HW) - dsum / M;
     loss[0] = bad > 0.0 ? __builtin_nanf("") : (float)v;   // a label outside [0, n_heads): torch's cross_entropy raises; here the value and that pixel's dlogits are NaN
   }
+}
+
+// One workgroup: both halves, the sums in the workspace.
+__global__ __launch_bounds__(256) void dce_finalize_kernel(const float* __restrict__ part, int chunks, int B, long long HW, int n, int NC, int batch_dice,
+                                                           float smooth, double* sums, double* dcs, float* __restrict__ coef,
+                                                           float* __restrict__ loss) {
+  dce_reduce_sums(part, chunks, B, 3 * NC + 2, batch_dice, sums);
+  __syncthreads();
+  dce_coef_loss(sums, sums, B, HW, n, NC, batch_dice, smooth, 1.0, dcs, coef, loss);
+}
+
+// The halves as kernels of their own (one workgroup each): the sums leave in a caller's buffer, may be added to other processes', and come back.
+__global__ __launch_bounds__(256) void dce_reduce_kernel(const float* __restrict__ part, int chunks, int B, int NACC, int batch_dice, double* __restrict__ sums) {
+  dce_reduce_sums(part, chunks, B, NACC, batch_dice, sums);
+}
+
+__global__ __launch_bounds__(256) void dce_from_sums_kernel(const double* dsums, const double* lsums, int B, long long HW, int n, int NC, int batch_dice, float smooth,
+                                                            int world, double* dcs, float* __restrict__ coef, float* __restrict__ loss) {
+  dce_coef_loss(dsums, lsums, B, HW, n, NC, batch_dice, smooth, (double)world, dcs, coef, loss);
 }
 
 // dlogits[pixel][k] = gsw ((p_k - [k == t]) / (B HW) + p_k (g_k - sum_j p_j g_j)),  g_c = -(coef0_c [t == c] - coef1_c) for c >= 1, g_0 = 0;  pad columns 0
@@ -355,6 +386,26 @@ void dce_launch(const f16* logits, const void* target, int i64, int B, long long
   HIP_CHECK(hipGetLastError());
 }
 
+template <int NV>
+void dce_stats_launch(const f16* logits, const void* target, int i64, int B, long long HW, int n, int batch_dice, double* sums_out, float* part, hipStream_t s) {
+  const int chunks = (int)((HW + DCE_PIX - 1) / DCE_PIX);
+  hipLaunchKernelGGL(dce_partial_kernel<NV>, dim3(chunks, B), dim3(256), 0, s, logits, target, i64, HW, n, part);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(dce_reduce_kernel, dim3(1), dim3(256), 0, s, part, chunks, B, dce_nacc(NV), batch_dice, sums_out);
+  HIP_CHECK(hipGetLastError());
+}
+
+template <int NV>
+void dce_from_sums_launch(const f16* logits, const void* target, int i64, int B, long long HW, int n, int batch_dice, float smooth, float gsw, const double* dsums,
+                          const double* lsums, int world, float* loss, f16* dlogits, double* dcs, float* coef, hipStream_t s) {
+  const int chunks = (int)((HW + DCE_PIX - 1) / DCE_PIX);
+  hipLaunchKernelGGL(dce_from_sums_kernel, dim3(1), dim3(256), 0, s, dsums, lsums, B, HW, n, 8 * NV, batch_dice, smooth, world, dcs, coef, loss);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(dce_grad_kernel<NV>, dim3(chunks, B), dim3(256), 0, s, logits, target, i64, HW, n, batch_dice, coef, (float)(1.0 / ((double)B * (double)HW)), gsw,
+                     dlogits);
+  HIP_CHECK(hipGetLastError());
+}
+
 // ---- SGD with Nesterov momentum, every tensor in one launch ----------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void sgd_nesterov_multi_kernel(const SgdTensor* __restrict__ tensors, const float* const* __restrict__ grads,
                                                                  const AdamChunk* __restrict__ chunks, float lr, float momentum, float wd, int first,
@@ -370,6 +421,83 @@ __global__ __launch_bounds__(256) void sgd_nesterov_multi_kernel(const SgdTensor
     const float bi = first ? gi : momentum * t.buf[i] + gi;
     t.buf[i] = bi;
     t.p[i] = pi - lr * (gi + momentum * bi);
+  }
+}
+
+// ---- gradient bucket and its norm (data-parallel step) ------------------------------------------------------------------------------------------------
+// bucket[offsets[t] + i] = grads[t][i]: workgroup c takes elements [first, first + ADAMW_CHUNK) of its tensor (the chunk table of the optimizer launches).
+// 16-byte loads and stores where source and destination share their offset within 16 bytes (a scalar head up to the boundary, a scalar tail), else dwords.
+__global__ __launch_bounds__(256) void bucket_pack_kernel(const float* const* __restrict__ grads, const long long* __restrict__ offsets,
+                                                          const AdamChunk* __restrict__ chunks, float* __restrict__ bucket) {
+  const AdamChunk c = chunks[blockIdx.x];
+  const long long n = offsets[c.tensor + 1] - offsets[c.tensor];
+  const long long end = c.first + ADAMW_CHUNK < n ? c.first + ADAMW_CHUNK : n;
+  const float* __restrict__ src = grads[c.tensor] + c.first;
+  float* __restrict__ dst = bucket + offsets[c.tensor] + c.first;
+  const int len = (int)(end - c.first), tid = threadIdx.x;
+  const unsigned long long sa = (unsigned long long)src, da = (unsigned long long)dst;
+  if (((sa ^ da) & 15) != 0) {
+    for (int i = tid; i < len; i += 256) dst[i] = src[i];
+    return;
+  }
+  int head = (int)(((16 - (sa & 15)) & 15) >> 2);
+  head = head < len ? head : len;
+  const int nv = (len - head) >> 2, tail = head + 4 * nv;
+  if (tid < head) dst[tid] = src[tid];
+  const float4* __restrict__ sv = reinterpret_cast<const float4*>(src + head);
+  float4* __restrict__ dv = reinterpret_cast<float4*>(dst + head);
+  for (int i = tid; i < nv; i += 256) dv[i] = sv[i];
+  if (tid < len - tail) dst[tail + tid] = src[tail + tid];
+}
+
+// sqrt(sum x^2) in two launches.  x = up to 3 scalar head elements to the first 16-byte boundary, nv float4 vectors, up to 3 scalar tail elements.  Workgroup w
+// takes vectors [w SSQ_VECS, (w + 1) SSQ_VECS): a thread 16 of them, 256 apart, into one fp32 accumulator per vector lane; workgroup 0 adds the head and
+// the tail (one more term in a lane-0 accumulator).  Then the four lanes as (a + b) + (c + d), the wave's xor tree, the four waves as (a + b) + (c + d): at most
+// SSQ_CHAIN = 16 + 1 + 2 + 6 + 2 dependent fp32 roundings on any path into a partial.  The finalize adds the partials in double in one fixed order:
+// 256 interleaved chains, then 8 chains of 32 of those in order, then the 8 in order.  No atomics: a replay gives the same bits.  Squares are not
+// negative, so an inf or a NaN anywhere (an fp32 overflow of the sum included) reaches the result.
+constexpr int SSQ_VECS = ADAMW_CHUNK / 4;
+__global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ x, long long n, int head, long long nv, float* __restrict__ part) {
+  __shared__ float red[4];
+  const int tid = threadIdx.x;
+  const float4* __restrict__ xv = reinterpret_cast<const float4*>(x + head);
+  const long long v0 = (long long)blockIdx.x * SSQ_VECS, v1 = v0 + SSQ_VECS < nv ? v0 + SSQ_VECS : nv;
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  for (long long i = v0 + tid; i < v1; i += 256) {
+    const float4 v = xv[i];
+    a0 = fmaf(v.x, v.x, a0); a1 = fmaf(v.y, v.y, a1); a2 = fmaf(v.z, v.z, a2); a3 = fmaf(v.w, v.w, a3);
+  }
+  if (blockIdx.x == 0) {
+    const long long tail = head + 4 * nv;
+    if (tid < head) { const float v = x[tid]; a0 = fmaf(v, v, a0); }
+    else if (tid >= 64 && tail + (tid - 64) < n) { const float v = x[tail + (tid - 64)]; a0 = fmaf(v, v, a0); }
+  }
+  float a = (a0 + a1) + (a2 + a3);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+  if ((tid & 63) == 0) red[tid >> 6] = a;
+  __syncthreads();
+  if (tid == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ __launch_bounds__(256) void sumsq_finalize_kernel(const float* __restrict__ part, int P, float* __restrict__ out) {
+  __shared__ double red[256];
+  __shared__ double red8[8];
+  const int tid = threadIdx.x;
+  double a = 0.0;
+  for (int w = tid; w < P; w += 256) a += (double)part[w];
+  red[tid] = a;
+  __syncthreads();
+  if (tid < 8) {
+    double t = 0.0;
+    for (int j = 0; j < 32; ++j) t += red[tid * 32 + j];
+    red8[tid] = t;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double t = 0.0;
+    for (int j = 0; j < 8; ++j) t += red8[j];
+    out[0] = (float)sqrt(t);
   }
 }
 
@@ -448,5 +576,73 @@ void launch_sgd_nesterov_multi(const SgdTensor* tensors, const float* const* gra
                                int first, const float* inv_scale, const float* clip_coef, hipStream_t s) {
   if (nchunks == 0) return;
   hipLaunchKernelGGL(sgd_nesterov_multi_kernel, dim3((unsigned)nchunks), dim3(256), 0, s, tensors, grads, chunks, lr, momentum, wd, first, inv_scale, clip_coef);
+  HIP_CHECK(hipGetLastError());
+}
+
+static void dice_ce_check(const char* what, int ld, int n_heads, int B, long long HW, long long ws_bytes) {
+  LDIFF_CHECK(n_heads >= 2 && n_heads <= 32, LDIFF_ERR_INVALID, "%s: %d heads (2 .. 32: background and at least one foreground class)", what, n_heads);
+  LDIFF_CHECK(ld == 8 * ((n_heads + 7) / 8), LDIFF_ERR_INVALID, "%s: row pitch %d, roundup(n_heads, 8) = %d expected (the seg layer's output layout)", what, ld,
+              8 * ((n_heads + 7) / 8));
+  LDIFF_CHECK(B >= 1 && B <= 65535 && HW >= 1 && HW <= (1ll << 40), LDIFF_ERR_INVALID, "%s: B=%d HW=%lld", what, B, HW);
+  LDIFF_CHECK(ws_bytes >= dice_ce_ws_bytes(B, HW, n_heads), LDIFF_ERR_INVALID, "%s: workspace of %lld bytes, %lld needed (ldiff_op_dice_ce_ws_bytes)", what, ws_bytes,
+              dice_ce_ws_bytes(B, HW, n_heads));
+}
+
+// the workspace is launch_dice_ce's, with the sums outside it: stats uses `part`, from_sums `dcs` and `coef`
+void launch_dice_ce_stats(const f16* logits, int ld, int n_heads, const void* target, int target_i64, int B, long long HW, int batch_dice, double* sums, void* ws,
+                          long long ws_bytes, hipStream_t s) {
+  dice_ce_check("dice_ce_stats", ld, n_heads, B, HW, ws_bytes);
+  const int NV = (n_heads + 7) / 8, NC = 8 * NV, NACC = dce_nacc(NV);
+  float* part = (float*)((double*)ws + (long long)B * NACC + (long long)B * NC) + (long long)B * NC * 2;
+  switch (NV) {
+    case 1: dce_stats_launch<1>(logits, target, target_i64, B, HW, n_heads, batch_dice, sums, part, s); break;
+    case 2: dce_stats_launch<2>(logits, target, target_i64, B, HW, n_heads, batch_dice, sums, part, s); break;
+    case 3: dce_stats_launch<3>(logits, target, target_i64, B, HW, n_heads, batch_dice, sums, part, s); break;
+    default: dce_stats_launch<4>(logits, target, target_i64, B, HW, n_heads, batch_dice, sums, part, s); break;
+  }
+}
+
+void launch_dice_ce_from_sums(const f16* logits, int ld, int n_heads, const void* target, int target_i64, int B, long long HW, int batch_dice, float smooth,
+                              float weight, float grad_scale, const double* dice_sums, const double* local_sums, int world, float* loss, f16* dlogits, void* ws,
+                              long long ws_bytes, hipStream_t s) {
+  dice_ce_check("dice_ce_from_sums", ld, n_heads, B, HW, ws_bytes);
+  LDIFF_CHECK(world >= 1, LDIFF_ERR_INVALID, "dice_ce_from_sums: world=%d", world);
+  LDIFF_CHECK(batch_dice || (world == 1 && dice_sums == local_sums), LDIFF_ERR_INVALID,
+              "dice_ce_from_sums: without batch_dice the Dice term is per sample and stays local (world = 1, dice_sums = local_sums)");
+  const int NV = (n_heads + 7) / 8, NC = 8 * NV, NACC = dce_nacc(NV);
+  double* dcs = (double*)ws + (long long)B * NACC;
+  float* coef = (float*)(dcs + (long long)B * NC);
+  const float gsw = weight * grad_scale;
+  switch (NV) {
+    case 1: dce_from_sums_launch<1>(logits, target, target_i64, B, HW, n_heads, batch_dice, smooth, gsw, dice_sums, local_sums, world, loss, dlogits, dcs, coef, s); break;
+    case 2: dce_from_sums_launch<2>(logits, target, target_i64, B, HW, n_heads, batch_dice, smooth, gsw, dice_sums, local_sums, world, loss, dlogits, dcs, coef, s); break;
+    case 3: dce_from_sums_launch<3>(logits, target, target_i64, B, HW, n_heads, batch_dice, smooth, gsw, dice_sums, local_sums, world, loss, dlogits, dcs, coef, s); break;
+    default: dce_from_sums_launch<4>(logits, target, target_i64, B, HW, n_heads, batch_dice, smooth, gsw, dice_sums, local_sums, world, loss, dlogits, dcs, coef, s); break;
+  }
+}
+
+void launch_bucket_pack(const float* const* grads, const long long* offsets, const AdamChunk* chunks, long long nchunks, float* bucket, hipStream_t s) {
+  if (nchunks == 0) return;
+  hipLaunchKernelGGL(bucket_pack_kernel, dim3((unsigned)nchunks), dim3(256), 0, s, grads, offsets, chunks, bucket);
+  HIP_CHECK(hipGetLastError());
+}
+
+long long sumsq_ws_bytes(long long n) {
+  if (n < 1) return 0;
+  const long long nv = (n + 3) / 4;
+  return ((nv + SSQ_VECS - 1) / SSQ_VECS) * 4;
+}
+
+void launch_sumsq(const float* x, long long n, float* out, float* ws, long long ws_bytes, hipStream_t s) {
+  LDIFF_CHECK(n >= 1 && n <= (1ll << 40), LDIFF_ERR_INVALID, "sumsq: n=%lld", n);
+  LDIFF_CHECK(((unsigned long long)x & 3) == 0, LDIFF_ERR_INVALID, "sumsq: x is not 4-byte aligned");
+  LDIFF_CHECK(ws_bytes >= sumsq_ws_bytes(n), LDIFF_ERR_INVALID, "sumsq: workspace of %lld bytes, %lld needed (ldiff_op_sumsq_ws_bytes)", ws_bytes, sumsq_ws_bytes(n));
+  long long head = (long long)(((16 - ((unsigned long long)x & 15)) & 15) >> 2);
+  head = head < n ? head : n;
+  const long long nv = (n - head) / 4;
+  const long long P = nv > 0 ? (nv + SSQ_VECS - 1) / SSQ_VECS : 1;   // <= sumsq_ws_bytes(n) / 4: nv <= n / 4
+  hipLaunchKernelGGL(sumsq_partial_kernel, dim3((unsigned)P), dim3(256), 0, s, x, n, (int)head, nv, ws);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(sumsq_finalize_kernel, dim3(1), dim3(256), 0, s, ws, (int)P, out);
   HIP_CHECK(hipGetLastError());
 }

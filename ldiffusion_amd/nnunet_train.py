@@ -10,8 +10,16 @@ Every contraction, normalisation, activation, loss term and parameter update run
 depth-to-space permute behind the transposed conv's GEMM and the global gradient norm.
 
 The trainer takes batches: `data` [B, C, H, W] float32 and `target`, the list the nnU-Net loader supplies, one label map per deep-supervision scale, highest
-resolution first; `nnunet_data.PatchLoader` makes them on the device; `Segmentor.train_tissue_model_nnUNetv2` wires planner, stores, loaders and this trainer together.  Not here: DDP, a captured-graph step, ResidualEncoderUNet,
-region labels and an ignore label.
+resolution first; `nnunet_data.PatchLoader` makes them on the device; `Segmentor.train_tissue_model_nnUNetv2` wires planner, stores, loaders and this trainer together.
+
+Data-parallel over a launch's ranks (`Trainer(ddp=...)`; nnUNetTrainer.is_ddp, :86): `rank_batch_sizes` splits the plans' batch, a step is three phases
+with two collectives between them --
+    step_forward   forward, ag.dice_ce_stats per graded scale            -> all_gather of the [scales, NACC] statistics, added in rank order
+    step_backward  ag.DiceCeSumsFn on the summed statistics, backward, ag.bucket_pack   -> all_reduce(SUM) of the flat gradient bucket
+    step_update    1 / world folded into the update's device scalar, ag.sumsq for the norm, the loss-scale rule, clip coefficient, one SGD launch
+-- and `run_training` pools losses and tp / fp / fn over the ranks; rank 0 writes the checkpoints.
+
+Not here: a captured-graph step, ResidualEncoderUNet, region labels and an ignore label.
 """
 from __future__ import annotations
 
@@ -41,6 +49,36 @@ def deep_supervision_weights(n: int) -> List[float]:
         w[-1] = 0
     w = w / w.sum()
     return [float(v) for v in w]
+
+
+def rank_batch_sizes(global_batch: int, world: int, oversample: float = 0.33):
+    """nnUNetTrainer._set_batch_size_and_oversample (:302-347) restated: [(batch_size, oversample_percent)] per rank.  Every rank takes
+    ceil(global_batch / world) samples until the batch runs out; a rank whose samples lie wholly below (above) the 1 - oversample mark of the global batch
+    forces foreground in none (all) of them, the rank that straddles the mark in the matching fraction of its own.
+    This project's extension: the rule leaves ranks with 0 or a negative batch for many worlds (12 over 5, 7 or 8 ranks; the reference would crash
+    there).  Where it leaves any rank below 1 the batch is split evenly instead -- the first global_batch mod world ranks take one sample more -- and the
+    percentages come from the same interval formula over that split."""
+    G, W = int(global_batch), int(world)
+    if W < 1:
+        raise ValueError(f"rank_batch_sizes: world = {world}")
+    if G < W:
+        raise ValueError("Cannot run DDP if the batch size is smaller than the number of GPUs... Duh.")
+    per = -(-G // W)
+    sizes = [per - ((r + 1) * per - G) if (r + 1) * per > G else per for r in range(W)]
+    if min(sizes) < 1:
+        sizes = [G // W + (1 if r < G % W else 0) for r in range(W)]
+    out, low, mark = [], 0, 1 - oversample
+    for b in sizes:
+        high = low + b
+        if high / G < mark:
+            pct = 0.0
+        elif low / G > mark:
+            pct = 1.0
+        else:
+            pct = 1 - ((mark - low / G) / (high / G - low / G))
+        out.append((b, pct))
+        low = high
+    return out
 
 
 def poly_lr(epoch: int, initial_lr: float, num_epochs: int, exponent: float = 0.9) -> float:
@@ -143,6 +181,35 @@ class TrainableSegNet(train._Graph):
         return {k: v.detach().to("cpu").clone() for k, v in self.p.items()}
 
 
+def _world(dist, group):
+    return dist.get_world_size(group) if dist is not None else 1
+
+
+def pooled_train_loss(losses, dist=None, group=None) -> float:
+    """nnUNetTrainer.on_train_epoch_end (:918-921): the mean of the epoch's step losses, under ddp over every rank's
+    (`np.vstack(all_gather_object(losses)).mean()`).  `dist` = torch.distributed, or None for one process."""
+    losses = np.asarray(losses, dtype=np.float64)
+    if _world(dist, group) > 1:
+        parts = [None] * dist.get_world_size(group)
+        dist.all_gather_object(parts, losses, group=group)
+        return float(np.vstack(parts).mean())
+    return float(np.mean(losses))
+
+
+def pooled_validation(val_outputs: List[dict], dist=None, group=None) -> List[dict]:
+    """nnUNetTrainer.on_validation_epoch_end under ddp (:1000-1017): tp / fp / fn summed over steps and ranks, the loss the mean over both.  Returns the
+    list `Trainer.on_validation_epoch_end` takes: unchanged for one process, one pooled entry under a group."""
+    if _world(dist, group) <= 1:
+        return val_outputs
+    mine = {k: np.sum([o[k] for o in val_outputs], 0) for k in ("tp_hard", "fp_hard", "fn_hard")}
+    mine["loss"] = np.asarray([o["loss"] for o in val_outputs], dtype=np.float64)
+    parts = [None] * dist.get_world_size(group)
+    dist.all_gather_object(parts, mine, group=group)
+    out = {k: np.vstack([q[k][None] for q in parts]).sum(0) for k in ("tp_hard", "fp_hard", "fn_hard")}
+    out["loss"] = float(np.vstack([q["loss"] for q in parts]).mean())
+    return [out]
+
+
 def _batch(b):
     if isinstance(b, dict):
         return b["data"], b["target"]
@@ -169,7 +236,10 @@ class Trainer:
 
     def __init__(self, spec: dict, state_dict, batch_dice: bool, num_epochs: int, initial_lr: float = 1e-2, weight_decay: float = 3e-5, device="cuda:0", *,
                  configuration: str = "2d", init_args: Optional[dict] = None, mirror_axes: Optional[Sequence[int]] = (0, 1), loss_scale: Optional[float] = None,
-                 slope: float = SLOPE):
+                 slope: float = SLOPE, ddp: Optional[bool] = None, group=None):
+        """`ddp`: None follows the launch (a process group of more than one rank: nnUNetTrainer.is_ddp), True / False force it; `group` the process group
+        (None: the default one).  ddp at world size 1 is legal: the collectives are identities.  `self.world` is the factor of the Dice gradient and of
+        the gradient mean; code that does the two collectives by hand for several trainers in one process sets it to their number."""
         self.spec = dict(spec)
         self.network = TrainableSegNet(spec, state_dict, device, slope)
         self.device = self.network.device
@@ -190,6 +260,20 @@ class Trainer:
         self._clip_t = torch.ones(1, dtype=torch.float32, device=self.device)
         self.last_grad_norm = None
         self._inv_scale = 1.0
+        import torch.distributed as dist
+        live = dist.is_available() and dist.is_initialized()
+        self.ddp = bool(live and dist.get_world_size(group) > 1) if ddp is None else bool(ddp)
+        self.group = group
+        self._dist = dist if (self.ddp and live) else None
+        self.world = dist.get_world_size(group) if self._dist is not None else 1
+        self.rank = dist.get_rank(group) if self._dist is not None else 0
+        self._pending = None
+        self._bucket_state: dict = {}
+        self._norm_t = torch.zeros(1, dtype=torch.float32, device=self.device)
+        if self._dist is not None and self.world > 1:   # DDP.__init__: everyone starts from rank 0's parameters
+            src = dist.get_global_rank(group, 0) if group is not None else 0
+            for p in self.params:
+                dist.broadcast(p.data, src=src, group=group)
 
     def lr(self, epoch: Optional[int] = None) -> float:
         return poly_lr(self.current_epoch if epoch is None else epoch, self.initial_lr, self.num_epochs)
@@ -225,9 +309,127 @@ class Trainer:
         self._clip_t.fill_(min(1.0, CLIP_NORM / (norm + 1e-6)))
         ag.sgd_nesterov_step(params, grads, opt_state["sgd"], lr, weight_decay, MOMENTUM, self._scale_t, self._clip_t)
 
+    # ---- the data-parallel step: three phases, the two collectives between them (a test may do those by hand) ----
+    def step_forward(self, data, targets) -> torch.Tensor:
+        """Phase 1: the forward pass and the loss statistics of every graded scale (weight not 0), highest resolution first.  Returns float64
+        [scales, NACC] on the device: per scale sum_pred / intersect / sum_gt per class, the cross-entropy sum and the count of labels outside
+        [0, n_heads), over this rank's batch.  The caller adds all ranks' tensors in rank order and hands the sum to `step_backward`."""
+        for p in self.params:
+            p.grad = None
+        with torch.cuda.device(self.device):
+            outputs = self.network(data)
+            self._pending = self._statistics(outputs, self._targets(targets, len(outputs)))
+        return self._pending[2]
+
+    def _statistics(self, outputs, targets):
+        """(graded scales, their local statistics, the [scales, NACC] table to exchange)"""
+        graded = [(o, t, w) for o, t, w in zip(outputs, targets, self.weights) if w != 0.0]
+        nacc = ag.dice_ce_nacc(self.n_heads)
+        table = torch.empty((len(graded), nacc), dtype=torch.float64, device=self.device)
+        local = []
+        for i, (o, t, _) in enumerate(graded):
+            if self.batch_dice:
+                local.append(ag.dice_ce_stats(o, t, self.n_heads, True, out=table[i]).view(1, nacc))
+            else:   # per-sample Dice stays on its rank; the exchanged row carries the bad-label count
+                local.append(ag.dice_ce_stats(o, t, self.n_heads, False))
+                table[i] = local[-1].sum(0)
+        return graded, local, table
+
+    def _loss_from_sums(self, graded, local, global_sums, grad_scale):
+        total = None
+        for i, ((o, t, w), loc) in enumerate(zip(graded, local)):
+            if self.batch_dice:
+                term = ag.DiceCeSumsFn.apply(o, t, self.n_heads, True, global_sums[i], loc, self.world, w, grad_scale, SMOOTH)
+            else:
+                term = ag.DiceCeSumsFn.apply(o, t, self.n_heads, False, loc, loc, 1, w, grad_scale, SMOOTH)
+            total = term if total is None else total + term
+        return total
+
+    def gather_sums(self, table: torch.Tensor) -> torch.Tensor:
+        """Collective 1: all ranks' statistics, added in rank order on every rank (identical bits everywhere)."""
+        if self._dist is None or self.world == 1:
+            return table
+        dist = self._dist
+        t = table.cpu() if dist.get_backend(self.group) == "gloo" else table
+        parts = [torch.empty_like(t) for _ in range(self.world)]
+        dist.all_gather(parts, t, group=self.group)
+        total = parts[0].clone()
+        for q in parts[1:]:
+            total += q
+        return total.to(self.device)
+
+    def step_backward(self, global_sums: torch.Tensor):
+        """Phase 2: the loss of this rank from the summed statistics (ag.DiceCeSumsFn per graded scale; with `batch_dice` the Dice term is the global
+        batch's and its gradient carries the factor world, without it the term stays local), backward at the loss scale, and every gradient packed
+        into one flat float32 bucket in one launch.  Returns (loss value as a 0-dim device tensor, bucket)."""
+        if self._pending is None:
+            raise RuntimeError("step_backward: no step_forward is pending")
+        graded, local, _ = self._pending
+        self._pending = None
+        scale = float(self.state["loss_scale"])
+        global_sums = global_sums.to(self.device, torch.float64).contiguous()
+        with torch.cuda.device(self.device):
+            total = self._loss_from_sums(graded, local, global_sums, scale)
+            total.backward()
+            self._inv_scale = 1.0 / scale
+            bucket, self._offsets = ag.bucket_pack([p.grad for p in self.params], self._bucket_state)
+        self._live = [i for i, p in enumerate(self.params) if p.grad is not None]
+        return total.detach(), bucket
+
+    def reduce_bucket(self, bucket: torch.Tensor) -> torch.Tensor:
+        """Collective 2: the sum of all ranks' buckets."""
+        if self._dist is not None and self.world > 1:
+            self._dist.all_reduce(bucket, group=self.group)
+        return bucket
+
+    def step_update(self, bucket: torch.Tensor) -> bool:
+        """Phase 3, on the summed bucket (identical bits on every rank, so every rank takes the same branch): the mean over the ranks is the factor
+        1 / world in the update's `inv_scale` device scalar and in the norm; the norm (ag.sumsq) of the averaged, unscaled gradient; train.finish_step's
+        loss-scale rule restated for this path -- non-finite: skip, halve, reset; LOSS_SCALE_GROWTH_INTERVAL finite steps double a lowered scale --;
+        clip_grad_norm_(CLIP_NORM)'s coefficient as `_update` forms it; one SGD launch whose gradient table points into the bucket.  True when the
+        update ran."""
+        st = self.state
+        with torch.cuda.device(self.device):
+            total = float(ag.sumsq(bucket, self._norm_t))   # of the summed gradients at the loss scale
+            st["grad_norm"] = total
+            if not math.isfinite(total):
+                st["skipped_steps"] = st.get("skipped_steps", 0) + 1
+                st["loss_scale"] = max(1.0, st.get("loss_scale", train.LOSS_SCALE) * 0.5)
+                st["finite_steps"] = 0
+                return False
+            st["finite_steps"] = st.get("finite_steps", 0) + 1
+            if st["finite_steps"] >= train.LOSS_SCALE_GROWTH_INTERVAL and st.get("loss_scale", train.LOSS_SCALE) < train.LOSS_SCALE:
+                st["loss_scale"] = min(train.LOSS_SCALE, st["loss_scale"] * 2.0)
+                st["finite_steps"] = 0
+            inv = self._inv_scale / self.world
+            norm = total * inv
+            self.last_grad_norm = norm
+            self._scale_t.fill_(inv)
+            self._clip_t.fill_(min(1.0, CLIP_NORM / (norm + 1e-6)))
+            grads: list = [None] * len(self.params)
+            for j, i in enumerate(self._live):
+                grads[i] = bucket[self._offsets[j]:self._offsets[j + 1]].view_as(self.params[i])
+            ag.sgd_nesterov_step(self.params, grads, st["sgd"], self.lr(), self.weight_decay, MOMENTUM, self._scale_t, self._clip_t)
+        return True
+
+    def _train_step_ddp(self, data, targets) -> float:
+        nacc = ag.dice_ce_nacc(self.n_heads)
+        sums = self.gather_sums(self.step_forward(data, targets))
+        host = sums.cpu()
+        if float(host[:, nacc - 1].sum()) > 0 or not bool(torch.isfinite(host).all()):   # the gathered count (non-finite logits make the gathered cross-entropy
+            # sum non-finite): every rank sees the same tensor, skips the update and raises together -- none is left waiting in a collective
+            self._pending = None
+            raise ValueError("train_step: the loss is NaN -- a label outside [0, n_heads) (torch's cross_entropy raises there too) or non-finite logits")
+        total, bucket = self.step_backward(sums)
+        self.step_update(self.reduce_bucket(bucket))
+        return float(total)
+
     def train_step(self, data, targets) -> float:
         """One step; returns the loss.  A non-finite gradient norm (a float16 activation gradient overflowed under the loss scale) skips the update and
-        halves the scale, a run of finite steps doubles a lowered scale again: train.finish_step's rule, which this calls."""
+        halves the scale, a run of finite steps doubles a lowered scale again: train.finish_step's rule, which this calls.  In ddp mode: the three
+        phases and their collectives; the value is this rank's (`run_training` pools them)."""
+        if self.ddp:
+            return self._train_step_ddp(data, targets)
         for p in self.params:
             p.grad = None
         scale = float(self.state["loss_scale"])
@@ -250,7 +452,13 @@ class Trainer:
         with torch.cuda.device(self.device):
             outputs = self.network(data)
             tl = self._targets(targets, 1)
-            loss = float(self.loss(outputs, tl)) if len(tl) >= len(outputs) else float("nan")
+            if len(tl) < len(outputs):
+                loss = float("nan")
+            elif self.ddp and self.world > 1:   # the reference's validation loss is the same loss object: its Dice term sees all ranks' batches
+                graded, local, table = self._statistics(outputs, tl)
+                loss = float(self._loss_from_sums(graded, local, self.gather_sums(table).to(self.device), 1.0))
+            else:
+                loss = float(self.loss(outputs, tl))
             top = tl[0]
             if top.dim() == 4:
                 top = top[:, 0]
@@ -299,14 +507,18 @@ class Trainer:
         while self.current_epoch < self.num_epochs:
             self.log["lrs"].append(self.lr())
             losses = [self.train_step(*_batch(next(tr))) for _ in range(iterations_per_epoch)]
-            self.log["train_losses"].append(float(np.mean(losses)))
-            self.on_validation_epoch_end([self.validation_step(*_batch(next(va))) for _ in range(val_iterations)])
+            self.log["train_losses"].append(pooled_train_loss(losses, self._dist, self.group))
+            self.on_validation_epoch_end(pooled_validation([self.validation_step(*_batch(next(va))) for _ in range(val_iterations)], self._dist, self.group))
             ema = self.log["ema_fg_dice"][-1]
-            if self._best_ema is None or ema > self._best_ema:
+            if self._best_ema is None or ema > self._best_ema:   # the pooled values are the same on every rank: so are the EMA and the best
                 self._best_ema = ema
-                self.save_checkpoint(os.path.join(output_folder, "checkpoint_best.pth"))
+                if self.rank == 0:
+                    self.save_checkpoint(os.path.join(output_folder, "checkpoint_best.pth"))
             self.current_epoch += 1
         self.current_epoch -= 1   # save_checkpoint stores current_epoch + 1; on_train_end runs after the last on_epoch_end's increment (:853)
-        self.save_checkpoint(os.path.join(output_folder, "checkpoint_final.pth"))
+        if self.rank == 0:   # nnUNetTrainer.save_checkpoint (:1057): `if self.local_rank == 0`
+            self.save_checkpoint(os.path.join(output_folder, "checkpoint_final.pth"))
         self.current_epoch += 1
+        if self._dist is not None and self.world > 1:
+            self._dist.barrier(group=self.group)
         return self.log

@@ -230,7 +230,11 @@ class Segmentor:
         nnUNet_results/<dataset>/nnUNetTrainer__nnUNetPlans__2d/fold_0, plans.json and dataset.json beside it.
         `iterations_per_epoch`, `val_iterations`: nnUNetTrainer's 250 / 50.  `num_foreground_voxels`: the fingerprint's sample budget (None: the
         reference's 10e7).  The three folders come from the environment variables nnUNet_raw, nnUNet_preprocessed, nnUNet_results.
-        Returns the model folder -- what `inference_tissue_model_nnUNetv2(segmentor_weight=...)` takes."""
+        Under a process group of more than one rank the stage is data-parallel, as the reference's nnUNetTrainer is under the same launch: rank 0 alone
+        writes the dataset, the fingerprint, plans, split and the model folder; `(new_num, dataset_name)` go out by `broadcast_object_list` and a
+        barrier; every rank then reads the PNGs and JSONs and builds both stores on its own device; its loaders take its entry of
+        `nnunet_train.rank_batch_sizes` (batch and oversample) and the seeds 2 rank / 2 rank + 1; the trainer runs with ddp on.
+        Returns the model folder -- what `inference_tissue_model_nnUNetv2(segmentor_weight=...)` takes -- on every rank."""
         import json
         from PIL import Image
         from . import nnunet, nnunet_data, nnunet_plan, nnunet_train, utils
@@ -239,6 +243,9 @@ class Segmentor:
             if not os.environ.get(name):
                 raise RuntimeError(f"train_tissue_model_nnUNetv2: the environment variable {name} is not set")
             roots[name] = os.environ[name]
+        import torch.distributed as dist
+        world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
+        rank = dist.get_rank() if world > 1 else 0
         print("\033[32m[LDiffusion] Preparing data by L-Diffusion...\033[0m")
         pipeline, unet, _ = self.load_ldiffusion(ldiffusion_weight, diffusion_path)
         if num_classes is None:
@@ -248,12 +255,18 @@ class Segmentor:
                 raise ValueError("train_loader/val_loader are required when explicit nnUNet data lists are not provided")
             train_images, train_labels = self.train_loader.dataset.image_dir, self.train_loader.dataset.label_dir
             test_images, test_labels = self.val_loader.dataset.image_dir, self.val_loader.dataset.label_dir
-        aligned_unet = unet
-        if utils.check_images_same_size(train_images) and utils.check_images_same_size(test_images):   # only then does a sampler run (utils.py:213)
-            self._ensure_ldiffusion_proj(pipeline, unet, ldiffusion_weight=ldiffusion_weight)
-            aligned_unet = TextAlignedUNet(unet, self._get_text_embeddings(PROMPT, 1, pipeline, unet))
-        new_num, dataset_name = utils.create_nnunet_dataset(train_images, train_labels, test_images, test_labels, num_classes, pipeline, aligned_unet,
-                                                            raw_dir=roots["nnUNet_raw"])
+        named = [None, None]
+        if rank == 0:   # one writer: W ranks would race for the next free DatasetNNN_* under nnUNet_raw
+            aligned_unet = unet
+            if utils.check_images_same_size(train_images) and utils.check_images_same_size(test_images):   # only then does a sampler run (utils.py:213)
+                self._ensure_ldiffusion_proj(pipeline, unet, ldiffusion_weight=ldiffusion_weight)
+                aligned_unet = TextAlignedUNet(unet, self._get_text_embeddings(PROMPT, 1, pipeline, unet))
+            named = list(utils.create_nnunet_dataset(train_images, train_labels, test_images, test_labels, num_classes, pipeline, aligned_unet,
+                                                     raw_dir=roots["nnUNet_raw"]))
+        if world > 1:
+            dist.broadcast_object_list(named, src=0)
+            dist.barrier()
+        new_num, dataset_name = named
 
         print("\033[32m[Segmentor-nnUNet] Data preprocessing and plan generation in progress...\033[0m")
         raw_dir = os.path.join(roots["nnUNet_raw"], dataset_name)
@@ -273,14 +286,21 @@ class Segmentor:
             with open(os.path.join(pre_dir, name), "w") as f:
                 json.dump(obj, f, indent=4, sort_keys=sort_keys)
 
-        save_json("dataset_fingerprint.json", nnunet_plan.extract_fingerprint([cases[k] for k in keys], dataset_json, **budget))
-        with open(os.path.join(pre_dir, "dataset_fingerprint.json")) as f:   # the planner plans from the file (ExperimentPlanner.__init__ :46): its key order
-            fingerprint = json.load(f)
-        plans = nnunet_plan.plan_experiment(fingerprint, dataset_json, dataset_name)
-        splits = nnunet_plan.crossval_splits(keys)
-        save_json("nnUNetPlans.json", plans, sort_keys=False)
-        save_json("dataset.json", dataset_json, sort_keys=False)
-        save_json("splits_final.json", splits)
+        def load_json(name):
+            with open(os.path.join(pre_dir, name)) as f:
+                return json.load(f)
+
+        if rank == 0:
+            save_json("dataset_fingerprint.json", nnunet_plan.extract_fingerprint([cases[k] for k in keys], dataset_json, **budget))
+            fingerprint = load_json("dataset_fingerprint.json")   # the planner plans from the file (ExperimentPlanner.__init__ :46): its key order
+            plans = nnunet_plan.plan_experiment(fingerprint, dataset_json, dataset_name)
+            splits = nnunet_plan.crossval_splits(keys)
+            save_json("nnUNetPlans.json", plans, sort_keys=False)
+            save_json("dataset.json", dataset_json, sort_keys=False)
+            save_json("splits_final.json", splits)
+        if world > 1:   # the other ranks plan nothing: they read what rank 0 wrote
+            dist.barrier()
+            plans, splits = load_json("nnUNetPlans.json"), load_json("splits_final.json")
 
         print("\033[32m[Segmentor-nnUNet] Training is starting...\033[0m")
         spec = nnunet.network_spec(plans, "2d", dataset_json)
@@ -288,11 +308,18 @@ class Segmentor:
         stores = [nnunet_data.CaseStore([cases[k] for k in splits[0][part]], spec["normalization_schemes"], spec["n_heads"], device=self.device,
                                         labels=dataset_json["labels"], prefilter="device", build="device") for part in ("train", "val")]
         n_scales = spec["n_stages"] - 1
-        loaders = [nnunet_data.PatchLoader(store, spec["patch_size"], cfg["batch_size"], n_scales, seed=seed, train=train)
-                   for store, seed, train in ((stores[0], 0, True), (stores[1], 1, False))]
+        if world > 1:
+            batch, oversample = nnunet_train.rank_batch_sizes(cfg["batch_size"], world, nnunet_data.OVERSAMPLE_FOREGROUND)[rank]
+            extra = {"oversample": oversample}
+        else:
+            batch, extra = cfg["batch_size"], {}
+        loaders = [nnunet_data.PatchLoader(store, spec["patch_size"], batch, n_scales, seed=seed, train=train, **extra)
+                   for store, seed, train in ((stores[0], 2 * rank, True), (stores[1], 2 * rank + 1, False))]
+        self.tissue_loaders = loaders
         trainer = nnunet_train.Trainer(spec, nnunet_train.initial_state_dict(spec), cfg["batch_dice"], num_epochs=epochs, device=self.device)
         model_dir = os.path.join(roots["nnUNet_results"], dataset_name, "nnUNetTrainer__nnUNetPlans__2d")
-        nnunet.write_trained_model_folder(model_dir, plans, dataset_json)
+        if rank == 0:
+            nnunet.write_trained_model_folder(model_dir, plans, dataset_json)
         self.training_log = trainer.run_training(loaders[0], loaders[1], os.path.join(model_dir, "fold_0"), iterations_per_epoch=iterations_per_epoch,
                                                  val_iterations=val_iterations)
         return model_dir

@@ -6,7 +6,11 @@ tests/golden/nnunet_plans_2d.json "2d") at 512^2 and the plans' batch size.
 The two sides alternate inside one call after a warm-up (device-synchronised wall time per step; median, min, max).  Then one library step runs under
 torch.profiler and its device time is split by kernel family (by kernel name).  No threshold is asserted on either number.
 
-usage: python scripts/bench_nnunet_train.py [--passes 5] [--size 512] [--batch 0 (= the plans')] [--config 2d]
+--ddp: instead, the plain step against the data-parallel step at world size 1 (`Trainer(ddp=True)` in one process: the loss split at its sums, the
+gradient bucket, ldiff_op_sumsq, the SGD launch reading the bucket; the collectives are identities), alternating after two warm-ups.  This prices the
+data-parallel path's own launches; it says nothing about scaling.
+
+usage: python scripts/bench_nnunet_train.py [--passes 5] [--size 512] [--batch 0 (= the plans')] [--config 2d] [--ddp]
 """
 import argparse
 import json
@@ -97,6 +101,7 @@ def main():
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--batch", type=int, default=0)
     ap.add_argument("--config", default="2d")
+    ap.add_argument("--ddp", action="store_true")
     a = ap.parse_args()
     with open(os.path.join(ROOT, "tests", "golden", "nnunet_plans_2d.json")) as f:
         plans = json.load(f)
@@ -113,6 +118,18 @@ def main():
     x = (F.avg_pool2d(torch.randn((B, 3, a.size + 4, a.size + 4), generator=g), 5, 1) * 2.2).to(dev)
     targets = [t.to(dev) for t in label_maps(B, spec["n_heads"], a.size, n_out, 2)]
     tr = nnunet_train.Trainer(spec, nnunet_train.initial_state_dict(spec, 0), batch_dice, 1000, device=dev, configuration=a.config)
+    if a.ddp:
+        td = nnunet_train.Trainer(spec, nnunet_train.initial_state_dict(spec, 0), batch_dice, 1000, device=dev, configuration=a.config, ddp=True)
+        for _ in range(2):
+            tr.train_step(x, targets); td.train_step(x, targets)
+        tp, tdd = [], []
+        for _ in range(a.passes):
+            tp.append(timed(lambda: tr.train_step(x, targets)))
+            tdd.append(timed(lambda: td.train_step(x, targets)))
+        f = lambda v: f"median {statistics.median(v):.1f} ms (min {min(v):.1f}, max {max(v):.1f})"
+        print(f"{a.config} B={B} {a.size}^2, {a.passes} alternating steps after 2 warm-ups: plain {f(tp)} | ddp at world 1 {f(tdd)} | ddp / plain = "
+              f"{statistics.median(tdd) / statistics.median(tp):.3f}; steps: plain {[round(v, 1) for v in tp]}, ddp {[round(v, 1) for v in tdd]}")
+        return
     tnet = TorchPlainConvUNet(spec).to(dev)
     opt = torch.optim.SGD(tnet.parameters(), 1e-2, weight_decay=3e-5, momentum=0.99, nesterov=True)
     scaler = torch.amp.GradScaler("cuda")
