@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define LDIFF_VERSION 209 /* 0.2.0.9: + ldiff_op_case_bbox / _stats / _counts / _apply / _rank_to_coord (plan and preprocess of the tissue head's training cases on the device: non-zero box, crop statistics, label counts per row, normalise into the arena, rank -> pixel); 0.2.0.8: + ldiff_op_seg_intensity_lr (the intensity chain with nnU-Net's low-resolution simulation between contrast and the gammas), ldiff_op_spline_prefilter (cubic B-spline prefilter on the device, one workgroup per plane); 0.2.0.7: + ldiff_op_conv_wgrad (direct MFMA weight gradient of the narrow convs over the pixel index, no im2col), ldiff_op_colsum_slabs (slab-reduced bias gradient), both with fixed-order partials; 0.2.0.6: + ldiff_op_seg_sample (patches, labels and deep-supervision targets of a training batch from cases resident on the device), ldiff_op_seg_intensity (nnU-Net's intensity augmentations, one workgroup per plane); 0.2.0.5: + ldiff_unet_set_plan_batch / ldiff_vae_set_plan_batch / ldiff_controlnet_set_plan_batch (batch-invariant mode: every launch planned for a nominal batch), ldiff_op_conv_pb, ldiff_op_attention_pb, ldiff_op_gn_stats_pb; 0.2.0.4: + ldiff_op_in_train_fwd / _bwd (InstanceNorm + LeakyReLU with saved statistics), ldiff_op_dice_ce (nnU-Net deep-supervision loss of one scale, value and gradient), ldiff_op_sgd_nesterov_multi; 0.2.0.3: + ldiff_confusion (per-image confusion matrices of masks or logits against labels, accumulated on the device), ldiff_seg_metrics (host: Dice / IoU / pixel accuracy / frequency-weighted IoU from one matrix); 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
+#define LDIFF_VERSION 210 /* 0.2.1.0: + ldiff_op_window_gather / _accumulate_batch / _finish (the tissue head's sliding window in batches: tiles x mirror variants gathered, un-flipped, averaged and Gaussian-accumulated per chunk, then divide + inf flag + arg-max + un-crop in one launch; ldiff_window_tiles by value), after ldiff_op_dice_ce_stats / _from_sums, ldiff_op_bucket_pack, ldiff_op_sumsq (data-parallel tissue training); 0.2.0.9: + ldiff_op_case_bbox / _stats / _counts / _apply / _rank_to_coord (plan and preprocess of the tissue head's training cases on the device: non-zero box, crop statistics, label counts per row, normalise into the arena, rank -> pixel); 0.2.0.8: + ldiff_op_seg_intensity_lr (the intensity chain with nnU-Net's low-resolution simulation between contrast and the gammas), ldiff_op_spline_prefilter (cubic B-spline prefilter on the device, one workgroup per plane); 0.2.0.7: + ldiff_op_conv_wgrad (direct MFMA weight gradient of the narrow convs over the pixel index, no im2col), ldiff_op_colsum_slabs (slab-reduced bias gradient), both with fixed-order partials; 0.2.0.6: + ldiff_op_seg_sample (patches, labels and deep-supervision targets of a training batch from cases resident on the device), ldiff_op_seg_intensity (nnU-Net's intensity augmentations, one workgroup per plane); 0.2.0.5: + ldiff_unet_set_plan_batch / ldiff_vae_set_plan_batch / ldiff_controlnet_set_plan_batch (batch-invariant mode: every launch planned for a nominal batch), ldiff_op_conv_pb, ldiff_op_attention_pb, ldiff_op_gn_stats_pb; 0.2.0.4: + ldiff_op_in_train_fwd / _bwd (InstanceNorm + LeakyReLU with saved statistics), ldiff_op_dice_ce (nnU-Net deep-supervision loss of one scale, value and gradient), ldiff_op_sgd_nesterov_multi; 0.2.0.3: + ldiff_confusion (per-image confusion matrices of masks or logits against labels, accumulated on the device), ldiff_seg_metrics (host: Dice / IoU / pixel accuracy / frequency-weighted IoU from one matrix); 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
 #define LDIFF_MAX_BLOCKS 8
 
 typedef enum { LDIFF_OK = 0, LDIFF_ERR_INVALID = -1, LDIFF_ERR_RUNTIME = -2, LDIFF_ERR_STATE = -3, LDIFF_ERR_NONFINITE = -4 } ldiff_status;
@@ -782,6 +782,43 @@ int ldiff_op_case_apply(const void* img, int dtype, int C, int H, int W, int64_t
 int ldiff_op_case_rank_to_coord(const void* label_u8, int H, int W, int64_t label_stride, int y0, int y1, int x0, int x1, int selector, const uint32_t* row_prefix,
                                 const int64_t* ranks, int64_t n, int32_t* coords, const void* img_or_null, int dtype, int C, int64_t row_stride, int64_t plane_stride,
                                 void* values_or_null, void* stream);
+
+/* Tissue head, batched sliding window: one image of nnUNetPredictor.predict_sliding_window_return_logits (predict_from_raw_data.py:547-635) in a few
+ * launches -- gather a batch of tiles x mirror variants, ONE ldiff_segnet_forward, accumulate the whole batch, finish.  A chunk of tiles travels BY VALUE
+ * in the kernels' arguments (a HOST ldiff_window_tiles: no copy to the device, no allocation); more than LDIFF_WINDOW_MAX_TILES tiles, n_variants not
+ * 1 / 2 / 4, a variant mask outside 0..3 or a tile that leaves the padded extent are LDIFF_ERR_INVALID and nothing is enqueued.  A variant is a flip
+ * mask: bit 0 flips axis 0 (rows), bit 1 axis 1 (columns); variants[0] is the identity in maybe_mirror_and_predict's order (predict_from_raw_data.py:530-545).
+ * Batch entry k * n_variants + v is tile k under variant v.
+ * ldiff_op_window_gather: img [C, h, w] float32, rows row_stride and planes plane_stride ELEMENTS apart, zero padded to [Hp, Wp] with its first pixel at
+ *   (pad_top, pad_left) (acvl_utils pad_nd_image) -> x [n_tiles * n_variants, C, th, tw] float32: x[k, v, c, y, x] = padded(c, y0[k] + y', x0[k] + x'),
+ *   y' = th - 1 - y when v flips axis 0, else y; likewise x'.  Exactly 0 in the pad.  n_valid is not read.
+ * ldiff_op_window_accumulate_batch: acc [heads, Hp, Wp], cnt [Hp, Wp], pred [n_tiles * n_variants, heads, th, tw], weight [th, tw] of acc's type or NULL
+ *   (weight 1).  dtypes as ldiff_window_accumulate -- 0: all float32, 1: all float16, 3: float16 accumulators and weight with a float32 prediction -- and
+ *   2: float32 accumulators and weight with a float16 prediction.  One thread owns a pixel (or four adjacent ones) of the bounding box of the first
+ *   n_valid tiles and walks those tiles IN ORDER; per covering tile and class:
+ *     p = pred[k, 0];  p = rn(p + pred[k, v] at the un-flipped coordinate) for v = 1 .. n_variants - 1;  p = rn(p / n_variants) when n_variants > 1
+ *       -- every rounding to the PREDICTION's type, as `prediction += flip(...); prediction /= n` rounds a tensor of that type;
+ *     prod = rn(p * weight) in the promoted type of (prediction, weight) (float16 only when both are; dtypes 2 widens p first);
+ *     acc = rn_T(acc + prod);  cnt = rn_T(cnt + weight)  -- ldiff_window_accumulate's rule, no fused multiply-add anywhere.
+ *   Tiles n_valid .. n_tiles - 1 (the filler of a short last chunk) are not read.  Every pixel has one writer and chunks are ordered by the stream, so
+ *   the result is that of n_valid ldiff_window_accumulate calls on the averaged tiles, bit for bit, whatever the chunk size.  heads <= 32.
+ * ldiff_op_window_finish: over the h x w pixels of the padded extent from (y0, x0) (the revert slices): l_c = rn_T(acc_c / cnt), a correctly rounded
+ *   float32 division and one rounding to the accumulators' type T (acc_f16 != 0: float16).  *inf_flag (device int32, zeroed by the caller) is set to 1
+ *   when any l_c is +-inf.  logits_or_null [heads, h, w] of type T receives l; mask_or_null uint8 [mask_H, mask_W] receives, at (mask_y0 + y, mask_x0 + x),
+ *   the arg-max by ldiff_argmax_u8's rule bit for bit (first maximal class; any NaN or +inf logit: class 0).  heads <= 32.
+ * All three: enqueued on `stream`, no synchronisation, no allocation, no workspace. */
+#define LDIFF_WINDOW_MAX_TILES 64
+typedef struct ldiff_window_tiles {
+  int32_t n_tiles, n_valid, n_variants, reserved;
+  int32_t variants[4];
+  int32_t y0[LDIFF_WINDOW_MAX_TILES], x0[LDIFF_WINDOW_MAX_TILES];
+} ldiff_window_tiles;
+int ldiff_op_window_gather(const void* img_f32, int C, int h, int w, int64_t row_stride, int64_t plane_stride, int pad_top, int pad_left, int Hp, int Wp,
+                           const ldiff_window_tiles* tiles, int th, int tw, void* x_f32, void* stream);
+int ldiff_op_window_accumulate_batch(void* acc, void* cnt, const void* pred, const void* weight_or_null, int heads, int Hp, int Wp, int th, int tw,
+                                     const ldiff_window_tiles* tiles, int dtypes, void* stream);
+int ldiff_op_window_finish(const void* acc, const void* cnt, int heads, int Hp, int Wp, int y0, int x0, int h, int w, int acc_f16, void* logits_or_null,
+                           void* mask_or_null, int mask_H, int mask_W, int mask_y0, int mask_x0, int32_t* inf_flag, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Live measurement for bench.py's roofline line: when enabled, every conv/linear, attention and

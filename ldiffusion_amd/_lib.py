@@ -67,6 +67,14 @@ class SegChan(C.Structure):     # ldiff_seg_chan
                 ("gamma", C.c_float)]
 
 
+WINDOW_MAX_TILES = 64           # LDIFF_WINDOW_MAX_TILES
+
+
+class WindowTiles(C.Structure):  # ldiff_window_tiles
+    _fields_ = [("n_tiles", C.c_int32), ("n_valid", C.c_int32), ("n_variants", C.c_int32), ("reserved", C.c_int32), ("variants", C.c_int32 * 4),
+                ("y0", C.c_int32 * WINDOW_MAX_TILES), ("x0", C.c_int32 * WINDOW_MAX_TILES)]
+
+
 # name -> (restype, argtypes); every symbol include/ldiff.h declares
 P, I, F, I64, U64 = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_uint64
 SIGNATURES = {
@@ -221,6 +229,9 @@ SIGNATURES = {
     "ldiff_op_case_counts": (I, [P, I, I, I64, I, I, I, I, I, P, P, P, P]),
     "ldiff_op_case_apply": (I, [P, I, I, I, I, I64, I64, P, I64, I, I, I, I, C.POINTER(F), C.POINTER(F), P, I64, C.POINTER(SegCase), I, P]),
     "ldiff_op_case_rank_to_coord": (I, [P, I, I, I64, I, I, I, I, I, P, P, I64, P, P, I, I, I64, I64, P, P]),
+    "ldiff_op_window_gather": (I, [P, I, I, I, I64, I64, I, I, I, I, C.POINTER(WindowTiles), I, I, P, P]),
+    "ldiff_op_window_accumulate_batch": (I, [P, P, P, P, I, I, I, I, I, C.POINTER(WindowTiles), I, P]),
+    "ldiff_op_window_finish": (I, [P, P, I, I, I, I, I, I, I, I, P, P, I, I, I, I, P, P]),
     "ldiff_stream_create_cu_share": (I, [I, I, P]),
     "ldiff_stream_destroy": (I, [P]),
     "ldiff_vae_set_side_cu_share": (I, [P, I, I]),

@@ -465,6 +465,29 @@ int ldiff_window_accumulate(void* acc, void* cnt, const void* pred, const void* 
   launch_window_accumulate(acc, cnt, pred, weight_or_null, C, H, W, th, tw, y0, x0, dtypes, (hipStream_t)stream);
   API_END
 }
+// batched sliding window of the tissue head (kernels_segwin.hip); the launchers hold every refusal, so that nothing is enqueued on a bad argument
+int ldiff_op_window_gather(const void* img_f32, int C, int h, int w, int64_t row_stride, int64_t plane_stride, int pad_top, int pad_left, int Hp, int Wp,
+                           const ldiff_window_tiles* tiles, int th, int tw, void* x_f32, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(img_f32 && tiles && x_f32, LDIFF_ERR_INVALID, "window_gather: null argument");
+  launch_window_gather((const float*)img_f32, C, h, w, row_stride, plane_stride, pad_top, pad_left, Hp, Wp, *tiles, th, tw, (float*)x_f32, (hipStream_t)stream);
+  API_END
+}
+int ldiff_op_window_accumulate_batch(void* acc, void* cnt, const void* pred, const void* weight_or_null, int heads, int Hp, int Wp, int th, int tw,
+                                     const ldiff_window_tiles* tiles, int dtypes, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(acc && cnt && pred && tiles, LDIFF_ERR_INVALID, "window_accumulate_batch: null argument");
+  launch_window_accumulate_batch(acc, cnt, pred, weight_or_null, heads, Hp, Wp, th, tw, *tiles, dtypes, (hipStream_t)stream);
+  API_END
+}
+int ldiff_op_window_finish(const void* acc, const void* cnt, int heads, int Hp, int Wp, int y0, int x0, int h, int w, int acc_f16, void* logits_or_null,
+                           void* mask_or_null, int mask_H, int mask_W, int mask_y0, int mask_x0, int32_t* inf_flag, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(acc && cnt && inf_flag, LDIFF_ERR_INVALID, "window_finish: null argument");
+  launch_window_finish(acc, cnt, heads, Hp, Wp, y0, x0, h, w, acc_f16, logits_or_null, (uint8_t*)mask_or_null, mask_H, mask_W, mask_y0, mask_x0, inf_flag,
+                       (hipStream_t)stream);
+  API_END
+}
 int ldiff_luma_float(const void* rgb_nchw, void* gray, int B, int H, int W, void* stream) {
   API_BEGIN
   LDIFF_CHECK(rgb_nchw && gray, LDIFF_ERR_INVALID, "luma_float: null argument");

@@ -323,6 +323,13 @@ void launch_bilinear_resize(const float* x, float* y, int B, int C, int H, int W
 void launch_luma_float(const float* rgb_nchw, float* gray, int B, int H, int W, hipStream_t s);
 void launch_zero_bytes(void* p, size_t bytes, hipStream_t s);   // zero fill by a kernel (capturable; see kernels_elem.hip)
 void launch_window_accumulate(void* acc, void* cnt, const void* pred, const void* g, int C, int H, int W, int th, int tw, int y0, int x0, int dtypes, hipStream_t s);
+// batched sliding window of the tissue head (kernels_segwin.hip): a chunk of tiles x mirror variants per launch, the chunk by value in the arguments
+void launch_window_gather(const float* img, int C, int h, int w, long long row_stride, long long plane_stride, int pad_top, int pad_left, int Hp, int Wp,
+                          const ldiff_window_tiles& tiles, int th, int tw, float* x, hipStream_t s);
+void launch_window_accumulate_batch(void* acc, void* cnt, const void* pred, const void* g, int heads, int Hp, int Wp, int th, int tw, const ldiff_window_tiles& tiles,
+                                    int dtypes, hipStream_t s);
+void launch_window_finish(const void* acc, const void* cnt, int heads, int Hp, int Wp, int y0, int x0, int h, int w, int acc_f16, void* logits, uint8_t* mask, int mask_H,
+                          int mask_W, int mask_y0, int mask_x0, int32_t* inf_flag, hipStream_t s);
 
 // ---- backward-pass primitives of the fine-tuning step (kernels_bwd.hip) -------------------------------------
 void launch_im2col_t(const f16* x, f16* out, int B, int H, int W, int C, int ks, int stride, int pad, int ups, int Ho, int Wo, int Mpad, hipStream_t s);

@@ -194,17 +194,18 @@ class LDiffusionModel:
         return ldiffusion_weight
 
     def inference(self, image_path, ldiffusion_weight, segmentor_weight, num_classes, head=None, predictor=None, output_path=None,
-                  text_embeddings=None, instances=None, **_readme_kwargs):
+                  text_embeddings=None, instances=None, batch_tiles=None, **_readme_kwargs):
         """ldiffusion.py:317-324.  Tissue: `segmentor_weight` = nnU-Net's trained-model folder, as in the reference (the head then runs on the HIP
         library, nnunet.py), or `predictor` = any head callable; cell: `segmentor_weight` = the folder with cellclassifier.pth (the ResNet152
         instance classifier then runs on the HIP library, cellhead.py; `instances` = the label-map callable, Cellpose where installed), or
-        `head` = any head callable; `output_path` is the folder-mode argument of the tissue path; other README-era keyword arguments (dtm_path)
+        `head` = any head callable; `output_path` is the folder-mode argument of the tissue path; `batch_tiles` (tissue) = tiles per head call of the batched
+        sliding window, None = one call per tile and mirror variant (Segmentor.inference_tissue_model_nnUNetv2); other README-era keyword arguments (dtm_path)
         are accepted and ignored like the code ignores them."""
         segmentor = Segmentor(train_loader=None, val_loader=None, level=self.level, num_classes=num_classes)
         if self.level == "tissue":
             return segmentor.inference_tissue_model_nnUNetv2(image_path, self.diffusion_path, ldiffusion_weight, segmentor_weight,
                                                              output_path=output_path, predictor=predictor if predictor is not None else head,
-                                                             text_embeddings=text_embeddings)
+                                                             text_embeddings=text_embeddings, batch_tiles=batch_tiles)
         elif self.level == "cell":
             return segmentor.inference_cell_model(image_path, self.diffusion_path, ldiffusion_weight, segmentor_weight, head=head,
                                                   text_embeddings=text_embeddings, instances=instances)

@@ -236,11 +236,14 @@ class TrainedModel:
         return self.network(x)
 
     @torch.no_grad()
-    def predict_mask(self, data: torch.Tensor, tile_size=None, tile_step_size: float = 0.5, mirror_axes="checkpoint", network=None) -> torch.Tensor:
+    def predict_mask(self, data: torch.Tensor, tile_size=None, tile_step_size: float = 0.5, mirror_axes="checkpoint", network=None,
+                     batch_tiles=None) -> torch.Tensor:
         """[C, H, W] in 0..255 scale on the device -> uint8 mask [H, W]: crop to non-zero, normalise, nnU-Net's sliding window, arg-max, un-crop.
         The tile is the plans' patch size (or `tile_size`), NOT clamped to the image: an image smaller than the patch is zero padded to it
         (predict_from_raw_data.py:614, tiling.pad_to_tile), as the reference does -- InstanceNorm statistics and Gaussian weights are then those of a full patch.
-        `network` replaces the head (tests: a float64 restatement under the same preprocessing)."""
+        `network` replaces the head (tests: a float64 restatement under the same preprocessing).
+        batch_tiles: None = one network call per tile and mirror variant; an integer = `tiling.predict_sliding_window_batched`: that many tiles times the mirror
+        variants per network call, the mask written at the crop box's place by the finish kernel.  The same mask bit for bit (the head is batch invariant)."""
         from . import tiling
         from .segmentor import argmax_mask
         x, box = preprocess(data, self.normalization_schemes)
@@ -251,6 +254,10 @@ class TrainedModel:
         if len(tile) != 2 or any(t < div or t % div for t in tile):
             raise ValueError(f"tile_size {tile} must be a multiple of the product of the network's strides, {div}, in both axes")
         axes = self.mirror_axes if mirror_axes == "checkpoint" else mirror_axes
+        if batch_tiles is not None:
+            out = torch.zeros(tuple(data.shape[1:]), dtype=torch.uint8, device=x.device)   # pixels outside the crop box are label 0 (uncrop_mask)
+            return tiling.predict_sliding_window_batched(x, network if network is not None else self.network, self.num_heads, tile, tile_step_size, True, axes,
+                                                         batch_tiles=int(batch_tiles), return_mask=True, mask_out=out, mask_origin=(box[0], box[2]))
         logits = tiling.predict_sliding_window_return_logits(x, network if network is not None else self.network, self.num_heads, tile, tile_step_size, True, axes)
         return uncrop_mask(argmax_mask(logits[None].float())[0], box, data.shape[1:])
 

@@ -391,7 +391,7 @@ class Segmentor:
     @torch.no_grad()
     def inference_tissue_model_nnUNetv2(self, image_path, diffusion_path, ldiffusion_weight, segmentor_weight, output_path=None,
                                         predictor=None, text_embeddings=None, tile_size=None, tile_step_size=0.5,
-                                        mirror_axes=None, num_heads=None):
+                                        mirror_axes=None, num_heads=None, batch_tiles=None):
         """segmentor.py:388-488.  The tissue head is either
         * built from `segmentor_weight`, a trained-model folder as the reference's nnUNetPredictor reads it (dataset.json, plans.json,
           fold_0/checkpoint_best.pth; :463-468), when `predictor` is None: nnU-Net v2's 2-D PlainConvUNet on the HIP library (`nnunet.py`; cached on this
@@ -406,7 +406,10 @@ class Segmentor:
           ratios skip the diffusion and feed the image as it is (:449-450).  The decoded RGB stays on the device, is handed to
           `predictor([1, 3, th, tw] float in 0..255 scale as the PNG would hold) -> [1, heads, th, tw]` tile by tile
           (nnU-Net order, Gaussian fp16 accumulation, mirroring), arg-max on the device, and `(decoded PIL image, uint8 mask)`
-          is returned like :486-488."""
+          is returned like :486-488.
+        * batch_tiles: None = one head call per tile and mirror variant; an integer = the batched sliding window (`tiling.predict_sliding_window_batched`), for the
+          library's head and an injected `predictor` alike, in folder mode too.  An injected predictor must then accept a batch,
+          `predictor([batch_tiles * M, 3, th, tw]) -> [batch_tiles * M, heads, th, tw]` (M = 1, 2 or 4 mirror variants), and treat its entries independently."""
         from PIL import Image
         from . import tiling
         head = None
@@ -422,7 +425,7 @@ class Segmentor:
             for name in sorted(os.listdir(image_path)):
                 if name.lower().endswith((".png", ".jpg", ".jpeg", ".tif", ".tiff", ".bmp")):
                     _, m = self.inference_tissue_model_nnUNetv2(os.path.join(image_path, name), diffusion_path, ldiffusion_weight, segmentor_weight,
-                                                                None, None, text_embeddings, tile_size, tile_step_size, mirror_axes, num_heads)
+                                                                None, None, text_embeddings, tile_size, tile_step_size, mirror_axes, num_heads, batch_tiles)
                     Image.fromarray(m).save(os.path.join(output_path, os.path.splitext(name)[0] + ".png"))
             return None, None   # batch mode returns no single mask (segmentor.py:421)
         if head is None:
@@ -443,7 +446,7 @@ class Segmentor:
             for name in sorted(os.listdir(image_path)):
                 if name.lower().endswith((".png", ".jpg", ".jpeg", ".tif", ".tiff", ".bmp")):
                     _, m = self.inference_tissue_model_nnUNetv2(os.path.join(image_path, name), diffusion_path, ldiffusion_weight, segmentor_weight,
-                                                                None, predictor, text_embeddings, tile_size, tile_step_size, mirror_axes, num_heads)
+                                                                None, predictor, text_embeddings, tile_size, tile_step_size, mirror_axes, num_heads, batch_tiles)
                     Image.fromarray(m).save(os.path.join(output_path, os.path.splitext(name)[0] + ".png"))
             return None, None   # batch mode returns no single mask (segmentor.py:421)
         pipeline, unet, _ = self.load_ldiffusion(ldiffusion_weight, diffusion_path)
@@ -463,11 +466,14 @@ class Segmentor:
             decoded = image
         data = rgb[0].permute(2, 0, 1).float()                                                # what the PNG the reference writes would hold
         if head is not None:
-            mask = head.predict_mask(data, tile_size, tile_step_size, "checkpoint" if mirror_axes is None else mirror_axes)
+            mask = head.predict_mask(data, tile_size, tile_step_size, "checkpoint" if mirror_axes is None else mirror_axes, batch_tiles=batch_tiles)
             head.network.check_finite()   # an fp16 overflow inside the head raises instead of yielding a plausible-looking mask
             return decoded, mask.cpu().numpy()
         heads = int(num_heads if num_heads is not None else self.num_classes)
         th, tw = min(tile_size[0], data.shape[1]), min(tile_size[1], data.shape[2])
+        if batch_tiles is not None:
+            mask = tiling.predict_sliding_window_batched(data, predictor, heads, (th, tw), tile_step_size, True, mirror_axes, batch_tiles=int(batch_tiles), return_mask=True)
+            return decoded, mask.cpu().numpy()
         logits = tiling.predict_sliding_window_return_logits(data, predictor, heads, (th, tw), tile_step_size, True, mirror_axes)
         mask = argmax_mask(logits[None].float())[0].cpu().numpy()
         return decoded, mask

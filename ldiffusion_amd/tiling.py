@@ -185,3 +185,210 @@ def merge_tile_masks(masks: torch.Tensor, origins: Sequence[Tuple[int, int]], im
     if not bool(seen.all()):
         raise RuntimeError("tiles do not cover the ROI")
     return out
+
+
+# ---- the sliding window in batches: a few launches per image instead of one network call per tile and mirror variant ---------------------
+WINDOW_MAX_TILES = 64   # LDIFF_WINDOW_MAX_TILES: tiles of one launch (they travel by value in the kernels' arguments)
+
+
+def mirror_variants(mirror_axes) -> List[int]:
+    """The evaluations of `maybe_mirror_and_predict`, in its order, as 2-bit flip masks (bit 0: axis 0 = rows, bit 1: axis 1 = columns): the
+    identity, then every non-empty combination of `mirror_axes` as itertools.combinations yields them.  1, 2 or 4 variants in 2-D."""
+    import itertools
+    masks = [0]
+    if mirror_axes is not None:
+        axes = [int(a) for a in mirror_axes]
+        if not axes or min(axes) < 0 or max(axes) > 1:
+            raise ValueError("mirror_axes does not match the dimension of the input!")
+        if len(set(axes)) != len(axes):
+            raise ValueError(f"mirror_axes {tuple(axes)} names an axis twice")
+        for i in range(len(axes)):
+            for combo in itertools.combinations(axes, i + 1):
+                masks.append(sum(1 << a for a in combo))
+    return masks
+
+
+class WindowPlan:
+    """Host plan of one image's batched sliding window (`window_plan`):
+    image_hw, tile_hw; padded_hw, pad = (top, left) and revert = (slice, slice) by `pad_to_tile`'s rule; origins in the reference's slicer order;
+    variants (flip masks, `mirror_variants`); batch_tiles; chunks = [(origins of exactly batch_tiles tiles, n_valid)]: consecutive runs of the
+    origins, a short last run filled by repeating its last tile so that every network call of the image has the batch batch_tiles * len(variants)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    @property
+    def batch(self) -> int:
+        return self.batch_tiles * len(self.variants)
+
+
+def window_plan(image_hw, tile_hw, tile_step_size: float = 0.5, mirror_axes=None, batch_tiles: int = 1) -> WindowPlan:
+    H, W = (int(v) for v in image_hw)
+    th, tw = (int(v) for v in tile_hw)
+    batch_tiles = int(batch_tiles)
+    if H < 1 or W < 1 or th < 1 or tw < 1:
+        raise ValueError(f"window_plan: image_hw {(H, W)} and tile_hw {(th, tw)} must be positive")
+    if not 1 <= batch_tiles <= WINDOW_MAX_TILES:
+        raise ValueError(f"window_plan: batch_tiles {batch_tiles} out of range [1, {WINDOW_MAX_TILES}] (tiles of one launch)")
+    ph, pw = max(th - H, 0), max(tw - W, 0)
+    top, left = ph // 2, pw // 2
+    padded = (H + ph, W + pw)
+    origins = tile_origins(padded, (th, tw), tile_step_size)
+    chunks = []
+    for i in range(0, len(origins), batch_tiles):
+        run = origins[i:i + batch_tiles]
+        chunks.append((run + [run[-1]] * (batch_tiles - len(run)), len(run)))
+    return WindowPlan(image_hw=(H, W), tile_hw=(th, tw), padded_hw=padded, pad=(top, left), revert=(slice(top, top + H), slice(left, left + W)),
+                      origins=origins, variants=mirror_variants(mirror_axes), batch_tiles=batch_tiles, chunks=chunks)
+
+
+def _window_tiles(origins, n_valid: int, variants):
+    """ldiff_window_tiles of one chunk (a host struct: the launchers copy it into the kernels' arguments)."""
+    from . import _lib
+    if len(origins) > WINDOW_MAX_TILES:
+        raise ValueError(f"window tiles: n_tiles {len(origins)} exceeds the {WINDOW_MAX_TILES} tiles of one launch")
+    t = _lib.WindowTiles()
+    t.n_tiles, t.n_valid, t.n_variants = len(origins), int(n_valid), len(variants)
+    for i, v in enumerate(variants):
+        t.variants[i] = int(v)
+    for k, (y, x) in enumerate(origins):
+        t.y0[k], t.x0[k] = int(y), int(x)
+    return t
+
+
+_WINDOW_KINDS = {(torch.float32, torch.float32): 0, (torch.float16, torch.float16): 1, (torch.float32, torch.float16): 2, (torch.float16, torch.float32): 3}
+_INF_MESSAGE = ("Encountered inf in predicted array. Aborting... If this problem persists, reduce value_scaling_factor in "
+                "compute_gaussian or increase the dtype of predicted_logits to fp32")
+
+
+def window_gather(image: torch.Tensor, plan: WindowPlan, origins, out: torch.Tensor = None) -> torch.Tensor:
+    """One launch of ldiff_op_window_gather: `origins` (at most WINDOW_MAX_TILES tiles of the padded extent) x plan.variants out of the float32 device image
+    [C, h, w] (unit stride along x; any row and plane stride) -> [len(origins) * M, C, th, tw] float32, tile-major then variant; exactly 0 in the pad."""
+    from . import _lib
+    if not (isinstance(image, torch.Tensor) and image.is_cuda and image.dim() == 3 and image.dtype == torch.float32 and image.stride(2) == 1):
+        raise ValueError("window gather: `image` must be a float32 device tensor [C, h, w] with unit stride along x")
+    if tuple(image.shape[1:]) != tuple(plan.image_hw):
+        raise ValueError(f"window gather: image {tuple(image.shape[1:])} does not match the plan's {tuple(plan.image_hw)}")
+    (th, tw), C = plan.tile_hw, image.shape[0]
+    t = _window_tiles(origins, len(origins), plan.variants)
+    shape = (len(origins) * len(plan.variants), C, th, tw)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=image.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != image.device:
+        raise ValueError(f"window gather: `out` must be a contiguous float32 {shape} on the image's device")
+    _lib.check(_lib.load().ldiff_op_window_gather(_lib.ptr(image), C, image.shape[1], image.shape[2], image.stride(1), image.stride(0), plan.pad[0], plan.pad[1],
+                                                  plan.padded_hw[0], plan.padded_hw[1], t, th, tw, _lib.ptr(out), _lib.stream_ptr()))
+    return out
+
+
+def window_accumulate_batch(acc: torch.Tensor, cnt: torch.Tensor, pred: torch.Tensor, g, origins, n_valid: int, variants) -> None:
+    """One launch of ldiff_op_window_accumulate_batch: pred [len(origins) * M, heads, th, tw] (float32 or float16, tile-major then variant) un-flipped,
+    averaged over the variants in the prediction's dtype, weighted by g [th, tw] (None: 1) and added into acc [heads, Hp, Wp] / cnt [Hp, Wp] for the first
+    `n_valid` tiles in order -- bit for bit what `maybe_mirror_and_predict` + `_window_accumulate` leave per tile."""
+    from . import _lib
+    if not (acc.is_cuda and cnt.is_cuda and pred.is_cuda):
+        raise ValueError("window accumulate batch: device tensors only")
+    if acc.dim() != 3 or acc.dtype != cnt.dtype or tuple(cnt.shape) != tuple(acc.shape[1:]) or not (acc.is_contiguous() and cnt.is_contiguous()):
+        raise ValueError("window accumulate batch: contiguous accumulators acc [heads, Hp, Wp] and cnt [Hp, Wp] of one dtype")
+    if (acc.dtype, pred.dtype) not in _WINDOW_KINDS:
+        raise ValueError(f"window accumulate batch: float32 / float16 accumulators with a float32 / float16 prediction, not {acc.dtype} with {pred.dtype}")
+    heads = acc.shape[0]
+    if pred.dim() != 4 or pred.shape[0] != len(origins) * len(variants) or pred.shape[1] != heads:
+        raise ValueError(f"window accumulate batch: prediction {tuple(pred.shape)} is not [{len(origins)} tiles * {len(variants)} variants, {heads} heads, th, tw]")
+    th, tw = pred.shape[-2:]
+    if g is not None and tuple(g.shape) != (th, tw):
+        raise ValueError(f"window accumulate batch: importance map {tuple(g.shape)} does not match the tile {(th, tw)}")
+    gg = None if g is None else g.to(acc.dtype).contiguous()
+    pred = pred.contiguous()
+    t = _window_tiles(origins, n_valid, variants)
+    _lib.check(_lib.load().ldiff_op_window_accumulate_batch(_lib.ptr(acc), _lib.ptr(cnt), _lib.ptr(pred), _lib.ptr(gg), heads, acc.shape[1], acc.shape[2], th, tw, t,
+                                                            _WINDOW_KINDS[(acc.dtype, pred.dtype)], _lib.stream_ptr()))
+
+
+def window_finish(acc: torch.Tensor, cnt: torch.Tensor, box, inf_flag: torch.Tensor, logits: torch.Tensor = None, mask: torch.Tensor = None, mask_origin=(0, 0)) -> None:
+    """One launch of ldiff_op_window_finish over box = (y0, x0, h, w) of the padded extent: logits [heads, h, w] (the accumulators' dtype) = acc / cnt, correctly
+    rounded; inf_flag (device int32 [1], zeroed by the caller) set when any logit is +-inf; the uint8 arg-max (`segmentor.argmax_mask`'s rule) into
+    mask [H0, W0] at mask_origin.  Either output may be None."""
+    from . import _lib
+    y0, x0, h, w = (int(v) for v in box)
+    if acc.dtype not in (torch.float32, torch.float16) or acc.dtype != cnt.dtype or not (acc.is_cuda and acc.is_contiguous() and cnt.is_contiguous()):
+        raise ValueError("window finish: contiguous float32 or float16 device accumulators of one dtype")
+    if inf_flag.dtype != torch.int32 or not inf_flag.is_cuda or inf_flag.numel() < 1:
+        raise ValueError("window finish: `inf_flag` must be a device int32 tensor")
+    if logits is not None and (tuple(logits.shape) != (acc.shape[0], h, w) or logits.dtype != acc.dtype or not logits.is_contiguous() or not logits.is_cuda):
+        raise ValueError(f"window finish: `logits` must be a contiguous {acc.dtype} device tensor {(acc.shape[0], h, w)}")
+    mh = mw = 0
+    if mask is not None:
+        if mask.dim() != 2 or mask.dtype != torch.uint8 or not mask.is_contiguous() or not mask.is_cuda:
+            raise ValueError("window finish: `mask` must be a contiguous uint8 device tensor [H0, W0]")
+        mh, mw = mask.shape
+    _lib.check(_lib.load().ldiff_op_window_finish(_lib.ptr(acc), _lib.ptr(cnt), acc.shape[0], acc.shape[1], acc.shape[2], y0, x0, h, w, int(acc.dtype == torch.float16),
+                                                  _lib.ptr(logits), _lib.ptr(mask), mh, mw, int(mask_origin[0]), int(mask_origin[1]), _lib.ptr(inf_flag), _lib.stream_ptr()))
+
+
+@torch.no_grad()
+def window_accumulate_image(image: torch.Tensor, network, num_heads: int, tile_hw, tile_step_size: float = 0.5, use_gaussian: bool = True, mirror_axes=None,
+                            acc_dtype=torch.float16, batch_tiles: int = 1):
+    """The chunk loop of `predict_sliding_window_batched`: gather, ONE network call, accumulate, per chunk of the image's plan.  Returns (acc [num_heads, Hp, Wp],
+    cnt [Hp, Wp], plan): the accumulators BEFORE the division, over the padded extent."""
+    if not isinstance(image, torch.Tensor) or not image.is_cuda:
+        raise ValueError("predict_sliding_window_batched: `image` must be a tensor on the device (a host tensor goes through predict_sliding_window_return_logits)")
+    if image.dim() != 3:
+        raise ValueError("input_image must be [C, H, W]")
+    if acc_dtype not in (torch.float32, torch.float16):
+        raise ValueError(f"predict_sliding_window_batched: acc_dtype {acc_dtype} is not float32 or float16")
+    num_heads = int(num_heads)
+    if not 1 <= num_heads <= 32:
+        raise ValueError(f"predict_sliding_window_batched: num_heads {num_heads} out of range [1, 32]")
+    if image.dtype != torch.float32:
+        image = image.float()
+    if image.stride(2) != 1 or image.stride(1) < image.shape[2] or image.stride(0) < (image.shape[1] - 1) * image.stride(1) + image.shape[2]:
+        image = image.contiguous()
+    plan = window_plan(tuple(image.shape[1:]), tile_hw, tile_step_size, mirror_axes, batch_tiles)
+    (th, tw), (Hp, Wp), dev = plan.tile_hw, plan.padded_hw, image.device
+    want = (plan.batch, num_heads, th, tw)
+    acc = torch.zeros((num_heads, Hp, Wp), dtype=acc_dtype, device=dev)
+    cnt = torch.zeros((Hp, Wp), dtype=acc_dtype, device=dev)
+    g = compute_gaussian((th, tw), sigma_scale=1.0 / 8, value_scaling_factor=10, dtype=acc_dtype, device=dev) if use_gaussian else None
+    x = torch.empty((plan.batch, image.shape[0], th, tw), dtype=torch.float32, device=dev)
+    for origins, n_valid in plan.chunks:
+        window_gather(image, plan, origins, out=x)
+        pred = network(x)
+        if not isinstance(pred, torch.Tensor) or not pred.is_cuda:
+            raise ValueError(f"predict_sliding_window_batched: the network must return a device tensor {want}")
+        if tuple(pred.shape) != want:
+            raise ValueError(f"predict_sliding_window_batched: the network returned {tuple(pred.shape)} for a batch of {plan.batch} "
+                             f"({plan.batch_tiles} tiles x {len(plan.variants)} mirror variants); expected {want}")
+        if pred.dtype not in (torch.float32, torch.float16):
+            raise ValueError(f"predict_sliding_window_batched: the network returned {pred.dtype}; expected float32 or float16")
+        window_accumulate_batch(acc, cnt, pred, g, origins, n_valid, plan.variants)
+    return acc, cnt, plan
+
+
+@torch.no_grad()
+def predict_sliding_window_batched(image: torch.Tensor, network, num_heads: int, tile_hw: Tuple[int, int], tile_step_size: float = 0.5, use_gaussian: bool = True,
+                                   mirror_axes=None, acc_dtype=torch.float16, batch_tiles: int = 1, return_mask: bool = False, mask_out: torch.Tensor = None,
+                                   mask_origin=(0, 0)):
+    """`predict_sliding_window_return_logits` in a few launches per image.  Per chunk of `batch_tiles` tiles (`window_plan`): ldiff_op_window_gather builds
+    x [batch_tiles * M, C, th, tw] float32 (tile-major, then the M mirror variants in `maybe_mirror_and_predict`'s order, already flipped), `network(x)` is called ONCE
+    and must return [batch_tiles * M, num_heads, th, tw] in float32 or float16 on the device, ldiff_op_window_accumulate_batch un-flips, averages (every add and the
+    division rounded to the prediction's dtype) and accumulates `logits[sl] += pred * g; n[sl] += g` in `acc_dtype`, tiles in slicer order; ldiff_op_window_finish
+    divides (correctly rounded), flags inf, and writes the logits or the arg-max.  Every call of one image has the same batch: a short last chunk repeats its
+    last tile and the repeats are not accumulated (the network must treat batch entries independently, as the library's head does bit for bit).
+    acc and cnt before the division equal the per-tile path's bit for bit, for any `batch_tiles`; the logits are those of a correctly rounded division (the host's),
+    where the per-tile path's device division of float16 accumulators may differ by one ulp.
+    Device tensors only.  Returns [num_heads, H, W] in `acc_dtype`; with return_mask=True the uint8 arg-max instead, written into `mask_out` [H0, W0] (zeroed by the
+    caller; default: a new [H, W] mask) at `mask_origin` -- `nnunet.uncrop_mask` without a copy.  The one host synchronisation is the read of the inf flag."""
+    acc, cnt, plan = window_accumulate_image(image, network, num_heads, tile_hw, tile_step_size, use_gaussian, mirror_axes, acc_dtype, batch_tiles)
+    (H, W), dev = plan.image_hw, acc.device
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    box = (plan.pad[0], plan.pad[1], H, W)
+    if return_mask:
+        out = mask_out if mask_out is not None else torch.zeros((H, W), dtype=torch.uint8, device=dev)
+        window_finish(acc, cnt, box, flag, mask=out, mask_origin=mask_origin)
+    else:
+        out = torch.empty((acc.shape[0], H, W), dtype=acc_dtype, device=dev)
+        window_finish(acc, cnt, box, flag, logits=out)
+    if int(flag.item()):
+        raise RuntimeError(_INF_MESSAGE)
+    return out
