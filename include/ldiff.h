@@ -707,6 +707,19 @@ int ldiff_op_conv_wgrad(const void* x, const void* dy, void* dw_f32, int B, int 
 int64_t ldiff_op_colsum_slabs_ws_bytes(int64_t M, int N);
 int ldiff_op_colsum_slabs(const void* dy, void* db_f32, int64_t M, int N, int ld, void* ws, int64_t ws_bytes, void* stream);
 
+/* ldiff_op_conv_wgrad_wide: the contraction, arguments, layouts and reduction of ldiff_op_conv_wgrad for the WIDE convs that entry refuses (the 128- and
+ *   256-channel stages, the transposed convs run as linears, the head): a workgroup owns a 64 (output) x 32 (input channels) block of dw, and the blocks of
+ *   both channel axes are grid axes beside the tile-walking workgroups.  Accepted, anything else LDIFF_ERR_INVALID naming the argument: k = 3 with stride 1 or
+ *   2 (pad 1) or k = 1 with stride 1 (pad 0); Ho, Wo = the conv's output size (no upsampling); Cx % 8 == 0, 8 <= Cx <= 1024; Cy % 8 == 0, 8 <= Cy <= 512
+ *   (k = 3) or 2048 (k = 1); 1 <= Cout <= Cy, 1 <= Cin <= Cx; wgs = 0 (planned) or 1 .. 65535 tile-walking workgroups per block; fewer than 2^31 tiles;
+ *   ws_bytes >= ldiff_op_conv_wgrad_wide_ws_bytes(...) (0 for a shape that is not accepted) for the same wgs.
+ *   Workspace = wgs * roundup(Cy, 64) * k * k * roundup(Cx, 32) * 4 bytes.  Planned (wgs = 0), wgs = max(1, min(tiles, 1024 / blocks)) and blocks <= 1024, so
+ *   the workspace never exceeds LDIFF_WGRAD_WIDE_MAX_WS_BYTES = 1024 * 64 * 32 * 9 * 4, whatever the channel counts (k = 1: a ninth of it). */
+#define LDIFF_WGRAD_WIDE_MAX_WS_BYTES 75497472
+int64_t ldiff_op_conv_wgrad_wide_ws_bytes(int B, int Ho, int Wo, int Cx, int Cy, int k, int wgs);
+int ldiff_op_conv_wgrad_wide(const void* x, const void* dy, void* dw_f32, int B, int H, int W, int Cx, int Ho, int Wo, int Cy, int Cout, int Cin, int k, int stride,
+                             int wgs, void* ws, int64_t ws_bytes, void* stream);
+
 /* Tissue head, training data: nnUNetDataLoader2D + the transforms of nnUNetTrainer.get_training_transforms (SimulateLowResolutionTransform only through
  * ldiff_op_seg_intensity_lr), on cases that stay on the device.  The host draws every random number and hands the kernels three tables (device memory, plain C structs):
  *   ldiff_seg_case    one per case: byte offsets into ONE arena (16-byte aligned) of the cubic B-spline coefficients f32 [C, H, stride], the raw

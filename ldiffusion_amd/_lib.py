@@ -215,6 +215,8 @@ SIGNATURES = {
     "ldiff_op_sgd_nesterov_multi": (I, [P, P, P, I64, F, F, F, I, P, P, P]),
     "ldiff_op_conv_wgrad_ws_bytes": (I64, [I, I, I, I, I, I, I]),
     "ldiff_op_conv_wgrad": (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, I64, P]),
+    "ldiff_op_conv_wgrad_wide_ws_bytes": (I64, [I, I, I, I, I, I, I]),
+    "ldiff_op_conv_wgrad_wide": (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, I64, P]),
     "ldiff_op_colsum_slabs_ws_bytes": (I64, [I64, I]),
     "ldiff_op_colsum_slabs": (I, [P, P, I64, I, I, P, I64, P]),
     "ldiff_op_seg_sample": (I, [P, I64, P, I, P, I, I, I, I, I, P, P, P]),

@@ -8,7 +8,8 @@ masters in the torch / diffusers layouts ([Cout, Cin, k, k], [out, in]) and rece
   * dgrad = the forward conv kernel on the weights rearranged to [Cin][k][k][Cout] with the taps flipped (a layout cast in torch),
   * wgrad = the forward GEMM kernel over K = M on dy^T (ldiff_op_transpose) and im2col(x)^T (ldiff_op_im2col_t): the "staged" route, the default;
     under `wgrad_route("direct")` / `("auto")` the narrow convs over many pixels take ldiff_op_conv_wgrad (an MFMA contraction over the pixel index straight
-    from the NHWC tensors) and the bias gradients ldiff_op_colsum_slabs instead (csrc/kernels_wgrad.hip; the tissue-head trainer runs under "auto"),
+    from the NHWC tensors) and the bias gradients ldiff_op_colsum_slabs instead (csrc/kernels_wgrad.hip; the tissue-head trainer runs under "auto");
+    under `wgrad_route("wide")` / `("auto-wide")` the wide convs that entry refuses take ldiff_op_conv_wgrad_wide as well (csrc/kernels_wgrad_wide.hip),
   * GroupNorm(+SiLU), LayerNorm, GEGLU, attention: dedicated backward kernels (csrc/kernels_bwd.hip).
 There is no CPU or torch-op fallback for those; reshapes / layout casts / the residual `+` are torch tensor plumbing.
 """
@@ -167,8 +168,12 @@ def _conv_call(x, w16, Cout, k, stride, ups, bias=None, Ho=None, Wo=None, out_f3
 # "staged": transpose + im2col_t + GEMM over K = M, and ldiff_op_colsum: what the fine-tuning step was built on (M a few hundred rows, N hundreds of columns).
 # "direct": ldiff_op_conv_wgrad wherever the shape is eligible (else staged) and ldiff_op_colsum_slabs for every bias gradient.
 # "auto":   "direct" for the launches with M = B Ho Wo >= WGRAD_DIRECT_MIN_ROWS, "staged" below.
+# "wide":   every weight gradient on a direct kernel wherever one takes the shape: ldiff_op_conv_wgrad where it is eligible (the bits of "direct"), else
+#           ldiff_op_conv_wgrad_wide (both channel counts blocked: csrc/kernels_wgrad_wide.hip), else staged; ldiff_op_colsum_slabs for every bias gradient it takes.
+# "auto-wide": the launches ldiff_op_conv_wgrad takes follow "auto" (and keep its bits); those only the wide entry takes go to it at
+#           M >= WGRAD_WIDE_MIN_ROWS; every bias gradient ldiff_op_colsum_slabs takes goes through it, whatever M.
 # The route is read when the FORWARD runs and kept with the node, so a backward() called outside the `with` follows the forward's route.
-WGRAD_ROUTES = ("staged", "direct", "auto")
+WGRAD_ROUTES = ("staged", "direct", "auto", "wide", "auto-wide")
 # Crossover of the two routes at 32 -> 32 channels, 3 x 3, B = 1 (scripts/bench_wgrad_routes.py on an MI355X, weight + bias gradient, device time per backward,
 # median of 20, the routes alternating; DESIGN.md section 7 "Direct weight and bias gradients"):
 #     M        1024    4096    9216    16384    36864    65536    262144
@@ -177,6 +182,23 @@ WGRAD_ROUTES = ("staged", "direct", "auto")
 # The direct route is the faster one from the smallest M measured on: the crossover lies BELOW 16384, and the constant never goes below 16384 -- the trainer's
 # tests reach M = 2 * 64^2 = 8192 and keep the staged route bit for bit -- so the floor is the value.
 WGRAD_DIRECT_MIN_ROWS = 16384
+# Crossover into the wide entry per layer class of the tissue-head trainer (scripts/bench_wgrad_routes.py --wide on an MI355X, B = 12, weight + bias gradient, device
+# time per backward in us, median of 10, staged / direct / wide alternating; "direct" is the staged weight gradient with the slab column sum, what "auto" gives
+# these layers from WGRAD_DIRECT_MIN_ROWS on; DESIGN.md section 7 "Wide weight gradients" has min and max):
+#     layer              at the trainer's M: staged / direct / wide      M = 12288                M = 3072             M = 768
+#     3x3  64->128 s2    196608:  22647 / 2817 / 282                    1012 / 221 / 161         264 / 186 / 163      187 / 190 / 166
+#     3x3 128->128       196608:  24446 / 4654 / 287                    1017 / 250 / 162         289 / 180 / 160      190 / 195 / 169
+#     3x3 128->256 s2     49152:   3835 /  720 / 208                    1021 / 254 / 163         313 / 186 / 162      184 / 194 / 170
+#     3x3 256->256        49152:   5759 / 1142 / 266                    1074 / 311 / 164         337 / 181 / 165      179 / 185 / 165
+#     3x3 256->128       196608:  24158 / 4391 / 387                    1096 / 306 / 162         334 / 186 / 166      186 / 194 / 169
+#     3x3 512->256        49152:   6444 / 1671 / 375                    1180 / 418 / 175         371 / 192 / 165      179 / 185 / 163
+#     1x1 128->256       196608:  18526 / 2321 / 301                     965 / 205 / 165         194 / 175 / 161      169 / 176 / 162
+#     1x1 256->512        49152:   3493 /  545 / 219                     939 / 217 / 164         256 / 174 / 160      169 / 175 / 160
+#     1x1 256->8          49152:   2279 /  525 / 164                     433 / 222 / 164         180 / 173 / 162      169 / 173 / 159
+# At its trainer's M every class is 2.5 -- 16 x faster on the wide entry than on "direct", far beyond the largest spread (max - min) of the three.  At M = 12288 eight of nine still
+# win by more than the spread (1x1 128->256: 40 us ahead under a spread of 61 us: staged by the rule); at 3072 and 768 the launches bound all three routes (160 us) and
+# the gap is within the spread for most.  So the crossover lies BELOW 16384 for every class, and, as with WGRAD_DIRECT_MIN_ROWS, the constant never goes below 16384.
+WGRAD_WIDE_MIN_ROWS = 16384
 _WGRAD_ROUTE = "staged"
 _WGRAD_ROUTE_STATED = False   # a caller has set the route (nnunet_train.TrainableSegNet runs under "auto" unless one has)
 
@@ -187,7 +209,7 @@ def _check_route(mode):
 
 
 def set_wgrad_route(mode: str) -> str:
-    """Set the module-wide route of weight / bias gradients ("staged", "direct" or "auto"); returns the previous one."""
+    """Set the module-wide route of weight / bias gradients (one of WGRAD_ROUTES); returns the previous one."""
     global _WGRAD_ROUTE, _WGRAD_ROUTE_STATED
     _check_route(mode)
     prev, _WGRAD_ROUTE, _WGRAD_ROUTE_STATED = _WGRAD_ROUTE, mode, True
@@ -236,6 +258,22 @@ def wgrad_plan(B, Ho, Wo, Cx, Cy, k, wgs=0) -> dict:
     return dict(TH=TH, tiles=tiles, wgs=n, slabs=slabs, chain=-(-tiles // n) * TH * 32, partials=n, ws_bytes=n * 32 * ntw * k * k * slabs * 32 * 4)
 
 
+def wgrad_wide_eligible(k, stride, ups, Cx, Cy, Cout, Cin) -> bool:
+    """The shapes ldiff_op_conv_wgrad_wide takes (include/ldiff.h)."""
+    return (ups == 0 and ((k == 3 and stride in (1, 2)) or (k == 1 and stride == 1)) and Cx % 8 == 0 and 8 <= Cx <= 1024 and Cy % 8 == 0
+            and 8 <= Cy <= (512 if k == 3 else 2048) and 1 <= Cout <= Cy and 1 <= Cin <= Cx)
+
+
+def wgrad_wide_plan(B, Ho, Wo, Cx, Cy, k, wgs=0) -> dict:
+    """The plan ldiff_op_conv_wgrad_wide makes for a launch (csrc/kernels_wgrad_wide.hip ww_plan), with the keys of wgrad_plan: the same tiles, `wgs` tile-walking
+    workgroups per 64 x 32 block of (Cy, Cx), `slabs` = the blocks."""
+    TH = 8 if k == 1 else 4
+    xslabs, yslabs = -(-Cx // 32), -(-Cy // 64)
+    tiles = -(-(B * Ho * Wo) // (TH * 32)) if k == 1 else B * (-(-Ho // TH)) * (-(-Wo // 32))
+    n = wgs if wgs > 0 else min(tiles, max(1, 1024 // (xslabs * yslabs)))
+    return dict(TH=TH, tiles=tiles, wgs=n, slabs=xslabs * yslabs, chain=-(-tiles // n) * TH * 32, partials=n, ws_bytes=n * 64 * yslabs * k * k * xslabs * 32 * 4)
+
+
 def colsum_slabs_plan(M, N) -> dict:
     """The plan of ldiff_op_colsum_slabs (csrc/kernels_wgrad.hip colsum_plan): `chain` = rows one thread adds plus the row lanes one LDS pass adds."""
     rp = 256 // (N // 8)
@@ -256,6 +294,20 @@ def conv_wgrad_direct(x, dy, Cout, Cin, k, stride, wgs=0):
     nb = lib.ldiff_op_conv_wgrad_ws_bytes(B, Ho, Wo, Cx, Cy, k, int(wgs))
     ws = _workspace(nb, x.device)
     _lib.check(lib.ldiff_op_conv_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, Cx, Ho, Wo, Cy, Cout, Cin, k, stride, int(wgs), ws.data_ptr(), nb, _sp()))
+    return dw
+
+
+def conv_wgrad_wide(x, dy, Cout, Cin, k, stride, wgs=0):
+    """ldiff_op_conv_wgrad_wide: x [B,H,W,Cx], dy [B,Ho,Wo,Cy] NHWC float16 -> dw float32 [Cout, Cin, k, k]."""
+    _check_act(x, "x")
+    _check_act(dy, "dy")
+    lib = _lib.load()
+    B, H, W, Cx = x.shape
+    _, Ho, Wo, Cy = dy.shape
+    dw = torch.empty((Cout, Cin, k, k), dtype=torch.float32, device=x.device)
+    nb = lib.ldiff_op_conv_wgrad_wide_ws_bytes(B, Ho, Wo, Cx, Cy, k, int(wgs))
+    ws = _workspace(nb, x.device)
+    _lib.check(lib.ldiff_op_conv_wgrad_wide(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, Cx, Ho, Wo, Cy, Cout, Cin, k, stride, int(wgs), ws.data_ptr(), nb, _sp()))
     return dw
 
 
@@ -299,7 +351,10 @@ class Conv2dFn(torch.autograd.Function):
         _, Ho, Wo, Cy = dy.shape
         w4 = weight if weight.dim() == 4 else weight[:, :, None, None]
         dx = dw = db = None
-        direct = ctx.wgrad_route == "direct" or (ctx.wgrad_route == "auto" and B * Ho * Wo >= WGRAD_DIRECT_MIN_ROWS)
+        route, M = ctx.wgrad_route, B * Ho * Wo
+        direct = route in ("direct", "wide") or (route in ("auto", "auto-wide") and M >= WGRAD_DIRECT_MIN_ROWS)   # ldiff_op_conv_wgrad where it is eligible
+        wide = route == "wide" or (route == "auto-wide" and M >= WGRAD_WIDE_MIN_ROWS)
+        slab_bias = direct or route == "auto-wide"
         if ctx.needs_input_grad[0]:
             # dgrad: conv (stride 1) of dy -- zero-inserted for a stride-2 forward -- with the weights [Cin][k][k][Cout], taps flipped
             wd = pack_weight(w4, dgrad=True, cols=Cy)
@@ -312,6 +367,8 @@ class Conv2dFn(torch.autograd.Function):
             dx = dxu if ups == 0 else dxu.view(B, H, 2, W, 2, Cx).float().sum((2, 4)).to(torch.float16)
         if ctx.needs_input_grad[1] and direct and wgrad_direct_eligible(k, stride, ups, Cx, Cy, Cout, Cin):
             dw = conv_wgrad_direct(x, dy, Cout, Cin, k, stride).view(weight.shape)
+        elif ctx.needs_input_grad[1] and wide and not wgrad_direct_eligible(k, stride, ups, Cx, Cy, Cout, Cin) and wgrad_wide_eligible(k, stride, ups, Cx, Cy, Cout, Cin):
+            dw = conv_wgrad_wide(x, dy, Cout, Cin, k, stride).view(weight.shape)
         elif ctx.needs_input_grad[1]:
             # wgrad: dW[n][tap*Cx + c] = sum_m dy[m, n] * xcol[m, tap*Cx + c]  as a GEMM over K = M
             M = B * Ho * Wo
@@ -330,7 +387,7 @@ class Conv2dFn(torch.autograd.Function):
                 dw = torch.empty(weight.shape, dtype=torch.float32, device=x.device)
                 _lib.check(lib.ldiff_op_unpack_wgrad(g.data_ptr(), dw.data_ptr(), Cout, Cin, k, Cx, g.shape[-1], _sp()))
         if has_bias and ctx.needs_input_grad[2]:
-            if direct and Cy % 8 == 0 and Cy <= 2048:
+            if slab_bias and Cy % 8 == 0 and Cy <= 2048:
                 db = colsum_slabs(dy)
             else:
                 db = torch.empty(Cy, dtype=torch.float32, device=x.device)

@@ -1154,6 +1154,18 @@ int ldiff_op_conv_wgrad(const void* x, const void* dy, void* dw_f32, int B, int 
   launch_conv_wgrad((const f16*)x, (const f16*)dy, (float*)dw_f32, B, H, W, Cx, Ho, Wo, Cy, Cout, Cin, k, stride, wgs, (float*)ws, ws_bytes, (hipStream_t)stream);
   API_END
 }
+// the wide convs: both channel counts blocked (kernels_wgrad_wide.hip)
+int64_t ldiff_op_conv_wgrad_wide_ws_bytes(int B, int Ho, int Wo, int Cx, int Cy, int k, int wgs) { return conv_wgrad_wide_ws_bytes(B, Ho, Wo, Cx, Cy, k, wgs); }
+int ldiff_op_conv_wgrad_wide(const void* x, const void* dy, void* dw_f32, int B, int H, int W, int Cx, int Ho, int Wo, int Cy, int Cout, int Cin, int k, int stride,
+                             int wgs, void* ws, int64_t ws_bytes, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(x, LDIFF_ERR_INVALID, "op_conv_wgrad_wide: null argument x");
+  LDIFF_CHECK(dy, LDIFF_ERR_INVALID, "op_conv_wgrad_wide: null argument dy");
+  LDIFF_CHECK(dw_f32, LDIFF_ERR_INVALID, "op_conv_wgrad_wide: null argument dw_f32");
+  LDIFF_CHECK(ws, LDIFF_ERR_INVALID, "op_conv_wgrad_wide: null argument ws");
+  launch_conv_wgrad_wide((const f16*)x, (const f16*)dy, (float*)dw_f32, B, H, W, Cx, Ho, Wo, Cy, Cout, Cin, k, stride, wgs, (float*)ws, ws_bytes, (hipStream_t)stream);
+  API_END
+}
 int64_t ldiff_op_colsum_slabs_ws_bytes(int64_t M, int N) { return colsum_slabs_ws_bytes(M, N); }
 int ldiff_op_colsum_slabs(const void* dy, void* db_f32, int64_t M, int N, int ld, void* ws, int64_t ws_bytes, void* stream) {
   API_BEGIN

@@ -384,6 +384,11 @@ void launch_sgd_nesterov_multi(const SgdTensor* tensors, const float* const* gra
 long long conv_wgrad_ws_bytes(int B, int Ho, int Wo, int Cx, int Cy, int k, int wgs);   // 0: a shape the kernel does not take
 void launch_conv_wgrad(const f16* x, const f16* dy, float* dw, int B, int H, int W, int Cx, int Ho, int Wo, int Cy, int Cout, int Cin, int k, int stride, int wgs,
                        float* ws, long long ws_bytes, hipStream_t s);
+void launch_wgrad_finalize(const float* ws, float* dw, int wgs, int CYP, int taps, int CXP, int Cout, int Cin, hipStream_t s);   // dw[n][c][tap] = sum over wg of ws[wg][n][tap][c]
+// the same contraction blocked over the channels on both sides (kernels_wgrad_wide.hip): Cx up to 1024, Cy up to 512 (k = 3) / 2048 (k = 1)
+long long conv_wgrad_wide_ws_bytes(int B, int Ho, int Wo, int Cx, int Cy, int k, int wgs);   // 0: a shape the kernel does not take
+void launch_conv_wgrad_wide(const f16* x, const f16* dy, float* dw, int B, int H, int W, int Cx, int Ho, int Wo, int Cy, int Cout, int Cin, int k, int stride, int wgs,
+                            float* ws, long long ws_bytes, hipStream_t s);
 long long colsum_slabs_ws_bytes(long long M, int N);
 void launch_colsum_slabs(const f16* dy, float* db, long long M, int N, int ld, float* ws, long long ws_bytes, hipStream_t s);
 

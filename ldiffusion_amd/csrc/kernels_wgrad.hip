@@ -286,6 +286,13 @@ void launch_conv_wgrad(const f16* x, const f16* dy, float* dw, int B, int H, int
   HIP_CHECK(hipGetLastError());
 }
 
+// the same finalize for the partials of kernels_wgrad_wide.hip: one definition of the fixed order
+void launch_wgrad_finalize(const float* ws, float* dw, int wgs, int CYP, int taps, int CXP, int Cout, int Cin, hipStream_t s) {
+  const long long n = (long long)Cout * taps * Cin;
+  hipLaunchKernelGGL(wgrad_finalize_kernel, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, s, ws, dw, wgs, CYP, taps, CXP, Cout, Cin);
+  HIP_CHECK(hipGetLastError());
+}
+
 long long colsum_slabs_ws_bytes(long long M, int N) {
   if (M < 1 || N < 8 || N % 8 != 0 || N > 2048) return 0;
   return colsum_plan(M, N).slabs * N * 4;

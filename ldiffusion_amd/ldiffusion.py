@@ -159,13 +159,14 @@ class LDiffusionModel:
         torch.cuda.empty_cache()
         return save_path
 
-    def train(self, args, component="all", ldiffusion_weight=None, train_loader=None, val_loader=None, **_ignored):
+    def train(self, args, component="all", ldiffusion_weight=None, train_loader=None, val_loader=None, wgrad_route=None, **_ignored):
         """ldiffusion.py:297-315.  The PUMA dataset / dataloader (dataset.py, cv2) is outside this build: the loaders are injected.
         `component="ldiffusion"` runs the L-Diffusion warm-up on the HIP kernels and returns the saved weight directory.  The segmentor stage
         ("segmentor", or after the warm-up with "all") at level "tissue" is `Segmentor.train_tissue_model_nnUNetv2(args.num_epochs - 10,
         ldiffusion_weight, args.diffusion_path)` with the loaders' `dataset.image_dir` / `label_dir` lists (:306-311) and returns the trained-model
         folder; loaders without such a dataset (plain lists of batches) need the four lists as keyword arguments `train_images`, `train_labels`,
-        `test_images`, `test_labels`.  `iterations_per_epoch`, `val_iterations` and `num_foreground_voxels` are handed on too.  At level "cell" it
+        `test_images`, `test_labels`.  `iterations_per_epoch`, `val_iterations` and `num_foreground_voxels` are handed on too, and so is `wgrad_route`
+        (the route of the tissue trainer's weight gradients, `nnunet_train.Trainer`'s keyword; None: its default).  At level "cell" it
         raises NotImplementedError: the cell trainer is not built."""
         if component not in ("all", "ldiffusion", "segmentor"):
             raise ValueError(f"unknown component {component!r}")
@@ -190,6 +191,8 @@ class LDiffusionModel:
                 # ldiffusion.py:306-311 hands the loaders on; their datasets hold the file lists
                 segmentor_kwargs.update(train_images=train_loader.dataset.image_dir, train_labels=train_loader.dataset.label_dir,
                                         test_images=val_loader.dataset.image_dir, test_labels=val_loader.dataset.label_dir)
+            if wgrad_route is not None:   # None: the call is the one of before the keyword existed
+                segmentor_kwargs["wgrad_route"] = wgrad_route
             return segmentor.train_tissue_model_nnUNetv2(args.num_epochs - 10, ldiffusion_weight, args.diffusion_path, **segmentor_kwargs)
         return ldiffusion_weight
 

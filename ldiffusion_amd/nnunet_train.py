@@ -109,9 +109,13 @@ class TrainableSegNet(train._Graph):
     ag.DiceCeFn reads (pad columns zero).  Lower heads missing from `state_dict` (an inference checkpoint cleaned by nnunet.clean_state_dict) start
     from `initial_state_dict`'s values."""
 
-    def __init__(self, spec: dict, state_dict, device="cuda:0", slope: float = SLOPE):
+    def __init__(self, spec: dict, state_dict, device="cuda:0", slope: float = SLOPE, wgrad_route: Optional[str] = None):
+        """`wgrad_route`: the route of the weight / bias gradients (one of ag.WGRAD_ROUTES); None = "auto"."""
         self.spec = dict(spec)
         self.slope = float(slope)
+        if wgrad_route is not None and wgrad_route not in ag.WGRAD_ROUTES:
+            raise ValueError(f"wgrad route {wgrad_route!r}: one of {ag.WGRAD_ROUTES}")
+        self.wgrad_route = "auto" if wgrad_route is None else wgrad_route
         want = nnunet.param_shapes(spec, deep_supervision=True)
         sd = dict(state_dict)
         unexpected = [k for k in sd if k not in want]
@@ -151,9 +155,9 @@ class TrainableSegNet(train._Graph):
         if x.shape[2] % div or x.shape[3] % div:
             raise ValueError(f"TrainableSegNet: input {list(x.shape[2:])} is not divisible by the product of the strides, {div}")
         n = sp["n_stages"]
-        # "auto": the convs with M = B Ho Wo >= ag.WGRAD_DIRECT_MIN_ROWS take the direct weight gradient and the slab column sum in their backward (the route is kept
-        # with each node); a route the caller has stated (ag.wgrad_route, ag.set_wgrad_route) holds instead
-        route = ag.wgrad_route(ag.stated_wgrad_route("auto"))
+        # "auto" (the constructor's default): the convs with M = B Ho Wo >= ag.WGRAD_DIRECT_MIN_ROWS take the direct weight gradient and the slab column sum in their
+        # backward (the route is kept with each node); a route the caller has stated (ag.wgrad_route, ag.set_wgrad_route) holds instead
+        route = ag.wgrad_route(ag.stated_wgrad_route(self.wgrad_route))
         with torch.cuda.device(self.device), route:
             h = train._nhwc16(x.to(self.device, torch.float32))
             skips = []
@@ -236,12 +240,12 @@ class Trainer:
 
     def __init__(self, spec: dict, state_dict, batch_dice: bool, num_epochs: int, initial_lr: float = 1e-2, weight_decay: float = 3e-5, device="cuda:0", *,
                  configuration: str = "2d", init_args: Optional[dict] = None, mirror_axes: Optional[Sequence[int]] = (0, 1), loss_scale: Optional[float] = None,
-                 slope: float = SLOPE, ddp: Optional[bool] = None, group=None):
+                 slope: float = SLOPE, ddp: Optional[bool] = None, group=None, wgrad_route: Optional[str] = None):
         """`ddp`: None follows the launch (a process group of more than one rank: nnUNetTrainer.is_ddp), True / False force it; `group` the process group
         (None: the default one).  ddp at world size 1 is legal: the collectives are identities.  `self.world` is the factor of the Dice gradient and of
         the gradient mean; code that does the two collectives by hand for several trainers in one process sets it to their number."""
         self.spec = dict(spec)
-        self.network = TrainableSegNet(spec, state_dict, device, slope)
+        self.network = TrainableSegNet(spec, state_dict, device, slope, wgrad_route)   # wgrad_route: TrainableSegNet's; None = "auto"
         self.device = self.network.device
         self.batch_dice = bool(batch_dice)
         self.num_epochs, self.initial_lr, self.weight_decay = int(num_epochs), float(initial_lr), float(weight_decay)

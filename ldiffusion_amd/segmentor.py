@@ -218,7 +218,7 @@ class Segmentor:
         return recon
 
     def train_tissue_model_nnUNetv2(self, epochs, ldiffusion_weight, diffusion_path, train_images=None, train_labels=None, test_images=None, test_labels=None,
-                                    num_classes=None, *, iterations_per_epoch=250, val_iterations=50, num_foreground_voxels=None):
+                                    num_classes=None, *, iterations_per_epoch=250, val_iterations=50, num_foreground_voxels=None, wgrad_route=None):
         """segmentor.py:163-241: the tissue head's training stage, from image lists to a trained-model folder.
         Dataset (:167-205): `load_ldiffusion`, the cached text embeddings of "A pathological slide", the text-alignment wrapper, and
         `utils.create_nnunet_dataset` under nnUNet_raw (the one-pass diffusion of every image when all share one size, else copies).
@@ -229,7 +229,7 @@ class Segmentor:
         `PatchLoader`s with the plans' patch and batch size, `nnunet_train.Trainer.run_training`; checkpoints under
         nnUNet_results/<dataset>/nnUNetTrainer__nnUNetPlans__2d/fold_0, plans.json and dataset.json beside it.
         `iterations_per_epoch`, `val_iterations`: nnUNetTrainer's 250 / 50.  `num_foreground_voxels`: the fingerprint's sample budget (None: the
-        reference's 10e7).  The three folders come from the environment variables nnUNet_raw, nnUNet_preprocessed, nnUNet_results.
+        reference's 10e7).  `wgrad_route`: `nnunet_train.Trainer`'s (None: its default).  The three folders come from the environment variables nnUNet_raw, nnUNet_preprocessed, nnUNet_results.
         Under a process group of more than one rank the stage is data-parallel, as the reference's nnUNetTrainer is under the same launch: rank 0 alone
         writes the dataset, the fingerprint, plans, split and the model folder; `(new_num, dataset_name)` go out by `broadcast_object_list` and a
         barrier; every rank then reads the PNGs and JSONs and builds both stores on its own device; its loaders take its entry of
@@ -316,7 +316,7 @@ class Segmentor:
         loaders = [nnunet_data.PatchLoader(store, spec["patch_size"], batch, n_scales, seed=seed, train=train, **extra)
                    for store, seed, train in ((stores[0], 2 * rank, True), (stores[1], 2 * rank + 1, False))]
         self.tissue_loaders = loaders
-        trainer = nnunet_train.Trainer(spec, nnunet_train.initial_state_dict(spec), cfg["batch_dice"], num_epochs=epochs, device=self.device)
+        trainer = nnunet_train.Trainer(spec, nnunet_train.initial_state_dict(spec), cfg["batch_dice"], num_epochs=epochs, device=self.device, wgrad_route=wgrad_route)
         model_dir = os.path.join(roots["nnUNet_results"], dataset_name, "nnUNetTrainer__nnUNetPlans__2d")
         if rank == 0:
             nnunet.write_trained_model_folder(model_dir, plans, dataset_json)

@@ -10,7 +10,10 @@ torch.profiler and its device time is split by kernel family (by kernel name).  
 gradient bucket, ldiff_op_sumsq, the SGD launch reading the bucket; the collectives are identities), alternating after two warm-ups.  This prices the
 data-parallel path's own launches; it says nothing about scaling.
 
-usage: python scripts/bench_nnunet_train.py [--passes 5] [--size 512] [--batch 0 (= the plans')] [--config 2d] [--ddp]
+--route R: a second library trainer with `Trainer(wgrad_route=R)` (autograd.WGRAD_ROUTES) joins the alternation -- default route, route R, torch -- and the
+profiled step is R's.  The default route's launches are those of a tree without the route, so this is the before / after of a route on one box in one call.
+
+usage: python scripts/bench_nnunet_train.py [--passes 5] [--size 512] [--batch 0 (= the plans')] [--config 2d] [--ddp] [--route auto-wide]
 """
 import argparse
 import json
@@ -31,6 +34,7 @@ from ldiffusion_amd import nnunet, nnunet_train  # noqa: E402
 FAMILIES = [("InstanceNorm + LeakyReLU (in_train)", ("in_partial", "in_apply", "in_fwd_finalize", "in_bwd_finalize")),
             ("Dice + cross-entropy (dice_ce)", ("dce_",)),
             ("SGD (sgd_nesterov_multi)", ("sgd_nesterov",)),
+            ("wide direct weight gradient (wgrad_wide; its finalize is in the next row)", ("wgrad_wide",)),
             ("direct weight gradient (wgrad_direct + finalize)", ("wgrad_direct", "wgrad_finalize")),
             ("wgrad staging: im2col_t", ("im2col_t",)),
             ("wgrad staging: transpose of dy", ("transpose_rows",)),
@@ -102,6 +106,7 @@ def main():
     ap.add_argument("--batch", type=int, default=0)
     ap.add_argument("--config", default="2d")
     ap.add_argument("--ddp", action="store_true")
+    ap.add_argument("--route", default=None, help="also time (and profile) a trainer under this weight-gradient route")
     a = ap.parse_args()
     with open(os.path.join(ROOT, "tests", "golden", "nnunet_plans_2d.json")) as f:
         plans = json.load(f)
@@ -137,6 +142,13 @@ def main():
     def run_lib():
         return tr.train_step(x, targets)
 
+    trr = None
+    if a.route is not None:
+        trr = nnunet_train.Trainer(spec, nnunet_train.initial_state_dict(spec, 0), batch_dice, 1000, device=dev, configuration=a.config, wgrad_route=a.route)
+
+    def run_route():
+        return trr.train_step(x, targets)
+
     def run_torch():
         opt.zero_grad(set_to_none=True)
         with torch.autocast("cuda", dtype=torch.float16):
@@ -151,17 +163,26 @@ def main():
 
     for _ in range(2):
         run_lib(); run_torch()
-    tl, tt = [], []
+        if trr is not None:
+            run_route()
+    tl, tt, tr_ = [], [], []
     for _ in range(a.passes):
         tl.append(timed(run_lib))
+        if trr is not None:
+            tr_.append(timed(run_route))
         tt.append(timed(run_torch))
     f = lambda v: f"median {statistics.median(v):.1f} ms (min {min(v):.1f}, max {max(v):.1f})"
+    if trr is not None:
+        print(f"{a.config} B={B} {a.size}^2, {a.passes} alternating steps: library under --route {a.route} {f(tr_)} | {a.route} / default = "
+              f"{statistics.median(tr_) / statistics.median(tl):.3f} | {a.route} / torch = {statistics.median(tr_) / statistics.median(tt):.2f}; steps: default "
+              f"{[round(v, 1) for v in tl]}, {a.route} {[round(v, 1) for v in tr_]}, torch {[round(v, 1) for v in tt]}; losses of the last step: default {run_lib():.6f}, "
+              f"{a.route} {run_route():.6f}")
     print(f"{a.config} B={B} {a.size}^2, {a.passes} alternating steps: library {f(tl)} | torch.nn under autocast(fp16) + torch.optim.SGD {f(tt)} | "
           f"library / torch = {statistics.median(tl) / statistics.median(tt):.2f}; peak device memory {torch.cuda.max_memory_allocated() / 2 ** 30:.1f} GiB; "
           f"loss scale {tr.state['loss_scale']:g}, skipped steps {tr.state.get('skipped_steps', 0)}")
     from torch.profiler import ProfilerActivity, profile
     with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        run_lib()
+        (run_lib if trr is None else run_route)()
         torch.cuda.synchronize()
     rows = [(e.key, getattr(e, "device_time_total", None) or getattr(e, "cuda_time_total", 0.0), e.count) for e in prof.key_averages()]
     rows = [r for r in rows if r[1] > 0]
@@ -173,7 +194,7 @@ def main():
         name = next((n for n, stems in FAMILIES if any(s in low for s in stems)), "torch kernels (concat, permutes, zero-insertion, norms, copies)")
         fam[name][0] += us
         fam[name][1] += count
-    print(f"one library step under torch.profiler: {total / 1e3:.1f} ms of device time in {sum(r[2] for r in rows)} launches")
+    print(f"one library step{'' if trr is None else ' under --route ' + a.route} under torch.profiler: {total / 1e3:.1f} ms of device time in {sum(r[2] for r in rows)} launches")
     for name, (us, count) in sorted(fam.items(), key=lambda kv: -kv[1][0]):
         print(f"  {name:<70} {us / 1e3:9.2f} ms  {us / total * 100:5.1f} %  x{count}")
     print("  largest kernels:")

@@ -1,0 +1,233 @@
+"""GPU (-m gpu): the wide direct weight gradient (csrc/kernels_wgrad_wide.hip; ldiff_op_conv_wgrad_wide) and the routes "wide" / "auto-wide" of
+autograd.Conv2dFn -- exact on integer data over every channel case, map, stride and workgroup count, within the derived bound of tests/wgrad_bound.py on
+random data, refusals, and one backward pass of the tissue-head trainer graded as tests/test_gpu_wgrad_direct.py grades the direct route."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import nnunet_train_ref as ref
+import test_gpu_wgrad_direct as td
+import wgrad_bound as wb
+from ldiffusion_amd import _lib, autograd as ag, nnunet, nnunet_train
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+def sp():
+    return _lib.stream_ptr()
+
+
+def run_wide(lib, x, dy, Cout, Cin, k, stride, wgs):
+    """numpy NHWC fp16 x, dy -> dw [Cout, Cin, k, k] as a float32 CPU tensor, straight through the C entry points, into NaN-filled buffers."""
+    xd, dyd = torch.from_numpy(x).to(DEV), torch.from_numpy(dy).to(DEV)
+    B, H, W, Cx = x.shape
+    _, Ho, Wo, Cy = dy.shape
+    nb = lib.ldiff_op_conv_wgrad_wide_ws_bytes(B, Ho, Wo, Cx, Cy, k, wgs)
+    assert nb == ag.wgrad_wide_plan(B, Ho, Wo, Cx, Cy, k, wgs)["ws_bytes"] > 0, "the python statement of the plan and the library's disagree"
+    ws = torch.full((nb // 4 + 4,), float("nan"), dtype=torch.float32, device=DEV)
+    dw = torch.full((Cout, Cin, k, k), float("nan"), dtype=torch.float32, device=DEV)
+    _lib.check(lib.ldiff_op_conv_wgrad_wide(_lib.ptr(xd), _lib.ptr(dyd), _lib.ptr(dw), B, H, W, Cx, Ho, Wo, Cy, Cout, Cin, k, stride, wgs, _lib.ptr(ws), nb, sp()))
+    torch.cuda.synchronize()
+    return dw.cpu()
+
+
+# ---- 1. exact integers ------------------------------------------------------------------------------------------------------------------------------
+CHANNELS = [(136, 130, 32, 32, 3), (32, 32, 72, 65, 3), (128, 128, 128, 128, 3), (64, 64, 136, 136, 3), (256, 256, 128, 128, 3), (512, 512, 256, 256, 3),
+            (1024, 1024, 512, 512, 3), (128, 128, 512, 512, 1), (512, 512, 2048, 2048, 1), (256, 256, 8, 7, 1)]   # (Cx, Cin, Cy, Cout, k)
+MAPS = [(2, 8, 8, 1), (2, 5, 33, 1)]   # (B, H, W, stride): one partial tile; an edge in both tile axes, the second column tile one pixel wide
+MAP_S2 = (2, 9, 40, 2)                 # k = 3 only: 5 x 20 outputs
+INT_CASES = [(c, m) for c in CHANNELS for m in ([MAPS[0]] if c[0] == 1024 else MAPS + ([MAP_S2] if c[4] == 3 else []))]
+
+
+@pytest.mark.parametrize("chan,shape", INT_CASES)
+def test_wide_exact_on_integers(lib, chan, shape):
+    """Integer data in [-3, 3], pad channels included: every fp32 sum is exact while 9 M < 2^24, so dw equals the float64 reference bit for bit -- with one
+    workgroup, three, the planned grid and one more than the tiles (the idle one contributes exact zeros); garbage in the pad channels of x and dy and the
+    zero padding of a partial last channel slab on either side do not leak; a second call into fresh buffers is bit-identical."""
+    Cx, Cin, Cy, Cout, k = chan
+    B, H, W, stride = shape
+    x, dy = wb.int_case(B, H, W, Cx, Cy, k, stride, 11 + Cx + Cy + H)
+    M = dy.shape[0] * dy.shape[1] * dy.shape[2]
+    assert 9 * M < 2 ** 24
+    if Cin < Cx:
+        assert np.abs(x[..., Cin:]).sum() > 0
+    if Cout < Cy:
+        assert np.abs(dy[..., Cout:]).sum() > 0
+    want64, _ = wb.wgrad_reference(x, dy, Cout, Cin, k, stride)
+    assert np.array_equal(want64, np.rint(want64))
+    want = torch.from_numpy(want64).float()
+    tiles = ag.wgrad_wide_plan(dy.shape[0], dy.shape[1], dy.shape[2], Cx, Cy, k, 0)["tiles"]
+    for wgs in (1, 3, 0, tiles + 1):
+        got = run_wide(lib, x, dy, Cout, Cin, k, stride, wgs)
+        assert got.isfinite().all(), f"wgs={wgs}: non-finite output"
+        assert torch.equal(got, want), f"wgs={wgs}: {(got.double() - want.double()).abs().max():.0f} off at most"
+        assert torch.equal(run_wide(lib, x, dy, Cout, Cin, k, stride, wgs), got), f"wgs={wgs}: a second call differs"
+
+
+# ---- 2. random data against float64 -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("Cin,Cout", [(128, 128), (512, 256)])
+def test_wide_against_float64(lib, Cin, Cout):
+    """Per element within (L + P + 2) 2^-24 sum |dy x| of float64 on the same fp16 inputs, L and P from ag.wgrad_wide_plan at wgs = 8 (tests/wgrad_bound.py)."""
+    B, H, W, k, stride = 2, 20, 40, 3, 1
+    x, dy = wb.random_case(B, H, W, Cin, Cout, k, stride, 10 + Cin + H)
+    plan = ag.wgrad_wide_plan(B, H, W, Cin, Cout, k, wb.BOUND_WGS)
+    assert len(wb.tile_rows(B, H, W, k, plan)) == plan["tiles"]
+    want, mag = wb.wgrad_reference(x, dy, Cout, Cin, k, stride)
+    got = run_wide(lib, x, dy, Cout, Cin, k, stride, wb.BOUND_WGS).double().numpy()
+    tol = wb.bound(mag, plan)
+    print(f"[wgrad_wide] B={B} {H}x{W} {Cin}->{Cout}: chain {plan['chain']}, partials {plan['partials']}: worst element at {(np.abs(got - want) / tol).max():.3f} of the bound")
+    assert (np.abs(got - want) <= tol).all()
+
+
+# ---- 3. refusals ------------------------------------------------------------------------------------------------------------------------------------
+def test_wide_refusals_name_the_argument(lib):
+    t = torch.zeros(8 * 8 * 2056, dtype=torch.float16, device=DEV)
+    dw = torch.zeros(2056 * 1032, dtype=torch.float32, device=DEV)
+    ws = torch.zeros(1 << 22, dtype=torch.float32, device=DEV)
+    big = ws.numel() * 4
+
+    def call(Cx=32, Cy=32, Cout=32, Cin=32, k=3, stride=1, H=8, Ho=8, ws_bytes=big, x=t, dy=t, out=dw, w=ws):
+        return lib.ldiff_op_conv_wgrad_wide(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(out), 1, H, H, Cx, Ho, Ho, Cy, Cout, Cin, k, stride, 0, _lib.ptr(w), ws_bytes, sp())
+
+    assert call() == 0
+    for kw, name in [(dict(k=5), "k=5"), (dict(k=1, stride=2, Ho=4), "stride=2"), (dict(Cx=1032, Cin=1032), "Cx=1032"), (dict(Cy=520, Cout=520), "Cy=520"),
+                     (dict(k=1, Cy=2056, Cout=2056), "Cy=2056"), (dict(Cout=33), "Cout=33"), (dict(Cin=33), "Cin=33"), (dict(ws_bytes=64), "ws_bytes=64"),
+                     (dict(x=None), "null argument x"), (dict(dy=None), "null argument dy"), (dict(out=None), "null argument dw"), (dict(w=None), "null argument ws"),
+                     (dict(Ho=7), "Ho=7")]:
+        assert call(**kw) == -1, kw
+        assert name in lib.ldiff_last_error().decode(), (kw, lib.ldiff_last_error().decode())
+    wsb = lib.ldiff_op_conv_wgrad_wide_ws_bytes
+    assert wsb(1, 8, 8, 1032, 32, 3, 0) == 0 and wsb(1, 8, 8, 32, 520, 3, 0) == 0 and wsb(1, 8, 8, 32, 2056, 1, 0) == 0 and wsb(1, 8, 8, 32, 32, 5, 0) == 0
+    assert wsb(1, 8, 8, 32, 32, 3, 65536) == 0 and wsb(1, 8, 8, 1024, 512, 3, 0) > 0 and wsb(1, 8, 8, 512, 2048, 1, 0) > 0
+    # the narrow entry keeps its refusal
+    assert lib.ldiff_op_conv_wgrad(_lib.ptr(t), _lib.ptr(t), _lib.ptr(dw), 1, 8, 8, 136, 8, 8, 32, 32, 136, 3, 1, 0, _lib.ptr(ws), big, sp()) == -1
+    assert "Cx=136" in lib.ldiff_last_error().decode()
+    assert lib.ldiff_op_conv_wgrad_ws_bytes(1, 8, 8, 136, 32, 3, 0) == 0
+    torch.cuda.synchronize()
+
+
+# ---- 4. the routes ----------------------------------------------------------------------------------------------------------------------------------
+ROUTE_CASE = td.ROUTE_CASES[0]   # ("2d_reduced", 2, 64, 41): slope 1.0, loss scale 1024
+assert ROUTE_CASE == ("2d_reduced", 2, 64, 41)
+# Measured on the MI355X under wgrad_route("wide") (DESIGN.md section 7 "Wide weight gradients"): the worst ratio over the weight tensors the WIDE entry forms of
+# max |g - g64| / max |g64| of the library to the fp16-storage model's.  Asserted: twice the measured ratio, at most td.M_CAP = 2.0.
+#   64^2, 8 tensors on the wide entry (ratios 0.877 -- 1.289): worst encoder.stages.2.0.convs.0.conv.weight (64 -> 128, stride 2), library 1.662e-3 / model 1.290e-3 = 1.289;
+#   decoder.stages.0.convs.1.conv.weight 1.247, decoder.transpconvs.0.weight 1.119, the other five below 1.  Twice 1.289 exceeds the cap, so 2.0 is asserted.
+MEASURED_WIDE = 1.289
+
+
+def _inputs(config, B, size, seed):
+    """The network, batch and targets of td.route_case, which keeps them to itself."""
+    with open(os.path.join(td.GOLDEN, "nnunet_plans_2d.json")) as f:
+        plans = json.load(f)
+    with open(os.path.join(td.GOLDEN, "nnunet_dataset.json")) as f:
+        ds = json.load(f)
+    spec = nnunet.network_spec(plans, config, ds)
+    sd = ref.synthetic_state_dict(spec, seed)
+    g = torch.Generator().manual_seed(seed + 100)
+    x = F.avg_pool2d(torch.randn((B, 3, size + 4, size + 4), generator=g), 5, 1) * 2.2
+    targets = ref.label_maps(B, spec["n_heads"], size, spec["n_stages"] - 1, seed + 200)
+    return spec, sd, x, targets, bool(plans["configurations"]["2d"]["batch_dice"])
+
+
+def _entry_of(name, shape):
+    """Which weight-gradient entry a parameter's launch is eligible for: "narrow", "wide" or None (a conv weight [Cout, Cin, k, k] at either stride; a transposed
+    conv [Cin, Cout, 2, 2] runs as a linear with 4 Cout output columns)."""
+    if ".transpconvs." in name:
+        k, Cin, Cout = 1, shape[0], 4 * shape[1]
+    else:
+        k, Cin, Cout = shape[2], shape[1], shape[0]
+    Cx, Cy = -(-Cin // 8) * 8, -(-Cout // 8) * 8
+    if ag.wgrad_direct_eligible(k, 1, 0, Cx, Cy, Cout, Cin):
+        return "narrow"
+    return "wide" if ag.wgrad_wide_eligible(k, 1, 0, Cx, Cy, Cout, Cin) else None
+
+
+def test_trainer_backward_on_the_wide_route():
+    """One backward pass under wgrad_route("wide"): norm gradients equal the staged run's bit for bit; every bias gradient and every weight gradient the narrow
+    entry takes equal the "direct" run's bit for bit; the weight gradients the wide entry forms are graded against the float64 tape relative to the
+    fp16-storage model, as tests/test_gpu_wgrad_direct.py grades the direct route."""
+    config, B, size, seed = ROUTE_CASE
+    c = td.route_case(config, B, size, seed)
+    staged, direct = c["runs"]["staged"], c["runs"]["direct"]
+    spec, sd, x, targets, batch_dice = _inputs(config, B, size, seed)
+    tr = nnunet_train.Trainer(spec, sd, batch_dice, 10, device=DEV, slope=1.0)
+    with ag.wgrad_route("wide"):
+        tr.loss(tr.network(x), [t.to(DEV) for t in targets], td.LOSS_SCALE).backward()
+    torch.cuda.synchronize()
+    wide = {k: (None if p.grad is None else p.grad.detach().cpu()) for k, p in tr.network.p.items()}
+    rows, moved = [], 0
+    for k, g64 in c["f64"].items():
+        assert (g64 is None) == (wide[k] is None)
+        if g64 is None:
+            continue
+        if not td._is_contraction_param(k):
+            assert torch.equal(wide[k], staged[k]), f"{k}: the wide route changed a gradient it does not compute"
+            continue
+        entry = None if k.endswith(".bias") else _entry_of(k, tuple(wide[k].shape))
+        if entry != "wide":
+            assert entry == "narrow" or k.endswith(".bias"), f"{k}: no direct entry takes it"
+            assert torch.equal(wide[k], direct[k]), f"{k}: differs from the direct route's ({'bias' if entry is None else 'narrow entry'})"
+            continue
+        assert torch.equal(direct[k], staged[k]), f"{k}: the direct route did not leave it staged"
+        moved += int(not torch.equal(wide[k], staged[k]))
+        gl, gm_ = wide[k].double() / td.LOSS_SCALE, c["model"][k]
+        rows.append((k, ((gl - g64).abs().max() / g64.abs().max()).item(), ((gm_ - g64).abs().max() / g64.abs().max()).item()))
+    assert rows and moved == len(rows), f"{moved} of {len(rows)} wide tensors differ from the staged run: the wide entry did not run for all"
+    worst = max(rows, key=lambda r: r[1] / r[2])
+    print(f"[route] {config} B={B} {size}^2 wide: {len(rows)} tensors on the wide entry, worst {worst[0]}: lib {worst[1]:.3e} model {worst[2]:.3e} ratio {worst[1] / worst[2]:.3f}")
+    for k, e_lib, e_model in rows:
+        print(f"[route]   {k}: lib {e_lib:.3e} model {e_model:.3e} ratio {e_lib / e_model:.3f}")
+    m =min(td.M_CAP, 2.0 * MEASURED_WIDE)
+    for k, e_lib, e_model in rows:
+        assert e_lib <= m * e_model, f"{k}: library {e_lib:.3e}, fp16-storage model {e_model:.3e}: {e_lib / e_model:.2f} x (asserted {m:.2f} x)"
+
+
+def test_train_hands_a_stated_route_to_the_segmentor_stage(tmp_path, monkeypatch):
+    """LDiffusionModel.train names `wgrad_route` (it swallows unknown keywords): a stated route reaches Segmentor.train_tissue_model_nnUNetv2, None adds nothing to the call."""
+    from types import SimpleNamespace
+
+    from ldiffusion_amd.ldiffusion import LDiffusionModel
+    from ldiffusion_amd.segmentor import Segmentor
+    calls = []
+    monkeypatch.setattr(Segmentor, "train_tissue_model_nnUNetv2", lambda self, epochs, weight, path, **kw: calls.append(kw) or "model-folder")
+    args = SimpleNamespace(num_epochs=12, diffusion_path="sd", num_classes=7)
+    lists = dict(train_images=["a.png"], train_labels=["a_l.png"], test_images=["b.png"], test_labels=["b_l.png"])
+    model = LDiffusionModel(str(tmp_path), "tissue")
+    assert model.train(args, component="segmentor", ldiffusion_weight="w", wgrad_route="auto-wide", **lists) == "model-folder"
+    assert model.train(args, component="segmentor", ldiffusion_weight="w", **lists) == "model-folder"
+    assert calls == [dict(lists, wgrad_route="auto-wide"), lists]
+
+
+def test_trainer_step_under_auto_wide_moves_only_bias_gradients():
+    """Trainer(wgrad_route="auto-wide").train_step against wgrad_route=None on one batch of 2 x 64^2: no launch reaches WGRAD_WIDE_MIN_ROWS (nor
+    WGRAD_DIRECT_MIN_ROWS), so every weight and norm gradient, the loss and the skipped-step count are equal bit for bit; the bias gradients come from the
+    slab column sum and may differ."""
+    config, B, size, seed = ROUTE_CASE
+    assert B * size * size < min(ag.WGRAD_WIDE_MIN_ROWS, ag.WGRAD_DIRECT_MIN_ROWS) and ag.WGRAD_WIDE_MIN_ROWS >= 16384
+    spec, sd, x, targets, batch_dice = _inputs(config, B, size, seed)
+    out = {}
+    for route in (None, "auto-wide"):
+        tr = nnunet_train.Trainer(spec, sd, batch_dice, 10, device=DEV, slope=1.0, loss_scale=td.LOSS_SCALE, wgrad_route=route)
+        loss = tr.train_step(x, targets)
+        torch.cuda.synchronize()
+        out[route] = (loss, tr.state.get("skipped_steps", 0), {k: (None if p.grad is None else p.grad.detach().cpu()) for k, p in tr.network.p.items()})
+    (l0, s0, g0), (l1, s1, g1) = out[None], out["auto-wide"]
+    assert l0 == l1 and s0 == s1 == 0
+    bias_moved = 0
+    for k, g in g0.items():
+        if g is None:
+            assert g1[k] is None
+        elif td._is_contraction_param(k) and k.endswith(".bias"):
+            bias_moved += int(not torch.equal(g1[k], g))
+        else:
+            assert torch.equal(g1[k], g), f"{k} differs under auto-wide below the threshold"
+    print(f"[route] auto-wide at {B} x {size}^2: {bias_moved} bias gradients differ in their bits from the default route's")
+    assert bias_moved > 0, "every bias gradient has the staged column sum's bits: the slab column sum did not run"
+    with pytest.raises(ValueError, match="wgrad route"):
+        nnunet_train.Trainer(spec, sd, batch_dice, 10, device=DEV, wgrad_route="widest")
