@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define LDIFF_VERSION 210 /* 0.2.1.0: + ldiff_op_window_gather / _accumulate_batch / _finish (the tissue head's sliding window in batches: tiles x mirror variants gathered, un-flipped, averaged and Gaussian-accumulated per chunk, then divide + inf flag + arg-max + un-crop in one launch; ldiff_window_tiles by value), after ldiff_op_dice_ce_stats / _from_sums, ldiff_op_bucket_pack, ldiff_op_sumsq (data-parallel tissue training); 0.2.0.9: + ldiff_op_case_bbox / _stats / _counts / _apply / _rank_to_coord (plan and preprocess of the tissue head's training cases on the device: non-zero box, crop statistics, label counts per row, normalise into the arena, rank -> pixel); 0.2.0.8: + ldiff_op_seg_intensity_lr (the intensity chain with nnU-Net's low-resolution simulation between contrast and the gammas), ldiff_op_spline_prefilter (cubic B-spline prefilter on the device, one workgroup per plane); 0.2.0.7: + ldiff_op_conv_wgrad (direct MFMA weight gradient of the narrow convs over the pixel index, no im2col), ldiff_op_colsum_slabs (slab-reduced bias gradient), both with fixed-order partials; 0.2.0.6: + ldiff_op_seg_sample (patches, labels and deep-supervision targets of a training batch from cases resident on the device), ldiff_op_seg_intensity (nnU-Net's intensity augmentations, one workgroup per plane); 0.2.0.5: + ldiff_unet_set_plan_batch / ldiff_vae_set_plan_batch / ldiff_controlnet_set_plan_batch (batch-invariant mode: every launch planned for a nominal batch), ldiff_op_conv_pb, ldiff_op_attention_pb, ldiff_op_gn_stats_pb; 0.2.0.4: + ldiff_op_in_train_fwd / _bwd (InstanceNorm + LeakyReLU with saved statistics), ldiff_op_dice_ce (nnU-Net deep-supervision loss of one scale, value and gradient), ldiff_op_sgd_nesterov_multi; 0.2.0.3: + ldiff_confusion (per-image confusion matrices of masks or logits against labels, accumulated on the device), ldiff_seg_metrics (host: Dice / IoU / pixel accuracy / frequency-weighted IoU from one matrix); 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
+#define LDIFF_VERSION 211 /* 0.2.1.0: + ldiff_op_window_gather / _accumulate_batch / _finish (the tissue head's sliding window in batches: tiles x mirror variants gathered, un-flipped, averaged and Gaussian-accumulated per chunk, then divide + inf flag + arg-max + un-crop in one launch; ldiff_window_tiles by value), after ldiff_op_dice_ce_stats / _from_sums, ldiff_op_bucket_pack, ldiff_op_sumsq (data-parallel tissue training); 0.2.0.9: + ldiff_op_case_bbox / _stats / _counts / _apply / _rank_to_coord (plan and preprocess of the tissue head's training cases on the device: non-zero box, crop statistics, label counts per row, normalise into the arena, rank -> pixel); 0.2.0.8: + ldiff_op_seg_intensity_lr (the intensity chain with nnU-Net's low-resolution simulation between contrast and the gammas), ldiff_op_spline_prefilter (cubic B-spline prefilter on the device, one workgroup per plane); 0.2.0.7: + ldiff_op_conv_wgrad (direct MFMA weight gradient of the narrow convs over the pixel index, no im2col), ldiff_op_colsum_slabs (slab-reduced bias gradient), both with fixed-order partials; 0.2.0.6: + ldiff_op_seg_sample (patches, labels and deep-supervision targets of a training batch from cases resident on the device), ldiff_op_seg_intensity (nnU-Net's intensity augmentations, one workgroup per plane); 0.2.0.5: + ldiff_unet_set_plan_batch / ldiff_vae_set_plan_batch / ldiff_controlnet_set_plan_batch (batch-invariant mode: every launch planned for a nominal batch), ldiff_op_conv_pb, ldiff_op_attention_pb, ldiff_op_gn_stats_pb; 0.2.0.4: + ldiff_op_in_train_fwd / _bwd (InstanceNorm + LeakyReLU with saved statistics), ldiff_op_dice_ce (nnU-Net deep-supervision loss of one scale, value and gradient), ldiff_op_sgd_nesterov_multi; 0.2.0.3: + ldiff_confusion (per-image confusion matrices of masks or logits against labels, accumulated on the device), ldiff_seg_metrics (host: Dice / IoU / pixel accuracy / frequency-weighted IoU from one matrix); 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
 #define LDIFF_MAX_BLOCKS 8
 
 typedef enum { LDIFF_OK = 0, LDIFF_ERR_INVALID = -1, LDIFF_ERR_RUNTIME = -2, LDIFF_ERR_STATE = -3, LDIFF_ERR_NONFINITE = -4 } ldiff_status;
@@ -221,6 +221,22 @@ int ldiff_resnet_set_graph(ldiff_resnet*, int on);
 int64_t ldiff_resnet_graph_replays(ldiff_resnet*);
 /* crops [B, S, S, 8] f16 NHWC (channels 3..7 zero: ldiff_op_crop_resize_norm), S % 32 == 0 -> logits [B, num_classes] f32, labels [B] i32 (may be NULL) = 1 + argmax(logits[:, 1:]) */
 int ldiff_resnet_forward(ldiff_resnet*, const void* crops_nhwc_f16, int B, int S, void* logits_f32, void* labels_i32_or_null, void* stream);
+/* Training mode (the reference's `self.model.train()`: every BatchNorm of the trunk normalises with the statistics of the batch it is given).
+ * ldiff_resnet_set_train(h, 1) BEFORE the tensors are loaded (afterwards LDIFF_ERR_STATE: the fold consumes the host tensors): the handle then also keeps every conv's UN-folded
+ * weight matrix (fp16, the same K-major layout, one rounding of w) and the fp32 gamma / beta of every BatchNorm on the device.  ldiff_resnet_forward on such a handle is unchanged
+ * bit for bit (it reads the folded matrices).
+ * The BatchNorms in forward order -- stem, then per block bn1, bn2, bn3 and, in a layer's first block, downsample.1 behind them -- share one flat channel axis of T =
+ * ldiff_resnet_bn_channels entries (ResNet152: 75712); ldiff_resnet_bn_entry(h, i, ...) names BatchNorm i by its checkpoint prefix ("encoder.6.3.bn2"; the pointer lives as long as
+ * the handle), its offset on that axis and its channel count, LDIFF_ERR_INVALID past the last.
+ * ldiff_resnet_forward_train: the trunk with batch statistics over ALL B crops, three launches per conv (clsconv with ldiff_conv_args.bn_stats -> bn_finalize -> bn_apply, which
+ * carries the ReLU and a block's identity), the adapter conv and the pooling / head as in eval mode.  Eager launches, no graph.  batch_stats_f32 [2][T] receives every BatchNorm's
+ * batch mean and UNBIASED variance (what torch's running statistics take with momentum 0.1); the handle's running statistics are not touched.  features_f32 [B][adapter_channels] =
+ * the pooled adapter map; logits / labels optional.  A BatchNorm with B * H * W == 1 values per channel is refused naming the layer (LDIFF_ERR_INVALID), before any launch. */
+int ldiff_resnet_set_train(ldiff_resnet*, int on);
+int64_t ldiff_resnet_bn_channels(ldiff_resnet*);
+int ldiff_resnet_bn_entry(ldiff_resnet*, int i, const char** name, int64_t* offset, int* channels);
+int ldiff_resnet_forward_train(ldiff_resnet*, const void* crops_nhwc_f16, int B, int S, void* batch_stats_f32, void* features_f32, void* logits_f32_or_null, void* labels_i32_or_null,
+                               void* stream);
 int ldiff_resnet_check_finite(ldiff_resnet*, void* stream);
 void ldiff_resnet_destroy(ldiff_resnet*);
 
@@ -498,6 +514,12 @@ typedef struct {
   int cls_conv;                                     /* that family: 0 = the executors' choice (the eligible launches that ask for relu_out; a plain launch of such a shape goes where it
                                                        always went), 1 = every eligible launch (the classifier's convs without a ReLU; the only route of ks = 7; tests, timing),
                                                        -1 = never (relu_out is then refused) */
+  void* bn_stats;                                   /* optional f32 [N][R][2] (8-byte aligned): training-mode BatchNorm partials of the classifier's conv family.  Needs cls_conv = 1 and a launch
+                                                       that family takes, without bias, res and relu_out (anything else: LDIFF_ERR_INVALID).  Beside the raw fp16 output the launch writes
+                                                       bn_stats[(n * R + r) * 2 + {0, 1}] = {sum, sum of squares} of the FP32 accumulators of channel n over the valid rows of row block
+                                                       r = 4 * workgroup + wave (64 or 16 rows each), R = ldiff_op_conv_bn_stats_blocks; blocks past M hold zeros.  No atomics, bit-reproducible.
+                                                       Not the per-image layout of `stats`, which keeps its meaning and its routes.  (Beside the family's other two fields and not
+                                                       behind act_out: the layout of the struct changed with LDIFF_VERSION 211, callers are recompiled against it) */
   int fold_gn;                                      /* 1: plan the launch as the executors plan a GroupNorm -> 1x1 conv / Linear without activation: where the LDS-DMA GEMM takes
                                                        per-image weights (ks = 1, one source, no silu_in / lrelu_in / GEGLU / fp32 output / statistics, K % 64 == 0, 64 | Hout * Wout)
                                                        gn_scale / gn_shift are folded into W_b = W diag(scale_b), bias_b = bias + W shift_b by the fold kernel (profiler row
@@ -515,6 +537,20 @@ int ldiff_op_conv(const ldiff_conv_args*, void* stream);
 int ldiff_op_conv_pb(const ldiff_conv_args*, int plan_batch, void* stream);
 /* row blocks per image the launch would emit statistics for (0 = unsupported for this shape) */
 int ldiff_op_conv_stats_blocks(const ldiff_conv_args*);
+/* R of ldiff_conv_args.bn_stats for the tile the plan picks for this launch: 4 * ceil(M / 64) or 4 * ceil(M / 256) (negative: the status of a launch the family refuses) */
+int ldiff_op_conv_bn_stats_blocks(const ldiff_conv_args*);
+/* Training-mode BatchNorm behind such a launch (kernels_clstrain.hip), eps 1e-5.
+ * bn_finalize: part f32 [N][R][2] -> per channel the R partials added in index order in double; mean = sum / n, var = max(sumsq / n - mean^2, 0) (biased);
+ *   scale[c] = gamma[c] / sqrt(var + eps), shift[c] = beta[c] - mean * scale (fp32, one rounding each); batch_stats[offset + c] = mean and
+ *   batch_stats[T + offset + c] = var * n / (n - 1) (the UNBIASED variance torch's running_var takes), fp32, batch_stats a flat f32 [2][T].
+ *   n < 2: LDIFF_ERR_INVALID before any launch (torch: "Expected more than 1 value per channel when training").
+ * bn_apply: y[m, c] = fp16(relu?(x[m, c] * scale[c] + shift[c] + id)) over [M, N] fp16 (N % 8 == 0, pointers 16-byte aligned), one launch; id = nothing (id NULL),
+ *   id[m, c] (a plain fp16 tensor: id_scale NULL) or id[m, c] * id_scale[c] + id_shift[c] (a second raw tensor with its own BatchNorm).  fp32 throughout, one rounding;
+ *   *nonfinite_i32_or_null (device or host-mapped) is set to 1 where the fp32 value is NaN or beyond 65504, in front of the ReLU. */
+int ldiff_op_bn_finalize(const void* part_f32, int R, int N, int64_t n, const void* gamma_f32, const void* beta_f32, void* scale_f32, void* shift_f32, void* batch_stats_f32,
+                         int64_t offset, int64_t T, void* stream);
+int ldiff_op_bn_apply(const void* x_f16, int64_t M, int N, const void* scale_f32, const void* shift_f32, const void* id_f16_or_null, const void* id_scale_f32_or_null,
+                      const void* id_shift_f32_or_null, int relu, void* y_f16, void* nonfinite_i32_or_null, void* stream);
 /* finalize producer-fused partial sums into per-(b,channel) scale/shift; part2 (second concat source) may be NULL */
 int ldiff_op_gn_finalize(const void* part1, int R1, int C1, const void* part2, int R2, int C2, int B, int HW, int groups, float eps,
                          const void* gamma, const void* beta, void* scale, void* shift, void* stream);
@@ -534,6 +570,9 @@ int ldiff_op_maxpool3x3s2(const void* x, void* y, int B, int H, int W, int C, vo
 int ldiff_op_crop_resize_norm(const void* rgb_u8, int H, int W, const void* boxes_i32, int n, const void* lut_u8, int S, const double* mean3, const double* std3, void* out_f16,
                               void* stream);
 int ldiff_op_cls_head(const void* x, int B, int HW, int A, int ldx, const void* w_f32, const void* bias_f32, int C, void* logits_f32, void* labels_i32_or_null, void* stream);
+/* cls_head with one more optional output: features_f32 [B, A], the fp32 mean over the map the logits are computed from.  logits / labels: bit for bit ldiff_op_cls_head's. */
+int ldiff_op_cls_head_feat(const void* x, int B, int HW, int A, int ldx, const void* w_f32, const void* bias_f32, int C, void* logits_f32_or_null, void* labels_i32_or_null,
+                           void* features_f32_or_null, void* stream);
 int ldiff_op_attention(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, int B, int heads,
                        int Lq, int Lk, int d, int64_t q_bstride, int64_t kv_bstride, int64_t o_bstride, float scale, void* stream);
 /* ldiff_op_attention with a plan batch (ldiff_unet_set_plan_batch): plan_batch = 0 is ldiff_op_attention; n >= B chooses the kernel as if the batch were n */

@@ -44,7 +44,7 @@ class ConvArgs(C.Structure):
                 ("lo8_slab0", C.c_int), ("lo8_scale", C.c_void_p), ("gemm_df", C.c_int),
                 ("sc_x", C.c_void_p), ("sc_C", C.c_int), ("sc_ld", C.c_int), ("sc_w", C.c_void_p), ("sc_bias", C.c_void_p), ("c3d_ups", C.c_int), ("n_real", C.c_int), ("splitk", C.c_int),
                 ("out_shift", C.c_int), ("silu_out", C.c_int), ("cond_conv", C.c_int), ("lrelu_in", C.c_int), ("tconv", C.c_int), ("seg_conv", C.c_int),
-                ("relu_out", C.c_int), ("cls_conv", C.c_int), ("fold_gn", C.c_int), ("act_out", C.c_int)]
+                ("relu_out", C.c_int), ("cls_conv", C.c_int), ("bn_stats", C.c_void_p), ("fold_gn", C.c_int), ("act_out", C.c_int)]
 
 
 class SegMetricsOut(C.Structure):
@@ -122,6 +122,10 @@ SIGNATURES = {
     "ldiff_resnet_set_graph": (I, [P, I]),
     "ldiff_resnet_graph_replays": (I64, [P]),
     "ldiff_resnet_forward": (I, [P, P, I, I, P, P, P]),
+    "ldiff_resnet_set_train": (I, [P, I]),
+    "ldiff_resnet_bn_channels": (I64, [P]),
+    "ldiff_resnet_bn_entry": (I, [P, I, C.POINTER(C.c_char_p), C.POINTER(I64), C.POINTER(I)]),
+    "ldiff_resnet_forward_train": (I, [P, P, I, I, P, P, P, P, P]),
     "ldiff_resnet_check_finite": (I, [P, P]),
     "ldiff_resnet_destroy": (None, [P]),
     "ldiff_textenc_create": (I, [C.POINTER(P), C.POINTER(TextEncCfg), I]),
@@ -168,11 +172,15 @@ SIGNATURES = {
     "ldiff_op_conv": (I, [C.POINTER(ConvArgs), P]),
     "ldiff_op_conv_pb": (I, [C.POINTER(ConvArgs), I, P]),
     "ldiff_op_conv_stats_blocks": (I, [C.POINTER(ConvArgs)]),
+    "ldiff_op_conv_bn_stats_blocks": (I, [C.POINTER(ConvArgs)]),
+    "ldiff_op_bn_finalize": (I, [P, I, I, I64, P, P, P, P, P, I64, I64, P]),
+    "ldiff_op_bn_apply": (I, [P, I64, I, P, P, P, P, P, I, P, P, P]),
     "ldiff_op_gn_finalize": (I, [P, I, I, P, I, I, I, I, I, F, P, P, P, P, P]),
     "ldiff_op_in_finalize": (I, [P, I, P, I, I, I, I, F, P, P, P, P, I, I, I, P]),
     "ldiff_op_maxpool3x3s2": (I, [P, P, I, I, I, I, P]),
     "ldiff_op_crop_resize_norm": (I, [P, I, I, P, I, P, I, C.POINTER(C.c_double), C.POINTER(C.c_double), P, P]),
     "ldiff_op_cls_head": (I, [P, I, I, I, I, P, P, I, P, P, P]),
+    "ldiff_op_cls_head_feat": (I, [P, I, I, I, I, P, P, I, P, P, P, P]),
     "ldiff_op_attention": (I, [P, I, P, I, P, I, P, I, I, I, I, I, I, I64, I64, I64, F, P]),
     "ldiff_op_attention_pb": (I, [P, I, P, I, P, I, P, I, I, I, I, I, I, I64, I64, I64, F, I, P]),
     "ldiff_op_attention_prescaled": (I, [P, I, P, I, P, I, P, I, I, I, I, I, I, I64, I64, I64, P]),

@@ -150,6 +150,46 @@ def build_lut(mean=IMAGENET_MEAN, std=IMAGENET_STD):
     return lut
 
 
+def instance_targets(label_map, mask, num_classes):
+    """The training target of every kept instance (the instances and the order of `instance_boxes`): int64 [n], the majority class among the classes
+    1 .. C - 1 of the mask's pixels under the instance, a tie to the lowest class, -1 where the instance covers no foreground pixel of the mask.
+    A mask of another size than the label map is resized with nearest neighbour first, as the reference's MicroDiceLoss resizes its targets
+    (model/loss.py:144-145: F.interpolate(mode="nearest"))."""
+    label_map = torch.as_tensor(label_map)
+    mask = torch.as_tensor(mask).to(label_map.device)
+    if mask.dim() != 2:
+        raise ValueError(f"instance_targets: mask must be [H, W], got {list(mask.shape)}")
+    if tuple(mask.shape) != tuple(label_map.shape):
+        mask = torch.nn.functional.interpolate(mask[None, None].float(), size=tuple(label_map.shape), mode="nearest")[0, 0]
+    mask = mask.to(torch.int64).reshape(-1)
+    ids, inv, keep, _ = _instance_table(label_map)
+    C_ = int(num_classes)
+    fg = (mask >= 1) & (mask < C_)
+    counts = torch.zeros((ids.numel(), C_), dtype=torch.int64, device=label_map.device)
+    counts.view(-1).scatter_add_(0, inv[fg] * C_ + mask[fg], torch.ones(int(fg.sum()), dtype=torch.int64, device=label_map.device))
+    counts = counts[keep][:, 1:]
+    best = counts.max(dim=1).values
+    first = (counts == best[:, None]).to(torch.int64).argmax(dim=1)      # the first maximum = the lowest class of a tie
+    return torch.where(best > 0, first + 1, torch.full_like(first, -1))
+
+
+def ema_update(state_dict, bn_layout, batch_mean, batch_var, momentum=0.1):
+    """What one training-mode forward does to the BatchNorms' buffers in torch: running = (1 - momentum) * running + momentum * batch, in float32, the
+    variance being the UNBIASED batch variance (`ResNetClassifier.forward_train` returns that), and `num_batches_tracked` += 1 (int64).
+    `bn_layout`: (prefix, offset, channels) per BatchNorm; batch_mean / batch_var: flat [T].  Updates `state_dict` in place and returns it."""
+    bm = torch.as_tensor(batch_mean).detach().to("cpu", torch.float32)
+    bv = torch.as_tensor(batch_var).detach().to("cpu", torch.float32)
+    m = torch.tensor(momentum, dtype=torch.float32)
+    for prefix, off, ch in bn_layout:
+        for name, batch in (("running_mean", bm), ("running_var", bv)):
+            run = state_dict[f"{prefix}.{name}"].detach().to("cpu", torch.float32)
+            # torch's kernel: running = momentum * batch + (1 - momentum) * running
+            state_dict[f"{prefix}.{name}"] = m * batch[off:off + ch] + (1 - m) * run
+        k = f"{prefix}.num_batches_tracked"
+        state_dict[k] = (torch.as_tensor(state_dict[k]).to(torch.int64) if k in state_dict else torch.zeros((), dtype=torch.int64)) + 1
+    return state_dict
+
+
 def _default_instances():
     """Cellpose `cyto2`, built lazily as conductor.py:156-160, 180 does; RuntimeError naming `instances=` where cellpose is not installed."""
     try:
@@ -168,9 +208,12 @@ def _default_instances():
 class CellSegClassifier:
     """`head(model_input [1, 3, H, W] normalised float) -> [1, C, H, W]` one-hot float, the protocol of `Segmentor.inference_cell_model(head=)`,
     and `predict_mask(rgb_u8 [H, W, 3] uint8, labels=None, instances=None) -> uint8 [H, W]` on the device.  `instances`: callable mapping the normalised HWC
-    float32 image (numpy) to an int label map; absent, Cellpose `cyto2` if it imports, else RuntimeError."""
+    float32 image (numpy) to an int label map; absent, Cellpose `cyto2` if it imports, else RuntimeError.
+    input_norm=False is the input convention of the reference's TRAINING loop (segmentor.py:263-268, 280-283): the head is handed the augmented image in
+    [0, 1], not the ImageNet-normalised one, so `(patch * 255).astype(np.uint8)` is the identity on grey levels (the identity table) and `instances` gets
+    the [0, 1] image.  train=True builds the classifier with `ResNetClassifier(train=True)`."""
 
-    def __init__(self, num_classes, state_dict, device=None, instances=None, layers=None, width=None, adapter_channels=None, crop_size=64):
+    def __init__(self, num_classes, state_dict, device=None, instances=None, layers=None, width=None, adapter_channels=None, crop_size=64, input_norm=True, train=False):
         from .models import ResNetClassifier
         nc, lay, wid, ad = infer_spec(state_dict)
         layers = tuple(layers) if layers is not None else lay
@@ -183,11 +226,12 @@ class CellSegClassifier:
         check_state_dict(state_dict, num_classes, layers, width, adapter_channels)
         self.num_classes = int(num_classes)
         self.crop_size = int(crop_size)
-        self.net = ResNetClassifier(num_classes, state_dict, device, layers, width, adapter_channels)
+        self.net = ResNetClassifier(num_classes, state_dict, device, layers, width, adapter_channels, train=train)
         self.device = self.net.device
+        self.input_norm = bool(input_norm)
         self._instances = instances   # the default of this head; predict_mask(instances=) / head(x, instances=) name another for ONE call
         self._cellpose = None
-        self._lut = torch.from_numpy(build_lut()).to(self.device)
+        self._lut = torch.from_numpy(build_lut() if self.input_norm else build_lut((0.0, 0.0, 0.0), (1.0, 1.0, 1.0))).to(self.device)
         self._mean = (C.c_double * 3)(*IMAGENET_MEAN)
         self._std = (C.c_double * 3)(*IMAGENET_STD)
 
@@ -199,7 +243,10 @@ class CellSegClassifier:
             instances = self._cellpose
         mean = torch.tensor(IMAGENET_MEAN, device=rgb_u8.device, dtype=torch.float32)
         std = torch.tensor(IMAGENET_STD, device=rgb_u8.device, dtype=torch.float32)
-        image = ((rgb_u8.to(torch.float32) / 255.0 - mean) / std).cpu().numpy()     # what the reference hands self.model (segmentor.py:533-535)
+        image = rgb_u8.to(torch.float32) / 255.0
+        if self.input_norm:
+            image = (image - mean) / std
+        image = image.cpu().numpy()     # what the reference hands self.model (segmentor.py:533-535; the training loop: the [0, 1] image, :265)
         labels = instances(image)
         return labels if torch.is_tensor(labels) else torch.from_numpy(np.asarray(labels).astype(np.int64))
 

@@ -267,6 +267,28 @@ int ldiff_resnet_forward(ldiff_resnet* r, const void* crops, int B, int S, void*
   r->forward((const f16*)crops, B, S, (float*)logits, (int*)labels, (hipStream_t)stream);
   API_END
 }
+int ldiff_resnet_set_train(ldiff_resnet* r, int on) {
+  API_BEGIN
+  LDIFF_CHECK(r, LDIFF_ERR_INVALID, "resnet_set_train: null handle");
+  r->set_train(on != 0);
+  API_END
+}
+int64_t ldiff_resnet_bn_channels(ldiff_resnet* r) { return r ? r->bn_total : -1; }
+int ldiff_resnet_bn_entry(ldiff_resnet* r, int i, const char** name, int64_t* offset, int* channels) {
+  API_BEGIN
+  LDIFF_CHECK(r && name && offset && channels, LDIFF_ERR_INVALID, "resnet_bn_entry: null argument");
+  LDIFF_CHECK(i >= 0 && i < (int)r->bn_order.size(), LDIFF_ERR_INVALID, "resnet_bn_entry: index %d outside the %d BatchNorms of this network", i, (int)r->bn_order.size());
+  const ClsConvW& c = r->convs[r->bn_order[i]];
+  *name = c.bn.c_str(); *offset = c.bn_off; *channels = c.Cout;
+  API_END
+}
+int ldiff_resnet_forward_train(ldiff_resnet* r, const void* crops, int B, int S, void* batch_stats, void* features, void* logits, void* labels, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(r, LDIFF_ERR_INVALID, "resnet_forward_train: null handle");
+  report_nonfinite(r->nf, "resnet_forward_train");
+  r->forward_train((const f16*)crops, B, S, (float*)batch_stats, (float*)features, (float*)logits, (int*)labels, (hipStream_t)stream);
+  API_END
+}
 int ldiff_resnet_check_finite(ldiff_resnet* r, void* stream) { return check_finite(r, stream, "resnet_check_finite"); }
 void ldiff_resnet_destroy(ldiff_resnet* r) { destroy(r); }
 // ---- CLIP text encoder of the prompt path ----
@@ -316,6 +338,13 @@ int ldiff_op_crop_resize_norm(const void* rgb_u8, int H, int W, const void* boxe
 int ldiff_op_cls_head(const void* x, int B, int HW, int A, int ldx, const void* w_f32, const void* bias_f32, int C, void* logits_f32, void* labels_i32_or_null, void* stream) {
   API_BEGIN
   launch_cls_head((const f16*)x, B, HW, A, ldx, (const float*)w_f32, (const float*)bias_f32, C, (float*)logits_f32, (int*)labels_i32_or_null, (hipStream_t)stream);
+  API_END
+}
+int ldiff_op_cls_head_feat(const void* x, int B, int HW, int A, int ldx, const void* w_f32, const void* bias_f32, int C, void* logits_f32_or_null, void* labels_i32_or_null,
+                           void* features_f32_or_null, void* stream) {
+  API_BEGIN
+  launch_cls_head_feat((const f16*)x, B, HW, A, ldx, (const float*)w_f32, (const float*)bias_f32, C, (float*)logits_f32_or_null, (int*)labels_i32_or_null, (float*)features_f32_or_null,
+                       (hipStream_t)stream);
   API_END
 }
 int ldiff_unet_attach_controlnet(ldiff_unet* u, ldiff_controlnet* c, float conditioning_scale) {
@@ -781,6 +810,7 @@ static void conv_args_to_params(const ldiff_conv_args* a, ConvParams& p) {
   p.lrelu_in = a->lrelu_in; p.tconv = a->tconv; p.seg_conv = a->seg_conv;
   p.relu_out = a->relu_out != 0; p.cls_force = a->cls_conv;
   p.act_out = a->act_out;   // (plan_conv checks 0 | 1 | 2 and the route)
+  p.bn_stats = (float*)a->bn_stats;   // (plan_conv: the classifier's conv family on request, or refused)
   if (p.tconv) p.K = a->C1;   // one GEMM over the coarse map: the four taps are column blocks, not K
 }
 int ldiff_op_conv_pb(const ldiff_conv_args* a, int plan_batch, void* stream) {
@@ -866,6 +896,30 @@ int ldiff_op_conv_stats_blocks(const ldiff_conv_args* a) {
     plan_conv(p, ask);
     return p.stats_R;
   } catch (const LdiffError& e) { return e.code; }
+}
+int ldiff_op_conv_bn_stats_blocks(const ldiff_conv_args* a) {
+  try {
+    ConvParams p;
+    conv_args_to_params(a, p);
+    float placeholder[2];
+    if (!p.bn_stats) p.bn_stats = reinterpret_cast<float*>(((uintptr_t)placeholder + 7) & ~(uintptr_t)7);   // (read as null / non-null and for its alignment only)
+    plan_conv(p, ConvAsk());
+    return cls_conv_bn_stats_blocks(p);
+  } catch (const LdiffError& e) { return e.code; }
+}
+int ldiff_op_bn_finalize(const void* part_f32, int R, int N, int64_t n, const void* gamma_f32, const void* beta_f32, void* scale_f32, void* shift_f32, void* batch_stats_f32,
+                         int64_t offset, int64_t T, void* stream) {
+  API_BEGIN
+  launch_bn_finalize((const float*)part_f32, R, N, n, (const float*)gamma_f32, (const float*)beta_f32, (float*)scale_f32, (float*)shift_f32, (float*)batch_stats_f32, offset, T,
+                     (hipStream_t)stream);
+  API_END
+}
+int ldiff_op_bn_apply(const void* x_f16, int64_t M, int N, const void* scale_f32, const void* shift_f32, const void* id_f16_or_null, const void* id_scale_f32_or_null,
+                      const void* id_shift_f32_or_null, int relu, void* y_f16, void* nonfinite_i32_or_null, void* stream) {
+  API_BEGIN
+  launch_bn_apply((const f16*)x_f16, M, N, (const float*)scale_f32, (const float*)shift_f32, (const f16*)id_f16_or_null, (const float*)id_scale_f32_or_null,
+                  (const float*)id_shift_f32_or_null, relu, (f16*)y_f16, (int*)nonfinite_i32_or_null, (hipStream_t)stream);
+  API_END
 }
 int ldiff_op_gn_finalize(const void* part1, int R1, int C1, const void* part2, int R2, int C2, int B, int HW, int groups, float eps,
                          const void* gamma, const void* beta, void* scale, void* shift, void* stream) {

@@ -124,6 +124,9 @@ struct ConvParams {
   // below), while grids, buffer extents and loop bounds keep the real B and M.  plan_conv refuses B > plan_B or M > plan_M: every size cap a predicate
   // applies then holds for the real launch too.  (plan_M is stated, not derived: the rows of a time-embedding or context launch are the batch itself.)
   int plan_B = 0, plan_M = 0;
+  // Training-mode BatchNorm partials of the classifier's conv family (ldiff_conv_args.bn_stats; kernels_cls.hip): [N][R][2] = {sum, sum of squares} of the fp32
+  // accumulators per row block r = 4 blockIdx.x + wave, R = cls_conv_bn_stats_blocks.  plan_conv refuses it beside a bias, a residual, a ReLU or cls_force != 1
+  float* bn_stats = nullptr;
 };
 // The decode_latents tail on a pixel's three fp32 sums (ConvParams::post_*; the epilogues of kernels_conv3x3n.hip and decode_post_kernel of kernels_elem.hip),
 // pinned bit for bit to torch, numpy and Pillow:
@@ -205,6 +208,14 @@ void launch_cls_conv(const ConvParams& p, hipStream_t s);
 void launch_maxpool3x3s2(const f16* x, f16* y, int B, int H, int W, int C, hipStream_t s);   // [B, H, W, C] -> [B, (H - 1) / 2 + 1, (W - 1) / 2 + 1, C], C % 8 == 0
 void launch_crop_resize_norm(const uint8_t* rgb, int H, int W, const int* boxes, int n, const uint8_t* lut, int S, const double* mean3, const double* std3, f16* out, hipStream_t s);
 void launch_cls_head(const f16* x, int B, int HW, int A, int ldx, const float* w, const float* bias, int C, float* logits, int* labels_or_null, hipStream_t s);
+void launch_cls_head_feat(const f16* x, int B, int HW, int A, int ldx, const float* w, const float* bias, int C, float* logits_or_null, int* labels_or_null, float* feat_or_null, hipStream_t s);
+// training-mode BatchNorm of that classifier (kernels_cls.hip: the conv's statistics epilogue; kernels_clstrain.hip: finalize and apply; include/ldiff.h ldiff_op_bn_*)
+bool cls_conv_bn_ok(const ConvParams& p);           // a launch with bn_stats the family takes: cls_force = 1, eligible, no bias / residual / ReLU
+int cls_conv_bn_stats_blocks(const ConvParams& p);  // R of ConvParams::bn_stats for the tile launch_cls_conv picks
+void launch_bn_finalize(const float* part, int R, int N, long long n, const float* gamma, const float* beta, float* scale, float* shift, float* batch_stats, long long offset, long long T,
+                        hipStream_t s);
+void launch_bn_apply(const f16* x, long long M, int N, const float* scale, const float* shift, const f16* id, const float* id_scale, const float* id_shift, int relu, f16* y, int* nonfinite,
+                     hipStream_t s);
 void launch_scale_f16(const f16* x, f16* y, float a, long long n, hipStream_t s);   // y = f16(x * a)
 bool conv3x3_eligible(const ConvParams& p);   // the halo-tile 3x3 family: kernels_conv3x3.hip
 void launch_splitk_reduce(const ConvParams& p, hipStream_t s);   // sums p.splitk fp32 partials of splitk_ws and applies the epilogue (+ the fused GroupNorm statistics: R = H W / 32)

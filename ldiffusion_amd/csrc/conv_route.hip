@@ -129,6 +129,16 @@ ConvPlan plan_conv(ConvParams& p, const ConvAsk& ask) {
   // likewise quick_gelu / gelu behind the sum (act_out, 0d below): nothing that selects one of the families in front of it
   LDIFF_CHECK(!q.act_out || !(q.relu_out || q.cls_force > 0 || q.silu_out || q.cond_force > 0 || q.tconv || q.lrelu_in || q.seg_conv > 0), LDIFF_ERR_INVALID,
               "conv: act_out cannot be combined with relu_out / cls_conv = 1 / silu_out / cond_conv = 1 / tconv / lrelu_in / seg_conv = 1 (only the LDS-DMA GEMM has that epilogue)");
+  // Training-mode BatchNorm partials (ConvParams::bn_stats) exist in the classifier's conv family alone, asked for by name: the launch is that family's raw form or it is refused
+  if (q.bn_stats) {
+    LDIFF_CHECK(ask.splitk < 2 && !ask.stats && cls_conv_bn_ok(q), LDIFF_ERR_INVALID,
+                "conv: bn_stats needs cls_conv = 1 and a launch the classifier's conv family takes, without bias, residual, ReLU, split-K or `stats` (Cin=%d N=%d ks=%d stride=%d cls_conv=%d)",
+                q.C1 + q.C2, q.N, q.ks, q.stride, q.cls_force);
+    pl.kernel = ConvKernel::CLSCONV;
+    p.splitk = 0;
+    p.stats_R = 0;
+    return pl;
+  }
   // 0. the conditioning-embedding 3x3 (kernels_cond.hip): channel counts no other family is made for; no split, no fused statistics (the caller's
   //    separate statistics pass), plain weights.  It is the one kernel with an activation behind its sum
   if (ask.splitk < 2 && cond_conv_selected(q)) {

@@ -1,5 +1,6 @@
 // Kernels of the cell head's instance classifier (ldiff_resnet: torchvision's ResNet152 trunk + adapter conv + linear head on 64 x 64 crops, hundreds per call):
-//   clsconv<ks, NT, MT>   implicit-GEMM conv, ks 1 | 3 | 7, stride 1 | 2, pad ks / 2, bias (+ residual) (+ ReLU) in the fp32 epilogue
+//   clsconv<ks, NT, MT>   implicit-GEMM conv, ks 1 | 3 | 7, stride 1 | 2, pad ks / 2, bias (+ residual) (+ ReLU) in the fp32 epilogue; <..., BN>: the raw sums and their
+//                         training-mode BatchNorm partials instead (ConvParams::bn_stats)
 //   maxpool3x3s2          the stem's pooling
 //   crop_resize_norm      bounding-box crops of the decoded image -> [n, S, S, 8] normalised fp16 (the reference's PIL / torchvision preprocessing chain)
 //   cls_head              mean over the adapter's map + Linear -> logits, label = 1 + argmax(logits[1:])
@@ -17,7 +18,7 @@
 
 namespace {
 
-template <int KS, int NT, int MT>
+template <int KS, int NT, int MT, bool BN>
 __global__ __launch_bounds__(256) void clsconv_kernel(const ConvParams p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, j = lane >> 4;
   const int C8 = p.C1 >> 3, KCH = KS * KS * C8, KSTEPS = (KCH + 3) >> 2;
@@ -113,26 +114,40 @@ __global__ __launch_bounds__(256) void clsconv_kernel(const ConvParams p) {
     }
   }
   if (bad && p.nonfinite) *p.nonfinite = 1;   // sticky flag of the owning handle (host-mapped; include/ldiff.h "Non-finite detection")
+  // Training-mode BatchNorm partials (BN launches carry no bias, residual or ReLU: acc IS the raw value): per wave = row block r = 4 blockIdx.x + wave and channel the
+  // float2 {sum v, sum v^2} of the FP32 accumulators over the block's valid rows, at bn_stats[(n R + r) 2], R = 4 gridDim.x.  A wave past M stores zeros; no atomics.
+  // Association (wave_stats_store): a lane adds its MT pixels in index order into a zero (the squares by fma), then row16_sum's fixed butterfly over the 16 pixel lanes
+  // (quad xor 1, quad xor 2, half mirror, mirror), so every launch gives the same bits.
+  // LONGEST CHAIN of fp32 additions into one partial: L = MT + 4 <= 8 (4 pixels of a lane + 4 butterfly steps).
+  if constexpr (BN) {
+    const long long R = 4ll * gridDim.x, rblk = (long long)blockIdx.x * 4 + wave;
+    wave_stats_store<MT, NT>(acc, mval, 0, MT, p.bn_stats + rblk * 2, R, p.N, n0 + 4 * j, l15);
+  }
 }
 
 template <int KS, int NT, int MT>
 void launch_tile(const ConvParams& p, hipStream_t s) {
   const dim3 grid((unsigned)((p.M + 64 * MT - 1) / (64 * MT)), (unsigned)(p.N / (16 * NT)));
   static const std::string base = "clsconv<" + std::to_string(KS) + "x" + std::to_string(KS) + "," + std::to_string(16 * NT) + "x" + std::to_string(16 * MT);
-  static const std::string name_plain = base + ">", name_relu = base + ",relu>";
+  static const std::string name_plain = base + ">", name_relu = base + ",relu>", name_bn = base + ",bn>";
   const double bytes = (double)p.B * p.Hin * p.Win * p.C1 * 2.0 + (double)p.N * p.K * 2.0 + (double)p.M * p.N * (p.res ? 4.0 : 2.0);
-  ProfScope prof(p.relu_out ? name_relu.c_str() : name_plain.c_str(), 2.0 * p.M * (double)p.N * p.K, bytes, s);
-  clsconv_kernel<KS, NT, MT><<<grid, 256, 0, s>>>(p);
+  ProfScope prof(p.bn_stats ? name_bn.c_str() : p.relu_out ? name_relu.c_str() : name_plain.c_str(), 2.0 * p.M * (double)p.N * p.K, bytes, s);
+  if (p.bn_stats) clsconv_kernel<KS, NT, MT, true><<<grid, 256, 0, s>>>(p);
+  else clsconv_kernel<KS, NT, MT, false><<<grid, 256, 0, s>>>(p);
   HIP_CHECK(hipGetLastError());
+}
+// the tile: 64 channels per workgroup where Cout has them; 64 pixels per wave where such workgroups still cover the chip twice
+struct ClsTile { bool nt4, mt4; };
+ClsTile cls_tile(const ConvParams& p) {
+  const bool nt4 = p.N % 64 == 0;
+  const long long wgs4 = (long long)((p.M + 255) / 256) * (p.N / (nt4 ? 64 : 16));
+  return ClsTile{nt4, wgs4 >= 512};
 }
 template <int KS>
 void launch_ks(const ConvParams& p, hipStream_t s) {
-  // the tile: 64 channels per workgroup where Cout has them; 64 pixels per wave where such workgroups still cover the chip twice
-  const bool nt4 = p.N % 64 == 0;
-  const long long wgs4 = (long long)((p.M + 255) / 256) * (p.N / (nt4 ? 64 : 16));
-  const bool mt4 = wgs4 >= 512;
-  if (nt4) { if (mt4) launch_tile<KS, 4, 4>(p, s); else launch_tile<KS, 4, 1>(p, s); }
-  else { if (mt4) launch_tile<KS, 1, 4>(p, s); else launch_tile<KS, 1, 1>(p, s); }
+  const ClsTile t = cls_tile(p);
+  if (t.nt4) { if (t.mt4) launch_tile<KS, 4, 4>(p, s); else launch_tile<KS, 4, 1>(p, s); }
+  else { if (t.mt4) launch_tile<KS, 1, 4>(p, s); else launch_tile<KS, 1, 1>(p, s); }
 }
 
 // ---- 3x3 stride-2 max pooling, padding 1 (taps outside the map are ignored), NHWC fp16; a thread = 8 channels of one output pixel ----
@@ -216,7 +231,7 @@ __global__ void crop_resize_norm_kernel(const uint8_t* __restrict__ rgb, int H, 
 
 // ---- head: a wave per instance.  feat[c] = mean over the HW pixels of the adapter's map (fp32 sum of the fp16 values), logits = W feat + b in fp32 ----
 __global__ __launch_bounds__(64) void cls_head_kernel(const f16* __restrict__ x, int HW, int A, int ldx, const float* __restrict__ w, const float* __restrict__ bias, int C,
-                                                      float* __restrict__ logits, int* __restrict__ labels) {
+                                                      float* __restrict__ logits, int* __restrict__ labels, float* __restrict__ feat_out) {
   extern __shared__ float feat[];
   const int b = blockIdx.x, lane = threadIdx.x;
   const f16* xb = x + (long long)b * HW * ldx;
@@ -225,6 +240,7 @@ __global__ __launch_bounds__(64) void cls_head_kernel(const f16* __restrict__ x,
     float sum = 0.f;
     for (int i = 0; i < HW; ++i) sum += (float)xb[(long long)i * ldx + c];
     feat[c] = sum * inv;
+    if (feat_out) feat_out[(long long)b * A + c] = feat[c];
   }
   __syncthreads();
   float best = 0.f;
@@ -235,7 +251,7 @@ __global__ __launch_bounds__(64) void cls_head_kernel(const f16* __restrict__ x,
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
     const float v = part + bias[k];
-    if (lane == 0) logits[(long long)b * C + k] = v;
+    if (lane == 0 && logits) logits[(long long)b * C + k] = v;
     if (k >= 1 && (arg == 0 || v > best)) { best = v; arg = k; }   // first maximum among the classes 1 .. C - 1 (softmax is monotonic: the reference's top-1 of softmax[:, 1:])
   }
   if (lane == 0 && labels) labels[b] = arg;
@@ -268,8 +284,13 @@ bool cls_conv_selected(const ConvParams& p) {
   if (p.cls_force < 0 || (p.cls_force == 0 && !p.relu_out)) return false;
   return cls_conv_eligible(p);
 }
+bool cls_conv_bn_ok(const ConvParams& p) {
+  return p.bn_stats && p.cls_force > 0 && !p.bias && !p.res && !p.relu_out && ((uintptr_t)p.bn_stats & 7) == 0 && cls_conv_eligible(p);
+}
+int cls_conv_bn_stats_blocks(const ConvParams& p) { return 4 * ((p.M + (cls_tile(p).mt4 ? 256 : 64) - 1) / (cls_tile(p).mt4 ? 256 : 64)); }
 void launch_cls_conv(const ConvParams& p, hipStream_t s) {
   LDIFF_CHECK(cls_conv_eligible(p), LDIFF_ERR_INVALID, "clsconv: not a launch of the classifier's conv family (ks=%d stride=%d Cin=%d N=%d)", p.ks, p.stride, p.C1, p.N);
+  LDIFF_CHECK(!p.bn_stats || cls_conv_bn_ok(p), LDIFF_ERR_INVALID, "clsconv: bn_stats needs cls_conv = 1 and a launch without bias, residual and ReLU");
   if (p.ks == 1) launch_ks<1>(p, s);
   else if (p.ks == 3) launch_ks<3>(p, s);
   else launch_ks<7>(p, s);
@@ -298,6 +319,12 @@ void launch_crop_resize_norm(const uint8_t* rgb, int H, int W, const int* boxes,
 void launch_cls_head(const f16* x, int B, int HW, int A, int ldx, const float* w, const float* bias, int C, float* logits, int* labels, hipStream_t s) {
   LDIFF_CHECK(x && w && bias && logits && B >= 1 && HW >= 1 && A >= 1 && A <= 8192 && ldx >= A && C >= 2, LDIFF_ERR_INVALID,
               "cls_head: null pointer, empty shape, more than 8192 features or fewer than 2 classes (A=%d C=%d)", A, C);
-  cls_head_kernel<<<(unsigned)B, 64, (size_t)A * sizeof(float), s>>>(x, HW, A, ldx, w, bias, C, logits, labels);
+  cls_head_kernel<<<(unsigned)B, 64, (size_t)A * sizeof(float), s>>>(x, HW, A, ldx, w, bias, C, logits, labels, nullptr);
+  HIP_CHECK(hipGetLastError());
+}
+void launch_cls_head_feat(const f16* x, int B, int HW, int A, int ldx, const float* w, const float* bias, int C, float* logits, int* labels, float* feat, hipStream_t s) {
+  LDIFF_CHECK(x && w && bias && B >= 1 && HW >= 1 && A >= 1 && A <= 8192 && ldx >= A && C >= 2, LDIFF_ERR_INVALID,
+              "cls_head_feat: null pointer, empty shape, more than 8192 features or fewer than 2 classes (A=%d C=%d)", A, C);
+  cls_head_kernel<<<(unsigned)B, 64, (size_t)A * sizeof(float), s>>>(x, HW, A, ldx, w, bias, C, logits, labels, feat);
   HIP_CHECK(hipGetLastError());
 }

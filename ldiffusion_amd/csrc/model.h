@@ -447,7 +447,12 @@ struct ClsConvW {
   f16* w = nullptr;              // [Cout][ks ks Cin_pad]
   float* b = nullptr;            // [Cout]
   bool folded = false;
+  // training mode (ldiff_resnet::set_train): the UN-folded matrix (one rounding of w, the layout of `w`), the BatchNorm's gamma / beta, its offset on the flat channel axis
+  f16* w_raw = nullptr;
+  float* gamma = nullptr; float* beta = nullptr;
+  long long bn_off = -1;
 };
+struct ClsBnOut { Act raw; float* scale = nullptr; float* shift = nullptr; };   // a conv's raw sums and the scale / shift its batch statistics give (forward_train)
 struct ClsBlockW { int c1 = -1, c2 = -1, c3 = -1, down = -1; };   // indices into ldiff_resnet::convs
 struct ldiff_resnet {
   int device = 0;
@@ -465,6 +470,14 @@ struct ldiff_resnet {
   Act conv(const ClsConvW& c, const Act& x, const Act* res, bool relu);
   void forward(const f16* crops, int B, int S, float* logits, int* labels, hipStream_t s);
   void forward_impl(const f16* crops, int B, int S, float* logits, int* labels, hipStream_t s);
+  // training mode (include/ldiff.h ldiff_resnet_set_train / _forward_train): batch statistics, three launches per conv, eager
+  bool train = false;
+  long long bn_total = 0;          // T: channels of all BatchNorms
+  std::vector<int> bn_order;       // convs with a BatchNorm, in forward order: BatchNorm i of ldiff_resnet_bn_entry
+  void set_train(bool on);
+  ClsBnOut conv_bn(const ClsConvW& c, const Act& x, float* batch_stats);
+  Act bn_apply(ClsBnOut& a, const Act* id_plain, ClsBnOut* id_bn, bool relu);
+  void forward_train(const f16* crops, int B, int S, float* batch_stats, float* features, float* logits, int* labels, hipStream_t s);
   GraphCache gc;
   DeviceBuf st_in, st_logits, st_labels;
   ~ldiff_resnet() { nf.destroy(); }

@@ -60,6 +60,25 @@ void ldiff_resnet::build() {
   fc_b = ws.alloc_vec(n_classes);
   ws.add_tensor("classifier.weight", {n_classes, adapter_ch}, fc_w);
   ws.add_tensor("classifier.bias", {n_classes}, fc_b);
+  for (size_t i = 0; i < convs.size(); ++i)
+    if (!convs[i].bn.empty()) { convs[i].bn_off = bn_total; bn_total += convs[i].Cout; bn_order.push_back((int)i); }
+}
+
+// Before the first load: fold() consumes the host tensors, and the un-folded matrices can only be made from them.
+void ldiff_resnet::set_train(bool on) {
+  if (on == train) return;
+  LDIFF_CHECK(ws.generation == 0, LDIFF_ERR_STATE,
+              "resnet_set_train: tensors were loaded already; training mode is chosen before the load, because the fold of a conv with its BatchNorm consumes the host tensors "
+              "the un-folded matrices are made from");
+  HIP_CHECK(hipSetDevice(device));
+  if (on)
+    for (ClsConvW& c : convs)
+      if (!c.bn.empty() && !c.w_raw) {
+        c.w_raw = ws.alloc_mat(c.Cout, c.ks * c.ks * c.Cin_pad);
+        c.gamma = ws.alloc_vec(c.Cout);
+        c.beta = ws.alloc_vec(c.Cout);
+      }
+  train = on;
 }
 
 void ldiff_resnet::load(const char* name, const void* host, int dtype, const int64_t* shape, int ndim) {
@@ -99,6 +118,15 @@ void ldiff_resnet::fold() {
     }
     HIP_CHECK(hipMemcpy(c.w, wf.data(), wf.size() * sizeof(f16), hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(c.b, bf.data(), bf.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (train && !c.bn.empty()) {   // the un-folded matrix: w rounded once, the same layout; gamma / beta as they are
+      std::fill(wf.begin(), wf.end(), (f16)0.f);
+      for (int n = 0; n < c.Cout; ++n)
+        for (int ci = 0; ci < c.Cin; ++ci)
+          for (int t = 0; t < taps; ++t) wf[(size_t)n * K + (size_t)t * c.Cin_pad + ci] = (f16)w[((size_t)n * c.Cin + ci) * taps + t];
+      HIP_CHECK(hipMemcpy(c.w_raw, wf.data(), wf.size() * sizeof(f16), hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(c.gamma, v[1]->data(), (size_t)c.Cout * sizeof(float), hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(c.beta, v[2]->data(), (size_t)c.Cout * sizeof(float), hipMemcpyHostToDevice));
+    }
     c.folded = true;
     for (auto& n : names) ws.consume(n);
   }
@@ -196,4 +224,122 @@ void ldiff_resnet::forward(const f16* crops, int B, int S, float* logits, int* l
            HIP_CHECK(hipMemcpyAsync(logits, st_logits.p, n_log, hipMemcpyDeviceToDevice, s));
            if (labels) HIP_CHECK(hipMemcpyAsync(labels, st_labels.p, n_lab, hipMemcpyDeviceToDevice, s));
          });
+}
+
+// ---- training mode: conv -> batch statistics -> scale / shift, then one apply launch that carries the ReLU and the block's identity ----
+ClsBnOut ldiff_resnet::conv_bn(const ClsConvW& c, const Act& x, float* batch_stats) {
+  ConvParams p;
+  memset(&p, 0, sizeof(p));
+  LDIFF_CHECK(x.C == c.Cin_pad && !x.split, LDIFF_ERR_INVALID, "resnet conv %s: input has %d channels, weight expects %d", c.conv.c_str(), x.C, c.Cin_pad);
+  p.x = x.p; p.C1 = x.C;
+  p.B = x.B; p.Hin = x.H; p.Win = x.W;
+  p.ks = c.ks; p.stride = c.stride; p.pad_t = c.ks / 2; p.pad_l = c.ks / 2;
+  p.Hout = (x.H - 1) / c.stride + 1; p.Wout = (x.W - 1) / c.stride + 1;
+  p.w = c.w_raw; p.N = c.Cout; p.Nrows = c.Cout; p.K = c.ks * c.ks * c.Cin_pad;
+  p.M = x.B * p.Hout * p.Wout;
+  p.ldy = c.Cout;
+  p.cls_force = 1;
+  p.nonfinite = ex.nonfinite;
+  ClsBnOut o;
+  o.raw = ex.new_act(x.B, p.Hout, p.Wout, c.Cout);
+  p.y = o.raw.p;
+  const int R = cls_conv_bn_stats_blocks(p);
+  float* part = ex.tmp<float>((size_t)c.Cout * R * 2);
+  p.bn_stats = part;
+  ConvAsk ask;
+  ask.splitk = 1;
+  const ConvPlan pl = plan_conv(p, ask);
+  LDIFF_CHECK(pl.kernel == ConvKernel::CLSCONV, LDIFF_ERR_INVALID, "resnet conv %s: not taken by the classifier's conv family", c.conv.c_str());
+  launch_igemm(p, pl, ex.s);
+  o.scale = ex.tmp<float>(c.Cout);
+  o.shift = ex.tmp<float>(c.Cout);
+  launch_bn_finalize(part, R, c.Cout, p.M, c.gamma, c.beta, o.scale, o.shift, batch_stats, c.bn_off, bn_total, ex.s);
+  ex.arena.free(part);   // (stream order: the next writer of these bytes runs behind the finalize)
+  return o;
+}
+
+Act ldiff_resnet::bn_apply(ClsBnOut& a, const Act* id_plain, ClsBnOut* id_bn, bool relu) {
+  const Act* id = id_bn ? &id_bn->raw : id_plain;
+  LDIFF_CHECK(!id || (id->rows() == a.raw.rows() && id->C == a.raw.C && !id->split), LDIFF_ERR_INVALID, "resnet bn_apply: identity shape mismatch");
+  Act y = ex.new_act(a.raw.B, a.raw.H, a.raw.W, a.raw.C);
+  launch_bn_apply(a.raw.p, a.raw.rows(), a.raw.C, a.scale, a.shift, id ? id->p : nullptr, id_bn ? id_bn->scale : nullptr, id_bn ? id_bn->shift : nullptr, relu ? 1 : 0, y.p,
+                  ex.nonfinite, ex.s);
+  for (ClsBnOut* o : {&a, id_bn}) {
+    if (!o) continue;
+    ex.release(o->raw);
+    ex.arena.free(o->scale); ex.arena.free(o->shift);
+    o->scale = o->shift = nullptr;
+  }
+  return y;
+}
+
+void ldiff_resnet::forward_train(const f16* crops, int B, int S, float* batch_stats, float* features, float* logits, int* labels, hipStream_t s) {
+  LDIFF_CHECK(train, LDIFF_ERR_STATE, "resnet_forward_train: the handle was not put in training mode (ldiff_resnet_set_train(h, 1) before the tensors are loaded; python: ResNetClassifier(train=True))");
+  LDIFF_CHECK(crops && batch_stats && features, LDIFF_ERR_INVALID, "resnet_forward_train: null pointer");
+  LDIFF_CHECK(B >= 1, LDIFF_ERR_INVALID, "resnet_forward_train: B = %d must be at least 1", B);
+  LDIFF_CHECK(S >= 32 && S <= 1024 && S % 32 == 0, LDIFF_ERR_INVALID, "resnet_forward_train: S = %d must be a multiple of 32 in 32..1024", S);
+  LDIFF_CHECK((long long)B * (S / 2) * (S / 2) * width < (1ll << 31), LDIFF_ERR_INVALID, "resnet_forward_train: B * (S / 2)^2 * width exceeds 2^31 (B = %d, S = %d)", B, S);
+  LDIFF_CHECK(ws.missing() == 0, LDIFF_ERR_STATE, "resnet: %d weight tensors not loaded (first: %s)", ws.missing(), ws.missing_name(0));
+  {   // every BatchNorm needs more than one value per channel (torch: "Expected more than 1 value per channel when training"): checked for the whole network before any launch
+    int h = S / 4, bi = 0;   // the map behind the pooling
+    for (int L = 0; L < 4; ++L)
+      for (int b = 0; b < layers[L]; ++b, ++bi) {
+        const int ho = (b == 0 && L > 0) ? (h - 1) / 2 + 1 : h;
+        const ClsBlockW& k = blocks[bi];
+        const std::pair<int, int> at[4] = {{k.c1, h}, {k.c2, ho}, {k.c3, ho}, {k.down, ho}};
+        for (const auto& e : at)
+          LDIFF_CHECK(e.first < 0 || (long long)B * e.second * e.second >= 2, LDIFF_ERR_INVALID,
+                      "resnet_forward_train: expected more than 1 value per channel when training: BatchNorm %s sees B * H * W = %d * %d * %d = 1 (S = %d)", e.first < 0 ? "" : convs[e.first].bn.c_str(),
+                      B, e.second, e.second, S);
+        h = ho;
+      }
+  }
+  HIP_CHECK(hipSetDevice(device));
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (s) (void)hipStreamIsCapturing(s, &cs);
+  LDIFF_CHECK(cs == hipStreamCaptureStatusNone, LDIFF_ERR_STATE, "resnet_forward_train: runs eagerly (B differs from image to image), not inside a stream capture");
+  fold();
+  ex.s = s;
+  ex.arena.reset();
+  // live at once, at most (first block of layer 1): the block's input and conv2's output (a quarter of the stem's output each), the raw downsample and conv3 tensors and the block's
+  // output (one each), plus a conv's partials (at most a quarter of its raw tensor) and scale / shift vectors
+  const size_t unit = (size_t)B * (S / 2) * (S / 2) * width * sizeof(f16);
+  ex.arena.reserve(6 * unit + (16u << 20));
+
+  Act in;
+  in.p = const_cast<f16*>(crops); in.B = B; in.H = S; in.W = S; in.C = 8; in.borrowed = true;
+  ClsBnOut st = conv_bn(convs[stem], in, batch_stats);
+  Act a = bn_apply(st, nullptr, nullptr, true);
+  ex.trace("stem", a);
+  Act cur = ex.new_act(B, (a.H - 1) / 2 + 1, (a.W - 1) / 2 + 1, width);
+  launch_maxpool3x3s2(a.p, cur.p, B, a.H, a.W, width, s);
+  ex.release(a);
+  int bi = 0;
+  for (int L = 0; L < 4; ++L) {
+    for (int b = 0; b < layers[L]; ++b, ++bi) {
+      const ClsBlockW& k = blocks[bi];
+      ClsBnOut r1 = conv_bn(convs[k.c1], cur, batch_stats);
+      Act t1 = bn_apply(r1, nullptr, nullptr, true);
+      ClsBnOut r2 = conv_bn(convs[k.c2], t1, batch_stats);
+      ex.release(t1);
+      Act t2 = bn_apply(r2, nullptr, nullptr, true);
+      ClsBnOut r3 = conv_bn(convs[k.c3], t2, batch_stats);
+      ex.release(t2);
+      Act out;
+      if (k.down >= 0) {
+        ClsBnOut rd = conv_bn(convs[k.down], cur, batch_stats);
+        out = bn_apply(r3, nullptr, &rd, true);   // relu(bn3(conv3) + bn_d(downsample))
+      } else {
+        out = bn_apply(r3, &cur, nullptr, true);  // relu(bn3(conv3) + identity)
+      }
+      ex.release(cur);
+      cur = out;
+    }
+    ex.trace(("layer" + std::to_string(L + 1)).c_str(), cur);
+  }
+  Act ad = conv(convs[adapter], cur, nullptr, false);   // (bias, no BatchNorm: as in eval mode)
+  ex.release(cur);
+  ex.trace("adapter", ad);
+  launch_cls_head_feat(ad.p, B, ad.H * ad.W, adapter_ch, ad.ld(), fc_w, fc_b, n_classes, logits, labels, features, s);
+  ex.release(ad);
 }

@@ -159,15 +159,19 @@ class LDiffusionModel:
         torch.cuda.empty_cache()
         return save_path
 
-    def train(self, args, component="all", ldiffusion_weight=None, train_loader=None, val_loader=None, wgrad_route=None, **_ignored):
+    def train(self, args, component="all", ldiffusion_weight=None, train_loader=None, val_loader=None, wgrad_route=None, cell_weights=None, instances=None, **_ignored):
         """ldiffusion.py:297-315.  The PUMA dataset / dataloader (dataset.py, cv2) is outside this build: the loaders are injected.
         `component="ldiffusion"` runs the L-Diffusion warm-up on the HIP kernels and returns the saved weight directory.  The segmentor stage
         ("segmentor", or after the warm-up with "all") at level "tissue" is `Segmentor.train_tissue_model_nnUNetv2(args.num_epochs - 10,
         ldiffusion_weight, args.diffusion_path)` with the loaders' `dataset.image_dir` / `label_dir` lists (:306-311) and returns the trained-model
         folder; loaders without such a dataset (plain lists of batches) need the four lists as keyword arguments `train_images`, `train_labels`,
         `test_images`, `test_labels`.  `iterations_per_epoch`, `val_iterations` and `num_foreground_voxels` are handed on too, and so is `wgrad_route`
-        (the route of the tissue trainer's weight gradients, `nnunet_train.Trainer`'s keyword; None: its default).  At level "cell" it
-        raises NotImplementedError: the cell trainer is not built."""
+        (the route of the tissue trainer's weight gradients, `nnunet_train.Trainer`'s keyword; None: its default).  At level "cell" it is
+        `Segmentor.train_cell_model(args.num_epochs - 10, ldiffusion_weight, args.diffusion_path, cell_weights=..., instances=...)` (:312-313) and returns
+        the folder that holds cellclassifier.pth (None when no epoch validated above 0.0).  `cell_weights` = the CellSegClassifier state dict (or its path)
+        the stage starts from: the reference starts from torchvision's ImageNet weights, which it downloads, and this build downloads nothing -- without
+        `cell_weights=` the stage raises NotImplementedError.  `instances` = the label-map callable (Cellpose where installed); `fit_classifier`,
+        `cache_features`, `lr`, `save_root`, `seed` and `text_embeddings` are handed on."""
         if component not in ("all", "ldiffusion", "segmentor"):
             raise ValueError(f"unknown component {component!r}")
         segmentor_kwargs = {k: _ignored[k] for k in ("train_images", "train_labels", "test_images", "test_labels", "iterations_per_epoch", "val_iterations",
@@ -180,8 +184,15 @@ class LDiffusionModel:
             ldiffusion_weight = self.train_ldiffusion(args, train_loader, val_loader)
         if component in ("all", "segmentor"):
             if self.level == "cell":
-                raise NotImplementedError("segmentor training at the cell level (train_cell_model, segmentor.py:243-299) trains the out-of-scope "
-                                          f"cell head; the L-Diffusion weights are at {ldiffusion_weight!r}")
+                if cell_weights is None:
+                    raise NotImplementedError("segmentor training at the cell level (train_cell_model, segmentor.py:243-299) starts from torchvision's downloaded ImageNet "
+                                              "weights in the reference; nothing is downloaded here: pass cell_weights= (a CellSegClassifier state dict or its path); "
+                                              f"the L-Diffusion weights are at {ldiffusion_weight!r}")
+                if self._is_main_process():
+                    print("Starting Segmentor training...")
+                cell_kwargs = {k: _ignored[k] for k in ("fit_classifier", "cache_features", "lr", "save_root", "seed", "text_embeddings") if k in _ignored}
+                return Segmentor(train_loader, val_loader, self.level, args.num_classes).train_cell_model(args.num_epochs - 10, ldiffusion_weight, args.diffusion_path,
+                                                                                                         cell_weights=cell_weights, instances=instances, **cell_kwargs)
             if self.level != "tissue":
                 raise ValueError("Invalid level specified. Choose 'tissue' or 'cell'.")
             if self._is_main_process():

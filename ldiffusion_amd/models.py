@@ -612,10 +612,15 @@ class ResNetClassifier(_GraphHandle):
     (3, 8, 36, 3), width 64) without avgpool / fc, `adapter` conv, mean over the map, linear head -- `encoder` / `adapter` / `classifier` of
     the reference's CellSegClassifier.  `state_dict` carries the module's own names (`cellhead.param_shapes`); every BatchNorm is folded into
     its conv at load.  `net(crops [B, S, S, 8] float16 NHWC on the device, channels 3..7 zero) -> (logits [B, C] float32, labels [B] int32)`,
-    labels = 1 + argmax(logits[:, 1:])."""
+    labels = 1 + argmax(logits[:, 1:]).
+    train=True (ldiff_resnet_set_train, chosen before the load): the handle also keeps the un-folded conv matrices and every BatchNorm's gamma / beta, and offers
+    `forward_train(crops) -> (features [B, A] float32, batch_mean [T] float32, batch_var [T] float32)` -- the trunk with batch statistics over all B crops, as
+    torch's modules compute in `.train()`; batch_var is the UNBIASED variance, T the channels of all BatchNorms -- and `bn_layout`, the list of (checkpoint
+    prefix, offset on that axis, channels) in forward order.  The eval-mode call is unchanged bit for bit.  Running statistics are never touched here: see
+    `cellhead.ema_update`."""
     _prefix, _noun = "resnet", "classifier"
 
-    def __init__(self, num_classes: int, state_dict, device=None, layers=(3, 8, 36, 3), width=64, adapter_channels=256):
+    def __init__(self, num_classes: int, state_dict, device=None, layers=(3, 8, 36, 3), width=64, adapter_channels=256, train=False):
         from . import cellhead
         _lib.require_gpu()
         self.num_classes, self.layers, self.width, self.adapter_channels = int(num_classes), tuple(int(v) for v in layers), int(width), int(adapter_channels)
@@ -627,10 +632,43 @@ class ResNetClassifier(_GraphHandle):
         _lib.check(self._lib.ldiff_resnet_create(C.byref(self._h), (C.c_int * 4)(*self.layers), self.width, self.adapter_channels, self.num_classes,
                                                  self.device.index or 0))
         self._shapes = cellhead.param_shapes(self.num_classes, self.layers, self.width, self.adapter_channels, counters=True)
+        self.train_mode = bool(train)
+        if self.train_mode:
+            self.set_train(True)
+        self.bn_channels = int(self._lib.ldiff_resnet_bn_channels(self._h))
+        self.bn_layout = []
+        name, off, ch = C.c_char_p(), C.c_int64(), C.c_int()
+        i = 0
+        while self._lib.ldiff_resnet_bn_entry(self._h, i, C.byref(name), C.byref(off), C.byref(ch)) == 0:
+            self.bn_layout.append((name.value.decode(), int(off.value), int(ch.value)))
+            i += 1
         self.load_state_dict(state_dict)
+
+    def set_train(self, on: bool):
+        """ldiff_resnet_set_train: only before the tensors are loaded (RuntimeError afterwards: the fold consumes the host tensors)."""
+        _lib.check(self._lib.ldiff_resnet_set_train(self._h, int(bool(on))))
+        self.train_mode = bool(on)
+        return self
 
     def to(self, *args, **kwargs):
         return self
+
+    @torch.no_grad()
+    def forward_train(self, crops, want_logits=False):
+        """One training-mode pass over all B crops (ldiff_resnet_forward_train): (features [B, A] f32, batch_mean [T] f32, batch_var [T] f32 unbiased);
+        want_logits=True appends (logits [B, C] f32, labels [B] i32) of the current linear head."""
+        if crops.dim() != 4 or crops.shape[1] != crops.shape[2] or crops.shape[3] != 8 or crops.dtype != torch.float16:
+            raise ValueError(f"ResNetClassifier: crops must be float16 [B, S, S, 8] (NHWC, channels 3..7 zero), got {crops.dtype} {list(crops.shape)}")
+        crops = crops.to(self.device).contiguous()
+        B, S = crops.shape[0], crops.shape[1]
+        stats = torch.empty((2, self.bn_channels), dtype=torch.float32, device=self.device)
+        feats = torch.empty((B, self.adapter_channels), dtype=torch.float32, device=self.device)
+        logits = torch.empty((B, self.num_classes), dtype=torch.float32, device=self.device) if want_logits else None
+        labels = torch.empty((B,), dtype=torch.int32, device=self.device) if want_logits else None
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.ldiff_resnet_forward_train(self._h, _lib.ptr(crops), B, S, _lib.ptr(stats), _lib.ptr(feats), _lib.ptr(logits), _lib.ptr(labels),
+                                                            _lib.stream_ptr()))
+        return (feats, stats[0], stats[1]) + ((logits, labels) if want_logits else ())
 
     @torch.no_grad()
     def __call__(self, crops):

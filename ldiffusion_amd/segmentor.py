@@ -133,10 +133,11 @@ class Segmentor:
             self._sampler = LaplaceSampler(pipeline)
         return self._sampler.sample(images, text_embeddings, 1, want_features=False, want_rgb=True)
 
-    def build_augmented_dataloader(self, dataloader, augment_fn, pipeline, unet, vae, device, batch_size, category, num_workers=0):
+    def build_augmented_dataloader(self, dataloader, augment_fn, pipeline, unet, vae, device, batch_size, category, num_workers=0, generator=None, with_index=False):
         """segmentor.py:144-161: run `augment_fn(inputs, pipeline, unet, vae)` (e.g. `ldiffusion_augment`) once over `dataloader` -- batches
         (inputs, masks, _) -- under no_grad, keep the augmented inputs and the masks on the host, and serve them from a shuffling
-        TensorDataset loader of `batch_size`.  `category` only labels the reference's progress bar."""
+        TensorDataset loader of `batch_size`.  `category` only labels the reference's progress bar.  `generator` seeds the shuffle (None: torch's global
+        one, as in the reference); with_index=True appends each sample's position in the dataset as a third tensor (what `train_cell_model` keys its caches by)."""
         from torch.utils.data import DataLoader, TensorDataset
         all_aug_inputs, all_masks = [], []
         for inputs, masks, _ in dataloader:
@@ -145,8 +146,10 @@ class Segmentor:
                 aug_inputs = augment_fn(inputs, pipeline, unet, vae)
             all_aug_inputs.append(aug_inputs.cpu())
             all_masks.append(masks.cpu())
-        dataset = TensorDataset(torch.cat(all_aug_inputs, dim=0), torch.cat(all_masks, dim=0))
-        return DataLoader(dataset, batch_size=batch_size, shuffle=True, num_workers=num_workers)
+        tensors = [torch.cat(all_aug_inputs, dim=0), torch.cat(all_masks, dim=0)]
+        if with_index:
+            tensors.append(torch.arange(tensors[0].shape[0]))
+        return DataLoader(TensorDataset(*tensors), batch_size=batch_size, shuffle=True, num_workers=num_workers, generator=generator)
 
     @torch.no_grad()
     def ldiffusion_augment(self, inputs, pipeline, unet, vae, text_embeddings=None):
@@ -323,6 +326,167 @@ class Segmentor:
         self.training_log = trainer.run_training(loaders[0], loaders[1], os.path.join(model_dir, "fold_0"), iterations_per_epoch=iterations_per_epoch,
                                                  val_iterations=val_iterations)
         return model_dir
+
+    def train_cell_model(self, epochs, ldiffusion_weight, diffusion_path, *, cell_weights, instances=None, fit_classifier=True, cache_features=True, lr=1e-4,
+                         save_root=None, seed=None, text_embeddings=None):
+        """segmentor.py:243-299, the cell head's training stage; returns the folder that holds the best epoch's `cellclassifier.pth` (what
+        `inference_cell_model(segmentor_weight=...)` takes), or None when no epoch's validation Dice beat 0.0 (nothing is written then).
+
+        What the reference's loop does, as its code reads (DESIGN.md section 7 "Cell head, training"):
+          1. no parameter ever gets a gradient -- CellSegClassifier.forward (model/conductor.py:175-233) runs encoder and adapter under no_grad, picks classes with
+             .item() and paints a fresh leaf tensor, so loss.backward() reaches nothing and AdamW(lr=1e-4) skips every parameter, weight decay included;
+          2. the state dict changes all the same: `self.model.train()` puts the trunk's BatchNorms in training mode, every training image's forward normalises
+             with the batch statistics of ALL of that image's crops and moves running_mean / running_var (momentum 0.1, unbiased variance) and
+             num_batches_tracked; validation then runs in eval mode on those, and the best mean micro_dice (> 0.0) writes the checkpoint;
+          3. the loop feeds the head the augmented image in [0, 1], un-normalised (`CellSegClassifier(input_norm=False)`).
+        `fit_classifier=False` reproduces exactly that: BatchNorm statistic adaptation plus best-epoch selection.  The default also fits the only parameters the
+        reference leaves outside no_grad, `classifier.{weight,bias}`: per training image, logits = features @ W.T + b in fp32 torch, the cross-entropy over the
+        instances whose target (`cellhead.instance_targets`: the majority class of the mask under the instance) is >= 1, one step of
+        torch.optim.AdamW([W, b], lr=lr) -- the reference's optimizer where a gradient can reach.
+        The "Loss" of the epoch lines is the epoch's MEAN CROSS-ENTROPY of those steps (0.0 with fit_classifier=False), NOT the reference's CombinedLoss: that loss
+        only reports a number there (nothing depends on it), and it cannot even be evaluated unless num_classes == 4 (model/loss.py:176 hard-codes four class weights).
+
+        `cell_weights` (required): a CellSegClassifier state dict or a path to one.  The reference starts from torchvision's ImageNet weights, which it downloads;
+        this build never downloads anything.  `instances`: the label-map callable (Cellpose where installed), called once per image with the [H, W, 3] float32
+        image in [0, 1]; its result is kept.  An image without a kept instance changes nothing (the reference returns before the encoder runs).
+        `cache_features`: no trunk weight moves, so an image's features and batch statistics are the same in every epoch: they are kept on the host after epoch 1
+        (ResNet152: about 0.6 MB of statistics per image) and the running-statistics update and the head steps are replayed from them; validation still runs
+        the trunk, whose folded weights change with the running statistics.  The written tensors are bit-identical either way.
+        `seed` seeds the loaders' shuffle.  `save_root`: default ./LDiffusion/train_save/cellclassifier; the checkpoint goes to <save_root>/<yy_mm_dd>/.
+        Under an initialised process group rank 0 trains, the others wait, and every rank returns the folder name rank 0 broadcasts."""
+        import torch.distributed as dist
+        kw = dict(cell_weights=cell_weights, instances=instances, fit_classifier=fit_classifier, cache_features=cache_features, lr=lr, save_root=save_root, seed=seed,
+                  text_embeddings=text_embeddings)
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+            return self._train_cell_model_rank0(epochs, ldiffusion_weight, diffusion_path, **kw)
+        out = [None, None]   # (folder, error text)
+        if dist.get_rank() == 0:
+            try:
+                out[0] = self._train_cell_model_rank0(epochs, ldiffusion_weight, diffusion_path, **kw)
+            except Exception as e:   # noqa: BLE001  (the other ranks must not wait forever)
+                out[1] = f"{type(e).__name__}: {e}"
+        dist.barrier()
+        dist.broadcast_object_list(out, src=0)
+        if out[1] is not None:
+            raise RuntimeError(f"train_cell_model failed on rank 0: {out[1]}")
+        return out[0]
+
+    def _train_cell_model_rank0(self, epochs, ldiffusion_weight, diffusion_path, *, cell_weights, instances, fit_classifier, cache_features, lr, save_root, seed,
+                                text_embeddings):
+        from datetime import datetime
+        from . import cellhead
+        print("Training cell-level model...")
+        if cell_weights is None:
+            raise ValueError("train_cell_model: cell_weights (a CellSegClassifier state dict or the path of one) is required; nothing is downloaded here")
+        sd = cell_weights if isinstance(cell_weights, dict) else cellhead.read_cellclassifier(cell_weights)
+        nc, layers, width, adapter = cellhead.infer_spec(sd)
+        if nc != int(self.num_classes):
+            raise ValueError(f"train_cell_model: cell_weights classify {nc} classes, this Segmentor has num_classes = {self.num_classes}")
+        cellhead.check_state_dict(sd, nc, layers, width, adapter)
+        counters = [k for k, shape in cellhead.param_shapes(nc, layers, width, adapter, counters=True).items() if k.endswith("num_batches_tracked")]
+        sd = {k: (v.detach().to("cpu", torch.int64).clone() if k.endswith("num_batches_tracked") else v.detach().to("cpu", torch.float32).clone()) for k, v in sd.items()}
+        for k in counters:
+            sd.setdefault(k, torch.zeros((), dtype=torch.int64))
+        pipeline, unet, vae = self.load_ldiffusion(ldiffusion_weight, diffusion_path)
+        current_date = datetime.now().strftime("%y_%m_%d")
+        if text_embeddings is None:
+            text_embeddings = self._get_text_embeddings(PROMPT, 1, pipeline, unet)
+        gens = [None, None]
+        if seed is not None:
+            gens = [torch.Generator().manual_seed(int(seed)), torch.Generator().manual_seed(int(seed) + 1)]
+
+        def augment(inputs, pipeline, unet, vae):
+            return self.ldiffusion_augment(inputs, pipeline, unet, vae, text_embeddings=text_embeddings)
+
+        aug_train_loader = self.build_augmented_dataloader(self.train_loader, augment, pipeline, unet, vae, self.device, batch_size=1, category="Train", generator=gens[0],
+                                                           with_index=True)
+        aug_val_loader = self.build_augmented_dataloader(self.val_loader, augment, pipeline, unet, vae, self.device, batch_size=1, category="Validation", generator=gens[1],
+                                                         with_index=True)
+
+        # the trunk's weights never move: ONE training-mode handle serves every epoch (its running statistics and linear head are not read by forward_train's features)
+        trainer = cellhead.CellSegClassifier(nc, sd, self.device, instances=instances, input_norm=False, train=True)
+        W = sd["classifier.weight"].clone().requires_grad_(True)
+        b = sd["classifier.bias"].clone().requires_grad_(True)
+        optimizer = torch.optim.AdamW([W, b], lr=lr) if fit_classifier else None
+        label_maps = {"train": {}, "val": {}}
+        cache = {}
+        self.cell_training_log = {"loss": [], "dice": [], "first_loss": None}
+
+        def to_u8(img):   # [1, 3, H, W] in [0, 1] = u8 / 255 -> the u8 image ((patch * 255).astype(uint8) is the identity on grey levels, cellhead.build_lut)
+            return (img[0].permute(1, 2, 0) * 255.0).round().clamp(0, 255).to(torch.uint8).contiguous().to(self.device)
+
+        def label_map(part, idx, head, rgb_u8):
+            if idx not in label_maps[part]:
+                label_maps[part][idx] = head._label_map(rgb_u8, instances).to(torch.int64).cpu()
+            return label_maps[part][idx]
+
+        def train_pass(idx, inputs, masks):
+            """(features, batch_mean, batch_var, targets) on the host, or None for an image without a kept instance."""
+            rgb_u8 = to_u8(inputs)
+            labels = label_map("train", idx, trainer, rgb_u8).to(self.device)
+            if tuple(labels.shape) != tuple(rgb_u8.shape[:2]):
+                raise ValueError(f"train_cell_model: label map {list(labels.shape)} against image {list(rgb_u8.shape[:2])}")
+            ids, boxes = cellhead.instance_boxes(labels)
+            if ids.numel() == 0:
+                return None
+            feats, bm, bv = trainer.net.forward_train(trainer.crops(rgb_u8, boxes))   # all N crops of the image in one batch, as the reference's forward has them
+            trainer.net.check_finite()
+            targets = cellhead.instance_targets(labels, masks[0].to(self.device), nc)
+            return feats.cpu(), bm.cpu(), bv.cpu(), targets.cpu()
+
+        best_dir, checkpoint = None, 0.0
+        for epoch in range(epochs):
+            losses = []
+            for inputs, masks, index in aug_train_loader:
+                idx = int(index[0])
+                if cache_features and idx in cache:
+                    got = cache[idx]
+                else:
+                    got = train_pass(idx, inputs, masks)
+                    if cache_features:
+                        cache[idx] = got
+                if got is None:
+                    continue
+                feats, bm, bv, targets = got
+                cellhead.ema_update(sd, trainer.net.bn_layout, bm, bv)
+                sel = targets >= 1
+                if fit_classifier and bool(sel.any()):
+                    optimizer.zero_grad()
+                    loss = F.cross_entropy(feats[sel] @ W.t() + b, targets[sel])
+                    loss.backward()
+                    optimizer.step()
+                    losses.append(loss.item())
+                    if self.cell_training_log["first_loss"] is None:
+                        self.cell_training_log["first_loss"] = loss.item()
+            avg_running_loss = sum(losses) / len(losses) if losses else 0.0
+            print(f"Epoch {epoch + 11}/{epochs + 10}, Loss: {avg_running_loss:.4f}")
+            sd["classifier.weight"], sd["classifier.bias"] = W.detach().clone(), b.detach().clone()
+
+            head = cellhead.CellSegClassifier(nc, sd, self.device, instances=instances, input_norm=False)   # eval mode on the current state
+            total_dice = 0.0
+            for images, labels, index in aug_val_loader:
+                rgb_u8 = to_u8(images)
+                lm = label_map("val", int(index[0]), head, rgb_u8)
+                pred = head.predict_mask(rgb_u8, labels=lm)
+                truth = labels.to(self.device)
+                if tuple(truth.shape[-2:]) != tuple(pred.shape):
+                    truth = F.interpolate(truth[:, None].float(), size=tuple(pred.shape), mode="nearest")[:, 0]
+                _, avg_dice = self.micro_dice(predicted_labels=pred[None].contiguous(), true_labels=truth.to(torch.int64).contiguous(), num_classes=nc)
+                total_dice += avg_dice.item()
+            head.net.check_finite()
+            del head
+            total_dice = total_dice / len(aug_val_loader)
+            self.cell_training_log["loss"].append(avg_running_loss)
+            self.cell_training_log["dice"].append(total_dice)
+            if total_dice > checkpoint:
+                checkpoint = total_dice
+                best_dir = os.path.join(save_root if save_root is not None else "./LDiffusion/train_save/cellclassifier", current_date)
+                os.makedirs(best_dir, exist_ok=True)
+                torch.save({k: v.detach().clone() for k, v in sd.items()}, os.path.join(best_dir, "cellclassifier.pth"))
+                print(f"\033[32mNew Best Validation Dice Score: {total_dice:.4f}\033[0m")
+            else:
+                print(f"Validation Dice Score: {total_dice:.4f}")
+        return best_dir
 
     def _cell_head(self, weight_dir):
         """The cell head of a `segmentor_weight` folder (cellclassifier.pth), built once per (file, mtime)."""
