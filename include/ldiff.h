@@ -50,8 +50,9 @@
 extern "C" {
 #endif
 
-#define LDIFF_VERSION 211 /* 0.2.1.0: + ldiff_op_window_gather / _accumulate_batch / _finish (the tissue head's sliding window in batches: tiles x mirror variants gathered, un-flipped, averaged and Gaussian-accumulated per chunk, then divide + inf flag + arg-max + un-crop in one launch; ldiff_window_tiles by value), after ldiff_op_dice_ce_stats / _from_sums, ldiff_op_bucket_pack, ldiff_op_sumsq (data-parallel tissue training); 0.2.0.9: + ldiff_op_case_bbox / _stats / _counts / _apply / _rank_to_coord (plan and preprocess of the tissue head's training cases on the device: non-zero box, crop statistics, label counts per row, normalise into the arena, rank -> pixel); 0.2.0.8: + ldiff_op_seg_intensity_lr (the intensity chain with nnU-Net's low-resolution simulation between contrast and the gammas), ldiff_op_spline_prefilter (cubic B-spline prefilter on the device, one workgroup per plane); 0.2.0.7: + ldiff_op_conv_wgrad (direct MFMA weight gradient of the narrow convs over the pixel index, no im2col), ldiff_op_colsum_slabs (slab-reduced bias gradient), both with fixed-order partials; 0.2.0.6: + ldiff_op_seg_sample (patches, labels and deep-supervision targets of a training batch from cases resident on the device), ldiff_op_seg_intensity (nnU-Net's intensity augmentations, one workgroup per plane); 0.2.0.5: + ldiff_unet_set_plan_batch / ldiff_vae_set_plan_batch / ldiff_controlnet_set_plan_batch (batch-invariant mode: every launch planned for a nominal batch), ldiff_op_conv_pb, ldiff_op_attention_pb, ldiff_op_gn_stats_pb; 0.2.0.4: + ldiff_op_in_train_fwd / _bwd (InstanceNorm + LeakyReLU with saved statistics), ldiff_op_dice_ce (nnU-Net deep-supervision loss of one scale, value and gradient), ldiff_op_sgd_nesterov_multi; 0.2.0.3: + ldiff_confusion (per-image confusion matrices of masks or logits against labels, accumulated on the device), ldiff_seg_metrics (host: Dice / IoU / pixel accuracy / frequency-weighted IoU from one matrix); 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
+#define LDIFF_VERSION 212 /* 0.2.1.1: + ldiff_op_resize_u8 / ldiff_op_resize_u8_ws_bytes (the device image front end: PIL.Image.resize(size, BILINEAR) of 8-bit interleaved images bit for bit from host-made coefficient tables, optionally through a float [3][256] table into the sampler's NCHW input; LDIFF_RESIZE_MAX_TAPS); 0.2.1.0: + ldiff_op_window_gather / _accumulate_batch / _finish (the tissue head's sliding window in batches: tiles x mirror variants gathered, un-flipped, averaged and Gaussian-accumulated per chunk, then divide + inf flag + arg-max + un-crop in one launch; ldiff_window_tiles by value), after ldiff_op_dice_ce_stats / _from_sums, ldiff_op_bucket_pack, ldiff_op_sumsq (data-parallel tissue training); 0.2.0.9: + ldiff_op_case_bbox / _stats / _counts / _apply / _rank_to_coord (plan and preprocess of the tissue head's training cases on the device: non-zero box, crop statistics, label counts per row, normalise into the arena, rank -> pixel); 0.2.0.8: + ldiff_op_seg_intensity_lr (the intensity chain with nnU-Net's low-resolution simulation between contrast and the gammas), ldiff_op_spline_prefilter (cubic B-spline prefilter on the device, one workgroup per plane); 0.2.0.7: + ldiff_op_conv_wgrad (direct MFMA weight gradient of the narrow convs over the pixel index, no im2col), ldiff_op_colsum_slabs (slab-reduced bias gradient), both with fixed-order partials; 0.2.0.6: + ldiff_op_seg_sample (patches, labels and deep-supervision targets of a training batch from cases resident on the device), ldiff_op_seg_intensity (nnU-Net's intensity augmentations, one workgroup per plane); 0.2.0.5: + ldiff_unet_set_plan_batch / ldiff_vae_set_plan_batch / ldiff_controlnet_set_plan_batch (batch-invariant mode: every launch planned for a nominal batch), ldiff_op_conv_pb, ldiff_op_attention_pb, ldiff_op_gn_stats_pb; 0.2.0.4: + ldiff_op_in_train_fwd / _bwd (InstanceNorm + LeakyReLU with saved statistics), ldiff_op_dice_ce (nnU-Net deep-supervision loss of one scale, value and gradient), ldiff_op_sgd_nesterov_multi; 0.2.0.3: + ldiff_confusion (per-image confusion matrices of masks or logits against labels, accumulated on the device), ldiff_seg_metrics (host: Dice / IoU / pixel accuracy / frequency-weighted IoU from one matrix); 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
 #define LDIFF_MAX_BLOCKS 8
+#define LDIFF_RESIZE_MAX_TAPS 128 /* longest coefficient row ldiff_op_resize_u8 takes: reductions up to 63x (a 16x reduction has 33 taps) */
 
 typedef enum { LDIFF_OK = 0, LDIFF_ERR_INVALID = -1, LDIFF_ERR_RUNTIME = -2, LDIFF_ERR_STATE = -3, LDIFF_ERR_NONFINITE = -4 } ldiff_status;
 typedef enum { LDIFF_F32 = 0, LDIFF_F16 = 1, LDIFF_BF16 = 2 } ldiff_dtype; /* host dtypes accepted by *_load */
@@ -364,6 +365,20 @@ int ldiff_luma_float(const void* rgb_nchw, void* gray, int B, int H, int W, void
 /* F.interpolate(x, size=(out_h,out_w), mode="bilinear", align_corners=False) on fp32 NCHW (ldiffusion.py:240,250: the decoded
  * image is resized to 64x64 before the float luma of the training-time features). */
 int ldiff_bilinear_resize(const void* x_nchw_f32, void* y_nchw_f32, int B, int C, int H, int W, int out_h, int out_w, void* stream);
+/* PIL.Image.resize((Wo, Ho), Image.BILINEAR) of 8-bit images, bit for bit (Pillow's 8-bit rule is integer arithmetic; utils.py:180, segmentor.py:92,428: the
+ * Resize((1024, 1024)) in front of the sampler and behind it).  x_u8 [B, Hs, Ws, C] interleaved, C = 1 or 3, all B images one size.
+ *   - the tables are made on the HOST in double, once per (in, out) pair (python: imgio.coefficients), and live on the device: bounds_i32 [out][2] =
+ *     (first source index, window length) and coef_i32 [out][taps] = int(0.5 + w * 2^22), zero behind the window; h* for Ws -> Wo, v* for Hs -> Ho.
+ *     The tables of a side that does not change are not read (NULL, 0): that pass is skipped.
+ *   - out = clip((2^21 + sum_j coef[j] * src[first + j]) >> 22, 0, 255); the horizontal pass first, the intermediate [B, Hs, Wo, C] rounded and clipped to
+ *     uint8 in `ws` (ldiff_op_resize_u8_ws_bytes bytes, caller-owned, 0 when one launch does it).  Reads are clamped into the source whatever the tables say.
+ *   - lut_f32_or_null NULL: out is uint8 [B, Ho, Wo, C].  Else (C = 3 only) lut is float [3][256] on the device and out is float32 [B, 3, Ho, Wo] NCHW with
+ *     out[b, c, y, x] = lut[c][resized byte]: ToTensor + Normalize as a table the caller evaluates (python: imgio.normalize_table), the sampler's input in one step.
+ *   - LDIFF_ERR_INVALID, naming the argument: C other than 1 | 3, a side of 0, a missing table, htaps / vtaps above LDIFF_RESIZE_MAX_TAPS, ws too small, lut with C = 1,
+ *     B, Hs or Ho above 65535. */
+int64_t ldiff_op_resize_u8_ws_bytes(int B, int Hs, int Ws, int C, int Ho, int Wo, int to_float); /* -1: a shape ldiff_op_resize_u8 refuses */
+int ldiff_op_resize_u8(const void* x_u8, int B, int Hs, int Ws, int C, int Ho, int Wo, const void* hbounds_i32, const void* hcoef_i32, int htaps, const void* vbounds_i32,
+                       const void* vcoef_i32, int vtaps, const void* lut_f32_or_null, void* out, void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Metrics  --  scoring the masks where they are (utils.py:55-104, evaluate.py:11-126, segmentor.py:114-142,284-289)

@@ -161,6 +161,8 @@ SIGNATURES = {
     "ldiff_window_accumulate": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P]),
     "ldiff_luma_float": (I, [P, P, I, I, I, P]),
     "ldiff_bilinear_resize": (I, [P, P, I, I, I, I, I, I, P]),
+    "ldiff_op_resize_u8_ws_bytes": (I64, [I, I, I, I, I, I, I]),
+    "ldiff_op_resize_u8": (I, [P, I, I, I, I, I, I, P, P, I, P, P, I, P, P, P, I64, P]),
     "ldiff_pipeline_create": (I, [C.POINTER(P), P, P]),
     "ldiff_pipeline_set_alphas_cumprod": (I, [P, C.POINTER(F), I]),
     "ldiff_pipeline_set_overlap": (I, [P, I]),

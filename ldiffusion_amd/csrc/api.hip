@@ -335,6 +335,14 @@ int ldiff_op_crop_resize_norm(const void* rgb_u8, int H, int W, const void* boxe
   launch_crop_resize_norm((const uint8_t*)rgb_u8, H, W, (const int*)boxes_i32, n, (const uint8_t*)lut_u8, S, mean3, std3, (f16*)out_f16, (hipStream_t)stream);
   API_END
 }
+int64_t ldiff_op_resize_u8_ws_bytes(int B, int Hs, int Ws, int C, int Ho, int Wo, int to_float) { return resize_u8_ws_bytes(B, Hs, Ws, C, Ho, Wo, to_float); }
+int ldiff_op_resize_u8(const void* x_u8, int B, int Hs, int Ws, int C, int Ho, int Wo, const void* hbounds_i32, const void* hcoef_i32, int htaps, const void* vbounds_i32,
+                       const void* vcoef_i32, int vtaps, const void* lut_f32_or_null, void* out, void* ws, int64_t ws_bytes, void* stream) {
+  API_BEGIN
+  launch_resize_u8((const uint8_t*)x_u8, B, Hs, Ws, C, Ho, Wo, (const int*)hbounds_i32, (const int*)hcoef_i32, htaps, (const int*)vbounds_i32, (const int*)vcoef_i32, vtaps,
+                   (const float*)lut_f32_or_null, out, ws, ws_bytes, (hipStream_t)stream);
+  API_END
+}
 int ldiff_op_cls_head(const void* x, int B, int HW, int A, int ldx, const void* w_f32, const void* bias_f32, int C, void* logits_f32, void* labels_i32_or_null, void* stream) {
   API_BEGIN
   launch_cls_head((const f16*)x, B, HW, A, ldx, (const float*)w_f32, (const float*)bias_f32, C, (float*)logits_f32, (int*)labels_i32_or_null, (hipStream_t)stream);

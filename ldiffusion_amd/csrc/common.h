@@ -207,6 +207,10 @@ bool cls_conv_selected(const ConvParams& p);
 void launch_cls_conv(const ConvParams& p, hipStream_t s);
 void launch_maxpool3x3s2(const f16* x, f16* y, int B, int H, int W, int C, hipStream_t s);   // [B, H, W, C] -> [B, (H - 1) / 2 + 1, (W - 1) / 2 + 1, C], C % 8 == 0
 void launch_crop_resize_norm(const uint8_t* rgb, int H, int W, const int* boxes, int n, const uint8_t* lut, int S, const double* mean3, const double* std3, f16* out, hipStream_t s);
+// kernels_imgio.hip: PIL's 8-bit bilinear resize from host-made tables (include/ldiff.h ldiff_op_resize_u8)
+long long resize_u8_ws_bytes(int B, int Hs, int Ws, int C, int Ho, int Wo, int to_float);
+void launch_resize_u8(const uint8_t* x, int B, int Hs, int Ws, int C, int Ho, int Wo, const int* hbounds, const int* hcoef, int htaps, const int* vbounds, const int* vcoef,
+                      int vtaps, const float* lut, void* out, void* ws, long long ws_bytes, hipStream_t s);
 void launch_cls_head(const f16* x, int B, int HW, int A, int ldx, const float* w, const float* bias, int C, float* logits, int* labels_or_null, hipStream_t s);
 void launch_cls_head_feat(const f16* x, int B, int HW, int A, int ldx, const float* w, const float* bias, int C, float* logits_or_null, int* labels_or_null, float* feat_or_null, hipStream_t s);
 // training-mode BatchNorm of that classifier (kernels_cls.hip: the conv's statistics epilogue; kernels_clstrain.hip: finalize and apply; include/ldiff.h ldiff_op_bn_*)

@@ -166,7 +166,8 @@ class LDiffusionModel:
         ldiffusion_weight, args.diffusion_path)` with the loaders' `dataset.image_dir` / `label_dir` lists (:306-311) and returns the trained-model
         folder; loaders without such a dataset (plain lists of batches) need the four lists as keyword arguments `train_images`, `train_labels`,
         `test_images`, `test_labels`.  `iterations_per_epoch`, `val_iterations` and `num_foreground_voxels` are handed on too, and so is `wgrad_route`
-        (the route of the tissue trainer's weight gradients, `nnunet_train.Trainer`'s keyword; None: its default).  At level "cell" it is
+        (the route of the tissue trainer's weight gradients, `nnunet_train.Trainer`'s keyword; None: its default), and `batch_images` / `io_workers` (the
+        batched dataset pass, `utils.create_nnunet_dataset`'s keywords; not given: the per-image pass).  At level "cell" it is
         `Segmentor.train_cell_model(args.num_epochs - 10, ldiffusion_weight, args.diffusion_path, cell_weights=..., instances=...)` (:312-313) and returns
         the folder that holds cellclassifier.pth (None when no epoch validated above 0.0).  `cell_weights` = the CellSegClassifier state dict (or its path)
         the stage starts from: the reference starts from torchvision's ImageNet weights, which it downloads, and this build downloads nothing -- without
@@ -175,7 +176,7 @@ class LDiffusionModel:
         if component not in ("all", "ldiffusion", "segmentor"):
             raise ValueError(f"unknown component {component!r}")
         segmentor_kwargs = {k: _ignored[k] for k in ("train_images", "train_labels", "test_images", "test_labels", "iterations_per_epoch", "val_iterations",
-                                                          "num_foreground_voxels") if k in _ignored}
+                                                          "num_foreground_voxels", "batch_images", "io_workers") if k in _ignored}
         if component in ("all", "ldiffusion"):
             if train_loader is None:
                 raise RuntimeError("LDiffusionModel.train: the reference's dataset pipeline (load_data, dataset.py) is outside this build; pass train_loader=")
@@ -208,18 +209,20 @@ class LDiffusionModel:
         return ldiffusion_weight
 
     def inference(self, image_path, ldiffusion_weight, segmentor_weight, num_classes, head=None, predictor=None, output_path=None,
-                  text_embeddings=None, instances=None, batch_tiles=None, **_readme_kwargs):
+                  text_embeddings=None, instances=None, batch_tiles=None, batch_images=None, **_readme_kwargs):
         """ldiffusion.py:317-324.  Tissue: `segmentor_weight` = nnU-Net's trained-model folder, as in the reference (the head then runs on the HIP
         library, nnunet.py), or `predictor` = any head callable; cell: `segmentor_weight` = the folder with cellclassifier.pth (the ResNet152
         instance classifier then runs on the HIP library, cellhead.py; `instances` = the label-map callable, Cellpose where installed), or
         `head` = any head callable; `output_path` is the folder-mode argument of the tissue path; `batch_tiles` (tissue) = tiles per head call of the batched
-        sliding window, None = one call per tile and mirror variant (Segmentor.inference_tissue_model_nnUNetv2); other README-era keyword arguments (dtm_path)
+        sliding window, None = one call per tile and mirror variant (Segmentor.inference_tissue_model_nnUNetv2); `batch_images` (tissue, folder mode) = images per
+        sampler call, None = one file at a time; other README-era keyword arguments (dtm_path)
         are accepted and ignored like the code ignores them."""
         segmentor = Segmentor(train_loader=None, val_loader=None, level=self.level, num_classes=num_classes)
         if self.level == "tissue":
             return segmentor.inference_tissue_model_nnUNetv2(image_path, self.diffusion_path, ldiffusion_weight, segmentor_weight,
                                                              output_path=output_path, predictor=predictor if predictor is not None else head,
-                                                             text_embeddings=text_embeddings, batch_tiles=batch_tiles)
+                                                             text_embeddings=text_embeddings, batch_tiles=batch_tiles,
+                                                             **({} if batch_images is None else {"batch_images": batch_images}))
         elif self.level == "cell":
             return segmentor.inference_cell_model(image_path, self.diffusion_path, ldiffusion_weight, segmentor_weight, head=head,
                                                   text_embeddings=text_embeddings, instances=instances)

@@ -161,9 +161,8 @@ class Segmentor:
         rgb = out["rgb"]  # [B,H,W,3] u8
         if rgb.shape[1:3] == (1024, 1024):
             return rgb.permute(0, 3, 1, 2).float() / 255.0
-        from PIL import Image  # other sizes: the reference's PIL bilinear Resize, on the host
-        ims = [np.asarray(Image.fromarray(a).resize((1024, 1024), Image.BILINEAR), np.float32) / 255.0 for a in rgb.cpu().numpy()]
-        return torch.from_numpy(np.stack(ims)).permute(0, 3, 1, 2).contiguous().to(self.device)
+        from . import imgio  # other sizes: the reference's PIL bilinear Resize + ToTensor, bit for bit on the device (imgio.resize_u8 behind numpy's float32 / 255.0 as a table)
+        return imgio.resize_to_tensor(rgb, (1024, 1024))
 
     @torch.no_grad()
     def ldiffusion_augment_for_multimodal(self, rgb, dtm, pipeline, unet, vae, controlnet, batch_size, device, u=None, seed=0):
@@ -221,7 +220,7 @@ class Segmentor:
         return recon
 
     def train_tissue_model_nnUNetv2(self, epochs, ldiffusion_weight, diffusion_path, train_images=None, train_labels=None, test_images=None, test_labels=None,
-                                    num_classes=None, *, iterations_per_epoch=250, val_iterations=50, num_foreground_voxels=None, wgrad_route=None):
+                                    num_classes=None, *, iterations_per_epoch=250, val_iterations=50, num_foreground_voxels=None, wgrad_route=None, batch_images=None, io_workers=4):
         """segmentor.py:163-241: the tissue head's training stage, from image lists to a trained-model folder.
         Dataset (:167-205): `load_ldiffusion`, the cached text embeddings of "A pathological slide", the text-alignment wrapper, and
         `utils.create_nnunet_dataset` under nnUNet_raw (the one-pass diffusion of every image when all share one size, else copies).
@@ -232,7 +231,8 @@ class Segmentor:
         `PatchLoader`s with the plans' patch and batch size, `nnunet_train.Trainer.run_training`; checkpoints under
         nnUNet_results/<dataset>/nnUNetTrainer__nnUNetPlans__2d/fold_0, plans.json and dataset.json beside it.
         `iterations_per_epoch`, `val_iterations`: nnUNetTrainer's 250 / 50.  `num_foreground_voxels`: the fingerprint's sample budget (None: the
-        reference's 10e7).  `wgrad_route`: `nnunet_train.Trainer`'s (None: its default).  The three folders come from the environment variables nnUNet_raw, nnUNet_preprocessed, nnUNet_results.
+        reference's 10e7).  `wgrad_route`: `nnunet_train.Trainer`'s (None: its default).  `batch_images`, `io_workers`: `utils.create_nnunet_dataset`'s
+        (None: the per-image dataset pass; an integer: the pass batched behind the device image front end).  The three folders come from the environment variables nnUNet_raw, nnUNet_preprocessed, nnUNet_results.
         Under a process group of more than one rank the stage is data-parallel, as the reference's nnUNetTrainer is under the same launch: rank 0 alone
         writes the dataset, the fingerprint, plans, split and the model folder; `(new_num, dataset_name)` go out by `broadcast_object_list` and a
         barrier; every rank then reads the PNGs and JSONs and builds both stores on its own device; its loaders take its entry of
@@ -264,8 +264,9 @@ class Segmentor:
             if utils.check_images_same_size(train_images) and utils.check_images_same_size(test_images):   # only then does a sampler run (utils.py:213)
                 self._ensure_ldiffusion_proj(pipeline, unet, ldiffusion_weight=ldiffusion_weight)
                 aligned_unet = TextAlignedUNet(unet, self._get_text_embeddings(PROMPT, 1, pipeline, unet))
+            batch_kwargs = {} if batch_images is None else dict(batch_images=batch_images, io_workers=io_workers)   # None: the call of before the keyword
             named = list(utils.create_nnunet_dataset(train_images, train_labels, test_images, test_labels, num_classes, pipeline, aligned_unet,
-                                                     raw_dir=roots["nnUNet_raw"]))
+                                                     raw_dir=roots["nnUNet_raw"], **batch_kwargs))
         if world > 1:
             dist.broadcast_object_list(named, src=0)
             dist.barrier()
@@ -553,9 +554,58 @@ class Segmentor:
         return cache[key]
 
     @torch.no_grad()
+    def _tissue_folder_batched(self, head, image_path, output_path, diffusion_path, ldiffusion_weight, text_embeddings, tile_size, tile_step_size, mirror_axes, batch_tiles,
+                               batch_images):
+        """Folder mode of `inference_tissue_model_nnUNetv2` with `batch_images`: one pipeline for the folder, the sampler in batches, the head per image."""
+        from PIL import Image
+        from . import imgio
+        if isinstance(batch_images, bool) or not isinstance(batch_images, int) or batch_images < 1:
+            raise ValueError(f"batch_images = {batch_images!r}: an integer >= 1")
+        names = [n for n in sorted(os.listdir(image_path)) if n.lower().endswith((".png", ".jpg", ".jpeg", ".tif", ".tiff", ".bmp"))]
+        axes = "checkpoint" if mirror_axes is None else mirror_axes
+
+        def head_mask(name, data):   # data [3, H, W] float on the device, what the PNG the reference writes would hold
+            mask = head.predict_mask(data, tile_size, tile_step_size, axes, batch_tiles=batch_tiles)
+            head.network.check_finite()
+            Image.fromarray(mask.cpu().numpy()).save(os.path.join(output_path, os.path.splitext(name)[0] + ".png"))
+
+        groups = {}   # source size -> names, in name order
+        for name in names:
+            with Image.open(os.path.join(image_path, name)) as im:
+                w, h = im.size
+            if w == h:
+                groups.setdefault((w, h), []).append(name)
+            else:                                                                             # non-square: no diffusion (segmentor.py:449-450)
+                with Image.open(os.path.join(image_path, name)) as im:
+                    head_mask(name, torch.from_numpy(np.array(im.convert("RGB"), np.uint8)).to(self.device).permute(2, 0, 1).float())
+        if not groups:
+            return
+        pipeline, unet, _ = self.load_ldiffusion(ldiffusion_weight, diffusion_path)
+        previous = (unet.plan_batch, pipeline.vae.plan_batch)
+        try:
+            pipeline.set_plan_batch(batch_images)
+            if text_embeddings is None:
+                text_embeddings = self._get_text_embeddings(PROMPT, 1, pipeline, unet)
+            for group in groups.values():
+                for i in range(0, len(group), batch_images):
+                    part = group[i:i + batch_images]
+                    host = []
+                    for name in part:
+                        with Image.open(os.path.join(image_path, name)) as im:
+                            host.append(np.asarray(im.convert("RGB"), np.uint8))
+                    x = imgio.resize_normalize(torch.from_numpy(np.stack(host)).to(self.device), (1024, 1024), IMAGENET_MEAN, IMAGENET_STD)
+                    rgb = self._one_pass(x, text_embeddings, pipeline, unet)["rgb"]           # [b, 1024, 1024, 3] u8, on the device
+                    self._sampler.check_finite()   # before any mask of the batch is written
+                    for j, name in enumerate(part):
+                        head_mask(name, rgb[j].permute(2, 0, 1).float())
+        finally:
+            unet.set_plan_batch(previous[0])
+            pipeline.vae.set_plan_batch(previous[1])
+
+    @torch.no_grad()
     def inference_tissue_model_nnUNetv2(self, image_path, diffusion_path, ldiffusion_weight, segmentor_weight, output_path=None,
                                         predictor=None, text_embeddings=None, tile_size=None, tile_step_size=0.5,
-                                        mirror_axes=None, num_heads=None, batch_tiles=None):
+                                        mirror_axes=None, num_heads=None, batch_tiles=None, batch_images=None):
         """segmentor.py:388-488.  The tissue head is either
         * built from `segmentor_weight`, a trained-model folder as the reference's nnUNetPredictor reads it (dataset.json, plans.json,
           fold_0/checkpoint_best.pth; :463-468), when `predictor` is None: nnU-Net v2's 2-D PlainConvUNet on the HIP library (`nnunet.py`; cached on this
@@ -573,7 +623,11 @@ class Segmentor:
           is returned like :486-488.
         * batch_tiles: None = one head call per tile and mirror variant; an integer = the batched sliding window (`tiling.predict_sliding_window_batched`), for the
           library's head and an injected `predictor` alike, in folder mode too.  An injected predictor must then accept a batch,
-          `predictor([batch_tiles * M, 3, th, tw]) -> [batch_tiles * M, heads, th, tw]` (M = 1, 2 or 4 mirror variants), and treat its entries independently."""
+          `predictor([batch_tiles * M, 3, th, tw]) -> [batch_tiles * M, heads, th, tw]` (M = 1, 2 or 4 mirror variants), and treat its entries independently.
+        * batch_images (folder mode of the library's head; None = one call per file, as above): the square images of the folder go through the sampler in
+          batches of up to `batch_images`, grouped by source size in name order, behind `imgio.resize_normalize`, under `set_plan_batch(batch_images)` (the
+          previous plan batch comes back afterwards); each decoded image then goes to the head as above and `batch_tiles` is unaffected; non-square images
+          skip the diffusion as above.  The mask files are those of the per-image path under the same plan batch."""
         from PIL import Image
         from . import tiling
         head = None
@@ -586,6 +640,10 @@ class Segmentor:
             if not output_path:
                 raise ValueError("When image_path is a folder, output_path must be specified!")
             os.makedirs(output_path, exist_ok=True)
+            if batch_images is not None:
+                self._tissue_folder_batched(head, image_path, output_path, diffusion_path, ldiffusion_weight, text_embeddings, tile_size, tile_step_size, mirror_axes,
+                                            batch_tiles, batch_images)
+                return None, None
             for name in sorted(os.listdir(image_path)):
                 if name.lower().endswith((".png", ".jpg", ".jpeg", ".tif", ".tiff", ".bmp")):
                     _, m = self.inference_tissue_model_nnUNetv2(os.path.join(image_path, name), diffusion_path, ldiffusion_weight, segmentor_weight,
