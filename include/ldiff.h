@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define LDIFF_VERSION 212 /* 0.2.1.1: + ldiff_op_resize_u8 / ldiff_op_resize_u8_ws_bytes (the device image front end: PIL.Image.resize(size, BILINEAR) of 8-bit interleaved images bit for bit from host-made coefficient tables, optionally through a float [3][256] table into the sampler's NCHW input; LDIFF_RESIZE_MAX_TAPS); 0.2.1.0: + ldiff_op_window_gather / _accumulate_batch / _finish (the tissue head's sliding window in batches: tiles x mirror variants gathered, un-flipped, averaged and Gaussian-accumulated per chunk, then divide + inf flag + arg-max + un-crop in one launch; ldiff_window_tiles by value), after ldiff_op_dice_ce_stats / _from_sums, ldiff_op_bucket_pack, ldiff_op_sumsq (data-parallel tissue training); 0.2.0.9: + ldiff_op_case_bbox / _stats / _counts / _apply / _rank_to_coord (plan and preprocess of the tissue head's training cases on the device: non-zero box, crop statistics, label counts per row, normalise into the arena, rank -> pixel); 0.2.0.8: + ldiff_op_seg_intensity_lr (the intensity chain with nnU-Net's low-resolution simulation between contrast and the gammas), ldiff_op_spline_prefilter (cubic B-spline prefilter on the device, one workgroup per plane); 0.2.0.7: + ldiff_op_conv_wgrad (direct MFMA weight gradient of the narrow convs over the pixel index, no im2col), ldiff_op_colsum_slabs (slab-reduced bias gradient), both with fixed-order partials; 0.2.0.6: + ldiff_op_seg_sample (patches, labels and deep-supervision targets of a training batch from cases resident on the device), ldiff_op_seg_intensity (nnU-Net's intensity augmentations, one workgroup per plane); 0.2.0.5: + ldiff_unet_set_plan_batch / ldiff_vae_set_plan_batch / ldiff_controlnet_set_plan_batch (batch-invariant mode: every launch planned for a nominal batch), ldiff_op_conv_pb, ldiff_op_attention_pb, ldiff_op_gn_stats_pb; 0.2.0.4: + ldiff_op_in_train_fwd / _bwd (InstanceNorm + LeakyReLU with saved statistics), ldiff_op_dice_ce (nnU-Net deep-supervision loss of one scale, value and gradient), ldiff_op_sgd_nesterov_multi; 0.2.0.3: + ldiff_confusion (per-image confusion matrices of masks or logits against labels, accumulated on the device), ldiff_seg_metrics (host: Dice / IoU / pixel accuracy / frequency-weighted IoU from one matrix); 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
+#define LDIFF_VERSION 213 /* 0.2.1.2: + ldiff_op_label_table_u8 / ldiff_op_gather_labels / ldiff_op_warmup_labels (+ _supported) / ldiff_op_warmup_images (the warm-up trainer's dataset resident on the device: label bytes through a grey-level table, a batch of labels and masks gathered by index, and the 64x64 warm-up batch -- labels by torch's bilinear rule in integers, images through the normalisation table and the antialiased triangle weights in one pass over the stored bytes); 0.2.1.1: + ldiff_op_resize_u8 / ldiff_op_resize_u8_ws_bytes (the device image front end: PIL.Image.resize(size, BILINEAR) of 8-bit interleaved images bit for bit from host-made coefficient tables, optionally through a float [3][256] table into the sampler's NCHW input; LDIFF_RESIZE_MAX_TAPS); 0.2.1.0: + ldiff_op_window_gather / _accumulate_batch / _finish (the tissue head's sliding window in batches: tiles x mirror variants gathered, un-flipped, averaged and Gaussian-accumulated per chunk, then divide + inf flag + arg-max + un-crop in one launch; ldiff_window_tiles by value), after ldiff_op_dice_ce_stats / _from_sums, ldiff_op_bucket_pack, ldiff_op_sumsq (data-parallel tissue training); 0.2.0.9: + ldiff_op_case_bbox / _stats / _counts / _apply / _rank_to_coord (plan and preprocess of the tissue head's training cases on the device: non-zero box, crop statistics, label counts per row, normalise into the arena, rank -> pixel); 0.2.0.8: + ldiff_op_seg_intensity_lr (the intensity chain with nnU-Net's low-resolution simulation between contrast and the gammas), ldiff_op_spline_prefilter (cubic B-spline prefilter on the device, one workgroup per plane); 0.2.0.7: + ldiff_op_conv_wgrad (direct MFMA weight gradient of the narrow convs over the pixel index, no im2col), ldiff_op_colsum_slabs (slab-reduced bias gradient), both with fixed-order partials; 0.2.0.6: + ldiff_op_seg_sample (patches, labels and deep-supervision targets of a training batch from cases resident on the device), ldiff_op_seg_intensity (nnU-Net's intensity augmentations, one workgroup per plane); 0.2.0.5: + ldiff_unet_set_plan_batch / ldiff_vae_set_plan_batch / ldiff_controlnet_set_plan_batch (batch-invariant mode: every launch planned for a nominal batch), ldiff_op_conv_pb, ldiff_op_attention_pb, ldiff_op_gn_stats_pb; 0.2.0.4: + ldiff_op_in_train_fwd / _bwd (InstanceNorm + LeakyReLU with saved statistics), ldiff_op_dice_ce (nnU-Net deep-supervision loss of one scale, value and gradient), ldiff_op_sgd_nesterov_multi; 0.2.0.3: + ldiff_confusion (per-image confusion matrices of masks or logits against labels, accumulated on the device), ldiff_seg_metrics (host: Dice / IoU / pixel accuracy / frequency-weighted IoU from one matrix); 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
 #define LDIFF_MAX_BLOCKS 8
 #define LDIFF_RESIZE_MAX_TAPS 128 /* longest coefficient row ldiff_op_resize_u8 takes: reductions up to 63x (a 16x reduction has 33 taps) */
 
@@ -379,6 +379,30 @@ int ldiff_bilinear_resize(const void* x_nchw_f32, void* y_nchw_f32, int B, int C
 int64_t ldiff_op_resize_u8_ws_bytes(int B, int Hs, int Ws, int C, int Ho, int Wo, int to_float); /* -1: a shape ldiff_op_resize_u8 refuses */
 int ldiff_op_resize_u8(const void* x_u8, int B, int Hs, int Ws, int C, int Ho, int Wo, const void* hbounds_i32, const void* hcoef_i32, int htaps, const void* vbounds_i32,
                        const void* vcoef_i32, int vtaps, const void* lut_f32_or_null, void* out, void* ws, int64_t ws_bytes, void* stream);
+
+/* The warm-up trainer's dataset on the device (dataset.py:10-89, ldiffusion.py:72-119,200,212,225; python: ldiffusion_amd/dataset.py DeviceLoader).  The store is
+ * two uint8 arrays on the device: images [N, Hs, Ws, 3] interleaved (already through ldiff_op_resize_u8) and labels [N, H, W] (already class indices).  A batch is
+ * idx_i32 [B] on the device; an index outside [0, N) is clamped into the store (callers validate on the host).  A sample's result depends on its own bytes alone:
+ * no atomics, fixed summation order, the same bits whatever B and whatever its position in the batch.
+ *   - ldiff_op_label_table_u8: dst[i] = table_u8[src[i]], i < n; table_u8 [256] on the device; dst may be src.
+ *   - ldiff_op_gather_labels: label_u8 [B, 1, H, W] = cache[idx] and mask_i64 [B, H, W] = the same values as int64, one launch.
+ *   - ldiff_op_warmup_labels: out_u8 [B, 1, oh, ow] = F.interpolate(label.float(), (oh, ow), mode="bilinear", align_corners=False).to(uint8) bit for bit, for
+ *     H % oh == 0 and W % ow == 0 (ldiff_op_warmup_labels_supported returns 1): per axis an even ratio r averages source indices r*i + r/2 - 1 and r*i + r/2 with
+ *     weights 1/2, an odd one picks r*i + (r - 1)/2, so the value is (a + b + c + d) >> 2 in integers.  Other sizes are LDIFF_ERR_INVALID: torch's float32 result is
+ *     the target there, and the caller evaluates it.
+ *   - ldiff_op_warmup_images: out_f32 [B, 3, oh, ow] (NCHW) = sum_y wy[oy][y] * (sum_x wx[ox][x] * table[c][cache[idx[b], yfirst + y, xfirst + x, c]]), the
+ *     horizontal sum first, each sum accumulated in index order in float32.  table_f32 [3][256] is ToTensor + Normalize of the grey levels (python:
+ *     imgio.normalize_table); {x,y}bounds_i32 [out][2] = (first source index, window length) and {x,y}weights_f32 [out][taps] are the antialiased triangle weights
+ *     of F.interpolate(..., mode="bilinear", antialias=True) = Pillow's window rule (python: imgio.weights, made in double), zero behind the window,
+ *     taps <= LDIFF_RESIZE_MAX_TAPS; upsampling is the same formula with support 1.  Reads are clamped into the source whatever the tables say.
+ *   - LDIFF_ERR_INVALID, naming the argument: null pointers, N < 1, a side of 0, B or a height above 65535, taps outside 1 .. LDIFF_RESIZE_MAX_TAPS, a reduction
+ *     whose row span does not fit 64 KiB of LDS. */
+int ldiff_op_label_table_u8(const void* src_u8, void* dst_u8, int64_t n, const void* table_u8, void* stream);
+int ldiff_op_gather_labels(const void* cache_u8, int N, int H, int W, const void* idx_i32, int B, void* label_u8, void* mask_i64, void* stream);
+int ldiff_op_warmup_labels_supported(int H, int W, int oh, int ow);
+int ldiff_op_warmup_labels(const void* cache_u8, int N, int H, int W, const void* idx_i32, int B, int oh, int ow, void* out_u8, void* stream);
+int ldiff_op_warmup_images(const void* cache_u8, int N, int Hs, int Ws, const void* idx_i32, int B, const void* table_f32, const void* ybounds_i32, const void* yweights_f32, int ytaps,
+                           const void* xbounds_i32, const void* xweights_f32, int xtaps, int oh, int ow, void* out_f32, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Metrics  --  scoring the masks where they are (utils.py:55-104, evaluate.py:11-126, segmentor.py:114-142,284-289)

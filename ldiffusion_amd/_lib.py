@@ -163,6 +163,11 @@ SIGNATURES = {
     "ldiff_bilinear_resize": (I, [P, P, I, I, I, I, I, I, P]),
     "ldiff_op_resize_u8_ws_bytes": (I64, [I, I, I, I, I, I, I]),
     "ldiff_op_resize_u8": (I, [P, I, I, I, I, I, I, P, P, I, P, P, I, P, P, P, I64, P]),
+    "ldiff_op_label_table_u8": (I, [P, P, I64, P, P]),
+    "ldiff_op_gather_labels": (I, [P, I, I, I, P, I, P, P, P]),
+    "ldiff_op_warmup_labels_supported": (I, [I, I, I, I]),
+    "ldiff_op_warmup_labels": (I, [P, I, I, I, P, I, I, I, P, P]),
+    "ldiff_op_warmup_images": (I, [P, I, I, I, P, I, P, P, P, I, P, P, I, I, I, P, P]),
     "ldiff_pipeline_create": (I, [C.POINTER(P), P, P]),
     "ldiff_pipeline_set_alphas_cumprod": (I, [P, C.POINTER(F), I]),
     "ldiff_pipeline_set_overlap": (I, [P, I]),

@@ -343,6 +343,29 @@ int ldiff_op_resize_u8(const void* x_u8, int B, int Hs, int Ws, int C, int Ho, i
                    (const float*)lut_f32_or_null, out, ws, ws_bytes, (hipStream_t)stream);
   API_END
 }
+int ldiff_op_label_table_u8(const void* src_u8, void* dst_u8, int64_t n, const void* table_u8, void* stream) {
+  API_BEGIN
+  launch_label_table_u8((const uint8_t*)src_u8, (uint8_t*)dst_u8, n, (const uint8_t*)table_u8, (hipStream_t)stream);
+  API_END
+}
+int ldiff_op_gather_labels(const void* cache_u8, int N, int H, int W, const void* idx_i32, int B, void* label_u8, void* mask_i64, void* stream) {
+  API_BEGIN
+  launch_gather_labels((const uint8_t*)cache_u8, N, H, W, (const int*)idx_i32, B, (uint8_t*)label_u8, (long long*)mask_i64, (hipStream_t)stream);
+  API_END
+}
+int ldiff_op_warmup_labels_supported(int H, int W, int oh, int ow) { return warmup_labels_supported(H, W, oh, ow); }
+int ldiff_op_warmup_labels(const void* cache_u8, int N, int H, int W, const void* idx_i32, int B, int oh, int ow, void* out_u8, void* stream) {
+  API_BEGIN
+  launch_warmup_labels((const uint8_t*)cache_u8, N, H, W, (const int*)idx_i32, B, oh, ow, (uint8_t*)out_u8, (hipStream_t)stream);
+  API_END
+}
+int ldiff_op_warmup_images(const void* cache_u8, int N, int Hs, int Ws, const void* idx_i32, int B, const void* table_f32, const void* ybounds_i32, const void* yweights_f32, int ytaps,
+                           const void* xbounds_i32, const void* xweights_f32, int xtaps, int oh, int ow, void* out_f32, void* stream) {
+  API_BEGIN
+  launch_warmup_images((const uint8_t*)cache_u8, N, Hs, Ws, (const int*)idx_i32, B, (const float*)table_f32, (const int*)ybounds_i32, (const float*)yweights_f32, ytaps,
+                       (const int*)xbounds_i32, (const float*)xweights_f32, xtaps, oh, ow, (float*)out_f32, (hipStream_t)stream);
+  API_END
+}
 int ldiff_op_cls_head(const void* x, int B, int HW, int A, int ldx, const void* w_f32, const void* bias_f32, int C, void* logits_f32, void* labels_i32_or_null, void* stream) {
   API_BEGIN
   launch_cls_head((const f16*)x, B, HW, A, ldx, (const float*)w_f32, (const float*)bias_f32, C, (float*)logits_f32, (int*)labels_i32_or_null, (hipStream_t)stream);

@@ -211,6 +211,13 @@ void launch_crop_resize_norm(const uint8_t* rgb, int H, int W, const int* boxes,
 long long resize_u8_ws_bytes(int B, int Hs, int Ws, int C, int Ho, int Wo, int to_float);
 void launch_resize_u8(const uint8_t* x, int B, int Hs, int Ws, int C, int Ho, int Wo, const int* hbounds, const int* hcoef, int htaps, const int* vbounds, const int* vcoef,
                       int vtaps, const float* lut, void* out, void* ws, long long ws_bytes, hipStream_t s);
+// kernels_dataset.hip: the warm-up trainer's dataset on the device (include/ldiff.h ldiff_op_label_table_u8 / _gather_labels / _warmup_labels / _warmup_images)
+void launch_label_table_u8(const uint8_t* src, uint8_t* dst, long long n, const uint8_t* table, hipStream_t s);
+void launch_gather_labels(const uint8_t* cache, int N, int H, int W, const int* idx, int B, uint8_t* label, long long* mask, hipStream_t s);
+int warmup_labels_supported(int H, int W, int oh, int ow);
+void launch_warmup_labels(const uint8_t* cache, int N, int H, int W, const int* idx, int B, int oh, int ow, uint8_t* out, hipStream_t s);
+void launch_warmup_images(const uint8_t* cache, int N, int Hs, int Ws, const int* idx, int B, const float* table, const int* ybounds, const float* ywts, int ytaps, const int* xbounds,
+                          const float* xwts, int xtaps, int oh, int ow, float* out, hipStream_t s);
 void launch_cls_head(const f16* x, int B, int HW, int A, int ldx, const float* w, const float* bias, int C, float* logits, int* labels_or_null, hipStream_t s);
 void launch_cls_head_feat(const f16* x, int B, int HW, int A, int ldx, const float* w, const float* bias, int C, float* logits_or_null, int* labels_or_null, float* feat_or_null, hipStream_t s);
 // training-mode BatchNorm of that classifier (kernels_cls.hip: the conv's statistics epilogue; kernels_clstrain.hip: finalize and apply; include/ldiff.h ldiff_op_bn_*)

@@ -31,9 +31,9 @@ def _side(name, v):
 
 
 @functools.lru_cache(maxsize=64)
-def coefficients(in_size: int, out_size: int):
-    """(bounds int32 [out, 2] = (first source index, window length), coef int32 [out, taps]) of one pass in_size -> out_size; taps =
-    ceil(max(in / out, 1)) * 2 + 1 as Pillow allocates it, zeros behind a row's window.  Cached; the arrays are read-only."""
+def _window_weights(in_size: int, out_size: int):
+    """The double stage of one pass in_size -> out_size: (xmin int64 [out], xmax int64 [out] = window length, w float64 [out, taps]), the normalised
+    triangle weights in index order, zeros behind a row's window."""
     in_size, out_size = _side("in_size", in_size), _side("out_size", out_size)
     scale = in_size / out_size
     fs = max(scale, 1.0)
@@ -54,6 +54,27 @@ def coefficients(in_size: int, out_size: int):
         ww += col
     nz = ww != 0.0
     w[nz] /= ww[nz, None]
+    for a in (xmin, xmax, w):
+        a.setflags(write=False)
+    return xmin, xmax, w
+
+
+def weights(in_size: int, out_size: int):
+    """(bounds int32 [out, 2] = (first source index, window length), w float64 [out, taps]) of one pass in_size -> out_size: the window rule above before
+    it turns into integers.  These are the antialiased triangle weights of `F.interpolate(..., mode="bilinear", antialias=True, align_corners=False)`
+    (the same window and the same normalisation), which the warm-up kernel applies in float32 (dataset.py, ldiff_op_warmup_images).  Read-only arrays."""
+    xmin, xmax, w = _window_weights(in_size, out_size)
+    bounds = np.stack([xmin, xmax], 1).astype(np.int32)
+    bounds.setflags(write=False)
+    return bounds, w
+
+
+@functools.lru_cache(maxsize=64)
+def coefficients(in_size: int, out_size: int):
+    """(bounds int32 [out, 2] = (first source index, window length), coef int32 [out, taps]) of one pass in_size -> out_size; taps =
+    ceil(max(in / out, 1)) * 2 + 1 as Pillow allocates it, zeros behind a row's window.  Cached; the arrays are read-only."""
+    xmin, xmax, w = _window_weights(in_size, out_size)
+    taps = w.shape[1]
     coef = np.where(w < 0, -0.5 + w * (1 << PRECISION_BITS), 0.5 + w * (1 << PRECISION_BITS)).astype(np.int32)
     coef[np.arange(taps)[None, :] >= xmax[:, None]] = 0
     bounds = np.stack([xmin, xmax], 1).astype(np.int32)

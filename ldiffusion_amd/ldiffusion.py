@@ -1,18 +1,39 @@
 """Host-side mirror of the reference's orchestrator `LDiffusionModel` (/root/reference/ldiffusion.py:31-324) for the
 sampling path: same constructor and `inference(...)` signature (cell and tissue levels), same error for an invalid level.
 Training: `train_ldiffusion` (ldiffusion.py:121-295) runs on the HIP kernels, forward and backward (`ldiffusion_amd.train`,
-parity-tested against torch.autograd over the oracle), with the data loader injected; what differs from the reference (no ZeRO-3, optional
-VGG19 content term, fp16 operands) is listed in its docstring.  The segmentor stage of `train` runs at the tissue level
+parity-tested against torch.autograd over the oracle); what differs from the reference (no ZeRO-3, optional
+VGG19 content term, fp16 operands) is listed in its docstring.  The loaders are the reference's (`load_data`, ldiffusion.py:72-119, over
+`ldiffusion_amd.dataset`), built from `args.image_dir` / `args.label_dir` where none is injected; for the warm-up they are device-resident
+(`dataset.DeviceLoader`).  `parse_args` and `python -m ldiffusion_amd.ldiffusion` are the reference's command line (:19-29,326-331).  The segmentor stage of `train` runs at the tissue level
 (`Segmentor.train_tissue_model_nnUNetv2`); at the cell level it raises.
 """
 from __future__ import annotations
 
+import argparse
 import os
 
 import torch
 
 from .parallel import world_info
 from .segmentor import Segmentor
+
+
+def parse_args(argv=None):
+    """ldiffusion.py:19-29: the reference's eight flags, plus --level, --component and --ldiffusion-weight (the reference hard-codes them in its
+    `__main__`, :330-331)."""
+    parser = argparse.ArgumentParser(description="Diffusion model training parameters")
+    parser.add_argument("--local_rank", type=int, default=int(os.environ.get("LOCAL_RANK", -1)))
+    parser.add_argument("--diffusion-path", type=str, required=True, help="stable diffusion base model path")
+    parser.add_argument("--image-dir", type=str, required=True)
+    parser.add_argument("--label-dir", type=str, required=True)
+    parser.add_argument("--num-epochs", type=int, required=True)
+    parser.add_argument("--batch-size", type=int, required=True)
+    parser.add_argument("--num-inference-steps", type=int, required=True)
+    parser.add_argument("--num-classes", type=int, required=True)
+    parser.add_argument("--level", type=str, default="tissue", choices=("tissue", "cell"))
+    parser.add_argument("--component", type=str, default="all", choices=("all", "ldiffusion", "segmentor"))
+    parser.add_argument("--ldiffusion-weight", type=str, default=None, help="trained L-Diffusion weights, for --component segmentor")
+    return parser.parse_args(argv)
 
 
 class LDiffusionModel:
@@ -50,6 +71,13 @@ class LDiffusionModel:
         dist.all_reduce(t)
         return float(t.item() / dist.get_world_size())
 
+    def load_data(self, image_dir, label_dir, batch_size, train_ratio=0.7, **kw):
+        """ldiffusion.py:72-119 -> (train_loader, val_loader, train_sampler): `dataset.load_data` at the model's level, world, rank and device
+        (device-resident loaders; `device=None` among the keywords gives the host DataLoaders).  `image_size`, `io_workers` and `cache_bytes` are handed on."""
+        from . import dataset
+        kw.setdefault("device", self.device)
+        return dataset.load_data(image_dir, label_dir, batch_size, self.level, train_ratio=train_ratio, world=self.world_size, rank=self.rank, **kw)
+
     def train_ldiffusion(self, args, train_loader, val_loader=None):
         """ldiffusion.py:121-295 on the HIP kernels (forward and backward, ldiffusion_amd.train): per batch Resize(64) -> VAE encode ->
         V5 loop -> InfoNCE loss -> backward -> gradient all-reduce -> clip 1.0 -> AdamW(lr 1e-5, wd 0.01) on UNet + text projection; per epoch
@@ -58,7 +86,9 @@ class LDiffusionModel:
         Differences, all explicit: replicated parameters + one gradient all-reduce instead of ZeRO-3 with CPU offload; fp16 MFMA operands
         with fp32 accumulation / gradients / master weights instead of fp32 everywhere; the VGG19 content term only when
         `args.vgg_features` (a callable) is given -- ImageNet weights are not available offline, and the loop says so once.
-        `train_loader` yields (image [B,3,H,W] float in ToTensor range, _, label [B,1,H,W]) like the reference's PUMA loader."""
+        `train_loader` yields (image [B,3,H,W] float in ToTensor range, _, label [B,1,H,W]) like the reference's PUMA loader.  A loader that has
+        `warmup_batches` (dataset.DeviceLoader) is iterated through it instead: it yields the 64x64 image and label of each batch straight from its
+        device store (same order, same generator draws), and the two reductions below are not run."""
         import csv
         import time
         from datetime import datetime
@@ -105,13 +135,19 @@ class LDiffusionModel:
             if hasattr(train_loader, "sampler") and hasattr(train_loader.sampler, "set_epoch"):
                 train_loader.sampler.set_epoch(epoch)
             total, start = 0.0, time.time()
-            for image, _, label in train_loader:
+            from_store = hasattr(train_loader, "warmup_batches")
+            for batch in (train_loader.warmup_batches(64) if from_store else train_loader):
+                if from_store:
+                    image, lab = batch
+                else:
+                    image, _, label = batch
+                    image = F.interpolate(image.to(self.device, dtype=torch.float32), size=(64, 64), mode="bilinear", align_corners=False, antialias=True)
                 B = image.shape[0]
-                image = F.interpolate(image.to(self.device, dtype=torch.float32), size=(64, 64), mode="bilinear", align_corners=False, antialias=True)
                 ids = torch.tensor(self.pipeline.tokenizer(["A pathological slide"] * B)["input_ids"], dtype=torch.long, device=self.device)
                 with torch.no_grad():
                     text_hidden = self.pipeline.text_encoder(ids)["last_hidden_state"].to(dtype=torch.float32)
-                    lab = F.interpolate(label.to(self.device, torch.float32), size=(64, 64), mode="bilinear", align_corners=False).to(torch.uint8)
+                    if not from_store:
+                        lab = F.interpolate(label.to(self.device, torch.float32), size=(64, 64), mode="bilinear", align_corners=False).to(torch.uint8)
                     latents = self.vae.encode(image).latent_dist.mean.to(dtype=torch.float32)
                 self.pipeline.scheduler.set_timesteps(n_sched, device=self.device)
                 ts = [int(t) for t in self.pipeline.scheduler.timesteps]
@@ -160,7 +196,9 @@ class LDiffusionModel:
         return save_path
 
     def train(self, args, component="all", ldiffusion_weight=None, train_loader=None, val_loader=None, wgrad_route=None, cell_weights=None, instances=None, **_ignored):
-        """ldiffusion.py:297-315.  The PUMA dataset / dataloader (dataset.py, cv2) is outside this build: the loaders are injected.
+        """ldiffusion.py:297-315.  The loaders are injected (`train_loader=`, `val_loader=`), or, with none injected and `args` carrying `image_dir` and
+        `label_dir`, built as the reference builds them (`self.load_data(args.image_dir, args.label_dir, args.batch_size)`, with `args.image_size` (1024) and
+        `args.io_workers` (4) where present): device-resident for the warm-up, plain host loaders when only the segmentor stage runs (it reads their file lists).
         `component="ldiffusion"` runs the L-Diffusion warm-up on the HIP kernels and returns the saved weight directory.  The segmentor stage
         ("segmentor", or after the warm-up with "all") at level "tissue" is `Segmentor.train_tissue_model_nnUNetv2(args.num_epochs - 10,
         ldiffusion_weight, args.diffusion_path)` with the loaders' `dataset.image_dir` / `label_dir` lists (:306-311) and returns the trained-model
@@ -177,9 +215,18 @@ class LDiffusionModel:
             raise ValueError(f"unknown component {component!r}")
         segmentor_kwargs = {k: _ignored[k] for k in ("train_images", "train_labels", "test_images", "test_labels", "iterations_per_epoch", "val_iterations",
                                                           "num_foreground_voxels", "batch_images", "io_workers") if k in _ignored}
+        if train_loader is None and getattr(args, "image_dir", None) is not None and getattr(args, "label_dir", None) is not None:
+            if component in ("all", "segmentor") and self.level == "cell" and cell_weights is None:   # before any file is read
+                raise NotImplementedError("segmentor training at the cell level (train_cell_model, segmentor.py:243-299) starts from torchvision's downloaded ImageNet "
+                                          "weights in the reference; nothing is downloaded here: pass cell_weights= (a CellSegClassifier state dict or its path)")
+            kw = {"image_size": getattr(args, "image_size", 1024), "io_workers": getattr(args, "io_workers", 4)}
+            if component == "segmentor":
+                kw["device"] = None
+            train_loader, val_loader, _ = self.load_data(args.image_dir, args.label_dir, args.batch_size, **kw)
         if component in ("all", "ldiffusion"):
             if train_loader is None:
-                raise RuntimeError("LDiffusionModel.train: the reference's dataset pipeline (load_data, dataset.py) is outside this build; pass train_loader=")
+                raise RuntimeError("LDiffusionModel.train: no loaders: pass train_loader=, or args with image_dir and label_dir (the reference's load_data, "
+                                   "ldiffusion_amd.dataset)")
             if self._is_main_process():
                 print("Starting LDiffusion warming up...")
             ldiffusion_weight = self.train_ldiffusion(args, train_loader, val_loader)
@@ -228,3 +275,16 @@ class LDiffusionModel:
                                                   text_embeddings=text_embeddings, instances=instances)
         else:
             raise ValueError("Invalid level specified. Choose 'tissue' or 'cell'.")
+
+
+def main(argv=None):
+    """ldiffusion.py:326-331: `python -m ldiffusion_amd.ldiffusion --diffusion-path ... --image-dir ... --label-dir ...`."""
+    args = parse_args(argv)
+    if int(os.environ.get("RANK", "0")) == 0:
+        print(str(vars(args)))
+    trainer = LDiffusionModel(args.diffusion_path, level=args.level, local_rank=args.local_rank)
+    return trainer.train(args, component=args.component, ldiffusion_weight=args.ldiffusion_weight)
+
+
+if __name__ == "__main__":
+    main()
