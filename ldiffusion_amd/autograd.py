@@ -9,7 +9,7 @@ masters in the torch / diffusers layouts ([Cout, Cin, k, k], [out, in]) and rece
   * wgrad = the forward GEMM kernel over K = M on dy^T (ldiff_op_transpose) and im2col(x)^T (ldiff_op_im2col_t): the "staged" route, the default;
     under `wgrad_route("direct")` / `("auto")` the narrow convs over many pixels take ldiff_op_conv_wgrad (an MFMA contraction over the pixel index straight
     from the NHWC tensors) and the bias gradients ldiff_op_colsum_slabs instead (csrc/kernels_wgrad.hip; the tissue-head trainer runs under "auto");
-    under `wgrad_route("wide")` / `("auto-wide")` the wide convs that entry refuses take ldiff_op_conv_wgrad_wide as well (csrc/kernels_wgrad_wide.hip),
+    under `wgrad_route("wide")` / `("auto-wide")` the wide convs that entry refuses take ldiff_op_conv_wgrad_wide as well (the same kernel, Cy in blocks of 64),
   * GroupNorm(+SiLU), LayerNorm, GEGLU, attention: dedicated backward kernels (csrc/kernels_bwd.hip).
 There is no CPU or torch-op fallback for those; reshapes / layout casts / the residual `+` are torch tensor plumbing.
 """
@@ -169,7 +169,7 @@ def _conv_call(x, w16, Cout, k, stride, ups, bias=None, Ho=None, Wo=None, out_f3
 # "direct": ldiff_op_conv_wgrad wherever the shape is eligible (else staged) and ldiff_op_colsum_slabs for every bias gradient.
 # "auto":   "direct" for the launches with M = B Ho Wo >= WGRAD_DIRECT_MIN_ROWS, "staged" below.
 # "wide":   every weight gradient on a direct kernel wherever one takes the shape: ldiff_op_conv_wgrad where it is eligible (the bits of "direct"), else
-#           ldiff_op_conv_wgrad_wide (both channel counts blocked: csrc/kernels_wgrad_wide.hip), else staged; ldiff_op_colsum_slabs for every bias gradient it takes.
+#           ldiff_op_conv_wgrad_wide (both channel counts blocked: the same kernel of csrc/kernels_wgrad.hip), else staged; ldiff_op_colsum_slabs for every bias gradient it takes.
 # "auto-wide": the launches ldiff_op_conv_wgrad takes follow "auto" (and keep its bits); those only the wide entry takes go to it at
 #           M >= WGRAD_WIDE_MIN_ROWS; every bias gradient ldiff_op_colsum_slabs takes goes through it, whatever M.
 # The route is read when the FORWARD runs and kept with the node, so a backward() called outside the `with` follows the forward's route.
@@ -240,38 +240,60 @@ class wgrad_route:
         return False
 
 
+_NARROW_LIMITS = (128, 64, 128)     # Cx, Cy at k = 3, Cy at k = 1: what ldiff_op_conv_wgrad takes (include/ldiff.h)
+_WIDE_LIMITS = (1024, 512, 2048)    # the same of ldiff_op_conv_wgrad_wide
+
+
+def _wgrad_eligible(limits, k, stride, ups, Cx, Cy, Cout, Cin) -> bool:
+    cx_max, cy_max3, cy_max1 = limits
+    return (ups == 0 and ((k == 3 and stride in (1, 2)) or (k == 1 and stride == 1)) and Cx % 8 == 0 and 8 <= Cx <= cx_max and Cy % 8 == 0
+            and 8 <= Cy <= (cy_max3 if k == 3 else cy_max1) and 1 <= Cout <= Cy and 1 <= Cin <= Cx)
+
+
 def wgrad_direct_eligible(k, stride, ups, Cx, Cy, Cout, Cin) -> bool:
     """The shapes ldiff_op_conv_wgrad takes (include/ldiff.h)."""
-    return (ups == 0 and ((k == 3 and stride in (1, 2)) or (k == 1 and stride == 1)) and Cx % 8 == 0 and 8 <= Cx <= 128 and Cy % 8 == 0
-            and 8 <= Cy <= (64 if k == 3 else 128) and 1 <= Cout <= Cy and 1 <= Cin <= Cx)
-
-
-def wgrad_plan(B, Ho, Wo, Cx, Cy, k, wgs=0) -> dict:
-    """The plan ldiff_op_conv_wgrad makes for a launch (csrc/kernels_wgrad.hip wgrad_plan), for the error bounds of the tests: tiles of TH x 32 output pixels
-    (k = 1: TH * 32 consecutive pixels), `wgs` tile-walking workgroups per 32-channel slab of Cx, `chain` = the most terms one accumulator adds (an MFMA's inner
-    sum counted as 32) and `partials` = the partial sums the finalize adds per element."""
-    TH = 8 if k == 1 else 4
-    ntw = 1 if Cy <= 32 else 2 if Cy <= 64 else 4
-    slabs = -(-Cx // 32)
-    tiles = -(-(B * Ho * Wo) // (TH * 32)) if k == 1 else B * (-(-Ho // TH)) * (-(-Wo // 32))
-    n = wgs if wgs > 0 else min(tiles, 1024 // slabs)
-    return dict(TH=TH, tiles=tiles, wgs=n, slabs=slabs, chain=-(-tiles // n) * TH * 32, partials=n, ws_bytes=n * 32 * ntw * k * k * slabs * 32 * 4)
+    return _wgrad_eligible(_NARROW_LIMITS, k, stride, ups, Cx, Cy, Cout, Cin)
 
 
 def wgrad_wide_eligible(k, stride, ups, Cx, Cy, Cout, Cin) -> bool:
     """The shapes ldiff_op_conv_wgrad_wide takes (include/ldiff.h)."""
-    return (ups == 0 and ((k == 3 and stride in (1, 2)) or (k == 1 and stride == 1)) and Cx % 8 == 0 and 8 <= Cx <= 1024 and Cy % 8 == 0
-            and 8 <= Cy <= (512 if k == 3 else 2048) and 1 <= Cout <= Cy and 1 <= Cin <= Cx)
+    return _wgrad_eligible(_WIDE_LIMITS, k, stride, ups, Cx, Cy, Cout, Cin)
+
+
+def _wgrad_plan(nb, yslabs, B, Ho, Wo, Cx, k, wgs) -> dict:
+    """The plan of csrc/kernels_wgrad.hip wgrad_plan for workgroups of `nb` output channels over `yslabs` slabs of Cy: tiles of TH x 32 output pixels (k = 1:
+    TH * 32 consecutive pixels), `wgs` tile-walking workgroups per nb x 32 block of (Cy, Cx), `slabs` = the blocks, `chain` = the most terms one accumulator adds
+    (an MFMA's inner sum counted as 32) and `partials` = the partial sums the finalize adds per element."""
+    TH = 8 if k == 1 else 4
+    xslabs = -(-Cx // 32)
+    tiles = -(-(B * Ho * Wo) // (TH * 32)) if k == 1 else B * (-(-Ho // TH)) * (-(-Wo // 32))
+    n = wgs if wgs > 0 else min(tiles, max(1, 1024 // (xslabs * yslabs)))
+    return dict(TH=TH, tiles=tiles, wgs=n, slabs=xslabs * yslabs, chain=-(-tiles // n) * TH * 32, partials=n, ws_bytes=n * nb * yslabs * k * k * xslabs * 32 * 4)
+
+
+def wgrad_plan(B, Ho, Wo, Cx, Cy, k, wgs=0) -> dict:
+    """The plan ldiff_op_conv_wgrad makes for a launch, for the error bounds of the tests: the whole of Cy (padded to 32 / 64 / 128) in one workgroup."""
+    return _wgrad_plan(32 if Cy <= 32 else 64 if Cy <= 64 else 128, 1, B, Ho, Wo, Cx, k, wgs)
 
 
 def wgrad_wide_plan(B, Ho, Wo, Cx, Cy, k, wgs=0) -> dict:
-    """The plan ldiff_op_conv_wgrad_wide makes for a launch (csrc/kernels_wgrad_wide.hip ww_plan), with the keys of wgrad_plan: the same tiles, `wgs` tile-walking
-    workgroups per 64 x 32 block of (Cy, Cx), `slabs` = the blocks."""
-    TH = 8 if k == 1 else 4
-    xslabs, yslabs = -(-Cx // 32), -(-Cy // 64)
-    tiles = -(-(B * Ho * Wo) // (TH * 32)) if k == 1 else B * (-(-Ho // TH)) * (-(-Wo // 32))
-    n = wgs if wgs > 0 else min(tiles, max(1, 1024 // (xslabs * yslabs)))
-    return dict(TH=TH, tiles=tiles, wgs=n, slabs=xslabs * yslabs, chain=-(-tiles // n) * TH * 32, partials=n, ws_bytes=n * 64 * yslabs * k * k * xslabs * 32 * 4)
+    """The plan ldiff_op_conv_wgrad_wide makes for a launch, with the keys of wgrad_plan: Cy in slabs of 64."""
+    return _wgrad_plan(64, -(-Cy // 64), B, Ho, Wo, Cx, k, wgs)
+
+
+def wgrad_entry(route, M, k, stride, ups, Cx, Cy, Cout, Cin):
+    """(entry, slab_bias) of a conv's backward under `route` at M = B Ho Wo rows, by the comment at the head of this section: entry = "narrow"
+    (ldiff_op_conv_wgrad), "wide" (ldiff_op_conv_wgrad_wide) or "staged"; slab_bias = the route asks for ldiff_op_colsum_slabs (its own limits on Cy are the launch's)."""
+    direct = route in ("direct", "wide") or (route in ("auto", "auto-wide") and M >= WGRAD_DIRECT_MIN_ROWS)
+    wide = route == "wide" or (route == "auto-wide" and M >= WGRAD_WIDE_MIN_ROWS)
+    narrow_ok = wgrad_direct_eligible(k, stride, ups, Cx, Cy, Cout, Cin)
+    if direct and narrow_ok:
+        entry = "narrow"
+    elif wide and not narrow_ok and wgrad_wide_eligible(k, stride, ups, Cx, Cy, Cout, Cin):
+        entry = "wide"
+    else:
+        entry = "staged"
+    return entry, direct or route == "auto-wide"
 
 
 def colsum_slabs_plan(M, N) -> dict:
@@ -283,32 +305,27 @@ def colsum_slabs_plan(M, N) -> dict:
     return dict(slabs=slabs, rows=rows, row_lanes=rp, chain=-(-rows // rp) + rp, partials=slabs, ws_bytes=slabs * N * 4)
 
 
-def conv_wgrad_direct(x, dy, Cout, Cin, k, stride, wgs=0):
-    """ldiff_op_conv_wgrad: x [B,H,W,Cx], dy [B,Ho,Wo,Cy] NHWC float16 -> dw float32 [Cout, Cin, k, k]."""
+def _conv_wgrad(entry, x, dy, Cout, Cin, k, stride, wgs):
     _check_act(x, "x")
     _check_act(dy, "dy")
     lib = _lib.load()
     B, H, W, Cx = x.shape
     _, Ho, Wo, Cy = dy.shape
     dw = torch.empty((Cout, Cin, k, k), dtype=torch.float32, device=x.device)
-    nb = lib.ldiff_op_conv_wgrad_ws_bytes(B, Ho, Wo, Cx, Cy, k, int(wgs))
+    nb = getattr(lib, entry + "_ws_bytes")(B, Ho, Wo, Cx, Cy, k, int(wgs))
     ws = _workspace(nb, x.device)
-    _lib.check(lib.ldiff_op_conv_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, Cx, Ho, Wo, Cy, Cout, Cin, k, stride, int(wgs), ws.data_ptr(), nb, _sp()))
+    _lib.check(getattr(lib, entry)(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, Cx, Ho, Wo, Cy, Cout, Cin, k, stride, int(wgs), ws.data_ptr(), nb, _sp()))
     return dw
+
+
+def conv_wgrad_direct(x, dy, Cout, Cin, k, stride, wgs=0):
+    """ldiff_op_conv_wgrad: x [B,H,W,Cx], dy [B,Ho,Wo,Cy] NHWC float16 -> dw float32 [Cout, Cin, k, k]."""
+    return _conv_wgrad("ldiff_op_conv_wgrad", x, dy, Cout, Cin, k, stride, wgs)
 
 
 def conv_wgrad_wide(x, dy, Cout, Cin, k, stride, wgs=0):
     """ldiff_op_conv_wgrad_wide: x [B,H,W,Cx], dy [B,Ho,Wo,Cy] NHWC float16 -> dw float32 [Cout, Cin, k, k]."""
-    _check_act(x, "x")
-    _check_act(dy, "dy")
-    lib = _lib.load()
-    B, H, W, Cx = x.shape
-    _, Ho, Wo, Cy = dy.shape
-    dw = torch.empty((Cout, Cin, k, k), dtype=torch.float32, device=x.device)
-    nb = lib.ldiff_op_conv_wgrad_wide_ws_bytes(B, Ho, Wo, Cx, Cy, k, int(wgs))
-    ws = _workspace(nb, x.device)
-    _lib.check(lib.ldiff_op_conv_wgrad_wide(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, Cx, Ho, Wo, Cy, Cout, Cin, k, stride, int(wgs), ws.data_ptr(), nb, _sp()))
-    return dw
+    return _conv_wgrad("ldiff_op_conv_wgrad_wide", x, dy, Cout, Cin, k, stride, wgs)
 
 
 def colsum_slabs(dy, N=None):
@@ -351,10 +368,7 @@ class Conv2dFn(torch.autograd.Function):
         _, Ho, Wo, Cy = dy.shape
         w4 = weight if weight.dim() == 4 else weight[:, :, None, None]
         dx = dw = db = None
-        route, M = ctx.wgrad_route, B * Ho * Wo
-        direct = route in ("direct", "wide") or (route in ("auto", "auto-wide") and M >= WGRAD_DIRECT_MIN_ROWS)   # ldiff_op_conv_wgrad where it is eligible
-        wide = route == "wide" or (route == "auto-wide" and M >= WGRAD_WIDE_MIN_ROWS)
-        slab_bias = direct or route == "auto-wide"
+        entry, slab_bias = wgrad_entry(ctx.wgrad_route, B * Ho * Wo, k, stride, ups, Cx, Cy, Cout, Cin)
         if ctx.needs_input_grad[0]:
             # dgrad: conv (stride 1) of dy -- zero-inserted for a stride-2 forward -- with the weights [Cin][k][k][Cout], taps flipped
             wd = pack_weight(w4, dgrad=True, cols=Cy)
@@ -365,10 +379,8 @@ class Conv2dFn(torch.autograd.Function):
                 g[:, ::2, ::2] = dy
             dxu = _conv_call(g, wd, Cx, k, 1, 0)
             dx = dxu if ups == 0 else dxu.view(B, H, 2, W, 2, Cx).float().sum((2, 4)).to(torch.float16)
-        if ctx.needs_input_grad[1] and direct and wgrad_direct_eligible(k, stride, ups, Cx, Cy, Cout, Cin):
-            dw = conv_wgrad_direct(x, dy, Cout, Cin, k, stride).view(weight.shape)
-        elif ctx.needs_input_grad[1] and wide and not wgrad_direct_eligible(k, stride, ups, Cx, Cy, Cout, Cin) and wgrad_wide_eligible(k, stride, ups, Cx, Cy, Cout, Cin):
-            dw = conv_wgrad_wide(x, dy, Cout, Cin, k, stride).view(weight.shape)
+        if ctx.needs_input_grad[1] and entry != "staged":
+            dw = (conv_wgrad_direct if entry == "narrow" else conv_wgrad_wide)(x, dy, Cout, Cin, k, stride).view(weight.shape)
         elif ctx.needs_input_grad[1]:
             # wgrad: dW[n][tap*Cx + c] = sum_m dy[m, n] * xcol[m, tap*Cx + c]  as a GEMM over K = M
             M = B * Ho * Wo

@@ -1227,7 +1227,7 @@ int ldiff_op_sgd_nesterov_multi(const void* tensors, const void* grads, const vo
                             (const float*)inv_scale, (const float*)clip_coef, (hipStream_t)stream);
   API_END
 }
-// ---- direct weight / bias gradients of the tissue head's narrow convs (kernels_wgrad.hip) ----
+// ---- direct weight / bias gradients of the tissue head's convs (kernels_wgrad.hip) ----
 int64_t ldiff_op_conv_wgrad_ws_bytes(int B, int Ho, int Wo, int Cx, int Cy, int k, int wgs) { return conv_wgrad_ws_bytes(B, Ho, Wo, Cx, Cy, k, wgs); }
 int ldiff_op_conv_wgrad(const void* x, const void* dy, void* dw_f32, int B, int H, int W, int Cx, int Ho, int Wo, int Cy, int Cout, int Cin, int k, int stride, int wgs,
                         void* ws, int64_t ws_bytes, void* stream) {
@@ -1239,7 +1239,7 @@ int ldiff_op_conv_wgrad(const void* x, const void* dy, void* dw_f32, int B, int 
   launch_conv_wgrad((const f16*)x, (const f16*)dy, (float*)dw_f32, B, H, W, Cx, Ho, Wo, Cy, Cout, Cin, k, stride, wgs, (float*)ws, ws_bytes, (hipStream_t)stream);
   API_END
 }
-// the wide convs: both channel counts blocked (kernels_wgrad_wide.hip)
+// the wide convs: both channel counts blocked (the same kernel of kernels_wgrad.hip under the wide entry's limits and plan)
 int64_t ldiff_op_conv_wgrad_wide_ws_bytes(int B, int Ho, int Wo, int Cx, int Cy, int k, int wgs) { return conv_wgrad_wide_ws_bytes(B, Ho, Wo, Cx, Cy, k, wgs); }
 int ldiff_op_conv_wgrad_wide(const void* x, const void* dy, void* dw_f32, int B, int H, int W, int Cx, int Ho, int Wo, int Cy, int Cout, int Cin, int k, int stride,
                              int wgs, void* ws, int64_t ws_bytes, void* stream) {

@@ -402,12 +402,11 @@ void launch_sumsq(const float* x, long long n, float* out, float* ws, long long 
 struct SgdTensor { float* p; float* buf; long long n; };
 void launch_sgd_nesterov_multi(const SgdTensor* tensors, const float* const* grads, const AdamChunk* chunks, long long nchunks, float lr, float momentum, float wd,
                                int first, const float* inv_scale, const float* clip_coef, hipStream_t s);
-// direct weight gradient of the narrow convs and slab-reduced bias gradient (kernels_wgrad.hip): per-workgroup partials in the caller's workspace, fixed-order finalize
+// direct weight gradient and slab-reduced bias gradient (kernels_wgrad.hip): per-workgroup partials in the caller's workspace, fixed-order finalize.  One kernel, two
+// entries: the narrow one keeps the whole of Cy in a workgroup (Cx up to 128, Cy up to 64 (k = 3) / 128 (k = 1)), the wide one blocks Cy by 64 (Cx up to 1024, Cy up to 512 / 2048)
 long long conv_wgrad_ws_bytes(int B, int Ho, int Wo, int Cx, int Cy, int k, int wgs);   // 0: a shape the kernel does not take
 void launch_conv_wgrad(const f16* x, const f16* dy, float* dw, int B, int H, int W, int Cx, int Ho, int Wo, int Cy, int Cout, int Cin, int k, int stride, int wgs,
                        float* ws, long long ws_bytes, hipStream_t s);
-void launch_wgrad_finalize(const float* ws, float* dw, int wgs, int CYP, int taps, int CXP, int Cout, int Cin, hipStream_t s);   // dw[n][c][tap] = sum over wg of ws[wg][n][tap][c]
-// the same contraction blocked over the channels on both sides (kernels_wgrad_wide.hip): Cx up to 1024, Cy up to 512 (k = 3) / 2048 (k = 1)
 long long conv_wgrad_wide_ws_bytes(int B, int Ho, int Wo, int Cx, int Cy, int k, int wgs);   // 0: a shape the kernel does not take
 void launch_conv_wgrad_wide(const f16* x, const f16* dy, float* dw, int B, int H, int W, int Cx, int Ho, int Wo, int Cy, int Cout, int Cin, int k, int stride, int wgs,
                             float* ws, long long ws_bytes, hipStream_t s);

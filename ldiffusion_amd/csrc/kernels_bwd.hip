@@ -7,9 +7,9 @@
 //   dgrad  dx = conv(dy, flip/transpose(W))                       -> ldiff_op_conv on rearranged weights (python side, a layout cast)
 //   wgrad  dW[n][tap*C + c] = sum_m dy[m, n] * xcol[m, tap*C + c]  -> ldiff_op_conv as a plain GEMM over K = M on the two transposed
 //                                                                    operands this file produces (im2col_t, transpose_rows)
-// (the "staged" route of autograd.Conv2dFn, its default).  At the opposite corner -- the nnU-Net tissue head's narrow convs over millions of pixels -- the staged
-// wgrad and colsum_kernel below are the wrong tools (one workgroup per 64 columns walks every row); kernels_wgrad.hip holds the direct weight gradient and the
-// slab-reduced column sum that autograd.wgrad_route("direct" / "auto") selects there.  colsum_kernel and the staging kernels stay as they are for this step.
+// (the "staged" route of autograd.Conv2dFn, its default).  At the opposite corner -- the nnU-Net tissue head's convs over tens of thousands to millions of pixels -- the staged
+// wgrad and colsum_kernel below are the wrong tools (one workgroup per 64 columns walks every row); kernels_wgrad.hip holds the direct weight gradient (one kernel,
+// a narrow and a wide entry) and the slab-reduced column sum that autograd.wgrad_route("direct" / "auto" / "wide" / "auto-wide") selects there.  colsum_kernel and the staging kernels stay as they are for this step.
 // This file adds what has no forward counterpart: the transposed im2col / transpose staging, bias-gradient column sums,
 // GroupNorm(+SiLU) and LayerNorm forward-with-statistics / backward, GEGLU backward, attention backward for short sequences, AdamW.
 // Activations and their gradients are NHWC fp16, reductions and parameter gradients fp32.

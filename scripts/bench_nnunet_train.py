@@ -34,8 +34,7 @@ from ldiffusion_amd import nnunet, nnunet_train  # noqa: E402
 FAMILIES = [("InstanceNorm + LeakyReLU (in_train)", ("in_partial", "in_apply", "in_fwd_finalize", "in_bwd_finalize")),
             ("Dice + cross-entropy (dice_ce)", ("dce_",)),
             ("SGD (sgd_nesterov_multi)", ("sgd_nesterov",)),
-            ("wide direct weight gradient (wgrad_wide; its finalize is in the next row)", ("wgrad_wide",)),
-            ("direct weight gradient (wgrad_direct + finalize)", ("wgrad_direct", "wgrad_finalize")),
+            ("direct weight gradient, narrow and wide entry (wgrad_direct + finalize)", ("wgrad_direct", "wgrad_finalize")),
             ("wgrad staging: im2col_t", ("im2col_t",)),
             ("wgrad staging: transpose of dy", ("transpose_rows",)),
             ("bias gradient: column sums of dy (colsum)", ("colsum",)),

@@ -89,7 +89,7 @@ def main():
     g = torch.Generator().manual_seed(0)
     w = (0.05 * torch.randn((Cc, Cc, 3, 3), generator=g)).to(dev).requires_grad_(True)
     b = torch.zeros(Cc, device=dev).requires_grad_(True)
-    print(f"3 x 3 conv {Cc} -> {Cc}, B = {B}: weight + bias gradient, device time per backward (median of {a.passes}, the routes alternating)")
+    print(f"3 x 3 conv {Cc} -> {Cc}, B = {B}: weight + bias gradient, device time per backward (median [min .. max] of {a.passes}, the routes alternating)")
     for size in (int(s) for s in a.sizes.split(",")):
         x = torch.randn((B, size, size, Cc), generator=g).to(torch.float16).to(dev)
         dy = (0.1 * torch.randn((B, size, size, Cc), generator=g)).to(torch.float16).to(dev)
@@ -108,7 +108,8 @@ def main():
                 if i >= 3:
                     times[route].append(e0.elapsed_time(e1) * 1e3)
         s, d = statistics.median(times["staged"]), statistics.median(times["direct"])
-        print(f"  M = {B * size * size:>8} ({B} x {size}^2): staged {s:10.1f} us   direct {d:10.1f} us   staged / direct = {s / d:6.2f}")
+        band = {r: f"[{min(t):9.1f} .. {max(t):9.1f}]" for r, t in times.items()}
+        print(f"  M = {B * size * size:>8} ({B} x {size}^2): staged {s:10.1f} {band['staged']} us   direct {d:10.1f} {band['direct']} us   staged / direct = {s / d:6.2f}", flush=True)
 
 
 if __name__ == "__main__":

@@ -1,5 +1,6 @@
-"""No GPU: the route names "wide" / "auto-wide", the eligibility and plan statements of the wide direct weight gradient in autograd.py against the library's
-own (ldiff_op_conv_wgrad_wide_ws_bytes is host code: the library loads without a device), and the workspace maximum include/ldiff.h states."""
+"""No GPU: the route names "wide" / "auto-wide", the route decision (autograd.wgrad_entry) against a table written out by hand, the eligibility and plan
+statements of the wide direct weight gradient in autograd.py against the library's own (ldiff_op_conv_wgrad_wide_ws_bytes is host code: the library loads
+without a device), and the workspace maximum include/ldiff.h states."""
 import os
 import re
 
@@ -54,6 +55,38 @@ def test_wide_eligibility_at_the_limits():
     assert not ok(3, 1, 0, 32, 32, 33, 32) and not ok(3, 1, 0, 32, 32, 32, 33) and not ok(3, 1, 0, 32, 32, 0, 32) and not ok(3, 1, 0, 32, 32, 32, 0)
     # the narrow entry's limits did not move
     assert ag.wgrad_direct_eligible(3, 1, 0, 128, 64, 64, 128) and not ag.wgrad_direct_eligible(3, 1, 0, 136, 64, 64, 136) and not ag.wgrad_direct_eligible(3, 1, 0, 128, 72, 72, 128)
+
+
+# (k, stride, ups, Cx, Cy, Cout, Cin): one the narrow entry takes, one only the wide entry takes, one neither takes (the conv upsamples its input)
+NARROW_LAUNCH, WIDE_LAUNCH, UPS_LAUNCH = (3, 1, 0, 32, 32, 32, 32), (3, 2, 0, 128, 256, 256, 128), (3, 1, 1, 32, 32, 32, 32)
+# Written out from the route comment of autograd.py ("which kernels form a conv's weight and bias gradient"), not computed:
+# (route, M) -> ((entry of the narrow launch, of the wide launch, of the upsampling launch), slab_bias).  16384 = both *_MIN_ROWS constants.
+ROUTE_TABLE = {
+    ("staged", 8192): (("staged", "staged", "staged"), False),       # "staged": nothing moves, at any M
+    ("staged", 16384): (("staged", "staged", "staged"), False),
+    ("direct", 8192): (("narrow", "staged", "staged"), True),        # "direct": the narrow entry wherever eligible, every bias gradient on the slab sum, at any M
+    ("direct", 16384): (("narrow", "staged", "staged"), True),
+    ("auto", 8192): (("staged", "staged", "staged"), False),         # "auto": "staged" below WGRAD_DIRECT_MIN_ROWS,
+    ("auto", 16384): (("narrow", "staged", "staged"), True),         #         "direct" from it on
+    ("wide", 8192): (("narrow", "wide", "staged"), True),            # "wide": a direct kernel wherever one takes the shape, the narrow entry first, at any M
+    ("wide", 16384): (("narrow", "wide", "staged"), True),
+    ("auto-wide", 8192): (("staged", "staged", "staged"), True),     # "auto-wide": every bias gradient on the slab sum whatever M; weights staged below the thresholds,
+    ("auto-wide", 16384): (("narrow", "wide", "staged"), True),      #              the narrow entry's launches follow "auto", the wide-only ones go to the wide entry
+}
+
+
+def test_wgrad_entry_against_the_route_comment():
+    assert ag.WGRAD_DIRECT_MIN_ROWS == ag.WGRAD_WIDE_MIN_ROWS == 16384, "the table's two M straddle these"
+    assert {r for r, _ in ROUTE_TABLE} == set(ag.WGRAD_ROUTES) and len(ROUTE_TABLE) == 2 * len(ag.WGRAD_ROUTES)
+    for (route, M), (entries, slab_bias) in ROUTE_TABLE.items():
+        for launch, entry in zip((NARROW_LAUNCH, WIDE_LAUNCH, UPS_LAUNCH), entries):
+            assert ag.wgrad_entry(route, M, *launch) == (entry, slab_bias), (route, M, launch)
+    # a 1 x 1 conv with 2056 output columns: past every direct entry and past the slab column sum's own limit (2048).  slab_bias states what the ROUTE asks
+    # for, so it stays True: the launch, not the route decision, tests Cy and falls back to ldiff_op_colsum.
+    for route, slab_bias in (("staged", False), ("direct", True), ("wide", True), ("auto-wide", True)):
+        assert ag.wgrad_entry(route, 16384, 1, 1, 0, 32, 2056, 2056, 32) == ("staged", slab_bias), route
+    # M one below the threshold stays staged
+    assert ag.wgrad_entry("auto", 16383, *NARROW_LAUNCH) == ("staged", False) and ag.wgrad_entry("auto-wide", 16383, *WIDE_LAUNCH) == ("staged", True)
 
 
 CHANNELS = [(136, 32, 3), (32, 72, 3), (128, 128, 3), (64, 136, 3), (256, 128, 3), (512, 256, 3), (1024, 512, 3), (128, 512, 1), (512, 2048, 1), (256, 8, 1), (8, 8, 3),

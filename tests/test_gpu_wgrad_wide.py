@@ -1,6 +1,7 @@
-"""GPU (-m gpu): the wide direct weight gradient (csrc/kernels_wgrad_wide.hip; ldiff_op_conv_wgrad_wide) and the routes "wide" / "auto-wide" of
+"""GPU (-m gpu): the wide entry of the direct weight gradient (csrc/kernels_wgrad.hip; ldiff_op_conv_wgrad_wide) and the routes "wide" / "auto-wide" of
 autograd.Conv2dFn -- exact on integer data over every channel case, map, stride and workgroup count, within the derived bound of tests/wgrad_bound.py on
-random data, refusals, and one backward pass of the tissue-head trainer graded as tests/test_gpu_wgrad_direct.py grades the direct route."""
+random data, the same bits as the narrow entry where both take a launch, refusals, and one backward pass of the tissue-head trainer graded as
+tests/test_gpu_wgrad_direct.py grades the direct route."""
 import json
 import os
 
@@ -84,6 +85,33 @@ def test_wide_against_float64(lib, Cin, Cout):
     assert (np.abs(got - want) <= tol).all()
 
 
+# ---- 2b. the two entries agree bit for bit ----------------------------------------------------------------------------------------------------------
+BOTH_CHANNELS = [(32, 32, 3, 1), (128, 64, 3, 2), (64, 128, 1, 1)]   # (Cx, Cy, k, stride): launches both entries accept; the output block is 32 / 64 / 128 against 64 (twice)
+
+
+@pytest.mark.parametrize("shape", MAPS[:2], ids=lambda m: "x".join(map(str, m[:3])))
+@pytest.mark.parametrize("chan", BOTH_CHANNELS, ids=lambda c: "-".join(map(str, c)))
+def test_both_entries_return_the_same_bits(lib, chan, shape):
+    """One kernel behind two entries: at the same stated wgs the tile walk is the same, so every element of dw adds the same terms in the same order whichever
+    width of output-channel block holds it -- random fp16 operands of order 1, wgs = 3 and 1.  The planned grids are equal too (and then the bits at wgs = 0)
+    except at 1 x 1 with Cy = 128, where the wide entry's two slabs of Cy halve its planned grid."""
+    Cx, Cy, k, stride = chan
+    B, H, W, _ = shape
+    rng = np.random.default_rng(1000 + Cx + Cy + W)
+    p = k // 2
+    Ho, Wo = (H + 2 * p - k) // stride + 1, (W + 2 * p - k) // stride + 1
+    x = rng.standard_normal((B, H, W, Cx)).astype(np.float16)
+    dy = rng.standard_normal((B, Ho, Wo, Cy)).astype(np.float16)
+    assert ag.wgrad_direct_eligible(k, stride, 0, Cx, Cy, Cy, Cx) and ag.wgrad_wide_eligible(k, stride, 0, Cx, Cy, Cy, Cx)
+    same_plan = (k, Cy) != (1, 128)
+    if same_plan:
+        assert ag.wgrad_plan(B, Ho, Wo, Cx, Cy, k, 0)["wgs"] == ag.wgrad_wide_plan(B, Ho, Wo, Cx, Cy, k, 0)["wgs"]
+    for wgs in (3, 1) + ((0,) if same_plan else ()):
+        narrow, wide = td.run_wgrad(lib, x, dy, Cy, Cx, k, stride, wgs), run_wide(lib, x, dy, Cy, Cx, k, stride, wgs)
+        assert narrow.isfinite().all() and narrow.abs().max() > 0
+        assert torch.equal(narrow, wide), f"wgs={wgs}: {(narrow != wide).sum().item()} of {narrow.numel()} elements differ, by at most {(narrow - wide).abs().max():.3e}"
+
+
 # ---- 3. refusals ------------------------------------------------------------------------------------------------------------------------------------
 def test_wide_refusals_name_the_argument(lib):
     t = torch.zeros(8 * 8 * 2056, dtype=torch.float16, device=DEV)
@@ -143,9 +171,8 @@ def _entry_of(name, shape):
     else:
         k, Cin, Cout = shape[2], shape[1], shape[0]
     Cx, Cy = -(-Cin // 8) * 8, -(-Cout // 8) * 8
-    if ag.wgrad_direct_eligible(k, 1, 0, Cx, Cy, Cout, Cin):
-        return "narrow"
-    return "wide" if ag.wgrad_wide_eligible(k, 1, 0, Cx, Cy, Cout, Cin) else None
+    entry, _ = ag.wgrad_entry("wide", 0, k, 1, 0, Cx, Cy, Cout, Cin)   # "wide": a direct entry wherever one takes the shape, whatever M
+    return None if entry == "staged" else entry
 
 
 def test_trainer_backward_on_the_wide_route():
