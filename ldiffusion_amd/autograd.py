@@ -20,10 +20,9 @@ import ctypes as C
 import torch
 
 from . import _lib
+from .optim import ADAMW_CHUNK, SUMSQ_CHAIN, adamw_step, bucket_pack, sgd_nesterov_step, sumsq, sumsq_plan  # noqa: F401  (the step tail: optim.py)
 
-
-def _sp():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+_sp = _lib.stream_ptr
 
 
 def _r(x, m):
@@ -595,53 +594,6 @@ class InfoNceFn(torch.autograd.Function):
         return g * df, None, None, None, None, None, None
 
 
-ADAMW_CHUNK = 16384   # elements per workgroup of ldiff_op_adamw_multi (csrc/common.h)
-
-
-def adamw_step(params, grads, state, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01):
-    """One AdamW update (torch.optim.AdamW semantics; the reference's DeepSpeed config, ldiffusion.py:168-171) of float32 CUDA
-    parameters, in place, ALL tensors in one launch (ldiff_op_adamw_multi).  `state` is a dict the caller keeps: the step count, the two
-    moment buffers per parameter and the device tables of the launch (parameter / moment pointers and the chunk list are built once;
-    only the gradient pointers change from step to step).  As in torch, a tensor whose gradient is None is skipped and its own step count
-    (the bias correction) does not advance; tensors whose counts differ are updated by one launch per count."""
-    lib = _lib.load()
-    live = [(i, p, g) for i, (p, g) in enumerate(zip(params, grads)) if g is not None]
-    if not live:
-        return   # nothing to update: the bias-correction step count must not advance either
-    state["step"] = state.get("step", 0) + 1
-    steps = state.setdefault("_steps", {})   # per-tensor step counts
-    dev = live[0][1].device
-    for i, p, g in live:
-        if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
-            raise ValueError("adamw_step: parameters must be contiguous float32 CUDA tensors")
-        if i not in state:
-            state[i] = (torch.zeros_like(p), torch.zeros_like(p))
-    groups = {}
-    for e in live:
-        steps[e[0]] = steps.get(e[0], 0) + 1
-        groups.setdefault(steps[e[0]], []).append(e)
-    old, tabs, keep = state.get("_tables") or [], [], []
-    for step, members in sorted(groups.items()):
-        key = tuple((i, p.data_ptr(), p.numel()) for i, p, _ in members)
-        tab = next((t for t in old if t[0] == key), None)
-        if tab is None:
-            tensors, chunks = [], []
-            for t, (i, p, _) in enumerate(members):
-                m, v = state[i]
-                tensors += [p.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()]
-                for first in range(0, p.numel(), ADAMW_CHUNK):
-                    chunks += [t, first]        # {int32 tensor, int32 pad} packed into one int64 (little endian), then int64 first
-            tab = (key, torch.tensor(tensors, dtype=torch.int64).to(dev), torch.tensor(chunks, dtype=torch.int64).to(dev), len(chunks) // 2)
-        tabs.append(tab)
-        gs = [g.detach().to(torch.float32).contiguous() for _, _, g in members]
-        gptr = torch.tensor([g.data_ptr() for g in gs], dtype=torch.int64).to(dev)
-        _lib.check(lib.ldiff_op_adamw_multi(tab[1].data_ptr(), gptr.data_ptr(), tab[2].data_ptr(), tab[3], float(lr), float(betas[0]), float(betas[1]),
-                                            float(eps), float(weight_decay), int(step), _sp()))
-        keep.append((gs, gptr))
-    state["_tables"] = tabs
-    state["_keep"] = keep   # the launches are asynchronous: the pointer tables and converted gradients must outlive them
-
-
 # ---- training form of the nnU-Net tissue head (csrc/kernels_segtrain.hip; ldiffusion_amd/nnunet_train.py) ----
 def _workspace(nbytes, device):
     return torch.empty(max(int(nbytes), 16) // 8 + 1, dtype=torch.float64, device=device)   # 8-byte elements: the loss kernels keep double sums in it
@@ -683,27 +635,33 @@ class InstanceNormLReLUFn(torch.autograd.Function):
         return dx, dg, db, None, None
 
 
-def dice_ce(logits, target, n_heads, batch_dice, weight=1.0, grad_scale=1.0, smooth=1e-5):
-    """ldiff_op_dice_ce on float16 logits [B, H, W, roundup(n_heads, 8)] and uint8 / int64 labels [B, H, W] (or [B, 1, H, W]):
-    (loss float32 0-dim, dlogits float16 = grad_scale * weight * d loss / d logits in the logits' layout).  Region labels and an ignore label are not
-    covered (nnunet.network_spec refuses them)."""
+def _dice_ce_args(logits, target, what):
     _check_act(logits, "logits")
-    lib = _lib.load()
     if target.dim() == 4 and target.shape[1] == 1:
         target = target[:, 0]
     B, H, W, ld = logits.shape
     if tuple(target.shape) != (B, H, W):
-        raise ValueError(f"dice_ce: target {tuple(target.shape)} does not match logits {tuple(logits.shape)}")
-    if target.dtype not in (torch.uint8, torch.int64):
-        if target.is_floating_point():   # the nnU-Net loader hands float label maps (RobustCrossEntropyLoss casts them with .long())
-            target = target.long()
-        else:
-            target = target.to(torch.int64)
-    target = target.to(logits.device).contiguous()
+        raise ValueError(f"{what}: target {tuple(target.shape)} does not match logits {tuple(logits.shape)}")
+    if target.dtype not in (torch.uint8, torch.int64):   # the nnU-Net loader hands float label maps (RobustCrossEntropyLoss casts them with .long())
+        target = target.long() if target.is_floating_point() else target.to(torch.int64)
+    return target.to(logits.device).contiguous(), B, H, W, ld
+
+
+def _dice_ce_ws(lib, B, HW, n_heads, device):
+    """(workspace, its byte count) of the three Dice + CE entries"""
+    nb = lib.ldiff_op_dice_ce_ws_bytes(B, HW, int(n_heads))
+    return _workspace(nb, device), nb
+
+
+def dice_ce(logits, target, n_heads, batch_dice, weight=1.0, grad_scale=1.0, smooth=1e-5):
+    """ldiff_op_dice_ce on float16 logits [B, H, W, roundup(n_heads, 8)] and uint8 / int64 labels [B, H, W] (or [B, 1, H, W]):
+    (loss float32 0-dim, dlogits float16 = grad_scale * weight * d loss / d logits in the logits' layout).  Region labels and an ignore label are not
+    covered (nnunet.network_spec refuses them)."""
+    target, B, H, W, ld = _dice_ce_args(logits, target, "dice_ce")
+    lib = _lib.load()
     loss = torch.empty(1, dtype=torch.float32, device=logits.device)
     dlogits = torch.empty_like(logits)
-    nb = lib.ldiff_op_dice_ce_ws_bytes(B, H * W, int(n_heads))
-    ws = _workspace(nb, logits.device)
+    ws, nb = _dice_ce_ws(lib, B, H * W, n_heads, logits.device)
     _lib.check(lib.ldiff_op_dice_ce(logits.data_ptr(), ld, int(n_heads), target.data_ptr(), int(target.dtype == torch.int64), B, H * W, int(bool(batch_dice)),
                                     float(smooth), float(weight), float(grad_scale), loss.data_ptr(), dlogits.data_ptr(), ws.data_ptr(), nb, _sp()))
     return loss[0], dlogits
@@ -728,18 +686,6 @@ class DiceCeFn(torch.autograd.Function):
         return (dlogits.float() * g).to(dlogits.dtype), None, None, None, None, None, None
 
 
-def _dice_ce_args(logits, target, what):
-    _check_act(logits, "logits")
-    if target.dim() == 4 and target.shape[1] == 1:
-        target = target[:, 0]
-    B, H, W, ld = logits.shape
-    if tuple(target.shape) != (B, H, W):
-        raise ValueError(f"{what}: target {tuple(target.shape)} does not match logits {tuple(logits.shape)}")
-    if target.dtype not in (torch.uint8, torch.int64):
-        target = target.long() if target.is_floating_point() else target.to(torch.int64)
-    return target.to(logits.device).contiguous(), B, H, W, ld
-
-
 def dice_ce_nacc(n_heads):
     """Doubles per row of the loss statistics: sum_pred, intersect, sum_gt per padded class, the cross-entropy sum, the count of labels outside [0, n_heads)."""
     return 3 * 8 * ((int(n_heads) + 7) // 8) + 2
@@ -755,8 +701,7 @@ def dice_ce_stats(logits, target, n_heads, batch_dice, out=None):
         out = torch.empty((rows, nacc), dtype=torch.float64, device=logits.device)
     elif not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == rows * nacc):
         raise ValueError(f"dice_ce_stats: out must be a contiguous float64 CUDA tensor of {rows * nacc} elements")
-    nb = lib.ldiff_op_dice_ce_ws_bytes(B, H * W, int(n_heads))
-    ws = _workspace(nb, logits.device)
+    ws, nb = _dice_ce_ws(lib, B, H * W, n_heads, logits.device)
     _lib.check(lib.ldiff_op_dice_ce_stats(logits.data_ptr(), ld, int(n_heads), target.data_ptr(), int(target.dtype == torch.int64), B, H * W,
                                           int(bool(batch_dice)), out.data_ptr(), ws.data_ptr(), nb, _sp()))
     return out
@@ -775,8 +720,7 @@ def dice_ce_from_sums(logits, target, n_heads, batch_dice, dice_sums, local_sums
         raise ValueError("dice_ce_from_sums: without batch_dice the Dice term is per sample and stays local (world = 1, dice_sums is local_sums)")
     loss = torch.empty(1, dtype=torch.float32, device=logits.device)
     dlogits = torch.empty_like(logits)
-    nb = lib.ldiff_op_dice_ce_ws_bytes(B, H * W, int(n_heads))
-    ws = _workspace(nb, logits.device)
+    ws, nb = _dice_ce_ws(lib, B, H * W, n_heads, logits.device)
     _lib.check(lib.ldiff_op_dice_ce_from_sums(logits.data_ptr(), ld, int(n_heads), target.data_ptr(), int(target.dtype == torch.int64), B, H * W,
                                               int(bool(batch_dice)), float(smooth), float(weight), float(grad_scale), dice_sums.data_ptr(), local_sums.data_ptr(),
                                               int(world), loss.data_ptr(), dlogits.data_ptr(), ws.data_ptr(), nb, _sp()))
@@ -797,112 +741,3 @@ class DiceCeSumsFn(torch.autograd.Function):
     def backward(ctx, g):
         (dlogits,) = ctx.saved_tensors
         return (dlogits.float() * g).to(dlogits.dtype), None, None, None, None, None, None, None, None, None
-
-
-SUMSQ_CHAIN = 27   # dependent fp32 roundings on the longest path into one partial of ldiff_op_sumsq (csrc/kernels_segtrain.hip: 16 + 1 + 2 + 6 + 2)
-
-
-def sumsq_plan(n):
-    """(chain, partials) of ldiff_op_sumsq on n elements: fp32 roundings per partial, and the most partials the double finalize adds."""
-    return SUMSQ_CHAIN, max(1, (((int(n) + 3) // 4) + ADAMW_CHUNK // 4 - 1) // (ADAMW_CHUNK // 4))
-
-
-def sumsq(x, out=None):
-    """ldiff_op_sumsq: sqrt(sum x^2) of a contiguous float32 CUDA tensor as a float32 device scalar [1] (no read-back here)."""
-    lib = _lib.load()
-    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() >= 1):
-        raise ValueError("sumsq: a non-empty contiguous float32 CUDA tensor is expected")
-    out = out if out is not None else torch.empty(1, dtype=torch.float32, device=x.device)
-    nb = lib.ldiff_op_sumsq_ws_bytes(x.numel())
-    ws = torch.empty(nb // 4, dtype=torch.float32, device=x.device)
-    _lib.check(lib.ldiff_op_sumsq(x.data_ptr(), x.numel(), out.data_ptr(), ws.data_ptr(), nb, _sp()))
-    return out
-
-
-def bucket_pack(grads, state=None, out=None):
-    """ldiff_op_bucket_pack: the float32 CUDA gradients that are not None, flattened in order into one buffer in ONE launch (torch.cat's result).
-    `state`: a dict the caller keeps; the offset and chunk tables are built once per set of sizes.  Returns (bucket, offsets): offsets[j] is the start of
-    the j-th live gradient, offsets[-1] the length."""
-    lib = _lib.load()
-    live = [g for g in grads if g is not None]
-    if not live:
-        raise ValueError("bucket_pack: no gradient")
-    dev = live[0].device
-    gs = []
-    for g in live:
-        if not (g.is_cuda and g.dtype == torch.float32):
-            raise ValueError("bucket_pack: gradients must be float32 CUDA tensors")
-        gs.append(g.detach().contiguous())
-    state = state if state is not None else {}
-    key = tuple(g.numel() for g in gs)
-    tab = state.get("_pack")
-    if tab is None or tab[0] != key:
-        offsets, chunks = [0], []
-        for t, n in enumerate(key):
-            offsets.append(offsets[-1] + n)
-            for at in range(0, n, ADAMW_CHUNK):
-                chunks += [t, at]
-        tab = (key, offsets, torch.tensor(offsets, dtype=torch.int64).to(dev), torch.tensor(chunks, dtype=torch.int64).to(dev), len(chunks) // 2)
-        state["_pack"] = tab
-    _, offsets, off_d, chunks_d, nchunks = tab
-    if out is None:
-        out = torch.empty(offsets[-1], dtype=torch.float32, device=dev)
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == offsets[-1]):
-        raise ValueError(f"bucket_pack: out must be a contiguous float32 CUDA tensor of {offsets[-1]} elements")
-    gptr = torch.tensor([g.data_ptr() for g in gs], dtype=torch.int64).to(dev)
-    _lib.check(lib.ldiff_op_bucket_pack(gptr.data_ptr(), off_d.data_ptr(), chunks_d.data_ptr(), nchunks, out.data_ptr(), _sp()))
-    state["_pack_keep"] = (gs, gptr)   # the launch is asynchronous
-    return out, offsets
-
-
-def sgd_nesterov_step(params, grads, state, lr, weight_decay=0.0, momentum=0.99, inv_scale=1.0, clip_coef=1.0):
-    """One torch.optim.SGD(momentum, nesterov=True, weight_decay) update of float32 CUDA parameters, in place, all tensors in one launch
-    (ldiff_op_sgd_nesterov_multi; a second launch for tensors that meet their first gradient later than the others: their buffer starts as g).
-    The gradient enters as inv_scale * clip_coef * grad: floats, or float32 device scalars (0-dim / 1-element tensors, read by the kernel).
-    As in torch, a tensor whose gradient is None is left untouched: no weight decay, no buffer.  `state` is the caller's dict: momentum buffers
-    by parameter index, the device tables."""
-    lib = _lib.load()
-    live = [(i, p, g) for i, (p, g) in enumerate(zip(params, grads)) if g is not None]
-    if not live:
-        return
-    dev = live[0][1].device
-
-    def scalar(name, v):
-        if torch.is_tensor(v):
-            if not (v.is_cuda and v.dtype == torch.float32 and v.numel() == 1):
-                raise ValueError(f"sgd_nesterov_step: {name} must be a float or a float32 CUDA scalar")
-            return v
-        return torch.tensor([float(v)], dtype=torch.float32, device=dev)
-
-    s_inv, s_clip = scalar("inv_scale", inv_scale), scalar("clip_coef", clip_coef)
-    bufs = state.setdefault("momentum_buffer", {})
-    groups = {0: [], 1: []}
-    for i, p, g in live:
-        if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
-            raise ValueError("sgd_nesterov_step: parameters must be contiguous float32 CUDA tensors")
-        first = i not in bufs
-        if first:
-            bufs[i] = torch.empty_like(p)
-        groups[int(first)].append((i, p, g))
-    old, tabs, keep = state.get("_tables") or [], [], [s_inv, s_clip]
-    for first, members in groups.items():
-        if not members:
-            continue
-        key = tuple((i, p.data_ptr(), p.numel()) for i, p, _ in members)
-        tab = next((t for t in old if t[0] == key), None)
-        if tab is None:
-            tensors, chunks = [], []
-            for t, (i, p, _) in enumerate(members):
-                tensors += [p.data_ptr(), bufs[i].data_ptr(), p.numel()]
-                for at in range(0, p.numel(), ADAMW_CHUNK):
-                    chunks += [t, at]
-            tab = (key, torch.tensor(tensors, dtype=torch.int64).to(dev), torch.tensor(chunks, dtype=torch.int64).to(dev), len(chunks) // 2)
-        tabs.append(tab)
-        gs = [g.detach().to(torch.float32).contiguous() for _, _, g in members]
-        gptr = torch.tensor([g.data_ptr() for g in gs], dtype=torch.int64).to(dev)
-        _lib.check(lib.ldiff_op_sgd_nesterov_multi(tab[1].data_ptr(), gptr.data_ptr(), tab[2].data_ptr(), tab[3], float(lr), float(momentum), float(weight_decay),
-                                                   first, s_inv.data_ptr(), s_clip.data_ptr(), _sp()))
-        keep.append((gs, gptr))
-    state["_tables"] = tabs
-    state["_keep"] = keep   # the launches are asynchronous: tables, scalars and converted gradients must outlive them
-    state["step"] = state.get("step", 0) + 1

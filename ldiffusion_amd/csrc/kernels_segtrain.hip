@@ -9,6 +9,8 @@
 // workspace and a small finalize that adds them in a fixed order (double): no floating-point atomics, so a replay on the same inputs is bit-identical.
 #include "common.h"
 
+#include <type_traits>
+
 namespace {
 
 __device__ __forceinline__ double wave_sum_d(double v) {
@@ -543,33 +545,53 @@ void launch_in_train_bwd(const f16* x, const f16* dy, const float* gamma, const 
   HIP_CHECK(hipGetLastError());
 }
 
-// workspace: doubles sums[B][NACC], dcs[B][NC]; floats coef[B][NC][2], part[B][chunks][NACC]
-long long dice_ce_ws_bytes(int B, long long HW, int n_heads) {
-  const int NV = (n_heads + 7) / 8, NC = 8 * NV, NACC = dce_nacc(NV);
-  const long long chunks = (HW + DCE_PIX - 1) / DCE_PIX;
-  return ((long long)B * NACC + (long long)B * NC) * 8 + ((long long)B * NC * 2 + (long long)B * chunks * NACC) * 4;
+// workspace: doubles sums[B][NACC], dcs[B][NC]; floats coef[B][NC][2], part[B][chunks][NACC].  dice_ce uses all four; stats `part`, from_sums `dcs` and `coef`
+struct DceWs {
+  int NV;
+  double *sums, *dcs;
+  float *coef, *part;
+  long long bytes;
+  DceWs(void* ws, int B, long long HW, int n_heads) : NV((n_heads + 7) / 8) {
+    const int NC = 8 * NV, NACC = dce_nacc(NV);
+    const long long chunks = (HW + DCE_PIX - 1) / DCE_PIX;
+    sums = (double*)ws;
+    dcs = sums + (long long)B * NACC;
+    coef = (float*)(dcs + (long long)B * NC);
+    part = coef + (long long)B * NC * 2;
+    bytes = ((long long)B * NACC + (long long)B * NC) * 8 + ((long long)B * NC * 2 + (long long)B * chunks * NACC) * 4;
+  }
+};
+
+long long dice_ce_ws_bytes(int B, long long HW, int n_heads) { return DceWs(nullptr, B, HW, n_heads).bytes; }
+
+static DceWs dice_ce_check(const char* what, int ld, int n_heads, int B, long long HW, void* ws, long long ws_bytes) {
+  LDIFF_CHECK(n_heads >= 2 && n_heads <= 32, LDIFF_ERR_INVALID, "%s: %d heads (2 .. 32: background and at least one foreground class)", what, n_heads);
+  LDIFF_CHECK(ld == 8 * ((n_heads + 7) / 8), LDIFF_ERR_INVALID, "%s: row pitch %d, roundup(n_heads, 8) = %d expected (the seg layer's output layout)", what, ld,
+              8 * ((n_heads + 7) / 8));
+  LDIFF_CHECK(B >= 1 && HW >= 1 && HW <= (1ll << 40), LDIFF_ERR_INVALID, "%s: B=%d HW=%lld", what, B, HW);
+  LDIFF_CHECK(B <= 65535, LDIFF_ERR_INVALID, "%s: B=%d exceeds the grid's second dimension", what, B);
+  const DceWs w(ws, B, HW, n_heads);
+  LDIFF_CHECK(ws_bytes >= w.bytes, LDIFF_ERR_INVALID, "%s: workspace of %lld bytes, %lld needed (ldiff_op_dice_ce_ws_bytes)", what, ws_bytes, w.bytes);
+  return w;
+}
+
+// f(integral constant NV): the launchers are templates on the number of 8-column vectors of a logits row
+template <class F>
+static void dce_dispatch(int NV, F&& f) {
+  switch (NV) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+  }
 }
 
 void launch_dice_ce(const f16* logits, int ld, int n_heads, const void* target, int target_i64, int B, long long HW, int batch_dice, float smooth, float weight,
                     float grad_scale, float* loss, f16* dlogits, void* ws, long long ws_bytes, hipStream_t s) {
-  LDIFF_CHECK(n_heads >= 2 && n_heads <= 32, LDIFF_ERR_INVALID, "dice_ce: %d heads (2 .. 32: background and at least one foreground class)", n_heads);
-  const int NV = (n_heads + 7) / 8, NC = 8 * NV, NACC = dce_nacc(NV);
-  LDIFF_CHECK(ld == NC, LDIFF_ERR_INVALID, "dice_ce: row pitch %d, roundup(n_heads, 8) = %d expected (the seg layer's output layout)", ld, NC);
-  LDIFF_CHECK(B >= 1 && HW >= 1 && HW <= (1ll << 40), LDIFF_ERR_INVALID, "dice_ce: B=%d HW=%lld", B, HW);
-  LDIFF_CHECK(B <= 65535, LDIFF_ERR_INVALID, "dice_ce: B=%d exceeds the grid's second dimension", B);
-  LDIFF_CHECK(ws_bytes >= dice_ce_ws_bytes(B, HW, n_heads), LDIFF_ERR_INVALID, "dice_ce: workspace of %lld bytes, %lld needed (ldiff_op_dice_ce_ws_bytes)",
-              ws_bytes, dice_ce_ws_bytes(B, HW, n_heads));
-  double* sums = (double*)ws;
-  double* dcs = sums + (long long)B * NACC;
-  float* coef = (float*)(dcs + (long long)B * NC);
-  float* part = coef + (long long)B * NC * 2;
-  const float gsw = weight * grad_scale;
-  switch (NV) {
-    case 1: dce_launch<1>(logits, target, target_i64, B, HW, n_heads, batch_dice, smooth, gsw, loss, dlogits, sums, dcs, coef, part, s); break;
-    case 2: dce_launch<2>(logits, target, target_i64, B, HW, n_heads, batch_dice, smooth, gsw, loss, dlogits, sums, dcs, coef, part, s); break;
-    case 3: dce_launch<3>(logits, target, target_i64, B, HW, n_heads, batch_dice, smooth, gsw, loss, dlogits, sums, dcs, coef, part, s); break;
-    default: dce_launch<4>(logits, target, target_i64, B, HW, n_heads, batch_dice, smooth, gsw, loss, dlogits, sums, dcs, coef, part, s); break;
-  }
+  const DceWs w = dice_ce_check("dice_ce", ld, n_heads, B, HW, ws, ws_bytes);
+  dce_dispatch(w.NV, [&](auto nv) {
+    dce_launch<decltype(nv)::value>(logits, target, target_i64, B, HW, n_heads, batch_dice, smooth, weight * grad_scale, loss, dlogits, w.sums, w.dcs, w.coef, w.part, s);
+  });
 }
 
 void launch_sgd_nesterov_multi(const SgdTensor* tensors, const float* const* grads, const AdamChunk* chunks, long long nchunks, float lr, float momentum, float wd,
@@ -579,46 +601,23 @@ void launch_sgd_nesterov_multi(const SgdTensor* tensors, const float* const* gra
   HIP_CHECK(hipGetLastError());
 }
 
-static void dice_ce_check(const char* what, int ld, int n_heads, int B, long long HW, long long ws_bytes) {
-  LDIFF_CHECK(n_heads >= 2 && n_heads <= 32, LDIFF_ERR_INVALID, "%s: %d heads (2 .. 32: background and at least one foreground class)", what, n_heads);
-  LDIFF_CHECK(ld == 8 * ((n_heads + 7) / 8), LDIFF_ERR_INVALID, "%s: row pitch %d, roundup(n_heads, 8) = %d expected (the seg layer's output layout)", what, ld,
-              8 * ((n_heads + 7) / 8));
-  LDIFF_CHECK(B >= 1 && B <= 65535 && HW >= 1 && HW <= (1ll << 40), LDIFF_ERR_INVALID, "%s: B=%d HW=%lld", what, B, HW);
-  LDIFF_CHECK(ws_bytes >= dice_ce_ws_bytes(B, HW, n_heads), LDIFF_ERR_INVALID, "%s: workspace of %lld bytes, %lld needed (ldiff_op_dice_ce_ws_bytes)", what, ws_bytes,
-              dice_ce_ws_bytes(B, HW, n_heads));
-}
-
-// the workspace is launch_dice_ce's, with the sums outside it: stats uses `part`, from_sums `dcs` and `coef`
 void launch_dice_ce_stats(const f16* logits, int ld, int n_heads, const void* target, int target_i64, int B, long long HW, int batch_dice, double* sums, void* ws,
                           long long ws_bytes, hipStream_t s) {
-  dice_ce_check("dice_ce_stats", ld, n_heads, B, HW, ws_bytes);
-  const int NV = (n_heads + 7) / 8, NC = 8 * NV, NACC = dce_nacc(NV);
-  float* part = (float*)((double*)ws + (long long)B * NACC + (long long)B * NC) + (long long)B * NC * 2;
-  switch (NV) {
-    case 1: dce_stats_launch<1>(logits, target, target_i64, B, HW, n_heads, batch_dice, sums, part, s); break;
-    case 2: dce_stats_launch<2>(logits, target, target_i64, B, HW, n_heads, batch_dice, sums, part, s); break;
-    case 3: dce_stats_launch<3>(logits, target, target_i64, B, HW, n_heads, batch_dice, sums, part, s); break;
-    default: dce_stats_launch<4>(logits, target, target_i64, B, HW, n_heads, batch_dice, sums, part, s); break;
-  }
+  const DceWs w = dice_ce_check("dice_ce_stats", ld, n_heads, B, HW, ws, ws_bytes);
+  dce_dispatch(w.NV, [&](auto nv) { dce_stats_launch<decltype(nv)::value>(logits, target, target_i64, B, HW, n_heads, batch_dice, sums, w.part, s); });
 }
 
 void launch_dice_ce_from_sums(const f16* logits, int ld, int n_heads, const void* target, int target_i64, int B, long long HW, int batch_dice, float smooth,
                               float weight, float grad_scale, const double* dice_sums, const double* local_sums, int world, float* loss, f16* dlogits, void* ws,
                               long long ws_bytes, hipStream_t s) {
-  dice_ce_check("dice_ce_from_sums", ld, n_heads, B, HW, ws_bytes);
+  const DceWs w = dice_ce_check("dice_ce_from_sums", ld, n_heads, B, HW, ws, ws_bytes);
   LDIFF_CHECK(world >= 1, LDIFF_ERR_INVALID, "dice_ce_from_sums: world=%d", world);
   LDIFF_CHECK(batch_dice || (world == 1 && dice_sums == local_sums), LDIFF_ERR_INVALID,
               "dice_ce_from_sums: without batch_dice the Dice term is per sample and stays local (world = 1, dice_sums = local_sums)");
-  const int NV = (n_heads + 7) / 8, NC = 8 * NV, NACC = dce_nacc(NV);
-  double* dcs = (double*)ws + (long long)B * NACC;
-  float* coef = (float*)(dcs + (long long)B * NC);
-  const float gsw = weight * grad_scale;
-  switch (NV) {
-    case 1: dce_from_sums_launch<1>(logits, target, target_i64, B, HW, n_heads, batch_dice, smooth, gsw, dice_sums, local_sums, world, loss, dlogits, dcs, coef, s); break;
-    case 2: dce_from_sums_launch<2>(logits, target, target_i64, B, HW, n_heads, batch_dice, smooth, gsw, dice_sums, local_sums, world, loss, dlogits, dcs, coef, s); break;
-    case 3: dce_from_sums_launch<3>(logits, target, target_i64, B, HW, n_heads, batch_dice, smooth, gsw, dice_sums, local_sums, world, loss, dlogits, dcs, coef, s); break;
-    default: dce_from_sums_launch<4>(logits, target, target_i64, B, HW, n_heads, batch_dice, smooth, gsw, dice_sums, local_sums, world, loss, dlogits, dcs, coef, s); break;
-  }
+  dce_dispatch(w.NV, [&](auto nv) {
+    dce_from_sums_launch<decltype(nv)::value>(logits, target, target_i64, B, HW, n_heads, batch_dice, smooth, weight * grad_scale, dice_sums, local_sums, world, loss,
+                                              dlogits, w.dcs, w.coef, s);
+  });
 }
 
 void launch_bucket_pack(const float* const* grads, const long long* offsets, const AdamChunk* chunks, long long nchunks, float* bucket, hipStream_t s) {

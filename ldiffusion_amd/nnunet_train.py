@@ -5,7 +5,7 @@ Per step (nnUNetTrainer.train_step, nnUNetTrainer.py:883-913):
     outputs = network(data)                       PlainConvUNet with deep supervision: one head per decoder stage          TrainableSegNet
     l = sum_i w_i * DC_and_CE(outputs[i], target[i])   w = 1 / 2^i, the last 0, normalised (:364-372)                      ag.DiceCeFn (ldiff_op_dice_ce)
     scaler.scale(l).backward()                    conv dgrad / wgrad on the forward kernels, InstanceNorm + LeakyReLU backward      ag.Conv2dFn, ag.InstanceNormLReLUFn
-    unscale, clip_grad_norm_(12), SGD(0.99, nesterov), scaler.update()                                                      train.finish_step + ag.sgd_nesterov_step
+    unscale, clip_grad_norm_(12), SGD(0.99, nesterov), scaler.update()                                                      train.finish_step + optim.sgd_nesterov_step
 Every contraction, normalisation, activation, loss term and parameter update runs in libldiff_hip.so; torch provides the tape, the channel concat, the
 depth-to-space permute behind the transposed conv's GEMM and the global gradient norm.
 
@@ -15,8 +15,8 @@ resolution first; `nnunet_data.PatchLoader` makes them on the device; `Segmentor
 Data-parallel over a launch's ranks (`Trainer(ddp=...)`; nnUNetTrainer.is_ddp, :86): `rank_batch_sizes` splits the plans' batch, a step is three phases
 with two collectives between them --
     step_forward   forward, ag.dice_ce_stats per graded scale            -> all_gather of the [scales, NACC] statistics, added in rank order
-    step_backward  ag.DiceCeSumsFn on the summed statistics, backward, ag.bucket_pack   -> all_reduce(SUM) of the flat gradient bucket
-    step_update    1 / world folded into the update's device scalar, ag.sumsq for the norm, the loss-scale rule, clip coefficient, one SGD launch
+    step_backward  ag.DiceCeSumsFn on the summed statistics, backward, optim.bucket_pack   -> all_reduce(SUM) of the flat gradient bucket
+    step_update    1 / world folded into the update's device scalar, optim.sumsq for the norm, optim.update_loss_scale, clip coefficient, one SGD launch
 -- and `run_training` pools losses and tp / fp / fn over the ranks; rank 0 writes the checkpoints.
 
 Not here: a captured-graph step, ResidualEncoderUNet, region labels and an ignore label.
@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from . import autograd as ag
-from . import metrics, nnunet, train
+from . import metrics, nnunet, optim, train
 
 EPS = 1e-5              # InstanceNorm2d eps (get_network_from_plans: norm_op_kwargs)
 SLOPE = 0.01            # LeakyReLU negative_slope, ditto
@@ -304,14 +304,17 @@ class Trainer:
             total = term if total is None else total + term
         return total
 
-    def _update(self, params, grads, opt_state, lr, weight_decay):
-        """What follows a finite backward pass: clip_grad_norm_'s coefficient (torch: max_norm / (norm + 1e-6), at most 1) from the global norm of the
-        UNSCALED gradients -- train.finish_step has just taken the norm of the scaled ones for its overflow test and left it in the state, so no second
-        pass over the gradients -- and the update: the kernel reads 1 / scale and the coefficient as device scalars, the gradients are not rewritten."""
-        norm = float(opt_state["grad_norm"]) * self._inv_scale
+    def _clipped_sgd(self, grads, norm, lr):
+        """The end of both step forms: clip_grad_norm_(CLIP_NORM)'s coefficient from `norm`, the global norm of the UNSCALED gradients, and the update --
+        the kernel reads `_scale_t` (1 / scale) and the coefficient as device scalars, the gradients are not rewritten."""
         self.last_grad_norm = norm
-        self._clip_t.fill_(min(1.0, CLIP_NORM / (norm + 1e-6)))
-        ag.sgd_nesterov_step(params, grads, opt_state["sgd"], lr, weight_decay, MOMENTUM, self._scale_t, self._clip_t)
+        self._clip_t.fill_(optim.clip_coef_torch(norm, CLIP_NORM))
+        optim.sgd_nesterov_step(self.params, grads, self.state["sgd"], lr, self.weight_decay, MOMENTUM, self._scale_t, self._clip_t)
+
+    def _update(self, params, grads, opt_state, lr, weight_decay):
+        """What follows a finite backward pass of the plain step: train.finish_step has just taken the norm of the scaled gradients for its overflow
+        test and left it in the state, so no second pass over the gradients."""
+        self._clipped_sgd(grads, float(opt_state["grad_norm"]) * self._inv_scale, lr)
 
     # ---- the data-parallel step: three phases, the two collectives between them (a test may do those by hand) ----
     def step_forward(self, data, targets) -> torch.Tensor:
@@ -376,7 +379,7 @@ class Trainer:
             total = self._loss_from_sums(graded, local, global_sums, scale)
             total.backward()
             self._inv_scale = 1.0 / scale
-            bucket, self._offsets = ag.bucket_pack([p.grad for p in self.params], self._bucket_state)
+            bucket, self._offsets = optim.bucket_pack([p.grad for p in self.params], self._bucket_state)
         self._live = [i for i, p in enumerate(self.params) if p.grad is not None]
         return total.detach(), bucket
 
@@ -388,32 +391,20 @@ class Trainer:
 
     def step_update(self, bucket: torch.Tensor) -> bool:
         """Phase 3, on the summed bucket (identical bits on every rank, so every rank takes the same branch): the mean over the ranks is the factor
-        1 / world in the update's `inv_scale` device scalar and in the norm; the norm (ag.sumsq) of the averaged, unscaled gradient; train.finish_step's
-        loss-scale rule restated for this path -- non-finite: skip, halve, reset; LOSS_SCALE_GROWTH_INTERVAL finite steps double a lowered scale --;
-        clip_grad_norm_(CLIP_NORM)'s coefficient as `_update` forms it; one SGD launch whose gradient table points into the bucket.  True when the
+        1 / world in the update's `inv_scale` device scalar and in the norm; the norm (optim.sumsq) of the averaged, unscaled gradient;
+        optim.update_loss_scale, as in train.finish_step; `_clipped_sgd`: one SGD launch whose gradient table points into the bucket.  True when the
         update ran."""
-        st = self.state
         with torch.cuda.device(self.device):
-            total = float(ag.sumsq(bucket, self._norm_t))   # of the summed gradients at the loss scale
-            st["grad_norm"] = total
-            if not math.isfinite(total):
-                st["skipped_steps"] = st.get("skipped_steps", 0) + 1
-                st["loss_scale"] = max(1.0, st.get("loss_scale", train.LOSS_SCALE) * 0.5)
-                st["finite_steps"] = 0
+            total = float(optim.sumsq(bucket, self._norm_t))   # of the summed gradients at the loss scale
+            self.state["grad_norm"] = total
+            if not optim.update_loss_scale(self.state, total):
                 return False
-            st["finite_steps"] = st.get("finite_steps", 0) + 1
-            if st["finite_steps"] >= train.LOSS_SCALE_GROWTH_INTERVAL and st.get("loss_scale", train.LOSS_SCALE) < train.LOSS_SCALE:
-                st["loss_scale"] = min(train.LOSS_SCALE, st["loss_scale"] * 2.0)
-                st["finite_steps"] = 0
             inv = self._inv_scale / self.world
-            norm = total * inv
-            self.last_grad_norm = norm
             self._scale_t.fill_(inv)
-            self._clip_t.fill_(min(1.0, CLIP_NORM / (norm + 1e-6)))
             grads: list = [None] * len(self.params)
             for j, i in enumerate(self._live):
                 grads[i] = bucket[self._offsets[j]:self._offsets[j + 1]].view_as(self.params[i])
-            ag.sgd_nesterov_step(self.params, grads, st["sgd"], self.lr(), self.weight_decay, MOMENTUM, self._scale_t, self._clip_t)
+            self._clipped_sgd(grads, total * inv, self.lr())
         return True
 
     def _train_step_ddp(self, data, targets) -> float:

@@ -27,6 +27,7 @@ import torch
 import torch.nn.functional as F
 
 from . import autograd as ag
+from .optim import LOSS_SCALE, LOSS_SCALE_GROWTH_INTERVAL, clip_coef_deepspeed, update_loss_scale  # noqa: F401  (the step tail: optim.py)
 
 LUMA = (0.2989, 0.5870, 0.1140)  # ldiffusion.py:241
 
@@ -373,10 +374,9 @@ class ShardedAdamW:
             # skips -- parameters, moments and the step count stay as they are (the caller lowers the loss scale, train.finish_step)
             self.skipped += 1
             return total
-        if max_grad_norm is not None:
-            coef = float(max_grad_norm) / max(total, float(max_grad_norm))
-            if coef < 1.0:
-                self.gshard *= coef
+        coef = clip_coef_deepspeed(total, max_grad_norm)
+        if coef < 1.0:
+            self.gshard *= coef
         self.step_count += 1
         if self.partition_params:   # the owned slice only; the full parameters come back with the next gather()
             self.update(self.master, self.gshard, self.m, self.v, self.step_count, self.lr, self.betas, self.eps, self.weight_decay)
@@ -391,33 +391,24 @@ class ShardedAdamW:
 
 
 def clip_grad_norm(params, max_norm):
-    """DeepSpeed's `gradient_clipping` (ldiffusion.py:187: 1.0): scale all gradients by max_norm / max(global L2 norm, max_norm).
+    """DeepSpeed's `gradient_clipping` (ldiffusion.py:187: 1.0): scale all gradients by optim.clip_coef_deepspeed of their global L2 norm.
     Multi-tensor reductions (688 gradient tensors at SD-v1.5 width: one norm launch each took 19 ms of a step)."""
     grads = [p.grad for p in params if p.grad is not None]
     if not grads:
         return 0.0
     total = float(torch.linalg.vector_norm(torch.stack(torch._foreach_norm(grads))))
-    if max_norm is None or not math.isfinite(total):
-        return total            # non-finite: the caller skips the update (finish_step); scaling by inf * 0 would plant NaN everywhere
-    coef = float(max_norm) / max(total, float(max_norm))
-    if coef < 1.0:
-        torch._foreach_mul_(grads, coef)
+    if math.isfinite(total):    # non-finite: the caller skips the update (finish_step); scaling by inf * 0 would plant NaN everywhere
+        coef = clip_coef_deepspeed(total, max_norm)
+        if coef < 1.0:
+            torch._foreach_mul_(grads, coef)
     return total
-
-
-LOSS_SCALE = 1024.0   # initial loss scale of the backward pass: activation gradients are stored in float16 (the reference trains in fp32,
-                      # ldiffusion.py:172 `fp16.enabled: False`); unscaled, 0.5 % of the non-negligible parameter-gradient entries underflow to zero
-
-
-LOSS_SCALE_GROWTH_INTERVAL = 200   # consecutive finite steps before a lowered loss scale doubles again (never above LOSS_SCALE)
 
 
 def finish_step(params, opt_state, lr, weight_decay, max_grad_norm, optimizer=None, update=None):
     """What follows the backward pass on every rank: gradient exchange -> global norm -> (clipping) -> AdamW.  The norm is taken AFTER the
     exchange, so all ranks see the same value and take the same branch: a non-finite norm (a float16 activation gradient overflowed under the
     loss scale; the reference trains in fp32 and cannot hit this) skips the update -- parameters, moments and the AdamW step count untouched --
-    and halves `opt_state["loss_scale"]` (dynamic loss scaling; the next step's backward reads it); LOSS_SCALE_GROWTH_INTERVAL finite steps in a row
-    double a lowered scale again, up to LOSS_SCALE.  Returns True when the update ran.
+    and lowers `opt_state["loss_scale"]` (optim.update_loss_scale; the next step's backward reads it).  Returns True when the update ran.
     `optimizer` = a ShardedAdamW (reduce-scatter / sharded update / all-gather) or None (flattened all-reduce + ag.adamw_step)."""
     if optimizer is not None:
         total = optimizer.step(max_grad_norm)
@@ -425,18 +416,8 @@ def finish_step(params, opt_state, lr, weight_decay, max_grad_norm, optimizer=No
         allreduce_gradients(params)
         total = clip_grad_norm(params, max_grad_norm)
     opt_state["grad_norm"] = total   # of the gradients as the backward pass left them (before clipping, at the loss scale): an `update` callback reuses it
-    if not math.isfinite(total):
-        opt_state["skipped_steps"] = opt_state.get("skipped_steps", 0) + 1
-        opt_state["loss_scale"] = max(1.0, opt_state.get("loss_scale", LOSS_SCALE) * 0.5)
-        opt_state["finite_steps"] = 0
+    if not update_loss_scale(opt_state, total):
         return False
-    # growth rule of dynamic loss scaling: after LOSS_SCALE_GROWTH_INTERVAL consecutive finite steps the scale doubles, up to the initial
-    # LOSS_SCALE -- one transient overflow must not pin the scale low for the rest of the run (the underflow LOSS_SCALE exists to avoid would
-    # come back).  `total` is the exchanged norm, identical on every rank, so the decision is rank-uniform.
-    opt_state["finite_steps"] = opt_state.get("finite_steps", 0) + 1
-    if opt_state["finite_steps"] >= LOSS_SCALE_GROWTH_INTERVAL and opt_state.get("loss_scale", LOSS_SCALE) < LOSS_SCALE:
-        opt_state["loss_scale"] = min(LOSS_SCALE, opt_state["loss_scale"] * 2.0)
-        opt_state["finite_steps"] = 0
     if optimizer is None:
         (update or ag.adamw_step)(params, [p.grad for p in params], opt_state, lr=lr, weight_decay=weight_decay)
     return True
