@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define LDIFF_VERSION 213 /* 0.2.1.2: + ldiff_op_label_table_u8 / ldiff_op_gather_labels / ldiff_op_warmup_labels (+ _supported) / ldiff_op_warmup_images (the warm-up trainer's dataset resident on the device: label bytes through a grey-level table, a batch of labels and masks gathered by index, and the 64x64 warm-up batch -- labels by torch's bilinear rule in integers, images through the normalisation table and the antialiased triangle weights in one pass over the stored bytes); 0.2.1.1: + ldiff_op_resize_u8 / ldiff_op_resize_u8_ws_bytes (the device image front end: PIL.Image.resize(size, BILINEAR) of 8-bit interleaved images bit for bit from host-made coefficient tables, optionally through a float [3][256] table into the sampler's NCHW input; LDIFF_RESIZE_MAX_TAPS); 0.2.1.0: + ldiff_op_window_gather / _accumulate_batch / _finish (the tissue head's sliding window in batches: tiles x mirror variants gathered, un-flipped, averaged and Gaussian-accumulated per chunk, then divide + inf flag + arg-max + un-crop in one launch; ldiff_window_tiles by value), after ldiff_op_dice_ce_stats / _from_sums, ldiff_op_bucket_pack, ldiff_op_sumsq (data-parallel tissue training); 0.2.0.9: + ldiff_op_case_bbox / _stats / _counts / _apply / _rank_to_coord (plan and preprocess of the tissue head's training cases on the device: non-zero box, crop statistics, label counts per row, normalise into the arena, rank -> pixel); 0.2.0.8: + ldiff_op_seg_intensity_lr (the intensity chain with nnU-Net's low-resolution simulation between contrast and the gammas), ldiff_op_spline_prefilter (cubic B-spline prefilter on the device, one workgroup per plane); 0.2.0.7: + ldiff_op_conv_wgrad (direct MFMA weight gradient of the narrow convs over the pixel index, no im2col), ldiff_op_colsum_slabs (slab-reduced bias gradient), both with fixed-order partials; 0.2.0.6: + ldiff_op_seg_sample (patches, labels and deep-supervision targets of a training batch from cases resident on the device), ldiff_op_seg_intensity (nnU-Net's intensity augmentations, one workgroup per plane); 0.2.0.5: + ldiff_unet_set_plan_batch / ldiff_vae_set_plan_batch / ldiff_controlnet_set_plan_batch (batch-invariant mode: every launch planned for a nominal batch), ldiff_op_conv_pb, ldiff_op_attention_pb, ldiff_op_gn_stats_pb; 0.2.0.4: + ldiff_op_in_train_fwd / _bwd (InstanceNorm + LeakyReLU with saved statistics), ldiff_op_dice_ce (nnU-Net deep-supervision loss of one scale, value and gradient), ldiff_op_sgd_nesterov_multi; 0.2.0.3: + ldiff_confusion (per-image confusion matrices of masks or logits against labels, accumulated on the device), ldiff_seg_metrics (host: Dice / IoU / pixel accuracy / frequency-weighted IoU from one matrix); 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
+#define LDIFF_VERSION 214 /* 0.2.1.3: + ldiff_op_dice_ce_ignore / _ignore_stats / _ignore_from_sums (+ _ignore_ws_bytes, _ignore_nacc): the tissue head's loss with nnU-Net's ignore label; + ldiff_op_case_counts_classes and the selectors -1 - m (`label < m`) of ldiff_op_case_rank_to_coord, for the annotated-pixel locations of a partly annotated case.  0.2.1.2: + ldiff_op_label_table_u8 / ldiff_op_gather_labels / ldiff_op_warmup_labels (+ _supported) / ldiff_op_warmup_images (the warm-up trainer's dataset resident on the device: label bytes through a grey-level table, a batch of labels and masks gathered by index, and the 64x64 warm-up batch -- labels by torch's bilinear rule in integers, images through the normalisation table and the antialiased triangle weights in one pass over the stored bytes); 0.2.1.1: + ldiff_op_resize_u8 / ldiff_op_resize_u8_ws_bytes (the device image front end: PIL.Image.resize(size, BILINEAR) of 8-bit interleaved images bit for bit from host-made coefficient tables, optionally through a float [3][256] table into the sampler's NCHW input; LDIFF_RESIZE_MAX_TAPS); 0.2.1.0: + ldiff_op_window_gather / _accumulate_batch / _finish (the tissue head's sliding window in batches: tiles x mirror variants gathered, un-flipped, averaged and Gaussian-accumulated per chunk, then divide + inf flag + arg-max + un-crop in one launch; ldiff_window_tiles by value), after ldiff_op_dice_ce_stats / _from_sums, ldiff_op_bucket_pack, ldiff_op_sumsq (data-parallel tissue training); 0.2.0.9: + ldiff_op_case_bbox / _stats / _counts / _apply / _rank_to_coord (plan and preprocess of the tissue head's training cases on the device: non-zero box, crop statistics, label counts per row, normalise into the arena, rank -> pixel); 0.2.0.8: + ldiff_op_seg_intensity_lr (the intensity chain with nnU-Net's low-resolution simulation between contrast and the gammas), ldiff_op_spline_prefilter (cubic B-spline prefilter on the device, one workgroup per plane); 0.2.0.7: + ldiff_op_conv_wgrad (direct MFMA weight gradient of the narrow convs over the pixel index, no im2col), ldiff_op_colsum_slabs (slab-reduced bias gradient), both with fixed-order partials; 0.2.0.6: + ldiff_op_seg_sample (patches, labels and deep-supervision targets of a training batch from cases resident on the device), ldiff_op_seg_intensity (nnU-Net's intensity augmentations, one workgroup per plane); 0.2.0.5: + ldiff_unet_set_plan_batch / ldiff_vae_set_plan_batch / ldiff_controlnet_set_plan_batch (batch-invariant mode: every launch planned for a nominal batch), ldiff_op_conv_pb, ldiff_op_attention_pb, ldiff_op_gn_stats_pb; 0.2.0.4: + ldiff_op_in_train_fwd / _bwd (InstanceNorm + LeakyReLU with saved statistics), ldiff_op_dice_ce (nnU-Net deep-supervision loss of one scale, value and gradient), ldiff_op_sgd_nesterov_multi; 0.2.0.3: + ldiff_confusion (per-image confusion matrices of masks or logits against labels, accumulated on the device), ldiff_seg_metrics (host: Dice / IoU / pixel accuracy / frequency-weighted IoU from one matrix); 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
 #define LDIFF_MAX_BLOCKS 8
 #define LDIFF_RESIZE_MAX_TAPS 128 /* longest coefficient row ldiff_op_resize_u8 takes: reductions up to 63x (a 16x reduction has 33 taps) */
 
@@ -753,6 +753,23 @@ int ldiff_op_dice_ce_stats(const void* logits, int ld, int n_heads, const void* 
 int ldiff_op_dice_ce_from_sums(const void* logits, int ld, int n_heads, const void* target, int target_i64, int B, int64_t HW, int batch_dice, float smooth,
                                float weight, float grad_scale, const void* dice_sums, const void* local_sums, int world, void* loss, void* dlogits, void* ws,
                                int64_t ws_bytes, void* stream);
+/* The three with nnU-Net's ignore label (DC_and_CE_loss(ignore_label = k); compound_losses.py:31-56, dice.py:72-119): a pixel whose label equals
+ * ignore_label (n_heads <= ignore_label <= 254; nnU-Net's rule makes it n_heads) adds nothing -- the Dice sums run over the other, annotated pixels, the
+ * cross-entropy is their sum over their count (this process's own; 0 when the count is 0, the Dice term is then -1), the pixel's dlogits row is +0 and its
+ * logits are never read.  A label that is neither a class nor ignore_label still makes the loss and that pixel's dlogits NaN.  Region labels are not built.
+ * A row of statistics holds ldiff_op_dice_ce_ignore_nacc(n_heads) = 3 ld + 3 doubles: the plain row, then the count of annotated pixels.
+ * ws: ldiff_op_dice_ce_ignore_ws_bytes(...) bytes each.  On a target without an ignored pixel the three give the plain entries' loss and dlogits bit for bit;
+ * stats then from_sums give ldiff_op_dice_ce_ignore's bits.  from_sums takes this process's own rows: the data-parallel exchange of the ignore form
+ * (all ranks' Dice statistics with each rank's own annotated count) is not built. */
+int64_t ldiff_op_dice_ce_ignore_ws_bytes(int B, int64_t HW, int n_heads);
+int ldiff_op_dice_ce_ignore_nacc(int n_heads);
+int ldiff_op_dice_ce_ignore(const void* logits, int ld, int n_heads, int ignore_label, const void* target, int target_i64, int B, int64_t HW, int batch_dice,
+                            float smooth, float weight, float grad_scale, void* loss, void* dlogits, void* ws, int64_t ws_bytes, void* stream);
+int ldiff_op_dice_ce_ignore_stats(const void* logits, int ld, int n_heads, int ignore_label, const void* target, int target_i64, int B, int64_t HW, int batch_dice,
+                                  void* sums, void* ws, int64_t ws_bytes, void* stream);
+int ldiff_op_dice_ce_ignore_from_sums(const void* logits, int ld, int n_heads, int ignore_label, const void* target, int target_i64, int B, int64_t HW,
+                                      int batch_dice, float smooth, float weight, float grad_scale, const void* sums, void* loss, void* dlogits, void* ws,
+                                      int64_t ws_bytes, void* stream);
 /* The gradient bucket of a data-parallel step.  ldiff_op_bucket_pack: bucket[offsets[t] + i] = grads[t][i] for every tensor in one launch; grads = device
  * table of const float*, offsets = device int64 [T + 1] (prefix sums of the element counts), chunks as ldiff_op_adamw_multi's.
  * ldiff_op_sumsq: out_f32[0] = sqrt(sum x^2) of n f32 elements (4-byte aligned) through one fp32 partial per 16384 elements (at most 27 dependent roundings
@@ -854,12 +871,16 @@ int ldiff_op_spline_prefilter(void* planes_f32, int n_planes, int H, int W, int 
  * ldiff_op_case_counts: row_counts uint32 [rows, n_heads + 1]: per row of the box the pixels of class 0 .. n_heads - 1, then those with a label >= n_heads;
  *   row_prefix uint32 [n_heads + 1, rows + 1]: per selector -- class c, or (index n_heads) `label > 0` -- the selected pixels above each row, the last
  *   entry the total; totals uint32 [n_heads + 2]: per class, `label > 0`, labels >= n_heads.  n_heads <= 32.  Exact.
+ * ldiff_op_case_counts_classes: the same with one more selector, `label < n_classes` (1 <= n_classes <= n_heads <= 33) -- "the label is a class" of a map
+ *   whose highest value is an ignore label, counted here as class n_heads - 1: row_prefix uint32 [n_heads + 2, rows + 1], that selector's row last;
+ *   totals uint32 [n_heads + 3], its count last.  The other rows and entries are ldiff_op_case_counts'.
  * ldiff_op_case_apply: the cropped planes as float32 (x - sub[c]) / div[c] (sub, div: HOST arrays of C floats; one subtraction and one correctly rounded
  *   division) to arena + row->raw_off [C, h, row->stride], also to row->coef_off when write_coef != 0 (ldiff_op_spline_prefilter then runs in place),
  *   and the cropped labels to row->label_off [h, row->label_stride].  row: a HOST ldiff_seg_case with H, W the box's extent; refused when a span leaves
  *   the arena or a float offset is no multiple of 4.
  * ldiff_op_case_rank_to_coord: coords int32 [n, 2] = (row, column) inside the box of the rank-th selected pixel in row-major order, numpy's
- *   argwhere(selection)[rank]; selector = a class, or -1 for `label > 0`; row_prefix: that selector's uint32 [rows + 1] of ldiff_op_case_counts; ranks int64
+ *   argwhere(selection)[rank]; selector = a class, -1 for `label > 0`, or -1 - m for `label < m` (1 <= m <= 255: ldiff_op_case_counts_classes' selector);
+ *   row_prefix: that selector's uint32 [rows + 1] of ldiff_op_case_counts; ranks int64
  *   [n], any order, repeats allowed.  values_or_null [n, C] of the image's dtype: the pixel's C channels.  A rank outside [0, total) yields (-1, -1) and
  *   zeros. */
 int ldiff_op_case_bbox(const void* img, int dtype, int C, int H, int W, int64_t row_stride, int64_t plane_stride, int32_t* box, void* stream);
@@ -868,6 +889,8 @@ int ldiff_op_case_stats(const void* img, int dtype, int C, int H, int W, int64_t
                         int64_t ws_bytes, void* stream);
 int ldiff_op_case_counts(const void* label_u8, int H, int W, int64_t label_stride, int y0, int y1, int x0, int x1, int n_heads, uint32_t* row_counts, uint32_t* row_prefix,
                          uint32_t* totals, void* stream);
+int ldiff_op_case_counts_classes(const void* label_u8, int H, int W, int64_t label_stride, int y0, int y1, int x0, int x1, int n_heads, int n_classes,
+                                 uint32_t* row_counts, uint32_t* row_prefix, uint32_t* totals, void* stream);
 int ldiff_op_case_apply(const void* img, int dtype, int C, int H, int W, int64_t row_stride, int64_t plane_stride, const void* label_u8, int64_t label_stride, int y0, int y1,
                         int x0, int x1, const float* sub, const float* div, void* arena, int64_t arena_bytes, const ldiff_seg_case* row, int write_coef, void* stream);
 int ldiff_op_case_rank_to_coord(const void* label_u8, int H, int W, int64_t label_stride, int y0, int y1, int x0, int x1, int selector, const uint32_t* row_prefix,

@@ -224,6 +224,11 @@ SIGNATURES = {
     "ldiff_op_dice_ce": (I, [P, I, I, P, I, I, I64, I, F, F, F, P, P, P, I64, P]),
     "ldiff_op_dice_ce_stats": (I, [P, I, I, P, I, I, I64, I, P, P, I64, P]),
     "ldiff_op_dice_ce_from_sums": (I, [P, I, I, P, I, I, I64, I, F, F, F, P, P, I, P, P, P, I64, P]),
+    "ldiff_op_dice_ce_ignore_ws_bytes": (I64, [I, I64, I]),
+    "ldiff_op_dice_ce_ignore_nacc": (I, [I]),
+    "ldiff_op_dice_ce_ignore": (I, [P, I, I, I, P, I, I, I64, I, F, F, F, P, P, P, I64, P]),
+    "ldiff_op_dice_ce_ignore_stats": (I, [P, I, I, I, P, I, I, I64, I, P, P, I64, P]),
+    "ldiff_op_dice_ce_ignore_from_sums": (I, [P, I, I, I, P, I, I, I64, I, F, F, F, P, P, P, P, I64, P]),
     "ldiff_op_bucket_pack": (I, [P, P, P, I64, P, P]),
     "ldiff_op_sumsq_ws_bytes": (I64, [I64]),
     "ldiff_op_sumsq": (I, [P, I64, P, P, I64, P]),
@@ -244,6 +249,7 @@ SIGNATURES = {
     "ldiff_op_case_stats_ws_bytes": (I64, [I]),
     "ldiff_op_case_stats": (I, [P, I, I, I, I, I64, I64, I, I, I, I, P, P, I64, P]),
     "ldiff_op_case_counts": (I, [P, I, I, I64, I, I, I, I, I, P, P, P, P]),
+    "ldiff_op_case_counts_classes": (I, [P, I, I, I64, I, I, I, I, I, I, P, P, P, P]),
     "ldiff_op_case_apply": (I, [P, I, I, I, I, I64, I64, P, I64, I, I, I, I, C.POINTER(F), C.POINTER(F), P, I64, C.POINTER(SegCase), I, P]),
     "ldiff_op_case_rank_to_coord": (I, [P, I, I, I64, I, I, I, I, I, P, P, I64, P, P, I, I, I64, I64, P, P]),
     "ldiff_op_window_gather": (I, [P, I, I, I, I64, I64, I, I, I, I, C.POINTER(WindowTiles), I, I, P, P]),

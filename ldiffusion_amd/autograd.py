@@ -647,21 +647,37 @@ def _dice_ce_args(logits, target, what):
     return target.to(logits.device).contiguous(), B, H, W, ld
 
 
-def _dice_ce_ws(lib, B, HW, n_heads, device):
-    """(workspace, its byte count) of the three Dice + CE entries"""
-    nb = lib.ldiff_op_dice_ce_ws_bytes(B, HW, int(n_heads))
+def _dice_ce_ws(lib, B, HW, n_heads, device, ignore_label=None):
+    """(workspace, its byte count) of the three Dice + CE entries, or of their ignore form"""
+    nb = (lib.ldiff_op_dice_ce_ws_bytes if ignore_label is None else lib.ldiff_op_dice_ce_ignore_ws_bytes)(B, HW, int(n_heads))
     return _workspace(nb, device), nb
 
 
-def dice_ce(logits, target, n_heads, batch_dice, weight=1.0, grad_scale=1.0, smooth=1e-5):
+def _ignore_label(ignore_label, n_heads, what):
+    """None, or the label as the C entries take it: an integer that is no class (nnU-Net's own rule, nnunet.label_spec, makes it n_heads)."""
+    if ignore_label is None:
+        return None
+    if isinstance(ignore_label, bool) or int(ignore_label) != ignore_label or not int(n_heads) <= int(ignore_label) <= 254:
+        raise ValueError(f"{what}: ignore_label {ignore_label!r} must be an integer in [n_heads = {int(n_heads)}, 254]")
+    return int(ignore_label)
+
+
+def dice_ce(logits, target, n_heads, batch_dice, weight=1.0, grad_scale=1.0, smooth=1e-5, ignore_label=None):
     """ldiff_op_dice_ce on float16 logits [B, H, W, roundup(n_heads, 8)] and uint8 / int64 labels [B, H, W] (or [B, 1, H, W]):
-    (loss float32 0-dim, dlogits float16 = grad_scale * weight * d loss / d logits in the logits' layout).  Region labels and an ignore label are not
-    covered (nnunet.network_spec refuses them)."""
+    (loss float32 0-dim, dlogits float16 = grad_scale * weight * d loss / d logits in the logits' layout).  `ignore_label`: nnU-Net's ignore label
+    (ldiff_op_dice_ce_ignore): pixels carrying it add nothing to the loss and get a zero gradient; None is the plain entry.  Region labels are not
+    built (nnunet.network_spec refuses them)."""
     target, B, H, W, ld = _dice_ce_args(logits, target, "dice_ce")
+    ignore_label = _ignore_label(ignore_label, n_heads, "dice_ce")
     lib = _lib.load()
     loss = torch.empty(1, dtype=torch.float32, device=logits.device)
     dlogits = torch.empty_like(logits)
-    ws, nb = _dice_ce_ws(lib, B, H * W, n_heads, logits.device)
+    ws, nb = _dice_ce_ws(lib, B, H * W, n_heads, logits.device, ignore_label)
+    if ignore_label is not None:
+        _lib.check(lib.ldiff_op_dice_ce_ignore(logits.data_ptr(), ld, int(n_heads), ignore_label, target.data_ptr(), int(target.dtype == torch.int64), B, H * W,
+                                               int(bool(batch_dice)), float(smooth), float(weight), float(grad_scale), loss.data_ptr(), dlogits.data_ptr(),
+                                               ws.data_ptr(), nb, _sp()))
+        return loss[0], dlogits
     _lib.check(lib.ldiff_op_dice_ce(logits.data_ptr(), ld, int(n_heads), target.data_ptr(), int(target.dtype == torch.int64), B, H * W, int(bool(batch_dice)),
                                     float(smooth), float(weight), float(grad_scale), loss.data_ptr(), dlogits.data_ptr(), ws.data_ptr(), nb, _sp()))
     return loss[0], dlogits
@@ -675,44 +691,54 @@ class DiceCeFn(torch.autograd.Function):
     `grad_scale` acts as the loss scale of this term and the caller unscales the parameter gradients by 1 / grad_scale (nnunet_train.Trainer.train_step)."""
 
     @staticmethod
-    def forward(ctx, logits, target, n_heads, batch_dice, weight, grad_scale, smooth=1e-5):
-        loss, dlogits = dice_ce(logits, target, n_heads, batch_dice, weight, grad_scale, smooth)
+    def forward(ctx, logits, target, n_heads, batch_dice, weight, grad_scale, smooth=1e-5, ignore_label=None):
+        loss, dlogits = dice_ce(logits, target, n_heads, batch_dice, weight, grad_scale, smooth, ignore_label)
         ctx.save_for_backward(dlogits)
         return loss * float(weight)
 
     @staticmethod
     def backward(ctx, g):
         (dlogits,) = ctx.saved_tensors
-        return (dlogits.float() * g).to(dlogits.dtype), None, None, None, None, None, None
+        return (dlogits.float() * g).to(dlogits.dtype), None, None, None, None, None, None, None
 
 
-def dice_ce_nacc(n_heads):
-    """Doubles per row of the loss statistics: sum_pred, intersect, sum_gt per padded class, the cross-entropy sum, the count of labels outside [0, n_heads)."""
-    return 3 * 8 * ((int(n_heads) + 7) // 8) + 2
+def dice_ce_nacc(n_heads, ignore_label=None):
+    """Doubles per row of the loss statistics: sum_pred, intersect, sum_gt per padded class, the cross-entropy sum, the count of labels outside [0, n_heads)
+    (ignored pixels excepted) and, in the ignore form (ldiff_op_dice_ce_ignore_nacc), the count of annotated pixels."""
+    return 3 * 8 * ((int(n_heads) + 7) // 8) + (2 if ignore_label is None else 3)
 
 
-def dice_ce_stats(logits, target, n_heads, batch_dice, out=None):
+def dice_ce_stats(logits, target, n_heads, batch_dice, out=None, ignore_label=None):
     """ldiff_op_dice_ce_stats: the sums `dice_ce` forms before its coefficients, float64 [1 or B, dice_ce_nacc(n_heads)] on the device (one row with
-    `batch_dice`), added in dice_ce's order.  `out`: a contiguous float64 device tensor of that many elements to write into (a row of a caller's table)."""
+    `batch_dice`), added in dice_ce's order.  `out`: a contiguous float64 device tensor of that many elements to write into (a row of a caller's table).
+    `ignore_label`: the ignore form (ldiff_op_dice_ce_ignore_stats), rows of dice_ce_nacc(n_heads, ignore_label)."""
     lib = _lib.load()
     target, B, H, W, ld = _dice_ce_args(logits, target, "dice_ce_stats")
-    rows, nacc = (1 if batch_dice else B), dice_ce_nacc(n_heads)
+    ignore_label = _ignore_label(ignore_label, n_heads, "dice_ce_stats")
+    rows, nacc = (1 if batch_dice else B), dice_ce_nacc(n_heads, ignore_label)
     if out is None:
         out = torch.empty((rows, nacc), dtype=torch.float64, device=logits.device)
     elif not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == rows * nacc):
         raise ValueError(f"dice_ce_stats: out must be a contiguous float64 CUDA tensor of {rows * nacc} elements")
-    ws, nb = _dice_ce_ws(lib, B, H * W, n_heads, logits.device)
+    ws, nb = _dice_ce_ws(lib, B, H * W, n_heads, logits.device, ignore_label)
+    if ignore_label is not None:
+        _lib.check(lib.ldiff_op_dice_ce_ignore_stats(logits.data_ptr(), ld, int(n_heads), ignore_label, target.data_ptr(), int(target.dtype == torch.int64), B, H * W,
+                                                     int(bool(batch_dice)), out.data_ptr(), ws.data_ptr(), nb, _sp()))
+        return out
     _lib.check(lib.ldiff_op_dice_ce_stats(logits.data_ptr(), ld, int(n_heads), target.data_ptr(), int(target.dtype == torch.int64), B, H * W,
                                           int(bool(batch_dice)), out.data_ptr(), ws.data_ptr(), nb, _sp()))
     return out
 
 
-def dice_ce_from_sums(logits, target, n_heads, batch_dice, dice_sums, local_sums, world=1, weight=1.0, grad_scale=1.0, smooth=1e-5):
+def dice_ce_from_sums(logits, target, n_heads, batch_dice, dice_sums, local_sums, world=1, weight=1.0, grad_scale=1.0, smooth=1e-5, ignore_label=None):
     """ldiff_op_dice_ce_from_sums: (loss, dlogits) as `dice_ce` returns them, the Dice term from `dice_sums` (with `batch_dice` possibly the sum of `world`
-    processes' statistics; its gradient then carries the factor `world`), the cross-entropy from `local_sums` over this process's B H W pixels."""
+    processes' statistics; its gradient then carries the factor `world`), the cross-entropy from `local_sums` over this process's B H W pixels.
+    `ignore_label`: the ignore form (ldiff_op_dice_ce_ignore_from_sums) on `dice_ce_stats(..., ignore_label=)`'s rows: the cross-entropy over this
+    process's annotated pixels.  It is built for one process: world = 1 and `dice_sums` is `local_sums`, anything else raises NotImplementedError."""
     lib = _lib.load()
     target, B, H, W, ld = _dice_ce_args(logits, target, "dice_ce_from_sums")
-    rows, nacc = (1 if batch_dice else B), dice_ce_nacc(n_heads)
+    ignore_label = _ignore_label(ignore_label, n_heads, "dice_ce_from_sums")
+    rows, nacc = (1 if batch_dice else B), dice_ce_nacc(n_heads, ignore_label)
     for name, t in (("dice_sums", dice_sums), ("local_sums", local_sums)):
         if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == rows * nacc):
             raise ValueError(f"dice_ce_from_sums: {name} must be a contiguous float64 CUDA tensor of {rows * nacc} elements")
@@ -720,7 +746,15 @@ def dice_ce_from_sums(logits, target, n_heads, batch_dice, dice_sums, local_sums
         raise ValueError("dice_ce_from_sums: without batch_dice the Dice term is per sample and stays local (world = 1, dice_sums is local_sums)")
     loss = torch.empty(1, dtype=torch.float32, device=logits.device)
     dlogits = torch.empty_like(logits)
-    ws, nb = _dice_ce_ws(lib, B, H * W, n_heads, logits.device)
+    ws, nb = _dice_ce_ws(lib, B, H * W, n_heads, logits.device, ignore_label)
+    if ignore_label is not None:
+        if int(world) != 1 or dice_sums.data_ptr() != local_sums.data_ptr():
+            raise NotImplementedError(f"dice_ce_from_sums(ignore_label={ignore_label}) with the statistics of world = {int(world)} processes: the data-parallel "
+                                      "exchange of the ignore form is not built")
+        _lib.check(lib.ldiff_op_dice_ce_ignore_from_sums(logits.data_ptr(), ld, int(n_heads), ignore_label, target.data_ptr(), int(target.dtype == torch.int64), B,
+                                                         H * W, int(bool(batch_dice)), float(smooth), float(weight), float(grad_scale), local_sums.data_ptr(),
+                                                         loss.data_ptr(), dlogits.data_ptr(), ws.data_ptr(), nb, _sp()))
+        return loss[0], dlogits
     _lib.check(lib.ldiff_op_dice_ce_from_sums(logits.data_ptr(), ld, int(n_heads), target.data_ptr(), int(target.dtype == torch.int64), B, H * W,
                                               int(bool(batch_dice)), float(smooth), float(weight), float(grad_scale), dice_sums.data_ptr(), local_sums.data_ptr(),
                                               int(world), loss.data_ptr(), dlogits.data_ptr(), ws.data_ptr(), nb, _sp()))
@@ -732,12 +766,12 @@ class DiceCeSumsFn(torch.autograd.Function):
     value, stored gradient and backward as DiceCeFn's.  At world = 1 on `dice_ce_stats`' own sums it is DiceCeFn bit for bit."""
 
     @staticmethod
-    def forward(ctx, logits, target, n_heads, batch_dice, dice_sums, local_sums, world, weight, grad_scale, smooth=1e-5):
-        loss, dlogits = dice_ce_from_sums(logits, target, n_heads, batch_dice, dice_sums, local_sums, world, weight, grad_scale, smooth)
+    def forward(ctx, logits, target, n_heads, batch_dice, dice_sums, local_sums, world, weight, grad_scale, smooth=1e-5, ignore_label=None):
+        loss, dlogits = dice_ce_from_sums(logits, target, n_heads, batch_dice, dice_sums, local_sums, world, weight, grad_scale, smooth, ignore_label)
         ctx.save_for_backward(dlogits)
         return loss * float(weight)
 
     @staticmethod
     def backward(ctx, g):
         (dlogits,) = ctx.saved_tensors
-        return (dlogits.float() * g).to(dlogits.dtype), None, None, None, None, None, None, None, None, None
+        return (dlogits.float() * g).to(dlogits.dtype), None, None, None, None, None, None, None, None, None, None

@@ -1206,6 +1206,35 @@ int ldiff_op_dice_ce_from_sums(const void* logits, int ld, int n_heads, const vo
                            (const double*)local_sums, world, (float*)loss, (f16*)dlogits, ws, ws_bytes, (hipStream_t)stream);
   API_END
 }
+int64_t ldiff_op_dice_ce_ignore_ws_bytes(int B, int64_t HW, int n_heads) {
+  if (B < 1 || HW < 1 || n_heads < 2 || n_heads > 32) return 0;
+  return dice_ce_ignore_ws_bytes(B, HW, n_heads);
+}
+int ldiff_op_dice_ce_ignore_nacc(int n_heads) { return (n_heads < 2 || n_heads > 32) ? 0 : dice_ce_ignore_nacc(n_heads); }
+int ldiff_op_dice_ce_ignore(const void* logits, int ld, int n_heads, int ignore_label, const void* target, int target_i64, int B, int64_t HW, int batch_dice,
+                            float smooth, float weight, float grad_scale, void* loss, void* dlogits, void* ws, int64_t ws_bytes, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(logits && target && loss && dlogits && ws, LDIFF_ERR_INVALID, "op_dice_ce_ignore: null argument");
+  launch_dice_ce_ignore((const f16*)logits, ld, n_heads, ignore_label, target, target_i64, B, HW, batch_dice, smooth, weight, grad_scale, (float*)loss, (f16*)dlogits,
+                        ws, ws_bytes, (hipStream_t)stream);
+  API_END
+}
+int ldiff_op_dice_ce_ignore_stats(const void* logits, int ld, int n_heads, int ignore_label, const void* target, int target_i64, int B, int64_t HW, int batch_dice,
+                                  void* sums, void* ws, int64_t ws_bytes, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(logits && target && sums && ws, LDIFF_ERR_INVALID, "op_dice_ce_ignore_stats: null argument");
+  launch_dice_ce_ignore_stats((const f16*)logits, ld, n_heads, ignore_label, target, target_i64, B, HW, batch_dice, (double*)sums, ws, ws_bytes, (hipStream_t)stream);
+  API_END
+}
+int ldiff_op_dice_ce_ignore_from_sums(const void* logits, int ld, int n_heads, int ignore_label, const void* target, int target_i64, int B, int64_t HW,
+                                      int batch_dice, float smooth, float weight, float grad_scale, const void* sums, void* loss, void* dlogits, void* ws,
+                                      int64_t ws_bytes, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(logits && target && sums && loss && dlogits && ws, LDIFF_ERR_INVALID, "op_dice_ce_ignore_from_sums: null argument");
+  launch_dice_ce_ignore_from_sums((const f16*)logits, ld, n_heads, ignore_label, target, target_i64, B, HW, batch_dice, smooth, weight, grad_scale,
+                                  (const double*)sums, (float*)loss, (f16*)dlogits, ws, ws_bytes, (hipStream_t)stream);
+  API_END
+}
 int ldiff_op_bucket_pack(const void* grads, const void* offsets, const void* chunks, int64_t nchunks, void* bucket, void* stream) {
   API_BEGIN
   LDIFF_CHECK(nchunks >= 0 && (nchunks == 0 || (grads && offsets && chunks && bucket)), LDIFF_ERR_INVALID, "op_bucket_pack: bad arguments");
@@ -1308,7 +1337,14 @@ int ldiff_op_case_stats(const void* img, int dtype, int Cc, int H, int W, int64_
 int ldiff_op_case_counts(const void* label_u8, int H, int W, int64_t label_stride, int y0, int y1, int x0, int x1, int n_heads, uint32_t* row_counts, uint32_t* row_prefix,
                          uint32_t* totals, void* stream) {
   API_BEGIN
-  launch_case_counts(label_u8, H, W, label_stride, y0, y1, x0, x1, n_heads, row_counts, row_prefix, totals, (hipStream_t)stream);
+  launch_case_counts(label_u8, H, W, label_stride, y0, y1, x0, x1, n_heads, 0, row_counts, row_prefix, totals, (hipStream_t)stream);
+  API_END
+}
+int ldiff_op_case_counts_classes(const void* label_u8, int H, int W, int64_t label_stride, int y0, int y1, int x0, int x1, int n_heads, int n_classes,
+                                 uint32_t* row_counts, uint32_t* row_prefix, uint32_t* totals, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(n_classes >= 1, LDIFF_ERR_INVALID, "op_case_counts_classes: n_classes %d below 1", n_classes);
+  launch_case_counts(label_u8, H, W, label_stride, y0, y1, x0, x1, n_heads, n_classes, row_counts, row_prefix, totals, (hipStream_t)stream);
   API_END
 }
 int ldiff_op_case_apply(const void* img, int dtype, int Cc, int H, int W, int64_t row_stride, int64_t plane_stride, const void* label_u8, int64_t label_stride, int y0, int y1,

@@ -395,6 +395,16 @@ void launch_dice_ce_stats(const f16* logits, int ld, int n_heads, const void* ta
 void launch_dice_ce_from_sums(const f16* logits, int ld, int n_heads, const void* target, int target_i64, int B, long long HW, int batch_dice, float smooth,
                               float weight, float grad_scale, const double* dice_sums, const double* local_sums, int world, float* loss, f16* dlogits, void* ws,
                               long long ws_bytes, hipStream_t s);
+// the three with nnU-Net's ignore label: pixels carrying it add nothing; rows of dice_ce_ignore_nacc doubles; ws of dice_ce_ignore_ws_bytes
+long long dice_ce_ignore_ws_bytes(int B, long long HW, int n_heads);
+int dice_ce_ignore_nacc(int n_heads);
+void launch_dice_ce_ignore(const f16* logits, int ld, int n_heads, int ignore_label, const void* target, int target_i64, int B, long long HW, int batch_dice,
+                           float smooth, float weight, float grad_scale, float* loss, f16* dlogits, void* ws, long long ws_bytes, hipStream_t s);
+void launch_dice_ce_ignore_stats(const f16* logits, int ld, int n_heads, int ignore_label, const void* target, int target_i64, int B, long long HW, int batch_dice,
+                                 double* sums, void* ws, long long ws_bytes, hipStream_t s);
+void launch_dice_ce_ignore_from_sums(const f16* logits, int ld, int n_heads, int ignore_label, const void* target, int target_i64, int B, long long HW,
+                                     int batch_dice, float smooth, float weight, float grad_scale, const double* sums, float* loss, f16* dlogits, void* ws,
+                                     long long ws_bytes, hipStream_t s);
 // every gradient into one flat buffer in one launch, and the buffer's L2 norm (fixed-order reduction)
 void launch_bucket_pack(const float* const* grads, const long long* offsets, const AdamChunk* chunks, long long nchunks, float* bucket, hipStream_t s);
 long long sumsq_ws_bytes(long long n);
@@ -427,8 +437,9 @@ void launch_case_bbox(const void* img, int dtype, int C, int H, int W, long long
 long long case_stats_ws_bytes(int C);
 void launch_case_stats(const void* img, int dtype, int C, int H, int W, long long row_stride, long long plane_stride, int y0, int y1, int x0, int x1, void* stats,
                        void* ws, long long ws_bytes, hipStream_t s);
-void launch_case_counts(const void* label, int H, int W, long long label_stride, int y0, int y1, int x0, int x1, int n_heads, unsigned* row_counts, unsigned* row_prefix,
-                        unsigned* totals, hipStream_t s);
+// n_classes > 0: one more selector, `label < n_classes` (prefix row n_heads + 1, totals[n_heads + 2]); 0: the plain table
+void launch_case_counts(const void* label, int H, int W, long long label_stride, int y0, int y1, int x0, int x1, int n_heads, int n_classes, unsigned* row_counts,
+                        unsigned* row_prefix, unsigned* totals, hipStream_t s);
 void launch_case_apply(const void* img, int dtype, int C, int H, int W, long long row_stride, long long plane_stride, const void* label, long long label_stride, int y0, int y1,
                        int x0, int x1, const float* sub, const float* div, void* arena, long long arena_bytes, const ldiff_seg_case* row, int write_coef, hipStream_t s);
 void launch_case_rank_to_coord(const void* label, int H, int W, long long label_stride, int y0, int y1, int x0, int x1, int selector, const unsigned* row_prefix,

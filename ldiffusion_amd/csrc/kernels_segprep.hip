@@ -125,7 +125,7 @@ __global__ void case_stats_final_kernel(const StatRec* part, StatRec* out, int C
 struct Lab { const uint8_t* p; long long stride; };
 
 __global__ __launch_bounds__(THREADS) void case_counts_kernel(Lab lab, Box b, int n_heads, unsigned* row_counts) {
-  __shared__ unsigned hist[WAVES][MAX_HEADS + 1];
+  __shared__ unsigned hist[WAVES][MAX_HEADS + 2];   // n_heads + 1 bins; the ignore form counts its label as one more class
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, rows = b.y1 - b.y0, w = b.x1 - b.x0;
   unsigned* h = hist[wave];
   for (int r0 = blockIdx.x * WAVES; r0 < rows; r0 += gridDim.x * WAVES) {      // a wave owns its row and its histogram; uniform trip counts throughout
@@ -154,21 +154,25 @@ __global__ __launch_bounds__(THREADS) void case_counts_kernel(Lab lab, Box b, in
 }
 
 // selector s in [0, n_heads): label == s; s == n_heads: label > 0 (labels >= n_heads included: the caller refuses such a case before it asks).
-// prefix[s, r] = number of selected pixels in rows [0, r) of the box, r = 0 .. rows; totals[s] = prefix[s, rows]; totals[n_heads + 1] = labels >= n_heads
-__global__ __launch_bounds__(THREADS) void case_prefix_kernel(const unsigned* row_counts, int rows, int n_heads, unsigned* prefix, unsigned* totals) {
+// prefix[s, r] = number of selected pixels in rows [0, r) of the box, r = 0 .. rows; totals[s] = prefix[s, rows]; totals[n_heads + 1] = labels >= n_heads.
+// A grid of n_heads + 3 workgroups adds the selector `label < n_classes` ("the label is a class" of a map whose highest value is an ignore label):
+// prefix row n_heads + 1, totals[n_heads + 2].
+__global__ __launch_bounds__(THREADS) void case_prefix_kernel(const unsigned* row_counts, int rows, int n_heads, int n_classes, unsigned* prefix, unsigned* totals) {
   __shared__ unsigned sh[THREADS];
   __shared__ unsigned carry;
   const int s = blockIdx.x, tid = threadIdx.x, nb = n_heads + 1;
   if (tid == 0) carry = 0;
   __syncthreads();
-  unsigned* out = prefix + (long long)s * (rows + 1);
+  const bool has_row = s <= n_heads || s == n_heads + 2;
+  unsigned* out = prefix + (long long)(s <= n_heads ? s : n_heads + 1) * (rows + 1);
   for (int r0 = 0; r0 < rows; r0 += THREADS) {
     const int r = r0 + tid;
     unsigned v = 0;
     if (r < rows) {
       if (s < n_heads) v = row_counts[(long long)r * nb + s];
       else if (s == n_heads) { for (int c = 1; c < nb; ++c) v += row_counts[(long long)r * nb + c]; }
-      else v = row_counts[(long long)r * nb + n_heads];
+      else if (s == n_heads + 1) v = row_counts[(long long)r * nb + n_heads];
+      else { for (int c = 0; c < n_classes; ++c) v += row_counts[(long long)r * nb + c]; }
     }
     sh[tid] = v;
     __syncthreads();
@@ -179,13 +183,13 @@ __global__ __launch_bounds__(THREADS) void case_prefix_kernel(const unsigned* ro
       __syncthreads();
     }
     const unsigned base = carry;
-    if (r < rows && s <= n_heads) out[r] = base + sh[tid] - v;
+    if (r < rows && has_row) out[r] = base + sh[tid] - v;
     __syncthreads();
     if (tid == THREADS - 1) carry = base + sh[tid];
     __syncthreads();
   }
   if (tid == 0) {
-    if (s <= n_heads) out[rows] = carry;
+    if (has_row) out[rows] = carry;
     totals[s] = carry;
   }
 }
@@ -219,7 +223,7 @@ __global__ __launch_bounds__(THREADS) void case_apply_kernel(ApplyParams q) {
 
 // ---- (e) rank to coordinate -------------------------------------------------------------------------------------------------------------------
 struct RankParams {
-  Lab lab; Box b; int selector;            // >= 0: label == selector; < 0: label > 0
+  Lab lab; Box b; int selector;            // >= 0: label == selector; -1: label > 0; -1 - m: label < m
   const unsigned* prefix;                  // [rows + 1]
   const long long* ranks; long long n;
   int* coords;                             // [n, 2]
@@ -244,7 +248,7 @@ __global__ __launch_bounds__(THREADS) void case_rank_kernel(RankParams q) {
       const uint8_t* p = q.lab.p + (long long)(q.b.y0 + row) * q.lab.stride + q.b.x0;
       for (int x0 = 0; x0 < w; x0 += 64) {
         bool sel = false;
-        if (x0 + lane < w) { const int v = p[x0 + lane]; sel = q.selector >= 0 ? v == q.selector : v > 0; }
+        if (x0 + lane < w) { const int v = p[x0 + lane]; sel = q.selector >= 0 ? v == q.selector : q.selector == -1 ? v > 0 : v < -1 - q.selector; }
         const unsigned long long m = __ballot(sel);
         const unsigned cnt = (unsigned)__popcll(m);
         if (k < cnt) {
@@ -326,10 +330,12 @@ void launch_case_stats(const void* img, int dtype, int C, int H, int W, long lon
   HIP_CHECK(hipGetLastError());
 }
 
-void launch_case_counts(const void* label, int H, int W, long long label_stride, int y0, int y1, int x0, int x1, int n_heads, unsigned* row_counts, unsigned* row_prefix,
-                        unsigned* totals, hipStream_t s) {
+void launch_case_counts(const void* label, int H, int W, long long label_stride, int y0, int y1, int x0, int x1, int n_heads, int n_classes, unsigned* row_counts,
+                        unsigned* row_prefix, unsigned* totals, hipStream_t s) {
   LDIFF_CHECK(H >= 1 && W >= 1 && H <= 32768 && W <= 32768, LDIFF_ERR_INVALID, "case_counts: extent %d x %d out of range [1,32768]", H, W);
-  LDIFF_CHECK(n_heads >= 1 && n_heads <= MAX_HEADS, LDIFF_ERR_INVALID, "case_counts: n_heads %d out of range [1,%d]", n_heads, MAX_HEADS);
+  const int max_heads = MAX_HEADS + (n_classes > 0 ? 1 : 0);   // with the class selector the ignore label may be counted as one more class
+  LDIFF_CHECK(n_heads >= 1 && n_heads <= max_heads, LDIFF_ERR_INVALID, "case_counts: n_heads %d out of range [1,%d]", n_heads, max_heads);
+  LDIFF_CHECK(n_classes >= 0 && n_classes <= n_heads, LDIFF_ERR_INVALID, "case_counts: n_classes %d out of range [1,%d]", n_classes, n_heads);
   const Lab lab = checked_lab("case_counts", label, W, label_stride);
   const Box b = checked_box("case_counts", H, W, y0, y1, x0, x1);
   LDIFF_CHECK(row_counts && row_prefix && totals, LDIFF_ERR_INVALID, "case_counts: null output");
@@ -339,7 +345,7 @@ void launch_case_counts(const void* label, int H, int W, long long label_stride,
   ProfScope prof("case_counts", 0.0, (double)rows * (x1 - x0), s);
   const int grid = (rows + WAVES - 1) / WAVES;
   hipLaunchKernelGGL(case_counts_kernel, dim3(grid < 1024 ? grid : 1024), dim3(THREADS), 0, s, lab, b, n_heads, row_counts);
-  hipLaunchKernelGGL(case_prefix_kernel, dim3(n_heads + 2), dim3(THREADS), 0, s, row_counts, rows, n_heads, row_prefix, totals);
+  hipLaunchKernelGGL(case_prefix_kernel, dim3(n_heads + 2 + (n_classes > 0 ? 1 : 0)), dim3(THREADS), 0, s, row_counts, rows, n_heads, n_classes, row_prefix, totals);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -377,7 +383,8 @@ void launch_case_rank_to_coord(const void* label, int H, int W, long long label_
                                hipStream_t s) {
   LDIFF_CHECK(H >= 1 && W >= 1 && H <= 32768 && W <= 32768, LDIFF_ERR_INVALID, "case_rank_to_coord: extent %d x %d out of range [1,32768]", H, W);
   LDIFF_CHECK(n >= 0, LDIFF_ERR_INVALID, "case_rank_to_coord: negative n");
-  LDIFF_CHECK(selector >= -1 && selector < 256, LDIFF_ERR_INVALID, "case_rank_to_coord: selector %d (a class 0..255, or -1 for label > 0)", selector);
+  LDIFF_CHECK(selector >= -256 && selector < 256, LDIFF_ERR_INVALID, "case_rank_to_coord: selector %d (a class 0..255, -1 for label > 0, -1 - m for label < m <= 255)",
+              selector);
   if (n == 0) return;
   RankParams q{};
   q.lab = checked_lab("case_rank_to_coord", label, W, label_stride);

@@ -408,6 +408,191 @@ void dce_from_sums_launch(const f16* logits, const void* target, int i64, int B,
   HIP_CHECK(hipGetLastError());
 }
 
+// ---- the ignore form: DC_and_CE_loss(ignore_label = k) -----------------------------------------------------------------------------------------------
+// A pixel whose label is `ignore` takes no part: none of the four accumulators sees it, its logits are never loaded, its dlogits row is +0.  The partial
+// row gains one slot, the count of annotated pixels (NACC = 3 * 8 NV + 3; the bad-label slot keeps its place); the cross-entropy is the sum over annotated
+// pixels over their count -- this process's own -- and 0 when there is none, and the finalize leaves 1 / count (0 for count 0) as a device scalar for the
+// gradient kernel.  These are kernels of their own, so the plain form's code is what it was; every statement that forms a value is the plain form's, in
+// its order, and the count of a batch without an ignored pixel is the integer B HW, so that batch gives the plain form's bits.
+inline int dce_nacc_ign(int NV) { return 3 * 8 * NV + 3; }
+
+template <int NV>
+__global__ __launch_bounds__(256) void dce_partial_ign_kernel(const f16* __restrict__ logits, const void* __restrict__ target, int i64, long long HW, int n,
+                                                              int ignore, float* __restrict__ part) {
+  constexpr int NC = 8 * NV, NACC = 3 * NC + 3;
+  __shared__ float red[4][NACC];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const long long p0 = (long long)blockIdx.x * DCE_PIX, p1 = p0 + DCE_PIX < HW ? p0 + DCE_PIX : HW;
+  float sp[NC], si[NC], sg[NC], ce = 0.f, bad = 0.f, ann = 0.f;
+#pragma unroll
+  for (int k = 0; k < NC; ++k) sp[k] = si[k] = sg[k] = 0.f;
+  for (long long px = p0 + tid; px < p1; px += 256) {
+    const long long at = (long long)b * HW + px;
+    const int t = dce_label(target, i64, at);
+    if (t == ignore) continue;
+    float v[NC], p[NC], lse, mx;
+    dce_softmax<NV>(logits + at * NC, n, v, p, lse, mx);
+    if (t >= n) { bad += 1.f; continue; }
+    ann += 1.f;
+    float vt = 0.f;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+      const bool hit = k == t;
+      sp[k] += p[k];
+      si[k] += hit ? p[k] : 0.f;
+      sg[k] += hit ? 1.f : 0.f;
+      vt = hit ? v[k] : vt;
+    }
+    ce += lse + mx - vt;
+  }
+  const int lane = tid & 63, w = tid >> 6;
+  auto wsum = [](float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+  };
+#pragma unroll
+  for (int k = 0; k < NC; ++k) {
+    const float a = wsum(sp[k]), c = wsum(si[k]), d = wsum(sg[k]);
+    if (lane == 0) { red[w][k] = a; red[w][NC + k] = c; red[w][2 * NC + k] = d; }
+  }
+  ce = wsum(ce); bad = wsum(bad); ann = wsum(ann);
+  if (lane == 0) { red[w][3 * NC] = ce; red[w][3 * NC + 1] = bad; red[w][3 * NC + 2] = ann; }
+  __syncthreads();
+  if (tid < NACC) part[((long long)b * gridDim.x + blockIdx.x) * NACC + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+}
+
+// dce_coef_loss for one process (world = 1, the Dice sums are the local ones: the data-parallel exchange of the ignore form is not built) with the
+// cross-entropy over the annotated count (exact: every partial count is an integer below 2^24, added in double), which also leaves as
+// inv_count[0] = (float)(1 / count), or 0 where no pixel of the batch is annotated.  The Dice sums saw annotated pixels only.
+__device__ __forceinline__ void dce_coef_loss_ign(const double* sums, int B, int n, int NC, int batch_dice, float smooth, double* dcs, float* __restrict__ coef,
+                                                  float* __restrict__ loss, float* __restrict__ inv_count) {
+  const int NACC = 3 * NC + 3, Bd = batch_dice ? 1 : B, tid = threadIdx.x;
+  const double M = (double)Bd * (double)(n - 1);
+  for (int e = tid; e < Bd * NC; e += 256) {
+    const int bo = e / NC, c = e - bo * NC;
+    double dc = 0.0, c0 = 0.0, c1 = 0.0;
+    if (c >= 1 && c < n) {
+      const double* s = sums + (long long)bo * NACC;
+      const double D = s[2 * NC + c] + s[c] + (double)smooth, N = 2.0 * s[NC + c] + (double)smooth;
+      const double Dc = D < 1e-8 ? 1e-8 : D;
+      dc = N / Dc;
+      c0 = 2.0 / (Dc * M);
+      c1 = D < 1e-8 ? 0.0 : N / (D * D * M);
+    }
+    dcs[e] = dc;
+    coef[(long long)e * 2] = (float)c0;   // the plain form's c0 * world at world = 1 (x 1.0 is exact)
+    coef[(long long)e * 2 + 1] = (float)c1;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double dsum = 0.0, ce = 0.0, bad = 0.0, count = 0.0;
+    for (int e = 0; e < Bd * NC; ++e) dsum += dcs[e];
+    for (int bo = 0; bo < Bd; ++bo) {
+      ce += sums[(long long)bo * NACC + 3 * NC];
+      bad += sums[(long long)bo * NACC + 3 * NC + 1];
+      count += sums[(long long)bo * NACC + 3 * NC + 2];
+    }
+    const double v = (count > 0.0 ? ce / count : 0.0) - dsum / M;
+    loss[0] = bad > 0.0 ? __builtin_nanf("") : (float)v;
+    inv_count[0] = count > 0.0 ? (float)(1.0 / count) : 0.f;
+  }
+}
+
+__global__ __launch_bounds__(256) void dce_finalize_ign_kernel(const float* __restrict__ part, int chunks, int B, int n, int NC, int batch_dice, float smooth,
+                                                               double* sums, double* dcs, float* __restrict__ coef, float* __restrict__ loss,
+                                                               float* __restrict__ inv_count) {
+  dce_reduce_sums(part, chunks, B, 3 * NC + 3, batch_dice, sums);
+  __syncthreads();
+  dce_coef_loss_ign(sums, B, n, NC, batch_dice, smooth, dcs, coef, loss, inv_count);
+}
+
+__global__ __launch_bounds__(256) void dce_from_sums_ign_kernel(const double* sums, int B, int n, int NC, int batch_dice, float smooth, double* dcs,
+                                                                float* __restrict__ coef, float* __restrict__ loss, float* __restrict__ inv_count) {
+  dce_coef_loss_ign(sums, B, n, NC, batch_dice, smooth, dcs, coef, loss, inv_count);
+}
+
+// dce_grad_kernel's row for an annotated pixel, with 1 / count read from the finalize's scalar; for an ignored one the zero row is selected by the label
+// alone, ahead of the logits' load
+template <int NV>
+__global__ __launch_bounds__(256) void dce_grad_ign_kernel(const f16* __restrict__ logits, const void* __restrict__ target, int i64, long long HW, int n,
+                                                           int ignore, int batch_dice, const float* __restrict__ coef,
+                                                           const float* __restrict__ inv_count_p, float gsw, f16* __restrict__ dlogits) {
+  constexpr int NC = 8 * NV;
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const long long p0 = (long long)blockIdx.x * DCE_PIX, p1 = p0 + DCE_PIX < HW ? p0 + DCE_PIX : HW;
+  float c0[NC], c1[NC];
+  const float* cf = coef + (long long)(batch_dice ? 0 : b) * NC * 2;
+#pragma unroll
+  for (int k = 0; k < NC; ++k) { c0[k] = cf[2 * k]; c1[k] = cf[2 * k + 1]; }
+  const float inv_count = inv_count_p[0];
+  for (long long px = p0 + tid; px < p1; px += 256) {
+    const long long at = (long long)b * HW + px;
+    const int t = dce_label(target, i64, at);
+    if (t == ignore) {
+      f16x8 z;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) z[j] = (f16)0.f;
+#pragma unroll
+      for (int q = 0; q < NV; ++q) *reinterpret_cast<f16x8*>(dlogits + at * NC + 8 * q) = z;
+      continue;
+    }
+    float v[NC], p[NC], lse, mx;
+    dce_softmax<NV>(logits + at * NC, n, v, p, lse, mx);
+    const float poison = t >= n ? __builtin_nanf("") : 0.f;
+    float g[NC], dot = 0.f;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+      g[k] = c1[k] - (k == t ? c0[k] : 0.f);
+      dot += p[k] * g[k];
+    }
+#pragma unroll
+    for (int q = 0; q < NV; ++q) {
+      f16x8 o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int k = 8 * q + j;
+        const float d = (p[k] - (k == t ? 1.f : 0.f)) * inv_count + p[k] * (g[k] - dot);
+        o[j] = (f16)(k < n ? gsw * d + poison : 0.f);
+      }
+      *reinterpret_cast<f16x8*>(dlogits + at * NC + 8 * q) = o;
+    }
+  }
+}
+
+template <int NV>
+void dce_ign_launch(const f16* logits, const void* target, int i64, int B, long long HW, int n, int ignore, int batch_dice, float smooth, float gsw, float* loss,
+                    f16* dlogits, double* sums, double* dcs, float* coef, float* inv_count, float* part, hipStream_t s) {
+  const int chunks = (int)((HW + DCE_PIX - 1) / DCE_PIX);
+  const dim3 grid(chunks, B);
+  hipLaunchKernelGGL(dce_partial_ign_kernel<NV>, grid, dim3(256), 0, s, logits, target, i64, HW, n, ignore, part);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(dce_finalize_ign_kernel, dim3(1), dim3(256), 0, s, part, chunks, B, n, 8 * NV, batch_dice, smooth, sums, dcs, coef, loss, inv_count);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(dce_grad_ign_kernel<NV>, grid, dim3(256), 0, s, logits, target, i64, HW, n, ignore, batch_dice, coef, inv_count, gsw, dlogits);
+  HIP_CHECK(hipGetLastError());
+}
+
+template <int NV>
+void dce_ign_stats_launch(const f16* logits, const void* target, int i64, int B, long long HW, int n, int ignore, int batch_dice, double* sums_out, float* part,
+                          hipStream_t s) {
+  const int chunks = (int)((HW + DCE_PIX - 1) / DCE_PIX);
+  hipLaunchKernelGGL(dce_partial_ign_kernel<NV>, dim3(chunks, B), dim3(256), 0, s, logits, target, i64, HW, n, ignore, part);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(dce_reduce_kernel, dim3(1), dim3(256), 0, s, part, chunks, B, dce_nacc_ign(NV), batch_dice, sums_out);
+  HIP_CHECK(hipGetLastError());
+}
+
+template <int NV>
+void dce_ign_from_sums_launch(const f16* logits, const void* target, int i64, int B, long long HW, int n, int ignore, int batch_dice, float smooth, float gsw,
+                              const double* sums, float* loss, f16* dlogits, double* dcs, float* coef, float* inv_count, hipStream_t s) {
+  const int chunks = (int)((HW + DCE_PIX - 1) / DCE_PIX);
+  hipLaunchKernelGGL(dce_from_sums_ign_kernel, dim3(1), dim3(256), 0, s, sums, B, n, 8 * NV, batch_dice, smooth, dcs, coef, loss, inv_count);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(dce_grad_ign_kernel<NV>, dim3(chunks, B), dim3(256), 0, s, logits, target, i64, HW, n, ignore, batch_dice, coef, inv_count, gsw, dlogits);
+  HIP_CHECK(hipGetLastError());
+}
+
 // ---- SGD with Nesterov momentum, every tensor in one launch ----------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void sgd_nesterov_multi_kernel(const SgdTensor* __restrict__ tensors, const float* const* __restrict__ grads,
                                                                  const AdamChunk* __restrict__ chunks, float lr, float momentum, float wd, int first,
@@ -617,6 +802,63 @@ void launch_dice_ce_from_sums(const f16* logits, int ld, int n_heads, const void
   dce_dispatch(w.NV, [&](auto nv) {
     dce_from_sums_launch<decltype(nv)::value>(logits, target, target_i64, B, HW, n_heads, batch_dice, smooth, weight * grad_scale, dice_sums, local_sums, world, loss,
                                               dlogits, w.dcs, w.coef, s);
+  });
+}
+
+// The ignore form's workspace: DceWs's four arrays at the wider row, then the 1 / count scalar.
+struct DceIgnWs {
+  int NV;
+  double *sums, *dcs;
+  float *coef, *inv_count, *part;
+  long long bytes;
+  DceIgnWs(void* ws, int B, long long HW, int n_heads) : NV((n_heads + 7) / 8) {
+    const int NC = 8 * NV, NACC = dce_nacc_ign(NV);
+    const long long chunks = (HW + DCE_PIX - 1) / DCE_PIX;
+    sums = (double*)ws;
+    dcs = sums + (long long)B * NACC;
+    coef = (float*)(dcs + (long long)B * NC);
+    inv_count = coef + (long long)B * NC * 2;
+    part = inv_count + 1;
+    bytes = ((long long)B * NACC + (long long)B * NC) * 8 + ((long long)B * NC * 2 + 1 + (long long)B * chunks * NACC) * 4;
+  }
+};
+
+long long dice_ce_ignore_ws_bytes(int B, long long HW, int n_heads) { return DceIgnWs(nullptr, B, HW, n_heads).bytes; }
+int dice_ce_ignore_nacc(int n_heads) { return dce_nacc_ign((n_heads + 7) / 8); }
+
+static DceIgnWs dice_ce_ignore_check(const char* what, int ld, int n_heads, int ignore_label, int B, long long HW, void* ws, long long ws_bytes) {
+  dice_ce_check(what, ld, n_heads, B, HW, ws, 1ll << 62);   // the shape rules of the plain form; the workspace is this form's own
+  LDIFF_CHECK(ignore_label >= n_heads && ignore_label <= 254, LDIFF_ERR_INVALID,
+              "%s: ignore label %d (n_heads = %d .. 254: no class, and not 255, which every int64 label outside a byte's range is read as)", what, ignore_label, n_heads);
+  const DceIgnWs w(ws, B, HW, n_heads);
+  LDIFF_CHECK(ws_bytes >= w.bytes, LDIFF_ERR_INVALID, "%s: workspace of %lld bytes, %lld needed (ldiff_op_dice_ce_ignore_ws_bytes)", what, ws_bytes, w.bytes);
+  return w;
+}
+
+void launch_dice_ce_ignore(const f16* logits, int ld, int n_heads, int ignore_label, const void* target, int target_i64, int B, long long HW, int batch_dice,
+                           float smooth, float weight, float grad_scale, float* loss, f16* dlogits, void* ws, long long ws_bytes, hipStream_t s) {
+  const DceIgnWs w = dice_ce_ignore_check("dice_ce_ignore", ld, n_heads, ignore_label, B, HW, ws, ws_bytes);
+  dce_dispatch(w.NV, [&](auto nv) {
+    dce_ign_launch<decltype(nv)::value>(logits, target, target_i64, B, HW, n_heads, ignore_label, batch_dice, smooth, weight * grad_scale, loss, dlogits, w.sums, w.dcs,
+                                        w.coef, w.inv_count, w.part, s);
+  });
+}
+
+void launch_dice_ce_ignore_stats(const f16* logits, int ld, int n_heads, int ignore_label, const void* target, int target_i64, int B, long long HW, int batch_dice,
+                                 double* sums, void* ws, long long ws_bytes, hipStream_t s) {
+  const DceIgnWs w = dice_ce_ignore_check("dice_ce_ignore_stats", ld, n_heads, ignore_label, B, HW, ws, ws_bytes);
+  dce_dispatch(w.NV, [&](auto nv) {
+    dce_ign_stats_launch<decltype(nv)::value>(logits, target, target_i64, B, HW, n_heads, ignore_label, batch_dice, sums, w.part, s);
+  });
+}
+
+void launch_dice_ce_ignore_from_sums(const f16* logits, int ld, int n_heads, int ignore_label, const void* target, int target_i64, int B, long long HW,
+                                     int batch_dice, float smooth, float weight, float grad_scale, const double* sums, float* loss, f16* dlogits, void* ws,
+                                     long long ws_bytes, hipStream_t s) {
+  const DceIgnWs w = dice_ce_ignore_check("dice_ce_ignore_from_sums", ld, n_heads, ignore_label, B, HW, ws, ws_bytes);
+  dce_dispatch(w.NV, [&](auto nv) {
+    dce_ign_from_sums_launch<decltype(nv)::value>(logits, target, target_i64, B, HW, n_heads, ignore_label, batch_dice, smooth, weight * grad_scale, sums, loss,
+                                                  dlogits, w.dcs, w.coef, w.inv_count, s);
   });
 }
 

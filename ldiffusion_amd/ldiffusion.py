@@ -20,7 +20,7 @@ from .segmentor import Segmentor
 
 def parse_args(argv=None):
     """ldiffusion.py:19-29: the reference's eight flags, plus --level, --component and --ldiffusion-weight (the reference hard-codes them in its
-    `__main__`, :330-331)."""
+    `__main__`, :330-331), and --ignore-pixel, the grey level of unlabelled pixels in partly annotated tissue labels (not given: fully annotated)."""
     parser = argparse.ArgumentParser(description="Diffusion model training parameters")
     parser.add_argument("--local_rank", type=int, default=int(os.environ.get("LOCAL_RANK", -1)))
     parser.add_argument("--diffusion-path", type=str, required=True, help="stable diffusion base model path")
@@ -33,6 +33,7 @@ def parse_args(argv=None):
     parser.add_argument("--level", type=str, default="tissue", choices=("tissue", "cell"))
     parser.add_argument("--component", type=str, default="all", choices=("all", "ldiffusion", "segmentor"))
     parser.add_argument("--ldiffusion-weight", type=str, default=None, help="trained L-Diffusion weights, for --component segmentor")
+    parser.add_argument("--ignore-pixel", type=int, default=None, help="grey level of unlabelled pixels in the label images (tissue level): nnU-Net's ignore label")
     return parser.parse_args(argv)
 
 
@@ -195,7 +196,8 @@ class LDiffusionModel:
         torch.cuda.empty_cache()
         return save_path
 
-    def train(self, args, component="all", ldiffusion_weight=None, train_loader=None, val_loader=None, wgrad_route=None, cell_weights=None, instances=None, **_ignored):
+    def train(self, args, component="all", ldiffusion_weight=None, train_loader=None, val_loader=None, wgrad_route=None, cell_weights=None, instances=None,
+              ignore_pixel=None, **_ignored):
         """ldiffusion.py:297-315.  The loaders are injected (`train_loader=`, `val_loader=`), or, with none injected and `args` carrying `image_dir` and
         `label_dir`, built as the reference builds them (`self.load_data(args.image_dir, args.label_dir, args.batch_size)`, with `args.image_size` (1024) and
         `args.io_workers` (4) where present): device-resident for the warm-up, plain host loaders when only the segmentor stage runs (it reads their file lists).
@@ -205,7 +207,9 @@ class LDiffusionModel:
         folder; loaders without such a dataset (plain lists of batches) need the four lists as keyword arguments `train_images`, `train_labels`,
         `test_images`, `test_labels`.  `iterations_per_epoch`, `val_iterations` and `num_foreground_voxels` are handed on too, and so is `wgrad_route`
         (the route of the tissue trainer's weight gradients, `nnunet_train.Trainer`'s keyword; None: its default), and `batch_images` / `io_workers` (the
-        batched dataset pass, `utils.create_nnunet_dataset`'s keywords; not given: the per-image pass).  At level "cell" it is
+        batched dataset pass, `utils.create_nnunet_dataset`'s keywords; not given: the per-image pass), and `ignore_pixel` (else `args.ignore_pixel` where
+        present; None: fully annotated labels): the grey level of unlabelled pixels, which the tissue stage trains around as nnU-Net's ignore label
+        (`Segmentor.train_tissue_model_nnUNetv2`'s keyword; the warm-up reads such pixels as background, as it reads every unmapped level).  At level "cell" it is
         `Segmentor.train_cell_model(args.num_epochs - 10, ldiffusion_weight, args.diffusion_path, cell_weights=..., instances=...)` (:312-313) and returns
         the folder that holds cellclassifier.pth (None when no epoch validated above 0.0).  `cell_weights` = the CellSegClassifier state dict (or its path)
         the stage starts from: the reference starts from torchvision's ImageNet weights, which it downloads, and this build downloads nothing -- without
@@ -252,6 +256,10 @@ class LDiffusionModel:
                                         test_images=val_loader.dataset.image_dir, test_labels=val_loader.dataset.label_dir)
             if wgrad_route is not None:   # None: the call is the one of before the keyword existed
                 segmentor_kwargs["wgrad_route"] = wgrad_route
+            if ignore_pixel is None:
+                ignore_pixel = getattr(args, "ignore_pixel", None)
+            if ignore_pixel is not None:
+                segmentor_kwargs["ignore_pixel"] = ignore_pixel
             return segmentor.train_tissue_model_nnUNetv2(args.num_epochs - 10, ldiffusion_weight, args.diffusion_path, **segmentor_kwargs)
         return ldiffusion_weight
 

@@ -53,9 +53,27 @@ def resolve_configuration(plans: dict, name: str) -> dict:
     return out
 
 
-def network_spec(plans: dict, configuration_name: str, dataset_json: dict) -> dict:
+def label_spec(labels: dict) -> Tuple[int, Optional[int]]:
+    """(n_heads, ignore_label) of a dataset.json `labels` mapping, by LabelManager's rules (label_handling.py:35-45, 101-106): the optional entry
+    `"ignore"` must be an integer and the highest value, max(all other labels) + 1 -- with consecutive labels their number, so it is the first value
+    the network has no head for; `n_heads` leaves it out.  Regions, and an ignore entry that breaks the rule, are refused naming the field."""
+    if any(isinstance(v, (list, tuple)) for v in labels.values()):
+        _refuse("labels", "defines regions")
+    if "ignore" not in labels:
+        return len(labels), None
+    k, n_heads = labels["ignore"], len(labels) - 1
+    if isinstance(k, bool) or not isinstance(k, int):
+        _refuse("labels", f"has an ignore label that is not an integer: {k!r}")
+    if k != n_heads:
+        _refuse("labels", f"has the ignore label {k}, which is not the highest value, the number of other labels {n_heads}")
+    return n_heads, k
+
+
+def network_spec(plans: dict, configuration_name: str, dataset_json: dict, accept_ignore: bool = False) -> dict:
     """The layer list of the network `get_network_from_plans` would build, plus what the sliding window and the preprocessing need.
-    Refuses, naming the field, whatever the HIP head does not cover."""
+    Refuses, naming the field, whatever the HIP head does not cover.  `accept_ignore`: a dataset with an ignore label (`label_spec`) is taken and
+    adds `ignore_label` to the spec; `n_heads` never counts it, so no head can predict it.  Off, the default, such a dataset is refused as it always
+    was: a caller that has not asked for the label would train on it as a class of its own."""
     cfg = resolve_configuration(plans, configuration_name)
     if cfg.get("UNet_class_name") != "PlainConvUNet":
         _refuse("UNet_class_name", f"is {cfg.get('UNet_class_name')!r}")
@@ -82,11 +100,9 @@ def network_spec(plans: dict, configuration_name: str, dataset_json: dict) -> di
     for s in schemes:
         if s not in NORMALIZATIONS:
             _refuse("normalization_schemes", f"names {s!r}")
-    labels = dataset_json["labels"]
-    if any(isinstance(v, (list, tuple)) for v in labels.values()):
-        _refuse("labels", "defines regions")
-    if "ignore" in labels:
-        _refuse("labels", "defines an ignore label")
+    n_heads, ignore_label = label_spec(dataset_json["labels"])
+    if ignore_label is not None and not accept_ignore:
+        _refuse("labels", "defines an ignore label (network_spec(accept_ignore=True) takes it)")
     channels = dataset_json["channel_names"] if "channel_names" in dataset_json else dataset_json["modality"]
     in_channels = len(channels)
     if len(schemes) != in_channels:
@@ -104,8 +120,11 @@ def network_spec(plans: dict, configuration_name: str, dataset_json: dict) -> di
         div *= s
     if len(patch) != 2 or any(p % div for p in patch):
         _refuse("patch_size", f"{patch} is not divisible by the product of the strides, {div}")
-    return dict(in_channels=in_channels, n_stages=n_stages, features=features, strides=strides, n_conv_encoder=nce, n_conv_decoder=ncd,
-                n_heads=len(labels), patch_size=tuple(patch), normalization_schemes=schemes)
+    spec = dict(in_channels=in_channels, n_stages=n_stages, features=features, strides=strides, n_conv_encoder=nce, n_conv_decoder=ncd,
+                n_heads=n_heads, patch_size=tuple(patch), normalization_schemes=schemes)
+    if ignore_label is not None:
+        spec["ignore_label"] = ignore_label
+    return spec
 
 
 def param_shapes(spec: dict, deep_supervision: bool = False) -> Dict[str, Tuple[int, ...]]:
@@ -273,7 +292,7 @@ def read_trained_model_folder(model_dir: str, fold=0, checkpoint_name: str = "ch
     with open(os.path.join(model_dir, "plans.json")) as f:
         plans = json.load(f)
     ckpt = torch.load(os.path.join(model_dir, f"fold_{fold}", checkpoint_name), map_location="cpu", weights_only=False)
-    spec = network_spec(plans, ckpt["init_args"]["configuration"], dataset_json)
+    spec = network_spec(plans, ckpt["init_args"]["configuration"], dataset_json, accept_ignore=True)   # the network has no head for it: inference is the same
     sd = clean_state_dict(ckpt["network_weights"], spec)
     check_state_dict(sd, spec)
     return spec, sd, ckpt.get("inference_allowed_mirroring_axes")

@@ -21,7 +21,8 @@ Order of draws (ours; `numpy.random`'s legacy stream is not reproduced).  Per sa
 `train`:
     1. integers: the case index
     2. integers: the class among those present, then the voxel among its recorded locations (a forced sample of a case with foreground), or the crop's
-       first row, then its first column (every other sample)
+       first row, then its first column (every other sample).  A store with an ignore label (get_bbox, base_data_loader.py:84-135): a sample that is
+       not forced draws ONE voxel among the case's annotated locations instead, and row and column only when the case has none
     3. random(8): rotation gate, angle; scale gate, coin, scale below 1, scale above 1; mirror of axis 0, of axis 1
     4. random(2): noise gate, noise sigma;  integers: the Philox offset
     5. random(5): the per-sample gates of blur, brightness, contrast, gamma on -x, gamma
@@ -124,17 +125,26 @@ def _target_num_samples(count: int) -> int:
     return max(min(10000, count), int(np.ceil(count * 0.01)))
 
 
-def sample_foreground_locations(seg: np.ndarray, classes: Sequence[int], seed: int = 1234) -> dict:
+def annotated_key(n_heads: int) -> Tuple[int, ...]:
+    """The key of the annotated pixels in `class_locations` of a dataset with an ignore label: tuple(LabelManager.all_labels), every class, background
+    included (default_preprocessor.py:99-102; nnUNetDataLoaderBase.annotated_classes_key)."""
+    return tuple(range(int(n_heads)))
+
+
+def sample_foreground_locations(seg: np.ndarray, classes: Sequence[int], seed: int = 1234, annotated: Optional[int] = None) -> dict:
     """DefaultPreprocessor._sample_foreground_locations (default_preprocessor.py:152-178) for plain labels of one [H, W] map: per class a subset of
-    np.argwhere(seg == c) chosen without replacement by ONE RandomState(seed) walked through the classes in order; an absent class gets []."""
+    np.argwhere(seg == c) chosen without replacement by ONE RandomState(seed) walked through the classes in order; an absent class gets [].
+    `annotated` = n_heads of a dataset with an ignore label: one more entry after the classes, key `annotated_key(n_heads)`, drawn by the same
+    walk from the pixels of any class 0 .. n_heads - 1 (:99-102), so the entries before it are what they are without it."""
     rndst = np.random.RandomState(seed)
     out = {}
-    for c in classes:
-        locs = np.argwhere(seg == c)
+    for c in list(classes) + ([annotated_key(annotated)] if annotated is not None else []):
+        key = c if isinstance(c, tuple) else int(c)
+        locs = np.argwhere(np.isin(seg, c) if isinstance(c, tuple) else seg == c)
         if len(locs) == 0:
-            out[int(c)] = []
+            out[key] = []
             continue
-        out[int(c)] = locs[rndst.choice(len(locs), _target_num_samples(len(locs)), replace=False)]
+        out[key] = locs[rndst.choice(len(locs), _target_num_samples(len(locs)), replace=False)]
     return out
 
 
@@ -143,7 +153,9 @@ class CaseStore:
     differ.  Each image is normalised by `nnunet.normalize(schemes)`; the arena holds, per case and 16-byte aligned, the cubic B-spline coefficients
     (float32 [C, H, W]), the normalised image itself (float32 [C, H, W], what an unmodified sample copies) and the labels (uint8 [H, W]); `table` is the
     per-case ldiff_seg_case row (offsets, H, W, row strides).  `class_locations[i]`: {class: [n, 2] (row, column)} for the foreground classes
-    1 .. n_heads - 1.  `labels`: a dataset.json `labels` mapping, only looked at to refuse what the tissue head does not cover.
+    1 .. n_heads - 1.  `labels`: a dataset.json `labels` mapping, looked at to refuse what the tissue head does not cover and for nnU-Net's ignore
+    label (`nnunet.label_spec`; it must equal `n_heads`): the label maps may then carry that value, `ignore_label` holds it (None otherwise), and
+    every `class_locations[i]` ends with the entry `annotated_key(n_heads)`, the sampled pixels of any class, which `draw_crop` centres samples on.
     `device="cpu"` keeps the arena on the host: enough for `draw_batch`, not for a PatchLoader.
     `prefilter`: "host" (the default) forms the coefficients by `spline_coefficients` in float64 and rounds them once; "device" uploads the normalised
     image in their place and filters it there (`spline_prefilter_`), so the coefficients carry the float32 filter's own error, a few 1e-6 of the
@@ -166,11 +178,11 @@ class CaseStore:
             raise ValueError(f"CaseStore: build must be 'host' or 'device', got {build!r}")
         if build == "device" and torch.device(device).type != "cuda":
             raise ValueError("CaseStore: build='device' needs the store on a GPU")
+        self.ignore_label = None
         if labels is not None:
-            if any(isinstance(v, (list, tuple)) for v in labels.values()):
-                nnunet._refuse("labels", "defines regions")
-            if "ignore" in labels:
-                nnunet._refuse("labels", "defines an ignore label")
+            heads, self.ignore_label = nnunet.label_spec(labels)
+            if self.ignore_label is not None and heads != int(n_heads):
+                raise ValueError(f"CaseStore: `labels` names {heads} classes and the ignore label {self.ignore_label}, n_heads is {n_heads}")
         if not 2 <= int(n_heads) <= 32:
             raise ValueError(f"CaseStore: n_heads {n_heads} out of range [2, 32]")
         cases = list(cases)
@@ -202,8 +214,9 @@ class CaseStore:
             if crop:
                 img, seg = img[:, box[0]:box[1], box[2]:box[3]], seg[box[0]:box[1], box[2]:box[3]]
                 H, W = box[1] - box[0], box[3] - box[2]
-            if seg.min() < 0 or seg.max() >= self.n_heads:
-                bad = sorted(int(v) for v in np.unique(seg) if v < 0 or v >= self.n_heads)
+            top = self.n_heads if self.ignore_label is None else self.n_heads + 1   # the ignore label is the one value past the classes
+            if seg.min() < 0 or seg.max() >= top:
+                bad = sorted(int(v) for v in np.unique(seg) if v < 0 or v >= top)
                 raise ValueError(f"CaseStore: case {i}: labels {bad[:5]} outside [0, {self.n_heads})")
             raw = nnunet.normalize(img.cpu().to(torch.float32), self.schemes).numpy()
             coef = spline_coefficients(raw).astype(np.float32) if prefilter == "host" else raw
@@ -214,7 +227,7 @@ class CaseStore:
                 row[key] = size
                 parts.append((size, np.ascontiguousarray(arr).view(np.uint8).reshape(-1)))
                 size += parts[-1][1].size
-            self.class_locations.append(sample_foreground_locations(seg, range(1, self.n_heads)))
+            self.class_locations.append(sample_foreground_locations(seg, range(1, self.n_heads), annotated=None if self.ignore_label is None else self.n_heads))
         host = np.zeros((size + 15) // 16 * 16, np.uint8)
         for off, arr in parts:
             host[off:off + arr.size] = arr
@@ -228,6 +241,8 @@ class CaseStore:
         """build="device": the case kernels in three rounds with one synchronisation each -- boxes; statistics and label counts over the boxes; then the
         arena is laid out, every case normalised into it and the sampled foreground ranks turned into pixels."""
         dev, nh = self.device, self.n_heads
+        ign = self.ignore_label is not None
+        counted = nh + 1 if ign else nh   # the ignore label is counted as one more class, so that "no class and not ignored" keeps its own count
         imgs, segs, given = [], [], []
         for i, (img, seg) in enumerate(cases):
             img, seg = torch.as_tensor(img), torch.as_tensor(seg)
@@ -253,19 +268,19 @@ class CaseStore:
                 _launch_case_bbox(imgs[i], boxes_dev[i])
             self.boxes = [tuple(int(v) for v in b) for b in boxes_dev.cpu().numpy()]
             stats_dev = torch.empty((n, self.channels, 4), dtype=torch.int64, device=dev)
-            totals_dev = torch.empty((n, nh + 2), dtype=torch.int32, device=dev)
+            totals_dev = torch.empty((n, counted + (3 if ign else 2)), dtype=torch.int32, device=dev)
             ws = torch.empty(max(int(_lib.load().ldiff_op_case_stats_ws_bytes(self.channels)), 16), dtype=torch.uint8, device=dev)
             prefixes = []
             for i in range(n):
                 _launch_case_stats(imgs[i], self.boxes[i], stats_dev[i], ws)
-                prefixes.append(_launch_case_counts(segs[i], self.boxes[i], nh, totals_dev[i])[1])
+                prefixes.append(_launch_case_counts(segs[i], self.boxes[i], counted, totals_dev[i], nh if ign else None)[1])
             stats, totals = stats_dev.cpu().numpy(), totals_dev.cpu().numpy().astype(np.int64)
             size = 0
             norm = []
             for i in range(n):
-                if totals[i, nh + 1]:
+                if totals[i, counted + 1]:
                     b = self.boxes[i]
-                    bad = sorted(int(v) for v in torch.unique(given[i][b[0]:b[1], b[2]:b[3]]).cpu() if v < 0 or v >= nh)   # the error path alone looks at values
+                    bad = sorted(int(v) for v in torch.unique(given[i][b[0]:b[1], b[2]:b[3]]).cpu() if v < 0 or v >= counted)   # the error path alone looks at values
                     raise ValueError(f"CaseStore: case {i}: labels {bad[:5]} outside [0, {nh})")
                 h, w = self.boxes[i][1] - self.boxes[i][0], self.boxes[i][3] - self.boxes[i][2]
                 norm.append(normalization_scalars(stats[i], imgs[i].dtype, h * w, self.schemes))
@@ -291,6 +306,11 @@ class CaseStore:
                         continue
                     ranks = torch.from_numpy(rndst.choice(count, _target_num_samples(count), replace=False).astype(np.int64)).to(dev)
                     picked[c] = _launch_case_rank(segs[i], self.boxes[i], c, prefixes[i][c], ranks, None)[0]
+                if ign:   # the same walk goes on to the annotated pixels, `label < n_heads`: the selector -1 - n_heads, its prefix the table's last row
+                    count = int(totals[i, counted + 2])
+                    picked[annotated_key(nh)] = [] if count == 0 else _launch_case_rank(
+                        segs[i], self.boxes[i], -1 - nh, prefixes[i][counted + 1],
+                        torch.from_numpy(rndst.choice(count, _target_num_samples(count), replace=False).astype(np.int64)).to(dev), None)[0]
                 self.class_locations.append({c: (v if isinstance(v, list) else v.cpu().numpy().astype(np.int64)) for c, v in picked.items()})
         self.cases_dev = torch.from_numpy(self.table.view(np.uint8).reshape(-1).copy()).to(dev)
 
@@ -345,14 +365,25 @@ def draw_crop(rng: np.random.Generator, store: CaseStore, sample_idx: int, batch
               oversample: float = OVERSAMPLE_FOREGROUND) -> dict:
     """The case and the loader's crop of one sample (nnUNetDataLoader2D.generate_train_batch + get_bbox): the case index, whether the sample is forced
     onto foreground, the bounds, the chosen voxel (None for a free crop) and the crop's first index `bbox_lbs`.
-    Draws: case index; then class and voxel (forced, and the case has foreground) or row and column of the crop."""
+    Draws: case index; then class and voxel (forced, and the case has foreground) or row and column of the crop.
+    A store with an ignore label (get_bbox :84-135, has_ignore): a sample that is not forced takes one of the case's annotated locations as its
+    centre (one draw, the voxel) and falls back to the free crop when the case has none; a forced sample chooses among the entries present with
+    the annotated key taken out whenever another entry is there."""
     ci = int(rng.integers(len(store)))
     lbs, ubs = crop_bounds(store.shape(ci), loader_patch, patch_size)
     forced = do_oversample(sample_idx, batch_size, oversample)
     eligible = [c for c, locs in store.class_locations[ci].items() if len(locs) > 0]
     voxel = None
-    if forced and eligible:   # get_bbox (:95-132): a class among those present, one of its recorded voxels as the centre
-        locs = store.class_locations[ci][eligible[int(rng.integers(len(eligible)))]]
+    has_ignore = getattr(store, "ignore_label", None) is not None
+    if has_ignore:
+        key = annotated_key(store.n_heads)
+        if not forced:
+            eligible = [key] if key in eligible else []
+        elif key in eligible and len(eligible) > 1:
+            eligible.remove(key)
+    if (forced or has_ignore) and eligible:   # get_bbox (:95-132): a class among those present, one of its recorded voxels as the centre
+        chosen = eligible[int(rng.integers(len(eligible)))] if forced else eligible[0]   # not forced: the annotated key by rule, nothing to draw
+        locs = store.class_locations[ci][chosen]
         voxel = [int(v) for v in locs[int(rng.integers(len(locs)))]]
         bbox = [max(lbs[d], voxel[d] - loader_patch[d] // 2) for d in range(2)]
     else:                     # :85 / :135: anywhere between the bounds (a forced sample of a case without foreground falls back to this)
@@ -629,15 +660,25 @@ def normalization_scalars(raw_stats: np.ndarray, dtype, n_pixels: int, schemes: 
     return sub, div
 
 
-def _launch_case_counts(seg: torch.Tensor, box, n_heads: int, totals: torch.Tensor):
+def _launch_case_counts(seg: torch.Tensor, box, n_heads: int, totals: torch.Tensor, n_classes: Optional[int] = None):
+    """`n_classes`: ldiff_op_case_counts_classes -- one more prefix row and one more total, for `label < n_classes`; n_heads may then be 33."""
     H, W, ls = _case_labels(seg, "case_counts")
     y0, y1, x0, x1 = _check_box(box, H, W, "case_counts")
-    if not 1 <= int(n_heads) <= 32:
-        raise ValueError(f"case_counts: n_heads {n_heads} out of range [1, 32]")
+    top = 32 if n_classes is None else 33
+    if not 1 <= int(n_heads) <= top:
+        raise ValueError(f"case_counts: n_heads {n_heads} out of range [1, {top}]")
+    if n_classes is not None and not 1 <= int(n_classes) <= int(n_heads):
+        raise ValueError(f"case_counts: n_classes {n_classes} out of range [1, {n_heads}]")
     rows = y1 - y0
     row_counts = torch.empty((rows, n_heads + 1), dtype=torch.int32, device=seg.device)
-    prefix = torch.empty((n_heads + 1, rows + 1), dtype=torch.int32, device=seg.device)
+    prefix = torch.empty((n_heads + (1 if n_classes is None else 2), rows + 1), dtype=torch.int32, device=seg.device)
+    if totals.numel() != n_heads + (2 if n_classes is None else 3):
+        raise ValueError(f"case_counts: totals must hold {n_heads + (2 if n_classes is None else 3)} counts, got {totals.numel()}")
     with torch.cuda.device(seg.device):
+        if n_classes is not None:
+            _lib.check(_lib.load().ldiff_op_case_counts_classes(_lib.ptr(seg), H, W, ls, y0, y1, x0, x1, int(n_heads), int(n_classes), _lib.ptr(row_counts),
+                                                                _lib.ptr(prefix), _lib.ptr(totals), _lib.stream_ptr()))
+            return row_counts, prefix
         _lib.check(_lib.load().ldiff_op_case_counts(_lib.ptr(seg), H, W, ls, y0, y1, x0, x1, int(n_heads), _lib.ptr(row_counts), _lib.ptr(prefix), _lib.ptr(totals),
                                                     _lib.stream_ptr()))
     return row_counts, prefix

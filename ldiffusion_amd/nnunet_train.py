@@ -19,7 +19,11 @@ with two collectives between them --
     step_update    1 / world folded into the update's device scalar, optim.sumsq for the norm, optim.update_loss_scale, clip coefficient, one SGD launch
 -- and `run_training` pools losses and tp / fp / fn over the ranks; rank 0 writes the checkpoints.
 
-Not here: a captured-graph step, ResidualEncoderUNet, region labels and an ignore label.
+Partly annotated labels (`Trainer(ignore_label=k)`, nnU-Net's ignore label: nnUNetTrainer.py:357-359 hands `label_manager.ignore_label` to the loss):
+pixels labelled k add nothing to the loss, the gradient or the validation counts (ag.dice_ce(ignore_label=), the ignore form of ldiff_op_dice_ce).
+The data-parallel step with an ignore label is NOT built: `Trainer(ddp=True, ignore_label=k)` at a world size above 1 raises NotImplementedError.
+
+Not here: a captured-graph step, ResidualEncoderUNet, region labels.
 """
 from __future__ import annotations
 
@@ -240,8 +244,9 @@ class Trainer:
 
     def __init__(self, spec: dict, state_dict, batch_dice: bool, num_epochs: int, initial_lr: float = 1e-2, weight_decay: float = 3e-5, device="cuda:0", *,
                  configuration: str = "2d", init_args: Optional[dict] = None, mirror_axes: Optional[Sequence[int]] = (0, 1), loss_scale: Optional[float] = None,
-                 slope: float = SLOPE, ddp: Optional[bool] = None, group=None, wgrad_route: Optional[str] = None):
-        """`ddp`: None follows the launch (a process group of more than one rank: nnUNetTrainer.is_ddp), True / False force it; `group` the process group
+                 slope: float = SLOPE, ddp: Optional[bool] = None, group=None, wgrad_route: Optional[str] = None, ignore_label: Optional[int] = None):
+        """`ignore_label`: the dataset's ignore label (spec["ignore_label"] of nnunet.network_spec; it equals n_heads), None for fully annotated labels.
+        `ddp`: None follows the launch (a process group of more than one rank: nnUNetTrainer.is_ddp), True / False force it; `group` the process group
         (None: the default one).  ddp at world size 1 is legal: the collectives are identities.  `self.world` is the factor of the Dice gradient and of
         the gradient mean; code that does the two collectives by hand for several trainers in one process sets it to their number."""
         self.spec = dict(spec)
@@ -250,6 +255,9 @@ class Trainer:
         self.batch_dice = bool(batch_dice)
         self.num_epochs, self.initial_lr, self.weight_decay = int(num_epochs), float(initial_lr), float(weight_decay)
         self.n_heads = int(spec["n_heads"])
+        if ignore_label is not None and int(ignore_label) != self.n_heads:
+            raise ValueError(f"Trainer: ignore_label {ignore_label} must be the first value past the classes, n_heads = {self.n_heads} (nnunet.label_spec)")
+        self.ignore_label = None if ignore_label is None else int(ignore_label)
         self.weights = deep_supervision_weights(spec["n_stages"] - 1)
         self.names = [k for k, _ in self.network.named_parameters()]
         self.params = self.network.parameters()
@@ -271,6 +279,7 @@ class Trainer:
         self._dist = dist if (self.ddp and live) else None
         self.world = dist.get_world_size(group) if self._dist is not None else 1
         self.rank = dist.get_rank(group) if self._dist is not None else 0
+        self._check_ignore_ddp()
         self._pending = None
         self._bucket_state: dict = {}
         self._norm_t = torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -278,6 +287,13 @@ class Trainer:
             src = dist.get_global_rank(group, 0) if group is not None else 0
             for p in self.params:
                 dist.broadcast(p.data, src=src, group=group)
+
+    def _check_ignore_ddp(self):
+        """The data-parallel step's ignore form is not built (the Dice statistics of all ranks with each rank's own annotated count); `world` may be
+        set after construction by code that does the collectives by hand, so the step's phases ask again."""
+        if self.ignore_label is not None and self.ddp and self.world > 1:
+            raise NotImplementedError(f"Trainer(ddp=True, ignore_label={self.ignore_label}) at world size {self.world}: the data-parallel step with an "
+                                      "ignore label is not built; train on one rank")
 
     def lr(self, epoch: Optional[int] = None) -> float:
         return poly_lr(self.current_epoch if epoch is None else epoch, self.initial_lr, self.num_epochs)
@@ -300,7 +316,7 @@ class Trainer:
         for o, t, w in zip(outputs, targets, self.weights):
             if w == 0.0:
                 continue
-            term = ag.DiceCeFn.apply(o, t, self.n_heads, self.batch_dice, w, grad_scale, SMOOTH)   # the weighted term
+            term = ag.DiceCeFn.apply(o, t, self.n_heads, self.batch_dice, w, grad_scale, SMOOTH, self.ignore_label)   # the weighted term
             total = term if total is None else total + term
         return total
 
@@ -321,6 +337,7 @@ class Trainer:
         """Phase 1: the forward pass and the loss statistics of every graded scale (weight not 0), highest resolution first.  Returns float64
         [scales, NACC] on the device: per scale sum_pred / intersect / sum_gt per class, the cross-entropy sum and the count of labels outside
         [0, n_heads), over this rank's batch.  The caller adds all ranks' tensors in rank order and hands the sum to `step_backward`."""
+        self._check_ignore_ddp()
         for p in self.params:
             p.grad = None
         with torch.cuda.device(self.device):
@@ -331,14 +348,14 @@ class Trainer:
     def _statistics(self, outputs, targets):
         """(graded scales, their local statistics, the [scales, NACC] table to exchange)"""
         graded = [(o, t, w) for o, t, w in zip(outputs, targets, self.weights) if w != 0.0]
-        nacc = ag.dice_ce_nacc(self.n_heads)
+        nacc = ag.dice_ce_nacc(self.n_heads, self.ignore_label)
         table = torch.empty((len(graded), nacc), dtype=torch.float64, device=self.device)
         local = []
         for i, (o, t, _) in enumerate(graded):
             if self.batch_dice:
-                local.append(ag.dice_ce_stats(o, t, self.n_heads, True, out=table[i]).view(1, nacc))
+                local.append(ag.dice_ce_stats(o, t, self.n_heads, True, out=table[i], ignore_label=self.ignore_label).view(1, nacc))
             else:   # per-sample Dice stays on its rank; the exchanged row carries the bad-label count
-                local.append(ag.dice_ce_stats(o, t, self.n_heads, False))
+                local.append(ag.dice_ce_stats(o, t, self.n_heads, False, ignore_label=self.ignore_label))
                 table[i] = local[-1].sum(0)
         return graded, local, table
 
@@ -346,9 +363,9 @@ class Trainer:
         total = None
         for i, ((o, t, w), loc) in enumerate(zip(graded, local)):
             if self.batch_dice:
-                term = ag.DiceCeSumsFn.apply(o, t, self.n_heads, True, global_sums[i], loc, self.world, w, grad_scale, SMOOTH)
+                term = ag.DiceCeSumsFn.apply(o, t, self.n_heads, True, global_sums[i], loc, self.world, w, grad_scale, SMOOTH, self.ignore_label)
             else:
-                term = ag.DiceCeSumsFn.apply(o, t, self.n_heads, False, loc, loc, 1, w, grad_scale, SMOOTH)
+                term = ag.DiceCeSumsFn.apply(o, t, self.n_heads, False, loc, loc, 1, w, grad_scale, SMOOTH, self.ignore_label)
             total = term if total is None else total + term
         return total
 
@@ -369,6 +386,7 @@ class Trainer:
         """Phase 2: the loss of this rank from the summed statistics (ag.DiceCeSumsFn per graded scale; with `batch_dice` the Dice term is the global
         batch's and its gradient carries the factor world, without it the term stays local), backward at the loss scale, and every gradient packed
         into one flat float32 bucket in one launch.  Returns (loss value as a 0-dim device tensor, bucket)."""
+        self._check_ignore_ddp()
         if self._pending is None:
             raise RuntimeError("step_backward: no step_forward is pending")
         graded, local, _ = self._pending
@@ -408,10 +426,10 @@ class Trainer:
         return True
 
     def _train_step_ddp(self, data, targets) -> float:
-        nacc = ag.dice_ce_nacc(self.n_heads)
+        bad = 3 * 8 * ((self.n_heads + 7) // 8) + 1   # the row's count of labels that are no class (and not the ignore label), in both forms
         sums = self.gather_sums(self.step_forward(data, targets))
         host = sums.cpu()
-        if float(host[:, nacc - 1].sum()) > 0 or not bool(torch.isfinite(host).all()):   # the gathered count (non-finite logits make the gathered cross-entropy
+        if float(host[:, bad].sum()) > 0 or not bool(torch.isfinite(host).all()):   # the gathered count (non-finite logits make the gathered cross-entropy
             # sum non-finite): every rank sees the same tensor, skips the update and raises together -- none is left waiting in a collective
             self._pending = None
             raise ValueError("train_step: the loss is NaN -- a label outside [0, n_heads) (torch's cross_entropy raises there too) or non-finite logits")
@@ -443,7 +461,8 @@ class Trainer:
     @torch.no_grad()
     def validation_step(self, data, targets) -> dict:
         """nnUNetTrainer.validation_step (:915-989) for plain labels: the loss, and per foreground class tp / fp / fn of the full-resolution arg-max, from
-        metrics' confusion kernel (rows = targets, columns = predictions)."""
+        metrics' confusion kernel (rows = targets, columns = predictions).  With an ignore label (:966-978: the counts are masked by
+        `target != ignore_label`) the kernel's own rule does it: a pixel whose target is no class enters no cell, so it is in no tp, fp or fn."""
         with torch.cuda.device(self.device):
             outputs = self.network(data)
             tl = self._targets(targets, 1)

@@ -220,7 +220,8 @@ class Segmentor:
         return recon
 
     def train_tissue_model_nnUNetv2(self, epochs, ldiffusion_weight, diffusion_path, train_images=None, train_labels=None, test_images=None, test_labels=None,
-                                    num_classes=None, *, iterations_per_epoch=250, val_iterations=50, num_foreground_voxels=None, wgrad_route=None, batch_images=None, io_workers=4):
+                                    num_classes=None, *, iterations_per_epoch=250, val_iterations=50, num_foreground_voxels=None, wgrad_route=None, batch_images=None, io_workers=4,
+                                    ignore_pixel=None):
         """segmentor.py:163-241: the tissue head's training stage, from image lists to a trained-model folder.
         Dataset (:167-205): `load_ldiffusion`, the cached text embeddings of "A pathological slide", the text-alignment wrapper, and
         `utils.create_nnunet_dataset` under nnUNet_raw (the one-pass diffusion of every image when all share one size, else copies).
@@ -232,7 +233,10 @@ class Segmentor:
         nnUNet_results/<dataset>/nnUNetTrainer__nnUNetPlans__2d/fold_0, plans.json and dataset.json beside it.
         `iterations_per_epoch`, `val_iterations`: nnUNetTrainer's 250 / 50.  `num_foreground_voxels`: the fingerprint's sample budget (None: the
         reference's 10e7).  `wgrad_route`: `nnunet_train.Trainer`'s (None: its default).  `batch_images`, `io_workers`: `utils.create_nnunet_dataset`'s
-        (None: the per-image dataset pass; an integer: the pass batched behind the device image front end).  The three folders come from the environment variables nnUNet_raw, nnUNet_preprocessed, nnUNet_results.
+        (None: the per-image dataset pass; an integer: the pass batched behind the device image front end).  `ignore_pixel`: the grey level of
+        unlabelled pixels in partly annotated label images (`utils.create_nnunet_dataset`'s): the dataset declares nnU-Net's ignore label, the stores
+        draw patches from annotated areas and the trainer leaves those pixels out of loss, gradient and validation counts; None: fully annotated
+        labels, the stage as it was.  With an ignore label the stage runs on one rank (the data-parallel step's ignore form is not built).  The three folders come from the environment variables nnUNet_raw, nnUNet_preprocessed, nnUNet_results.
         Under a process group of more than one rank the stage is data-parallel, as the reference's nnUNetTrainer is under the same launch: rank 0 alone
         writes the dataset, the fingerprint, plans, split and the model folder; `(new_num, dataset_name)` go out by `broadcast_object_list` and a
         barrier; every rank then reads the PNGs and JSONs and builds both stores on its own device; its loaders take its entry of
@@ -265,6 +269,8 @@ class Segmentor:
                 self._ensure_ldiffusion_proj(pipeline, unet, ldiffusion_weight=ldiffusion_weight)
                 aligned_unet = TextAlignedUNet(unet, self._get_text_embeddings(PROMPT, 1, pipeline, unet))
             batch_kwargs = {} if batch_images is None else dict(batch_images=batch_images, io_workers=io_workers)   # None: the call of before the keyword
+            if ignore_pixel is not None:
+                batch_kwargs["ignore_pixel"] = ignore_pixel
             named = list(utils.create_nnunet_dataset(train_images, train_labels, test_images, test_labels, num_classes, pipeline, aligned_unet,
                                                      raw_dir=roots["nnUNet_raw"], **batch_kwargs))
         if world > 1:
@@ -307,7 +313,7 @@ class Segmentor:
             plans, splits = load_json("nnUNetPlans.json"), load_json("splits_final.json")
 
         print("\033[32m[Segmentor-nnUNet] Training is starting...\033[0m")
-        spec = nnunet.network_spec(plans, "2d", dataset_json)
+        spec = nnunet.network_spec(plans, "2d", dataset_json, accept_ignore=ignore_pixel is not None)
         cfg = plans["configurations"]["2d"]
         stores = [nnunet_data.CaseStore([cases[k] for k in splits[0][part]], spec["normalization_schemes"], spec["n_heads"], device=self.device,
                                         labels=dataset_json["labels"], prefilter="device", build="device") for part in ("train", "val")]
@@ -320,7 +326,11 @@ class Segmentor:
         loaders = [nnunet_data.PatchLoader(store, spec["patch_size"], batch, n_scales, seed=seed, train=train, **extra)
                    for store, seed, train in ((stores[0], 2 * rank, True), (stores[1], 2 * rank + 1, False))]
         self.tissue_loaders = loaders
-        trainer = nnunet_train.Trainer(spec, nnunet_train.initial_state_dict(spec), cfg["batch_dice"], num_epochs=epochs, device=self.device, wgrad_route=wgrad_route)
+        ignore = {}
+        if spec.get("ignore_label") is not None:   # nnUNetTrainer keeps the dataset.json it was built with, ignore entry included, in the checkpoint's init_args
+            ignore = dict(ignore_label=spec["ignore_label"], init_args={"configuration": "2d", "fold": 0, "dataset_json": dataset_json})
+        trainer = nnunet_train.Trainer(spec, nnunet_train.initial_state_dict(spec), cfg["batch_dice"], num_epochs=epochs, device=self.device, wgrad_route=wgrad_route,
+                                       **ignore)
         model_dir = os.path.join(roots["nnUNet_results"], dataset_name, "nnUNetTrainer__nnUNetPlans__2d")
         if rank == 0:
             nnunet.write_trained_model_folder(model_dir, plans, dataset_json)

@@ -214,18 +214,31 @@ def convert_and_save_label(lbl, dst_path, mapping):
     Image.fromarray(lut[np.asarray(lbl.convert("L"), np.uint8)]).save(dst_path)
 
 
-def create_nnunet_dataset(train_images, train_labels, test_images, test_labels, num_classes, pipeline, unet, raw_dir=None, batch_images=None, io_workers=4):
+def create_nnunet_dataset(train_images, train_labels, test_images, test_labels, num_classes, pipeline, unet, raw_dir=None, batch_images=None, io_workers=4,
+                          ignore_pixel=None):
     """utils.py:210-294: the next `DatasetNNN_Custom` under nnUNet_raw (`raw_dir`, else the environment variable nnUNet_raw) with imagesTr / labelsTr /
     imagesTs / labelsTs, `case_%03d_0000.png` + `case_%03d.png` and `caseTs_%03d...`; every image goes through `copy_or_convert_image` -- the
     one-pass diffusion when ALL train and ALL test images share one size, else a plain copy --, every label is resized to its image (NEAREST) and
     mapped through metrics.PIXEL_TO_LABEL; `dataset.json` as the reference writes it.  Returns (new_num, new_dataset_name).
     `batch_images` (None: the per-image path above, byte for byte): with the diffusion on, the images of each list go through
     `copy_or_convert_images(batch_images=..., io_workers=...)` after the list's labels are written -- the files are those of `copy_or_convert_image`
-    alone under `pipeline.set_plan_batch(batch_images)`, the labels and dataset.json those of the default call.  With mixed sizes (plain copies) it changes nothing."""
+    alone under `pipeline.set_plan_batch(batch_images)`, the labels and dataset.json those of the default call.  With mixed sizes (plain copies) it changes nothing.
+    `ignore_pixel` (None: everything above, byte for byte): the grey level of unlabelled pixels in partly annotated label images.  The label PNGs
+    carry `num_classes` there and dataset.json gains `"ignore": num_classes` -- nnU-Net's ignore label, the highest value.  A grey level
+    metrics.PIXEL_TO_LABEL already maps raises ValueError."""
     import json
     import os
     from pathlib import Path
     from PIL import Image
+    mapping = metrics.PIXEL_TO_LABEL
+    if ignore_pixel is not None:
+        if isinstance(ignore_pixel, bool) or int(ignore_pixel) != ignore_pixel or not 0 <= int(ignore_pixel) <= 255:
+            raise ValueError(f"create_nnunet_dataset: ignore_pixel {ignore_pixel!r} is not a grey level 0 .. 255")
+        if int(ignore_pixel) in {int(level) for level in mapping}:
+            raise ValueError(f"create_nnunet_dataset: ignore_pixel {int(ignore_pixel)} is the grey level of class {mapping[int(ignore_pixel)]}")
+        if not 2 <= int(num_classes) <= 254:
+            raise ValueError(f"create_nnunet_dataset: an ignore label needs 2 .. 254 classes, got {num_classes}")
+        mapping = {**mapping, int(ignore_pixel): int(num_classes)}
     raw = raw_dir if raw_dir is not None else os.environ.get("nnUNet_raw")
     if raw is None:
         raise RuntimeError("create_nnunet_dataset: no nnUNet_raw folder: pass raw_dir= or set the environment variable nnUNet_raw")
@@ -259,7 +272,7 @@ def create_nnunet_dataset(train_images, train_labels, test_images, test_labels, 
                 pending.append((img_path, new_path / img_dir / f"{case_id}_0000.png"))
             else:
                 copy_or_convert_image(img, img_path, new_path / img_dir / f"{case_id}_0000.png", pipeline, unet, use_diffusion)
-            convert_and_save_label(lbl, new_path / lbl_dir / f"{case_id}.png", metrics.PIXEL_TO_LABEL)
+            convert_and_save_label(lbl, new_path / lbl_dir / f"{case_id}.png", mapping)
             n_train += stem == "case"
             if batched:
                 img.close()
@@ -267,7 +280,7 @@ def create_nnunet_dataset(train_images, train_labels, test_images, test_labels, 
             copy_or_convert_images([p for p, _ in pending], [d for _, d in pending], pipeline, unet, batch_images=batch_images, io_workers=io_workers)
     dataset_json = {
         "channel_names": {"0": "R", "1": "G", "2": "B"},
-        "labels": {"background": 0, **{f"class{i}": i for i in range(1, num_classes)}},
+        "labels": {"background": 0, **{f"class{i}": i for i in range(1, num_classes)}, **({} if ignore_pixel is None else {"ignore": int(num_classes)})},
         "numTraining": n_train,
         "file_ending": ".png",
     }

@@ -13,7 +13,12 @@ data-parallel path's own launches; it says nothing about scaling.
 --route R: a second library trainer with `Trainer(wgrad_route=R)` (autograd.WGRAD_ROUTES) joins the alternation -- default route, route R, torch -- and the
 profiled step is R's.  The default route's launches are those of a tree without the route, so this is the before / after of a route on one box in one call.
 
-usage: python scripts/bench_nnunet_train.py [--passes 5] [--size 512] [--batch 0 (= the plans')] [--config 2d] [--ddp] [--route auto-wide]
+--ignore: instead, the ignore form of the loss (nnU-Net's ignore label, ag.dice_ce(ignore_label=)) against the plain entry.  First the three loss launches
+alone on the full-resolution logits' shape [B, size, size, roundup(n_heads, 8)], device-synchronised wall time over 20 calls, several runs alternating:
+plain entry | ignore form on the same fully annotated target | ignore form with about 30 % of the pixels ignored (in blocks).  Then the trainer step,
+alternating: Trainer() | Trainer(ignore_label=n_heads) on the same targets | the same with about 30 % ignored.
+
+usage: python scripts/bench_nnunet_train.py [--passes 5] [--size 512] [--batch 0 (= the plans')] [--config 2d] [--ddp] [--route auto-wide] [--ignore]
 """
 import argparse
 import json
@@ -29,7 +34,7 @@ import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 from torch import nn  # noqa: E402
 
-from ldiffusion_amd import nnunet, nnunet_train  # noqa: E402
+from ldiffusion_amd import autograd as ag, nnunet, nnunet_train  # noqa: E402
 
 FAMILIES = [("InstanceNorm + LeakyReLU (in_train)", ("in_partial", "in_apply", "in_fwd_finalize", "in_bwd_finalize")),
             ("Dice + cross-entropy (dice_ce)", ("dce_",)),
@@ -105,6 +110,7 @@ def main():
     ap.add_argument("--batch", type=int, default=0)
     ap.add_argument("--config", default="2d")
     ap.add_argument("--ddp", action="store_true")
+    ap.add_argument("--ignore", action="store_true", help="time the loss's ignore form and a trainer with an ignore label against the plain ones")
     ap.add_argument("--route", default=None, help="also time (and profile) a trainer under this weight-gradient route")
     a = ap.parse_args()
     with open(os.path.join(ROOT, "tests", "golden", "nnunet_plans_2d.json")) as f:
@@ -133,6 +139,40 @@ def main():
         f = lambda v: f"median {statistics.median(v):.1f} ms (min {min(v):.1f}, max {max(v):.1f})"
         print(f"{a.config} B={B} {a.size}^2, {a.passes} alternating steps after 2 warm-ups: plain {f(tp)} | ddp at world 1 {f(tdd)} | ddp / plain = "
               f"{statistics.median(tdd) / statistics.median(tp):.3f}; steps: plain {[round(v, 1) for v in tp]}, ddp {[round(v, 1) for v in tdd]}")
+        return
+    if a.ignore:
+        k = spec["n_heads"]
+        f = lambda v: f"median {statistics.median(v):.3f} ms (min {min(v):.3f}, max {max(v):.3f})"
+        blocks = (torch.rand((B, a.size // 32, a.size // 32), generator=torch.Generator().manual_seed(3)) < 0.3).to(dev)   # 32 x 32 blocks, about 30 % of them
+        partly = [torch.where(blocks.repeat_interleave(32 >> min(i, 5), 1).repeat_interleave(32 >> min(i, 5), 2)[:, :t.shape[1], :t.shape[2]], torch.full_like(t, k), t)
+                  for i, t in enumerate(targets)]
+        ld = (k + 7) // 8 * 8
+        logits = torch.zeros((B, a.size, a.size, ld), dtype=torch.float16, device=dev)
+        logits[..., :k] = (2.0 * torch.randn((B, a.size, a.size, k), generator=torch.Generator().manual_seed(4))).to(torch.float16).to(dev)
+        t8, p8 = targets[0].to(torch.uint8), partly[0].to(torch.uint8)   # the loader's label maps are uint8
+        forms = [("plain entry", t8, None), ("ignore form, nothing ignored", t8, k), (f"ignore form, {float((p8 == k).float().mean()):.2f} ignored", p8, k)]
+        calls = 20
+        for _, t, ign in forms:
+            ag.dice_ce(logits, t, k, batch_dice, 1.0, 1024.0, ignore_label=ign)
+        times = {name: [] for name, _, _ in forms}
+        for _ in range(a.passes):
+            for name, t, ign in forms:
+                times[name].append(timed(lambda: [ag.dice_ce(logits, t, k, batch_dice, 1.0, 1024.0, ignore_label=ign) for _ in range(calls)]) / calls)
+        print(f"dice_ce B={B} {a.size}^2 n_heads={k} batch_dice={batch_dice}, per call (three launches), {a.passes} alternating runs of {calls} calls: "
+              + " | ".join(f"{name} {f(v)}" for name, v in times.items()))
+        trainers = [("Trainer()", tr, targets),
+                    ("Trainer(ignore_label), nothing ignored", nnunet_train.Trainer(spec, nnunet_train.initial_state_dict(spec, 0), batch_dice, 1000, device=dev,
+                                                                                    configuration=a.config, ignore_label=k), targets),
+                    ("Trainer(ignore_label), 30 % ignored", nnunet_train.Trainer(spec, nnunet_train.initial_state_dict(spec, 0), batch_dice, 1000, device=dev,
+                                                                                 configuration=a.config, ignore_label=k), partly)]
+        for _ in range(2):
+            for _, t, tg in trainers:
+                t.train_step(x, tg)
+        steps = {name: [] for name, _, _ in trainers}
+        for _ in range(a.passes):
+            for name, t, tg in trainers:
+                steps[name].append(timed(lambda: t.train_step(x, tg)))
+        print(f"{a.config} B={B} {a.size}^2 train_step, {a.passes} alternating steps after 2 warm-ups: " + " | ".join(f"{name} {f(v)}" for name, v in steps.items()))
         return
     tnet = TorchPlainConvUNet(spec).to(dev)
     opt = torch.optim.SGD(tnet.parameters(), 1e-2, weight_decay=3e-5, momentum=0.99, nesterov=True)
