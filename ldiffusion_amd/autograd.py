@@ -704,7 +704,9 @@ class DiceCeFn(torch.autograd.Function):
 
 def dice_ce_nacc(n_heads, ignore_label=None):
     """Doubles per row of the loss statistics: sum_pred, intersect, sum_gt per padded class, the cross-entropy sum, the count of labels outside [0, n_heads)
-    (ignored pixels excepted) and, in the ignore form (ldiff_op_dice_ce_ignore_nacc), the count of annotated pixels."""
+    (ignored pixels excepted) and, in the ignore form (ldiff_op_dice_ce_ignore_nacc), the count of annotated pixels.
+    The one definition is csrc/kernels_segtrain.hip's NACC = 3 NC + 2 + IGN (NC = 8 NV columns of a padded row); this mirrors it, to spare the step a
+    library call per scale."""
     return 3 * 8 * ((int(n_heads) + 7) // 8) + (2 if ignore_label is None else 3)
 
 

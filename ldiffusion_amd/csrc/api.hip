@@ -1180,21 +1180,21 @@ int ldiff_op_in_train_bwd(const void* x, const void* dy, const void* gamma, cons
 }
 int64_t ldiff_op_dice_ce_ws_bytes(int B, int64_t HW, int n_heads) {
   if (B < 1 || HW < 1 || n_heads < 2 || n_heads > 32) return 0;
-  return dice_ce_ws_bytes(B, HW, n_heads);
+  return dice_ce_ws_bytes(B, HW, n_heads, false);
 }
 int ldiff_op_dice_ce(const void* logits, int ld, int n_heads, const void* target, int target_i64, int B, int64_t HW, int batch_dice, float smooth, float weight,
                      float grad_scale, void* loss, void* dlogits, void* ws, int64_t ws_bytes, void* stream) {
   API_BEGIN
   LDIFF_CHECK(logits && target && loss && dlogits && ws, LDIFF_ERR_INVALID, "op_dice_ce: null argument");
-  launch_dice_ce((const f16*)logits, ld, n_heads, target, target_i64, B, HW, batch_dice, smooth, weight, grad_scale, (float*)loss, (f16*)dlogits, ws, ws_bytes,
-                 (hipStream_t)stream);
+  launch_dice_ce((const f16*)logits, ld, n_heads, std::nullopt, target, target_i64, B, HW, batch_dice, smooth, weight, grad_scale, (float*)loss, (f16*)dlogits, ws,
+                 ws_bytes, (hipStream_t)stream);
   API_END
 }
 int ldiff_op_dice_ce_stats(const void* logits, int ld, int n_heads, const void* target, int target_i64, int B, int64_t HW, int batch_dice, void* sums, void* ws,
                            int64_t ws_bytes, void* stream) {
   API_BEGIN
   LDIFF_CHECK(logits && target && sums && ws, LDIFF_ERR_INVALID, "op_dice_ce_stats: null argument");
-  launch_dice_ce_stats((const f16*)logits, ld, n_heads, target, target_i64, B, HW, batch_dice, (double*)sums, ws, ws_bytes, (hipStream_t)stream);
+  launch_dice_ce_stats((const f16*)logits, ld, n_heads, std::nullopt, target, target_i64, B, HW, batch_dice, (double*)sums, ws, ws_bytes, (hipStream_t)stream);
   API_END
 }
 int ldiff_op_dice_ce_from_sums(const void* logits, int ld, int n_heads, const void* target, int target_i64, int B, int64_t HW, int batch_dice, float smooth,
@@ -1202,28 +1202,28 @@ int ldiff_op_dice_ce_from_sums(const void* logits, int ld, int n_heads, const vo
                                int64_t ws_bytes, void* stream) {
   API_BEGIN
   LDIFF_CHECK(logits && target && dice_sums && local_sums && loss && dlogits && ws, LDIFF_ERR_INVALID, "op_dice_ce_from_sums: null argument");
-  launch_dice_ce_from_sums((const f16*)logits, ld, n_heads, target, target_i64, B, HW, batch_dice, smooth, weight, grad_scale, (const double*)dice_sums,
-                           (const double*)local_sums, world, (float*)loss, (f16*)dlogits, ws, ws_bytes, (hipStream_t)stream);
+  launch_dice_ce_from_sums((const f16*)logits, ld, n_heads, std::nullopt, target, target_i64, B, HW, batch_dice, smooth, weight, grad_scale,
+                           (const double*)dice_sums, (const double*)local_sums, world, (float*)loss, (f16*)dlogits, ws, ws_bytes, (hipStream_t)stream);
   API_END
 }
 int64_t ldiff_op_dice_ce_ignore_ws_bytes(int B, int64_t HW, int n_heads) {
   if (B < 1 || HW < 1 || n_heads < 2 || n_heads > 32) return 0;
-  return dice_ce_ignore_ws_bytes(B, HW, n_heads);
+  return dice_ce_ws_bytes(B, HW, n_heads, true);
 }
-int ldiff_op_dice_ce_ignore_nacc(int n_heads) { return (n_heads < 2 || n_heads > 32) ? 0 : dice_ce_ignore_nacc(n_heads); }
+int ldiff_op_dice_ce_ignore_nacc(int n_heads) { return (n_heads < 2 || n_heads > 32) ? 0 : dice_ce_nacc(n_heads, true); }
 int ldiff_op_dice_ce_ignore(const void* logits, int ld, int n_heads, int ignore_label, const void* target, int target_i64, int B, int64_t HW, int batch_dice,
                             float smooth, float weight, float grad_scale, void* loss, void* dlogits, void* ws, int64_t ws_bytes, void* stream) {
   API_BEGIN
   LDIFF_CHECK(logits && target && loss && dlogits && ws, LDIFF_ERR_INVALID, "op_dice_ce_ignore: null argument");
-  launch_dice_ce_ignore((const f16*)logits, ld, n_heads, ignore_label, target, target_i64, B, HW, batch_dice, smooth, weight, grad_scale, (float*)loss, (f16*)dlogits,
-                        ws, ws_bytes, (hipStream_t)stream);
+  launch_dice_ce((const f16*)logits, ld, n_heads, ignore_label, target, target_i64, B, HW, batch_dice, smooth, weight, grad_scale, (float*)loss, (f16*)dlogits, ws,
+                 ws_bytes, (hipStream_t)stream);
   API_END
 }
 int ldiff_op_dice_ce_ignore_stats(const void* logits, int ld, int n_heads, int ignore_label, const void* target, int target_i64, int B, int64_t HW, int batch_dice,
                                   void* sums, void* ws, int64_t ws_bytes, void* stream) {
   API_BEGIN
   LDIFF_CHECK(logits && target && sums && ws, LDIFF_ERR_INVALID, "op_dice_ce_ignore_stats: null argument");
-  launch_dice_ce_ignore_stats((const f16*)logits, ld, n_heads, ignore_label, target, target_i64, B, HW, batch_dice, (double*)sums, ws, ws_bytes, (hipStream_t)stream);
+  launch_dice_ce_stats((const f16*)logits, ld, n_heads, ignore_label, target, target_i64, B, HW, batch_dice, (double*)sums, ws, ws_bytes, (hipStream_t)stream);
   API_END
 }
 int ldiff_op_dice_ce_ignore_from_sums(const void* logits, int ld, int n_heads, int ignore_label, const void* target, int target_i64, int B, int64_t HW,
@@ -1231,8 +1231,9 @@ int ldiff_op_dice_ce_ignore_from_sums(const void* logits, int ld, int n_heads, i
                                       int64_t ws_bytes, void* stream) {
   API_BEGIN
   LDIFF_CHECK(logits && target && sums && loss && dlogits && ws, LDIFF_ERR_INVALID, "op_dice_ce_ignore_from_sums: null argument");
-  launch_dice_ce_ignore_from_sums((const f16*)logits, ld, n_heads, ignore_label, target, target_i64, B, HW, batch_dice, smooth, weight, grad_scale,
-                                  (const double*)sums, (float*)loss, (f16*)dlogits, ws, ws_bytes, (hipStream_t)stream);
+  // one process: the Dice sums are the local ones (the data-parallel exchange of the ignore form is not built)
+  launch_dice_ce_from_sums((const f16*)logits, ld, n_heads, ignore_label, target, target_i64, B, HW, batch_dice, smooth, weight, grad_scale, (const double*)sums,
+                           (const double*)sums, 1, (float*)loss, (f16*)dlogits, ws, ws_bytes, (hipStream_t)stream);
   API_END
 }
 int ldiff_op_bucket_pack(const void* grads, const void* offsets, const void* chunks, int64_t nchunks, void* bucket, void* stream) {

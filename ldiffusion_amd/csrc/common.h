@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -386,25 +387,18 @@ void launch_in_train_fwd(const f16* x, f16* y, const float* gamma, const float* 
                          float* ws, long long ws_bytes, hipStream_t s);
 void launch_in_train_bwd(const f16* x, const f16* dy, const float* gamma, const float* beta, const float* mean, const float* rstd, f16* dx, float* dgamma,
                          float* dbeta, int B, int HW, int C, float slope, float* ws, long long ws_bytes, hipStream_t s);
-long long dice_ce_ws_bytes(int B, long long HW, int n_heads);
-void launch_dice_ce(const f16* logits, int ld, int n_heads, const void* target, int target_i64, int B, long long HW, int batch_dice, float smooth, float weight,
-                    float grad_scale, float* loss, f16* dlogits, void* ws, long long ws_bytes, hipStream_t s);
+// Dice + cross-entropy of one deep-supervision scale.  With `ignore_label` (nnU-Net's ignore label) pixels carrying it add nothing, the workspace and the rows
+// of sums are the ignore form's (ign = true: one slot more, the annotated count); without, the plain loss.
+long long dice_ce_ws_bytes(int B, long long HW, int n_heads, bool ign);
+int dice_ce_nacc(int n_heads, bool ign);   // doubles per row of sums
+void launch_dice_ce(const f16* logits, int ld, int n_heads, std::optional<int> ignore_label, const void* target, int target_i64, int B, long long HW, int batch_dice,
+                    float smooth, float weight, float grad_scale, float* loss, f16* dlogits, void* ws, long long ws_bytes, hipStream_t s);
 // the same loss split at its sums (data-parallel step): dice_sums may be the sum over ranks, the cross-entropy stays local; ws as launch_dice_ce's
-void launch_dice_ce_stats(const f16* logits, int ld, int n_heads, const void* target, int target_i64, int B, long long HW, int batch_dice, double* sums, void* ws,
-                          long long ws_bytes, hipStream_t s);
-void launch_dice_ce_from_sums(const f16* logits, int ld, int n_heads, const void* target, int target_i64, int B, long long HW, int batch_dice, float smooth,
-                              float weight, float grad_scale, const double* dice_sums, const double* local_sums, int world, float* loss, f16* dlogits, void* ws,
-                              long long ws_bytes, hipStream_t s);
-// the three with nnU-Net's ignore label: pixels carrying it add nothing; rows of dice_ce_ignore_nacc doubles; ws of dice_ce_ignore_ws_bytes
-long long dice_ce_ignore_ws_bytes(int B, long long HW, int n_heads);
-int dice_ce_ignore_nacc(int n_heads);
-void launch_dice_ce_ignore(const f16* logits, int ld, int n_heads, int ignore_label, const void* target, int target_i64, int B, long long HW, int batch_dice,
-                           float smooth, float weight, float grad_scale, float* loss, f16* dlogits, void* ws, long long ws_bytes, hipStream_t s);
-void launch_dice_ce_ignore_stats(const f16* logits, int ld, int n_heads, int ignore_label, const void* target, int target_i64, int B, long long HW, int batch_dice,
-                                 double* sums, void* ws, long long ws_bytes, hipStream_t s);
-void launch_dice_ce_ignore_from_sums(const f16* logits, int ld, int n_heads, int ignore_label, const void* target, int target_i64, int B, long long HW,
-                                     int batch_dice, float smooth, float weight, float grad_scale, const double* sums, float* loss, f16* dlogits, void* ws,
-                                     long long ws_bytes, hipStream_t s);
+void launch_dice_ce_stats(const f16* logits, int ld, int n_heads, std::optional<int> ignore_label, const void* target, int target_i64, int B, long long HW,
+                          int batch_dice, double* sums, void* ws, long long ws_bytes, hipStream_t s);
+void launch_dice_ce_from_sums(const f16* logits, int ld, int n_heads, std::optional<int> ignore_label, const void* target, int target_i64, int B, long long HW,
+                              int batch_dice, float smooth, float weight, float grad_scale, const double* dice_sums, const double* local_sums, int world, float* loss,
+                              f16* dlogits, void* ws, long long ws_bytes, hipStream_t s);
 // every gradient into one flat buffer in one launch, and the buffer's L2 norm (fixed-order reduction)
 void launch_bucket_pack(const float* const* grads, const long long* offsets, const AdamChunk* chunks, long long nchunks, float* bucket, hipStream_t s);
 long long sumsq_ws_bytes(long long n);

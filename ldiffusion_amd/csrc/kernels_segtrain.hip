@@ -191,9 +191,24 @@ __global__ __launch_bounds__(256) void in_apply_kernel(const f16* __restrict__ x
 
 // ---- Dice + cross-entropy of one deep-supervision scale --------------------------------------------------------------------------------------------
 // A thread takes a pixel: its ld = 8 NV logits in NV 16-byte loads, softmax over the n real columns in fp32.  A workgroup owns DCE_PIX consecutive pixels
-// of one image and writes NACC = 3 * 8 NV + 2 partial sums: sum_pred[c], intersect[c], sum_gt[c], the cross-entropy sum, the count of labels outside [0, n).
+// of one image and writes NACC = 3 * 8 NV + 2 + IGN partial sums: sum_pred[c], intersect[c], sum_gt[c], the cross-entropy sum, the count of labels outside
+// [0, n) and, in the ignore form, the count of annotated pixels.
+//
+// IGN is DC_and_CE_loss(ignore_label = k) in the same kernels.  A pixel whose label is `ignore` takes no part: no accumulator sees it, its logits are never
+// loaded (the label is read first), its dlogits row is +0.  The cross-entropy is the sum over annotated pixels over their count -- this process's own -- and
+// 0 when there is none, and the finalize leaves 1 / count (0 for count 0) as a device scalar for the gradient kernel, where the plain form passes
+// 1 / (B HW) by value.  The count of a batch without an ignored pixel is the integer B HW, so that batch gives the plain form's bits.  IGN = false compiles
+// none of this: its kernels have neither the compare nor the arguments.
 constexpr int DCE_PIX = 4096;
-inline int dce_nacc(int NV) { return 3 * 8 * NV + 2; }
+inline int dce_nacc(int NV, bool ign) { return 3 * 8 * NV + 2 + ign; }
+
+// What the ignore form adds to the streaming kernels' arguments, and what the plain form has in their place: chosen so that no other argument of a
+// plain kernel moves (DceNone is one byte of the padding behind `n`; a DceCount<false> is the float it holds).
+struct DceNone {};
+template <bool IGN> using DceIgnore = std::conditional_t<IGN, int, DceNone>;   // the partial kernel: the label to skip / nothing
+template <bool IGN> struct DceCount;                                           // the gradient kernel:
+template <> struct DceCount<false> { float inv; };                             //   1 / (B HW), formed on the host
+template <> struct DceCount<true> { const float* inv; int ignore; };           //   the finalize's 1 / count, and the label to skip
 
 template <int NV>
 __device__ __forceinline__ void dce_softmax(const f16* __restrict__ row, int n, float (&v)[8 * NV], float (&p)[8 * NV], float& log_sum, float& mx) {
@@ -223,22 +238,29 @@ __device__ __forceinline__ int dce_label(const void* __restrict__ target, int i6
   return (int)reinterpret_cast<const unsigned char*>(target)[at];
 }
 
-template <int NV>
+template <int NV, bool IGN>
 __global__ __launch_bounds__(256) void dce_partial_kernel(const f16* __restrict__ logits, const void* __restrict__ target, int i64, long long HW, int n,
-                                                          float* __restrict__ part) {
-  constexpr int NC = 8 * NV, NACC = 3 * NC + 2;
+                                                          DceIgnore<IGN> ignore, float* __restrict__ part) {
+  constexpr int NC = 8 * NV, NACC = 3 * NC + 2 + IGN;
   __shared__ float red[4][NACC];
   const int b = blockIdx.y, tid = threadIdx.x;
   const long long p0 = (long long)blockIdx.x * DCE_PIX, p1 = p0 + DCE_PIX < HW ? p0 + DCE_PIX : HW;
   float sp[NC], si[NC], sg[NC], ce = 0.f, bad = 0.f;
+  [[maybe_unused]] float ann = 0.f;   // IGN: the annotated pixels
 #pragma unroll
   for (int k = 0; k < NC; ++k) sp[k] = si[k] = sg[k] = 0.f;
   for (long long px = p0 + tid; px < p1; px += 256) {
     const long long at = (long long)b * HW + px;
+    int t;
+    if constexpr (IGN) {   // the label first: an ignored pixel's logits are never loaded.  The plain form keeps its order, the logits' loads ahead
+      t = dce_label(target, i64, at);
+      if (t == ignore) continue;
+    }
     float v[NC], p[NC], lse, mx;
     dce_softmax<NV>(logits + at * NC, n, v, p, lse, mx);
-    const int t = dce_label(target, i64, at);
+    if constexpr (!IGN) t = dce_label(target, i64, at);
     if (t >= n) { bad += 1.f; continue; }
+    if constexpr (IGN) ann += 1.f;
     float vt = 0.f;
 #pragma unroll
     for (int k = 0; k < NC; ++k) {
@@ -262,7 +284,11 @@ __global__ __launch_bounds__(256) void dce_partial_kernel(const f16* __restrict_
     if (lane == 0) { red[w][k] = a; red[w][NC + k] = c; red[w][2 * NC + k] = d; }
   }
   ce = wsum(ce); bad = wsum(bad);
-  if (lane == 0) { red[w][3 * NC] = ce; red[w][3 * NC + 1] = bad; }
+  if constexpr (IGN) ann = wsum(ann);
+  if (lane == 0) {
+    red[w][3 * NC] = ce; red[w][3 * NC + 1] = bad;
+    if constexpr (IGN) red[w][3 * NC + 2] = ann;
+  }
   __syncthreads();
   if (tid < NACC) part[((long long)b * gridDim.x + blockIdx.x) * NACC + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
 }
@@ -286,9 +312,13 @@ __device__ __forceinline__ void dce_reduce_sums(const float* __restrict__ part, 
 //   dc = N / max(D, 1e-8);   coef[..][c] = world {2 / (max(D, 1e-8) M),  D < 1e-8 ? 0 : N / (D^2 M)}     d(-mean dc) / d p_c(pixel) = -(coef0 [t == c] - coef1)
 // world = 1 and dsums == lsums is the single-process loss.  Under data parallelism dsums is the sum of the ranks' statistics and world their number: the
 // gathered statistics' backward all-reduces identical rows, so every rank's Dice gradient carries the factor world (x 1.0 is exact).
+// The ignore form is `inv_count` != nullptr (a run-time switch: scalar work of one workgroup, so the finalize kernels exist once): rows of 3 NC + 3, the
+// cross-entropy over lsums' annotated count (exact: every partial count is an integer below 2^24, added in double; 0 when the count is 0), and
+// inv_count[0] = (float)(1 / count), or 0, left for the gradient kernel.  The Dice sums saw annotated pixels only.
 __device__ __forceinline__ void dce_coef_loss(const double* dsums, const double* lsums, int B, long long HW, int n, int NC, int batch_dice, float smooth, double world,
-                                              double* dcs, float* __restrict__ coef, float* __restrict__ loss) {
-  const int NACC = 3 * NC + 2, Bd = batch_dice ? 1 : B, tid = threadIdx.x;
+                                              double* dcs, float* __restrict__ coef, float* __restrict__ loss, float* __restrict__ inv_count) {
+  const bool ign = inv_count != nullptr;
+  const int NACC = 3 * NC + 2 + ign, Bd = batch_dice ? 1 : B, tid = threadIdx.x;
   const double M = (double)Bd * (double)(n - 1);
   for (int e = tid; e < Bd * NC; e += 256) {
     const int bo = e / NC, c = e - bo * NC;
@@ -307,25 +337,28 @@ __device__ __forceinline__ void dce_coef_loss(const double* dsums, const double*
   }
   __syncthreads();
   if (tid == 0) {
-    double dsum = 0.0, ce = 0.0, bad = 0.0;
+    double dsum = 0.0, ce = 0.0, bad = 0.0, count = 0.0;
     for (int e = 0; e < Bd * NC; ++e) dsum += dcs[e];
     for (int bo = 0; bo < Bd; ++bo) {
       ce += lsums[(long long)bo * NACC + 3 * NC];
       bad += lsums[(long long)bo * NACC + 3 * NC + 1];
       if (dsums != lsums) bad += dsums[(long long)bo * NACC + 3 * NC + 1];   // another process's bad label: the exchanged count
+      if (ign) count += lsums[(long long)bo * NACC + 3 * NC + 2];
     }
-    const double v = ce / ((double)B * (double)HW) - dsum / M;
+    if (!ign) count = (double)B * (double)HW;
+    const double v = (count > 0.0 ? ce / count : 0.0) - dsum / M;
     loss[0] = bad > 0.0 ? __builtin_nanf("") : (float)v;   // a label outside [0, n_heads): torch's cross_entropy raises; here the value and that pixel's dlogits are NaN
+    if (ign) inv_count[0] = count > 0.0 ? (float)(1.0 / count) : 0.f;
   }
 }
 
 // One workgroup: both halves, the sums in the workspace.
 __global__ __launch_bounds__(256) void dce_finalize_kernel(const float* __restrict__ part, int chunks, int B, long long HW, int n, int NC, int batch_dice,
                                                            float smooth, double* sums, double* dcs, float* __restrict__ coef,
-                                                           float* __restrict__ loss) {
-  dce_reduce_sums(part, chunks, B, 3 * NC + 2, batch_dice, sums);
+                                                           float* __restrict__ loss, float* __restrict__ inv_count) {
+  dce_reduce_sums(part, chunks, B, 3 * NC + 2 + (inv_count != nullptr), batch_dice, sums);
   __syncthreads();
-  dce_coef_loss(sums, sums, B, HW, n, NC, batch_dice, smooth, 1.0, dcs, coef, loss);
+  dce_coef_loss(sums, sums, B, HW, n, NC, batch_dice, smooth, 1.0, dcs, coef, loss, inv_count);
 }
 
 // The halves as kernels of their own (one workgroup each): the sums leave in a caller's buffer, may be added to other processes', and come back.
@@ -334,14 +367,16 @@ __global__ __launch_bounds__(256) void dce_reduce_kernel(const float* __restrict
 }
 
 __global__ __launch_bounds__(256) void dce_from_sums_kernel(const double* dsums, const double* lsums, int B, long long HW, int n, int NC, int batch_dice, float smooth,
-                                                            int world, double* dcs, float* __restrict__ coef, float* __restrict__ loss) {
-  dce_coef_loss(dsums, lsums, B, HW, n, NC, batch_dice, smooth, (double)world, dcs, coef, loss);
+                                                            int world, double* dcs, float* __restrict__ coef, float* __restrict__ loss,
+                                                            float* __restrict__ inv_count) {
+  dce_coef_loss(dsums, lsums, B, HW, n, NC, batch_dice, smooth, (double)world, dcs, coef, loss, inv_count);
 }
 
-// dlogits[pixel][k] = gsw ((p_k - [k == t]) / (B HW) + p_k (g_k - sum_j p_j g_j)),  g_c = -(coef0_c [t == c] - coef1_c) for c >= 1, g_0 = 0;  pad columns 0
-template <int NV>
+// dlogits[pixel][k] = gsw ((p_k - [k == t]) / count + p_k (g_k - sum_j p_j g_j)),  g_c = -(coef0_c [t == c] - coef1_c) for c >= 1, g_0 = 0;  pad columns 0
+// count is B HW, or in the ignore form the annotated pixels, whose rows these are: an ignored pixel's row is +0, selected by the label alone
+template <int NV, bool IGN>
 __global__ __launch_bounds__(256) void dce_grad_kernel(const f16* __restrict__ logits, const void* __restrict__ target, int i64, long long HW, int n,
-                                                       int batch_dice, const float* __restrict__ coef, float inv_count, float gsw, f16* __restrict__ dlogits) {
+                                                       int batch_dice, const float* __restrict__ coef, DceCount<IGN> count, float gsw, f16* __restrict__ dlogits) {
   constexpr int NC = 8 * NV;
   const int b = blockIdx.y, tid = threadIdx.x;
   const long long p0 = (long long)blockIdx.x * DCE_PIX, p1 = p0 + DCE_PIX < HW ? p0 + DCE_PIX : HW;
@@ -349,11 +384,25 @@ __global__ __launch_bounds__(256) void dce_grad_kernel(const f16* __restrict__ l
   const float* cf = coef + (long long)(batch_dice ? 0 : b) * NC * 2;
 #pragma unroll
   for (int k = 0; k < NC; ++k) { c0[k] = cf[2 * k]; c1[k] = cf[2 * k + 1]; }
+  float inv_count;
+  if constexpr (IGN) inv_count = count.inv[0]; else inv_count = count.inv;
   for (long long px = p0 + tid; px < p1; px += 256) {
     const long long at = (long long)b * HW + px;
+    int t;
+    if constexpr (IGN) {   // as in the partial kernel
+      t = dce_label(target, i64, at);
+      if (t == count.ignore) {
+        f16x8 z;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) z[j] = (f16)0.f;
+#pragma unroll
+        for (int q = 0; q < NV; ++q) *reinterpret_cast<f16x8*>(dlogits + at * NC + 8 * q) = z;
+        continue;
+      }
+    }
     float v[NC], p[NC], lse, mx;
     dce_softmax<NV>(logits + at * NC, n, v, p, lse, mx);
-    const int t = dce_label(target, i64, at);
+    if constexpr (!IGN) t = dce_label(target, i64, at);
     const float poison = t >= n ? __builtin_nanf("") : 0.f;   // a label outside [0, n): the loss is NaN and so is this pixel's gradient, so the step is skipped
     float g[NC], dot = 0.f;
 #pragma unroll
@@ -375,221 +424,48 @@ __global__ __launch_bounds__(256) void dce_grad_kernel(const f16* __restrict__ l
   }
 }
 
-template <int NV>
-void dce_launch(const f16* logits, const void* target, int i64, int B, long long HW, int n, int batch_dice, float smooth, float gsw, float* loss, f16* dlogits,
-                double* sums, double* dcs, float* coef, float* part, hipStream_t s) {
+// The launchers' arguments that depend on the form: `ignore` is read only where IGN, `inv_count` (the workspace's scalar) is null in the plain form.
+template <bool IGN>
+DceIgnore<IGN> dce_ignore_arg(int ignore) {
+  if constexpr (IGN) return ignore; else return {};
+}
+template <bool IGN>
+DceCount<IGN> dce_count_arg(int B, long long HW, const float* inv_count, int ignore) {
+  if constexpr (IGN) return {inv_count, ignore}; else return {(float)(1.0 / ((double)B * (double)HW))};
+}
+
+template <int NV, bool IGN>
+void dce_launch(const f16* logits, const void* target, int i64, int B, long long HW, int n, int ignore, int batch_dice, float smooth, float gsw, float* loss,
+                f16* dlogits, double* sums, double* dcs, float* coef, float* inv_count, float* part, hipStream_t s) {
   const int chunks = (int)((HW + DCE_PIX - 1) / DCE_PIX);
   const dim3 grid(chunks, B);
-  hipLaunchKernelGGL(dce_partial_kernel<NV>, grid, dim3(256), 0, s, logits, target, i64, HW, n, part);
+  hipLaunchKernelGGL((dce_partial_kernel<NV, IGN>), grid, dim3(256), 0, s, logits, target, i64, HW, n, dce_ignore_arg<IGN>(ignore), part);
   HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(dce_finalize_kernel, dim3(1), dim3(256), 0, s, part, chunks, B, HW, n, 8 * NV, batch_dice, smooth, sums, dcs, coef, loss);
+  hipLaunchKernelGGL(dce_finalize_kernel, dim3(1), dim3(256), 0, s, part, chunks, B, HW, n, 8 * NV, batch_dice, smooth, sums, dcs, coef, loss, inv_count);
   HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(dce_grad_kernel<NV>, grid, dim3(256), 0, s, logits, target, i64, HW, n, batch_dice, coef, (float)(1.0 / ((double)B * (double)HW)), gsw, dlogits);
-  HIP_CHECK(hipGetLastError());
-}
-
-template <int NV>
-void dce_stats_launch(const f16* logits, const void* target, int i64, int B, long long HW, int n, int batch_dice, double* sums_out, float* part, hipStream_t s) {
-  const int chunks = (int)((HW + DCE_PIX - 1) / DCE_PIX);
-  hipLaunchKernelGGL(dce_partial_kernel<NV>, dim3(chunks, B), dim3(256), 0, s, logits, target, i64, HW, n, part);
-  HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(dce_reduce_kernel, dim3(1), dim3(256), 0, s, part, chunks, B, dce_nacc(NV), batch_dice, sums_out);
-  HIP_CHECK(hipGetLastError());
-}
-
-template <int NV>
-void dce_from_sums_launch(const f16* logits, const void* target, int i64, int B, long long HW, int n, int batch_dice, float smooth, float gsw, const double* dsums,
-                          const double* lsums, int world, float* loss, f16* dlogits, double* dcs, float* coef, hipStream_t s) {
-  const int chunks = (int)((HW + DCE_PIX - 1) / DCE_PIX);
-  hipLaunchKernelGGL(dce_from_sums_kernel, dim3(1), dim3(256), 0, s, dsums, lsums, B, HW, n, 8 * NV, batch_dice, smooth, world, dcs, coef, loss);
-  HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(dce_grad_kernel<NV>, dim3(chunks, B), dim3(256), 0, s, logits, target, i64, HW, n, batch_dice, coef, (float)(1.0 / ((double)B * (double)HW)), gsw,
+  hipLaunchKernelGGL((dce_grad_kernel<NV, IGN>), grid, dim3(256), 0, s, logits, target, i64, HW, n, batch_dice, coef, dce_count_arg<IGN>(B, HW, inv_count, ignore), gsw,
                      dlogits);
   HIP_CHECK(hipGetLastError());
 }
 
-// ---- the ignore form: DC_and_CE_loss(ignore_label = k) -----------------------------------------------------------------------------------------------
-// A pixel whose label is `ignore` takes no part: none of the four accumulators sees it, its logits are never loaded, its dlogits row is +0.  The partial
-// row gains one slot, the count of annotated pixels (NACC = 3 * 8 NV + 3; the bad-label slot keeps its place); the cross-entropy is the sum over annotated
-// pixels over their count -- this process's own -- and 0 when there is none, and the finalize leaves 1 / count (0 for count 0) as a device scalar for the
-// gradient kernel.  These are kernels of their own, so the plain form's code is what it was; every statement that forms a value is the plain form's, in
-// its order, and the count of a batch without an ignored pixel is the integer B HW, so that batch gives the plain form's bits.
-inline int dce_nacc_ign(int NV) { return 3 * 8 * NV + 3; }
-
-template <int NV>
-__global__ __launch_bounds__(256) void dce_partial_ign_kernel(const f16* __restrict__ logits, const void* __restrict__ target, int i64, long long HW, int n,
-                                                              int ignore, float* __restrict__ part) {
-  constexpr int NC = 8 * NV, NACC = 3 * NC + 3;
-  __shared__ float red[4][NACC];
-  const int b = blockIdx.y, tid = threadIdx.x;
-  const long long p0 = (long long)blockIdx.x * DCE_PIX, p1 = p0 + DCE_PIX < HW ? p0 + DCE_PIX : HW;
-  float sp[NC], si[NC], sg[NC], ce = 0.f, bad = 0.f, ann = 0.f;
-#pragma unroll
-  for (int k = 0; k < NC; ++k) sp[k] = si[k] = sg[k] = 0.f;
-  for (long long px = p0 + tid; px < p1; px += 256) {
-    const long long at = (long long)b * HW + px;
-    const int t = dce_label(target, i64, at);
-    if (t == ignore) continue;
-    float v[NC], p[NC], lse, mx;
-    dce_softmax<NV>(logits + at * NC, n, v, p, lse, mx);
-    if (t >= n) { bad += 1.f; continue; }
-    ann += 1.f;
-    float vt = 0.f;
-#pragma unroll
-    for (int k = 0; k < NC; ++k) {
-      const bool hit = k == t;
-      sp[k] += p[k];
-      si[k] += hit ? p[k] : 0.f;
-      sg[k] += hit ? 1.f : 0.f;
-      vt = hit ? v[k] : vt;
-    }
-    ce += lse + mx - vt;
-  }
-  const int lane = tid & 63, w = tid >> 6;
-  auto wsum = [](float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-  };
-#pragma unroll
-  for (int k = 0; k < NC; ++k) {
-    const float a = wsum(sp[k]), c = wsum(si[k]), d = wsum(sg[k]);
-    if (lane == 0) { red[w][k] = a; red[w][NC + k] = c; red[w][2 * NC + k] = d; }
-  }
-  ce = wsum(ce); bad = wsum(bad); ann = wsum(ann);
-  if (lane == 0) { red[w][3 * NC] = ce; red[w][3 * NC + 1] = bad; red[w][3 * NC + 2] = ann; }
-  __syncthreads();
-  if (tid < NACC) part[((long long)b * gridDim.x + blockIdx.x) * NACC + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-}
-
-// dce_coef_loss for one process (world = 1, the Dice sums are the local ones: the data-parallel exchange of the ignore form is not built) with the
-// cross-entropy over the annotated count (exact: every partial count is an integer below 2^24, added in double), which also leaves as
-// inv_count[0] = (float)(1 / count), or 0 where no pixel of the batch is annotated.  The Dice sums saw annotated pixels only.
-__device__ __forceinline__ void dce_coef_loss_ign(const double* sums, int B, int n, int NC, int batch_dice, float smooth, double* dcs, float* __restrict__ coef,
-                                                  float* __restrict__ loss, float* __restrict__ inv_count) {
-  const int NACC = 3 * NC + 3, Bd = batch_dice ? 1 : B, tid = threadIdx.x;
-  const double M = (double)Bd * (double)(n - 1);
-  for (int e = tid; e < Bd * NC; e += 256) {
-    const int bo = e / NC, c = e - bo * NC;
-    double dc = 0.0, c0 = 0.0, c1 = 0.0;
-    if (c >= 1 && c < n) {
-      const double* s = sums + (long long)bo * NACC;
-      const double D = s[2 * NC + c] + s[c] + (double)smooth, N = 2.0 * s[NC + c] + (double)smooth;
-      const double Dc = D < 1e-8 ? 1e-8 : D;
-      dc = N / Dc;
-      c0 = 2.0 / (Dc * M);
-      c1 = D < 1e-8 ? 0.0 : N / (D * D * M);
-    }
-    dcs[e] = dc;
-    coef[(long long)e * 2] = (float)c0;   // the plain form's c0 * world at world = 1 (x 1.0 is exact)
-    coef[(long long)e * 2 + 1] = (float)c1;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    double dsum = 0.0, ce = 0.0, bad = 0.0, count = 0.0;
-    for (int e = 0; e < Bd * NC; ++e) dsum += dcs[e];
-    for (int bo = 0; bo < Bd; ++bo) {
-      ce += sums[(long long)bo * NACC + 3 * NC];
-      bad += sums[(long long)bo * NACC + 3 * NC + 1];
-      count += sums[(long long)bo * NACC + 3 * NC + 2];
-    }
-    const double v = (count > 0.0 ? ce / count : 0.0) - dsum / M;
-    loss[0] = bad > 0.0 ? __builtin_nanf("") : (float)v;
-    inv_count[0] = count > 0.0 ? (float)(1.0 / count) : 0.f;
-  }
-}
-
-__global__ __launch_bounds__(256) void dce_finalize_ign_kernel(const float* __restrict__ part, int chunks, int B, int n, int NC, int batch_dice, float smooth,
-                                                               double* sums, double* dcs, float* __restrict__ coef, float* __restrict__ loss,
-                                                               float* __restrict__ inv_count) {
-  dce_reduce_sums(part, chunks, B, 3 * NC + 3, batch_dice, sums);
-  __syncthreads();
-  dce_coef_loss_ign(sums, B, n, NC, batch_dice, smooth, dcs, coef, loss, inv_count);
-}
-
-__global__ __launch_bounds__(256) void dce_from_sums_ign_kernel(const double* sums, int B, int n, int NC, int batch_dice, float smooth, double* dcs,
-                                                                float* __restrict__ coef, float* __restrict__ loss, float* __restrict__ inv_count) {
-  dce_coef_loss_ign(sums, B, n, NC, batch_dice, smooth, dcs, coef, loss, inv_count);
-}
-
-// dce_grad_kernel's row for an annotated pixel, with 1 / count read from the finalize's scalar; for an ignored one the zero row is selected by the label
-// alone, ahead of the logits' load
-template <int NV>
-__global__ __launch_bounds__(256) void dce_grad_ign_kernel(const f16* __restrict__ logits, const void* __restrict__ target, int i64, long long HW, int n,
-                                                           int ignore, int batch_dice, const float* __restrict__ coef,
-                                                           const float* __restrict__ inv_count_p, float gsw, f16* __restrict__ dlogits) {
-  constexpr int NC = 8 * NV;
-  const int b = blockIdx.y, tid = threadIdx.x;
-  const long long p0 = (long long)blockIdx.x * DCE_PIX, p1 = p0 + DCE_PIX < HW ? p0 + DCE_PIX : HW;
-  float c0[NC], c1[NC];
-  const float* cf = coef + (long long)(batch_dice ? 0 : b) * NC * 2;
-#pragma unroll
-  for (int k = 0; k < NC; ++k) { c0[k] = cf[2 * k]; c1[k] = cf[2 * k + 1]; }
-  const float inv_count = inv_count_p[0];
-  for (long long px = p0 + tid; px < p1; px += 256) {
-    const long long at = (long long)b * HW + px;
-    const int t = dce_label(target, i64, at);
-    if (t == ignore) {
-      f16x8 z;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) z[j] = (f16)0.f;
-#pragma unroll
-      for (int q = 0; q < NV; ++q) *reinterpret_cast<f16x8*>(dlogits + at * NC + 8 * q) = z;
-      continue;
-    }
-    float v[NC], p[NC], lse, mx;
-    dce_softmax<NV>(logits + at * NC, n, v, p, lse, mx);
-    const float poison = t >= n ? __builtin_nanf("") : 0.f;
-    float g[NC], dot = 0.f;
-#pragma unroll
-    for (int k = 0; k < NC; ++k) {
-      g[k] = c1[k] - (k == t ? c0[k] : 0.f);
-      dot += p[k] * g[k];
-    }
-#pragma unroll
-    for (int q = 0; q < NV; ++q) {
-      f16x8 o;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int k = 8 * q + j;
-        const float d = (p[k] - (k == t ? 1.f : 0.f)) * inv_count + p[k] * (g[k] - dot);
-        o[j] = (f16)(k < n ? gsw * d + poison : 0.f);
-      }
-      *reinterpret_cast<f16x8*>(dlogits + at * NC + 8 * q) = o;
-    }
-  }
-}
-
-template <int NV>
-void dce_ign_launch(const f16* logits, const void* target, int i64, int B, long long HW, int n, int ignore, int batch_dice, float smooth, float gsw, float* loss,
-                    f16* dlogits, double* sums, double* dcs, float* coef, float* inv_count, float* part, hipStream_t s) {
+template <int NV, bool IGN>
+void dce_stats_launch(const f16* logits, const void* target, int i64, int B, long long HW, int n, int ignore, int batch_dice, double* sums_out, float* part,
+                      hipStream_t s) {
   const int chunks = (int)((HW + DCE_PIX - 1) / DCE_PIX);
-  const dim3 grid(chunks, B);
-  hipLaunchKernelGGL(dce_partial_ign_kernel<NV>, grid, dim3(256), 0, s, logits, target, i64, HW, n, ignore, part);
+  hipLaunchKernelGGL((dce_partial_kernel<NV, IGN>), dim3(chunks, B), dim3(256), 0, s, logits, target, i64, HW, n, dce_ignore_arg<IGN>(ignore), part);
   HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(dce_finalize_ign_kernel, dim3(1), dim3(256), 0, s, part, chunks, B, n, 8 * NV, batch_dice, smooth, sums, dcs, coef, loss, inv_count);
-  HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(dce_grad_ign_kernel<NV>, grid, dim3(256), 0, s, logits, target, i64, HW, n, ignore, batch_dice, coef, inv_count, gsw, dlogits);
+  hipLaunchKernelGGL(dce_reduce_kernel, dim3(1), dim3(256), 0, s, part, chunks, B, dce_nacc(NV, IGN), batch_dice, sums_out);
   HIP_CHECK(hipGetLastError());
 }
 
-template <int NV>
-void dce_ign_stats_launch(const f16* logits, const void* target, int i64, int B, long long HW, int n, int ignore, int batch_dice, double* sums_out, float* part,
-                          hipStream_t s) {
+template <int NV, bool IGN>
+void dce_from_sums_launch(const f16* logits, const void* target, int i64, int B, long long HW, int n, int ignore, int batch_dice, float smooth, float gsw,
+                          const double* dsums, const double* lsums, int world, float* loss, f16* dlogits, double* dcs, float* coef, float* inv_count, hipStream_t s) {
   const int chunks = (int)((HW + DCE_PIX - 1) / DCE_PIX);
-  hipLaunchKernelGGL(dce_partial_ign_kernel<NV>, dim3(chunks, B), dim3(256), 0, s, logits, target, i64, HW, n, ignore, part);
+  hipLaunchKernelGGL(dce_from_sums_kernel, dim3(1), dim3(256), 0, s, dsums, lsums, B, HW, n, 8 * NV, batch_dice, smooth, world, dcs, coef, loss, inv_count);
   HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(dce_reduce_kernel, dim3(1), dim3(256), 0, s, part, chunks, B, dce_nacc_ign(NV), batch_dice, sums_out);
-  HIP_CHECK(hipGetLastError());
-}
-
-template <int NV>
-void dce_ign_from_sums_launch(const f16* logits, const void* target, int i64, int B, long long HW, int n, int ignore, int batch_dice, float smooth, float gsw,
-                              const double* sums, float* loss, f16* dlogits, double* dcs, float* coef, float* inv_count, hipStream_t s) {
-  const int chunks = (int)((HW + DCE_PIX - 1) / DCE_PIX);
-  hipLaunchKernelGGL(dce_from_sums_ign_kernel, dim3(1), dim3(256), 0, s, sums, B, n, 8 * NV, batch_dice, smooth, dcs, coef, loss, inv_count);
-  HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(dce_grad_ign_kernel<NV>, dim3(chunks, B), dim3(256), 0, s, logits, target, i64, HW, n, ignore, batch_dice, coef, inv_count, gsw, dlogits);
+  hipLaunchKernelGGL((dce_grad_kernel<NV, IGN>), dim3(chunks, B), dim3(256), 0, s, logits, target, i64, HW, n, batch_dice, coef,
+                     dce_count_arg<IGN>(B, HW, inv_count, ignore), gsw, dlogits);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -730,52 +606,66 @@ void launch_in_train_bwd(const f16* x, const f16* dy, const float* gamma, const 
   HIP_CHECK(hipGetLastError());
 }
 
-// workspace: doubles sums[B][NACC], dcs[B][NC]; floats coef[B][NC][2], part[B][chunks][NACC].  dice_ce uses all four; stats `part`, from_sums `dcs` and `coef`
+// workspace: doubles sums[B][NACC], dcs[B][NC]; floats coef[B][NC][2], in the ignore form the 1 / count scalar, part[B][chunks][NACC].  dice_ce uses all of
+// them; stats `part`, from_sums `dcs`, `coef` and the scalar.  inv_count is null in the plain form, which is how the finalize kernels tell the forms apart.
 struct DceWs {
   int NV;
+  bool ign;
   double *sums, *dcs;
-  float *coef, *part;
+  float *coef, *inv_count, *part;
   long long bytes;
-  DceWs(void* ws, int B, long long HW, int n_heads) : NV((n_heads + 7) / 8) {
-    const int NC = 8 * NV, NACC = dce_nacc(NV);
+  DceWs(void* ws, int B, long long HW, int n_heads, bool ign) : NV((n_heads + 7) / 8), ign(ign) {
+    const int NC = 8 * NV, NACC = dce_nacc(NV, ign);
     const long long chunks = (HW + DCE_PIX - 1) / DCE_PIX;
     sums = (double*)ws;
     dcs = sums + (long long)B * NACC;
     coef = (float*)(dcs + (long long)B * NC);
-    part = coef + (long long)B * NC * 2;
-    bytes = ((long long)B * NACC + (long long)B * NC) * 8 + ((long long)B * NC * 2 + (long long)B * chunks * NACC) * 4;
+    inv_count = ign ? coef + (long long)B * NC * 2 : nullptr;
+    part = coef + (long long)B * NC * 2 + ign;
+    bytes = ((long long)B * NACC + (long long)B * NC) * 8 + ((long long)B * NC * 2 + ign + (long long)B * chunks * NACC) * 4;
   }
 };
 
-long long dice_ce_ws_bytes(int B, long long HW, int n_heads) { return DceWs(nullptr, B, HW, n_heads).bytes; }
+long long dice_ce_ws_bytes(int B, long long HW, int n_heads, bool ign) { return DceWs(nullptr, B, HW, n_heads, ign).bytes; }
+int dice_ce_nacc(int n_heads, bool ign) { return dce_nacc((n_heads + 7) / 8, ign); }
 
-static DceWs dice_ce_check(const char* what, int ld, int n_heads, int B, long long HW, void* ws, long long ws_bytes) {
+// the shape rules of the three entries and their workspace; with an ignore label, that label's rule and the ignore form's layout
+static DceWs dice_ce_check(const char* what, int ld, int n_heads, std::optional<int> ignore_label, int B, long long HW, void* ws, long long ws_bytes) {
+  const bool ign = ignore_label.has_value();
   LDIFF_CHECK(n_heads >= 2 && n_heads <= 32, LDIFF_ERR_INVALID, "%s: %d heads (2 .. 32: background and at least one foreground class)", what, n_heads);
   LDIFF_CHECK(ld == 8 * ((n_heads + 7) / 8), LDIFF_ERR_INVALID, "%s: row pitch %d, roundup(n_heads, 8) = %d expected (the seg layer's output layout)", what, ld,
               8 * ((n_heads + 7) / 8));
   LDIFF_CHECK(B >= 1 && HW >= 1 && HW <= (1ll << 40), LDIFF_ERR_INVALID, "%s: B=%d HW=%lld", what, B, HW);
   LDIFF_CHECK(B <= 65535, LDIFF_ERR_INVALID, "%s: B=%d exceeds the grid's second dimension", what, B);
-  const DceWs w(ws, B, HW, n_heads);
-  LDIFF_CHECK(ws_bytes >= w.bytes, LDIFF_ERR_INVALID, "%s: workspace of %lld bytes, %lld needed (ldiff_op_dice_ce_ws_bytes)", what, ws_bytes, w.bytes);
+  LDIFF_CHECK(!ign || (*ignore_label >= n_heads && *ignore_label <= 254), LDIFF_ERR_INVALID,
+              "%s: ignore label %d (n_heads = %d .. 254: no class, and not 255, which every int64 label outside a byte's range is read as)", what,
+              ignore_label.value_or(-1), n_heads);
+  const DceWs w(ws, B, HW, n_heads, ign);
+  LDIFF_CHECK(ws_bytes >= w.bytes, LDIFF_ERR_INVALID, "%s: workspace of %lld bytes, %lld needed (ldiff_op_dice_ce%s_ws_bytes)", what, ws_bytes, w.bytes,
+              ign ? "_ignore" : "");
   return w;
 }
 
-// f(integral constant NV): the launchers are templates on the number of 8-column vectors of a logits row
+// f(integral constant NV, bool constant IGN): the launchers are templates on the number of 8-column vectors of a logits row and on the form
 template <class F>
-static void dce_dispatch(int NV, F&& f) {
-  switch (NV) {
-    case 1: f(std::integral_constant<int, 1>{}); break;
-    case 2: f(std::integral_constant<int, 2>{}); break;
-    case 3: f(std::integral_constant<int, 3>{}); break;
-    default: f(std::integral_constant<int, 4>{}); break;
-  }
+static void dce_dispatch(const DceWs& w, F&& f) {
+  auto by_nv = [&](auto ign) {
+    switch (w.NV) {
+      case 1: f(std::integral_constant<int, 1>{}, ign); break;
+      case 2: f(std::integral_constant<int, 2>{}, ign); break;
+      case 3: f(std::integral_constant<int, 3>{}, ign); break;
+      default: f(std::integral_constant<int, 4>{}, ign); break;
+    }
+  };
+  if (w.ign) by_nv(std::true_type{}); else by_nv(std::false_type{});
 }
 
-void launch_dice_ce(const f16* logits, int ld, int n_heads, const void* target, int target_i64, int B, long long HW, int batch_dice, float smooth, float weight,
-                    float grad_scale, float* loss, f16* dlogits, void* ws, long long ws_bytes, hipStream_t s) {
-  const DceWs w = dice_ce_check("dice_ce", ld, n_heads, B, HW, ws, ws_bytes);
-  dce_dispatch(w.NV, [&](auto nv) {
-    dce_launch<decltype(nv)::value>(logits, target, target_i64, B, HW, n_heads, batch_dice, smooth, weight * grad_scale, loss, dlogits, w.sums, w.dcs, w.coef, w.part, s);
+void launch_dice_ce(const f16* logits, int ld, int n_heads, std::optional<int> ignore_label, const void* target, int target_i64, int B, long long HW, int batch_dice,
+                    float smooth, float weight, float grad_scale, float* loss, f16* dlogits, void* ws, long long ws_bytes, hipStream_t s) {
+  const DceWs w = dice_ce_check(ignore_label ? "dice_ce_ignore" : "dice_ce", ld, n_heads, ignore_label, B, HW, ws, ws_bytes);
+  dce_dispatch(w, [&](auto nv, auto ign) {
+    dce_launch<decltype(nv)::value, decltype(ign)::value>(logits, target, target_i64, B, HW, n_heads, ignore_label.value_or(0), batch_dice, smooth, weight * grad_scale,
+                                                          loss, dlogits, w.sums, w.dcs, w.coef, w.inv_count, w.part, s);
   });
 }
 
@@ -786,79 +676,25 @@ void launch_sgd_nesterov_multi(const SgdTensor* tensors, const float* const* gra
   HIP_CHECK(hipGetLastError());
 }
 
-void launch_dice_ce_stats(const f16* logits, int ld, int n_heads, const void* target, int target_i64, int B, long long HW, int batch_dice, double* sums, void* ws,
-                          long long ws_bytes, hipStream_t s) {
-  const DceWs w = dice_ce_check("dice_ce_stats", ld, n_heads, B, HW, ws, ws_bytes);
-  dce_dispatch(w.NV, [&](auto nv) { dce_stats_launch<decltype(nv)::value>(logits, target, target_i64, B, HW, n_heads, batch_dice, sums, w.part, s); });
+void launch_dice_ce_stats(const f16* logits, int ld, int n_heads, std::optional<int> ignore_label, const void* target, int target_i64, int B, long long HW,
+                          int batch_dice, double* sums, void* ws, long long ws_bytes, hipStream_t s) {
+  const DceWs w = dice_ce_check(ignore_label ? "dice_ce_ignore_stats" : "dice_ce_stats", ld, n_heads, ignore_label, B, HW, ws, ws_bytes);
+  dce_dispatch(w, [&](auto nv, auto ign) {
+    dce_stats_launch<decltype(nv)::value, decltype(ign)::value>(logits, target, target_i64, B, HW, n_heads, ignore_label.value_or(0), batch_dice, sums, w.part, s);
+  });
 }
 
-void launch_dice_ce_from_sums(const f16* logits, int ld, int n_heads, const void* target, int target_i64, int B, long long HW, int batch_dice, float smooth,
-                              float weight, float grad_scale, const double* dice_sums, const double* local_sums, int world, float* loss, f16* dlogits, void* ws,
-                              long long ws_bytes, hipStream_t s) {
-  const DceWs w = dice_ce_check("dice_ce_from_sums", ld, n_heads, B, HW, ws, ws_bytes);
-  LDIFF_CHECK(world >= 1, LDIFF_ERR_INVALID, "dice_ce_from_sums: world=%d", world);
+void launch_dice_ce_from_sums(const f16* logits, int ld, int n_heads, std::optional<int> ignore_label, const void* target, int target_i64, int B, long long HW,
+                              int batch_dice, float smooth, float weight, float grad_scale, const double* dice_sums, const double* local_sums, int world, float* loss,
+                              f16* dlogits, void* ws, long long ws_bytes, hipStream_t s) {
+  const char* what = ignore_label ? "dice_ce_ignore_from_sums" : "dice_ce_from_sums";
+  const DceWs w = dice_ce_check(what, ld, n_heads, ignore_label, B, HW, ws, ws_bytes);
+  LDIFF_CHECK(world >= 1, LDIFF_ERR_INVALID, "%s: world=%d", what, world);
   LDIFF_CHECK(batch_dice || (world == 1 && dice_sums == local_sums), LDIFF_ERR_INVALID,
-              "dice_ce_from_sums: without batch_dice the Dice term is per sample and stays local (world = 1, dice_sums = local_sums)");
-  dce_dispatch(w.NV, [&](auto nv) {
-    dce_from_sums_launch<decltype(nv)::value>(logits, target, target_i64, B, HW, n_heads, batch_dice, smooth, weight * grad_scale, dice_sums, local_sums, world, loss,
-                                              dlogits, w.dcs, w.coef, s);
-  });
-}
-
-// The ignore form's workspace: DceWs's four arrays at the wider row, then the 1 / count scalar.
-struct DceIgnWs {
-  int NV;
-  double *sums, *dcs;
-  float *coef, *inv_count, *part;
-  long long bytes;
-  DceIgnWs(void* ws, int B, long long HW, int n_heads) : NV((n_heads + 7) / 8) {
-    const int NC = 8 * NV, NACC = dce_nacc_ign(NV);
-    const long long chunks = (HW + DCE_PIX - 1) / DCE_PIX;
-    sums = (double*)ws;
-    dcs = sums + (long long)B * NACC;
-    coef = (float*)(dcs + (long long)B * NC);
-    inv_count = coef + (long long)B * NC * 2;
-    part = inv_count + 1;
-    bytes = ((long long)B * NACC + (long long)B * NC) * 8 + ((long long)B * NC * 2 + 1 + (long long)B * chunks * NACC) * 4;
-  }
-};
-
-long long dice_ce_ignore_ws_bytes(int B, long long HW, int n_heads) { return DceIgnWs(nullptr, B, HW, n_heads).bytes; }
-int dice_ce_ignore_nacc(int n_heads) { return dce_nacc_ign((n_heads + 7) / 8); }
-
-static DceIgnWs dice_ce_ignore_check(const char* what, int ld, int n_heads, int ignore_label, int B, long long HW, void* ws, long long ws_bytes) {
-  dice_ce_check(what, ld, n_heads, B, HW, ws, 1ll << 62);   // the shape rules of the plain form; the workspace is this form's own
-  LDIFF_CHECK(ignore_label >= n_heads && ignore_label <= 254, LDIFF_ERR_INVALID,
-              "%s: ignore label %d (n_heads = %d .. 254: no class, and not 255, which every int64 label outside a byte's range is read as)", what, ignore_label, n_heads);
-  const DceIgnWs w(ws, B, HW, n_heads);
-  LDIFF_CHECK(ws_bytes >= w.bytes, LDIFF_ERR_INVALID, "%s: workspace of %lld bytes, %lld needed (ldiff_op_dice_ce_ignore_ws_bytes)", what, ws_bytes, w.bytes);
-  return w;
-}
-
-void launch_dice_ce_ignore(const f16* logits, int ld, int n_heads, int ignore_label, const void* target, int target_i64, int B, long long HW, int batch_dice,
-                           float smooth, float weight, float grad_scale, float* loss, f16* dlogits, void* ws, long long ws_bytes, hipStream_t s) {
-  const DceIgnWs w = dice_ce_ignore_check("dice_ce_ignore", ld, n_heads, ignore_label, B, HW, ws, ws_bytes);
-  dce_dispatch(w.NV, [&](auto nv) {
-    dce_ign_launch<decltype(nv)::value>(logits, target, target_i64, B, HW, n_heads, ignore_label, batch_dice, smooth, weight * grad_scale, loss, dlogits, w.sums, w.dcs,
-                                        w.coef, w.inv_count, w.part, s);
-  });
-}
-
-void launch_dice_ce_ignore_stats(const f16* logits, int ld, int n_heads, int ignore_label, const void* target, int target_i64, int B, long long HW, int batch_dice,
-                                 double* sums, void* ws, long long ws_bytes, hipStream_t s) {
-  const DceIgnWs w = dice_ce_ignore_check("dice_ce_ignore_stats", ld, n_heads, ignore_label, B, HW, ws, ws_bytes);
-  dce_dispatch(w.NV, [&](auto nv) {
-    dce_ign_stats_launch<decltype(nv)::value>(logits, target, target_i64, B, HW, n_heads, ignore_label, batch_dice, sums, w.part, s);
-  });
-}
-
-void launch_dice_ce_ignore_from_sums(const f16* logits, int ld, int n_heads, int ignore_label, const void* target, int target_i64, int B, long long HW,
-                                     int batch_dice, float smooth, float weight, float grad_scale, const double* sums, float* loss, f16* dlogits, void* ws,
-                                     long long ws_bytes, hipStream_t s) {
-  const DceIgnWs w = dice_ce_ignore_check("dice_ce_ignore_from_sums", ld, n_heads, ignore_label, B, HW, ws, ws_bytes);
-  dce_dispatch(w.NV, [&](auto nv) {
-    dce_ign_from_sums_launch<decltype(nv)::value>(logits, target, target_i64, B, HW, n_heads, ignore_label, batch_dice, smooth, weight * grad_scale, sums, loss,
-                                                  dlogits, w.dcs, w.coef, w.inv_count, s);
+              "%s: without batch_dice the Dice term is per sample and stays local (world = 1, dice_sums = local_sums)", what);
+  dce_dispatch(w, [&](auto nv, auto ign) {
+    dce_from_sums_launch<decltype(nv)::value, decltype(ign)::value>(logits, target, target_i64, B, HW, n_heads, ignore_label.value_or(0), batch_dice, smooth,
+                                                                    weight * grad_scale, dice_sums, local_sums, world, loss, dlogits, w.dcs, w.coef, w.inv_count, s);
   });
 }
 

@@ -53,9 +53,13 @@ def run(logits, target, n, batch_dice, ignore, weight=WEIGHT, grad_scale=SCALE):
 
 SHAPES = [(15, 13), (48, 40), (72, 64)]   # fewer pixels than a workgroup has threads; one ragged chunk of DCE_PIX = 4096; one full chunk plus 512 pixels
 KERNEL_CASES = [(n, hw, bd, i64) for n in (3, 9) for hw in SHAPES for bd in (True, False) for i64 in (False, True)]
+# row pitches 24 and 32, the kernels' NV = 3 and NV = 4 instantiations.  The leading number is the case's seed offset, picked on the CPU so that
+# ignore_blobs ends within the fraction asserted below and every class keeps an annotated pixel in each image
+WIDE_CASES = [(24, 17, (72, 64), True, True), (25, 17, (72, 64), False, True), (26, 17, (15, 13), True, True), (27, 17, (15, 13), False, True),
+              (28, 32, (72, 64), True, True), (29, 32, (72, 64), False, True), (31, 32, (15, 13), True, True), (33, 32, (15, 13), False, True)]
 
 
-@pytest.mark.parametrize("i,n,hw,batch_dice,i64", [(i,) + c for i, c in enumerate(KERNEL_CASES)])
+@pytest.mark.parametrize("i,n,hw,batch_dice,i64", [(i,) + c for i, c in enumerate(KERNEL_CASES)] + WIDE_CASES)
 def test_dice_ce_ignore_against_float64(lib, i, n, hw, batch_dice, i64):
     """Value and dlogits of the ignore form against the float64 restatement (pinned to the reference's modules by tests/test_cpu_nnunet_ignore.py) within
     nnunet_ignore_ref.loss_bounds; every ignored pixel's row exactly zero, pad columns exactly zero, two launches bit-identical; the bound rejects the

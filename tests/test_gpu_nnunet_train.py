@@ -190,13 +190,17 @@ def loss_bounds(logits, target, n, batch_dice, weight, grad_scale):
 
 LOSS_CASES = [(n, shape, bd, i64, gs, absent) for n in (4, 7, 11) for shape in ((2, 4, 4), (1, 24, 40), (2, 64, 64)) for bd in (True, False)
               for i64 in (False, True) for gs in (1.0, 65536.0) for absent in (False, True)]
+# row pitches 24 and 32, the kernels' NV = 3 and NV = 4 instantiations: one full chunk of DCE_PIX pixels plus a ragged one, and fewer pixels than a
+# workgroup has threads; at the loss scale that keeps the gradient's entries in fp16's normal range, where the bound is a relative one
+LOSS_CASES += [(n, (2,) + hw, bd, True, 65536.0, False) for n in (17, 32) for hw in ((72, 64), (15, 13)) for bd in (True, False)]
 
 
 @pytest.mark.parametrize("i,n,shape,batch_dice,i64,grad_scale,absent", [(i,) + c for i, c in enumerate(LOSS_CASES)])
 def test_dice_ce_against_float64(lib, i, n, shape, batch_dice, i64, grad_scale, absent):
     """Value and dlogits of ldiff_op_dice_ce against the float64 restatement (pinned to the reference's modules by tests/test_cpu_nnunet_train.py), over the
     full product of: n_heads 4 / 7 / 11 (row pitch 8 / 8 / 16); fewer pixels than a workgroup's share, an odd size, two workgroups per image; batch_dice
-    on / off; uint8 / int64 labels; loss scale 1 / 65536; every class present / a foreground class absent from the target.  Pad columns exactly zero; two
+    on / off; uint8 / int64 labels; loss scale 1 / 65536; every class present / a foreground class absent from the target; and n_heads 17 / 32 (row pitch
+    24 / 32) at two sizes with both batch_dice values.  Pad columns exactly zero; two
     launches bit-identical; the bound rejects do_bg = True, smooth = 1 and, for a batch of more than one image, the flipped batch_dice (by the value or by
     an entry of the gradient)."""
     B, H, W = shape
