@@ -33,6 +33,12 @@ def dc_ce_loss(logits, target, batch_dice, do_bg=False, smooth=1e-5):
     return ce - dc.mean()
 
 
+def first_pass_dice_loss(logits, target, keep, loss, ce):
+    """A WRONG loss the bounds must reject: the cross-entropy `ce(logits, target)` of the whole batch, the Dice term of `loss` from samples < keep alone
+    (what the finalize's first pass over its [sample][accumulator] slots covers).  `loss`, `ce`: callables on (logits [b, n, H, W], target [b, H, W])."""
+    return ce(logits, target) + loss(logits[:keep], target[:keep]) - ce(logits[:keep], target[:keep])
+
+
 def deep_supervision_loss(outputs, targets, weights, batch_dice, **kw):
     return sum(w * dc_ce_loss(o, t, batch_dice, **kw) for o, t, w in zip(outputs, targets, weights) if w != 0.0)
 
@@ -102,6 +108,31 @@ def in_lrelu_bounds(x, dy, gm, bt, eps, slope):
     tol_dgamma = (HW * d_m2).sum((0, 1)) + U * ref["dgamma"].abs()
     tol_dbeta = (HW * d_m1).sum((0, 1)) + U * ref["dbeta"].abs()
     return ref, dict(y=tol_y, dx=tol_dx, dgamma=tol_dgamma, dbeta=tol_dbeta, ambiguous=amb)
+
+
+def in_layout(HW, C):
+    """csrc/kernels_segtrain.hip's in_layout restated: a row is C8 = C / 8 vectors, G = min(C8, 256) threads cover it (C8 > 256: in several passes), nrl =
+    256 // G row lanes take alternate rows (256 - nrl G threads idle), a workgroup owns a slab of S = nrl IN_ROWS rows, an image has R slabs.  The two
+    finalize kernels add an image's R partials 64 at a time.  tests/test_cpu_nnunet_train.py pins this to the library's workspace size."""
+    C8 = C // 8
+    G = min(C8, 256)
+    nrl = 256 // G
+    S = nrl * IN_ROWS
+    return dict(C8=C8, G=G, nrl=nrl, S=S, R=-(-HW // S))
+
+
+def in_lrelu_first_pass_reference(x, dy, gm, bt, eps, slope, rows):
+    """What the kernels would hand out if each finalize stopped after its first pass over the slabs (a WRONG reference the bounds must reject): every sum over
+    the pixels of an image runs over pixels < `rows` only and is still divided by HW.  Returns mu, var, r [B, 1, C] and dgamma, dbeta [C], float64."""
+    HW = x.shape[1]
+    xs = x[:, :rows]
+    mu = xs.sum(1, keepdim=True) / HW
+    var = ((xs * xs).sum(1, keepdim=True) / HW - mu * mu).clamp_min(0.0)
+    r = 1.0 / torch.sqrt(var + eps)
+    xh = (xs - mu) * r
+    a = xh * gm + bt
+    da = dy[:, :rows] * torch.where(a > 0, torch.ones_like(a), torch.full_like(a, slope))
+    return dict(mu=mu, var=var, r=r, dgamma=(da * xh).sum((0, 1)), dbeta=da.sum((0, 1)))
 
 
 # ---- the network with deep supervision on a float64 tape -------------------------------------------------------------------------------------------

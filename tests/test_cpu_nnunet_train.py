@@ -1,6 +1,7 @@
 """CPU: the host side of the tissue head's training step -- the float64 restatement of nnU-Net's deep-supervision loss (tests/nnunet_train_ref.py) against
 values recorded from the reference's own modules (tests/golden/reference_dc_ce_loss.npz, scripts/gen_golden_dc_ce_loss.py), the deep-supervision weights,
-the poly schedule, the parameter names with deep supervision on, and the ctypes prototypes of the new entry points."""
+the poly schedule, the parameter names with deep supervision on, the ctypes prototypes of the new entry points, and the GPU case tables against the
+pass widths of the reduction kernels' finalize loops."""
 import ctypes as C
 import json
 import os
@@ -119,6 +120,67 @@ def test_written_folder_is_read_back(tmp_path):
     spec2, sd2, axes = nnunet.read_trained_model_folder(path)
     assert spec2 == spec and axes == (0, 1)
     assert set(sd2) == set(nnunet.param_shapes(spec)) and all(torch.equal(sd2[k], sd[k]) for k in sd2)
+
+
+def _constant(src, name):
+    m = re.search(r"constexpr int [^;]*\b" + name + r" = (\d+)", src)
+    assert m, f"{name} is no longer a constexpr int"
+    return int(m.group(1))
+
+
+def test_gpu_case_tables_cross_the_finalize_thresholds():
+    """Every finalize of the trainer's streaming reductions covers its partials in passes of a fixed width: the GPU case tables must hold cases beyond one
+    pass and beyond two, and thread layouts that leave a workgroup ragged.  The widths are read off the kernels (64 slabs a pass in the InstanceNorm
+    finalizes; 256 threads in the loss's, the norm's and the column sum's workgroups), the layouts restated in nnunet_train_ref.in_layout and pinned to the
+    library's own workspace sizes (host-only calls), so that a change to a constant cannot quietly move the cases back under a threshold."""
+    import test_gpu_nnunet_ddp as D
+    import test_gpu_nnunet_ignore as G
+    import test_gpu_nnunet_train as T
+    import test_gpu_wgrad_direct as W
+    from ldiffusion_amd import autograd as ag, optim
+    lib = _lib.load()
+    with open(os.path.join(ROOT, "ldiffusion_amd", "csrc", "kernels_segtrain.hip")) as f:
+        src = f.read()
+    with open(os.path.join(ROOT, "ldiffusion_amd", "csrc", "kernels_wgrad.hip")) as f:
+        wsrc = f.read()
+    assert _constant(src, "IN_ROWS") == ref.IN_ROWS and _constant(src, "DCE_PIX") == 4096
+    assert (_constant(wsrc, "CS_ROWS"), _constant(wsrc, "CS_MAX_SLABS")) == (256, 1024)
+    assert "for (int r = lane; r < R; r += 64)" in src and "slot < Bd * NACC; slot += 256" in src and "e < Bd * NC; e += 256" in src and "w < P; w += 256" in src
+    # InstanceNorm + LeakyReLU
+    new = T.IN_LANE_SHAPES + T.IN_WRAP_SHAPES
+    assert all(s + (0.01,) in T.IN_CASES for s in new)
+    lay = {}
+    for B, C, H, W_ in T.IN_SHAPES + new:
+        l = lay[(B, C, H, W_)] = ref.in_layout(H * W_, C)
+        assert lib.ldiff_op_in_train_ws_bytes(B, H * W_, C) == 4 * (2 * B * l["R"] * C + 2 * B * C), (B, C, H, W_)
+    assert all(l["R"] <= 64 and 256 % l["C8"] == 0 for s, l in lay.items() if s in T.IN_SHAPES), "the earlier shapes were the ones below every threshold"
+    R = sorted(lay[s]["R"] for s in T.IN_WRAP_SHAPES)
+    assert 64 < R[0] <= 128 < R[-1], R                                                  # a second pass; a third
+    assert any(lay[s]["R"] > 64 and (s[2] * s[3]) % lay[s]["S"] and s[0] > 1 for s in T.IN_WRAP_SHAPES)   # with a ragged last slab, in a batch
+    ragged = [lay[s] for s in T.IN_LANE_SHAPES if lay[s]["C8"] <= 256 and 256 % lay[s]["C8"]]
+    assert len({l["nrl"] for l in ragged}) >= 3 and all(l["nrl"] * l["G"] < 256 for l in ragged)          # idle threads, three lane counts
+    assert any(l["R"] > 1 for l in ragged) and any(s[2] * s[3] < lay[s]["nrl"] for s in T.IN_LANE_SHAPES)   # over several slabs; fewer rows than row lanes
+    assert any(lay[s]["C8"] > 256 for s in T.IN_LANE_SHAPES)                                              # a second pass over the channel vectors
+    # Dice + cross-entropy: the plain form's table, the ignore form's, and the split entries'
+    wraps = [(n, shape[0]) for n, shape, bd, *_ in T.LOSS_CASES if not bd]
+    assert all(B * ag.dice_ce_nacc(n) <= 256 and B * 8 * ((n + 7) // 8) <= 256 for n, B in set(wraps) - set(T.LOSS_WRAP_NB))
+    for table, ignore in ((wraps, False), ([(n, B) for _, n, B, _, bd in G.WRAP_CASES if not bd], True)):
+        slots = [B * ag.dice_ce_nacc(n, n if ignore else None) for n, B in table]
+        coefs = [B * 8 * ((n + 7) // 8) for n, B in table]
+        assert any(s > 256 and c <= 256 for s, c in zip(slots, coefs)) and any(s > 512 and c > 256 for s, c in zip(slots, coefs)), (slots, coefs)
+        assert all(lib.ldiff_op_dice_ce_ignore_nacc(n) == ag.dice_ce_nacc(n, n) for n, _ in table)
+    assert {(n, B) for n, B in T.LOSS_WRAP_NB} == {(n, B) for _, n, B, _, _ in G.WRAP_CASES}
+    # the gradient norm
+    P = [optim.sumsq_plan(n)[1] for n in D.SUMSQ_WRAP]
+    assert min(P) > 256 and max(P) > 768 and max(P) % 256, P
+    assert all(lib.ldiff_op_sumsq_ws_bytes(n) == 4 * p for n, p in zip(D.SUMSQ_WRAP, P))
+    # the slab column sum
+    plans = {(M, N): ag.colsum_slabs_plan(M, N) for M, N in W.COLSUM_INT_CASES}
+    assert all(lib.ldiff_op_colsum_slabs_ws_bytes(M, N) == p["ws_bytes"] for (M, N), p in plans.items())
+    capped = [(M, N) for (M, N), p in plans.items() if -(-M // 256) > 1024]
+    assert capped and all(plans[c]["slabs"] == 1024 and plans[c]["rows"] > 256 and M % plans[c]["rows"] for c in capped for M in [c[0]])
+    assert any(256 % (N // 8) for M, N in capped) and len({N for M, N in plans if 256 % (N // 8)}) >= 3 and any(N == 2048 for _, N in plans)
+    assert (W.COLSUM_CAPPED_M, 24) in plans
 
 
 def test_prototypes_of_the_new_entry_points():

@@ -2,7 +2,10 @@
 split at its sums, the gradient bucket and its norm, the three phases driven by hand against two ranks over gloo, the averaged gradient against the
 float64 tape, and the training stage on two ranks.  The two-rank cases start fresh child processes that share the one GPU over gloo.
 
-u = 2^-24 as in tests/test_gpu_nnunet_train.py, whose cases, bounds and helpers this file imports."""
+u = 2^-24 as in tests/test_gpu_nnunet_train.py, whose cases, bounds and helpers this file imports.
+
+SUMSQ_WRAP (258 and 776 partials, beyond one pass of the norm's finalize), measured on an MI355X: relative error at most 4.45e-8 and 5.21e-8 against the bound
+1.73e-6 of those cases, 0.026 and 0.030 of it (the existing sizes in the same run: at most 4.79e-8)."""
 import json
 import math
 import os
@@ -29,10 +32,12 @@ U = ref.U
 # ---- (a) world 1 changes nothing -------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("i64", [False, True], ids=["u8", "i64"])
 @pytest.mark.parametrize("batch_dice", [True, False])
-@pytest.mark.parametrize("n,shape", [(4, (2, 4, 4)), (7, (1, 24, 40)), (11, (2, 72, 72))])
+@pytest.mark.parametrize("n,shape", [(4, (2, 4, 4)), (7, (1, 24, 40)), (11, (2, 72, 72)), (4, (11, 15, 13)), (17, (11, 72, 64)), (32, (9, 15, 13))])
 def test_stats_then_from_sums_at_world_one_is_dice_ce(lib, n, shape, batch_dice, i64):
     """ag.dice_ce_stats followed by ag.DiceCeSumsFn at world = 1 equals ag.dice_ce / ag.DiceCeFn bit for bit, in the loss and in dlogits: the smallest of
-    the existing loss shapes, an odd map, and a map of 5184 pixels (two workgroups an image, no multiple of 4096)."""
+    the existing loss shapes, an odd map, and a map of 5184 pixels (two workgroups an image, no multiple of 4096); and test_gpu_nnunet_train.LOSS_WRAP_NB's
+    batches, where without batch_dice the sums table has more than 256 slots (the reduce kernel's later passes) and two of the three more than 256
+    coefficients: every row carries its sample's exact histogram."""
     B, H, W = shape
     logits, target = T.loss_case(n, B, H, W, False, 900 + n)
     tgt = (target if i64 else target.to(torch.uint8)).to(DEV)
@@ -110,12 +115,19 @@ def test_exchanged_statistics_against_float64(lib, n, size, split):
 
 
 # ---- (c) the bucket and its norm -------------------------------------------------------------------------------------------------------------------
+SUMSQ_WRAP = [257 * 16384 + 5, 776 * 16384 - 9]   # 258 and 776 partials: the finalize's `w += 256` loop takes a second pass, and three and a ragged fourth
+
+
 @pytest.mark.parametrize("off", [0, 1], ids=["aligned", "4-bytes-off"])
-@pytest.mark.parametrize("n", [1, 255, 4097, 2 ** 20 + 3])
+@pytest.mark.parametrize("n", [1, 255, 4097, 2 ** 20 + 3] + SUMSQ_WRAP)
 def test_sumsq_against_float64(lib, n, off):
     """ldiff_op_sumsq against float64, relative bound (chain + partials + 2) u from the kernel's own plan (ag.sumsq_plan): `chain` fp32 roundings into a
     partial of non-negative terms, the partials added in double (counted all the same), the square root and the final rounding.  Two calls give equal
-    bits; one inf or NaN gives a non-finite result."""
+    bits; one inf or NaN gives a non-finite result.
+    SUMSQ_WRAP, where that count of the double adds would leave the bound too loose to tell anything: (chain + 2) 2^-24 + partials 2^-53.  A partial is a sum
+    of non-negative terms through `chain` fp32 roundings: within chain u of itself (first order); the partials are non-negative and added in double,
+    2^-53 a step; the square root halves a relative error; one unit each for the square root and the rounding to fp32.  That bound rejects the norm without
+    partial 256 (the first of the finalize's second pass), and a bad value inside that partial and inside the last one reaches the result."""
     g = torch.Generator().manual_seed(n + off)
     base = (torch.randn(n + off, generator=g) * 37.0).to(DEV)
     x = base[off:]
@@ -125,16 +137,23 @@ def test_sumsq_against_float64(lib, n, off):
     want = float(x.double().square().sum().sqrt())
     chain, partials = ag.sumsq_plan(n)
     assert partials == lib.ldiff_op_sumsq_ws_bytes(n) // 4
-    bound = (chain + partials + 2) * U
+    wrap = n in SUMSQ_WRAP
+    bound = (chain + 2) * U + partials * 2.0 ** -53 if wrap else (chain + partials + 2) * U
     print(f"[sumsq] n={n} offset {off}: relative error {abs(float(a) - want) / want:.2e}, bound {bound:.2e}")
     assert abs(float(a) - want) <= bound * want
+    spots = [n // 2] + ([n - 1] if n > 4 else [])   # in the scalar tail / the last vector as well
+    if wrap:
+        head = (4 - off) % 4                         # scalar elements up to the first 16-byte boundary; partial w is elements [head + 16384 w, head + 16384 (w + 1))
+        last = -(-((n - head) // 4) // (ag.ADAMW_CHUNK // 4)) - 1
+        assert last >= 256
+        lo = head + 256 * ag.ADAMW_CHUNK
+        without = float((x.double().square().sum() - x[lo:lo + ag.ADAMW_CHUNK].double().square().sum()).sqrt())
+        assert abs(float(a) - without) > bound * without, "the bound accepts the norm without partial 256"
+        spots += [lo + 5, head + last * ag.ADAMW_CHUNK + 1]
     for bad in (float("inf"), float("nan"), float("-inf")):
-        y = x.clone() if off == 0 else base.clone()[off:]
-        y[n // 2] = bad
-        assert not math.isfinite(float(ag.sumsq(y)))
-        if n > 4:   # in the scalar tail / the last vector as well
+        for at in spots:
             y = x.clone() if off == 0 else base.clone()[off:]
-            y[n - 1] = bad
+            y[at] = bad
             assert not math.isfinite(float(ag.sumsq(y)))
 
 

@@ -2,7 +2,12 @@
 kernels alone against float64 with derived bounds (tests/nnunet_train_ref.py states them), the whole backward pass against the float64 tape with the
 fp16-storage model as the yardstick, a short training run, and the round trip through a trained-model folder.
 
-u = 2^-24, gamma(n) = 2 n u as in tests/test_gpu_nnunet.py."""
+u = 2^-24, gamma(n) = 2 n u as in tests/test_gpu_nnunet.py.
+
+Where the kernels' loops wrap (IN_LANE_SHAPES, IN_WRAP_SHAPES, LOSS_WRAP_NB; tests/test_cpu_nnunet_train.py pins the thresholds), measured on an MI355X as the worst
+error / bound over the group's cases: IN_LANE_SHAPES y 0.983, dx 0.975, dgamma 0.006, dbeta 0.016; IN_WRAP_SHAPES y 0.987, dx 0.982, dgamma 0.001, dbeta 0.002, saved
+mean 0.012, saved rstd 0.013 (the existing IN_SHAPES in the same run: 0.985, 0.973, 0.008, 0.018); LOSS_WRAP_NB value 0.012, gradient 0.966 (the fp16 rounding
+of the stored gradient alone takes 0.96 of that bound).  With both finalizes cut to their first pass over the partials exactly the wrap cases fail."""
 import json
 import math
 import os
@@ -54,13 +59,23 @@ def run_in_train(lib, x, dy, gm, bt, eps, slope):
 IN_SHAPES = [(2, 32, 4, 4), (1, 16, 24, 40), (2, 64, 64, 64), (3, 256, 8, 8), (2, 512, 2, 2), (2, 512, 8, 8)]   # the last two: the bottleneck norms of the `2d` plan
 
 
-@pytest.mark.parametrize("slope", [0.01, 1.0])
-@pytest.mark.parametrize("B,C,H,W", IN_SHAPES)
+# Thread layouts no shape above reaches (ref.in_layout): C / 8 = 3, 5, 12 does not divide 256, so 256 - nrl G = 1, 1, 4 threads of a workgroup idle and a
+# row lane's first thread is no multiple of a wave's width -- with 63 rows (fewer than the 85 row lanes), with two slabs an image, with 51 and with 21 row
+# lanes; C / 8 = 257 takes a second pass over the channel vectors with a single live thread.
+IN_LANE_SHAPES = [(2, 24, 7, 9), (2, 24, 40, 70), (3, 40, 33, 50), (2, 96, 30, 30), (2, 2056, 9, 9)]
+# More than 64 slabs an image, where the finalize kernels' `r += 64` loops take a second and a third pass: R = 72; R = 72 with a last slab of 127 rows; R = 131.
+# R > 64 needs HW C > 64 * 65536 elements an image whatever C is, so these are the smallest such shapes.  One slope: the float64 side takes seconds.
+IN_WRAP_SHAPES = [(1, 512, 96, 96), (2, 512, 97, 95), (1, 512, 129, 129)]
+IN_CASES = [s + (slope,) for slope in (0.01, 1.0) for s in IN_SHAPES + IN_LANE_SHAPES] + [s + (0.01,) for s in IN_WRAP_SHAPES]
+
+
+@pytest.mark.parametrize("B,C,H,W,slope", IN_CASES)
 def test_instance_norm_lrelu_against_float64(lib, B, C, H, W, slope):
     """Forward and backward on the same fp16 inputs against float64, per element, with nnunet_train_ref.in_lrelu_bounds (derived there from the kernel's
     summation order).  Inputs of unit scale with a per-channel offset, as a conv's output is.  Elements whose float64 pre-activation is smaller than
     the fp32 evaluation error of that value may take either branch (at most 0.5 % of them).  The same bounds must reject a reference with slope 0 and
-    one whose statistics run over the batch (where the batch has more than one image: with one they are the same function)."""
+    one whose statistics run over the batch (where the batch has more than one image: with one they are the same function) and, where an image has
+    more than 64 slabs, one whose sums stop after the first 64 (nnunet_train_ref.in_lrelu_first_pass_reference: mean, rstd, dgamma, dbeta)."""
     HW = H * W
     g = torch.Generator().manual_seed(B * 1000 + C + HW)
     x = (torch.randn((B, HW, C), generator=g) * (0.5 + torch.rand((1, 1, C), generator=g)) + 0.5 * torch.randn((B, 1, C), generator=g)).to(torch.float16)
@@ -105,6 +120,16 @@ def test_instance_norm_lrelu_against_float64(lib, B, C, H, W, slope):
         assert ((dg - w["dgamma"]).abs() > tol["dgamma"]).double().mean() > 0.2, f"the dgamma bound accepts {what}"
         if not (slope == 1.0 and what == "batch statistics"):   # at slope 1 dbeta = sum dy whatever the statistics are: the same function, nothing to reject
             assert ((db - w["dbeta"]).abs() > tol["dbeta"]).double().mean() > 0.2, f"the dbeta bound accepts {what}"
+    lay = ref.in_layout(HW, C)
+    if lay["R"] > 64:   # a finalize that stopped after its first pass over the slabs: the sums of the first 64 S pixels of an image
+        w = ref.in_lrelu_first_pass_reference(x64, dy64, gm64, bt64, eps, slope, 64 * lay["S"])
+        what = f"sums over the first 64 of {lay['R']} slabs"
+        print(f"[in_train] B={B} C={C} {H}x{W}: {lay['R']} slabs an image: mean {((mean - mu).abs() / (gs * x64.abs().mean(1) + U * mu.abs())).max():.3f} "
+              f"rstd {((rstd * torch.sqrt(var + eps) - 1).abs() / e_r).max():.3f} of the bound")
+        assert ((mean - w["mu"][:, 0]).abs() > gs * x64.abs().mean(1) + U * mu.abs()).double().mean() > 0.2, f"the bound on the saved mean accepts {what}"
+        assert ((rstd * torch.sqrt(w["var"][:, 0] + eps) - 1).abs() > e_r).double().mean() > 0.2, f"the bound on the saved rstd accepts {what}"
+        assert ((dg - w["dgamma"]).abs() > tol["dgamma"]).double().mean() > 0.2, f"the dgamma bound accepts {what}"
+        assert ((db - w["dbeta"]).abs() > tol["dbeta"]).double().mean() > 0.2, f"the dbeta bound accepts {what}"
 
 
 def test_instance_norm_lrelu_function_and_refusals(lib):
@@ -193,6 +218,19 @@ LOSS_CASES = [(n, shape, bd, i64, gs, absent) for n in (4, 7, 11) for shape in (
 # row pitches 24 and 32, the kernels' NV = 3 and NV = 4 instantiations: one full chunk of DCE_PIX pixels plus a ragged one, and fewer pixels than a
 # workgroup has threads; at the loss scale that keeps the gradient's entries in fp16's normal range, where the bound is a relative one
 LOSS_CASES += [(n, (2,) + hw, bd, True, 65536.0, False) for n in (17, 32) for hw in ((72, 64), (15, 13)) for bd in (True, False)]
+# Batches at which the one-workgroup finalize covers its tables in several passes of 256 threads once batch_dice is off: B NACC = 286 / 814 / 882 slots
+# of sums (dce_reduce_sums), B NC = 88 / 264 / 288 coefficients (dce_coef_loss): the first wraps the sums alone, the others both.  batch_dice on has one
+# row whatever B is: the control.  tests/test_cpu_nnunet_train.py pins the two thresholds to these cases.
+LOSS_WRAP_NB = [(4, 11), (17, 11), (32, 9)]
+LOSS_CASES += [(n, (B,) + hw, bd, True, 65536.0, False) for n, B in LOSS_WRAP_NB for hw in ((15, 13), (72, 64)) for bd in (False, True)]
+
+
+def first_pass_reference(logits, target, n, batch_dice, weight, grad_scale, keep):
+    """loss_reference for ref.first_pass_dice_loss: the Dice term of samples < keep alone (WRONG: the bounds must reject it)."""
+    z = logits[..., :n].double().permute(0, 3, 1, 2).clone().requires_grad_(True)
+    loss = ref.first_pass_dice_loss(z, target, keep, lambda a, t: ref.dc_ce_loss(a, t, batch_dice), F.cross_entropy)
+    (grad,) = torch.autograd.grad(loss, z)
+    return float(loss.detach()), (grad * (weight * grad_scale)).permute(0, 2, 3, 1)
 
 
 @pytest.mark.parametrize("i,n,shape,batch_dice,i64,grad_scale,absent", [(i,) + c for i, c in enumerate(LOSS_CASES)])
@@ -202,7 +240,8 @@ def test_dice_ce_against_float64(lib, i, n, shape, batch_dice, i64, grad_scale, 
     on / off; uint8 / int64 labels; loss scale 1 / 65536; every class present / a foreground class absent from the target; and n_heads 17 / 32 (row pitch
     24 / 32) at two sizes with both batch_dice values.  Pad columns exactly zero; two
     launches bit-identical; the bound rejects do_bg = True, smooth = 1 and, for a batch of more than one image, the flipped batch_dice (by the value or by
-    an entry of the gradient)."""
+    an entry of the gradient).  LOSS_WRAP_NB: n_heads 4 / 17 / 32 at batches of 11 / 11 / 9 and two sizes, where the finalize's loops over [sample][slot]
+    wrap with batch_dice off; there the bounds also reject, by the value and by the gradient, a Dice term that leaves out the samples of the later passes."""
     B, H, W = shape
     weight = 4 / 7
     logits, target = loss_case(n, B, H, W, absent, 300 + i)
@@ -227,6 +266,34 @@ def test_dice_ce_against_float64(lib, i, n, shape, batch_dice, i64, grad_scale, 
     for what, kw, bd in wrong:
         w, gw = loss_reference(logits, target, n, bd, weight, grad_scale, **kw)
         assert abs(float(loss) - w) > tol_value or ((got - gw).abs() > tol_of(gw)).any(), f"the bounds accept {what}"
+    keep = 256 // ag.dice_ce_nacc(n)   # the samples whose every slot of the sums table lies in the finalize's first pass
+    if keep < B:
+        w, gw = first_pass_reference(logits, target, n, batch_dice, weight, grad_scale, keep)
+        assert abs(float(loss) - w) > tol_value, f"the value's bound accepts a Dice term of the first {keep} samples of {B}"
+        assert ((got - gw).abs() > tol_of(gw)).any(), f"the gradient's bound accepts a Dice term of the first {keep} samples of {B}"
+
+
+@pytest.mark.parametrize("n,B,ignore", [(32, 9, None), (17, 11, 17)], ids=["plain", "ignore"])
+def test_dice_ce_stays_inside_its_workspace(lib, n, B, ignore):
+    """One case per form straight through the C entry with batch_dice off, where `sums`, `dcs` and `coef` scale with B: a workspace of exactly ws_bytes with
+    64 NaN floats behind it.  The canaries stay NaN, and loss and dlogits are the wrapper's bits (whose workspace is the same size, sized by the same call)."""
+    H, W = 72, 64
+    logits, target = loss_case(n, B, H, W, False, 40 + n)
+    if ignore is not None:
+        target[:, 10:30, 5:40] = ignore
+    weight, scale = 4 / 7, 65536.0
+    want_loss, want_dl = ag.dice_ce(logits.to(DEV), target.to(DEV), n, False, weight, scale, ignore_label=ignore)
+    ld, td = logits.to(DEV), target.to(DEV)
+    nb = (lib.ldiff_op_dice_ce_ws_bytes if ignore is None else lib.ldiff_op_dice_ce_ignore_ws_bytes)(B, H * W, n)
+    assert nb > 0 and nb % 4 == 0
+    ws = torch.full((nb // 4 + 64,), float("nan"), dtype=torch.float32, device=DEV)
+    loss, dl = torch.full((1,), float("nan"), device=DEV), torch.full_like(ld, float("nan"))
+    head = (_lib.ptr(ld), ld.shape[-1], n) + (() if ignore is None else (ignore,))
+    entry = lib.ldiff_op_dice_ce if ignore is None else lib.ldiff_op_dice_ce_ignore
+    _lib.check(entry(*head, _lib.ptr(td), 1, B, H * W, 0, 1e-5, weight, scale, _lib.ptr(loss), _lib.ptr(dl), _lib.ptr(ws), nb, sp()))
+    torch.cuda.synchronize()
+    assert ws[nb // 4:].isnan().all(), "the entry wrote behind ws_bytes"
+    assert torch.equal(loss[0], want_loss) and torch.equal(dl, want_dl) and math.isfinite(float(loss))
 
 
 def test_dice_ce_refusals_and_bad_labels(lib):
