@@ -756,7 +756,7 @@ int ldiff_op_dice_ce_from_sums(const void* logits, int ld, int n_heads, const vo
 /* The three with nnU-Net's ignore label (DC_and_CE_loss(ignore_label = k); compound_losses.py:31-56, dice.py:72-119): a pixel whose label equals
  * ignore_label (n_heads <= ignore_label <= 254; nnU-Net's rule makes it n_heads) adds nothing -- the Dice sums run over the other, annotated pixels, the
  * cross-entropy is their sum over their count (this process's own; 0 when the count is 0, the Dice term is then -1), the pixel's dlogits row is +0 and its
- * logits are never read.  A label that is neither a class nor ignore_label still makes the loss and that pixel's dlogits NaN.  Region labels are not built.
+ * logits are never read.  A label that is neither a class nor ignore_label still makes the loss and that pixel's dlogits NaN.  Region labels have entries of their own (ldiff_op_dice_focal, below).
  * A row of statistics holds ldiff_op_dice_ce_ignore_nacc(n_heads) = 3 ld + 3 doubles: the plain row, then the count of annotated pixels.
  * ws: ldiff_op_dice_ce_ignore_ws_bytes(...) bytes each.  On a target without an ignored pixel the three give the plain entries' loss and dlogits bit for bit;
  * stats then from_sums give ldiff_op_dice_ce_ignore's bits.  from_sums takes this process's own rows: the data-parallel exchange of the ignore form
@@ -770,6 +770,42 @@ int ldiff_op_dice_ce_ignore_stats(const void* logits, int ld, int n_heads, int i
 int ldiff_op_dice_ce_ignore_from_sums(const void* logits, int ld, int n_heads, int ignore_label, const void* target, int target_i64, int B, int64_t HW,
                                       int batch_dice, float smooth, float weight, float grad_scale, const void* sums, void* loss, void* dlogits, void* ws,
                                       int64_t ws_bytes, void* stream);
+/* Region labels (nnU-Net's region-based training: one sigmoid head per region, regions may overlap).  The target stays the LABEL MAP; membership is looked up in
+ * table = device uint32 [256] indexed by label value (nnunet.region_spec builds it): bit r = the value belongs to region r (r < n_regions <= 24), bit 31 = the
+ * ignore label, bit 30 = no label of the dataset (makes the loss and that pixel's dlogits NaN, as a label outside [0, n_heads) does in ldiff_op_dice_ce; an
+ * int64 label outside a byte's range is read as 255).  logits f16 [B, HW, ld], ld = roundup(n_regions, 8), target uint8 / int64 [B, HW].
+ * Per annotated pixel and region, in fp32: x the logit, y the table bit, s = 2 y - 1, p = sigmoid(x), p_t = sigmoid(s x), q = sigmoid(-s x),
+ * bce = max(x, 0) - x y + log1p(exp(-|x|));  bce = 0: f = 0.25 q^2 bce (DC_and_Focal_loss, alpha 0.25, gamma 2);  bce = 1: f = bce (DC_and_BCE_loss).
+ *   use_ignore = 0: term = mean f over B n_regions HW (a pixel with the ignore bit is then a bad label);
+ *   use_ignore = 1: pixels with the ignore bit take no part (logits never read, dlogits row +0); term = sum f / max(A, 1e-8), A = this process's annotated
+ *                   PIXELS -- not times n_regions, as the reference has it: the two differ by the factor n_regions even when nothing is ignored.
+ * Dice = MemoryEfficientSoftDiceLoss(sigmoid, do_bg = True): sums over annotated pixels, ALL regions, M = (batch_dice ? 1 : B) n_regions averaged terms,
+ * dc = (2 intersect + smooth) / max(sum_gt + sum_pred + smooth, 1e-8).  loss[0] = term - mean dc;  dlogits = grad_scale * weight * d loss / d logits, pad columns +0.
+ * Rows of statistics hold ldiff_op_dice_focal_nacc(n_regions) = 3 ld + 3 doubles: sum_pred[ld], intersect[ld], sum_gt[ld], sum f, bad labels, annotated pixels.
+ * _stats / _from_sums split the loss as ldiff_op_dice_ce_stats / _from_sums do (same roles of dice_sums, local_sums, world; stats then from_sums at world = 1
+ * give ldiff_op_dice_focal's bits); with use_ignore = 1 from_sums takes world = 1 and dice_sums == local_sums only.  No floating-point atomics: bit-reproducible.
+ * ws: ldiff_op_dice_focal_ws_bytes(...) bytes each, 16-byte aligned. */
+int64_t ldiff_op_dice_focal_ws_bytes(int B, int64_t HW, int n_regions);
+int ldiff_op_dice_focal_nacc(int n_regions);
+int ldiff_op_dice_focal(const void* logits, int ld, int n_regions, const void* table, const void* target, int target_i64, int use_ignore, int bce, int B, int64_t HW,
+                        int batch_dice, float smooth, float weight, float grad_scale, void* loss, void* dlogits, void* ws, int64_t ws_bytes, void* stream);
+int ldiff_op_dice_focal_stats(const void* logits, int ld, int n_regions, const void* table, const void* target, int target_i64, int use_ignore, int bce, int B,
+                              int64_t HW, int batch_dice, void* sums, void* ws, int64_t ws_bytes, void* stream);
+int ldiff_op_dice_focal_from_sums(const void* logits, int ld, int n_regions, const void* table, const void* target, int target_i64, int use_ignore, int bce, int B,
+                                  int64_t HW, int batch_dice, float smooth, float weight, float grad_scale, const void* dice_sums, const void* local_sums, int world,
+                                  void* loss, void* dlogits, void* ws, int64_t ws_bytes, void* stream);
+/* Validation counts of region training (nnUNetTrainer.validation_step's region branch): counts = device int64 [3, n_regions] = tp, fp, fn of
+ * `logit > threshold` against the table bit, over the pixels without the ignore bit; exact.  A pixel whose label has bit 30 (no label of the dataset) is a
+ * member of no region here: it counts towards fp where a logit exceeds the threshold, and raises nothing -- the loss entries make the same pixel NaN.  ws: ldiff_op_region_counts_ws_bytes(...) bytes. */
+int64_t ldiff_op_region_counts_ws_bytes(int B, int64_t HW, int n_regions);
+int ldiff_op_region_counts(const void* logits, int ld, int n_regions, const void* table, const void* target, int target_i64, int B, int64_t HW, float threshold,
+                           void* counts, void* ws, int64_t ws_bytes, void* stream);
+/* LabelManager.convert_probabilities_to_segmentation's region branch on logits [n_regions, H, W] (f16, or f32 with logits_f32 = 1): the pixel is 0, then for
+ * i in order regions_class_order[i] (host int [n_regions], 0 .. 255) where logit_i > threshold, later entries overwriting earlier ones; a NaN logit compares
+ * false.  Written into mask u8 [mask_H, mask_W] at (mask_y0, mask_x0), as ldiff_op_window_finish places its mask.  `sigmoid(l) > 0.5` is a step function of
+ * the logit: the caller passes the step of the dtype the reference thresholds in (nnunet.REGION_THRESHOLD_F32 / _F16). */
+int ldiff_op_region_mask_u8(const void* logits, int logits_f32, int n_regions, int H, int W, const int* regions_class_order, float threshold, void* mask, int mask_H,
+                            int mask_W, int mask_y0, int mask_x0, void* stream);
 /* The gradient bucket of a data-parallel step.  ldiff_op_bucket_pack: bucket[offsets[t] + i] = grads[t][i] for every tensor in one launch; grads = device
  * table of const float*, offsets = device int64 [T + 1] (prefix sums of the element counts), chunks as ldiff_op_adamw_multi's.
  * ldiff_op_sumsq: out_f32[0] = sqrt(sum x^2) of n f32 elements (4-byte aligned) through one fp32 partial per 16384 elements (at most 27 dependent roundings

@@ -229,6 +229,14 @@ SIGNATURES = {
     "ldiff_op_dice_ce_ignore": (I, [P, I, I, I, P, I, I, I64, I, F, F, F, P, P, P, I64, P]),
     "ldiff_op_dice_ce_ignore_stats": (I, [P, I, I, I, P, I, I, I64, I, P, P, I64, P]),
     "ldiff_op_dice_ce_ignore_from_sums": (I, [P, I, I, I, P, I, I, I64, I, F, F, F, P, P, P, P, I64, P]),
+    "ldiff_op_dice_focal_ws_bytes": (I64, [I, I64, I]),
+    "ldiff_op_dice_focal_nacc": (I, [I]),
+    "ldiff_op_dice_focal": (I, [P, I, I, P, P, I, I, I, I, I64, I, F, F, F, P, P, P, I64, P]),
+    "ldiff_op_dice_focal_stats": (I, [P, I, I, P, P, I, I, I, I, I64, I, P, P, I64, P]),
+    "ldiff_op_dice_focal_from_sums": (I, [P, I, I, P, P, I, I, I, I, I64, I, F, F, F, P, P, I, P, P, P, I64, P]),
+    "ldiff_op_region_counts_ws_bytes": (I64, [I, I64, I]),
+    "ldiff_op_region_counts": (I, [P, I, I, P, P, I, I, I64, F, P, P, I64, P]),
+    "ldiff_op_region_mask_u8": (I, [P, I, I, I, I, P, F, P, I, I, I, I, P]),
     "ldiff_op_bucket_pack": (I, [P, P, P, I64, P, P]),
     "ldiff_op_sumsq_ws_bytes": (I64, [I64]),
     "ldiff_op_sumsq": (I, [P, I64, P, P, I64, P]),

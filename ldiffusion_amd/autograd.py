@@ -665,8 +665,8 @@ def _ignore_label(ignore_label, n_heads, what):
 def dice_ce(logits, target, n_heads, batch_dice, weight=1.0, grad_scale=1.0, smooth=1e-5, ignore_label=None):
     """ldiff_op_dice_ce on float16 logits [B, H, W, roundup(n_heads, 8)] and uint8 / int64 labels [B, H, W] (or [B, 1, H, W]):
     (loss float32 0-dim, dlogits float16 = grad_scale * weight * d loss / d logits in the logits' layout).  `ignore_label`: nnU-Net's ignore label
-    (ldiff_op_dice_ce_ignore): pixels carrying it add nothing to the loss and get a zero gradient; None is the plain entry.  Region labels are not
-    built (nnunet.network_spec refuses them)."""
+    (ldiff_op_dice_ce_ignore): pixels carrying it add nothing to the loss and get a zero gradient; None is the plain entry.  Region labels go through
+    `dice_focal` (nnunet.network_spec(accept_regions=True))."""
     target, B, H, W, ld = _dice_ce_args(logits, target, "dice_ce")
     ignore_label = _ignore_label(ignore_label, n_heads, "dice_ce")
     lib = _lib.load()
@@ -777,3 +777,137 @@ class DiceCeSumsFn(torch.autograd.Function):
     def backward(ctx, g):
         (dlogits,) = ctx.saved_tensors
         return (dlogits.float() * g).to(dlogits.dtype), None, None, None, None, None, None, None, None, None, None
+
+
+# ---- region labels: Dice + focal / BCE on the label map through the membership table (csrc/kernels_segregion.hip) ----
+def _region_args(logits, target, table, n_regions, what):
+    target, B, H, W, ld = _dice_ce_args(logits, target, what)
+    n_regions = int(n_regions)
+    if not 1 <= n_regions <= 24:
+        raise ValueError(f"{what}: {n_regions} regions (1 .. 24)")
+    if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.int32 and table.is_contiguous() and table.numel() == 256):
+        raise ValueError(f"{what}: `table` must be the membership table as nnunet.region_table_tensor(table, device) gives it: int32 [256] on the device")
+    return target, B, H, W, ld, n_regions
+
+
+def _region_form(region_loss, what):
+    if region_loss not in ("focal", "bce"):
+        raise ValueError(f"{what}: region_loss {region_loss!r} is neither 'focal' nor 'bce'")
+    return int(region_loss == "bce")
+
+
+def dice_focal_nacc(n_regions):
+    """Doubles per row of the region loss's statistics (ldiff_op_dice_focal_nacc): sum_pred, intersect, sum_gt per padded region, the focal / BCE sum, the count
+    of bad labels, the count of annotated pixels."""
+    return 3 * 8 * ((int(n_regions) + 7) // 8) + 3
+
+
+def dice_focal(logits, target, table, n_regions, batch_dice, weight=1.0, grad_scale=1.0, smooth=1e-5, use_ignore=False, region_loss="focal"):
+    """ldiff_op_dice_focal on float16 logits [B, H, W, roundup(n_regions, 8)] and the uint8 / int64 LABEL MAP [B, H, W] (or [B, 1, H, W]): the reference's
+    DC_and_Focal_loss (`region_loss="bce"`: nnU-Net's DC_and_BCE_loss) of one scale -> (loss float32 0-dim, dlogits float16 = grad_scale * weight * d loss /
+    d logits).  `table`: the membership table on the device; `use_ignore`: pixels whose label carries the table's ignore bit take no part."""
+    what = "dice_focal"
+    target, B, H, W, ld, n = _region_args(logits, target, table, n_regions, what)
+    bce = _region_form(region_loss, what)
+    lib = _lib.load()
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    dlogits = torch.empty_like(logits)
+    nb = lib.ldiff_op_dice_focal_ws_bytes(B, H * W, n)
+    ws = _workspace(nb, logits.device)
+    _lib.check(lib.ldiff_op_dice_focal(logits.data_ptr(), ld, n, table.data_ptr(), target.data_ptr(), int(target.dtype == torch.int64), int(bool(use_ignore)), bce, B,
+                                       H * W, int(bool(batch_dice)), float(smooth), float(weight), float(grad_scale), loss.data_ptr(), dlogits.data_ptr(),
+                                       ws.data_ptr(), nb, _sp()))
+    return loss[0], dlogits
+
+
+def dice_focal_stats(logits, target, table, n_regions, batch_dice, out=None, use_ignore=False, region_loss="focal"):
+    """ldiff_op_dice_focal_stats: the sums `dice_focal` forms before its coefficients, float64 [1 or B, dice_focal_nacc(n_regions)] on the device, added in
+    dice_focal's order.  `out` as dice_ce_stats'."""
+    what = "dice_focal_stats"
+    target, B, H, W, ld, n = _region_args(logits, target, table, n_regions, what)
+    bce = _region_form(region_loss, what)
+    lib = _lib.load()
+    rows, nacc = (1 if batch_dice else B), dice_focal_nacc(n)
+    if out is None:
+        out = torch.empty((rows, nacc), dtype=torch.float64, device=logits.device)
+    elif not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == rows * nacc):
+        raise ValueError(f"{what}: out must be a contiguous float64 CUDA tensor of {rows * nacc} elements")
+    nb = lib.ldiff_op_dice_focal_ws_bytes(B, H * W, n)
+    ws = _workspace(nb, logits.device)
+    _lib.check(lib.ldiff_op_dice_focal_stats(logits.data_ptr(), ld, n, table.data_ptr(), target.data_ptr(), int(target.dtype == torch.int64), int(bool(use_ignore)),
+                                             bce, B, H * W, int(bool(batch_dice)), out.data_ptr(), ws.data_ptr(), nb, _sp()))
+    return out
+
+
+def dice_focal_from_sums(logits, target, table, n_regions, batch_dice, dice_sums, local_sums, world=1, weight=1.0, grad_scale=1.0, smooth=1e-5, use_ignore=False,
+                         region_loss="focal"):
+    """ldiff_op_dice_focal_from_sums: (loss, dlogits) as `dice_focal` returns them, the Dice term from `dice_sums` (with `batch_dice` possibly the sum of `world`
+    processes' statistics; its gradient then carries the factor `world`), the focal / BCE term from `local_sums`.  With `use_ignore` it is built for one
+    process: world = 1 and `dice_sums` is `local_sums`, anything else raises NotImplementedError."""
+    what = "dice_focal_from_sums"
+    target, B, H, W, ld, n = _region_args(logits, target, table, n_regions, what)
+    bce = _region_form(region_loss, what)
+    lib = _lib.load()
+    rows, nacc = (1 if batch_dice else B), dice_focal_nacc(n)
+    for name, t in (("dice_sums", dice_sums), ("local_sums", local_sums)):
+        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == rows * nacc):
+            raise ValueError(f"{what}: {name} must be a contiguous float64 CUDA tensor of {rows * nacc} elements")
+    local = int(world) == 1 and dice_sums.data_ptr() == local_sums.data_ptr()
+    if not batch_dice and not local:
+        raise ValueError(f"{what}: without batch_dice the Dice term is per sample and stays local (world = 1, dice_sums is local_sums)")
+    if use_ignore and not local:
+        raise NotImplementedError(f"{what}(use_ignore=True) with the statistics of world = {int(world)} processes: the data-parallel exchange with an ignore "
+                                  "label is not built")
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    dlogits = torch.empty_like(logits)
+    nb = lib.ldiff_op_dice_focal_ws_bytes(B, H * W, n)
+    ws = _workspace(nb, logits.device)
+    _lib.check(lib.ldiff_op_dice_focal_from_sums(logits.data_ptr(), ld, n, table.data_ptr(), target.data_ptr(), int(target.dtype == torch.int64),
+                                                 int(bool(use_ignore)), bce, B, H * W, int(bool(batch_dice)), float(smooth), float(weight), float(grad_scale),
+                                                 dice_sums.data_ptr(), local_sums.data_ptr(), int(world), loss.data_ptr(), dlogits.data_ptr(), ws.data_ptr(), nb, _sp()))
+    return loss[0], dlogits
+
+
+class DiceFocalFn(torch.autograd.Function):
+    """DiceCeFn for region labels: `weight` * the region loss of one deep-supervision scale; value, stored gradient and backward as DiceCeFn's."""
+
+    @staticmethod
+    def forward(ctx, logits, target, table, n_regions, batch_dice, weight, grad_scale, smooth=1e-5, use_ignore=False, region_loss="focal"):
+        loss, dlogits = dice_focal(logits, target, table, n_regions, batch_dice, weight, grad_scale, smooth, use_ignore, region_loss)
+        ctx.save_for_backward(dlogits)
+        return loss * float(weight)
+
+    @staticmethod
+    def backward(ctx, g):
+        (dlogits,) = ctx.saved_tensors
+        return (dlogits.float() * g).to(dlogits.dtype), None, None, None, None, None, None, None, None, None
+
+
+class DiceFocalSumsFn(torch.autograd.Function):
+    """DiceFocalFn with the statistics supplied: the term of a data-parallel rank, as DiceCeSumsFn is DiceCeFn's."""
+
+    @staticmethod
+    def forward(ctx, logits, target, table, n_regions, batch_dice, dice_sums, local_sums, world, weight, grad_scale, smooth=1e-5, use_ignore=False, region_loss="focal"):
+        loss, dlogits = dice_focal_from_sums(logits, target, table, n_regions, batch_dice, dice_sums, local_sums, world, weight, grad_scale, smooth, use_ignore,
+                                             region_loss)
+        ctx.save_for_backward(dlogits)
+        return loss * float(weight)
+
+    @staticmethod
+    def backward(ctx, g):
+        (dlogits,) = ctx.saved_tensors
+        return (dlogits.float() * g).to(dlogits.dtype), None, None, None, None, None, None, None, None, None, None, None, None
+
+
+def region_counts(logits, target, table, n_regions, threshold):
+    """ldiff_op_region_counts: int64 [3, n_regions] on the device = tp, fp, fn of `logit > threshold` against the table's region bits, over the pixels whose
+    label does not carry the ignore bit; exact."""
+    what = "region_counts"
+    target, B, H, W, ld, n = _region_args(logits, target, table, n_regions, what)
+    lib = _lib.load()
+    out = torch.empty((3, n), dtype=torch.int64, device=logits.device)
+    nb = lib.ldiff_op_region_counts_ws_bytes(B, H * W, n)
+    ws = _workspace(nb, logits.device)
+    _lib.check(lib.ldiff_op_region_counts(logits.data_ptr(), ld, n, table.data_ptr(), target.data_ptr(), int(target.dtype == torch.int64), B, H * W, float(threshold),
+                                          out.data_ptr(), ws.data_ptr(), nb, _sp()))
+    return out

@@ -1236,6 +1236,55 @@ int ldiff_op_dice_ce_ignore_from_sums(const void* logits, int ld, int n_heads, i
                            (const double*)sums, 1, (float*)loss, (f16*)dlogits, ws, ws_bytes, (hipStream_t)stream);
   API_END
 }
+int64_t ldiff_op_dice_focal_ws_bytes(int B, int64_t HW, int n_regions) {
+  if (B < 1 || HW < 1 || n_regions < 1 || n_regions > 24) return 0;
+  return dice_focal_ws_bytes(B, HW, n_regions);
+}
+int ldiff_op_dice_focal_nacc(int n_regions) { return (n_regions < 1 || n_regions > 24) ? 0 : dice_focal_nacc(n_regions); }
+int ldiff_op_dice_focal(const void* logits, int ld, int n_regions, const void* table, const void* target, int target_i64, int use_ignore, int bce, int B, int64_t HW,
+                        int batch_dice, float smooth, float weight, float grad_scale, void* loss, void* dlogits, void* ws, int64_t ws_bytes, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(logits && table && target && loss && dlogits && ws, LDIFF_ERR_INVALID, "op_dice_focal: null argument");
+  launch_dice_focal((const f16*)logits, ld, n_regions, (const unsigned*)table, target, target_i64, use_ignore, bce, B, HW, batch_dice, smooth, weight, grad_scale,
+                    (float*)loss, (f16*)dlogits, ws, ws_bytes, (hipStream_t)stream);
+  API_END
+}
+int ldiff_op_dice_focal_stats(const void* logits, int ld, int n_regions, const void* table, const void* target, int target_i64, int use_ignore, int bce, int B,
+                              int64_t HW, int batch_dice, void* sums, void* ws, int64_t ws_bytes, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(logits && table && target && sums && ws, LDIFF_ERR_INVALID, "op_dice_focal_stats: null argument");
+  launch_dice_focal_stats((const f16*)logits, ld, n_regions, (const unsigned*)table, target, target_i64, use_ignore, bce, B, HW, batch_dice, (double*)sums, ws, ws_bytes,
+                          (hipStream_t)stream);
+  API_END
+}
+int ldiff_op_dice_focal_from_sums(const void* logits, int ld, int n_regions, const void* table, const void* target, int target_i64, int use_ignore, int bce, int B,
+                                  int64_t HW, int batch_dice, float smooth, float weight, float grad_scale, const void* dice_sums, const void* local_sums, int world,
+                                  void* loss, void* dlogits, void* ws, int64_t ws_bytes, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(logits && table && target && dice_sums && local_sums && loss && dlogits && ws, LDIFF_ERR_INVALID, "op_dice_focal_from_sums: null argument");
+  launch_dice_focal_from_sums((const f16*)logits, ld, n_regions, (const unsigned*)table, target, target_i64, use_ignore, bce, B, HW, batch_dice, smooth, weight,
+                              grad_scale, (const double*)dice_sums, (const double*)local_sums, world, (float*)loss, (f16*)dlogits, ws, ws_bytes, (hipStream_t)stream);
+  API_END
+}
+int64_t ldiff_op_region_counts_ws_bytes(int B, int64_t HW, int n_regions) {
+  if (B < 1 || HW < 1 || n_regions < 1 || n_regions > 24) return 0;
+  return region_counts_ws_bytes(B, HW, n_regions);
+}
+int ldiff_op_region_counts(const void* logits, int ld, int n_regions, const void* table, const void* target, int target_i64, int B, int64_t HW, float threshold,
+                           void* counts, void* ws, int64_t ws_bytes, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(logits && table && target && counts && ws, LDIFF_ERR_INVALID, "op_region_counts: null argument");
+  launch_region_counts((const f16*)logits, ld, n_regions, (const unsigned*)table, target, target_i64, B, HW, threshold, (long long*)counts, ws, ws_bytes,
+                       (hipStream_t)stream);
+  API_END
+}
+int ldiff_op_region_mask_u8(const void* logits, int logits_f32, int n_regions, int H, int W, const int* regions_class_order, float threshold, void* mask, int mask_H,
+                            int mask_W, int mask_y0, int mask_x0, void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(logits && regions_class_order && mask, LDIFF_ERR_INVALID, "op_region_mask_u8: null argument");
+  launch_region_mask_u8(logits, logits_f32, n_regions, H, W, regions_class_order, threshold, (uint8_t*)mask, mask_H, mask_W, mask_y0, mask_x0, (hipStream_t)stream);
+  API_END
+}
 int ldiff_op_bucket_pack(const void* grads, const void* offsets, const void* chunks, int64_t nchunks, void* bucket, void* stream) {
   API_BEGIN
   LDIFF_CHECK(nchunks >= 0 && (nchunks == 0 || (grads && offsets && chunks && bucket)), LDIFF_ERR_INVALID, "op_bucket_pack: bad arguments");

@@ -399,6 +399,22 @@ void launch_dice_ce_stats(const f16* logits, int ld, int n_heads, std::optional<
 void launch_dice_ce_from_sums(const f16* logits, int ld, int n_heads, std::optional<int> ignore_label, const void* target, int target_i64, int B, long long HW,
                               int batch_dice, float smooth, float weight, float grad_scale, const double* dice_sums, const double* local_sums, int world, float* loss,
                               f16* dlogits, void* ws, long long ws_bytes, hipStream_t s);
+// region labels (kernels_segregion.hip): Dice + focal / BCE of one deep-supervision scale on the label map through the 256-entry membership table, its split at
+// the sums, the validation counts and the region rule of the mask
+long long dice_focal_ws_bytes(int B, long long HW, int n_regions);
+int dice_focal_nacc(int n_regions);   // doubles per row of sums
+void launch_dice_focal(const f16* logits, int ld, int n_regions, const unsigned* table, const void* target, int target_i64, int use_ignore, int bce, int B, long long HW,
+                       int batch_dice, float smooth, float weight, float grad_scale, float* loss, f16* dlogits, void* ws, long long ws_bytes, hipStream_t s);
+void launch_dice_focal_stats(const f16* logits, int ld, int n_regions, const unsigned* table, const void* target, int target_i64, int use_ignore, int bce, int B,
+                             long long HW, int batch_dice, double* sums, void* ws, long long ws_bytes, hipStream_t s);
+void launch_dice_focal_from_sums(const f16* logits, int ld, int n_regions, const unsigned* table, const void* target, int target_i64, int use_ignore, int bce, int B,
+                                 long long HW, int batch_dice, float smooth, float weight, float grad_scale, const double* dice_sums, const double* local_sums, int world,
+                                 float* loss, f16* dlogits, void* ws, long long ws_bytes, hipStream_t s);
+long long region_counts_ws_bytes(int B, long long HW, int n_regions);
+void launch_region_counts(const f16* logits, int ld, int n_regions, const unsigned* table, const void* target, int target_i64, int B, long long HW, float threshold,
+                          long long* counts, void* ws, long long ws_bytes, hipStream_t s);
+void launch_region_mask_u8(const void* logits, int is_f32, int R, int H, int W, const int* order, float threshold, uint8_t* mask, int mask_H, int mask_W, int mask_y0,
+                           int mask_x0, hipStream_t s);
 // every gradient into one flat buffer in one launch, and the buffer's L2 norm (fixed-order reduction)
 void launch_bucket_pack(const float* const* grads, const long long* offsets, const AdamChunk* chunks, long long nchunks, float* bucket, hipStream_t s);
 long long sumsq_ws_bytes(long long n);

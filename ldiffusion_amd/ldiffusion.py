@@ -20,7 +20,8 @@ from .segmentor import Segmentor
 
 def parse_args(argv=None):
     """ldiffusion.py:19-29: the reference's eight flags, plus --level, --component and --ldiffusion-weight (the reference hard-codes them in its
-    `__main__`, :330-331), and --ignore-pixel, the grey level of unlabelled pixels in partly annotated tissue labels (not given: fully annotated)."""
+    `__main__`, :330-331), --ignore-pixel, the grey level of unlabelled pixels in partly annotated tissue labels (not given: fully annotated), and
+    --regions, a JSON file {"regions": {name: [grey levels or class indices]}, "regions_class_order": [...]} for region-based tissue training."""
     parser = argparse.ArgumentParser(description="Diffusion model training parameters")
     parser.add_argument("--local_rank", type=int, default=int(os.environ.get("LOCAL_RANK", -1)))
     parser.add_argument("--diffusion-path", type=str, required=True, help="stable diffusion base model path")
@@ -34,6 +35,7 @@ def parse_args(argv=None):
     parser.add_argument("--component", type=str, default="all", choices=("all", "ldiffusion", "segmentor"))
     parser.add_argument("--ldiffusion-weight", type=str, default=None, help="trained L-Diffusion weights, for --component segmentor")
     parser.add_argument("--ignore-pixel", type=int, default=None, help="grey level of unlabelled pixels in the label images (tissue level): nnU-Net's ignore label")
+    parser.add_argument("--regions", type=str, default=None, help="JSON file with `regions` and `regions_class_order` (tissue level): nnU-Net's region labels")
     return parser.parse_args(argv)
 
 
@@ -197,7 +199,7 @@ class LDiffusionModel:
         return save_path
 
     def train(self, args, component="all", ldiffusion_weight=None, train_loader=None, val_loader=None, wgrad_route=None, cell_weights=None, instances=None,
-              ignore_pixel=None, **_ignored):
+              ignore_pixel=None, regions=None, regions_class_order=None, region_loss=None, **_ignored):
         """ldiffusion.py:297-315.  The loaders are injected (`train_loader=`, `val_loader=`), or, with none injected and `args` carrying `image_dir` and
         `label_dir`, built as the reference builds them (`self.load_data(args.image_dir, args.label_dir, args.batch_size)`, with `args.image_size` (1024) and
         `args.io_workers` (4) where present): device-resident for the warm-up, plain host loaders when only the segmentor stage runs (it reads their file lists).
@@ -209,7 +211,9 @@ class LDiffusionModel:
         (the route of the tissue trainer's weight gradients, `nnunet_train.Trainer`'s keyword; None: its default), and `batch_images` / `io_workers` (the
         batched dataset pass, `utils.create_nnunet_dataset`'s keywords; not given: the per-image pass), and `ignore_pixel` (else `args.ignore_pixel` where
         present; None: fully annotated labels): the grey level of unlabelled pixels, which the tissue stage trains around as nnU-Net's ignore label
-        (`Segmentor.train_tissue_model_nnUNetv2`'s keyword; the warm-up reads such pixels as background, as it reads every unmapped level).  At level "cell" it is
+        (`Segmentor.train_tissue_model_nnUNetv2`'s keyword; the warm-up reads such pixels as background, as it reads every unmapped level), and `regions` /
+        `regions_class_order` (else the file `args.regions` names, where present; None: plain labels): region labels, which the tissue stage trains with one
+        sigmoid head per region (`Segmentor.train_tissue_model_nnUNetv2`'s keywords, and so is `region_loss`: None is its default, the focal form).  At level "cell" it is
         `Segmentor.train_cell_model(args.num_epochs - 10, ldiffusion_weight, args.diffusion_path, cell_weights=..., instances=...)` (:312-313) and returns
         the folder that holds cellclassifier.pth (None when no epoch validated above 0.0).  `cell_weights` = the CellSegClassifier state dict (or its path)
         the stage starts from: the reference starts from torchvision's ImageNet weights, which it downloads, and this build downloads nothing -- without
@@ -260,6 +264,15 @@ class LDiffusionModel:
                 ignore_pixel = getattr(args, "ignore_pixel", None)
             if ignore_pixel is not None:
                 segmentor_kwargs["ignore_pixel"] = ignore_pixel
+            if regions is None and getattr(args, "regions", None) is not None:
+                import json
+                with open(args.regions) as f:
+                    given = json.load(f)
+                regions, regions_class_order = given["regions"], given["regions_class_order"]
+            if regions is not None:
+                segmentor_kwargs.update(regions=regions, regions_class_order=regions_class_order)
+                if region_loss is not None:
+                    segmentor_kwargs["region_loss"] = region_loss
             return segmentor.train_tissue_model_nnUNetv2(args.num_epochs - 10, ldiffusion_weight, args.diffusion_path, **segmentor_kwargs)
         return ldiffusion_weight
 

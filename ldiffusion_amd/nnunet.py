@@ -18,6 +18,7 @@ import re
 from copy import deepcopy
 from typing import Dict, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 NORMALIZATIONS = ("ZScoreNormalization", "RGBTo01Normalization", "RescaleTo01Normalization", "NoNormalization")
@@ -56,7 +57,8 @@ def resolve_configuration(plans: dict, name: str) -> dict:
 def label_spec(labels: dict) -> Tuple[int, Optional[int]]:
     """(n_heads, ignore_label) of a dataset.json `labels` mapping, by LabelManager's rules (label_handling.py:35-45, 101-106): the optional entry
     `"ignore"` must be an integer and the highest value, max(all other labels) + 1 -- with consecutive labels their number, so it is the first value
-    the network has no head for; `n_heads` leaves it out.  Regions, and an ignore entry that breaks the rule, are refused naming the field."""
+    the network has no head for; `n_heads` leaves it out.  Regions (they go through `region_spec`), and an ignore entry that breaks the rule, are refused
+    naming the field."""
     if any(isinstance(v, (list, tuple)) for v in labels.values()):
         _refuse("labels", "defines regions")
     if "ignore" not in labels:
@@ -69,11 +71,86 @@ def label_spec(labels: dict) -> Tuple[int, Optional[int]]:
     return n_heads, k
 
 
-def network_spec(plans: dict, configuration_name: str, dataset_json: dict, accept_ignore: bool = False) -> dict:
+# `sigmoid(logit) > 0.5` is a step function of the logit; the step depends on the dtype the sigmoid is taken in.  Each constant is the LARGEST logit that
+# still compares false, so the rule is `logit > threshold` (tests/test_cpu_nnunet_regions.py finds both again with torch on the CPU):
+#   inference thresholds sigmoid(l.float()) (label_handling.py:136-141, 171): float32; torch's 1 / (1 + exp(-x)) gives 0.5 up to x = 1.5 * 2^-24, where
+#   1 + exp(-x) still rounds to 2 (bisection over float32, and every float32 of [2^-27, 2^-21) enumerated: one step);
+#   validation thresholds torch.sigmoid(output) on the network's float16 output (nnUNetTrainer.py:960): the float32 value rounds to the float16 0.5 up
+#   to x = 2^-10, a tie that goes to even (all finite float16 values enumerated).
+REGION_THRESHOLD_F32 = 1.5 * 2.0 ** -24
+REGION_THRESHOLD_F16 = 2.0 ** -10
+REGION_IGNORE_BIT, REGION_BAD_BIT, REGION_MAX = 1 << 31, 1 << 30, 24
+
+
+def has_regions(labels: dict) -> bool:
+    """LabelManager's rule (label_handling.py:32-33): an entry that lists more than one value."""
+    return any(isinstance(v, (list, tuple)) and len(v) > 1 for v in labels.values())
+
+
+def region_spec(labels: dict, regions_class_order) -> dict:
+    """LabelManager (label_handling.py:22-100, 204-234) for a dataset.json `labels` mapping with list-valued entries:
+    `all_labels` (sorted, the ignore label left out), `foreground_regions` (dictionary order, as tuples or single integers; entries that are only
+    background dropped, a region that holds 0 among other labels kept), `n_heads` = their number, `ignore_label` (None, or the integer max(all_labels) + 1),
+    `regions_class_order` (required, one entry per region, each 0 .. 255: the value `ldiff_op_region_mask_u8` writes) and `table`: uint32 [256] indexed by
+    label value -- bit r: the value belongs to foreground region r; bit 31: the ignore label; bit 30: neither a label nor the ignore label.
+    Refusals name the field."""
+    if "background" not in labels or isinstance(labels["background"], (list, tuple)) or int(labels["background"]) != 0:
+        _refuse("labels", "must declare `background` as the label 0")
+    ignore = labels.get("ignore")
+    if ignore is not None and (isinstance(ignore, bool) or not isinstance(ignore, int)):
+        _refuse("labels", f"has an ignore label that is not an integer: {ignore!r}")
+    if not has_regions(labels):   # LabelManager reads such a mapping as plain classes (softmax heads), single-valued lists included
+        _refuse("labels", "defines no region of more than one value, so nnU-Net reads it as plain labels")
+    all_labels, regions = set(), []
+    for name, r in labels.items():
+        if name == "ignore":
+            continue
+        values = [int(v) for v in r] if isinstance(r, (list, tuple)) else [int(r)]
+        all_labels.update(values)
+        if set(values) == {0}:   # a region that is only background
+            continue
+        regions.append(tuple(values) if isinstance(r, (list, tuple)) else int(r))
+    all_labels = sorted(all_labels)
+    if all_labels[0] < 0 or all_labels[-1] > 254:
+        _refuse("labels", f"holds values outside 0 .. 254: {all_labels[0]} .. {all_labels[-1]} (label maps are bytes, and 255 stands for every value beyond them)")
+    if ignore is not None and ignore != all_labels[-1] + 1:
+        _refuse("labels", f"has the ignore label {ignore}, which is not the highest value, max(all labels) + 1 = {all_labels[-1] + 1}")
+    if len(regions) < 1:
+        _refuse("labels", "defines no foreground region")
+    if len(regions) > REGION_MAX:
+        _refuse("labels", f"defines {len(regions)} regions; the membership table has {REGION_MAX} region bits")
+    if regions_class_order is None:
+        _refuse("regions_class_order", "is missing, and region labels need it")
+    order = list(regions_class_order)
+    if len(order) != len(regions):
+        _refuse("regions_class_order", f"has {len(order)} entries for {len(regions)} regions")
+    if any(isinstance(c, bool) or int(c) != c or not 0 <= int(c) <= 255 for c in order):
+        _refuse("regions_class_order", f"holds an entry that is no integer in 0 .. 255: {order}")
+    table = [REGION_BAD_BIT] * 256
+    for v in all_labels:
+        table[v] = 0
+    for i, r in enumerate(regions):
+        for v in (r if isinstance(r, tuple) else (r,)):
+            table[v] |= 1 << i
+    if ignore is not None:
+        table[ignore] = REGION_IGNORE_BIT
+    return dict(all_labels=all_labels, foreground_regions=regions, n_heads=len(regions), ignore_label=ignore, regions_class_order=[int(c) for c in order],
+                table=np.array(table, dtype=np.uint32))
+
+
+def region_table_tensor(table, device=None) -> torch.Tensor:
+    """The membership table as the kernels take it: the uint32 [256] bit patterns in an int32 tensor (torch has no arithmetic on uint32), on `device`."""
+    t = torch.from_numpy(np.ascontiguousarray(np.asarray(table, dtype=np.uint32)).view(np.int32).copy())
+    return t if device is None else t.to(device)
+
+
+def network_spec(plans: dict, configuration_name: str, dataset_json: dict, accept_ignore: bool = False, accept_regions: bool = False) -> dict:
     """The layer list of the network `get_network_from_plans` would build, plus what the sliding window and the preprocessing need.
     Refuses, naming the field, whatever the HIP head does not cover.  `accept_ignore`: a dataset with an ignore label (`label_spec`) is taken and
     adds `ignore_label` to the spec; `n_heads` never counts it, so no head can predict it.  Off, the default, such a dataset is refused as it always
-    was: a caller that has not asked for the label would train on it as a class of its own."""
+    was: a caller that has not asked for the label would train on it as a class of its own.
+    `accept_regions`: a dataset whose labels define regions is taken through `region_spec`: `n_heads` is the number of foreground regions (one sigmoid head
+    each) and the spec gains `regions`, `regions_class_order`, `region_table` and, where one is declared, `ignore_label`.  Off, it is refused as before."""
     cfg = resolve_configuration(plans, configuration_name)
     if cfg.get("UNet_class_name") != "PlainConvUNet":
         _refuse("UNet_class_name", f"is {cfg.get('UNet_class_name')!r}")
@@ -100,8 +177,13 @@ def network_spec(plans: dict, configuration_name: str, dataset_json: dict, accep
     for s in schemes:
         if s not in NORMALIZATIONS:
             _refuse("normalization_schemes", f"names {s!r}")
-    n_heads, ignore_label = label_spec(dataset_json["labels"])
-    if ignore_label is not None and not accept_ignore:
+    regions = None
+    if accept_regions and has_regions(dataset_json["labels"]):
+        regions = region_spec(dataset_json["labels"], dataset_json.get("regions_class_order"))
+        n_heads, ignore_label = regions["n_heads"], regions["ignore_label"]
+    else:
+        n_heads, ignore_label = label_spec(dataset_json["labels"])
+    if ignore_label is not None and regions is None and not accept_ignore:
         _refuse("labels", "defines an ignore label (network_spec(accept_ignore=True) takes it)")
     channels = dataset_json["channel_names"] if "channel_names" in dataset_json else dataset_json["modality"]
     in_channels = len(channels)
@@ -124,6 +206,8 @@ def network_spec(plans: dict, configuration_name: str, dataset_json: dict, accep
                 n_heads=n_heads, patch_size=tuple(patch), normalization_schemes=schemes)
     if ignore_label is not None:
         spec["ignore_label"] = ignore_label
+    if regions is not None:
+        spec.update(regions=regions["foreground_regions"], regions_class_order=regions["regions_class_order"], region_table=regions["table"])
     return spec
 
 
@@ -239,6 +323,27 @@ def uncrop_mask(mask: torch.Tensor, box, full_hw) -> torch.Tensor:
     return out
 
 
+def region_mask_u8(logits: torch.Tensor, regions_class_order, threshold: float = REGION_THRESHOLD_F32, out: torch.Tensor = None, origin=(0, 0)) -> torch.Tensor:
+    """ldiff_op_region_mask_u8: LabelManager.convert_probabilities_to_segmentation's region branch on device logits [R, H, W] (float16 or float32) --
+    0, then regions_class_order[i] where logit i > threshold, in order.  Written into `out` (uint8 [H0, W0] on the device) at `origin`, or a new [H, W] mask."""
+    import ctypes
+    from . import _lib
+    if logits.dim() != 3 or not logits.is_cuda or logits.dtype not in (torch.float16, torch.float32):
+        raise ValueError("region_mask_u8: `logits` must be a float16 or float32 device tensor [R, H, W]")
+    logits = logits.contiguous()
+    R, H, W = logits.shape
+    order = [int(c) for c in regions_class_order]
+    if len(order) != R:
+        raise ValueError(f"region_mask_u8: regions_class_order has {len(order)} entries for {R} regions")
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.uint8, device=logits.device)
+    elif out.dim() != 2 or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != logits.device:
+        raise ValueError("region_mask_u8: `out` must be a contiguous uint8 tensor [H0, W0] on the logits' device")
+    _lib.check(_lib.load().ldiff_op_region_mask_u8(_lib.ptr(logits), int(logits.dtype == torch.float32), R, H, W, (ctypes.c_int * R)(*order), float(threshold),
+                                                   _lib.ptr(out), out.shape[0], out.shape[1], int(origin[0]), int(origin[1]), _lib.stream_ptr()))
+    return out
+
+
 class TrainedModel:
     """What the predictor keeps after initialize_from_trained_model_folder: `.network` (callable [B, C, h, w] -> [B, heads, h, w]), `.patch_size`,
     `.mirror_axes` (the checkpoint's inference_allowed_mirroring_axes), `.normalization_schemes`, `.num_heads`, `.spec`."""
@@ -273,6 +378,14 @@ class TrainedModel:
         if len(tile) != 2 or any(t < div or t % div for t in tile):
             raise ValueError(f"tile_size {tile} must be a multiple of the product of the network's strides, {div}, in both axes")
         axes = self.mirror_axes if mirror_axes == "checkpoint" else mirror_axes
+        if "regions" in self.spec:   # one sigmoid head per region: the region rule in place of the arg-max; outside the crop box 0 (revert_cropping_on_probabilities)
+            net = network if network is not None else self.network
+            if batch_tiles is not None:
+                logits = tiling.predict_sliding_window_batched(x, net, self.num_heads, tile, tile_step_size, True, axes, batch_tiles=int(batch_tiles))
+            else:
+                logits = tiling.predict_sliding_window_return_logits(x, net, self.num_heads, tile, tile_step_size, True, axes)
+            out = torch.zeros(tuple(data.shape[1:]), dtype=torch.uint8, device=x.device)
+            return region_mask_u8(logits, self.spec["regions_class_order"], REGION_THRESHOLD_F32, out=out, origin=(box[0], box[2]))
         if batch_tiles is not None:
             out = torch.zeros(tuple(data.shape[1:]), dtype=torch.uint8, device=x.device)   # pixels outside the crop box are label 0 (uncrop_mask)
             return tiling.predict_sliding_window_batched(x, network if network is not None else self.network, self.num_heads, tile, tile_step_size, True, axes,
@@ -292,7 +405,8 @@ def read_trained_model_folder(model_dir: str, fold=0, checkpoint_name: str = "ch
     with open(os.path.join(model_dir, "plans.json")) as f:
         plans = json.load(f)
     ckpt = torch.load(os.path.join(model_dir, f"fold_{fold}", checkpoint_name), map_location="cpu", weights_only=False)
-    spec = network_spec(plans, ckpt["init_args"]["configuration"], dataset_json, accept_ignore=True)   # the network has no head for it: inference is the same
+    # the network has no head for an ignore label: inference is the same.  A trained folder with region labels was made on purpose: no opt-in to load it
+    spec = network_spec(plans, ckpt["init_args"]["configuration"], dataset_json, accept_ignore=True, accept_regions=True)
     sd = clean_state_dict(ckpt["network_weights"], spec)
     check_state_dict(sd, spec)
     return spec, sd, ckpt.get("inference_allowed_mirroring_axes")

@@ -135,10 +135,12 @@ def sample_foreground_locations(seg: np.ndarray, classes: Sequence[int], seed: i
     """DefaultPreprocessor._sample_foreground_locations (default_preprocessor.py:152-178) for plain labels of one [H, W] map: per class a subset of
     np.argwhere(seg == c) chosen without replacement by ONE RandomState(seed) walked through the classes in order; an absent class gets [].
     `annotated` = n_heads of a dataset with an ignore label: one more entry after the classes, key `annotated_key(n_heads)`, drawn by the same
-    walk from the pixels of any class 0 .. n_heads - 1 (:99-102), so the entries before it are what they are without it."""
+    walk from the pixels of any class 0 .. n_heads - 1 (:99-102), so the entries before it are what they are without it.
+    Region labels: `classes` holds LabelManager.foreground_regions (tuples, or single integers), which key the entries as nnU-Net's class_locations are
+    keyed; `annotated` is then the key itself, tuple(all_labels)."""
     rndst = np.random.RandomState(seed)
     out = {}
-    for c in list(classes) + ([annotated_key(annotated)] if annotated is not None else []):
+    for c in list(classes) + ([annotated if isinstance(annotated, tuple) else annotated_key(annotated)] if annotated is not None else []):
         key = c if isinstance(c, tuple) else int(c)
         locs = np.argwhere(np.isin(seg, c) if isinstance(c, tuple) else seg == c)
         if len(locs) == 0:
@@ -169,7 +171,10 @@ class CaseStore:
     (y0, y1, x0, x1) of case i in its source image (the full extent without a crop)."""
 
     def __init__(self, cases, schemes: Sequence[str], n_heads: int, device="cuda:0", labels: Optional[dict] = None, prefilter: str = "host",
-                 build: str = "host", crop: bool = False):
+                 build: str = "host", crop: bool = False, regions: Optional[dict] = None):
+        """`regions`: a `nnunet.region_spec` result -- region labels.  The label maps keep their label values (the loss looks membership up in the
+        spec's table); `n_heads` is the number of regions; `class_locations` is keyed by the foreground regions, as nnU-Net's is, and with an ignore label
+        ends with the annotated key tuple(all_labels).  `labels=` keeps refusing regions."""
         if prefilter not in ("host", "device"):
             raise ValueError(f"CaseStore: prefilter must be 'host' or 'device', got {prefilter!r}")
         if prefilter == "device" and torch.device(device).type != "cuda":
@@ -183,8 +188,22 @@ class CaseStore:
             heads, self.ignore_label = nnunet.label_spec(labels)
             if self.ignore_label is not None and heads != int(n_heads):
                 raise ValueError(f"CaseStore: `labels` names {heads} classes and the ignore label {self.ignore_label}, n_heads is {n_heads}")
-        if not 2 <= int(n_heads) <= 32:
-            raise ValueError(f"CaseStore: n_heads {n_heads} out of range [2, 32]")
+        self.regions = None if regions is None else list(regions["foreground_regions"])
+        if regions is not None:
+            if labels is not None:
+                raise ValueError("CaseStore: `labels` and `regions` exclude each other (`regions` carries the ignore label)")
+            if int(n_heads) != int(regions["n_heads"]):
+                raise ValueError(f"CaseStore: `regions` defines {regions['n_heads']} regions, n_heads is {n_heads}")
+            self.ignore_label = regions["ignore_label"]
+            self.region_table = np.asarray(regions["table"], dtype=np.uint32)
+            self._top = int(regions["all_labels"][-1]) + 1          # label values run over [0, _top), and _top is the ignore label where there is one
+            self.annotated = tuple(int(v) for v in regions["all_labels"]) if self.ignore_label is not None else None
+        else:
+            self._top = int(n_heads)
+            self.annotated = annotated_key(n_heads) if self.ignore_label is not None else None
+        lo, hi = (1, nnunet.REGION_MAX) if regions is not None else (2, 32)
+        if not lo <= int(n_heads) <= hi:
+            raise ValueError(f"CaseStore: n_heads {n_heads} out of range [{lo}, {hi}]")
         cases = list(cases)
         if not cases:
             raise ValueError("CaseStore: no cases")
@@ -214,10 +233,11 @@ class CaseStore:
             if crop:
                 img, seg = img[:, box[0]:box[1], box[2]:box[3]], seg[box[0]:box[1], box[2]:box[3]]
                 H, W = box[1] - box[0], box[3] - box[2]
-            top = self.n_heads if self.ignore_label is None else self.n_heads + 1   # the ignore label is the one value past the classes
+            top = self._top if self.ignore_label is None else self._top + 1   # the ignore label is the one value past the classes
             if seg.min() < 0 or seg.max() >= top:
                 bad = sorted(int(v) for v in np.unique(seg) if v < 0 or v >= top)
-                raise ValueError(f"CaseStore: case {i}: labels {bad[:5]} outside [0, {self.n_heads})")
+                raise ValueError(f"CaseStore: case {i}: labels {bad[:5]} outside [0, {self._top})")
+            self._check_region_values(i, seg)
             raw = nnunet.normalize(img.cpu().to(torch.float32), self.schemes).numpy()
             coef = spline_coefficients(raw).astype(np.float32) if prefilter == "host" else raw
             row = self.table[i]
@@ -227,7 +247,9 @@ class CaseStore:
                 row[key] = size
                 parts.append((size, np.ascontiguousarray(arr).view(np.uint8).reshape(-1)))
                 size += parts[-1][1].size
-            self.class_locations.append(sample_foreground_locations(seg, range(1, self.n_heads), annotated=None if self.ignore_label is None else self.n_heads))
+            self.class_locations.append(sample_foreground_locations(seg, self.regions if self.regions is not None else range(1, self.n_heads),
+                                                                    annotated=self.annotated if self.regions is not None else
+                                                                    (None if self.ignore_label is None else self.n_heads)))
         host = np.zeros((size + 15) // 16 * 16, np.uint8)
         for off, arr in parts:
             host[off:off + arr.size] = arr
@@ -237,10 +259,19 @@ class CaseStore:
                 spline_prefilter_(self.coefficients(i))
         self.cases_dev = torch.from_numpy(self.table.view(np.uint8).reshape(-1).copy()).to(self.device)
 
+    def _check_region_values(self, i: int, seg) -> None:
+        """Region labels: a value below the top that is no label of the dataset (the table's bit 30) is refused like one outside the range."""
+        if self.regions is None:
+            return
+        values = np.unique(seg.cpu().numpy() if torch.is_tensor(seg) else seg)
+        bad = sorted(int(v) for v in values if self.region_table[int(v)] & (1 << 30))
+        if bad:
+            raise ValueError(f"CaseStore: case {i}: labels {bad[:5]} are no labels of the dataset")
+
     def _build_on_device(self, cases, prefilter: str):
         """build="device": the case kernels in three rounds with one synchronisation each -- boxes; statistics and label counts over the boxes; then the
         arena is laid out, every case normalised into it and the sampled foreground ranks turned into pixels."""
-        dev, nh = self.device, self.n_heads
+        dev, nh = self.device, self._top   # the label values counted: the classes, or with regions every value up to the highest label
         ign = self.ignore_label is not None
         counted = nh + 1 if ign else nh   # the ignore label is counted as one more class, so that "no class and not ignored" keeps its own count
         imgs, segs, given = [], [], []
@@ -297,9 +328,24 @@ class CaseStore:
                     spline_prefilter_(self.coefficients(i))
                 else:
                     self.coefficients(i).copy_(torch.from_numpy(spline_coefficients(self.raw(i).cpu().numpy()).astype(np.float32)))
+            if self.regions is not None:   # the membership table on the device, once for all cases
+                member_table = torch.from_numpy(self.region_table.astype(np.int64)).to(dev)
+                plane_totals = torch.empty(4, dtype=torch.int32, device=dev)
             for i in range(n):   # sample_foreground_locations: ONE RandomState per case walked through the classes; only the counts are needed here
                 rndst, picked = np.random.RandomState(1234), {}
-                for c in range(1, nh):
+                if self.regions is not None:   # per region its binary membership plane, once: a gather through the table, then the class kernels with selector 1
+                    b = self.boxes[i]
+                    member = member_table[segs[i].long()]
+                    if bool((member[b[0]:b[1], b[2]:b[3]] & (1 << 30)).any()):   # one reduction on the device; the error path alone looks at values
+                        self._check_region_values(i, segs[i][b[0]:b[1], b[2]:b[3]])
+                    for r, region in enumerate(self.regions):
+                        plane = ((member >> r) & 1).to(torch.uint8).contiguous()
+                        prefix = _launch_case_counts(plane, self.boxes[i], 2, plane_totals)[1]
+                        count = int(plane_totals[1])
+                        picked[region] = [] if count == 0 else _launch_case_rank(
+                            plane, self.boxes[i], 1, prefix[1], torch.from_numpy(rndst.choice(count, _target_num_samples(count), replace=False).astype(np.int64)).to(dev),
+                            None)[0]
+                for c in (range(1, nh) if self.regions is None else ()):
                     count = int(totals[i, c])
                     if count == 0:
                         picked[c] = []
@@ -308,7 +354,7 @@ class CaseStore:
                     picked[c] = _launch_case_rank(segs[i], self.boxes[i], c, prefixes[i][c], ranks, None)[0]
                 if ign:   # the same walk goes on to the annotated pixels, `label < n_heads`: the selector -1 - n_heads, its prefix the table's last row
                     count = int(totals[i, counted + 2])
-                    picked[annotated_key(nh)] = [] if count == 0 else _launch_case_rank(
+                    picked[self.annotated] = [] if count == 0 else _launch_case_rank(
                         segs[i], self.boxes[i], -1 - nh, prefixes[i][counted + 1],
                         torch.from_numpy(rndst.choice(count, _target_num_samples(count), replace=False).astype(np.int64)).to(dev), None)[0]
                 self.class_locations.append({c: (v if isinstance(v, list) else v.cpu().numpy().astype(np.int64)) for c, v in picked.items()})
@@ -376,7 +422,7 @@ def draw_crop(rng: np.random.Generator, store: CaseStore, sample_idx: int, batch
     voxel = None
     has_ignore = getattr(store, "ignore_label", None) is not None
     if has_ignore:
-        key = annotated_key(store.n_heads)
+        key = getattr(store, "annotated", None) or annotated_key(store.n_heads)   # with regions: tuple(all_labels)
         if not forced:
             eligible = [key] if key in eligible else []
         elif key in eligible and len(eligible) > 1:

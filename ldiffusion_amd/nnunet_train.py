@@ -244,8 +244,11 @@ class Trainer:
 
     def __init__(self, spec: dict, state_dict, batch_dice: bool, num_epochs: int, initial_lr: float = 1e-2, weight_decay: float = 3e-5, device="cuda:0", *,
                  configuration: str = "2d", init_args: Optional[dict] = None, mirror_axes: Optional[Sequence[int]] = (0, 1), loss_scale: Optional[float] = None,
-                 slope: float = SLOPE, ddp: Optional[bool] = None, group=None, wgrad_route: Optional[str] = None, ignore_label: Optional[int] = None):
-        """`ignore_label`: the dataset's ignore label (spec["ignore_label"] of nnunet.network_spec; it equals n_heads), None for fully annotated labels.
+                 slope: float = SLOPE, ddp: Optional[bool] = None, group=None, wgrad_route: Optional[str] = None, ignore_label: Optional[int] = None, region_loss: str = "focal"):
+        """A `spec` with `regions` (nnunet.network_spec(accept_regions=True)) trains region labels: one sigmoid head per region, the loss the reference's
+        DC_and_Focal_loss (`region_loss="focal"`) or nnU-Net's DC_and_BCE_loss ("bce") on the label map through the spec's membership table, the
+        validation counts per region; the ignore label is then the spec's own (max(all labels) + 1).
+        `ignore_label`: the dataset's ignore label (spec["ignore_label"] of nnunet.network_spec; it equals n_heads), None for fully annotated labels.
         `ddp`: None follows the launch (a process group of more than one rank: nnUNetTrainer.is_ddp), True / False force it; `group` the process group
         (None: the default one).  ddp at world size 1 is legal: the collectives are identities.  `self.world` is the factor of the Dice gradient and of
         the gradient mean; code that does the two collectives by hand for several trainers in one process sets it to their number."""
@@ -255,7 +258,17 @@ class Trainer:
         self.batch_dice = bool(batch_dice)
         self.num_epochs, self.initial_lr, self.weight_decay = int(num_epochs), float(initial_lr), float(weight_decay)
         self.n_heads = int(spec["n_heads"])
-        if ignore_label is not None and int(ignore_label) != self.n_heads:
+        self.regions = "regions" in spec
+        if region_loss not in ("focal", "bce"):
+            raise ValueError(f"Trainer: region_loss {region_loss!r} is neither 'focal' nor 'bce'")
+        self.region_loss = region_loss
+        if self.regions:
+            from . import nnunet
+            if ignore_label is not None and ignore_label != spec.get("ignore_label"):
+                raise ValueError(f"Trainer: ignore_label {ignore_label} is not the region spec's, {spec.get('ignore_label')} (nnunet.region_spec)")
+            ignore_label = spec.get("ignore_label")
+            self.region_table = nnunet.region_table_tensor(spec["region_table"], self.device)
+        elif ignore_label is not None and int(ignore_label) != self.n_heads:
             raise ValueError(f"Trainer: ignore_label {ignore_label} must be the first value past the classes, n_heads = {self.n_heads} (nnunet.label_spec)")
         self.ignore_label = None if ignore_label is None else int(ignore_label)
         self.weights = deep_supervision_weights(spec["n_stages"] - 1)
@@ -316,7 +329,11 @@ class Trainer:
         for o, t, w in zip(outputs, targets, self.weights):
             if w == 0.0:
                 continue
-            term = ag.DiceCeFn.apply(o, t, self.n_heads, self.batch_dice, w, grad_scale, SMOOTH, self.ignore_label)   # the weighted term
+            if self.regions:
+                term = ag.DiceFocalFn.apply(o, t, self.region_table, self.n_heads, self.batch_dice, w, grad_scale, SMOOTH, self.ignore_label is not None,
+                                            self.region_loss)
+            else:
+                term = ag.DiceCeFn.apply(o, t, self.n_heads, self.batch_dice, w, grad_scale, SMOOTH, self.ignore_label)   # the weighted term
             total = term if total is None else total + term
         return total
 
@@ -348,21 +365,32 @@ class Trainer:
     def _statistics(self, outputs, targets):
         """(graded scales, their local statistics, the [scales, NACC] table to exchange)"""
         graded = [(o, t, w) for o, t, w in zip(outputs, targets, self.weights) if w != 0.0]
-        nacc = ag.dice_ce_nacc(self.n_heads, self.ignore_label)
+        nacc = ag.dice_focal_nacc(self.n_heads) if self.regions else ag.dice_ce_nacc(self.n_heads, self.ignore_label)
         table = torch.empty((len(graded), nacc), dtype=torch.float64, device=self.device)
         local = []
+
+        def stats(o, t, batch_dice, out=None):
+            if self.regions:
+                return ag.dice_focal_stats(o, t, self.region_table, self.n_heads, batch_dice, out=out, use_ignore=self.ignore_label is not None,
+                                           region_loss=self.region_loss)
+            return ag.dice_ce_stats(o, t, self.n_heads, batch_dice, out=out, ignore_label=self.ignore_label)
+
         for i, (o, t, _) in enumerate(graded):
             if self.batch_dice:
-                local.append(ag.dice_ce_stats(o, t, self.n_heads, True, out=table[i], ignore_label=self.ignore_label).view(1, nacc))
+                local.append(stats(o, t, True, table[i]).view(1, nacc))
             else:   # per-sample Dice stays on its rank; the exchanged row carries the bad-label count
-                local.append(ag.dice_ce_stats(o, t, self.n_heads, False, ignore_label=self.ignore_label))
+                local.append(stats(o, t, False))
                 table[i] = local[-1].sum(0)
         return graded, local, table
 
     def _loss_from_sums(self, graded, local, global_sums, grad_scale):
         total = None
         for i, ((o, t, w), loc) in enumerate(zip(graded, local)):
-            if self.batch_dice:
+            if self.regions:
+                dsums, world = (global_sums[i], self.world) if self.batch_dice else (loc, 1)
+                term = ag.DiceFocalSumsFn.apply(o, t, self.region_table, self.n_heads, self.batch_dice, dsums, loc, world, w, grad_scale, SMOOTH,
+                                                self.ignore_label is not None, self.region_loss)
+            elif self.batch_dice:
                 term = ag.DiceCeSumsFn.apply(o, t, self.n_heads, True, global_sums[i], loc, self.world, w, grad_scale, SMOOTH, self.ignore_label)
             else:
                 term = ag.DiceCeSumsFn.apply(o, t, self.n_heads, False, loc, loc, 1, w, grad_scale, SMOOTH, self.ignore_label)
@@ -478,6 +506,10 @@ class Trainer:
                 top = top[:, 0]
             if top.is_floating_point():
                 top = top.long()
+            if self.regions:   # :955-982, region branch: sigmoid(output) > 0.5 on the network's float16 output, all R regions, no background row to drop
+                from . import nnunet
+                c = ag.region_counts(outputs[0], top.to(self.device), self.region_table, self.n_heads, nnunet.REGION_THRESHOLD_F16).cpu().numpy()
+                return {"loss": loss, "tp_hard": c[0], "fp_hard": c[1], "fn_hard": c[2]}
             logits = outputs[0][..., :self.n_heads].permute(0, 3, 1, 2).contiguous()
             conf = metrics.confusion_matrix(logits, top.to(self.device), self.n_heads).sum(0).cpu().numpy()
         tp = np.diag(conf)

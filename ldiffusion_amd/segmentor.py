@@ -221,7 +221,7 @@ class Segmentor:
 
     def train_tissue_model_nnUNetv2(self, epochs, ldiffusion_weight, diffusion_path, train_images=None, train_labels=None, test_images=None, test_labels=None,
                                     num_classes=None, *, iterations_per_epoch=250, val_iterations=50, num_foreground_voxels=None, wgrad_route=None, batch_images=None, io_workers=4,
-                                    ignore_pixel=None):
+                                    ignore_pixel=None, regions=None, regions_class_order=None, region_loss="focal"):
         """segmentor.py:163-241: the tissue head's training stage, from image lists to a trained-model folder.
         Dataset (:167-205): `load_ldiffusion`, the cached text embeddings of "A pathological slide", the text-alignment wrapper, and
         `utils.create_nnunet_dataset` under nnUNet_raw (the one-pass diffusion of every image when all share one size, else copies).
@@ -236,7 +236,10 @@ class Segmentor:
         (None: the per-image dataset pass; an integer: the pass batched behind the device image front end).  `ignore_pixel`: the grey level of
         unlabelled pixels in partly annotated label images (`utils.create_nnunet_dataset`'s): the dataset declares nnU-Net's ignore label, the stores
         draw patches from annotated areas and the trainer leaves those pixels out of loss, gradient and validation counts; None: fully annotated
-        labels, the stage as it was.  With an ignore label the stage runs on one rank (the data-parallel step's ignore form is not built).  The three folders come from the environment variables nnUNet_raw, nnUNet_preprocessed, nnUNet_results.
+        labels, the stage as it was.  With an ignore label the stage runs on one rank (the data-parallel step's ignore form is not built).
+        `regions`, `regions_class_order` (`utils.create_nnunet_dataset`'s): region labels -- one sigmoid head per region, the reference's Dice + focal loss
+        (`region_loss="bce"`: nnU-Net's Dice + BCE), patches oversampled among regions, validation Dice per region; the written folder predicts through
+        the region rule.  None: the stage as it was.  The three folders come from the environment variables nnUNet_raw, nnUNet_preprocessed, nnUNet_results.
         Under a process group of more than one rank the stage is data-parallel, as the reference's nnUNetTrainer is under the same launch: rank 0 alone
         writes the dataset, the fingerprint, plans, split and the model folder; `(new_num, dataset_name)` go out by `broadcast_object_list` and a
         barrier; every rank then reads the PNGs and JSONs and builds both stores on its own device; its loaders take its entry of
@@ -271,6 +274,8 @@ class Segmentor:
             batch_kwargs = {} if batch_images is None else dict(batch_images=batch_images, io_workers=io_workers)   # None: the call of before the keyword
             if ignore_pixel is not None:
                 batch_kwargs["ignore_pixel"] = ignore_pixel
+            if regions is not None:
+                batch_kwargs.update(regions=regions, regions_class_order=regions_class_order)
             named = list(utils.create_nnunet_dataset(train_images, train_labels, test_images, test_labels, num_classes, pipeline, aligned_unet,
                                                      raw_dir=roots["nnUNet_raw"], **batch_kwargs))
         if world > 1:
@@ -313,10 +318,14 @@ class Segmentor:
             plans, splits = load_json("nnUNetPlans.json"), load_json("splits_final.json")
 
         print("\033[32m[Segmentor-nnUNet] Training is starting...\033[0m")
-        spec = nnunet.network_spec(plans, "2d", dataset_json, accept_ignore=ignore_pixel is not None)
+        spec = nnunet.network_spec(plans, "2d", dataset_json, accept_ignore=ignore_pixel is not None, accept_regions=regions is not None)
         cfg = plans["configurations"]["2d"]
+        if "regions" in spec:
+            store_labels = dict(regions=nnunet.region_spec(dataset_json["labels"], dataset_json["regions_class_order"]))
+        else:
+            store_labels = dict(labels=dataset_json["labels"])
         stores = [nnunet_data.CaseStore([cases[k] for k in splits[0][part]], spec["normalization_schemes"], spec["n_heads"], device=self.device,
-                                        labels=dataset_json["labels"], prefilter="device", build="device") for part in ("train", "val")]
+                                        prefilter="device", build="device", **store_labels) for part in ("train", "val")]
         n_scales = spec["n_stages"] - 1
         if world > 1:
             batch, oversample = nnunet_train.rank_batch_sizes(cfg["batch_size"], world, nnunet_data.OVERSAMPLE_FOREGROUND)[rank]
@@ -329,6 +338,8 @@ class Segmentor:
         ignore = {}
         if spec.get("ignore_label") is not None:   # nnUNetTrainer keeps the dataset.json it was built with, ignore entry included, in the checkpoint's init_args
             ignore = dict(ignore_label=spec["ignore_label"], init_args={"configuration": "2d", "fold": 0, "dataset_json": dataset_json})
+        if "regions" in spec:
+            ignore.update(region_loss=region_loss, init_args={"configuration": "2d", "fold": 0, "dataset_json": dataset_json})
         trainer = nnunet_train.Trainer(spec, nnunet_train.initial_state_dict(spec), cfg["batch_dice"], num_epochs=epochs, device=self.device, wgrad_route=wgrad_route,
                                        **ignore)
         model_dir = os.path.join(roots["nnUNet_results"], dataset_name, "nnUNetTrainer__nnUNetPlans__2d")

@@ -215,7 +215,7 @@ def convert_and_save_label(lbl, dst_path, mapping):
 
 
 def create_nnunet_dataset(train_images, train_labels, test_images, test_labels, num_classes, pipeline, unet, raw_dir=None, batch_images=None, io_workers=4,
-                          ignore_pixel=None):
+                          ignore_pixel=None, regions=None, regions_class_order=None):
     """utils.py:210-294: the next `DatasetNNN_Custom` under nnUNet_raw (`raw_dir`, else the environment variable nnUNet_raw) with imagesTr / labelsTr /
     imagesTs / labelsTs, `case_%03d_0000.png` + `case_%03d.png` and `caseTs_%03d...`; every image goes through `copy_or_convert_image` -- the
     one-pass diffusion when ALL train and ALL test images share one size, else a plain copy --, every label is resized to its image (NEAREST) and
@@ -225,7 +225,12 @@ def create_nnunet_dataset(train_images, train_labels, test_images, test_labels, 
     alone under `pipeline.set_plan_batch(batch_images)`, the labels and dataset.json those of the default call.  With mixed sizes (plain copies) it changes nothing.
     `ignore_pixel` (None: everything above, byte for byte): the grey level of unlabelled pixels in partly annotated label images.  The label PNGs
     carry `num_classes` there and dataset.json gains `"ignore": num_classes` -- nnU-Net's ignore label, the highest value.  A grey level
-    metrics.PIXEL_TO_LABEL already maps raises ValueError."""
+    metrics.PIXEL_TO_LABEL already maps raises ValueError.
+    `regions` (None: everything above, byte for byte): region labels -- a mapping from a region's name to the list of classes it unites, as class
+    indices, or as the label images' grey levels (keys of metrics.PIXEL_TO_LABEL) when any value is not a class index; `regions_class_order`: the value
+    inference writes per region, in order (nnU-Net's field).  The label PNGs keep class indices; dataset.json carries the region `labels` and
+    `regions_class_order`.  Every foreground class must lie in a region (nnU-Net has no head for a label outside all of them); `nnunet.region_spec`
+    checks the rest before anything is written."""
     import json
     import os
     from pathlib import Path
@@ -239,6 +244,27 @@ def create_nnunet_dataset(train_images, train_labels, test_images, test_labels, 
         if not 2 <= int(num_classes) <= 254:
             raise ValueError(f"create_nnunet_dataset: an ignore label needs 2 .. 254 classes, got {num_classes}")
         mapping = {**mapping, int(ignore_pixel): int(num_classes)}
+    region_labels = None
+    if regions is not None:
+        from . import nnunet
+        values = [v for r in regions.values() for v in r]
+        if any(isinstance(v, bool) or int(v) != v for v in values) or not values:
+            raise ValueError("create_nnunet_dataset: `regions` maps names to non-empty lists of integers")
+        as_levels = any(not 0 <= int(v) < int(num_classes) for v in values)   # grey levels of the label images, not class indices
+        if as_levels and any(int(v) not in metrics.PIXEL_TO_LABEL for v in values):
+            raise ValueError(f"create_nnunet_dataset: `regions` holds {sorted({int(v) for v in values if int(v) not in metrics.PIXEL_TO_LABEL})}: neither class "
+                             f"indices below {num_classes} nor grey levels of metrics.PIXEL_TO_LABEL")
+        region_labels = {"background": 0, **{str(name): [int(metrics.PIXEL_TO_LABEL[int(v)]) if as_levels else int(v) for v in r] for name, r in regions.items()}}
+        if "background" in regions or "ignore" in regions:
+            raise ValueError("create_nnunet_dataset: `regions` may not name a region `background` or `ignore`")
+        outside = sorted(set(range(1, int(num_classes))) - {v for r in region_labels.values() if isinstance(r, list) for v in r})
+        if outside:
+            raise ValueError(f"create_nnunet_dataset: the classes {outside} lie in no region of `regions`")
+        if ignore_pixel is not None:
+            region_labels["ignore"] = int(num_classes)
+        nnunet.region_spec(region_labels, regions_class_order)   # refuses, naming the field, before anything is written
+    elif regions_class_order is not None:
+        raise ValueError("create_nnunet_dataset: `regions_class_order` without `regions`")
     raw = raw_dir if raw_dir is not None else os.environ.get("nnUNet_raw")
     if raw is None:
         raise RuntimeError("create_nnunet_dataset: no nnUNet_raw folder: pass raw_dir= or set the environment variable nnUNet_raw")
@@ -284,6 +310,9 @@ def create_nnunet_dataset(train_images, train_labels, test_images, test_labels, 
         "numTraining": n_train,
         "file_ending": ".png",
     }
+    if region_labels is not None:
+        dataset_json["labels"] = region_labels
+        dataset_json["regions_class_order"] = [int(c) for c in regions_class_order]
     with open(new_path / "dataset.json", "w") as f:
         json.dump(dataset_json, f, indent=4)
     print(f"create new nnUNet Dataset：{new_dataset_name}")
