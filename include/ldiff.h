@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define LDIFF_VERSION 214 /* 0.2.1.3: + ldiff_op_dice_ce_ignore / _ignore_stats / _ignore_from_sums (+ _ignore_ws_bytes, _ignore_nacc): the tissue head's loss with nnU-Net's ignore label; + ldiff_op_case_counts_classes and the selectors -1 - m (`label < m`) of ldiff_op_case_rank_to_coord, for the annotated-pixel locations of a partly annotated case.  0.2.1.2: + ldiff_op_label_table_u8 / ldiff_op_gather_labels / ldiff_op_warmup_labels (+ _supported) / ldiff_op_warmup_images (the warm-up trainer's dataset resident on the device: label bytes through a grey-level table, a batch of labels and masks gathered by index, and the 64x64 warm-up batch -- labels by torch's bilinear rule in integers, images through the normalisation table and the antialiased triangle weights in one pass over the stored bytes); 0.2.1.1: + ldiff_op_resize_u8 / ldiff_op_resize_u8_ws_bytes (the device image front end: PIL.Image.resize(size, BILINEAR) of 8-bit interleaved images bit for bit from host-made coefficient tables, optionally through a float [3][256] table into the sampler's NCHW input; LDIFF_RESIZE_MAX_TAPS); 0.2.1.0: + ldiff_op_window_gather / _accumulate_batch / _finish (the tissue head's sliding window in batches: tiles x mirror variants gathered, un-flipped, averaged and Gaussian-accumulated per chunk, then divide + inf flag + arg-max + un-crop in one launch; ldiff_window_tiles by value), after ldiff_op_dice_ce_stats / _from_sums, ldiff_op_bucket_pack, ldiff_op_sumsq (data-parallel tissue training); 0.2.0.9: + ldiff_op_case_bbox / _stats / _counts / _apply / _rank_to_coord (plan and preprocess of the tissue head's training cases on the device: non-zero box, crop statistics, label counts per row, normalise into the arena, rank -> pixel); 0.2.0.8: + ldiff_op_seg_intensity_lr (the intensity chain with nnU-Net's low-resolution simulation between contrast and the gammas), ldiff_op_spline_prefilter (cubic B-spline prefilter on the device, one workgroup per plane); 0.2.0.7: + ldiff_op_conv_wgrad (direct MFMA weight gradient of the narrow convs over the pixel index, no im2col), ldiff_op_colsum_slabs (slab-reduced bias gradient), both with fixed-order partials; 0.2.0.6: + ldiff_op_seg_sample (patches, labels and deep-supervision targets of a training batch from cases resident on the device), ldiff_op_seg_intensity (nnU-Net's intensity augmentations, one workgroup per plane); 0.2.0.5: + ldiff_unet_set_plan_batch / ldiff_vae_set_plan_batch / ldiff_controlnet_set_plan_batch (batch-invariant mode: every launch planned for a nominal batch), ldiff_op_conv_pb, ldiff_op_attention_pb, ldiff_op_gn_stats_pb; 0.2.0.4: + ldiff_op_in_train_fwd / _bwd (InstanceNorm + LeakyReLU with saved statistics), ldiff_op_dice_ce (nnU-Net deep-supervision loss of one scale, value and gradient), ldiff_op_sgd_nesterov_multi; 0.2.0.3: + ldiff_confusion (per-image confusion matrices of masks or logits against labels, accumulated on the device), ldiff_seg_metrics (host: Dice / IoU / pixel accuracy / frequency-weighted IoU from one matrix); 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
+#define LDIFF_VERSION 215 /* 0.2.1.4: + ldiff_op_keep_largest_component (+ _ws_bytes) and ldiff_op_cc_label: 8-connected components of label maps and nnU-Net's largest-component postprocessing on the device.  0.2.1.3: + ldiff_op_dice_ce_ignore / _ignore_stats / _ignore_from_sums (+ _ignore_ws_bytes, _ignore_nacc): the tissue head's loss with nnU-Net's ignore label; + ldiff_op_case_counts_classes and the selectors -1 - m (`label < m`) of ldiff_op_case_rank_to_coord, for the annotated-pixel locations of a partly annotated case.  0.2.1.2: + ldiff_op_label_table_u8 / ldiff_op_gather_labels / ldiff_op_warmup_labels (+ _supported) / ldiff_op_warmup_images (the warm-up trainer's dataset resident on the device: label bytes through a grey-level table, a batch of labels and masks gathered by index, and the 64x64 warm-up batch -- labels by torch's bilinear rule in integers, images through the normalisation table and the antialiased triangle weights in one pass over the stored bytes); 0.2.1.1: + ldiff_op_resize_u8 / ldiff_op_resize_u8_ws_bytes (the device image front end: PIL.Image.resize(size, BILINEAR) of 8-bit interleaved images bit for bit from host-made coefficient tables, optionally through a float [3][256] table into the sampler's NCHW input; LDIFF_RESIZE_MAX_TAPS); 0.2.1.0: + ldiff_op_window_gather / _accumulate_batch / _finish (the tissue head's sliding window in batches: tiles x mirror variants gathered, un-flipped, averaged and Gaussian-accumulated per chunk, then divide + inf flag + arg-max + un-crop in one launch; ldiff_window_tiles by value), after ldiff_op_dice_ce_stats / _from_sums, ldiff_op_bucket_pack, ldiff_op_sumsq (data-parallel tissue training); 0.2.0.9: + ldiff_op_case_bbox / _stats / _counts / _apply / _rank_to_coord (plan and preprocess of the tissue head's training cases on the device: non-zero box, crop statistics, label counts per row, normalise into the arena, rank -> pixel); 0.2.0.8: + ldiff_op_seg_intensity_lr (the intensity chain with nnU-Net's low-resolution simulation between contrast and the gammas), ldiff_op_spline_prefilter (cubic B-spline prefilter on the device, one workgroup per plane); 0.2.0.7: + ldiff_op_conv_wgrad (direct MFMA weight gradient of the narrow convs over the pixel index, no im2col), ldiff_op_colsum_slabs (slab-reduced bias gradient), both with fixed-order partials; 0.2.0.6: + ldiff_op_seg_sample (patches, labels and deep-supervision targets of a training batch from cases resident on the device), ldiff_op_seg_intensity (nnU-Net's intensity augmentations, one workgroup per plane); 0.2.0.5: + ldiff_unet_set_plan_batch / ldiff_vae_set_plan_batch / ldiff_controlnet_set_plan_batch (batch-invariant mode: every launch planned for a nominal batch), ldiff_op_conv_pb, ldiff_op_attention_pb, ldiff_op_gn_stats_pb; 0.2.0.4: + ldiff_op_in_train_fwd / _bwd (InstanceNorm + LeakyReLU with saved statistics), ldiff_op_dice_ce (nnU-Net deep-supervision loss of one scale, value and gradient), ldiff_op_sgd_nesterov_multi; 0.2.0.3: + ldiff_confusion (per-image confusion matrices of masks or logits against labels, accumulated on the device), ldiff_seg_metrics (host: Dice / IoU / pixel accuracy / frequency-weighted IoU from one matrix); 0.2.0.2: + ldiff_textenc_* (the CLIP text encoder of the prompt path, with the optional prompt projection), ldiff_op_text_attention (causal attention over a short sequence), ldiff_conv_args.act_out (quick_gelu / gelu behind a linear layer's sum); 0.2.0.1: + ldiff_conv_args.fold_gn (GroupNorm folded into per-image 1x1 weights, as the executors run it), profiler names gn_stats<1> / gn_stats<2> (one-launch / partial + finalize statistics) and fold_gn_weights; 0.2.0.0: + ldiff_resnet_* (the cell head's ResNet152 instance classifier), ldiff_op_maxpool3x3s2 / ldiff_op_crop_resize_norm / ldiff_op_cls_head, ldiff_conv_args.relu_out / cls_conv (the classifier's conv family, ks 1 | 3 | 7); 0.1.9.0: + ldiff_segnet_* (the nnU-Net tissue head), ldiff_conv_args.lrelu_in / tconv / seg_conv (LeakyReLU prologue, 2x2 transposed conv kernel, narrow 3x3 kernel); 0.1.8.0: + ldiff_controlnet_* (the ControlNet of the multimodal sampler), ldiff_unet_attach_controlnet, ldiff_conv_args.silu_out / cond_conv (conditioning-embedding conv kernel); 0.1.7.0: + ldiff_vae_set_range_shift, ldiff_conv_args.out_shift; 0.1.6.0: + non-finite detection (LDIFF_ERR_NONFINITE, ldiff_*_check_finite), ldiff_conv_args.splitk (split launches emit statistics); 0.1.5.2: + ldiff_conv_args.n_real (tap-folded conv_out kernel), c3d_ups (upsampling convs on the dataflow kernel); 0.1.5.1: dataflow GEMM (gemm_df), shortcut conv folded into the dataflow conv3x3 (sc_*) */
 #define LDIFF_MAX_BLOCKS 8
 #define LDIFF_RESIZE_MAX_TAPS 128 /* longest coefficient row ldiff_op_resize_u8 takes: reductions up to 63x (a 16x reduction has 33 taps) */
 
@@ -806,6 +806,26 @@ int ldiff_op_region_counts(const void* logits, int ld, int n_regions, const void
  * the logit: the caller passes the step of the dtype the reference thresholds in (nnunet.REGION_THRESHOLD_F32 / _F16). */
 int ldiff_op_region_mask_u8(const void* logits, int logits_f32, int n_regions, int H, int W, const int* regions_class_order, float threshold, void* mask, int mask_H,
                             int mask_W, int mask_y0, int mask_x0, void* stream);
+/* Postprocessing (postprocessing/remove_connected_components.py:22-34, remove_all_but_largest_component_from_segmentation) on N uint8 label maps [N, H, W],
+ * each image on its own.  table = 256 device bytes: byte v is 1 when the value v belongs to the label, list of labels or region being filtered; the binary
+ * mask is table[seg] and is never stored.  Components under 8-connectivity (full connectivity: skimage.measure.label(mask, connectivity=None)); a component's
+ * label is the smallest linear pixel index y W + x in it, so nothing depends on scheduling.  The largest component is kept; among components of equal
+ * largest size the one whose first pixel in raster order comes first, that is the smallest label (UNPINNED: the reference calls acvl_utils, which the
+ * test-suite cannot import; the rule lives in cc_winner_key of kernels_segpost.hip).  An empty mask changes nothing.
+ *   ldiff_op_keep_largest_component: seg_out = seg_in with every member pixel outside the kept component set to background_label (0 .. 255), every other
+ *     pixel copied.  seg_in is not modified; a seg_out that overlaps seg_in is refused.
+ *   ldiff_op_cc_label: labels int32 [N, H, W] = the component's label + 1, 0 outside the mask; sizes int32 [N, H, W] = the component's pixel count at its
+ *     label's pixel, 0 everywhere else.
+ * Seven launches: union-find per LDIFF_CC_TILE_H x LDIFF_CC_TILE_W tile in LDS, a merge of the tile seams (agent-scope atomic loads and atomicMin only, no
+ * waiting between workgroups), flatten, sizes by integer atomic adds, the per-image winner, the result.  Integer atomics only: bit-reproducible.
+ * Limits, anything else LDIFF_ERR_INVALID naming the argument: 1 <= N, 1 <= H, 1 <= W, H * W <= 2^30, N * ceil(H W / 256) < 2^31.
+ * ws: ldiff_op_keep_largest_component_ws_bytes(N, H, W) bytes (both entries; 8 bytes per pixel + 8 per image; 0 for a shape that is not accepted), 8-byte aligned. */
+#define LDIFF_CC_TILE_H 32
+#define LDIFF_CC_TILE_W 32
+int64_t ldiff_op_keep_largest_component_ws_bytes(int N, int H, int W);
+int ldiff_op_keep_largest_component(const void* seg_in, void* seg_out, int N, int H, int W, const void* table, int background_label, void* ws, int64_t ws_bytes,
+                                    void* stream);
+int ldiff_op_cc_label(const void* seg, int N, int H, int W, const void* table, void* labels_i32, void* sizes_i32, void* ws, int64_t ws_bytes, void* stream);
 /* The gradient bucket of a data-parallel step.  ldiff_op_bucket_pack: bucket[offsets[t] + i] = grads[t][i] for every tensor in one launch; grads = device
  * table of const float*, offsets = device int64 [T + 1] (prefix sums of the element counts), chunks as ldiff_op_adamw_multi's.
  * ldiff_op_sumsq: out_f32[0] = sqrt(sum x^2) of n f32 elements (4-byte aligned) through one fp32 partial per 16384 elements (at most 27 dependent roundings

@@ -68,6 +68,7 @@ class SegChan(C.Structure):     # ldiff_seg_chan
 
 
 WINDOW_MAX_TILES = 64           # LDIFF_WINDOW_MAX_TILES
+CC_TILE_H, CC_TILE_W = 32, 32   # LDIFF_CC_TILE_H / _W: the tile of the connected-component kernels (tests straddle it)
 
 
 class WindowTiles(C.Structure):  # ldiff_window_tiles
@@ -237,6 +238,9 @@ SIGNATURES = {
     "ldiff_op_region_counts_ws_bytes": (I64, [I, I64, I]),
     "ldiff_op_region_counts": (I, [P, I, I, P, P, I, I, I64, F, P, P, I64, P]),
     "ldiff_op_region_mask_u8": (I, [P, I, I, I, I, P, F, P, I, I, I, I, P]),
+    "ldiff_op_keep_largest_component_ws_bytes": (I64, [I, I, I]),
+    "ldiff_op_keep_largest_component": (I, [P, P, I, I, I, P, I, P, I64, P]),
+    "ldiff_op_cc_label": (I, [P, I, I, I, P, P, P, P, I64, P]),
     "ldiff_op_bucket_pack": (I, [P, P, P, I64, P, P]),
     "ldiff_op_sumsq_ws_bytes": (I64, [I64]),
     "ldiff_op_sumsq": (I, [P, I64, P, P, I64, P]),

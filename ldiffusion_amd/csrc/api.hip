@@ -1285,6 +1285,19 @@ int ldiff_op_region_mask_u8(const void* logits, int logits_f32, int n_regions, i
   launch_region_mask_u8(logits, logits_f32, n_regions, H, W, regions_class_order, threshold, (uint8_t*)mask, mask_H, mask_W, mask_y0, mask_x0, (hipStream_t)stream);
   API_END
 }
+// ---- connected components and the largest-component filter (kernels_segpost.hip) ----
+int64_t ldiff_op_keep_largest_component_ws_bytes(int N, int H, int W) { return keep_largest_component_ws_bytes(N, H, W); }
+int ldiff_op_keep_largest_component(const void* seg_in, void* seg_out, int N, int H, int W, const void* table, int background_label, void* ws, int64_t ws_bytes,
+                                    void* stream) {
+  API_BEGIN
+  launch_keep_largest_component((const uint8_t*)seg_in, (uint8_t*)seg_out, N, H, W, (const uint8_t*)table, background_label, ws, ws_bytes, (hipStream_t)stream);
+  API_END
+}
+int ldiff_op_cc_label(const void* seg, int N, int H, int W, const void* table, void* labels_i32, void* sizes_i32, void* ws, int64_t ws_bytes, void* stream) {
+  API_BEGIN
+  launch_cc_label((const uint8_t*)seg, N, H, W, (const uint8_t*)table, (int*)labels_i32, (int*)sizes_i32, ws, ws_bytes, (hipStream_t)stream);
+  API_END
+}
 int ldiff_op_bucket_pack(const void* grads, const void* offsets, const void* chunks, int64_t nchunks, void* bucket, void* stream) {
   API_BEGIN
   LDIFF_CHECK(nchunks >= 0 && (nchunks == 0 || (grads && offsets && chunks && bucket)), LDIFF_ERR_INVALID, "op_bucket_pack: bad arguments");

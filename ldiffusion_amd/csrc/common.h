@@ -415,6 +415,11 @@ void launch_region_counts(const f16* logits, int ld, int n_regions, const unsign
                           long long* counts, void* ws, long long ws_bytes, hipStream_t s);
 void launch_region_mask_u8(const void* logits, int is_f32, int R, int H, int W, const int* order, float threshold, uint8_t* mask, int mask_H, int mask_W, int mask_y0,
                            int mask_x0, hipStream_t s);
+// 8-connected components of label maps and the largest-component filter of nnU-Net's postprocessing (kernels_segpost.hip)
+long long keep_largest_component_ws_bytes(int N, int H, int W);   // 0: a shape the kernels do not take
+void launch_keep_largest_component(const uint8_t* seg_in, uint8_t* seg_out, int N, int H, int W, const uint8_t* table, int background_label, void* ws,
+                                   long long ws_bytes, hipStream_t s);
+void launch_cc_label(const uint8_t* seg, int N, int H, int W, const uint8_t* table, int* labels, int* sizes, void* ws, long long ws_bytes, hipStream_t s);
 // every gradient into one flat buffer in one launch, and the buffer's L2 norm (fixed-order reduction)
 void launch_bucket_pack(const float* const* grads, const long long* offsets, const AdamChunk* chunks, long long nchunks, float* bucket, hipStream_t s);
 long long sumsq_ws_bytes(long long n);

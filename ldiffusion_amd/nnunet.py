@@ -361,13 +361,20 @@ class TrainedModel:
 
     @torch.no_grad()
     def predict_mask(self, data: torch.Tensor, tile_size=None, tile_step_size: float = 0.5, mirror_axes="checkpoint", network=None,
-                     batch_tiles=None) -> torch.Tensor:
+                     batch_tiles=None, postprocess=None) -> torch.Tensor:
         """[C, H, W] in 0..255 scale on the device -> uint8 mask [H, W]: crop to non-zero, normalise, nnU-Net's sliding window, arg-max, un-crop.
         The tile is the plans' patch size (or `tile_size`), NOT clamped to the image: an image smaller than the patch is zero padded to it
         (predict_from_raw_data.py:614, tiling.pad_to_tile), as the reference does -- InstanceNorm statistics and Gaussian weights are then those of a full patch.
         `network` replaces the head (tests: a float64 restatement under the same preprocessing).
         batch_tiles: None = one network call per tile and mirror variant; an integer = `tiling.predict_sliding_window_batched`: that many tiles times the mirror
-        variants per network call, the mask written at the crop box's place by the finish kernel.  The same mask bit for bit (the head is batch invariant)."""
+        variants per network call, the mask written at the crop box's place by the finish kernel.  The same mask bit for bit (the head is batch invariant).
+        postprocess: None = the mask as predicted; `(fns, kwargs)` or the path of a `postprocessing.json` (`nnunet_post.determine_postprocessing*`) = nnU-Net's
+        fitted postprocessing applied to the finished, un-cropped mask on the device (`nnunet_post.apply_postprocessing`)."""
+        if postprocess is not None:
+            from . import nnunet_post
+            fns, kwargs = nnunet_post.load_postprocessing(postprocess) if isinstance(postprocess, (str, os.PathLike)) else postprocess
+            mask = self.predict_mask(data, tile_size, tile_step_size, mirror_axes, network, batch_tiles)
+            return nnunet_post.apply_postprocessing(mask.contiguous(), fns, kwargs)
         from . import tiling
         from .segmentor import argmax_mask
         x, box = preprocess(data, self.normalization_schemes)

@@ -221,7 +221,8 @@ class Segmentor:
 
     def train_tissue_model_nnUNetv2(self, epochs, ldiffusion_weight, diffusion_path, train_images=None, train_labels=None, test_images=None, test_labels=None,
                                     num_classes=None, *, iterations_per_epoch=250, val_iterations=50, num_foreground_voxels=None, wgrad_route=None, batch_images=None, io_workers=4,
-                                    ignore_pixel=None, regions=None, regions_class_order=None, region_loss="focal"):
+                                    ignore_pixel=None, regions=None, regions_class_order=None, region_loss="focal", validate=False, postprocessing=False,
+                                    validation_checkpoint="checkpoint_final.pth"):
         """segmentor.py:163-241: the tissue head's training stage, from image lists to a trained-model folder.
         Dataset (:167-205): `load_ldiffusion`, the cached text embeddings of "A pathological slide", the text-alignment wrapper, and
         `utils.create_nnunet_dataset` under nnUNet_raw (the one-pass diffusion of every image when all share one size, else copies).
@@ -244,6 +245,11 @@ class Segmentor:
         writes the dataset, the fingerprint, plans, split and the model folder; `(new_num, dataset_name)` go out by `broadcast_object_list` and a
         barrier; every rank then reads the PNGs and JSONs and builds both stores on its own device; its loaders take its entry of
         `nnunet_train.rank_batch_sizes` (batch and oversample) and the seeds 2 rank / 2 rank + 1; the trainer runs with ddp on.
+        `validate` (off: `fold_0/` holds the two checkpoints and nothing else): nnUNetTrainer.perform_actual_validation after the last epoch --
+        `nnunet_post.validate_fold` predicts fold 0's validation cases in full with `validation_checkpoint`, writes `fold_0/validation/<key>.png` and
+        `summary.json`; the summary is kept as `self.validation_summary`.  `postprocessing` (implies `validate`): nnU-Net's largest-component
+        postprocessing fitted on those predictions against labelsTr (`nnunet_post.determine_postprocessing_folder`): `fold_0/validation/postprocessing.json`
+        and `fold_0/validation/postprocessed/`, what `inference_tissue_model_nnUNetv2(postprocess=True)` reads.  Rank 0 does both; the others wait.
         Returns the model folder -- what `inference_tissue_model_nnUNetv2(segmentor_weight=...)` takes -- on every rank."""
         import json
         from PIL import Image
@@ -347,6 +353,15 @@ class Segmentor:
             nnunet.write_trained_model_folder(model_dir, plans, dataset_json)
         self.training_log = trainer.run_training(loaders[0], loaders[1], os.path.join(model_dir, "fold_0"), iterations_per_epoch=iterations_per_epoch,
                                                  val_iterations=val_iterations)
+        if validate or postprocessing:
+            from . import nnunet_post
+            self.validation_summary = nnunet_post.validate_fold(model_dir, cases, splits[0]["val"], checkpoint_name=validation_checkpoint, io_workers=io_workers)
+            if postprocessing:
+                if rank == 0:
+                    nnunet_post.determine_postprocessing_folder(os.path.join(model_dir, "fold_0", "validation"), os.path.join(raw_dir, "labelsTr"), model_dir,
+                                                                device=self.device, io_workers=io_workers)
+                if world > 1:
+                    dist.barrier()
         return model_dir
 
     def train_cell_model(self, epochs, ldiffusion_weight, diffusion_path, *, cell_weights, instances=None, fit_classifier=True, cache_features=True, lr=1e-4,
@@ -576,7 +591,7 @@ class Segmentor:
 
     @torch.no_grad()
     def _tissue_folder_batched(self, head, image_path, output_path, diffusion_path, ldiffusion_weight, text_embeddings, tile_size, tile_step_size, mirror_axes, batch_tiles,
-                               batch_images):
+                               batch_images, postprocess=None):
         """Folder mode of `inference_tissue_model_nnUNetv2` with `batch_images`: one pipeline for the folder, the sampler in batches, the head per image."""
         from PIL import Image
         from . import imgio
@@ -586,7 +601,7 @@ class Segmentor:
         axes = "checkpoint" if mirror_axes is None else mirror_axes
 
         def head_mask(name, data):   # data [3, H, W] float on the device, what the PNG the reference writes would hold
-            mask = head.predict_mask(data, tile_size, tile_step_size, axes, batch_tiles=batch_tiles)
+            mask = head.predict_mask(data, tile_size, tile_step_size, axes, batch_tiles=batch_tiles, postprocess=postprocess)
             head.network.check_finite()
             Image.fromarray(mask.cpu().numpy()).save(os.path.join(output_path, os.path.splitext(name)[0] + ".png"))
 
@@ -626,7 +641,7 @@ class Segmentor:
     @torch.no_grad()
     def inference_tissue_model_nnUNetv2(self, image_path, diffusion_path, ldiffusion_weight, segmentor_weight, output_path=None,
                                         predictor=None, text_embeddings=None, tile_size=None, tile_step_size=0.5,
-                                        mirror_axes=None, num_heads=None, batch_tiles=None, batch_images=None):
+                                        mirror_axes=None, num_heads=None, batch_tiles=None, batch_images=None, postprocess=False):
         """segmentor.py:388-488.  The tissue head is either
         * built from `segmentor_weight`, a trained-model folder as the reference's nnUNetPredictor reads it (dataset.json, plans.json,
           fold_0/checkpoint_best.pth; :463-468), when `predictor` is None: nnU-Net v2's 2-D PlainConvUNet on the HIP library (`nnunet.py`; cached on this
@@ -648,9 +663,20 @@ class Segmentor:
         * batch_images (folder mode of the library's head; None = one call per file, as above): the square images of the folder go through the sampler in
           batches of up to `batch_images`, grouped by source size in name order, behind `imgio.resize_normalize`, under `set_plan_batch(batch_images)` (the
           previous plan batch comes back afterwards); each decoded image then goes to the head as above and `batch_tiles` is unaffected; non-square images
-          skip the diffusion as above.  The mask files are those of the per-image path under the same plan batch."""
+          skip the diffusion as above.  The mask files are those of the per-image path under the same plan batch.
+        * postprocess (False: the masks as predicted): True = nnU-Net's fitted postprocessing, read from `<segmentor_weight>/fold_0/validation/postprocessing.json`
+          (what `train_tissue_model_nnUNetv2(postprocessing=True)` writes; a missing file raises FileNotFoundError naming the path), or the path of such a
+          file, or `(fns, kwargs)`; applied to every finished mask on the device (`nnunet_post.apply_postprocessing`), single image and folder alike."""
         from PIL import Image
         from . import tiling
+        post = None   # (fns, kwargs), read once
+        if postprocess is not None and postprocess is not False:
+            from . import nnunet_post
+            if postprocess is True:
+                postprocess = os.path.join(os.fspath(segmentor_weight) if isinstance(segmentor_weight, (str, os.PathLike)) else str(segmentor_weight), "fold_0",
+                                           "validation", "postprocessing.json")
+            post = nnunet_post.load_postprocessing(postprocess) if isinstance(postprocess, (str, os.PathLike)) else (list(postprocess[0]), list(postprocess[1]))
+        keep = {} if post is None else {"postprocess": post}   # nothing new goes downstream without the keyword
         head = None
         if predictor is None:
             if not (isinstance(segmentor_weight, (str, os.PathLike)) and os.path.isfile(os.path.join(segmentor_weight, "plans.json"))):
@@ -663,12 +689,12 @@ class Segmentor:
             os.makedirs(output_path, exist_ok=True)
             if batch_images is not None:
                 self._tissue_folder_batched(head, image_path, output_path, diffusion_path, ldiffusion_weight, text_embeddings, tile_size, tile_step_size, mirror_axes,
-                                            batch_tiles, batch_images)
+                                            batch_tiles, batch_images, **keep)
                 return None, None
             for name in sorted(os.listdir(image_path)):
                 if name.lower().endswith((".png", ".jpg", ".jpeg", ".tif", ".tiff", ".bmp")):
                     _, m = self.inference_tissue_model_nnUNetv2(os.path.join(image_path, name), diffusion_path, ldiffusion_weight, segmentor_weight,
-                                                                None, None, text_embeddings, tile_size, tile_step_size, mirror_axes, num_heads, batch_tiles)
+                                                                None, None, text_embeddings, tile_size, tile_step_size, mirror_axes, num_heads, batch_tiles, **keep)
                     Image.fromarray(m).save(os.path.join(output_path, os.path.splitext(name)[0] + ".png"))
             return None, None   # batch mode returns no single mask (segmentor.py:421)
         if head is None:
@@ -689,7 +715,7 @@ class Segmentor:
             for name in sorted(os.listdir(image_path)):
                 if name.lower().endswith((".png", ".jpg", ".jpeg", ".tif", ".tiff", ".bmp")):
                     _, m = self.inference_tissue_model_nnUNetv2(os.path.join(image_path, name), diffusion_path, ldiffusion_weight, segmentor_weight,
-                                                                None, predictor, text_embeddings, tile_size, tile_step_size, mirror_axes, num_heads, batch_tiles)
+                                                                None, predictor, text_embeddings, tile_size, tile_step_size, mirror_axes, num_heads, batch_tiles, **keep)
                     Image.fromarray(m).save(os.path.join(output_path, os.path.splitext(name)[0] + ".png"))
             return None, None   # batch mode returns no single mask (segmentor.py:421)
         pipeline, unet, _ = self.load_ldiffusion(ldiffusion_weight, diffusion_path)
@@ -709,14 +735,16 @@ class Segmentor:
             decoded = image
         data = rgb[0].permute(2, 0, 1).float()                                                # what the PNG the reference writes would hold
         if head is not None:
-            mask = head.predict_mask(data, tile_size, tile_step_size, "checkpoint" if mirror_axes is None else mirror_axes, batch_tiles=batch_tiles)
+            mask = head.predict_mask(data, tile_size, tile_step_size, "checkpoint" if mirror_axes is None else mirror_axes, batch_tiles=batch_tiles, **keep)
             head.network.check_finite()   # an fp16 overflow inside the head raises instead of yielding a plausible-looking mask
             return decoded, mask.cpu().numpy()
         heads = int(num_heads if num_heads is not None else self.num_classes)
         th, tw = min(tile_size[0], data.shape[1]), min(tile_size[1], data.shape[2])
         if batch_tiles is not None:
             mask = tiling.predict_sliding_window_batched(data, predictor, heads, (th, tw), tile_step_size, True, mirror_axes, batch_tiles=int(batch_tiles), return_mask=True)
-            return decoded, mask.cpu().numpy()
-        logits = tiling.predict_sliding_window_return_logits(data, predictor, heads, (th, tw), tile_step_size, True, mirror_axes)
-        mask = argmax_mask(logits[None].float())[0].cpu().numpy()
-        return decoded, mask
+        else:
+            logits = tiling.predict_sliding_window_return_logits(data, predictor, heads, (th, tw), tile_step_size, True, mirror_axes)
+            mask = argmax_mask(logits[None].float())[0]
+        if post is not None:
+            mask = nnunet_post.apply_postprocessing(mask.contiguous(), *post)
+        return decoded, mask.cpu().numpy()
