@@ -976,7 +976,17 @@ int ldiff_op_case_rank_to_coord(const void* label_u8, int H, int W, int64_t labe
  *   float32 division and one rounding to the accumulators' type T (acc_f16 != 0: float16).  *inf_flag (device int32, zeroed by the caller) is set to 1
  *   when any l_c is +-inf.  logits_or_null [heads, h, w] of type T receives l; mask_or_null uint8 [mask_H, mask_W] receives, at (mask_y0 + y, mask_x0 + x),
  *   the arg-max by ldiff_argmax_u8's rule bit for bit (first maximal class; any NaN or +inf logit: class 0).  heads <= 32.
- * All three: enqueued on `stream`, no synchronisation, no allocation, no workspace. */
+ * ldiff_op_window_finish_ensemble: the finish of n_folds heads of one image in ONE launch, where nnUNetPredictor sums the folds' logits and divides by
+ *   their number (predict_from_raw_data.py:459-494).  acc is a HOST array of n_folds device pointers, each [heads, Hp, Wp] of type T; the table travels by
+ *   value in the kernel's arguments.  cnt_or_null [Hp, Wp] is the count plane all folds share; NULL: the inputs are logits already (the per-tile path).
+ *   Per pixel and head, every operation rounded on its own, no fused multiply-add:
+ *     l_k = cnt ? rn_T(acc_k / cnt) : acc_k;  *inf_flag = 1 when any l_k is +-inf (the reference raises per fold, before the sum);
+ *     s = l_0;  s = rn_T(s + l_k) for k = 1 .. n_folds - 1 in table order;  s = rn_T(s / (float)n_folds) when n_folds > 1, the float32 division correctly
+ *     rounded.  An overflow of the sum itself is not flagged (the reference does not look there); the arg-max rule sends such a pixel to class 0.
+ *   logits_or_null and mask_or_null receive s and its arg-max as ldiff_op_window_finish writes them.  With n_folds == 1 and cnt given the outputs are
+ *   ldiff_op_window_finish's bit for bit.  n_folds outside 1 .. LDIFF_ENSEMBLE_MAX_FOLDS, heads outside 1 .. 32, a box or mask box that leaves its extent
+ *   or a null table entry are LDIFF_ERR_INVALID and nothing is enqueued.
+ * All four: enqueued on `stream`, no synchronisation, no allocation, no workspace. */
 #define LDIFF_WINDOW_MAX_TILES 64
 typedef struct ldiff_window_tiles {
   int32_t n_tiles, n_valid, n_variants, reserved;
@@ -989,6 +999,10 @@ int ldiff_op_window_accumulate_batch(void* acc, void* cnt, const void* pred, con
                                      const ldiff_window_tiles* tiles, int dtypes, void* stream);
 int ldiff_op_window_finish(const void* acc, const void* cnt, int heads, int Hp, int Wp, int y0, int x0, int h, int w, int acc_f16, void* logits_or_null,
                            void* mask_or_null, int mask_H, int mask_W, int mask_y0, int mask_x0, int32_t* inf_flag, void* stream);
+#define LDIFF_ENSEMBLE_MAX_FOLDS 8
+int ldiff_op_window_finish_ensemble(const void* const* acc, int n_folds, const void* cnt_or_null, int heads, int Hp, int Wp, int y0, int x0, int h, int w,
+                                    int acc_f16, void* logits_or_null, void* mask_or_null, int mask_H, int mask_W, int mask_y0, int mask_x0, int32_t* inf_flag,
+                                    void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Live measurement for bench.py's roofline line: when enabled, every conv/linear, attention and

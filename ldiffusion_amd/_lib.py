@@ -267,6 +267,7 @@ SIGNATURES = {
     "ldiff_op_window_gather": (I, [P, I, I, I, I64, I64, I, I, I, I, C.POINTER(WindowTiles), I, I, P, P]),
     "ldiff_op_window_accumulate_batch": (I, [P, P, P, P, I, I, I, I, I, C.POINTER(WindowTiles), I, P]),
     "ldiff_op_window_finish": (I, [P, P, I, I, I, I, I, I, I, I, P, P, I, I, I, I, P, P]),
+    "ldiff_op_window_finish_ensemble": (I, [C.POINTER(P), I, P, I, I, I, I, I, I, I, I, P, P, I, I, I, I, P, P]),
     "ldiff_stream_create_cu_share": (I, [I, I, P]),
     "ldiff_stream_destroy": (I, [P]),
     "ldiff_vae_set_side_cu_share": (I, [P, I, I]),

@@ -548,6 +548,15 @@ int ldiff_op_window_finish(const void* acc, const void* cnt, int heads, int Hp, 
                        (hipStream_t)stream);
   API_END
 }
+int ldiff_op_window_finish_ensemble(const void* const* acc, int n_folds, const void* cnt_or_null, int heads, int Hp, int Wp, int y0, int x0, int h, int w,
+                                    int acc_f16, void* logits_or_null, void* mask_or_null, int mask_H, int mask_W, int mask_y0, int mask_x0, int32_t* inf_flag,
+                                    void* stream) {
+  API_BEGIN
+  LDIFF_CHECK(acc && inf_flag, LDIFF_ERR_INVALID, "window_finish_ensemble: null argument");
+  launch_window_finish_ensemble(acc, n_folds, cnt_or_null, heads, Hp, Wp, y0, x0, h, w, acc_f16, logits_or_null, (uint8_t*)mask_or_null, mask_H, mask_W, mask_y0,
+                                mask_x0, inf_flag, (hipStream_t)stream);
+  API_END
+}
 int ldiff_luma_float(const void* rgb_nchw, void* gray, int B, int H, int W, void* stream) {
   API_BEGIN
   LDIFF_CHECK(rgb_nchw && gray, LDIFF_ERR_INVALID, "luma_float: null argument");

@@ -353,6 +353,8 @@ void launch_window_accumulate_batch(void* acc, void* cnt, const void* pred, cons
                                     int dtypes, hipStream_t s);
 void launch_window_finish(const void* acc, const void* cnt, int heads, int Hp, int Wp, int y0, int x0, int h, int w, int acc_f16, void* logits, uint8_t* mask, int mask_H,
                           int mask_W, int mask_y0, int mask_x0, int32_t* inf_flag, hipStream_t s);
+void launch_window_finish_ensemble(const void* const* acc, int n_folds, const void* cnt, int heads, int Hp, int Wp, int y0, int x0, int h, int w, int acc_f16, void* logits,
+                                   uint8_t* mask, int mask_H, int mask_W, int mask_y0, int mask_x0, int32_t* inf_flag, hipStream_t s);
 
 // ---- backward-pass primitives of the fine-tuning step (kernels_bwd.hip) -------------------------------------
 void launch_im2col_t(const f16* x, f16* out, int B, int H, int W, int C, int ks, int stride, int pad, int ups, int Ho, int Wo, int Mpad, hipStream_t s);

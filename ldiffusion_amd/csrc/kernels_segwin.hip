@@ -3,7 +3,7 @@
 // :563-570 accumulation, :572-589 division, inf check and revert of the padding), in three bandwidth-bound element kernels per image:
 //   gather      a chunk of tiles x mirror variants out of the (virtually zero padded) image -> the network's NCHW float32 batch
 //   accumulate  un-flip, average the variants, weight and add a whole chunk; one thread owns its pixels and walks the chunk's tiles in slicer order
-//   finish      logits = acc / cnt, inf flag, arg-max, written at the crop box's place of the full-size mask
+//   finish      logits = acc / cnt, inf flag, arg-max, written at the crop box's place of the full-size mask; for several folds, their mean in between
 // The chunk (tile origins, variant masks) is a kernel argument: the indices below read the kernarg segment, nothing is copied to the device.
 // Every float operation is rounded on its own, in the order the tensor formulation rounds (see the header): contraction is off for the whole file.
 #include <type_traits>
@@ -152,6 +152,29 @@ __global__ __launch_bounds__(256) void window_accumulate_batch_kernel(T* __restr
 // ---- finish ---------------------------------------------------------------------------------------------------------------------------------
 // One thread per run of VEC pixels of the h x w box at (y0, x0) of the padded extent.  The arg-max is argmax_u8_kernel's (kernels_elem.hip): the
 // first maximal class, and class 0 for a pixel with any NaN or +inf logit.
+// Both finish kernels run these two steps; they are macros, so that each kernel compiles exactly the statements it would hold written out.
+// One class c of pixel j into the run's arg-max: the first maximal class wins, and bad[j] remembers a NaN or +inf logit (the pixel is class 0 then).
+#define WINDOW_ARGMAX_TAKE(c, l, j)                                    \
+  {                                                                    \
+    const bool nan_or_inf = l[j] != l[j] || l[j] == INFINITY;          \
+    if (c == 0) { best[j] = l[j]; bi[j] = 0; bad[j] = nan_or_inf; }    \
+    else {                                                             \
+      bad[j] |= nan_or_inf;                                            \
+      if (l[j] > best[j]) { best[j] = l[j]; bi[j] = c; }               \
+    }                                                                  \
+  }
+// The run's classes as bytes at pixel (y, x) of the mask box; VEC == 4 is one aligned 4-byte store (the launchers check the alignment).
+#define WINDOW_ARGMAX_STORE()                                                                 \
+  if (mask) {                                                                                 \
+    uint8_t* mp = mask + (long long)(mask_y0 + y) * mask_W + mask_x0 + x;                     \
+    if constexpr (VEC == 1) mp[0] = bad[0] ? (uint8_t)0 : (uint8_t)bi[0];                     \
+    else {                                                                                    \
+      unsigned u = 0;                                                                         \
+      _Pragma("unroll") for (int j = 0; j < 4; ++j) u |= (bad[j] ? 0u : (unsigned)bi[j]) << (8 * j); \
+      *reinterpret_cast<unsigned*>(mp) = u;                                                   \
+    }                                                                                         \
+  }
+
 template <typename T, int VEC>
 __global__ __launch_bounds__(256) void window_finish_kernel(const T* __restrict__ acc, const T* __restrict__ cnt, int heads, int Hp, int Wp, int y0, int x0, int h, int w,
                                                             T* __restrict__ logits, uint8_t* __restrict__ mask, int mask_W, int mask_y0, int mask_x0,
@@ -172,26 +195,58 @@ __global__ __launch_bounds__(256) void window_finish_kernel(const T* __restrict_
     for (int j = 0; j < VEC; ++j) {
       l[j] = rnd<T>(div_rn(l[j], n[j]));
       any_inf |= l[j] == INFINITY || l[j] == -INFINITY;
-      const bool nan_or_inf = l[j] != l[j] || l[j] == INFINITY;
-      if (c == 0) { best[j] = l[j]; bi[j] = 0; bad[j] = nan_or_inf; }
-      else {
-        bad[j] |= nan_or_inf;
-        if (l[j] > best[j]) { best[j] = l[j]; bi[j] = c; }
-      }
+      WINDOW_ARGMAX_TAKE(c, l, j)
     }
     if (logits) store_run<T, VEC>(logits + c * out_plane + oo, l);
   }
   if (any_inf) *inf_flag = 1;   // every writer stores the same value
-  if (mask) {
-    uint8_t* mp = mask + (long long)(mask_y0 + y) * mask_W + mask_x0 + x;
-    if constexpr (VEC == 1) mp[0] = bad[0] ? (uint8_t)0 : (uint8_t)bi[0];
-    else {
-      unsigned u = 0;
+  WINDOW_ARGMAX_STORE()
+}
+
+// ---- finish of a fold ensemble --------------------------------------------------------------------------------------------------------------
+// The folds' accumulators (or, without a count plane, their finished logits) of one image: each fold's logits as window_finish_kernel makes them, the
+// inf flag per fold, then the sum in fold order and the division by the fold count, every step rounded to T (predict_from_raw_data.py:459-494:
+// `prediction += logits` and `prediction /= n` on tensors of that type).  The pointer table is a kernel argument, like the chunk of tiles above.
+struct window_fold_table { const void* acc[LDIFF_ENSEMBLE_MAX_FOLDS]; };
+
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void window_finish_ensemble_kernel(window_fold_table t, int n_folds, const T* __restrict__ cnt, int heads, int Hp, int Wp, int y0, int x0,
+                                                                     int h, int w, T* __restrict__ logits, uint8_t* __restrict__ mask, int mask_W, int mask_y0, int mask_x0,
+                                                                     int32_t* __restrict__ inf_flag) {
+  const int rw = w / VEC;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)h * rw) return;
+  const int y = (int)(i / rw), x = (int)(i - (long long)y * rw) * VEC;
+  const long long o = (long long)(y0 + y) * Wp + x0 + x, img_plane = (long long)Hp * Wp, out_plane = (long long)h * w, oo = (long long)y * w + x;
+  const float fK = (float)n_folds;
+  // The arg-max state starts defined, and `bad` is a word: left as an unset bool for class 0 to set, the element path's flag came out of a scalar register
+  // pair that nothing writes (profiles/segwin_ensemble_flag_codegen.txt has the assembly and how to see it again).
+  float n[VEC], best[VEC] = {};
+  int bi[VEC] = {};
+  unsigned bad[VEC] = {};
+  bool any_inf = false;
+  if (cnt) load_run<T, VEC>(cnt + o, n);
+  for (int c = 0; c < heads; ++c) {
+    float s[VEC];
+    for (int k = 0; k < n_folds; ++k) {
+      float l[VEC];
+      load_run<T, VEC>((const T*)t.acc[k] + c * img_plane + o, l);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) u |= (bad[j] ? 0u : (unsigned)bi[j]) << (8 * j);
-      *reinterpret_cast<unsigned*>(mp) = u;
+      for (int j = 0; j < VEC; ++j) {
+        if (cnt) l[j] = rnd<T>(div_rn(l[j], n[j]));
+        any_inf |= l[j] == INFINITY || l[j] == -INFINITY;
+        s[j] = k == 0 ? l[j] : rnd<T>(__fadd_rn(s[j], l[j]));
+      }
     }
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      if (n_folds > 1) s[j] = rnd<T>(div_rn(s[j], fK));
+      WINDOW_ARGMAX_TAKE(c, s, j)
+    }
+    if (logits) store_run<T, VEC>(logits + c * out_plane + oo, s);
   }
+  if (any_inf) *inf_flag = 1;   // every writer stores the same value
+  WINDOW_ARGMAX_STORE()
 }
 
 // what every launch checks of its chunk: the counts, the variant masks and that tiles 0 .. n - 1 lie inside the padded extent
@@ -241,6 +296,20 @@ void finish(const void* acc, const void* cnt, int heads, int Hp, int Wp, int y0,
                        mask, mask_W, mask_y0, mask_x0, inf_flag);
 }
 
+template <typename T>
+void finish_ensemble(const window_fold_table& t, int n_folds, const void* cnt, int heads, int Hp, int Wp, int y0, int x0, int h, int w, void* logits, uint8_t* mask, int mask_W,
+                     int mask_y0, int mask_x0, int32_t* inf_flag, hipStream_t s) {
+  bool vec = w % 4 == 0 && Wp % 4 == 0 && x0 % 4 == 0 && aligned16(cnt) && aligned16(logits) &&
+             (!mask || (mask_W % 4 == 0 && mask_x0 % 4 == 0 && ((size_t)mask & 3) == 0));
+  for (int k = 0; k < n_folds; ++k) vec = vec && aligned16(t.acc[k]);
+  if (vec)
+    hipLaunchKernelGGL((window_finish_ensemble_kernel<T, 4>), dim3(nblocks((long long)h * (w / 4))), dim3(256), 0, s, t, n_folds, (const T*)cnt, heads, Hp, Wp, y0, x0, h, w,
+                       (T*)logits, mask, mask_W, mask_y0, mask_x0, inf_flag);
+  else
+    hipLaunchKernelGGL((window_finish_ensemble_kernel<T, 1>), dim3(nblocks((long long)h * w)), dim3(256), 0, s, t, n_folds, (const T*)cnt, heads, Hp, Wp, y0, x0, h, w,
+                       (T*)logits, mask, mask_W, mask_y0, mask_x0, inf_flag);
+}
+
 }  // namespace
 
 void launch_window_gather(const float* img, int C, int h, int w, long long row_stride, long long plane_stride, int pad_top, int pad_left, int Hp, int Wp,
@@ -286,5 +355,24 @@ void launch_window_finish(const void* acc, const void* cnt, int heads, int Hp, i
               "%s: the box %d x %d at (mask_y0 = %d, mask_x0 = %d) leaves the mask %d x %d", who, h, w, mask_y0, mask_x0, mask_H, mask_W);
   if (acc_f16) finish<f16>(acc, cnt, heads, Hp, Wp, y0, x0, h, w, logits, mask, mask_W, mask_y0, mask_x0, inf_flag, s);
   else finish<float>(acc, cnt, heads, Hp, Wp, y0, x0, h, w, logits, mask, mask_W, mask_y0, mask_x0, inf_flag, s);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_window_finish_ensemble(const void* const* acc, int n_folds, const void* cnt, int heads, int Hp, int Wp, int y0, int x0, int h, int w, int acc_f16, void* logits,
+                                   uint8_t* mask, int mask_H, int mask_W, int mask_y0, int mask_x0, int32_t* inf_flag, hipStream_t s) {
+  const char* who = "window_finish_ensemble";
+  LDIFF_CHECK(n_folds >= 1 && n_folds <= LDIFF_ENSEMBLE_MAX_FOLDS, LDIFF_ERR_INVALID, "%s: n_folds %d out of range [1, %d]", who, n_folds, LDIFF_ENSEMBLE_MAX_FOLDS);
+  LDIFF_CHECK(heads >= 1 && heads <= 32, LDIFF_ERR_INVALID, "%s: heads %d out of range [1, 32]", who, heads);
+  LDIFF_CHECK(h >= 1 && w >= 1 && y0 >= 0 && x0 >= 0 && y0 <= Hp - h && x0 <= Wp - w, LDIFF_ERR_INVALID, "%s: the box %d x %d at (y0 = %d, x0 = %d) leaves the padded extent %d x %d",
+              who, h, w, y0, x0, Hp, Wp);
+  LDIFF_CHECK(!mask || (mask_y0 >= 0 && mask_x0 >= 0 && mask_y0 <= mask_H - h && mask_x0 <= mask_W - w), LDIFF_ERR_INVALID,
+              "%s: the box %d x %d at (mask_y0 = %d, mask_x0 = %d) leaves the mask %d x %d", who, h, w, mask_y0, mask_x0, mask_H, mask_W);
+  window_fold_table t = {};
+  for (int k = 0; k < n_folds; ++k) {
+    LDIFF_CHECK(acc[k], LDIFF_ERR_INVALID, "%s: acc[%d] is null (a table of n_folds = %d device pointers)", who, k, n_folds);
+    t.acc[k] = acc[k];
+  }
+  if (acc_f16) finish_ensemble<f16>(t, n_folds, cnt, heads, Hp, Wp, y0, x0, h, w, logits, mask, mask_W, mask_y0, mask_x0, inf_flag, s);
+  else finish_ensemble<float>(t, n_folds, cnt, heads, Hp, Wp, y0, x0, h, w, logits, mask, mask_W, mask_y0, mask_x0, inf_flag, s);
   HIP_CHECK(hipGetLastError());
 }

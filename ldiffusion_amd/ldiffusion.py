@@ -22,7 +22,8 @@ def parse_args(argv=None):
     """ldiffusion.py:19-29: the reference's eight flags, plus --level, --component and --ldiffusion-weight (the reference hard-codes them in its
     `__main__`, :330-331), --ignore-pixel, the grey level of unlabelled pixels in partly annotated tissue labels (not given: fully annotated), and
     --regions, a JSON file {"regions": {name: [grey levels or class indices]}, "regions_class_order": [...]} for region-based tissue training, and
-    --validate / --postprocessing, the final validation of the tissue fold and the postprocessing fitted on it (`Segmentor.train_tissue_model_nnUNetv2`'s)."""
+    --validate / --postprocessing, the final validation of the tissue fold and the postprocessing fitted on it (`Segmentor.train_tissue_model_nnUNetv2`'s),
+    and --folds, the folds of the five-fold split the tissue stage trains one after the other (not given: fold 0)."""
     parser = argparse.ArgumentParser(description="Diffusion model training parameters")
     parser.add_argument("--local_rank", type=int, default=int(os.environ.get("LOCAL_RANK", -1)))
     parser.add_argument("--diffusion-path", type=str, required=True, help="stable diffusion base model path")
@@ -39,6 +40,7 @@ def parse_args(argv=None):
     parser.add_argument("--regions", type=str, default=None, help="JSON file with `regions` and `regions_class_order` (tissue level): nnU-Net's region labels")
     parser.add_argument("--validate", action="store_true", help="after the tissue training: predict fold 0's validation cases in full, write fold_0/validation/summary.json")
     parser.add_argument("--postprocessing", action="store_true", help="--validate, then fit nnU-Net's largest-component postprocessing: fold_0/validation/postprocessing.json")
+    parser.add_argument("--folds", type=int, nargs="+", default=None, help="folds of the five-fold split to train, e.g. --folds 0 1 2 3 4 (tissue level; default: fold 0)")
     return parser.parse_args(argv)
 
 
@@ -203,7 +205,7 @@ class LDiffusionModel:
 
     def train(self, args, component="all", ldiffusion_weight=None, train_loader=None, val_loader=None, wgrad_route=None, cell_weights=None, instances=None,
               ignore_pixel=None, regions=None, regions_class_order=None, region_loss=None, validate=None, postprocessing=None, validation_checkpoint=None,
-              **_ignored):
+              folds=None, **_ignored):
         """ldiffusion.py:297-315.  The loaders are injected (`train_loader=`, `val_loader=`), or, with none injected and `args` carrying `image_dir` and
         `label_dir`, built as the reference builds them (`self.load_data(args.image_dir, args.label_dir, args.batch_size)`, with `args.image_size` (1024) and
         `args.io_workers` (4) where present): device-resident for the warm-up, plain host loaders when only the segmentor stage runs (it reads their file lists).
@@ -219,7 +221,9 @@ class LDiffusionModel:
         `regions_class_order` (else the file `args.regions` names, where present; None: plain labels): region labels, which the tissue stage trains with one
         sigmoid head per region (`Segmentor.train_tissue_model_nnUNetv2`'s keywords, and so is `region_loss`: None is its default, the focal form), and `validate` /
         `postprocessing` (else `args.validate` / `args.postprocessing` where present and set; None or False: the stage ends at the checkpoints) with
-        `validation_checkpoint`: the final validation of the fold and the largest-component postprocessing fitted on it.  At level "cell" it is
+        `validation_checkpoint`: the final validation of the fold and the largest-component postprocessing fitted on it, and `folds` (else `args.folds` where
+        present; None: fold 0, and nothing handed on): the folds the tissue stage trains, validates and, with more than one, merges
+        (`Segmentor.train_tissue_model_nnUNetv2`'s keyword).  At level "cell" it is
         `Segmentor.train_cell_model(args.num_epochs - 10, ldiffusion_weight, args.diffusion_path, cell_weights=..., instances=...)` (:312-313) and returns
         the folder that holds cellclassifier.pth (None when no epoch validated above 0.0).  `cell_weights` = the CellSegClassifier state dict (or its path)
         the stage starts from: the reference starts from torchvision's ImageNet weights, which it downloads, and this build downloads nothing -- without
@@ -289,18 +293,24 @@ class LDiffusionModel:
                 segmentor_kwargs["postprocessing"] = True
             if validation_checkpoint is not None and (validate or postprocessing):
                 segmentor_kwargs["validation_checkpoint"] = validation_checkpoint
+            if folds is None:
+                folds = getattr(args, "folds", None)
+            if folds is not None:   # None: the call is the one of before the keyword existed
+                segmentor_kwargs["folds"] = tuple(folds)
             return segmentor.train_tissue_model_nnUNetv2(args.num_epochs - 10, ldiffusion_weight, args.diffusion_path, **segmentor_kwargs)
         return ldiffusion_weight
 
     def inference(self, image_path, ldiffusion_weight, segmentor_weight, num_classes, head=None, predictor=None, output_path=None,
-                  text_embeddings=None, instances=None, batch_tiles=None, batch_images=None, postprocess=False, **_readme_kwargs):
+                  text_embeddings=None, instances=None, batch_tiles=None, batch_images=None, postprocess=False, use_folds=None,
+                  **_readme_kwargs):
         """ldiffusion.py:317-324.  Tissue: `segmentor_weight` = nnU-Net's trained-model folder, as in the reference (the head then runs on the HIP
         library, nnunet.py), or `predictor` = any head callable; cell: `segmentor_weight` = the folder with cellclassifier.pth (the ResNet152
         instance classifier then runs on the HIP library, cellhead.py; `instances` = the label-map callable, Cellpose where installed), or
         `head` = any head callable; `output_path` is the folder-mode argument of the tissue path; `batch_tiles` (tissue) = tiles per head call of the batched
         sliding window, None = one call per tile and mirror variant (Segmentor.inference_tissue_model_nnUNetv2); `batch_images` (tissue, folder mode) = images per
         sampler call, None = one file at a time; `postprocess` (tissue) = nnU-Net's fitted largest-component postprocessing on every mask, True reading
-        `<segmentor_weight>/fold_0/validation/postprocessing.json` (Segmentor.inference_tissue_model_nnUNetv2's keyword; False: not handed on); other README-era keyword arguments (dtm_path)
+        `<segmentor_weight>/fold_0/validation/postprocessing.json` (Segmentor.inference_tissue_model_nnUNetv2's keyword; False: not handed on); `use_folds` (tissue) = the folds of `segmentor_weight` whose logits are averaged,
+        the reference's `use_folds=` (None: fold 0, and not handed on); other README-era keyword arguments (dtm_path)
         are accepted and ignored like the code ignores them."""
         segmentor = Segmentor(train_loader=None, val_loader=None, level=self.level, num_classes=num_classes)
         if self.level == "tissue":
@@ -308,7 +318,8 @@ class LDiffusionModel:
                                                              output_path=output_path, predictor=predictor if predictor is not None else head,
                                                              text_embeddings=text_embeddings, batch_tiles=batch_tiles,
                                                              **({} if batch_images is None else {"batch_images": batch_images}),
-                                                             **({} if postprocess is False or postprocess is None else {"postprocess": postprocess}))
+                                                             **({} if postprocess is False or postprocess is None else {"postprocess": postprocess}),
+                                                             **({} if use_folds is None else {"use_folds": tuple(use_folds)}))
         elif self.level == "cell":
             return segmentor.inference_cell_model(image_path, self.diffusion_path, ldiffusion_weight, segmentor_weight, head=head,
                                                   text_embeddings=text_embeddings, instances=instances)

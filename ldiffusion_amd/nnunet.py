@@ -370,35 +370,70 @@ class TrainedModel:
         variants per network call, the mask written at the crop box's place by the finish kernel.  The same mask bit for bit (the head is batch invariant).
         postprocess: None = the mask as predicted; `(fns, kwargs)` or the path of a `postprocessing.json` (`nnunet_post.determine_postprocessing*`) = nnU-Net's
         fitted postprocessing applied to the finished, un-cropped mask on the device (`nnunet_post.apply_postprocessing`)."""
-        if postprocess is not None:
-            from . import nnunet_post
-            fns, kwargs = nnunet_post.load_postprocessing(postprocess) if isinstance(postprocess, (str, os.PathLike)) else postprocess
-            mask = self.predict_mask(data, tile_size, tile_step_size, mirror_axes, network, batch_tiles)
-            return nnunet_post.apply_postprocessing(mask.contiguous(), fns, kwargs)
-        from . import tiling
-        from .segmentor import argmax_mask
-        x, box = preprocess(data, self.normalization_schemes)
-        tile = tuple(int(t) for t in tile_size) if tile_size is not None else self.patch_size
-        div = 1
-        for st in self.spec["strides"]:
-            div *= st
-        if len(tile) != 2 or any(t < div or t % div for t in tile):
-            raise ValueError(f"tile_size {tile} must be a multiple of the product of the network's strides, {div}, in both axes")
-        axes = self.mirror_axes if mirror_axes == "checkpoint" else mirror_axes
-        if "regions" in self.spec:   # one sigmoid head per region: the region rule in place of the arg-max; outside the crop box 0 (revert_cropping_on_probabilities)
-            net = network if network is not None else self.network
-            if batch_tiles is not None:
-                logits = tiling.predict_sliding_window_batched(x, net, self.num_heads, tile, tile_step_size, True, axes, batch_tiles=int(batch_tiles))
-            else:
-                logits = tiling.predict_sliding_window_return_logits(x, net, self.num_heads, tile, tile_step_size, True, axes)
-            out = torch.zeros(tuple(data.shape[1:]), dtype=torch.uint8, device=x.device)
-            return region_mask_u8(logits, self.spec["regions_class_order"], REGION_THRESHOLD_F32, out=out, origin=(box[0], box[2]))
-        if batch_tiles is not None:
-            out = torch.zeros(tuple(data.shape[1:]), dtype=torch.uint8, device=x.device)   # pixels outside the crop box are label 0 (uncrop_mask)
-            return tiling.predict_sliding_window_batched(x, network if network is not None else self.network, self.num_heads, tile, tile_step_size, True, axes,
-                                                         batch_tiles=int(batch_tiles), return_mask=True, mask_out=out, mask_origin=(box[0], box[2]))
-        logits = tiling.predict_sliding_window_return_logits(x, network if network is not None else self.network, self.num_heads, tile, tile_step_size, True, axes)
-        return uncrop_mask(argmax_mask(logits[None].float())[0], box, data.shape[1:])
+        return _predict_mask(self, [network if network is not None else self.network], False, data, tile_size, tile_step_size, mirror_axes, batch_tiles, postprocess)
+
+
+def _predict_mask(head, networks, ensemble: bool, data: torch.Tensor, tile_size, tile_step_size, mirror_axes, batch_tiles, postprocess) -> torch.Tensor:
+    """`TrainedModel.predict_mask` and `FoldEnsemble.predict_mask`: preprocessing, tile check, crop box, the sliding window of `networks` (one head: `tiling`'s
+    single-head entries as ever; `ensemble`: `tiling.predict_sliding_window_ensemble`), region rule or arg-max, un-crop, postprocessing.  `head` gives spec, patch
+    size, mirror axes, normalisation and head count."""
+    if postprocess is not None:
+        from . import nnunet_post
+        fns, kwargs = nnunet_post.load_postprocessing(postprocess) if isinstance(postprocess, (str, os.PathLike)) else postprocess
+        mask = _predict_mask(head, networks, ensemble, data, tile_size, tile_step_size, mirror_axes, batch_tiles, None)
+        return nnunet_post.apply_postprocessing(mask.contiguous(), fns, kwargs)
+    from . import tiling
+    from .segmentor import argmax_mask
+    x, box = preprocess(data, head.normalization_schemes)
+    tile = tuple(int(t) for t in tile_size) if tile_size is not None else head.patch_size
+    div = 1
+    for st in head.spec["strides"]:
+        div *= st
+    if len(tile) != 2 or any(t < div or t % div for t in tile):
+        raise ValueError(f"tile_size {tile} must be a multiple of the product of the network's strides, {div}, in both axes")
+    axes = head.mirror_axes if mirror_axes == "checkpoint" else mirror_axes
+    bt = None if batch_tiles is None else int(batch_tiles)
+    if "regions" in head.spec:   # one sigmoid head per region: the region rule in place of the arg-max; outside the crop box 0 (revert_cropping_on_probabilities)
+        if ensemble:
+            logits = tiling.predict_sliding_window_ensemble(x, networks, head.num_heads, tile, tile_step_size, True, axes, batch_tiles=bt)
+        elif bt is not None:
+            logits = tiling.predict_sliding_window_batched(x, networks[0], head.num_heads, tile, tile_step_size, True, axes, batch_tiles=bt)
+        else:
+            logits = tiling.predict_sliding_window_return_logits(x, networks[0], head.num_heads, tile, tile_step_size, True, axes)
+        out = torch.zeros(tuple(data.shape[1:]), dtype=torch.uint8, device=x.device)
+        return region_mask_u8(logits, head.spec["regions_class_order"], REGION_THRESHOLD_F32, out=out, origin=(box[0], box[2]))
+    if ensemble or bt is not None:
+        out = torch.zeros(tuple(data.shape[1:]), dtype=torch.uint8, device=x.device)   # pixels outside the crop box are label 0 (uncrop_mask)
+        if ensemble:
+            return tiling.predict_sliding_window_ensemble(x, networks, head.num_heads, tile, tile_step_size, True, axes, batch_tiles=bt, return_mask=True, mask_out=out,
+                                                          mask_origin=(box[0], box[2]))
+        return tiling.predict_sliding_window_batched(x, networks[0], head.num_heads, tile, tile_step_size, True, axes, batch_tiles=bt, return_mask=True, mask_out=out,
+                                                     mask_origin=(box[0], box[2]))
+    logits = tiling.predict_sliding_window_return_logits(x, networks[0], head.num_heads, tile, tile_step_size, True, axes)
+    return uncrop_mask(argmax_mask(logits[None].float())[0], box, data.shape[1:])
+
+
+class FoldEnsemble:
+    """The folds of one trained-model folder behind one `predict_mask`: what nnUNetPredictor holds after `initialize_from_trained_model_folder(..., use_folds=(0, 1, ...))`
+    -- `.models` (one `TrainedModel` per fold, in the given order), and `.spec`, `.patch_size`, `.mirror_axes`, `.normalization_schemes`, `.num_heads` of the FIRST
+    fold (predict_from_raw_data.py:95-105 keeps the first checkpoint's trainer name, configuration and mirroring axes)."""
+
+    def __init__(self, models, folds=None):
+        self.models = list(models)
+        if not self.models:
+            raise ValueError("FoldEnsemble: no folds")
+        self.folds = tuple(folds) if folds is not None else tuple(range(len(self.models)))
+        first = self.models[0]
+        self.spec, self.patch_size, self.mirror_axes = first.spec, first.patch_size, first.mirror_axes
+        self.normalization_schemes, self.num_heads = first.normalization_schemes, first.num_heads
+
+    @torch.no_grad()
+    def predict_mask(self, data: torch.Tensor, tile_size=None, tile_step_size: float = 0.5, mirror_axes="checkpoint", network=None,
+                     batch_tiles=None, postprocess=None) -> torch.Tensor:
+        """`TrainedModel.predict_mask` with the folds' logits averaged before the arg-max (or the region rule), on the device, with the reference's roundings
+        (`tiling.predict_sliding_window_ensemble`).  `network`: a sequence of callables that replaces the folds' heads, one per fold."""
+        networks = [m.network for m in self.models] if network is None else list(network)
+        return _predict_mask(self, networks, True, data, tile_size, tile_step_size, mirror_axes, batch_tiles, postprocess)
 
 
 def read_trained_model_folder(model_dir: str, fold=0, checkpoint_name: str = "checkpoint_best.pth"):
@@ -407,16 +442,34 @@ def read_trained_model_folder(model_dir: str, fold=0, checkpoint_name: str = "ch
         if len(fold) != 1:
             _refuse("use_folds", f"names {len(fold)} folds")
         fold = fold[0]
+    plans, dataset_json = _read_model_jsons(model_dir)
+    ckpt = _load_fold_checkpoint(model_dir, fold, checkpoint_name)
+    spec = _checkpoint_spec(ckpt, plans, dataset_json)
+    return spec, _checked_state_dict(ckpt, spec), ckpt.get("inference_allowed_mirroring_axes")
+
+
+# one reading of a trained-model folder's files, for `read_trained_model_folder` and `read_fold_ensemble`
+def _read_model_jsons(model_dir: str):
     with open(os.path.join(model_dir, "dataset.json")) as f:
         dataset_json = json.load(f)
     with open(os.path.join(model_dir, "plans.json")) as f:
         plans = json.load(f)
-    ckpt = torch.load(os.path.join(model_dir, f"fold_{fold}", checkpoint_name), map_location="cpu", weights_only=False)
+    return plans, dataset_json
+
+
+def _load_fold_checkpoint(model_dir: str, fold, checkpoint_name: str) -> dict:
+    return torch.load(os.path.join(model_dir, f"fold_{fold}", checkpoint_name), map_location="cpu", weights_only=False)
+
+
+def _checkpoint_spec(ckpt: dict, plans: dict, dataset_json: dict) -> dict:
     # the network has no head for an ignore label: inference is the same.  A trained folder with region labels was made on purpose: no opt-in to load it
-    spec = network_spec(plans, ckpt["init_args"]["configuration"], dataset_json, accept_ignore=True, accept_regions=True)
+    return network_spec(plans, ckpt["init_args"]["configuration"], dataset_json, accept_ignore=True, accept_regions=True)
+
+
+def _checked_state_dict(ckpt: dict, spec: dict) -> dict:
     sd = clean_state_dict(ckpt["network_weights"], spec)
     check_state_dict(sd, spec)
-    return spec, sd, ckpt.get("inference_allowed_mirroring_axes")
+    return sd
 
 
 def write_trained_model_folder(path: str, plans: dict, dataset_json: dict) -> str:
@@ -434,3 +487,71 @@ def load_trained_model_folder(model_dir: str, fold=0, checkpoint_name: str = "ch
     from .models import PlainConvUNet
     spec, sd, axes = read_trained_model_folder(model_dir, fold, checkpoint_name)
     return TrainedModel(PlainConvUNet(spec, sd, device=device), spec, axes)
+
+
+def available_folds(model_dir: str, checkpoint_name: str = "checkpoint_best.pth") -> List[int]:
+    """nnUNetPredictor.auto_detect_available_folds (predict_from_raw_data.py:123-131): the `fold_<int>` folders of `model_dir` that hold `checkpoint_name`, sorted;
+    `fold_all` is never among them."""
+    folds = []
+    for name in os.listdir(model_dir):
+        m = re.fullmatch(r"fold_(\d+)", name)
+        if m and os.path.isfile(os.path.join(model_dir, name, checkpoint_name)):
+            folds.append(int(m.group(1)))
+    return sorted(folds)
+
+
+def check_folds(folds, what: str = "use_folds") -> Tuple[int, ...]:
+    """A sequence of distinct fold numbers as a tuple of ints; `all` and anything that is no integer are refused by name."""
+    if isinstance(folds, (str, bytes)) or not isinstance(folds, (list, tuple)):
+        raise ValueError(f"`{what}` must be a sequence of fold numbers, not {folds!r}" + (" (fold \"all\" is not covered)" if folds == "all" else ""))
+    out = []
+    for f in folds:
+        if f == "all":
+            raise ValueError(f"`{what}` names the fold \"all\" (training on every case), which is not covered")
+        if isinstance(f, bool) or not isinstance(f, (int, np.integer)) or f < 0:
+            raise ValueError(f"`{what}` holds {f!r}, which is no fold number")
+        out.append(int(f))
+    if not out:
+        raise ValueError(f"`{what}` names no fold")
+    if len(set(out)) != len(out):
+        raise ValueError(f"`{what}` names a fold twice: {tuple(out)}")
+    return tuple(out)
+
+
+def read_fold_ensemble(model_dir: str, folds=None, checkpoint_name: str = "checkpoint_best.pth"):
+    """`load_fold_ensemble` without the networks: (folds, spec, [cleaned state dict per fold], mirror axes).  Nothing here touches the device."""
+    if folds is None:
+        folds = available_folds(model_dir, checkpoint_name)
+        if not folds:
+            raise ValueError(f"no fold_<n>/{checkpoint_name} in {model_dir}")
+    folds = check_folds(folds)
+    from .tiling import ENSEMBLE_MAX_FOLDS
+    if len(folds) > ENSEMBLE_MAX_FOLDS:
+        raise ValueError(f"`use_folds` names {len(folds)} folds; one ensemble averages at most {ENSEMBLE_MAX_FOLDS}")
+    plans, dataset_json = _read_model_jsons(model_dir)
+    spec = axes = configuration = None
+    sds = []
+    for i, fold in enumerate(folds):
+        path = os.path.join(model_dir, f"fold_{fold}", checkpoint_name)
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"fold {fold}: {path} does not exist")
+        ckpt = _load_fold_checkpoint(model_dir, fold, checkpoint_name)
+        name = ckpt["init_args"]["configuration"]
+        if i == 0:   # the first fold decides configuration and mirroring (predict_from_raw_data.py:95-105)
+            configuration, axes = name, ckpt.get("inference_allowed_mirroring_axes")
+            spec = _checkpoint_spec(ckpt, plans, dataset_json)
+        elif name != configuration:
+            raise ValueError(f"fold {fold}: the checkpoint names the configuration {name!r}, fold {folds[0]} names {configuration!r}; one ensemble has one configuration")
+        try:
+            sds.append(_checked_state_dict(ckpt, spec))
+        except (ValueError, RuntimeError) as e:
+            raise type(e)(f"fold {fold}: {e}") from e
+    return folds, spec, sds, axes
+
+
+def load_fold_ensemble(model_dir: str, folds=None, checkpoint_name: str = "checkpoint_best.pth", device=None) -> FoldEnsemble:
+    """initialize_from_trained_model_folder for several folds (predict_from_raw_data.py:78-121): `folds` None = every fold `available_folds` finds; one fold is
+    allowed.  Every checkpoint is read and checked before the first network is built."""
+    from .models import PlainConvUNet
+    folds, spec, sds, axes = read_fold_ensemble(model_dir, folds, checkpoint_name)
+    return FoldEnsemble([TrainedModel(PlainConvUNet(spec, sd, device=device), spec, axes) for sd in sds], folds)

@@ -16,6 +16,7 @@ nothing could load it; `load_postprocessing` reads the JSON instead.
 
     python -m ldiffusion_amd.nnunet_post determine -i PRED_DIR -ref LABEL_DIR -m MODEL_DIR
     python -m ldiffusion_amd.nnunet_post apply -i IN_DIR -o OUT_DIR -pp_json PRED_DIR/postprocessing.json
+    python -m ldiffusion_amd.nnunet_post accumulate -m MODEL_DIR -f 0 1 2 3 4 -ref LABEL_DIR
 """
 from __future__ import annotations
 
@@ -407,11 +408,11 @@ def apply_postprocessing_to_folder(in_dir: str, out_dir: str, postprocessing_jso
 # ---- the final validation of a fold -------------------------------------------------------------------------------------------------------------------
 @torch.no_grad()
 def validate_fold(model_dir: str, cases: dict, val_keys: Sequence[str], *, checkpoint_name: str = "checkpoint_final.pth", batch_tiles=None, io_workers: int = 4,
-                  device=None) -> dict:
-    """nnUNetTrainer.perform_actual_validation (nnUNetTrainer.py:1119-1246) for fold 0 of a trained-model folder: every key of `val_keys` is predicted
+                  device=None, fold: int = 0) -> dict:
+    """nnUNetTrainer.perform_actual_validation (nnUNetTrainer.py:1119-1246) for one fold (`fold`, default 0) of a trained-model folder: every key of `val_keys` is predicted
     in full from its raw device image -- `cases[key]` = (uint8 [C, H, W], uint8 label map [H, W]), as the tissue stage holds them -- with
     `TrainedModel.predict_mask`: step 0.5, Gaussian weighting, the checkpoint's mirror axes, the predictor that function builds.  Writes
-    `fold_0/validation/<key>.png` and `fold_0/validation/summary.json` (foreground regions for a region model, else foreground labels; the ignore label
+    `fold_<fold>/validation/<key>.png` and `fold_<fold>/validation/summary.json` (foreground regions for a region model, else foreground labels; the ignore label
     left out of every count) and returns the summary.  Under a process group of several ranks rank 0 validates and the others wait at a barrier (they
     return None)."""
     import torch.distributed as dist
@@ -423,8 +424,8 @@ def validate_fold(model_dir: str, cases: dict, val_keys: Sequence[str], *, check
             labels_or_regions, _, ignore = label_lists(json.load(f))
         if device is None:
             device = cases[val_keys[0]][0].device
-        head = nnunet.load_trained_model_folder(model_dir, 0, checkpoint_name, device=device)
-        out_dir = os.path.join(model_dir, "fold_0", "validation")
+        head = nnunet.load_trained_model_folder(model_dir, fold, checkpoint_name, device=device)
+        out_dir = os.path.join(model_dir, f"fold_{fold}", "validation")
         masks = {}
         for key in val_keys:
             img = cases[key][0]
@@ -440,8 +441,47 @@ def validate_fold(model_dir: str, cases: dict, val_keys: Sequence[str], *, check
     return summary
 
 
+# ---- the folds of a cross-validation, scored together --------------------------------------------------------------------------------------------------
+def crossval_folder(model_dir: str, folds) -> str:
+    """`<model_dir>/crossval_results_folds_<f0>_<f1>...`: where find_best_configuration keeps the merged validation of `folds` (find_best_configuration.py,
+    `folds_tuple_to_string`: the fold numbers in the given order, joined by `_`)."""
+    return os.path.join(model_dir, "crossval_results_folds_" + "_".join(str(f) for f in folds))
+
+
+def accumulate_cv_results(model_dir: str, folds, gt_dir: str, device="cuda:0", io_workers: int = 4) -> dict:
+    """evaluation/accumulate_cv_results.py with overwrite=True: `crossval_folder(model_dir, folds)` is made anew and receives dataset.json, plans.json and every
+    `fold_<f>/validation/*.png`; the merged folder is then scored again against the files of the same names in `gt_dir` (`case_metrics`, `summarize`: no fold's own
+    summary.json is read) into its `summary.json`.  RuntimeError, in the reference's words, for a fold without `validation/` and for a case that more than one
+    fold predicted.  `io_workers` stands where the reference has num_processes; the copies are made in line.  Returns the summary."""
+    import shutil
+    merged = crossval_folder(model_dir, folds)
+    if os.path.isdir(merged):
+        shutil.rmtree(merged)
+    os.makedirs(merged)
+    with open(os.path.join(model_dir, "dataset.json")) as f:
+        labels_or_regions, _, ignore = label_lists(json.load(f))
+    for name in ("dataset.json", "plans.json"):
+        shutil.copy(os.path.join(model_dir, name), os.path.join(merged, name))
+    for f in folds:
+        val_dir = os.path.join(model_dir, f"fold_{f}", "validation")
+        if not os.path.isdir(val_dir):
+            raise RuntimeError(f"fold {f} of model {model_dir} is missing. Please train it!")
+        for pf in sorted(n for n in os.listdir(val_dir) if n.endswith(FILE_ENDING) and os.path.isfile(os.path.join(val_dir, n))):
+            if os.path.isfile(os.path.join(merged, pf)):
+                raise RuntimeError(f"More than one of your folds has a prediction for case {pf}")
+            shutil.copy(os.path.join(val_dir, pf), os.path.join(merged, pf))
+    files = sorted(n for n in os.listdir(merged) if n.endswith(FILE_ENDING))
+    if not files:
+        raise ValueError(f"accumulate_cv_results: the folds {tuple(folds)} of {model_dir} hold no {FILE_ENDING} predictions")
+    per_case = [{"metrics": case_metrics(_read_mask(os.path.join(gt_dir, n), device), _read_mask(os.path.join(merged, n), device), labels_or_regions, ignore),
+                 "reference_file": os.path.join(gt_dir, n), "prediction_file": os.path.join(merged, n)} for n in files]
+    summary = summarize(per_case)
+    save_summary_json(summary, os.path.join(merged, "summary.json"))
+    return summary
+
+
 def main(argv=None):
-    """The reference's two entry points (remove_connected_components.py:298-333), with the JSON record in the pickle's place."""
+    """The reference's two entry points (remove_connected_components.py:298-333), with the JSON record in the pickle's place, and accumulate_cv_results."""
     import argparse
     parser = argparse.ArgumentParser(prog="python -m ldiffusion_amd.nnunet_post")
     sub = parser.add_subparsers(dest="command", required=True)
@@ -453,10 +493,16 @@ def main(argv=None):
     a.add_argument("-i", required=True, help="input folder")
     a.add_argument("-o", required=True, help="output folder")
     a.add_argument("-pp_json", required=True, help="postprocessing.json")
-    for p in (d, a):
+    c = sub.add_parser("accumulate", help="merges the folds' validation folders into crossval_results_folds_... and scores them again")
+    c.add_argument("-m", required=True, help="trained-model folder")
+    c.add_argument("-f", type=int, nargs="+", default=[0, 1, 2, 3, 4], help="folds")
+    c.add_argument("-ref", required=True, help="folder with ground-truth label maps")
+    for p in (d, a, c):
         p.add_argument("-np", type=int, default=4, help="writer threads")
         p.add_argument("--device", default="cuda:0")
     args = parser.parse_args(argv)
+    if args.command == "accumulate":
+        return accumulate_cv_results(args.m, tuple(args.f), args.ref, device=args.device, io_workers=args.np)
     if args.command == "determine":
         return determine_postprocessing_folder(args.i, args.ref, args.m, device=args.device, io_workers=args.np)
     return apply_postprocessing_to_folder(args.i, args.o, args.pp_json, device=args.device, io_workers=args.np)

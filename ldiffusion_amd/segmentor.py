@@ -222,7 +222,7 @@ class Segmentor:
     def train_tissue_model_nnUNetv2(self, epochs, ldiffusion_weight, diffusion_path, train_images=None, train_labels=None, test_images=None, test_labels=None,
                                     num_classes=None, *, iterations_per_epoch=250, val_iterations=50, num_foreground_voxels=None, wgrad_route=None, batch_images=None, io_workers=4,
                                     ignore_pixel=None, regions=None, regions_class_order=None, region_loss="focal", validate=False, postprocessing=False,
-                                    validation_checkpoint="checkpoint_final.pth"):
+                                    validation_checkpoint="checkpoint_final.pth", folds=None):
         """segmentor.py:163-241: the tissue head's training stage, from image lists to a trained-model folder.
         Dataset (:167-205): `load_ldiffusion`, the cached text embeddings of "A pathological slide", the text-alignment wrapper, and
         `utils.create_nnunet_dataset` under nnUNet_raw (the one-pass diffusion of every image when all share one size, else copies).
@@ -250,6 +250,15 @@ class Segmentor:
         `summary.json`; the summary is kept as `self.validation_summary`.  `postprocessing` (implies `validate`): nnU-Net's largest-component
         postprocessing fitted on those predictions against labelsTr (`nnunet_post.determine_postprocessing_folder`): `fold_0/validation/postprocessing.json`
         and `fold_0/validation/postprocessed/`, what `inference_tissue_model_nnUNetv2(postprocess=True)` reads.  Rank 0 does both; the others wait.
+        `folds` (None: fold 0, the stage as it was): a sequence of distinct fold numbers of the five-fold split, trained one after the other in the given
+        order (`nnUNetv2_train ... FOLD` once per fold) from one dataset, fingerprint, plans and split and one read of the cases.  Fold f takes its stores from
+        `splits[f]`, `initial_state_dict(spec, seed=f)`, the loader seeds 2 rank + 2 world f and + 1 (fold 0: the seeds of before), `init_args["fold"] = f` and
+        writes `fold_<f>/`; under a process group every rank walks the same folds.  With `validate`, each fold is validated after its training
+        (`fold_<f>/validation/`); with more than one fold the folds' predictions are then merged and scored again (`nnunet_post.accumulate_cv_results`:
+        `crossval_results_folds_<f0>_<f1>.../`, `self.crossval_summary`), and `postprocessing` is fitted ONCE, on the merged folder, as
+        find_best_configuration does -- what `inference_tissue_model_nnUNetv2(use_folds=..., postprocess=True)` reads.  `self.training_log` and
+        `self.validation_summary` are the last fold's; `self.training_logs[f]` and `self.validation_summaries[f]` hold every fold's.  The fold "all" and
+        fold numbers beyond the split (nnU-Net's random 80:20 split) are refused.
         Returns the model folder -- what `inference_tissue_model_nnUNetv2(segmentor_weight=...)` takes -- on every rank."""
         import json
         from PIL import Image
@@ -259,6 +268,10 @@ class Segmentor:
             if not os.environ.get(name):
                 raise RuntimeError(f"train_tissue_model_nnUNetv2: the environment variable {name} is not set")
             roots[name] = os.environ[name]
+        fold_list = (0,) if folds is None else nnunet.check_folds(folds, "folds")
+        if any(f >= 5 for f in fold_list):   # nnunet_plan.crossval_splits' five folds
+            raise ValueError(f"`folds` names fold {max(fold_list)}: the split has the folds 0 .. 4, and nnU-Net's random 80:20 split for "
+                             "fold numbers beyond it is not covered")
         import torch.distributed as dist
         world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
         rank = dist.get_rank() if world > 1 else 0
@@ -330,38 +343,53 @@ class Segmentor:
             store_labels = dict(regions=nnunet.region_spec(dataset_json["labels"], dataset_json["regions_class_order"]))
         else:
             store_labels = dict(labels=dataset_json["labels"])
-        stores = [nnunet_data.CaseStore([cases[k] for k in splits[0][part]], spec["normalization_schemes"], spec["n_heads"], device=self.device,
-                                        prefilter="device", build="device", **store_labels) for part in ("train", "val")]
         n_scales = spec["n_stages"] - 1
         if world > 1:
             batch, oversample = nnunet_train.rank_batch_sizes(cfg["batch_size"], world, nnunet_data.OVERSAMPLE_FOREGROUND)[rank]
             extra = {"oversample": oversample}
         else:
             batch, extra = cfg["batch_size"], {}
-        loaders = [nnunet_data.PatchLoader(store, spec["patch_size"], batch, n_scales, seed=seed, train=train, **extra)
-                   for store, seed, train in ((stores[0], 2 * rank, True), (stores[1], 2 * rank + 1, False))]
-        self.tissue_loaders = loaders
-        ignore = {}
-        if spec.get("ignore_label") is not None:   # nnUNetTrainer keeps the dataset.json it was built with, ignore entry included, in the checkpoint's init_args
-            ignore = dict(ignore_label=spec["ignore_label"], init_args={"configuration": "2d", "fold": 0, "dataset_json": dataset_json})
-        if "regions" in spec:
-            ignore.update(region_loss=region_loss, init_args={"configuration": "2d", "fold": 0, "dataset_json": dataset_json})
-        trainer = nnunet_train.Trainer(spec, nnunet_train.initial_state_dict(spec), cfg["batch_dice"], num_epochs=epochs, device=self.device, wgrad_route=wgrad_route,
-                                       **ignore)
         model_dir = os.path.join(roots["nnUNet_results"], dataset_name, "nnUNetTrainer__nnUNetPlans__2d")
         if rank == 0:
             nnunet.write_trained_model_folder(model_dir, plans, dataset_json)
-        self.training_log = trainer.run_training(loaders[0], loaders[1], os.path.join(model_dir, "fold_0"), iterations_per_epoch=iterations_per_epoch,
-                                                 val_iterations=val_iterations)
+        self.training_logs, self.validation_summaries, self.crossval_summary = {}, {}, None
+        for f in fold_list:   # one nnUNetv2_train per fold: a fresh network, stores and loaders; `folds=None` makes exactly the calls of before the keyword
+            of_fold = {} if folds is None else {"fold": f}
+            stores = [nnunet_data.CaseStore([cases[k] for k in splits[f][part]], spec["normalization_schemes"], spec["n_heads"], device=self.device,
+                                            prefilter="device", build="device", **store_labels) for part in ("train", "val")]
+            first_seed = 2 * rank + 2 * world * f
+            loaders = [nnunet_data.PatchLoader(store, spec["patch_size"], batch, n_scales, seed=seed, train=train, **extra)
+                       for store, seed, train in ((stores[0], first_seed, True), (stores[1], first_seed + 1, False))]
+            self.tissue_loaders = loaders
+            ignore = {}
+            if spec.get("ignore_label") is not None:   # nnUNetTrainer keeps the dataset.json it was built with, ignore entry included, in the checkpoint's init_args
+                ignore = dict(ignore_label=spec["ignore_label"], init_args={"configuration": "2d", "fold": f, "dataset_json": dataset_json})
+            if "regions" in spec:
+                ignore.update(region_loss=region_loss, init_args={"configuration": "2d", "fold": f, "dataset_json": dataset_json})
+            if folds is not None:
+                ignore.setdefault("init_args", {"configuration": "2d", "fold": f})
+            state = nnunet_train.initial_state_dict(spec) if folds is None else nnunet_train.initial_state_dict(spec, seed=f)
+            trainer = nnunet_train.Trainer(spec, state, cfg["batch_dice"], num_epochs=epochs, device=self.device, wgrad_route=wgrad_route, **ignore)
+            self.training_log = trainer.run_training(loaders[0], loaders[1], os.path.join(model_dir, f"fold_{f}"), iterations_per_epoch=iterations_per_epoch,
+                                                     val_iterations=val_iterations)
+            self.training_logs[f] = self.training_log
+            if validate or postprocessing:
+                from . import nnunet_post
+                self.validation_summary = nnunet_post.validate_fold(model_dir, cases, splits[f]["val"], checkpoint_name=validation_checkpoint, io_workers=io_workers,
+                                                                    **of_fold)
+                self.validation_summaries[f] = self.validation_summary
+            del trainer, stores
         if validate or postprocessing:
-            from . import nnunet_post
-            self.validation_summary = nnunet_post.validate_fold(model_dir, cases, splits[0]["val"], checkpoint_name=validation_checkpoint, io_workers=io_workers)
-            if postprocessing:
+            fit_dir = os.path.join(model_dir, f"fold_{fold_list[0]}", "validation")
+            if len(fold_list) > 1:   # find_best_configuration's order: merge the folds, score the merged folder, fit the postprocessing there
+                fit_dir = nnunet_post.crossval_folder(model_dir, fold_list)
                 if rank == 0:
-                    nnunet_post.determine_postprocessing_folder(os.path.join(model_dir, "fold_0", "validation"), os.path.join(raw_dir, "labelsTr"), model_dir,
-                                                                device=self.device, io_workers=io_workers)
-                if world > 1:
-                    dist.barrier()
+                    self.crossval_summary = nnunet_post.accumulate_cv_results(model_dir, fold_list, os.path.join(raw_dir, "labelsTr"), device=self.device,
+                                                                              io_workers=io_workers)
+            if postprocessing and rank == 0:
+                nnunet_post.determine_postprocessing_folder(fit_dir, os.path.join(raw_dir, "labelsTr"), model_dir, device=self.device, io_workers=io_workers)
+            if world > 1 and (postprocessing or len(fold_list) > 1):
+                dist.barrier()
         return model_dir
 
     def train_cell_model(self, epochs, ldiffusion_weight, diffusion_path, *, cell_weights, instances=None, fit_classifier=True, cache_features=True, lr=1e-4,
@@ -576,18 +604,32 @@ class Segmentor:
         mask = np.array(Image.fromarray(mask.astype(np.uint8)).resize((width, height), resample=Image.NEAREST))
         return decoded.resize((width, height), Image.BILINEAR), mask
 
-    def _tissue_head(self, model_dir):
-        """The nnU-Net head of a trained-model folder, built once per (folder, checkpoint mtime)."""
+    def _tissue_head(self, model_dir, use_folds=None):
+        """The nnU-Net head of a trained-model folder, built once per (folder, checkpoint mtime); with `use_folds` the `nnunet.FoldEnsemble` of those folds,
+        built once per (folder, folds, every fold's checkpoint mtime)."""
         from . import nnunet
-        ckpt = os.path.join(model_dir, "fold_0", "checkpoint_best.pth")
-        key = (os.path.abspath(model_dir), os.path.getmtime(ckpt) if os.path.exists(ckpt) else None)
+        folds = (0,) if use_folds is None else nnunet.check_folds(use_folds)
+        mtimes = []
+        for f in folds:
+            ckpt = os.path.join(model_dir, f"fold_{f}", "checkpoint_best.pth")
+            mtimes.append(os.path.getmtime(ckpt) if os.path.exists(ckpt) else None)
+        key = (os.path.abspath(model_dir), mtimes[0]) if use_folds is None else (os.path.abspath(model_dir), folds, tuple(mtimes))
         cache = getattr(self, "_tissue_heads", None)
         if cache is None:
             cache = self._tissue_heads = {}
         if key not in cache:
             cache.clear()
-            cache[key] = nnunet.load_trained_model_folder(model_dir, 0, "checkpoint_best.pth", device=self.device)
+            if use_folds is None:
+                cache[key] = nnunet.load_trained_model_folder(model_dir, 0, "checkpoint_best.pth", device=self.device)
+            else:
+                cache[key] = nnunet.load_fold_ensemble(model_dir, folds, "checkpoint_best.pth", device=self.device)
         return cache[key]
+
+    @staticmethod
+    def _check_head_finite(head):
+        """An fp16 overflow inside the head (any fold of an ensemble) raises instead of yielding a plausible-looking mask."""
+        for model in getattr(head, "models", (head,)):
+            model.network.check_finite()
 
     @torch.no_grad()
     def _tissue_folder_batched(self, head, image_path, output_path, diffusion_path, ldiffusion_weight, text_embeddings, tile_size, tile_step_size, mirror_axes, batch_tiles,
@@ -602,7 +644,7 @@ class Segmentor:
 
         def head_mask(name, data):   # data [3, H, W] float on the device, what the PNG the reference writes would hold
             mask = head.predict_mask(data, tile_size, tile_step_size, axes, batch_tiles=batch_tiles, postprocess=postprocess)
-            head.network.check_finite()
+            self._check_head_finite(head)
             Image.fromarray(mask.cpu().numpy()).save(os.path.join(output_path, os.path.splitext(name)[0] + ".png"))
 
         groups = {}   # source size -> names, in name order
@@ -641,7 +683,7 @@ class Segmentor:
     @torch.no_grad()
     def inference_tissue_model_nnUNetv2(self, image_path, diffusion_path, ldiffusion_weight, segmentor_weight, output_path=None,
                                         predictor=None, text_embeddings=None, tile_size=None, tile_step_size=0.5,
-                                        mirror_axes=None, num_heads=None, batch_tiles=None, batch_images=None, postprocess=False):
+                                        mirror_axes=None, num_heads=None, batch_tiles=None, batch_images=None, postprocess=False, use_folds=None):
         """segmentor.py:388-488.  The tissue head is either
         * built from `segmentor_weight`, a trained-model folder as the reference's nnUNetPredictor reads it (dataset.json, plans.json,
           fold_0/checkpoint_best.pth; :463-468), when `predictor` is None: nnU-Net v2's 2-D PlainConvUNet on the HIP library (`nnunet.py`; cached on this
@@ -666,15 +708,27 @@ class Segmentor:
           skip the diffusion as above.  The mask files are those of the per-image path under the same plan batch.
         * postprocess (False: the masks as predicted): True = nnU-Net's fitted postprocessing, read from `<segmentor_weight>/fold_0/validation/postprocessing.json`
           (what `train_tissue_model_nnUNetv2(postprocessing=True)` writes; a missing file raises FileNotFoundError naming the path), or the path of such a
-          file, or `(fns, kwargs)`; applied to every finished mask on the device (`nnunet_post.apply_postprocessing`), single image and folder alike."""
+          file, or `(fns, kwargs)`; applied to every finished mask on the device (`nnunet_post.apply_postprocessing`), single image and folder alike.
+        * use_folds (the library's head; None = fold 0, the head as above): a sequence of fold numbers = `nnunet.load_fold_ensemble` of
+          `fold_<f>/checkpoint_best.pth`, the reference's `use_folds=` (:466): the folds' logits are averaged on the device before the arg-max
+          (`tiling.predict_sliding_window_ensemble`), single image, folder and `batch_images` folder alike.  With more than one fold `postprocess=True`
+          reads `<segmentor_weight>/crossval_results_folds_<f0>_<f1>.../postprocessing.json`, the record fitted on the folds' merged validation."""
         from PIL import Image
         from . import tiling
+        if use_folds is not None:
+            from . import nnunet
+            use_folds = nnunet.check_folds(use_folds)
+            if predictor is not None:
+                raise ValueError("inference_tissue_model_nnUNetv2: `use_folds` names folds of `segmentor_weight`; an injected `predictor` has none")
         post = None   # (fns, kwargs), read once
         if postprocess is not None and postprocess is not False:
             from . import nnunet_post
             if postprocess is True:
-                postprocess = os.path.join(os.fspath(segmentor_weight) if isinstance(segmentor_weight, (str, os.PathLike)) else str(segmentor_weight), "fold_0",
-                                           "validation", "postprocessing.json")
+                weight = os.fspath(segmentor_weight) if isinstance(segmentor_weight, (str, os.PathLike)) else str(segmentor_weight)
+                if use_folds is not None and len(use_folds) > 1:
+                    postprocess = os.path.join(nnunet_post.crossval_folder(weight, use_folds), "postprocessing.json")
+                else:
+                    postprocess = os.path.join(weight, f"fold_{0 if use_folds is None else use_folds[0]}", "validation", "postprocessing.json")
             post = nnunet_post.load_postprocessing(postprocess) if isinstance(postprocess, (str, os.PathLike)) else (list(postprocess[0]), list(postprocess[1]))
         keep = {} if post is None else {"postprocess": post}   # nothing new goes downstream without the keyword
         head = None
@@ -682,7 +736,7 @@ class Segmentor:
             if not (isinstance(segmentor_weight, (str, os.PathLike)) and os.path.isfile(os.path.join(segmentor_weight, "plans.json"))):
                 raise RuntimeError("inference_tissue_model_nnUNetv2: the nnU-Net tissue head needs `segmentor_weight` to be a trained-model folder "
                                    "(dataset.json, plans.json, fold_0/checkpoint_best.pth), or pass `predictor=`")
-            head = self._tissue_head(segmentor_weight)
+            head = self._tissue_head(segmentor_weight) if use_folds is None else self._tissue_head(segmentor_weight, use_folds)
         if head is not None and os.path.isdir(image_path):   # every image of the folder through the same head
             if not output_path:
                 raise ValueError("When image_path is a folder, output_path must be specified!")
@@ -694,7 +748,8 @@ class Segmentor:
             for name in sorted(os.listdir(image_path)):
                 if name.lower().endswith((".png", ".jpg", ".jpeg", ".tif", ".tiff", ".bmp")):
                     _, m = self.inference_tissue_model_nnUNetv2(os.path.join(image_path, name), diffusion_path, ldiffusion_weight, segmentor_weight,
-                                                                None, None, text_embeddings, tile_size, tile_step_size, mirror_axes, num_heads, batch_tiles, **keep)
+                                                                None, None, text_embeddings, tile_size, tile_step_size, mirror_axes, num_heads, batch_tiles, **keep,
+                                                                **({} if use_folds is None else {"use_folds": use_folds}))
                     Image.fromarray(m).save(os.path.join(output_path, os.path.splitext(name)[0] + ".png"))
             return None, None   # batch mode returns no single mask (segmentor.py:421)
         if head is None:
@@ -736,7 +791,7 @@ class Segmentor:
         data = rgb[0].permute(2, 0, 1).float()                                                # what the PNG the reference writes would hold
         if head is not None:
             mask = head.predict_mask(data, tile_size, tile_step_size, "checkpoint" if mirror_axes is None else mirror_axes, batch_tiles=batch_tiles, **keep)
-            head.network.check_finite()   # an fp16 overflow inside the head raises instead of yielding a plausible-looking mask
+            self._check_head_finite(head)
             return decoded, mask.cpu().numpy()
         heads = int(num_heads if num_heads is not None else self.num_classes)
         th, tw = min(tile_size[0], data.shape[1]), min(tile_size[1], data.shape[2])

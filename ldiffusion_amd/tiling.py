@@ -331,6 +331,14 @@ def window_accumulate_image(image: torch.Tensor, network, num_heads: int, tile_h
                             acc_dtype=torch.float16, batch_tiles: int = 1):
     """The chunk loop of `predict_sliding_window_batched`: gather, ONE network call, accumulate, per chunk of the image's plan.  Returns (acc [num_heads, Hp, Wp],
     cnt [Hp, Wp], plan): the accumulators BEFORE the division, over the padded extent."""
+    accs, cnt, plan = _window_accumulate_folds(image, [network], num_heads, tile_hw, tile_step_size, use_gaussian, mirror_axes, acc_dtype, batch_tiles)
+    return accs[0], cnt, plan
+
+
+def _window_accumulate_folds(image: torch.Tensor, networks, num_heads: int, tile_hw, tile_step_size, use_gaussian, mirror_axes, acc_dtype, batch_tiles):
+    """`window_accumulate_image` for a list of networks: one plan, one gather per chunk, then per network in order one call and one accumulate launch into that
+    network's own accumulators.  The count plane does not depend on the prediction: the first network's is returned, the others add into one scratch plane.
+    Returns (accs, cnt, plan)."""
     if not isinstance(image, torch.Tensor) or not image.is_cuda:
         raise ValueError("predict_sliding_window_batched: `image` must be a tensor on the device (a host tensor goes through predict_sliding_window_return_logits)")
     if image.dim() != 3:
@@ -347,22 +355,24 @@ def window_accumulate_image(image: torch.Tensor, network, num_heads: int, tile_h
     plan = window_plan(tuple(image.shape[1:]), tile_hw, tile_step_size, mirror_axes, batch_tiles)
     (th, tw), (Hp, Wp), dev = plan.tile_hw, plan.padded_hw, image.device
     want = (plan.batch, num_heads, th, tw)
-    acc = torch.zeros((num_heads, Hp, Wp), dtype=acc_dtype, device=dev)
+    accs = [torch.zeros((num_heads, Hp, Wp), dtype=acc_dtype, device=dev) for _ in networks]
     cnt = torch.zeros((Hp, Wp), dtype=acc_dtype, device=dev)
+    scratch = torch.zeros((Hp, Wp), dtype=acc_dtype, device=dev) if len(networks) > 1 else None
     g = compute_gaussian((th, tw), sigma_scale=1.0 / 8, value_scaling_factor=10, dtype=acc_dtype, device=dev) if use_gaussian else None
     x = torch.empty((plan.batch, image.shape[0], th, tw), dtype=torch.float32, device=dev)
     for origins, n_valid in plan.chunks:
         window_gather(image, plan, origins, out=x)
-        pred = network(x)
-        if not isinstance(pred, torch.Tensor) or not pred.is_cuda:
-            raise ValueError(f"predict_sliding_window_batched: the network must return a device tensor {want}")
-        if tuple(pred.shape) != want:
-            raise ValueError(f"predict_sliding_window_batched: the network returned {tuple(pred.shape)} for a batch of {plan.batch} "
-                             f"({plan.batch_tiles} tiles x {len(plan.variants)} mirror variants); expected {want}")
-        if pred.dtype not in (torch.float32, torch.float16):
-            raise ValueError(f"predict_sliding_window_batched: the network returned {pred.dtype}; expected float32 or float16")
-        window_accumulate_batch(acc, cnt, pred, g, origins, n_valid, plan.variants)
-    return acc, cnt, plan
+        for k, network in enumerate(networks):
+            pred = network(x)
+            if not isinstance(pred, torch.Tensor) or not pred.is_cuda:
+                raise ValueError(f"predict_sliding_window_batched: the network must return a device tensor {want}")
+            if tuple(pred.shape) != want:
+                raise ValueError(f"predict_sliding_window_batched: the network returned {tuple(pred.shape)} for a batch of {plan.batch} "
+                                 f"({plan.batch_tiles} tiles x {len(plan.variants)} mirror variants); expected {want}")
+            if pred.dtype not in (torch.float32, torch.float16):
+                raise ValueError(f"predict_sliding_window_batched: the network returned {pred.dtype}; expected float32 or float16")
+            window_accumulate_batch(accs[k], cnt if k == 0 else scratch, pred, g, origins, n_valid, plan.variants)
+    return accs, cnt, plan
 
 
 @torch.no_grad()
@@ -389,6 +399,80 @@ def predict_sliding_window_batched(image: torch.Tensor, network, num_heads: int,
     else:
         out = torch.empty((acc.shape[0], H, W), dtype=acc_dtype, device=dev)
         window_finish(acc, cnt, box, flag, logits=out)
+    if int(flag.item()):
+        raise RuntimeError(_INF_MESSAGE)
+    return out
+
+
+# ---- several heads of one image: the folds of a cross-validation, averaged as nnUNetPredictor averages them -------------------------------
+ENSEMBLE_MAX_FOLDS = 8   # LDIFF_ENSEMBLE_MAX_FOLDS: accumulators of one finish launch (their pointers travel by value in the kernel's arguments)
+
+
+def window_finish_ensemble(accs, cnt, box, inf_flag: torch.Tensor, logits: torch.Tensor = None, mask: torch.Tensor = None, mask_origin=(0, 0)) -> None:
+    """One launch of ldiff_op_window_finish_ensemble over box = (y0, x0, h, w): per fold `l_k = acc_k / cnt` as `window_finish` rounds it (cnt None: the entries of
+    `accs` are logits already), inf_flag set when any l_k is +-inf, then `s = l_0; s += l_k` in order and `s /= len(accs)`, every step rounded to the accumulators'
+    dtype (predict_from_raw_data.py:459-494); logits [heads, h, w] receives s, mask its arg-max at mask_origin.  Either output may be None."""
+    import ctypes
+    from . import _lib
+    accs = list(accs)
+    y0, x0, h, w = (int(v) for v in box)
+    if not 1 <= len(accs) <= ENSEMBLE_MAX_FOLDS:
+        raise ValueError(f"window finish ensemble: n_folds {len(accs)} out of range [1, {ENSEMBLE_MAX_FOLDS}]")
+    first = accs[0]
+    for k, acc in enumerate(accs):
+        if not isinstance(acc, torch.Tensor) or acc.dtype not in (torch.float32, torch.float16) or acc.dim() != 3 or not (acc.is_cuda and acc.is_contiguous()):
+            raise ValueError(f"window finish ensemble: accumulator {k} is no contiguous float32 or float16 device tensor [heads, Hp, Wp]")
+        if acc.dtype != first.dtype or tuple(acc.shape) != tuple(first.shape) or acc.device != first.device:
+            raise ValueError(f"window finish ensemble: accumulator {k} ({acc.dtype} {tuple(acc.shape)} on {acc.device}) does not match accumulator 0 "
+                             f"({first.dtype} {tuple(first.shape)} on {first.device})")
+    if cnt is not None and (cnt.dtype != first.dtype or tuple(cnt.shape) != tuple(first.shape[1:]) or not (cnt.is_cuda and cnt.is_contiguous())):
+        raise ValueError(f"window finish ensemble: `cnt` must be a contiguous {first.dtype} device tensor {tuple(first.shape[1:])}")
+    if inf_flag.dtype != torch.int32 or not inf_flag.is_cuda or inf_flag.numel() < 1:
+        raise ValueError("window finish ensemble: `inf_flag` must be a device int32 tensor")
+    if logits is not None and (tuple(logits.shape) != (first.shape[0], h, w) or logits.dtype != first.dtype or not logits.is_contiguous() or not logits.is_cuda):
+        raise ValueError(f"window finish ensemble: `logits` must be a contiguous {first.dtype} device tensor {(first.shape[0], h, w)}")
+    mh = mw = 0
+    if mask is not None:
+        if mask.dim() != 2 or mask.dtype != torch.uint8 or not mask.is_contiguous() or not mask.is_cuda:
+            raise ValueError("window finish ensemble: `mask` must be a contiguous uint8 device tensor [H0, W0]")
+        mh, mw = mask.shape
+    table = (ctypes.c_void_p * len(accs))(*[acc.data_ptr() for acc in accs])
+    _lib.check(_lib.load().ldiff_op_window_finish_ensemble(table, len(accs), _lib.ptr(cnt), first.shape[0], first.shape[1], first.shape[2], y0, x0, h, w,
+                                                           int(first.dtype == torch.float16), _lib.ptr(logits), _lib.ptr(mask), mh, mw, int(mask_origin[0]),
+                                                           int(mask_origin[1]), _lib.ptr(inf_flag), _lib.stream_ptr()))
+
+
+@torch.no_grad()
+def predict_sliding_window_ensemble(image: torch.Tensor, networks, num_heads: int, tile_hw: Tuple[int, int], tile_step_size: float = 0.5, use_gaussian: bool = True,
+                                    mirror_axes=None, acc_dtype=torch.float16, batch_tiles=1, return_mask: bool = False, mask_out: torch.Tensor = None,
+                                    mask_origin=(0, 0)):
+    """nnUNetPredictor.predict_logits_from_preprocessed_data for several parameter sets (predict_from_raw_data.py:459-494): every network's sliding window over the
+    image, the logits summed in the networks' order and divided by their number, each step rounded to `acc_dtype`.
+    batch_tiles an integer: `predict_sliding_window_batched`'s launches with ONE plan and one gather per chunk; every network is called once per chunk on the same
+    batch and accumulated into its own accumulators; ONE ldiff_op_window_finish_ensemble divides every fold by the count plane (the same for every fold: the first
+    one's is used), flags inf per fold, averages and writes the logits or the arg-max; one read of the inf flag.  With one network the result is
+    `predict_sliding_window_batched`'s bit for bit.
+    batch_tiles None: each network's `predict_sliding_window_return_logits` (which raises on inf itself), then the same kernel without a count plane.
+    Returns and `return_mask`, `mask_out`, `mask_origin` as `predict_sliding_window_batched`."""
+    networks = list(networks)
+    if not 1 <= len(networks) <= ENSEMBLE_MAX_FOLDS:
+        raise ValueError(f"predict_sliding_window_ensemble: {len(networks)} networks; one launch averages 1 to {ENSEMBLE_MAX_FOLDS}")
+    if batch_tiles is None:
+        if not isinstance(image, torch.Tensor) or not image.is_cuda:
+            raise ValueError("predict_sliding_window_ensemble: `image` must be a tensor on the device")
+        accs = [predict_sliding_window_return_logits(image, net, num_heads, tile_hw, tile_step_size, use_gaussian, mirror_axes, acc_dtype).contiguous() for net in networks]
+        cnt, (H, W), box, dev = None, tuple(accs[0].shape[1:]), (0, 0) + tuple(accs[0].shape[1:]), accs[0].device
+    else:
+        accs, cnt, plan = _window_accumulate_folds(image, networks, num_heads, tile_hw, tile_step_size, use_gaussian, mirror_axes, acc_dtype, batch_tiles)
+        (H, W), dev = plan.image_hw, accs[0].device
+        box = (plan.pad[0], plan.pad[1], H, W)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    if return_mask:
+        out = mask_out if mask_out is not None else torch.zeros((H, W), dtype=torch.uint8, device=dev)
+        window_finish_ensemble(accs, cnt, box, flag, mask=out, mask_origin=mask_origin)
+    else:
+        out = torch.empty((accs[0].shape[0], H, W), dtype=acc_dtype, device=dev)
+        window_finish_ensemble(accs, cnt, box, flag, logits=out)
     if int(flag.item()):
         raise RuntimeError(_INF_MESSAGE)
     return out
